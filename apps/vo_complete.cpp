@@ -3,12 +3,16 @@
 // association.  Same call sequence, same output files (written into the
 // current directory or into argv[2]): world.txt, trajectory_gt.txt, map.txt,
 // map_appearances.txt, trajectory_est_complete.txt, trajectory_est_data.txt.
-//   usage: vo_complete <data dir> [output dir] [rounds=100] [--resident [--match-up-front]] [--exact]
+//   usage: vo_complete <data dir> [output dir] [rounds=100] [--resident [--match-up-front]] [--exact] [--ransac[=px]]
 // --resident: the same sequence through vo::DeviceSequence -- all measurement files are read and uploaded first, the
 // whole frame chain runs on the GPU without a host round trip per frame, the map upkeep included (vo_map_*: the
 // reference's upsert as a hash table of first occurrences in device memory).  Same outputs.
 // --exact: the solver in reference-order arithmetic (PICPSolver::setExact): every pose of the chain is then
 // bit-identical to the reference's float32 arithmetic given the same first relative pose.
+// --ransac[=px]: the first relative pose from the inliers of a RANSAC over the first pair's matches (2048 hypotheses,
+// Sampson threshold px, default 1, seed 0: vo::estimate_transform_ransac / DeviceSequence::setInitRansac) instead of from
+// all of them.  The frame-by-frame form refits the inliers with the same estimate_transform it uses without the flag;
+// with no mismatched pair every output file is the same as without the flag.
 // Also written: poses_raw.txt, one camera pose per line (row-major 4x4, %.9g = exact float32 round trip), and map_raw.txt,
 // one map entry per line (x y z a0..a9, %.9g).
 #include <cstdio>
@@ -40,7 +44,8 @@ static void write_map_raw(const std::string& file, const PointCloudVector<3>& ma
 }
 
 // the device-resident form of the loop below: same call sequence, the frame chain inside vo::DeviceSequence
-static int run_resident(const std::string& path, const std::string& out, int rounds, bool exact, bool up_front, const std::string& first_file,
+static int run_resident(const std::string& path, const std::string& out, int rounds, bool exact, bool up_front, float ransac_px,
+                        const std::string& first_file,
                         const std::string& second_file, const std::set<std::string>& files) {
   std::vector<PointCloudVector<2>> frames;
   std::vector<std::string> names{first_file, second_file};
@@ -62,6 +67,7 @@ static int run_resident(const std::string& path, const std::string& out, int rou
   DeviceSequence seq(cam, frames, rounds);
   seq.setExact(exact);
   seq.setMatchUpFront(up_front);              // all consecutive pairs in one batched matcher call before the chain
+  if (ransac_px > 0.f) seq.setInitRansac(ransac_params(ransac_px));
   seq.setKeepMap(true);                       // map.update / history inside the chain, on the device (vo_complete.cpp:145-147,175-176)
   seq.run();
   const IsometryVector trajectory = seq.trajectory();          // waits for the chain
@@ -85,12 +91,18 @@ static int run_resident(const std::string& path, const std::string& out, int rou
 int main(int argc, char* argv[]) {
   // flags first, wherever they stand; what is left are the positional arguments
   bool resident = false, exact = false, up_front = false;
+  float ransac_px = 0.f;                      // 0: no RANSAC
   std::vector<std::string> pos;
   for (int i = 1; i < argc; ++i) {
     const std::string a(argv[i]);
     if (a == "--resident") resident = true;
     else if (a == "--exact") exact = true;
     else if (a == "--match-up-front") up_front = true;
+    else if (a == "--ransac") ransac_px = 1.f;
+    else if (a.rfind("--ransac=", 0) == 0) {
+      ransac_px = std::strtof(a.c_str() + 9, nullptr);
+      if (!(ransac_px > 0.f)) { std::cout << "--ransac=px needs a positive threshold" << std::endl; return -1; }
+    }
     else if (a.rfind("--", 0) == 0) { std::cout << "unknown option " << a << std::endl; return -1; }
     else pos.push_back(a);
   }
@@ -110,7 +122,7 @@ int main(int argc, char* argv[]) {
     const auto second_file = *(files.erase(files.begin()));
     files.erase(files.begin());
 
-    if (resident) return run_resident(path, out, rounds, exact, up_front, first_file, second_file, files);
+    if (resident) return run_resident(path, out, rounds, exact, up_front, ransac_px, first_file, second_file, files);
     PointCloudVector<2> reference_pc, current_pc;
     if (!get_meas_content(path + first_file, reference_pc)) { std::cout << "Unable to open file measurement file 0\n"; return -1; }
     if (!get_meas_content(path + second_file, current_pc)) { std::cout << "Unable to open file measurement file 1\n"; return -1; }
@@ -126,7 +138,15 @@ int main(int argc, char* argv[]) {
     if (!get_camera_params(path + "camera.dat", int_params, k, H)) { std::cout << "Unable to get camera parameters\n"; return -1; }
     Camera cam(int_params[3], int_params[2], int_params[0], int_params[1], k);
 
-    const Isometry3f X = estimate_transform(cam.cameraMatrix(), correspondences_imgs, reference_pc.points(), current_pc.points());
+    IntPairVector init_pairs;                  // --ransac: the inliers of the first pair's matches
+    if (ransac_px > 0.f) {
+      std::vector<uint8_t> inlier;
+      estimate_transform_ransac(cam.cameraMatrix(), correspondences_imgs, reference_pc.points(), current_pc.points(),
+                                ransac_params(ransac_px), &inlier);
+      for (size_t i = 0; i < correspondences_imgs.size(); ++i) if (inlier[i]) init_pairs.push_back(correspondences_imgs[i]);
+    }
+    const Isometry3f X = estimate_transform(cam.cameraMatrix(), ransac_px > 0.f ? init_pairs : correspondences_imgs,
+                                            reference_pc.points(), current_pc.points());
 
     PointCloudVector<3> triangulated_pc;
     IntPairVector correspondences_world;

@@ -7,6 +7,14 @@
 #include <cmath>
 #include <vector>
 
+// Mat3d and svd3 also compile for the device (hipcc): the RANSAC minimal solve (csrc/ransac.hip) projects its
+// hypotheses to rank 2 with the same 3x3 SVD the host uses
+#if defined(__HIPCC__) || defined(__HIP__)
+#define VO_LINALG_HD __host__ __device__
+#else
+#define VO_LINALG_HD
+#endif
+
 namespace vo {
 namespace linalg {
 
@@ -57,16 +65,16 @@ inline void jacobi_eigen_sym(int n, std::vector<double> a, std::vector<double>& 
 
 struct Mat3d {
   double m[3][3];
-  static Mat3d zero() { Mat3d z; for (auto& r : z.m) for (double& x : r) x = 0; return z; }
-  static Mat3d identity() { Mat3d z = zero(); z.m[0][0] = z.m[1][1] = z.m[2][2] = 1; return z; }
-  Mat3d operator*(const Mat3d& b) const {
+  VO_LINALG_HD static Mat3d zero() { Mat3d z; for (auto& r : z.m) for (double& x : r) x = 0; return z; }
+  VO_LINALG_HD static Mat3d identity() { Mat3d z = zero(); z.m[0][0] = z.m[1][1] = z.m[2][2] = 1; return z; }
+  VO_LINALG_HD Mat3d operator*(const Mat3d& b) const {
     Mat3d c = zero();
     for (int i = 0; i < 3; ++i) for (int j = 0; j < 3; ++j) for (int k = 0; k < 3; ++k) c.m[i][j] += m[i][k] * b.m[k][j];
     return c;
   }
-  Mat3d transpose() const { Mat3d t; for (int i = 0; i < 3; ++i) for (int j = 0; j < 3; ++j) t.m[i][j] = m[j][i]; return t; }
-  Mat3d operator-() const { Mat3d t; for (int i = 0; i < 3; ++i) for (int j = 0; j < 3; ++j) t.m[i][j] = -m[i][j]; return t; }
-  double det() const {
+  VO_LINALG_HD Mat3d transpose() const { Mat3d t; for (int i = 0; i < 3; ++i) for (int j = 0; j < 3; ++j) t.m[i][j] = m[j][i]; return t; }
+  VO_LINALG_HD Mat3d operator-() const { Mat3d t; for (int i = 0; i < 3; ++i) for (int j = 0; j < 3; ++j) t.m[i][j] = -m[i][j]; return t; }
+  VO_LINALG_HD double det() const {
     return m[0][0] * (m[1][1] * m[2][2] - m[1][2] * m[2][1]) - m[0][1] * (m[1][0] * m[2][2] - m[1][2] * m[2][0]) +
            m[0][2] * (m[1][0] * m[2][1] - m[1][1] * m[2][0]);
   }
@@ -78,7 +86,7 @@ struct Mat3d {
 // M^T M this keeps small singular values and their vectors accurate RELATIVE to their own size -- the essential matrix has
 // one (near-)zero singular value, and its left singular vector enters the rotation candidates (epipolar_utils.cpp:154).
 // Columns whose norm vanishes against the largest get their left vector by orthogonal completion.
-inline void svd3(const Mat3d& M, Mat3d& U, double s[3], Mat3d& V) {
+VO_LINALG_HD inline void svd3(const Mat3d& M, Mat3d& U, double s[3], Mat3d& V) {
   double A[3][3], W[3][3] = {{1, 0, 0}, {0, 1, 0}, {0, 0, 1}};
   for (int i = 0; i < 3; ++i) for (int j = 0; j < 3; ++j) A[i][j] = M.m[i][j];
   for (int sweep = 0; sweep < 60; ++sweep) {
@@ -87,11 +95,11 @@ inline void svd3(const Mat3d& M, Mat3d& U, double s[3], Mat3d& V) {
       for (int q = p + 1; q < 3; ++q) {
         double app = 0, aqq = 0, apq = 0;
         for (int i = 0; i < 3; ++i) { app += A[i][p] * A[i][p]; aqq += A[i][q] * A[i][q]; apq += A[i][p] * A[i][q]; }
-        if (std::fabs(apq) <= 1e-17 * std::sqrt(app * aqq) || apq == 0.0) continue;
+        if (fabs(apq) <= 1e-17 * sqrt(app * aqq) || apq == 0.0) continue;
         rotated = true;
         const double zeta = (aqq - app) / (2.0 * apq);
-        const double t = (zeta >= 0 ? 1.0 : -1.0) / (std::fabs(zeta) + std::sqrt(1.0 + zeta * zeta));
-        const double c = 1.0 / std::sqrt(1.0 + t * t), sn = c * t;
+        const double t = (zeta >= 0 ? 1.0 : -1.0) / (fabs(zeta) + sqrt(1.0 + zeta * zeta));
+        const double c = 1.0 / sqrt(1.0 + t * t), sn = c * t;
         for (int i = 0; i < 3; ++i) {
           const double x = A[i][p], y = A[i][q];
           A[i][p] = c * x - sn * y; A[i][q] = sn * x + c * y;
@@ -103,9 +111,9 @@ inline void svd3(const Mat3d& M, Mat3d& U, double s[3], Mat3d& V) {
   }
   double nrm[3];
   int order[3] = {0, 1, 2};
-  for (int j = 0; j < 3; ++j) nrm[j] = std::sqrt(A[0][j] * A[0][j] + A[1][j] * A[1][j] + A[2][j] * A[2][j]);
-  for (int i = 0; i < 2; ++i) for (int j = i + 1; j < 3; ++j) if (nrm[order[j]] > nrm[order[i]]) std::swap(order[i], order[j]);   // descending, stable
-  const double tol = 1e-13 * std::max(nrm[order[0]], 1e-300);
+  for (int j = 0; j < 3; ++j) nrm[j] = sqrt(A[0][j] * A[0][j] + A[1][j] * A[1][j] + A[2][j] * A[2][j]);
+  for (int i = 0; i < 2; ++i) for (int j = i + 1; j < 3; ++j) if (nrm[order[j]] > nrm[order[i]]) { const int o = order[i]; order[i] = order[j]; order[j] = o; }   // descending, stable
+  const double tol = 1e-13 * (nrm[order[0]] < 1e-300 ? 1e-300 : nrm[order[0]]);   // std::max, spelt out for the device
   int have = 0;
   for (int c = 0; c < 3; ++c) {
     const int j = order[c];
@@ -122,11 +130,11 @@ inline void svd3(const Mat3d& M, Mat3d& U, double s[3], Mat3d& V) {
   if (have == 0) { U = Mat3d::identity(); return; }
   if (have == 1) {
     double u0[3]; col(0, u0);
-    int k = std::fabs(u0[0]) < std::fabs(u0[1]) ? (std::fabs(u0[0]) < std::fabs(u0[2]) ? 0 : 2) : (std::fabs(u0[1]) < std::fabs(u0[2]) ? 1 : 2);
+    int k = fabs(u0[0]) < fabs(u0[1]) ? (fabs(u0[0]) < fabs(u0[2]) ? 0 : 2) : (fabs(u0[1]) < fabs(u0[2]) ? 1 : 2);
     double e[3] = {0, 0, 0}; e[k] = 1;
     const double d = u0[k];
     double u1[3] = {e[0] - d * u0[0], e[1] - d * u0[1], e[2] - d * u0[2]};
-    const double n1 = std::sqrt(u1[0] * u1[0] + u1[1] * u1[1] + u1[2] * u1[2]);
+    const double n1 = sqrt(u1[0] * u1[0] + u1[1] * u1[1] + u1[2] * u1[2]);
     for (double& x : u1) x /= n1;
     set(1, u1);
     have = 2;

@@ -15,7 +15,7 @@
 // pairs, same order, same results.  setMatchesExternal(): the pairs come from somewhere else altogether -- the native
 // multi-GPU driver matches blocks of consecutive pairs on the node's GPUs and gathers them (apps/sequence_mgpu.cpp,
 // SURVEY 8(e)) -- as [row][capacity] pairs + one count per row in device memory of this context, row_of[t - 1] naming
-// the row of pair (t-1, t).  The mode in force when run() starts is the one counts() / cloud() read afterwards.
+// the row of pair (t-1, t).  setInitRansac(): the first pair's pose comes from vo_estimate_transform_ransac_dev.  The mode in force when run() starts is the one counts() / cloud() read afterwards.
 #pragma once
 
 #include <algorithm>
@@ -82,6 +82,13 @@ class DeviceSequence {
     }
     keep_map_ = on;
   }
+  //! initialise the first pair through vo_estimate_transform_ransac_dev (robust to mismatched pairs) instead of
+  //! vo_estimate_transform_dev; nothing else in the chain changes
+  void setInitRansac(const vo_ransac_params& params) {
+    if (ran_) throw Error(VO_ERR_INVALID_ARG, "DeviceSequence: setInitRansac after run()");
+    ransac_params_ = params;
+    ransac_ = true;
+  }
   //! match every consecutive pair in one batched call at the start of run() instead of one call per frame inside the chain
   void setMatchUpFront(bool on) {
     if (ran_) throw Error(VO_ERR_INVALID_ARG, "DeviceSequence: the matching mode cannot change after run()");
@@ -119,8 +126,13 @@ class DeviceSequence {
     }
     // first pair: vo_complete.cpp:121-132
     match(1);
-    check(vo_estimate_transform_dev(ctx_, cam_.cameraMatrix().data(), m_of(1), (int)std::min(n(0), n(1)), cnt(1, 0), pts_of(0), (int)n(0),
-                                    pts_of(1), (int)n(1), X0_.data()), "vo_estimate_transform_dev");
+    if (ransac_)
+      check(vo_estimate_transform_ransac_dev(ctx_, cam_.cameraMatrix().data(), m_of(1), (int)std::min(n(0), n(1)), cnt(1, 0), pts_of(0),
+                                             (int)n(0), pts_of(1), (int)n(1), &ransac_params_, X0_.data(), nullptr, nullptr, nullptr),
+            "vo_estimate_transform_ransac_dev");
+    else
+      check(vo_estimate_transform_dev(ctx_, cam_.cameraMatrix().data(), m_of(1), (int)std::min(n(0), n(1)), cnt(1, 0), pts_of(0), (int)n(0),
+                                      pts_of(1), (int)n(1), X0_.data()), "vo_estimate_transform_dev");
     triangulate(1, X0_.data());
     const Isometry3f I = Isometry3f::Identity();
     check(vo_memcpy_h2d(ctx_, d_traj_, I.data(), 64), "DeviceSequence::run");
@@ -256,6 +268,8 @@ class DeviceSequence {
   std::vector<int> row_of_;
   enum Mode { PerFrame, UpFront, External } mode_ = PerFrame;
   bool ran_ = false;
+  bool ransac_ = false;
+  vo_ransac_params ransac_params_{};
   std::vector<void*> owned_;
 };
 

@@ -7,6 +7,7 @@
 #include "kdtree.hpp"
 #include "files.hpp"
 #include "picp_solver.hpp"
+#include "ransac.hpp"
 #include "point_cloud.hpp"
 #include "sequence.hpp"
 #include "types.hpp"

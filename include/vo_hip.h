@@ -366,6 +366,48 @@ int vo_estimate_transform(vo_ctx *ctx, const float K[9], const int32_t *pairs, i
 int vo_estimate_transform_dev(vo_ctx *ctx, const float K[9], const int32_t *d_pairs, int n_max, const int *d_n_pairs,
                               const float *d_p1_uv, int n1, const float *d_p2_uv, int n2, float X_out[16]);
 
+/* ---- estimate_transform behind RANSAC (robust initialisation) ---------------- */
+/* The same pose as vo_estimate_transform, computed on the largest consensus set of n_hypotheses minimal
+ * 8-point fits instead of on every pair, so that mismatched pairs do not bias it.
+ *
+ * Sampling (reproducible bit for bit outside the library).  n = live pairs, all arithmetic on uint64:
+ *   splitmix64(x): x += 0x9E3779B97F4A7C15; z = x; z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9;
+ *                  z = (z ^ (z >> 27)) * 0x94D049BB133111EB; return z ^ (z >> 31)
+ *   draw(h, j)   = ((splitmix64(seed ^ ((h << 20) | j)) >> 32) * n) >> 32          j = 0, 1, 2, ... 63
+ * The sample of hypothesis h is the first 8 DISTINCT values of draw(h, 0), draw(h, 1), ...; fewer than 8 within
+ * j < 64 leaves the hypothesis invalid.  Its F solves the 8 x 9 system of those pairs' normalised points (the
+ * normalisation of vo_estimate_transform: per-axis maxima of ALL n1 / n2 points) in double, projected to rank 2,
+ * un-normalised (F = T1^T F T2) and scaled to unit Frobenius norm; a (near-)singular system leaves it invalid.
+ * Scoring: pair (u1, v1) <-> (u2, v2), x1 = (u1, v1, 1), x2 = (u2, v2, 1), e = x1^T F x2,
+ *   d^2 = e^2 / ((F x2)_0^2 + (F x2)_1^2 + (F^T x1)_0^2 + (F^T x1)_1^2)       (Sampson distance, pixels^2)
+ * is an inlier iff d^2 < threshold_px^2 (strict; a zero denominator or a NaN is an outlier).  The winner has the most
+ * inliers, ties going to the lowest h.
+ * Refit: the winner's inlier pairs, in their original order, go through vo_estimate_transform_dev -- X_out is bit
+ * for bit what vo_estimate_transform returns for those pairs.  inlier_mask (n entries, or NULL) marks them;
+ * *n_inliers (or NULL) counts them.  Refused: fewer than 8 pairs or a winner with fewer than 8 inliers
+ * (VO_ERR_INVALID_ARG), a bad index (VO_ERR_BAD_INDEX), n_hypotheses outside 1 .. 65536, a threshold that is not
+ * positive and finite, a call during a graph capture. */
+typedef struct vo_ransac_params {
+  int      n_hypotheses;   /* 1 .. 65536 */
+  float    threshold_px;   /* Sampson distance in pixels, > 0 and finite */
+  uint64_t seed;
+} vo_ransac_params;
+
+int vo_estimate_transform_ransac(vo_ctx *ctx, const float K[9], const int32_t *pairs, int n,
+                                 const float *p1_uv, int n1, const float *p2_uv, int n2,
+                                 const vo_ransac_params *params, float X_out[16],
+                                 uint8_t *inlier_mask /* n entries or NULL */, int *n_inliers /* or NULL */);
+/* The same from arrays in device memory (as vo_estimate_transform_dev): *d_n_pairs (or NULL) <= n_max pairs are
+ * live, pairs beyond them are never sampled and get mask 0.  d_inlier_mask: n_max bytes of device memory, or NULL.
+ * d_hypothesis_counts: n_hypotheses ints of device memory, or NULL -- every hypothesis's inlier count, -1 for an
+ * invalid one.  One read-back after the selection, then the refit's two; X_out and *n_inliers on the host. */
+int vo_estimate_transform_ransac_dev(vo_ctx *ctx, const float K[9], const int32_t *d_pairs, int n_max,
+                                     const int *d_n_pairs, const float *d_p1_uv, int n1, const float *d_p2_uv, int n2,
+                                     const vo_ransac_params *params, float X_out[16],
+                                     uint8_t *d_inlier_mask /* n_max or NULL */,
+                                     int32_t *d_hypothesis_counts /* n_hypotheses or NULL */,
+                                     int *n_inliers /* host, or NULL */);
+
 /* ---- many independent frame pairs at once (throughput form of vo_complete.cpp:156-173) ---- */
 /* For each of n_frames independent frame pairs: match -> join -> X_prev * model -> n_iters rounds
  * from the identity -> triangulate, every stage one batched launch (frame = a grid dimension) and

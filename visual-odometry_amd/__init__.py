@@ -17,7 +17,9 @@ from .api import (  # noqa: F401
     VoError,
     compute_correspondences_images,
     default_context,
+    RansacParams,
     estimate_transform,
+    estimate_transform_ransac,
     extract_correspondences_world,
     load_library,
     radius_search,

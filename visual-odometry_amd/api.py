@@ -448,6 +448,30 @@ def estimate_transform(k, correspondences, p1_img, p2_img, ctx: Context | None =
     return X.reshape(4, 4).T.copy()
 
 
+class RansacParams(C.Structure):
+    """vo_ransac_params (include/vo_hip.h)"""
+    _fields_ = [("n_hypotheses", C.c_int), ("threshold_px", C.c_float), ("seed", C.c_uint64)]
+
+
+def estimate_transform_ransac(k, correspondences, p1_img, p2_img, threshold_px=1.0, n_hypotheses=2048, seed=0,
+                              ctx: Context | None = None):
+    """estimate_transform behind RANSAC (vo_estimate_transform_ransac): n_hypotheses minimal 8-point fits scored by
+    Sampson distance on the GPU, the pose refitted on the best one's inliers -- bit for bit
+    estimate_transform(k, correspondences[mask], p1_img, p2_img).  Returns (X, mask (bool, one per pair), n_inliers)."""
+    ctx = ctx or default_context()
+    pairs = _i32pairs(correspondences)
+    a = _f32(p1_img, (-1, 2))
+    b = _f32(p2_img, (-1, 2))
+    X = np.zeros(16, dtype=np.float32)
+    mask = np.zeros(max(len(pairs), 1), dtype=np.uint8)
+    n_in = C.c_int()
+    prm = RansacParams(int(n_hypotheses), float(threshold_px), int(seed) & 0xFFFFFFFFFFFFFFFF)
+    _chk(ctx.lib.vo_estimate_transform_ransac(ctx.h, _ptr(_colmajor(k, 3)), _ptr(pairs), C.c_int(len(pairs)), _ptr(a),
+                                              C.c_int(len(a)), _ptr(b), C.c_int(len(b)), C.byref(prm), _ptr(X), _ptr(mask),
+                                              C.byref(n_in)))
+    return X.reshape(4, 4).T.copy(), mask[: len(pairs)].astype(bool), n_in.value
+
+
 def radius_search(tree_appearances, query_appearances, radius=0.1, ctx: Context | None = None):
     """TreeNode_::fullSearch (eigen_kdtree.h:56-71) for every query: list of int32 arrays, one per query,
     with the indices of ALL tree points closer than `radius` (ascending; the library's order is unspecified)."""

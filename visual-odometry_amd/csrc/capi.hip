@@ -109,6 +109,7 @@ struct vo_ctx {
   const PicpParams* batch_params_dev = nullptr;
   DevBuf prune_ws;    // sorted copies / tables of the matcher's sorted variants
   DevBuf epi_ws;      // maxima, A^T A and vote counts of vo_estimate_transform
+  DevBuf ransac_ws;   // points, hypotheses, counts, mask and inlier pairs of vo_estimate_transform_ransac
   // Steering of the automatic matcher by what the previous batched call found: after a call that ran the
   // exact-duplicate pass, "did any frame take it?" travels to pinned host memory behind the call (no wait); a later call
   // that finds the answer "none" there leaves the pass out for the next HINT_SKIP calls, then probes again.  Data whose
@@ -281,7 +282,7 @@ int vo_ctx_destroy(vo_ctx* c) {
   (void)hipSetDevice(c->device);
   (void)hipStreamSynchronize(c->stream);
   c->scratch.release(); c->best.release(); c->table.release(); c->counts.release();
-  c->batch_pack.release(); c->batch_bad.release(); c->prune_ws.release(); c->epi_ws.release();
+  c->batch_pack.release(); c->batch_bad.release(); c->prune_ws.release(); c->epi_ws.release(); c->ransac_ws.release();
   if (c->hint_ev) (void)hipEventDestroy(c->hint_ev);
   if (c->hint_host) (void)hipHostFree(c->hint_host);
   if (c->hint_dev) (void)hipFree(c->hint_dev); c->batch_states.release(); c->batch_partials.release(); c->batch_help.release();
@@ -1655,6 +1656,77 @@ int vo_estimate_transform(vo_ctx* c, const float K[9], const int32_t* pairs, int
   if (int r = upload(c, c->in[1], p1, sizeof(float) * 2 * (size_t)n1)) return r;
   if (int r = upload(c, c->in[2], p2, sizeof(float) * 2 * (size_t)n2)) return r;
   return vo_estimate_transform_dev(c, K, c->in[0].as<int32_t>(), n, nullptr, c->in[1].as<float>(), n1, c->in[2].as<float>(), n2, X_out);
+}
+
+// ---- RANSAC in front of the epipolar initialisation (ransac.hip) ---------------------------------------------------------
+// gather -> hypotheses -> scoring -> selection -> mask and compaction: one read-back (live pairs, bad indices, winner, inliers);
+// then vo_estimate_transform_dev itself on the compacted inlier pairs, which makes the result that of vo_estimate_transform
+// on those pairs bit for bit.
+static int ransac_check_params(const vo_ransac_params* p) {
+  if (p->n_hypotheses < 1 || p->n_hypotheses > 65536)
+    return fail(VO_ERR_INVALID_ARG, "vo_estimate_transform_ransac: n_hypotheses %d outside 1 .. 65536", p->n_hypotheses);
+  if (!(p->threshold_px > 0.f) || !std::isfinite(p->threshold_px))
+    return fail(VO_ERR_INVALID_ARG, "vo_estimate_transform_ransac: threshold_px must be positive and finite (%g)", (double)p->threshold_px);
+  return VO_OK;
+}
+
+int vo_estimate_transform_ransac_dev(vo_ctx* c, const float K[9], const int32_t* d_pairs, int n_max, const int* d_n,
+                                     const float* d_p1, int n1, const float* d_p2, int n2, const vo_ransac_params* params,
+                                     float X_out[16], uint8_t* d_mask, int32_t* d_counts, int* n_inliers) {
+  VO_REQUIRE(c && K && d_pairs && d_p1 && d_p2 && params && X_out, "null argument");
+  VO_NOT_CAPTURING(c);
+  VO_REQUIRE(n_max >= 8, "fewer than 8 correspondences");
+  VO_REQUIRE(n1 > 0 && n2 > 0, "empty point set");
+  VO_REQUIRE(aligned8(d_pairs, d_p1, d_p2), "device arrays must be 8-byte aligned");
+  if (int r = ransac_check_params(params)) return r;
+  if (int r = set_device(c)) return r;
+  const int H = params->n_hypotheses;
+  VO_HIP_CHECK(c->ransac_ws.ensure(ransac_workspace_bytes(n_max, H), c->stream));
+  RansacArgs a = ransac_layout(c->ransac_ws.p, n_max, H);
+  a.pairs = d_pairs; a.d_n = d_n; a.p1 = d_p1; a.n1 = n1; a.p2 = d_p2; a.n2 = n2;
+  a.seed = params->seed; a.thr2 = params->threshold_px * params->threshold_px;
+  if (d_mask) a.mask = d_mask;
+  if (d_counts) a.counts = d_counts;
+  VO_HIP_CHECK(launch_ransac(c->stream, a));
+  int info[8];
+  VO_HIP_CHECK(hipMemcpyAsync(info, a.info, sizeof(info), hipMemcpyDeviceToHost, c->stream));
+  VO_HIP_CHECK(hipStreamSynchronize(c->stream));
+  if (info[1] > 0)
+    return fail(VO_ERR_BAD_INDEX, "vo_estimate_transform_ransac: %d pair(s) index outside the point arrays", info[1]);
+  if (info[0] < 8) return fail(VO_ERR_INVALID_ARG, "vo_estimate_transform_ransac: fewer than 8 correspondences (%d)", info[0]);
+  if (info[2] < 0) return fail(VO_ERR_INVALID_ARG, "vo_estimate_transform_ransac: no valid hypothesis among %d", H);
+  if (info[4] < 8)
+    return fail(VO_ERR_INVALID_ARG, "vo_estimate_transform_ransac: the best hypothesis (%d) has %d inlier(s), fewer than 8", info[2], info[4]);
+  if (int r = vo_estimate_transform_dev(c, K, a.out_pairs, info[4], nullptr, d_p1, n1, d_p2, n2, X_out)) return r;
+  if (n_inliers) *n_inliers = info[4];
+  return VO_OK;
+}
+
+int vo_estimate_transform_ransac(vo_ctx* c, const float K[9], const int32_t* pairs, int n, const float* p1, int n1,
+                                 const float* p2, int n2, const vo_ransac_params* params, float X_out[16], uint8_t* inlier_mask,
+                                 int* n_inliers) {
+  VO_REQUIRE(c && K && pairs && p1 && p2 && params && X_out, "null argument");
+  VO_NOT_CAPTURING(c);
+  VO_REQUIRE(n >= 8, "fewer than 8 correspondences");
+  VO_REQUIRE(n1 > 0 && n2 > 0, "empty point set");
+  if (int r = ransac_check_params(params)) return r;
+  for (int i = 0; i < n; ++i)
+    if (pairs[2 * i] < 0 || pairs[2 * i] >= n1 || pairs[2 * i + 1] < 0 || pairs[2 * i + 1] >= n2)
+      return fail(VO_ERR_BAD_INDEX, "vo_estimate_transform_ransac: pair %d = (%d,%d) outside the point arrays", i,
+                  pairs[2 * i], pairs[2 * i + 1]);
+  if (int r = set_device(c)) return r;
+  if (int r = upload(c, c->in[0], pairs, sizeof(int32_t) * 2 * (size_t)n)) return r;
+  if (int r = upload(c, c->in[1], p1, sizeof(float) * 2 * (size_t)n1)) return r;
+  if (int r = upload(c, c->in[2], p2, sizeof(float) * 2 * (size_t)n2)) return r;
+  if (inlier_mask) VO_HIP_CHECK(c->out[0].ensure((size_t)n, c->stream));
+  if (int r = vo_estimate_transform_ransac_dev(c, K, c->in[0].as<int32_t>(), n, nullptr, c->in[1].as<float>(), n1, c->in[2].as<float>(),
+                                               n2, params, X_out, inlier_mask ? c->out[0].as<uint8_t>() : nullptr, nullptr, n_inliers))
+    return r;
+  if (inlier_mask) {
+    VO_HIP_CHECK(hipMemcpyAsync(inlier_mask, c->out[0].p, (size_t)n, hipMemcpyDeviceToHost, c->stream));
+    VO_HIP_CHECK(hipStreamSynchronize(c->stream));
+  }
+  return VO_OK;
 }
 
 // ---- the map (PointCloudVector<3>::update + the history chain of vo_complete.cpp:145-147,175-176,183) ---------------------------

@@ -180,6 +180,13 @@ hipError_t launch_epi_front(hipStream_t st, const int32_t* d_pairs, int n_max, c
   return hipGetLastError();
 }
 
+hipError_t launch_epi_maxima(hipStream_t st, const float* d_p1, int n1, const float* d_p2, int n2, unsigned* out) {
+  int big = n1 > n2 ? n1 : n2;
+  int g = (big + EB - 1) / EB; if (g < 1) g = 1; if (g > 512) g = 512;
+  hipLaunchKernelGGL(epi_max_kernel, dim3(g), dim3(EB), 0, st, d_p1, n1, d_p2, n2, out);
+  return hipGetLastError();
+}
+
 hipError_t launch_epi_vote(hipStream_t st, const float K[9], const Pose X[4], const int32_t* d_pairs, int n_max, const int* d_n,
                            const float* d_p1, int n1, const float* d_p2, int n2, void* ws) {
   VoteArgs a;

@@ -319,5 +319,27 @@ hipError_t launch_epi_front(hipStream_t st, const int32_t* d_pairs, int n_max, c
                             const float* d_p2, int n2, void* ws);
 hipError_t launch_epi_vote(hipStream_t st, const float K[9], const Pose X[4], const int32_t* d_pairs, int n_max, const int* d_n,
                            const float* d_p1, int n1, const float* d_p2, int n2, void* ws);
+// the per-axis maxima of both point sets alone (epi_max_kernel) into out[4], which the caller has zeroed
+hipError_t launch_epi_maxima(hipStream_t st, const float* d_p1, int n1, const float* d_p2, int n2, unsigned* out);
+
+// ---- RANSAC in front of the epipolar initialisation (ransac.hip) --------------------------------------------
+struct RansacArgs {
+  const int32_t* pairs; int n_max; const int* d_n;
+  const float* p1; int n1;
+  const float* p2; int n2;
+  int n_hyp; unsigned long long seed; float thr2;
+  int* info;                  // [0] live pairs  [1] pairs with a bad index  [2] winner (-1: none)  [3] its count  [4] inliers compacted
+  unsigned* maxima;           // [4] per-axis maxima of p1, p2 (float bits)
+  float4* pts;                // [n_max] (u1, v1, u2, v2) of the live pairs
+  float* F;                   // [n_hyp][12]: F row-major, [9] = 1 valid / 0 invalid
+  int* counts;                // [n_hyp] inliers per hypothesis, -1 invalid
+  uint8_t* mask;              // [n_max] the winner's inliers
+  int* blk;                   // per-workgroup counts of the compaction
+  int32_t* out_pairs;         // [n_max][2] the winner's inlier pairs, in their original order
+};
+size_t ransac_workspace_bytes(int n_max, int n_hyp);
+// the workspace's arrays; the caller fills in the inputs and may point counts / mask elsewhere
+RansacArgs ransac_layout(void* ws, int n_max, int n_hyp);
+hipError_t launch_ransac(hipStream_t st, const RansacArgs& a);
 
 }  // namespace vo

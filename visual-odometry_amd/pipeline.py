@@ -385,7 +385,8 @@ class SequencePipeline:
 
     def __init__(self, ctx: Context, seq: dict, n_iters: int = 100, kernel_threshold: float = 10000.0,
                  keep_appearance: bool = False, matches: list | None = None, overlap_match: bool = False, exact: bool = False,
-                 prematch: bool = False, keep_map: bool = False, map_capacity: int | None = None):
+                 prematch: bool = False, keep_map: bool = False, map_capacity: int | None = None,
+                 init_ransac: dict | None = None):
         """prematch: the matcher depends on the appearances alone, so when the whole sequence is on hand -- as it
         is for vo_complete, which reads its measurement files from a directory -- all F-1 consecutive pairs are matched by ONE
         vo_match_appearances_batch_dev call at start() (frames of different sizes, per-frame tree choice as in the single
@@ -399,7 +400,9 @@ class SequencePipeline:
         context (its own HIP stream), one frame ahead into a double buffer, ordered against the chain by
         events.  Results are identical; on MI355X at 50k points it is SLOWER than the single-stream chain
         (1.35 k vs 1.52 k frames/s): the matcher's waves take issue slots from the latency-bound solver
-        rounds, so it is off by default and kept as a measured option."""
+        rounds, so it is off by default and kept as a measured option.
+        init_ransac: initialise through vo_estimate_transform_ransac_dev instead (robust to mismatched pairs), e.g.
+        dict(threshold_px=1.0, n_hypotheses=2048, seed=0) -- missing keys take those values; nothing else changes."""
         self.ctx, self.lib = ctx, ctx.lib
         self.n_iters = n_iters
         fr = seq["frames"]
@@ -462,6 +465,11 @@ class SequencePipeline:
         _chk(self.lib.vo_picp_pose_dev_ptr(h, C.byref(p)))
         self.d_pose = p.value
         self.X0 = None
+        self.ransac = None
+        if init_ransac is not None:
+            from .api import RansacParams
+            r = dict(dict(threshold_px=1.0, n_hypotheses=2048, seed=0), **init_ransac)
+            self.ransac = RansacParams(int(r["n_hypotheses"]), float(r["threshold_px"]), int(r["seed"]) & 0xFFFFFFFFFFFFFFFF)
 
     # device addresses of frame t's inputs / outputs
     def _pts(self, t): return C.c_void_p(self.d_pts + 8 * int(self.off[t]))
@@ -526,9 +534,14 @@ class SequencePipeline:
         self._match(1)
         X = np.zeros(16, np.float32)
         # pairs, count and both images as they lie in device memory: no copy of the pairs to the host (vo_estimate_transform_dev)
-        _chk(self.lib.vo_estimate_transform_dev(self.ctx.h, _ptr(self.K), self._m(1), C.c_int(min(self.n[0], self.n[1])),
-                                                self._cnt(1, 0), self._pts(0), C.c_int(self.n[0]), self._pts(1),
-                                                C.c_int(self.n[1]), _ptr(X)))
+        if self.ransac is not None:
+            _chk(self.lib.vo_estimate_transform_ransac_dev(self.ctx.h, _ptr(self.K), self._m(1), C.c_int(min(self.n[0], self.n[1])),
+                                                           self._cnt(1, 0), self._pts(0), C.c_int(self.n[0]), self._pts(1),
+                                                           C.c_int(self.n[1]), C.byref(self.ransac), _ptr(X), None, None, None))
+        else:
+            _chk(self.lib.vo_estimate_transform_dev(self.ctx.h, _ptr(self.K), self._m(1), C.c_int(min(self.n[0], self.n[1])),
+                                                    self._cnt(1, 0), self._pts(0), C.c_int(self.n[0]), self._pts(1),
+                                                    C.c_int(self.n[1]), _ptr(X)))
         self.X0 = X
         self._triangulate(1, X)
         self._release(1)
