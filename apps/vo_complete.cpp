@@ -4,6 +4,7 @@
 // current directory or into argv[2]): world.txt, trajectory_gt.txt, map.txt,
 // map_appearances.txt, trajectory_est_complete.txt, trajectory_est_data.txt.
 //   usage: vo_complete <data dir> [output dir] [rounds=100] [--resident [--match-up-front]] [--exact] [--ransac[=px]]
+//          [--track-ransac[=px]]
 // --resident: the same sequence through vo::DeviceSequence -- all measurement files are read and uploaded first, the
 // whole frame chain runs on the GPU without a host round trip per frame, the map upkeep included (vo_map_*: the
 // reference's upsert as a hash table of first occurrences in device memory).  Same outputs.
@@ -13,6 +14,10 @@
 // Sampson threshold px, default 1, seed 0: vo::estimate_transform_ransac / DeviceSequence::setInitRansac) instead of from
 // all of them.  The frame-by-frame form refits the inliers with the same estimate_transform it uses without the flag;
 // with no mismatched pair every output file is the same as without the flag.
+// --track-ransac[=px]: every frame t >= 2 is tracked from the best of 2048 P3P hypotheses over its joined pairs (reprojection
+// threshold px, default 1, seed 0: vo::estimate_pose_ransac / DeviceSequence::setTrackRansac) -- the solver starts from the
+// winner's pose and runs its rounds on the winner's inliers.  A frame the host form refuses (fewer than 4 pairs, no valid
+// hypothesis, fewer than 6 inliers) runs as without the flag, which is what the device form does on its own.
 // Also written: poses_raw.txt, one camera pose per line (row-major 4x4, %.9g = exact float32 round trip), and map_raw.txt,
 // one map entry per line (x y z a0..a9, %.9g).
 #include <cstdio>
@@ -45,7 +50,7 @@ static void write_map_raw(const std::string& file, const PointCloudVector<3>& ma
 
 // the device-resident form of the loop below: same call sequence, the frame chain inside vo::DeviceSequence
 static int run_resident(const std::string& path, const std::string& out, int rounds, bool exact, bool up_front, float ransac_px,
-                        const std::string& first_file,
+                        float track_px, const std::string& first_file,
                         const std::string& second_file, const std::set<std::string>& files) {
   std::vector<PointCloudVector<2>> frames;
   std::vector<std::string> names{first_file, second_file};
@@ -68,6 +73,7 @@ static int run_resident(const std::string& path, const std::string& out, int rou
   seq.setExact(exact);
   seq.setMatchUpFront(up_front);              // all consecutive pairs in one batched matcher call before the chain
   if (ransac_px > 0.f) seq.setInitRansac(ransac_params(ransac_px));
+  if (track_px > 0.f) seq.setTrackRansac(track_ransac_params(track_px));
   seq.setKeepMap(true);                       // map.update / history inside the chain, on the device (vo_complete.cpp:145-147,175-176)
   seq.run();
   const IsometryVector trajectory = seq.trajectory();          // waits for the chain
@@ -92,6 +98,7 @@ int main(int argc, char* argv[]) {
   // flags first, wherever they stand; what is left are the positional arguments
   bool resident = false, exact = false, up_front = false;
   float ransac_px = 0.f;                      // 0: no RANSAC
+  float track_px = 0.f;                       // 0: no tracking RANSAC
   std::vector<std::string> pos;
   for (int i = 1; i < argc; ++i) {
     const std::string a(argv[i]);
@@ -102,6 +109,11 @@ int main(int argc, char* argv[]) {
     else if (a.rfind("--ransac=", 0) == 0) {
       ransac_px = std::strtof(a.c_str() + 9, nullptr);
       if (!(ransac_px > 0.f)) { std::cout << "--ransac=px needs a positive threshold" << std::endl; return -1; }
+    }
+    else if (a == "--track-ransac") track_px = 1.f;
+    else if (a.rfind("--track-ransac=", 0) == 0) {
+      track_px = std::strtof(a.c_str() + 15, nullptr);
+      if (!(track_px > 0.f)) { std::cout << "--track-ransac=px needs a positive threshold" << std::endl; return -1; }
     }
     else if (a.rfind("--", 0) == 0) { std::cout << "unknown option " << a << std::endl; return -1; }
     else pos.push_back(a);
@@ -122,7 +134,7 @@ int main(int argc, char* argv[]) {
     const auto second_file = *(files.erase(files.begin()));
     files.erase(files.begin());
 
-    if (resident) return run_resident(path, out, rounds, exact, up_front, ransac_px, first_file, second_file, files);
+    if (resident) return run_resident(path, out, rounds, exact, up_front, ransac_px, track_px, first_file, second_file, files);
     PointCloudVector<2> reference_pc, current_pc;
     if (!get_meas_content(path + first_file, reference_pc)) { std::cout << "Unable to open file measurement file 0\n"; return -1; }
     if (!get_meas_content(path + second_file, current_pc)) { std::cout << "Unable to open file measurement file 1\n"; return -1; }
@@ -172,8 +184,20 @@ int main(int argc, char* argv[]) {
       correspondences_world = extract_correspondences_world(correspondences_imgs, correspondences_world);
       triangulated_transformed = X_curr * triangulated_pc;
       cam.setWorldInCameraPose(Isometry3f::Identity());
+      const IntPairVector* round_pairs = &correspondences_world;
+      IntPairVector track_pairs;              // --track-ransac: the winner's inliers, the solve starting from its pose
+      if (track_px > 0.f) {
+        try {
+          std::vector<uint8_t> inlier;
+          const Isometry3f T = estimate_pose_ransac(cam, triangulated_transformed.points(), current_pc.points(), correspondences_world,
+                                                    track_ransac_params(track_px), &inlier);
+          for (size_t i = 0; i < correspondences_world.size(); ++i) if (inlier[i]) track_pairs.push_back(correspondences_world[i]);
+          cam.setWorldInCameraPose(T);
+          round_pairs = &track_pairs;
+        } catch (const vo::Error&) {}         // refused: the plain frame, as the device form falls back
+      }
       solver.init(cam, triangulated_transformed.points(), current_pc.points());
-      for (int i = 0; i < rounds; i++) solver.oneRound(correspondences_world, false);
+      for (int i = 0; i < rounds; i++) solver.oneRound(*round_pairs, false);
       cam = solver.camera();
       trajectory.push_back(cam.worldInCameraPose());
       X_curr = cam.worldInCameraPose();

@@ -1,11 +1,14 @@
 // vo/ransac.hpp -- estimate_transform behind RANSAC (vo_estimate_transform_ransac): an extension of the facade, not a
 // reference interface.  n_hypotheses minimal 8-point fits are scored by Sampson distance on the GPU; the pose is the
 // plain GPU estimate_transform of the best hypothesis's inliers (bit for bit vo_estimate_transform of those pairs).
+// estimate_pose_ransac (vo_estimate_pose_ransac): the tracking counterpart -- minimal P3P fits over 2D-3D pairs scored by
+// reprojection on the GPU; the winner's pose and inliers are the start and the input of the PICP rounds that follow.
 #pragma once
 
 #include <cstdint>
 #include <vector>
 
+#include "camera.hpp"
 #include "context.hpp"
 #include "utils.hpp"
 
@@ -31,6 +34,29 @@ inline Isometry3f estimate_transform_ransac(const Matrix3f& k, const IntPairVect
                                      X.data(), inliers && n ? inliers->data() : nullptr, nullptr),
         "estimate_transform_ransac");
   return X;
+}
+
+//! defaults of apps/vo_complete --track-ransac: 2048 hypotheses, 1 px, seed 0
+inline vo_ransac_params track_ransac_params(float threshold_px = 1.f, int n_hypotheses = 2048, uint64_t seed = 0) {
+  return ransac_params(threshold_px, n_hypotheses, seed);
+}
+
+//! pose of the camera (world in camera, what Camera::setWorldInCameraPose takes) from the best of n_hypotheses P3P fits
+//! of the correspondences (meas_idx, world_idx) -- the solver's orientation; *inliers (if given) receives one 0/1 per
+//! correspondence.  Throws vo::Error where vo_estimate_pose_ransac refuses (fewer than 4 pairs, no valid hypothesis, a
+//! winner with fewer than 6 inliers, a bad index, bad parameters).
+inline Isometry3f estimate_pose_ransac(const Camera& cam, const Vector3fVector& world_points, const Vector2fVector& image_points,
+                                       const IntPairVector& correspondences, const vo_ransac_params& params,
+                                       std::vector<uint8_t>* inliers = nullptr) {
+  const int n = (int)correspondences.size();
+  if (inliers) inliers->assign(correspondences.size(), 0);
+  Isometry3f T = Isometry3f::Identity();
+  check(vo_estimate_pose_ransac(default_context().handle(), cam.rows(), cam.cols(), cam.zNear(), cam.zFar(), cam.cameraMatrix().data(),
+                                world_points.empty() ? nullptr : world_points[0].data(), (int)world_points.size(),
+                                detail::ptr(image_points), (int)image_points.size(), n ? pair_data(correspondences) : nullptr, n,
+                                &params, T.data(), inliers && n ? inliers->data() : nullptr, nullptr),
+        "estimate_pose_ransac");
+  return T;
 }
 
 }  // namespace vo

@@ -15,7 +15,9 @@
 // pairs, same order, same results.  setMatchesExternal(): the pairs come from somewhere else altogether -- the native
 // multi-GPU driver matches blocks of consecutive pairs on the node's GPUs and gathers them (apps/sequence_mgpu.cpp,
 // SURVEY 8(e)) -- as [row][capacity] pairs + one count per row in device memory of this context, row_of[t - 1] naming
-// the row of pair (t-1, t).  setInitRansac(): the first pair's pose comes from vo_estimate_transform_ransac_dev.  The mode in force when run() starts is the one counts() / cloud() read afterwards.
+// the row of pair (t-1, t).  setInitRansac(): the first pair's pose comes from vo_estimate_transform_ransac_dev.  setTrackRansac():
+// every frame t >= 2 runs vo_estimate_pose_ransac_dev on its joined pairs first, and the solve starts from the winner's
+// pose on the winner's inliers (a frame that falls back is the plain frame; trackStats() reads what each frame did).  The mode in force when run() starts is the one counts() / cloud() read afterwards.
 #pragma once
 
 #include <algorithm>
@@ -89,6 +91,26 @@ class DeviceSequence {
     ransac_params_ = params;
     ransac_ = true;
   }
+  //! track every frame t >= 2 through vo_estimate_pose_ransac_dev: the solve starts from the winner's pose on the winner's
+  //! inliers instead of from the identity on every joined pair (a frame that falls back runs exactly the plain solve)
+  void setTrackRansac(const vo_ransac_params& params) {
+    if (ran_) throw Error(VO_ERR_INVALID_ARG, "DeviceSequence: setTrackRansac after run()");
+    if (!track_) {
+      d_track_T_ = alloc<float>(16);
+      d_track_pairs_ = alloc<int32_t>(2 * cap_);
+      d_track_st_ = alloc<int>(2 * (size_t)F_);
+    }
+    track_params_ = params;
+    track_ = true;
+  }
+  //! frame t >= 2 of a setTrackRansac run: the status of vo_estimate_pose_ransac_dev (VO_POSE_RANSAC_*; 0: tracked) and the
+  //! number of pairs the solve was given (the winner's inliers, or every joined pair on a fallback); waits for the chain
+  void trackStats(int t, int& status, int& n_pairs) const {
+    if (!track_ || t < 2 || t >= F_) throw Error(VO_ERR_INVALID_ARG, "DeviceSequence::trackStats: frame t >= 2 of a setTrackRansac run");
+    int c[2];
+    check(vo_memcpy_d2h(ctx_, c, d_track_st_ + 2 * (size_t)t, sizeof(c)), "DeviceSequence::trackStats");
+    status = c[0]; n_pairs = c[1];
+  }
   //! match every consecutive pair in one batched call at the start of run() instead of one call per frame inside the chain
   void setMatchUpFront(bool on) {
     if (ran_) throw Error(VO_ERR_INVALID_ARG, "DeviceSequence: the matching mode cannot change after run()");
@@ -153,8 +175,18 @@ class DeviceSequence {
                                     cnt(t - 1, 2), d_model_t_), "vo_transform_points_dev");
       // the capacity (not the live count) sizes the solver's grid: one launch graph serves every frame
       check(vo_picp_set_points_dev(solver_, d_model_t_, (int)cap_, pts_of(t), (int)n(t)), "vo_picp_set_points_dev");
-      check(vo_picp_set_pose_dev(solver_, d_ident_), "vo_picp_set_pose_dev");
-      check(vo_picp_solve_dev(solver_, d_j_, (int)cap_, cnt(t, 1), 0, rounds_), "vo_picp_solve_dev");
+      if (track_) {                                              // the winner's pose and inliers (or the plain frame's)
+        int* st = d_track_st_ + 2 * (size_t)t;
+        check(vo_estimate_pose_ransac_dev(ctx_, cam_.rows(), cam_.cols(), cam_.zNear(), cam_.zFar(), cam_.cameraMatrix().data(),
+                                          d_model_t_, (int)cap_, pts_of(t), (int)n(t), d_j_, (int)cap_, cnt(t, 1), &track_params_,
+                                          d_track_T_, d_track_pairs_, st + 1, nullptr, nullptr, st),
+              "vo_estimate_pose_ransac_dev");
+        check(vo_picp_set_pose_dev(solver_, d_track_T_), "vo_picp_set_pose_dev");
+        check(vo_picp_solve_dev(solver_, d_track_pairs_, (int)cap_, st + 1, 0, rounds_), "vo_picp_solve_dev");
+      } else {
+        check(vo_picp_set_pose_dev(solver_, d_ident_), "vo_picp_set_pose_dev");
+        check(vo_picp_solve_dev(solver_, d_j_, (int)cap_, cnt(t, 1), 0, rounds_), "vo_picp_solve_dev");
+      }
       check(vo_picp_get_pose_dev(solver_, d_traj_ + 16 * (size_t)t), "vo_picp_get_pose_dev");
       triangulate(t, nullptr);
       if (keep_map_) {                                           // vo_complete.cpp:175-176
@@ -270,6 +302,11 @@ class DeviceSequence {
   bool ran_ = false;
   bool ransac_ = false;
   vo_ransac_params ransac_params_{};
+  bool track_ = false;
+  vo_ransac_params track_params_{};
+  float* d_track_T_ = nullptr;
+  int32_t* d_track_pairs_ = nullptr;
+  int* d_track_st_ = nullptr;                 // [t] = (status, pairs handed to the solve)
   std::vector<void*> owned_;
 };
 

@@ -408,6 +408,57 @@ int vo_estimate_transform_ransac_dev(vo_ctx *ctx, const float K[9], const int32_
                                      int32_t *d_hypothesis_counts /* n_hypotheses or NULL */,
                                      int *n_inliers /* host, or NULL */);
 
+/* ---- P3P RANSAC in front of the tracking solve (robust tracking) ------------- */
+/* A camera pose T (world in camera, column-major 4x4, what vo_picp_set_pose[_dev] takes) from the largest consensus
+ * set of n_hypotheses minimal P3P fits over 2D-3D pairs, and those pairs: the start and the input of a PICP solve
+ * that mismatched pairs cannot pull.  pairs = (meas_idx, world_idx), the solver's orientation; params as above.
+ *
+ * Sampling: draw(h, j) of vo_estimate_transform_ransac (n = live pairs).  The sample of hypothesis h is the first 4
+ *   DISTINCT values of draw(h, 0), draw(h, 1), ... within j < 64 (fewer: the hypothesis is invalid), s0 .. s3.
+ * Minimal solve, in double, on s0, s1, s2: world points P1, P2, P3; bearings j_k = K^-1 (u, v, 1) normalised to unit
+ *   length (K^-1 in double of the float K: any K).  Grunert's solution (Haralick et al. 1994, "Review and analysis of
+ *   solutions of the three point perspective pose estimation problem"): a^2 = |P2-P3|^2, b^2 = |P1-P3|^2,
+ *   c^2 = |P1-P2|^2, cos(alpha) = j2.j3, cos(beta) = j1.j3, cos(gamma) = j1.j2; the distances along the bearings
+ *   are s1, s2 = u s1, s3 = v s1, v a real root of Grunert's quartic A4 v^4 + A3 v^3 + A2 v^2 + A1 v + A0 (the paper's
+ *   coefficients), u = ((-1 + (a^2-c^2)/b^2) v^2 - 2 ((a^2-c^2)/b^2) cos(beta) v + 1 + (a^2-c^2)/b^2)
+ *   / (2 (cos(gamma) - v cos(alpha))), s1^2 = b^2 / (1 + v^2 - 2 v cos(beta)).  The roots are taken in closed form
+ *   (Ferrari) and refined by two Newton steps on the quartic.  A root is a solution when v > 0, u > 0, s1^2 > 0, all
+ *   finite; its R, t is the rigid motion taking P1, P2, P3 onto the camera points s_k j_k (the triangles are
+ *   congruent up to rounding).  Among the solutions the hypothesis is the one whose projection of the 4th sample's
+ *   world point lies closest to its measurement (squared pixels, +inf for a depth <= 0), ties going to the smaller v.
+ *   Invalid (count -1): fewer than 4 distinct draws, a degenerate world triangle (|(P2-P1) x (P3-P1)| <=
+ *   1e-9 |P2-P1| |P3-P1|), A4 = 0 or a non-finite coefficient, no solution.  The pose is then rounded to float.
+ * Scoring, in float with that pose: pair (m, w) is an inlier iff Camera::projectPoint of world point w succeeds
+ *   (depth in [z_near, z_far], pixel in [0, cols-1] x [0, rows-1]) and the squared reprojection error
+ *   |projection - measurement m|^2 < threshold_px^2 (strict).  The winner has the most inliers, ties to the lowest h.
+ * Output: the winner's pose, its inlier pairs compacted in their ORIGINAL order, their count. */
+#define VO_POSE_RANSAC_OK            0
+#define VO_POSE_RANSAC_FEW_PAIRS     1   /* fewer than 4 live pairs */
+#define VO_POSE_RANSAC_NO_HYPOTHESIS 2   /* every hypothesis invalid */
+#define VO_POSE_RANSAC_FEW_INLIERS   3   /* the winner has fewer than 6 inliers */
+#define VO_POSE_RANSAC_BAD_INDEX     4   /* a live pair indexes outside its array (takes precedence over 1-3) */
+/* Host form: refuses the cases 1-3 (VO_ERR_INVALID_ARG) and 4 (VO_ERR_BAD_INDEX, checked on the host first), a
+ * call during a graph capture and the parameter errors of vo_estimate_transform_ransac.  T_out: column-major 4x4;
+ * inlier_mask (n entries, or NULL) marks the winner's inliers; *n_inliers (or NULL) counts them. */
+int vo_estimate_pose_ransac(vo_ctx *ctx, int rows, int cols, int z_near, int z_far, const float K[9],
+                            const float *world_xyz, int n_world, const float *meas_uv, int n_meas,
+                            const int32_t *pairs, int n, const vo_ransac_params *params, float T_out[16],
+                            uint8_t *inlier_mask /* n entries or NULL */, int *n_inliers /* or NULL */);
+/* Device form: every argument array and every output in device memory, no host synchronisation: capturable
+ * (vo_ctx_begin_capture) once a call with the same n_max and n_hypotheses has sized the context's workspace; a
+ * capture that would need a bigger one is refused (VO_ERR_NOT_READY).  *d_n_pairs (or NULL) <= n_max pairs are
+ * live; pairs beyond them are never sampled and get mask 0.  As it cannot refuse at run time, cases 1-4 FALL BACK:
+ * *d_status = their code, d_T16_out = the identity and EVERY live pair goes to d_inlier_pairs / *d_n_inliers / the
+ * mask, so that vo_picp_set_pose_dev(d_T16_out) + vo_picp_solve_dev(d_inlier_pairs, n_max, d_n_inliers) is then
+ * exactly the plain solve from the identity.  Otherwise *d_status = 0.  d_T16_out: 16 floats; d_inlier_pairs:
+ * n_max pairs; d_inlier_mask: n_max bytes or NULL; d_hypothesis_counts: n_hypotheses ints or NULL (-1 invalid). */
+int vo_estimate_pose_ransac_dev(vo_ctx *ctx, int rows, int cols, int z_near, int z_far, const float K[9],
+                                const float *d_world_xyz, int n_world, const float *d_meas_uv, int n_meas,
+                                const int32_t *d_pairs, int n_max, const int *d_n_pairs,
+                                const vo_ransac_params *params, float *d_T16_out, int32_t *d_inlier_pairs,
+                                int *d_n_inliers, uint8_t *d_inlier_mask /* or NULL */,
+                                int32_t *d_hypothesis_counts /* or NULL */, int *d_status);
+
 /* ---- many independent frame pairs at once (throughput form of vo_complete.cpp:156-173) ---- */
 /* For each of n_frames independent frame pairs: match -> join -> X_prev * model -> n_iters rounds
  * from the identity -> triangulate, every stage one batched launch (frame = a grid dimension) and

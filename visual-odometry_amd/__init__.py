@@ -20,6 +20,7 @@ from .api import (  # noqa: F401
     RansacParams,
     estimate_transform,
     estimate_transform_ransac,
+    estimate_pose_ransac,
     extract_correspondences_world,
     load_library,
     radius_search,

@@ -472,6 +472,25 @@ def estimate_transform_ransac(k, correspondences, p1_img, p2_img, threshold_px=1
     return X.reshape(4, 4).T.copy(), mask[: len(pairs)].astype(bool), n_in.value
 
 
+def estimate_pose_ransac(k, rows, cols, z_near, z_far, world, meas, correspondences, threshold_px=1.0, n_hypotheses=2048, seed=0,
+                         ctx: Context | None = None):
+    """P3P RANSAC over 2D-3D pairs (vo_estimate_pose_ransac): n_hypotheses minimal P3P fits scored by reprojection error on
+    the GPU behind Camera::projectPoint's gates.  correspondences = (meas_idx, world_idx), the solver's orientation.  Returns
+    (T (4x4, world in camera: the pose a PICP solve starts from), mask (bool, one per pair), n_inliers)."""
+    ctx = ctx or default_context()
+    pairs = _i32pairs(correspondences)
+    w = _f32(world, (-1, 3))
+    m = _f32(meas, (-1, 2))
+    T = np.zeros(16, dtype=np.float32)
+    mask = np.zeros(max(len(pairs), 1), dtype=np.uint8)
+    n_in = C.c_int()
+    prm = RansacParams(int(n_hypotheses), float(threshold_px), int(seed) & 0xFFFFFFFFFFFFFFFF)
+    _chk(ctx.lib.vo_estimate_pose_ransac(ctx.h, C.c_int(rows), C.c_int(cols), C.c_int(z_near), C.c_int(z_far), _ptr(_colmajor(k, 3)),
+                                         _ptr(w), C.c_int(len(w)), _ptr(m), C.c_int(len(m)), _ptr(pairs), C.c_int(len(pairs)),
+                                         C.byref(prm), _ptr(T), _ptr(mask), C.byref(n_in)))
+    return T.reshape(4, 4).T.copy(), mask[: len(pairs)].astype(bool), n_in.value
+
+
 def radius_search(tree_appearances, query_appearances, radius=0.1, ctx: Context | None = None):
     """TreeNode_::fullSearch (eigen_kdtree.h:56-71) for every query: list of int32 arrays, one per query,
     with the indices of ALL tree points closer than `radius` (ascending; the library's order is unspecified)."""

@@ -110,6 +110,7 @@ struct vo_ctx {
   DevBuf prune_ws;    // sorted copies / tables of the matcher's sorted variants
   DevBuf epi_ws;      // maxima, A^T A and vote counts of vo_estimate_transform
   DevBuf ransac_ws;   // points, hypotheses, counts, mask and inlier pairs of vo_estimate_transform_ransac
+  DevBuf pose_ws;     // the same for vo_estimate_pose_ransac
   // Steering of the automatic matcher by what the previous batched call found: after a call that ran the
   // exact-duplicate pass, "did any frame take it?" travels to pinned host memory behind the call (no wait); a later call
   // that finds the answer "none" there leaves the pass out for the next HINT_SKIP calls, then probes again.  Data whose
@@ -282,7 +283,7 @@ int vo_ctx_destroy(vo_ctx* c) {
   (void)hipSetDevice(c->device);
   (void)hipStreamSynchronize(c->stream);
   c->scratch.release(); c->best.release(); c->table.release(); c->counts.release();
-  c->batch_pack.release(); c->batch_bad.release(); c->prune_ws.release(); c->epi_ws.release(); c->ransac_ws.release();
+  c->batch_pack.release(); c->batch_bad.release(); c->prune_ws.release(); c->epi_ws.release(); c->ransac_ws.release(); c->pose_ws.release();
   if (c->hint_ev) (void)hipEventDestroy(c->hint_ev);
   if (c->hint_host) (void)hipHostFree(c->hint_host);
   if (c->hint_dev) (void)hipFree(c->hint_dev); c->batch_states.release(); c->batch_partials.release(); c->batch_help.release();
@@ -1726,6 +1727,113 @@ int vo_estimate_transform_ransac(vo_ctx* c, const float K[9], const int32_t* pai
     VO_HIP_CHECK(hipMemcpyAsync(inlier_mask, c->out[0].p, (size_t)n, hipMemcpyDeviceToHost, c->stream));
     VO_HIP_CHECK(hipStreamSynchronize(c->stream));
   }
+  return VO_OK;
+}
+
+// ---- P3P RANSAC in front of the tracking solve (pose_ransac.hip) ---------------------------------------------------------------
+// gather -> hypotheses -> scoring -> selection (status, pose handed on) -> mask and compaction, all on the stream: the device
+// form never reads back, so it falls back to the plain frame (identity pose, every live pair) where the host form refuses.
+static int pose_ransac_camera(int rows, int cols, int z_near, int z_far, const float K[9], CamK& cam, double Kinv[9]) {
+  for (int i = 0; i < 9; ++i) cam.K[i] = K[i];
+  cam.rows = rows; cam.cols = cols; cam.z_near = z_near; cam.z_far = z_far;
+  double k[9];
+  for (int i = 0; i < 9; ++i) k[i] = K[i];
+#define VO_K(r, c) k[(r) + 3 * (c)]
+  const double c00 = VO_K(1, 1) * VO_K(2, 2) - VO_K(1, 2) * VO_K(2, 1), c01 = VO_K(1, 2) * VO_K(2, 0) - VO_K(1, 0) * VO_K(2, 2),
+               c02 = VO_K(1, 0) * VO_K(2, 1) - VO_K(1, 1) * VO_K(2, 0);
+  const double det = VO_K(0, 0) * c00 + VO_K(0, 1) * c01 + VO_K(0, 2) * c02;
+  if (!(det != 0.0) || !std::isfinite(det)) return fail(VO_ERR_INVALID_ARG, "vo_estimate_pose_ransac: K is singular");
+  // inverse = adjugate / det, column-major: Kinv(r, c) = cofactor(c, r) / det
+  Kinv[0 + 3 * 0] = c00 / det;
+  Kinv[1 + 3 * 0] = c01 / det;
+  Kinv[2 + 3 * 0] = c02 / det;
+  Kinv[0 + 3 * 1] = (VO_K(0, 2) * VO_K(2, 1) - VO_K(0, 1) * VO_K(2, 2)) / det;
+  Kinv[1 + 3 * 1] = (VO_K(0, 0) * VO_K(2, 2) - VO_K(0, 2) * VO_K(2, 0)) / det;
+  Kinv[2 + 3 * 1] = (VO_K(0, 1) * VO_K(2, 0) - VO_K(0, 0) * VO_K(2, 1)) / det;
+  Kinv[0 + 3 * 2] = (VO_K(0, 1) * VO_K(1, 2) - VO_K(0, 2) * VO_K(1, 1)) / det;
+  Kinv[1 + 3 * 2] = (VO_K(0, 2) * VO_K(1, 0) - VO_K(0, 0) * VO_K(1, 2)) / det;
+  Kinv[2 + 3 * 2] = (VO_K(0, 0) * VO_K(1, 1) - VO_K(0, 1) * VO_K(1, 0)) / det;
+#undef VO_K
+  return VO_OK;
+}
+
+int vo_estimate_pose_ransac_dev(vo_ctx* c, int rows, int cols, int z_near, int z_far, const float K[9], const float* d_world,
+                                int n_world, const float* d_meas, int n_meas, const int32_t* d_pairs, int n_max, const int* d_n,
+                                const vo_ransac_params* params, float* d_T16, int32_t* d_inl, int* d_n_inl, uint8_t* d_mask,
+                                int32_t* d_counts, int* d_status) {
+  VO_REQUIRE(c && K && d_world && d_meas && d_pairs && params && d_T16 && d_inl && d_n_inl && d_status, "null argument");
+  VO_REQUIRE(n_max >= 1, "n_max must be positive");
+  VO_REQUIRE(n_world >= 0 && n_meas >= 0, "negative point count");
+  VO_REQUIRE(aligned8(d_pairs, d_meas, d_inl), "device arrays must be 8-byte aligned");
+  if (int r = ransac_check_params(params)) return r;
+  const int H = params->n_hypotheses;
+  PoseRansacArgs a{};
+  double Kinv[9];
+  if (int r = pose_ransac_camera(rows, cols, z_near, z_far, K, a.cam, Kinv)) return r;
+  const size_t need = pose_ransac_workspace_bytes(n_max, H);
+  if (c->capturing && c->pose_ws.cap < need)
+    return fail(VO_ERR_NOT_READY, "vo_estimate_pose_ransac_dev: the workspace would have to grow inside a graph capture (make one "
+                                  "call with n_max %d and %d hypotheses before capturing)", n_max, H);
+  if (int r = set_device(c)) return r;
+  VO_HIP_CHECK(c->pose_ws.ensure(need, c->stream));
+  const CamK cam = a.cam;
+  a = pose_ransac_layout(c->pose_ws.p, n_max, H);
+  a.cam = cam;
+  for (int i = 0; i < 9; ++i) a.Kinv[i] = Kinv[i];
+  a.pairs = d_pairs; a.d_n = d_n; a.world = d_world; a.n_world = n_world; a.meas = d_meas; a.n_meas = n_meas;
+  a.seed = params->seed; a.thr2 = params->threshold_px * params->threshold_px;
+  a.out_pairs = d_inl; a.n_out = d_n_inl; a.T_out = d_T16; a.status = d_status;
+  if (d_mask) a.mask = d_mask;
+  if (d_counts) a.counts = d_counts;
+  VO_HIP_CHECK(launch_pose_ransac(c->stream, a));
+  return VO_OK;
+}
+
+int vo_estimate_pose_ransac(vo_ctx* c, int rows, int cols, int z_near, int z_far, const float K[9], const float* world, int n_world,
+                            const float* meas, int n_meas, const int32_t* pairs, int n, const vo_ransac_params* params,
+                            float T_out[16], uint8_t* inlier_mask, int* n_inliers) {
+  VO_REQUIRE(c && K && params && T_out, "null argument");
+  VO_NOT_CAPTURING(c);
+  if (n < 4) return fail(VO_ERR_INVALID_ARG, "vo_estimate_pose_ransac: fewer than 4 correspondences (%d)", n);
+  VO_REQUIRE(pairs && world && meas, "null argument");
+  VO_REQUIRE(n_world > 0 && n_meas > 0, "empty point set");
+  if (int r = ransac_check_params(params)) return r;
+  for (int i = 0; i < n; ++i)
+    if (pairs[2 * i] < 0 || pairs[2 * i] >= n_meas || pairs[2 * i + 1] < 0 || pairs[2 * i + 1] >= n_world)
+      return fail(VO_ERR_BAD_INDEX, "vo_estimate_pose_ransac: pair %d = (%d,%d) outside the point arrays", i, pairs[2 * i],
+                  pairs[2 * i + 1]);
+  if (int r = set_device(c)) return r;
+  if (int r = upload(c, c->in[0], pairs, sizeof(int32_t) * 2 * (size_t)n)) return r;
+  if (int r = upload(c, c->in[1], world, sizeof(float) * 3 * (size_t)n_world)) return r;
+  if (int r = upload(c, c->in[2], meas, sizeof(float) * 2 * (size_t)n_meas)) return r;
+  VO_HIP_CHECK(c->out[0].ensure((size_t)n, c->stream));
+  VO_HIP_CHECK(c->out[1].ensure(sizeof(int32_t) * 2 * (size_t)n, c->stream));
+  VO_HIP_CHECK(c->out[2].ensure(128, c->stream));
+  float* d_res = c->out[2].as<float>();                    // [0, 16) pose, [16] inlier count, [17] status
+  int* d_res_i = c->out[2].as<int>();
+  if (int r = vo_estimate_pose_ransac_dev(c, rows, cols, z_near, z_far, K, c->in[1].as<float>(), n_world, c->in[2].as<float>(), n_meas,
+                                          c->in[0].as<int32_t>(), n, nullptr, params, d_res, c->out[1].as<int32_t>(), d_res_i + 16,
+                                          c->out[0].as<uint8_t>(), nullptr, d_res_i + 17))
+    return r;
+  float res[18];
+  VO_HIP_CHECK(hipMemcpyAsync(res, d_res, sizeof(res), hipMemcpyDeviceToHost, c->stream));
+  VO_HIP_CHECK(hipStreamSynchronize(c->stream));
+  int cnt, st;
+  std::memcpy(&cnt, &res[16], sizeof(int));
+  std::memcpy(&st, &res[17], sizeof(int));
+  if (st == VO_POSE_RANSAC_BAD_INDEX) return fail(VO_ERR_BAD_INDEX, "vo_estimate_pose_ransac: a pair indexes outside the point arrays");
+  if (st == VO_POSE_RANSAC_FEW_PAIRS) return fail(VO_ERR_INVALID_ARG, "vo_estimate_pose_ransac: fewer than 4 correspondences");
+  if (st == VO_POSE_RANSAC_NO_HYPOTHESIS)
+    return fail(VO_ERR_INVALID_ARG, "vo_estimate_pose_ransac: no valid hypothesis among %d", params->n_hypotheses);
+  if (st == VO_POSE_RANSAC_FEW_INLIERS)
+    return fail(VO_ERR_INVALID_ARG, "vo_estimate_pose_ransac: the best hypothesis has %d inlier(s), fewer than 6", cnt);
+  if (st != VO_POSE_RANSAC_OK) return fail(VO_ERR_HIP, "vo_estimate_pose_ransac: unexpected status %d", st);
+  std::memcpy(T_out, res, sizeof(float) * 16);
+  if (inlier_mask) {
+    VO_HIP_CHECK(hipMemcpyAsync(inlier_mask, c->out[0].p, (size_t)n, hipMemcpyDeviceToHost, c->stream));
+    VO_HIP_CHECK(hipStreamSynchronize(c->stream));
+  }
+  if (n_inliers) *n_inliers = cnt;
   return VO_OK;
 }
 

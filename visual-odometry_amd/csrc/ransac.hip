@@ -16,6 +16,7 @@
 // Counts are integers: nothing here depends on scheduling.  The refit of the winner's inliers is vo_estimate_transform_dev
 // itself (capi.hip).
 #include "vo_internal.h"
+#include "ransac_common.h"
 #include "../../include/vo/linalg.hpp"
 
 namespace vo {
@@ -24,21 +25,6 @@ constexpr int RB = 256;            // threads per workgroup (gather, scoring, ma
 constexpr int RANSAC_PTS = 4;      // correspondences per thread of the scoring pass
 constexpr int RANSAC_HB = 64;      // hypotheses per scoring workgroup: one per lane of the count register
 constexpr int RANSAC_FS = 12;      // floats per hypothesis: F row-major in [0, 9), [9] = 1 valid / 0 invalid
-
-__device__ __forceinline__ int ransac_rows(const int* d_n, int n_max) {
-  int n = n_max;
-  if (d_n) { const int m = *d_n; n = m < n ? (m < 0 ? 0 : m) : n; }
-  return n;
-}
-
-// the sample rule of vo_hip.h (vo_estimate_transform_ransac), bit for bit
-__device__ __forceinline__ unsigned long long splitmix64(unsigned long long x) {
-  x += 0x9E3779B97F4A7C15ull;
-  unsigned long long z = x;
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  return z ^ (z >> 31);
-}
 
 // Sampson distance below the threshold: e^2 < thr^2 * den, e = x1^T F x2, den = (F x2)_0^2 + (F x2)_1^2 + (F^T x1)_0^2 +
 // (F^T x1)_1^2 -- d^2 = e^2 / den < thr^2 without the division; den = 0 or a NaN anywhere never passes
@@ -81,8 +67,7 @@ __global__ __launch_bounds__(64) void ransac_hyp_kernel(RansacArgs a) {
   int k = 0;
   if (n >= 8)
     for (unsigned j = 0; j < 64 && k < 8; ++j) {
-      const unsigned long long r = splitmix64(a.seed ^ (((unsigned long long)h << 20) | j)) >> 32;
-      const int v = (int)((r * (unsigned long long)n) >> 32);
+      const int v = ransac_draw(a.seed, h, j, n);
       bool fresh = true;
       for (int q = 0; q < k; ++q) fresh &= idx[q] != v;
       if (fresh) idx[k++] = v;
@@ -191,43 +176,11 @@ __global__ __launch_bounds__(RB) void ransac_score_kernel(RansacArgs a) {
 }
 
 __global__ __launch_bounds__(1024) void ransac_select_kernel(RansacArgs a) {
-  __shared__ unsigned long long s_best[1024 / 64];
-  unsigned long long best = 0;                   // 0: no valid hypothesis (a valid one has a key > 0: h < 2^16)
-  for (int h = threadIdx.x; h < a.n_hyp; h += 1024) {
-    if (a.F[(size_t)h * RANSAC_FS + 9] == 0.f) { a.counts[h] = -1; continue; }
-    const unsigned long long key = ((unsigned long long)(unsigned)a.counts[h] << 32) | (0xFFFFFFFFull - (unsigned)h);
-    if (key > best) best = key;
-  }
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) {
-    const unsigned long long o = __shfl_xor(best, d);
-    if (o > best) best = o;
-  }
-  if ((threadIdx.x & 63) == 0) s_best[threadIdx.x >> 6] = best;
-  __syncthreads();
+  const unsigned long long best = ransac_select_best(a.n_hyp, a.F + 9, RANSAC_FS, a.counts);
   if (threadIdx.x == 0) {
-    for (int w = 0; w < 1024 / 64; ++w) if (s_best[w] > best) best = s_best[w];
     a.info[2] = best ? (int)(0xFFFFFFFFull - (best & 0xFFFFFFFFull)) : -1;
     a.info[3] = best ? (int)(best >> 32) : 0;
   }
-}
-
-// exclusive rank of `flag` inside the workgroup (as geom.hip's block_rank); total = flags set
-__device__ __forceinline__ int ransac_rank(bool flag, int* s_wave, int& total) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const unsigned long long m = __ballot(flag);
-  const int before = __popcll(m & ((1ull << lane) - 1ull));
-  if (lane == 0) s_wave[wave] = __popcll(m);
-  __syncthreads();
-  int off = 0, tot = 0;
-#pragma unroll
-  for (int w = 0; w < RB / 64; ++w) {
-    const int c = s_wave[w];
-    if (w < wave) off += c;
-    tot += c;
-  }
-  total = tot;
-  return off + before;
 }
 
 __global__ __launch_bounds__(RB) void ransac_mask_kernel(RansacArgs a) {
@@ -245,7 +198,7 @@ __global__ __launch_bounds__(RB) void ransac_mask_kernel(RansacArgs a) {
   }
   if (i < a.n_max) a.mask[i] = in ? 1 : 0;
   int total;
-  ransac_rank(in, s_wave, total);
+  ransac_rank<RB>(in, s_wave, total);
   if (threadIdx.x == 0) a.blk[blockIdx.x] = total;
 }
 
@@ -254,7 +207,7 @@ __global__ __launch_bounds__(RB) void ransac_scatter_kernel(RansacArgs a) {
   const int i = blockIdx.x * RB + threadIdx.x;
   const bool in = i < a.n_max && a.mask[i];
   int total;
-  const int r = ransac_rank(in, s_wave, total);
+  const int r = ransac_rank<RB>(in, s_wave, total);
   if (in) reinterpret_cast<int2*>(a.out_pairs)[a.blk[blockIdx.x] + r] = reinterpret_cast<const int2*>(a.pairs)[i];
 }
 

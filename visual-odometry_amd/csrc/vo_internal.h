@@ -342,4 +342,29 @@ size_t ransac_workspace_bytes(int n_max, int n_hyp);
 RansacArgs ransac_layout(void* ws, int n_max, int n_hyp);
 hipError_t launch_ransac(hipStream_t st, const RansacArgs& a);
 
+// ---- P3P RANSAC in front of the tracking solve (pose_ransac.hip) ------------------------------------------
+struct PoseRansacArgs {
+  const int32_t* pairs; int n_max; const int* d_n;   // (meas_idx, world_idx)
+  const float* world; int n_world;
+  const float* meas; int n_meas;
+  CamK cam;                   // K (float, column-major), image size and depth range of the projection gates
+  double Kinv[9];             // K^-1 in double, column-major
+  int n_hyp; unsigned long long seed; float thr2;
+  int* info;                  // [0] live pairs  [1] pairs with a bad index  [2] winner (-1: none)  [3] its count  [4] status
+  float4* pts;                // [n_max] (world x, y, z, measured u) of the live pairs
+  float* pv;                  // [n_max] measured v
+  float* poses;               // [n_hyp][16]: R column-major [0, 9), t [9, 12), [12] = 1 valid / 0 invalid
+  int* counts;                // [n_hyp] inliers per hypothesis, -1 invalid
+  uint8_t* mask;              // [n_max] the pairs handed on: the winner's inliers, or every live pair on a fallback
+  int* blk;                   // per-workgroup counts of the compaction
+  int32_t* out_pairs;         // [n_max][2] the pairs handed on, in their original order
+  int* n_out;                 // their count
+  float* T_out;               // [16] column-major: the winner's pose, or the identity on a fallback
+  int* status;                // the status code (as info[4]), or null
+};
+size_t pose_ransac_workspace_bytes(int n_max, int n_hyp);
+// the workspace's arrays; the caller fills in the inputs and the outputs and may point counts / mask elsewhere
+PoseRansacArgs pose_ransac_layout(void* ws, int n_max, int n_hyp);
+hipError_t launch_pose_ransac(hipStream_t st, const PoseRansacArgs& a);
+
 }  // namespace vo

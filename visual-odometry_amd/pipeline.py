@@ -386,7 +386,7 @@ class SequencePipeline:
     def __init__(self, ctx: Context, seq: dict, n_iters: int = 100, kernel_threshold: float = 10000.0,
                  keep_appearance: bool = False, matches: list | None = None, overlap_match: bool = False, exact: bool = False,
                  prematch: bool = False, keep_map: bool = False, map_capacity: int | None = None,
-                 init_ransac: dict | None = None):
+                 init_ransac: dict | None = None, track_ransac: dict | None = None):
         """prematch: the matcher depends on the appearances alone, so when the whole sequence is on hand -- as it
         is for vo_complete, which reads its measurement files from a directory -- all F-1 consecutive pairs are matched by ONE
         vo_match_appearances_batch_dev call at start() (frames of different sizes, per-frame tree choice as in the single
@@ -402,7 +402,11 @@ class SequencePipeline:
         (1.35 k vs 1.52 k frames/s): the matcher's waves take issue slots from the latency-bound solver
         rounds, so it is off by default and kept as a measured option.
         init_ransac: initialise through vo_estimate_transform_ransac_dev instead (robust to mismatched pairs), e.g.
-        dict(threshold_px=1.0, n_hypotheses=2048, seed=0) -- missing keys take those values; nothing else changes."""
+        dict(threshold_px=1.0, n_hypotheses=2048, seed=0) -- missing keys take those values; nothing else changes.
+        track_ransac: every frame t >= 2 runs vo_estimate_pose_ransac_dev on its joined pairs first, and the solve starts from
+        the winner's pose on the winner's inliers, e.g. dict(threshold_px=1.0, n_hypotheses=2048, seed=0) -- missing keys take
+        those values.  A frame that falls back (fewer than 4 pairs, no valid hypothesis, fewer than 6 inliers) is the plain
+        frame; track_stats() reads each frame's status and pair count after run()."""
         self.ctx, self.lib = ctx, ctx.lib
         self.n_iters = n_iters
         fr = seq["frames"]
@@ -470,6 +474,14 @@ class SequencePipeline:
             from .api import RansacParams
             r = dict(dict(threshold_px=1.0, n_hypotheses=2048, seed=0), **init_ransac)
             self.ransac = RansacParams(int(r["n_hypotheses"]), float(r["threshold_px"]), int(r["seed"]) & 0xFFFFFFFFFFFFFFFF)
+        self.track = None
+        if track_ransac is not None:
+            from .api import RansacParams
+            r = dict(dict(threshold_px=1.0, n_hypotheses=2048, seed=0), **track_ransac)
+            self.track = RansacParams(int(r["n_hypotheses"]), float(r["threshold_px"]), int(r["seed"]) & 0xFFFFFFFFFFFFFFFF)
+            self.d_track_T, self.d_track_pairs = a(64), a(cap * 8)
+            self.d_track_st = a(2 * F * 4)                                      # [t] = (status, pairs handed to the solve)
+            ctx.h2d(self.d_track_st, np.zeros((F, 2), np.int32))
 
     # device addresses of frame t's inputs / outputs
     def _pts(self, t): return C.c_void_p(self.d_pts + 8 * int(self.off[t]))
@@ -567,9 +579,21 @@ class SequencePipeline:
         # the capacity (not the live count) is what sizes the solver's grid: the same graph serves every frame
         _chk(self.lib.vo_picp_set_points_dev(self.solver, C.c_void_p(self.d_model_t), C.c_int(self.cap), self._pts(t),
                                              C.c_int(self.n[t])))
-        _chk(self.lib.vo_picp_set_pose_dev(self.solver, C.c_void_p(self.d_ident)))
-        _chk(self.lib.vo_picp_solve_dev(self.solver, C.c_void_p(self.d_j), C.c_int(self.cap), self._cnt(t, 1),
-                                        C.c_int(0), C.c_int(self.n_iters)))
+        if self.track is not None:
+            # the winner's pose and inliers, or (fallback) the identity and every joined pair: the plain frame
+            st = C.c_void_p(self.d_track_st + 8 * t)
+            n_in = C.c_void_p(self.d_track_st + 8 * t + 4)
+            _chk(self.lib.vo_estimate_pose_ransac_dev(self.ctx.h, *map(C.c_int, self.cam), _ptr(self.K), C.c_void_p(self.d_model_t),
+                                                      C.c_int(self.cap), self._pts(t), C.c_int(self.n[t]), C.c_void_p(self.d_j),
+                                                      C.c_int(self.cap), self._cnt(t, 1), C.byref(self.track),
+                                                      C.c_void_p(self.d_track_T), C.c_void_p(self.d_track_pairs), n_in, None, None, st))
+            _chk(self.lib.vo_picp_set_pose_dev(self.solver, C.c_void_p(self.d_track_T)))
+            _chk(self.lib.vo_picp_solve_dev(self.solver, C.c_void_p(self.d_track_pairs), C.c_int(self.cap), n_in,
+                                            C.c_int(0), C.c_int(self.n_iters)))
+        else:
+            _chk(self.lib.vo_picp_set_pose_dev(self.solver, C.c_void_p(self.d_ident)))
+            _chk(self.lib.vo_picp_solve_dev(self.solver, C.c_void_p(self.d_j), C.c_int(self.cap), self._cnt(t, 1),
+                                            C.c_int(0), C.c_int(self.n_iters)))
         _chk(self.lib.vo_picp_get_pose_dev(self.solver, C.c_void_p(self.d_traj + 64 * t)))
         self._triangulate(t, None)
         if self.map is not None:                          # vo_complete.cpp:175-176
@@ -612,6 +636,15 @@ class SequencePipeline:
             c[1:, 0] = m
         return c
 
+    def track_stats(self):
+        """track_ransac: (status (F,), pairs handed to the solve (F,)) per frame -- VO_POSE_RANSAC_* (0: tracked from the
+        winner; nonzero: the plain frame) and the winner's inlier count (every joined pair on a fallback); frames 0 and 1
+        are 0"""
+        assert self.track is not None, "SequencePipeline(track_ransac=...) only"
+        c = np.zeros((self.F, 2), np.int32)
+        self.ctx.d2h(c, self.d_track_st)
+        return c[:, 0].copy(), c[:, 1].copy()
+
     def cloud(self, t):
         """triangulated points of frame t (in the frame of camera t), their (idx in frame t, k) pairs and,
         when kept, appearances"""
@@ -646,5 +679,6 @@ class SequencePipeline:
         for d in (self.d_pts, self.d_app, self.d_m, self.d_j, self.d_model_t, self.d_tri_xyz, self.d_tri_pairs,
                   self.d_counts, self.d_traj, self.d_ident) + ((self.d_tri_app,) if self.d_tri_app else ()) + \
                 ((self.pre,) if self.pre is not None else ()) + \
-                ((self.d_app_pad, self.d_n_all, self.d_pm, self.d_pm_cnt) if self.prematch else ()):
+                ((self.d_app_pad, self.d_n_all, self.d_pm, self.d_pm_cnt) if self.prematch else ()) + \
+                ((self.d_track_T, self.d_track_pairs, self.d_track_st) if self.track is not None else ()):
             self.ctx.free(d)
