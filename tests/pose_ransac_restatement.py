@@ -80,14 +80,15 @@ def degenerate(P):
     return not np.linalg.norm(np.cross(e12, e13)) > 1e-9 * np.linalg.norm(e12) * np.linalg.norm(e13)
 
 
-def hypothesis(K, world4, uv4):
-    """the hypothesis of one 4-point sample: (R, t) in float64, or None when invalid"""
+def hypothesis(K, world4, uv4, n_solutions=False):
+    """the hypothesis of one 4-point sample: (R, t) in float64, or None when invalid (n_solutions: also the number of
+    admissible solutions the 4th point chose among)"""
     world4 = np.asarray(world4, np.float64)
     if degenerate(world4[:3]):
-        return None
+        return (None, 0) if n_solutions else None
     K64 = np.asarray(K, np.float32).astype(np.float64)
-    best = None
-    for v, R, t in p3p(K, world4[:3], uv4[:3]):
+    best, sols = None, p3p(K, world4[:3], uv4[:3])
+    for v, R, t in sols:
         q = R @ world4[3] + t
         h = K64 @ q
         err = np.sum((h[:2] / h[2] - uv4[3]) ** 2) if q[2] > 0 else np.inf
@@ -95,7 +96,8 @@ def hypothesis(K, world4, uv4):
             err = np.inf
         if best is None or err < best[0] or (err == best[0] and v < best[1]):
             best = (err, v, R, t)
-    return None if best is None else (best[2], best[3])
+    r = None if best is None else (best[2], best[3])
+    return (r, len(sols)) if n_solutions else r
 
 
 def hypotheses(K, world, meas, pairs, n_hyp, seed):
@@ -111,6 +113,50 @@ def hypotheses(K, world, meas, pairs, n_hyp, seed):
             continue
         T[h, :3, :3], T[h, :3, 3] = r
     return T.astype(np.float32).astype(np.float64), valid, idx
+
+
+def hypotheses_at(K, world, meas, pairs, hs, n_hyp, seed):
+    """hypotheses() restated for the hypotheses hs of n_hyp only: (poses (len(hs), 4, 4), valid, sample indices, number of
+    admissible solutions) -- equal to hypotheses()[.][hs]"""
+    pairs = np.asarray(pairs, np.int64)
+    hs = np.asarray(hs, np.int64)
+    assert hs.min() >= 0 and hs.max() < n_hyp
+    d = RR.draws(seed, n_hyp, len(pairs))[hs]
+    idx = np.zeros((len(hs), 4), np.int64)
+    valid = np.zeros(len(hs), bool)
+    nsol = np.zeros(len(hs), np.int64)
+    T = np.tile(np.eye(4), (len(hs), 1, 1))
+    for k in range(len(hs)):
+        _, first = np.unique(d[k], return_index=True)
+        first = np.sort(first)
+        if len(first) < 4:
+            continue
+        idx[k] = d[k, first[:4]]
+        p = pairs[idx[k]]
+        r, nsol[k] = hypothesis(K, np.asarray(world, np.float64)[p[:, 1]], np.asarray(meas, np.float64)[p[:, 0]], True)
+        if r is not None:
+            valid[k] = True
+            T[k, :3, :3], T[k, :3, 3] = r
+    return T.astype(np.float32).astype(np.float64), valid, idx, nsol
+
+
+def sq_errors(K, T, world, meas, pairs, rows, cols, z_near, z_far):
+    """the squared reprojection error of every pair under one pose, +inf where Camera::projectPoint's gates fail and NaN
+    where the error is NaN: (n,)"""
+    pairs = np.asarray(pairs, np.int64)
+    _, uv_ok, pc, uv = _project(K, T, np.asarray(world, np.float64)[pairs[:, 1]], rows, cols, z_near, z_far)
+    e = uv - np.asarray(meas, np.float64)[pairs[:, 0]]
+    with np.errstate(invalid="ignore", over="ignore"):
+        return np.where(uv_ok, (e * e).sum(1), np.inf)
+
+
+def error_bands(K, T, world, meas, pairs, thr_px, delta, rows, cols, z_near, z_far):
+    """for one pose: (exact count, lower bound, upper bound) -- the pairs inside the gates with e^2 < thr^2, < thr^2 (1 - delta)
+    and < thr^2 (1 + delta)"""
+    e2 = sq_errors(K, T, world, meas, pairs, rows, cols, z_near, z_far)
+    thr2 = float(thr_px) ** 2
+    with np.errstate(invalid="ignore"):
+        return tuple(int((e2 < thr2 * f).sum()) for f in (1.0, 1.0 - delta, 1.0 + delta))
 
 
 def inliers(K, T, world, meas, pairs, thr_px, rows, cols, z_near, z_far):
@@ -173,3 +219,83 @@ def tracking_problem(vo, n, seed=2001, noise_px=0.5, frac=0.0, max_angle=0.05, m
     pairs[hit, 1] = rng.integers(0, len(fp["model"]), int(hit.sum()))
     bad = pairs[:, 1] != clean[:, 1]
     return fp, fp["model"], fp["cur_pts"], pairs, bad, clean
+
+
+# ---- constructed minimal problems (geometries random samples never reach) ---------------------------------------------------
+K_WIDE = np.array([[100.0, 0.0, 320.0], [0.0, 100.0, 240.0], [0.0, 0.0, 1.0]], np.float32)     # +-73 degrees across 640 px
+
+
+def _pixels(K, Q):
+    h = np.asarray(Q, np.float64) @ np.asarray(K, np.float64).T
+    return (h[:, :2] / h[:, 2:3]).astype(np.float32)
+
+
+def quartic_terms(K, world4, uv4):
+    """Grunert's quartic of the sample's first three points, its depressed form's p, q, r (Ferrari: x = v + B/4) and the
+    roots' (real parts, imaginary parts) -- what the constructed cases claim properties of"""
+    A, _ = grunert_coefficients(np.asarray(world4, np.float64)[:3], bearings(K, np.asarray(uv4)[:3]))
+    B, C, D, E = A[1] / A[0], A[2] / A[0], A[3] / A[0], A[4] / A[0]
+    p = C - 3 * B * B / 8
+    q = D - B * C / 2 + B ** 3 / 8
+    r = E - B * D / 4 + B * B * C / 16 - 3 * B ** 4 / 256
+    roots = np.roots(A)
+    return dict(A=A, p=p, q=q, r=r, scale=max(abs(p), abs(r), 1.0), re=roots.real, im=roots.imag)
+
+
+def constructed(name):
+    """one 4-point sample: (K, world4 (4, 3) float32, uv4 (4, 2) float32).  World = camera frame (T = identity) unless said.
+      collinear_above / collinear_below  |(P2-P1) x (P3-P1)| = (1 +- 1e-3) 1e-9 |P2-P1| |P3-P1|, exactly in double
+      danger_cylinder                    the camera centre on the cylinder through the triangle's circumcircle: a double root
+      near_cylinder                      the centre 1e-4 of the radius outside it: two roots close together
+      biquadratic                        K_WIDE and bearings with j3 . j1 = j3 . j2 = 0 to rounding: A3 = A1 = 0, q = 0
+      tie_behind                         a 4th point behind the camera under every solution: +inf each, the smaller v wins
+      behind_one                         a 4th point behind the camera under one solution and in front under another"""
+    K = np.array([[180.0, 0.0, 320.0], [0.0, 180.0, 240.0], [0.0, 0.0, 1.0]], np.float32)      # synth.K_REF
+    if name in ("collinear_above", "collinear_below"):
+        f = 1 + 1e-3 if name == "collinear_above" else 1 - 1e-3
+        dy = np.float32(2e-9 * f)            # e12 = (1, 0, 0), e13 = (2, dy, 0): |cross| = dy, |e12| |e13| = 2 in double
+        W = np.array([[-1, 0, 5], [0, 0, 5], [1, dy, 5], [0.3, -0.4, 6]], np.float32)
+        return K, W, _pixels(K, W)
+    if name in ("danger_cylinder", "near_cylinder"):
+        rad, th = 1.5, np.radians([0.0, 100.0, 220.0])
+        W = np.array([[rad * np.cos(a), rad * np.sin(a), 5.0] for a in th] + [[0.3, -0.2, 6.0]], np.float32)
+        k = 1.0 if name == "danger_cylinder" else 1.0 + 1e-4
+        C = np.array([rad * k * np.cos(np.radians(300.0)), rad * k * np.sin(np.radians(300.0)), 0.0])
+        return K, W, _pixels(K, W.astype(np.float64) - C)
+    if name == "biquadratic":
+        K = K_WIDE
+        uv = np.array([[220, 240], [320, 140], [420, 340], [330, 250]], np.float32)
+        Q = bearings(K, uv) * np.array([3.0, 4.0, 5.0, 4.0])[:, None]
+        return K, Q.astype(np.float32), uv
+    if name in ("tie_behind", "behind_one"):
+        W = np.array([[-1.0, -0.5, 4.0], [1.2, -0.3, 5.0], [0.1, 0.9, 4.5]], np.float32)
+        uv = _pixels(K, W)
+        sols = p3p(K, W, uv)
+        (_, Ra, ta), (_, Rb, tb) = sols[0], sols[1]
+        rng = np.random.default_rng(0)
+        for _ in range(100000):
+            X = rng.uniform(-8, 8, 3).astype(np.float32).astype(np.float64)
+            za, zb = (Ra @ X + ta)[2], (Rb @ X + tb)[2]
+            if za < -0.5 and (zb < -0.5 if name == "tie_behind" else zb > 0.5):
+                break
+        h = np.asarray(K, np.float64) @ (Ra @ X + ta)
+        return K, np.vstack([W, X]).astype(np.float32), np.vstack([uv, h[:2] / h[2]]).astype(np.float32)
+    raise KeyError(name)
+
+
+def embedded(K, world4, uv4, seed, n=12, rows=480, cols=640):
+    """an n-pair problem whose hypothesis 0 (of 1, seed) draws the sample in its order, the other pairs inliers of the
+    restatement's hypothesis of it (or of the identity when it is invalid), inside the image: (world, meas, pairs)"""
+    idx = samples4(seed, 1, n)[0][0]
+    r = hypothesis(K, world4, uv4)
+    R_, t_ = (np.eye(3), np.zeros(3)) if r is None else r
+    rng = np.random.default_rng(seed)
+    world = np.zeros((n, 3), np.float32)
+    meas = np.zeros((n, 2), np.float32)
+    rest = [i for i in range(n) if i not in idx]
+    Q = np.stack([rng.uniform(-0.6, 0.6, len(rest)), rng.uniform(-0.5, 0.5, len(rest)), np.ones(len(rest))], 1)
+    Q *= rng.uniform(2, 8, len(rest))[:, None]
+    world[rest] = ((Q - t_) @ R_).astype(np.float32)                      # R^T (Q - t)
+    meas[rest] = _pixels(K, world[rest].astype(np.float64) @ R_.T + t_)
+    world[idx], meas[idx] = world4, uv4
+    return world, meas, np.stack([np.arange(n), np.arange(n)], 1).astype(np.int32)

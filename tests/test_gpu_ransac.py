@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 import ransac_restatement as R
+from ransac_dev import _p, dev_call as _dev_call
 from oracle import vo_pipeline as vp
 
 pytestmark = pytest.mark.gpu
@@ -21,41 +22,10 @@ TOL_ROT, TOL_DIR = 1e-2, 0.25
 NOISE_PX, THR_PX = 0.25, 1.0
 
 
-def _p(a):
-    return a.ctypes.data_as(C.c_void_p)
-
-
 def _corrupted(vo, n, frac, seed=2000):
     fp = vo.synth.frame_pair(n, seed=seed, noise_px=NOISE_PX)
     pairs, bad = R.corrupt(fp["gt_matches"], len(fp["cur_pts"]), frac)
     return fp, pairs, bad
-
-
-def _dev_call(vo, ctx, K, pairs, p1, p2, n_hyp=2048, thr=THR_PX, seed=0, n_live=None):
-    """the _dev form from device copies: (status, X, mask, counts, n_inliers)"""
-    pairs = np.ascontiguousarray(pairs, np.int32).reshape(-1, 2)
-    p1 = np.ascontiguousarray(p1, np.float32); p2 = np.ascontiguousarray(p2, np.float32)
-    n = len(pairs)
-    d_pairs, d_p1, d_p2 = ctx.alloc(max(pairs.nbytes, 8)), ctx.alloc(p1.nbytes), ctx.alloc(p2.nbytes)
-    d_mask, d_counts, d_n = ctx.alloc(max(n, 8)), ctx.alloc(4 * n_hyp), ctx.alloc(8)
-    try:
-        ctx.h2d(d_pairs, pairs); ctx.h2d(d_p1, p1); ctx.h2d(d_p2, p2)
-        if n_live is not None:
-            ctx.h2d(d_n, np.array([n_live], np.int32))
-        X = np.zeros(16, np.float32)
-        n_in = C.c_int(-7)
-        prm = vo.RansacParams(n_hyp, thr, seed)
-        rc = ctx.lib.vo_estimate_transform_ransac_dev(
-            ctx.h, _p(np.ascontiguousarray(np.asarray(K, np.float32).T).ravel()), C.c_void_p(d_pairs), C.c_int(n),
-            C.c_void_p(d_n) if n_live is not None else None, C.c_void_p(d_p1), C.c_int(len(p1)), C.c_void_p(d_p2),
-            C.c_int(len(p2)), C.byref(prm), _p(X), C.c_void_p(d_mask), C.c_void_p(d_counts), C.byref(n_in))
-        mask = np.zeros(n, np.uint8); counts = np.zeros(n_hyp, np.int32)
-        if rc == 0:
-            ctx.d2h(mask, d_mask); ctx.d2h(counts, d_counts)
-        return rc, X.reshape(4, 4).T.copy(), mask, counts, n_in.value
-    finally:
-        for d in (d_pairs, d_p1, d_p2, d_mask, d_counts, d_n):
-            ctx.free(d)
 
 
 def test_scoring_matches_restatement(vo, ctx):

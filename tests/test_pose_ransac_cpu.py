@@ -104,3 +104,74 @@ def test_library_exports_the_pose_ransac_entry_points(vo):
     for s in ("VO_POSE_RANSAC_OK", "VO_POSE_RANSAC_FEW_PAIRS", "VO_POSE_RANSAC_NO_HYPOTHESIS", "VO_POSE_RANSAC_FEW_INLIERS",
               "VO_POSE_RANSAC_BAD_INDEX", "Grunert", "first 4"):
         assert s in hdr, s
+
+
+def test_subset_restatement_and_error_bands(vo):
+    """hypotheses_at() restates the hypotheses it is given exactly as hypotheses() does all of them; error_bands bracket
+    the exact count, which is inliers()'s"""
+    fp, world, meas, pairs, bad, clean = P.tracking_problem(vo, 400, seed=4300, noise_px=0.5, frac=0.3, max_angle=0.3, max_t=0.5)
+    K = fp["K"]
+    T, valid, idx = P.hypotheses(K, world, meas, pairs, 200, 9)
+    hs = np.array([0, 63, 64, 127, 128, 199, 17, 101])
+    Ts, vs, ids, nsol = P.hypotheses_at(K, world, meas, pairs, hs, 200, 9)
+    assert np.array_equal(Ts, T[hs]) and np.array_equal(vs, valid[hs]) and np.array_equal(ids, idx[hs])
+    assert (nsol[vs] >= 1).all() and (nsol[~vs] == 0).all()
+    for h in np.nonzero(valid)[0][:40]:
+        exact, lo, hi = P.error_bands(K, T[h], world, meas, pairs, THR_PX, 1e-2, 480, 640, 0, 10)
+        assert exact == int(P.inliers(K, T[h], world, meas, pairs, THR_PX, 480, 640, 0, 10).sum()) and lo <= exact <= hi
+    e2 = P.sq_errors(K, T[0], world, meas, pairs, 480, 640, 0, 10)
+    assert e2.shape == (len(pairs),) and (e2 >= 0).all()
+
+
+def test_constructed_samples_have_their_properties():
+    def ratio(W):
+        W = np.asarray(W, np.float64)
+        e12, e13 = W[1] - W[0], W[2] - W[0]
+        return np.linalg.norm(np.cross(e12, e13)) / (np.linalg.norm(e12) * np.linalg.norm(e13))
+
+    for name, f in (("collinear_above", 1 + 1e-3), ("collinear_below", 1 - 1e-3)):
+        K, W, uv = P.constructed(name)
+        assert abs(ratio(W) / 1e-9 - f) < 1e-6 and P.degenerate(W[:3]) == (f < 1)
+    # on the danger cylinder three roots meet (split by the float32 pixels); 1e-4 of the radius outside, two lie close
+    for name in ("danger_cylinder", "near_cylinder"):
+        qt = P.quartic_terms(*P.constructed(name))
+        r = qt["re"] + 1j * qt["im"]
+        close = sorted(abs(r[i] - r[j]) for i in range(4) for j in range(i + 1, 4))
+        assert close[1] < 2e-3 and close[-1] > 0.05, close
+    # wide-angle K, j3 orthogonal to j1 and j2: A3 and A1 vanish to rounding, so q = 0 (the biquadratic branch)
+    qt = P.quartic_terms(*P.constructed("biquadratic"))
+    assert abs(qt["q"]) < 1e-12 * qt["scale"] and abs(qt["A"][1]) < 1e-12 and abs(qt["A"][3]) < 1e-12
+    # the 4th point behind the camera under every solution: all errors +inf, the smaller v chosen
+    K, W, uv = P.constructed("tie_behind")
+    sols = P.p3p(K, W[:3], uv[:3])
+    assert len(sols) >= 2 and all((R_ @ W[3] + t_)[2] <= 0 for _, R_, t_ in sols)
+    v_min = min(sols, key=lambda s: s[0])
+    R_, t_ = P.hypothesis(K, W, uv)
+    assert np.array_equal(R_, v_min[1]) and np.array_equal(t_, v_min[2])
+    # behind one solution, in front of another: the one in front wins although the other reprojects it exactly
+    K, W, uv = P.constructed("behind_one")
+    sols = P.p3p(K, W[:3], uv[:3])
+    z = [(R_ @ W[3] + t_)[2] for _, R_, t_ in sols]
+    assert min(z) < 0 < max(z)
+    R_, t_ = P.hypothesis(K, W, uv)
+    assert (R_ @ W[3] + t_)[2] > 0
+    # embedded: hypothesis 0 of seed 77 draws the sample in its order
+    world, meas, pairs = P.embedded(K, W, uv, seed=77)
+    idx = P.samples4(77, 1, len(pairs))[0][0]
+    assert np.array_equal(world[idx], W) and np.array_equal(meas[idx], uv)
+
+
+def test_tie_cases_are_ties(vo):
+    """the hard-coded tie cases of tests/test_gpu_ransac_sizes.py, checked from the float64 side alone"""
+    import test_gpu_ransac_sizes as S
+    import ransac_restatement as R
+    fp = vo.synth.frame_pair(300000, seed=4200, noise_px=0.25)
+    pairs, _ = R.corrupt(fp["gt_matches"], len(fp["cur_pts"]), 0.3, seed=4)
+    t = S.EPI_TIE
+    pr, p1, p2 = pairs[:t["n"]], fp["ref_pts"], fp["cur_pts"]
+    idx, valid = R.samples(t["seed"], t["n_hyp"], t["n"])
+    F, valid = R.minimal_fits(pr, p1, p2, idx, valid)
+    exact, lo, hi = R.sampson_bands(F, valid, pr, p1, p2, S.EPI_THR, S.DELTA)
+    tied = np.nonzero(exact == exact.max())[0]
+    d2, band = R.sampson_band(F[tied], pr, p1, p2, S.EPI_THR, S.DELTA)
+    assert tied.tolist() == t["tied"] and not band.any() and not np.array_equal(d2[0] < 1, d2[-1] < 1)

@@ -84,3 +84,37 @@ def test_library_exports_the_ransac_entry_points(vo):
     assert C.sizeof(vo.RansacParams) == 16 and vo.RansacParams.seed.offset == 8
     hdr = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "vo_hip.h")).read()
     assert "0x9E3779B97F4A7C15" in hdr and "typedef struct vo_ransac_params" in hdr
+
+
+def test_float64_fit_helpers_restate_the_oracle(vo, o32):
+    """fundamental() / estimate_transform() (thin SVD, maxima by image_maxima) are vp.estimate_fundamental /
+    vp.estimate_transform on finite images, and image_maxima skips NaN and values <= 0"""
+    from oracle import vo_pipeline as vp
+    fp = vo.synth.frame_pair(1500, seed=4100)
+    pairs, _ = R.corrupt(fp["gt_matches"], len(fp["cur_pts"]), 0.05, seed=2)
+    p1, p2 = fp["ref_pts"], fp["cur_pts"]
+    F, F_o = R.fundamental(pairs, p1, p2), vp.estimate_fundamental(pairs, p1, p2)
+    F, F_o = F / np.linalg.norm(F), F_o / np.linalg.norm(F_o)
+    assert min(np.abs(F - F_o).max(), np.abs(F + F_o).max()) < 1e-12
+    X = R.estimate_transform(o32, fp["K"], pairs, p1, p2)
+    assert np.abs(X - vp.estimate_transform(o32, fp["K"], pairs, p1, p2)).max() < 1e-6
+    assert np.abs(R.pose_8point(fp["K"], pairs, p1, p2, F=R.fundamental(pairs, p1, p2)) - X).max() < 1e-6
+    p = np.array([[np.nan, 3], [-5, np.nan], [2, -1], [1, 1]], np.float32)
+    assert R.image_maxima(p) == (2, 3) and R.image_maxima(-np.abs(p)) == (0, 0)
+
+
+def test_sampson_bands_bracket_the_exact_count(vo):
+    fp = vo.synth.frame_pair(1500, seed=4200, noise_px=NOISE_PX)
+    pairs, _ = R.corrupt(fp["gt_matches"], len(fp["cur_pts"]), 0.3, seed=4)
+    p1, p2 = fp["ref_pts"], fp["cur_pts"]
+    counts, win, mask, F = R.ransac(pairs, p1, p2, THR_PX, 300, 5)
+    idx, valid = R.samples(5, 300, len(pairs))
+    F2, valid2, cond = R.minimal_fits(pairs, p1, p2, idx, valid, with_conditioning=True)
+    assert np.array_equal(F, F2) and np.array_equal(valid2, counts >= 0) and (cond[valid2] > 0).all()
+    exact, lo, hi = R.sampson_bands(F2, valid2, pairs, p1, p2, THR_PX, 1e-2, chunk=7)
+    assert np.array_equal(exact, counts) and (lo <= exact).all() and (exact <= hi).all() and (hi > lo).any()
+    # the band grows with delta, and holds only pairs near the threshold
+    d2, band0 = R.sampson_band(F2[win:win + 1], pairs, p1, p2, THR_PX, 0.0)
+    _, band1 = R.sampson_band(F2[win:win + 1], pairs, p1, p2, THR_PX, 1e-2)
+    assert d2.shape == band0.shape == (1, len(pairs)) and not (band0 & ~band1).any() and band1.sum() < 0.05 * len(pairs)
+    assert (np.abs(d2[band1] / THR_PX ** 2 - 1) < 0.5).all()
