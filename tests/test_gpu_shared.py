@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 from oracle.oracle import Camera as OCam
+from picp_cases import Batch
 
 pytestmark = pytest.mark.gpu
 ENV = ("VO_PICP_SHARE", "VO_PICP_HELP_KEEP", "VO_PICP_HELP_G", "VO_PICP_HELP_SLACK", "VO_PICP_HELP_ABSENT")
@@ -22,52 +23,6 @@ def _clean_env():
         os.environ.pop(k, None)
         if v is not None:
             os.environ[k] = v
-
-
-def _corr(fp):
-    mp = dict(fp["model_pairs"].tolist())
-    return np.array([(c, mp[r]) for r, c in fp["gt_matches"].tolist()], np.int32)
-
-
-class Batch:
-    """P problems over ONE generated frame pair (so that the oracle has one camera and the test one upload): problem p uses
-    the first sizes[p] pairs and starts at T0[p]"""
-
-    def __init__(self, vo, ctx, n, sizes, seed, K=None, rng_seed=3):
-        self.vo, self.ctx, self.n = vo, ctx, n
-        self.fp = vo.synth.frame_pair(n, seed=seed, distractors=n // 50)
-        self.pairs = _corr(self.fp)
-        self.sizes = np.array([min(s, len(self.pairs)) for s in sizes], np.int32)
-        self.P = len(sizes)
-        self.stride = len(self.pairs)
-        self.K = np.asarray(self.fp["K"] if K is None else K, np.float32)
-        rng = np.random.default_rng(rng_seed)
-        self.T0 = np.stack([vo.synth.random_isometry(rng, 0.01, 0.02) for _ in range(self.P)]).astype(np.float32)
-        self.d = [ctx.to_device(np.tile(self.fp["model"], (self.P, 1))), ctx.to_device(np.tile(self.fp["cur_pts"], (self.P, 1))),
-                  ctx.to_device(np.tile(self.pairs, (self.P, 1))), ctx.to_device(self.sizes),
-                  ctx.to_device(np.ascontiguousarray(np.transpose(self.T0, (0, 2, 1))).reshape(self.P, 16))]
-        self.d_T, self.d_S = ctx.alloc(self.P * 64), ctx.alloc(self.P * 16)
-
-    def run(self, iters, thr, keep, form=2):
-        lib, ctx = self.ctx.lib, self.ctx
-        assert lib.vo_picp_batch_set_form(ctx.h, form) == 0
-        K = np.ascontiguousarray(self.K.T).ravel()
-        n_pts = len(self.fp["model"])
-        rc = lib.vo_picp_solve_batch_dev(ctx.h, self.P, 480, 640, 0, 10, K.ctypes.data_as(C.c_void_p), C.c_float(thr), int(keep),
-                                         C.c_void_p(self.d[0]), C.c_size_t(n_pts), C.c_void_p(self.d[1]), C.c_size_t(len(self.fp["cur_pts"])),
-                                         C.c_void_p(self.d[2]), C.c_size_t(self.stride), C.c_void_p(self.d[3]), C.c_void_p(self.d[4]),
-                                         iters, C.c_void_p(self.d_T), C.c_void_p(self.d_S))
-        assert rc == 0, lib.vo_last_error()
-        f, w = C.c_int(), C.c_int()
-        assert lib.vo_picp_batch_info(ctx.h, C.byref(f), C.byref(w)) == 0
-        T = np.zeros((self.P, 16), np.float32); S = np.zeros((self.P, 4), np.float32)
-        ctx.d2h(T, self.d_T); ctx.d2h(S, self.d_S)
-        lib.vo_picp_batch_set_form(ctx.h, 0)
-        return T, S, f.value, w.value
-
-    def close(self):
-        for x in self.d + [self.d_T, self.d_S]:
-            self.ctx.free(x)
 
 
 @pytest.mark.parametrize("keep,pinhole", [(False, True), (True, True), (False, False), (True, False)])
