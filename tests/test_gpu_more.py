@@ -481,11 +481,11 @@ def test_device_arrays_off_an_8_byte_boundary_are_refused(vo, ctx):
             ctx.free(p)
 
 
-def test_single_pass_compaction_equals_the_default(vo, ctx):
-    """VO_ONE_PASS=1 (geom.hip: chained scan with decoupled look-back -- built in round 5, measured slower, kept opt-in):
-    matcher output, join (+ the solver's gather), triangulation of a batched call and of single-frame calls, bit for bit
-    what the count / scan / scatter form writes, survivors in the reference's order (utils.cpp:97-99,126-128)."""
-    import os
+def test_compactions_that_drop_items_equal_the_oracle(vo, ctx, o32):
+    """Every stable compaction (geom.hip: count / scan / scatter) with items to drop in every frame: matcher output, join
+    (+ the solver's gather), triangulation of a batched call -- nine equal-sized frames: the frame-major 1-D grid with a last
+    group that is not full -- and of single-frame calls of other sizes, stage by stage what the CPU oracle writes, survivors
+    in the reference's order (utils.cpp:97-99,126-128)."""
     rng = np.random.default_rng(5)
     batch = []
     for p in range(9):                        # equal sizes (a batch needs them); the gaps are planted afterwards
@@ -499,29 +499,27 @@ def test_single_pass_compaction_equals_the_default(vo, ctx):
         fp["model_pairs"][rng.choice(len(fp["model_pairs"]), len(fp["model_pairs"]) // 5, replace=False), 0] = -1   # no partner
         batch.append(fp)
     singles = [vo.synth.frame_pair(7000, seed=5200 + p, drop=0.1, distractors=50, model_drop=0.2) for p in range(3)]
-    res = {}
-    for one_pass in ("0", "1"):
-        os.environ["VO_ONE_PASS"] = one_pass
-        try:
-            out = []
-            bp = vo.BatchPipeline(ctx, batch, n_iters=4)
-            bp.run(); ctx.synchronize()
-            c = bp.counts()
-            assert np.all(c[0] < 9000) and np.all(c[1] < c[0]) and np.all(c[2] > 0) and np.all(c[2] <= c[0])
-            out.append((c.tobytes(), bp.poses().tobytes()))
-            for f in range(len(batch)):
-                out.append(tuple(bp.fetch(w, f).tobytes() for w in ("match", "join", "tri_xyz", "tri_pairs", "tri_app")))
-            bp.close()
-            for fp in singles:
-                m = vo.compute_correspondences_images(fp["ref_app"], fp["cur_app"], ctx=ctx)
-                j = vo.extract_correspondences_world(m, fp["model_pairs"], ctx=ctx)
-                xyz, pairs, app = vo.triangulate_points(fp["K"], fp["X_gt"], m, fp["ref_pts"], fp["cur_pts"], fp["cur_app"], ctx=ctx)
-                assert 0 < len(xyz) <= len(m) and 0 < len(j) < len(m)
-                out.append((m.tobytes(), j.tobytes(), xyz.tobytes(), pairs.tobytes(), app.tobytes()))
-            res[one_pass] = out
-        finally:
-            os.environ.pop("VO_ONE_PASS", None)
-    assert res["0"] == res["1"]
+    bp = vo.BatchPipeline(ctx, batch, n_iters=4)
+    bp.run(); ctx.synchronize()
+    c, poses = bp.counts(), bp.poses()
+    assert np.all(c[0] < 9000) and np.all(c[1] < c[0]) and np.all(c[2] > 0) and np.all(c[2] <= c[0])
+    for f, fp in enumerate(batch):
+        m_o = o32.match(fp["ref_app"], fp["cur_app"]); j_o = o32.join(m_o, fp["model_pairs"])
+        assert np.array_equal(bp.fetch("match", f), m_o) and np.array_equal(bp.fetch("join", f), j_o), f
+        xo, po, ao = o32.triangulate(fp["K"], poses[f], m_o, fp["ref_pts"], fp["cur_pts"], fp["cur_app"])
+        assert c[0, f] == len(m_o) and c[1, f] == len(j_o) and c[2, f] == len(po), f
+        assert np.array_equal(bp.fetch("tri_pairs", f), po) and np.array_equal(bp.fetch("tri_app", f), ao), f
+        assert np.array_equal(bp.fetch("tri_xyz", f), xo), f
+    bp.close()
+    for fp in singles:
+        m = vo.compute_correspondences_images(fp["ref_app"], fp["cur_app"], ctx=ctx)
+        j = vo.extract_correspondences_world(m, fp["model_pairs"], ctx=ctx)
+        xyz, pairs, app = vo.triangulate_points(fp["K"], fp["X_gt"], m, fp["ref_pts"], fp["cur_pts"], fp["cur_app"], ctx=ctx)
+        assert 0 < len(xyz) <= len(m) and 0 < len(j) < len(m)
+        m_o = o32.match(fp["ref_app"], fp["cur_app"])
+        assert np.array_equal(m, m_o) and np.array_equal(j, o32.join(m_o, fp["model_pairs"]))
+        xo, po, ao = o32.triangulate(fp["K"], fp["X_gt"], m_o, fp["ref_pts"], fp["cur_pts"], fp["cur_app"])
+        assert np.array_equal(pairs, po) and np.array_equal(app, ao) and np.array_equal(xyz, xo)
 
 
 @pytest.mark.parametrize("general_k", [False, True])

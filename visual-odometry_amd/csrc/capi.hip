@@ -1185,7 +1185,6 @@ static int with_hash(int v, int nt, int n_frames) {
   const bool on = env < 0 ? n_frames >= 8 : env == 1;
   return (on && (v == 2 || v == 3) && match_hash_supported(nt, n_frames)) ? v + 2 : v;
 }
-static int match_auto_flag(const vo_ctx* c) { return c->match_mode == 0 ? MATCH_VARIANT_AUTO : 0; }
 
 // the two halves of the steering described at vo_ctx::hint_host, around a batched matcher call in automatic mode
 constexpr int HINT_SKIP = 16;
@@ -1290,7 +1289,7 @@ int vo_match_appearances_dev(vo_ctx* c, const float* d_a1, int n1, const float* 
   void* ws = nullptr;
   if (nq > 0) if (int r = match_workspace(c, variant, nt, nq, 1, &ws)) return r;
   VO_HIP_CHECK(launch_match(c->stream, d_a1, n1, d_a2, n2, radius, d_out_pairs, d_n_out,
-                            c->best.as<unsigned long long>(), c->scratch.as<int>(), c->n_cu, ws, variant | match_auto_flag(c)));
+                            c->best.as<unsigned long long>(), c->scratch.as<int>(), c->n_cu, ws, variant));
   return VO_OK;
 }
 
@@ -1343,7 +1342,7 @@ int vo_match_appearances_batch_dev(vo_ctx* c, int n_frames, const float* d_a1, i
   if (q > 0) if (int r = match_workspace(c, variant_rule, nt, d_n1 ? nt : q, n_frames, &ws)) return r;
   VO_HIP_CHECK(launch_match_batch(c->stream, d_a1, cap1, 10 * (size_t)cap1, d_a2, cap2, 10 * (size_t)cap2, radius, d_out_pairs,
                                   (size_t)q, d_n_out, c->best.as<unsigned long long>(), c->scratch.as<int>(), c->n_cu, ws, n_frames,
-                                  variant | match_auto_flag(c), d_n1, d_n2));
+                                  variant, d_n1, d_n2));
   match_hint_after(c, variant, skipped, ws, n_frames, c->best.as<unsigned long long>(), (size_t)q, q, d_n1, d_n2);
   return VO_OK;
 }
@@ -1392,7 +1391,7 @@ static int frames_batch(vo_ctx* c, const vo_frame_batch* b, const vo_frame_sizes
   // compute_correspondences_images, all frames                                  vo_complete.cpp:156
   VO_HIP_CHECK(launch_match_batch(c->stream, b->ref_app, b->n_ref, 10 * (size_t)b->n_ref, b->cur_app, b->n_cur,
                                   10 * (size_t)b->n_cur, b->radius, b->matches, (size_t)q, n_match,
-                                  c->best.as<unsigned long long>(), c->scratch.as<int>(), c->n_cu, ws, F, variant | match_auto_flag(c),
+                                  c->best.as<unsigned long long>(), c->scratch.as<int>(), c->n_cu, ws, F, variant,
                                   sz ? sz->n_ref : nullptr, sz ? sz->n_cur : nullptr));
   match_hint_after(c, variant, skipped, ws, F, c->best.as<unsigned long long>(), (size_t)q, q, sz ? sz->n_ref : nullptr, sz ? sz->n_cur : nullptr);
   // X_curr * triangulated_pc                                                    vo_complete.cpp:159

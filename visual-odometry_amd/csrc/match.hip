@@ -618,8 +618,7 @@ static hipError_t launch_match_pruned(hipStream_t st, const float* tree, int nt,
   hipLaunchKernelGGL(match_bucket_place_kernel, dim3(SORT_BLOCKS, 1, Z), dim3(256), 0, st, tree, nt, qry, nq, bp,
                      block_hist, tree_rec, qry_rec, d_best, r2, ms);
   const int qblocks = (nq + MBP * QPP - 1) / (MBP * QPP) + NA;   // upper bound: workgroups are aligned to A-cells
-  static const int chunk_factor = [] { const char* e = getenv("VO_MATCH_CHUNK_FACTOR"); return e ? atoi(e) : 16; }();
-  int nchunks = (chunk_factor * (n_cu > 0 ? n_cu : 256) + qblocks * n_frames - 1) / (qblocks * n_frames);
+  int nchunks = (16 * (n_cu > 0 ? n_cu : 256) + qblocks * n_frames - 1) / (qblocks * n_frames);
   if (nchunks < 1) nchunks = 1;
   if (nchunks > 64) nchunks = 64;
   hipLaunchKernelGGL(match_pruned_kernel, dim3(qblocks, nchunks, Z), dim3(MBP), 0, st, tree_rec, nt, qry_rec, nq, starts,
@@ -1373,9 +1372,6 @@ __global__ __launch_bounds__(CS_THREADS, CS_THREADS * CS_WG_PER_CU / 256) void c
   __syncthreads();
 
   const unsigned T = (unsigned)cp.T;
-#if defined(VO_CS_EXP) && VO_CS_EXP == 1
-  if (a.r2 >= 0.f) return;                                // experiment: staging only
-#endif
   for (; qi < qe; qi += CS_THREADS) {
     if (qi >= qb + CS_THREADS) qrec = q1[qi];             // later batches (rare)
     const int qorig = (int)qrec.x;
@@ -1462,9 +1458,6 @@ __global__ __launch_bounds__(CS_THREADS, CS_THREADS * CS_WG_PER_CU / 256) void c
       Row10 first_row;
       int first_ti = -1;
       int n_surv = 0;
-#if defined(VO_CS_EXP) && VO_CS_EXP == 2
-      if (a.r2 >= 0.f) hits = hits & 0x80000000u;         // experiment: no survivor is examined
-#endif
       while (hits != 0u) {
         const int bit = __builtin_ctz(hits);
         hits &= hits - 1u;
@@ -1564,9 +1557,7 @@ struct HashArgs {
   int qcap;                   // records a part's queue holds
   int* unres;                 // [n_frames] queries left open (zeroed per call)
   unsigned* sample_mask;      // [n_frames] (zeroed per call) bit k: sample query k of the frame has a bitwise copy in the tree -- a frame
-                              //   with fewer than sample_min of its HJ_SAMPLES samples found skips the tables and the lookup: its queries all go to the search
-  int sample_min;             // automatic mode: HJ_SAMPLE_MIN (the pass pays while fewer than ~10 % of a frame's queries lack a copy);
-                              //   forced modes 4 / 5: 1 (any copy at all)
+                              //   with none of its HJ_SAMPLES samples found skips the tables and the lookup: its queries all go to the search
   int* open_list;             // [n_frames][OPEN_MAX] their indices when there are at most OPEN_MAX, in no particular order (hash_open_kernel)
   size_t queue_stride;        // uint2 per frame of `queues`; the lookup reuses a frame's queues for its workgroups' open queries:
   int seg_counts;             //   ints [0, seg_counts) the segments (256 HJ_Q per workgroup), behind them one count per workgroup
@@ -1578,16 +1569,15 @@ struct HashArgs {
   int n_frames, log2p, ib, qblocks, hblocks;   // parts = 1 << log2p; ib: index bits of a word (the tag takes the other 31 - ib)
 };
 
-// Sample queries per frame and how many of them must have a bitwise copy in the tree for the frame to take the pass in the
-// automatic mode.  Matcher stage per 200 x 50k frames by share of queries WITHOUT a copy: 0 %: 0.52 ms, 1 %:
+// Sample queries per frame; a frame takes the pass when any of them has a bitwise copy in the tree.  Matcher stage per 200 x 50k frames by share of queries WITHOUT a copy: 0 %: 0.52 ms, 1 %:
 // 0.72, 5 %: 0.77, 25 %: 1.26, 100 %: 1.21 with "any of 8 samples" (round 4) -- the search alone: 1.10 at every share, so the
 // pass loses 0.1-0.2 ms from ~10 % on.  Round 5 tried the obvious repair: 16 samples, at least 15 found -- taken
 // with probability 0.99 / 0.81 / 0.06 / 0 at 1 / 5 / 25 / 100 % -- and measured it WORSE at every share: 0.77 / 1.10 / 1.32 /
 // 1.29 ms (frames of one call split over two routes keep both chains of kernels busy, and sixteen scalar sample loads per
 // wave lengthen the row-hash kernel by 0.08 ms).  So the rule stays "any of 8"; vo_match_set_mode(3) is the choice for data
-// known to carry recomputed descriptors.  The plumbing for a threshold stays (HashArgs::sample_min).
-constexpr int HJ_SAMPLES = 8, HJ_SAMPLE_MIN = 1;
-__device__ __forceinline__ bool hash_frame_takes_pass(const HashArgs& a, int f) { return __popc(a.sample_mask[f]) >= a.sample_min; }
+// known to carry recomputed descriptors.
+constexpr int HJ_SAMPLES = 8;
+__device__ __forceinline__ bool hash_frame_takes_pass(const HashArgs& a, int f) { return a.sample_mask[f] != 0u; }
 __device__ __forceinline__ bool row_safe(const Row10& r) {       // every |x| in [2^-40, inf): an unsigned range test on the bits
   unsigned worst = 0;
 #pragma unroll
@@ -2261,7 +2251,7 @@ size_t match_hash_workspace_bytes(int nt, int n_frames) { return hash_ws_bytes(n
 static hipError_t launch_hash_first(hipStream_t st, const float* tree, int nt, const float* qry, int nq, float r2,
                                     unsigned long long* d_best, void* ws, int n_frames, size_t tree_stride, size_t qry_stride,
                                     size_t best_stride, const int* d_n1, const int* d_n2, int** d_unres_out, int32_t* d_out_pairs,
-                                    size_t out_stride, int tree_is_1, bool automatic) {
+                                    size_t out_stride, int tree_is_1) {
   HashPlan p;
   const int nt_plan = d_n1 ? (nt > nq ? nt : nq) : nt;
   if (!hash_plan(nt_plan, p)) return hipErrorInvalidValue;
@@ -2277,7 +2267,6 @@ static hipError_t launch_hash_first(hipStream_t st, const float* tree, int nt, c
   a.tables_stride = hash_table_bytes(p) / sizeof(unsigned);
   a.queues = reinterpret_cast<uint2*>(a.tables + a.tables_stride * (size_t)n_frames);
   a.qcap = p.qcap;
-  a.sample_min = automatic ? HJ_SAMPLE_MIN : 1;
   a.hblocks = (nt_plan + 255) / 256;
   hipError_t e0 = hipMemsetAsync(ws, 0, sizeof(int) * (size_t)n_frames * (3 + HJ_MAXP), st);
   if (e0 != hipSuccess) return e0;
@@ -2308,9 +2297,9 @@ static hipError_t launch_hash_first(hipStream_t st, const float* tree, int nt, c
 
 // "did any frame of the call that just ran take the exact-duplicate pass?" (sample masks at the head of its workspace) into
 // *d_out: what the host reads -- without waiting, capi.hip -- to decide whether the next calls run the pass at all
-__global__ void hash_hint_kernel(const unsigned* masks, int n_frames, int sample_min, int* out) {
+__global__ void hash_hint_kernel(const unsigned* masks, int n_frames, int* out) {
   int any = 0;
-  for (int f = threadIdx.x; f < n_frames; f += blockDim.x) any |= __popc(masks[f]) >= sample_min ? 1 : 0;
+  for (int f = threadIdx.x; f < n_frames; f += blockDim.x) any |= masks[f] != 0u ? 1 : 0;
   any = __syncthreads_or(any);
   if (threadIdx.x == 0) *out = any;
 }
@@ -2337,7 +2326,7 @@ hipError_t launch_match_hint_from_best(hipStream_t st, const unsigned long long*
 }
 hipError_t launch_match_hint(hipStream_t st, const void* d_prune_ws, int n_frames, int* d_out) {
   const unsigned* masks = reinterpret_cast<const unsigned*>(static_cast<const int*>(d_prune_ws) + 2 * (size_t)n_frames);
-  hipLaunchKernelGGL(hash_hint_kernel, dim3(1), dim3(256), 0, st, masks, n_frames, HJ_SAMPLE_MIN, d_out);
+  hipLaunchKernelGGL(hash_hint_kernel, dim3(1), dim3(256), 0, st, masks, n_frames, d_out);
   return hipGetLastError();
 }
 
@@ -2362,8 +2351,7 @@ static hipError_t launch_cells_sort(hipStream_t st, CellArgs& a, const float* tr
   hipLaunchKernelGGL(cell_bounds_kernel, dim3(Z), dim3(1024), 0, st, a);
   if (d_unres && d_todo && d_open_list) {
     // frames with few open queries: the tree streamed past them; the sorted search below then sees todo[] instead of unres[]
-    static const int open_div = [] { const char* e = getenv("VO_MATCH_OPEN_DIV"); return e ? atoi(e) : OPEN_DIV_DEFAULT; }();
-    a.todo = d_todo; a.open_div = open_div; a.open_list = d_open_list;
+    a.todo = d_todo; a.open_div = OPEN_DIV_DEFAULT; a.open_list = d_open_list;
     const int big = d_n1 ? (nt > nq ? nt : nq) : nt;
     // ~4 workgroups per CU over the call, so that the staging round trip at a workgroup's start is a small part of it
     const int runs = (big + 63) / 64;
@@ -2418,8 +2406,6 @@ hipError_t launch_match_batch(hipStream_t st, const float* d_a1, int n1, size_t 
   // variants 4 / 5: the exact-duplicate pass first, then variant 2 / 3 for the queries it left open (its workspace comes
   // first in d_prune_ws)
   if (n_cu > 0) t_n_cu = n_cu;
-  const bool automatic = (variant_in & MATCH_VARIANT_AUTO) != 0;       // picked by the automatic rule, not forced (vo_match_set_mode)
-  variant_in &= ~MATCH_VARIANT_AUTO;
   const bool hash_first = variant_in >= 4 && d_prune_ws != nullptr;
   const int variant = variant_in >= 4 ? variant_in - 2 : variant_in;
   int* d_unres = nullptr;
@@ -2432,7 +2418,7 @@ hipError_t launch_match_batch(hipStream_t st, const float* d_a1, int n1, size_t 
       void* ws = d_prune_ws;
       if (hash_first) {
         hipError_t eh = launch_hash_first(st, d_a1, n1, d_a2, n2, r2, d_best, d_prune_ws, n_frames, a1_stride, a2_stride, (size_t)q,
-                                          d_n1, d_n2, &d_unres, q > SMALL_COMPACT ? d_out_pairs : nullptr, out_stride, 1, automatic);
+                                          d_n1, d_n2, &d_unres, q > SMALL_COMPACT ? d_out_pairs : nullptr, out_stride, 1);
         if (eh == hipErrorNotSupported) d_unres = nullptr;        // sizes the pass does not take: the plain search answers every query
         else if (eh != hipSuccess) return eh;
         ws = static_cast<char*>(d_prune_ws) + hash_ws_bytes(n1 > n2 ? n1 : n2, n_frames);
@@ -2471,7 +2457,7 @@ hipError_t launch_match_batch(hipStream_t st, const float* d_a1, int n1, size_t 
   if (hash_first && nq > 0 && nt > 0 && (variant == 2 || variant == 3)) {
     hipError_t eh = launch_hash_first(st, tree, nt, qry, nq, r2, d_best, d_prune_ws, n_frames, n_frames > 1 ? ts : 0,
                                       n_frames > 1 ? qs : 0, best_stride, nullptr, nullptr, &d_unres,
-                                      nq > SMALL_COMPACT ? d_out_pairs : nullptr, n_frames > 1 ? out_stride : 0, tree_is_1, automatic);
+                                      nq > SMALL_COMPACT ? d_out_pairs : nullptr, n_frames > 1 ? out_stride : 0, tree_is_1);
     if (eh == hipErrorNotSupported) d_unres = nullptr;            // sizes the pass does not take: the plain search answers every query
     else if (eh != hipSuccess) return eh;
     ws = static_cast<char*>(d_prune_ws) + hash_ws_bytes(nt, n_frames);

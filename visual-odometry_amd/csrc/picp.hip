@@ -25,7 +25,6 @@
 #include <stdlib.h>
 
 #include "vo_internal.h"
-#include "chain_scan.h"
 
 namespace vo {
 
@@ -496,10 +495,7 @@ __global__ __launch_bounds__(PICP_BLOCK) void picp_round_batch_kernel(const Picp
 }
 
 int picp_grid_for(int n_corr, int n_cu) {
-  // correspondences per thread (VO_PICP_PER_THREAD in the environment, default 1): fewer workgroups mean fewer partial rows
-  // for every workgroup of the next round to wait for, against a longer linearisation in each
-  static const int per_thread = [] { const char* e = getenv("VO_PICP_PER_THREAD"); const int v = e ? atoi(e) : 1; return v >= 1 && v <= 16 ? v : 1; }();
-  int g = (n_corr + PICP_BLOCK * per_thread - 1) / (PICP_BLOCK * per_thread);
+  int g = (n_corr + PICP_BLOCK - 1) / PICP_BLOCK;
   if (g < 1) g = 1;
   // beyond one workgroup per CU let each thread take several correspondences
   // before adding workgroups: the per-iteration partial reduction reads
@@ -889,6 +885,7 @@ constexpr int HELP_SLACK10 = 20;                // what a helper's round costs b
 constexpr int HELP_ITER100 = 71;                // a wave-trip on a CU full of helper waves, in hundredths of a home's trip
 constexpr unsigned HELP_POLLS_HOME = 1u << 9;   // ~0.6 us each: a few hundred microseconds
 constexpr unsigned HELP_POLLS_HELPER = 1u << 13;
+typedef __attribute__((address_space(1))) unsigned long long help_word;      // a tagged word, in global memory
 
 // wave-trips per chunk for a home that keeps `keep` trips: what a helper wave finishes within the home's round
 __device__ __forceinline__ int help_chunk_len(int keep, int slack10) {
@@ -956,8 +953,8 @@ __global__ __launch_bounds__(PICP_BATCH_BLOCK) void picp_batch_shared_kernel(Bat
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int P = a.n_problems, H = (int)gridDim.x - P;
   const CamK cam = a.cam;
-  chain_word* rows = chain_ptr(a.help_words);
-  chain_word* posew = rows + (size_t)a.help_rows * 32;
+  help_word* rows = (help_word*)a.help_words;
+  help_word* posew = rows + (size_t)a.help_rows * 32;
   auto clamp_n = [&](int p) { int n = a.n_pairs[p]; if (n < 0) n = 0; if ((size_t)n > a.cap) n = (int)a.cap; return n; };
   auto sgpr = [](int v) { return __builtin_amdgcn_readfirstlane(v); };      // (values every lane read from the same LDS word)
 
