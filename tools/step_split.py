@@ -1,0 +1,103 @@
+#!/usr/bin/env python3
+"""Where one headline step goes, kernel by kernel, from a rocprofv3 kernel trace of bench.py --no-extras.
+
+usage: tools/step_split.py <dir with *kernel_trace.csv> [--json out.json]
+
+A step ends with the finishing launch (picp_round_kernel<true, true, ...>).  Everything between the end of one finishing
+launch and the start of the next step's first PRE round (picp_round_kernel<true, false, ...>, or the tally instantiation
+of round 1) is the FIXED part of a step:
+it is listed launch by launch (gap in front of the kernel, kernel time).  The rounds are summarised start to start.  All
+figures are medians over the steps of the trace that have the most common launch sequence (the timed region).  The tracer
+itself stretches the gaps between plain launches (host-side cost per launch); kernel times and the gaps inside a graph
+replay are what the untraced run sees.
+"""
+import csv
+import glob
+import json
+import statistics
+import sys
+from collections import Counter
+
+
+def short(name):
+    name = name.replace("void ", "").replace("vo::", "")
+    i = name.find("(")
+    return (name if i < 0 else name[:i]).strip()
+
+
+def load(d):
+    files = glob.glob(d + "/**/*kernel_trace.csv", recursive=True)
+    if not files:
+        raise SystemExit("no *kernel_trace.csv under " + d)
+    rows = []
+    for f in files:
+        for r in csv.DictReader(open(f)):
+            rows.append((int(r["Start_Timestamp"]), int(r["End_Timestamp"]), short(r["Kernel_Name"])))
+    rows.sort()
+    return rows
+
+
+def main():
+    d = sys.argv[1]
+    out_json = sys.argv[sys.argv.index("--json") + 1] if "--json" in sys.argv else None
+    rows = load(d)
+    # (round 1 of a solve, or the finishing launch of a one-round solve, is the instantiation that also takes the tally of
+    # dropped pairs: picp_tally_round_kernel<FINISH, ...>)
+    is_finish = lambda n: n.startswith(("picp_round_kernel<true, true", "picp_tally_round_kernel<true"))
+    is_round = lambda n: n.startswith(("picp_round_kernel<true, false", "picp_tally_round_kernel<false"))
+    steps, cur, prev_end = [], [], None
+    for s, e, n in rows:
+        cur.append((s, e, n))
+        if is_finish(n):
+            if prev_end is not None:
+                steps.append((prev_end, cur))
+            prev_end, cur = e, []
+    sig = lambda st: tuple(n for _, _, n in st[1])
+    common, count = Counter(sig(st) for st in steps).most_common(1)[0]
+    steps = [st for st in steps if sig(st) == common]
+    med = lambda xs: statistics.median(xs) / 1e3 if xs else float("nan")
+    first_round = next(i for i, n in enumerate(common) if is_round(n))
+    res = {"steps_used": len(steps), "launches_per_step": len(common), "fixed": [], "unit": "us"}
+    print("%d steps of %d launches each" % (len(steps), len(common)))
+    print("fixed part (end of the finishing launch -> start of the first PRE round):")
+    fixed_total = []
+    for k in range(first_round + 1):
+        gaps, durs = [], []
+        for pe, st in steps:
+            before = pe if k == 0 else st[k - 1][1]
+            gaps.append(st[k][0] - before)
+            durs.append(st[k][1] - st[k][0])
+        if k < first_round:
+            print("  gap %7.2f  kernel %7.2f  %s" % (med(gaps), med(durs), common[k]))
+            res["fixed"].append({"kernel": common[k], "gap_before": med(gaps), "kernel_time": med(durs)})
+        else:
+            print("  gap %7.2f  (then the first PRE round starts)" % med(gaps))
+            res["fixed"].append({"kernel": "(first PRE round starts)", "gap_before": med(gaps), "kernel_time": 0.0})
+    for pe, st in steps:
+        fixed_total.append(st[first_round][0] - pe)
+    rr, rk, rg = [], [], []
+    fin_gap, fin_dur, total = [], [], []
+    for pe, st in steps:
+        rounds = [x for x in st if is_round(x[2])]
+        for a, b in zip(rounds, rounds[1:]):
+            rr.append(b[0] - a[0])
+            rg.append(b[0] - a[1])
+        rk += [e - s for s, e, _ in rounds]
+        fin_gap.append(st[-1][0] - st[-2][1])
+        fin_dur.append(st[-1][1] - st[-1][0])
+        total.append(st[-1][1] - pe)
+    n_rounds = sum(1 for n in common if is_round(n))
+    res.update({"fixed_total": med(fixed_total), "pre_rounds_per_step": n_rounds, "round_start_to_start": med(rr),
+                "round_kernel_time": med(rk), "round_gap": med(rg), "finish_gap": med(fin_gap), "finish_kernel_time": med(fin_dur),
+                "step_total": med(total)})
+    print("  fixed part in all          %7.2f us" % res["fixed_total"])
+    print("PRE rounds per step: %d ; start to start %.2f us (kernel %.2f + gap %.2f)"
+          % (n_rounds, res["round_start_to_start"], res["round_kernel_time"], res["round_gap"]))
+    print("finishing launch: gap %.2f us, kernel %.2f us" % (res["finish_gap"], res["finish_kernel_time"]))
+    print("step, finish end to finish end: %.2f us" % res["step_total"])
+    if out_json:
+        json.dump(res, open(out_json, "w"), indent=1)
+
+
+if __name__ == "__main__":
+    main()

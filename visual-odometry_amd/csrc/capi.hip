@@ -181,6 +181,9 @@ struct vo_picp {
   int set_n = -1;             // pair count handed over by vo_picp_set_correspondences
   int grid = 1;
   const float* pending_T0 = nullptr;   // device 4x4 to load as the pose by the next pack launch
+  // A solve in the fast mode gathers in its first round (launch_picp_rounds): picp_prepare leaves what the pack launch would
+  // have got here (on = 1), and the picp_enqueue that follows it in the same call consumes it.
+  PicpGather gather;
   int zeroed_for_grid = -1;   // grid the (zero-padded) partial buffers were last cleared for
   // Rounds enqueued since the state (pose[0], T16, H, b, statistics) was last complete: vo_picp_one_round enqueues ONE
   // launch per call and leaves the finishing launch to whoever needs the state next (a getter, a setter, a multi-round
@@ -638,7 +641,15 @@ __global__ void T16_to_pose12_kernel(const float* T, float* p) {
   else if (k < 12) p[k] = T[12 + (k - 9)];
 }
 
-static int picp_prepare(vo_picp* s, const int32_t* d_pairs, int n_pairs, const int* d_n, int keep_outliers) {
+static bool picp_chainable(const vo_picp* s);
+
+// VO_PICP_GATHER=0 in the environment keeps the separate gather launch in front of every solve (read per call: tests compare
+// the two routes in one process)
+static bool picp_gather_enabled() { const char* e = getenv("VO_PICP_GATHER"); return !(e && e[0] == '0'); }
+
+// n_iters / lazy: what the caller hands to picp_enqueue next (0: nothing that could take the gather along)
+static int picp_prepare(vo_picp* s, const int32_t* d_pairs, int n_pairs, const int* d_n, int keep_outliers, int n_iters = 0,
+                        bool lazy = false) {
   vo_ctx* c = s->ctx;
   if (!s->have_points) return fail(VO_ERR_NOT_READY, "vo_picp: set_points has not been called");
   if (s->hp.keep_outliers != (keep_outliers ? 1 : 0)) { s->hp.keep_outliers = keep_outliers ? 1 : 0; s->params_dirty = true; }
@@ -671,8 +682,16 @@ static int picp_prepare(vo_picp* s, const int32_t* d_pairs, int n_pairs, const i
       }
     }
     PackedCorr pk{s->packed.as<float>(), s->packed.cap / (5 * sizeof(float)) & ~(size_t)3};
-    VO_HIP_CHECK(launch_picp_pack(c->stream, d_pairs, d_n, n_pairs, s->d_world, s->n_world, s->d_meas,
-                                  s->n_meas, pk, s->d_params, s->d_state, s->pending_T0));
+    // With rounds behind it the gather rides in round 0.  Not where no round kernel follows: the reference-order mode, a
+    // single workgroup's all-rounds launch, no round at all, and the one open round of vo_picp_one_round (whose chain
+    // kernels are the plain ones).
+    if (n_iters >= 1 && !s->exact && picp_rounds_chain(s->grid) && !(lazy && n_iters == 1 && picp_chainable(s)) &&
+        picp_gather_enabled()) {
+      s->gather = PicpGather{d_pairs, d_n, n_pairs, s->d_world, s->n_world, s->d_meas, s->n_meas, s->pending_T0, 1};
+    } else {
+      VO_HIP_CHECK(launch_picp_pack(c->stream, d_pairs, d_n, n_pairs, s->d_world, s->n_world, s->d_meas,
+                                    s->n_meas, pk, s->d_params, s->d_state, s->pending_T0));
+    }
     s->pending_T0 = nullptr;
     s->packed_valid = true;
   }
@@ -744,15 +763,25 @@ static int picp_enqueue(vo_picp* s, int n_iters, bool lazy = false) {
   vo_ctx* c = s->ctx;
   s->ahead = 0;                                  // whatever ran ahead of the caller is not claimed by this call
   if (lazy && n_iters == 1 && picp_chainable(s)) { const int r = picp_enqueue_chain_rounds(s, 1, true); return r < 0 ? r : VO_OK; }
-  if (n_iters > 0) { if (int r = picp_flush(s)) return r; }
+  const PicpGather gather = s->gather;           // round 0 gathers (picp_prepare) or takes the packed arrays as they are
+  s->gather = PicpGather{};
+  if (n_iters > 0) { if (int r = picp_flush(s)) { if (gather.on) s->packed_valid = false; return r; } }
   PackedCorr pk{s->packed.as<float>(), s->packed.cap / (5 * sizeof(float)) & ~(size_t)3};
   float* partials = s->partials.as<float>();
   const bool pinhole = is_pinhole(s->hp.cam.K), keep = s->hp.keep_outliers != 0;
+  if (gather.on && (s->exact || n_iters < 1)) {
+    s->packed_valid = false;
+    return fail(VO_ERR_NOT_READY, "vo_picp: a gather was left without its round");
+  }
   if (s->exact) {
     VO_HIP_CHECK(launch_picp_exact(c->stream, s->d_params, s->d_state, pk, n_iters));
     return VO_OK;
   }
   if (s->use_graph && n_iters >= 2 && !c->capturing) {
+    // Where the rounds are launches of their own, round 0 -- whose arguments (what it gathers from, or that it does not) are
+    // the caller's and change from call to call -- is a plain launch, and the graph holds what follows it: one graph per
+    // solve shape, whatever it is replayed behind.  (Round 0 as the graph's first node measured the same: DESIGN.md section 8.)
+    const int part = picp_rounds_chain(s->grid) ? PICP_AFTER_ROUND0 : PICP_WHOLE;
     auto key = std::make_tuple(n_iters, s->grid, (const void*)pk.base, pk.cap, (const void*)partials,
                                (pinhole ? 1 : 0) | (keep ? 2 : 0));
     auto it = s->graphs.find(key);
@@ -761,7 +790,7 @@ static int picp_enqueue(vo_picp* s, int n_iters, bool lazy = false) {
       hipGraphExec_t exec = nullptr;
       hipError_t e = hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal);
       if (e == hipSuccess) {
-        hipError_t el = launch_picp_rounds(c->stream, s->d_params, s->d_state, pk, partials, s->grid, n_iters, pinhole, keep);
+        hipError_t el = launch_picp_rounds(c->stream, s->d_params, s->d_state, pk, partials, s->grid, n_iters, pinhole, keep, gather, part);
         e = hipStreamEndCapture(c->stream, &graph);
         if (e == hipSuccess && el != hipSuccess) e = el;
       }
@@ -787,11 +816,20 @@ static int picp_enqueue(vo_picp* s, int n_iters, bool lazy = false) {
       }
     }
     if (s->use_graph && it != s->graphs.end()) {
-      VO_HIP_CHECK(hipGraphLaunch(it->second, c->stream));
+      hipError_t e = hipSuccess;
+      if (part == PICP_AFTER_ROUND0)
+        e = launch_picp_rounds(c->stream, s->d_params, s->d_state, pk, partials, s->grid, n_iters, pinhole, keep, gather, PICP_ROUND0);
+      if (e == hipSuccess) e = hipGraphLaunch(it->second, c->stream);
+      if (e != hipSuccess && gather.on) s->packed_valid = false;
+      VO_HIP_CHECK(e);
       return VO_OK;
     }
   }
-  VO_HIP_CHECK(launch_picp_rounds(c->stream, s->d_params, s->d_state, pk, partials, s->grid, n_iters, pinhole, keep));
+  {
+    const hipError_t e = launch_picp_rounds(c->stream, s->d_params, s->d_state, pk, partials, s->grid, n_iters, pinhole, keep, gather);
+    if (e != hipSuccess && gather.on) s->packed_valid = false;
+    VO_HIP_CHECK(e);
+  }
   return VO_OK;
 }
 
@@ -808,7 +846,7 @@ int vo_picp_solve_dev(vo_picp* s, const int32_t* d_pairs, int n_pairs, const int
   // device pairs may have been rewritten in place by the producer: always re-pack
   s->packed_valid = false;
   s->shadow_valid = false;
-  if (int r = picp_prepare(s, d_pairs, n_pairs, d_n_pairs, keep_outliers)) return r;
+  if (int r = picp_prepare(s, d_pairs, n_pairs, d_n_pairs, keep_outliers, n_iters)) return r;
   return picp_enqueue(s, n_iters);
 }
 
@@ -872,7 +910,7 @@ int vo_picp_solve(vo_picp* s, const int32_t* pairs, int n_pairs, int keep_outlie
   // pairs_own / shadow now hold THIS array: a later vo_picp_rounds continues on it (not on a stale count from an earlier
   // vo_picp_set_correspondences, which would re-pack a mix of both arrays once set_points invalidated the packing)
   s->set_n = n_pairs;
-  if (int r = picp_prepare(s, s->pairs_own.as<int32_t>(), n_pairs, nullptr, keep_outliers)) return r;
+  if (int r = picp_prepare(s, s->pairs_own.as<int32_t>(), n_pairs, nullptr, keep_outliers, n_iters, true)) return r;
   return picp_enqueue(s, n_iters, true);
 }
 
@@ -900,7 +938,7 @@ int vo_picp_rounds(vo_picp* s, int keep_outliers, int n_iters) {
   if (s->set_n < 0 || !s->shadow_valid)
     return fail(VO_ERR_NOT_READY, "vo_picp_rounds: vo_picp_set_correspondences has not been called");
   if (int r = set_device(s->ctx)) return r;
-  if (int r = picp_prepare(s, s->pairs_own.as<int32_t>(), s->set_n, nullptr, keep_outliers)) return r;
+  if (int r = picp_prepare(s, s->pairs_own.as<int32_t>(), s->set_n, nullptr, keep_outliers, n_iters, true)) return r;
   return picp_enqueue(s, n_iters, true);
 }
 

@@ -7,6 +7,8 @@
 //                      meas[pair.first] into five SoA arrays (20 B per
 //                      correspondence) so that every iteration streams
 //                      coalesced data and never touches the index pairs again.
+//                      (A multi-launch solve does this inside its first round
+//                      instead: picp_gather_round_kernel.)
 //   picp_round_kernel  one launch per Gauss-Newton iteration.  Every workgroup
 //                      first re-derives the pose of this iteration from the
 //                      previous launch's workgroup partials (fixed-order
@@ -295,6 +297,12 @@ __global__ __launch_bounds__(256) void picp_pack_kernel(const int32_t* __restric
 // ---- one Gauss-Newton round ---------------------------------------------------
 // PRE:    first derive this round's pose from the partials of launch it-1.
 // FINISH: only derive the pose (single workgroup), publish the statistics.
+// TALLY:  (PRE) the rows read may be those of a gathering round: then also sum their count of dropped pairs into n_bad.
+// GATHER: (first round of a solve, PRE = false) when told to (RoundGather::on) the round gathers its correspondences from
+//         the index pairs itself -- what picp_pack_kernel does, same range checks, same dropped-marker --, stores the five
+//         packed values for the rounds that follow and linearises from registers; it also takes the count, a pending pose
+//         reset and the tally of dropped pairs along, so that a solve needs neither the gather launch nor the memset of
+//         n_bad in front of it.  Told not to, it is round 0 on the packed arrays as they are.
 // BATCH: several problems per launch, problem = blockIdx.y (a few problems with many workgroups each; many problems
 // go through picp_batch_kernel instead).  Everything per-problem is reached through strides.
 struct RoundBatch {
@@ -304,10 +312,32 @@ struct RoundBatch {
   float* T_out;              // FINISH: n_problems x 16
   float* stats_out;          // FINISH: n_problems x 4, or null
 };
+// what the gathering first round reads (the arguments of picp_pack_kernel)
+struct RoundGather {
+  const int32_t* pairs;
+  const int* d_n;
+  int n_max;
+  const float* world;
+  int n_world;
+  const float* meas;
+  int n_meas;
+  const float* T0;           // pending pose reset (column-major 4x4) or null
+  int on;                    // 0: the packed arrays are current, nothing to gather
+};
+// The tally of dropped pairs travels in the two spare slots of the partial row: a round that gathers writes its workgroup's
+// count into slot PICP_BAD_SLOT (an exact integer in float, like the inlier count) and 1 into slot PICP_GATHERED_SLOT, every
+// other round writes zeros there.  The launch that sums the rows of a solve's round 0 (round 1, or the finishing launch of a
+// one-round solve) is the TALLY instantiation: two more lanes sum the two slots, and where the mark is set workgroup 0 stores
+// the total as n_bad.  The rounds after it are the plain instantiation, untouched.
+constexpr int PICP_BAD_SLOT = NACC, PICP_GATHERED_SLOT = NACC + 1;
+static_assert(PICP_GATHERED_SLOT < PICP_PSTRIDE, "the partial row has two spare slots");
 
-template <bool PRE, bool FINISH, bool PINHOLE, bool KEEP, bool BATCH>
+template <bool PRE, bool FINISH, bool PINHOLE, bool KEEP, bool BATCH, bool GATHER = false, bool TALLY = false>
 __device__ __forceinline__ void picp_round_body(const PicpParams* __restrict__ P, PicpState* S, PackedCorr pk,
-                                                float* partials, int it, int nb, const RoundBatch& rb) {
+                                                float* partials, int it, int nb, const RoundBatch& rb,
+                                                const RoundGather& gt = RoundGather{}) {
+  static_assert(!GATHER || (!PRE && !FINISH && !BATCH), "the gathering round is the first round of one problem");
+  static_assert(!TALLY || (PRE && !BATCH), "the tally is read from the rows of a gathering round");
   if (BATCH) {
     const size_t p = blockIdx.y;
     S += p;
@@ -317,7 +347,12 @@ __device__ __forceinline__ void picp_round_body(const PicpParams* __restrict__ P
   __shared__ __attribute__((aligned(16))) float s_acc[PICP_SACC];   // also the staging of the partial rows
   __shared__ float s_part[PICP_PARTS * 32];
   __shared__ float s_stat[4];
+  __shared__ int s_bad;
   const int tid = threadIdx.x;
+  if (GATHER) {
+    if (tid == 0) s_bad = 0;
+    __syncthreads();
+  }
   VO_STAMP(0);
   VO_STAMP_REAL(7);
 
@@ -354,11 +389,30 @@ __device__ __forceinline__ void picp_round_body(const PicpParams* __restrict__ P
   }
 
   // (2) this thread's first correspondence (coalesced SoA loads), in flight during the solve
-  int n = P->n_corr;
+  const bool gathers = GATHER && gt.on != 0;
+  int n = gathers ? gt.n_max : P->n_corr;
   if (BATCH) {
     n = rb.n_pairs[blockIdx.y];
     n = n < 0 ? 0 : ((size_t)n > rb.cap ? (int)rb.cap : n);
   }
+  if (gathers) {
+    if (gt.d_n) { const int m = *gt.d_n; n = m < gt.n_max ? (m < 0 ? 0 : m) : gt.n_max; }
+    if (blockIdx.x == 0 && tid == 0) const_cast<PicpParams*>(P)->n_corr = n;
+  }
+  int nbad = 0;
+  // correspondence i from its index pair (picp_pack_kernel's body), kept for the later rounds
+  auto gather = [&](int i, float& x, float& y, float& z, float& u, float& v) {
+    const int m = gt.pairs[2 * i];       // .first  -> measurement (picp_solver.cpp:66)
+    const int w = gt.pairs[2 * i + 1];   // .second -> world point (picp_solver.cpp:67)
+    x = __int_as_float((int)VO_DROPPED_BITS); y = 0.f; z = 0.f; u = 0.f; v = 0.f;
+    if (m >= 0 && m < gt.n_meas && w >= 0 && w < gt.n_world) {
+      x = gt.world[3 * (size_t)w]; y = gt.world[3 * (size_t)w + 1]; z = gt.world[3 * (size_t)w + 2];
+      u = gt.meas[2 * (size_t)m]; v = gt.meas[2 * (size_t)m + 1];
+    } else {
+      ++nbad;
+    }
+    pk.arr(0)[i] = x; pk.arr(1)[i] = y; pk.arr(2)[i] = z; pk.arr(3)[i] = u; pk.arr(4)[i] = v;
+  };
   // camera and threshold: fetched here, while the partial rows are in flight, and pinned in scalar registers (left
   // alone the compiler re-loads them after the solve, on the chain)
   CamK cam = P->cam;
@@ -373,7 +427,10 @@ __device__ __forceinline__ void picp_round_body(const PicpParams* __restrict__ P
   int i = blockIdx.x * PICP_BLOCK + tid;
   bool have = !FINISH && i < n;
   float x = 0.f, y = 0.f, z = 0.f, u = 0.f, v = 0.f;
-  if (have) { x = pk.arr(0)[i]; y = pk.arr(1)[i]; z = pk.arr(2)[i]; u = pk.arr(3)[i]; v = pk.arr(4)[i]; }
+  if (have) {
+    if (gathers) gather(i, x, y, z, u, v);
+    else { x = pk.arr(0)[i]; y = pk.arr(1)[i]; z = pk.arr(2)[i]; u = pk.arr(3)[i]; v = pk.arr(4)[i]; }
+  }
 
   Pose T;
   if (PRE) {
@@ -395,7 +452,7 @@ __device__ __forceinline__ void picp_round_body(const PicpParams* __restrict__ P
     // statistics.  Fixed order => every wave of every workgroup gets the same bits.
     const int wave = tid >> 6, lane = tid & 63;
     float val = 0.f;                                         // this lane's entry of the system (picp_tail_direct)
-    if (lane < 45) {
+    if (lane < (TALLY ? 47 : 45)) {
       int slot;
       bool diag = false;
       if (lane < 36) {
@@ -404,7 +461,7 @@ __device__ __forceinline__ void picp_round_body(const PicpParams* __restrict__ P
         slot = (13 * lo - lo * lo) / 2 + (hi - lo);          // row-major upper triangle
         diag = r == c;
       } else {
-        slot = 21 + (lane - 36);                             // 21..26 b, 27..29 chi_in, chi_out, n_in
+        slot = 21 + (lane - 36);                             // 21..26 b, 27..29 chi_in, chi_out, n_in (TALLY: 30 dropped pairs, 31 their mark)
       }
       const float4* row = reinterpret_cast<const float4*>(s_acc + slot * STG_STRIDE);
       float tsum = 0.f;
@@ -416,6 +473,9 @@ __device__ __forceinline__ void picp_round_body(const PicpParams* __restrict__ P
       } else if (lane < 42) {
         val = -tsum;                                         // picp_solver.cpp:109 solve(-b)
         if (FINISH && blockIdx.x == 0 && wave == 0) S->b[lane - 36] = tsum;
+      } else if (TALLY && lane >= 45) {
+        const float mark = __shfl_down(tsum, 1);             // (lanes 45 and 46 are both here)
+        if (lane == 45 && mark > 0.f && blockIdx.x == 0 && wave == 0) S->n_bad = (int)(tsum + 0.5f);
       } else if (wave == 0) {
         s_stat[lane - 42] = tsum;
       }
@@ -448,6 +508,15 @@ __device__ __forceinline__ void picp_round_body(const PicpParams* __restrict__ P
     VO_STAMP(3);
     if (FINISH) return;
     __syncthreads();   // every wave is done with the staged rows: s_acc is reused by the reduction
+  } else if (gathers && gt.T0) {
+    // a pending pose reset: every workgroup takes the pose from T0 itself (workgroup 0 rewrites pose[0] meanwhile)
+    Pose T0p;
+#pragma unroll
+    for (int k = 0; k < 9; ++k) T0p.R[k] = gt.T0[(k % 3) + 4 * (k / 3)];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) T0p.t[k] = gt.T0[12 + k];
+    if (blockIdx.x == 0 && tid < 12) S->pose[0][tid] = tid < 9 ? gt.T0[(tid % 3) + 4 * (tid / 3)] : gt.T0[12 + (tid - 9)];
+    T = uniform_pose(T0p);
   } else {
     T = uniform_pose(load_pose12(S->pose[0]));
   }
@@ -460,15 +529,23 @@ __device__ __forceinline__ void picp_round_body(const PicpParams* __restrict__ P
     const float cx = x, cy = y, cz = z, cu = u, cv = v;
     i += stride;
     have = i < n;
-    if (have) { x = pk.arr(0)[i]; y = pk.arr(1)[i]; z = pk.arr(2)[i]; u = pk.arr(3)[i]; v = pk.arr(4)[i]; }
+    if (have) {
+      if (gathers) gather(i, x, y, z, u, v);
+      else { x = pk.arr(0)[i]; y = pk.arr(1)[i]; z = pk.arr(2)[i]; u = pk.arr(3)[i]; v = pk.arr(4)[i]; }
+    }
     picp_accumulate_t<PINHOLE, KEEP>(cam, T, thr, cx, cy, cz, cu, cv, acc);
   }
+  if (gathers && nbad) atomicAdd(&s_bad, nbad);             // (the reduction's barriers stand between this and the read below)
   VO_STAMP(4);
   const float tot = block_reduce_quad(acc, s_acc, s_part);
   VO_STAMP(5);
   if (tid < PICP_PSTRIDE) {
     float o = tot;   // slot 29 (inlier count) is an exact integer in float: < 2^24 correspondences
     if (tid >= NACC) o = 0.f;
+    if (gathers) {
+      if (tid == PICP_BAD_SLOT) o = (float)s_bad;
+      if (tid == PICP_GATHERED_SLOT) o = 1.f;
+    }
 #pragma unroll
     for (int r = 0; r < PICP_REPLICAS; ++r)
       partials[(size_t)r * PICP_SLOTS * ((nb + 255) & ~255) * PICP_PSTRIDE + ((size_t)(it & (PICP_SLOTS - 1)) * ((nb + 255) & ~255) + blockIdx.x) * PICP_PSTRIDE + tid] = o;
@@ -484,6 +561,24 @@ __global__ __launch_bounds__(PICP_BLOCK) void picp_round_kernel(const PicpParams
                                                                 float* pk_base, size_t pk_cap, float* partials, int it,
                                                                 int nb) {
   picp_round_body<PRE, FINISH, PINHOLE, KEEP, false>(P, S, PackedCorr{pk_base, pk_cap}, partials, it, nb, RoundBatch{});
+}
+
+// round 1 (or the finishing launch) of a solve, behind the round that may have gathered
+template <bool FINISH, bool PINHOLE, bool KEEP>
+__global__ __launch_bounds__(PICP_BLOCK) void picp_tally_round_kernel(const PicpParams* __restrict__ P, PicpState* S, float* pk_base,
+                                                                      size_t pk_cap, float* partials, int it, int nb) {
+  picp_round_body<true, FINISH, PINHOLE, KEEP, false, false, true>(P, S, PackedCorr{pk_base, pk_cap}, partials, it, nb, RoundBatch{});
+}
+
+// the first round of a solve, with the gather in it when `on` (a launch per solve: its arguments beyond the preloaded ones are
+// loaded)
+template <bool PINHOLE, bool KEEP>
+__global__ __launch_bounds__(PICP_BLOCK) void picp_gather_round_kernel(PicpParams* P, PicpState* S, float* pk_base, size_t pk_cap,
+                                                                       float* partials, int nb, const int32_t* pairs,
+                                                                       const int* d_n, int n_max, const float* world, int n_world,
+                                                                       const float* meas, int n_meas, const float* T0, int on) {
+  picp_round_body<false, false, PINHOLE, KEEP, false, true>(P, S, PackedCorr{pk_base, pk_cap}, partials, 0, nb, RoundBatch{},
+                                                            RoundGather{pairs, d_n, n_max, world, n_world, meas, n_meas, T0, on});
 }
 
 // a few problems per launch: problem = blockIdx.y
@@ -601,15 +696,25 @@ static bool picp_small_enabled() {
 }
 
 template <bool PINHOLE, bool KEEP>
-static void launch_rounds_t(hipStream_t st, const PicpParams* d_params, PicpState* d_state, PackedCorr pk,
-                            float* d_partials, int grid, int n_iters) {
-  hipLaunchKernelGGL((picp_round_kernel<false, false, PINHOLE, KEEP>), dim3(grid), dim3(PICP_BLOCK), 0, st,
-                     d_params, d_state, pk.base, pk.cap, d_partials, 0, grid);
-  for (int it = 1; it < n_iters; ++it)
+static void launch_rounds_t(hipStream_t st, PicpParams* d_params, PicpState* d_state, PackedCorr pk,
+                            float* d_partials, int grid, int n_iters, const PicpGather& g, int part) {
+  // round 0 gathers when g.on; the launch that reads its rows also takes the tally of dropped pairs
+  if (part != PICP_AFTER_ROUND0)
+    hipLaunchKernelGGL((picp_gather_round_kernel<PINHOLE, KEEP>), dim3(grid), dim3(PICP_BLOCK), 0, st, d_params, d_state, pk.base,
+                       pk.cap, d_partials, grid, g.pairs, g.d_n, g.n_max, g.world, g.n_world, g.meas, g.n_meas, g.T0, g.on);
+  if (part == PICP_ROUND0) return;
+  if (n_iters > 1)
+    hipLaunchKernelGGL((picp_tally_round_kernel<false, PINHOLE, KEEP>), dim3(grid), dim3(PICP_BLOCK), 0, st,
+                       d_params, d_state, pk.base, pk.cap, d_partials, 1, grid);
+  for (int it = 2; it < n_iters; ++it)
     hipLaunchKernelGGL((picp_round_kernel<true, false, PINHOLE, KEEP>), dim3(grid), dim3(PICP_BLOCK), 0, st,
                        d_params, d_state, pk.base, pk.cap, d_partials, it, grid);
-  hipLaunchKernelGGL((picp_round_kernel<true, true, false, false>), dim3(1), dim3(PICP_BLOCK), 0, st, d_params,
-                     d_state, pk.base, pk.cap, d_partials, n_iters, grid);
+  if (n_iters == 1)
+    hipLaunchKernelGGL((picp_tally_round_kernel<true, false, false>), dim3(1), dim3(PICP_BLOCK), 0, st, d_params,
+                       d_state, pk.base, pk.cap, d_partials, n_iters, grid);
+  else
+    hipLaunchKernelGGL((picp_round_kernel<true, true, false, false>), dim3(1), dim3(PICP_BLOCK), 0, st, d_params,
+                       d_state, pk.base, pk.cap, d_partials, n_iters, grid);
 }
 
 // ---- a chain of rounds without its finishing launch (vo_picp_one_round, capi.hip) ------------------------------------
@@ -644,11 +749,12 @@ hipError_t launch_picp_finish(hipStream_t st, const PicpParams* d_params, PicpSt
   return hipGetLastError();
 }
 
-hipError_t launch_picp_rounds(hipStream_t st, const PicpParams* d_params, PicpState* d_state,
+hipError_t launch_picp_rounds(hipStream_t st, PicpParams* d_params, PicpState* d_state,
                               PackedCorr pk, float* d_partials, int grid, int n_iters, bool pinhole,
-                              bool keep_outliers) {
+                              bool keep_outliers, const PicpGather& gt, int part) {
   if (n_iters <= 0) return hipSuccess;
   if (grid == 1 && picp_small_enabled()) {      // one workgroup's worth of correspondences (picp_grid_for): all rounds in one launch
+    if (part != PICP_WHOLE) return hipErrorInvalidValue;      // (never in parts: picp_rounds_chain(grid) is false)
     const dim3 g(1), b(PICP_BLOCK);
     if (pinhole && keep_outliers) hipLaunchKernelGGL((picp_small_kernel<true, true>), g, b, 0, st, d_params, d_state, pk.base, pk.cap, n_iters);
     else if (pinhole) hipLaunchKernelGGL((picp_small_kernel<true, false>), g, b, 0, st, d_params, d_state, pk.base, pk.cap, n_iters);
@@ -657,11 +763,11 @@ hipError_t launch_picp_rounds(hipStream_t st, const PicpParams* d_params, PicpSt
     return hipGetLastError();
   }
   if (pinhole) {
-    if (keep_outliers) launch_rounds_t<true, true>(st, d_params, d_state, pk, d_partials, grid, n_iters);
-    else launch_rounds_t<true, false>(st, d_params, d_state, pk, d_partials, grid, n_iters);
+    if (keep_outliers) launch_rounds_t<true, true>(st, d_params, d_state, pk, d_partials, grid, n_iters, gt, part);
+    else launch_rounds_t<true, false>(st, d_params, d_state, pk, d_partials, grid, n_iters, gt, part);
   } else {
-    if (keep_outliers) launch_rounds_t<false, true>(st, d_params, d_state, pk, d_partials, grid, n_iters);
-    else launch_rounds_t<false, false>(st, d_params, d_state, pk, d_partials, grid, n_iters);
+    if (keep_outliers) launch_rounds_t<false, true>(st, d_params, d_state, pk, d_partials, grid, n_iters, gt, part);
+    else launch_rounds_t<false, false>(st, d_params, d_state, pk, d_partials, grid, n_iters, gt, part);
   }
   return hipGetLastError();
 }

@@ -80,11 +80,29 @@ hipError_t launch_picp_pack(hipStream_t st, const int32_t* d_pairs, const int* d
                             const float* d_world, int n_world, const float* d_meas, int n_meas,
                             PackedCorr pk, PicpParams* d_params, PicpState* d_state, const float* d_T0);
 
+// What round 0 of a solve gathers (the arguments of launch_picp_pack): with `on` it does what launch_picp_pack does -- and the
+// memset of n_bad: the tally of dropped pairs travels in the partial rows, the next launch stores it -- before it linearises;
+// without, the packed arrays are taken as they are.
+struct PicpGather {
+  const int32_t* pairs = nullptr;
+  const int* d_n = nullptr;
+  int n_max = 0;
+  const float* world = nullptr;
+  int n_world = 0;
+  const float* meas = nullptr;
+  int n_meas = 0;
+  const float* T0 = nullptr;
+  int on = 0;
+};
 // Enqueue n_iters Gauss-Newton rounds (n_iters+1 launches).  d_partials holds
 // PICP_REPLICAS * PICP_SLOTS * round_up(grid,256) * PICP_PSTRIDE floats, zero-initialised.
-hipError_t launch_picp_rounds(hipStream_t st, const PicpParams* d_params, PicpState* d_state,
+// part: the whole solve, round 0 alone, or everything behind round 0 -- the host replays the latter as a captured graph behind
+// a plain launch of round 0, whose arguments are the caller's and change from call to call.  The parts exist where the rounds
+// are launches of their own (picp_rounds_chain(grid)).
+constexpr int PICP_WHOLE = 0, PICP_ROUND0 = 1, PICP_AFTER_ROUND0 = 2;
+hipError_t launch_picp_rounds(hipStream_t st, PicpParams* d_params, PicpState* d_state,
                               PackedCorr pk, float* d_partials, int grid, int n_iters, bool pinhole,
-                              bool keep_outliers);
+                              bool keep_outliers, const PicpGather& g = PicpGather{}, int part = PICP_WHOLE);
 
 int picp_grid_for(int n_corr, int n_cu);
 
