@@ -227,6 +227,14 @@ int vo_picp_get_system(vo_picp *s, float H[36], float b[6]);
  * launch.  Either pointer may be NULL. */
 int vo_picp_batch_set_form(vo_ctx *ctx, int form);
 int vo_picp_batch_info(vo_ctx *ctx, int *form, int *workgroups);
+/* Test support.  With VO_PICP_HELP_SCHEDULE="mode,mod,rem,round[,polls]" in the environment a form-4 call runs an
+ * instantiation of its kernel that makes chosen helper waves (or problems' own workgroups) late or absent by script
+ * (csrc/picp.hip; modes none, leave, stall, home-stall) and records, per problem: the chunks its own workgroup ended up
+ * computing itself (bit j: chunk j), its number of chunks, and how many of its helper waves returned before their last
+ * round.  The results of the call must be those of the undisturbed call bit for bit.  vo_picp_batch_help_info waits for
+ * the context's stream and copies that record of the LAST batched call out (n_problems entries each, any pointer may be
+ * NULL); VO_ERR_INVALID_ARG when that call did not run so, or n_problems is not its problem count. */
+int vo_picp_batch_help_info(vo_ctx *ctx, int n_problems, unsigned long long *own_chunks, int *n_chunks, int *left_early);
 int vo_picp_solve_batch_dev(vo_ctx *ctx, int n_problems, int rows, int cols, int z_near, int z_far,
                             const float K[9], float kernel_threshold, int keep_outliers,
                             const float *d_world_xyz, size_t world_stride, const float *d_meas_uv,

@@ -6,6 +6,8 @@ thresholds, outlier policy, projection (pinhole / with skew), round counts; per 
   * the call twice: the same bits (helper waves arrive when they arrive);
   * the call with every helper wave absent (VO_PICP_HELP_ABSENT: the problems' own workgroups stand in for all chunks): the
     same bits;
+  * the call under a random scripted schedule of late or absent waves (VO_PICP_HELP_SCHEDULE: the kernel's instantiation with
+    the scheduling hooks; none / leave / stall / home-stall, random waves, random round): the same bits;
   * problems that share data and starting pose: the same bits;
   * against the call in its other forms (one launch per round; one workgroup per problem without helpers; other chunks):
     poses within 3e-5 and the same inliers when no threshold is in play, within 3e-3 and a few flipped inliers otherwise;
@@ -23,7 +25,7 @@ ctx = vo.Context(0)
 lib = ctx.lib
 rng = np.random.default_rng(int(sys.argv[1]) if len(sys.argv) > 1 else 1)
 t_end = time.time() + (float(sys.argv[2]) if len(sys.argv) > 2 else 120)
-for k in ("VO_PICP_SHARE", "VO_PICP_HELP_KEEP", "VO_PICP_HELP_G", "VO_PICP_HELP_SLACK", "VO_PICP_HELP_ABSENT"):
+for k in ("VO_PICP_SHARE", "VO_PICP_HELP_KEEP", "VO_PICP_HELP_G", "VO_PICP_HELP_SLACK", "VO_PICP_HELP_ABSENT", "VO_PICP_HELP_SCHEDULE"):
     os.environ.pop(k, None)
 cases = fails = 0
 pool = {}
@@ -87,6 +89,12 @@ while time.time() < t_end:
     if again[0].tobytes() != ref[0].tobytes() or again[1].tobytes() != ref[1].tobytes(): why.append("run to run")
     alone = run(VO_PICP_HELP_ABSENT=1)
     if alone[0].tobytes() != ref[0].tobytes() or alone[1].tobytes() != ref[1].tobytes(): why.append("helpers absent")
+    mode = str(rng.choice(["none", "leave", "stall", "home-stall"]))
+    if mode == "home-stall" and iters < 2: mode = "leave"     # (a home holds back the pose of a round from 1 on)
+    mod = int(rng.choice([1, 2, 3, 5, 64]))
+    sched = "%s,%d,%d,%d,%d" % (mode, mod, int(rng.integers(0, mod)), int(rng.integers(1 if mode == "home-stall" else 0, iters)), int(rng.choice([8, 64])))
+    scripted = run(VO_PICP_HELP_SCHEDULE=sched)
+    if scripted[0].tobytes() != ref[0].tobytes() or scripted[1].tobytes() != ref[1].tobytes(): why.append("schedule " + sched)
     if twin and (ref[0][twin[0]].tobytes() != ref[0][twin[1]].tobytes() or ref[1][twin[0]].tobytes() != ref[1][twin[1]].tobytes()): why.append("twins")
     others = [run(form=1), run(VO_PICP_SHARE=0), run(VO_PICP_HELP_KEEP=int(rng.integers(2, 9)), VO_PICP_HELP_G=int(rng.integers(1, 9)))]
     # Another summation order gives rounding-level differences -- unless correspondences sit AT the kernel threshold (tight

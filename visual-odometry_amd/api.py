@@ -125,6 +125,14 @@ class Context:
         self.h2d(p, arr)
         return p
 
+    def picp_batch_help_info(self, n_problems: int):
+        """(own_chunks uint64, n_chunks int32, left_early int32) per problem of the last batched call, which ran with helper
+        waves under VO_PICP_HELP_SCHEDULE (vo_picp_batch_help_info; test support)"""
+        own = np.zeros(n_problems, np.uint64)
+        n_chunks, left = np.zeros(n_problems, np.int32), np.zeros(n_problems, np.int32)
+        _chk(self.lib.vo_picp_batch_help_info(self.h, C.c_int(n_problems), _ptr(own), _ptr(n_chunks), _ptr(left)))
+        return own, n_chunks, left
+
 
 class Event:
     """A point in one context's stream that another context can wait for (vo_event_*)."""

@@ -129,6 +129,7 @@ struct vo_ctx {
   int match_mode = 0; // 0 auto, 1 full scan, 2 bucket-pruned scan, 3 cell-hash search, 4 / 5 exact-duplicate pass first, then 2 / 3
   int batch_form = 0; // batched solver: 0 auto, 1 one launch per round, 2 one workgroup per problem
   int batch_last_form = 0, batch_last_wgs = 0;   // what the last batched call ran as (vo_picp_batch_info)
+  int batch_last_help_rows = 0, batch_last_problems = 0, batch_last_help_mode = 0;   // ... and where its helper record lies (vo_picp_batch_help_info)
   bool capturing = false;
   unsigned long long id = 0;   // unique per context ever created: an address can be reused, an id cannot
 };
@@ -1083,6 +1084,25 @@ int vo_picp_batch_info(vo_ctx* c, int* form, int* workgroups) {
   return VO_OK;
 }
 
+int vo_picp_batch_help_info(vo_ctx* c, int n_problems, unsigned long long* own, int* n_chunks, int* left_early) {
+  VO_REQUIRE(c, "ctx is null");
+  VO_NOT_CAPTURING(c);
+  VO_REQUIRE(c->batch_last_form == 4 && c->batch_last_help_mode != HELP_SCHED_OFF,
+             "the last batched call did not run with helper waves under VO_PICP_HELP_SCHEDULE: it left no record");
+  VO_REQUIRE(n_problems == c->batch_last_problems, "n_problems is not the last batched call's");
+  if (int r = set_device(c)) return r;
+  std::vector<unsigned long long> w((size_t)n_problems * 16);
+  VO_HIP_CHECK(hipMemcpyAsync(w.data(), c->batch_help.as<unsigned long long>() + (size_t)c->batch_last_help_rows * 32,
+                              sizeof(unsigned long long) * w.size(), hipMemcpyDeviceToHost, c->stream));
+  VO_HIP_CHECK(hipStreamSynchronize(c->stream));
+  for (int p = 0; p < n_problems; ++p) {
+    if (own) own[p] = w[(size_t)p * 16 + 12];
+    if (n_chunks) n_chunks[p] = (int)w[(size_t)p * 16 + 13];
+    if (left_early) left_early[p] = (int)w[(size_t)p * 16 + 14];
+  }
+  return VO_OK;
+}
+
 static int picp_solve_batch(vo_ctx* c, int n_problems, int rows, int cols, int z_near, int z_far,
                             const float K[9], float thr, int keep_outliers, const float* d_world,
                             size_t world_stride, const float* d_meas, size_t meas_stride,
@@ -1193,6 +1213,7 @@ static int picp_batch_prepare(vo_ctx* c, int n_problems, int rows, int cols, int
   }
   c->batch_last_form = a.exact ? 3 : a.states ? 1 : a.help_words ? 4 : 2;
   c->batch_last_wgs = a.states ? a.grid * n_problems : a.help_words ? a.help_grid : n_problems;
+  c->batch_last_help_rows = a.help_rows; c->batch_last_problems = n_problems; c->batch_last_help_mode = help_sched_mode(a.help_sched);
   return VO_OK;
 }
 

@@ -24,7 +24,9 @@
 // rows and waves -> workgroup partial.  No MFMA: the normal equations are a
 // tall-skinny accumulate (21+6+3 sums per correspondence), not a contraction.
 #include <type_traits>
+#include <stdio.h>
 #include <stdlib.h>
+#include <string.h>
 
 #include "vo_internal.h"
 
@@ -983,6 +985,20 @@ __global__ __launch_bounds__(PICP_BATCH_BLOCK) void picp_batch_kernel(BatchArgs 
 // (the home has gone on without it), or none within HELP_POLLS_HELPER polls, leaves.  Nothing assumes that the workgroups of
 // the launch are resident together (another stream's kernel may hold CUs): late helpers cost time, not correctness, and
 // every wave reaches its exit.  Two problems with the same data in one launch get the same bits (same keep, same C).
+//
+// HOOKS (a test instantiation, taken only when VO_PICP_HELP_SCHEDULE is set; the product instantiation holds none of it):
+// chosen waves are late or absent BY SCRIPT, so that every fallback above is reached in a fixed order of events, without a
+// clock and without a second kernel holding CUs.  BatchArgs::help_sched holds (mode, mod, rem, round):
+//   LEAVE       helper waves g with g % mod == rem return at the head of round `round` (earlier rounds delivered).
+//   STALL       those waves compute round `round` and hold the row back until the pose word of their problem carries the tag
+//               of two rounds on (of the end of the solve, if that comes first): the home has finished the round without the
+//               row.  Then they store it -- nobody reads it -- and go on: the next poll finds a tag beyond its round and leaves.
+//   HOME_STALL  homes p with p % mod == rem hold the pose of round `round` (>= 1) back until every helper wave of the problem
+//               has given up polling for it (those waves have help_polls polls for that pose instead of HELP_POLLS_HELPER),
+//               then publish it to nobody and stand in for every chunk.
+// Words 12-14 of a problem's 16 pose words (zeroed with the others before the launch) take the record: the home's final
+// `own`, its chunk count, and the helper waves of the problem that returned before their last round (each adds one as it
+// goes; a stalled home waits on this count, not on time).  vo_picp_batch_help_info reads them.
 constexpr int HELP_TRIP = PICP_BATCH_BLOCK * 4;
 constexpr int HELP_WAVES = PICP_BATCH_BLOCK / 64;
 constexpr int HELP_MAXP = 1024;                 // problems the partition tables hold (the form serves n_problems < CUs)
@@ -991,6 +1007,8 @@ constexpr int HELP_SLACK10 = 20;                // what a helper's round costs b
 constexpr int HELP_ITER100 = 71;                // a wave-trip on a CU full of helper waves, in hundredths of a home's trip
 constexpr unsigned HELP_POLLS_HOME = 1u << 9;   // ~0.6 us each: a few hundred microseconds
 constexpr unsigned HELP_POLLS_HELPER = 1u << 13;
+constexpr unsigned HELP_POLLS_STALLED_HOME = 1u << 16;     // (HOOKS) a scripted home's wait for its helpers to give up: ends on a count
+constexpr int HELP_INFO_OWN = 12, HELP_INFO_NCHUNK = 13, HELP_INFO_LEFT = 14;      // (HOOKS) the record among a problem's pose words (capi.hip reads it)
 typedef __attribute__((address_space(1))) unsigned long long help_word;      // a tagged word, in global memory
 
 // wave-trips per chunk for a home that keeps `keep` trips: what a helper wave finishes within the home's round
@@ -1044,7 +1062,7 @@ __device__ __forceinline__ void batch_stream(const CamK& cam, const Pose& T, flo
   }
 }
 
-template <bool PINHOLE, bool KEEP>
+template <bool PINHOLE, bool KEEP, bool HOOKS>
 __global__ __launch_bounds__(PICP_BATCH_BLOCK) void picp_batch_shared_kernel(BatchArgs a) {
   __shared__ float s_red[HELP_WAVES * 4 * 32];
   __shared__ float s_tot[32];
@@ -1059,6 +1077,8 @@ __global__ __launch_bounds__(PICP_BATCH_BLOCK) void picp_batch_shared_kernel(Bat
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int P = a.n_problems, H = (int)gridDim.x - P;
   const CamK cam = a.cam;
+  [[maybe_unused]] const int sched_mode = a.help_sched & 15, sched_mod = (a.help_sched >> 4) & 255, sched_rem = (a.help_sched >> 12) & 255,
+                             sched_round = (a.help_sched >> 20) & 4095;      // (HOOKS only)
   help_word* rows = (help_word*)a.help_words;
   help_word* posew = rows + (size_t)a.help_rows * 32;
   auto clamp_n = [&](int p) { int n = a.n_pairs[p]; if (n < 0) n = 0; if ((size_t)n > a.cap) n = (int)a.cap; return n; };
@@ -1161,9 +1181,24 @@ __global__ __launch_bounds__(PICP_BATCH_BLOCK) void picp_batch_shared_kernel(Bat
     int lo = 0, hi = P;                                     // the problem whose chunks include g
     while (hi - lo > 1) { const int mid = (lo + hi) >> 1; if (sgpr(s_chunkpre[mid]) <= g) lo = mid; else hi = mid; }
     const int p = lo, c = g - sgpr(s_chunkpre[p]);
+    bool scripted = false;                                  // (HOOKS) this wave, or for HOME_STALL its home, is in the script
+    if constexpr (HOOKS)
+      if (sched_mode >= HELP_SCHED_LEAVE && sched_mod > 0)
+        scripted = (sched_mode == HELP_SCHED_HOME_STALL ? p : g) % sched_mod == sched_rem;
+    auto leaves_early = [&] {
+      if constexpr (HOOKS)
+        if (lane == 0) __hip_atomic_fetch_add(posew + (size_t)p * 16 + HELP_INFO_LEFT, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    };
     for (int r = 0; r < a.n_iters; ++r) {
       float val = 0.f;
       bool ok = true;
+      unsigned poll_bound = HELP_POLLS_HELPER;
+      if constexpr (HOOKS) {
+        if (scripted && r == sched_round) {
+          if (sched_mode == HELP_SCHED_LEAVE) { leaves_early(); return; }
+          if (sched_mode == HELP_SCHED_HOME_STALL && a.help_polls > 0) poll_bound = (unsigned)a.help_polls;
+        }
+      }
       if (r == 0) {
         if (lane < 12) {
           if (a.T0) val = lane < 9 ? a.T0[16 * (size_t)p + (lane % 3) + 4 * (lane / 3)] : a.T0[16 * (size_t)p + 12 + (lane - 9)];
@@ -1171,7 +1206,7 @@ __global__ __launch_bounds__(PICP_BATCH_BLOCK) void picp_batch_shared_kernel(Bat
         }
       } else {
         ok = false;
-        for (unsigned polls = 0; polls < HELP_POLLS_HELPER; ++polls) {
+        for (unsigned polls = 0; polls < poll_bound; ++polls) {
           unsigned long long w = (unsigned long long)(unsigned)r << 32;
           if (lane < 12) w = __hip_atomic_load(posew + (size_t)p * 16 + lane, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
           const int tag = (int)(w >> 32);
@@ -1180,7 +1215,7 @@ __global__ __launch_bounds__(PICP_BATCH_BLOCK) void picp_batch_shared_kernel(Bat
           __builtin_amdgcn_s_sleep(2);
         }
       }
-      if (!ok) return;
+      if (!ok) { leaves_early(); return; }
       Pose T;
 #pragma unroll
       for (int i = 0; i < 9; ++i) T.R[i] = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(val), i));
@@ -1190,6 +1225,17 @@ __global__ __launch_bounds__(PICP_BATCH_BLOCK) void picp_batch_shared_kernel(Bat
       float tot;
       if (r == a.n_iters - 1) tot = chunk_sums(p, c, T, std::true_type{});
       else tot = chunk_sums(p, c, T, std::false_type{});
+      if constexpr (HOOKS) {
+        if (scripted && r == sched_round && sched_mode == HELP_SCHED_STALL) {
+          const int want = r + 2 < a.n_iters ? r + 2 : a.n_iters;      // the home has taken round r (and r + 1) without this row
+          for (unsigned polls = 0; polls < HELP_POLLS_HELPER; ++polls) {
+            unsigned long long w = (unsigned long long)(unsigned)want << 32;
+            if (lane < 12) w = __hip_atomic_load(posew + (size_t)p * 16 + lane, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if (__all((int)(w >> 32) >= want)) break;
+            __builtin_amdgcn_s_sleep(2);
+          }
+        }
+      }
       if (lane < 32)
         __hip_atomic_store(rows + (size_t)g * 32 + lane, ((unsigned long long)(unsigned)(r + 1) << 32) | (unsigned)__float_as_int(tot),
                            __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -1304,6 +1350,18 @@ __global__ __launch_bounds__(PICP_BATCH_BLOCK) void picp_batch_shared_kernel(Bat
       }
     }
     __syncthreads();
+    if constexpr (HOOKS) {
+      if (sched_mode == HELP_SCHED_HOME_STALL && sched_mod > 0 && p % sched_mod == sched_rem && it + 1 == sched_round &&
+          nchunk > 0 && !a.help_absent) {
+        if (tid == 0)
+          for (unsigned polls = 0; polls < HELP_POLLS_STALLED_HOME; ++polls) {
+            const unsigned long long gone = __hip_atomic_load(posew + (size_t)p * 16 + HELP_INFO_LEFT, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if (gone >= (unsigned long long)nchunk) break;
+            __builtin_amdgcn_s_sleep(2);
+          }
+        __syncthreads();
+      }
+    }
     if (nchunk > 0 && tid < 12)                              // the pose of round it + 1 (after the last round: lets late helpers go)
       __hip_atomic_store(posew + (size_t)p * 16 + tid, ((unsigned long long)(unsigned)(it + 1) << 32) | (unsigned)__float_as_int(s_pose[tid]),
                          __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -1322,6 +1380,10 @@ __global__ __launch_bounds__(PICP_BATCH_BLOCK) void picp_batch_shared_kernel(Bat
     if (a.n_iters <= 0 && a.stats_out) {
       float* so = a.stats_out + 4 * (size_t)p;
       so[0] = so[1] = so[2] = so[3] = 0.f;
+    }
+    if constexpr (HOOKS) {
+      posew[(size_t)p * 16 + HELP_INFO_OWN] = own;
+      posew[(size_t)p * 16 + HELP_INFO_NCHUNK] = (unsigned long long)nchunk;
     }
   }
 }
@@ -1564,10 +1626,28 @@ static hipError_t launch_picp_batch_solve(hipStream_t st, const BatchArgs& a);
 // The shared form (picp_batch_shared_kernel) for calls that leave CUs without a problem: from 6 trips per problem on (below,
 // a home's round is too short for a hand-over to pay).  VO_PICP_SHARE=0 in the environment keeps every call on
 // picp_batch_kernel; VO_PICP_HELP_KEEP / _G / _SLACK (tenths of a trip) pin what the kernel otherwise derives.
-struct HelpEnv { int share, keep, g, slack10, absent; };
+// VO_PICP_HELP_SCHEDULE="mode,mod,rem,round[,polls]" (mode: none, leave, stall, home-stall) takes the instantiation with the
+// scheduling hooks and scripts late or absent waves (tests/test_gpu_help_schedule.py); a value that does not parse is "none".
+struct HelpEnv { int share, keep, g, slack10, absent, mode, mod, rem, round, polls; };
 static HelpEnv help_env() {      // read per call (a batched call is milliseconds; tests flip these in-process)
   auto num = [](const char* name, int dflt) { const char* v = getenv(name); return v && v[0] ? atoi(v) : dflt; };
-  return HelpEnv{num("VO_PICP_SHARE", 1), num("VO_PICP_HELP_KEEP", 0), num("VO_PICP_HELP_G", 0), num("VO_PICP_HELP_SLACK", 0), num("VO_PICP_HELP_ABSENT", 0)};
+  HelpEnv e{num("VO_PICP_SHARE", 1), num("VO_PICP_HELP_KEEP", 0), num("VO_PICP_HELP_G", 0), num("VO_PICP_HELP_SLACK", 0), num("VO_PICP_HELP_ABSENT", 0),
+            HELP_SCHED_OFF, 1, 0, 0, 64};
+  const char* v = getenv("VO_PICP_HELP_SCHEDULE");
+  if (v && v[0]) {
+    char name[16] = {0};
+    int mod = 1, rem = 0, round = 0, polls = 64;
+    const int got = sscanf(v, "%15[a-z-],%d,%d,%d,%d", name, &mod, &rem, &round, &polls);
+    e.mode = HELP_SCHED_NONE;
+    const int mode = !strcmp(name, "leave") ? HELP_SCHED_LEAVE : !strcmp(name, "stall") ? HELP_SCHED_STALL
+                   : !strcmp(name, "home-stall") ? HELP_SCHED_HOME_STALL : HELP_SCHED_NONE;
+    if (mode != HELP_SCHED_NONE && got >= 4 && mod >= 1 && mod <= HELP_SCHED_MAX_MOD && rem >= 0 && rem < mod &&
+        round >= (mode == HELP_SCHED_HOME_STALL ? 1 : 0) && round <= HELP_SCHED_MAX_ROUND) {
+      e.mode = mode; e.mod = mod; e.rem = rem; e.round = round;
+      e.polls = polls < 1 ? 1 : polls > (int)HELP_POLLS_HELPER ? (int)HELP_POLLS_HELPER : polls;
+    }
+  }
+  return e;
 }
 bool picp_batch_shares(int n_problems, size_t cap, int n_iters, int n_cu) {
   // up to 0.65 problems per CU: beyond, the homes alone already draw what the memory side delivers (200 x 50k: 5.9 TB/s out of
@@ -1581,6 +1661,7 @@ void picp_help_args(BatchArgs& a, unsigned long long* words, int n_cu) {
   a.help_words = words; a.help_grid = words ? n_cu : 0; a.help_rows = words ? picp_help_rows(a.n_problems, n_cu) : 0;
   const HelpEnv e = help_env();
   a.help_keep = e.keep; a.help_g = e.g; a.help_slack10 = e.slack10; a.help_absent = e.absent;
+  a.help_sched = words ? help_sched_pack(e.mode, e.mod, e.rem, e.round) : HELP_SCHED_OFF; a.help_polls = e.polls;
 }
 
 hipError_t launch_picp_batch(hipStream_t st, const BatchArgs& a) {
@@ -1613,10 +1694,17 @@ static hipError_t launch_picp_batch_solve(hipStream_t st, const BatchArgs& a) {
     hipError_t e = hipMemsetAsync(a.help_words, 0, sizeof(unsigned long long) * ((size_t)a.help_rows * 32 + (size_t)a.n_problems * 16), st);
     if (e != hipSuccess) return e;
     const dim3 g(a.help_grid), b(PICP_BATCH_BLOCK);
-    if (ph && !keep) hipLaunchKernelGGL((picp_batch_shared_kernel<true, false>), g, b, 0, st, a);
-    else if (ph) hipLaunchKernelGGL((picp_batch_shared_kernel<true, true>), g, b, 0, st, a);
-    else if (!keep) hipLaunchKernelGGL((picp_batch_shared_kernel<false, false>), g, b, 0, st, a);
-    else hipLaunchKernelGGL((picp_batch_shared_kernel<false, true>), g, b, 0, st, a);
+    if (help_sched_mode(a.help_sched) != HELP_SCHED_OFF) {    // the test instantiation (VO_PICP_HELP_SCHEDULE)
+      if (ph && !keep) hipLaunchKernelGGL((picp_batch_shared_kernel<true, false, true>), g, b, 0, st, a);
+      else if (ph) hipLaunchKernelGGL((picp_batch_shared_kernel<true, true, true>), g, b, 0, st, a);
+      else if (!keep) hipLaunchKernelGGL((picp_batch_shared_kernel<false, false, true>), g, b, 0, st, a);
+      else hipLaunchKernelGGL((picp_batch_shared_kernel<false, true, true>), g, b, 0, st, a);
+      return hipGetLastError();
+    }
+    if (ph && !keep) hipLaunchKernelGGL((picp_batch_shared_kernel<true, false, false>), g, b, 0, st, a);
+    else if (ph) hipLaunchKernelGGL((picp_batch_shared_kernel<true, true, false>), g, b, 0, st, a);
+    else if (!keep) hipLaunchKernelGGL((picp_batch_shared_kernel<false, false, false>), g, b, 0, st, a);
+    else hipLaunchKernelGGL((picp_batch_shared_kernel<false, true, false>), g, b, 0, st, a);
     return hipGetLastError();
   }
   const dim3 g(a.n_problems), b(PICP_BATCH_BLOCK);

@@ -144,10 +144,13 @@ struct BatchArgs {
   int pack_gx;         // workgroups per problem of the gather pass
   int* n_bad;          // n_problems counters (zeroed by the caller): correspondences dropped for a bad index, or null
   int exact;           // reference-order form (picp_exact_kernel): one workgroup per problem, sequential sums
+  int help_sched;      // test hook (VO_PICP_HELP_SCHEDULE, picp.hip: help_env): scripted late or absent waves, packed (help_sched_*
+                       //   below).  Mode 0 takes the product instantiation, any other the one with the hooks compiled in.
   const float* X_world;  // n_problems x 16 (column-major) or null: the gather applies X * p to every world point it fetches
                          //   (X_curr * triangulated_pc of vo_complete.cpp:159 without the pass that writes the moved cloud)
   int prepacked;         // the packed arrays are already filled (the join's writing pass gathered through its own pairs:
                          //   launch_join_batch with a sink): no gather pass
+  int help_polls;        // test hook, mode home-stall: the polls a helper wave of a stalled home has for the withheld pose
   // fewer problems than CUs (picp_batch_shared_kernel): the workgroups beyond n_problems take trips off the problems' own
   unsigned long long* help_words;   // picp_help_words(n_problems, n_cu) tagged words, zeroed by launch_picp_batch; null: form off
   int help_grid;         // workgroups of the launch (n_problems + helpers), 0: form off
@@ -156,6 +159,17 @@ struct BatchArgs {
   int help_keep, help_g, help_slack10;   // 0: the kernel's own choice (experiments: VO_PICP_HELP_KEEP / _G / _SLACK): trips a home keeps,
                          //   wave-trips per chunk, a helper's overhead per round in tenths of a trip
 };
+// The two test-hook words sit where the struct had padding: the kernels' hidden arguments follow it in the kernarg segment,
+// so its size is part of the instruction stream of every kernel that takes it.
+static_assert(sizeof(BatchArgs) == 272, "BatchArgs grew: the offsets of the hidden kernel arguments move in every kernel that takes it");
+// help_sched: mode | mod << 4 | rem << 12 | round << 20
+enum { HELP_SCHED_OFF = 0, HELP_SCHED_NONE = 1, HELP_SCHED_LEAVE = 2, HELP_SCHED_STALL = 3, HELP_SCHED_HOME_STALL = 4 };
+constexpr int HELP_SCHED_MAX_MOD = 255, HELP_SCHED_MAX_ROUND = 4095;
+inline int help_sched_pack(int mode, int mod, int rem, int round) { return mode | mod << 4 | rem << 12 | round << 20; }
+#if defined(__HIPCC__)
+__host__ __device__
+#endif
+inline int help_sched_mode(int s) { return s & 15; }
 hipError_t launch_picp_batch(hipStream_t st, const BatchArgs& a);
 // the shared form: whether it serves this call, and what it needs (rows of 32 words, then 16 words per problem)
 bool picp_batch_shares(int n_problems, size_t cap, int n_iters, int n_cu);
