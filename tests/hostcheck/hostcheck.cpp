@@ -96,6 +96,23 @@ void hc_ldlt6_ordered(const float* A_colmajor, const float* rhs, float* x) {
 }
 void hc_sincos_small(float v, float* s, float* c) { sincos_small(v, *s, *c); }
 
+// The pieces of the round kernels' tail (picp.hip, picp_tail_direct) put together as that function puts them together:
+// ldlt6_solve_ordered on H itself with -b, ONE branch for the three angles (sincosf when any exceeds 0.5 rad, the polynomial
+// otherwise), v2t_from_sincos, T <- dT * T.  H col-major with the damping on its diagonal.
+void hc_picp_tail_fast(const float* H_colmajor, const float* b, const float* T16, float* T16_out) {
+  float B[6][6], y[6];
+  for (int r = 0; r < 6; ++r) { y[r] = -b[r]; for (int c = 0; c < 6; ++c) B[r][c] = c <= r ? H_colmajor[r + 6 * c] : 0.f; }
+  ldlt6_solve_ordered(B, y);
+  float sn[3], cs[3];
+  const bool big = !(fabsf(y[3]) <= 0.5f && fabsf(y[4]) <= 0.5f && fabsf(y[5]) <= 0.5f);
+  for (int m = 0; m < 3; ++m) {
+    if (big) sincosf(y[3 + m], &sn[m], &cs[m]);
+    else sincos_small(y[3 + m], sn[m], cs[m]);
+  }
+  const Pose dT = v2t_from_sincos(y, sn[0], cs[0], sn[1], cs[1], sn[2], cs[2]);
+  pose_to_T16(pose_mul(dT, pose_from_T16(T16)), T16_out);
+}
+
 void hc_ldlt2(const float* m, const float* rhs, float* x) { ldlt2_solve(m[0], m[1], m[3], rhs[0], rhs[1], x[0], x[1]); }
 
 int hc_triangulate_point(const float* d1, const float* d2, const float* p2, float* p) {

@@ -31,7 +31,12 @@ R the Cholesky factor of H64 + I: a 6x6 LDL^T / Cholesky solve has the backward 
 Accuracy and Stability, thm 10.4), 3n + 1 = 19 = C_LDLT.  dx of a GPU pose is read off T_out T0^-1 (dx_of); the pose
 composition's own rounding -- sin / cos (2 ulp), Rx Ry Rz (two products and an add per entry: 3), the 3-term product with T0
 and the added translation (4) -- is C_POSE = 9 roundings of |v2t(dx)| |T0| per entry of T_out, carried through |T0^-1| and
-through the derivatives of the angle extraction."""
+through the derivatives of the angle extraction.
+
+The tail alone.  A solver that returns the float32 H (damping included) and b it solved is held more sharply: tail() is the
+same step with tol_H = tol_b = 0 -- the float64 solution of THAT system composed with the pose before the round, bounded by
+the LDL^T and composition terms only, no sum over correspondences in it (check_tail; ceiling: picp_cases.ceiling_tail).
+tail32() restates the tail in float32, one rounding per operation, and takes planted faults (TAIL_FAULTS)."""
 import numpy as np
 
 from np_restatement import v2t_euler
@@ -262,24 +267,15 @@ def rho_system(ref, H, b, chi_in, chi_out, n_in=None, damping=0.0):
                 n_in_ok=True, delta=D[k])
 
 
-def step(ref, T0, C, delta=None):
-    """one damped Gauss-Newton step from system()'s float64 result: dx64, T1_64 = v2t(dx64) T0 and the entrywise bound of dx
-    for an evaluation that keeps rho <= C.  delta: a row of combos() -- the ambiguous correspondences decided that way, no
-    allowance; None: the float64 decisions with the allowances E_X."""
+def _solve_bounds(Hd, b, T0):
+    """what step() and tail() share: dx = Hd^-1 (-b) in float64, |Hd^-1|, the LDL^T backward-error term and the pose
+    composition's term of the bound (module docstring), T1 = v2t(dx) T0"""
     T0 = np.asarray(T0, np.float64)
-    H, b = ref["H"], ref["b"]
-    E_H, E_b = ref["E_H"], ref["E_b"]
-    if delta is not None:
-        H = H + _unpack_H(delta); b = b + delta[21:27]
-        E_H, E_b = 0.0, 0.0
-    Hd = H + np.eye(6)
     dx = np.linalg.solve(Hd, -b)
     Hi = np.abs(np.linalg.inv(Hd))
-    tol_H = C * U * (ref["A_H"] + np.eye(6)) + E_H
-    tol_b = C * U * ref["A_b"] + E_b
     R = np.linalg.cholesky(Hd).T
     adx = np.abs(dx)
-    tol = Hi @ (tol_b + tol_H @ adx) + C_LDLT * U * (Hi @ ((np.abs(R.T) @ np.abs(R)) @ adx))
+    tol_ldlt = C_LDLT * U * (Hi @ ((np.abs(R.T) @ np.abs(R)) @ adx))
     dT = v2t_euler(dx)
     # what the composition's own rounding moves dx_of(T_out, T0) by
     E_T = C_POSE * U * (np.abs(dT) @ np.abs(T0))
@@ -287,7 +283,121 @@ def step(ref, T0, C, delta=None):
     cy = max(abs(np.cos(dx[4])), 1e-3)
     ext = np.array([E_dT[0, 3], E_dT[1, 3], E_dT[2, 3], (E_dT[1, 2] + E_dT[2, 2]) / cy, E_dT[0, 2] / cy,
                     (E_dT[0, 1] + E_dT[0, 0]) / cy])
-    return dict(dx=dx, T1=dT @ T0, tol=tol + ext, tol_system=tol, tol_pose=ext)
+    return dict(dx=dx, adx=adx, Hi=Hi, T1=dT @ T0, tol_ldlt=tol_ldlt, tol_pose=ext)
+
+
+def step(ref, T0, C, delta=None):
+    """one damped Gauss-Newton step from system()'s float64 result: dx64, T1_64 = v2t(dx64) T0 and the entrywise bound of dx
+    for an evaluation that keeps rho <= C.  delta: a row of combos() -- the ambiguous correspondences decided that way, no
+    allowance; None: the float64 decisions with the allowances E_X."""
+    H, b = ref["H"], ref["b"]
+    E_H, E_b = ref["E_H"], ref["E_b"]
+    if delta is not None:
+        H = H + _unpack_H(delta); b = b + delta[21:27]
+        E_H, E_b = 0.0, 0.0
+    s = _solve_bounds(H + np.eye(6), b, T0)
+    tol_H = C * U * (ref["A_H"] + np.eye(6)) + E_H
+    tol_b = C * U * ref["A_b"] + E_b
+    tol = s["Hi"] @ (tol_b + tol_H @ s["adx"]) + s["tol_ldlt"]
+    return dict(dx=s["dx"], T1=s["T1"], tol=tol + s["tol_pose"], tol_system=tol, tol_pose=s["tol_pose"])
+
+
+def tail(H32, b32, T_at):
+    """the solver's tail as a pure function of the float32 system it solved (H with the damping on its diagonal, b:
+    vo_picp_get_system) and the pose before the round: the float64 step dx = H^-1 (-b), T1 = v2t(dx) T_at, and what is left
+    of step()'s bound when H and b are exact (tol_H = tol_b = 0) -- the LDL^T backward error and the composition's
+    roundings.  No sum over correspondences is in it."""
+    s = _solve_bounds(np.asarray(H32, np.float64), np.asarray(b32, np.float64), T_at)
+    return dict(dx=s["dx"], T1=s["T1"], tol=s["tol_ldlt"] + s["tol_pose"], tol_ldlt=s["tol_ldlt"], tol_pose=s["tol_pose"])
+
+
+def check_tail(H32, b32, T_at, T_out):
+    """-> max |dx_of(T_out, T_at) - dx64| / tail()'s bound; inf for a pose that is not finite"""
+    t = tail(H32, b32, T_at)
+    if not np.isfinite(np.asarray(T_out, np.float64)).all():
+        return float("inf")
+    d = np.abs(dx_of(T_out, T_at) - t["dx"])
+    with np.errstate(all="ignore"):
+        r = np.where(t["tol"] > 0, d / t["tol"], np.where(d == 0, 0.0, np.inf))
+    return float(np.max(r)) if np.isfinite(r).all() else float("inf")
+
+
+TAIL_FAULTS = ("swap_angles", "compose_order", "drop_translation", "recip_17ulp", "poly_everywhere", "stale_pose", "b_sign")
+
+
+def _sincos_poly32(x):
+    """csrc/vo_math.h sincos_small with every operation rounded once (no FMA)"""
+    f = np.float32
+    z = x * x
+    ps = f(-1.9515295891e-4) * z + f(8.3321608736e-3)
+    ps = ps * z + f(-1.6666654611e-1)
+    s = (ps * z) * x + x
+    pc = f(2.443315711809948e-5) * z + f(-1.388731625493765e-3)
+    pc = pc * z + f(4.166664568298827e-2)
+    c = (pc * z) * z + (f(-0.5) * z + f(1.0))
+    return f(s), f(c)
+
+
+def tail32(H32, b32, T_at, fault=None, T_prev=None):
+    """the tail in float32, one rounding per operation, written out like system(dt=float32): LDL^T of H in the natural
+    order without pivoting (unfused products, a true division for each pivot's reciprocal), forward / diagonal / backward
+    substitution of -b, float32 sin / cos, R = Rx Ry Rz, T_out = v2t(dx) T_at with 3-term products and the translation added
+    last.  -> T_out (4x4 float32).  `fault` plants one of TAIL_FAULTS; stale_pose composes with T_prev, the pose one round
+    older."""
+    f = np.float32
+    assert fault is None or fault in TAIL_FAULTS, fault
+    B = np.array(H32, f).reshape(6, 6).copy()
+    b = np.asarray(b32, f)
+    y = [b[i] if fault == "b_sign" else -b[i] for i in range(6)]
+    T = np.array(T_prev if fault == "stale_pose" else T_at, f).reshape(4, 4)
+    inv = [f(0)] * 6
+    with np.errstate(all="ignore"):
+        for k in range(6):
+            if k > 0:
+                tmp = [B[j, j] * B[k, j] for j in range(k)]
+                acc = f(0)
+                for j in range(k):
+                    acc = acc + B[k, j] * tmp[j]
+                B[k, k] = B[k, k] - acc
+                for i in range(k + 1, 6):
+                    acc = f(0)
+                    for j in range(k):
+                        acc = acc + B[i, j] * tmp[j]
+                    B[i, k] = B[i, k] - acc
+            inv[k] = f(1) / B[k, k] if abs(B[k, k]) > f(1.17549435e-38) else f(0)
+            if fault == "recip_17ulp":
+                inv[k] = inv[k] * f(1 + 2e-6)
+            for i in range(k + 1, 6):
+                B[i, k] = B[i, k] * inv[k]
+        for i in range(1, 6):
+            for j in range(i):
+                y[i] = y[i] - B[i, j] * y[j]
+        for i in range(6):
+            y[i] = y[i] * inv[i]
+        for i in range(4, -1, -1):
+            for j in range(i + 1, 6):
+                y[i] = y[i] - B[j, i] * y[j]
+        ax, ay, az = (y[4], y[3], y[5]) if fault == "swap_angles" else (y[3], y[4], y[5])
+        if fault == "poly_everywhere":
+            (sx, cx), (sy, cy), (sz, cz) = _sincos_poly32(ax), _sincos_poly32(ay), _sincos_poly32(az)
+        else:
+            sx, cx, sy, cy, sz, cz = np.sin(ax), np.cos(ax), np.sin(ay), np.cos(ay), np.sin(az), np.cos(az)
+        # Rx Ry = [cy 0 sy; sx sy  cx  -sx cy; -cx sy  sx  cx cy], then times Rz (structural zeros and ones dropped: exact)
+        a10, a12, a20, a22 = sx * sy, -sx * cy, -cx * sy, cx * cy
+        dT = np.eye(4, dtype=f)
+        dT[0, :3] = [cy * cz, cy * -sz, sy]
+        dT[1, :3] = [a10 * cz + cx * sz, a10 * -sz + cx * cz, a12]
+        dT[2, :3] = [a20 * cz + sx * sz, a20 * -sz + sx * cz, a22]
+        dT[:3, 3] = y[:3]
+        A, Bm = (T, dT) if fault == "compose_order" else (dT, T)
+        out = np.eye(4, dtype=f)
+        for r in range(3):
+            for c in range(4):
+                e = A[r, 0] * Bm[0, c] + (A[r, 1] * Bm[1, c] + A[r, 2] * Bm[2, c])
+                if c == 3 and fault != "drop_translation":
+                    e = e + A[r, 3]
+                out[r, c] = e
+    return out
 
 
 def dx_of(T_out, T0):

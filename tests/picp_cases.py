@@ -56,7 +56,7 @@ def frame(n):
     world_g, G = general_world(rng, fp["model"])
     T_g = (synth.random_isometry(rng, 0.01, 0.02).astype(np.float64) @ G).astype(np.float32)
     poses = dict(identity=(np.eye(4, dtype=np.float32), fp["model"]), small=(small, fp["model"]), general=(T_g, world_g))
-    return dict(fp=fp, corr=corr, poses=poses, K=dict(pinhole=np.asarray(fp["K"], np.float32), general=general_K(fp["K"])))
+    return dict(fp=fp, corr=corr, poses=poses, G=G, K=dict(pinhole=np.asarray(fp["K"], np.float32), general=general_K(fp["K"])))
 
 
 def case_ids():
@@ -88,8 +88,86 @@ def case(cid):
     """-> dict(K, T0, world, meas, corr, thr, keep): the arguments of picp_budget.system after K and T"""
     n, pose, thr, keep, k = cid
     f = frame(n)
-    T0, world = f["poses"][pose]
+    if pose in LARGE:
+        T0, world = large_start(n, LARGE_AT.get((pose, n), LARGE[pose])), f["poses"]["general"][1]
+    else:
+        T0, world = f["poses"][pose]
     return dict(K=f["K"][k], T0=T0, world=world, meas=f["fp"]["cur_pts"], corr=f["corr"], thr=thr, keep=keep)
+
+
+# ---- the cases of the tail check (tests/test_picp_tail_cpu.py, tests/test_gpu_picp_tail.py) beside the matrix above --------
+# A large-step case starts at T0 = v2t(d)^-1 X_gt G in the general world: the first Gauss-Newton step is then about d.  With
+# (10000, drop) whatever the offset moves more than 100 px, or out of the image, is dropped; the rest takes the step.  What
+# each d is FOR is a condition on the float64 first step (large_conditions), asserted on the reference side, not assumed:
+# the solver's tail takes sincosf for all three angles when ANY of them exceeds 0.5 rad and its polynomial otherwise.
+# An x or y angle alone moves every pixel by f tan(angle) > 100 px and leaves no inlier; the translation -angle x z0 about the
+# other axis cancels that at the depth z0 = 4, so the pairs around that depth stay inside the threshold and the step keeps its angle.
+LARGE = {
+    "large-x": (0.02, 2.48, 0.01, 0.62, 0.03, -0.05),        # only the x angle above 0.5
+    "large-y": (-2.48, 0.03, 0.02, -0.04, 0.62, 0.06),       # only the y angle
+    "large-z": (0.03, 0.02, -0.02, 0.05, -0.04, 0.70),       # only the z angle
+    "large-mid": (-2.24, 1.44, 0.0, 0.36, 0.56, 0.36),       # all three in (0.3, 0.5]: the polynomial at the top of its range
+    "large-two": (-2.4, 0.02, 0.02, 0.15, 0.60, -0.75),      # two above 0.5
+    "large-roll": (0.0, 0.0, -1.5, 0.0, 0.0, 1.4),           # the wrong-branch case: a roll, and closer by 1.5 (a GN step of a
+}                                                            # pure roll is about sin: never above 1 rad; the scale lifts it)
+LARGE_AT = {("large-two", 257): (-2.22, -2.16, -0.04, -0.53, 0.55, 0.0),     # a roll of 0.6 leaves 257 pairs too few inliers,
+            ("large-z", 257): (0.03, 0.02, -0.02, 0.05, -0.04, 0.60)}        # one of 0.7 leaves 54
+LARGE_SIZES = (257, 4097, 65537)                   # the one-launch kernel, and two sizes of the round kernels
+TINY_SIZES = (1, 2, 3, 5, 15)                      # near-singular without the damping: cond(H) up to 4e5
+MIN_INLIERS = 64
+WRONG_BRANCH = ("large-roll",)
+
+
+def large_start(n, d):
+    f = frame(n)
+    from np_restatement import v2t_euler
+    D = v2t_euler(np.asarray(d, np.float64))
+    return (np.linalg.inv(D) @ f["fp"]["X_gt"].astype(np.float64) @ f["G"]).astype(np.float32)
+
+
+def large_conditions(kind, ang):
+    """what the float64 first-step angles (x, y, z) of a large-step case of this kind must satisfy"""
+    a = np.abs(np.asarray(ang, np.float64))
+    if kind in ("large-x", "large-y", "large-z"):
+        i = "xyz".index(kind[-1])
+        return bool(a[i] > 0.5 and (np.delete(a, i) < 0.5).all())
+    if kind == "large-mid":
+        return bool(((a > 0.3) & (a <= 0.5)).all())
+    if kind == "large-two":
+        return bool((a > 0.5).sum() == 2)
+    return True
+
+
+def tail_case_ids():
+    """the new cases: every large-step kind x LARGE_SIZES with (10000, drop), K alternating; the tiny problems at the
+    general pose with a small step"""
+    ids = []
+    for i, n in enumerate(LARGE_SIZES):
+        for j, kind in enumerate(LARGE):
+            if kind in WRONG_BRANCH and n != 4097:
+                continue
+            ids.append((n, kind, 10000.0, False, "general" if (i + j) % 2 else "pinhole"))
+    for i, n in enumerate(TINY_SIZES):
+        ids.append((n, "general", 10000.0, False, "general" if i % 2 else "pinhole"))
+    return ids
+
+
+BATCH_N, BATCH_SEED = 24000, 7300
+BATCH_KINDS = ("large-x", "large-y", "large-z", "large-mid", "large-two", "large-roll")
+
+
+@functools.lru_cache(maxsize=None)
+def large_batch():
+    """P = 6 large-step problems on ONE 24 000-pair frame (Batch(vo, ctx, BATCH_N, [BATCH_N] * 6, seed=BATCH_SEED, world=...,
+    T0=...) generates the same frame): the world moved by G^-1, problem p starts at v2t(d_p)^-1 X_gt G, one d per kind.
+    -> dict(fp, pairs, world, T0)"""
+    fp = synth.frame_pair(BATCH_N, seed=BATCH_SEED, distractors=BATCH_N // 50)
+    rng = np.random.default_rng(BATCH_SEED)
+    world, G = general_world(rng, fp["model"])
+    from np_restatement import v2t_euler
+    X = fp["X_gt"].astype(np.float64) @ G
+    T0 = np.stack([np.linalg.inv(v2t_euler(np.asarray(LARGE[k], np.float64))) @ X for k in BATCH_KINDS]).astype(np.float32)
+    return dict(fp=fp, pairs=corr_of(fp), world=world, T0=T0)
 
 
 def system_args(c, T=None):
@@ -143,15 +221,33 @@ class Batch:
 
 
 @functools.lru_cache(maxsize=None)
+def _systems(cid):
+    import picp_budget as pb
+    a = system_args(case(cid))
+    return pb.system(*a), pb.system(*a, dt=np.float32)
+
+
+@functools.lru_cache(maxsize=None)
 def reference(cid):
     """round 0 of a case on the reference side: the float64 system with its budgets, and rho of the float32 restatement with
     pairwise sums (picp_budget.system(dt=float32)) against it"""
     import picp_budget as pb
-    a = system_args(case(cid))
-    ref = pb.system(*a)
-    f = pb.system(*a, dt=np.float32)
+    ref, f = _systems(cid)
     r32 = pb.rho_system(ref, f["H"], f["b"], f["chi_in"], f["chi_out"], f["n_in"])
     return ref, r32
+
+
+@functools.lru_cache(maxsize=None)
+def tail_reference(cid):
+    """round 0 of a case through the tail on the reference side: the float32 restatement's system with the damping on its
+    diagonal (H32, b32 -- what a float32 solver would hand its tail), the float64 step of THAT system with its bound
+    (picp_budget.tail) and the ratio of the float32 restatement of the tail (picp_budget.tail32) against it"""
+    import picp_budget as pb
+    f = _systems(cid)[1]
+    H32 = (f["H"] + np.eye(6, dtype=np.float32)).astype(np.float32)
+    b32 = f["b"].astype(np.float32)
+    T0 = case(cid)["T0"]
+    return dict(H=H32, b=b32, tail=pb.tail(H32, b32, T0), ratio=pb.check_tail(H32, b32, T0, pb.tail32(H32, b32, T0)))
 
 
 @functools.lru_cache(maxsize=None)
@@ -159,3 +255,12 @@ def ceiling():
     """C: 4 times the largest rho, over H, b and the chi^2 sums of the whole case matrix, of the reference's formulas
     evaluated in float32 with pairwise sums.  Measured on the reference side only, never on the kernels."""
     return 4.0 * max(reference(cid)[1]["worst"] for cid in case_ids())
+
+
+@functools.lru_cache(maxsize=None)
+def ceiling_tail():
+    """what the tail check holds a GPU pose to, as a fraction of picp_budget.tail's bound: 4 times the largest ratio of the
+    float32 restatement of the tail over the whole case matrix and the tail cases -- the margin ceiling() has, here for the
+    ~1 ulp per operation by which the kernel's FMA contraction and Newton reciprocal differ from the restatement -- and never
+    more than the bound itself.  Measured on the reference side only, never on the kernels."""
+    return min(1.0, 4.0 * max(tail_reference(cid)["ratio"] for cid in case_ids() + tail_case_ids()))

@@ -1,10 +1,14 @@
 """Every operator of the path against the oracle at set sizes around the edges the kernels tile on: wave (64), workgroup
 (256), float4 groups (4), LDS tiles (128), compaction blocks, the matcher's mode switch-overs.  Integer outputs, survivor
 order, projection / transform / triangulation (same pose in) and the reference-order solver are compared bit for bit;
-the fast solver within the tolerances of test_gpu_parity.py.  Sizes are small: the whole file runs in seconds."""
+the fast solver within the tolerances of test_gpu_parity.py, and the tail of its last round -- at every size, the near-singular
+problems of a few pairs included -- against the float64 step of the system it read back (picp_budget.check_tail).  Sizes are
+small: the whole file runs in seconds."""
 import numpy as np
 import pytest
 
+import picp_budget as pb
+import picp_cases as pc
 from oracle.oracle import Camera as OCam
 
 pytestmark = pytest.mark.gpu
@@ -68,6 +72,19 @@ def test_operators_at_tile_edges(vo, ctx, o32, n):
             elif len(j) >= 16:      # below that the normal equations are near-singular: rounding is amplified without bound
                 assert np.abs(T - r["T"][-1]).max() < 1e-4 * max(1.0, float(np.abs(r["T"][-1]).max()))
             s.close()
+            if not exact:
+                # ... in the comparison with ANOTHER float32 chain.  The last round alone, from the pose a twin handle's
+                # solve(5) leaves, is a function of the H and b just read: its bound knows cond(H), and holds at every size
+                t = vo.PICPSolver(ctx)
+                t.setKernelThreshold(thr)
+                t.init(vo.Camera(fp["rows"], fp["cols"], fp["z_near"], fp["z_far"], fp["K"], np.eye(4), ctx=ctx), fp["model"], fp["cur_pts"])
+                t.solve(j, keep, 5)
+                T_at = t.camera().worldInCameraPose().copy()
+                t.close()
+                assert np.isfinite(T_at).all() and np.isfinite(T).all() and np.isfinite(H).all() and np.isfinite(b).all()
+                ratio = pb.check_tail(H, b, T_at, T)
+                print(f"{len(j)} pairs thr {thr}: tail of round 6, step / bound {ratio:.4f} (ceiling {pc.ceiling_tail():.4f}), cond(H) {np.linalg.cond(H.astype(np.float64)):.3g}")
+                assert ratio <= pc.ceiling_tail(), (len(j), thr, ratio)
 
 
 @pytest.mark.parametrize("n,F", [(700, 1), (700, 2), (700, 7), (700, 8), (2500, 8), (2500, 15), (2500, 17), (700, 24)])
