@@ -385,6 +385,9 @@ __device__ __forceinline__ void picp_round_body(const PicpParams* __restrict__ P
 #pragma unroll
       for (int j = 0; j < NJ; ++j)
         r[j] = src[(size_t)(b0 + PICP_GROUPS * j) * (PICP_PSTRIDE / 4)];      // (rows >= nb read as zero)
+      // Nothing crosses this line: left alone the scheduler lifts the first add above the third load, the wait in front of
+      // it then holds back loads 3..8 until load 1 is home, and the fetch costs two dependent round trips instead of one.
+      __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
       for (int j = 0; j < NJ; ++j) { psum.x += r[j].x; psum.y += r[j].y; psum.z += r[j].z; psum.w += r[j].w; }
     }
