@@ -1,13 +1,16 @@
 // batch_frames -- BASELINE config 4 from C++: F independent synthetic frame pairs, generated here, resident in
 // HBM, solved by ONE vo_frames_batch_dev call (match -> join -> transform -> n rounds -> triangulate for every
 // frame, the frame as a grid dimension), poses checked against the generator's ground truth.
-//   usage: batch_frames [frames=64] [points=20000] [rounds=50] [repeats=5]
+//   usage: batch_frames [frames=64] [points=20000] [rounds=50] [repeats=5] [--track-ransac[=px[,hyp]]]
+// --track-ransac (last argument; defaults 2 px, 128 hypotheses): the call is vo_frames_batch_track_dev -- the batched P3P
+// RANSAC between the join and the solve -- and a second line reports what it handed on.
 // Plain C++ over the C ABI (include/vo_hip.h): no facade classes, no Python.
 #include <algorithm>
 #include <chrono>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <numeric>
 #include <vector>
 
@@ -77,6 +80,22 @@ T* alloc(vo_ctx* ctx, size_t n) {
 }  // namespace
 
 int main(int argc, char** argv) {
+  bool track = false;
+  vo_frame_track tr{};
+  tr.ransac.n_hypotheses = 128; tr.ransac.threshold_px = 2.f; tr.ransac.seed = 0;
+  if (argc > 1 && std::strncmp(argv[argc - 1], "--track-ransac", 14) == 0) {
+    const char* v = argv[argc - 1] + 14;
+    track = true;
+    if (*v == '=') {
+      char* end = nullptr;
+      tr.ransac.threshold_px = std::strtof(v + 1, &end);
+      if (end && *end == ',') tr.ransac.n_hypotheses = std::atoi(end + 1);
+    } else if (*v) {
+      std::fprintf(stderr, "usage: batch_frames [frames] [points] [rounds] [repeats] [--track-ransac[=px[,hyp]]]\n");
+      return 2;
+    }
+    --argc;
+  }
   const int F = argc > 1 ? std::atoi(argv[1]) : 64, n = argc > 2 ? std::atoi(argv[2]) : 20000;
   const int rounds = argc > 3 ? std::atoi(argv[3]) : 50, repeats = argc > 4 ? std::atoi(argv[4]) : 5;
   const float K[9] = {180, 0, 0, 0, 180, 0, 320, 240, 1};     // column-major [180 0 320; 0 180 240; 0 0 1]
@@ -111,10 +130,18 @@ int main(int argc, char** argv) {
     std::fprintf(stderr, "device allocation failed: %s\n", vo_last_error());
     return 2;
   }
-  CHECK(vo_frames_batch_dev(ctx, &b));                        // sizes every workspace
+  if (track) {
+    tr.status = alloc<int>(ctx, (size_t)F); tr.n_tracked = alloc<int>(ctx, (size_t)F);
+    if (!tr.status || !tr.n_tracked) {
+      std::fprintf(stderr, "device allocation failed: %s\n", vo_last_error());
+      return 2;
+    }
+  }
+  auto call = [&] { return track ? vo_frames_batch_track_dev(ctx, &b, nullptr, &tr) : vo_frames_batch_dev(ctx, &b); };
+  CHECK(call());                                              // sizes every workspace
   CHECK(vo_ctx_synchronize(ctx));
   const auto t0 = std::chrono::steady_clock::now();
-  for (int r = 0; r < repeats; ++r) CHECK(vo_frames_batch_dev(ctx, &b));
+  for (int r = 0; r < repeats; ++r) CHECK(call());
   CHECK(vo_ctx_synchronize(ctx));
   const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count() / repeats;
   std::vector<float> poses(16 * (size_t)F), stats(4 * (size_t)F);
@@ -122,15 +149,30 @@ int main(int argc, char** argv) {
   CHECK(vo_memcpy_d2h(ctx, poses.data(), b.poses, poses.size() * sizeof(float)));
   CHECK(vo_memcpy_d2h(ctx, stats.data(), b.stats, stats.size() * sizeof(float)));
   CHECK(vo_memcpy_d2h(ctx, counts.data(), b.counts, counts.size() * sizeof(int)));
+  std::vector<int> status((size_t)F, 0), tracked((size_t)F, n);
+  if (track) {
+    CHECK(vo_memcpy_d2h(ctx, status.data(), tr.status, status.size() * sizeof(int)));
+    CHECK(vo_memcpy_d2h(ctx, tracked.data(), tr.n_tracked, tracked.size() * sizeof(int)));
+  }
   float worst = 0.f;
-  int bad = 0;
+  int bad = 0, fell_back = 0;
+  long handed_on = 0;
   for (int f = 0; f < F; ++f) {
     for (int k = 0; k < 16; ++k) worst = std::max(worst, std::fabs(poses[16 * (size_t)f + k] - gt[(size_t)f].m[k]));
-    if (counts[(size_t)f] != n || counts[(size_t)F + f] != n || (int)stats[4 * (size_t)f + 2] != n) ++bad;
+    // (tracked: the solve sees the pairs the RANSAC handed on, all of them inliers of the solve too)
+    if (counts[(size_t)f] != n || counts[(size_t)F + f] != n || (int)stats[4 * (size_t)f + 2] != tracked[(size_t)f]) ++bad;
+    fell_back += status[(size_t)f] != VO_POSE_RANSAC_OK;
+    handed_on += tracked[(size_t)f];
   }
   std::printf("batch_frames: %d frames x %d points, %d rounds: %.3f ms per call, %.0f frames/s; worst |T - T_gt| %.2e; "
               "frames with a missing match/join/inlier: %d; triangulated (frame 0): %d\n",
               F, n, rounds, ms, F * 1e3 / ms, worst, bad, counts[2 * (size_t)F]);
+  if (track) {
+    std::printf("track-ransac: %.2f px, %d hypotheses: %d frame(s) fell back, %.1f pairs per frame handed to the solve\n",
+                (double)tr.ransac.threshold_px, tr.ransac.n_hypotheses, fell_back, (double)handed_on / F);
+    vo_dev_free(ctx, tr.status); vo_dev_free(ctx, tr.n_tracked);
+    if (fell_back) bad += fell_back;
+  }
   for (void* d : {(void*)b.ref_app, (void*)b.cur_app, (void*)b.ref_pts, (void*)b.cur_pts, (void*)b.model, (void*)b.model_pairs,
                   (void*)b.matches, (void*)b.joined, (void*)b.model_moved, (void*)b.poses, (void*)b.stats, (void*)b.tri_xyz,
                   (void*)b.tri_pairs, (void*)b.counts})

@@ -3,6 +3,7 @@
 // plain GPU estimate_transform of the best hypothesis's inliers (bit for bit vo_estimate_transform of those pairs).
 // estimate_pose_ransac (vo_estimate_pose_ransac): the tracking counterpart -- minimal P3P fits over 2D-3D pairs scored by
 // reprojection on the GPU; the winner's pose and inliers are the start and the input of the PICP rounds that follow.
+// estimate_pose_ransac_batch (vo_estimate_pose_ransac_batch_dev): the same for many problems in device memory in one call.
 #pragma once
 
 #include <cstdint>
@@ -57,6 +58,29 @@ inline Isometry3f estimate_pose_ransac(const Camera& cam, const Vector3fVector& 
                                 &params, T.data(), inliers && n ? inliers->data() : nullptr, nullptr),
         "estimate_pose_ransac");
   return T;
+}
+
+//! defaults of the batched tracking options (apps/batch_frames --track-ransac): 128 hypotheses, 2 px, seed 0
+inline vo_ransac_params ransac_batch_params(float threshold_px = 2.f, int n_hypotheses = 128, uint64_t seed = 0) {
+  return ransac_params(threshold_px, n_hypotheses, seed);
+}
+
+//! estimate_pose_ransac for n_problems problems in DEVICE memory in one call (vo_estimate_pose_ransac_batch_dev): problem p
+//! reads d_world_xyz + p * world_stride points, d_meas_uv + p * meas_stride pixels and d_n_pairs[p] (or, null, pairs_stride)
+//! of the pairs at d_pairs + p * pairs_stride; its pose, pairs handed on, their count and its status (VO_POSE_RANSAC_*; 1-4:
+//! the identity and every live pair) go to d_T16_out + 16 p, d_inlier_pairs + p * pairs_stride, d_n_inliers[p], d_status[p]
+//! -- bit for bit vo_estimate_pose_ransac_dev on that problem alone, ready for vo_picp_solve_batch_dev.  Enqueues on the
+//! default context's stream and returns; throws vo::Error on the refusals of the C call.
+inline void estimate_pose_ransac_batch(const Camera& cam, int n_problems, const float* d_world_xyz, size_t world_stride, int n_world,
+                                       const float* d_meas_uv, size_t meas_stride, int n_meas, const int32_t* d_pairs,
+                                       size_t pairs_stride, const int* d_n_pairs, const vo_ransac_params& params, float* d_T16_out,
+                                       int32_t* d_inlier_pairs, int* d_n_inliers, int* d_status, uint8_t* d_inlier_mask = nullptr,
+                                       int32_t* d_hypothesis_counts = nullptr) {
+  check(vo_estimate_pose_ransac_batch_dev(default_context().handle(), n_problems, cam.rows(), cam.cols(), cam.zNear(), cam.zFar(),
+                                          cam.cameraMatrix().data(), d_world_xyz, world_stride, n_world, d_meas_uv, meas_stride, n_meas,
+                                          d_pairs, pairs_stride, d_n_pairs, &params, d_T16_out, d_inlier_pairs, d_n_inliers,
+                                          d_inlier_mask, d_hypothesis_counts, d_status),
+        "estimate_pose_ransac_batch");
 }
 
 }  // namespace vo

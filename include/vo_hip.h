@@ -466,6 +466,31 @@ int vo_estimate_pose_ransac_dev(vo_ctx *ctx, int rows, int cols, int z_near, int
                                 const vo_ransac_params *params, float *d_T16_out, int32_t *d_inlier_pairs,
                                 int *d_n_inliers, uint8_t *d_inlier_mask /* or NULL */,
                                 int32_t *d_hypothesis_counts /* or NULL */, int *d_status);
+/* Batched form: n_problems independent problems in one call -- 3 memsets and 7 launches whatever their number, the
+ * problem being a grid dimension -- for callers with many frames per call.  Problem p reads d_world_xyz + p * world_stride
+ * points (n_world of them valid indices), d_meas_uv + p * meas_stride pixels (n_meas valid) and d_pairs + p * pairs_stride
+ * pairs, of which d_n_pairs[p] <= pairs_stride are live (d_n_pairs = NULL: pairs_stride in every problem).  Strides count
+ * ELEMENTS (points, pixels, pairs), the convention of vo_picp_solve_batch_dev.
+ * CONTRACT: problem p's pose d_T16_out[p], status d_status[p], inlier pairs d_inlier_pairs + p * pairs_stride, count
+ * d_n_inliers[p], mask d_inlier_mask + p * pairs_stride and hypothesis counts d_hypothesis_counts + p * n_hypotheses are
+ * BIT FOR BIT what vo_estimate_pose_ransac_dev returns for that problem alone with n_max = pairs_stride and the same
+ * params; every problem uses params->seed unchanged.  The fallbacks 1-4 are per problem and mean what they mean there: a
+ * bad index in one problem leaves every other problem's status alone.
+ * Hence vo_picp_solve_batch_dev(..., d_pairs = d_inlier_pairs, pairs_stride, d_n_pairs = d_n_inliers, d_T0 = d_T16_out,
+ * ...) is robust batched tracking, and a problem that fell back is the plain problem from the identity.
+ * Capturable under the single form's rule: once a call with the same n_problems, pairs_stride and n_hypotheses has sized
+ * the context's workspace; a capture that would need a bigger one is refused (VO_ERR_NOT_READY).
+ * Refused (VO_ERR_INVALID_ARG): the single form's parameter errors, n_problems < 1 or > 65535, a world or measurement
+ * stride smaller than its count, pairs_stride < 1, a NULL required pointer (only d_n_pairs, d_inlier_mask and
+ * d_hypothesis_counts may be NULL). */
+int vo_estimate_pose_ransac_batch_dev(vo_ctx *ctx, int n_problems, int rows, int cols, int z_near, int z_far,
+                                      const float K[9], const float *d_world_xyz, size_t world_stride, int n_world,
+                                      const float *d_meas_uv, size_t meas_stride, int n_meas,
+                                      const int32_t *d_pairs, size_t pairs_stride, const int *d_n_pairs /* or NULL */,
+                                      const vo_ransac_params *params, float *d_T16_out /* [P][16] */,
+                                      int32_t *d_inlier_pairs /* stride pairs_stride */, int *d_n_inliers /* [P] */,
+                                      uint8_t *d_inlier_mask /* [P][pairs_stride] or NULL */,
+                                      int32_t *d_hypothesis_counts /* [P][n_hypotheses] or NULL */, int *d_status /* [P] */);
 
 /* ---- many independent frame pairs at once (throughput form of vo_complete.cpp:156-173) ---- */
 /* For each of n_frames independent frame pairs: match -> join -> X_prev * model -> n_iters rounds
@@ -512,6 +537,23 @@ typedef struct vo_frame_sizes {
   const int *n_ref, *n_cur, *n_model_pairs;
 } vo_frame_sizes;
 int vo_frames_batch_ragged_dev(vo_ctx *ctx, const vo_frame_batch *batch, const vo_frame_sizes *sizes);
+/* The many-frames call with robust tracking (batched form), composed of the stages above:
+ * match -> join -> X_prev * model -> vo_estimate_pose_ransac_batch_dev on (moved cloud, cur_pts, joined, counts[1]) ->
+ * the solve of vo_picp_solve_batch_dev from the winners on the pairs handed on -> triangulate with the final pose.
+ * `batch` and `sizes` (or NULL: uniform sizes) are those of the two calls above and every output of `batch` keeps its
+ * meaning: joined / counts[1] hold EVERY joined pair, the filtered ones go to `track`.  The moved cloud is always written
+ * (the RANSAC gather reads it): into batch->model_moved when given, else into the context's workspace.  Per frame,
+ * status / n_tracked / tracked_pairs / T_winner are d_status / d_n_inliers / d_inlier_pairs / d_T16_out of the batched
+ * RANSAC, bit for bit; a frame that fell back (status 1-4) is solved as the plain call solves it. */
+typedef struct vo_frame_track {
+  vo_ransac_params ransac;
+  int     *status;         /* [n_frames] VO_POSE_RANSAC_* */
+  int     *n_tracked;      /* [n_frames] pairs handed to the solve */
+  int32_t *tracked_pairs;  /* [n_frames][q][2] or NULL */
+  float   *T_winner;       /* [n_frames][16] or NULL */
+} vo_frame_track;
+int vo_frames_batch_track_dev(vo_ctx *ctx, const vo_frame_batch *batch, const vo_frame_sizes *sizes /* or NULL */,
+                              const vo_frame_track *track);
 /* The matcher alone for n_frames pairs of appearance sets: frame f = d_a1 + f*cap1*10 (d_n1[f] <= cap1 rows) against
  * d_a2 + f*cap2*10 (d_n2[f] <= cap2 rows); d_n1 = d_n2 = NULL: every frame holds cap1 / cap2 rows.  d_out_pairs: [n_frames][min(cap1, cap2)][2] (ref index, cur index), d_n_out[f] = pairs found.  Replaces
  * n_frames calls of compute_correspondences_images (vo_complete.cpp:12-49): the up-front matching of a whole sequence. */

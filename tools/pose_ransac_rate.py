@@ -5,6 +5,10 @@
   python tools/pose_ransac_rate.py [--hyp 512,2048,8192] [--reps 30]       -> one JSON line per hypothesis count
   rocprofv3 --kernel-trace --stats --output-format csv -d DIR -- python tools/pose_ransac_rate.py --hyp 2048
   python tools/pose_ransac_rate.py --split DIR/*/*kernel_stats.csv        -> the traced run's kernels folded into stages
+  python tools/pose_ransac_rate.py --batch 200 [--sizes 127,2000,50000] [--hyp 128,512] [--frames 200x50000]
+      vo_estimate_pose_ransac_batch_dev on P problems against a loop of P single calls on the same data (five alternating
+      runs per shape, the median run each), then the tracked many-frames call against the plain one (--frames FxN, 50 rounds,
+      128 hypotheses; --frames 0 leaves it out): one JSON line per measurement, each stamped (tools/stamp.py)
 
 Stages: gather (the packed records), hypotheses (sample + P3P), scoring, select (selection, mask, scan, compaction) and, for
 the solve that follows, picp (its kernels).  The call itself never waits: its wall time is taken to a stream
@@ -20,9 +24,12 @@ import time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
-STAGES = [("gather", ("pose_gather_kernel",)), ("hypotheses", ("pose_hyp_kernel",)), ("scoring", ("pose_score_kernel",)),
-          ("select", ("pose_select_kernel", "pose_mask_kernel", "scan_counts_kernel", "pose_scatter_kernel")),
-          ("picp", ("picp",))]
+STAGES = [("gather", ("pose_gather_kernel", "pose_gather_batch_kernel")), ("hypotheses", ("pose_hyp_kernel", "pose_hyp_batch_kernel")),
+          ("scoring", ("pose_score_kernel", "pose_score_batch_kernel")),
+          ("select", ("pose_select_kernel", "pose_mask_kernel", "pose_scatter_kernel", "pose_select_batch_kernel",
+                      "pose_mask_batch_kernel", "pose_scatter_batch_kernel")),
+          ("picp", ("picp",)), ("match", ("match", "hash", "cell")), ("join", ("join",)), ("triangulate", ("triang",)),
+          ("transform", ("transform",)), ("scan", ("scan_counts_kernel",))]
 
 
 def split(path):
@@ -42,8 +49,106 @@ def split(path):
     print(json.dumps({"kernel_stats": os.path.basename(path), "stages": out}, indent=1))
 
 
+def batch_mode(a):
+    import ctypes as C
+
+    import numpy as np
+
+    import __graft_entry__ as g
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    sys.path.insert(0, os.path.join(ROOT, "tools"))
+    import pose_ransac_restatement as P
+    import stamp
+    vo = g.load_package()
+    ctx = vo.Context(0)
+    lib, V, I, S = ctx.lib, C.c_void_p, C.c_int, C.c_size_t
+    st = stamp.current()
+    cam = (480, 640, 0, 10)
+    NP = a.batch
+
+    def sync():
+        assert lib.vo_ctx_synchronize(ctx.h) == 0
+
+    def timed(f, reps):
+        sync()
+        t = time.perf_counter()
+        for _ in range(reps):
+            f()
+        sync()
+        return (time.perf_counter() - t) / reps * 1e3
+
+    def alternate(fa, fb, reps):
+        """five alternating runs of each: (median ms of a, median ms of b)"""
+        fa(); fb()
+        ta, tb = [], []
+        for _ in range(5):
+            ta.append(timed(fa, reps)); tb.append(timed(fb, reps))
+        return statistics.median(ta), statistics.median(tb), ta, tb
+
+    for n in [int(x) for x in a.sizes.split(",") if x.strip() and int(x) > 0]:      # (--sizes 0: the frames measurement alone)
+        # P problems of n pairs: the same generator, another seed per problem up to 8, then repeated (the timing does not see it)
+        base = [P.tracking_problem(vo, n, seed=2001 + i, noise_px=0.5, frac=a.frac, max_angle=0.3, max_t=0.5) for i in range(min(NP, 8))]
+        K = np.ascontiguousarray(np.asarray(base[0][0]["K"], np.float32).T).ravel()
+        pick = [base[i % len(base)] for i in range(NP)]
+        world = np.ascontiguousarray(np.stack([np.asarray(b[1], np.float32) for b in pick]))
+        meas = np.ascontiguousarray(np.stack([np.asarray(b[2], np.float32) for b in pick]))
+        pairs = np.ascontiguousarray(np.stack([np.asarray(b[3], np.int32) for b in pick]))
+        d_w, d_m, d_p = ctx.to_device(world), ctx.to_device(meas), ctx.to_device(pairs)
+        d_T, d_inl, d_nin, d_st = ctx.alloc(NP * 64), ctx.alloc(NP * n * 8), ctx.alloc(NP * 4 + 8), ctx.alloc(NP * 4 + 8)
+        d_T1, d_inl1, d_nin1, d_st1 = ctx.alloc(NP * 64), ctx.alloc(NP * n * 8), ctx.alloc(NP * 4 + 8), ctx.alloc(NP * 4 + 8)
+        for H in [int(x) for x in a.hyp.split(",")]:
+            prm = vo.RansacParams(H, 2.0, 0)
+
+            def batched():
+                rc = lib.vo_estimate_pose_ransac_batch_dev(ctx.h, I(NP), *map(I, cam), K.ctypes.data_as(V), V(d_w), S(n), I(n), V(d_m), S(n),
+                                                           I(n), V(d_p), S(n), None, C.byref(prm), V(d_T), V(d_inl), V(d_nin), None, None,
+                                                           V(d_st))
+                assert rc == 0, lib.vo_last_error()
+
+            def loop():
+                for q in range(NP):
+                    rc = lib.vo_estimate_pose_ransac_dev(ctx.h, *map(I, cam), K.ctypes.data_as(V), V(d_w + 12 * n * q), I(n),
+                                                         V(d_m + 8 * n * q), I(n), V(d_p + 8 * n * q), I(n), None, C.byref(prm),
+                                                         V(d_T1 + 64 * q), V(d_inl1 + 8 * n * q), V(d_nin1 + 4 * q), None, None,
+                                                         V(d_st1 + 4 * q))
+                    assert rc == 0, lib.vo_last_error()
+
+            reps = max(1, min(a.reps, int(2e8 / (NP * n * H)) + 1))
+            tb, tl, rb, rl = alternate(batched, loop, reps)
+            get = lambda d, k, dt: (lambda x: (ctx.d2h(x, d), x)[1])(np.zeros(k, dt))
+            same = get(d_T, NP * 16, np.float32).tobytes() == get(d_T1, NP * 16, np.float32).tobytes() and \
+                np.array_equal(get(d_nin, NP, np.int32), get(d_nin1, NP, np.int32)) and \
+                np.array_equal(get(d_st, NP, np.int32), get(d_st1, NP, np.int32))
+            print(json.dumps({"measurement": "batched call vs loop of single calls", "problems": NP, "pairs": n, "mismatched": a.frac,
+                              "hypotheses": H, "reps_per_run": reps, "batched_ms": round(tb, 4), "loop_ms": round(tl, 4),
+                              "loop_over_batched": round(tl / tb, 2), "batched_runs_ms": [round(x, 4) for x in rb],
+                              "loop_runs_ms": [round(x, 4) for x in rl], "same_poses_counts_status": bool(same),
+                              "fell_back": int((get(d_st, NP, np.int32) != 0).sum()), "device": ctx.device_info()[0], "stamp": st}),
+                  flush=True)
+        for d in (d_w, d_m, d_p, d_T, d_inl, d_nin, d_st, d_T1, d_inl1, d_nin1, d_st1):
+            ctx.free(d)
+    if a.frames and a.frames != "0":
+        F, n = (int(x) for x in a.frames.lower().split("x"))
+        fps = [vo.synth.frame_pair(n, seed=2001 + i, noise_px=0.5) for i in range(min(F, 4))]
+        gen = lambda lo, hi: [fps[i % len(fps)] for i in range(lo, hi)]
+        plain = vo.BatchPipeline(ctx, gen, n_iters=50, with_appearance=False, n_frames=F, upload_block=50)
+        tracked = vo.BatchPipeline(ctx, gen, n_iters=50, with_appearance=False, n_frames=F, upload_block=50,
+                                   track_ransac=dict(threshold_px=2.0, n_hypotheses=128, seed=0))
+        tt, tp, rt, rp = alternate(tracked.run, plain.run, max(1, a.reps // 6))
+        stt, ntr = tracked.track_stats()
+        print(json.dumps({"measurement": "tracked many-frames call vs plain", "frames": F, "points": n, "rounds": 50, "hypotheses": 128,
+                          "tracked_ms": round(tt, 4), "plain_ms": round(tp, 4), "tracked_frames_per_s": round(F * 1e3 / tt),
+                          "plain_frames_per_s": round(F * 1e3 / tp), "tracked_runs_ms": [round(x, 4) for x in rt],
+                          "plain_runs_ms": [round(x, 4) for x in rp], "fell_back": int((stt != 0).sum()),
+                          "pairs_handed_on_mean": float(ntr.mean()), "device": ctx.device_info()[0], "stamp": st}), flush=True)
+        plain.close(); tracked.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--batch", type=int, default=0)
+    ap.add_argument("--sizes", default="127,2000,50000")
+    ap.add_argument("--frames", default="200x50000")
     ap.add_argument("--hyp", default="512,2048,8192")
     ap.add_argument("--n", type=int, default=50000)
     ap.add_argument("--frac", type=float, default=0.3)
@@ -52,6 +157,10 @@ def main():
     a = ap.parse_args()
     if a.split:
         return split(a.split)
+    if a.batch:
+        if a.hyp == "512,2048,8192":
+            a.hyp = "128,512"
+        return batch_mode(a)
     import ctypes as C
 
     import numpy as np

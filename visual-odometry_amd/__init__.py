@@ -21,6 +21,8 @@ from .api import (  # noqa: F401
     estimate_transform,
     estimate_transform_ransac,
     estimate_pose_ransac,
+    estimate_pose_ransac_batch,
+    estimate_pose_ransac_batch_dev,
     extract_correspondences_world,
     load_library,
     radius_search,

@@ -499,6 +499,59 @@ def estimate_pose_ransac(k, rows, cols, z_near, z_far, world, meas, corresponden
     return T.reshape(4, 4).T.copy(), mask[: len(pairs)].astype(bool), n_in.value
 
 
+def estimate_pose_ransac_batch_dev(ctx: Context, n_problems, rows, cols, z_near, z_far, k, d_world, world_stride, n_world, d_meas,
+                                   meas_stride, n_meas, d_pairs, pairs_stride, d_n_pairs, params: RansacParams, d_T16, d_inlier_pairs,
+                                   d_n_inliers, d_mask, d_counts, d_status):
+    """vo_estimate_pose_ransac_batch_dev on device pointers (ints; d_n_pairs, d_mask, d_counts may be None): enqueues and
+    returns.  Strides in elements (points, pixels, pairs)."""
+    v = lambda d: C.c_void_p(d) if d else None
+    _chk(ctx.lib.vo_estimate_pose_ransac_batch_dev(
+        ctx.h, C.c_int(n_problems), C.c_int(rows), C.c_int(cols), C.c_int(z_near), C.c_int(z_far), _ptr(_colmajor(k, 3)),
+        v(d_world), C.c_size_t(world_stride), C.c_int(n_world), v(d_meas), C.c_size_t(meas_stride), C.c_int(n_meas), v(d_pairs),
+        C.c_size_t(pairs_stride), v(d_n_pairs), C.byref(params), v(d_T16), v(d_inlier_pairs), v(d_n_inliers), v(d_mask), v(d_counts),
+        v(d_status)))
+
+
+def estimate_pose_ransac_batch(ctx: Context, problems, k, rows, cols, z_near, z_far, threshold_px=2.0, n_hypotheses=128, seed=0):
+    """P3P RANSAC over many 2D-3D problems in ONE call (vo_estimate_pose_ransac_batch_dev).  problems: a list of host problems
+    (world (n, 3), meas (m, 2), correspondences (p, 2) = (meas_idx, world_idx)) of any sizes -- padded to common strides and
+    uploaded.  Every problem's result is bit for bit that of the single device call on it alone.  Returns, per problem,
+    (T (4x4), status (VO_POSE_RANSAC_*: 0 tracked, 1-4 fell back to the identity and every pair), inlier pairs (n, 2) in
+    their original order, mask (bool, one per pair)).  The batched default is 128 hypotheses."""
+    P = len(problems)
+    if P == 0:
+        return []
+    W = [_f32(w, (-1, 3)) for w, _, _ in problems]
+    M = [_f32(m, (-1, 2)) for _, m, _ in problems]
+    Q = [_i32pairs(c) for _, _, c in problems]
+    nw, nm, npr = max(max(map(len, W)), 1), max(max(map(len, M)), 1), max(max(map(len, Q)), 1)
+
+    def stack(arrs, cap, width, dt):
+        out = np.zeros((P, cap, width), dt)
+        for i, a in enumerate(arrs):
+            out[i, : len(a)] = a
+        return out
+
+    n = np.array([len(q) for q in Q], np.int32)
+    ins = [ctx.to_device(stack(W, nw, 3, np.float32)), ctx.to_device(stack(M, nm, 2, np.float32)),
+           ctx.to_device(stack(Q, npr, 2, np.int32)), ctx.to_device(n)]
+    outs = [ctx.alloc(P * 64), ctx.alloc(P * npr * 8), ctx.alloc(max(P * 4, 8)), ctx.alloc(max(P * npr, 8)), ctx.alloc(max(P * 4, 8))]
+    try:
+        prm = RansacParams(int(n_hypotheses), float(threshold_px), int(seed) & 0xFFFFFFFFFFFFFFFF)
+        # the points every problem may index are its own: a stride's padding is never a valid index
+        estimate_pose_ransac_batch_dev(ctx, P, rows, cols, z_near, z_far, k, ins[0], nw, nw, ins[1], nm, nm, ins[2], npr, ins[3], prm,
+                                       outs[0], outs[1], outs[2], outs[3], None, outs[4])
+        T = np.zeros((P, 16), np.float32); ctx.d2h(T, outs[0])
+        inl = np.zeros((P, npr, 2), np.int32); ctx.d2h(inl, outs[1])
+        nin = np.zeros(P, np.int32); ctx.d2h(nin, outs[2])
+        mask = np.zeros((P, npr), np.uint8); ctx.d2h(mask, outs[3])
+        st = np.zeros(P, np.int32); ctx.d2h(st, outs[4])
+    finally:
+        for d in ins + outs:
+            ctx.free(d)
+    return [(T[p].reshape(4, 4).T.copy(), int(st[p]), inl[p, : nin[p]].copy(), mask[p, : n[p]].astype(bool)) for p in range(P)]
+
+
 def radius_search(tree_appearances, query_appearances, radius=0.1, ctx: Context | None = None):
     """TreeNode_::fullSearch (eigen_kdtree.h:56-71) for every query: list of int32 arrays, one per query,
     with the indices of ALL tree points closer than `radius` (ascending; the library's order is unspecified)."""

@@ -111,6 +111,8 @@ struct vo_ctx {
   DevBuf epi_ws;      // maxima, A^T A and vote counts of vo_estimate_transform
   DevBuf ransac_ws;   // points, hypotheses, counts, mask and inlier pairs of vo_estimate_transform_ransac
   DevBuf pose_ws;     // the same for vo_estimate_pose_ransac
+  DevBuf pose_batch_ws;   // ... and for vo_estimate_pose_ransac_batch_dev (all problems' blocks)
+  DevBuf track_ws;    // vo_frames_batch_track_dev: the moved cloud, the tracked pairs and the winners the caller did not ask for
   // Steering of the automatic matcher by what the previous batched call found: after a call that ran the
   // exact-duplicate pass, "did any frame take it?" travels to pinned host memory behind the call (no wait); a later call
   // that finds the answer "none" there leaves the pass out for the next HINT_SKIP calls, then probes again.  Data whose
@@ -288,6 +290,7 @@ int vo_ctx_destroy(vo_ctx* c) {
   (void)hipStreamSynchronize(c->stream);
   c->scratch.release(); c->best.release(); c->table.release(); c->counts.release();
   c->batch_pack.release(); c->batch_bad.release(); c->prune_ws.release(); c->epi_ws.release(); c->ransac_ws.release(); c->pose_ws.release();
+  c->pose_batch_ws.release(); c->track_ws.release();
   if (c->hint_ev) (void)hipEventDestroy(c->hint_ev);
   if (c->hint_host) (void)hipHostFree(c->hint_host);
   if (c->hint_dev) (void)hipFree(c->hint_dev); c->batch_states.release(); c->batch_partials.release(); c->batch_help.release();
@@ -1892,6 +1895,143 @@ int vo_estimate_pose_ransac(vo_ctx* c, int rows, int cols, int z_near, int z_far
     VO_HIP_CHECK(hipStreamSynchronize(c->stream));
   }
   if (n_inliers) *n_inliers = cnt;
+  return VO_OK;
+}
+
+// The batched form: P problems in one fixed set of launches (pose_ransac.hip), every problem held to the single call above
+// bit for bit.  The argument checks come first and touch neither the context nor the device.
+static int pose_ransac_batch_check(const void* c, int n_problems, const float* K, const float* d_world, size_t world_stride, int n_world,
+                                   const float* d_meas, size_t meas_stride, int n_meas, const int32_t* d_pairs, size_t pairs_stride,
+                                   const vo_ransac_params* params, const float* d_T16, const int32_t* d_inl, const int* d_n_inl,
+                                   const int* d_status) {
+  const char* fn = "vo_estimate_pose_ransac_batch_dev";
+  if (!(c && K && d_world && d_meas && d_pairs && params && d_T16 && d_inl && d_n_inl && d_status))
+    return fail(VO_ERR_INVALID_ARG, "%s: null argument", fn);
+  if (n_problems < 1) return fail(VO_ERR_INVALID_ARG, "%s: n_problems must be positive (%d)", fn, n_problems);
+  if (n_problems > 65535) return fail(VO_ERR_INVALID_ARG, "%s: more than 65535 problems per call (the problem is a grid dimension)", fn);
+  if (n_world < 0 || n_meas < 0) return fail(VO_ERR_INVALID_ARG, "%s: negative point count", fn);
+  if (pairs_stride < 1) return fail(VO_ERR_INVALID_ARG, "%s: pairs_stride must be positive", fn);
+  if (world_stride >= 0x7fffffff || meas_stride >= 0x7fffffff || pairs_stride >= 0x7fffffff)
+    return fail(VO_ERR_INVALID_ARG, "%s: stride too large", fn);
+  if (world_stride < (size_t)n_world || meas_stride < (size_t)n_meas)
+    return fail(VO_ERR_INVALID_ARG, "%s: a stride is smaller than its point count (world %zu < %d or meas %zu < %d)", fn, world_stride,
+                n_world, meas_stride, n_meas);
+  if (!aligned8(d_pairs, d_meas, d_inl)) return fail(VO_ERR_INVALID_ARG, "%s: device arrays must be 8-byte aligned", fn);
+  return ransac_check_params(params);
+}
+
+static int pose_ransac_batch(vo_ctx* c, int n_problems, int rows, int cols, int z_near, int z_far, const float K[9], const float* d_world,
+                             size_t world_stride, int n_world, const float* d_meas, size_t meas_stride, int n_meas,
+                             const int32_t* d_pairs, size_t pairs_stride, const int* d_n, const vo_ransac_params* params, float* d_T16,
+                             int32_t* d_inl, int* d_n_inl, uint8_t* d_mask, int32_t* d_counts, int* d_status) {
+  if (int r = pose_ransac_batch_check(c, n_problems, K, d_world, world_stride, n_world, d_meas, meas_stride, n_meas, d_pairs, pairs_stride,
+                                      params, d_T16, d_inl, d_n_inl, d_status))
+    return r;
+  const int H = params->n_hypotheses, n_max = (int)pairs_stride;
+  CamK cam;
+  double Kinv[9];
+  if (int r = pose_ransac_camera(rows, cols, z_near, z_far, K, cam, Kinv)) return r;
+  const size_t need = pose_ransac_batch_workspace_bytes(n_problems, n_max, H);
+  if (c->capturing && c->pose_batch_ws.cap < need)
+    return fail(VO_ERR_NOT_READY, "vo_estimate_pose_ransac_batch_dev: the workspace would have to grow inside a graph capture (make "
+                                  "one call with %d problems of stride %d and %d hypotheses before capturing)", n_problems, n_max, H);
+  if (int r = set_device(c)) return r;
+  VO_HIP_CHECK(c->pose_batch_ws.ensure(need, c->stream));
+  PoseRansacBatchArgs b = pose_ransac_batch_layout(c->pose_batch_ws.p, n_problems, n_max, H);
+  PoseRansacArgs& a = b.a;
+  a.cam = cam;
+  for (int i = 0; i < 9; ++i) a.Kinv[i] = Kinv[i];
+  a.pairs = d_pairs; a.d_n = d_n; a.world = d_world; a.n_world = n_world; a.meas = d_meas; a.n_meas = n_meas;
+  a.seed = params->seed; a.thr2 = params->threshold_px * params->threshold_px;
+  a.out_pairs = d_inl; a.n_out = d_n_inl; a.T_out = d_T16; a.status = d_status;
+  if (d_mask) a.mask = d_mask;
+  if (d_counts) a.counts = d_counts;
+  b.world_stride = world_stride; b.meas_stride = meas_stride; b.pairs_stride = pairs_stride;
+  VO_HIP_CHECK(launch_pose_ransac_batch(c->stream, b));
+  return VO_OK;
+}
+
+int vo_estimate_pose_ransac_batch_dev(vo_ctx* c, int n_problems, int rows, int cols, int z_near, int z_far, const float K[9],
+                                      const float* d_world, size_t world_stride, int n_world, const float* d_meas, size_t meas_stride,
+                                      int n_meas, const int32_t* d_pairs, size_t pairs_stride, const int* d_n,
+                                      const vo_ransac_params* params, float* d_T16, int32_t* d_inl, int* d_n_inl, uint8_t* d_mask,
+                                      int32_t* d_counts, int* d_status) {
+  return pose_ransac_batch(c, n_problems, rows, cols, z_near, z_far, K, d_world, world_stride, n_world, d_meas, meas_stride, n_meas,
+                           d_pairs, pairs_stride, d_n, params, d_T16, d_inl, d_n_inl, d_mask, d_counts, d_status);
+}
+
+// ---- the many-frames call with robust tracking: the stages of frames_batch with the batched RANSAC between the join and the
+// solve.  The join is the plain one (the pairs are filtered before the solver packs them) and the moved cloud is always
+// written, because the RANSAC gather reads it.
+int vo_frames_batch_track_dev(vo_ctx* c, const vo_frame_batch* b, const vo_frame_sizes* sz, const vo_frame_track* t) {
+  VO_REQUIRE(c && b && t, "null argument");
+  VO_REQUIRE(t->status && t->n_tracked, "null tracking output array");
+  VO_REQUIRE(!sz || (sz->n_ref && sz->n_cur && sz->n_model_pairs), "null per-frame size array");
+  const int F = b->n_frames;
+  VO_REQUIRE(F >= 0 && b->n_ref >= 0 && b->n_cur >= 0 && b->n_model >= 0 && b->n_model_pairs >= 0 && b->n_iters >= 0,
+             "negative count");
+  if (int r = ransac_check_params(&t->ransac)) return r;
+  if (F == 0) return VO_OK;
+  VO_REQUIRE(F <= 65535, "more than 65535 frames per call (the frame is a grid dimension)");
+  const int q = b->n_ref < b->n_cur ? b->n_ref : b->n_cur;
+  VO_REQUIRE(q > 0 && b->n_model > 0, "empty frames");
+  VO_REQUIRE(b->ref_app && b->cur_app && b->ref_pts && b->cur_pts && b->model && b->model_pairs, "null input array");
+  VO_REQUIRE(b->matches && b->joined && b->poses && b->tri_xyz && b->tri_pairs && b->counts, "null output array");
+  VO_REQUIRE(aligned8(b->ref_app, b->cur_app, b->ref_pts, b->cur_pts, b->model_pairs, b->matches, b->joined, b->tri_pairs, b->tri_app,
+                      t->tracked_pairs),
+             "device array not on an 8-byte boundary");
+  if (int r = set_device(c)) return r;
+  const int nt = b->n_ref > b->n_cur ? b->n_ref : b->n_cur;
+  // what the caller did not ask for lives in the context: moved cloud | tracked pairs | winners (256-aligned blocks)
+  const size_t moved_bytes = b->model_moved ? 0 : (sizeof(float) * 3 * (size_t)b->n_model * (size_t)F + 255) & ~(size_t)255;
+  const size_t pairs_bytes = t->tracked_pairs ? 0 : (sizeof(int32_t) * 2 * (size_t)q * (size_t)F + 255) & ~(size_t)255;
+  const size_t win_bytes = t->T_winner ? 0 : sizeof(float) * 16 * (size_t)F;
+  const size_t track_need = moved_bytes + pairs_bytes + win_bytes;
+  if (c->capturing && c->track_ws.cap < track_need)
+    return fail(VO_ERR_NOT_READY, "vo_frames_batch_track_dev: the workspace would have to grow inside a graph capture (make one call "
+                                  "with the same sizes before capturing)");
+  VO_HIP_CHECK(c->track_ws.ensure(track_need, c->stream));
+  float* moved = b->model_moved ? b->model_moved : c->track_ws.as<float>();
+  int32_t* tracked = t->tracked_pairs ? t->tracked_pairs : reinterpret_cast<int32_t*>(c->track_ws.as<char>() + moved_bytes);
+  float* winners = t->T_winner ? t->T_winner : reinterpret_cast<float*>(c->track_ws.as<char>() + moved_bytes + pairs_bytes);
+  VO_HIP_CHECK(c->scratch.ensure(triangulate_scratch_bytes(q, F), c->stream));
+  VO_HIP_CHECK(c->best.ensure(sizeof(unsigned long long) * (size_t)q * (size_t)F, c->stream));
+  VO_HIP_CHECK(c->table.ensure(sizeof(unsigned long long) * (size_t)(b->n_ref ? b->n_ref : 1) * (size_t)F, c->stream));
+  bool skipped = false;
+  const int variant_rule = sz ? ragged_variant(c, nt, q, F) : match_variant(c, nt, q, F);
+  const int variant = match_hint_before(c, variant_rule, &skipped);
+  void* ws = nullptr;
+  if (int r = match_workspace(c, variant_rule, nt, sz ? nt : q, F, &ws)) return r;
+  int* n_match = b->counts;
+  int* n_join = b->counts + F;
+  int* n_tri = b->counts + 2 * (size_t)F;
+  // 1. match and join, as frames_batch
+  VO_HIP_CHECK(launch_match_batch(c->stream, b->ref_app, b->n_ref, 10 * (size_t)b->n_ref, b->cur_app, b->n_cur,
+                                  10 * (size_t)b->n_cur, b->radius, b->matches, (size_t)q, n_match,
+                                  c->best.as<unsigned long long>(), c->scratch.as<int>(), c->n_cu, ws, F, variant,
+                                  sz ? sz->n_ref : nullptr, sz ? sz->n_cur : nullptr));
+  match_hint_after(c, variant, skipped, ws, F, c->best.as<unsigned long long>(), (size_t)q, q, sz ? sz->n_ref : nullptr, sz ? sz->n_cur : nullptr);
+  VO_HIP_CHECK(launch_join_batch(c->stream, b->matches, q, n_match, b->model_pairs, b->n_model_pairs,
+                                 sz ? sz->n_model_pairs : nullptr, b->n_ref,
+                                 b->joined, n_join, c->table.as<unsigned long long>(), c->scratch.as<int>(), F, (size_t)q,
+                                 (size_t)b->n_model_pairs, (size_t)q, nullptr));
+  // 2. X_prev * model, always materialised
+  VO_HIP_CHECK(launch_transform_batch(c->stream, b->X_prev, b->model, b->n_model, (size_t)b->n_model, moved, F));
+  // 3. the batched RANSAC on (moved cloud, cur_pts, joined, counts[1])
+  if (int r = pose_ransac_batch(c, F, b->rows, b->cols, b->z_near, b->z_far, b->K, moved, (size_t)b->n_model, b->n_model, b->cur_pts,
+                                (size_t)b->n_cur, b->n_cur, b->joined, (size_t)q, n_join, &t->ransac, winners, tracked, t->n_tracked,
+                                nullptr, nullptr, t->status))
+    return r;
+  // 4. the batched solve from the winners on the pairs handed on
+  if (int r = picp_solve_batch(c, F, b->rows, b->cols, b->z_near, b->z_far, b->K, b->kernel_threshold, b->keep_outliers, moved,
+                               (size_t)b->n_model, b->cur_pts, (size_t)b->n_cur, tracked, (size_t)q, t->n_tracked, winners, b->n_iters,
+                               b->poses, b->stats, nullptr))
+    return r;
+  // 5. triangulation with the final pose
+  VO_HIP_CHECK(launch_triangulate_batch(c->stream, b->K, nullptr, b->poses, b->matches, q, n_match, b->ref_pts, b->n_ref,
+                                        b->cur_pts, b->n_cur, b->tri_app ? b->cur_app : nullptr, b->tri_xyz, b->tri_pairs,
+                                        b->tri_app, n_tri, c->scratch.as<int>(), F, (size_t)q, (size_t)b->n_ref,
+                                        (size_t)b->n_cur, (size_t)q));
   return VO_OK;
 }
 

@@ -14,6 +14,8 @@
 //   pose_mask_kernel / pose_scatter_kernel
 //                         the pairs handed on (the winner's inliers, or every live pair on a fallback) as a mask and
 //                         compacted in their original order: count / scan (geom.hip's launch_scan) / scatter.
+// The batched form (vo_estimate_pose_ransac_batch_dev) runs the same bodies with the problem as a grid dimension, every
+// problem on its own info words, hypotheses, counts and per-workgroup counts: its results are the single form's bit for bit.
 // No host synchronisation anywhere: the call can be captured into a graph, and the solve that follows reads the pose and
 // the pair count where these kernels leave them.  Counts are integers: nothing here depends on scheduling.
 #include "vo_internal.h"
@@ -133,13 +135,13 @@ __device__ __forceinline__ Pose load_pose(const float* g) {
   return T;
 }
 
-}  // namespace
-
-__global__ __launch_bounds__(PB) void pose_gather_kernel(PoseRansacArgs a) {
+// ---- the per-problem bodies: one problem's arrays in `a`, the workgroup's place in that problem's grid in bx / by.  The
+// single form calls them with its own block indices, the batched form (below) with the problem taken off the grid first.
+__device__ __forceinline__ void pose_gather_body(const PoseRansacArgs& a, unsigned bx, unsigned gx) {
   const int n = ransac_rows(a.d_n, a.n_max);
   const float qnan = __int_as_float(0x7fc00000);
   int bad = 0;
-  for (int i = blockIdx.x * PB + threadIdx.x; i < n; i += gridDim.x * PB) {
+  for (int i = bx * PB + threadIdx.x; i < n; i += gx * PB) {
     const int2 pr = reinterpret_cast<const int2*>(a.pairs)[i];
     float4 o = make_float4(qnan, qnan, qnan, qnan);            // a bad pair is never an inlier
     float ov = qnan;
@@ -154,11 +156,10 @@ __global__ __launch_bounds__(PB) void pose_gather_kernel(PoseRansacArgs a) {
     a.pv[i] = ov;
   }
   if (bad) atomicAdd(&a.info[1], bad);
-  if (blockIdx.x == 0 && threadIdx.x == 0) a.info[0] = n;
+  if (bx == 0 && threadIdx.x == 0) a.info[0] = n;
 }
 
-__global__ __launch_bounds__(64) void pose_hyp_kernel(PoseRansacArgs a) {
-  const int h = blockIdx.x * 64 + threadIdx.x;
+__device__ __forceinline__ void pose_hyp_body(const PoseRansacArgs a, const int h) {
   if (h >= a.n_hyp) return;
   const int n = ransac_rows(a.d_n, a.n_max);
   // the first 4 distinct draws, held in four registers (no array: the selects below replace the indexed stores)
@@ -254,7 +255,7 @@ __global__ __launch_bounds__(64) void pose_hyp_kernel(PoseRansacArgs a) {
   dst[3] = make_float4(out[12], out[13], out[14], out[15]);
 }
 
-__global__ __launch_bounds__(PB) void pose_score_kernel(PoseRansacArgs a) {
+__device__ __forceinline__ void pose_score_body(const PoseRansacArgs a, unsigned bx, unsigned by) {
   __shared__ int s_cnt[PB / 64][POSE_HB];
   const int n = ransac_rows(a.d_n, a.n_max);
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -263,12 +264,12 @@ __global__ __launch_bounds__(PB) void pose_score_kernel(PoseRansacArgs a) {
   bool live[POSE_PTS];
 #pragma unroll
   for (int q = 0; q < POSE_PTS; ++q) {
-    const int i = (blockIdx.x * POSE_PTS + q) * PB + threadIdx.x;
+    const int i = (bx * POSE_PTS + q) * PB + threadIdx.x;
     live[q] = i < n;
     p[q] = live[q] ? a.pts[i] : make_float4(0.f, 0.f, 0.f, 0.f);
     pv[q] = live[q] ? a.pv[i] : 0.f;
   }
-  const int h0 = blockIdx.y * POSE_HB;
+  const int h0 = by * POSE_HB;
   const int hn = a.n_hyp - h0 < POSE_HB ? a.n_hyp - h0 : POSE_HB;
   int mine = 0;                                  // the count of hypothesis h0 + lane over this wave's pairs
   for (int k = 0; k < hn; ++k) {
@@ -290,7 +291,7 @@ __global__ __launch_bounds__(PB) void pose_score_kernel(PoseRansacArgs a) {
   }
 }
 
-__global__ __launch_bounds__(1024) void pose_select_kernel(PoseRansacArgs a) {
+__device__ __forceinline__ void pose_select_body(const PoseRansacArgs a) {
   const unsigned long long best = ransac_select_best(a.n_hyp, a.poses + 12, POSE_FS, a.counts);
   if (threadIdx.x == 0) {
     const int win = best ? (int)(0xFFFFFFFFull - (best & 0xFFFFFFFFull)) : -1;
@@ -312,11 +313,11 @@ __global__ __launch_bounds__(1024) void pose_select_kernel(PoseRansacArgs a) {
   }
 }
 
-__global__ __launch_bounds__(PB) void pose_mask_kernel(PoseRansacArgs a) {
+__device__ __forceinline__ void pose_mask_body(const PoseRansacArgs& a, unsigned bx) {
   __shared__ int s_wave[PB / 64];
   const int n = ransac_rows(a.d_n, a.n_max);
   const int st = a.info[4], win = a.info[2];
-  const int i = blockIdx.x * PB + threadIdx.x;
+  const int i = bx * PB + threadIdx.x;
   bool in = false;
   if (i < n) {
     if (st != VO_POSE_RANSAC_OK) in = true;                      // fallback: every live pair, as the plain frame
@@ -325,16 +326,92 @@ __global__ __launch_bounds__(PB) void pose_mask_kernel(PoseRansacArgs a) {
   if (i < a.n_max) a.mask[i] = in ? 1 : 0;
   int total;
   ransac_rank<PB>(in, s_wave, total);
-  if (threadIdx.x == 0) a.blk[blockIdx.x] = total;
+  if (threadIdx.x == 0) a.blk[bx] = total;
 }
 
-__global__ __launch_bounds__(PB) void pose_scatter_kernel(PoseRansacArgs a) {
+__device__ __forceinline__ void pose_scatter_body(const PoseRansacArgs& a, unsigned bx) {
   __shared__ int s_wave[PB / 64];
-  const int i = blockIdx.x * PB + threadIdx.x;
+  const int i = bx * PB + threadIdx.x;
   const bool in = i < a.n_max && a.mask[i];
   int total;
   const int r = ransac_rank<PB>(in, s_wave, total);
-  if (in) reinterpret_cast<int2*>(a.out_pairs)[a.blk[blockIdx.x] + r] = reinterpret_cast<const int2*>(a.pairs)[i];
+  if (in) reinterpret_cast<int2*>(a.out_pairs)[a.blk[bx] + r] = reinterpret_cast<const int2*>(a.pairs)[i];
+}
+
+// problem p of a batched call: problem 0's arrays moved on by p strides (elements, as vo_picp_solve_batch_dev counts them)
+__device__ __forceinline__ PoseRansacArgs pose_problem(const PoseRansacBatchArgs& b, int p) {
+  PoseRansacArgs a = b.a;
+  const size_t n = (size_t)a.n_max, H = (size_t)a.n_hyp;
+  a.pairs += 2 * p * b.pairs_stride;
+  if (a.d_n) a.d_n += p;
+  a.world += 3 * p * b.world_stride;
+  a.meas += 2 * p * b.meas_stride;
+  a.info += 8 * p;
+  a.pts += p * n;
+  a.pv += p * n;
+  a.poses += p * H * POSE_FS;
+  a.counts += p * H;
+  a.mask += p * n;
+  a.blk += p * (size_t)b.nb;
+  a.out_pairs += 2 * p * b.pairs_stride;
+  a.n_out += p;
+  a.T_out += 16 * p;
+  a.status += p;
+  return a;
+}
+
+}  // namespace
+
+// ---- the single form -------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(PB) void pose_gather_kernel(PoseRansacArgs a) {
+  pose_gather_body(a, blockIdx.x, gridDim.x);
+}
+
+__global__ __launch_bounds__(64) void pose_hyp_kernel(PoseRansacArgs a) { pose_hyp_body(a, blockIdx.x * 64 + threadIdx.x); }
+
+__global__ __launch_bounds__(PB) void pose_score_kernel(PoseRansacArgs a) {
+  pose_score_body(a, blockIdx.x, blockIdx.y);
+}
+
+__global__ __launch_bounds__(1024) void pose_select_kernel(PoseRansacArgs a) { pose_select_body(a); }
+
+__global__ __launch_bounds__(PB) void pose_mask_kernel(PoseRansacArgs a) {
+  pose_mask_body(a, blockIdx.x);
+}
+
+__global__ __launch_bounds__(PB) void pose_scatter_kernel(PoseRansacArgs a) { pose_scatter_body(a, blockIdx.x); }
+
+// ---- the batched form: the problem is the last grid dimension, every kernel runs the single form's body on that problem's
+// arrays.  A workgroup of the scoring, mask and scatter grids that lies wholly beyond its problem's live pairs returns at
+// once (the grids are sized by the capacity): it would add nothing to a count, and the mask bytes and the per-workgroup
+// count it leaves alone were zeroed by the launch.
+__global__ __launch_bounds__(PB) void pose_gather_batch_kernel(PoseRansacBatchArgs b) {
+  const PoseRansacArgs a = pose_problem(b, blockIdx.y);
+  pose_gather_body(a, blockIdx.x, gridDim.x);
+}
+
+__global__ __launch_bounds__(64) void pose_hyp_batch_kernel(PoseRansacBatchArgs b) {
+  pose_hyp_body(pose_problem(b, blockIdx.y), blockIdx.x * 64 + threadIdx.x);
+}
+
+__global__ __launch_bounds__(PB) void pose_score_batch_kernel(PoseRansacBatchArgs b) {
+  const PoseRansacArgs a = pose_problem(b, blockIdx.z);
+  if ((int)blockIdx.x * (PB * POSE_PTS) >= ransac_rows(a.d_n, a.n_max)) return;
+  pose_score_body(a, blockIdx.x, blockIdx.y);
+}
+
+__global__ __launch_bounds__(1024) void pose_select_batch_kernel(PoseRansacBatchArgs b) { pose_select_body(pose_problem(b, blockIdx.x)); }
+
+__global__ __launch_bounds__(PB) void pose_mask_batch_kernel(PoseRansacBatchArgs b) {
+  const PoseRansacArgs a = pose_problem(b, blockIdx.y);
+  if ((int)blockIdx.x * PB >= ransac_rows(a.d_n, a.n_max)) return;
+  pose_mask_body(a, blockIdx.x);
+}
+
+__global__ __launch_bounds__(PB) void pose_scatter_batch_kernel(PoseRansacBatchArgs b) {
+  const PoseRansacArgs a = pose_problem(b, blockIdx.y);
+  if ((int)blockIdx.x * PB >= ransac_rows(a.d_n, a.n_max)) return;
+  pose_scatter_body(a, blockIdx.x);
 }
 
 // ws layout (bytes): [0,256) info (ints [0, 8)), default pair count (int [8]), default pose (floats [16, 32)), then
@@ -380,6 +457,58 @@ hipError_t launch_pose_ransac(hipStream_t st, const PoseRansacArgs& a) {
   e = launch_scan(st, a.blk, nb, a.n_out);
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL(pose_scatter_kernel, dim3(nb), dim3(PB), 0, st, a);
+  return hipGetLastError();
+}
+
+// ws layout of the batched form (bytes, every block 256-aligned; P problems of capacity n, H hypotheses, nb = ceil(n / 256)):
+// info [P][8] ints | per-workgroup counts [P][nb] | counts [P][H]   -- zeroed by every call, as one block
+// pts [P][n] float4 | pv [P][n] | poses [P][H][16] | mask [P][n]
+// (the single form's blocks times P, without its default outputs: those go to the caller's arrays)
+size_t pose_ransac_batch_workspace_bytes(int n_problems, int n_max, int n_hyp) {
+  const size_t P = (size_t)n_problems, n = (size_t)n_max, H = (size_t)n_hyp;
+  return up256(32 * P) + up256(4 * P * (size_t)pose_nb(n_max)) + up256(4 * P * H) + up256(16 * P * n) + up256(4 * P * n) +
+         up256(4 * POSE_FS * P * H) + up256(P * n);
+}
+
+PoseRansacBatchArgs pose_ransac_batch_layout(void* ws, int n_problems, int n_max, int n_hyp) {
+  PoseRansacBatchArgs b{};
+  const size_t P = (size_t)n_problems, n = (size_t)n_max, H = (size_t)n_hyp;
+  char* w = static_cast<char*>(ws);
+  size_t o = 0;
+  b.a.info = reinterpret_cast<int*>(w + o); o += up256(32 * P);
+  b.a.blk = reinterpret_cast<int*>(w + o); o += up256(4 * P * (size_t)pose_nb(n_max));
+  b.a.counts = reinterpret_cast<int*>(w + o); o += up256(4 * P * H);
+  b.a.pts = reinterpret_cast<float4*>(w + o); o += up256(16 * P * n);
+  b.a.pv = reinterpret_cast<float*>(w + o); o += up256(4 * P * n);
+  b.a.poses = reinterpret_cast<float*>(w + o); o += up256(4 * POSE_FS * P * H);
+  b.a.mask = reinterpret_cast<uint8_t*>(w + o);
+  b.a.n_max = n_max; b.a.n_hyp = n_hyp;
+  b.nb = pose_nb(n_max); b.n_problems = n_problems;
+  return b;
+}
+
+// 3 memsets at the most and 7 launches, whatever the number of problems
+hipError_t launch_pose_ransac_batch(hipStream_t st, const PoseRansacBatchArgs& b) {
+  const PoseRansacArgs& a = b.a;
+  const size_t P = (size_t)b.n_problems, H = (size_t)a.n_hyp;
+  // info and the per-workgroup counts, and the hypothesis counts with them while they are the workspace's own
+  const char* zero_end = reinterpret_cast<const char*>(a.blk) + up256(4 * P * (size_t)b.nb);
+  const bool own_counts = reinterpret_cast<const char*>(a.counts) == zero_end;
+  if (own_counts) zero_end += 4 * P * H;
+  hipError_t e = hipMemsetAsync(a.info, 0, (size_t)(zero_end - reinterpret_cast<const char*>(a.info)), st);
+  if (e == hipSuccess && !own_counts) e = hipMemsetAsync(a.counts, 0, 4 * P * H, st);
+  if (e == hipSuccess) e = hipMemsetAsync(a.mask, 0, P * (size_t)a.n_max, st);
+  if (e != hipSuccess) return e;
+  const unsigned np = (unsigned)b.n_problems;
+  hipLaunchKernelGGL(pose_gather_batch_kernel, dim3(b.nb < 1024 ? b.nb : 1024, np), dim3(PB), 0, st, b);
+  hipLaunchKernelGGL(pose_hyp_batch_kernel, dim3((a.n_hyp + 63) / 64, np), dim3(64), 0, st, b);
+  const int nsb = (a.n_max + PB * POSE_PTS - 1) / (PB * POSE_PTS);
+  hipLaunchKernelGGL(pose_score_batch_kernel, dim3(nsb, (a.n_hyp + POSE_HB - 1) / POSE_HB, np), dim3(PB), 0, st, b);
+  hipLaunchKernelGGL(pose_select_batch_kernel, dim3(np), dim3(1024), 0, st, b);
+  hipLaunchKernelGGL(pose_mask_batch_kernel, dim3(b.nb, np), dim3(PB), 0, st, b);
+  e = launch_scan(st, a.blk, b.nb, a.n_out, nullptr, b.n_problems, (size_t)b.nb);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(pose_scatter_batch_kernel, dim3(b.nb, np), dim3(PB), 0, st, b);
   return hipGetLastError();
 }
 

@@ -396,5 +396,17 @@ size_t pose_ransac_workspace_bytes(int n_max, int n_hyp);
 // the workspace's arrays; the caller fills in the inputs and the outputs and may point counts / mask elsewhere
 PoseRansacArgs pose_ransac_layout(void* ws, int n_max, int n_hyp);
 hipError_t launch_pose_ransac(hipStream_t st, const PoseRansacArgs& a);
+// the batched form: `a` holds problem 0's arrays and the settings all problems share; problem p's inputs and outputs lie p
+// strides (in elements: points, pixels, pairs) further, its workspace arrays p x (n_max | n_hyp | nb) items further
+struct PoseRansacBatchArgs {
+  PoseRansacArgs a;
+  size_t world_stride, meas_stride, pairs_stride;
+  int nb;                     // workgroups of 256 pairs per problem = the stride of blk
+  int n_problems;
+};
+size_t pose_ransac_batch_workspace_bytes(int n_problems, int n_max, int n_hyp);
+// the workspace's arrays; the caller fills in the inputs, the strides and the outputs and may point counts / mask elsewhere
+PoseRansacBatchArgs pose_ransac_batch_layout(void* ws, int n_problems, int n_max, int n_hyp);
+hipError_t launch_pose_ransac_batch(hipStream_t st, const PoseRansacBatchArgs& b);
 
 }  // namespace vo

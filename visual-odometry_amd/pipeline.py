@@ -13,7 +13,7 @@ import ctypes as C
 
 import numpy as np
 
-from .api import Context, Event, _chk, _colmajor, _ptr
+from .api import Context, Event, RansacParams, _chk, _colmajor, _ptr
 
 
 class FramePipeline:
@@ -156,6 +156,18 @@ class _FrameBatch(C.Structure):
                 ("counts", C.c_void_p)]
 
 
+class _FrameTrack(C.Structure):
+    """vo_frame_track of include/vo_hip.h"""
+    _fields_ = [("ransac", RansacParams), ("status", C.c_void_p), ("n_tracked", C.c_void_p), ("tracked_pairs", C.c_void_p),
+                ("T_winner", C.c_void_p)]
+
+
+def _track_params(opt):
+    """the batched tracking options: 2 px, 128 hypotheses (batched form), seed 0"""
+    r = dict(dict(threshold_px=2.0, n_hypotheses=128, seed=0), **opt)
+    return RansacParams(int(r["n_hypotheses"]), float(r["threshold_px"]), int(r["seed"]) & 0xFFFFFFFFFFFFFFFF)
+
+
 class BatchPipeline:
     """n_frames independent frame pairs (vo_frames_batch_dev): every stage is one batched launch per call, the solver
     is the batched kernel.  All frames must have the same set sizes.  `fps` is a list of frame-pair dicts, or -- for
@@ -167,12 +179,16 @@ class BatchPipeline:
 
     def __init__(self, ctx: Context, fps, n_iters: int = 50, kernel_threshold: float = 10000.0,
                  with_appearance: bool = True, poses_ptr: int | None = None, n_frames: int | None = None,
-                 upload_block: int = 100, frames_per_call: int | None = None, with_moved: bool = False, X_prev=None):
+                 upload_block: int = 100, frames_per_call: int | None = None, with_moved: bool = False, X_prev=None,
+                 track_ransac: dict | None = None):
         """poses_ptr: optional device buffer (n_frames*16 floats, e.g. a torch tensor's data_ptr) that
         receives the poses directly, so that a collective can read them without a copy.
         with_moved: also produce X_prev * model as an output array (vo_frame_batch.model_moved); without it the solver's
         gather moves the points it fetches itself.  X_prev: optional (F, 4, 4) poses of the previous frames
-        (vo_complete.cpp:159); default: identity."""
+        (vo_complete.cpp:159); default: identity.
+        track_ransac: dict(threshold_px=2.0, n_hypotheses=128, seed=0), any key optional: run() calls vo_frames_batch_track_dev --
+        the batched P3P RANSAC on every frame's joined pairs, the solve from the winners on their inliers; track_stats() and
+        tracked() return what it hands on.  None (default): vo_frames_batch_dev."""
         self.ctx, self.lib = ctx, ctx.lib
         gen = fps if callable(fps) else (lambda lo, hi: fps[lo:hi])
         F = self.F = int(n_frames if n_frames is not None else len(fps))
@@ -209,8 +225,11 @@ class BatchPipeline:
         self.d_tri_xyz, self.d_tri_pairs = a(F * q * 12), a(F * q * 8)
         self.d_tri_app = a(F * q * 40) if with_appearance else 0
         self.d_counts = a(3 * F * 4)
+        self.track = _track_params(track_ransac) if track_ransac is not None else None
+        self._track_bufs = [a(F * 4), a(F * 4), a(F * q * 8), a(F * 64)] if self.track is not None else []
         per_call = F if not frames_per_call else max(1, min(int(frames_per_call), F))
         self.calls = []
+        self.tracks = []
         for lo in range(0, F, per_call):
             hi = min(lo + per_call, F)
             b = _FrameBatch()
@@ -228,11 +247,34 @@ class BatchPipeline:
             b.tri_app = (self.d_tri_app + lo * q * 40) if self.d_tri_app else None
             b.counts = self.d_counts + 3 * lo * 4        # this call's [3][hi - lo] block
             self.calls.append((lo, hi, b))
+            if self.track is not None:
+                st, nt, tp, tw = self._track_bufs
+                self.tracks.append(_FrameTrack(self.track, st + lo * 4, nt + lo * 4, tp + lo * q * 8, tw + lo * 64))
         self.b = self.calls[0][2]
 
     def run(self):
-        for _, _, b in self.calls:
-            _chk(self.lib.vo_frames_batch_dev(self.ctx.h, C.byref(b)))
+        for i, (_, _, b) in enumerate(self.calls):
+            if self.track is not None:
+                _chk(self.lib.vo_frames_batch_track_dev(self.ctx.h, C.byref(b), None, C.byref(self.tracks[i])))
+            else:
+                _chk(self.lib.vo_frames_batch_dev(self.ctx.h, C.byref(b)))
+
+    def track_stats(self):
+        """track_ransac: (status (F,), pairs handed to the solve (F,)) per frame -- VO_POSE_RANSAC_* (0: tracked from the
+        winner; nonzero: the plain frame) and the winner's inlier count (every joined pair on a fallback)"""
+        assert self.track is not None, "BatchPipeline(track_ransac=...) only"
+        st = np.zeros(self.F, np.int32); n = np.zeros(self.F, np.int32)
+        self.ctx.d2h(st, self._track_bufs[0]); self.ctx.d2h(n, self._track_bufs[1])
+        return st, n
+
+    def tracked(self, f):
+        """track_ransac: frame f's (pairs handed to the solve (n, 2), winner pose (4x4))"""
+        n = int(self.track_stats()[1][f])
+        pairs = np.zeros((n, 2), np.int32); T = np.zeros(16, np.float32)
+        if n:
+            self.ctx.d2h(pairs, self._track_bufs[2] + f * self.q * 8)
+        self.ctx.d2h(T, self._track_bufs[3] + f * 64)
+        return pairs, T.reshape(4, 4).T.copy()
 
     def match_only(self):
         """the matcher stage of every call alone (vo_match_appearances_batch_dev on the same inputs, into the same outputs)"""
@@ -288,7 +330,7 @@ class BatchPipeline:
         for d in self._in + [self.d_matches, self.d_joined, self.d_stats, self.d_tri_xyz,
                              self.d_tri_pairs, self.d_counts] + ([self.d_tri_app] if self.d_tri_app else []) + \
                 ([self.d_moved] if self.d_moved else []) + ([self.d_X] if self.d_X else []) + \
-                ([self.d_poses] if self._own_poses else []):
+                ([self.d_poses] if self._own_poses else []) + self._track_bufs:
             self.ctx.free(d)
 
 
@@ -331,10 +373,12 @@ def match_batch_ragged(ctx: Context, apps1, apps2, radius: float = 0.1):
 
 
 def frames_batch_ragged(ctx: Context, frames, K, cam, n_iters: int = 50, kernel_threshold: float = 10000.0, radius: float = 0.1,
-                        keep_outliers: bool = False, X_prev=None):
+                        keep_outliers: bool = False, X_prev=None, track_ransac: dict | None = None):
     """The loop body of vo_complete.cpp:150-179 for many frames of DIFFERENT sizes in ONE call (vo_frames_batch_ragged_dev).
     frames: dicts with ref_app, cur_app, ref_pts, cur_pts, model, model_pairs; cam = (rows, cols, z_near, z_far).
-    Returns per frame a dict(matches, joined, pose, stats, tri_xyz, tri_pairs)."""
+    Returns per frame a dict(matches, joined, pose, stats, tri_xyz, tri_pairs).
+    track_ransac (dict(threshold_px=2.0, n_hypotheses=128, seed=0), any key optional): the call is vo_frames_batch_track_dev
+    and every dict also holds status, tracked_pairs and T_winner."""
     F = len(frames)
     keys = (("ref_app", np.float32, 10), ("cur_app", np.float32, 10), ("ref_pts", np.float32, 2), ("cur_pts", np.float32, 2),
             ("model", np.float32, 3), ("model_pairs", np.int32, 2))
@@ -358,8 +402,14 @@ def frames_batch_ragged(ctx: Context, frames, K, cam, n_iters: int = 50, kernel_
     b.matches, b.joined, b.model_moved, b.poses, b.stats = out["matches"], out["joined"], out["moved"], out["poses"], out["stats"]
     b.tri_xyz, b.tri_pairs, b.tri_app, b.counts = out["tri_xyz"], out["tri_pairs"], None, out["counts"]
     sz = _FrameSizes(d_n["ref_app"], d_n["cur_app"], d_n["model_pairs"])
+    if track_ransac is not None:
+        out.update(status=a(F * 4), n_tracked=a(F * 4), tracked=a(F * q * 8), winners=a(F * 64))
+        tr = _FrameTrack(_track_params(track_ransac), out["status"], out["n_tracked"], out["tracked"], out["winners"])
     try:
-        _chk(ctx.lib.vo_frames_batch_ragged_dev(ctx.h, C.byref(b), C.byref(sz)))
+        if track_ransac is not None:
+            _chk(ctx.lib.vo_frames_batch_track_dev(ctx.h, C.byref(b), C.byref(sz), C.byref(tr)))
+        else:
+            _chk(ctx.lib.vo_frames_batch_ragged_dev(ctx.h, C.byref(b), C.byref(sz)))
         cnt = np.zeros((3, F), np.int32); ctx.d2h(cnt, out["counts"])
         m = np.zeros((F, q, 2), np.int32); ctx.d2h(m, out["matches"])
         j = np.zeros((F, q, 2), np.int32); ctx.d2h(j, out["joined"])
@@ -367,11 +417,20 @@ def frames_batch_ragged(ctx: Context, frames, K, cam, n_iters: int = 50, kernel_
         st = np.zeros((F, 4), np.float32); ctx.d2h(st, out["stats"])
         xyz = np.zeros((F, q, 3), np.float32); ctx.d2h(xyz, out["tri_xyz"])
         tp = np.zeros((F, q, 2), np.int32); ctx.d2h(tp, out["tri_pairs"])
+        if track_ransac is not None:
+            ts = np.zeros(F, np.int32); ctx.d2h(ts, out["status"])
+            tn = np.zeros(F, np.int32); ctx.d2h(tn, out["n_tracked"])
+            tk = np.zeros((F, q, 2), np.int32); ctx.d2h(tk, out["tracked"])
+            tw = np.zeros((F, 16), np.float32); ctx.d2h(tw, out["winners"])
     finally:
         for d in list(dev.values()) + list(d_n.values()) + list(out.values()) + ([d_X] if d_X else []):
             ctx.free(d)
-    return [dict(matches=m[f, : cnt[0, f]].copy(), joined=j[f, : cnt[1, f]].copy(), pose=T[f].reshape(4, 4).T.copy(), stats=st[f].copy(),
-                 tri_xyz=xyz[f, : cnt[2, f]].copy(), tri_pairs=tp[f, : cnt[2, f]].copy()) for f in range(F)]
+    res = [dict(matches=m[f, : cnt[0, f]].copy(), joined=j[f, : cnt[1, f]].copy(), pose=T[f].reshape(4, 4).T.copy(), stats=st[f].copy(),
+                tri_xyz=xyz[f, : cnt[2, f]].copy(), tri_pairs=tp[f, : cnt[2, f]].copy()) for f in range(F)]
+    if track_ransac is not None:
+        for f, r in enumerate(res):
+            r.update(status=int(ts[f]), tracked_pairs=tk[f, : tn[f]].copy(), T_winner=tw[f].reshape(4, 4).T.copy())
+    return res
 
 
 class SequencePipeline:
