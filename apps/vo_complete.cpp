@@ -4,7 +4,7 @@
 // current directory or into argv[2]): world.txt, trajectory_gt.txt, map.txt,
 // map_appearances.txt, trajectory_est_complete.txt, trajectory_est_data.txt.
 //   usage: vo_complete <data dir> [output dir] [rounds=100] [--resident [--match-up-front]] [--exact] [--ransac[=px]]
-//          [--track-ransac[=px]]
+//          [--track-ransac[=px]] [--refine-init[=huber_px]]
 // --resident: the same sequence through vo::DeviceSequence -- all measurement files are read and uploaded first, the
 // whole frame chain runs on the GPU without a host round trip per frame, the map upkeep included (vo_map_*: the
 // reference's upsert as a hash table of first occurrences in device memory).  Same outputs.
@@ -18,8 +18,13 @@
 // threshold px, default 1, seed 0: vo::estimate_pose_ransac / DeviceSequence::setTrackRansac) -- the solver starts from the
 // winner's pose and runs its rounds on the winner's inliers.  A frame the host form refuses (fewer than 4 pairs, no valid
 // hypothesis, fewer than 6 inliers) runs as without the flag, which is what the device form does on its own.
+// --refine-init[=huber_px]: the first relative pose, from either initialisation, is refined by 10 Gauss-Newton rounds on the
+// Sampson error of the first pair's matches (Huber weight at huber_px pixels, default 1, 0: none: vo::refine_transform /
+// DeviceSequence::setInitRefine) before anything uses it; behind --ransac only the winner's inliers take part, marked at
+// their positions among the matches, so that both forms sum the same pairs in the same order and write the same files.
 // Also written: poses_raw.txt, one camera pose per line (row-major 4x4, %.9g = exact float32 round trip), and map_raw.txt,
 // one map entry per line (x y z a0..a9, %.9g).
+#include <cmath>
 #include <cstdio>
 #include <iostream>
 
@@ -50,7 +55,7 @@ static void write_map_raw(const std::string& file, const PointCloudVector<3>& ma
 
 // the device-resident form of the loop below: same call sequence, the frame chain inside vo::DeviceSequence
 static int run_resident(const std::string& path, const std::string& out, int rounds, bool exact, bool up_front, float ransac_px,
-                        float track_px, const std::string& first_file,
+                        float track_px, float refine_px, const std::string& first_file,
                         const std::string& second_file, const std::set<std::string>& files) {
   std::vector<PointCloudVector<2>> frames;
   std::vector<std::string> names{first_file, second_file};
@@ -74,9 +79,15 @@ static int run_resident(const std::string& path, const std::string& out, int rou
   seq.setMatchUpFront(up_front);              // all consecutive pairs in one batched matcher call before the chain
   if (ransac_px > 0.f) seq.setInitRansac(ransac_params(ransac_px));
   if (track_px > 0.f) seq.setTrackRansac(track_ransac_params(track_px));
+  if (refine_px >= 0.f) seq.setInitRefine(10, refine_px);
   seq.setKeepMap(true);                       // map.update / history inside the chain, on the device (vo_complete.cpp:145-147,175-176)
   seq.run();
   const IsometryVector trajectory = seq.trajectory();          // waits for the chain
+  if (refine_px >= 0.f) {
+    const vo_epi_refine_stats rs = seq.initRefineStats();
+    std::printf("refine-init: status %d, %d rounds, %d pairs, cost %.6g -> %.6g\n", rs.status, rs.rounds, rs.n_used, rs.cost_before,
+                rs.cost_after);
+  }
   for (int t = 2; t < seq.frames(); ++t) {
     int n_match, n_join, n_tri;
     seq.counts(t, n_match, n_join, n_tri);
@@ -99,6 +110,7 @@ int main(int argc, char* argv[]) {
   bool resident = false, exact = false, up_front = false;
   float ransac_px = 0.f;                      // 0: no RANSAC
   float track_px = 0.f;                       // 0: no tracking RANSAC
+  float refine_px = -1.f;                     // < 0: no refit of the first pose; otherwise its Huber width (0: no weight)
   std::vector<std::string> pos;
   for (int i = 1; i < argc; ++i) {
     const std::string a(argv[i]);
@@ -114,6 +126,14 @@ int main(int argc, char* argv[]) {
     else if (a.rfind("--track-ransac=", 0) == 0) {
       track_px = std::strtof(a.c_str() + 15, nullptr);
       if (!(track_px > 0.f)) { std::cout << "--track-ransac=px needs a positive threshold" << std::endl; return -1; }
+    }
+    else if (a == "--refine-init") refine_px = 1.f;
+    else if (a.rfind("--refine-init=", 0) == 0) {
+      char* end = nullptr;
+      refine_px = std::strtof(a.c_str() + 14, &end);
+      if (end == a.c_str() + 14 || !(refine_px >= 0.f) || !std::isfinite(refine_px)) {
+        std::cout << "--refine-init=huber_px needs a width >= 0" << std::endl; return -1;
+      }
     }
     else if (a.rfind("--", 0) == 0) { std::cout << "unknown option " << a << std::endl; return -1; }
     else pos.push_back(a);
@@ -134,7 +154,7 @@ int main(int argc, char* argv[]) {
     const auto second_file = *(files.erase(files.begin()));
     files.erase(files.begin());
 
-    if (resident) return run_resident(path, out, rounds, exact, up_front, ransac_px, track_px, first_file, second_file, files);
+    if (resident) return run_resident(path, out, rounds, exact, up_front, ransac_px, track_px, refine_px, first_file, second_file, files);
     PointCloudVector<2> reference_pc, current_pc;
     if (!get_meas_content(path + first_file, reference_pc)) { std::cout << "Unable to open file measurement file 0\n"; return -1; }
     if (!get_meas_content(path + second_file, current_pc)) { std::cout << "Unable to open file measurement file 1\n"; return -1; }
@@ -151,14 +171,21 @@ int main(int argc, char* argv[]) {
     Camera cam(int_params[3], int_params[2], int_params[0], int_params[1], k);
 
     IntPairVector init_pairs;                  // --ransac: the inliers of the first pair's matches
+    std::vector<uint8_t> inlier;
     if (ransac_px > 0.f) {
-      std::vector<uint8_t> inlier;
       estimate_transform_ransac(cam.cameraMatrix(), correspondences_imgs, reference_pc.points(), current_pc.points(),
                                 ransac_params(ransac_px), &inlier);
       for (size_t i = 0; i < correspondences_imgs.size(); ++i) if (inlier[i]) init_pairs.push_back(correspondences_imgs[i]);
     }
-    const Isometry3f X = estimate_transform(cam.cameraMatrix(), ransac_px > 0.f ? init_pairs : correspondences_imgs,
-                                            reference_pc.points(), current_pc.points());
+    Isometry3f X = estimate_transform(cam.cameraMatrix(), ransac_px > 0.f ? init_pairs : correspondences_imgs,
+                                      reference_pc.points(), current_pc.points());
+    if (refine_px >= 0.f) {                    // --refine-init: the matches where they lie, the inliers marked
+      vo_epi_refine_stats rs;
+      X = refine_transform(cam.cameraMatrix(), correspondences_imgs, reference_pc.points(), current_pc.points(), X,
+                           refine_params(10, refine_px), ransac_px > 0.f ? &inlier : nullptr, &rs);
+      std::printf("refine-init: status %d, %d rounds, %d pairs, cost %.6g -> %.6g\n", rs.status, rs.rounds, rs.n_used, rs.cost_before,
+                  rs.cost_after);
+    }
 
     PointCloudVector<3> triangulated_pc;
     IntPairVector correspondences_world;

@@ -15,7 +15,8 @@
 // pairs, same order, same results.  setMatchesExternal(): the pairs come from somewhere else altogether -- the native
 // multi-GPU driver matches blocks of consecutive pairs on the node's GPUs and gathers them (apps/sequence_mgpu.cpp,
 // SURVEY 8(e)) -- as [row][capacity] pairs + one count per row in device memory of this context, row_of[t - 1] naming
-// the row of pair (t-1, t).  setInitRansac(): the first pair's pose comes from vo_estimate_transform_ransac_dev.  setTrackRansac():
+// the row of pair (t-1, t).  setInitRansac(): the first pair's pose comes from vo_estimate_transform_ransac_dev.  setInitRefine():
+// that pose, from either initialisation, is refined by vo_refine_transform_dev before anything uses it.  setTrackRansac():
 // every frame t >= 2 runs vo_estimate_pose_ransac_dev on its joined pairs first, and the solve starts from the winner's
 // pose on the winner's inliers (a frame that falls back is the plain frame; trackStats() reads what each frame did).  The mode in force when run() starts is the one counts() / cloud() read afterwards.
 #pragma once
@@ -91,6 +92,25 @@ class DeviceSequence {
     ransac_params_ = params;
     ransac_ = true;
   }
+  //! refine the first pair's pose, from either initialisation, by vo_refine_transform_dev (Gauss-Newton on the Sampson error:
+  //! `rounds` plain rounds, Huber weight at huber_px pixels, 0: none) before anything uses it; behind setInitRansac only the
+  //! winner's inliers take part (its mask).  A refit that is not accepted leaves the pose as it was (initRefineStats()).
+  void setInitRefine(int rounds = 10, float huber_px = 1.f) {
+    if (ran_) throw Error(VO_ERR_INVALID_ARG, "DeviceSequence: setInitRefine after run()");
+    if (!refine_) {
+      d_refine_ = alloc<float>(16 + 16);          // the refined pose, then vo_epi_refine_stats
+      d_refine_mask_ = alloc<uint8_t>(cap_);
+    }
+    refine_params_.n_rounds = rounds; refine_params_.huber_px = huber_px;
+    refine_ = true;
+  }
+  //! what the refit of a setInitRefine run did (after run())
+  vo_epi_refine_stats initRefineStats() const {
+    if (!refine_ || !ran_) throw Error(VO_ERR_INVALID_ARG, "DeviceSequence::initRefineStats: after run() of a setInitRefine sequence");
+    vo_epi_refine_stats s;
+    check(vo_memcpy_d2h(ctx_, &s, d_refine_ + 16, sizeof(s)), "DeviceSequence::initRefineStats");
+    return s;
+  }
   //! track every frame t >= 2 through vo_estimate_pose_ransac_dev: the solve starts from the winner's pose on the winner's
   //! inliers instead of from the identity on every joined pair (a frame that falls back runs exactly the plain solve)
   void setTrackRansac(const vo_ransac_params& params) {
@@ -150,11 +170,19 @@ class DeviceSequence {
     match(1);
     if (ransac_)
       check(vo_estimate_transform_ransac_dev(ctx_, cam_.cameraMatrix().data(), m_of(1), (int)std::min(n(0), n(1)), cnt(1, 0), pts_of(0),
-                                             (int)n(0), pts_of(1), (int)n(1), &ransac_params_, X0_.data(), nullptr, nullptr, nullptr),
+                                             (int)n(0), pts_of(1), (int)n(1), &ransac_params_, X0_.data(),
+                                             refine_ ? d_refine_mask_ : nullptr, nullptr, nullptr),
             "vo_estimate_transform_ransac_dev");
     else
       check(vo_estimate_transform_dev(ctx_, cam_.cameraMatrix().data(), m_of(1), (int)std::min(n(0), n(1)), cnt(1, 0), pts_of(0), (int)n(0),
                                       pts_of(1), (int)n(1), X0_.data()), "vo_estimate_transform_dev");
+    if (refine_) {
+      check(vo_refine_transform_dev(ctx_, cam_.cameraMatrix().data(), m_of(1), (int)std::min(n(0), n(1)), cnt(1, 0),
+                                    ransac_ ? d_refine_mask_ : nullptr, pts_of(0), (int)n(0), pts_of(1), (int)n(1), X0_.data(), nullptr,
+                                    &refine_params_, d_refine_, reinterpret_cast<vo_epi_refine_stats*>(d_refine_ + 16)),
+            "vo_refine_transform_dev");
+      check(vo_memcpy_d2h(ctx_, X0_.data(), d_refine_, 64), "DeviceSequence::run");
+    }
     triangulate(1, X0_.data());
     const Isometry3f I = Isometry3f::Identity();
     check(vo_memcpy_h2d(ctx_, d_traj_, I.data(), 64), "DeviceSequence::run");
@@ -302,6 +330,10 @@ class DeviceSequence {
   bool ran_ = false;
   bool ransac_ = false;
   vo_ransac_params ransac_params_{};
+  bool refine_ = false;
+  vo_epi_refine_params refine_params_{};
+  float* d_refine_ = nullptr;
+  uint8_t* d_refine_mask_ = nullptr;
   bool track_ = false;
   vo_ransac_params track_params_{};
   float* d_track_T_ = nullptr;

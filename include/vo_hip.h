@@ -492,6 +492,77 @@ int vo_estimate_pose_ransac_batch_dev(vo_ctx *ctx, int n_problems, int rows, int
                                       uint8_t *d_inlier_mask /* [P][pairs_stride] or NULL */,
                                       int32_t *d_hypothesis_counts /* [P][n_hypotheses] or NULL */, int *d_status /* [P] */);
 
+/* ---- non-linear refit of the relative pose (Gauss-Newton on the Sampson error) ---- */
+/* Refines a relative pose X (column-major 4x4, p_cur = X p_ref: what vo_estimate_transform[_ransac] returns) over 2D-2D
+ * pairs = (index in p1, index in p2).  Opt-in: no other entry point calls it.  All arithmetic in double.
+ *
+ * Residual.  Pair (i, j): x1 = (u1, v1, 1) pixel i of p1 (reference image), x2 = (u2, v2, 1) pixel j of p2 (current
+ *   image).  With R, t of X, th = t / |t| and [v]x the cross-product matrix,
+ *     F = K^-T R^T [th]x^T K^-1          (K^-1 in double of the float K: any invertible K)
+ *   so that x1^T F x2 = 0 for a true pair (the orientation of vo_estimate_transform_ransac), and
+ *     r = x1^T F x2 / sqrt((F x2)_0^2 + (F x2)_1^2 + (F^T x1)_0^2 + (F^T x1)_1^2)        (Sampson distance, pixels).
+ *   A pair whose denominator is zero or whose r is not finite is SKIPPED.
+ * Parameters (5).  d = (w0, w1, w2, a, b):  R <- exp([w]x) R;  th <- normalise(th + a b1 + b b2), with
+ *   b1 = normalise(th x e_k), k the axis of the smallest |th_k| (the lowest k on ties), b2 = th x b1.
+ *   |t| of the input is kept as a double factor: the scale is gauge, t_out = |t| th.
+ *   exp([w]x) = I + A W + B W^2, A = sin(|w|)/|w|, B = 2 sin^2(|w|/2)/|w|^2 (series 1 - |w|^2/6, 1/2 - |w|^2/24
+ *   below |w|^2 = 1e-16).
+ * Weight.  Huber on |r| with huber_px (0: none): w = 1 for |r| <= huber_px, else huber_px / |r|.  Cost = sum w r^2.
+ * A round.  J = d r / d d at d = 0 (analytic); H = sum w J^T J, g = sum w J^T r over the pairs taking part; H d = -g
+ *   solved by LDL^T without pivoting -- a pivot that is not > 1e-12 x the largest diagonal entry of H is SINGULAR --
+ *   and the update above applied.  Plain Gauss-Newton: no damping, no line search.  After n_rounds rounds one more
+ *   accumulation evaluates the final cost.  The sums are taken per workgroup of 256 POSITIONS of the pair array and
+ *   added in workgroup order: no atomics, so the result is a function of the positions, the mask and the live count
+ *   alone -- the same bits on every call, and whatever n_max >= the live count is.
+ * Taking part.  Position p < live count takes part when mask is NULL or mask[p] != 0, its indices lie inside the point
+ *   arrays (checked before anything is loaded) and it is not skipped.  n_used counts those, n_bad the marked positions
+ *   with an index outside its array, n_skipped every other live position (unmarked, or skipped):
+ *   n_used + n_skipped + n_bad = live count.  The three counts and cost_before are those of the INPUT pose.
+ * Accept rule.  The refined pose is written (rounded to float, last row 0 0 0 1) when every round's solve was valid, the
+ *   final accumulation used as many pairs as the first and the final cost is <= the initial cost.  Otherwise X_out is
+ *   X_in bit for bit.  cost_after is the cost of the pose written (= cost_before when not accepted); rounds the number
+ *   of updates applied before the refit ended.
+ * Status.  Precedence: BAD_INDEX, then BAD_INPUT, then FEW_PAIRS (all three found at the input pose, before any round),
+ *   then SINGULAR (the first round that meets it ends the refit), then COST_ROSE. */
+#define VO_EPI_REFINE_OK         0
+#define VO_EPI_REFINE_FEW_PAIRS  1   /* fewer than 8 pairs used at the input pose */
+#define VO_EPI_REFINE_SINGULAR   2   /* a round's 5 x 5 system was singular */
+#define VO_EPI_REFINE_COST_ROSE  3   /* the final cost is above the initial one (or pairs dropped out on the way) */
+#define VO_EPI_REFINE_BAD_INPUT  4   /* |t| of X_in is zero or not finite (takes precedence over 1-3) */
+#define VO_EPI_REFINE_BAD_INDEX  5   /* a marked live pair indexes outside its array (takes precedence over 1-4) */
+typedef struct vo_epi_refine_params {
+  int   n_rounds;   /* 1 .. 100 */
+  float huber_px;   /* >= 0 and finite; 0: no Huber weight */
+} vo_epi_refine_params;
+typedef struct vo_epi_refine_stats {
+  int32_t status;                  /* VO_EPI_REFINE_* */
+  int32_t rounds;                  /* updates applied */
+  int32_t n_used, n_skipped, n_bad;
+  int32_t reserved;                /* 0 */
+  double  cost_before, cost_after;
+} vo_epi_refine_stats;
+/* Device form: arrays, pose out and statistics in device memory (d_stats 8-byte aligned), nothing read back,
+ * 2 (n_rounds + 1) launches on the context's stream: capturable (vo_ctx_begin_capture) once a call with the same n_max
+ * has sized the context's workspace; a capture that would need a bigger one is refused (VO_ERR_NOT_READY).
+ * *d_n_pairs (or NULL) <= n_max pairs are live.  d_mask (n_max bytes, or NULL): only marked positions take part -- the
+ * d_inlier_mask of vo_estimate_transform_ransac_dev feeds the refit without a compaction.  The start pose is X_in
+ * (host: copied into the launch arguments) or d_X_in (device; may be d_X_out): exactly one of them.  As it cannot
+ * refuse at run time, every status other than OK falls back to X_out = X_in and the call still returns VO_OK.
+ * Refused (VO_ERR_INVALID_ARG): a NULL required pointer, n_max < 1, a negative point count, n_rounds outside 1 .. 100,
+ * huber_px negative or not finite, both or neither of X_in / d_X_in, a singular K, a misaligned device array. */
+int vo_refine_transform_dev(vo_ctx *ctx, const float K[9], const int32_t *d_pairs, int n_max,
+                            const int *d_n_pairs /* or NULL */, const uint8_t *d_mask /* n_max or NULL */,
+                            const float *d_p1_uv, int n1, const float *d_p2_uv, int n2,
+                            const float X_in[16] /* host, or NULL */, const float *d_X_in /* device, or NULL */,
+                            const vo_epi_refine_params *params, float *d_X_out, vo_epi_refine_stats *d_stats);
+/* Host form: three (with a mask four) uploads, the device call, one read-back of the 64 bytes of the pose and the
+ * statistics.  Same results bit for bit, same refusals, and not during a graph capture.  The status words are
+ * reported in stats_out (required), not as errors: the call returns VO_OK with X_out = X_in for them. */
+int vo_refine_transform(vo_ctx *ctx, const float K[9], const int32_t *pairs, int n,
+                        const uint8_t *mask /* n entries or NULL */, const float *p1_uv, int n1,
+                        const float *p2_uv, int n2, const float X_in[16], const vo_epi_refine_params *params,
+                        float X_out[16], vo_epi_refine_stats *stats_out);
+
 /* ---- many independent frame pairs at once (throughput form of vo_complete.cpp:156-173) ---- */
 /* For each of n_frames independent frame pairs: match -> join -> X_prev * model -> n_iters rounds
  * from the identity -> triangulate, every stage one batched launch (frame = a grid dimension) and

@@ -23,6 +23,11 @@ from .api import (  # noqa: F401
     estimate_pose_ransac,
     estimate_pose_ransac_batch,
     estimate_pose_ransac_batch_dev,
+    EpiRefineParams,
+    EpiRefineStats,
+    EPI_REFINE_STATUS,
+    refine_transform,
+    refine_transform_dev,
     extract_correspondences_world,
     load_library,
     radius_search,

@@ -480,6 +480,58 @@ def estimate_transform_ransac(k, correspondences, p1_img, p2_img, threshold_px=1
     return X.reshape(4, 4).T.copy(), mask[: len(pairs)].astype(bool), n_in.value
 
 
+class EpiRefineParams(C.Structure):
+    """vo_epi_refine_params (include/vo_hip.h)"""
+    _fields_ = [("n_rounds", C.c_int), ("huber_px", C.c_float)]
+
+
+class EpiRefineStats(C.Structure):
+    """vo_epi_refine_stats (include/vo_hip.h)"""
+    _fields_ = [("status", C.c_int32), ("rounds", C.c_int32), ("n_used", C.c_int32), ("n_skipped", C.c_int32),
+                ("n_bad", C.c_int32), ("reserved", C.c_int32), ("cost_before", C.c_double), ("cost_after", C.c_double)]
+
+    def as_dict(self):
+        return dict(status=self.status, rounds=self.rounds, n_used=self.n_used, n_skipped=self.n_skipped, n_bad=self.n_bad,
+                    cost_before=self.cost_before, cost_after=self.cost_after)
+
+
+EPI_REFINE_STATUS = ("OK", "FEW_PAIRS", "SINGULAR", "COST_ROSE", "BAD_INPUT", "BAD_INDEX")     # VO_EPI_REFINE_*
+
+
+def refine_transform_dev(ctx: Context, k, d_pairs, n_max, d_n_pairs, d_mask, d_p1, n1, d_p2, n2, X_in, d_X_in, params: EpiRefineParams,
+                         d_X_out, d_stats):
+    """vo_refine_transform_dev on device pointers (ints; d_n_pairs and d_mask may be None): enqueues and returns.  X_in: a 4x4
+    start pose on the host, or None with d_X_in a device pointer to 16 floats (column-major).  d_X_out: 16 floats,
+    d_stats: 40 bytes (EpiRefineStats)."""
+    v = lambda d: C.c_void_p(d) if d else None
+    _chk(ctx.lib.vo_refine_transform_dev(ctx.h, _ptr(_colmajor(k, 3)), v(d_pairs), C.c_int(n_max), v(d_n_pairs), v(d_mask), v(d_p1),
+                                         C.c_int(n1), v(d_p2), C.c_int(n2), _ptr(_colmajor(X_in, 4)) if X_in is not None else None,
+                                         v(d_X_in), C.byref(params), v(d_X_out), v(d_stats)))
+
+
+def refine_transform(k, correspondences, p1_img, p2_img, X, n_rounds=10, huber_px=0.0, mask=None, ctx: Context | None = None):
+    """Gauss-Newton refit of the relative pose X (4x4, e.g. from estimate_transform[_ransac]) on the Sampson error of the
+    pairs (vo_refine_transform): n_rounds plain rounds, Huber weight at huber_px pixels (0: none), only the pairs marked in
+    mask (one flag per pair, or None: all).  Returns (X_out (4x4), stats dict): X_out is X bit for bit unless
+    stats["status"] == 0 (EPI_REFINE_STATUS names the others)."""
+    ctx = ctx or default_context()
+    pairs = _i32pairs(correspondences)
+    a = _f32(p1_img, (-1, 2))
+    b = _f32(p2_img, (-1, 2))
+    m = None
+    if mask is not None:
+        m = np.ascontiguousarray(np.asarray(mask).reshape(-1) != 0, dtype=np.uint8)
+        if len(m) != len(pairs):
+            raise ValueError("mask must hold one flag per pair")
+    out = np.zeros(16, dtype=np.float32)
+    st = EpiRefineStats()
+    prm = EpiRefineParams(int(n_rounds), float(huber_px))
+    _chk(ctx.lib.vo_refine_transform(ctx.h, _ptr(_colmajor(k, 3)), _ptr(pairs), C.c_int(len(pairs)), _ptr(m) if m is not None else None,
+                                     _ptr(a), C.c_int(len(a)), _ptr(b), C.c_int(len(b)), _ptr(_colmajor(X, 4)), C.byref(prm),
+                                     _ptr(out), C.byref(st)))
+    return out.reshape(4, 4).T.copy(), st.as_dict()
+
+
 def estimate_pose_ransac(k, rows, cols, z_near, z_far, world, meas, correspondences, threshold_px=1.0, n_hypotheses=2048, seed=0,
                          ctx: Context | None = None):
     """P3P RANSAC over 2D-3D pairs (vo_estimate_pose_ransac): n_hypotheses minimal P3P fits scored by reprojection error on

@@ -112,6 +112,7 @@ struct vo_ctx {
   DevBuf ransac_ws;   // points, hypotheses, counts, mask and inlier pairs of vo_estimate_transform_ransac
   DevBuf pose_ws;     // the same for vo_estimate_pose_ransac
   DevBuf pose_batch_ws;   // ... and for vo_estimate_pose_ransac_batch_dev (all problems' blocks)
+  DevBuf refine_ws;   // state and workgroup rows of vo_refine_transform_dev
   DevBuf track_ws;    // vo_frames_batch_track_dev: the moved cloud, the tracked pairs and the winners the caller did not ask for
   // Steering of the automatic matcher by what the previous batched call found: after a call that ran the
   // exact-duplicate pass, "did any frame take it?" travels to pinned host memory behind the call (no wait); a later call
@@ -290,7 +291,7 @@ int vo_ctx_destroy(vo_ctx* c) {
   (void)hipStreamSynchronize(c->stream);
   c->scratch.release(); c->best.release(); c->table.release(); c->counts.release();
   c->batch_pack.release(); c->batch_bad.release(); c->prune_ws.release(); c->epi_ws.release(); c->ransac_ws.release(); c->pose_ws.release();
-  c->pose_batch_ws.release(); c->track_ws.release();
+  c->pose_batch_ws.release(); c->track_ws.release(); c->refine_ws.release();
   if (c->hint_ev) (void)hipEventDestroy(c->hint_ev);
   if (c->hint_host) (void)hipHostFree(c->hint_host);
   if (c->hint_dev) (void)hipFree(c->hint_dev); c->batch_states.release(); c->batch_partials.release(); c->batch_help.release();
@@ -1794,16 +1795,15 @@ int vo_estimate_transform_ransac(vo_ctx* c, const float K[9], const int32_t* pai
 // ---- P3P RANSAC in front of the tracking solve (pose_ransac.hip) ---------------------------------------------------------------
 // gather -> hypotheses -> scoring -> selection (status, pose handed on) -> mask and compaction, all on the stream: the device
 // form never reads back, so it falls back to the plain frame (identity pose, every live pair) where the host form refuses.
-static int pose_ransac_camera(int rows, int cols, int z_near, int z_far, const float K[9], CamK& cam, double Kinv[9]) {
-  for (int i = 0; i < 9; ++i) cam.K[i] = K[i];
-  cam.rows = rows; cam.cols = cols; cam.z_near = z_near; cam.z_far = z_far;
+// K^-1 in double of the float K (column-major in, column-major out): adjugate / determinant; false when K is singular
+static bool invert_k(const float K[9], double Kinv[9]) {
   double k[9];
   for (int i = 0; i < 9; ++i) k[i] = K[i];
 #define VO_K(r, c) k[(r) + 3 * (c)]
   const double c00 = VO_K(1, 1) * VO_K(2, 2) - VO_K(1, 2) * VO_K(2, 1), c01 = VO_K(1, 2) * VO_K(2, 0) - VO_K(1, 0) * VO_K(2, 2),
                c02 = VO_K(1, 0) * VO_K(2, 1) - VO_K(1, 1) * VO_K(2, 0);
   const double det = VO_K(0, 0) * c00 + VO_K(0, 1) * c01 + VO_K(0, 2) * c02;
-  if (!(det != 0.0) || !std::isfinite(det)) return fail(VO_ERR_INVALID_ARG, "vo_estimate_pose_ransac: K is singular");
+  if (!(det != 0.0) || !std::isfinite(det)) return false;
   // inverse = adjugate / det, column-major: Kinv(r, c) = cofactor(c, r) / det
   Kinv[0 + 3 * 0] = c00 / det;
   Kinv[1 + 3 * 0] = c01 / det;
@@ -1815,6 +1815,13 @@ static int pose_ransac_camera(int rows, int cols, int z_near, int z_far, const f
   Kinv[1 + 3 * 2] = (VO_K(0, 2) * VO_K(1, 0) - VO_K(0, 0) * VO_K(1, 2)) / det;
   Kinv[2 + 3 * 2] = (VO_K(0, 0) * VO_K(1, 1) - VO_K(0, 1) * VO_K(1, 0)) / det;
 #undef VO_K
+  return true;
+}
+
+static int pose_ransac_camera(int rows, int cols, int z_near, int z_far, const float K[9], CamK& cam, double Kinv[9]) {
+  for (int i = 0; i < 9; ++i) cam.K[i] = K[i];
+  cam.rows = rows; cam.cols = cols; cam.z_near = z_near; cam.z_far = z_far;
+  if (!invert_k(K, Kinv)) return fail(VO_ERR_INVALID_ARG, "vo_estimate_pose_ransac: K is singular");
   return VO_OK;
 }
 
@@ -1895,6 +1902,78 @@ int vo_estimate_pose_ransac(vo_ctx* c, int rows, int cols, int z_near, int z_far
     VO_HIP_CHECK(hipStreamSynchronize(c->stream));
   }
   if (n_inliers) *n_inliers = cnt;
+  return VO_OK;
+}
+
+// ---- Gauss-Newton refit of the relative pose on the Sampson error (epi_refine.hip) -----------------------------------------------
+// 2 (n_rounds + 1) launches on the stream and nothing else: the start pose travels in the launch arguments or is read from
+// device memory, the state and the workgroup rows live in the context's workspace, pose and statistics are written by the
+// last launch.
+static int refine_check_params(const vo_epi_refine_params* p) {
+  if (p->n_rounds < 1 || p->n_rounds > 100)
+    return fail(VO_ERR_INVALID_ARG, "vo_refine_transform: n_rounds %d outside 1 .. 100", p->n_rounds);
+  if (!(p->huber_px >= 0.f) || !std::isfinite(p->huber_px))
+    return fail(VO_ERR_INVALID_ARG, "vo_refine_transform: huber_px must be >= 0 and finite (%g)", (double)p->huber_px);
+  return VO_OK;
+}
+
+int vo_refine_transform_dev(vo_ctx* c, const float K[9], const int32_t* d_pairs, int n_max, const int* d_n, const uint8_t* d_mask,
+                            const float* d_p1, int n1, const float* d_p2, int n2, const float X_in[16], const float* d_X_in,
+                            const vo_epi_refine_params* params, float* d_X_out, vo_epi_refine_stats* d_stats) {
+  VO_REQUIRE(c && K && d_pairs && d_p1 && d_p2 && params && d_X_out && d_stats, "null argument");
+  VO_REQUIRE((X_in != nullptr) != (d_X_in != nullptr), "exactly one of X_in and d_X_in must be given");
+  VO_REQUIRE(n_max >= 1, "n_max must be positive");
+  VO_REQUIRE(n1 >= 0 && n2 >= 0, "negative point count");
+  VO_REQUIRE(aligned8(d_pairs, d_p1, d_p2, d_stats), "device arrays must be 8-byte aligned");
+  if (int r = refine_check_params(params)) return r;
+  RefineArgs a{};
+  {
+    double Kinv[9];
+    if (!invert_k(K, Kinv)) return fail(VO_ERR_INVALID_ARG, "vo_refine_transform: K is singular");
+    for (int r = 0; r < 3; ++r)
+      for (int q = 0; q < 3; ++q) a.Kinv[3 * r + q] = Kinv[r + 3 * q];
+  }
+  const size_t need = epi_refine_workspace_bytes(n_max);
+  if (c->capturing && c->refine_ws.cap < need)
+    return fail(VO_ERR_NOT_READY, "vo_refine_transform_dev: the workspace would have to grow inside a graph capture (make one "
+                                  "call with n_max %d before capturing)", n_max);
+  if (int r = set_device(c)) return r;
+  VO_HIP_CHECK(c->refine_ws.ensure(need, c->stream));
+  a.pairs = d_pairs; a.n_max = n_max; a.d_n = d_n; a.mask = d_mask; a.p1 = d_p1; a.n1 = n1; a.p2 = d_p2; a.n2 = n2;
+  if (X_in) memcpy(a.X_in, X_in, sizeof(a.X_in));
+  a.d_X_in = d_X_in;
+  a.n_rounds = params->n_rounds; a.huber = (double)params->huber_px;
+  a.X_out = d_X_out; a.stats = d_stats;
+  VO_HIP_CHECK(launch_epi_refine(c->stream, a, c->refine_ws.p));
+  return VO_OK;
+}
+
+int vo_refine_transform(vo_ctx* c, const float K[9], const int32_t* pairs, int n, const uint8_t* mask, const float* p1, int n1,
+                        const float* p2, int n2, const float X_in[16], const vo_epi_refine_params* params, float X_out[16],
+                        vo_epi_refine_stats* stats_out) {
+  VO_REQUIRE(c && K && pairs && p1 && p2 && X_in && params && X_out && stats_out, "null argument");
+  VO_NOT_CAPTURING(c);
+  VO_REQUIRE(n >= 1, "n must be positive");
+  VO_REQUIRE(n1 > 0 && n2 > 0, "empty point set");
+  if (int r = refine_check_params(params)) return r;
+  if (int r = set_device(c)) return r;
+  if (int r = upload(c, c->in[0], pairs, sizeof(int32_t) * 2 * (size_t)n)) return r;
+  if (int r = upload(c, c->in[1], p1, sizeof(float) * 2 * (size_t)n1)) return r;
+  if (int r = upload(c, c->in[2], p2, sizeof(float) * 2 * (size_t)n2)) return r;
+  if (mask)
+    if (int r = upload(c, c->in[3], mask, (size_t)n)) return r;
+  VO_HIP_CHECK(c->out[2].ensure(128, c->stream));
+  struct { float X[16]; vo_epi_refine_stats s; } h;
+  static_assert(sizeof(h) == 104, "pose and statistics come back in one copy");
+  char* d_res = c->out[2].as<char>();
+  if (int r = vo_refine_transform_dev(c, K, c->in[0].as<int32_t>(), n, nullptr, mask ? c->in[3].as<uint8_t>() : nullptr,
+                                      c->in[1].as<float>(), n1, c->in[2].as<float>(), n2, X_in, nullptr, params,
+                                      reinterpret_cast<float*>(d_res), reinterpret_cast<vo_epi_refine_stats*>(d_res + 64)))
+    return r;
+  VO_HIP_CHECK(hipMemcpyAsync(&h, d_res, sizeof(h), hipMemcpyDeviceToHost, c->stream));
+  VO_HIP_CHECK(hipStreamSynchronize(c->stream));
+  memcpy(X_out, h.X, sizeof(h.X));
+  *stats_out = h.s;
   return VO_OK;
 }
 

@@ -352,6 +352,33 @@ hipError_t launch_epi_vote(hipStream_t st, const float K[9], const Pose X[4], co
 // the per-axis maxima of both point sets alone (epi_max_kernel) into out[4], which the caller has zeroed
 hipError_t launch_epi_maxima(hipStream_t st, const float* d_p1, int n1, const float* d_p2, int n2, unsigned* out);
 
+// ---- Gauss-Newton refit of the relative pose on the Sampson error (epi_refine.hip) ---------------------------
+constexpr int REFINE_ROW = 24;  // doubles per workgroup row: 15 of J^T w J (upper triangle, row-major), 5 of J^T w r, the cost,
+                                // then the counts of pairs used / skipped / with a bad index
+struct RefineState {            // head of the workspace; written by the step kernel alone
+  double R[9];                  // row-major
+  double th[3];                 // translation direction
+  double tn;                    // |t| of the input
+  double cost0, cost1;          // cost at the input pose / of the pose handed out
+  int status, rounds, used0, skipped0, bad0, pad;
+  float X_in[16];               // the input's bits, handed back when the refit is not accepted
+};
+struct RefineArgs {
+  const int32_t* pairs; int n_max; const int* d_n;
+  const uint8_t* mask;          // per position, or null
+  const float* p1; int n1;
+  const float* p2; int n2;
+  double Kinv[9];               // K^-1 in double, ROW-major
+  float X_in[16];               // column-major; read when d_X_in is null
+  const float* d_X_in;
+  int n_rounds; double huber;   // 0: no Huber weight
+  RefineState* st; double* partials; int grid;      // set by launch_epi_refine
+  float* X_out; void* stats;    // 16 floats; vo_epi_refine_stats
+};
+size_t epi_refine_workspace_bytes(int n_max);
+// 2 (n_rounds + 1) launches, no memset, no read-back
+hipError_t launch_epi_refine(hipStream_t st, RefineArgs a, void* ws);
+
 // ---- RANSAC in front of the epipolar initialisation (ransac.hip) --------------------------------------------
 struct RansacArgs {
   const int32_t* pairs; int n_max; const int* d_n;

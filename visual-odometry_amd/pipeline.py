@@ -445,7 +445,7 @@ class SequencePipeline:
     def __init__(self, ctx: Context, seq: dict, n_iters: int = 100, kernel_threshold: float = 10000.0,
                  keep_appearance: bool = False, matches: list | None = None, overlap_match: bool = False, exact: bool = False,
                  prematch: bool = False, keep_map: bool = False, map_capacity: int | None = None,
-                 init_ransac: dict | None = None, track_ransac: dict | None = None):
+                 init_ransac: dict | None = None, track_ransac: dict | None = None, init_refine: dict | None = None):
         """prematch: the matcher depends on the appearances alone, so when the whole sequence is on hand -- as it
         is for vo_complete, which reads its measurement files from a directory -- all F-1 consecutive pairs are matched by ONE
         vo_match_appearances_batch_dev call at start() (frames of different sizes, per-frame tree choice as in the single
@@ -465,7 +465,11 @@ class SequencePipeline:
         track_ransac: every frame t >= 2 runs vo_estimate_pose_ransac_dev on its joined pairs first, and the solve starts from
         the winner's pose on the winner's inliers, e.g. dict(threshold_px=1.0, n_hypotheses=2048, seed=0) -- missing keys take
         those values.  A frame that falls back (fewer than 4 pairs, no valid hypothesis, fewer than 6 inliers) is the plain
-        frame; track_stats() reads each frame's status and pair count after run()."""
+        frame; track_stats() reads each frame's status and pair count after run().
+        init_refine: the first relative pose, from either initialisation, goes through vo_refine_transform_dev (Gauss-Newton on
+        the Sampson error) before anything uses it, e.g. dict(n_rounds=10, huber_px=1.0) -- missing
+        keys take those values.  With init_ransac only the winner's inliers take part (its mask, no compaction).  A refit
+        that is not accepted leaves the pose as it was; refine_stats() reads what happened."""
         self.ctx, self.lib = ctx, ctx.lib
         self.n_iters = n_iters
         fr = seq["frames"]
@@ -533,6 +537,13 @@ class SequencePipeline:
             from .api import RansacParams
             r = dict(dict(threshold_px=1.0, n_hypotheses=2048, seed=0), **init_ransac)
             self.ransac = RansacParams(int(r["n_hypotheses"]), float(r["threshold_px"]), int(r["seed"]) & 0xFFFFFFFFFFFFFFFF)
+        self.refine = None
+        if init_refine is not None:
+            from .api import EpiRefineParams
+            r = dict(dict(n_rounds=10, huber_px=1.0), **init_refine)
+            self.refine = EpiRefineParams(int(r["n_rounds"]), float(r["huber_px"]))
+            self.d_refine = a(64 + 64)                                          # the refined pose, then vo_epi_refine_stats
+            self.d_refine_mask = a(cap) if self.ransac is not None else 0
         self.track = None
         if track_ransac is not None:
             from .api import RansacParams
@@ -608,11 +619,21 @@ class SequencePipeline:
         if self.ransac is not None:
             _chk(self.lib.vo_estimate_transform_ransac_dev(self.ctx.h, _ptr(self.K), self._m(1), C.c_int(min(self.n[0], self.n[1])),
                                                            self._cnt(1, 0), self._pts(0), C.c_int(self.n[0]), self._pts(1),
-                                                           C.c_int(self.n[1]), C.byref(self.ransac), _ptr(X), None, None, None))
+                                                           C.c_int(self.n[1]), C.byref(self.ransac), _ptr(X),
+                                                           C.c_void_p(self.d_refine_mask) if self.refine is not None else None,
+                                                           None, None))
         else:
             _chk(self.lib.vo_estimate_transform_dev(self.ctx.h, _ptr(self.K), self._m(1), C.c_int(min(self.n[0], self.n[1])),
                                                     self._cnt(1, 0), self._pts(0), C.c_int(self.n[0]), self._pts(1),
                                                     C.c_int(self.n[1]), _ptr(X)))
+        if self.refine is not None:
+            # the same pairs where they lie (behind RANSAC: the winner's inliers through its mask); 64 bytes come back
+            _chk(self.lib.vo_refine_transform_dev(self.ctx.h, _ptr(self.K), self._m(1), C.c_int(min(self.n[0], self.n[1])),
+                                                  self._cnt(1, 0), C.c_void_p(self.d_refine_mask) if self.ransac is not None else None,
+                                                  self._pts(0), C.c_int(self.n[0]), self._pts(1), C.c_int(self.n[1]), _ptr(X), None,
+                                                  C.byref(self.refine), C.c_void_p(self.d_refine), C.c_void_p(self.d_refine + 64)))
+            X = np.zeros(16, np.float32)
+            self.ctx.d2h(X, self.d_refine)
         self.X0 = X
         self._triangulate(1, X)
         self._release(1)
@@ -704,6 +725,14 @@ class SequencePipeline:
         self.ctx.d2h(c, self.d_track_st)
         return c[:, 0].copy(), c[:, 1].copy()
 
+    def refine_stats(self):
+        """init_refine: the statistics of the first pose's refit (vo_epi_refine_stats as a dict) after initialise()"""
+        assert self.refine is not None, "SequencePipeline(init_refine=...) only"
+        from .api import EpiRefineStats
+        raw = np.zeros(40, np.uint8)
+        self.ctx.d2h(raw, self.d_refine + 64)
+        return EpiRefineStats.from_buffer_copy(raw.tobytes()).as_dict()
+
     def cloud(self, t):
         """triangulated points of frame t (in the frame of camera t), their (idx in frame t, k) pairs and,
         when kept, appearances"""
@@ -739,5 +768,7 @@ class SequencePipeline:
                   self.d_counts, self.d_traj, self.d_ident) + ((self.d_tri_app,) if self.d_tri_app else ()) + \
                 ((self.pre,) if self.pre is not None else ()) + \
                 ((self.d_app_pad, self.d_n_all, self.d_pm, self.d_pm_cnt) if self.prematch else ()) + \
-                ((self.d_track_T, self.d_track_pairs, self.d_track_st) if self.track is not None else ()):
+                ((self.d_track_T, self.d_track_pairs, self.d_track_st) if self.track is not None else ()) + \
+                ((self.d_refine,) if self.refine is not None else ()) + \
+                ((self.d_refine_mask,) if self.refine is not None and self.d_refine_mask else ()):
             self.ctx.free(d)
