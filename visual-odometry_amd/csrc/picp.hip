@@ -78,7 +78,8 @@ constexpr int ACC_STRIDE = 36;
 constexpr int PICP_PARTS = PICP_BLOCK / 32;          // 32-row parts of the first reduction stage
 constexpr int PICP_GROUPS = PICP_BLOCK / 8;          // row groups of the partial-row fetch (8 threads per 128-B row)
 constexpr int STG_STRIDE = PICP_GROUPS + 4;          // floats per slot of the transposed staging (conflict-free 16-B reads)
-constexpr int PICP_SACC = PICP_BLOCK * ACC_STRIDE > 32 * STG_STRIDE ? PICP_BLOCK * ACC_STRIDE : 32 * STG_STRIDE;
+constexpr int PICP_SACC = (PICP_BLOCK / 4) * ACC_STRIDE;   // floats of the reduction's rows: one row per quad (block_reduce_quad)
+constexpr int PICP_SSTG = 32 * STG_STRIDE;                 // floats of the staging of the partial-row sums (picp_round_body)
 // The reduction with a quad pre-reduction in registers: two DPP adds per accumulator leave every quad's sum in its four
 // lanes, lane q of the quad then stores accumulators 8q .. 8q+7 -- TWO 16-byte LDS writes per lane instead of eight (a
 // ds_write_b128 costs ~13 cycles of the wave's LDS path whatever it holds, and the four waves share that path) -- and the
@@ -182,7 +183,8 @@ __device__ __forceinline__ void pose_lane_operands(const Pose& T, float& b0, flo
   b0 = c3 ? t0 : b0; b1 = c3 ? t1 : b1; b2 = c3 ? t2 : b2;
 }
 
-__device__ __forceinline__ Pose picp_tail_direct(float val, float b0, float b1, float b2) {
+// m = lane % 3, the row of dR this lane takes: a caller on a latency chain computes it ahead of the chain (picp_round_body).
+__device__ __forceinline__ Pose picp_tail_direct(float val, float b0, float b1, float b2, int m) {
   const int lane = threadIdx.x & 63;
   float B[6][6], y[6];
 #pragma unroll
@@ -193,7 +195,6 @@ __device__ __forceinline__ Pose picp_tail_direct(float val, float b0, float b1, 
     y[i] = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(val), 36 + i));
   }
   ldlt6_solve_ordered(B, y);
-  const int m = lane % 3;
   const float y3 = y[3], y4 = y[4], y5 = y[5];
   float ang = y3;
   ang = m == 1 ? y4 : ang;
@@ -223,6 +224,9 @@ __device__ __forceinline__ Pose picp_tail_direct(float val, float b0, float b1, 
 #pragma unroll
   for (int i = 0; i < 3; ++i) Tn.t[i] = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(e), 9 + i));
   return Tn;
+}
+__device__ __forceinline__ Pose picp_tail_direct(float val, float b0, float b1, float b2) {
+  return picp_tail_direct(val, b0, b1, b2, (int)(threadIdx.x & 63) % 3);
 }
 
 // what lane l of the solving wave contributes: H(l / 6, l % 6) + damping on the diagonal from the reduced accumulators
@@ -346,11 +350,15 @@ __device__ __forceinline__ void picp_round_body(const PicpParams* __restrict__ P
     pk.base += p * 5 * rb.cap;
     partials += p * rb.partials_stride;
   }
-  __shared__ __attribute__((aligned(16))) float s_acc[PICP_SACC];   // also the staging of the partial rows
+  __shared__ __attribute__((aligned(16))) float s_acc[PICP_SACC];   // rows of the workgroup reduction (block_reduce_quad)
+  // The staging of the partial-row sums is an array of its own: the waves that are still summing staged rows and the waves
+  // that already store their reduction rows touch different memory, so no barrier stands between the tail and the
+  // linearisation.  (s_stat is written and read by wave 0 alone; s_bad has the reduction's barriers between add and read.)
+  __shared__ __attribute__((aligned(16))) float s_stg[PRE ? PICP_SSTG : 4];
   __shared__ float s_part[PICP_PARTS * 32];
   __shared__ float s_stat[4];
   __shared__ int s_bad;
-  const int tid = threadIdx.x;
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
   if (GATHER) {
     if (tid == 0) s_bad = 0;
     __syncthreads();
@@ -358,48 +366,91 @@ __device__ __forceinline__ void picp_round_body(const PicpParams* __restrict__ P
   VO_STAMP(0);
   VO_STAMP_REAL(7);
 
-  // (1) The previous launch's workgroup partials (nb rows of 32 floats, zero-padded to
-  // a multiple of 256 rows) depend on kernel arguments only: their loads go out first,
-  // before anything that waits on a parameter load.  Thread (g = tid/8, q = tid%8) owns
+  // A round is ONE dependency chain -- rows home, sums, solve, linearisation, reduction, row stored -- and each CU runs one
+  // wave per SIMD, so every instruction between "rows home" and "row stored" costs its full issue latency on that chain,
+  // whether it depends on the pose or not.  Everything that depends on the thread index and the arguments alone is therefore
+  // computed in the shadow of the row loads, and pinned there (an opaque asm): left alone the compiler sinks it next to its
+  // use, behind the waits.
+
+  // (0) Camera, threshold, damping and count: scalar loads, issued in front of the row loads (the scalar cache is cold
+  // behind a kernel boundary).  Their wait stands in step (3), still ahead of the first row wait: the parameter block comes
+  // out of the XCD's L2, the rows come from the other XCDs.
+  const bool gathers = GATHER && gt.on != 0;
+  CamK cam = P->cam;
+  float thr = P->thr;
+  float damping = P->damping;
+  int n = gathers ? gt.n_max : P->n_corr;
+  if (BATCH) n = rb.n_pairs[blockIdx.y];
+  if (PRE) __builtin_amdgcn_sched_barrier(0);
+
+  // (1) The previous launch's workgroup partials (nb >= 1 rows of 32 floats, zero-padded to
+  // a multiple of 256 rows) depend on kernel arguments only: their loads are the first
+  // vector-memory instructions of the kernel.  Thread (g = tid/8, q = tid%8) owns
   // the 16-B quad q of rows g + 32j: eight independent 16-B loads per pass (the rows were
   // written by workgroups on all eight XCDs: Infinity-Cache/HBM round trips that must
-  // overlap, not chain).
+  // overlap, not chain).  Quad q of row g lies 16 * tid bytes into a group of 32 rows.
+  constexpr int NJ = 256 / PICP_GROUPS;              // loads per thread and pass of 256 rows
+  const int nb_pad = (nb + 255) & ~255;
   float4 psum = make_float4(0.f, 0.f, 0.f, 0.f);
+  float4 r[NJ];
+  const char* prev = nullptr;
+  const unsigned row_at = (unsigned)tid * 16u;
   // The previous round's pose (written by workgroup 0 of the previous launch, i.e. on another XCD for most readers) goes out
-  // with the partial rows, as VECTOR loads: lane l fetches the column of the old pose it will multiply by in the tail
+  // behind the partial rows, as VECTOR loads: lane l fetches the column of the old pose it will multiply by in the tail
   // (picp_tail_direct: entries 3c .. 3c+2 of the 12 floats, c = l / 3 clamped to 3).
   float pb0 = 0.f, pb1 = 0.f, pb2 = 0.f;
   if (PRE) {
-    const int l = tid & 63;
-    const int c3 = l < 3 ? 0 : (l < 6 ? 3 : (l < 9 ? 6 : 9));
+    static_assert(PICP_PSTRIDE * 4 == 8 * 16 && PICP_GROUPS * 8 == PICP_BLOCK, "a row is eight 16-B quads, a thread per quad of a group");
+    prev = reinterpret_cast<const char*>(partials + (size_t)(blockIdx.x % PICP_REPLICAS) * PICP_SLOTS * nb_pad * PICP_PSTRIDE + (size_t)((it - 1) & (PICP_SLOTS - 1)) * nb_pad * PICP_PSTRIDE);
+#pragma unroll
+    for (int j = 0; j < NJ; ++j)
+      r[j] = *reinterpret_cast<const float4*>(prev + (size_t)(PICP_GROUPS * j) * (PICP_PSTRIDE * 4) + row_at);      // (rows >= nb read as zero)
+    const int c3 = lane < 3 ? 0 : (lane < 6 ? 3 : (lane < 9 ? 6 : 9));
     const float* pp = S->pose[(it - 1) & (PICP_SLOTS - 1)] + c3;
     pb0 = pp[0]; pb1 = pp[1]; pb2 = pp[2];
-  }
-  if (PRE) {
-    const int nb_pad = (nb + 255) & ~255;
-    const float* prev = partials + (size_t)(blockIdx.x % PICP_REPLICAS) * PICP_SLOTS * nb_pad * PICP_PSTRIDE + (size_t)((it - 1) & (PICP_SLOTS - 1)) * nb_pad * PICP_PSTRIDE;
-    const float4* src = reinterpret_cast<const float4*>(prev + (size_t)(tid >> 3) * PICP_PSTRIDE) + (tid & 7);
-    constexpr int NJ = 256 / PICP_GROUPS;              // loads per thread and pass of 256 rows
-    for (int b0 = 0; b0 < nb; b0 += 256) {
-      float4 r[NJ];
-#pragma unroll
-      for (int j = 0; j < NJ; ++j)
-        r[j] = src[(size_t)(b0 + PICP_GROUPS * j) * (PICP_PSTRIDE / 4)];      // (rows >= nb read as zero)
-      // Nothing crosses this line: left alone the scheduler lifts the first add above the third load, the wait in front of
-      // it then holds back loads 3..8 until load 1 is home, and the fetch costs two dependent round trips instead of one.
-      __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-      for (int j = 0; j < NJ; ++j) { psum.x += r[j].x; psum.y += r[j].y; psum.z += r[j].z; psum.w += r[j].w; }
-    }
+    // Nothing crosses this line: the loads above are out before any of what follows is issued.
+    __builtin_amdgcn_sched_barrier(0);
   }
 
-  // (2) this thread's first correspondence (coalesced SoA loads), in flight during the solve
-  const bool gathers = GATHER && gt.on != 0;
-  int n = gathers ? gt.n_max : P->n_corr;
-  if (BATCH) {
-    n = rb.n_pairs[blockIdx.y];
-    n = n < 0 ? 0 : ((size_t)n > rb.cap ? (int)rb.cap : n);
+  // (2) what the thread index and the arguments decide
+  // the accumulators, zeroed once
+  float acc[NACC];
+#pragma unroll
+  for (int k = 0; k < NACC; ++k) {
+    if (FINISH) acc[k] = 0.f;
+    else asm volatile("v_mov_b32 %0, 0" : "=v"(acc[k]));
   }
+  // where this thread's entry of the partial row goes (threads < PICP_PSTRIDE), one address per replica
+  // (an address goes through the asm as an integer and comes back as a pointer to GLOBAL memory: a pointer that went through
+  // it would come back generic, and its accesses as flat ones, which count against the LDS waits too)
+  typedef __attribute__((address_space(1))) float* global_ptr;
+  typedef const __attribute__((address_space(1))) float* global_cptr;
+  unsigned long long dst[PICP_REPLICAS];
+#pragma unroll
+  for (int k = 0; k < PICP_REPLICAS; ++k) {
+    dst[k] = reinterpret_cast<unsigned long long>(partials + (size_t)k * PICP_SLOTS * nb_pad * PICP_PSTRIDE + ((size_t)(it & (PICP_SLOTS - 1)) * nb_pad + blockIdx.x) * PICP_PSTRIDE + tid);
+    if (!FINISH) asm volatile("" : "+v"(dst[k]));
+  }
+  // the summing lanes of step (6): lane l < 36 sums the slot of H(r, c), lanes 36.. slots 21..; the row of dR a lane takes in
+  // the pose composition (picp_tail_direct)
+  int stg_at = 0, diag = 0, m3 = 0, stg_to = 0;
+  if (PRE) {
+    const int rr = lane / 6, cc = lane - 6 * rr;
+    const int lo = rr < cc ? rr : cc, hi = rr < cc ? cc : rr;
+    const int slot = lane < 36 ? (13 * lo - lo * lo) / 2 + (hi - lo)      // row-major upper triangle
+                               : 21 + (lane - 36);                       // 21..26 b, 27..29 chi_in, chi_out, n_in (TALLY: 30 dropped pairs, 31 their mark)
+    stg_at = slot * STG_STRIDE;
+    diag = lane < 36 && rr == cc;
+    m3 = lane % 3;
+    stg_to = (tid & 7) * 4 * STG_STRIDE + (tid >> 3);
+    asm volatile("" : "+v"(stg_at), "+v"(diag), "+v"(m3), "+v"(stg_to));
+  }
+
+  // (3) The parameters are waited for here, and pinned in scalar registers (left alone the compiler re-loads them after the
+  // solve, on the chain); what follows from them -- the gates' bounds as floats, whether this thread has a correspondence and
+  // where it lies -- is computed here too.
+  // (readfirstlane: a no-op on a scalar load; behind the stamps' stores of the diagnostic build the count is a vector load)
+  if (BATCH) n = __builtin_amdgcn_readfirstlane(n < 0 ? 0 : ((size_t)n > rb.cap ? (int)rb.cap : n));
   if (gathers) {
     if (gt.d_n) { const int m = *gt.d_n; n = m < gt.n_max ? (m < 0 ? 0 : m) : gt.n_max; }
     if (blockIdx.x == 0 && tid == 0) const_cast<PicpParams*>(P)->n_corr = n;
@@ -418,57 +469,71 @@ __device__ __forceinline__ void picp_round_body(const PicpParams* __restrict__ P
     }
     pk.arr(0)[i] = x; pk.arr(1)[i] = y; pk.arr(2)[i] = z; pk.arr(3)[i] = u; pk.arr(4)[i] = v;
   };
-  // camera and threshold: fetched here, while the partial rows are in flight, and pinned in scalar registers (left
-  // alone the compiler re-loads them after the solve, on the chain)
-  CamK cam = P->cam;
-  float thr = P->thr;
-  float damping = P->damping;
   asm volatile("" : "+s"(damping), "+s"(nb));
+  if (!GATHER) asm volatile("" : "+s"(n));                  // (the gathering round's count goes through its own logic above)
+  CamBounds cb = cam_bounds(cam);
   if (!FINISH) {
 #pragma unroll
     for (int k = 0; k < 9; ++k) asm volatile("" : "+s"(cam.K[k]));
     asm volatile("" : "+s"(cam.rows), "+s"(cam.cols), "+s"(cam.z_near), "+s"(cam.z_far), "+s"(thr));
+    asm volatile("" : "+v"(cb.z_far), "+v"(cb.z_near), "+v"(cb.u_max), "+v"(cb.v_max));     // the gates' bounds as floats
   }
   int i = blockIdx.x * PICP_BLOCK + tid;
   bool have = !FINISH && i < n;
+  // Where the grid covers the call (the headline's case) a thread has one correspondence and the linearisation is straight-line
+  // code; beyond the grid cap the threads loop.  Wave-uniform.
+  const int stride = gridDim.x * PICP_BLOCK;
+  const bool one_each = stride >= n;
+  unsigned long long at[5];
+#pragma unroll
+  for (int k = 0; k < 5; ++k) {
+    at[k] = reinterpret_cast<unsigned long long>(pk.arr(k) + i);
+    if (PRE && !FINISH) asm volatile("" : "+v"(at[k]));
+  }
+  auto corr = [&](int k) { return *reinterpret_cast<global_cptr>(at[k]); };
+
+  if (PRE) {
+    // Nothing crosses this line either: left alone the scheduler lifts the first add above the third load, the wait in front
+    // of it then holds back loads 3..8 until load 1 is home, and the fetch costs two dependent round trips instead of one.
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) { psum.x += r[j].x; psum.y += r[j].y; psum.z += r[j].z; psum.w += r[j].w; }
+    for (int b0 = 256; b0 < nb; b0 += 256) {           // further passes of 256 rows
+#pragma unroll
+      for (int j = 0; j < NJ; ++j)
+        r[j] = *reinterpret_cast<const float4*>(prev + (size_t)(b0 + PICP_GROUPS * j) * (PICP_PSTRIDE * 4) + row_at);
+      __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+      for (int j = 0; j < NJ; ++j) { psum.x += r[j].x; psum.y += r[j].y; psum.z += r[j].z; psum.w += r[j].w; }
+    }
+  }
+  // (4) this thread's first correspondence (coalesced SoA loads), in flight during the solve.  The loads go out behind the
+  // rows' waits, not in front of them: the waves without a correspondence skip the five, so a wait on a row could no longer
+  // count on them and would wait for most of them as well.  Their addresses are ready (step (3)).
   float x = 0.f, y = 0.f, z = 0.f, u = 0.f, v = 0.f;
   if (have) {
     if (gathers) gather(i, x, y, z, u, v);
-    else { x = pk.arr(0)[i]; y = pk.arr(1)[i]; z = pk.arr(2)[i]; u = pk.arr(3)[i]; v = pk.arr(4)[i]; }
+    else { x = corr(0); y = corr(1); z = corr(2); u = corr(3); v = corr(4); }
   }
 
   Pose T;
   if (PRE) {
     VO_STAMP(1);
-    // (3) stage the 32 group sums transposed: s_acc[slot*36 + group], so that one slot's 32
+    // (5) stage the 32 group sums transposed: s_stg[slot*36 + group], so that one slot's 32
     // values are eight conflict-free 16-B reads.
-    {
-      const int g32 = tid >> 3, q4 = (tid & 7) * 4;
-      s_acc[(q4 + 0) * STG_STRIDE + g32] = psum.x;
-      s_acc[(q4 + 1) * STG_STRIDE + g32] = psum.y;
-      s_acc[(q4 + 2) * STG_STRIDE + g32] = psum.z;
-      s_acc[(q4 + 3) * STG_STRIDE + g32] = psum.w;
-    }
+    s_stg[stg_to + 0 * STG_STRIDE] = psum.x;
+    s_stg[stg_to + 1 * STG_STRIDE] = psum.y;
+    s_stg[stg_to + 2 * STG_STRIDE] = psum.z;
+    s_stg[stg_to + 3 * STG_STRIDE] = psum.w;
     __syncthreads();
-    // (4) Every wave finishes the sums it needs and runs the (uniform) 6x6 solve on its own:
+    // (6) Every wave finishes the sums it needs and runs the (uniform) 6x6 solve on its own:
     // the four waves sit on four SIMDs, so the redundancy is free and spares three
     // workgroup barriers plus the LDS broadcast of the pose.  Lane l < 36 builds H(r,c)
     // (+damping on the diagonal, picp_solver.cpp:102), lanes 36..41 -b, lanes 42..44 the
     // statistics.  Fixed order => every wave of every workgroup gets the same bits.
-    const int wave = tid >> 6, lane = tid & 63;
     float val = 0.f;                                         // this lane's entry of the system (picp_tail_direct)
     if (lane < (TALLY ? 47 : 45)) {
-      int slot;
-      bool diag = false;
-      if (lane < 36) {
-        const int r = lane / 6, c = lane - 6 * r;
-        const int lo = r < c ? r : c, hi = r < c ? c : r;
-        slot = (13 * lo - lo * lo) / 2 + (hi - lo);          // row-major upper triangle
-        diag = r == c;
-      } else {
-        slot = 21 + (lane - 36);                             // 21..26 b, 27..29 chi_in, chi_out, n_in (TALLY: 30 dropped pairs, 31 their mark)
-      }
-      const float4* row = reinterpret_cast<const float4*>(s_acc + slot * STG_STRIDE);
+      const float4* row = reinterpret_cast<const float4*>(s_stg + stg_at);
       float tsum = 0.f;
 #pragma unroll
       for (int k = 0; k < PICP_GROUPS / 4; ++k) { const float4 t4 = row[k]; tsum += t4.x; tsum += t4.y; tsum += t4.z; tsum += t4.w; }
@@ -487,7 +552,7 @@ __device__ __forceinline__ void picp_round_body(const PicpParams* __restrict__ P
     }
     VO_STAMP(2);
     {
-      const Pose Tn = picp_tail_direct(val, pb0, pb1, pb2);
+      const Pose Tn = picp_tail_direct(val, pb0, pb1, pb2, m3);
       if (tid == 0 && blockIdx.x == 0) {
         store_pose12(S->pose[FINISH ? 0 : (it & (PICP_SLOTS - 1))], Tn);
         if (FINISH) {
@@ -512,7 +577,6 @@ __device__ __forceinline__ void picp_round_body(const PicpParams* __restrict__ P
     }
     VO_STAMP(3);
     if (FINISH) return;
-    __syncthreads();   // every wave is done with the staged rows: s_acc is reused by the reduction
   } else if (gathers && gt.T0) {
     // a pending pose reset: every workgroup takes the pose from T0 itself (workgroup 0 rewrites pose[0] meanwhile)
     Pose T0p;
@@ -526,19 +590,25 @@ __device__ __forceinline__ void picp_round_body(const PicpParams* __restrict__ P
     T = uniform_pose(load_pose12(S->pose[0]));
   }
 
-  float acc[NACC];
+  if (one_each) {
+    if (have) picp_accumulate_t<PINHOLE, KEEP>(cam, cb, T, thr, x, y, z, u, v, acc);
+  } else {
+    // (accumulators of its own: sharing the zeroed ones between the two paths costs a register copy of each on both)
+    float acl[NACC];
 #pragma unroll
-  for (int k = 0; k < NACC; ++k) acc[k] = 0.f;
-  const int stride = gridDim.x * PICP_BLOCK;
-  while (have) {
-    const float cx = x, cy = y, cz = z, cu = u, cv = v;
-    i += stride;
-    have = i < n;
-    if (have) {
-      if (gathers) gather(i, x, y, z, u, v);
-      else { x = pk.arr(0)[i]; y = pk.arr(1)[i]; z = pk.arr(2)[i]; u = pk.arr(3)[i]; v = pk.arr(4)[i]; }
+    for (int k = 0; k < NACC; ++k) acl[k] = 0.f;
+    while (have) {
+      const float cx = x, cy = y, cz = z, cu = u, cv = v;
+      i += stride;
+      have = i < n;
+      if (have) {
+        if (gathers) gather(i, x, y, z, u, v);
+        else { x = pk.arr(0)[i]; y = pk.arr(1)[i]; z = pk.arr(2)[i]; u = pk.arr(3)[i]; v = pk.arr(4)[i]; }
+      }
+      picp_accumulate_t<PINHOLE, KEEP>(cam, cb, T, thr, cx, cy, cz, cu, cv, acl);
     }
-    picp_accumulate_t<PINHOLE, KEEP>(cam, T, thr, cx, cy, cz, cu, cv, acc);
+#pragma unroll
+    for (int k = 0; k < NACC; ++k) acc[k] = acl[k];
   }
   if (gathers && nbad) atomicAdd(&s_bad, nbad);             // (the reduction's barriers stand between this and the read below)
   VO_STAMP(4);
@@ -552,8 +622,7 @@ __device__ __forceinline__ void picp_round_body(const PicpParams* __restrict__ P
       if (tid == PICP_GATHERED_SLOT) o = 1.f;
     }
 #pragma unroll
-    for (int r = 0; r < PICP_REPLICAS; ++r)
-      partials[(size_t)r * PICP_SLOTS * ((nb + 255) & ~255) * PICP_PSTRIDE + ((size_t)(it & (PICP_SLOTS - 1)) * ((nb + 255) & ~255) + blockIdx.x) * PICP_PSTRIDE + tid] = o;
+    for (int k = 0; k < PICP_REPLICAS; ++k) *reinterpret_cast<global_ptr>(dst[k]) = o;
   }
   VO_STAMP(6);
 }

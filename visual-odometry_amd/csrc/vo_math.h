@@ -211,15 +211,24 @@ VO_HD bool is_pinhole(const float K[9]) {
 // MUL0: the zeroing of a term that must not contribute through vo_mul0 (four selects instead of eight; same values for every
 // contributing term).  The batched solver, bound by VALU issue, takes it (-2 %: 1.56 -> 1.53 ms per 200 x 50k x 50 rounds); the
 // launch-per-round kernels, a latency chain, do not (the VOP3 products lengthen it: 4.57 -> 4.60 us per round).
+// The gates' bounds as the floats the comparisons take (camera.h:28, :32-34): a caller that runs on a latency chain converts
+// them once, ahead of it (picp_round_body).
+struct CamBounds {
+  float z_far, z_near, u_max, v_max;
+};
+VO_HD CamBounds cam_bounds(const CamK& cam) {
+  return CamBounds{(float)cam.z_far, (float)cam.z_near, (float)(cam.cols - 1), (float)(cam.rows - 1)};
+}
+
 template <bool PINHOLE, bool KEEP, bool STATS = true, bool MUL0 = false>
-VO_HD void picp_accumulate_t(const CamK& cam, const Pose& T, float thr, float wx, float wy, float wz,
+VO_HD void picp_accumulate_t(const CamK& cam, const CamBounds& cb, const Pose& T, float thr, float wx, float wy, float wz,
                              float zu, float zv, float acc[NACC]) {
   constexpr bool keep_outliers = KEEP;
   // pc = t + R p (camera.h:27), one FMA per product
   const float pc0 = vo_fma(T.R[6], wz, vo_fma(T.R[3], wy, vo_fma(T.R[0], wx, T.t[0])));
   const float pc1 = vo_fma(T.R[7], wz, vo_fma(T.R[4], wy, vo_fma(T.R[1], wx, T.t[1])));
   const float pc2 = vo_fma(T.R[8], wz, vo_fma(T.R[5], wy, vo_fma(T.R[2], wx, T.t[2])));
-  const bool z_ok = !(pc2 > (float)cam.z_far || pc2 < (float)cam.z_near);       // camera.h:28
+  const bool z_ok = !(pc2 > cb.z_far || pc2 < cb.z_near);                       // camera.h:28
   float ph0, ph1, ph2;                                                          // camera.h:30
   if (PINHOLE) {
     ph0 = vo_fma(cam.K[0], pc0, cam.K[6] * pc2);
@@ -232,7 +241,7 @@ VO_HD void picp_accumulate_t(const CamK& cam, const Pose& T, float thr, float wx
   }
   float iz = vo_recip_z(ph2);                                                   // camera.h:31, picp_solver.cpp:44
   const float u = ph0 * iz, v = ph1 * iz;
-  const bool in_img = !(u < 0.f || u > (float)(cam.cols - 1)) && !(v < 0.f || v > (float)(cam.rows - 1));
+  const bool in_img = !(u < 0.f || u > cb.u_max) && !(v < 0.f || v > cb.v_max);
   const bool ok = z_ok && in_img && !is_dropped(wx);                            // :32-34, :72-73
   float e0 = u - zu, e1 = v - zv;                                               // :35
   const float chi = vo_fma(e0, e0, e1 * e1);                                    // :75
@@ -314,6 +323,12 @@ VO_HD void picp_accumulate_t(const CamK& cam, const Pose& T, float thr, float wx
     if (!z0) acc[21 + r] = vo_fma(L0[r], e0, acc[21 + r]);
     if (!z1) acc[21 + r] = vo_fma(L1[r], e1, acc[21 + r]);
   }
+}
+
+template <bool PINHOLE, bool KEEP, bool STATS = true, bool MUL0 = false>
+VO_HD void picp_accumulate_t(const CamK& cam, const Pose& T, float thr, float wx, float wy, float wz,
+                             float zu, float zv, float acc[NACC]) {
+  picp_accumulate_t<PINHOLE, KEEP, STATS, MUL0>(cam, cam_bounds(cam), T, thr, wx, wy, wz, zu, zv, acc);
 }
 
 // ---- reference-order ("exact") form of the same term --------------------------
