@@ -1,0 +1,146 @@
+// vo/localise.hpp -- reading the device map by appearance (vo_map_lookup*, vo_map_localise*): an extension of the facade,
+// not a reference interface (the reference never reads its map back).  DeviceMap owns a vo_map: update() is
+// PointCloudVector<3>::update, lookup() answers "which entries of the map does this frame see?", localise() "where is this
+// camera in the map?" -- lookup -> P3P RANSAC -> PICP rounds, from the frame alone.  A frame that cannot be localised is a
+// status in the statistics, not an exception; vo::Error is thrown where the C call refuses.
+#pragma once
+
+#include <cstdint>
+#include <vector>
+
+#include "camera.hpp"
+#include "context.hpp"
+#include "ransac.hpp"
+#include "utils.hpp"
+
+namespace vo {
+
+//! defaults of apps/localise: 64 hypotheses, 2 px, seed 0
+inline vo_ransac_params localise_ransac_params(float threshold_px = 2.f, int n_hypotheses = 64, uint64_t seed = 0) {
+  return ransac_params(threshold_px, n_hypotheses, seed);
+}
+
+struct LocaliseOptions {
+  vo_ransac_params ransac = localise_ransac_params();   //!< n_hypotheses == 0: no RANSAC, the prior T0 is the start
+  float kernel_threshold = 10000.f;
+  int n_iters = 50;
+  int min_inliers = 6;
+};
+
+inline const char* localise_status_name(int status) {
+  static const char* names[] = {"OK", "FEW_MATCHES", "NO_CONSENSUS", "FEW_INLIERS", "NOT_FINITE"};
+  return status >= 0 && status < 5 ? names[status] : "?";
+}
+
+class DeviceMap {
+ public:
+  explicit DeviceMap(int capacity = 0, Context& ctx = default_context()) : ctx_(ctx.handle()) {
+    check(vo_map_create(ctx_, capacity, &h_), "vo_map_create");
+  }
+  ~DeviceMap() { if (h_) vo_map_destroy(h_); }
+  DeviceMap(const DeviceMap&) = delete;
+  DeviceMap& operator=(const DeviceMap&) = delete;
+  vo_map* handle() const { return h_; }
+
+  //! map.update(T * cloud) (PointCloud.h:52-66)
+  void update(const Vector3fVector& points, const Vector10fVector& appearances, const Isometry3f* T = nullptr) {
+    if (points.size() != appearances.size()) throw Error(VO_ERR_INVALID_ARG, "DeviceMap::update: points and appearances differ in size");
+    check(vo_map_update(h_, points.empty() ? nullptr : points[0].data(), appearances.empty() ? nullptr : appearances[0].data(),
+                        (int)points.size(), T ? T->data() : nullptr), "vo_map_update");
+  }
+  int size() const { int n = 0; check(vo_map_size(h_, &n), "vo_map_size"); return n; }
+  void clear() { check(vo_map_clear(h_), "vo_map_clear"); }
+
+  //! the hits in query order as (query index, entry index); *points: the hit entries' points; *entries: the entry of every
+  //! query, -1 for none
+  IntPairVector lookup(const Vector10fVector& appearances, Vector3fVector* points = nullptr, std::vector<int32_t>* entries = nullptr) const {
+    const int n = (int)appearances.size();
+    IntPairVector pairs(appearances.size());
+    if (points) points->resize(appearances.size());
+    if (entries) entries->assign(appearances.size(), -1);
+    int k = 0;
+    check(vo_map_lookup(h_, n ? appearances[0].data() : nullptr, n, n ? pair_data(pairs) : nullptr, &k,
+                        points && n ? (*points)[0].data() : nullptr, entries && n ? entries->data() : nullptr), "vo_map_lookup");
+    pairs.resize((size_t)k);
+    if (points) points->resize((size_t)k);
+    return pairs;
+  }
+
+  //! pose of the camera in the map (p_cam = T * p_map) from one frame; stats->status says whether it is one (VO_MAP_LOCALISE_*):
+  //! otherwise the result is *T0, or the identity
+  Isometry3f localise(const Camera& cam, const Vector2fVector& pixels, const Vector10fVector& appearances,
+                      const LocaliseOptions& opt = LocaliseOptions(), vo_map_localise_stats* stats = nullptr,
+                      const Isometry3f* T0 = nullptr) const {
+    if (pixels.size() != appearances.size()) throw Error(VO_ERR_INVALID_ARG, "DeviceMap::localise: pixels and appearances differ in size");
+    Isometry3f T = Isometry3f::Identity();
+    vo_map_localise_stats s{};
+    check(vo_map_localise(h_, cam.rows(), cam.cols(), cam.zNear(), cam.zFar(), cam.cameraMatrix().data(), detail::ptr(pixels),
+                          appearances.empty() ? nullptr : appearances[0].data(), (int)pixels.size(), &opt.ransac, opt.kernel_threshold,
+                          opt.n_iters, opt.min_inliers, T0 ? T0->data() : nullptr, T.data(), &s), "vo_map_localise");
+    if (stats) *stats = s;
+    return T;
+  }
+
+  //! every frame of `pixels` / `appearances` in ONE call (vo_map_localise_batch_dev): padded to the largest frame, uploaded,
+  //! localised, read back.  stats (if given) receives one entry per frame.
+  IsometryVector localise_batch(const Camera& cam, const std::vector<Vector2fVector>& pixels, const std::vector<Vector10fVector>& appearances,
+                                const LocaliseOptions& opt = LocaliseOptions(), std::vector<vo_map_localise_stats>* stats = nullptr,
+                                const IsometryVector* T0 = nullptr) const {
+    const size_t F = pixels.size();
+    if (appearances.size() != F || (T0 && T0->size() != F)) throw Error(VO_ERR_INVALID_ARG, "DeviceMap::localise_batch: per-frame arrays differ in size");
+    IsometryVector out(F, Isometry3f::Identity());
+    if (stats) stats->assign(F, vo_map_localise_stats{});
+    if (F == 0) return out;
+    size_t cap = 1;
+    for (size_t f = 0; f < F; ++f) {
+      if (pixels[f].size() != appearances[f].size()) throw Error(VO_ERR_INVALID_ARG, "DeviceMap::localise_batch: pixels and appearances differ in size");
+      if (pixels[f].size() > cap) cap = pixels[f].size();
+    }
+    std::vector<float> uv(F * cap * 2, 0.f), app(F * cap * 10, 0.f);
+    std::vector<int> n(F);
+    for (size_t f = 0; f < F; ++f) {
+      n[f] = (int)pixels[f].size();
+      for (size_t i = 0; i < pixels[f].size(); ++i) {
+        for (int k = 0; k < 2; ++k) uv[(f * cap + i) * 2 + k] = pixels[f][i][k];
+        for (int k = 0; k < 10; ++k) app[(f * cap + i) * 10 + k] = appearances[f][i][k];
+      }
+    }
+    struct Buf {
+      vo_ctx* c; void* p = nullptr;
+      Buf(vo_ctx* ctx, size_t bytes, const void* src) : c(ctx) {
+        check(vo_dev_alloc(c, bytes, &p), "vo_dev_alloc");
+        if (src) { const int rc = vo_memcpy_h2d(c, p, src, bytes); if (rc != VO_OK) { vo_dev_free(c, p); check(rc, "vo_memcpy_h2d"); } }
+      }
+      ~Buf() { if (p) vo_dev_free(c, p); }
+      Buf(const Buf&) = delete;
+      Buf& operator=(const Buf&) = delete;
+    };
+    Buf d_uv(ctx_, uv.size() * sizeof(float), uv.data()), d_app(ctx_, app.size() * sizeof(float), app.data());
+    Buf d_n(ctx_, F * sizeof(int), n.data()), d_T(ctx_, F * 64, nullptr), d_st(ctx_, F * sizeof(vo_map_localise_stats), nullptr);
+    Buf d_T0(ctx_, F * 64, T0 ? (const void*)(*T0)[0].data() : nullptr);
+    check(vo_map_localise_batch_dev(h_, (int)F, cam.rows(), cam.cols(), cam.zNear(), cam.zFar(), cam.cameraMatrix().data(),
+                                    static_cast<const float*>(d_uv.p), cap, static_cast<const float*>(d_app.p), cap, (int)cap,
+                                    static_cast<const int*>(d_n.p), &opt.ransac, opt.kernel_threshold, opt.n_iters, opt.min_inliers,
+                                    T0 ? static_cast<const float*>(d_T0.p) : nullptr, static_cast<float*>(d_T.p),
+                                    static_cast<vo_map_localise_stats*>(d_st.p)), "vo_map_localise_batch_dev");
+    check(vo_memcpy_d2h(ctx_, out[0].data(), d_T.p, F * 64), "vo_memcpy_d2h");
+    if (stats) check(vo_memcpy_d2h(ctx_, stats->data(), d_st.p, F * sizeof(vo_map_localise_stats)), "vo_memcpy_d2h");
+    return out;
+  }
+
+ private:
+  vo_ctx* ctx_ = nullptr;
+  vo_map* h_ = nullptr;
+};
+
+//! free functions with the library's error behaviour
+inline IntPairVector map_lookup(const DeviceMap& map, const Vector10fVector& appearances, Vector3fVector* points = nullptr) {
+  return map.lookup(appearances, points);
+}
+inline Isometry3f map_localise(const DeviceMap& map, const Camera& cam, const Vector2fVector& pixels, const Vector10fVector& appearances,
+                               const LocaliseOptions& opt = LocaliseOptions(), vo_map_localise_stats* stats = nullptr,
+                               const Isometry3f* T0 = nullptr) {
+  return map.localise(cam, pixels, appearances, opt, stats, T0);
+}
+
+}  // namespace vo

@@ -665,6 +665,105 @@ int vo_map_read(vo_map *m, float *xyz, float *app, int capacity, int *n_out);
 /* the arrays in device memory (entries [0, *d_size)); they move when the map grows */
 int vo_map_dev_ptrs(vo_map *m, const float **d_xyz, const float **d_app, const int **d_size);
 
+/* ---- reading the map by appearance (an extension: the reference never reads its map back) --------------------------
+ * LOOKUP.  For every live query row (ten floats) the index of the entry map.update() would have found for it: the first
+ * entry whose appearance compares equal under operator== on ten floats (-0 equals +0; a row with a NaN equals nothing, so
+ * a NaN query finds nothing and a NaN entry is never found), or none.  A read-only probe of the table the updates keep
+ * (no atomics, nothing written to the map), then a count / scan / scatter by QUERY index: 3 launches, and a result that is
+ * a function of the data alone.  A lookup never grows or changes the map.
+ * d_app [n_max][10] (8-byte aligned), *d_n_rows (or NULL) <= n_max rows are live.  Outputs, all in device memory:
+ *   d_pairs_out       [n_max][2]  the hits compacted in query order as (query index, entry index) -- the solver's
+ *                                 (meas_idx, world_idx) orientation against the map's own arrays (vo_map_dev_ptrs)
+ *   *d_n_out                      their count
+ *   d_xyz_out         [n_max][3]  or NULL: the point of hit k, gathered in the same order
+ *   d_local_pairs_out [n_max][2]  or NULL: (query index, k) -- the same hits indexing d_xyz_out, so that a consumer works on
+ *                                 a per-frame point array
+ *   d_entry_out       [n_max]     or NULL: per query POSITION the entry, or -1 (also for the positions behind the live rows)
+ * Items behind the count are left as they were.
+ * Capturable (vo_ctx_begin_capture) once a call of the same shape (n_max, n_frames, with or without d_entry_out) has sized
+ * the map's lookup scratch; a capture that would have to grow it is refused (VO_ERR_NOT_READY) before anything is enqueued.
+ * Refused (VO_ERR_INVALID_ARG): a null map or required pointer, appearance rows / pair arrays not 8-byte aligned, a
+ * negative count, n_frames outside 1 .. 65535, more than 2^30 rows in one call. */
+int vo_map_lookup_dev(vo_map *m, const float *d_app, int n_max, const int *d_n_rows /* or NULL */, int32_t *d_pairs_out,
+                      int *d_n_out, float *d_xyz_out /* or NULL */, int32_t *d_local_pairs_out /* or NULL */,
+                      int32_t *d_entry_out /* or NULL */);
+/* n_frames frames against ONE map in the same 3 launches (the frame is a grid dimension): frame f's rows lie at
+ * d_app + 10 * f * app_stride floats (app_stride in ROWS, >= n_max), d_n_rows[f] (or, NULL, n_max) of them live; its
+ * outputs lie f * n_max items further (pairs, points, entries) and its count is d_n_out[f].  CONTRACT: frame f's outputs
+ * are BIT FOR BIT those of vo_map_lookup_dev on that frame alone. */
+int vo_map_lookup_batch_dev(vo_map *m, int n_frames, const float *d_app, size_t app_stride, int n_max,
+                            const int *d_n_rows /* [n_frames] or NULL */, int32_t *d_pairs_out, int *d_n_out /* [n_frames] */,
+                            float *d_xyz_out /* or NULL */, int32_t *d_local_pairs_out /* or NULL */,
+                            int32_t *d_entry_out /* or NULL */);
+/* host arrays in, host arrays out (any of xyz_out, entry_out may be NULL; pairs_out has room for n pairs); waits */
+int vo_map_lookup(vo_map *m, const float *app, int n, int32_t *pairs_out, int *n_out, float *xyz_out /* or NULL */,
+                  int32_t *entry_out /* or NULL */);
+
+/* LOCALISATION.  The pose of a camera in the map from one frame alone: T (column-major 4x4, p_cam = T * p_map, the
+ * convention of vo_picp_set_pose).  d_uv [n_max][2] pixels and d_app [n_max][10] appearances of the frame, *d_n_rows (or
+ * NULL) <= n_max of them live.  Steps, all enqueued on the context's stream, no host round trip:
+ *   1. vo_map_lookup_dev with gathered points: world = d_xyz_out [n_max][3], pairs = d_local_pairs_out (query index, k).
+ *   2. params->n_hypotheses > 0: vo_estimate_pose_ransac_dev on them (n_world = n_meas = n_max) -- global, no prior needed.
+ *      params->n_hypotheses == 0: no RANSAC; d_T0 is REQUIRED, every hit is handed on and the start is T0 (tracking
+ *      against the map with a prior).  threshold_px and seed are then not read.
+ *   3. n_iters >= 1 PICP rounds (kernel_threshold, keep_outliers = 0) from the winner's pose on its inliers, or from T0 on
+ *      every hit, on a solver the map handle owns (created by the first call, which must lie outside a capture).
+ *   4. one finishing launch decides the status on the device and writes d_T16_out and *d_stats.
+ * Status (vo_map_localise_stats.status), in this order of precedence:
+ *   FEW_MATCHES   fewer than 6 hits
+ *   NO_CONSENSUS  the RANSAC fell back (its codes 1-3; BAD_INDEX cannot occur, the pairs come from the lookup)
+ *   NOT_FINITE    the solved pose holds a NaN or an infinity
+ *   FEW_INLIERS   the solver's final inlier count is below min_inliers
+ *   OK            otherwise: d_T16_out is the solved pose.
+ * When the status is not OK, d_T16_out is T0 BIT FOR BIT when d_T0 was given and the identity otherwise; the statistics
+ * are still those of the steps that ran.  The call returns VO_OK either way: a lost frame is a status, not an error.
+ * CONTRACT.  The call is a composition plus the finishing launch; it adds no arithmetic of its own.  d_T16_out (status
+ * OK) and the statistics equal BIT FOR BIT what the caller gets from the explicit sequence of public calls on the lookup's
+ * outputs: vo_map_lookup_dev -> vo_estimate_pose_ransac_dev -> vo_picp_set_camera / vo_picp_set_kernel_threshold /
+ * vo_picp_set_points_dev(d_xyz_out, n_max, d_uv, n_max) / vo_picp_set_pose_dev(winner or T0) / vo_picp_solve_dev(pairs
+ * handed on, n_max, their device count, 0, n_iters) -> vo_picp_get_pose_dev and vo_picp_get_stats.
+ * Capturable once a call of the same shape (n_max, n_hypotheses, camera, threshold) has run outside a capture.
+ * Refused (VO_ERR_INVALID_ARG): the lookup's refusals, n_max < 1, n_iters < 1, min_inliers < 0, a singular K, d_T0
+ * missing with n_hypotheses == 0, n_hypotheses < 0 or > 65536, with n_hypotheses > 0 a threshold that is not positive and
+ * finite, d_uv / d_stats not 8-byte aligned. */
+#define VO_MAP_LOCALISE_OK           0
+#define VO_MAP_LOCALISE_FEW_MATCHES  1
+#define VO_MAP_LOCALISE_NO_CONSENSUS 2
+#define VO_MAP_LOCALISE_FEW_INLIERS  3
+#define VO_MAP_LOCALISE_NOT_FINITE   4
+typedef struct vo_map_localise_stats {
+  int32_t status;           /* VO_MAP_LOCALISE_* */
+  int32_t n_rows;           /* live rows of the frame */
+  int32_t n_hits;           /* rows found in the map */
+  int32_t ransac_status;    /* VO_POSE_RANSAC_* (0 when n_hypotheses == 0) */
+  int32_t ransac_inliers;   /* pairs handed to the solver: the winner's inliers, every hit on a fallback or without RANSAC */
+  int32_t num_inliers;      /* the solver's inlier count after the last round */
+  float   chi_inliers, chi_outliers;   /* its two chi^2 sums */
+} vo_map_localise_stats;
+int vo_map_localise_dev(vo_map *m, int rows, int cols, int z_near, int z_far, const float K[9], const float *d_uv,
+                        const float *d_app, int n_max, const int *d_n_rows /* or NULL */, const vo_ransac_params *params,
+                        float kernel_threshold, int n_iters, int min_inliers, const float *d_T0 /* 16 floats, or NULL */,
+                        float *d_T16_out, vo_map_localise_stats *d_stats);
+/* n_frames frames against one map in one call: vo_map_lookup_batch_dev (world stride = n_max, so that the public batched
+ * calls compose unchanged) -> vo_estimate_pose_ransac_batch_dev -> vo_picp_solve_batch_dev (n_meas = uv_stride there) ->
+ * the finishing launch with the frame as grid dimension.  Frame f reads d_uv + 2 * f * uv_stride floats and d_app + 10 * f *
+ * app_stride floats (strides in pixels / rows, both >= n_max), d_n_rows[f] (or n_max) rows, d_T0 + 16 f; it writes
+ * d_T16_out + 16 f and d_stats[f].  CONTRACT: bit for bit the explicit batched composition of those public calls.  Against
+ * vo_map_localise_dev on the frame alone: hits, RANSAC status, winner and inlier set are bit for bit equal; the solved pose
+ * agrees within the 1e-4 stated between the single and the batched solver (their summation orders differ), so the status
+ * agrees on every frame whose solver inlier count is not within 1 of min_inliers.  A lost frame leaves its neighbours'
+ * outputs alone.  Refusals: those of the single form and of the calls it is composed of. */
+int vo_map_localise_batch_dev(vo_map *m, int n_frames, int rows, int cols, int z_near, int z_far, const float K[9],
+                              const float *d_uv, size_t uv_stride, const float *d_app, size_t app_stride, int n_max,
+                              const int *d_n_rows /* [n_frames] or NULL */, const vo_ransac_params *params,
+                              float kernel_threshold, int n_iters, int min_inliers, const float *d_T0 /* [n_frames][16] or NULL */,
+                              float *d_T16_out /* [n_frames][16] */, vo_map_localise_stats *d_stats /* [n_frames] */);
+/* host arrays: uv [n][2], app [n][10], T0 (16 floats, or NULL); two or three uploads, the device call, one read-back of
+ * pose and statistics.  Same results bit for bit; returns VO_OK with the status in *stats_out (required). */
+int vo_map_localise(vo_map *m, int rows, int cols, int z_near, int z_far, const float K[9], const float *uv,
+                    const float *app, int n, const vo_ransac_params *params, float kernel_threshold, int n_iters,
+                    int min_inliers, const float T0[16] /* or NULL */, float T_out[16], vo_map_localise_stats *stats_out);
+
 #ifdef __cplusplus
 }
 #endif

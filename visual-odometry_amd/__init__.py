@@ -13,6 +13,8 @@ from .api import (  # noqa: F401
     Event,
     KdTree,
     Map,
+    MapLocaliseStats,
+    MAP_LOCALISE_STATUS,
     PICPSolver,
     VoError,
     compute_correspondences_images,

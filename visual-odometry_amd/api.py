@@ -386,6 +386,116 @@ class Map:
         _chk(self.lib.vo_map_read(self.h, _ptr(p), _ptr(a), C.c_int(n), C.byref(m)))
         return p[:n].copy(), a[:n].copy()
 
+    # ---- reading the map by appearance (vo_map_lookup*, vo_map_localise*) ----
+    def lookup(self, appearances, want_points=False):
+        """vo_map_lookup: which entry would update() have found for every row?  Returns (pairs (k, 2) = (query index,
+        entry index) in query order, entries (n,) = the entry per query or -1) and, with want_points, the hits' points (k, 3)."""
+        a = _f32(appearances, (-1, 10))
+        n = len(a)
+        pairs = np.zeros((max(n, 1), 2), np.int32)
+        ent = np.full(max(n, 1), -1, np.int32)
+        xyz = np.zeros((max(n, 1), 3), np.float32)
+        k = C.c_int()
+        _chk(self.lib.vo_map_lookup(self.h, _ptr(a), C.c_int(n), _ptr(pairs), C.byref(k), _ptr(xyz) if want_points else None, _ptr(ent)))
+        out = (pairs[: k.value].copy(), ent[:n].copy())
+        return out + (xyz[: k.value].copy(),) if want_points else out
+
+    def lookup_dev(self, d_app, n_max, d_n, d_pairs, d_n_out, d_xyz=None, d_local_pairs=None, d_entries=None):
+        """vo_map_lookup_dev on device pointers (ints; d_n and the last three may be None): enqueues and returns"""
+        v = lambda d: C.c_void_p(d) if d else None
+        _chk(self.lib.vo_map_lookup_dev(self.h, v(d_app), C.c_int(n_max), v(d_n), v(d_pairs), v(d_n_out), v(d_xyz), v(d_local_pairs),
+                                        v(d_entries)))
+
+    def lookup_batch_dev(self, n_frames, d_app, app_stride, n_max, d_n, d_pairs, d_n_out, d_xyz=None, d_local_pairs=None,
+                         d_entries=None):
+        """vo_map_lookup_batch_dev: n_frames frames against this map in one call (app_stride in rows)"""
+        v = lambda d: C.c_void_p(d) if d else None
+        _chk(self.lib.vo_map_lookup_batch_dev(self.h, C.c_int(n_frames), v(d_app), C.c_size_t(app_stride), C.c_int(n_max), v(d_n),
+                                              v(d_pairs), v(d_n_out), v(d_xyz), v(d_local_pairs), v(d_entries)))
+
+    @staticmethod
+    def _ransac(threshold_px, n_hypotheses, seed):
+        return RansacParams(int(n_hypotheses), float(threshold_px), int(seed) & 0xFFFFFFFFFFFFFFFF)
+
+    def localise(self, camera: Camera, pixels, appearances, threshold_px=2.0, n_hypotheses=64, seed=0, kernel_threshold=10000.0,
+                 n_iters=50, min_inliers=6, T0=None):
+        """vo_map_localise: the camera's pose in the map (4x4, p_cam = T p_map) from one frame's pixels (n, 2) and appearances
+        (n, 10): lookup -> P3P RANSAC (n_hypotheses == 0: none, T0 is the start) -> n_iters PICP rounds.  Returns (T, stats
+        dict); T is T0 (or the identity) unless stats["status"] == 0 (MAP_LOCALISE_STATUS names the others)."""
+        uv = _f32(pixels, (-1, 2))
+        a = _f32(appearances, (-1, 10))
+        assert len(uv) == len(a)
+        T = np.zeros(16, np.float32)
+        st = MapLocaliseStats()
+        prm = self._ransac(threshold_px, n_hypotheses, seed)
+        _chk(self.lib.vo_map_localise(self.h, C.c_int(camera._rows), C.c_int(camera._cols), C.c_int(camera._z_near), C.c_int(camera._z_far),
+                                      _ptr(_colmajor(camera._K, 3)), _ptr(uv), _ptr(a), C.c_int(len(uv)), C.byref(prm),
+                                      C.c_float(kernel_threshold), C.c_int(n_iters), C.c_int(min_inliers),
+                                      _ptr(_colmajor(T0, 4)) if T0 is not None else None, _ptr(T), C.byref(st)))
+        return T.reshape(4, 4).T.copy(), st.as_dict()
+
+    def localise_dev(self, camera: Camera, d_uv, d_app, n_max, d_n, params: "RansacParams", kernel_threshold, n_iters, min_inliers,
+                     d_T0, d_T16_out, d_stats):
+        """vo_map_localise_dev on device pointers (ints; d_n and d_T0 may be None): enqueues and returns.  d_T16_out: 16
+        floats, d_stats: 32 bytes (MapLocaliseStats)."""
+        v = lambda d: C.c_void_p(d) if d else None
+        _chk(self.lib.vo_map_localise_dev(self.h, C.c_int(camera._rows), C.c_int(camera._cols), C.c_int(camera._z_near),
+                                          C.c_int(camera._z_far), _ptr(_colmajor(camera._K, 3)), v(d_uv), v(d_app), C.c_int(n_max), v(d_n),
+                                          C.byref(params), C.c_float(kernel_threshold), C.c_int(n_iters), C.c_int(min_inliers), v(d_T0),
+                                          v(d_T16_out), v(d_stats)))
+
+    def localise_batch_dev(self, camera: Camera, n_frames, d_uv, uv_stride, d_app, app_stride, n_max, d_n, params: "RansacParams",
+                           kernel_threshold, n_iters, min_inliers, d_T0, d_T16_out, d_stats):
+        """vo_map_localise_batch_dev on device pointers (strides in pixels / rows)"""
+        v = lambda d: C.c_void_p(d) if d else None
+        _chk(self.lib.vo_map_localise_batch_dev(self.h, C.c_int(n_frames), C.c_int(camera._rows), C.c_int(camera._cols),
+                                                C.c_int(camera._z_near), C.c_int(camera._z_far), _ptr(_colmajor(camera._K, 3)), v(d_uv),
+                                                C.c_size_t(uv_stride), v(d_app), C.c_size_t(app_stride), C.c_int(n_max), v(d_n),
+                                                C.byref(params), C.c_float(kernel_threshold), C.c_int(n_iters), C.c_int(min_inliers),
+                                                v(d_T0), v(d_T16_out), v(d_stats)))
+
+    def localise_batch(self, camera: Camera, frames, threshold_px=2.0, n_hypotheses=64, seed=0, kernel_threshold=10000.0, n_iters=50,
+                       min_inliers=6, T0=None):
+        """vo_map_localise_batch_dev for a list of host frames (pixels (n, 2), appearances (n, 10)) of any sizes: padded to a
+        common n_max, uploaded, localised in ONE call.  T0: one 4x4 per frame, or None.  Returns a list of (T, stats dict)."""
+        F = len(frames)
+        if F == 0:
+            return []
+        ctx = self.ctx
+        n = np.array([len(_f32(a, (-1, 10))) for _, a in frames], np.int32)
+        cap = max(int(n.max()), 1)
+        uv = np.zeros((F, cap, 2), np.float32)
+        app = np.zeros((F, cap, 10), np.float32)
+        for f, (p, a) in enumerate(frames):
+            uv[f, : n[f]] = _f32(p, (-1, 2))
+            app[f, : n[f]] = _f32(a, (-1, 10))
+        t0 = None if T0 is None else np.stack([_colmajor(T, 4) for T in T0]).astype(np.float32)
+        ins = [ctx.to_device(uv), ctx.to_device(app), ctx.to_device(n)] + ([ctx.to_device(t0)] if t0 is not None else [])
+        outs = [ctx.alloc(F * 64), ctx.alloc(F * 32)]
+        try:
+            self.localise_batch_dev(camera, F, ins[0], cap, ins[1], cap, cap, ins[2], self._ransac(threshold_px, n_hypotheses, seed),
+                                    kernel_threshold, n_iters, min_inliers, ins[3] if t0 is not None else None, outs[0], outs[1])
+            T = np.zeros((F, 16), np.float32); ctx.d2h(T, outs[0])
+            st = (MapLocaliseStats * F)()
+            raw = np.zeros(F * 32, np.uint8); ctx.d2h(raw, outs[1])
+            C.memmove(st, raw.ctypes.data, F * 32)
+        finally:
+            for d in ins + outs:
+                ctx.free(d)
+        return [(T[f].reshape(4, 4).T.copy(), st[f].as_dict()) for f in range(F)]
+
+
+class MapLocaliseStats(C.Structure):
+    """vo_map_localise_stats (include/vo_hip.h)"""
+    _fields_ = [("status", C.c_int32), ("n_rows", C.c_int32), ("n_hits", C.c_int32), ("ransac_status", C.c_int32),
+                ("ransac_inliers", C.c_int32), ("num_inliers", C.c_int32), ("chi_inliers", C.c_float), ("chi_outliers", C.c_float)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+MAP_LOCALISE_STATUS = ("OK", "FEW_MATCHES", "NO_CONSENSUS", "FEW_INLIERS", "NOT_FINITE")     # VO_MAP_LOCALISE_*
+
 
 def triangulate_points(k, X, correspondences, p1_img, p2_img, app2=None, want_pairs=True,
                        ctx: Context | None = None):

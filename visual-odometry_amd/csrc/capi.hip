@@ -2123,6 +2123,9 @@ struct vo_map {
   float* hist = nullptr;        // [0,16) the history isometry, [16,32) staging of a host isometry (vo_map_update)
   long long size_ub = 0;        // upper bound of the size known without asking the device
   DevBuf up_xyz, up_app;        // staging of vo_map_update
+  DevBuf look_ws;               // vo_map_lookup*: per-workgroup counts, entries per query position
+  DevBuf loc_ws;                // vo_map_localise*: what passes from stage to stage (hits, gathered points, winner, pairs handed on)
+  vo_picp* solver = nullptr;    // vo_map_localise[_dev]: made by the first call
 };
 
 constexpr int MAP_MAX_ENTRIES = 1 << 29;      // 2.5 x that many table slots still fit 32 bits
@@ -2211,7 +2214,8 @@ int vo_map_destroy(vo_map* m) {
   map_free_arrays(m->d);
   if (m->d.hdr) (void)hipFree(m->d.hdr);
   if (m->hist) (void)hipFree(m->hist);
-  m->scratch.release(); m->up_xyz.release(); m->up_app.release();
+  m->scratch.release(); m->up_xyz.release(); m->up_app.release(); m->look_ws.release(); m->loc_ws.release();
+  if (m->solver) (void)vo_picp_destroy(m->solver);
   delete m;
   return VO_OK;
 }
@@ -2332,6 +2336,232 @@ int vo_map_dev_ptrs(vo_map* m, const float** d_xyz, const float** d_app, const i
   if (d_xyz) *d_xyz = m->d.pts;
   if (d_app) *d_app = m->d.app;
   if (d_size) *d_size = m->d.hdr;
+  return VO_OK;
+}
+
+// ---- reading the map by appearance: the lookup (map.hip) and the localisation composed of it, the P3P RANSAC and the PICP
+// solvers.  The localisation calls go through the PUBLIC entry points of the stages, in the order the header's contract names.
+static int map_lookup_check(const vo_map* m, int n_frames, const float* d_app, size_t app_stride, int n_max, const int32_t* d_pairs,
+                            const int* d_n_out, const int32_t* d_local) {
+  const char* fn = "vo_map_lookup";
+  if (n_frames < 1 || n_frames > 65535) return fail(VO_ERR_INVALID_ARG, "%s: n_frames %d outside 1 .. 65535 (the frame is a grid dimension)", fn, n_frames);
+  if (n_max < 0) return fail(VO_ERR_INVALID_ARG, "%s: negative row count", fn);
+  if (!d_n_out || (n_max > 0 && !(d_app && d_pairs))) return fail(VO_ERR_INVALID_ARG, "%s: null argument", fn);
+  if (!aligned8(d_app, d_pairs, d_local)) return fail(VO_ERR_INVALID_ARG, "%s: device appearance rows and pair arrays must be 8-byte aligned", fn);
+  if (n_frames > 1 && app_stride < (size_t)n_max) return fail(VO_ERR_INVALID_ARG, "%s: app_stride %zu is smaller than n_max %d", fn, app_stride, n_max);
+  if (app_stride >= 0x7fffffff / 10 || (long long)n_max * n_frames > (1ll << 30))
+    return fail(VO_ERR_INVALID_ARG, "%s: more than 2^30 rows in one call", fn);
+  (void)m;
+  return VO_OK;
+}
+
+static int map_lookup(vo_map* m, int n_frames, const float* d_app, size_t app_stride, int n_max, const int* d_n, int32_t* d_pairs,
+                      int* d_n_out, float* d_xyz, int32_t* d_local, int32_t* d_entries) {
+  VO_MAP_LIVE(m);
+  if (int r = map_lookup_check(m, n_frames, d_app, app_stride, n_max, d_pairs, d_n_out, d_local)) return r;
+  vo_ctx* c = m->ctx;
+  const size_t need = sizeof(int) * map_lookup_scratch_ints(n_max, n_frames, d_entries == nullptr);
+  if (c->capturing && m->look_ws.cap < need)
+    return fail(VO_ERR_NOT_READY, "vo_map_lookup: the scratch would have to grow inside a graph capture (make one call with %d frame(s) "
+                                  "of n_max %d before capturing)", n_frames, n_max);
+  if (int r = set_device(c)) return r;
+  VO_HIP_CHECK(m->look_ws.ensure(need, c->stream));
+  VO_HIP_CHECK(launch_map_lookup(c->stream, m->d, d_app, app_stride, n_max, d_n, n_frames, d_pairs, d_n_out, d_xyz, d_local, d_entries,
+                                 m->look_ws.as<int>()));
+  return VO_OK;
+}
+
+int vo_map_lookup_dev(vo_map* m, const float* d_app, int n_max, const int* d_n, int32_t* d_pairs, int* d_n_out, float* d_xyz,
+                      int32_t* d_local, int32_t* d_entries) {
+  return map_lookup(m, 1, d_app, (size_t)(n_max > 0 ? n_max : 0), n_max, d_n, d_pairs, d_n_out, d_xyz, d_local, d_entries);
+}
+
+int vo_map_lookup_batch_dev(vo_map* m, int n_frames, const float* d_app, size_t app_stride, int n_max, const int* d_n, int32_t* d_pairs,
+                            int* d_n_out, float* d_xyz, int32_t* d_local, int32_t* d_entries) {
+  return map_lookup(m, n_frames, d_app, app_stride, n_max, d_n, d_pairs, d_n_out, d_xyz, d_local, d_entries);
+}
+
+int vo_map_lookup(vo_map* m, const float* app, int n, int32_t* pairs_out, int* n_out, float* xyz_out, int32_t* entry_out) {
+  VO_MAP_LIVE(m);
+  vo_ctx* c = m->ctx;
+  VO_NOT_CAPTURING(c);
+  VO_REQUIRE(n >= 0 && n_out && (n == 0 || (app && pairs_out)), "bad arguments");
+  *n_out = 0;
+  if (n == 0) return VO_OK;
+  if (int r = set_device(c)) return r;
+  if (int r = upload(c, c->in[0], app, sizeof(float) * 10 * (size_t)n)) return r;
+  VO_HIP_CHECK(c->out[0].ensure(sizeof(int32_t) * 2 * (size_t)n, c->stream));
+  VO_HIP_CHECK(c->out[1].ensure(sizeof(float) * 3 * (size_t)n, c->stream));
+  VO_HIP_CHECK(c->out[2].ensure(sizeof(int32_t) * (size_t)n + 128, c->stream));
+  if (int r = ensure_counts(c)) return r;
+  if (int r = vo_map_lookup_dev(m, c->in[0].as<float>(), n, nullptr, c->out[0].as<int32_t>(), c->counts.as<int>(),
+                                xyz_out ? c->out[1].as<float>() : nullptr, nullptr, entry_out ? c->out[2].as<int32_t>() : nullptr))
+    return r;
+  int k = 0;
+  VO_HIP_CHECK(hipMemcpyAsync(&k, c->counts.p, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+  VO_HIP_CHECK(hipStreamSynchronize(c->stream));
+  if (k < 0 || k > n) return fail(VO_ERR_HIP, "vo_map_lookup: unexpected count %d", k);
+  if (k > 0) VO_HIP_CHECK(hipMemcpyAsync(pairs_out, c->out[0].p, sizeof(int32_t) * 2 * (size_t)k, hipMemcpyDeviceToHost, c->stream));
+  if (k > 0 && xyz_out) VO_HIP_CHECK(hipMemcpyAsync(xyz_out, c->out[1].p, sizeof(float) * 3 * (size_t)k, hipMemcpyDeviceToHost, c->stream));
+  if (entry_out) VO_HIP_CHECK(hipMemcpyAsync(entry_out, c->out[2].p, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost, c->stream));
+  VO_HIP_CHECK(hipStreamSynchronize(c->stream));
+  *n_out = k;
+  return VO_OK;
+}
+
+static_assert(sizeof(vo_map_localise_stats) == 32, "the finishing kernel writes eight 4-byte words per frame");
+
+// what passes from stage to stage, per frame, in the map's workspace (256-byte aligned blocks)
+struct LocaliseWs {
+  int32_t *pairs, *local, *handed;   // [F][n_max][2]: (query, entry), (query, k), the pairs handed to the solver
+  float* xyz;                        // [F][n_max][3] gathered points
+  int *n_hits, *n_handed, *rstat;    // [F]
+  float *T_start, *T_solved, *stats4;   // [F][16], [F][16], [F][4]
+  size_t bytes;
+};
+static LocaliseWs localise_layout(void* base, int n_frames, int n_max) {
+  LocaliseWs w{};
+  size_t off = 0;
+  auto take = [&](size_t bytes) { char* p = static_cast<char*>(base) + off; off += (bytes + 255) & ~(size_t)255; return p; };
+  const size_t F = (size_t)n_frames, N = (size_t)n_max;
+  w.pairs = reinterpret_cast<int32_t*>(take(8 * F * N));
+  w.local = reinterpret_cast<int32_t*>(take(8 * F * N));
+  w.handed = reinterpret_cast<int32_t*>(take(8 * F * N));
+  w.xyz = reinterpret_cast<float*>(take(12 * F * N));
+  w.n_hits = reinterpret_cast<int*>(take(4 * F));
+  w.n_handed = reinterpret_cast<int*>(take(4 * F));
+  w.rstat = reinterpret_cast<int*>(take(4 * F));
+  w.T_start = reinterpret_cast<float*>(take(64 * F));
+  w.T_solved = reinterpret_cast<float*>(take(64 * F));
+  w.stats4 = reinterpret_cast<float*>(take(16 * F));
+  w.bytes = off;
+  return w;
+}
+
+static int localise_check(const char* fn, const vo_map* m, const float* K, const float* d_uv, const float* d_app, int n_max,
+                          const vo_ransac_params* params, int n_iters, int min_inliers, const float* d_T0, const float* d_T16,
+                          const vo_map_localise_stats* d_stats) {
+  (void)m;
+  if (!(K && d_uv && d_app && params && d_T16 && d_stats)) return fail(VO_ERR_INVALID_ARG, "%s: null argument", fn);
+  if (n_max < 1) return fail(VO_ERR_INVALID_ARG, "%s: n_max must be positive", fn);
+  if (n_iters < 1) return fail(VO_ERR_INVALID_ARG, "%s: n_iters must be positive", fn);
+  if (min_inliers < 0) return fail(VO_ERR_INVALID_ARG, "%s: negative min_inliers", fn);
+  if (!aligned8(d_uv, d_app, d_stats)) return fail(VO_ERR_INVALID_ARG, "%s: device arrays must be 8-byte aligned", fn);
+  if (params->n_hypotheses == 0) {
+    if (!d_T0) return fail(VO_ERR_INVALID_ARG, "%s: n_hypotheses == 0 (no RANSAC) needs the prior d_T0", fn);
+  } else if (int r = ransac_check_params(params)) {
+    return r;
+  }
+  double Kinv[9];
+  if (!invert_k(K, Kinv)) return fail(VO_ERR_INVALID_ARG, "%s: K is singular", fn);
+  return VO_OK;
+}
+
+int vo_map_localise_dev(vo_map* m, int rows, int cols, int z_near, int z_far, const float K[9], const float* d_uv, const float* d_app,
+                        int n_max, const int* d_n, const vo_ransac_params* params, float thr, int n_iters, int min_inliers,
+                        const float* d_T0, float* d_T16, vo_map_localise_stats* d_stats) {
+  VO_MAP_LIVE(m);
+  if (int r = localise_check("vo_map_localise_dev", m, K, d_uv, d_app, n_max, params, n_iters, min_inliers, d_T0, d_T16, d_stats)) return r;
+  vo_ctx* c = m->ctx;
+  const size_t need = localise_layout(nullptr, 1, n_max).bytes;
+  if (c->capturing && (m->loc_ws.cap < need || !m->solver))
+    return fail(VO_ERR_NOT_READY, "vo_map_localise_dev: the workspace would have to grow inside a graph capture (make one call with n_max "
+                                  "%d before capturing)", n_max);
+  if (int r = set_device(c)) return r;
+  if (!m->solver) { if (int r = vo_picp_create(c, &m->solver)) return r; }
+  VO_HIP_CHECK(m->loc_ws.ensure(need, c->stream));
+  const LocaliseWs w = localise_layout(m->loc_ws.p, 1, n_max);
+  // 1. the lookup, with the hits' points gathered
+  if (int r = vo_map_lookup_dev(m, d_app, n_max, d_n, w.pairs, w.n_hits, w.xyz, w.local, nullptr)) return r;
+  // 2. the start pose and the pairs handed on
+  const bool ransac = params->n_hypotheses > 0;
+  if (ransac) {
+    if (int r = vo_estimate_pose_ransac_dev(c, rows, cols, z_near, z_far, K, w.xyz, n_max, d_uv, n_max, w.local, n_max, w.n_hits, params,
+                                            w.T_start, w.handed, w.n_handed, nullptr, nullptr, w.rstat))
+      return r;
+  }
+  // 3. the rounds (vo_picp_set_camera / _set_kernel_threshold without the pose upload: the pose comes from device memory)
+  vo_picp* s = m->solver;
+  {
+    const CamK cam = make_cam(rows, cols, z_near, z_far, K);
+    if (memcmp(&cam, &s->hp.cam, sizeof(cam)) != 0) { s->hp.cam = cam; s->params_dirty = true; }
+    if (memcmp(&thr, &s->hp.thr, sizeof(thr)) != 0) { s->hp.thr = thr; s->params_dirty = true; }
+  }
+  if (int r = vo_picp_set_points_dev(s, w.xyz, n_max, d_uv, n_max)) return r;
+  if (int r = vo_picp_set_pose_dev(s, ransac ? w.T_start : d_T0)) return r;
+  if (int r = vo_picp_solve_dev(s, ransac ? w.handed : w.local, n_max, ransac ? w.n_handed : w.n_hits, 0, n_iters)) return r;
+  // 4. status, pose, statistics
+  MapLocaliseFinish f{};
+  f.n_frames = 1; f.n_max = n_max; f.d_n = d_n; f.n_hits = w.n_hits; f.ransac_status = ransac ? w.rstat : nullptr;
+  f.n_handed = ransac ? w.n_handed : w.n_hits; f.state = s->d_state; f.T0 = d_T0; f.min_inliers = min_inliers;
+  f.T_out = d_T16; f.stats = reinterpret_cast<int*>(d_stats);
+  VO_HIP_CHECK(launch_map_localise_finish(c->stream, f));
+  return VO_OK;
+}
+
+int vo_map_localise_batch_dev(vo_map* m, int n_frames, int rows, int cols, int z_near, int z_far, const float K[9], const float* d_uv,
+                              size_t uv_stride, const float* d_app, size_t app_stride, int n_max, const int* d_n,
+                              const vo_ransac_params* params, float thr, int n_iters, int min_inliers, const float* d_T0, float* d_T16,
+                              vo_map_localise_stats* d_stats) {
+  VO_MAP_LIVE(m);
+  if (int r = localise_check("vo_map_localise_batch_dev", m, K, d_uv, d_app, n_max, params, n_iters, min_inliers, d_T0, d_T16, d_stats)) return r;
+  VO_REQUIRE(n_frames >= 1 && n_frames <= 65535, "n_frames outside 1 .. 65535 (the frame is a grid dimension)");
+  VO_REQUIRE(uv_stride >= (size_t)n_max && app_stride >= (size_t)n_max, "a stride is smaller than n_max");
+  VO_REQUIRE(uv_stride < 0x7fffffff, "stride too large");
+  vo_ctx* c = m->ctx;
+  const size_t need = localise_layout(nullptr, n_frames, n_max).bytes;
+  if (c->capturing && m->loc_ws.cap < need)
+    return fail(VO_ERR_NOT_READY, "vo_map_localise_batch_dev: the workspace would have to grow inside a graph capture (make one call with "
+                                  "%d frames of n_max %d before capturing)", n_frames, n_max);
+  if (int r = set_device(c)) return r;
+  VO_HIP_CHECK(m->loc_ws.ensure(need, c->stream));
+  const LocaliseWs w = localise_layout(m->loc_ws.p, n_frames, n_max);
+  if (int r = vo_map_lookup_batch_dev(m, n_frames, d_app, app_stride, n_max, d_n, w.pairs, w.n_hits, w.xyz, w.local, nullptr)) return r;
+  const bool ransac = params->n_hypotheses > 0;
+  if (ransac) {
+    if (int r = vo_estimate_pose_ransac_batch_dev(c, n_frames, rows, cols, z_near, z_far, K, w.xyz, (size_t)n_max, n_max, d_uv, uv_stride,
+                                                  n_max, w.local, (size_t)n_max, w.n_hits, params, w.T_start, w.handed, w.n_handed,
+                                                  nullptr, nullptr, w.rstat))
+      return r;
+  }
+  if (int r = vo_picp_solve_batch_dev(c, n_frames, rows, cols, z_near, z_far, K, thr, 0, w.xyz, (size_t)n_max, d_uv, uv_stride,
+                                      ransac ? w.handed : w.local, (size_t)n_max, ransac ? w.n_handed : w.n_hits,
+                                      ransac ? w.T_start : d_T0, n_iters, w.T_solved, w.stats4))
+    return r;
+  MapLocaliseFinish f{};
+  f.n_frames = n_frames; f.n_max = n_max; f.d_n = d_n; f.n_hits = w.n_hits; f.ransac_status = ransac ? w.rstat : nullptr;
+  f.n_handed = ransac ? w.n_handed : w.n_hits; f.state = nullptr; f.T_solved = w.T_solved; f.stats4 = w.stats4; f.T0 = d_T0;
+  f.min_inliers = min_inliers; f.T_out = d_T16; f.stats = reinterpret_cast<int*>(d_stats);
+  VO_HIP_CHECK(launch_map_localise_finish(c->stream, f));
+  return VO_OK;
+}
+
+int vo_map_localise(vo_map* m, int rows, int cols, int z_near, int z_far, const float K[9], const float* uv, const float* app, int n,
+                    const vo_ransac_params* params, float thr, int n_iters, int min_inliers, const float T0[16], float T_out[16],
+                    vo_map_localise_stats* stats_out) {
+  VO_MAP_LIVE(m);
+  vo_ctx* c = m->ctx;
+  VO_NOT_CAPTURING(c);
+  VO_REQUIRE(K && uv && app && params && T_out && stats_out, "null argument");
+  VO_REQUIRE(n >= 1, "n must be positive");
+  if (int r = set_device(c)) return r;
+  if (int r = upload(c, c->in[0], uv, sizeof(float) * 2 * (size_t)n)) return r;
+  if (int r = upload(c, c->in[1], app, sizeof(float) * 10 * (size_t)n)) return r;
+  if (T0)
+    if (int r = upload(c, c->in[2], T0, sizeof(float) * 16)) return r;
+  VO_HIP_CHECK(c->out[2].ensure(128, c->stream));
+  VO_HIP_CHECK(hipStreamSynchronize(c->stream));          // the host arrays may go away after the call
+  struct { float T[16]; vo_map_localise_stats s; } h;
+  static_assert(sizeof(h) == 96, "pose and statistics come back in one copy");
+  char* d_res = c->out[2].as<char>();
+  if (int r = vo_map_localise_dev(m, rows, cols, z_near, z_far, K, c->in[0].as<float>(), c->in[1].as<float>(), n, nullptr, params, thr,
+                                  n_iters, min_inliers, T0 ? c->in[2].as<float>() : nullptr, reinterpret_cast<float*>(d_res),
+                                  reinterpret_cast<vo_map_localise_stats*>(d_res + 64)))
+    return r;
+  VO_HIP_CHECK(hipMemcpyAsync(&h, d_res, sizeof(h), hipMemcpyDeviceToHost, c->stream));
+  VO_HIP_CHECK(hipStreamSynchronize(c->stream));
+  memcpy(T_out, h.T, sizeof(h.T));
+  *stats_out = h.s;
   return VO_OK;
 }
 

@@ -268,7 +268,162 @@ __global__ __launch_bounds__(256) void map_transform_kernel(MapArgs a, Pose T) {
   }
 }
 
+// ---- the read-only side: which entry would update() have found for this row? ---------------------------------------------
+// map_lookup_probe_kernel walks the table exactly as map_probe_kernel does (same hash, same home slot, same linear step) but
+// only reads: it stops at the first free word, skips words of another tag or of another row, and takes the entry of the first
+// word whose row compares equal -- the class's entry, since a class owns one slot.  No atomics, no store to the table or the
+// entries.  Then count / scan / scatter compact the hits by QUERY index: the result is a function of the data alone.
+__device__ __forceinline__ int lookup_rows(const MapLookupArgs& a, int f) {
+  int n = a.n_max;
+  if (a.d_n) { const int m = a.d_n[f]; n = m < n ? (m < 0 ? 0 : m) : n; }
+  return n;
+}
+
+__global__ __launch_bounds__(MB) void map_lookup_probe_kernel(MapLookupArgs a) {
+  __shared__ int s_wave[MB / 64];
+  const FrameBlock fb = frame_block(a.nb, a.n_frames);
+  if (!fb.live) return;                                     // (the whole workgroup)
+  const int n = lookup_rows(a, fb.f);
+  int M = a.hdr[0];
+  M = M < a.cap ? M : a.cap;
+  const int i = fb.b * MB + threadIdx.x;
+  int found = -1;
+  if (i < n) {
+    const Row r = map_load_row(a.q_app + (size_t)fb.f * a.q_stride, (size_t)i);
+    if (!map_row_has_nan(r)) {
+      const unsigned h = map_hash(r);
+      unsigned s = (h * 0x9e3779b1u) & a.tmask;             // the home slot of map_probe_kernel
+      for (unsigned probes = 0; probes <= a.tmask; ++probes, s = (s + 1) & a.tmask) {
+        const unsigned long long w = a.table[s];
+        if (w == MAP_EMPTY) break;                          // the class was never entered
+        if ((unsigned)(w >> 32) != h) continue;             // another class lives here
+        const unsigned e = (unsigned)w;
+        if (e >= (unsigned)M) continue;                     // (never, between updates: a slot names an entry)
+        if (!map_rows_equal(r, map_load_row(a.app, (size_t)e))) continue;   // same tag, another row
+        found = (int)e;
+        break;
+      }
+    }
+  }
+  if (i < a.n_max) a.ent[(size_t)fb.f * a.n_max + i] = found;
+  const unsigned long long m = __ballot(found >= 0);
+  if ((threadIdx.x & 63) == 0) s_wave[threadIdx.x >> 6] = __popcll(m);
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    int tot = 0;
+#pragma unroll
+    for (int w = 0; w < MB / 64; ++w) tot += s_wave[w];
+    a.counts[(size_t)fb.f * a.counts_stride + fb.b] = tot;
+  }
+}
+
+__global__ __launch_bounds__(MB) void map_lookup_scatter_kernel(MapLookupArgs a) {
+  __shared__ int s_wave[MB / 64];
+  const FrameBlock fb = frame_block(a.nb, a.n_frames);
+  if (!fb.live) return;
+  const int i = fb.b * MB + threadIdx.x;
+  const int e = i < a.n_max ? a.ent[(size_t)fb.f * a.n_max + i] : -1;      // (-1 beyond the live rows)
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const unsigned long long m = __ballot(e >= 0);
+  if (lane == 0) s_wave[wave] = __popcll(m);
+  __syncthreads();
+  if (e < 0) return;
+  int off = a.counts[(size_t)fb.f * a.counts_stride + fb.b];
+#pragma unroll
+  for (int w = 0; w < MB / 64; ++w) if (w < wave) off += s_wave[w];
+  const size_t k = (size_t)(off + __popcll(m & ((1ull << lane) - 1ull)));      // < n_max: one hit per live row at most
+  const size_t o = (size_t)fb.f * a.n_max + k;
+  if (a.pairs) reinterpret_cast<int2*>(a.pairs)[o] = make_int2(i, e);
+  if (a.local_pairs) reinterpret_cast<int2*>(a.local_pairs)[o] = make_int2(i, (int)k);
+  if (a.xyz) {
+    const float* p = a.pts + 3 * (size_t)e;
+    float* q = a.xyz + 3 * o;
+    q[0] = p[0]; q[1] = p[1]; q[2] = p[2];
+  }
+}
+
+// one thread per frame: the status of vo_map_localise*_dev, the pose handed out and the statistics (8 words per frame:
+// status, live rows, hits, RANSAC status, pairs handed to the solver, the solver's inliers, chi^2 of inliers / outliers)
+__global__ __launch_bounds__(64) void map_localise_finish_kernel(MapLocaliseFinish a) {
+  const int f = blockIdx.x * 64 + threadIdx.x;
+  if (f >= a.n_frames) return;
+  int rows = a.n_max;
+  if (a.d_n) { const int m = a.d_n[f]; rows = m < rows ? (m < 0 ? 0 : m) : rows; }
+  const int hits = a.n_hits[f];
+  const int rstat = a.ransac_status ? a.ransac_status[f] : 0;
+  const int handed = a.n_handed[f];
+  float T[16];
+  int n_in;
+  float chi_in, chi_out;
+  if (a.state) {                                            // the single solver: its pose as vo_picp_get_pose_dev writes it
+    const float* p = a.state->pose[0];
+#pragma unroll
+    for (int k = 0; k < 16; ++k) {
+      const int r = k & 3, c = k >> 2;
+      T[k] = r == 3 ? (c == 3 ? 1.f : 0.f) : (c == 3 ? p[9 + r] : p[r + 3 * c]);
+    }
+    n_in = a.state->n_in; chi_in = a.state->chi_in; chi_out = a.state->chi_out;
+  } else {
+#pragma unroll
+    for (int k = 0; k < 16; ++k) T[k] = a.T_solved[16 * (size_t)f + k];
+    chi_in = a.stats4[4 * (size_t)f]; chi_out = a.stats4[4 * (size_t)f + 1]; n_in = (int)a.stats4[4 * (size_t)f + 2];
+  }
+  bool finite = true;
+#pragma unroll
+  for (int k = 0; k < 16; ++k) finite &= fabsf(T[k]) <= 3.402823466e38f;      // false for NaN and +-inf
+  int status = 0;
+  if (hits < 6) status = 1;
+  else if (rstat != 0) status = 2;
+  else if (!finite) status = 4;
+  else if (n_in < a.min_inliers) status = 3;
+  float* out = a.T_out + 16 * (size_t)f;
+  if (status == 0) {
+#pragma unroll
+    for (int k = 0; k < 16; ++k) out[k] = T[k];
+  } else if (a.T0) {
+    const unsigned* src = reinterpret_cast<const unsigned*>(a.T0) + 16 * (size_t)f;      // T0's bits, whatever they are
+    unsigned* dst = reinterpret_cast<unsigned*>(out);
+#pragma unroll
+    for (int k = 0; k < 16; ++k) dst[k] = src[k];
+  } else {
+#pragma unroll
+    for (int k = 0; k < 16; ++k) out[k] = (k % 5 == 0) ? 1.f : 0.f;
+  }
+  int* s = a.stats + 8 * (size_t)f;
+  s[0] = status; s[1] = rows; s[2] = hits; s[3] = rstat; s[4] = handed; s[5] = n_in;
+  s[6] = __float_as_int(chi_in); s[7] = __float_as_int(chi_out);
+}
+
 size_t map_scratch_ints(int n_max) { return 2 * (size_t)n_max + (size_t)((n_max + MB - 1) / MB) + 8; }
+
+static size_t lookup_counts_stride(int n_max) { const size_t nb = (size_t)((n_max + MB - 1) / MB); return ((nb ? nb : 1) + 3) & ~(size_t)3; }
+size_t map_lookup_scratch_ints(int n_max, int n_frames, bool with_entries) {
+  return (size_t)n_frames * (lookup_counts_stride(n_max) + (with_entries ? (size_t)n_max : 0)) + 8;
+}
+
+hipError_t launch_map_lookup(hipStream_t st, const MapDev& m, const float* d_app, size_t app_stride_rows, int n_max, const int* d_n,
+                             int n_frames, int32_t* d_pairs, int* d_n_out, float* d_xyz, int32_t* d_local_pairs, int32_t* d_entries,
+                             int* d_scratch) {
+  if (n_max <= 0) return hipMemsetAsync(d_n_out, 0, sizeof(int) * (size_t)n_frames, st);
+  MapLookupArgs a;
+  a.app = m.app; a.pts = m.pts; a.table = m.table; a.hdr = m.hdr; a.tmask = m.tcap - 1u; a.cap = m.cap;
+  a.q_app = d_app; a.q_stride = 10 * app_stride_rows; a.n_max = n_max; a.d_n = d_n; a.n_frames = n_frames;
+  a.nb = (n_max + MB - 1) / MB;
+  a.counts_stride = lookup_counts_stride(n_max);
+  a.counts = d_scratch;
+  a.ent = d_entries ? d_entries : d_scratch + (size_t)n_frames * a.counts_stride;
+  a.pairs = d_pairs; a.local_pairs = d_local_pairs; a.xyz = d_xyz;
+  hipLaunchKernelGGL(map_lookup_probe_kernel, frame_grid(a.nb, n_frames), dim3(MB), 0, st, a);
+  hipError_t e = launch_scan(st, a.counts, a.nb, d_n_out, nullptr, n_frames, a.counts_stride);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(map_lookup_scatter_kernel, frame_grid(a.nb, n_frames), dim3(MB), 0, st, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_map_localise_finish(hipStream_t st, const MapLocaliseFinish& a) {
+  hipLaunchKernelGGL(map_localise_finish_kernel, dim3((a.n_frames + 63) / 64), dim3(64), 0, st, a);
+  return hipGetLastError();
+}
 
 static MapArgs map_args(const MapDev& m, const float* c_xyz, const float* c_app, int n_max, const int* d_n, const float* T16,
                         int* scratch) {

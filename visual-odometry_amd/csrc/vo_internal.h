@@ -340,6 +340,39 @@ hipError_t launch_map_update(hipStream_t st, const MapDev& m, const float* d_xyz
 hipError_t launch_map_rehash(hipStream_t st, const MapDev& m, int size_bound);      // empties the table, enters entries 0 .. size-1
 hipError_t launch_map_history(hipStream_t st, float* d_hist16, const float* d_X16, int reset);
 hipError_t launch_map_transform(hipStream_t st, const MapDev& m, const Pose& T, int size_bound);
+// The read-only lookup (vo_map_lookup*): frame f's rows at q_app + f * q_stride floats, d_n[f] (or n_max) of them live.
+struct MapLookupArgs {
+  const float* app; const float* pts;   // the map's entries
+  const unsigned long long* table; const int* hdr; unsigned tmask; int cap;
+  const float* q_app; size_t q_stride;  // floats between frames
+  int n_max; const int* d_n; int n_frames;
+  int nb;                               // workgroups of 256 rows per frame
+  int* counts; size_t counts_stride;    // per-workgroup hit counts -> offsets
+  int* ent;                             // [n_frames][n_max] entry of every query position, -1: none
+  int32_t* pairs;                       // [n_frames][n_max][2] (query index, entry), or null
+  int32_t* local_pairs;                 // [n_frames][n_max][2] (query index, k), or null
+  float* xyz;                           // [n_frames][n_max][3] point of hit k, or null
+};
+// d_scratch: map_lookup_scratch_ints(n_max, n_frames, d_entries == null) ints.  3 launches whatever n_frames is.
+size_t map_lookup_scratch_ints(int n_max, int n_frames, bool with_entries);
+hipError_t launch_map_lookup(hipStream_t st, const MapDev& m, const float* d_app, size_t app_stride_rows, int n_max, const int* d_n,
+                             int n_frames, int32_t* d_pairs, int* d_n_out, float* d_xyz, int32_t* d_local_pairs, int32_t* d_entries,
+                             int* d_scratch);
+// The last launch of vo_map_localise*_dev: status, pose handed out and statistics of every frame.
+struct MapLocaliseFinish {
+  int n_frames, n_max; const int* d_n;
+  const int* n_hits;                    // [n_frames]
+  const int* ransac_status;             // [n_frames], or null (no RANSAC ran)
+  const int* n_handed;                  // [n_frames] pairs handed to the solver
+  const PicpState* state;               // the single solver's state, or null: the batched solver's outputs below
+  const float* T_solved;                // [n_frames][16]
+  const float* stats4;                  // [n_frames][4] of vo_picp_solve_batch_dev
+  const float* T0;                      // [n_frames][16], or null
+  int min_inliers;
+  float* T_out;                         // [n_frames][16]
+  int* stats;                           // [n_frames][8]: vo_map_localise_stats
+};
+hipError_t launch_map_localise_finish(hipStream_t st, const MapLocaliseFinish& a);
 
 // ---- epipolar initialisation, device half (epi.hip) ------------------------------------------------------
 size_t epi_workspace_bytes();
