@@ -1704,16 +1704,21 @@ int vo_estimate_transform_dev(vo_ctx* c, const float K[9], const int32_t* d_pair
   return VO_OK;
 }
 
+// the host forms refuse a pair outside its point arrays before anything is uploaded: first index against n_a, second against n_b
+static int check_pair_range(const char* fn, const int32_t* pairs, int n, int n_a, int n_b) {
+  for (int i = 0; i < n; ++i)
+    if (pairs[2 * i] < 0 || pairs[2 * i] >= n_a || pairs[2 * i + 1] < 0 || pairs[2 * i + 1] >= n_b)
+      return fail(VO_ERR_BAD_INDEX, "%s: pair %d = (%d,%d) outside the point arrays", fn, i, pairs[2 * i], pairs[2 * i + 1]);
+  return VO_OK;
+}
+
 int vo_estimate_transform(vo_ctx* c, const float K[9], const int32_t* pairs, int n, const float* p1, int n1,
                           const float* p2, int n2, float X_out[16]) {
   VO_REQUIRE(c && K && pairs && p1 && p2 && X_out, "null argument");
   VO_NOT_CAPTURING(c);
   VO_REQUIRE(n >= 8, "fewer than 8 correspondences");
   VO_REQUIRE(n1 > 0 && n2 > 0, "empty point set");
-  for (int i = 0; i < n; ++i)
-    if (pairs[2 * i] < 0 || pairs[2 * i] >= n1 || pairs[2 * i + 1] < 0 || pairs[2 * i + 1] >= n2)
-      return fail(VO_ERR_BAD_INDEX, "vo_estimate_transform: pair %d = (%d,%d) outside the point arrays", i,
-                  pairs[2 * i], pairs[2 * i + 1]);
+  if (int r = check_pair_range("vo_estimate_transform", pairs, n, n1, n2)) return r;
   if (int r = set_device(c)) return r;
   if (int r = upload(c, c->in[0], pairs, sizeof(int32_t) * 2 * (size_t)n)) return r;
   if (int r = upload(c, c->in[1], p1, sizeof(float) * 2 * (size_t)n1)) return r;
@@ -1773,10 +1778,7 @@ int vo_estimate_transform_ransac(vo_ctx* c, const float K[9], const int32_t* pai
   VO_REQUIRE(n >= 8, "fewer than 8 correspondences");
   VO_REQUIRE(n1 > 0 && n2 > 0, "empty point set");
   if (int r = ransac_check_params(params)) return r;
-  for (int i = 0; i < n; ++i)
-    if (pairs[2 * i] < 0 || pairs[2 * i] >= n1 || pairs[2 * i + 1] < 0 || pairs[2 * i + 1] >= n2)
-      return fail(VO_ERR_BAD_INDEX, "vo_estimate_transform_ransac: pair %d = (%d,%d) outside the point arrays", i,
-                  pairs[2 * i], pairs[2 * i + 1]);
+  if (int r = check_pair_range("vo_estimate_transform_ransac", pairs, n, n1, n2)) return r;
   if (int r = set_device(c)) return r;
   if (int r = upload(c, c->in[0], pairs, sizeof(int32_t) * 2 * (size_t)n)) return r;
   if (int r = upload(c, c->in[1], p1, sizeof(float) * 2 * (size_t)n1)) return r;
@@ -1825,6 +1827,19 @@ static int pose_ransac_camera(int rows, int cols, int z_near, int z_far, const f
   return VO_OK;
 }
 
+// the caller's side of a PoseRansacArgs that a layout function has carved: camera, inputs, parameters and outputs
+static void pose_ransac_fill(PoseRansacArgs& a, const CamK& cam, const double Kinv[9], const float* d_world, int n_world,
+                             const float* d_meas, int n_meas, const int32_t* d_pairs, const int* d_n, const vo_ransac_params* params,
+                             float* d_T16, int32_t* d_inl, int* d_n_inl, uint8_t* d_mask, int32_t* d_counts, int* d_status) {
+  a.cam = cam;
+  for (int i = 0; i < 9; ++i) a.Kinv[i] = Kinv[i];
+  a.pairs = d_pairs; a.d_n = d_n; a.world = d_world; a.n_world = n_world; a.meas = d_meas; a.n_meas = n_meas;
+  a.seed = params->seed; a.thr2 = params->threshold_px * params->threshold_px;
+  a.out_pairs = d_inl; a.n_out = d_n_inl; a.T_out = d_T16; a.status = d_status;
+  if (d_mask) a.mask = d_mask;
+  if (d_counts) a.counts = d_counts;
+}
+
 int vo_estimate_pose_ransac_dev(vo_ctx* c, int rows, int cols, int z_near, int z_far, const float K[9], const float* d_world,
                                 int n_world, const float* d_meas, int n_meas, const int32_t* d_pairs, int n_max, const int* d_n,
                                 const vo_ransac_params* params, float* d_T16, int32_t* d_inl, int* d_n_inl, uint8_t* d_mask,
@@ -1835,24 +1850,18 @@ int vo_estimate_pose_ransac_dev(vo_ctx* c, int rows, int cols, int z_near, int z
   VO_REQUIRE(aligned8(d_pairs, d_meas, d_inl), "device arrays must be 8-byte aligned");
   if (int r = ransac_check_params(params)) return r;
   const int H = params->n_hypotheses;
-  PoseRansacArgs a{};
+  CamK cam;
   double Kinv[9];
-  if (int r = pose_ransac_camera(rows, cols, z_near, z_far, K, a.cam, Kinv)) return r;
+  if (int r = pose_ransac_camera(rows, cols, z_near, z_far, K, cam, Kinv)) return r;
   const size_t need = pose_ransac_workspace_bytes(n_max, H);
   if (c->capturing && c->pose_ws.cap < need)
     return fail(VO_ERR_NOT_READY, "vo_estimate_pose_ransac_dev: the workspace would have to grow inside a graph capture (make one "
                                   "call with n_max %d and %d hypotheses before capturing)", n_max, H);
   if (int r = set_device(c)) return r;
   VO_HIP_CHECK(c->pose_ws.ensure(need, c->stream));
-  const CamK cam = a.cam;
-  a = pose_ransac_layout(c->pose_ws.p, n_max, H);
-  a.cam = cam;
-  for (int i = 0; i < 9; ++i) a.Kinv[i] = Kinv[i];
-  a.pairs = d_pairs; a.d_n = d_n; a.world = d_world; a.n_world = n_world; a.meas = d_meas; a.n_meas = n_meas;
-  a.seed = params->seed; a.thr2 = params->threshold_px * params->threshold_px;
-  a.out_pairs = d_inl; a.n_out = d_n_inl; a.T_out = d_T16; a.status = d_status;
-  if (d_mask) a.mask = d_mask;
-  if (d_counts) a.counts = d_counts;
+  PoseRansacArgs a = pose_ransac_layout(c->pose_ws.p, n_max, H);
+  pose_ransac_fill(a, cam, Kinv, d_world, n_world, d_meas, n_meas, d_pairs, d_n, params, d_T16, d_inl, d_n_inl, d_mask, d_counts,
+                   d_status);
   VO_HIP_CHECK(launch_pose_ransac(c->stream, a));
   return VO_OK;
 }
@@ -1866,10 +1875,7 @@ int vo_estimate_pose_ransac(vo_ctx* c, int rows, int cols, int z_near, int z_far
   VO_REQUIRE(pairs && world && meas, "null argument");
   VO_REQUIRE(n_world > 0 && n_meas > 0, "empty point set");
   if (int r = ransac_check_params(params)) return r;
-  for (int i = 0; i < n; ++i)
-    if (pairs[2 * i] < 0 || pairs[2 * i] >= n_meas || pairs[2 * i + 1] < 0 || pairs[2 * i + 1] >= n_world)
-      return fail(VO_ERR_BAD_INDEX, "vo_estimate_pose_ransac: pair %d = (%d,%d) outside the point arrays", i, pairs[2 * i],
-                  pairs[2 * i + 1]);
+  if (int r = check_pair_range("vo_estimate_pose_ransac", pairs, n, n_meas, n_world)) return r;
   if (int r = set_device(c)) return r;
   if (int r = upload(c, c->in[0], pairs, sizeof(int32_t) * 2 * (size_t)n)) return r;
   if (int r = upload(c, c->in[1], world, sizeof(float) * 3 * (size_t)n_world)) return r;
@@ -2017,14 +2023,8 @@ static int pose_ransac_batch(vo_ctx* c, int n_problems, int rows, int cols, int 
   if (int r = set_device(c)) return r;
   VO_HIP_CHECK(c->pose_batch_ws.ensure(need, c->stream));
   PoseRansacBatchArgs b = pose_ransac_batch_layout(c->pose_batch_ws.p, n_problems, n_max, H);
-  PoseRansacArgs& a = b.a;
-  a.cam = cam;
-  for (int i = 0; i < 9; ++i) a.Kinv[i] = Kinv[i];
-  a.pairs = d_pairs; a.d_n = d_n; a.world = d_world; a.n_world = n_world; a.meas = d_meas; a.n_meas = n_meas;
-  a.seed = params->seed; a.thr2 = params->threshold_px * params->threshold_px;
-  a.out_pairs = d_inl; a.n_out = d_n_inl; a.T_out = d_T16; a.status = d_status;
-  if (d_mask) a.mask = d_mask;
-  if (d_counts) a.counts = d_counts;
+  pose_ransac_fill(b.a, cam, Kinv, d_world, n_world, d_meas, n_meas, d_pairs, d_n, params, d_T16, d_inl, d_n_inl, d_mask, d_counts,
+                   d_status);
   b.world_stride = world_stride; b.meas_stride = meas_stride; b.pairs_stride = pairs_stride;
   VO_HIP_CHECK(launch_pose_ransac_batch(c->stream, b));
   return VO_OK;
@@ -2062,8 +2062,8 @@ int vo_frames_batch_track_dev(vo_ctx* c, const vo_frame_batch* b, const vo_frame
   if (int r = set_device(c)) return r;
   const int nt = b->n_ref > b->n_cur ? b->n_ref : b->n_cur;
   // what the caller did not ask for lives in the context: moved cloud | tracked pairs | winners (256-aligned blocks)
-  const size_t moved_bytes = b->model_moved ? 0 : (sizeof(float) * 3 * (size_t)b->n_model * (size_t)F + 255) & ~(size_t)255;
-  const size_t pairs_bytes = t->tracked_pairs ? 0 : (sizeof(int32_t) * 2 * (size_t)q * (size_t)F + 255) & ~(size_t)255;
+  const size_t moved_bytes = b->model_moved ? 0 : up256(sizeof(float) * 3 * (size_t)b->n_model * (size_t)F);
+  const size_t pairs_bytes = t->tracked_pairs ? 0 : up256(sizeof(int32_t) * 2 * (size_t)q * (size_t)F);
   const size_t win_bytes = t->T_winner ? 0 : sizeof(float) * 16 * (size_t)F;
   const size_t track_need = moved_bytes + pairs_bytes + win_bytes;
   if (c->capturing && c->track_ws.cap < track_need)
@@ -2421,20 +2421,19 @@ struct LocaliseWs {
 };
 static LocaliseWs localise_layout(void* base, int n_frames, int n_max) {
   LocaliseWs w{};
-  size_t off = 0;
-  auto take = [&](size_t bytes) { char* p = static_cast<char*>(base) + off; off += (bytes + 255) & ~(size_t)255; return p; };
+  WsCarver c(base);
   const size_t F = (size_t)n_frames, N = (size_t)n_max;
-  w.pairs = reinterpret_cast<int32_t*>(take(8 * F * N));
-  w.local = reinterpret_cast<int32_t*>(take(8 * F * N));
-  w.handed = reinterpret_cast<int32_t*>(take(8 * F * N));
-  w.xyz = reinterpret_cast<float*>(take(12 * F * N));
-  w.n_hits = reinterpret_cast<int*>(take(4 * F));
-  w.n_handed = reinterpret_cast<int*>(take(4 * F));
-  w.rstat = reinterpret_cast<int*>(take(4 * F));
-  w.T_start = reinterpret_cast<float*>(take(64 * F));
-  w.T_solved = reinterpret_cast<float*>(take(64 * F));
-  w.stats4 = reinterpret_cast<float*>(take(16 * F));
-  w.bytes = off;
+  w.pairs = c.take<int32_t>(8 * F * N);
+  w.local = c.take<int32_t>(8 * F * N);
+  w.handed = c.take<int32_t>(8 * F * N);
+  w.xyz = c.take<float>(12 * F * N);
+  w.n_hits = c.take<int>(4 * F);
+  w.n_handed = c.take<int>(4 * F);
+  w.rstat = c.take<int>(4 * F);
+  w.T_start = c.take<float>(64 * F);
+  w.T_solved = c.take<float>(64 * F);
+  w.stats4 = c.take<float>(16 * F);
+  w.bytes = c.bytes;
   return w;
 }
 

@@ -15,12 +15,6 @@ namespace vo {
 
 constexpr int EB = 256;
 
-__device__ __forceinline__ int epi_rows(const int* d_n, int n_max) {
-  int n = n_max;
-  if (d_n) { const int m = *d_n; n = m < n ? (m < 0 ? 0 : m) : n; }
-  return n;
-}
-
 // out[0..1] = max x, max y of p1, out[2..3] of p2, as float bits (zeroed by the host: "max = 0.f" of the reference;
 // a positive float orders like its bit pattern, values <= 0 and NaN never replace the running maximum -- as `v > max`)
 __global__ __launch_bounds__(EB) void epi_max_kernel(const float* __restrict__ p1, int n1, const float* __restrict__ p2, int n2,
@@ -64,7 +58,7 @@ struct EpiArgs {
 
 __global__ __launch_bounds__(EB) void epi_ata_kernel(EpiArgs a) {
   __shared__ double s_red[EB / 64][45];
-  const int n = epi_rows(a.d_n, a.n_max);
+  const int n = live_rows(a.d_n, a.n_max);
   // normalize(): x / (max_x / 2.f) - 1.f in float (epipolar_utils.cpp:58-59)
   const float hx1 = __uint_as_float(a.maxima[0]) / 2.f, hy1 = __uint_as_float(a.maxima[1]) / 2.f;
   const float hx2 = __uint_as_float(a.maxima[2]) / 2.f, hy2 = __uint_as_float(a.maxima[3]) / 2.f;
@@ -114,7 +108,7 @@ __global__ void epi_sum_kernel(EpiArgs a) {
     for (int b = 0; b < a.grid; ++b) v += a.partials[(size_t)b * 45 + k];
     a.ata[k] = v;
   }
-  if (k == 63) a.info[0] = epi_rows(a.d_n, a.n_max);
+  if (k == 63) a.info[0] = live_rows(a.d_n, a.n_max);
 }
 
 struct VoteArgs {
@@ -131,7 +125,7 @@ __global__ __launch_bounds__(EB) void epi_vote_kernel(VoteArgs a) {
   __shared__ int s_cnt[4];
   if (threadIdx.x < 4) { s_c[threadIdx.x] = tri_constants(a.K, a.X[threadIdx.x]); s_cnt[threadIdx.x] = 0; }      // utils.cpp:79-82
   __syncthreads();
-  const int n = epi_rows(a.d_n, a.n_max);
+  const int n = live_rows(a.d_n, a.n_max);
   int cnt[4] = {0, 0, 0, 0};
   for (int i = blockIdx.x * EB + threadIdx.x; i < n; i += gridDim.x * EB) {
     const int2 pr = reinterpret_cast<const int2*>(a.pairs)[i];

@@ -18,12 +18,6 @@ constexpr int RB = 256;
 constexpr int STEP_ROWS = 128;     // rows the step kernel stages in LDS at a time (24 KB)
 static_assert(sizeof(vo_epi_refine_stats) == 40, "the statistics are written as 6 ints and 2 doubles");
 
-__device__ __forceinline__ int refine_rows(const int* d_n, int n_max) {
-  int n = n_max;
-  if (d_n) { const int m = *d_n; n = m < n ? (m < 0 ? 0 : m) : n; }
-  return n;
-}
-
 __device__ __forceinline__ void cross3(const double a[3], const double b[3], double c[3]) {
   c[0] = a[1] * b[2] - a[2] * b[1];
   c[1] = a[2] * b[0] - a[0] * b[2];
@@ -111,7 +105,7 @@ __global__ __launch_bounds__(RB) void epi_refine_acc_kernel(RefineArgs a, int it
     for (int k = 0; k < 9; ++k) s_M[threadIdx.x][k] = M[k];
   }
   __syncthreads();
-  const int n = refine_rows(a.d_n, a.n_max);
+  const int n = live_rows(a.d_n, a.n_max);
   double acc[REFINE_ROW];
 #pragma unroll
   for (int k = 0; k < REFINE_ROW; ++k) acc[k] = 0.0;
@@ -257,7 +251,7 @@ __global__ __launch_bounds__(RB) void epi_refine_step_kernel(RefineArgs a, int i
   if (!dead) {
     // the rows in workgroup order: staged through LDS by the whole workgroup (coalesced, every load in flight at once), added
     // sequentially by one thread per column -- the order of the additions is that of the plain loop over the rows
-    const int n = refine_rows(a.d_n, a.n_max);
+    const int n = live_rows(a.d_n, a.n_max);
     int nb = (n + RB - 1) / RB;
     if (nb > a.grid) nb = a.grid;
     double v = 0.0;

@@ -35,23 +35,7 @@ size_t compaction_scratch_ints(int n) {
 // memory-level parallelism than the second visit costs bytes.  Built twice, measured slower at 1 to 16 rows per workgroup,
 // removed: DESIGN.md section 8.
 
-// exclusive rank of `flag` inside a 256-thread workgroup; total = survivors
-__device__ __forceinline__ int block_rank(bool flag, int* s_wave, int& total) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const unsigned long long m = __ballot(flag);
-  const int before = __popcll(m & ((1ull << lane) - 1ull));
-  if (lane == 0) s_wave[wave] = __popcll(m);
-  __syncthreads();
-  int off = 0, tot = 0;
-#pragma unroll
-  for (int w = 0; w < CB / 64; ++w) {
-    const int c = s_wave[w];
-    if (w < wave) off += c;
-    tot += c;
-  }
-  total = tot;
-  return off + before;
-}
+// (the exclusive rank inside a workgroup, block_rank<CB>: vo_math.h)
 
 // Small frames -- every frame of the reference's dataset holds 14..127 points -- are compacted by ONE workgroup per frame: it walks
 // the items 256 at a time with the running count in a register, so count, scan and scatter are one launch instead of three
@@ -144,7 +128,7 @@ __global__ __launch_bounds__(CB) void project_count_kernel(ProjArgs a) {
     }
   }
   int total;
-  block_rank(ok, s_wave, total);
+  block_rank<CB>(ok, s_wave, total);
   if (threadIdx.x == 0) a.counts[blockIdx.x] = total;
 }
 
@@ -155,7 +139,7 @@ __global__ __launch_bounds__(CB) void project_scatter_kernel(ProjArgs a) {
   float u = 0.f, v = 0.f;
   if (i < a.n) ok = proj_eval(a, i, u, v);
   int total;
-  const int r = block_rank(ok, s_wave, total);
+  const int r = block_rank<CB>(ok, s_wave, total);
   if (ok) {
     const size_t dst = (size_t)a.counts[blockIdx.x] + r;
     *reinterpret_cast<float2*>(a.out_uv + 2 * dst) = make_float2(u, v);
@@ -350,7 +334,7 @@ __global__ __launch_bounds__(CB) void tri_count_kernel(TriArgs a0) {
   const unsigned long long m = __ballot(ok);
   if ((threadIdx.x & 63) == 0 && k < a.n_max) a.tmp_ok[k >> 6] = m;
   int total;
-  block_rank(ok, s_wave, total);
+  block_rank<CB>(ok, s_wave, total);
   if (threadIdx.x == 0) a.counts[fb.b] = total;
 }
 
@@ -372,7 +356,7 @@ __global__ __launch_bounds__(CB) void tri_scatter_kernel(TriArgs a0) {
     }
   }
   int total;
-  const int r = block_rank(ok, s_wave, total);
+  const int r = block_rank<CB>(ok, s_wave, total);
   __shared__ int s_src[CB];
   if (ok) {
     const size_t dst = (size_t)a.counts[fb.b] + r;
@@ -409,7 +393,7 @@ __global__ __launch_bounds__(CB) void tri_small_kernel(TriArgs a0, int* d_n_out)
     float p[3] = {0.f, 0.f, 0.f};
     if (k < n) ok = tri_eval(a, s_c, k, i2, p);
     int total;
-    const int r = block_rank(ok, s_wave, total);
+    const int r = block_rank<CB>(ok, s_wave, total);
     if (ok) {
       const size_t dst = (size_t)first + r;
       a.out_xyz[3 * dst] = p[0]; a.out_xyz[3 * dst + 1] = p[1]; a.out_xyz[3 * dst + 2] = p[2];
@@ -563,7 +547,7 @@ __global__ __launch_bounds__(CB) void join_count_kernel(JoinArgs a0) {
     if ((threadIdx.x & 63) == 0) a.tmp_ok[i >> 6] = m;
   }
   int total;
-  block_rank(ok, s_wave, total);
+  block_rank<CB>(ok, s_wave, total);
   if (threadIdx.x == 0) a.counts[fb.b] = total;
 }
 
@@ -583,7 +567,7 @@ __device__ __forceinline__ void join_scatter_body(const JoinArgs& a0, const Batc
   Pose Xw;
   if (SINK) Xw = batch_pack_pose(*sink, fb.f);
   int total;
-  const int r = block_rank(ok, s_wave, total);
+  const int r = block_rank<CB>(ok, s_wave, total);
   if (ok) {
     const size_t dst = (size_t)a.counts[fb.b] + r;
     a.out[2 * dst] = c;        // vo_complete.cpp:59
@@ -627,7 +611,7 @@ __global__ __launch_bounds__(CB) void join_small_kernel(JoinArgs a0, int n_world
       }
     }
     int total;
-    const int r = block_rank(ok, s_wave, total);
+    const int r = block_rank<CB>(ok, s_wave, total);
     if (ok) reinterpret_cast<int2*>(a.out)[(size_t)first + r] = make_int2(c, w);      // vo_complete.cpp:59
     first += total;
     __syncthreads();
@@ -734,7 +718,7 @@ __global__ __launch_bounds__(CB) void match_count_kernel(MatchOutArgs a) {
   }
   const bool ok = q < nq && (unsigned)(best[q] & 0xffffffffull) != 0xffffffffu;
   int total;
-  block_rank(ok, s_wave, total);
+  block_rank<CB>(ok, s_wave, total);
   if (threadIdx.x == 0) a.counts[blockIdx.y * a.counts_stride + blockIdx.x] = total;
 }
 
@@ -750,7 +734,7 @@ __global__ __launch_bounds__(CB) void match_scatter_kernel(MatchOutArgs a) {
   if (q < nq) idx = (unsigned)(best[q] & 0xffffffffull);
   const bool ok = idx != 0xffffffffu;
   int total;
-  const int r = block_rank(ok, s_wave, total);
+  const int r = block_rank<CB>(ok, s_wave, total);
   if (ok) {
     const size_t dst = (size_t)a.counts[blockIdx.y * a.counts_stride + blockIdx.x] + r;
     out[2 * dst] = tree_is_1 ? (int)idx : q;
@@ -771,7 +755,7 @@ __global__ __launch_bounds__(CB) void match_compact_small_kernel(MatchOutArgs a,
     if (q < nq) idx = (unsigned)(best[q] & 0xffffffffull);
     const bool ok = idx != 0xffffffffu;
     int total;
-    const int r = block_rank(ok, s_wave, total);
+    const int r = block_rank<CB>(ok, s_wave, total);
     if (ok) {
       const size_t dst = (size_t)first + r;
       out[2 * dst] = tree_is_1 ? (int)idx : q;

@@ -79,14 +79,9 @@ __device__ __forceinline__ unsigned map_hash(const Row& r) {
   x ^= x >> 15; x *= 0x2c1b3c6du; x ^= x >> 12; x *= 0x297a2d39u; x ^= x >> 15;
   return x;
 }
-__device__ __forceinline__ int map_rows(const MapArgs& a) {
-  int n = a.n_max;
-  if (a.d_n) { const int m = *a.d_n; n = m < n ? (m < 0 ? 0 : m) : n; }
-  return n;
-}
 
 __global__ __launch_bounds__(MB) void map_probe_kernel(MapArgs a) {
-  const int n = map_rows(a);
+  const int n = live_rows(a.d_n, a.n_max);
   const int M = a.hdr[0];
   const int i = blockIdx.x * MB + threadIdx.x;
   if (i >= n) return;
@@ -118,7 +113,7 @@ __global__ __launch_bounds__(MB) void map_probe_kernel(MapArgs a) {
 
 __global__ __launch_bounds__(MB) void map_flag_kernel(MapArgs a) {
   __shared__ int s_wave[MB / 64];
-  const int n = map_rows(a);
+  const int n = live_rows(a.d_n, a.n_max);
   const int M = a.hdr[0];
   const int i = blockIdx.x * MB + threadIdx.x;
   bool first = false;
@@ -166,7 +161,7 @@ __global__ __launch_bounds__(1024) void map_scan_kernel(MapArgs a) {
     int dropped = 0;
     if (M + add > a.cap) { dropped = M + add - a.cap; add = a.cap - M; }      // (the host grows the arrays before this can happen)
     a.hdr[1] = M;
-    a.hdr[2] = map_rows(a);
+    a.hdr[2] = live_rows(a.d_n, a.n_max);
     a.hdr[3] += dropped;
     a.hdr[0] = M + add;
   }
@@ -273,17 +268,11 @@ __global__ __launch_bounds__(256) void map_transform_kernel(MapArgs a, Pose T) {
 // only reads: it stops at the first free word, skips words of another tag or of another row, and takes the entry of the first
 // word whose row compares equal -- the class's entry, since a class owns one slot.  No atomics, no store to the table or the
 // entries.  Then count / scan / scatter compact the hits by QUERY index: the result is a function of the data alone.
-__device__ __forceinline__ int lookup_rows(const MapLookupArgs& a, int f) {
-  int n = a.n_max;
-  if (a.d_n) { const int m = a.d_n[f]; n = m < n ? (m < 0 ? 0 : m) : n; }
-  return n;
-}
-
 __global__ __launch_bounds__(MB) void map_lookup_probe_kernel(MapLookupArgs a) {
   __shared__ int s_wave[MB / 64];
   const FrameBlock fb = frame_block(a.nb, a.n_frames);
   if (!fb.live) return;                                     // (the whole workgroup)
-  const int n = lookup_rows(a, fb.f);
+  const int n = live_rows(a.d_n ? a.d_n + fb.f : nullptr, a.n_max);      // (a null d_n stays null: every frame holds n_max)
   int M = a.hdr[0];
   M = M < a.cap ? M : a.cap;
   const int i = fb.b * MB + threadIdx.x;

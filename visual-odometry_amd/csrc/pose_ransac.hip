@@ -5,15 +5,15 @@
 //                         vo_hip.h, first 4 distinct), Grunert's P3P on the first three (one quartic, closed form + two
 //                         Newton steps), every real solution with positive depths turned into R, t (triads of the two
 //                         congruent triangles), the one that reprojects the 4th sample closest kept, rounded to float;
-//   pose_score_kernel     the hot path, shaped as ransac_score_kernel: RANSAC_PTS pairs per thread in registers, a block
-//                         of 64 wave-uniform poses per workgroup, Camera::projectPoint's gates and the squared
-//                         reprojection error in float, one ballot + popcount per wave and hypothesis, an LDS sum over the
-//                         waves, one atomicAdd per (workgroup, hypothesis);
+//   pose_score_kernel     the hot path, ransac_common.h's scoring tile on PoseModel (below): POSE_PTS pairs per thread in
+//                         registers, a block of 64 wave-uniform poses per workgroup, Camera::projectPoint's gates and the
+//                         squared reprojection error in float;
 //   pose_select_kernel    one workgroup: the winner (ransac_common.h), the status code, and the pose handed on (the
 //                         winner's, or the identity on a fallback);
 //   pose_mask_kernel / pose_scatter_kernel
 //                         the pairs handed on (the winner's inliers, or every live pair on a fallback) as a mask and
-//                         compacted in their original order: count / scan (geom.hip's launch_scan) / scatter.
+//                         compacted in their original order: count / scan (geom.hip's launch_scan) / scatter; the mask
+//                         tail and the scatter are ransac_common.h's.
 // The batched form (vo_estimate_pose_ransac_batch_dev) runs the same bodies with the problem as a grid dimension, every
 // problem on its own info words, hypotheses, counts and per-workgroup counts: its results are the single form's bit for bit.
 // No host synchronisation anywhere: the call can be captured into a graph, and the solve that follows reads the pose and
@@ -28,7 +28,6 @@ namespace {
 
 constexpr int PB = 256;            // threads per workgroup (gather, scoring, mask)
 constexpr int POSE_PTS = 4;        // pairs per thread of the scoring pass
-constexpr int POSE_HB = 64;        // hypotheses per scoring workgroup: one per lane of the count register
 constexpr int POSE_FS = 16;        // floats per hypothesis: R column-major [0, 9), t [9, 12), [12] = 1 valid / 0 invalid
 
 struct D3 { double x, y, z; };
@@ -138,7 +137,7 @@ __device__ __forceinline__ Pose load_pose(const float* g) {
 // ---- the per-problem bodies: one problem's arrays in `a`, the workgroup's place in that problem's grid in bx / by.  The
 // single form calls them with its own block indices, the batched form (below) with the problem taken off the grid first.
 __device__ __forceinline__ void pose_gather_body(const PoseRansacArgs& a, unsigned bx, unsigned gx) {
-  const int n = ransac_rows(a.d_n, a.n_max);
+  const int n = live_rows(a.d_n, a.n_max);
   const float qnan = __int_as_float(0x7fc00000);
   int bad = 0;
   for (int i = bx * PB + threadIdx.x; i < n; i += gx * PB) {
@@ -161,7 +160,7 @@ __device__ __forceinline__ void pose_gather_body(const PoseRansacArgs& a, unsign
 
 __device__ __forceinline__ void pose_hyp_body(const PoseRansacArgs a, const int h) {
   if (h >= a.n_hyp) return;
-  const int n = ransac_rows(a.d_n, a.n_max);
+  const int n = live_rows(a.d_n, a.n_max);
   // the first 4 distinct draws, held in four registers (no array: the selects below replace the indexed stores)
   int i0 = 0, i1 = 0, i2 = 0, i3 = 0, k = 0;
   if (n >= 4)
@@ -255,40 +254,22 @@ __device__ __forceinline__ void pose_hyp_body(const PoseRansacArgs a, const int 
   dst[3] = make_float4(out[12], out[13], out[14], out[15]);
 }
 
-__device__ __forceinline__ void pose_score_body(const PoseRansacArgs a, unsigned bx, unsigned by) {
-  __shared__ int s_cnt[PB / 64][POSE_HB];
-  const int n = ransac_rows(a.d_n, a.n_max);
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  float4 p[POSE_PTS];
-  float pv[POSE_PTS];
-  bool live[POSE_PTS];
-#pragma unroll
-  for (int q = 0; q < POSE_PTS; ++q) {
-    const int i = (bx * POSE_PTS + q) * PB + threadIdx.x;
-    live[q] = i < n;
-    p[q] = live[q] ? a.pts[i] : make_float4(0.f, 0.f, 0.f, 0.f);
-    pv[q] = live[q] ? a.pv[i] : 0.f;
-  }
-  const int h0 = by * POSE_HB;
-  const int hn = a.n_hyp - h0 < POSE_HB ? a.n_hyp - h0 : POSE_HB;
-  int mine = 0;                                  // the count of hypothesis h0 + lane over this wave's pairs
-  for (int k = 0; k < hn; ++k) {
-    const float* g = a.poses + (size_t)(h0 + k) * POSE_FS;     // the same address in every lane
-    if (g[12] == 0.f) continue;
-    const Pose T = load_pose(g);
-    int cnt = 0;
-#pragma unroll
-    for (int q = 0; q < POSE_PTS; ++q) cnt += __popcll(__ballot(live[q] && pose_inlier(a.cam, T, p[q], pv[q], a.thr2)));
-    if (lane == k) mine = cnt;
-  }
-  s_cnt[wave][lane] = mine;
-  __syncthreads();
-  if (threadIdx.x < hn) {
-    int v = 0;
-#pragma unroll
-    for (int w = 0; w < PB / 64; ++w) v += s_cnt[w][threadIdx.x];
-    if (v) atomicAdd(&a.counts[h0 + threadIdx.x], v);
-  }
+// the P3P front end as a model of ransac_common.h: a pair is (world x, y, z, measured u) + measured v, a hypothesis a pose
+// behind its valid flag
+struct PoseModel {
+  static constexpr int NT = PB, PTS = POSE_PTS;
+  struct Pair { float4 p; float v; };
+  using Hyp = Pose;
+  const PoseRansacArgs& a;
+  __device__ __forceinline__ Pair load_pair(int i) const { return Pair{a.pts[i], a.pv[i]}; }
+  static __device__ __forceinline__ Pair zero_pair() { return Pair{make_float4(0.f, 0.f, 0.f, 0.f), 0.f}; }
+  __device__ __forceinline__ bool valid(int h) const { return !(a.poses[(size_t)h * POSE_FS + 12] == 0.f); }
+  __device__ __forceinline__ Hyp load(int h) const { return load_pose(a.poses + (size_t)h * POSE_FS); }
+  __device__ __forceinline__ bool inlier(const Hyp& T, const Pair& p) const { return pose_inlier(a.cam, T, p.p, p.v, a.thr2); }
+};
+
+__device__ __forceinline__ void pose_score_body(const PoseRansacArgs& a, unsigned bx, unsigned by) {
+  ransac_score_body(PoseModel{a}, bx, by, live_rows(a.d_n, a.n_max), a.n_hyp, a.counts);
 }
 
 __device__ __forceinline__ void pose_select_body(const PoseRansacArgs a) {
@@ -296,7 +277,7 @@ __device__ __forceinline__ void pose_select_body(const PoseRansacArgs a) {
   if (threadIdx.x == 0) {
     const int win = best ? (int)(0xFFFFFFFFull - (best & 0xFFFFFFFFull)) : -1;
     const int cnt = best ? (int)(best >> 32) : 0;
-    const int n = ransac_rows(a.d_n, a.n_max);
+    const int n = live_rows(a.d_n, a.n_max);
     const int st = a.info[1] > 0 ? VO_POSE_RANSAC_BAD_INDEX : n < 4 ? VO_POSE_RANSAC_FEW_PAIRS
                  : win < 0 ? VO_POSE_RANSAC_NO_HYPOTHESIS : cnt < 6 ? VO_POSE_RANSAC_FEW_INLIERS : VO_POSE_RANSAC_OK;
     a.info[2] = win; a.info[3] = cnt; a.info[4] = st;
@@ -314,8 +295,7 @@ __device__ __forceinline__ void pose_select_body(const PoseRansacArgs a) {
 }
 
 __device__ __forceinline__ void pose_mask_body(const PoseRansacArgs& a, unsigned bx) {
-  __shared__ int s_wave[PB / 64];
-  const int n = ransac_rows(a.d_n, a.n_max);
+  const int n = live_rows(a.d_n, a.n_max);
   const int st = a.info[4], win = a.info[2];
   const int i = bx * PB + threadIdx.x;
   bool in = false;
@@ -323,19 +303,11 @@ __device__ __forceinline__ void pose_mask_body(const PoseRansacArgs& a, unsigned
     if (st != VO_POSE_RANSAC_OK) in = true;                      // fallback: every live pair, as the plain frame
     else in = pose_inlier(a.cam, load_pose(a.poses + (size_t)win * POSE_FS), a.pts[i], a.pv[i], a.thr2);
   }
-  if (i < a.n_max) a.mask[i] = in ? 1 : 0;
-  int total;
-  ransac_rank<PB>(in, s_wave, total);
-  if (threadIdx.x == 0) a.blk[bx] = total;
+  ransac_mask_tail<PB>(in, bx, a.n_max, a.mask, a.blk);
 }
 
 __device__ __forceinline__ void pose_scatter_body(const PoseRansacArgs& a, unsigned bx) {
-  __shared__ int s_wave[PB / 64];
-  const int i = bx * PB + threadIdx.x;
-  const bool in = i < a.n_max && a.mask[i];
-  int total;
-  const int r = ransac_rank<PB>(in, s_wave, total);
-  if (in) reinterpret_cast<int2*>(a.out_pairs)[a.blk[bx] + r] = reinterpret_cast<const int2*>(a.pairs)[i];
+  ransac_scatter_body<PB>(bx, a.n_max, a.mask, a.blk, a.pairs, a.out_pairs);
 }
 
 // problem p of a batched call: problem 0's arrays moved on by p strides (elements, as vo_picp_solve_batch_dev counts them)
@@ -396,7 +368,7 @@ __global__ __launch_bounds__(64) void pose_hyp_batch_kernel(PoseRansacBatchArgs 
 
 __global__ __launch_bounds__(PB) void pose_score_batch_kernel(PoseRansacBatchArgs b) {
   const PoseRansacArgs a = pose_problem(b, blockIdx.z);
-  if ((int)blockIdx.x * (PB * POSE_PTS) >= ransac_rows(a.d_n, a.n_max)) return;
+  if ((int)blockIdx.x * (PB * POSE_PTS) >= live_rows(a.d_n, a.n_max)) return;
   pose_score_body(a, blockIdx.x, blockIdx.y);
 }
 
@@ -404,43 +376,40 @@ __global__ __launch_bounds__(1024) void pose_select_batch_kernel(PoseRansacBatch
 
 __global__ __launch_bounds__(PB) void pose_mask_batch_kernel(PoseRansacBatchArgs b) {
   const PoseRansacArgs a = pose_problem(b, blockIdx.y);
-  if ((int)blockIdx.x * PB >= ransac_rows(a.d_n, a.n_max)) return;
+  if ((int)blockIdx.x * PB >= live_rows(a.d_n, a.n_max)) return;
   pose_mask_body(a, blockIdx.x);
 }
 
 __global__ __launch_bounds__(PB) void pose_scatter_batch_kernel(PoseRansacBatchArgs b) {
   const PoseRansacArgs a = pose_problem(b, blockIdx.y);
-  if ((int)blockIdx.x * PB >= ransac_rows(a.d_n, a.n_max)) return;
+  if ((int)blockIdx.x * PB >= live_rows(a.d_n, a.n_max)) return;
   pose_scatter_body(a, blockIdx.x);
 }
 
-// ws layout (bytes): [0,256) info (ints [0, 8)), default pair count (int [8]), default pose (floats [16, 32)), then
-// pts [n_max] float4 | pv [n_max] | poses [n_hyp][16] | counts [n_hyp] | mask [n_max] | per-workgroup counts |
-// default compacted pairs [n_max][2]
-static size_t up256(size_t b) { return (b + 255) & ~(size_t)255; }
 static int pose_nb(int n_max) { return (n_max + PB - 1) / PB; }
 
-size_t pose_ransac_workspace_bytes(int n_max, int n_hyp) {
-  return 256 + up256(16 * (size_t)n_max) + up256(4 * (size_t)n_max) + up256(4 * POSE_FS * (size_t)n_hyp) + up256(4 * (size_t)n_hyp) +
-         up256((size_t)n_max) + up256(4 * (size_t)pose_nb(n_max)) + up256(8 * (size_t)n_max);
+// The workspace, block by block (each 256-aligned), in this order; ws may be null (the walk then only measures)
+PoseRansacArgs pose_ransac_layout(void* ws, int n_max, int n_hyp, size_t* bytes) {
+  PoseRansacArgs a{};
+  WsCarver w(ws);
+  a.info = w.take<int>(256);                                   // ints [0, 8) info, int [8] default pair count,
+  a.n_out = WsCarver::within<int>(a.info, 32);                 // floats [16, 32) default pose
+  a.T_out = WsCarver::within<float>(a.info, 64);
+  a.pts = w.take<float4>(16 * (size_t)n_max);
+  a.pv = w.take<float>(4 * (size_t)n_max);
+  a.poses = w.take<float>(4 * POSE_FS * (size_t)n_hyp);
+  a.counts = w.take<int>(4 * (size_t)n_hyp);
+  a.mask = w.take<uint8_t>((size_t)n_max);
+  a.blk = w.take<int>(4 * (size_t)pose_nb(n_max));             // per-workgroup counts
+  a.out_pairs = w.take<int32_t>(8 * (size_t)n_max);            // default compacted pairs
+  a.n_max = n_max; a.n_hyp = n_hyp;
+  if (bytes) *bytes = w.bytes;
+  return a;
 }
 
-PoseRansacArgs pose_ransac_layout(void* ws, int n_max, int n_hyp) {
-  PoseRansacArgs a{};
-  char* w = static_cast<char*>(ws);
-  a.info = reinterpret_cast<int*>(w);
-  a.n_out = a.info + 8;
-  a.T_out = reinterpret_cast<float*>(w) + 16;
-  size_t o = 256;
-  a.pts = reinterpret_cast<float4*>(w + o); o += up256(16 * (size_t)n_max);
-  a.pv = reinterpret_cast<float*>(w + o); o += up256(4 * (size_t)n_max);
-  a.poses = reinterpret_cast<float*>(w + o); o += up256(4 * POSE_FS * (size_t)n_hyp);
-  a.counts = reinterpret_cast<int*>(w + o); o += up256(4 * (size_t)n_hyp);
-  a.mask = reinterpret_cast<uint8_t*>(w + o); o += up256((size_t)n_max);
-  a.blk = reinterpret_cast<int*>(w + o); o += up256(4 * (size_t)pose_nb(n_max));
-  a.out_pairs = reinterpret_cast<int32_t*>(w + o);
-  a.n_max = n_max; a.n_hyp = n_hyp;
-  return a;
+size_t pose_ransac_workspace_bytes(int n_max, int n_hyp) {
+  size_t bytes;
+  return pose_ransac_layout(nullptr, n_max, n_hyp, &bytes), bytes;
 }
 
 hipError_t launch_pose_ransac(hipStream_t st, const PoseRansacArgs& a) {
@@ -451,7 +420,7 @@ hipError_t launch_pose_ransac(hipStream_t st, const PoseRansacArgs& a) {
   hipLaunchKernelGGL(pose_gather_kernel, dim3(nb < 1024 ? nb : 1024), dim3(PB), 0, st, a);
   hipLaunchKernelGGL(pose_hyp_kernel, dim3((a.n_hyp + 63) / 64), dim3(64), 0, st, a);
   const int nsb = (a.n_max + PB * POSE_PTS - 1) / (PB * POSE_PTS);
-  hipLaunchKernelGGL(pose_score_kernel, dim3(nsb, (a.n_hyp + POSE_HB - 1) / POSE_HB), dim3(PB), 0, st, a);
+  hipLaunchKernelGGL(pose_score_kernel, dim3(nsb, (a.n_hyp + RANSAC_HB - 1) / RANSAC_HB), dim3(PB), 0, st, a);
   hipLaunchKernelGGL(pose_select_kernel, dim3(1), dim3(1024), 0, st, a);
   hipLaunchKernelGGL(pose_mask_kernel, dim3(nb), dim3(PB), 0, st, a);
   e = launch_scan(st, a.blk, nb, a.n_out);
@@ -460,41 +429,40 @@ hipError_t launch_pose_ransac(hipStream_t st, const PoseRansacArgs& a) {
   return hipGetLastError();
 }
 
-// ws layout of the batched form (bytes, every block 256-aligned; P problems of capacity n, H hypotheses, nb = ceil(n / 256)):
-// info [P][8] ints | per-workgroup counts [P][nb] | counts [P][H]   -- zeroed by every call, as one block
-// pts [P][n] float4 | pv [P][n] | poses [P][H][16] | mask [P][n]
-// (the single form's blocks times P, without its default outputs: those go to the caller's arrays)
-size_t pose_ransac_batch_workspace_bytes(int n_problems, int n_max, int n_hyp) {
-  const size_t P = (size_t)n_problems, n = (size_t)n_max, H = (size_t)n_hyp;
-  return up256(32 * P) + up256(4 * P * (size_t)pose_nb(n_max)) + up256(4 * P * H) + up256(16 * P * n) + up256(4 * P * n) +
-         up256(4 * POSE_FS * P * H) + up256(P * n);
-}
-
-PoseRansacBatchArgs pose_ransac_batch_layout(void* ws, int n_problems, int n_max, int n_hyp) {
+// The batched form's workspace (P problems of capacity n_max, H hypotheses, nb = ceil(n_max / 256)): the single form's blocks
+// times P, without its default outputs (those go to the caller's arrays).  The first three blocks are zeroed by every call, as
+// one range.
+PoseRansacBatchArgs pose_ransac_batch_layout(void* ws, int n_problems, int n_max, int n_hyp, size_t* bytes) {
   PoseRansacBatchArgs b{};
   const size_t P = (size_t)n_problems, n = (size_t)n_max, H = (size_t)n_hyp;
-  char* w = static_cast<char*>(ws);
-  size_t o = 0;
-  b.a.info = reinterpret_cast<int*>(w + o); o += up256(32 * P);
-  b.a.blk = reinterpret_cast<int*>(w + o); o += up256(4 * P * (size_t)pose_nb(n_max));
-  b.a.counts = reinterpret_cast<int*>(w + o); o += up256(4 * P * H);
-  b.a.pts = reinterpret_cast<float4*>(w + o); o += up256(16 * P * n);
-  b.a.pv = reinterpret_cast<float*>(w + o); o += up256(4 * P * n);
-  b.a.poses = reinterpret_cast<float*>(w + o); o += up256(4 * POSE_FS * P * H);
-  b.a.mask = reinterpret_cast<uint8_t*>(w + o);
+  WsCarver w(ws);
+  b.a.info = w.take<int>(32 * P);                              // [P][8]
+  b.a.blk = w.take<int>(4 * P * (size_t)pose_nb(n_max));       // [P][nb]
+  b.a.counts = w.take<int>(4 * P * H);                         // [P][H]
+  b.a.pts = w.take<float4>(16 * P * n);
+  b.a.pv = w.take<float>(4 * P * n);
+  b.a.poses = w.take<float>(4 * POSE_FS * P * H);
+  b.a.mask = w.take<uint8_t>(P * n);
   b.a.n_max = n_max; b.a.n_hyp = n_hyp;
   b.nb = pose_nb(n_max); b.n_problems = n_problems;
+  if (bytes) *bytes = w.bytes;
   return b;
+}
+
+size_t pose_ransac_batch_workspace_bytes(int n_problems, int n_max, int n_hyp) {
+  size_t bytes;
+  return pose_ransac_batch_layout(nullptr, n_problems, n_max, n_hyp, &bytes), bytes;
 }
 
 // 3 memsets at the most and 7 launches, whatever the number of problems
 hipError_t launch_pose_ransac_batch(hipStream_t st, const PoseRansacBatchArgs& b) {
   const PoseRansacArgs& a = b.a;
   const size_t P = (size_t)b.n_problems, H = (size_t)a.n_hyp;
-  // info and the per-workgroup counts, and the hypothesis counts with them while they are the workspace's own
-  const char* zero_end = reinterpret_cast<const char*>(a.blk) + up256(4 * P * (size_t)b.nb);
-  const bool own_counts = reinterpret_cast<const char*>(a.counts) == zero_end;
-  if (own_counts) zero_end += 4 * P * H;
+  // info and the per-workgroup counts, and the hypothesis counts with them while they are the workspace's own: the layout
+  // walked again from its first block says where those lie
+  const char* own = reinterpret_cast<const char*>(pose_ransac_batch_layout(a.info, b.n_problems, a.n_max, a.n_hyp).a.counts);
+  const bool own_counts = reinterpret_cast<const char*>(a.counts) == own;
+  const char* zero_end = own + (own_counts ? 4 * P * H : 0);
   hipError_t e = hipMemsetAsync(a.info, 0, (size_t)(zero_end - reinterpret_cast<const char*>(a.info)), st);
   if (e == hipSuccess && !own_counts) e = hipMemsetAsync(a.counts, 0, 4 * P * H, st);
   if (e == hipSuccess) e = hipMemsetAsync(a.mask, 0, P * (size_t)a.n_max, st);
@@ -503,7 +471,7 @@ hipError_t launch_pose_ransac_batch(hipStream_t st, const PoseRansacBatchArgs& b
   hipLaunchKernelGGL(pose_gather_batch_kernel, dim3(b.nb < 1024 ? b.nb : 1024, np), dim3(PB), 0, st, b);
   hipLaunchKernelGGL(pose_hyp_batch_kernel, dim3((a.n_hyp + 63) / 64, np), dim3(64), 0, st, b);
   const int nsb = (a.n_max + PB * POSE_PTS - 1) / (PB * POSE_PTS);
-  hipLaunchKernelGGL(pose_score_batch_kernel, dim3(nsb, (a.n_hyp + POSE_HB - 1) / POSE_HB, np), dim3(PB), 0, st, b);
+  hipLaunchKernelGGL(pose_score_batch_kernel, dim3(nsb, (a.n_hyp + RANSAC_HB - 1) / RANSAC_HB, np), dim3(PB), 0, st, b);
   hipLaunchKernelGGL(pose_select_batch_kernel, dim3(np), dim3(1024), 0, st, b);
   hipLaunchKernelGGL(pose_mask_batch_kernel, dim3(b.nb, np), dim3(PB), 0, st, b);
   e = launch_scan(st, a.blk, b.nb, a.n_out, nullptr, b.n_problems, (size_t)b.nb);

@@ -5,14 +5,14 @@
 //                         normalised points formed in float as epi_ata_kernel forms its rows, its null vector by Gaussian
 //                         elimination with full pivoting in double, the rank-2 projection (linalg::svd3, as
 //                         fundamental_from_normal_matrix), F = T1^T F T2 scaled to unit Frobenius norm, 9 floats;
-//   ransac_score_kernel   the hot path: every thread holds RANSAC_PTS correspondences in registers, the workgroup walks a
-//                         block of 64 hypotheses whose F is wave-uniform; per wave one ballot + popcount per hypothesis, the
-//                         count parked in the lane of that hypothesis; one global atomicAdd per (workgroup, hypothesis);
+//   ransac_score_kernel   the hot path, ransac_common.h's scoring tile on EpiModel (below): every thread holds RANSAC_PTS
+//                         correspondences in registers, the workgroup walks a block of 64 hypotheses whose F is wave-uniform;
 //   ransac_select_kernel  one workgroup: invalid hypotheses get -1, the winner is the maximum of (count << 32) | ~h (the
 //                         most inliers, ties to the lowest h);
 //   ransac_mask_kernel / ransac_scatter_kernel
 //                         the winner's inlier mask (the same per-pair predicate) and the inlier pairs compacted in their
-//                         original order: count / scan (geom.hip's launch_scan) / scatter.
+//                         original order: count / scan (geom.hip's launch_scan) / scatter; the mask tail and the scatter
+//                         are ransac_common.h's.
 // Counts are integers: nothing here depends on scheduling.  The refit of the winner's inliers is vo_estimate_transform_dev
 // itself (capi.hip).
 #include "vo_internal.h"
@@ -23,7 +23,6 @@ namespace vo {
 
 constexpr int RB = 256;            // threads per workgroup (gather, scoring, mask)
 constexpr int RANSAC_PTS = 4;      // correspondences per thread of the scoring pass
-constexpr int RANSAC_HB = 64;      // hypotheses per scoring workgroup: one per lane of the count register
 constexpr int RANSAC_FS = 12;      // floats per hypothesis: F row-major in [0, 9), [9] = 1 valid / 0 invalid
 
 // Sampson distance below the threshold: e^2 < thr^2 * den, e = x1^T F x2, den = (F x2)_0^2 + (F x2)_1^2 + (F^T x1)_0^2 +
@@ -40,7 +39,7 @@ __device__ __forceinline__ bool sampson_inlier(const float* f, const float4 p, f
 }
 
 __global__ __launch_bounds__(RB) void ransac_gather_kernel(RansacArgs a) {
-  const int n = ransac_rows(a.d_n, a.n_max);
+  const int n = live_rows(a.d_n, a.n_max);
   const float qnan = __int_as_float(0x7fc00000);
   int bad = 0;
   for (int i = blockIdx.x * RB + threadIdx.x; i < n; i += gridDim.x * RB) {
@@ -61,7 +60,7 @@ __global__ __launch_bounds__(RB) void ransac_gather_kernel(RansacArgs a) {
 __global__ __launch_bounds__(64) void ransac_hyp_kernel(RansacArgs a) {
   const int h = blockIdx.x * 64 + threadIdx.x;
   if (h >= a.n_hyp) return;
-  const int n = ransac_rows(a.d_n, a.n_max);
+  const int n = live_rows(a.d_n, a.n_max);
   float* out = a.F + (size_t)h * RANSAC_FS;
   int idx[8];
   int k = 0;
@@ -139,40 +138,27 @@ __global__ __launch_bounds__(64) void ransac_hyp_kernel(RansacArgs a) {
   out[9] = ok ? 1.f : 0.f;
 }
 
+// the epipolar front end as a model of ransac_common.h: a pair is (u1, v1, u2, v2), a hypothesis F with its valid flag
+struct EpiModel {
+  static constexpr int NT = RB, PTS = RANSAC_PTS;
+  using Pair = float4;
+  struct Hyp { float f[9]; };
+  const RansacArgs& a;
+  __device__ __forceinline__ Pair load_pair(int i) const { return a.pts[i]; }
+  static __device__ __forceinline__ Pair zero_pair() { return make_float4(0.f, 0.f, 0.f, 0.f); }
+  __device__ __forceinline__ bool valid(int h) const { return !(a.F[(size_t)h * RANSAC_FS + 9] == 0.f); }
+  __device__ __forceinline__ Hyp load(int h) const {
+    const float* g = a.F + (size_t)h * RANSAC_FS;
+    Hyp hyp;
+#pragma unroll
+    for (int c = 0; c < 9; ++c) hyp.f[c] = g[c];
+    return hyp;
+  }
+  __device__ __forceinline__ bool inlier(const Hyp& hyp, const Pair& p) const { return sampson_inlier(hyp.f, p, a.thr2); }
+};
+
 __global__ __launch_bounds__(RB) void ransac_score_kernel(RansacArgs a) {
-  __shared__ int s_cnt[RB / 64][RANSAC_HB];
-  const int n = ransac_rows(a.d_n, a.n_max);
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  float4 p[RANSAC_PTS];
-  bool live[RANSAC_PTS];
-#pragma unroll
-  for (int q = 0; q < RANSAC_PTS; ++q) {
-    const int i = (blockIdx.x * RANSAC_PTS + q) * RB + threadIdx.x;
-    live[q] = i < n;
-    p[q] = live[q] ? a.pts[i] : make_float4(0.f, 0.f, 0.f, 0.f);
-  }
-  const int h0 = blockIdx.y * RANSAC_HB;
-  const int hn = a.n_hyp - h0 < RANSAC_HB ? a.n_hyp - h0 : RANSAC_HB;
-  int mine = 0;                                  // the count of hypothesis h0 + lane over this wave's correspondences
-  for (int k = 0; k < hn; ++k) {
-    const float* g = a.F + (size_t)(h0 + k) * RANSAC_FS;
-    float f[10];
-#pragma unroll
-    for (int c = 0; c < 10; ++c) f[c] = g[c];    // the same address in every lane
-    if (f[9] == 0.f) continue;
-    int cnt = 0;
-#pragma unroll
-    for (int q = 0; q < RANSAC_PTS; ++q) cnt += __popcll(__ballot(live[q] && sampson_inlier(f, p[q], a.thr2)));
-    if (lane == k) mine = cnt;
-  }
-  s_cnt[wave][lane] = mine;
-  __syncthreads();
-  if (threadIdx.x < hn) {
-    int v = 0;
-#pragma unroll
-    for (int w = 0; w < RB / 64; ++w) v += s_cnt[w][threadIdx.x];
-    if (v) atomicAdd(&a.counts[h0 + threadIdx.x], v);
-  }
+  ransac_score_body(EpiModel{a}, blockIdx.x, blockIdx.y, live_rows(a.d_n, a.n_max), a.n_hyp, a.counts);
 }
 
 __global__ __launch_bounds__(1024) void ransac_select_kernel(RansacArgs a) {
@@ -184,8 +170,7 @@ __global__ __launch_bounds__(1024) void ransac_select_kernel(RansacArgs a) {
 }
 
 __global__ __launch_bounds__(RB) void ransac_mask_kernel(RansacArgs a) {
-  __shared__ int s_wave[RB / 64];
-  const int n = ransac_rows(a.d_n, a.n_max);
+  const int n = live_rows(a.d_n, a.n_max);
   const int win = a.info[2];
   const int i = blockIdx.x * RB + threadIdx.x;
   bool in = false;
@@ -196,45 +181,35 @@ __global__ __launch_bounds__(RB) void ransac_mask_kernel(RansacArgs a) {
     for (int c = 0; c < 9; ++c) f[c] = g[c];
     in = sampson_inlier(f, a.pts[i], a.thr2);
   }
-  if (i < a.n_max) a.mask[i] = in ? 1 : 0;
-  int total;
-  ransac_rank<RB>(in, s_wave, total);
-  if (threadIdx.x == 0) a.blk[blockIdx.x] = total;
+  ransac_mask_tail<RB>(in, blockIdx.x, a.n_max, a.mask, a.blk);
 }
 
 __global__ __launch_bounds__(RB) void ransac_scatter_kernel(RansacArgs a) {
-  __shared__ int s_wave[RB / 64];
-  const int i = blockIdx.x * RB + threadIdx.x;
-  const bool in = i < a.n_max && a.mask[i];
-  int total;
-  const int r = ransac_rank<RB>(in, s_wave, total);
-  if (in) reinterpret_cast<int2*>(a.out_pairs)[a.blk[blockIdx.x] + r] = reinterpret_cast<const int2*>(a.pairs)[i];
+  ransac_scatter_body<RB>(blockIdx.x, a.n_max, a.mask, a.blk, a.pairs, a.out_pairs);
 }
 
-// ws layout (bytes): [0,64) info + maxima  then pts [n_max] float4 | F [n_hyp][12] | counts [n_hyp] | mask [n_max] |
-// per-workgroup counts | compacted pairs [n_max][2]
-static size_t up256(size_t b) { return (b + 255) & ~(size_t)255; }
 static int ransac_nb(int n_max) { return (n_max + RB - 1) / RB; }
 
-size_t ransac_workspace_bytes(int n_max, int n_hyp) {
-  return 256 + up256(16 * (size_t)n_max) + up256(4 * RANSAC_FS * (size_t)n_hyp) + up256(4 * (size_t)n_hyp) + up256((size_t)n_max) +
-         up256(4 * (size_t)ransac_nb(n_max)) + up256(8 * (size_t)n_max);
+// The workspace, block by block (each 256-aligned), in this order; ws may be null (the walk then only measures)
+RansacArgs ransac_layout(void* ws, int n_max, int n_hyp, size_t* bytes) {
+  RansacArgs a{};
+  WsCarver w(ws);
+  a.info = w.take<int>(256);                                   // [0, 32) info, [32, 48) maxima
+  a.maxima = WsCarver::within<unsigned>(a.info, 32);
+  a.pts = w.take<float4>(16 * (size_t)n_max);
+  a.F = w.take<float>(4 * RANSAC_FS * (size_t)n_hyp);
+  a.counts = w.take<int>(4 * (size_t)n_hyp);
+  a.mask = w.take<uint8_t>((size_t)n_max);
+  a.blk = w.take<int>(4 * (size_t)ransac_nb(n_max));           // per-workgroup counts
+  a.out_pairs = w.take<int32_t>(8 * (size_t)n_max);            // compacted pairs
+  a.n_max = n_max; a.n_hyp = n_hyp;
+  if (bytes) *bytes = w.bytes;
+  return a;
 }
 
-RansacArgs ransac_layout(void* ws, int n_max, int n_hyp) {
-  RansacArgs a{};
-  char* w = static_cast<char*>(ws);
-  a.info = reinterpret_cast<int*>(w);
-  a.maxima = reinterpret_cast<unsigned*>(w + 32);
-  size_t o = 256;
-  a.pts = reinterpret_cast<float4*>(w + o); o += up256(16 * (size_t)n_max);
-  a.F = reinterpret_cast<float*>(w + o); o += up256(4 * RANSAC_FS * (size_t)n_hyp);
-  a.counts = reinterpret_cast<int*>(w + o); o += up256(4 * (size_t)n_hyp);
-  a.mask = reinterpret_cast<uint8_t*>(w + o); o += up256((size_t)n_max);
-  a.blk = reinterpret_cast<int*>(w + o); o += up256(4 * (size_t)ransac_nb(n_max));
-  a.out_pairs = reinterpret_cast<int32_t*>(w + o);
-  a.n_max = n_max; a.n_hyp = n_hyp;
-  return a;
+size_t ransac_workspace_bytes(int n_max, int n_hyp) {
+  size_t bytes;
+  return ransac_layout(nullptr, n_max, n_hyp, &bytes), bytes;
 }
 
 hipError_t launch_ransac(hipStream_t st, const RansacArgs& a) {

@@ -15,6 +15,25 @@ extern "C" __attribute__((visibility("hidden"))) unsigned long long vo_ctx_id(st
 
 namespace vo {
 
+// ---- workspaces ------------------------------------------------------------
+inline size_t up256(size_t b) { return (b + 255) & ~(size_t)255; }
+// Carves a workspace into 256-aligned blocks in the order they are taken; `bytes` is the running size.  The base may be
+// null: the blocks are then null too and the walk only measures, so a layout function is also its own size function.
+struct WsCarver {
+  char* base;
+  size_t bytes = 0;
+  explicit WsCarver(void* ws) : base(static_cast<char*>(ws)) {}
+  template <class T>
+  T* take(size_t block_bytes) {
+    T* p = base ? reinterpret_cast<T*>(base + bytes) : nullptr;
+    bytes += up256(block_bytes);
+    return p;
+  }
+  // `off` bytes into a block taken before (a null block stays null)
+  template <class T>
+  static T* within(void* block, size_t off) { return block ? reinterpret_cast<T*>(static_cast<char*>(block) + off) : nullptr; }
+};
+
 // ---- PICP ------------------------------------------------------------------
 #ifndef VO_PICP_BLOCK
 #define VO_PICP_BLOCK 256
@@ -428,8 +447,9 @@ struct RansacArgs {
   int32_t* out_pairs;         // [n_max][2] the winner's inlier pairs, in their original order
 };
 size_t ransac_workspace_bytes(int n_max, int n_hyp);
-// the workspace's arrays; the caller fills in the inputs and may point counts / mask elsewhere
-RansacArgs ransac_layout(void* ws, int n_max, int n_hyp);
+// the workspace's arrays (ws may be null: only *bytes, the size, means something then); the caller fills in the inputs and may
+// point counts / mask elsewhere
+RansacArgs ransac_layout(void* ws, int n_max, int n_hyp, size_t* bytes = nullptr);
 hipError_t launch_ransac(hipStream_t st, const RansacArgs& a);
 
 // ---- P3P RANSAC in front of the tracking solve (pose_ransac.hip) ------------------------------------------
@@ -453,8 +473,9 @@ struct PoseRansacArgs {
   int* status;                // the status code (as info[4]), or null
 };
 size_t pose_ransac_workspace_bytes(int n_max, int n_hyp);
-// the workspace's arrays; the caller fills in the inputs and the outputs and may point counts / mask elsewhere
-PoseRansacArgs pose_ransac_layout(void* ws, int n_max, int n_hyp);
+// the workspace's arrays (ws, *bytes: as ransac_layout); the caller fills in the inputs and the outputs and may point counts /
+// mask elsewhere
+PoseRansacArgs pose_ransac_layout(void* ws, int n_max, int n_hyp, size_t* bytes = nullptr);
 hipError_t launch_pose_ransac(hipStream_t st, const PoseRansacArgs& a);
 // the batched form: `a` holds problem 0's arrays and the settings all problems share; problem p's inputs and outputs lie p
 // strides (in elements: points, pixels, pairs) further, its workspace arrays p x (n_max | n_hyp | nb) items further
@@ -465,8 +486,9 @@ struct PoseRansacBatchArgs {
   int n_problems;
 };
 size_t pose_ransac_batch_workspace_bytes(int n_problems, int n_max, int n_hyp);
-// the workspace's arrays; the caller fills in the inputs, the strides and the outputs and may point counts / mask elsewhere
-PoseRansacBatchArgs pose_ransac_batch_layout(void* ws, int n_problems, int n_max, int n_hyp);
+// the workspace's arrays (ws, *bytes: as ransac_layout); the caller fills in the inputs, the strides and the outputs and may
+// point counts / mask elsewhere
+PoseRansacBatchArgs pose_ransac_batch_layout(void* ws, int n_problems, int n_max, int n_hyp, size_t* bytes = nullptr);
 hipError_t launch_pose_ransac_batch(hipStream_t st, const PoseRansacBatchArgs& b);
 
 }  // namespace vo

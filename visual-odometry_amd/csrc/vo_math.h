@@ -768,4 +768,33 @@ VO_HD TriConst tri_constants(const float K[9], const Pose& X) {
   return c;
 }
 
+#if defined(__HIPCC__)
+// ---- two pieces every kernel file uses (device only) ----------------------------------------------------
+// live rows of a call: *d_n clamped to [0, n_max], or n_max when d_n is null
+__device__ __forceinline__ int live_rows(const int* d_n, int n_max) {
+  int n = n_max;
+  if (d_n) { const int m = *d_n; n = m < n ? (m < 0 ? 0 : m) : n; }
+  return n;
+}
+
+// exclusive rank of `flag` inside a workgroup of NT threads (s_wave: NT / 64 ints of LDS); total = flags set
+template <int NT>
+__device__ __forceinline__ int block_rank(bool flag, int* s_wave, int& total) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const unsigned long long m = __ballot(flag);
+  const int before = __popcll(m & ((1ull << lane) - 1ull));
+  if (lane == 0) s_wave[wave] = __popcll(m);
+  __syncthreads();
+  int off = 0, tot = 0;
+#pragma unroll
+  for (int w = 0; w < NT / 64; ++w) {
+    const int c = s_wave[w];
+    if (w < wave) off += c;
+    tot += c;
+  }
+  total = tot;
+  return off + before;
+}
+#endif
+
 }  // namespace vo
