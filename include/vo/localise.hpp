@@ -1,7 +1,8 @@
 // vo/localise.hpp -- reading the device map by appearance (vo_map_lookup*, vo_map_localise*): an extension of the facade,
 // not a reference interface (the reference never reads its map back).  DeviceMap owns a vo_map: update() is
 // PointCloudVector<3>::update, lookup() answers "which entries of the map does this frame see?", localise() "where is this
-// camera in the map?" -- lookup -> P3P RANSAC -> PICP rounds, from the frame alone.  A frame that cannot be localised is a
+// camera in the map?" -- lookup -> P3P RANSAC -> PICP rounds, from the frame alone; refine() re-estimates the map's points from
+// all the frames that see them, the poses fixed (vo_map_refine).  A frame that cannot be localised is a
 // status in the statistics, not an exception; vo::Error is thrown where the C call refuses.
 #pragma once
 
@@ -30,6 +31,19 @@ struct LocaliseOptions {
 inline const char* localise_status_name(int status) {
   static const char* names[] = {"OK", "FEW_MATCHES", "NO_CONSENSUS", "FEW_INLIERS", "NOT_FINITE"};
   return status >= 0 && status < 5 ? names[status] : "?";
+}
+
+//! vo_map_refine: structure-only adjustment of the map's points (the poses are fixed)
+struct RefineOptions {
+  int n_rounds = 10;
+  int min_obs = 3;
+  float huber_px = 0;   //!< 0: squared error
+  float damping = 0;
+};
+
+inline const char* refine_status_name(int status) {
+  static const char* names[] = {"OK", "UNSEEN", "FEW_OBS", "BEHIND", "NOT_FINITE", "COST_ROSE"};
+  return status >= 0 && status < 6 ? names[status] : "?";
 }
 
 class DeviceMap {
@@ -126,6 +140,45 @@ class DeviceMap {
     check(vo_memcpy_d2h(ctx_, out[0].data(), d_T.p, F * 64), "vo_memcpy_d2h");
     if (stats) check(vo_memcpy_d2h(ctx_, stats->data(), d_st.p, F * sizeof(vo_map_localise_stats)), "vo_memcpy_d2h");
     return out;
+  }
+
+  //! every point of the map re-estimated, in place, from all the rows of the frames that see it, the poses (p_cam = T p_map,
+  //! one per frame) fixed (vo_map_refine: the frames are padded to the largest one and uploaded).  *status receives one
+  //! VO_MAP_REFINE_* per entry; only OK entries are replaced.
+  void refine(const Camera& cam, const std::vector<Vector2fVector>& pixels, const std::vector<Vector10fVector>& appearances,
+              const IsometryVector& poses, const RefineOptions& opt = RefineOptions(), vo_map_refine_stats* stats = nullptr,
+              std::vector<int32_t>* status = nullptr) {
+    const size_t F = pixels.size();
+    if (appearances.size() != F || poses.size() != F) throw Error(VO_ERR_INVALID_ARG, "DeviceMap::refine: per-frame arrays differ in size");
+    size_t cap = 0;
+    for (size_t f = 0; f < F; ++f) {
+      if (pixels[f].size() != appearances[f].size()) throw Error(VO_ERR_INVALID_ARG, "DeviceMap::refine: pixels and appearances differ in size");
+      if (pixels[f].size() > cap) cap = pixels[f].size();
+    }
+    std::vector<float> uv(F * cap * 2 + 2, 0.f), app(F * cap * 10 + 10, 0.f), T(F * 16 + 16, 0.f);
+    std::vector<int> n(F + 1, 0);
+    for (size_t f = 0; f < F; ++f) {
+      n[f] = (int)pixels[f].size();
+      for (size_t i = 0; i < pixels[f].size(); ++i) {
+        for (int k = 0; k < 2; ++k) uv[(f * cap + i) * 2 + k] = pixels[f][i][k];
+        for (int k = 0; k < 10; ++k) app[(f * cap + i) * 10 + k] = appearances[f][i][k];
+      }
+      for (int k = 0; k < 16; ++k) T[16 * f + k] = poses[f].data()[k];
+    }
+    if (status) status->assign((size_t)size(), -1);
+    const vo_map_refine_params prm{opt.n_rounds, opt.min_obs, opt.huber_px, opt.damping};
+    vo_map_refine_stats s{};
+    check(vo_map_refine(h_, (int)F, cam.cameraMatrix().data(), uv.data(), app.data(), n.data(), (int)cap, T.data(), &prm,
+                        status && !status->empty() ? status->data() : nullptr, &s), "vo_map_refine");
+    if (stats) *stats = s;
+  }
+
+  //! the map's points and appearances in entry order
+  void read(Vector3fVector& points, Vector10fVector& appearances) const {
+    const int n = size();
+    points.resize((size_t)n); appearances.resize((size_t)n);
+    int m = 0;
+    if (n > 0) check(vo_map_read(h_, points[0].data(), appearances[0].data(), n, &m), "vo_map_read");
   }
 
  private:

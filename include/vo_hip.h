@@ -764,6 +764,61 @@ int vo_map_localise(vo_map *m, int rows, int cols, int z_near, int z_far, const 
                     const float *app, int n, const vo_ransac_params *params, float kernel_threshold, int n_iters,
                     int min_inliers, const float T0[16] /* or NULL */, float T_out[16], vo_map_localise_stats *stats_out);
 
+/* REFINEMENT (structure-only adjustment: the poses are fixed, the points move).  Every entry of the map is re-estimated
+ * from ALL the rows of n_frames frames that see it, by Gauss-Newton on the reprojection error.  Frame f: pixels d_uv + 2 f
+ * uv_stride floats, appearances d_app + 10 f app_stride floats (strides in pixels / rows, both >= n_max), d_n_rows[f] (or
+ * n_max) live rows, pose d_T16 + 16 f (column-major 4x4, p_cam = T p_map).  Everything is enqueued on the context's stream:
+ * vo_map_lookup_batch_dev with the entry of every query position, the observation lists by entry (count, scan, scatter,
+ * order), ONE launch that runs all rounds of every landmark, one launch for the statistics.  The ordering pass compares every
+ * observation with the others of its landmark: it is meant for a few to a few thousand observations per landmark, and a
+ * landmark seen by n rows costs n^2 reads (n = 10^5: 10^10, about a second of the device).  RULES:
+ *   observation  a live row (frame f, position i) whose lookup returns the entry; its key is f * n_max + i; a landmark
+ *                consumes its observations in ascending key order; two rows of one frame that hit one entry are two
+ *                observations.
+ *   cost         sum of rho(e), e = proj(K, T_f p) - uv with q = K p_cam, u = q0 / q2, v = q1 / q2 (the full K; no image or
+ *                depth gate: camera z > 0 is a status, below).  huber_px == 0: rho = |e|^2.  huber_px > 0: the Huber cost,
+ *                rho = |e|^2 up to |e| = huber_px and huber_px (2 |e| - huber_px) beyond, minimised by IRLS with the weight
+ *                w = min(1, huber_px / |e|).
+ *   round        H = sum w J^T J + damping I, b = sum w J^T e, p <- p - H^-1 b; the 3x3 solve is an LDL^T in natural order;
+ *                sums, solve and p are double; p is rounded to float32 once, after the last round.  n_rounds == 0
+ *                evaluates cost and status and writes nothing.
+ *   status       per entry, in this order of precedence:
+ *                UNSEEN      no observation
+ *                FEW_OBS     1 .. min_obs - 1 observations
+ *                NOT_FINITE  a sum of some evaluation, the step or the point is not finite, or a pivot is not > 0 (the
+ *                            landmark stops there)
+ *                BEHIND      at the start, in some round or at the end an observation has camera z that is not > 0
+ *                COST_ROSE   the cost of the float32-rounded final point is larger than the cost of the point found
+ *                OK          otherwise: the 12 bytes of the point are replaced.  Every other status leaves them bit for bit.
+ * d_status_out [map size] (or NULL) receives the status of every entry; with d_xyz_out [map size][3] the map is NOT written
+ * and d_xyz_out holds every entry's point, refined or not; *d_stats (8-byte aligned) the census.  cost_before / cost_after
+ * are sums over the OK landmarks in double, taken in a fixed order (entries e, e + 1024, ... in entry order into partial sum
+ * e mod 1024, the partial sums in order; tests/map_refine_restatement.py sums in the same order, the landmarks' own costs
+ * differ from float64 numpy in the last bits).  Every output is a function of the data alone: three calls give the same bytes.
+ * Capturable once a call of the same shape (n_frames, n_max, on a map no smaller) has sized the workspace; a capture that
+ * would have to grow it is refused (VO_ERR_NOT_READY) before anything is enqueued.
+ * Refused (VO_ERR_INVALID_ARG): the lookup's refusals, n_rounds < 0, min_obs < 2, a negative or non-finite huber_px or
+ * damping, a singular K, a null map / K / params / d_T16 / d_stats (d_uv, d_app with n_max > 0), a stride below n_max,
+ * d_uv / d_app / d_stats not 8-byte aligned. */
+#define VO_MAP_REFINE_OK          0   /* the point was replaced */
+#define VO_MAP_REFINE_UNSEEN      1   /* no observation */
+#define VO_MAP_REFINE_FEW_OBS     2   /* 1 .. min_obs-1 observations */
+#define VO_MAP_REFINE_BEHIND      3   /* at the start, in some round or at the end, an observation has camera z that is not > 0 */
+#define VO_MAP_REFINE_NOT_FINITE  4   /* a non-finite sum, a pivot that is not > 0, a non-finite step or point */
+#define VO_MAP_REFINE_COST_ROSE   5   /* final cost > initial cost */
+typedef struct vo_map_refine_params { int32_t n_rounds; int32_t min_obs; float huber_px; float damping; } vo_map_refine_params;
+typedef struct vo_map_refine_stats  { int32_t n_entries, n_obs; int32_t by_status[6]; double cost_before, cost_after; } vo_map_refine_stats;
+int vo_map_refine_batch_dev(vo_map *m, int n_frames, const float K[9], const float *d_uv, size_t uv_stride,
+                            const float *d_app, size_t app_stride, int n_max, const int *d_n_rows /* [n_frames] or NULL */,
+                            const float *d_T16 /* [n_frames][16], p_cam = T p_map */, const vo_map_refine_params *params,
+                            int32_t *d_status_out /* [map size] or NULL */, float *d_xyz_out /* [map size][3] or NULL: NULL = in place */,
+                            vo_map_refine_stats *d_stats);
+/* host arrays: uv [n_frames][n_max][2], app [n_frames][n_max][10], n_rows [n_frames] (or NULL), T16 [n_frames][16];
+ * status_out [vo_map_size] (or NULL).  Uploads, the device call in place, one read-back; the same results bit for bit. */
+int vo_map_refine(vo_map *m, int n_frames, const float K[9], const float *uv, const float *app, const int *n_rows,
+                  int n_max, const float *T16, const vo_map_refine_params *params, int32_t *status_out,
+                  vo_map_refine_stats *stats_out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -15,6 +15,9 @@ from .api import (  # noqa: F401
     Map,
     MapLocaliseStats,
     MAP_LOCALISE_STATUS,
+    MapRefineParams,
+    MapRefineStats,
+    MAP_REFINE_STATUS,
     PICPSolver,
     VoError,
     compute_correspondences_images,

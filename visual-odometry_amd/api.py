@@ -485,6 +485,40 @@ class Map:
         return [(T[f].reshape(4, 4).T.copy(), st[f].as_dict()) for f in range(F)]
 
 
+    # ---- structure-only refinement (vo_map_refine*) ----
+    def refine_batch_dev(self, camera: Camera, n_frames, d_uv, uv_stride, d_app, app_stride, n_max, d_n, d_T16, params: "MapRefineParams",
+                         d_status_out, d_xyz_out, d_stats):
+        """vo_map_refine_batch_dev on device pointers (ints; d_n, d_status_out and d_xyz_out may be None; strides in pixels /
+        rows): enqueues and returns.  d_stats: 48 bytes (MapRefineStats)."""
+        v = lambda d: C.c_void_p(d) if d else None
+        _chk(self.lib.vo_map_refine_batch_dev(self.h, C.c_int(n_frames), _ptr(_colmajor(camera._K, 3)), v(d_uv), C.c_size_t(uv_stride),
+                                              v(d_app), C.c_size_t(app_stride), C.c_int(n_max), v(d_n), v(d_T16), C.byref(params),
+                                              v(d_status_out), v(d_xyz_out), v(d_stats)))
+
+    def refine(self, camera: Camera, frames, poses, n_rounds=10, min_obs=3, huber_px=0.0, damping=0.0):
+        """vo_map_refine: every entry re-estimated, in place, from all the rows of `frames` (a list of (pixels (n, 2),
+        appearances (n, 10)) of any sizes, padded here to a common n_max) that see it, the poses (4x4, p_cam = T p_map, one
+        per frame) fixed.  Returns (status (size,) int32: MAP_REFINE_STATUS names the codes, stats dict)."""
+        F = len(frames)
+        if F < 1 or F != len(poses):
+            raise ValueError("Map.refine: one pose per frame, at least one frame")
+        n = np.array([len(_f32(a, (-1, 10))) for _, a in frames], np.int32)
+        cap = int(n.max())
+        uv = np.zeros((F, max(cap, 1), 2), np.float32)
+        app = np.zeros((F, max(cap, 1), 10), np.float32)
+        for f, (p, a) in enumerate(frames):
+            uv[f, : n[f]] = _f32(p, (-1, 2))
+            app[f, : n[f]] = _f32(a, (-1, 10))
+        T = np.stack([_colmajor(X, 4) for X in poses]).astype(np.float32)
+        status = np.full(max(len(self), 1), -1, np.int32)
+        st = MapRefineStats()
+        prm = MapRefineParams(int(n_rounds), int(min_obs), float(huber_px), float(damping))
+        _chk(self.lib.vo_map_refine(self.h, C.c_int(F), _ptr(_colmajor(camera._K, 3)), _ptr(uv[:, :cap]) if cap else None,
+                                    _ptr(app[:, :cap]) if cap else None, _ptr(n), C.c_int(cap), _ptr(T), C.byref(prm), _ptr(status),
+                                    C.byref(st)))
+        return status[: st.n_entries].copy(), st.as_dict()
+
+
 class MapLocaliseStats(C.Structure):
     """vo_map_localise_stats (include/vo_hip.h)"""
     _fields_ = [("status", C.c_int32), ("n_rows", C.c_int32), ("n_hits", C.c_int32), ("ransac_status", C.c_int32),
@@ -495,6 +529,25 @@ class MapLocaliseStats(C.Structure):
 
 
 MAP_LOCALISE_STATUS = ("OK", "FEW_MATCHES", "NO_CONSENSUS", "FEW_INLIERS", "NOT_FINITE")     # VO_MAP_LOCALISE_*
+
+
+class MapRefineParams(C.Structure):
+    """vo_map_refine_params (include/vo_hip.h)"""
+    _fields_ = [("n_rounds", C.c_int32), ("min_obs", C.c_int32), ("huber_px", C.c_float), ("damping", C.c_float)]
+
+
+class MapRefineStats(C.Structure):
+    """vo_map_refine_stats (include/vo_hip.h)"""
+    _fields_ = [("n_entries", C.c_int32), ("n_obs", C.c_int32), ("by_status", C.c_int32 * 6), ("cost_before", C.c_double),
+                ("cost_after", C.c_double)]
+
+    def as_dict(self):
+        return dict(n_entries=self.n_entries, n_obs=self.n_obs, by_status=list(self.by_status), cost_before=self.cost_before,
+                    cost_after=self.cost_after)
+
+
+assert C.sizeof(MapRefineParams) == 16 and C.sizeof(MapRefineStats) == 48
+MAP_REFINE_STATUS = ("OK", "UNSEEN", "FEW_OBS", "BEHIND", "NOT_FINITE", "COST_ROSE")      # VO_MAP_REFINE_*
 
 
 def triangulate_points(k, X, correspondences, p1_img, p2_img, app2=None, want_pairs=True,

@@ -2126,6 +2126,7 @@ struct vo_map {
   DevBuf look_ws;               // vo_map_lookup*: per-workgroup counts, entries per query position
   DevBuf loc_ws;                // vo_map_localise*: what passes from stage to stage (hits, gathered points, winner, pairs handed on)
   vo_picp* solver = nullptr;    // vo_map_localise[_dev]: made by the first call
+  DevBuf ref_ws;                // vo_map_refine*: the entries seen, the observation lists, status and cost per entry
 };
 
 constexpr int MAP_MAX_ENTRIES = 1 << 29;      // 2.5 x that many table slots still fit 32 bits
@@ -2214,7 +2215,7 @@ int vo_map_destroy(vo_map* m) {
   map_free_arrays(m->d);
   if (m->d.hdr) (void)hipFree(m->d.hdr);
   if (m->hist) (void)hipFree(m->hist);
-  m->scratch.release(); m->up_xyz.release(); m->up_app.release(); m->look_ws.release(); m->loc_ws.release();
+  m->scratch.release(); m->up_xyz.release(); m->up_app.release(); m->look_ws.release(); m->loc_ws.release(); m->ref_ws.release();
   if (m->solver) (void)vo_picp_destroy(m->solver);
   delete m;
   return VO_OK;
@@ -2561,6 +2562,84 @@ int vo_map_localise(vo_map* m, int rows, int cols, int z_near, int z_far, const 
   VO_HIP_CHECK(hipStreamSynchronize(c->stream));
   memcpy(T_out, h.T, sizeof(h.T));
   *stats_out = h.s;
+  return VO_OK;
+}
+
+// ---- structure-only refinement: the lookup of every frame, then the launches of map_refine.hip ----------------------------
+static_assert(sizeof(vo_map_refine_params) == 16 && sizeof(vo_map_refine_stats) == 48, "the statistics kernel writes eight 4-byte words and two doubles");
+
+int vo_map_refine_batch_dev(vo_map* m, int n_frames, const float K[9], const float* d_uv, size_t uv_stride, const float* d_app,
+                            size_t app_stride, int n_max, const int* d_n, const float* d_T16, const vo_map_refine_params* params,
+                            int32_t* d_status_out, float* d_xyz_out, vo_map_refine_stats* d_stats) {
+  VO_MAP_LIVE(m);
+  const char* fn = "vo_map_refine_batch_dev";
+  if (!(K && params && d_T16 && d_stats)) return fail(VO_ERR_INVALID_ARG, "%s: null argument", fn);
+  if (n_frames < 1 || n_frames > 65535) return fail(VO_ERR_INVALID_ARG, "%s: n_frames %d outside 1 .. 65535 (the frame is a grid dimension)", fn, n_frames);
+  if (n_max < 0) return fail(VO_ERR_INVALID_ARG, "%s: negative row count", fn);
+  if (n_max > 0 && !(d_uv && d_app)) return fail(VO_ERR_INVALID_ARG, "%s: null argument", fn);
+  if (!aligned8(d_uv, d_app, d_stats)) return fail(VO_ERR_INVALID_ARG, "%s: device arrays must be 8-byte aligned", fn);
+  if (uv_stride < (size_t)n_max || app_stride < (size_t)n_max) return fail(VO_ERR_INVALID_ARG, "%s: a stride is smaller than n_max", fn);
+  if (uv_stride >= 0x7fffffff) return fail(VO_ERR_INVALID_ARG, "%s: stride too large", fn);
+  if (params->n_rounds < 0) return fail(VO_ERR_INVALID_ARG, "%s: negative n_rounds", fn);
+  if (params->min_obs < 2) return fail(VO_ERR_INVALID_ARG, "%s: min_obs must be at least 2", fn);
+  if (!(params->huber_px >= 0.f && params->huber_px <= 3.402823466e38f)) return fail(VO_ERR_INVALID_ARG, "%s: huber_px must be finite and not negative", fn);
+  if (!(params->damping >= 0.f && params->damping <= 3.402823466e38f)) return fail(VO_ERR_INVALID_ARG, "%s: damping must be finite and not negative", fn);
+  double Kinv[9];
+  if (!invert_k(K, Kinv)) return fail(VO_ERR_INVALID_ARG, "%s: K is singular", fn);
+  vo_ctx* c = m->ctx;
+  const long long bound_ll = m->size_ub < m->d.cap ? m->size_ub : m->d.cap;
+  const int bound = (int)bound_ll;
+  MapRefineWs w = map_refine_layout(nullptr, n_frames, n_max, bound);
+  if (app_stride >= 0x7fffffff / 10 || (long long)n_max * n_frames > (1ll << 30))      // (the lookup's own limit, met before anything is sized)
+    return fail(VO_ERR_INVALID_ARG, "%s: more than 2^30 rows in one call", fn);
+  const size_t look_need = sizeof(int) * map_lookup_scratch_ints(n_max, n_frames, false);
+  if (c->capturing && (m->ref_ws.cap < w.bytes || (n_max > 0 && m->look_ws.cap < look_need)))
+    return fail(VO_ERR_NOT_READY, "%s: the workspace would have to grow inside a graph capture (make one call with %d frames of n_max %d "
+                                  "on this map before capturing)", fn, n_frames, n_max);
+  if (int r = set_device(c)) return r;
+  VO_HIP_CHECK(m->ref_ws.ensure(w.bytes, c->stream));
+  w = map_refine_layout(m->ref_ws.p, n_frames, n_max, bound);
+  if (n_max > 0)
+    if (int r = vo_map_lookup_batch_dev(m, n_frames, d_app, app_stride, n_max, d_n, w.pairs, w.n_hits, nullptr, nullptr, w.ent)) return r;
+  MapRefineArgs a{};
+  a.w = w;
+  a.pts = m->d.pts; a.hdr = m->d.hdr; a.cap = m->d.cap; a.bound = bound;
+  a.uv = d_uv; a.uv_stride = uv_stride; a.n_max = n_max; a.n_frames = n_frames; a.T16 = d_T16;
+  for (int k = 0; k < 9; ++k) a.K[k] = K[k];
+  a.n_rounds = params->n_rounds; a.min_obs = params->min_obs; a.huber = params->huber_px; a.damping = params->damping;
+  a.status = d_status_out ? d_status_out : w.status;
+  a.xyz_out = d_xyz_out; a.stats = d_stats;
+  VO_HIP_CHECK(launch_map_refine(c->stream, a, c->n_cu));
+  return VO_OK;
+}
+
+int vo_map_refine(vo_map* m, int n_frames, const float K[9], const float* uv, const float* app, const int* n_rows, int n_max,
+                  const float* T16, const vo_map_refine_params* params, int32_t* status_out, vo_map_refine_stats* stats_out) {
+  VO_MAP_LIVE(m);
+  vo_ctx* c = m->ctx;
+  VO_NOT_CAPTURING(c);
+  VO_REQUIRE(K && T16 && params && stats_out, "null argument");
+  VO_REQUIRE(n_frames >= 1 && n_frames <= 65535, "n_frames outside 1 .. 65535");
+  VO_REQUIRE(n_max >= 0 && (n_max == 0 || (uv && app)), "bad frames");
+  VO_REQUIRE((long long)n_max * n_frames <= (1ll << 30), "more than 2^30 rows in one call");
+  if (int r = set_device(c)) return r;
+  const size_t rows = (size_t)n_frames * (size_t)n_max;
+  if (int r = upload(c, c->in[0], uv, sizeof(float) * 2 * rows)) return r;
+  if (int r = upload(c, c->in[1], app, sizeof(float) * 10 * rows)) return r;
+  if (int r = upload(c, c->in[2], T16, sizeof(float) * 16 * (size_t)n_frames)) return r;
+  if (n_rows)
+    if (int r = upload(c, c->in[3], n_rows, sizeof(int) * (size_t)n_frames)) return r;
+  int size = 0;
+  if (int r = vo_map_size(m, &size)) return r;                // (waits: the host arrays may go away after the call)
+  VO_HIP_CHECK(c->out[2].ensure(sizeof(vo_map_refine_stats) + 16, c->stream));
+  if (status_out) VO_HIP_CHECK(c->out[1].ensure(sizeof(int32_t) * (size_t)(size > 0 ? size : 1), c->stream));
+  if (int r = vo_map_refine_batch_dev(m, n_frames, K, c->in[0].as<float>(), (size_t)n_max, c->in[1].as<float>(), (size_t)n_max, n_max,
+                                      n_rows ? c->in[3].as<int>() : nullptr, c->in[2].as<float>(), params,
+                                      status_out ? c->out[1].as<int32_t>() : nullptr, nullptr, c->out[2].as<vo_map_refine_stats>()))
+    return r;
+  VO_HIP_CHECK(hipMemcpyAsync(stats_out, c->out[2].p, sizeof(vo_map_refine_stats), hipMemcpyDeviceToHost, c->stream));
+  if (status_out && size > 0) VO_HIP_CHECK(hipMemcpyAsync(status_out, c->out[1].p, sizeof(int32_t) * (size_t)size, hipMemcpyDeviceToHost, c->stream));
+  VO_HIP_CHECK(hipStreamSynchronize(c->stream));
   return VO_OK;
 }
 

@@ -1,0 +1,296 @@
+// map_refine.hip -- structure-only adjustment of the device map (vo_map_refine*): the poses are fixed, every landmark is
+// re-estimated from ALL the rows of n_frames frames that see it.  The rules are those of include/vo_hip.h; in short:
+//   observation   a live row (frame f, position i) whose lookup returns entry e; key f * n_max + i; consumed in ascending key order
+//   cost          rho(proj(K, T_f p) - uv), |e|^2 or Huber by IRLS; the only gate is camera z > 0, and it is a status, not a weight
+//   round         H = sum w J^T J + damping I, b = sum w J^T e, p <- p - H^-1 b (LDL^T in natural order), everything in double
+// Launches behind the lookup (which wrote the entry of every query position):
+//   memset                          counts and cursors of the entries
+//   map_refine_count_kernel         observations per entry (integer atomics: a count does not depend on the order)
+//   map_refine_offsets_kernel       exclusive scan inside every block of 256 entries + the block's total
+//   scan_counts_kernel              (geom.hip) the block totals -> block offsets, the number of observations
+//   map_refine_scatter_kernel       every observation's key into its entry's segment, at a cursor drawn by an atomic: the
+//                                   ORDER inside a segment depends on scheduling, the SET does not
+//   map_refine_order_kernel         one thread per scattered key: its rank among its segment's keys (they are distinct) is
+//                                   its place in the ordered segment -- a function of the data alone from here on
+//   map_refine_kernel               16 lanes per landmark, all rounds in this one launch: observations strided over the lanes,
+//                                   the 10 sums reduced in double by a fixed DPP tree inside the 16 lanes (every lane ends
+//                                   with the same bits), the 3x3 solve done redundantly by the 16
+//   map_refine_stats_kernel         one workgroup: status census and the two cost sums in a fixed order, no float atomics
+// Per-observation terms are evaluated in DOUBLE (vo_math.h: map_refine_term): DESIGN.md section 4.13 says why.
+#include "vo_internal.h"
+
+namespace vo {
+
+constexpr int RB = 256;                   // threads per workgroup
+constexpr int RG = 16;                    // lanes per landmark
+constexpr int RLPB = RB / RG;             // landmarks per workgroup and trip
+constexpr int REFINE_LDS_FRAMES = 512;    // poses staged in LDS up to here (12 floats each: 24 KiB), read through L2 beyond
+constexpr int RSTAT = 1024;               // threads of the statistics workgroup
+
+enum { ST_OK = 0, ST_UNSEEN = 1, ST_FEW_OBS = 2, ST_BEHIND = 3, ST_NOT_FINITE = 4, ST_COST_ROSE = 5 };
+
+__device__ __forceinline__ int refine_size(const MapRefineArgs& a) {
+  int M = a.hdr[0];
+  M = M < a.cap ? M : a.cap;
+  return M < a.bound ? M : a.bound;
+}
+
+__global__ __launch_bounds__(RB) void map_refine_count_kernel(MapRefineArgs a) {
+  const size_t rows = (size_t)a.n_frames * a.n_max;
+  const size_t k = (size_t)blockIdx.x * RB + threadIdx.x;
+  if (k >= rows) return;
+  const int e = a.w.ent[k];
+  if (e >= 0 && e < a.bound) atomicAdd(&a.w.cnt[e], 1);
+}
+
+__global__ __launch_bounds__(RB) void map_refine_offsets_kernel(MapRefineArgs a) {
+  __shared__ int s_wave[RB / 64];
+  const int e = blockIdx.x * RB + threadIdx.x;
+  const int v = e < a.bound ? a.w.cnt[e] : 0;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  int incl = v;
+#pragma unroll
+  for (int d = 1; d < 64; d <<= 1) { const int o = __shfl_up(incl, d); if (lane >= d) incl += o; }
+  if (lane == 63) s_wave[wave] = incl;
+  __syncthreads();
+  int off = 0, tot = 0;
+#pragma unroll
+  for (int w = 0; w < RB / 64; ++w) { const int c = s_wave[w]; if (w < wave) off += c; tot += c; }
+  if (e < a.bound) a.w.cnt[e] = off + incl - v;
+  if (threadIdx.x == 0) a.w.blk[blockIdx.x] = tot;
+}
+
+__device__ __forceinline__ int refine_offset(const MapRefineArgs& a, int e) { return a.w.cnt[e] + a.w.blk[e / RB]; }
+
+__global__ __launch_bounds__(RB) void map_refine_scatter_kernel(MapRefineArgs a) {
+  const size_t rows = (size_t)a.n_frames * a.n_max;
+  const size_t k = (size_t)blockIdx.x * RB + threadIdx.x;
+  if (k >= rows) return;
+  const int e = a.w.ent[k];
+  if (e < 0 || e >= a.bound) return;
+  const int at = atomicAdd(&a.w.cur[e], 1);
+  const size_t o = (size_t)refine_offset(a, e) + at;
+  if (o < rows) a.w.tmp[o] = (int)k;                         // (always: the segments partition the observations)
+}
+
+__global__ __launch_bounds__(RB) void map_refine_order_kernel(MapRefineArgs a) {
+  const size_t rows = (size_t)a.n_frames * a.n_max;
+  const int total = *a.w.total;
+  const size_t s = (size_t)blockIdx.x * RB + threadIdx.x;
+  if (s >= rows || s >= (size_t)total) return;
+  const int key = a.w.tmp[s];
+  if (key < 0 || (size_t)key >= rows) return;
+  const int e = a.w.ent[key];
+  if (e < 0 || e >= a.bound) return;
+  const int off = refine_offset(a, e), n = a.w.cur[e];
+  int rank = 0;
+  for (int j = 0; j < n; ++j) rank += a.w.tmp[off + j] < key;
+  a.w.keys[off + rank] = key;
+}
+
+// a double moved between lanes by a DPP control (two 32-bit moves; no LDS traffic)
+template <int CTRL>
+__device__ __forceinline__ double refine_dpp(double x) {
+  const long long b = __double_as_longlong(x);
+  int lo = (int)b, hi = (int)(b >> 32);
+  lo = __builtin_amdgcn_update_dpp(lo, lo, CTRL, 0xf, 0xf, false);
+  hi = __builtin_amdgcn_update_dpp(hi, hi, CTRL, 0xf, 0xf, false);
+  return __longlong_as_double(((long long)hi << 32) | (long long)(unsigned)lo);
+}
+// the sum over the 16 lanes of a DPP row (= one landmark's lanes), the same bits in every lane: the neighbour in the quad
+// (quad_perm [1,0,3,2]), the other pair of the quad (quad_perm [2,3,0,1]), the mirrored half row, the mirrored row.  Every step
+// adds two values that both lanes of a pair hold, and a + b = b + a bit for bit.
+__device__ __forceinline__ double refine_row_sum(double x) {
+  static_assert(RG == 16, "a landmark's lanes are one DPP row");
+  x += refine_dpp<0xB1>(x);
+  x += refine_dpp<0x4E>(x);
+  x += refine_dpp<0x141>(x);
+  x += refine_dpp<0x140>(x);
+  return x;
+}
+
+__device__ __forceinline__ bool refine_finite(double x) { return fabs(x) <= 1.7976931348623157e308; }
+
+template <bool LDS>
+__global__ __launch_bounds__(RB) void map_refine_kernel(MapRefineArgs a) {
+  __shared__ float s_pose[LDS ? REFINE_LDS_FRAMES * 12 : 12];
+  if (LDS) {
+    for (int k = threadIdx.x; k < a.n_frames * 12; k += RB) {
+      const int f = k / 12, j = k - 12 * f;
+      s_pose[k] = a.T16[16 * (size_t)f + (j < 9 ? (j % 3) + 4 * (j / 3) : 3 + j)];      // R column-major, then t
+    }
+    __syncthreads();
+  }
+  const int M = refine_size(a);
+  const int lg = threadIdx.x & (RG - 1), grp = threadIdx.x / RG;
+  const int shift = (threadIdx.x & 63) & ~(RG - 1);          // this group's bits in a ballot of the wave
+  double K[9];
+#pragma unroll
+  for (int k = 0; k < 9; ++k) K[k] = a.K[k];
+  const int n_batches = (a.bound + RLPB - 1) / RLPB;
+  for (int batch = blockIdx.x; batch < n_batches; batch += gridDim.x) {      // (uniform in the workgroup: the shuffles below see whole waves)
+    const int e = batch * RLPB + grp;
+    const bool in = e < M;
+    const int n = in ? a.w.cur[e] : 0;
+    const int off = in ? refine_offset(a, e) : 0;
+    float p0[3] = {0.f, 0.f, 0.f};
+    if (in) { p0[0] = a.pts[3 * (size_t)e]; p0[1] = a.pts[3 * (size_t)e + 1]; p0[2] = a.pts[3 * (size_t)e + 2]; }
+    double p[3] = {(double)p0[0], (double)p0[1], (double)p0[2]};
+    float pf[3] = {p0[0], p0[1], p0[2]};
+    bool run = in && n >= a.min_obs;                         // (min_obs >= 2: an unseen entry does not run either)
+    bool not_finite = false, behind = false;
+    double cost0 = 0.0, cost1 = 0.0;
+    for (int r = 0; r <= a.n_rounds; ++r) {
+      double acc[NREF];
+#pragma unroll
+      for (int k = 0; k < NREF; ++k) acc[k] = 0.0;
+      bool bh = false;
+      if (run) {
+        for (int j = lg; j < n; j += RG) {
+          const int key = a.w.keys[off + j];
+          const int f = key / a.n_max, i = key - f * a.n_max;
+          const float2 m = reinterpret_cast<const float2*>(a.uv)[(size_t)f * a.uv_stride + i];
+          float Rt[12];
+          if (LDS) {
+#pragma unroll
+            for (int k = 0; k < 12; ++k) Rt[k] = s_pose[12 * f + k];
+          } else {
+            const float* T = a.T16 + 16 * (size_t)f;
+#pragma unroll
+            for (int k = 0; k < 9; ++k) Rt[k] = T[(k % 3) + 4 * (k / 3)];
+            Rt[9] = T[12]; Rt[10] = T[13]; Rt[11] = T[14];
+          }
+          bh |= !map_refine_term(K, Rt, p, (double)m.x, (double)m.y, a.huber, acc);
+        }
+      }
+#pragma unroll
+      for (int k = 0; k < NREF; ++k) acc[k] = refine_row_sum(acc[k]);
+      const bool any_behind = ((__ballot(bh) >> shift) & ((1ull << RG) - 1ull)) != 0ull;
+      if (run) {
+        bool finite = true;
+#pragma unroll
+        for (int k = 0; k < NREF; ++k) finite &= refine_finite(acc[k]);
+        if (!finite) {
+          not_finite = true; run = false;
+        } else {
+          behind |= any_behind;
+          if (r == 0) cost0 = acc[9];
+          if (r == a.n_rounds) {
+            cost1 = acc[9];
+          } else {
+            const double H[6] = {acc[0] + a.damping, acc[1], acc[2], acc[3] + a.damping, acc[4], acc[5] + a.damping};
+            double x[3];
+            if (!ldlt3_solve(H, acc + 6, x)) {
+              not_finite = true; run = false;
+            } else {
+              p[0] -= x[0]; p[1] -= x[1]; p[2] -= x[2];
+              if (r == a.n_rounds - 1) {                     // rounded once: the cost that decides is the stored point's
+                pf[0] = (float)p[0]; pf[1] = (float)p[1]; pf[2] = (float)p[2];
+                p[0] = (double)pf[0]; p[1] = (double)pf[1]; p[2] = (double)pf[2];
+              }
+              if (!(refine_finite(p[0]) && refine_finite(p[1]) && refine_finite(p[2]))) { not_finite = true; run = false; }
+            }
+          }
+        }
+      }
+    }
+    if (in && lg == 0) {
+      int status = ST_OK;
+      if (n == 0) status = ST_UNSEEN;
+      else if (n < a.min_obs) status = ST_FEW_OBS;
+      else if (not_finite) status = ST_NOT_FINITE;
+      else if (behind) status = ST_BEHIND;
+      else if (cost1 > cost0) status = ST_COST_ROSE;
+      const bool replace = status == ST_OK && a.n_rounds > 0;
+      a.status[e] = status;
+      a.w.cost[2 * (size_t)e] = cost0;
+      a.w.cost[2 * (size_t)e + 1] = cost1;
+      if (a.xyz_out) {
+        float* o = a.xyz_out + 3 * (size_t)e;
+        o[0] = replace ? pf[0] : p0[0]; o[1] = replace ? pf[1] : p0[1]; o[2] = replace ? pf[2] : p0[2];
+      } else if (replace) {
+        float* o = a.pts + 3 * (size_t)e;
+        o[0] = pf[0]; o[1] = pf[1]; o[2] = pf[2];
+      }
+    }
+  }
+}
+
+// vo_map_refine_stats: int32 n_entries, n_obs, by_status[6]; double cost_before, cost_after.  Thread t takes the entries t,
+// t + 1024, ... in that order, thread 0 adds the 1024 partial sums in thread order: a fixed order, whatever the scheduling.
+__global__ __launch_bounds__(RSTAT) void map_refine_stats_kernel(MapRefineArgs a) {
+  __shared__ double s_c0[RSTAT], s_c1[RSTAT];
+  __shared__ int s_n[6];
+  const int M = refine_size(a);
+  if (threadIdx.x < 6) s_n[threadIdx.x] = 0;
+  __syncthreads();
+  int n[6] = {0, 0, 0, 0, 0, 0};
+  double c0 = 0.0, c1 = 0.0;
+  for (int e = threadIdx.x; e < M; e += RSTAT) {
+    const int s = a.status[e];
+#pragma unroll
+    for (int k = 0; k < 6; ++k) n[k] += s == k;
+    if (s == ST_OK) { c0 += a.w.cost[2 * (size_t)e]; c1 += a.w.cost[2 * (size_t)e + 1]; }
+  }
+  s_c0[threadIdx.x] = c0; s_c1[threadIdx.x] = c1;
+#pragma unroll
+  for (int k = 0; k < 6; ++k) if (n[k]) atomicAdd(&s_n[k], n[k]);
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    double t0 = 0.0, t1 = 0.0;
+    for (int t = 0; t < RSTAT; ++t) { t0 += s_c0[t]; t1 += s_c1[t]; }
+    int* si = static_cast<int*>(a.stats);
+    si[0] = M; si[1] = *a.w.total;
+    for (int k = 0; k < 6; ++k) si[2 + k] = s_n[k];
+    double* sd = reinterpret_cast<double*>(si + 8);
+    sd[0] = t0; sd[1] = t1;
+  }
+}
+
+MapRefineWs map_refine_layout(void* base, int n_frames, int n_max, int bound) {
+  MapRefineWs w{};
+  WsCarver c(base);
+  const size_t rows = (size_t)n_frames * (size_t)n_max, B = (size_t)(bound > 0 ? bound : 1);
+  w.ent = c.take<int32_t>(4 * (rows ? rows : 1));
+  w.pairs = c.take<int32_t>(8 * (rows ? rows : 1));
+  w.tmp = reinterpret_cast<int*>(w.pairs);
+  w.keys = w.pairs ? reinterpret_cast<int*>(w.pairs) + rows : nullptr;
+  w.n_hits = c.take<int>(4 * (size_t)n_frames);
+  w.cnt = c.take<int>(8 * B);
+  w.cur = w.cnt ? w.cnt + B : nullptr;
+  w.blk = c.take<int>(4 * ((B + RB - 1) / RB));
+  w.total = c.take<int>(4);
+  w.status = c.take<int32_t>(4 * B);
+  w.cost = c.take<double>(16 * B);
+  w.bytes = c.bytes;
+  return w;
+}
+
+hipError_t launch_map_refine(hipStream_t st, const MapRefineArgs& a, int n_cu) {
+  const size_t rows = (size_t)a.n_frames * (size_t)a.n_max, B = (size_t)(a.bound > 0 ? a.bound : 1);
+  const int nbE = (int)((B + RB - 1) / RB);
+  hipError_t e = hipMemsetAsync(a.w.cnt, 0, sizeof(int) * 2 * B, st);
+  if (e != hipSuccess) return e;
+  const unsigned row_blocks = (unsigned)((rows + RB - 1) / RB);
+  if (rows) hipLaunchKernelGGL(map_refine_count_kernel, dim3(row_blocks), dim3(RB), 0, st, a);
+  hipLaunchKernelGGL(map_refine_offsets_kernel, dim3(nbE), dim3(RB), 0, st, a);
+  e = launch_scan(st, a.w.blk, nbE, a.w.total);
+  if (e != hipSuccess) return e;
+  if (rows) {
+    hipLaunchKernelGGL(map_refine_scatter_kernel, dim3(row_blocks), dim3(RB), 0, st, a);
+    hipLaunchKernelGGL(map_refine_order_kernel, dim3(row_blocks), dim3(RB), 0, st, a);
+  }
+  if (a.bound > 0) {
+    const int n_batches = (a.bound + RLPB - 1) / RLPB;
+    // 104 VGPRs leave 4 waves per SIMD, i.e. 4 workgroups of 256 threads per CU (4 x 24 KiB of LDS fit as well): that many stay
+    // resident and stride over the batches, so that the poses are staged once per resident workgroup
+    const int cap = 4 * (n_cu > 0 ? n_cu : 256);
+    const int grid = n_batches < cap ? n_batches : cap;
+    if (a.n_frames <= REFINE_LDS_FRAMES) hipLaunchKernelGGL(map_refine_kernel<true>, dim3(grid), dim3(RB), 0, st, a);
+    else hipLaunchKernelGGL(map_refine_kernel<false>, dim3(grid), dim3(RB), 0, st, a);
+  }
+  hipLaunchKernelGGL(map_refine_stats_kernel, dim3(1), dim3(RSTAT), 0, st, a);
+  return hipGetLastError();
+}
+
+}  // namespace vo

@@ -393,6 +393,38 @@ struct MapLocaliseFinish {
 };
 hipError_t launch_map_localise_finish(hipStream_t st, const MapLocaliseFinish& a);
 
+// ---- structure-only refinement of the map's points (map_refine.hip, vo_map_refine*) ---------------------------------
+// The workspace of one call: `bound` >= the map's size (the launches are sized by it, the kernels read the size itself).
+struct MapRefineWs {
+  int32_t* ent;        // [n_frames][n_max] the lookup's entry per query position
+  int32_t* pairs;      // [n_frames][n_max][2] the lookup's pairs; afterwards the two key arrays below live here
+  int *tmp, *keys;     // [n_frames * n_max] keys as scattered / every entry's segment in ascending order
+  int* n_hits;         // [n_frames] (the lookup's counts)
+  int *cnt, *cur;      // [bound] observations per entry -> offset inside its block of 256 entries; scatter cursors = the counts
+  int* blk;            // [ceil(bound / 256)] block totals -> block offsets
+  int* total;          // [1] observations in all
+  int32_t* status;     // [bound] (the caller's d_status_out takes its place when given)
+  double* cost;        // [bound][2] cost before / after
+  size_t bytes;
+};
+MapRefineWs map_refine_layout(void* base, int n_frames, int n_max, int bound);
+struct MapRefineArgs {
+  MapRefineWs w;
+  float* pts; const int* hdr; int cap;  // the map
+  int bound;
+  const float* uv; size_t uv_stride;    // pixels between frames
+  int n_max, n_frames;
+  const float* T16;                     // [n_frames][16] column-major, p_cam = T p_map
+  double K[9];                          // column-major
+  int n_rounds, min_obs;
+  double huber, damping;
+  int32_t* status;                      // [size]
+  float* xyz_out;                       // [size][3] or null: in place
+  void* stats;                          // vo_map_refine_stats
+};
+// after the lookup has filled w.ent: lists (memset, count, offsets, scan, scatter, order), the refinement, the statistics
+hipError_t launch_map_refine(hipStream_t st, const MapRefineArgs& a, int n_cu);
+
 // ---- epipolar initialisation, device half (epi.hip) ------------------------------------------------------
 size_t epi_workspace_bytes();
 // maxima of both point sets + the 45 sums of A^T A + the number of rows / of pairs with a bad index, into ws:

@@ -768,6 +768,68 @@ VO_HD TriConst tri_constants(const float K[9], const Pose& X) {
   return c;
 }
 
+// ---- structure-only refinement of a landmark (map_refine.hip; both functions also compile for the host) ----------
+// sums of one evaluation: 0..5 H upper triangle row by row ((0,0),(0,1),(0,2),(1,1),(1,2),(2,2)), 6..8 b, 9 the cost
+constexpr int NREF = 10;
+
+// One observation's terms at the point p (map frame), all in double: p_cam = R p + t (Rt: R column-major, then t, the
+// caller's float32 bits), q = K p_cam (K column-major, the full matrix), e = (q0 / q2, q1 / q2) - (mu, mv); J = de / dp;
+// w = min(1, huber / |e|) (huber == 0: 1); acc += w J^T J, w J^T e, rho(e).  Returns whether camera z is > 0 (a NaN is not).
+VO_HD bool map_refine_term(const double K[9], const float Rt[12], const double p[3], double mu, double mv, double huber,
+                           double acc[NREF]) {
+  double pc[3], q[3];
+  for (int r = 0; r < 3; ++r)
+    pc[r] = __builtin_fma((double)Rt[r + 6], p[2], __builtin_fma((double)Rt[r + 3], p[1], __builtin_fma((double)Rt[r], p[0], (double)Rt[9 + r])));
+  for (int r = 0; r < 3; ++r) q[r] = __builtin_fma(K[r + 6], pc[2], __builtin_fma(K[r + 3], pc[1], K[r] * pc[0]));
+  const double iz = 1.0 / q[2];
+  const double u = q[0] * iz, v = q[1] * iz;
+  const double e0 = u - mu, e1 = v - mv;
+  // de / dp_cam = (K row 0 - u K row 2, K row 1 - v K row 2) / q2, then times R
+  double j0[3], j1[3], J0[3], J1[3];
+  for (int c = 0; c < 3; ++c) { j0[c] = (K[3 * c] - u * K[2 + 3 * c]) * iz; j1[c] = (K[1 + 3 * c] - v * K[2 + 3 * c]) * iz; }
+  for (int c = 0; c < 3; ++c) {
+    J0[c] = __builtin_fma(j0[2], (double)Rt[2 + 3 * c], __builtin_fma(j0[1], (double)Rt[1 + 3 * c], j0[0] * (double)Rt[3 * c]));
+    J1[c] = __builtin_fma(j1[2], (double)Rt[2 + 3 * c], __builtin_fma(j1[1], (double)Rt[1 + 3 * c], j1[0] * (double)Rt[3 * c]));
+  }
+  const double r2 = e0 * e0 + e1 * e1;
+  double w = 1.0, rho = r2;
+  if (huber > 0.0) {
+    const double r = sqrt(r2);
+    if (r > huber) { w = huber / r; rho = huber * (2.0 * r - huber); }
+  }
+  const double w0[3] = {w * J0[0], w * J0[1], w * J0[2]}, w1[3] = {w * J1[0], w * J1[1], w * J1[2]};
+  acc[0] += __builtin_fma(w1[0], J1[0], w0[0] * J0[0]);
+  acc[1] += __builtin_fma(w1[0], J1[1], w0[0] * J0[1]);
+  acc[2] += __builtin_fma(w1[0], J1[2], w0[0] * J0[2]);
+  acc[3] += __builtin_fma(w1[1], J1[1], w0[1] * J0[1]);
+  acc[4] += __builtin_fma(w1[1], J1[2], w0[1] * J0[2]);
+  acc[5] += __builtin_fma(w1[2], J1[2], w0[2] * J0[2]);
+  acc[6] += __builtin_fma(w1[0], e1, w0[0] * e0);
+  acc[7] += __builtin_fma(w1[1], e1, w0[1] * e0);
+  acc[8] += __builtin_fma(w1[2], e1, w0[2] * e0);
+  acc[9] += rho;
+  return pc[2] > 0.0;
+}
+
+// x = H^-1 b for the symmetric 3x3 H (upper triangle as above) by an LDL^T in natural order, in double.  False when a pivot is
+// not > 0 (a NaN is not) or the step is not finite.
+VO_HD bool ldlt3_solve(const double H[6], const double b[3], double x[3]) {
+  const double d0 = H[0];
+  if (!(d0 > 0.0)) return false;
+  const double l10 = H[1] / d0, l20 = H[2] / d0;
+  const double d1 = H[3] - l10 * l10 * d0;
+  if (!(d1 > 0.0)) return false;
+  const double l21 = (H[4] - l20 * l10 * d0) / d1;
+  const double d2 = H[5] - l20 * l20 * d0 - l21 * l21 * d1;
+  if (!(d2 > 0.0)) return false;
+  const double y0 = b[0], y1 = b[1] - l10 * y0, y2 = b[2] - l20 * y0 - l21 * y1;
+  x[2] = y2 / d2;
+  x[1] = y1 / d1 - l21 * x[2];
+  x[0] = y0 / d0 - l10 * x[1] - l20 * x[2];
+  const double big = 1.7976931348623157e308;
+  return fabs(x[0]) <= big && fabs(x[1]) <= big && fabs(x[2]) <= big;
+}
+
 #if defined(__HIPCC__)
 // ---- two pieces every kernel file uses (device only) ----------------------------------------------------
 // live rows of a call: *d_n clamped to [0, n_max], or n_max when d_n is null
