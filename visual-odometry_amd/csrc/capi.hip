@@ -107,7 +107,7 @@ struct vo_ctx {
   DevBuf batch_help;  // shared form (fewer problems than CUs): tagged words handed between workgroups
   PicpParams batch_params_host{};        //   its parameter block as last uploaded, and where
   const PicpParams* batch_params_dev = nullptr;
-  DevBuf prune_ws;    // sorted copies / tables of the matcher's sorted variants
+  DevBuf prune_ws;    // sorted copies / tables of the matcher's sorted searches
   DevBuf epi_ws;      // maxima, A^T A and vote counts of vo_estimate_transform
   DevBuf ransac_ws;   // points, hypotheses, counts, mask and inlier pairs of vo_estimate_transform_ransac
   DevBuf pose_ws;     // the same for vo_estimate_pose_ransac
@@ -1222,39 +1222,70 @@ static int picp_batch_prepare(vo_ctx* c, int n_problems, int rows, int cols, int
 }
 
 // ---- matcher ------------------------------------------------------------------------------
-// the sorted variants pay several small launches: worth it from ~4 M candidate pairs on
-static int match_workspace(vo_ctx* c, int variant, int nt, int nq, int n_frames, void** ws) {
+static int match_workspace(vo_ctx* c, MatchPlan plan, int nt, int nq, int n_frames, void** ws) {
   *ws = nullptr;
-  if (variant == 1) return VO_OK;
-  VO_HIP_CHECK(c->prune_ws.ensure(match_workspace_bytes(variant, nt, nq, n_frames), c->stream));
+  if (plan.search == MatchSearch::Scan) return VO_OK;
+  VO_HIP_CHECK(c->prune_ws.ensure(match_workspace_bytes(plan, nt, nq, n_frames), c->stream));
   *ws = c->prune_ws.p;
   return VO_OK;
 }
 
+// The one place where the public mode (vo_match_set_mode: 0 auto, 1 full scan, 2 bucket-pruned scan, 3 cell-hash search, 4 / 5
+// the exact-duplicate pass first, then 2 / 3) becomes a plan.  nt / nq: the larger / the smaller set (ragged: capacity).
+//
 // Auto: full scan for small sets; for one frame the bucket-pruned scan (its LDS-tiled scan is the shorter
 // dependency chain when the GPU is not full: 82 vs 130 us at 50k x 50k); for many frames per call the cell-hash
 // search (25 instead of ~1400 candidates per query: 4.0 vs 4.4 ms per 200 frames, its random accesses hidden
-// by occupancy).  In front of either sorted search auto mode runs the exact-duplicate pass (variants 4 / 5, match.hip
+// by occupancy).  In front of either sorted search auto mode runs the exact-duplicate pass (match.hip
 // "hash-first": appearances are copied from frame to frame, so almost every query has a bitwise copy in the tree, which
 // is its nearest neighbour at distance 0; the search then only sees the queries without one) -- from 8 frames per call on.
 // For one frame the pass (three launches, ~45 us at 50k) pays only when NO query is left over: 55 against 78 us; a tracking
 // sequence brings new landmarks with every frame, and the sorted search it then still needs costs what it costs without
 // the pass (the tree must be sorted for a single open query): 123 against 75 us per frame of the synthetic 200 x 50k
 // sequence.  Modes 4 / 5 ask for the pass at any size.
-// VO_MATCH_AUTO=2|3 forces one of the sorted variants in auto mode, VO_MATCH_HASH=0 leaves the exact-duplicate pass out,
+// VO_MATCH_AUTO=2|3 forces one of the sorted searches in auto mode, VO_MATCH_HASH=0 leaves the exact-duplicate pass out,
 // VO_MATCH_HASH=1 puts it in front of every sorted search.
-static int with_hash(int v, int nt, int n_frames) {
-  static const int env = [] { const char* e = getenv("VO_MATCH_HASH"); return e ? (e[0] == '0' ? 0 : 1) : -1; }();
-  const bool on = env < 0 ? n_frames >= 8 : env == 1;
-  return (on && (v == 2 || v == 3) && match_hash_supported(nt, n_frames)) ? v + 2 : v;
+//
+// Ragged: frames of different sizes: the full scan, or -- from the sizes on where a sorted search pays -- the cell-hash search (its
+// workspace is then laid out for the larger capacity in both roles), with the exact-duplicate pass in front of it like
+// the rule for equal sizes decides; the bucket-pruned scan takes one size only
+static MatchPlan match_plan(const vo_ctx* c, int nt, int nq, int n_frames, bool ragged) {
+  MatchSearch search;
+  bool pass;
+  if (c->match_mode != 0) {
+    static const MatchPlan of_mode[6] = {{}, {MatchSearch::Scan, false}, {MatchSearch::Buckets, false}, {MatchSearch::Cells, false},
+                                         {MatchSearch::Buckets, true}, {MatchSearch::Cells, true}};
+    search = of_mode[c->match_mode].search;
+    pass = of_mode[c->match_mode].hash_first;               // 4 / 5: exact-duplicate pass first, at any size it takes
+  } else {
+    // the full scan: below ~4 M candidate pairs per frame whatever the frame count, and -- a call of one or a few frames, whose
+    // sorted searches are a chain of ~8 small launches (45 us) -- up to 1e8 pairs in the whole call: one frame of up to ~10 000 x
+    // 10 000 points (measured, one frame, full scan against the sorted searches: 5000: 30 / 46 us, 8500: 36 / 48, 10 000: 42 / 49,
+    // 12 000: 60 / 49; tools/match_sizes.py)
+    const double pairs = (double)nt * (double)nq;
+    // (the 1e8 rule is measured for ONE frame only; calls of 2..7 frames keep the 4 M-pairs-per-frame crossover)
+    if (pairs < 4.0e6 || (n_frames <= 1 && pairs < 1.0e8)) return MatchPlan{};
+    static const int forced = [] { const char* e = getenv("VO_MATCH_AUTO"); const int v = e ? atoi(e) : 0; return (v == 2 || v == 3) ? v : 0; }();
+    search = (forced ? forced == 3 : n_frames >= 8) ? MatchSearch::Cells : MatchSearch::Buckets;
+    static const int env = [] { const char* e = getenv("VO_MATCH_HASH"); return e ? (e[0] == '0' ? 0 : 1) : -1; }();
+    pass = env < 0 ? n_frames >= 8 : env == 1;
+  }
+  if (search == MatchSearch::Scan) return MatchPlan{};
+  if (ragged) {
+    if (!match_cells_supported(nt, nt)) return MatchPlan{};
+    search = MatchSearch::Cells;
+  } else if (!match_cells_supported(nt, nq)) {              // the cell-hash search serves sets of up to 1.8 M points
+    search = MatchSearch::Buckets;
+  }
+  return MatchPlan{search, pass && match_hash_supported(nt, n_frames)};
 }
 
 // the two halves of the steering described at vo_ctx::hint_host, around a batched matcher call in automatic mode
 constexpr int HINT_SKIP = 16;
-static int match_hint_before(vo_ctx* c, int variant, bool* skipped) {
+// the plan the call runs: the rule's, or -- while the steering leaves the pass out -- the rule's without the pass
+static MatchPlan match_hint_before(vo_ctx* c, MatchPlan plan) {
   static const bool off = [] { const char* e = getenv("VO_MATCH_HINT"); return e && e[0] == '0'; }();
-  *skipped = false;
-  if (off || c->match_mode != 0 || variant < 4 || c->capturing) return variant;
+  if (off || c->match_mode != 0 || !plan.hash_first || c->capturing) return plan;
   if (c->hint_pending && hipEventQuery(c->hint_ev) == hipSuccess) {
     c->hint_pending = false;
     if (c->hint_of_skipped_call) {
@@ -1266,13 +1297,13 @@ static int match_hint_before(vo_ctx* c, int variant, bool* skipped) {
     }
   }
   (void)hipGetLastError();                        // (hipErrorNotReady of the query is not an error of this call)
-  if (c->hint_skip_left > 0) { --c->hint_skip_left; *skipped = true; return variant - 2; }      // the plain search: same pairs
-  return variant;
+  if (c->hint_skip_left > 0) { --c->hint_skip_left; plan.hash_first = false; }      // the plain search: same pairs
+  return plan;
 }
-// skipped: the call ran without the pass (match_hint_before took it out); best / nq_cap / sizes: its keys
-static void match_hint_after(vo_ctx* c, int variant, bool skipped, const void* ws, int n_frames, const unsigned long long* d_best,
+// plan: what ran; skipped: it ran without the pass because match_hint_before took it out; best / nq_cap / sizes: its keys
+static void match_hint_after(vo_ctx* c, MatchPlan plan, bool skipped, const void* ws, int n_frames, const unsigned long long* d_best,
                              size_t best_stride, int nq_cap, const int* d_n1, const int* d_n2) {
-  if (c->match_mode != 0 || (variant < 4 && !skipped) || c->capturing || !ws || nq_cap <= 0) return;
+  if (c->match_mode != 0 || (!plan.hash_first && !skipped) || c->capturing || !ws || nq_cap <= 0) return;
   if (!c->hint_host) {
     if (hipHostMalloc(reinterpret_cast<void**>(&c->hint_host), 64, hipHostMallocDefault) != hipSuccess ||
         hipMalloc(reinterpret_cast<void**>(&c->hint_dev), 64) != hipSuccess ||
@@ -1292,36 +1323,29 @@ static void match_hint_after(vo_ctx* c, int variant, bool skipped, const void* w
       hipEventRecord(c->hint_ev, c->stream) != hipSuccess) { (void)hipGetLastError(); return; }
   c->hint_pending = true;
 }
-static int match_variant(const vo_ctx* c, int nt, int nq, int n_frames) {
-  const bool cells_ok = match_cells_supported(nt, nq);      // the cell-hash search serves sets of up to 1.8 M points
-  if (c->match_mode != 0) {
-    int m = c->match_mode;
-    const bool hash = m >= 4;                               // 4 / 5: exact-duplicate pass first, at any size it takes
-    if (hash) m -= 2;
-    if (m == 3 && !cells_ok) m = 2;
-    return (hash && match_hash_supported(nt, n_frames)) ? m + 2 : m;
-  }
-  // the full scan: below ~4 M candidate pairs per frame whatever the frame count, and -- a call of one or a few frames, whose
-  // sorted searches are a chain of ~8 small launches (45 us) -- up to 1e8 pairs in the whole call: one frame of up to ~10 000 x
-  // 10 000 points (measured, one frame, full scan against the sorted searches: 5000: 30 / 46 us, 8500: 36 / 48, 10 000: 42 / 49,
-  // 12 000: 60 / 49; tools/match_sizes.py)
-  {
-    const double pairs = (double)nt * (double)nq;
-    // (the 1e8 rule is measured for ONE frame only; calls of 2..7 frames keep the 4 M-pairs-per-frame crossover)
-    if (pairs < 4.0e6 || (n_frames <= 1 && pairs < 1.0e8)) return 1;
-  }
-  static const int forced = [] { const char* e = getenv("VO_MATCH_AUTO"); const int v = e ? atoi(e) : 0; return (v == 2 || v == 3) ? v : 0; }();
-  if (forced) return with_hash((forced == 3 && !cells_ok) ? 2 : forced, nt, n_frames);
-  return with_hash((n_frames >= 8 && cells_ok) ? 3 : 2, nt, n_frames);
-}
 
-// frames of different sizes: the full scan, or -- from the sizes on where a sorted search pays -- the cell-hash search (its
-// workspace is then laid out for the larger capacity in both roles), with the exact-duplicate pass in front of it like
-// match_variant decides; the bucket-pruned scan takes one size only
-static int ragged_variant(const vo_ctx* c, int nt_cap, int q_cap, int n_frames) {
-  const int v = match_variant(c, nt_cap, q_cap, n_frames);
-  if (v == 1 || !match_cells_supported(nt_cap, nt_cap)) return 1;
-  return v >= 4 ? 5 : 3;
+// "Match these frames": the rule's plan, the steering's say on it, the workspace, the launches, the steering's question.
+// The caller has sized c->scratch and c->best.  batched: the frames of a many-frames call, cap1 / cap2 rows apart (d_n1 / d_n2:
+// their sizes, or null) and steered; otherwise the one frame of vo_match_appearances_dev, which is not.
+static int match_frames(vo_ctx* c, bool batched, int n_frames, const float* d_a1, int cap1, const int* d_n1, const float* d_a2,
+                        int cap2, const int* d_n2, float radius, int32_t* d_out_pairs, int* d_n_out) {
+  const int q = cap1 < cap2 ? cap1 : cap2, nt = cap1 > cap2 ? cap1 : cap2;
+  const bool ragged = d_n1 != nullptr;
+  const MatchPlan rule = match_plan(c, nt, q, n_frames, ragged);
+  const MatchPlan plan = batched ? match_hint_before(c, rule) : rule;
+  // (sized for what the rule picks, also while the steering leaves the pass out: the call that brings it back must not have to
+  // grow the workspace -- a device allocation of gigabytes and a synchronisation in the middle of a run)
+  void* ws = nullptr;
+  if (q > 0) if (int r = match_workspace(c, rule, nt, ragged ? nt : q, n_frames, &ws)) return r;
+  unsigned long long* best = c->best.as<unsigned long long>();
+  if (!batched) {
+    VO_HIP_CHECK(launch_match(c->stream, d_a1, cap1, d_a2, cap2, radius, d_out_pairs, d_n_out, best, c->scratch.as<int>(), c->n_cu, ws, plan));
+    return VO_OK;
+  }
+  VO_HIP_CHECK(launch_match_batch(c->stream, d_a1, cap1, 10 * (size_t)cap1, d_a2, cap2, 10 * (size_t)cap2, radius, d_out_pairs,
+                                  (size_t)q, d_n_out, best, c->scratch.as<int>(), c->n_cu, ws, n_frames, plan, d_n1, d_n2));
+  match_hint_after(c, plan, rule.hash_first && !plan.hash_first, ws, n_frames, best, (size_t)q, q, d_n1, d_n2);
+  return VO_OK;
 }
 
 int vo_match_set_mode(vo_ctx* c, int mode) {
@@ -1346,14 +1370,7 @@ int vo_match_appearances_dev(vo_ctx* c, const float* d_a1, int n1, const float* 
   if (int r = set_device(c)) return r;
   if (int r = ensure_scratch(c, nq)) return r;
   VO_HIP_CHECK(c->best.ensure(sizeof(unsigned long long) * (size_t)(nq ? nq : 1), c->stream));
-  // the pruned scan pays ~8 small launches of sorting: worth it from ~4 M candidate pairs on
-  const int nt = n1 > n2 ? n1 : n2;
-  const int variant = match_variant(c, nt, nq, 1);
-  void* ws = nullptr;
-  if (nq > 0) if (int r = match_workspace(c, variant, nt, nq, 1, &ws)) return r;
-  VO_HIP_CHECK(launch_match(c->stream, d_a1, n1, d_a2, n2, radius, d_out_pairs, d_n_out,
-                            c->best.as<unsigned long long>(), c->scratch.as<int>(), c->n_cu, ws, variant));
-  return VO_OK;
+  return match_frames(c, false, 1, d_a1, n1, nullptr, d_a2, n2, nullptr, radius, d_out_pairs, d_n_out);
 }
 
 int vo_match_appearances(vo_ctx* c, const float* a1, int n1, const float* a2, int n2, float radius,
@@ -1395,19 +1412,7 @@ int vo_match_appearances_batch_dev(vo_ctx* c, int n_frames, const float* d_a1, i
   if (int r = set_device(c)) return r;
   VO_HIP_CHECK(c->scratch.ensure(sizeof(int) * compaction_scratch_ints(q) * (size_t)n_frames, c->stream));
   VO_HIP_CHECK(c->best.ensure(sizeof(unsigned long long) * (size_t)(q ? q : 1) * (size_t)n_frames, c->stream));
-  const int nt = cap1 > cap2 ? cap1 : cap2;
-  bool skipped = false;
-  const int variant_rule = d_n1 ? ragged_variant(c, nt, q, n_frames) : match_variant(c, nt, q, n_frames);
-  const int variant = match_hint_before(c, variant_rule, &skipped);
-  // (sized for what the rule picks, also while the steering leaves the pass out: the call that brings it back must not have to
-  // grow the workspace -- a device allocation of gigabytes and a synchronisation in the middle of a run)
-  void* ws = nullptr;
-  if (q > 0) if (int r = match_workspace(c, variant_rule, nt, d_n1 ? nt : q, n_frames, &ws)) return r;
-  VO_HIP_CHECK(launch_match_batch(c->stream, d_a1, cap1, 10 * (size_t)cap1, d_a2, cap2, 10 * (size_t)cap2, radius, d_out_pairs,
-                                  (size_t)q, d_n_out, c->best.as<unsigned long long>(), c->scratch.as<int>(), c->n_cu, ws, n_frames,
-                                  variant, d_n1, d_n2));
-  match_hint_after(c, variant, skipped, ws, n_frames, c->best.as<unsigned long long>(), (size_t)q, q, d_n1, d_n2);
-  return VO_OK;
+  return match_frames(c, true, n_frames, d_a1, cap1, d_n1, d_a2, cap2, d_n2, radius, d_out_pairs, d_n_out);
 }
 
 // ---- batched frames -----------------------------------------------------------------------
@@ -1437,26 +1442,18 @@ static int frames_batch(vo_ctx* c, const vo_frame_batch* b, const vo_frame_sizes
   VO_REQUIRE(aligned8(b->ref_app, b->cur_app, b->ref_pts, b->cur_pts, b->model_pairs, b->matches, b->joined, b->tri_pairs, b->tri_app),
              "device array not on an 8-byte boundary");
   if (int r = set_device(c)) return r;
-  const int nt = b->n_ref > b->n_cur ? b->n_ref : b->n_cur;
   VO_HIP_CHECK(c->scratch.ensure(triangulate_scratch_bytes(q, F), c->stream));    // (covers the counts of the other compactions)
   VO_HIP_CHECK(c->best.ensure(sizeof(unsigned long long) * (size_t)q * (size_t)F, c->stream));
   VO_HIP_CHECK(c->table.ensure(sizeof(unsigned long long) * (size_t)(b->n_ref ? b->n_ref : 1) * (size_t)F, c->stream));
   // ragged frames (sz): the counts of the struct are capacities (= strides), frame f holds sz->n_ref[f] / n_cur[f] points and
   // n_model_pairs[f] model pairs; the matcher (full scan or cell-hash search) picks every frame's roles itself (vo_complete.cpp:15-20)
-  bool skipped = false;
-  const int variant_rule = sz ? ragged_variant(c, nt, q, F) : match_variant(c, nt, q, F);
-  const int variant = match_hint_before(c, variant_rule, &skipped);
-  void* ws = nullptr;                                     // (sized for the rule's pick: see vo_match_appearances_batch_dev)
-  if (int r = match_workspace(c, variant_rule, nt, sz ? nt : q, F, &ws)) return r;
   int* n_match = b->counts;
   int* n_join = b->counts + F;
   int* n_tri = b->counts + 2 * (size_t)F;
   // compute_correspondences_images, all frames                                  vo_complete.cpp:156
-  VO_HIP_CHECK(launch_match_batch(c->stream, b->ref_app, b->n_ref, 10 * (size_t)b->n_ref, b->cur_app, b->n_cur,
-                                  10 * (size_t)b->n_cur, b->radius, b->matches, (size_t)q, n_match,
-                                  c->best.as<unsigned long long>(), c->scratch.as<int>(), c->n_cu, ws, F, variant,
-                                  sz ? sz->n_ref : nullptr, sz ? sz->n_cur : nullptr));
-  match_hint_after(c, variant, skipped, ws, F, c->best.as<unsigned long long>(), (size_t)q, q, sz ? sz->n_ref : nullptr, sz ? sz->n_cur : nullptr);
+  if (int r = match_frames(c, true, F, b->ref_app, b->n_ref, sz ? sz->n_ref : nullptr, b->cur_app, b->n_cur, sz ? sz->n_cur : nullptr,
+                           b->radius, b->matches, n_match))
+    return r;
   // X_curr * triangulated_pc                                                    vo_complete.cpp:159
   // The moved cloud as an output is optional: without it the solver's gather applies X_prev to the points it fetches (the
   // same arithmetic, PointCloud.h:80) and the pass that writes n_model points per frame only to re-read the joined ones
@@ -1551,7 +1548,7 @@ int vo_radius_search_dev(vo_ctx* c, const float* d_tree, int n_tree, const float
   VO_REQUIRE(aligned8(d_tree, d_qry), "device array not on an 8-byte boundary");       // (the cell-hash path loads rows as 8-byte words)
   if (int r = set_device(c)) return r;
   void* ws = nullptr;
-  if (n_tree > 0 && n_q > 0) if (int r = match_workspace(c, 3, n_tree, n_q, 1, &ws)) return r;
+  if (n_tree > 0 && n_q > 0) if (int r = match_workspace(c, MatchPlan{MatchSearch::Cells, false}, n_tree, n_q, 1, &ws)) return r;
   VO_HIP_CHECK(launch_radius_search(c->stream, d_tree, n_tree, d_qry, n_q, radius, d_offsets, d_indices, capacity, ws));
   return VO_OK;
 }
@@ -2060,7 +2057,6 @@ int vo_frames_batch_track_dev(vo_ctx* c, const vo_frame_batch* b, const vo_frame
                       t->tracked_pairs),
              "device array not on an 8-byte boundary");
   if (int r = set_device(c)) return r;
-  const int nt = b->n_ref > b->n_cur ? b->n_ref : b->n_cur;
   // what the caller did not ask for lives in the context: moved cloud | tracked pairs | winners (256-aligned blocks)
   const size_t moved_bytes = b->model_moved ? 0 : up256(sizeof(float) * 3 * (size_t)b->n_model * (size_t)F);
   const size_t pairs_bytes = t->tracked_pairs ? 0 : up256(sizeof(int32_t) * 2 * (size_t)q * (size_t)F);
@@ -2076,20 +2072,13 @@ int vo_frames_batch_track_dev(vo_ctx* c, const vo_frame_batch* b, const vo_frame
   VO_HIP_CHECK(c->scratch.ensure(triangulate_scratch_bytes(q, F), c->stream));
   VO_HIP_CHECK(c->best.ensure(sizeof(unsigned long long) * (size_t)q * (size_t)F, c->stream));
   VO_HIP_CHECK(c->table.ensure(sizeof(unsigned long long) * (size_t)(b->n_ref ? b->n_ref : 1) * (size_t)F, c->stream));
-  bool skipped = false;
-  const int variant_rule = sz ? ragged_variant(c, nt, q, F) : match_variant(c, nt, q, F);
-  const int variant = match_hint_before(c, variant_rule, &skipped);
-  void* ws = nullptr;
-  if (int r = match_workspace(c, variant_rule, nt, sz ? nt : q, F, &ws)) return r;
   int* n_match = b->counts;
   int* n_join = b->counts + F;
   int* n_tri = b->counts + 2 * (size_t)F;
   // 1. match and join, as frames_batch
-  VO_HIP_CHECK(launch_match_batch(c->stream, b->ref_app, b->n_ref, 10 * (size_t)b->n_ref, b->cur_app, b->n_cur,
-                                  10 * (size_t)b->n_cur, b->radius, b->matches, (size_t)q, n_match,
-                                  c->best.as<unsigned long long>(), c->scratch.as<int>(), c->n_cu, ws, F, variant,
-                                  sz ? sz->n_ref : nullptr, sz ? sz->n_cur : nullptr));
-  match_hint_after(c, variant, skipped, ws, F, c->best.as<unsigned long long>(), (size_t)q, q, sz ? sz->n_ref : nullptr, sz ? sz->n_cur : nullptr);
+  if (int r = match_frames(c, true, F, b->ref_app, b->n_ref, sz ? sz->n_ref : nullptr, b->cur_app, b->n_cur, sz ? sz->n_cur : nullptr,
+                           b->radius, b->matches, n_match))
+    return r;
   VO_HIP_CHECK(launch_join_batch(c->stream, b->matches, q, n_match, b->model_pairs, b->n_model_pairs,
                                  sz ? sz->n_model_pairs : nullptr, b->n_ref,
                                  b->joined, n_join, c->table.as<unsigned long long>(), c->scratch.as<int>(), F, (size_t)q,

@@ -146,7 +146,7 @@ __global__ __launch_bounds__(MB) void match_kernel(const float* __restrict__ tre
   }
 }
 
-// ---- pruned variant ---------------------------------------------------------------
+// ---- bucket-pruned scan ---------------------------------------------------------------
 // For large sets the same exact scan runs over a pruned candidate set.  Both
 // sets are counting-sorted by a two-level key: NA coarse cells along the
 // appearance component A of largest spread, NB fine buckets along the component
@@ -577,56 +577,79 @@ __global__ __launch_bounds__(MBP) void match_pruned_kernel(const float* __restri
 }
 
 
-static size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
+// What a call hands to its searches: the two sets, the keys they answer into, the device they run on.  Filled once per call
+// (launch_match_batch; launch_radius_search for its one frame) and passed to the exact-duplicate pass and to every search.
+struct MatchSets {
+  const float* tree; const float* qry;   // the sets in their roles -- ragged: set 1 / set 2, every frame picks its roles itself
+  int nt, nq;                            //   their sizes -- ragged: the capacities of set 1 / set 2
+  size_t tree_stride, qry_stride;        // floats between frames
+  const int* d_n1; const int* d_n2;      // ragged: per-frame sizes of set 1 / set 2 (both or neither)
+  int n_frames;
+  unsigned long long* best; size_t best_stride;   // one key per query, `best_stride` keys between frames
+  int q;                                 // queries per frame, at most (= the room per frame in best)
+  int tree_is_1;                         // set 1 is the tree (ragged: 1 -- the pairs are written in the sets' own order)
+  int n_cu;
+  bool ragged() const { return d_n1 != nullptr; }
+  int big() const { return ragged() && nq > nt ? nq : nt; }   // the largest tree a frame can have
+};
+// What the exact-duplicate pass leaves for the search behind it: empty (no pass ran: every query is open) or complete.
+struct HashHandoff {
+  const int* unres = nullptr;       // [n_frames] queries the pass left open
+  int* todo = nullptr;              // [n_frames] the sorted search's share of them (open_collect_kernel)
+  const int* open_list = nullptr;   // [n_frames][OPEN_MAX] the open queries' indices
+};
 
-// per-frame block (sorted records, histograms, bucket starts, parameters)
-static size_t match_frame_ws_bytes(int nt, int nq) {
-  return align256(sizeof(float) * 12 * ((size_t)nt + (size_t)nq) +
-                  sizeof(int) * ((size_t)SORT_BLOCKS * 2 * NBUCKET + 2 * (NBUCKET + 1) + 8) + sizeof(BucketParams) + 512);
+// workspace of the bucket-pruned scan: the min/max words of all frames first (128 B each), then the per-frame blocks (sorted
+// records, histograms, bucket starts, parameters: all offsets multiples of 16 bytes) -- frame 0's below, frame f lives
+// f * frame_bytes further.  ws may be null: the walk then only measures.
+struct PrunedWs { unsigned* mm; float *tree_rec, *qry_rec; int *block_hist, *starts; BucketParams* bp; size_t frame_bytes, total; };
+static PrunedWs pruned_ws_layout(void* ws, int nt, int nq, int n_frames) {
+  const size_t frame0 = up256(128 * (size_t)n_frames);
+  size_t o = frame0;
+  const auto take = [&](size_t bytes) -> void* { o += bytes; return WsCarver::within<char>(ws, o - bytes); };
+  PrunedWs w;
+  w.mm = static_cast<unsigned*>(ws);
+  w.tree_rec = static_cast<float*>(take(sizeof(float) * 12 * (size_t)nt));
+  w.qry_rec = static_cast<float*>(take(sizeof(float) * 12 * (size_t)nq));
+  w.block_hist = static_cast<int*>(take(sizeof(int) * (size_t)SORT_BLOCKS * 2 * NBUCKET));
+  w.starts = static_cast<int*>(take(sizeof(int) * (2 * (NBUCKET + 1) + 6)));
+  w.bp = static_cast<BucketParams*>(take(sizeof(BucketParams)));
+  w.frame_bytes = up256(o - frame0 + 2 * sizeof(int) + 512);   // (two ints and 512 bytes of slack that nothing uses)
+  w.total = frame0 + (size_t)n_frames * w.frame_bytes;
+  return w;
 }
-// whole workspace: the min/max words of all frames first (128 B each), then the per-frame blocks
-size_t match_pruned_workspace_bytes(int nt, int nq, int n_frames) {
-  return align256(128 * (size_t)n_frames) + (size_t)n_frames * match_frame_ws_bytes(nt, nq);
-}
+size_t match_pruned_workspace_bytes(int nt, int nq, int n_frames) { return pruned_ws_layout(nullptr, nt, nq, n_frames).total; }
 
-static hipError_t launch_match_pruned(hipStream_t st, const float* tree, int nt, const float* qry, int nq,
-                                      float radius, float r2, unsigned long long* d_best, void* ws, int n_cu,
-                                      int n_frames, size_t tree_stride, size_t qry_stride, size_t best_stride,
-                                      const int* d_unres = nullptr) {
-  // workspace carve of frame 0 (all offsets multiples of 16 bytes); frame f lives ws_stride bytes further
-  unsigned* mm = static_cast<unsigned*>(ws);
-  char* p = static_cast<char*>(ws) + align256(128 * (size_t)n_frames);
-  float* tree_rec = reinterpret_cast<float*>(p); p += sizeof(float) * 12 * (size_t)nt;
-  float* qry_rec = reinterpret_cast<float*>(p); p += sizeof(float) * 12 * (size_t)nq;
-  int* block_hist = reinterpret_cast<int*>(p); p += sizeof(int) * (size_t)SORT_BLOCKS * 2 * NBUCKET;
-  int* starts = reinterpret_cast<int*>(p); p += sizeof(int) * (2 * (NBUCKET + 1) + 6);
-  BucketParams* bp = reinterpret_cast<BucketParams*>(p);
+static hipError_t launch_match_pruned(hipStream_t st, const MatchSets& s, float radius, float r2, void* ws, const int* d_unres) {
+  const float* tree = s.tree; const float* qry = s.qry;
+  const int nt = s.nt, nq = s.nq, n_frames = s.n_frames;
+  const PrunedWs w = pruned_ws_layout(ws, nt, nq, n_frames);
   MatchStrides ms;
-  ms.tree = tree_stride; ms.qry = qry_stride; ms.best = best_stride;
-  ms.ws = n_frames > 1 ? match_frame_ws_bytes(nt, nq) : 0;
+  ms.tree = s.tree_stride; ms.qry = s.qry_stride; ms.best = s.best_stride;
+  ms.ws = n_frames > 1 ? w.frame_bytes : 0;
   ms.mm = 128;
-  ms.unres = d_unres; ms.best0 = d_best;
+  ms.unres = d_unres; ms.best0 = s.best;
   const unsigned Z = (unsigned)n_frames;
-  hipError_t e = hipMemsetAsync(mm, 0xff, 128 * (size_t)n_frames, st);
+  hipError_t e = hipMemsetAsync(w.mm, 0xff, 128 * (size_t)n_frames, st);
   if (e != hipSuccess) return e;
   const int st_t = (nt + 4095) / 4096 > 0 ? (nt + 4095) / 4096 : 1, st_q = (nq + 4095) / 4096 > 0 ? (nq + 4095) / 4096 : 1;   // <= 4096 rows per set
   const int g = ((nt + st_t - 1) / st_t + (nq + st_q - 1) / st_q + 255) / 256;
-  hipLaunchKernelGGL(match_minmax_kernel, dim3(g > 0 ? g : 1, 1, Z), dim3(256), 0, st, tree, nt, st_t, qry, nq, st_q, mm, ms);
-  hipLaunchKernelGGL(match_bucket_hist_kernel, dim3(SORT_BLOCKS, 1, Z), dim3(256), 0, st, tree, nt, qry, nq, mm, radius,
-                     bp, block_hist, ms);
-  hipLaunchKernelGGL(match_bucket_offsets_kernel, dim3(2, 1, Z), dim3(NBUCKET), 0, st, block_hist, starts, ms);
-  hipLaunchKernelGGL(match_bucket_place_kernel, dim3(SORT_BLOCKS, 1, Z), dim3(256), 0, st, tree, nt, qry, nq, bp,
-                     block_hist, tree_rec, qry_rec, d_best, r2, ms);
+  hipLaunchKernelGGL(match_minmax_kernel, dim3(g > 0 ? g : 1, 1, Z), dim3(256), 0, st, tree, nt, st_t, qry, nq, st_q, w.mm, ms);
+  hipLaunchKernelGGL(match_bucket_hist_kernel, dim3(SORT_BLOCKS, 1, Z), dim3(256), 0, st, tree, nt, qry, nq, w.mm, radius,
+                     w.bp, w.block_hist, ms);
+  hipLaunchKernelGGL(match_bucket_offsets_kernel, dim3(2, 1, Z), dim3(NBUCKET), 0, st, w.block_hist, w.starts, ms);
+  hipLaunchKernelGGL(match_bucket_place_kernel, dim3(SORT_BLOCKS, 1, Z), dim3(256), 0, st, tree, nt, qry, nq, w.bp,
+                     w.block_hist, w.tree_rec, w.qry_rec, s.best, r2, ms);
   const int qblocks = (nq + MBP * QPP - 1) / (MBP * QPP) + NA;   // upper bound: workgroups are aligned to A-cells
-  int nchunks = (16 * (n_cu > 0 ? n_cu : 256) + qblocks * n_frames - 1) / (qblocks * n_frames);
+  int nchunks = (16 * s.n_cu + qblocks * n_frames - 1) / (qblocks * n_frames);
   if (nchunks < 1) nchunks = 1;
   if (nchunks > 64) nchunks = 64;
-  hipLaunchKernelGGL(match_pruned_kernel, dim3(qblocks, nchunks, Z), dim3(MBP), 0, st, tree_rec, nt, qry_rec, nq, starts,
-                     bp, nchunks, r2, d_best, ms);
+  hipLaunchKernelGGL(match_pruned_kernel, dim3(qblocks, nchunks, Z), dim3(MBP), 0, st, w.tree_rec, nt, w.qry_rec, nq, w.starts,
+                     w.bp, nchunks, r2, s.best, ms);
   return hipGetLastError();
 }
 
-// ---- cell-hash variant ---------------------------------------------------------------
+// ---- cell-hash search ----------------------------------------------------------------
 // Exact search over a 4-D grid.  Four appearance components (largest spreads, taken from components 4..9
 // when those are not much flatter, so the filter on components 0..3 keeps its selectivity) are cut into
 // nc_k = clamp(floor(spread_k / R), 1, 20) cells of width >= R each (R = 1.001 radius).  The spreads come
@@ -684,7 +707,7 @@ constexpr int CELL_SAMPLE = 2048;        // points per set that define the grid'
 #endif
 constexpr int CELL_SLICE = VO_CELL_SLICE;         // points per level-1 workgroup: 7 per thread, ordered in 28 KiB of LDS
 constexpr int CELL_PPT = CELL_SLICE / 256;
-constexpr int CELL_MAX_SLICES = 1024;    // per set: the cell variant serves sets of up to 1 835 008 points (beyond: pruned scan)
+constexpr int CELL_MAX_SLICES = 1024;    // per set: the cell-hash search serves sets of up to 1 835 008 points (beyond: pruned scan)
 #ifndef VO_CS_NB
 #define VO_CS_NB 3
 #endif
@@ -784,7 +807,7 @@ __device__ __forceinline__ float pick10(const float* v, int k) {
   return __uint_as_float(x);
 }
 
-// per-frame workspace of the cell variant (bytes, every block 256-aligned)
+// per-frame workspace of the cell-hash search (bytes, every block 256-aligned)
 struct CellWs {
   size_t cp, dir, t1, ql1, coarse_start, tree_word, tree_idx, q1, start_t, start_rel, open_start, open_rec, total;
 };
@@ -800,21 +823,21 @@ static int cell_slices(int n) { const int s = (n + CELL_SLICE - 1) / CELL_SLICE;
 static CellWs cell_ws_layout(int nt, int nq) {
   CellWs w;
   size_t o = 0;
-  w.cp = o; o += align256(sizeof(CellParams));
-  w.dir = o; o += align256(sizeof(unsigned) * (size_t)(cell_slices(nt) + cell_slices(nq)) * HCPAD);   // (count << 16 | offset) per (slice, bin)
-  w.t1 = o; o += align256(sizeof(uint4) * (size_t)nt);                // level 1: (filter word, original index, fine | coarse << 16, -) in slice order
-  w.ql1 = o; o += align256(sizeof(uint4) * (size_t)nq);               //   query records (below) in slice order
-  w.coarse_start = o; o += align256(sizeof(int) * 2 * (HCPAD + 1));
-  w.tree_word = o; o += align256(sizeof(unsigned) * (size_t)nt);      // sorted tree: filter word,
-  w.tree_idx = o; o += align256(sizeof(int) * (size_t)nt);            //   original index
-  w.q1 = o; o += align256(sizeof(uint4) * (size_t)nq);                // query records grouped by coarse bin: (original index, filter word,
+  w.cp = o; o += up256(sizeof(CellParams));
+  w.dir = o; o += up256(sizeof(unsigned) * (size_t)(cell_slices(nt) + cell_slices(nq)) * HCPAD);   // (count << 16 | offset) per (slice, bin)
+  w.t1 = o; o += up256(sizeof(uint4) * (size_t)nt);                // level 1: (filter word, original index, fine | coarse << 16, -) in slice order
+  w.ql1 = o; o += up256(sizeof(uint4) * (size_t)nq);               //   query records (below) in slice order
+  w.coarse_start = o; o += up256(sizeof(int) * 2 * (HCPAD + 1));
+  w.tree_word = o; o += up256(sizeof(unsigned) * (size_t)nt);      // sorted tree: filter word,
+  w.tree_idx = o; o += up256(sizeof(int) * (size_t)nt);            //   original index
+  w.q1 = o; o += up256(sizeof(uint4) * (size_t)nq);                // query records grouped by coarse bin: (original index, filter word,
                                                                       //   box = cell(q - R) per component : 5 bits each, width - 1 : 2 bits each, coarse bin)
-  w.start_t = o; o += align256(sizeof(int) * (size_t)HCOARSE * SROW); // first tree slot of every cell, rows of SROW per coarse bin
-  w.start_rel = o; o += align256(sizeof(unsigned short) * (size_t)HCOARSE * HROW);   // the same relative to the bin's first slot
+  w.start_t = o; o += up256(sizeof(int) * (size_t)HCOARSE * SROW); // first tree slot of every cell, rows of SROW per coarse bin
+  w.start_rel = o; o += up256(sizeof(unsigned short) * (size_t)HCOARSE * HROW);   // the same relative to the bin's first slot
                                                                       //   (16-bit, rows of HROW: what the search stages)
   // few open queries behind the exact-duplicate pass: their records ordered by coarse bin (open_collect_kernel -> open_scan_kernel)
-  w.open_start = o; o += align256(sizeof(unsigned short) * OPEN_SROW_WS);       // 16-bit first slot of every bin (c0, c1, c2)
-  w.open_rec = o; o += align256(sizeof(unsigned) * 2 * OPEN_RECS);              // filter words, then original indices
+  w.open_start = o; o += up256(sizeof(unsigned short) * OPEN_SROW_WS);       // 16-bit first slot of every bin (c0, c1, c2)
+  w.open_rec = o; o += up256(sizeof(unsigned) * 2 * OPEN_RECS);              // filter words, then original indices
   w.total = o;
   return w;
 }
@@ -1156,7 +1179,7 @@ __global__ __launch_bounds__(256) void cell_fine_kernel(CellArgs a) {
   // source slot of element i: the last run that starts at or before i (empty runs share a start with their successor and
   // are skipped by "last")
   auto source_of = [&](int set, int i, int nr) {
-    int lo = 0, hi = nr;                                  // invariant: s_rs[lo] <= i < s_rs[hi]
+    int lo = 0, hi = nr;                                  // throughout: s_rs[lo] <= i < s_rs[hi]
     while (hi - lo > 1) {
       const int mid = (lo + hi) >> 1;
       if (s_rs[set][mid] <= i) lo = mid; else hi = mid;
@@ -1537,7 +1560,7 @@ __global__ __launch_bounds__(CS_THREADS, CS_THREADS * CS_WG_PER_CU / 256) void c
 // Queries without a copy (new landmarks, noise, unsafe rows; rows a full part could not take) keep the "no hit" key and are
 // counted per frame; the general search that follows (bucket-pruned scan or cell-hash search) then sorts in only those queries
 // and is skipped altogether by a frame that has none.  Results are identical to the general search alone for every input
-// (tests/test_gpu_parity.py::test_matcher_variants_agree, tests/test_gpu_hashfirst.py).
+// (tests/test_gpu_parity.py, tests/test_gpu_hashfirst.py).
 constexpr unsigned HJ_EMPTY = 0xffffffffu;
 #ifndef VO_HJ_THREADS
 #define VO_HJ_THREADS 768
@@ -1973,7 +1996,7 @@ __global__ __launch_bounds__(256) void hash_open_kernel(HashArgs a) {
 // ONCE past them (open_scan_kernel): a tree point t can only be within the radius of queries whose cells lie in
 // [cell(t - R), cell(t + R)] per component -- fl(t - R) <= q <= fl(t + R) for every float q with |t - q| < r < R because
 // rounding is monotone, and the cell function is monotone -- i.e. of <= 3 runs of the ordered list (contiguous along c1).  Every
-// candidate goes through the search's filter (one v_sad_u8 on the quantised components 0..3, proof at the cell variant) and a
+// candidate goes through the search's filter (one v_sad_u8 on the quantised components 0..3, proof at the cell-hash search) and a
 // survivor is decided from the two full rows in the reference's operation order; the result enters the query's key by
 // atomicMin on (distance bits, tree index) -- the smallest distance, the lowest index among equals, strictly inside the radius:
 // the reference's rule, whatever the order in which tree points arrive.  ~9 M / 400 candidates per tree point (M open queries):
@@ -2234,50 +2257,65 @@ static bool hash_plan(int nt, HashPlan& p) {
   p.qcap = fill[l] + fill[l] / 2;                    // a part's queue: 1.5 x its average share (table load <= 0.59)
   return true;
 }
-static size_t hash_table_bytes(const HashPlan& p) { return align256(sizeof(unsigned) * ((size_t)1 << (p.log2s + p.log2p))); }
-static size_t hash_queue_bytes(const HashPlan& p) { return align256(sizeof(uint2) * ((size_t)p.qcap << p.log2p)); }
-static size_t hash_head_bytes(int n_frames) { return align256(sizeof(int) * (size_t)n_frames * (3 + HJ_MAXP)); }   // open-query counters, the sorted search's share of them (todo), sample masks, queue cursors
-// workspace of the pass: the counters (zeroed per call), then the tables, then the queues
-static size_t hash_list_bytes(int n_frames) { return align256(sizeof(int) * (size_t)n_frames * OPEN_MAX); }   // the open queries' indices
-static size_t hash_ws_bytes(int nt, int n_frames) {
-  HashPlan p;
-  if (!hash_plan(nt, p)) return 0;
-  return hash_head_bytes(n_frames) + hash_list_bytes(n_frames) + (hash_table_bytes(p) + hash_queue_bytes(p)) * (size_t)n_frames;
+static size_t hash_table_bytes(const HashPlan& p) { return up256(sizeof(unsigned) * ((size_t)1 << (p.log2s + p.log2p))); }
+static size_t hash_queue_bytes(const HashPlan& p) { return up256(sizeof(uint2) * ((size_t)p.qcap << p.log2p)); }
+// workspace of the pass: the head (ints, zeroed per call: per frame the open-query counter, the sorted search's share of it,
+// the sample mask, then the queue cursors of all frames), the open queries' indices, the tables, the queues.  The head and the
+// list do not depend on the plan (launch_match_hint reads the masks without one).
+struct HashWs {
+  int* unres; int* todo; unsigned* sample_mask; int* cursors;
+  int* open_list;
+  unsigned* tables; uint2* queues;
+  size_t head_bytes;        // what a call zeroes
+  size_t bytes;
+};
+static HashWs hash_ws_layout(void* ws, int n_frames, const HashPlan& p = HashPlan{}) {
+  WsCarver c(ws);
+  HashWs w;
+  w.head_bytes = sizeof(int) * (size_t)n_frames * (3 + HJ_MAXP);
+  w.unres = c.take<int>(w.head_bytes);
+  w.todo = WsCarver::within<int>(w.unres, sizeof(int) * (size_t)n_frames);
+  w.sample_mask = WsCarver::within<unsigned>(w.unres, sizeof(int) * 2 * (size_t)n_frames);
+  w.cursors = WsCarver::within<int>(w.unres, sizeof(int) * 3 * (size_t)n_frames);
+  w.open_list = c.take<int>(sizeof(int) * (size_t)n_frames * OPEN_MAX);
+  w.tables = c.take<unsigned>(hash_table_bytes(p) * (size_t)n_frames);
+  w.queues = c.take<uint2>(hash_queue_bytes(p) * (size_t)n_frames);
+  w.bytes = c.bytes;
+  return w;
 }
 bool match_hash_supported(int nt, int n_frames) { (void)n_frames; HashPlan p; return hash_plan(nt, p); }
-size_t match_hash_workspace_bytes(int nt, int n_frames) { return hash_ws_bytes(nt, n_frames); }
-
-// (tree, qry, nt, nq): the two sets in their roles, or (set 1, set 2, capacities) with the per-frame sizes d_n1 / d_n2
-static hipError_t launch_hash_first(hipStream_t st, const float* tree, int nt, const float* qry, int nq, float r2,
-                                    unsigned long long* d_best, void* ws, int n_frames, size_t tree_stride, size_t qry_stride,
-                                    size_t best_stride, const int* d_n1, const int* d_n2, int** d_unres_out, int32_t* d_out_pairs,
-                                    size_t out_stride, int tree_is_1) {
+size_t match_hash_workspace_bytes(int nt, int n_frames) {
   HashPlan p;
-  const int nt_plan = d_n1 ? (nt > nq ? nt : nq) : nt;
-  if (!hash_plan(nt_plan, p)) return hipErrorInvalidValue;
+  return hash_plan(nt, p) ? hash_ws_layout(nullptr, n_frames, p).bytes : 0;
+}
+
+// out_pairs (or null) / out_stride: where the pass writes the pairs of a frame it answers completely.  *open: what it leaves to
+// the search behind it -- left empty with hipErrorNotSupported, for sizes the pass does not take
+static hipError_t launch_hash_first(hipStream_t st, const MatchSets& s, float r2, void* ws, int32_t* d_out_pairs, size_t out_stride,
+                                    HashHandoff* open) {
+  HashPlan p;
+  const int n_frames = s.n_frames, big = s.big();   // the plan is made for the largest tree a frame can have
+  if (!hash_plan(big, p)) return hipErrorInvalidValue;
+  const HashWs w = hash_ws_layout(ws, n_frames, p);
   HashArgs a;
-  a.tree = tree; a.qry = qry; a.nt = nt; a.nq = nq;
-  a.tree_stride = tree_stride; a.qry_stride = qry_stride; a.best_stride = best_stride;
-  a.d_n1 = d_n1; a.d_n2 = d_n2;
-  a.unres = static_cast<int*>(ws);
-  a.sample_mask = reinterpret_cast<unsigned*>(a.unres + 2 * (size_t)n_frames);   // (unres + n_frames: todo[], written by open_collect_kernel)
-  a.cursors = a.unres + 3 * (size_t)n_frames;
-  a.open_list = reinterpret_cast<int*>(static_cast<char*>(ws) + hash_head_bytes(n_frames));
-  a.tables = reinterpret_cast<unsigned*>(static_cast<char*>(ws) + hash_head_bytes(n_frames) + hash_list_bytes(n_frames));
+  a.tree = s.tree; a.qry = s.qry; a.nt = s.nt; a.nq = s.nq;
+  a.tree_stride = s.tree_stride; a.qry_stride = s.qry_stride; a.best_stride = s.best_stride;
+  a.d_n1 = s.d_n1; a.d_n2 = s.d_n2;
+  a.unres = w.unres; a.sample_mask = w.sample_mask; a.cursors = w.cursors; a.open_list = w.open_list;
+  a.tables = w.tables;
   a.tables_stride = hash_table_bytes(p) / sizeof(unsigned);
-  a.queues = reinterpret_cast<uint2*>(a.tables + a.tables_stride * (size_t)n_frames);
+  a.queues = w.queues;
   a.qcap = p.qcap;
-  a.hblocks = (nt_plan + 255) / 256;
-  hipError_t e0 = hipMemsetAsync(ws, 0, sizeof(int) * (size_t)n_frames * (3 + HJ_MAXP), st);
+  a.hblocks = (big + 255) / 256;
+  hipError_t e0 = hipMemsetAsync(ws, 0, w.head_bytes, st);
   if (e0 != hipSuccess) return e0;
-  a.best = d_best; a.r2 = r2;
-  a.out_pairs = d_out_pairs; a.out_stride = out_stride; a.tree_is_1 = tree_is_1;
+  a.best = s.best; a.r2 = r2;
+  a.out_pairs = d_out_pairs; a.out_stride = out_stride; a.tree_is_1 = s.tree_is_1;
   a.n_frames = n_frames; a.log2p = p.log2p; a.ib = p.ib;
-  const int q_cap = d_n1 ? (nt < nq ? nt : nq) : nq;       // ragged: either set may be the queries, never more than the smaller capacity
-  a.qblocks = (q_cap + 256 * HJ_Q - 1) / (256 * HJ_Q);
+  a.qblocks = (s.q + 256 * HJ_Q - 1) / (256 * HJ_Q);     // (ragged: either set may be the queries, never more than the smaller capacity)
   a.queue_stride = (size_t)p.qcap << p.log2p;
   a.seg_counts = a.qblocks * 256 * HJ_Q;                  // (4 (seg_counts + qblocks) <= 8 queue_stride: a queue holds 1.5 x the tree)
-  if (4 * ((size_t)a.seg_counts + (size_t)a.qblocks) > 8 * a.queue_stride) { *d_unres_out = nullptr; return hipErrorNotSupported; }   // (unreachable while nq <= nt; the caller then runs the plain search)
+  if (4 * ((size_t)a.seg_counts + (size_t)a.qblocks) > 8 * a.queue_stride) return hipErrorNotSupported;   // (unreachable while nq <= nt; the caller then runs the plain search)
   const dim3 gb(xcd_grid(1 << p.log2p, n_frames)), gp(xcd_grid(a.qblocks, n_frames)), tb(HJ_THREADS);
   hipLaunchKernelGGL(hash_rows_kernel, dim3(xcd_grid(a.hblocks, n_frames)), dim3(256), 0, st, a);
   switch (p.log2s) {
@@ -2291,7 +2329,7 @@ static hipError_t launch_hash_first(hipStream_t st, const float* tree, int nt, c
              hipLaunchKernelGGL(hash_probe_kernel<15>, gp, dim3(256), 0, st, a); break;
   }
   hipLaunchKernelGGL(hash_open_kernel, dim3((unsigned)n_frames), dim3(256), 0, st, a);
-  *d_unres_out = a.unres;
+  open->unres = w.unres; open->todo = w.todo; open->open_list = w.open_list;
   return hipGetLastError();
 }
 
@@ -2325,43 +2363,38 @@ hipError_t launch_match_hint_from_best(hipStream_t st, const unsigned long long*
   return hipGetLastError();
 }
 hipError_t launch_match_hint(hipStream_t st, const void* d_prune_ws, int n_frames, int* d_out) {
-  const unsigned* masks = reinterpret_cast<const unsigned*>(static_cast<const int*>(d_prune_ws) + 2 * (size_t)n_frames);
+  const unsigned* masks = hash_ws_layout(const_cast<void*>(d_prune_ws), n_frames).sample_mask;
   hipLaunchKernelGGL(hash_hint_kernel, dim3(1), dim3(256), 0, st, masks, n_frames, d_out);
   return hipGetLastError();
 }
 
-// compute units of the device the running call targets (launch_match_batch sets it from its n_cu argument; the radius search,
-// which has none, keeps the last value or MI355X's 256)
-static thread_local int t_n_cu = 256;
-static hipError_t launch_cells_sort(hipStream_t st, CellArgs& a, const float* tree, int nt, const float* qry, int nq,
-                                    float radius, float r2, unsigned long long* d_best, void* ws, int n_frames,
-                                    size_t tree_stride, size_t qry_stride, size_t best_stride, const int* d_n1 = nullptr,
-                                    const int* d_n2 = nullptr, const int* d_unres = nullptr, int* d_todo = nullptr, const int* d_open_list = nullptr) {
-  a.tree = tree; a.qry = qry; a.nt = nt; a.nq = nq;
-  a.d_n1 = d_n1; a.d_n2 = d_n2; a.unres = d_unres; a.todo = nullptr; a.open_div = 0; a.open_list = nullptr;
+// bounds, [the open-query route,] level 1, offsets, level 2: leaves `a` ready for a search kernel
+static hipError_t launch_cells_sort(hipStream_t st, CellArgs& a, const MatchSets& s, float radius, float r2, void* ws,
+                                    const HashHandoff& open) {
+  const int n_frames = s.n_frames, big = s.big();
+  a.tree = s.tree; a.qry = s.qry; a.nt = s.nt; a.nq = s.nq;
+  a.d_n1 = s.d_n1; a.d_n2 = s.d_n2; a.unres = open.unres; a.todo = nullptr; a.open_div = 0; a.open_list = nullptr;
   a.ws = static_cast<char*>(ws);
-  if (d_n1) { const int cap = nt > nq ? nt : nq; a.w = cell_ws_layout(cap, cap); }   // ragged: either set may play either role
-  else a.w = cell_ws_layout(nt, nq);
-  a.ws_stride = a.w.total; a.tree_stride = tree_stride; a.qry_stride = qry_stride; a.best_stride = best_stride;
+  a.w = s.ragged() ? cell_ws_layout(big, big) : cell_ws_layout(s.nt, s.nq);   // ragged: either set may play either role
+  a.ws_stride = a.w.total; a.tree_stride = s.tree_stride; a.qry_stride = s.qry_stride; a.best_stride = s.best_stride;
   a.n_frames = n_frames;
-  a.tb = cell_slices(d_n1 ? (nt > nq ? nt : nq) : nt); a.qb = cell_slices(d_n1 ? (nt > nq ? nt : nq) : nq);
-  a.radius = radius; a.r2 = r2; a.best = d_best;
+  a.tb = cell_slices(big); a.qb = cell_slices(s.ragged() ? big : s.nq);
+  a.radius = radius; a.r2 = r2; a.best = s.best;
   a.rs_offsets = nullptr; a.rs_indices = nullptr; a.rs_capacity = 0;
   const unsigned Z = (unsigned)n_frames;
   hipLaunchKernelGGL(cell_bounds_kernel, dim3(Z), dim3(1024), 0, st, a);
-  if (d_unres && d_todo && d_open_list) {
+  if (open.unres) {
     // frames with few open queries: the tree streamed past them; the sorted search below then sees todo[] instead of unres[]
-    a.todo = d_todo; a.open_div = OPEN_DIV_DEFAULT; a.open_list = d_open_list;
-    const int big = d_n1 ? (nt > nq ? nt : nq) : nt;
+    a.todo = open.todo; a.open_div = OPEN_DIV_DEFAULT; a.open_list = open.open_list;
     // ~4 workgroups per CU over the call, so that the staging round trip at a workgroup's start is a small part of it
     const int runs = (big + 63) / 64;
-    int tblocks = (4 * t_n_cu + n_frames - 1) / n_frames;
+    int tblocks = (4 * s.n_cu + n_frames - 1) / n_frames;
     const int tb_max = (runs + OPEN_SCAN_WAVES - 1) / OPEN_SCAN_WAVES;
     tblocks = tblocks > tb_max ? tb_max : tblocks;
     const int runs_per_wave = (runs + tblocks * OPEN_SCAN_WAVES - 1) / (tblocks * OPEN_SCAN_WAVES);
     hipLaunchKernelGGL(open_collect_kernel, dim3(Z), dim3(OPEN_THREADS), 0, st, a);
     hipLaunchKernelGGL(open_scan_kernel, dim3(xcd_grid(tblocks, n_frames)), dim3(OPEN_SCAN_THREADS), 0, st, a, tblocks, runs_per_wave);
-    a.unres = d_todo;
+    a.unres = open.todo;
   }
   hipLaunchKernelGGL(cell_place_kernel, dim3(xcd_grid(a.tb + a.qb, n_frames)), dim3(256), 0, st, a);
   hipLaunchKernelGGL(cell_offsets_kernel, dim3(2, 1, Z), dim3(HCPAD), 0, st, a);
@@ -2369,15 +2402,11 @@ static hipError_t launch_cells_sort(hipStream_t st, CellArgs& a, const float* tr
   return hipGetLastError();
 }
 
-static hipError_t launch_match_cells(hipStream_t st, const float* tree, int nt, const float* qry, int nq,
-                                     float radius, float r2, unsigned long long* d_best, void* ws, int n_frames,
-                                     size_t tree_stride, size_t qry_stride, size_t best_stride, const int* d_n1 = nullptr,
-                                     const int* d_n2 = nullptr, const int* d_unres = nullptr, int* d_todo = nullptr, const int* d_open_list = nullptr) {
+static hipError_t launch_match_cells(hipStream_t st, const MatchSets& s, float radius, float r2, void* ws, const HashHandoff& open) {
   CellArgs a;
-  hipError_t e = launch_cells_sort(st, a, tree, nt, qry, nq, radius, r2, d_best, ws, n_frames, tree_stride, qry_stride,
-                                   best_stride, d_n1, d_n2, d_unres, d_todo, d_open_list);
+  hipError_t e = launch_cells_sort(st, a, s, radius, r2, ws, open);
   if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(cell_search_kernel<0>, dim3(xcd_grid(HNC * CS_STRIPS, n_frames)), dim3(CS_THREADS), 0, st, a);
+  hipLaunchKernelGGL(cell_search_kernel<0>, dim3(xcd_grid(HNC * CS_STRIPS, s.n_frames)), dim3(CS_THREADS), 0, st, a);
   return hipGetLastError();
 }
 
@@ -2386,8 +2415,11 @@ static hipError_t launch_match_cells(hipStream_t st, const float* tree, int nt, 
 hipError_t launch_radius_search(hipStream_t st, const float* d_tree, int nt, const float* d_qry, int nq, float radius,
                                 int* d_offsets, int32_t* d_indices, int capacity, void* ws) {
   if (nq <= 0 || nt <= 0) return hipMemsetAsync(d_offsets, 0, sizeof(int) * (size_t)((nq > 0 ? nq : 0) + 1), st);
+  // one frame, no keys; no exact-duplicate pass in front, so the open-query route is never taken and no launch depends on
+  // the CU count
+  const MatchSets s{d_tree, d_qry, nt, nq, 0, 0, nullptr, nullptr, 1, nullptr, 0, nq, 1, 0};
   CellArgs a;
-  hipError_t e = launch_cells_sort(st, a, d_tree, nt, d_qry, nq, radius, radius * radius, nullptr, ws, 1, 0, 0, 0);
+  hipError_t e = launch_cells_sort(st, a, s, radius, radius * radius, ws, HashHandoff{});
   if (e != hipSuccess) return e;
   a.rs_offsets = d_offsets; a.rs_indices = d_indices; a.rs_capacity = capacity;
   hipLaunchKernelGGL(cell_search_kernel<1>, dim3(xcd_grid(HNC * CS_STRIPS, 1)), dim3(CS_THREADS), 0, st, a);
@@ -2397,107 +2429,78 @@ hipError_t launch_radius_search(hipStream_t st, const float* d_tree, int nt, con
   return hipGetLastError();
 }
 
-// n_frames frames with identical set sizes; frame f reads a1 + f*a1_stride etc.  d_prune_ws holds
-// match_pruned_workspace_bytes(nt, nq, n_frames) bytes (or is null: full scan).
+// the full scan: the keys set to "nothing within the radius", then every query against every tree point
+static hipError_t launch_match_scan(hipStream_t st, const MatchSets& s, float r2) {
+  const int q = s.q, big = s.big(), n_frames = s.n_frames;
+  const unsigned Z = (unsigned)n_frames;
+  hipLaunchKernelGGL(match_init_kernel, dim3((q + 255) / 256, 1, Z), dim3(256), 0, st, s.best, q, r2, s.best_stride);
+  const int qblocks = (q + MB * QPT - 1) / (MB * QPT);      // (ragged: either set may be the queries, but never more than q of them)
+  // enough tree chunks to put ~8 workgroups on every CU, whole tiles each
+  int want = (8 * s.n_cu + qblocks * n_frames - 1) / (qblocks * n_frames);
+  const int tiles = (big + TILE - 1) / TILE;
+  if (want > tiles) want = tiles;
+  if (want < 1) want = 1;
+  const int chunk = ((tiles + want - 1) / want) * TILE;
+  const dim3 grid(qblocks, (big + chunk - 1) / chunk, Z);
+  if (s.ragged())
+    hipLaunchKernelGGL(match_kernel<true>, grid, dim3(MB), 0, st, s.tree, s.nt, s.qry, s.nq, chunk, r2, s.best, s.tree_stride,
+                       s.qry_stride, s.best_stride, s.d_n1, s.d_n2);
+  else
+    hipLaunchKernelGGL(match_kernel<false>, grid, dim3(MB), 0, st, s.tree, s.nt, s.qry, s.nq, chunk, r2, s.best, s.tree_stride,
+                       s.qry_stride, s.best_stride, nullptr, nullptr);
+  return hipGetLastError();
+}
+
+// Frame f reads a1 + f * a1_stride etc.  The exact-duplicate pass (when the plan asks for it and a sorted search follows), the
+// plan's search for the queries still open, the compaction of the keys into pairs.
 hipError_t launch_match_batch(hipStream_t st, const float* d_a1, int n1, size_t a1_stride, const float* d_a2, int n2,
                               size_t a2_stride, float radius, int32_t* d_out_pairs, size_t out_stride, int* d_n_out,
                               unsigned long long* d_best, int* d_scratch, int n_cu, void* d_prune_ws, int n_frames,
-                              int variant_in, const int* d_n1, const int* d_n2) {
-  // variants 4 / 5: the exact-duplicate pass first, then variant 2 / 3 for the queries it left open (its workspace comes
-  // first in d_prune_ws)
-  if (n_cu > 0) t_n_cu = n_cu;
-  const bool hash_first = variant_in >= 4 && d_prune_ws != nullptr;
-  const int variant = variant_in >= 4 ? variant_in - 2 : variant_in;
-  int* d_unres = nullptr;
-  if (d_n1 && d_n2) {
-    // ragged frames: every frame its own sizes and roles; full scan or (variant 3) the cell-hash search.
-    // q = min(n1, n2) is the room per frame in d_best / d_out_pairs.
-    const int q = n1 < n2 ? n1 : n2;
-    const float r2 = radius * radius;
-    if (q > 0 && variant == 3 && d_prune_ws) {
-      void* ws = d_prune_ws;
-      if (hash_first) {
-        hipError_t eh = launch_hash_first(st, d_a1, n1, d_a2, n2, r2, d_best, d_prune_ws, n_frames, a1_stride, a2_stride, (size_t)q,
-                                          d_n1, d_n2, &d_unres, q > SMALL_COMPACT ? d_out_pairs : nullptr, out_stride, 1);
-        if (eh == hipErrorNotSupported) d_unres = nullptr;        // sizes the pass does not take: the plain search answers every query
-        else if (eh != hipSuccess) return eh;
-        ws = static_cast<char*>(d_prune_ws) + hash_ws_bytes(n1 > n2 ? n1 : n2, n_frames);
-      }
-      // the cell-hash search with per-frame sizes and roles (workspace laid out for max(n1, n2) in both roles)
-      hipError_t ec = launch_match_cells(st, d_a1, n1, d_a2, n2, radius, r2, d_best, ws, n_frames, a1_stride, a2_stride,
-                                         (size_t)q, d_n1, d_n2, d_unres, d_unres ? d_unres + n_frames : nullptr,
-                                         d_unres ? reinterpret_cast<const int*>(static_cast<char*>(d_prune_ws) + hash_head_bytes(n_frames)) : nullptr);
-      if (ec != hipSuccess) return ec;
-    } else if (q > 0) {
-      hipLaunchKernelGGL(match_init_kernel, dim3((q + 255) / 256, 1, (unsigned)n_frames), dim3(256), 0, st, d_best, q, r2, (size_t)q);
-      const int big = n1 > n2 ? n1 : n2;
-      const int qblocks = (q + MB * QPT - 1) / (MB * QPT);      // either set may be the queries, but never more than q of them
-      int want = (8 * (n_cu > 0 ? n_cu : 256) + qblocks * n_frames - 1) / (qblocks * n_frames);
-      const int tiles = (big + TILE - 1) / TILE;
-      if (want > tiles) want = tiles;
-      if (want < 1) want = 1;
-      const int chunk = ((tiles + want - 1) / want) * TILE;
-      const int nchunks = (big + chunk - 1) / chunk;
-      hipLaunchKernelGGL(match_kernel<true>, dim3(qblocks, nchunks, (unsigned)n_frames), dim3(MB), 0, st, d_a1, n1, d_a2, n2, chunk, r2,
-                         d_best, a1_stride, a2_stride, (size_t)q, d_n1, d_n2);
-    }
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
-    return launch_match_compact(st, d_best, q, 1, d_out_pairs, d_n_out, d_scratch, n_frames, (size_t)q, out_stride, d_n1, d_n2, n1, n2, d_unres);
+                              MatchPlan plan, const int* d_n1, const int* d_n2) {
+  const bool ragged = d_n1 && d_n2;
+  MatchSets s;
+  s.n_frames = n_frames; s.best = d_best; s.n_cu = n_cu > 0 ? n_cu : 256;   // (MI355X's)
+  s.d_n1 = ragged ? d_n1 : nullptr; s.d_n2 = ragged ? d_n2 : nullptr;
+  size_t hash_out_stride = out_stride;
+  if (ragged) {
+    // every frame its own sizes and roles: the sets stay set 1 / set 2, q = min(n1, n2) is the room per frame in d_best / d_out_pairs
+    s.tree = d_a1; s.nt = n1; s.tree_stride = a1_stride;
+    s.qry = d_a2; s.nq = n2; s.qry_stride = a2_stride;
+    s.q = n1 < n2 ? n1 : n2; s.best_stride = (size_t)s.q; s.tree_is_1 = 1;
+  } else {
+    s.tree_is_1 = n1 >= n2;                 // vo_complete.cpp:15-20 (ties: a1 is the tree)
+    s.tree = s.tree_is_1 ? d_a1 : d_a2; s.nt = s.tree_is_1 ? n1 : n2; s.tree_stride = s.tree_is_1 ? a1_stride : a2_stride;
+    s.qry = s.tree_is_1 ? d_a2 : d_a1; s.nq = s.tree_is_1 ? n2 : n1; s.qry_stride = s.tree_is_1 ? a2_stride : a1_stride;
+    s.q = s.nq; s.best_stride = (size_t)s.nq;
+    if (n_frames <= 1) s.tree_stride = s.qry_stride = s.best_stride = hash_out_stride = 0;   // one frame: no strides at all
   }
-  const int tree_is_1 = n1 >= n2;                 // vo_complete.cpp:15-20 (ties: a1 is the tree)
-  const float* tree = tree_is_1 ? d_a1 : d_a2;
-  const float* qry = tree_is_1 ? d_a2 : d_a1;
-  const size_t ts = tree_is_1 ? a1_stride : a2_stride, qs = tree_is_1 ? a2_stride : a1_stride;
-  const int nt = tree_is_1 ? n1 : n2, nq = tree_is_1 ? n2 : n1;
+  // without a workspace the full scan; ragged frames: the bucket-pruned scan takes one size only
+  const MatchSearch search = (!d_prune_ws || (ragged && plan.search == MatchSearch::Buckets)) ? MatchSearch::Scan : plan.search;
   const float r2 = radius * radius;
-  const size_t best_stride = n_frames > 1 ? (size_t)nq : 0;
-  const unsigned Z = (unsigned)n_frames;
-  void* ws = d_prune_ws;
-  if (hash_first && nq > 0 && nt > 0 && (variant == 2 || variant == 3)) {
-    hipError_t eh = launch_hash_first(st, tree, nt, qry, nq, r2, d_best, d_prune_ws, n_frames, n_frames > 1 ? ts : 0,
-                                      n_frames > 1 ? qs : 0, best_stride, nullptr, nullptr, &d_unres,
-                                      nq > SMALL_COMPACT ? d_out_pairs : nullptr, n_frames > 1 ? out_stride : 0, tree_is_1);
-    if (eh == hipErrorNotSupported) d_unres = nullptr;            // sizes the pass does not take: the plain search answers every query
-    else if (eh != hipSuccess) return eh;
-    ws = static_cast<char*>(d_prune_ws) + hash_ws_bytes(nt, n_frames);
-  }
-  if (nq > 0 && nt > 0 && d_prune_ws && variant == 3) {
-    hipError_t ep = launch_match_cells(st, tree, nt, qry, nq, radius, r2, d_best, ws, n_frames, ts, qs,
-                                       best_stride, nullptr, nullptr, d_unres, d_unres ? d_unres + n_frames : nullptr,
-                                       d_unres ? reinterpret_cast<const int*>(static_cast<char*>(d_prune_ws) + hash_head_bytes(n_frames)) : nullptr);
-    if (ep != hipSuccess) return ep;
-  } else if (nq > 0 && nt > 0 && d_prune_ws) {
-    hipError_t ep = launch_match_pruned(st, tree, nt, qry, nq, radius, r2, d_best, ws, n_cu, n_frames, ts, qs,
-                                        best_stride, d_unres);
-    if (ep != hipSuccess) return ep;
-  } else if (nq > 0) {
-    hipLaunchKernelGGL(match_init_kernel, dim3((nq + 255) / 256, 1, Z), dim3(256), 0, st, d_best, nq, r2, best_stride);
-    if (nt > 0) {
-      const int qblocks = (nq + MB * QPT - 1) / (MB * QPT);
-      // enough tree chunks to put ~8 workgroups on every CU, whole tiles each
-      int want = (8 * (n_cu > 0 ? n_cu : 256) + qblocks * n_frames - 1) / (qblocks * n_frames);
-      const int tiles = (nt + TILE - 1) / TILE;
-      if (want > tiles) want = tiles;
-      if (want < 1) want = 1;
-      const int tiles_per_chunk = (tiles + want - 1) / want;
-      const int chunk = tiles_per_chunk * TILE;
-      const int nchunks = (nt + chunk - 1) / chunk;
-      hipLaunchKernelGGL(match_kernel<false>, dim3(qblocks, nchunks, Z), dim3(MB), 0, st, tree, nt, qry, nq, chunk, r2, d_best,
-                         n_frames > 1 ? ts : 0, n_frames > 1 ? qs : 0, best_stride, nullptr, nullptr);
+  HashHandoff open;
+  if (s.q > 0) {
+    void* ws = d_prune_ws;
+    if (plan.hash_first && search != MatchSearch::Scan) {
+      const hipError_t eh = launch_hash_first(st, s, r2, ws, s.q > SMALL_COMPACT ? d_out_pairs : nullptr, hash_out_stride, &open);
+      if (eh != hipSuccess && eh != hipErrorNotSupported) return eh;   // (not supported: the plain search answers every query)
+      ws = static_cast<char*>(ws) + match_hash_workspace_bytes(s.big(), n_frames);
     }
+    const hipError_t es = search == MatchSearch::Cells     ? launch_match_cells(st, s, radius, r2, ws, open)
+                          : search == MatchSearch::Buckets ? launch_match_pruned(st, s, radius, r2, ws, open.unres)
+                                                           : launch_match_scan(st, s, r2);
+    if (es != hipSuccess) return es;
   }
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;
-  return launch_match_compact(st, d_best, nq, tree_is_1, d_out_pairs, d_n_out, d_scratch, n_frames, best_stride,
-                              out_stride, nullptr, nullptr, 0, 0, d_unres);
+  return launch_match_compact(st, d_best, s.q, s.tree_is_1, d_out_pairs, d_n_out, d_scratch, n_frames, s.best_stride, out_stride,
+                              s.d_n1, s.d_n2, ragged ? n1 : 0, ragged ? n2 : 0, open.unres);
 }
 
 hipError_t launch_match(hipStream_t st, const float* d_a1, int n1, const float* d_a2, int n2,
                         float radius, int32_t* d_out_pairs, int* d_n_out,
-                        unsigned long long* d_best, int* d_scratch, int n_cu, void* d_prune_ws, int variant) {
+                        unsigned long long* d_best, int* d_scratch, int n_cu, void* d_prune_ws, MatchPlan plan) {
   return launch_match_batch(st, d_a1, n1, 0, d_a2, n2, 0, radius, d_out_pairs, 0, d_n_out, d_best, d_scratch, n_cu,
-                            d_prune_ws, 1, variant, nullptr, nullptr);
+                            d_prune_ws, 1, plan, nullptr, nullptr);
 }
 
 }  // namespace vo

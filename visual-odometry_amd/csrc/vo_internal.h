@@ -287,10 +287,16 @@ hipError_t launch_join(hipStream_t st, const int32_t* d_img, int n_img, const in
                        int32_t* d_out, int* d_n_out, unsigned long long* d_table /* n_ref words */,
                        int* d_scratch);
 
-// matcher variants: 1 = full scan (no workspace), 2 = bucket-pruned scan, 3 = cell-hash search, 4 / 5 = the
-// exact-duplicate pass first ("hash-first", match.hip), then variant 2 / 3 for the queries it left open; the
-// workspace of variant v holds match_workspace_bytes(v, nt, nq, n_frames) bytes
-// after a call that ran variant 4 / 5 on d_prune_ws: *d_out = 1 when at least one frame took the exact-duplicate pass
+// How one matcher call searches: the full scan (no workspace), the bucket-pruned scan or the cell-hash search, and whether the
+// exact-duplicate pass ("hash-first", match.hip) runs in front of a sorted search, which then only sees the queries the pass
+// left open.  capi.hip (match_plan) turns the public mode 0..5 into a plan; nothing below it sees the mode.  The workspace of a
+// plan holds match_workspace_bytes(plan, nt, nq, n_frames) bytes: the pass's block first, then the search's.
+enum class MatchSearch { Scan, Buckets, Cells };
+struct MatchPlan {
+  MatchSearch search = MatchSearch::Scan;
+  bool hash_first = false;
+};
+// after a call that ran the exact-duplicate pass on d_prune_ws: *d_out = 1 when at least one frame took it
 hipError_t launch_match_hint(hipStream_t st, const void* d_prune_ws, int n_frames, int* d_out);
 // after a call that ran WITHOUT the pass: *d_out = 1 when one of eight sample queries of some frame found its match at distance 0
 hipError_t launch_match_hint_from_best(hipStream_t st, const unsigned long long* d_best, size_t best_stride, int nq_cap,
@@ -300,20 +306,20 @@ size_t match_cells_workspace_bytes(int nt, int nq, int n_frames);
 size_t match_hash_workspace_bytes(int nt, int n_frames);
 bool match_cells_supported(int nt, int nq);   // set sizes the cell-hash search takes (beyond: the bucket-pruned scan)
 bool match_hash_supported(int nt, int n_frames);   // tree sizes the exact-duplicate pass takes (beyond: the general search alone)
-inline size_t match_workspace_bytes(int variant, int nt, int nq, int n_frames) {
-  const size_t hash = variant >= 4 ? match_hash_workspace_bytes(nt, n_frames) : 0;
-  const int v = variant >= 4 ? variant - 2 : variant;
-  return hash + (v == 3 ? match_cells_workspace_bytes(nt, nq, n_frames)
-               : v == 2 ? match_pruned_workspace_bytes(nt, nq, n_frames) : 0);
+inline size_t match_workspace_bytes(MatchPlan p, int nt, int nq, int n_frames) {
+  return (p.hash_first ? match_hash_workspace_bytes(nt, n_frames) : 0) +
+         (p.search == MatchSearch::Cells     ? match_cells_workspace_bytes(nt, nq, n_frames)
+          : p.search == MatchSearch::Buckets ? match_pruned_workspace_bytes(nt, nq, n_frames) : 0);
 }
 // n_frames frames of identical set sizes, frame f at base + f*stride (strides in floats / pairs);
 // d_best: n_frames*min(n1,n2) keys; d_scratch: n_frames * compaction_scratch_ints(min(n1,n2)) ints; d_n_out[n_frames]
 // d_n1 / d_n2 (both or neither): ragged frames -- frame f holds d_n1[f] <= n1 and d_n2[f] <= n2 points (n1, n2 are then the
-// capacities, the strides must be >= them) and picks its own tree (its larger set); always the full scan
+// capacities, the strides must be >= them) and picks its own tree (its larger set); the full scan or the cell-hash search
+// d_prune_ws: the plan's workspace (null: the full scan whatever the plan says)
 hipError_t launch_match_batch(hipStream_t st, const float* d_a1, int n1, size_t a1_stride, const float* d_a2, int n2,
                               size_t a2_stride, float radius, int32_t* d_out_pairs, size_t out_stride, int* d_n_out,
                               unsigned long long* d_best, int* d_scratch, int n_cu, void* d_prune_ws, int n_frames,
-                              int variant, const int* d_n1 = nullptr, const int* d_n2 = nullptr);
+                              MatchPlan plan, const int* d_n1 = nullptr, const int* d_n2 = nullptr);
 hipError_t launch_transform_batch(hipStream_t st, const float* d_T16, const float* d_in, int n, size_t stride,
                                   float* d_out, int n_frames);
 hipError_t launch_triangulate_batch(hipStream_t st, const float K[9], const Pose* X_host, const float* d_X16,
@@ -340,7 +346,7 @@ hipError_t launch_radius_search(hipStream_t st, const float* d_tree, int nt, con
 hipError_t launch_match(hipStream_t st, const float* d_a1, int n1, const float* d_a2, int n2,
                         float radius, int32_t* d_out_pairs, int* d_n_out,
                         unsigned long long* d_best /* min(n1,n2) u64 */, int* d_scratch, int n_cu,
-                        void* d_prune_ws, int variant);
+                        void* d_prune_ws, MatchPlan plan);
 
 // ---- the map on the device (map.hip) ------------------------------------------------------------------
 struct MapDev {
