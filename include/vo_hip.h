@@ -642,7 +642,22 @@ int vo_match_appearances_batch_dev(vo_ctx *ctx, int n_frames, const float *d_a1,
  * are always appended.  O(cloud) per update through a hash table of first occurrences (the reference: O(cloud x map)).
  * All calls are enqueued on the context's stream; only vo_map_size / vo_map_read / vo_map_get_history wait.
  * The arrays grow by themselves (a stream synchronisation and a copy when they do: give vo_map_create the capacity a
- * run will need to avoid it; growing is refused inside a graph capture). */
+ * run will need to avoid it; growing is refused inside a graph capture).
+ *
+ * A CAPTURED UPDATE (vo_map_update_dev between vo_ctx_begin_capture and vo_ctx_end_capture) is admitted while the host's
+ * bound of the size says that its n_max rows fit, and refused (VO_ERR_NOT_READY) otherwise; the graph's replays add
+ * entries the host does not count.  So, once an update of a map has been captured, calls OUTSIDE a capture no longer
+ * trust that bound: vo_map_update[_dev] asks the device for the size first (a stream synchronisation per call) and grows
+ * the map when the rows would not fit, vo_map_transform and vo_map_refine_batch_dev reach every entry (they size their
+ * work by the capacity).  The graph names the arrays it was captured on: do not replay it after the map has grown.
+ *
+ * OVERFLOW.  A replayed update cannot grow the map.  What then does not fit is dropped: the map holds what the
+ * reference's map holds cut to `capacity` entries -- the classes with the earliest first occurrence in the cloud stay,
+ * entries already there still take their new points -- and a dropped class is forgotten: sent again it is a new class
+ * (and dropped again while the map is full).  Every dropped entry is counted; from then on vo_map_size and vo_map_read
+ * fail with VO_ERR_BAD_INDEX and name the running count (vo_map_size still sets *n), until vo_map_clear; so does every
+ * host form that reads the size first (vo_map_refine).  The entries, vo_map_dev_ptrs, vo_map_lookup and the *_dev forms of
+ * lookup, localisation and refinement stay valid on the entries the map kept. */
 typedef struct vo_map vo_map;
 int vo_map_create(vo_ctx *ctx, int capacity, vo_map **out);
 int vo_map_destroy(vo_map *m);

@@ -127,6 +127,24 @@ void hc_tri_constants(const float* K, const float* X16, float* iK, float* iRiK, 
 
 void hc_v2t(const float* v, float* T16) { pose_to_T16(v2t_euler(v), T16); }
 
+// the map's key functions (map.hip runs these very definitions): n rows of ten floats -> hash, NaN flag; hashes -> home slots
+void hc_map_hash(const float* app, int n, uint32_t* h, int* has_nan) {
+  for (int i = 0; i < n; ++i) {
+    Row r;
+    for (int k = 0; k < 10; ++k) r.v[k] = app[10 * (size_t)i + k];
+    h[i] = map_hash(r);
+    if (has_nan) has_nan[i] = map_row_has_nan(r) ? 1 : 0;
+  }
+}
+void hc_map_home_slot(const uint32_t* h, int n, uint32_t tmask, uint32_t* slot) {
+  for (int i = 0; i < n; ++i) slot[i] = map_home_slot(h[i], tmask);
+}
+int hc_map_rows_equal(const float* a, const float* b) {
+  Row x, y;
+  for (int k = 0; k < 10; ++k) { x.v[k] = a[k]; y.v[k] = b[k]; }
+  return map_rows_equal(x, y) ? 1 : 0;
+}
+
 // The arithmetic of picp_exact_kernel on the host: terms by picp_term_exact, entry k summed sequentially in
 // correspondence order, tail picp_update_t<true>.  Records per round H (damping included, col-major), b,
 // (chi_in, chi_out, n_in), pose -- must equal the oracle's picp_solve_raw bit for bit.

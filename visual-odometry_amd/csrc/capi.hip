@@ -2110,7 +2110,8 @@ struct vo_map {
   MapDev d;
   DevBuf scratch;
   float* hist = nullptr;        // [0,16) the history isometry, [16,32) staging of a host isometry (vo_map_update)
-  long long size_ub = 0;        // upper bound of the size known without asking the device
+  long long size_ub = 0;        // upper bound of the size known without asking the device, as long as !replayable
+  bool replayable = false;      // an update of this map has been captured: the graph's replays add entries the host never counts
   DevBuf up_xyz, up_app;        // staging of vo_map_update
   DevBuf look_ws;               // vo_map_lookup*: per-workgroup counts, entries per query position
   DevBuf loc_ws;                // vo_map_localise*: what passes from stage to stage (hits, gathered points, winner, pairs handed on)
@@ -2142,11 +2143,15 @@ static int map_alloc_arrays(MapDev& d, int cap) {
   return VO_OK;
 }
 
+// what bounds the size where the host must not wait: size_ub, or the capacity once replays may have outrun it
+static int map_bound(const vo_map* m) { return (int)(m->replayable || m->size_ub > m->d.cap ? m->d.cap : m->size_ub); }
+
 // room for n more entries: the bound the host keeps (size_ub grows by a cloud's row count per update) is refreshed from
-// the device only when it would pass the capacity, and the arrays grow only when the true size would
+// the device only when it would pass the capacity, and the arrays grow only when the true size would.  A map whose update
+// has been captured asks the device every time outside a capture; inside one nobody can ask, and the bound decides as before.
 static int map_reserve(vo_map* m, int n) {
   vo_ctx* c = m->ctx;
-  if (m->size_ub + n <= m->d.cap) return VO_OK;
+  if ((c->capturing || !m->replayable) && m->size_ub + n <= m->d.cap) return VO_OK;
   if (c->capturing) return fail(VO_ERR_NOT_READY, "vo_map: the map would have to grow inside a graph capture (create it with the capacity it will need)");
   int size = 0;
   VO_HIP_CHECK(hipMemcpyAsync(&size, m->d.hdr, sizeof(int), hipMemcpyDeviceToHost, c->stream));
@@ -2235,6 +2240,7 @@ int vo_map_update_dev(vo_map* m, const float* d_xyz, const float* d_app, int n_m
   VO_HIP_CHECK(m->scratch.ensure(sizeof(int) * map_scratch_ints(n_max), c->stream));
   VO_HIP_CHECK(launch_map_update(c->stream, m->d, d_xyz, d_app, n_max, d_n, d_T16, m->scratch.as<int>()));
   m->size_ub += n_max;
+  if (c->capturing) m->replayable = true;
   return VO_OK;
 }
 
@@ -2316,8 +2322,7 @@ int vo_map_transform(vo_map* m, const float T16[16]) {
   VO_MAP_LIVE(m);
   VO_REQUIRE(T16, "null argument");
   if (int r = set_device(m->ctx)) return r;
-  const long long bound = m->size_ub < m->d.cap ? m->size_ub : m->d.cap;
-  VO_HIP_CHECK(launch_map_transform(m->ctx->stream, m->d, pose_from_T16(T16), (int)bound));
+  VO_HIP_CHECK(launch_map_transform(m->ctx->stream, m->d, pose_from_T16(T16), map_bound(m)));
   return VO_OK;
 }
 
@@ -2576,8 +2581,7 @@ int vo_map_refine_batch_dev(vo_map* m, int n_frames, const float K[9], const flo
   double Kinv[9];
   if (!invert_k(K, Kinv)) return fail(VO_ERR_INVALID_ARG, "%s: K is singular", fn);
   vo_ctx* c = m->ctx;
-  const long long bound_ll = m->size_ub < m->d.cap ? m->size_ub : m->d.cap;
-  const int bound = (int)bound_ll;
+  const int bound = map_bound(m);
   MapRefineWs w = map_refine_layout(nullptr, n_frames, n_max, bound);
   if (app_stride >= 0x7fffffff / 10 || (long long)n_max * n_frames > (1ll << 30))      // (the lookup's own limit, met before anything is sized)
     return fail(VO_ERR_INVALID_ARG, "%s: more than 2^30 rows in one call", fn);

@@ -25,11 +25,16 @@ namespace vo {
 
 constexpr int MB = 256;                                   // rows per workgroup
 constexpr unsigned long long MAP_EMPTY = ~0ull;
+// A class that found no room in the arrays (its entry would have been >= cap) leaves this word in its slot.  A free word there
+// would cut the probe chains that run over the slot, and an entry index >= cap would be read as a row of the NEXT update's
+// cloud; the marker is neither: probe, lookup and re-hash step over it, nothing claims it, and it goes away when the table is
+// rebuilt (growth, vo_map_clear).  No slot's word equals it: entries and provisional indices stay below 2^30.
+constexpr unsigned long long MAP_DROPPED = ~0ull - 1ull;
 
 struct MapArgs {
   float* pts;                  // [cap][3]
   float* app;                  // [cap][10]
-  unsigned long long* table;   // [tcap] (tag << 32) | entry, MAP_EMPTY when free
+  unsigned long long* table;   // [tcap] (tag << 32) | entry, MAP_EMPTY when free, MAP_DROPPED where a class found no room
   int* last;                   // [tcap] last cloud index of the slot's class in the running update, -1 otherwise
   unsigned tmask;              // tcap - 1 (a power of two)
   int cap;                     // entries the arrays hold
@@ -45,8 +50,6 @@ struct MapArgs {
   int nb;
 };
 
-struct Row { float v[10]; };
-
 __device__ __forceinline__ Row map_load_row(const float* app, size_t i) {
   const float2* p = reinterpret_cast<const float2*>(app) + 5 * i;
   Row r;
@@ -54,31 +57,7 @@ __device__ __forceinline__ Row map_load_row(const float* app, size_t i) {
   for (int k = 0; k < 5; ++k) { const float2 t = p[k]; r.v[2 * k] = t.x; r.v[2 * k + 1] = t.y; }
   return r;
 }
-__device__ __forceinline__ bool map_row_has_nan(const Row& r) {
-  bool nan = false;
-#pragma unroll
-  for (int k = 0; k < 10; ++k) nan |= r.v[k] != r.v[k];
-  return nan;
-}
-// operator== on ten floats (PointCloud.h:56) for rows without NaN
-__device__ __forceinline__ bool map_rows_equal(const Row& a, const Row& b) {
-  bool eq = true;
-#pragma unroll
-  for (int k = 0; k < 10; ++k) eq &= a.v[k] == b.v[k];
-  return eq;
-}
-__device__ __forceinline__ unsigned map_rotl(unsigned x, int r) { return (x << r) | (x >> (32 - r)); }
-// hash of the canonical row: -0 hashes as +0, so that rows equal under == share a hash
-__device__ __forceinline__ unsigned map_hash(const Row& r) {
-  unsigned x = 0x9e3779b9u;
-#pragma unroll
-  for (int k = 0; k < 10; ++k) {
-    const unsigned w = r.v[k] == 0.f ? 0u : __float_as_uint(r.v[k]);
-    x = (k & 1) ? map_rotl(x, 7) + w : map_rotl(x, 11) ^ w;
-  }
-  x ^= x >> 15; x *= 0x2c1b3c6du; x ^= x >> 12; x *= 0x297a2d39u; x ^= x >> 15;
-  return x;
-}
+// Row, map_row_has_nan, map_rows_equal, map_hash and map_home_slot: vo_math.h (the host build of the tests runs them too)
 
 __global__ __launch_bounds__(MB) void map_probe_kernel(MapArgs a) {
   const int n = live_rows(a.d_n, a.n_max);
@@ -89,7 +68,7 @@ __global__ __launch_bounds__(MB) void map_probe_kernel(MapArgs a) {
   if (map_row_has_nan(r)) { a.slot[i] = -1; return; }
   const unsigned h = map_hash(r);
   const unsigned long long mine = ((unsigned long long)h << 32) | (unsigned)(M + i);
-  unsigned s = (h * 0x9e3779b1u) & a.tmask;                 // home slot: other bits than the tag's comparison relies on
+  unsigned s = map_home_slot(h, a.tmask);
   int found = -2;
   for (unsigned probes = 0; probes <= a.tmask; ++probes, s = (s + 1) & a.tmask) {
     unsigned long long w = a.table[s];
@@ -97,7 +76,9 @@ __global__ __launch_bounds__(MB) void map_probe_kernel(MapArgs a) {
       w = atomicCAS(&a.table[s], MAP_EMPTY, mine);
       if (w == MAP_EMPTY) { found = (int)s; break; }        // claimed
     }
-    if ((unsigned)(w >> 32) != h) continue;                 // another class lives here
+    if (w == MAP_DROPPED || (unsigned)(w >> 32) != h) continue;      // a class that was dropped, or another class, lives here
+    // w names an entry (< M: commit leaves nothing else behind) or a row of THIS cloud (M + i', i' < n: written above by a
+    // thread of this launch)
     const unsigned e = (unsigned)w;
     const Row o = e < (unsigned)M ? map_load_row(a.app, (size_t)e) : map_load_row(a.c_app, (size_t)(e - (unsigned)M));
     if (!map_rows_equal(r, o)) continue;                    // same tag, another row
@@ -109,6 +90,7 @@ __global__ __launch_bounds__(MB) void map_probe_kernel(MapArgs a) {
   }
   a.slot[i] = found;                                        // (-2: the table is full -- the host keeps it at most half full)
   if (found >= 0) atomicMax(&a.last[found], i);
+  else atomicAdd(&a.hdr[3], 1);                             // a row without a slot is a row dropped (hdr[3] is read by no launch of the update)
 }
 
 __global__ __launch_bounds__(MB) void map_flag_kernel(MapArgs a) {
@@ -195,8 +177,8 @@ __global__ __launch_bounds__(MB) void map_commit_kernel(MapArgs a) {
     } else {
       const int f = (int)(idx - (unsigned)M);               // the class's first occurrence in this cloud
       e = M + a.counts[f / MB] + a.rank[f];
-      // the slot now names the entry (only this thread touches the slot in this launch)
-      a.table[s] = (a.table[s] & 0xffffffff00000000ull) | (unsigned)e;
+      // the slot now names the entry, or says that the class was dropped (only this thread touches the slot in this launch)
+      a.table[s] = e < a.cap ? ((a.table[s] & 0xffffffff00000000ull) | (unsigned)e) : MAP_DROPPED;
     }
     a.last[s] = -1;
   }
@@ -222,14 +204,14 @@ __global__ __launch_bounds__(MB) void map_rehash_kernel(MapArgs a) {
   if (map_row_has_nan(r)) return;
   const unsigned h = map_hash(r);
   const unsigned long long mine = ((unsigned long long)h << 32) | (unsigned)j;
-  unsigned s = (h * 0x9e3779b1u) & a.tmask;
+  unsigned s = map_home_slot(h, a.tmask);
   for (unsigned probes = 0; probes <= a.tmask; ++probes, s = (s + 1) & a.tmask) {
     unsigned long long w = a.table[s];
     if (w == MAP_EMPTY) {
       w = atomicCAS(&a.table[s], MAP_EMPTY, mine);
       if (w == MAP_EMPTY) return;
     }
-    if ((unsigned)(w >> 32) != h) continue;
+    if (w == MAP_DROPPED || (unsigned)(w >> 32) != h) continue;
     if (!map_rows_equal(r, map_load_row(a.app, (size_t)(unsigned)w))) continue;
     atomicMin(&a.table[s], mine);
     return;
@@ -281,11 +263,11 @@ __global__ __launch_bounds__(MB) void map_lookup_probe_kernel(MapLookupArgs a) {
     const Row r = map_load_row(a.q_app + (size_t)fb.f * a.q_stride, (size_t)i);
     if (!map_row_has_nan(r)) {
       const unsigned h = map_hash(r);
-      unsigned s = (h * 0x9e3779b1u) & a.tmask;             // the home slot of map_probe_kernel
+      unsigned s = map_home_slot(h, a.tmask);               // the home slot of map_probe_kernel
       for (unsigned probes = 0; probes <= a.tmask; ++probes, s = (s + 1) & a.tmask) {
         const unsigned long long w = a.table[s];
         if (w == MAP_EMPTY) break;                          // the class was never entered
-        if ((unsigned)(w >> 32) != h) continue;             // another class lives here
+        if (w == MAP_DROPPED || (unsigned)(w >> 32) != h) continue;      // a dropped class, or another class, lives here
         const unsigned e = (unsigned)w;
         if (e >= (unsigned)M) continue;                     // (never, between updates: a slot names an entry)
         if (!map_rows_equal(r, map_load_row(a.app, (size_t)e))) continue;   // same tag, another row

@@ -830,6 +830,37 @@ VO_HD bool ldlt3_solve(const double H[6], const double b[3], double x[3]) {
   return fabs(x[0]) <= big && fabs(x[1]) <= big && fabs(x[2]) <= big;
 }
 
+// ---- the map's key (map.hip): ten floats, their hash and the home slot of the hash -- integer code, the same on both sides --
+struct Row { float v[10]; };
+
+VO_HD bool map_row_has_nan(const Row& r) {
+  bool nan = false;
+#pragma unroll
+  for (int k = 0; k < 10; ++k) nan |= r.v[k] != r.v[k];
+  return nan;
+}
+// operator== on ten floats (PointCloud.h:56) for rows without NaN
+VO_HD bool map_rows_equal(const Row& a, const Row& b) {
+  bool eq = true;
+#pragma unroll
+  for (int k = 0; k < 10; ++k) eq &= a.v[k] == b.v[k];
+  return eq;
+}
+VO_HD uint32_t map_rotl(uint32_t x, int r) { return (x << r) | (x >> (32 - r)); }
+// hash of the canonical row: -0 hashes as +0, so that rows equal under == share a hash
+VO_HD uint32_t map_hash(const Row& r) {
+  uint32_t x = 0x9e3779b9u;
+#pragma unroll
+  for (int k = 0; k < 10; ++k) {
+    const uint32_t w = r.v[k] == 0.f ? 0u : __builtin_bit_cast(uint32_t, r.v[k]);
+    x = (k & 1) ? map_rotl(x, 7) + w : map_rotl(x, 11) ^ w;
+  }
+  x ^= x >> 15; x *= 0x2c1b3c6du; x ^= x >> 12; x *= 0x297a2d39u; x ^= x >> 15;
+  return x;
+}
+// where a hash starts probing in a table of tmask + 1 slots: other bits than the tag's comparison relies on
+VO_HD uint32_t map_home_slot(uint32_t h, uint32_t tmask) { return (h * 0x9e3779b1u) & tmask; }
+
 #if defined(__HIPCC__)
 // ---- two pieces every kernel file uses (device only) ----------------------------------------------------
 // live rows of a call: *d_n clamped to [0, n_max], or n_max when d_n is null
