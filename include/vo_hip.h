@@ -197,7 +197,14 @@ int vo_picp_get_pose(vo_picp *s, float T[16]);                  /* camera(), pic
 int vo_picp_get_pose_dev(vo_picp *s, float *d_T16);             /* async copy on the stream */
 /* device address of the solver's own 4x4 pose (column-major), valid for the life of the
  * handle and rewritten by every solve: lets a consumer kernel read the result in place
- * (rounds of vo_picp_one_round reach it with the next getter call -- this one included) */
+ * (rounds of vo_picp_one_round reach it with the next getter call -- this one included).
+ * Behind the 16 floats lie five ints, the cycle report of the last vo_picp_solve / vo_picp_solve_dev / vo_picp_rounds of
+ * more than one workgroup: [0], [1] internal; [2] detected_at, [3] period, [4] skipped.  Within a solve a round is a
+ * deterministic map of the pose, so once the pose after round k equals, bit for bit, the pose after an earlier round j,
+ * the rounds that follow repeat earlier ones and their launches return at once -- the results are the bytes of the full
+ * solve.  detected_at: the launch that found the repeat, k + 1 (0: none); period: k - j; skipped: launches that returned
+ * at once.  Read them once the stream has drained (vo_memcpy_d2h does).  VO_PICP_CYCLE=0 in the environment (read per
+ * call) turns the detection off. */
 int vo_picp_pose_dev_ptr(vo_picp *s, const float **d_T16);
 int vo_picp_get_stats(vo_picp *s, float *chi_inliers, float *chi_outliers, int *num_inliers); /* :44-50 */
 /* H (6x6 col-major, damping included, as _H after oneRound) and b of the last round */

@@ -275,6 +275,15 @@ class PICPSolver:
         _chk(self.lib.vo_picp_chain_info(self.h, C.byref(o), C.byref(a), C.byref(b)))
         return o.value, a.value, b.value
 
+    def cycleInfo(self):
+        """(launch that found the pose of an earlier round again -- 0: none --, the repeat's period, launches of the last
+        solve that returned at once): the five ints behind the pose of vo_picp_pose_dev_ptr (include/vo_hip.h); synchronises"""
+        p = C.c_void_p()
+        _chk(self.lib.vo_picp_pose_dev_ptr(self.h, C.byref(p)))
+        blk = np.zeros(5, np.int32)
+        self.ctx.d2h(blk, p.value + 16 * 4)
+        return int(blk[2]), int(blk[3]), int(blk[4])
+
     def setCorrespondences(self, correspondences):
         p = _i32pairs(correspondences)
         _chk(self.lib.vo_picp_set_correspondences(self.h, _ptr(p), C.c_int(len(p))))

@@ -651,6 +651,9 @@ static bool picp_chainable(const vo_picp* s);
 // VO_PICP_GATHER=0 in the environment keeps the separate gather launch in front of every solve (read per call: tests compare
 // the two routes in one process)
 static bool picp_gather_enabled() { const char* e = getenv("VO_PICP_GATHER"); return !(e && e[0] == '0'); }
+// VO_PICP_CYCLE=0 in the environment turns the cycle detection of a launch-per-round solve off (read per call, part of the
+// graph's key): no detector workgroup, every round runs.  Diagnostic runs of the round itself (stamps, step splits) set it.
+static bool picp_cycle_enabled() { const char* e = getenv("VO_PICP_CYCLE"); return !(e && e[0] == '0'); }
 
 // n_iters / lazy: what the caller hands to picp_enqueue next (0: nothing that could take the gather along)
 static int picp_prepare(vo_picp* s, const int32_t* d_pairs, int n_pairs, const int* d_n, int keep_outliers, int n_iters = 0,
@@ -774,6 +777,7 @@ static int picp_enqueue(vo_picp* s, int n_iters, bool lazy = false) {
   PackedCorr pk{s->packed.as<float>(), s->packed.cap / (5 * sizeof(float)) & ~(size_t)3};
   float* partials = s->partials.as<float>();
   const bool pinhole = is_pinhole(s->hp.cam.K), keep = s->hp.keep_outliers != 0;
+  const bool cycle = picp_cycle_enabled();
   if (gather.on && (s->exact || n_iters < 1)) {
     s->packed_valid = false;
     return fail(VO_ERR_NOT_READY, "vo_picp: a gather was left without its round");
@@ -788,14 +792,14 @@ static int picp_enqueue(vo_picp* s, int n_iters, bool lazy = false) {
     // solve shape, whatever it is replayed behind.  (Round 0 as the graph's first node measured the same: DESIGN.md section 8.)
     const int part = picp_rounds_chain(s->grid) ? PICP_AFTER_ROUND0 : PICP_WHOLE;
     auto key = std::make_tuple(n_iters, s->grid, (const void*)pk.base, pk.cap, (const void*)partials,
-                               (pinhole ? 1 : 0) | (keep ? 2 : 0));
+                               (pinhole ? 1 : 0) | (keep ? 2 : 0) | (cycle ? 4 : 0));
     auto it = s->graphs.find(key);
     if (it == s->graphs.end()) {
       hipGraph_t graph = nullptr;
       hipGraphExec_t exec = nullptr;
       hipError_t e = hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal);
       if (e == hipSuccess) {
-        hipError_t el = launch_picp_rounds(c->stream, s->d_params, s->d_state, pk, partials, s->grid, n_iters, pinhole, keep, gather, part);
+        hipError_t el = launch_picp_rounds(c->stream, s->d_params, s->d_state, pk, partials, s->grid, n_iters, pinhole, keep, gather, part, cycle);
         e = hipStreamEndCapture(c->stream, &graph);
         if (e == hipSuccess && el != hipSuccess) e = el;
       }
@@ -823,7 +827,7 @@ static int picp_enqueue(vo_picp* s, int n_iters, bool lazy = false) {
     if (s->use_graph && it != s->graphs.end()) {
       hipError_t e = hipSuccess;
       if (part == PICP_AFTER_ROUND0)
-        e = launch_picp_rounds(c->stream, s->d_params, s->d_state, pk, partials, s->grid, n_iters, pinhole, keep, gather, PICP_ROUND0);
+        e = launch_picp_rounds(c->stream, s->d_params, s->d_state, pk, partials, s->grid, n_iters, pinhole, keep, gather, PICP_ROUND0, cycle);
       if (e == hipSuccess) e = hipGraphLaunch(it->second, c->stream);
       if (e != hipSuccess && gather.on) s->packed_valid = false;
       VO_HIP_CHECK(e);
@@ -831,7 +835,8 @@ static int picp_enqueue(vo_picp* s, int n_iters, bool lazy = false) {
     }
   }
   {
-    const hipError_t e = launch_picp_rounds(c->stream, s->d_params, s->d_state, pk, partials, s->grid, n_iters, pinhole, keep, gather);
+    const hipError_t e = launch_picp_rounds(c->stream, s->d_params, s->d_state, pk, partials, s->grid, n_iters, pinhole, keep, gather,
+                                            PICP_WHOLE, cycle);
     if (e != hipSuccess && gather.on) s->packed_valid = false;
     VO_HIP_CHECK(e);
   }
@@ -976,7 +981,8 @@ int vo_picp_set_exact(vo_picp* s, int on) {
 
 static int picp_read_state(vo_picp* s, PicpState* h) {
   if (int r = picp_flush(s)) return r;
-  VO_HIP_CHECK(hipMemcpyAsync(h, s->d_state, sizeof(PicpState), hipMemcpyDeviceToHost, s->ctx->stream));
+  // (the pose history of the cycle detection stays on the device: nothing on the host reads it)
+  VO_HIP_CHECK(hipMemcpyAsync(h, s->d_state, offsetof(PicpState, hist), hipMemcpyDeviceToHost, s->ctx->stream));
   VO_HIP_CHECK(hipStreamSynchronize(s->ctx->stream));
   if (h->n_bad > 0)
     return fail(VO_ERR_BAD_INDEX, "vo_picp: %d correspondence(s) index outside the point arrays", h->n_bad);

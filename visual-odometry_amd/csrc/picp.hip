@@ -338,12 +338,72 @@ struct RoundGather {
 constexpr int PICP_BAD_SLOT = NACC, PICP_GATHERED_SLOT = NACC + 1;
 static_assert(PICP_GATHERED_SLOT < PICP_PSTRIDE, "the partial row has two spare slots");
 
-template <bool PRE, bool FINISH, bool PINHOLE, bool KEEP, bool BATCH, bool GATHER = false, bool TALLY = false>
+// ---- rounds whose pose has already occurred -----------------------------------------------------
+// Within a solve a round is a deterministic map of the 12 floats of the pose (correspondences, camera, threshold and summation
+// order are fixed), and after the first few rounds the pose walks through a handful of neighbouring float values: once the pose
+// after round k equals, bit for bit, the pose after an earlier round j, round k + 1 repeats round j + 1 and every later round
+// repeats an earlier one.  The detector is ONE extra workgroup (block index nb) of every launch it >= 1 of a solve with cycle
+// detection on; it writes no partial row and is on nobody's chain.  Wave 0 of it
+//   * reads the pose after round k = it - 1 (written by the launch before) and compares it, as 32-bit integers (NaN, +0 and -0
+//     are told apart by their bits), with the history: lane l holds round k - 1 - l, one ballot decides, the most recent wins;
+//   * stores that pose as hist[k % PICP_HIST];
+//   * on the first repeat (pose k = pose j) fills the reporting fields, and where a launch is left to skip (it + 1 < last)
+//     sets the target round -- pose(last) = pose(j + (last - j) % (k - j)) -- and then the state: launches it + 1 .. last - 1
+//     return at once, launch `last` takes its pose from hist[target] (picp_round_body), the finishing launch runs as ever.
+// Once the state is SKIP the detector does nothing: the pose ring is no longer written, the history must stay as it is.
+// Every access is a vector access (an opaque zero in the address): the code lies behind the round's in the kernel and must
+// not put a scalar load there.
+__device__ __forceinline__ void picp_cycle_detect(PicpState* S, int it, int last) {
+  const int lane = threadIdx.x;
+  if (lane >= 64) return;
+  int vz = 0;
+  asm volatile("" : "+v"(vz));
+  const int* ctl = reinterpret_cast<const int*>(&S->cyc) + vz;
+  const int skip_from = ctl[offsetof(PicpCycle, skip_from) / 4], detected_at = ctl[offsetof(PicpCycle, detected_at) / 4];
+  const int k = it - 1;
+  const int* cur = reinterpret_cast<const int*>(S->pose[k & (PICP_SLOTS - 1)]) + vz;
+  const int r = k - 1 - lane;                              // the round this lane holds (lane 63 would be the entry about to be replaced)
+  const bool live = r >= 0 && lane < PICP_HIST - 1;
+  const int* old = reinterpret_cast<const int*>(S->hist[(live ? r : 0) & (PICP_HIST - 1)]);
+  // one round trip: control block, pose and history entry are all asked for before the first of them is looked at
+  int c[12], o[12];
+#pragma unroll
+  for (int i = 0; i < 12; ++i) { c[i] = cur[i]; o[i] = old[i]; }
+  int differ = 0;
+#pragma unroll
+  for (int i = 0; i < 12; ++i) differ |= c[i] ^ o[i];
+  if (skip_from != PICP_CYCLE_RUN) return;
+  const unsigned long long hits = __ballot(live && differ == 0);
+  int* put = reinterpret_cast<int*>(S->hist[k & (PICP_HIST - 1)]);
+  if (lane < 12) {
+    int mine = c[0];
+#pragma unroll
+    for (int i = 1; i < 12; ++i) mine = lane == i ? c[i] : mine;
+    put[lane] = mine;
+  }
+  if (hits == 0 || detected_at != 0 || lane != 0) return;
+  const int period = __ffsll((long long)hits);             // lane l <-> round k - 1 - l: the lowest set lane is the latest round
+  const int j = k - period;
+  int* out = reinterpret_cast<int*>(&S->cyc);
+  const bool skips = it + 1 < last;
+  out[offsetof(PicpCycle, detected_at) / 4] = it;
+  out[offsetof(PicpCycle, period) / 4] = period;
+  out[offsetof(PicpCycle, skipped) / 4] = skips ? last - 1 - it : 0;
+  if (skips) {
+    out[offsetof(PicpCycle, target) / 4] = j + (last - j) % period;
+    out[offsetof(PicpCycle, skip_from) / 4] = it + 1;
+  }
+}
+
+// CYCLE: (PRE, single problem, not FINISH) the launch may carry the detector workgroup at block index nb, and -- told so by
+// `cyc` -- reads the control word: see picp_cycle_detect.  `last` is the index of the solve's last round launch.
+template <bool PRE, bool FINISH, bool PINHOLE, bool KEEP, bool BATCH, bool GATHER = false, bool TALLY = false, bool CYCLE = false>
 __device__ __forceinline__ void picp_round_body(const PicpParams* __restrict__ P, PicpState* S, PackedCorr pk,
                                                 float* partials, int it, int nb, const RoundBatch& rb,
-                                                const RoundGather& gt = RoundGather{}) {
+                                                const RoundGather& gt = RoundGather{}, int last = 0, int cyc = 0) {
   static_assert(!GATHER || (!PRE && !FINISH && !BATCH), "the gathering round is the first round of one problem");
   static_assert(!TALLY || (PRE && !BATCH), "the tally is read from the rows of a gathering round");
+  static_assert(!CYCLE || (PRE && !FINISH && !BATCH), "cycle detection belongs to the rounds of one problem that read rows");
   if (BATCH) {
     const size_t p = blockIdx.y;
     S += p;
@@ -359,9 +419,16 @@ __device__ __forceinline__ void picp_round_body(const PicpParams* __restrict__ P
   __shared__ float s_stat[4];
   __shared__ int s_bad;
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  if (CYCLE && __builtin_expect((int)blockIdx.x == nb, 0)) {      // the detector workgroup: no row of its own, nothing of a round
+    picp_cycle_detect(S, it, last);
+    return;
+  }
   if (GATHER) {
     if (tid == 0) s_bad = 0;
     __syncthreads();
+    // a solve starts with every round running and nothing to report (picp_cycle_detect)
+    if (blockIdx.x == 0 && tid < (int)(sizeof(PicpCycle) / 4))
+      reinterpret_cast<int*>(&S->cyc)[tid] = tid == (int)(offsetof(PicpCycle, skip_from) / 4) ? PICP_CYCLE_RUN : 0;
   }
   VO_STAMP(0);
   VO_STAMP_REAL(7);
@@ -381,6 +448,10 @@ __device__ __forceinline__ void picp_round_body(const PicpParams* __restrict__ P
   float damping = P->damping;
   int n = gathers ? gt.n_max : P->n_corr;
   if (BATCH) n = rb.n_pairs[blockIdx.y];
+  // the cycle control word and the target round: two more scalar loads beside the parameter block (TALLY: round 1 never skips)
+  int skip_from = PICP_CYCLE_RUN, target = 0;
+  // (loaded whether or not `cyc`: a branch here would put a wait in front of the row loads)
+  if (CYCLE && !TALLY) { skip_from = S->cyc.skip_from; target = S->cyc.target; }
   if (PRE) __builtin_amdgcn_sched_barrier(0);
 
   // (1) The previous launch's workgroup partials (nb >= 1 rows of 32 floats, zero-padded to
@@ -470,6 +541,17 @@ __device__ __forceinline__ void picp_round_body(const PicpParams* __restrict__ P
     pk.arr(0)[i] = x; pk.arr(1)[i] = y; pk.arr(2)[i] = z; pk.arr(3)[i] = u; pk.arr(4)[i] = v;
   };
   asm volatile("" : "+s"(damping), "+s"(nb));
+  // state SKIP: a launch before the last one has nothing to do (its rows and its pose have occurred before; nobody reads
+  // them); the last one takes its pose from the history instead of the rows and goes on as ever.  Wave-uniform, and the same
+  // in every workgroup: the word was written by an earlier launch.
+  bool from_hist = false;
+  if (CYCLE && !TALLY) {
+    asm volatile("" : "+s"(skip_from), "+s"(target));
+    if (cyc && it >= skip_from) {
+      if (it < last) return;                                  // (behind the issue of the row loads: in front of it measured slower)
+      from_hist = true;
+    }
+  }
   if (!GATHER) asm volatile("" : "+s"(n));                  // (the gathering round's count goes through its own logic above)
   CamBounds cb = cam_bounds(cam);
   if (!FINISH) {
@@ -482,7 +564,7 @@ __device__ __forceinline__ void picp_round_body(const PicpParams* __restrict__ P
   bool have = !FINISH && i < n;
   // Where the grid covers the call (the headline's case) a thread has one correspondence and the linearisation is straight-line
   // code; beyond the grid cap the threads loop.  Wave-uniform.
-  const int stride = gridDim.x * PICP_BLOCK;
+  const int stride = nb * PICP_BLOCK;                       // (nb, not gridDim.x: a launch may carry the detector workgroup)
   const bool one_each = stride >= n;
   unsigned long long at[5];
 #pragma unroll
@@ -517,7 +599,14 @@ __device__ __forceinline__ void picp_round_body(const PicpParams* __restrict__ P
   }
 
   Pose T;
-  if (PRE) {
+  if (CYCLE && !TALLY && from_hist) {
+    // the pose of this round has occurred before: hist[target] stands for rows, sums and tail (vector loads, as the detector's)
+    int vz = 0;
+    asm volatile("" : "+v"(vz));
+    const Pose Th = load_pose12(S->hist[target & (PICP_HIST - 1)] + vz);
+    if (tid == 0 && blockIdx.x == 0) store_pose12(S->pose[it & (PICP_SLOTS - 1)], Th);
+    T = uniform_pose(Th);
+  } else if (PRE) {
     VO_STAMP(1);
     // (5) stage the 32 group sums transposed: s_stg[slot*36 + group], so that one slot's 32
     // values are eight conflict-free 16-B reads.
@@ -633,15 +722,19 @@ __device__ __forceinline__ void picp_round_body(const PicpParams* __restrict__ P
 template <bool PRE, bool FINISH, bool PINHOLE, bool KEEP>
 __global__ __launch_bounds__(PICP_BLOCK) void picp_round_kernel(const PicpParams* __restrict__ P, PicpState* S,
                                                                 float* pk_base, size_t pk_cap, float* partials, int it,
-                                                                int nb) {
-  picp_round_body<PRE, FINISH, PINHOLE, KEEP, false>(P, S, PackedCorr{pk_base, pk_cap}, partials, it, nb, RoundBatch{});
+                                                                int nb, int last, int cyc) {
+  // (last, cyc: cycle detection -- the index of the solve's last round launch, and whether this solve detects at all; 0, 0
+  // from the finishing launch and from the chain rounds of vo_picp_one_round)
+  picp_round_body<PRE, FINISH, PINHOLE, KEEP, false, false, false, PRE && !FINISH>(P, S, PackedCorr{pk_base, pk_cap}, partials, it, nb,
+                                                                        RoundBatch{}, RoundGather{}, last, cyc);
 }
 
 // round 1 (or the finishing launch) of a solve, behind the round that may have gathered
 template <bool FINISH, bool PINHOLE, bool KEEP>
 __global__ __launch_bounds__(PICP_BLOCK) void picp_tally_round_kernel(const PicpParams* __restrict__ P, PicpState* S, float* pk_base,
                                                                       size_t pk_cap, float* partials, int it, int nb) {
-  picp_round_body<true, FINISH, PINHOLE, KEEP, false, false, true>(P, S, PackedCorr{pk_base, pk_cap}, partials, it, nb, RoundBatch{});
+  // (round 1 may carry the detector workgroup -- it stores pose 0 into the history -- but never skips: no control word here)
+  picp_round_body<true, FINISH, PINHOLE, KEEP, false, false, true, !FINISH>(P, S, PackedCorr{pk_base, pk_cap}, partials, it, nb, RoundBatch{});
 }
 
 // the first round of a solve, with the gather in it when `on` (a launch per solve: its arguments beyond the preloaded ones are
@@ -771,24 +864,27 @@ static bool picp_small_enabled() {
 
 template <bool PINHOLE, bool KEEP>
 static void launch_rounds_t(hipStream_t st, PicpParams* d_params, PicpState* d_state, PackedCorr pk,
-                            float* d_partials, int grid, int n_iters, const PicpGather& g, int part) {
+                            float* d_partials, int grid, int n_iters, const PicpGather& g, int part, bool cycle) {
+  // With cycle detection every launch behind round 0 carries one more workgroup, the detector (picp_cycle_detect); the rounds
+  // are told the last round launch's index.  Round 0 resets the control block whether or not detection is on.
+  const int cyc = cycle ? 1 : 0, last = n_iters - 1;
   // round 0 gathers when g.on; the launch that reads its rows also takes the tally of dropped pairs
   if (part != PICP_AFTER_ROUND0)
     hipLaunchKernelGGL((picp_gather_round_kernel<PINHOLE, KEEP>), dim3(grid), dim3(PICP_BLOCK), 0, st, d_params, d_state, pk.base,
                        pk.cap, d_partials, grid, g.pairs, g.d_n, g.n_max, g.world, g.n_world, g.meas, g.n_meas, g.T0, g.on);
   if (part == PICP_ROUND0) return;
   if (n_iters > 1)
-    hipLaunchKernelGGL((picp_tally_round_kernel<false, PINHOLE, KEEP>), dim3(grid), dim3(PICP_BLOCK), 0, st,
+    hipLaunchKernelGGL((picp_tally_round_kernel<false, PINHOLE, KEEP>), dim3(grid + cyc), dim3(PICP_BLOCK), 0, st,
                        d_params, d_state, pk.base, pk.cap, d_partials, 1, grid);
   for (int it = 2; it < n_iters; ++it)
-    hipLaunchKernelGGL((picp_round_kernel<true, false, PINHOLE, KEEP>), dim3(grid), dim3(PICP_BLOCK), 0, st,
-                       d_params, d_state, pk.base, pk.cap, d_partials, it, grid);
+    hipLaunchKernelGGL((picp_round_kernel<true, false, PINHOLE, KEEP>), dim3(grid + cyc), dim3(PICP_BLOCK), 0, st,
+                       d_params, d_state, pk.base, pk.cap, d_partials, it, grid, last, cyc);
   if (n_iters == 1)
     hipLaunchKernelGGL((picp_tally_round_kernel<true, false, false>), dim3(1), dim3(PICP_BLOCK), 0, st, d_params,
                        d_state, pk.base, pk.cap, d_partials, n_iters, grid);
   else
     hipLaunchKernelGGL((picp_round_kernel<true, true, false, false>), dim3(1), dim3(PICP_BLOCK), 0, st, d_params,
-                       d_state, pk.base, pk.cap, d_partials, n_iters, grid);
+                       d_state, pk.base, pk.cap, d_partials, n_iters, grid, 0, 0);
 }
 
 // ---- a chain of rounds without its finishing launch (vo_picp_one_round, capi.hip) ------------------------------------
@@ -803,7 +899,7 @@ hipError_t launch_picp_chain_round(hipStream_t st, const PicpParams* d_params, P
                                    float* d_partials, int grid, int it, bool pinhole, bool keep_outliers) {
   const dim3 g(grid), b(PICP_BLOCK);
 #define VO_CHAIN_LAUNCH(PRE, PH, KP) \
-  hipLaunchKernelGGL((picp_round_kernel<PRE, false, PH, KP>), g, b, 0, st, d_params, d_state, pk.base, pk.cap, d_partials, it, grid)
+  hipLaunchKernelGGL((picp_round_kernel<PRE, false, PH, KP>), g, b, 0, st, d_params, d_state, pk.base, pk.cap, d_partials, it, grid, 0, 0)
   if (it > 0) {
     if (pinhole) { if (keep_outliers) VO_CHAIN_LAUNCH(true, true, true); else VO_CHAIN_LAUNCH(true, true, false); }
     else { if (keep_outliers) VO_CHAIN_LAUNCH(true, false, true); else VO_CHAIN_LAUNCH(true, false, false); }
@@ -819,13 +915,13 @@ hipError_t launch_picp_chain_round(hipStream_t st, const PicpParams* d_params, P
 hipError_t launch_picp_finish(hipStream_t st, const PicpParams* d_params, PicpState* d_state, PackedCorr pk,
                               float* d_partials, int grid, int n_rounds) {
   hipLaunchKernelGGL((picp_round_kernel<true, true, false, false>), dim3(1), dim3(PICP_BLOCK), 0, st, d_params, d_state,
-                     pk.base, pk.cap, d_partials, n_rounds, grid);
+                     pk.base, pk.cap, d_partials, n_rounds, grid, 0, 0);
   return hipGetLastError();
 }
 
 hipError_t launch_picp_rounds(hipStream_t st, PicpParams* d_params, PicpState* d_state,
                               PackedCorr pk, float* d_partials, int grid, int n_iters, bool pinhole,
-                              bool keep_outliers, const PicpGather& gt, int part) {
+                              bool keep_outliers, const PicpGather& gt, int part, bool cycle) {
   if (n_iters <= 0) return hipSuccess;
   if (grid == 1 && picp_small_enabled()) {      // one workgroup's worth of correspondences (picp_grid_for): all rounds in one launch
     if (part != PICP_WHOLE) return hipErrorInvalidValue;      // (never in parts: picp_rounds_chain(grid) is false)
@@ -837,11 +933,11 @@ hipError_t launch_picp_rounds(hipStream_t st, PicpParams* d_params, PicpState* d
     return hipGetLastError();
   }
   if (pinhole) {
-    if (keep_outliers) launch_rounds_t<true, true>(st, d_params, d_state, pk, d_partials, grid, n_iters, gt, part);
-    else launch_rounds_t<true, false>(st, d_params, d_state, pk, d_partials, grid, n_iters, gt, part);
+    if (keep_outliers) launch_rounds_t<true, true>(st, d_params, d_state, pk, d_partials, grid, n_iters, gt, part, cycle);
+    else launch_rounds_t<true, false>(st, d_params, d_state, pk, d_partials, grid, n_iters, gt, part, cycle);
   } else {
-    if (keep_outliers) launch_rounds_t<false, true>(st, d_params, d_state, pk, d_partials, grid, n_iters, gt, part);
-    else launch_rounds_t<false, false>(st, d_params, d_state, pk, d_partials, grid, n_iters, gt, part);
+    if (keep_outliers) launch_rounds_t<false, true>(st, d_params, d_state, pk, d_partials, grid, n_iters, gt, part, cycle);
+    else launch_rounds_t<false, false>(st, d_params, d_state, pk, d_partials, grid, n_iters, gt, part, cycle);
   }
   return hipGetLastError();
 }

@@ -70,6 +70,20 @@ struct PicpParams {
   int n_corr;
 };
 
+// Cycle detection of a launch-per-round solve (picp.hip, "rounds whose pose has already occurred").  The control block is
+// reset by round 0 of every solve and written by the detector workgroup alone.  Its state is ONE word, the first launch
+// that skips: PICP_CYCLE_RUN while every round runs, d + 1 once the detector of launch d has found a repeat -- the
+// workgroups of launch d itself, which read the word while the detector writes it, take either value as "run".
+constexpr int PICP_HIST = 64;                  // poses kept (a power of two, at most a wave's lanes): repeats up to 63 rounds back are seen
+constexpr int PICP_CYCLE_RUN = 0x7fffffff;
+struct PicpCycle {
+  int skip_from;       // launches it >= skip_from skip (state SKIP), PICP_CYCLE_RUN: none does (state RUN)
+  int target;          // round whose pose (hist[target % PICP_HIST]) is the pose of the last round launch
+  int detected_at;     // reporting: launch that first found a repeat (0: none), the repeat's period, launches skipped
+  int period;
+  int skipped;
+};
+
 // Solver state in device memory.
 struct PicpState {
   float pose[PICP_SLOTS][12];   // ring (slot = round % PICP_SLOTS; slot 0 also holds the finished pose): R (col-major 3x3) then t
@@ -79,6 +93,8 @@ struct PicpState {
   int n_in;
   int n_bad;           // correspondences whose indices were out of range (dropped)
   float T16[16];       // pose after the last solve as a column-major 4x4 (written by the finish launch)
+  PicpCycle cyc;       // directly behind T16: include/vo_hip.h documents this layout at vo_picp_pose_dev_ptr
+  float hist[PICP_HIST][12];    // hist[k % PICP_HIST]: the pose after round k of this solve (pose[k % PICP_SLOTS] when it was written)
 #ifdef VO_STAMPS
   // diagnostic build only (make STAMPS=1 -> libvo_hip_stamps.so, tools/stamp_rounds.py):
   // s_memtime at phase boundaries of workgroup 0, per round
@@ -118,10 +134,12 @@ struct PicpGather {
 // part: the whole solve, round 0 alone, or everything behind round 0 -- the host replays the latter as a captured graph behind
 // a plain launch of round 0, whose arguments are the caller's and change from call to call.  The parts exist where the rounds
 // are launches of their own (picp_rounds_chain(grid)).
+// cycle: launches behind round 0 carry the detector workgroup and skip rounds whose pose has already occurred in this solve
+// (picp.hip, picp_cycle_detect); results are the same bytes either way.
 constexpr int PICP_WHOLE = 0, PICP_ROUND0 = 1, PICP_AFTER_ROUND0 = 2;
 hipError_t launch_picp_rounds(hipStream_t st, PicpParams* d_params, PicpState* d_state,
                               PackedCorr pk, float* d_partials, int grid, int n_iters, bool pinhole,
-                              bool keep_outliers, const PicpGather& g = PicpGather{}, int part = PICP_WHOLE);
+                              bool keep_outliers, const PicpGather& g = PicpGather{}, int part = PICP_WHOLE, bool cycle = false);
 
 int picp_grid_for(int n_corr, int n_cu);
 
