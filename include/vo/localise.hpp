@@ -2,11 +2,14 @@
 // not a reference interface (the reference never reads its map back).  DeviceMap owns a vo_map: update() is
 // PointCloudVector<3>::update, lookup() answers "which entries of the map does this frame see?", localise() "where is this
 // camera in the map?" -- lookup -> P3P RANSAC -> PICP rounds, from the frame alone; refine() re-estimates the map's points from
-// all the frames that see them, the poses fixed (vo_map_refine).  A frame that cannot be localised is a
+// all the frames that see them, the poses fixed (vo_map_refine), refinePoses() the poses from the map (vo_map_refine_poses),
+// adjust() alternates the two (vo_map_adjust).  A frame that cannot be localised is a
 // status in the statistics, not an exception; vo::Error is thrown where the C call refuses.
 #pragma once
 
 #include <cstdint>
+#include <limits>
+#include <string>
 #include <vector>
 
 #include "camera.hpp"
@@ -45,6 +48,28 @@ inline const char* refine_status_name(int status) {
   static const char* names[] = {"OK", "UNSEEN", "FEW_OBS", "BEHIND", "NOT_FINITE", "COST_ROSE"};
   return status >= 0 && status < 6 ? names[status] : "?";
 }
+
+//! vo_map_refine_poses: motion-only adjustment of the frames' poses on the same cost (the points are fixed)
+struct PoseRefineOptions {
+  int n_rounds = 10;
+  int min_obs = 3;
+  float huber_px = 0;   //!< 0: squared error
+  float damping = 0;
+};
+
+inline const char* pose_refine_status_name(int status) {
+  static const char* names[] = {"OK", "FIXED", "FEW_OBS", "BEHIND", "NOT_FINITE", "COST_ROSE"};
+  return status >= 0 && status < 6 ? names[status] : "?";
+}
+
+//! vo_map_adjust: the alternation of the two halves.  A descent, not a fast one.
+struct AdjustOptions {
+  int n_sweeps = 6;
+  int pose_rounds = 2, point_rounds = 2;
+  int min_obs_pose = 3, min_obs_point = 3;
+  float huber_px = 0;
+  float damping = 0;
+};
 
 class DeviceMap {
  public:
@@ -148,29 +173,54 @@ class DeviceMap {
   void refine(const Camera& cam, const std::vector<Vector2fVector>& pixels, const std::vector<Vector10fVector>& appearances,
               const IsometryVector& poses, const RefineOptions& opt = RefineOptions(), vo_map_refine_stats* stats = nullptr,
               std::vector<int32_t>* status = nullptr) {
-    const size_t F = pixels.size();
-    if (appearances.size() != F || poses.size() != F) throw Error(VO_ERR_INVALID_ARG, "DeviceMap::refine: per-frame arrays differ in size");
-    size_t cap = 0;
-    for (size_t f = 0; f < F; ++f) {
-      if (pixels[f].size() != appearances[f].size()) throw Error(VO_ERR_INVALID_ARG, "DeviceMap::refine: pixels and appearances differ in size");
-      if (pixels[f].size() > cap) cap = pixels[f].size();
-    }
-    std::vector<float> uv(F * cap * 2 + 2, 0.f), app(F * cap * 10 + 10, 0.f), T(F * 16 + 16, 0.f);
-    std::vector<int> n(F + 1, 0);
-    for (size_t f = 0; f < F; ++f) {
-      n[f] = (int)pixels[f].size();
-      for (size_t i = 0; i < pixels[f].size(); ++i) {
-        for (int k = 0; k < 2; ++k) uv[(f * cap + i) * 2 + k] = pixels[f][i][k];
-        for (int k = 0; k < 10; ++k) app[(f * cap + i) * 10 + k] = appearances[f][i][k];
-      }
-      for (int k = 0; k < 16; ++k) T[16 * f + k] = poses[f].data()[k];
-    }
+    const Window w = pack("DeviceMap::refine", pixels, appearances, poses);
     if (status) status->assign((size_t)size(), -1);
     const vo_map_refine_params prm{opt.n_rounds, opt.min_obs, opt.huber_px, opt.damping};
     vo_map_refine_stats s{};
-    check(vo_map_refine(h_, (int)F, cam.cameraMatrix().data(), uv.data(), app.data(), n.data(), (int)cap, T.data(), &prm,
+    check(vo_map_refine(h_, (int)w.F, cam.cameraMatrix().data(), w.uv.data(), w.app.data(), w.n.data(), (int)w.cap, w.T.data(), &prm,
                         status && !status->empty() ? status->data() : nullptr, &s), "vo_map_refine");
     if (stats) *stats = s;
+  }
+
+  //! every frame's pose (p_cam = T p_map) re-estimated, in place, from all its rows that hit an entry, the map fixed
+  //! (vo_map_refine_poses: the other half of the same cost).  fixed: one flag per frame, or null for none.  *status receives
+  //! one VO_MAP_POSE_* per frame; only OK poses are replaced.  *information: per frame the damped 6x6 H of the last solved
+  //! round, column-major (36 doubles; NaN for a frame that never solved).
+  void refinePoses(const Camera& cam, const std::vector<Vector2fVector>& pixels, const std::vector<Vector10fVector>& appearances,
+                   IsometryVector& poses, const std::vector<uint8_t>* fixed = nullptr, const PoseRefineOptions& opt = PoseRefineOptions(),
+                   vo_map_pose_refine_stats* stats = nullptr, std::vector<int32_t>* status = nullptr,
+                   std::vector<double>* information = nullptr) {
+    Window w = pack("DeviceMap::refinePoses", pixels, appearances, poses, fixed);
+    if (status) status->assign(w.F, -1);
+    if (information) information->assign(w.F * 36, std::numeric_limits<double>::quiet_NaN());
+    const vo_map_pose_refine_params prm{opt.n_rounds, opt.min_obs, opt.huber_px, opt.damping};
+    vo_map_pose_refine_stats s{};
+    check(vo_map_refine_poses(h_, (int)w.F, cam.cameraMatrix().data(), w.uv.data(), w.app.data(), w.n.data(), (int)w.cap, w.T.data(),
+                              fixed ? fixed->data() : nullptr, &prm, status ? status->data() : nullptr,
+                              information ? information->data() : nullptr, &s), "vo_map_refine_poses");
+    for (size_t f = 0; f < w.F; ++f)
+      for (int k = 0; k < 16; ++k) poses[f].data()[k] = w.T[16 * f + k];
+    if (stats) *stats = s;
+  }
+
+  //! block-coordinate bundle adjustment (vo_map_adjust): opt.n_sweeps times refinePoses in place on `poses`, then refine in
+  //! place on the map.  Hold the gauge with `fixed`: with no frame held the solution drifts in its seven free parameters.
+  //! *sweeps receives one pair of statistics per sweep; the statuses are those of the last sweep.
+  void adjust(const Camera& cam, const std::vector<Vector2fVector>& pixels, const std::vector<Vector10fVector>& appearances,
+              IsometryVector& poses, const std::vector<uint8_t>* fixed, const AdjustOptions& opt = AdjustOptions(),
+              std::vector<vo_map_adjust_stats>* sweeps = nullptr, std::vector<int32_t>* pose_status = nullptr,
+              std::vector<int32_t>* point_status = nullptr) {
+    Window w = pack("DeviceMap::adjust", pixels, appearances, poses, fixed);
+    if (pose_status) pose_status->assign(w.F, -1);
+    if (point_status) point_status->assign((size_t)size(), -1);
+    const vo_map_adjust_params prm{opt.n_sweeps, opt.pose_rounds, opt.point_rounds, opt.min_obs_pose, opt.min_obs_point, opt.huber_px, opt.damping};
+    std::vector<vo_map_adjust_stats> s((size_t)(opt.n_sweeps > 0 ? opt.n_sweeps : 1));
+    check(vo_map_adjust(h_, (int)w.F, cam.cameraMatrix().data(), w.uv.data(), w.app.data(), w.n.data(), (int)w.cap, w.T.data(),
+                        fixed ? fixed->data() : nullptr, &prm, pose_status ? pose_status->data() : nullptr,
+                        point_status && !point_status->empty() ? point_status->data() : nullptr, s.data()), "vo_map_adjust");
+    for (size_t f = 0; f < w.F; ++f)
+      for (int k = 0; k < 16; ++k) poses[f].data()[k] = w.T[16 * f + k];
+    if (sweeps) *sweeps = s;
   }
 
   //! the map's points and appearances in entry order
@@ -182,6 +232,37 @@ class DeviceMap {
   }
 
  private:
+  //! the frames of a window padded to the largest one, as the host forms of the refinement calls take them
+  struct Window {
+    size_t F = 0, cap = 0;
+    std::vector<float> uv, app, T;
+    std::vector<int> n;
+  };
+  static Window pack(const char* who, const std::vector<Vector2fVector>& pixels, const std::vector<Vector10fVector>& appearances,
+                     const IsometryVector& poses, const std::vector<uint8_t>* fixed = nullptr) {
+    Window w;
+    const size_t F = w.F = pixels.size();
+    if (appearances.size() != F || poses.size() != F || (fixed && fixed->size() != F))
+      throw Error(VO_ERR_INVALID_ARG, std::string(who) + ": per-frame arrays differ in size");
+    size_t cap = 0;
+    for (size_t f = 0; f < F; ++f) {
+      if (pixels[f].size() != appearances[f].size()) throw Error(VO_ERR_INVALID_ARG, std::string(who) + ": pixels and appearances differ in size");
+      if (pixels[f].size() > cap) cap = pixels[f].size();
+    }
+    w.cap = cap;
+    w.uv.assign(F * cap * 2 + 2, 0.f); w.app.assign(F * cap * 10 + 10, 0.f); w.T.assign(F * 16 + 16, 0.f);
+    w.n.assign(F + 1, 0);
+    for (size_t f = 0; f < F; ++f) {
+      w.n[f] = (int)pixels[f].size();
+      for (size_t i = 0; i < pixels[f].size(); ++i) {
+        for (int k = 0; k < 2; ++k) w.uv[(f * cap + i) * 2 + k] = pixels[f][i][k];
+        for (int k = 0; k < 10; ++k) w.app[(f * cap + i) * 10 + k] = appearances[f][i][k];
+      }
+      for (int k = 0; k < 16; ++k) w.T[16 * f + k] = poses[f].data()[k];
+    }
+    return w;
+  }
+
   vo_ctx* ctx_ = nullptr;
   vo_map* h_ = nullptr;
 };

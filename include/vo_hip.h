@@ -844,4 +844,7 @@ int vo_map_refine(vo_map *m, int n_frames, const float K[9], const float *uv, co
 #ifdef __cplusplus
 }
 #endif
+
+/* motion-only refinement of a window's poses on the map's cost and its alternation with vo_map_refine: a header of its own */
+#include "vo_map_adjust.h"
 #endif /* VO_HIP_H */

@@ -18,6 +18,11 @@ from .api import (  # noqa: F401
     MapRefineParams,
     MapRefineStats,
     MAP_REFINE_STATUS,
+    MapPoseRefineParams,
+    MapPoseRefineStats,
+    MAP_POSE_STATUS,
+    MapAdjustParams,
+    MapAdjustStats,
     PICPSolver,
     VoError,
     compute_correspondences_images,

@@ -527,6 +527,75 @@ class Map:
                                     C.byref(st)))
         return status[: st.n_entries].copy(), st.as_dict()
 
+    # ---- motion-only refinement and the alternation of the two halves (vo_map_refine_poses*, vo_map_adjust*) ----
+    @staticmethod
+    def _window(frames, poses, fixed):
+        """host frames of any sizes padded to a common n_max: (F, cap, uv, app, n, T (F, 16) column-major, mask or None)"""
+        F = len(frames)
+        if F < 1 or F != len(poses) or (fixed is not None and len(fixed) != F):
+            raise ValueError("one pose (and one mask byte) per frame, at least one frame")
+        n = np.array([len(_f32(a, (-1, 10))) for _, a in frames], np.int32)
+        cap = int(n.max())
+        uv = np.zeros((F, max(cap, 1), 2), np.float32)
+        app = np.zeros((F, max(cap, 1), 10), np.float32)
+        for f, (p, a) in enumerate(frames):
+            uv[f, : n[f]] = _f32(p, (-1, 2))
+            app[f, : n[f]] = _f32(a, (-1, 10))
+        T = np.ascontiguousarray(np.stack([_colmajor(X, 4) for X in poses]).astype(np.float32))
+        mask = None if fixed is None else np.ascontiguousarray(np.asarray(fixed).astype(bool).astype(np.uint8))
+        return F, cap, uv, app, n, T, mask
+
+    def refine_poses_batch_dev(self, camera: Camera, n_frames, d_uv, uv_stride, d_app, app_stride, n_max, d_n, d_T16_in, d_fixed,
+                               params: "MapPoseRefineParams", d_T16_out, d_status_out, d_H_out, d_stats):
+        """vo_map_refine_poses_batch_dev on device pointers (ints; d_n, d_fixed, d_status_out and d_H_out may be None; d_T16_out
+        may be d_T16_in; strides in pixels / rows): enqueues and returns.  d_stats: 48 bytes (MapPoseRefineStats)."""
+        v = lambda d: C.c_void_p(d) if d else None
+        _chk(self.lib.vo_map_refine_poses_batch_dev(self.h, C.c_int(n_frames), _ptr(_colmajor(camera._K, 3)), v(d_uv), C.c_size_t(uv_stride),
+                                                    v(d_app), C.c_size_t(app_stride), C.c_int(n_max), v(d_n), v(d_T16_in), v(d_fixed),
+                                                    C.byref(params), v(d_T16_out), v(d_status_out), v(d_H_out), v(d_stats)))
+
+    def refine_poses(self, camera: Camera, frames, poses, fixed=None, n_rounds=10, min_obs=3, huber_px=0.0, damping=0.0, want_H=False):
+        """vo_map_refine_poses: every frame's pose (4x4, p_cam = T p_map) re-estimated from all its rows that hit an entry, the
+        map fixed; `fixed` (one truth value per frame, or None) holds frames.  Returns (poses (F, 4, 4) float32, status (F,)
+        int32: MAP_POSE_STATUS names the codes, stats dict) and, with want_H, the information matrices (F, 6, 6) float64 (NaN
+        for a frame that never solved)."""
+        F, cap, uv, app, n, T, mask = self._window(frames, poses, fixed)
+        status = np.full(F, -1, np.int32)
+        H = np.full((F, 36), np.nan, np.float64)
+        st = MapPoseRefineStats()
+        prm = MapPoseRefineParams(int(n_rounds), int(min_obs), float(huber_px), float(damping))
+        _chk(self.lib.vo_map_refine_poses(self.h, C.c_int(F), _ptr(_colmajor(camera._K, 3)), _ptr(uv[:, :cap]) if cap else None,
+                                          _ptr(app[:, :cap]) if cap else None, _ptr(n), C.c_int(cap), _ptr(T),
+                                          _ptr(mask) if mask is not None else None, C.byref(prm), _ptr(status),
+                                          _ptr(H) if want_H else None, C.byref(st)))
+        out = (T.reshape(F, 4, 4).transpose(0, 2, 1).copy(), status, st.as_dict())
+        return out + (H.reshape(F, 6, 6),) if want_H else out
+
+    def adjust_batch_dev(self, camera: Camera, n_frames, d_uv, uv_stride, d_app, app_stride, n_max, d_n, d_T16, d_fixed,
+                         params: "MapAdjustParams", d_pose_status_out, d_point_status_out, d_stats):
+        """vo_map_adjust_batch_dev on device pointers: d_T16 and the map in place; d_stats: n_sweeps x 96 bytes (MapAdjustStats)"""
+        v = lambda d: C.c_void_p(d) if d else None
+        _chk(self.lib.vo_map_adjust_batch_dev(self.h, C.c_int(n_frames), _ptr(_colmajor(camera._K, 3)), v(d_uv), C.c_size_t(uv_stride),
+                                              v(d_app), C.c_size_t(app_stride), C.c_int(n_max), v(d_n), v(d_T16), v(d_fixed),
+                                              C.byref(params), v(d_pose_status_out), v(d_point_status_out), v(d_stats)))
+
+    def adjust(self, camera: Camera, frames, poses, fixed=None, n_sweeps=6, pose_rounds=2, point_rounds=2, min_obs_pose=3,
+               min_obs_point=3, huber_px=0.0, damping=0.0):
+        """vo_map_adjust: n_sweeps times the pose half (refine_poses, in place on the poses) and then the point half (refine, in
+        place on the map).  Hold the gauge with `fixed`: with no frame held the solution drifts.  Returns (poses (F, 4, 4)
+        float32, pose status (F,), point status (size,), [per sweep dict(poses=stats dict, points=stats dict)])."""
+        F, cap, uv, app, n, T, mask = self._window(frames, poses, fixed)
+        pose_status = np.full(F, -1, np.int32)
+        point_status = np.full(max(len(self), 1), -1, np.int32)
+        st = (MapAdjustStats * int(n_sweeps))() if n_sweeps >= 1 else (MapAdjustStats * 1)()
+        prm = MapAdjustParams(int(n_sweeps), int(pose_rounds), int(point_rounds), int(min_obs_pose), int(min_obs_point), float(huber_px),
+                              float(damping))
+        _chk(self.lib.vo_map_adjust(self.h, C.c_int(F), _ptr(_colmajor(camera._K, 3)), _ptr(uv[:, :cap]) if cap else None,
+                                    _ptr(app[:, :cap]) if cap else None, _ptr(n), C.c_int(cap), _ptr(T),
+                                    _ptr(mask) if mask is not None else None, C.byref(prm), _ptr(pose_status), _ptr(point_status), st))
+        sweeps = [dict(poses=s.poses.as_dict(), points=s.points.as_dict()) for s in st]
+        return T.reshape(F, 4, 4).transpose(0, 2, 1).copy(), pose_status, point_status[: st[0].points.n_entries].copy(), sweeps
+
 
 class MapLocaliseStats(C.Structure):
     """vo_map_localise_stats (include/vo_hip.h)"""
@@ -557,6 +626,37 @@ class MapRefineStats(C.Structure):
 
 assert C.sizeof(MapRefineParams) == 16 and C.sizeof(MapRefineStats) == 48
 MAP_REFINE_STATUS = ("OK", "UNSEEN", "FEW_OBS", "BEHIND", "NOT_FINITE", "COST_ROSE")      # VO_MAP_REFINE_*
+
+
+class MapPoseRefineParams(C.Structure):
+    """vo_map_pose_refine_params (include/vo_map_adjust.h)"""
+    _fields_ = [("n_rounds", C.c_int32), ("min_obs", C.c_int32), ("huber_px", C.c_float), ("damping", C.c_float)]
+
+
+class MapPoseRefineStats(C.Structure):
+    """vo_map_pose_refine_stats (include/vo_map_adjust.h)"""
+    _fields_ = [("n_frames", C.c_int32), ("n_obs", C.c_int32), ("by_status", C.c_int32 * 6), ("cost_before", C.c_double),
+                ("cost_after", C.c_double)]
+
+    def as_dict(self):
+        return dict(n_frames=self.n_frames, n_obs=self.n_obs, by_status=list(self.by_status), cost_before=self.cost_before,
+                    cost_after=self.cost_after)
+
+
+class MapAdjustParams(C.Structure):
+    """vo_map_adjust_params (include/vo_map_adjust.h)"""
+    _fields_ = [("n_sweeps", C.c_int32), ("pose_rounds", C.c_int32), ("point_rounds", C.c_int32), ("min_obs_pose", C.c_int32),
+                ("min_obs_point", C.c_int32), ("huber_px", C.c_float), ("damping", C.c_float)]
+
+
+class MapAdjustStats(C.Structure):
+    """vo_map_adjust_stats (include/vo_map_adjust.h): one sweep"""
+    _fields_ = [("poses", MapPoseRefineStats), ("points", MapRefineStats)]
+
+
+assert C.sizeof(MapPoseRefineParams) == 16 and C.sizeof(MapPoseRefineStats) == 48
+assert C.sizeof(MapAdjustParams) == 28 and C.sizeof(MapAdjustStats) == 96
+MAP_POSE_STATUS = ("OK", "FIXED", "FEW_OBS", "BEHIND", "NOT_FINITE", "COST_ROSE")          # VO_MAP_POSE_*
 
 
 def triangulate_points(k, X, correspondences, p1_img, p2_img, app2=None, want_pairs=True,

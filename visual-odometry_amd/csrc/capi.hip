@@ -2123,6 +2123,7 @@ struct vo_map {
   DevBuf loc_ws;                // vo_map_localise*: what passes from stage to stage (hits, gathered points, winner, pairs handed on)
   vo_picp* solver = nullptr;    // vo_map_localise[_dev]: made by the first call
   DevBuf ref_ws;                // vo_map_refine*: the entries seen, the observation lists, status and cost per entry
+  DevBuf pose_ws;               // vo_map_refine_poses*: the entries seen, status, observation count and cost per frame
 };
 
 constexpr int MAP_MAX_ENTRIES = 1 << 29;      // 2.5 x that many table slots still fit 32 bits
@@ -2215,7 +2216,7 @@ int vo_map_destroy(vo_map* m) {
   map_free_arrays(m->d);
   if (m->d.hdr) (void)hipFree(m->d.hdr);
   if (m->hist) (void)hipFree(m->hist);
-  m->scratch.release(); m->up_xyz.release(); m->up_app.release(); m->look_ws.release(); m->loc_ws.release(); m->ref_ws.release();
+  m->scratch.release(); m->up_xyz.release(); m->up_app.release(); m->look_ws.release(); m->loc_ws.release(); m->ref_ws.release(); m->pose_ws.release();
   if (m->solver) (void)vo_picp_destroy(m->solver);
   delete m;
   return VO_OK;
@@ -2568,29 +2569,32 @@ int vo_map_localise(vo_map* m, int rows, int cols, int z_near, int z_far, const 
 // ---- structure-only refinement: the lookup of every frame, then the launches of map_refine.hip ----------------------------
 static_assert(sizeof(vo_map_refine_params) == 16 && sizeof(vo_map_refine_stats) == 48, "the statistics kernel writes eight 4-byte words and two doubles");
 
-int vo_map_refine_batch_dev(vo_map* m, int n_frames, const float K[9], const float* d_uv, size_t uv_stride, const float* d_app,
-                            size_t app_stride, int n_max, const int* d_n, const float* d_T16, const vo_map_refine_params* params,
-                            int32_t* d_status_out, float* d_xyz_out, vo_map_refine_stats* d_stats) {
-  VO_MAP_LIVE(m);
-  const char* fn = "vo_map_refine_batch_dev";
-  if (!(K && params && d_T16 && d_stats)) return fail(VO_ERR_INVALID_ARG, "%s: null argument", fn);
+// the refusals the refinement calls share (both halves of the adjustment take the same frames)
+static int refine_check(const char* fn, int n_frames, const float K[9], const float* d_uv, size_t uv_stride, const float* d_app, size_t app_stride,
+                        int n_max, const void* d_stats, int n_rounds, int most_rounds, int min_obs, int least_obs, float huber_px, float damping) {
   if (n_frames < 1 || n_frames > 65535) return fail(VO_ERR_INVALID_ARG, "%s: n_frames %d outside 1 .. 65535 (the frame is a grid dimension)", fn, n_frames);
   if (n_max < 0) return fail(VO_ERR_INVALID_ARG, "%s: negative row count", fn);
   if (n_max > 0 && !(d_uv && d_app)) return fail(VO_ERR_INVALID_ARG, "%s: null argument", fn);
   if (!aligned8(d_uv, d_app, d_stats)) return fail(VO_ERR_INVALID_ARG, "%s: device arrays must be 8-byte aligned", fn);
   if (uv_stride < (size_t)n_max || app_stride < (size_t)n_max) return fail(VO_ERR_INVALID_ARG, "%s: a stride is smaller than n_max", fn);
   if (uv_stride >= 0x7fffffff) return fail(VO_ERR_INVALID_ARG, "%s: stride too large", fn);
-  if (params->n_rounds < 0) return fail(VO_ERR_INVALID_ARG, "%s: negative n_rounds", fn);
-  if (params->min_obs < 2) return fail(VO_ERR_INVALID_ARG, "%s: min_obs must be at least 2", fn);
-  if (!(params->huber_px >= 0.f && params->huber_px <= 3.402823466e38f)) return fail(VO_ERR_INVALID_ARG, "%s: huber_px must be finite and not negative", fn);
-  if (!(params->damping >= 0.f && params->damping <= 3.402823466e38f)) return fail(VO_ERR_INVALID_ARG, "%s: damping must be finite and not negative", fn);
+  if (n_rounds < 0) return fail(VO_ERR_INVALID_ARG, "%s: negative n_rounds", fn);
+  if (n_rounds > most_rounds) return fail(VO_ERR_INVALID_ARG, "%s: more than %d rounds", fn, most_rounds);
+  if (min_obs < least_obs) return fail(VO_ERR_INVALID_ARG, "%s: min_obs must be at least %d", fn, least_obs);
+  if (!(huber_px >= 0.f && huber_px <= 3.402823466e38f)) return fail(VO_ERR_INVALID_ARG, "%s: huber_px must be finite and not negative", fn);
+  if (!(damping >= 0.f && damping <= 3.402823466e38f)) return fail(VO_ERR_INVALID_ARG, "%s: damping must be finite and not negative", fn);
   double Kinv[9];
   if (!invert_k(K, Kinv)) return fail(VO_ERR_INVALID_ARG, "%s: K is singular", fn);
+  if (app_stride >= 0x7fffffff / 10 || (long long)n_max * n_frames > (1ll << 30))      // (the lookup's own limit, met before anything is sized)
+    return fail(VO_ERR_INVALID_ARG, "%s: more than 2^30 rows in one call", fn);
+  return VO_OK;
+}
+
+// the point half's workspace, sized and laid out, and the lookup of every frame into it
+static int refine_prepare(const char* fn, vo_map* m, int n_frames, const float* d_app, size_t app_stride, int n_max, const int* d_n, MapRefineWs* out) {
   vo_ctx* c = m->ctx;
   const int bound = map_bound(m);
   MapRefineWs w = map_refine_layout(nullptr, n_frames, n_max, bound);
-  if (app_stride >= 0x7fffffff / 10 || (long long)n_max * n_frames > (1ll << 30))      // (the lookup's own limit, met before anything is sized)
-    return fail(VO_ERR_INVALID_ARG, "%s: more than 2^30 rows in one call", fn);
   const size_t look_need = sizeof(int) * map_lookup_scratch_ints(n_max, n_frames, false);
   if (c->capturing && (m->ref_ws.cap < w.bytes || (n_max > 0 && m->look_ws.cap < look_need)))
     return fail(VO_ERR_NOT_READY, "%s: the workspace would have to grow inside a graph capture (make one call with %d frames of n_max %d "
@@ -2600,16 +2604,40 @@ int vo_map_refine_batch_dev(vo_map* m, int n_frames, const float K[9], const flo
   w = map_refine_layout(m->ref_ws.p, n_frames, n_max, bound);
   if (n_max > 0)
     if (int r = vo_map_lookup_batch_dev(m, n_frames, d_app, app_stride, n_max, d_n, w.pairs, w.n_hits, nullptr, nullptr, w.ent)) return r;
+  *out = w;
+  return VO_OK;
+}
+
+// the point half's launches on a prepared workspace
+static int refine_run(vo_map* m, const MapRefineWs& w, int n_frames, const float K[9], const float* d_uv, size_t uv_stride, int n_max,
+                      const float* d_T16, int n_rounds, int min_obs, float huber_px, float damping, int32_t* d_status_out, float* d_xyz_out,
+                      vo_map_refine_stats* d_stats) {
+  vo_ctx* c = m->ctx;
   MapRefineArgs a{};
   a.w = w;
-  a.pts = m->d.pts; a.hdr = m->d.hdr; a.cap = m->d.cap; a.bound = bound;
+  a.pts = m->d.pts; a.hdr = m->d.hdr; a.cap = m->d.cap; a.bound = map_bound(m);
   a.uv = d_uv; a.uv_stride = uv_stride; a.n_max = n_max; a.n_frames = n_frames; a.T16 = d_T16;
   for (int k = 0; k < 9; ++k) a.K[k] = K[k];
-  a.n_rounds = params->n_rounds; a.min_obs = params->min_obs; a.huber = params->huber_px; a.damping = params->damping;
+  a.n_rounds = n_rounds; a.min_obs = min_obs; a.huber = huber_px; a.damping = damping;
   a.status = d_status_out ? d_status_out : w.status;
   a.xyz_out = d_xyz_out; a.stats = d_stats;
   VO_HIP_CHECK(launch_map_refine(c->stream, a, c->n_cu));
   return VO_OK;
+}
+
+int vo_map_refine_batch_dev(vo_map* m, int n_frames, const float K[9], const float* d_uv, size_t uv_stride, const float* d_app,
+                            size_t app_stride, int n_max, const int* d_n, const float* d_T16, const vo_map_refine_params* params,
+                            int32_t* d_status_out, float* d_xyz_out, vo_map_refine_stats* d_stats) {
+  VO_MAP_LIVE(m);
+  const char* fn = "vo_map_refine_batch_dev";
+  if (!(K && params && d_T16 && d_stats)) return fail(VO_ERR_INVALID_ARG, "%s: null argument", fn);
+  if (int r = refine_check(fn, n_frames, K, d_uv, uv_stride, d_app, app_stride, n_max, d_stats, params->n_rounds, INT_MAX, params->min_obs, 2,
+                           params->huber_px, params->damping))
+    return r;
+  MapRefineWs w;
+  if (int r = refine_prepare(fn, m, n_frames, d_app, app_stride, n_max, d_n, &w)) return r;
+  return refine_run(m, w, n_frames, K, d_uv, uv_stride, n_max, d_T16, params->n_rounds, params->min_obs, params->huber_px, params->damping,
+                    d_status_out, d_xyz_out, d_stats);
 }
 
 int vo_map_refine(vo_map* m, int n_frames, const float K[9], const float* uv, const float* app, const int* n_rows, int n_max,
@@ -2638,6 +2666,172 @@ int vo_map_refine(vo_map* m, int n_frames, const float K[9], const float* uv, co
     return r;
   VO_HIP_CHECK(hipMemcpyAsync(stats_out, c->out[2].p, sizeof(vo_map_refine_stats), hipMemcpyDeviceToHost, c->stream));
   if (status_out && size > 0) VO_HIP_CHECK(hipMemcpyAsync(status_out, c->out[1].p, sizeof(int32_t) * (size_t)size, hipMemcpyDeviceToHost, c->stream));
+  VO_HIP_CHECK(hipStreamSynchronize(c->stream));
+  return VO_OK;
+}
+
+// ---- motion-only refinement and the alternation of the two halves (map_pose_refine.hip) ------------------------------------
+static_assert(sizeof(vo_map_pose_refine_params) == 16 && sizeof(vo_map_pose_refine_stats) == 48 && sizeof(vo_map_adjust_params) == 28 &&
+              sizeof(vo_map_adjust_stats) == 96, "the statistics kernels write eight 4-byte words and two doubles each");
+
+// the pose half's workspace; with `ent` (the entries of a lookup already made for these frames) no lookup is enqueued
+static int pose_prepare(const char* fn, vo_map* m, int n_frames, const float* d_app, size_t app_stride, int n_max, const int* d_n,
+                        const int32_t* ent, MapPoseWs* out) {
+  vo_ctx* c = m->ctx;
+  MapPoseWs w = map_pose_layout(nullptr, n_frames, n_max, !ent);
+  const size_t look_need = sizeof(int) * map_lookup_scratch_ints(n_max, n_frames, false);
+  if (c->capturing && (m->pose_ws.cap < w.bytes || (!ent && n_max > 0 && m->look_ws.cap < look_need)))
+    return fail(VO_ERR_NOT_READY, "%s: the workspace would have to grow inside a graph capture (make one call with %d frames of n_max %d "
+                                  "on this map before capturing)", fn, n_frames, n_max);
+  if (int r = set_device(c)) return r;
+  VO_HIP_CHECK(m->pose_ws.ensure(w.bytes, c->stream));
+  w = map_pose_layout(m->pose_ws.p, n_frames, n_max, !ent);
+  if (!ent && n_max > 0)
+    if (int r = vo_map_lookup_batch_dev(m, n_frames, d_app, app_stride, n_max, d_n, w.pairs, w.n_hits, nullptr, nullptr, w.ent)) return r;
+  *out = w;
+  return VO_OK;
+}
+
+static int pose_run(vo_map* m, const MapPoseWs& w, const int32_t* ent, int n_frames, const float K[9], const float* d_uv, size_t uv_stride,
+                    int n_max, const float* d_T_in, const uint8_t* d_fixed, int n_rounds, int min_obs, float huber_px, float damping,
+                    float* d_T_out, int32_t* d_status_out, double* d_H_out, vo_map_pose_refine_stats* d_stats) {
+  vo_ctx* c = m->ctx;
+  MapPoseArgs a{};
+  a.ent = ent ? ent : w.ent; a.n_obs = w.n_obs; a.cost = w.cost;
+  a.pts = m->d.pts; a.hdr = m->d.hdr; a.cap = m->d.cap; a.bound = map_bound(m);
+  a.uv = d_uv; a.uv_stride = uv_stride; a.n_max = n_max; a.n_frames = n_frames;
+  a.T_in = d_T_in; a.T_out = d_T_out; a.fixed = d_fixed;
+  for (int k = 0; k < 9; ++k) a.K[k] = K[k];
+  a.n_rounds = n_rounds; a.min_obs = min_obs; a.huber = huber_px; a.damping = damping;
+  a.status = d_status_out ? d_status_out : w.status;
+  a.H_out = d_H_out; a.stats = d_stats;
+  VO_HIP_CHECK(launch_map_pose_refine(c->stream, a));
+  return VO_OK;
+}
+
+int vo_map_refine_poses_batch_dev(vo_map* m, int n_frames, const float K[9], const float* d_uv, size_t uv_stride, const float* d_app,
+                                  size_t app_stride, int n_max, const int* d_n, const float* d_T16_in, const uint8_t* d_fixed,
+                                  const vo_map_pose_refine_params* params, float* d_T16_out, int32_t* d_status_out, double* d_H_out,
+                                  vo_map_pose_refine_stats* d_stats) {
+  VO_MAP_LIVE(m);
+  const char* fn = "vo_map_refine_poses_batch_dev";
+  if (!(K && params && d_T16_in && d_T16_out && d_stats)) return fail(VO_ERR_INVALID_ARG, "%s: null argument", fn);
+  if (!aligned8(d_H_out)) return fail(VO_ERR_INVALID_ARG, "%s: device arrays must be 8-byte aligned", fn);
+  if (int r = refine_check(fn, n_frames, K, d_uv, uv_stride, d_app, app_stride, n_max, d_stats, params->n_rounds, VO_MAP_ADJUST_MAX_ROUNDS, params->min_obs, 3,
+                           params->huber_px, params->damping))
+    return r;
+  MapPoseWs w;
+  if (int r = pose_prepare(fn, m, n_frames, d_app, app_stride, n_max, d_n, nullptr, &w)) return r;
+  return pose_run(m, w, nullptr, n_frames, K, d_uv, uv_stride, n_max, d_T16_in, d_fixed, params->n_rounds, params->min_obs, params->huber_px,
+                  params->damping, d_T16_out, d_status_out, d_H_out, d_stats);
+}
+
+int vo_map_adjust_batch_dev(vo_map* m, int n_frames, const float K[9], const float* d_uv, size_t uv_stride, const float* d_app,
+                            size_t app_stride, int n_max, const int* d_n, float* d_T16, const uint8_t* d_fixed,
+                            const vo_map_adjust_params* p, int32_t* d_pose_status_out, int32_t* d_point_status_out,
+                            vo_map_adjust_stats* d_stats) {
+  VO_MAP_LIVE(m);
+  const char* fn = "vo_map_adjust_batch_dev";
+  if (!(K && p && d_T16 && d_stats)) return fail(VO_ERR_INVALID_ARG, "%s: null argument", fn);
+  if (p->n_sweeps < 1 || p->n_sweeps > VO_MAP_ADJUST_MAX_ROUNDS) return fail(VO_ERR_INVALID_ARG, "%s: n_sweeps outside 1 .. %d", fn, VO_MAP_ADJUST_MAX_ROUNDS);
+  if (int r = refine_check(fn, n_frames, K, d_uv, uv_stride, d_app, app_stride, n_max, d_stats, p->pose_rounds, VO_MAP_ADJUST_MAX_ROUNDS, p->min_obs_pose, 3, p->huber_px,
+                           p->damping))
+    return r;
+  if (int r = refine_check(fn, n_frames, K, d_uv, uv_stride, d_app, app_stride, n_max, d_stats, p->point_rounds, VO_MAP_ADJUST_MAX_ROUNDS, p->min_obs_point, 2,
+                           p->huber_px, p->damping))
+    return r;
+  vo_ctx* c = m->ctx;
+  if (c->capturing && m->pose_ws.cap < map_pose_layout(nullptr, n_frames, n_max, false).bytes)      // (before the point half enqueues its lookup)
+    return fail(VO_ERR_NOT_READY, "%s: the workspace would have to grow inside a graph capture (make one call with %d frames of n_max %d "
+                                  "on this map before capturing)", fn, n_frames, n_max);
+  MapRefineWs rw;
+  MapPoseWs pw;
+  if (int r = refine_prepare(fn, m, n_frames, d_app, app_stride, n_max, d_n, &rw)) return r;      // the one lookup: both halves read rw.ent
+  if (int r = pose_prepare(fn, m, n_frames, d_app, app_stride, n_max, d_n, rw.ent, &pw)) return r;
+  for (int s = 0; s < p->n_sweeps; ++s) {
+    if (int r = pose_run(m, pw, rw.ent, n_frames, K, d_uv, uv_stride, n_max, d_T16, d_fixed, p->pose_rounds, p->min_obs_pose, p->huber_px,
+                         p->damping, d_T16, d_pose_status_out, nullptr, &d_stats[s].poses))
+      return r;
+    if (int r = refine_run(m, rw, n_frames, K, d_uv, uv_stride, n_max, d_T16, p->point_rounds, p->min_obs_point, p->huber_px, p->damping,
+                           d_point_status_out, nullptr, &d_stats[s].points))
+      return r;
+  }
+  return VO_OK;
+}
+
+// the frames of a host call into the context's staging buffers in[0..4]: pixels, appearances, poses, row counts, the mask
+static int upload_window(vo_ctx* c, int n_frames, const float* uv, const float* app, const int* n_rows, int n_max, const float* T16,
+                         const uint8_t* fixed) {
+  const size_t rows = (size_t)n_frames * (size_t)n_max;
+  if (int r = upload(c, c->in[0], uv, sizeof(float) * 2 * rows)) return r;
+  if (int r = upload(c, c->in[1], app, sizeof(float) * 10 * rows)) return r;
+  if (int r = upload(c, c->in[2], T16, sizeof(float) * 16 * (size_t)n_frames)) return r;
+  if (n_rows)
+    if (int r = upload(c, c->in[3], n_rows, sizeof(int) * (size_t)n_frames)) return r;
+  if (fixed)
+    if (int r = upload(c, c->in[4], fixed, (size_t)n_frames)) return r;
+  return VO_OK;
+}
+
+int vo_map_refine_poses(vo_map* m, int n_frames, const float K[9], const float* uv, const float* app, const int* n_rows, int n_max,
+                        float* T16, const uint8_t* fixed, const vo_map_pose_refine_params* params, int32_t* status_out, double* H_out,
+                        vo_map_pose_refine_stats* stats_out) {
+  VO_MAP_LIVE(m);
+  vo_ctx* c = m->ctx;
+  VO_NOT_CAPTURING(c);
+  VO_REQUIRE(K && T16 && params && stats_out, "null argument");
+  VO_REQUIRE(n_frames >= 1 && n_frames <= 65535, "n_frames outside 1 .. 65535");
+  VO_REQUIRE(n_max >= 0 && (n_max == 0 || (uv && app)), "bad frames");
+  VO_REQUIRE((long long)n_max * n_frames <= (1ll << 30), "more than 2^30 rows in one call");
+  if (int r = set_device(c)) return r;
+  if (int r = upload_window(c, n_frames, uv, app, n_rows, n_max, T16, fixed)) return r;
+  const size_t F = (size_t)n_frames;
+  VO_HIP_CHECK(c->out[0].ensure(sizeof(double) * 36 * F, c->stream));
+  VO_HIP_CHECK(c->out[1].ensure(sizeof(int32_t) * F, c->stream));
+  VO_HIP_CHECK(c->out[2].ensure(sizeof(vo_map_pose_refine_stats) + 16, c->stream));
+  if (H_out) VO_HIP_CHECK(hipMemcpyAsync(c->out[0].p, H_out, sizeof(double) * 36 * F, hipMemcpyHostToDevice, c->stream));
+  if (int r = vo_map_refine_poses_batch_dev(m, n_frames, K, c->in[0].as<float>(), (size_t)n_max, c->in[1].as<float>(), (size_t)n_max, n_max,
+                                            n_rows ? c->in[3].as<int>() : nullptr, c->in[2].as<float>(), fixed ? c->in[4].as<uint8_t>() : nullptr,
+                                            params, c->in[2].as<float>(), status_out ? c->out[1].as<int32_t>() : nullptr,
+                                            H_out ? c->out[0].as<double>() : nullptr, c->out[2].as<vo_map_pose_refine_stats>()))
+    return r;
+  VO_HIP_CHECK(hipMemcpyAsync(stats_out, c->out[2].p, sizeof(vo_map_pose_refine_stats), hipMemcpyDeviceToHost, c->stream));
+  VO_HIP_CHECK(hipMemcpyAsync(T16, c->in[2].p, sizeof(float) * 16 * F, hipMemcpyDeviceToHost, c->stream));
+  if (status_out) VO_HIP_CHECK(hipMemcpyAsync(status_out, c->out[1].p, sizeof(int32_t) * F, hipMemcpyDeviceToHost, c->stream));
+  if (H_out) VO_HIP_CHECK(hipMemcpyAsync(H_out, c->out[0].p, sizeof(double) * 36 * F, hipMemcpyDeviceToHost, c->stream));
+  VO_HIP_CHECK(hipStreamSynchronize(c->stream));
+  return VO_OK;
+}
+
+int vo_map_adjust(vo_map* m, int n_frames, const float K[9], const float* uv, const float* app, const int* n_rows, int n_max, float* T16,
+                  const uint8_t* fixed, const vo_map_adjust_params* params, int32_t* pose_status_out, int32_t* point_status_out,
+                  vo_map_adjust_stats* stats_out) {
+  VO_MAP_LIVE(m);
+  vo_ctx* c = m->ctx;
+  VO_NOT_CAPTURING(c);
+  VO_REQUIRE(K && T16 && params && stats_out, "null argument");
+  VO_REQUIRE(params->n_sweeps >= 1 && params->n_sweeps <= VO_MAP_ADJUST_MAX_ROUNDS, "n_sweeps outside 1 .. 65536");
+  VO_REQUIRE(n_frames >= 1 && n_frames <= 65535, "n_frames outside 1 .. 65535");
+  VO_REQUIRE(n_max >= 0 && (n_max == 0 || (uv && app)), "bad frames");
+  VO_REQUIRE((long long)n_max * n_frames <= (1ll << 30), "more than 2^30 rows in one call");
+  if (int r = set_device(c)) return r;
+  if (int r = upload_window(c, n_frames, uv, app, n_rows, n_max, T16, fixed)) return r;
+  int size = 0;
+  if (int r = vo_map_size(m, &size)) return r;                // (waits: the host arrays may go away after the call)
+  const size_t F = (size_t)n_frames, S = (size_t)params->n_sweeps;
+  VO_HIP_CHECK(c->out[0].ensure(sizeof(int32_t) * F, c->stream));
+  if (point_status_out) VO_HIP_CHECK(c->out[1].ensure(sizeof(int32_t) * (size_t)(size > 0 ? size : 1), c->stream));
+  VO_HIP_CHECK(c->out[2].ensure(sizeof(vo_map_adjust_stats) * S + 16, c->stream));
+  if (int r = vo_map_adjust_batch_dev(m, n_frames, K, c->in[0].as<float>(), (size_t)n_max, c->in[1].as<float>(), (size_t)n_max, n_max,
+                                      n_rows ? c->in[3].as<int>() : nullptr, c->in[2].as<float>(), fixed ? c->in[4].as<uint8_t>() : nullptr,
+                                      params, pose_status_out ? c->out[0].as<int32_t>() : nullptr,
+                                      point_status_out ? c->out[1].as<int32_t>() : nullptr, c->out[2].as<vo_map_adjust_stats>()))
+    return r;
+  VO_HIP_CHECK(hipMemcpyAsync(stats_out, c->out[2].p, sizeof(vo_map_adjust_stats) * S, hipMemcpyDeviceToHost, c->stream));
+  VO_HIP_CHECK(hipMemcpyAsync(T16, c->in[2].p, sizeof(float) * 16 * F, hipMemcpyDeviceToHost, c->stream));
+  if (pose_status_out) VO_HIP_CHECK(hipMemcpyAsync(pose_status_out, c->out[0].p, sizeof(int32_t) * F, hipMemcpyDeviceToHost, c->stream));
+  if (point_status_out && size > 0)
+    VO_HIP_CHECK(hipMemcpyAsync(point_status_out, c->out[1].p, sizeof(int32_t) * (size_t)size, hipMemcpyDeviceToHost, c->stream));
   VO_HIP_CHECK(hipStreamSynchronize(c->stream));
   return VO_OK;
 }

@@ -88,28 +88,7 @@ __global__ __launch_bounds__(RB) void map_refine_order_kernel(MapRefineArgs a) {
   a.w.keys[off + rank] = key;
 }
 
-// a double moved between lanes by a DPP control (two 32-bit moves; no LDS traffic)
-template <int CTRL>
-__device__ __forceinline__ double refine_dpp(double x) {
-  const long long b = __double_as_longlong(x);
-  int lo = (int)b, hi = (int)(b >> 32);
-  lo = __builtin_amdgcn_update_dpp(lo, lo, CTRL, 0xf, 0xf, false);
-  hi = __builtin_amdgcn_update_dpp(hi, hi, CTRL, 0xf, 0xf, false);
-  return __longlong_as_double(((long long)hi << 32) | (long long)(unsigned)lo);
-}
-// the sum over the 16 lanes of a DPP row (= one landmark's lanes), the same bits in every lane: the neighbour in the quad
-// (quad_perm [1,0,3,2]), the other pair of the quad (quad_perm [2,3,0,1]), the mirrored half row, the mirrored row.  Every step
-// adds two values that both lanes of a pair hold, and a + b = b + a bit for bit.
-__device__ __forceinline__ double refine_row_sum(double x) {
-  static_assert(RG == 16, "a landmark's lanes are one DPP row");
-  x += refine_dpp<0xB1>(x);
-  x += refine_dpp<0x4E>(x);
-  x += refine_dpp<0x141>(x);
-  x += refine_dpp<0x140>(x);
-  return x;
-}
-
-__device__ __forceinline__ bool refine_finite(double x) { return fabs(x) <= 1.7976931348623157e308; }
+static_assert(RG == 16, "a landmark's lanes are one DPP row (refine_row_sum, vo_internal.h)");
 
 template <bool LDS>
 __global__ __launch_bounds__(RB) void map_refine_kernel(MapRefineArgs a) {

@@ -449,6 +449,57 @@ struct MapRefineArgs {
 // after the lookup has filled w.ent: lists (memset, count, offsets, scan, scatter, order), the refinement, the statistics
 hipError_t launch_map_refine(hipStream_t st, const MapRefineArgs& a, int n_cu);
 
+// a double moved between lanes by a DPP control (two 32-bit moves; no LDS traffic)
+template <int CTRL>
+__device__ __forceinline__ double refine_dpp(double x) {
+  const long long b = __double_as_longlong(x);
+  int lo = (int)b, hi = (int)(b >> 32);
+  lo = __builtin_amdgcn_update_dpp(lo, lo, CTRL, 0xf, 0xf, false);
+  hi = __builtin_amdgcn_update_dpp(hi, hi, CTRL, 0xf, 0xf, false);
+  return __longlong_as_double(((long long)hi << 32) | (long long)(unsigned)lo);
+}
+// the sum over the 16 lanes of a DPP row, the same bits in every lane: the neighbour in the quad (quad_perm [1,0,3,2]), the
+// other pair of the quad (quad_perm [2,3,0,1]), the mirrored half row, the mirrored row.  Every step adds two values that both
+// lanes of a pair hold, and a + b = b + a bit for bit.
+__device__ __forceinline__ double refine_row_sum(double x) {
+  x += refine_dpp<0xB1>(x);
+  x += refine_dpp<0x4E>(x);
+  x += refine_dpp<0x141>(x);
+  x += refine_dpp<0x140>(x);
+  return x;
+}
+__device__ __forceinline__ bool refine_finite(double x) { return fabs(x) <= 1.7976931348623157e308; }
+
+// ---- motion-only refinement of the frames' poses on the same cost (map_pose_refine.hip, vo_map_refine_poses*) --------
+struct MapPoseWs {
+  int32_t* ent;        // [n_frames][n_max] the lookup's entry per query position (null without the lookup)
+  int32_t* pairs;      // [n_frames][n_max][2] the lookup's pairs (not read; null without the lookup)
+  int* n_hits;         // [n_frames] (the lookup's counts; not read; null without the lookup)
+  int32_t* status;     // [n_frames] (the caller's d_status_out takes its place when given)
+  int* n_obs;          // [n_frames]
+  double* cost;        // [n_frames][2] cost before / after
+  size_t bytes;
+};
+// with_lookup: room for the lookup's own outputs (ent, pairs, n_hits); without it they are null and the caller brings the entries
+MapPoseWs map_pose_layout(void* base, int n_frames, int n_max, bool with_lookup);
+struct MapPoseArgs {
+  const int32_t* ent;                   // [n_frames][n_max]: -1 or the entry (also -1 behind the live rows)
+  int* n_obs; double* cost;             // of the workspace
+  const float* pts; const int* hdr; int cap, bound;   // the map
+  const float* uv; size_t uv_stride;    // pixels between frames
+  int n_max, n_frames;
+  const float* T_in; float* T_out;      // [n_frames][16] column-major, p_cam = T p_map; may be the same array
+  const uint8_t* fixed;                 // [n_frames] or null
+  double K[9];                          // column-major
+  int n_rounds, min_obs;
+  double huber, damping;
+  int32_t* status;                      // [n_frames]
+  double* H_out;                        // [n_frames][36] or null
+  void* stats;                          // vo_map_pose_refine_stats
+};
+// after the lookup has filled `ent`: one workgroup per frame runs all rounds, then the statistics
+hipError_t launch_map_pose_refine(hipStream_t st, const MapPoseArgs& a);
+
 // ---- epipolar initialisation, device half (epi.hip) ------------------------------------------------------
 size_t epi_workspace_bytes();
 // maxima of both point sets + the 45 sums of A^T A + the number of rows / of pairs with a bad index, into ws:

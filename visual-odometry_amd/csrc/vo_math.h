@@ -830,6 +830,105 @@ VO_HD bool ldlt3_solve(const double H[6], const double b[3], double x[3]) {
   return fabs(x[0]) <= big && fabs(x[1]) <= big && fabs(x[2]) <= big;
 }
 
+// ---- motion-only refinement of a frame's pose on the same cost (map_pose_refine.hip; these also compile for the host) ----
+// sums of one evaluation: 0..20 H upper triangle row by row ((0,0) .. (0,5), (1,1) .. (5,5)), 21..26 b, 27 the cost
+constexpr int NPOSE = 28;
+
+// One observation's terms at the pose T (R column-major, then t, in double): p_cam = R p + t with p the entry's float32 point
+// widened, q = K p_cam, e = (q0 / q2, q1 / q2) - (mu, mv); J = de / dp_cam [I, -[p_cam]x] for the step (t, alpha) of
+// T <- v2t(dx) T; w = min(1, huber / |e|) (huber == 0: 1); acc += w J^T J, w J^T e, rho(e).  Returns whether camera z is > 0.
+VO_HD bool map_pose_term(const double K[9], const double T[12], const float pt[3], double mu, double mv, double huber,
+                         double acc[NPOSE]) {
+  const double p[3] = {(double)pt[0], (double)pt[1], (double)pt[2]};
+  double pc[3], q[3];
+  for (int r = 0; r < 3; ++r) pc[r] = __builtin_fma(T[r + 6], p[2], __builtin_fma(T[r + 3], p[1], __builtin_fma(T[r], p[0], T[9 + r])));
+  for (int r = 0; r < 3; ++r) q[r] = __builtin_fma(K[r + 6], pc[2], __builtin_fma(K[r + 3], pc[1], K[r] * pc[0]));
+  const double iz = 1.0 / q[2];
+  const double u = q[0] * iz, v = q[1] * iz;
+  const double e0 = u - mu, e1 = v - mv;
+  double J0[6], J1[6];
+  for (int c = 0; c < 3; ++c) { J0[c] = (K[3 * c] - u * K[2 + 3 * c]) * iz; J1[c] = (K[1 + 3 * c] - v * K[2 + 3 * c]) * iz; }
+  // j (-[p_cam]x) = p_cam x j
+  J0[3] = J0[2] * pc[1] - J0[1] * pc[2]; J0[4] = J0[0] * pc[2] - J0[2] * pc[0]; J0[5] = J0[1] * pc[0] - J0[0] * pc[1];
+  J1[3] = J1[2] * pc[1] - J1[1] * pc[2]; J1[4] = J1[0] * pc[2] - J1[2] * pc[0]; J1[5] = J1[1] * pc[0] - J1[0] * pc[1];
+  const double r2 = e0 * e0 + e1 * e1;
+  double w = 1.0, rho = r2;
+  if (huber > 0.0) {
+    const double r = sqrt(r2);
+    if (r > huber) { w = huber / r; rho = huber * (2.0 * r - huber); }
+  }
+  int k = 0;
+#pragma unroll
+  for (int a = 0; a < 6; ++a) {
+    const double w0 = w * J0[a], w1 = w * J1[a];
+#pragma unroll
+    for (int b = a; b < 6; ++b) acc[k++] += __builtin_fma(w1, J1[b], w0 * J0[b]);
+    acc[21 + a] += __builtin_fma(w1, e1, w0 * e0);
+  }
+  acc[27] += rho;
+  return pc[2] > 0.0;
+}
+
+// x = H^-1 b for the symmetric 6x6 H (upper triangle as above) by an LDL^T in natural order, in double.  False when a pivot is
+// not > 0 (a NaN is not) or the step is not finite.
+VO_HD bool ldlt6d_solve(const double Hu[21], const double b[6], double x[6]) {
+  double L[6][6], D[6];
+  int k = 0;
+#pragma unroll
+  for (int r = 0; r < 6; ++r)
+#pragma unroll
+    for (int c = r; c < 6; ++c) L[c][r] = Hu[k++];            // the lower triangle holds H, overwritten by L column by column
+#pragma unroll
+  for (int j = 0; j < 6; ++j) {
+    double d = L[j][j];
+#pragma unroll
+    for (int m = 0; m < j; ++m) d -= L[j][m] * L[j][m] * D[m];
+    if (!(d > 0.0)) return false;
+    D[j] = d;
+#pragma unroll
+    for (int i = j + 1; i < 6; ++i) {
+      double s = L[i][j];
+#pragma unroll
+      for (int m = 0; m < j; ++m) s -= L[i][m] * L[j][m] * D[m];
+      L[i][j] = s / d;
+    }
+  }
+  double y[6];
+#pragma unroll
+  for (int i = 0; i < 6; ++i) {
+    double s = b[i];
+#pragma unroll
+    for (int m = 0; m < i; ++m) s -= L[i][m] * y[m];
+    y[i] = s;
+  }
+  bool finite = true;
+#pragma unroll
+  for (int i = 5; i >= 0; --i) {
+    double s = y[i] / D[i];
+#pragma unroll
+    for (int m = i + 1; m < 6; ++m) s -= L[m][i] * x[m];
+    x[i] = s;
+    finite = finite && fabs(s) <= 1.7976931348623157e308;
+  }
+  return finite;
+}
+
+// T <- v2t(dx) T in double: v2t is the solver's (translation dx[0:3], R = Rx(dx3) Ry(dx4) Rz(dx5), v2t_from_sincos above)
+VO_HD void pose_apply_v2t(const double dx[6], double T[12]) {
+  const double sx = sin(dx[3]), cx = cos(dx[3]), sy = sin(dx[4]), cy = cos(dx[4]), sz = sin(dx[5]), cz = cos(dx[5]);
+  const double a10 = sx * sy, a12 = -sx * cy, a20 = -cx * sy, a22 = cx * cy;
+  const double dR[9] = {cy * cz, a10 * cz + cx * sz, a20 * cz + sx * sz, cy * (-sz), a10 * (-sz) + cx * cz, a20 * (-sz) + sx * cz,
+                        sy, a12, a22};                        // column-major
+  double N[12];
+#pragma unroll
+  for (int c = 0; c < 4; ++c)
+#pragma unroll
+    for (int r = 0; r < 3; ++r)
+      N[r + 3 * c] = __builtin_fma(dR[r + 6], T[2 + 3 * c], __builtin_fma(dR[r + 3], T[1 + 3 * c], dR[r] * T[3 * c])) + (c == 3 ? dx[r] : 0.0);
+#pragma unroll
+  for (int k = 0; k < 12; ++k) T[k] = N[k];
+}
+
 // ---- the map's key (map.hip): ten floats, their hash and the home slot of the hash -- integer code, the same on both sides --
 struct Row { float v[10]; };
 
