@@ -3,7 +3,7 @@
 // PointCloudVector<3>::update, lookup() answers "which entries of the map does this frame see?", localise() "where is this
 // camera in the map?" -- lookup -> P3P RANSAC -> PICP rounds, from the frame alone; refine() re-estimates the map's points from
 // all the frames that see them, the poses fixed (vo_map_refine), refinePoses() the poses from the map (vo_map_refine_poses),
-// adjust() alternates the two (vo_map_adjust).  A frame that cannot be localised is a
+// adjust() alternates the two (vo_map_adjust), bundle() adjusts both jointly (vox_map_bundle).  A frame that cannot be localised is a
 // status in the statistics, not an exception; vo::Error is thrown where the C call refuses.
 #pragma once
 
@@ -69,6 +69,17 @@ struct AdjustOptions {
   int min_obs_pose = 3, min_obs_point = 3;
   float huber_px = 0;
   float damping = 0;
+};
+
+//! vox_map_bundle: the joint adjustment -- Levenberg-Marquardt rounds, the reduced camera system solved by matrix-free PCG
+//!
+struct BundleOptions {
+  int n_rounds = 3;
+  int n_cg = 64;
+  float cg_tol = 1e-8f;
+  float lambda0 = 1e-4f;
+  int min_obs_pose = 3, min_obs_point = 3;
+  float huber_px = 0;
 };
 
 class DeviceMap {
@@ -221,6 +232,29 @@ class DeviceMap {
     for (size_t f = 0; f < w.F; ++f)
       for (int k = 0; k < 16; ++k) poses[f].data()[k] = w.T[16 * f + k];
     if (sweeps) *sweeps = s;
+  }
+
+  //! joint bundle adjustment (vox_map_bundle): the free frames' poses in place on `poses`, the free landmarks' points in place on
+  //! the map, only when the call's status (the returned statistics) is VOX_MAP_BUNDLE_OK.  Hold the gauge with `fixed`.
+  //! *rounds receives one record per round; the statuses say which frames and landmarks were free.
+  vox_map_bundle_stats bundle(const Camera& cam, const std::vector<Vector2fVector>& pixels, const std::vector<Vector10fVector>& appearances,
+                              IsometryVector& poses, const std::vector<uint8_t>* fixed, const BundleOptions& opt = BundleOptions(),
+                              std::vector<vox_map_bundle_round>* rounds = nullptr, std::vector<int32_t>* pose_status = nullptr,
+                              std::vector<int32_t>* point_status = nullptr) {
+    Window w = pack("DeviceMap::bundle", pixels, appearances, poses, fixed);
+    if (pose_status) pose_status->assign(w.F, -1);
+    if (point_status) point_status->assign((size_t)size(), -1);
+    const vox_map_bundle_params prm{opt.n_rounds, opt.n_cg, opt.cg_tol, opt.lambda0, opt.min_obs_pose, opt.min_obs_point, opt.huber_px};
+    std::vector<vox_map_bundle_round> r((size_t)(opt.n_rounds > 0 ? opt.n_rounds : 1));
+    vox_map_bundle_stats st{};
+    check(vox_map_bundle(h_, (int)w.F, cam.cameraMatrix().data(), w.uv.data(), w.app.data(), w.n.data(), (int)w.cap, w.T.data(),
+                         fixed ? fixed->data() : nullptr, &prm, pose_status ? pose_status->data() : nullptr,
+                         point_status && !point_status->empty() ? point_status->data() : nullptr, r.data(), &st), "vox_map_bundle");
+    for (size_t f = 0; f < w.F; ++f)
+      for (int k = 0; k < 16; ++k) poses[f].data()[k] = w.T[16 * f + k];
+    r.resize((size_t)(opt.n_rounds > 0 ? opt.n_rounds : 0));
+    if (rounds) *rounds = r;
+    return st;
   }
 
   //! the map's points and appearances in entry order

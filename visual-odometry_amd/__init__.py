@@ -23,6 +23,10 @@ from .api import (  # noqa: F401
     MAP_POSE_STATUS,
     MapAdjustParams,
     MapAdjustStats,
+    MapBundleParams,
+    MapBundleRound,
+    MapBundleStats,
+    MAP_BUNDLE_STATUS,
     PICPSolver,
     VoError,
     compute_correspondences_images,

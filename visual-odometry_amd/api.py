@@ -596,6 +596,35 @@ class Map:
         sweeps = [dict(poses=s.poses.as_dict(), points=s.points.as_dict()) for s in st]
         return T.reshape(F, 4, 4).transpose(0, 2, 1).copy(), pose_status, point_status[: st[0].points.n_entries].copy(), sweeps
 
+    # ---- joint adjustment by matrix-free Schur PCG (vox_map_bundle*, include/vo_map_bundle.h) ----
+    def bundle_batch_dev(self, camera: Camera, n_frames, d_uv, uv_stride, d_app, app_stride, n_max, d_n, d_T16, d_fixed,
+                         params: "MapBundleParams", d_pose_status_out, d_point_status_out, d_rounds_out, d_stats):
+        """vox_map_bundle_batch_dev on device pointers: d_T16 and the map in place; d_rounds_out: n_rounds x 40 bytes
+        (MapBundleRound) or None; d_stats: 48 bytes (MapBundleStats)"""
+        v = lambda d: C.c_void_p(d) if d else None
+        _chk(self.lib.vox_map_bundle_batch_dev(self.h, C.c_int(n_frames), _ptr(_colmajor(camera._K, 3)), v(d_uv), C.c_size_t(uv_stride),
+                                               v(d_app), C.c_size_t(app_stride), C.c_int(n_max), v(d_n), v(d_T16), v(d_fixed),
+                                               C.byref(params), v(d_pose_status_out), v(d_point_status_out), v(d_rounds_out), v(d_stats)))
+
+    def bundle(self, camera: Camera, frames, poses, fixed=None, n_rounds=3, n_cg=64, cg_tol=1e-8, lambda0=1e-4, min_obs_pose=3,
+               min_obs_point=3, huber_px=0.0):
+        """vox_map_bundle: the poses of the free frames and the points of the free landmarks adjusted jointly, in place on the
+        map, by n_rounds Levenberg-Marquardt rounds whose reduced camera system is solved by at most n_cg PCG iterations.  Hold
+        the gauge with `fixed`.  Returns (poses (F, 4, 4) float32, pose status (F,), point status (size,), [per round dict],
+        stats dict: MAP_BUNDLE_STATUS names stats["status"])."""
+        F, cap, uv, app, n, T, mask = self._window(frames, poses, fixed)
+        pose_status = np.full(F, -1, np.int32)
+        point_status = np.full(max(len(self), 1), -1, np.int32)
+        rounds = (MapBundleRound * max(int(n_rounds), 1))()
+        st = MapBundleStats()
+        prm = MapBundleParams(int(n_rounds), int(n_cg), float(cg_tol), float(lambda0), int(min_obs_pose), int(min_obs_point), float(huber_px))
+        _chk(self.lib.vox_map_bundle(self.h, C.c_int(F), _ptr(_colmajor(camera._K, 3)), _ptr(uv[:, :cap]) if cap else None,
+                                     _ptr(app[:, :cap]) if cap else None, _ptr(n), C.c_int(cap), _ptr(T),
+                                     _ptr(mask) if mask is not None else None, C.byref(prm), _ptr(pose_status), _ptr(point_status), rounds,
+                                     C.byref(st)))
+        return (T.reshape(F, 4, 4).transpose(0, 2, 1).copy(), pose_status, point_status[: st.n_entries].copy(),
+                [rounds[k].as_dict() for k in range(max(int(n_rounds), 0))], st.as_dict())
+
 
 class MapLocaliseStats(C.Structure):
     """vo_map_localise_stats (include/vo_hip.h)"""
@@ -657,6 +686,36 @@ class MapAdjustStats(C.Structure):
 assert C.sizeof(MapPoseRefineParams) == 16 and C.sizeof(MapPoseRefineStats) == 48
 assert C.sizeof(MapAdjustParams) == 28 and C.sizeof(MapAdjustStats) == 96
 MAP_POSE_STATUS = ("OK", "FIXED", "FEW_OBS", "BEHIND", "NOT_FINITE", "COST_ROSE")          # VO_MAP_POSE_*
+
+
+class MapBundleParams(C.Structure):
+    """vox_map_bundle_params (include/vo_map_bundle.h)"""
+    _fields_ = [("n_rounds", C.c_int32), ("n_cg", C.c_int32), ("cg_tol", C.c_float), ("lambda0", C.c_float), ("min_obs_pose", C.c_int32),
+                ("min_obs_point", C.c_int32), ("huber_px", C.c_float)]
+
+
+class MapBundleRound(C.Structure):
+    """vox_map_bundle_round (include/vo_map_bundle.h): one round"""
+    _fields_ = [("cost", C.c_double), ("cost_candidate", C.c_double), ("lambda_", C.c_double), ("residual", C.c_double),
+                ("cg_iterations", C.c_int32), ("accepted", C.c_int32)]
+
+    def as_dict(self):
+        return dict(cost=self.cost, cost_candidate=self.cost_candidate, lambda_=self.lambda_, residual=self.residual,
+                    cg_iterations=self.cg_iterations, accepted=self.accepted)
+
+
+class MapBundleStats(C.Structure):
+    """vox_map_bundle_stats (include/vo_map_bundle.h)"""
+    _fields_ = [("status", C.c_int32), ("n_frames", C.c_int32), ("n_entries", C.c_int32), ("n_obs", C.c_int32), ("n_free_frames", C.c_int32),
+                ("n_free_points", C.c_int32), ("n_accepted", C.c_int32), ("reserved", C.c_int32), ("cost_before", C.c_double),
+                ("cost_after", C.c_double)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_ if k != "reserved"}
+
+
+assert C.sizeof(MapBundleParams) == 28 and C.sizeof(MapBundleRound) == 40 and C.sizeof(MapBundleStats) == 48
+MAP_BUNDLE_STATUS = ("OK", "NOT_FINITE", "BEHIND", "NOTHING_FREE", "NO_STEP", "COST_ROSE")   # VOX_MAP_BUNDLE_*
 
 
 def triangulate_points(k, X, correspondences, p1_img, p2_img, app2=None, want_pairs=True,

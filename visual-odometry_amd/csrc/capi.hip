@@ -2124,6 +2124,7 @@ struct vo_map {
   vo_picp* solver = nullptr;    // vo_map_localise[_dev]: made by the first call
   DevBuf ref_ws;                // vo_map_refine*: the entries seen, the observation lists, status and cost per entry
   DevBuf pose_ws;               // vo_map_refine_poses*: the entries seen, status, observation count and cost per frame
+  DevBuf bundle_ws;             // vox_map_bundle*: the state in double, the blocks and the PCG vectors (the lists live in ref_ws)
 };
 
 constexpr int MAP_MAX_ENTRIES = 1 << 29;      // 2.5 x that many table slots still fit 32 bits
@@ -2216,7 +2217,7 @@ int vo_map_destroy(vo_map* m) {
   map_free_arrays(m->d);
   if (m->d.hdr) (void)hipFree(m->d.hdr);
   if (m->hist) (void)hipFree(m->hist);
-  m->scratch.release(); m->up_xyz.release(); m->up_app.release(); m->look_ws.release(); m->loc_ws.release(); m->ref_ws.release(); m->pose_ws.release();
+  m->scratch.release(); m->up_xyz.release(); m->up_app.release(); m->look_ws.release(); m->loc_ws.release(); m->ref_ws.release(); m->pose_ws.release(); m->bundle_ws.release();
   if (m->solver) (void)vo_picp_destroy(m->solver);
   delete m;
   return VO_OK;
@@ -2828,6 +2829,85 @@ int vo_map_adjust(vo_map* m, int n_frames, const float K[9], const float* uv, co
                                       point_status_out ? c->out[1].as<int32_t>() : nullptr, c->out[2].as<vo_map_adjust_stats>()))
     return r;
   VO_HIP_CHECK(hipMemcpyAsync(stats_out, c->out[2].p, sizeof(vo_map_adjust_stats) * S, hipMemcpyDeviceToHost, c->stream));
+  VO_HIP_CHECK(hipMemcpyAsync(T16, c->in[2].p, sizeof(float) * 16 * F, hipMemcpyDeviceToHost, c->stream));
+  if (pose_status_out) VO_HIP_CHECK(hipMemcpyAsync(pose_status_out, c->out[0].p, sizeof(int32_t) * F, hipMemcpyDeviceToHost, c->stream));
+  if (point_status_out && size > 0)
+    VO_HIP_CHECK(hipMemcpyAsync(point_status_out, c->out[1].p, sizeof(int32_t) * (size_t)size, hipMemcpyDeviceToHost, c->stream));
+  VO_HIP_CHECK(hipStreamSynchronize(c->stream));
+  return VO_OK;
+}
+
+// ---- joint adjustment by matrix-free Schur PCG (map_bundle.hip; include/vo_map_bundle.h: the vox_ namespace) ---------------
+static_assert(sizeof(vox_map_bundle_params) == 28 && sizeof(vox_map_bundle_round) == 40 && sizeof(vox_map_bundle_stats) == 48,
+              "the records of include/vo_map_bundle.h as the kernels write them");
+
+int vox_map_bundle_batch_dev(vo_map* m, int n_frames, const float K[9], const float* d_uv, size_t uv_stride, const float* d_app,
+                             size_t app_stride, int n_max, const int* d_n, float* d_T16, const uint8_t* d_fixed,
+                             const vox_map_bundle_params* p, int32_t* d_pose_status_out, int32_t* d_point_status_out,
+                             vox_map_bundle_round* d_rounds_out, vox_map_bundle_stats* d_stats) {
+  VO_MAP_LIVE(m);
+  const char* fn = "vox_map_bundle_batch_dev";
+  if (!(K && p && d_T16 && d_stats)) return fail(VO_ERR_INVALID_ARG, "%s: null argument", fn);
+  if (!aligned8(d_rounds_out)) return fail(VO_ERR_INVALID_ARG, "%s: device arrays must be 8-byte aligned", fn);
+  if (int r = refine_check(fn, n_frames, K, d_uv, uv_stride, d_app, app_stride, n_max, d_stats, p->n_rounds, VOX_MAP_BUNDLE_MAX_STEPS, p->min_obs_pose, 3,
+                           p->huber_px, 0.f))
+    return r;
+  if (p->min_obs_point < 2) return fail(VO_ERR_INVALID_ARG, "%s: min_obs_point must be at least 2", fn);
+  if (p->n_cg < 1) return fail(VO_ERR_INVALID_ARG, "%s: n_cg must be at least 1", fn);
+  if (!(p->cg_tol >= 0.f && p->cg_tol <= 3.402823466e38f)) return fail(VO_ERR_INVALID_ARG, "%s: cg_tol must be finite and not negative", fn);
+  if (!(p->lambda0 >= 0.f && p->lambda0 <= 3.402823466e38f)) return fail(VO_ERR_INVALID_ARG, "%s: lambda0 must be finite and not negative", fn);
+  if ((long long)p->n_rounds * ((long long)p->n_cg + 2) > VOX_MAP_BUNDLE_MAX_STEPS)
+    return fail(VO_ERR_INVALID_ARG, "%s: n_rounds * (n_cg + 2) above %d (the launches of a call are a fixed sequence)", fn, VOX_MAP_BUNDLE_MAX_STEPS);
+  vo_ctx* c = m->ctx;
+  const int bound = map_bound(m);
+  MapBundleWs bw = map_bundle_layout(nullptr, n_frames, bound);
+  if (c->capturing && m->bundle_ws.cap < bw.bytes)            // (before the lookup is enqueued)
+    return fail(VO_ERR_NOT_READY, "%s: the workspace would have to grow inside a graph capture (make one call with %d frames of n_max %d "
+                                  "on this map before capturing)", fn, n_frames, n_max);
+  MapRefineWs rw;
+  if (int r = refine_prepare(fn, m, n_frames, d_app, app_stride, n_max, d_n, &rw)) return r;      // the one lookup of the call
+  VO_HIP_CHECK(m->bundle_ws.ensure(bw.bytes, c->stream));
+  MapBundleArgs a{};
+  a.l = rw; a.w = map_bundle_layout(m->bundle_ws.p, n_frames, bound);
+  a.pts = m->d.pts; a.hdr = m->d.hdr; a.cap = m->d.cap; a.bound = bound;
+  a.uv = d_uv; a.uv_stride = uv_stride; a.n_max = n_max; a.n_frames = n_frames;
+  a.T16 = d_T16; a.fixed = d_fixed;
+  for (int k = 0; k < 9; ++k) a.K[k] = K[k];
+  a.n_rounds = p->n_rounds; a.n_cg = p->n_cg; a.min_obs_pose = p->min_obs_pose; a.min_obs_point = p->min_obs_point;
+  a.cg_tol = p->cg_tol; a.lambda0 = p->lambda0; a.huber = p->huber_px;
+  a.pose_status_out = d_pose_status_out; a.point_status_out = d_point_status_out; a.rounds_out = d_rounds_out; a.stats = d_stats;
+  VO_HIP_CHECK(launch_map_bundle(c->stream, a, c->n_cu));
+  return VO_OK;
+}
+
+int vox_map_bundle(vo_map* m, int n_frames, const float K[9], const float* uv, const float* app, const int* n_rows, int n_max, float* T16,
+                   const uint8_t* fixed, const vox_map_bundle_params* params, int32_t* pose_status_out, int32_t* point_status_out,
+                   vox_map_bundle_round* rounds_out, vox_map_bundle_stats* stats_out) {
+  VO_MAP_LIVE(m);
+  vo_ctx* c = m->ctx;
+  VO_NOT_CAPTURING(c);
+  VO_REQUIRE(K && T16 && params && stats_out, "null argument");
+  VO_REQUIRE(params->n_rounds >= 0 && params->n_rounds <= VOX_MAP_BUNDLE_MAX_STEPS, "n_rounds outside 0 .. 65536");
+  VO_REQUIRE(n_frames >= 1 && n_frames <= 65535, "n_frames outside 1 .. 65535");
+  VO_REQUIRE(n_max >= 0 && (n_max == 0 || (uv && app)), "bad frames");
+  VO_REQUIRE((long long)n_max * n_frames <= (1ll << 30), "more than 2^30 rows in one call");
+  if (int r = set_device(c)) return r;
+  if (int r = upload_window(c, n_frames, uv, app, n_rows, n_max, T16, fixed)) return r;
+  int size = 0;
+  if (int r = vo_map_size(m, &size)) return r;                // (waits: the host arrays may go away after the call)
+  const size_t F = (size_t)n_frames, S = (size_t)params->n_rounds;
+  VO_HIP_CHECK(c->out[0].ensure(sizeof(int32_t) * F, c->stream));
+  if (point_status_out) VO_HIP_CHECK(c->out[1].ensure(sizeof(int32_t) * (size_t)(size > 0 ? size : 1), c->stream));
+  VO_HIP_CHECK(c->out[2].ensure(sizeof(vox_map_bundle_stats) + sizeof(vox_map_bundle_round) * S + 16, c->stream));
+  vox_map_bundle_stats* d_st = c->out[2].as<vox_map_bundle_stats>();
+  vox_map_bundle_round* d_rd = reinterpret_cast<vox_map_bundle_round*>(d_st + 1);
+  if (int r = vox_map_bundle_batch_dev(m, n_frames, K, c->in[0].as<float>(), (size_t)n_max, c->in[1].as<float>(), (size_t)n_max, n_max,
+                                       n_rows ? c->in[3].as<int>() : nullptr, c->in[2].as<float>(), fixed ? c->in[4].as<uint8_t>() : nullptr,
+                                       params, pose_status_out ? c->out[0].as<int32_t>() : nullptr,
+                                       point_status_out ? c->out[1].as<int32_t>() : nullptr, rounds_out && S ? d_rd : nullptr, d_st))
+    return r;
+  VO_HIP_CHECK(hipMemcpyAsync(stats_out, d_st, sizeof(vox_map_bundle_stats), hipMemcpyDeviceToHost, c->stream));
+  if (rounds_out && S) VO_HIP_CHECK(hipMemcpyAsync(rounds_out, d_rd, sizeof(vox_map_bundle_round) * S, hipMemcpyDeviceToHost, c->stream));
   VO_HIP_CHECK(hipMemcpyAsync(T16, c->in[2].p, sizeof(float) * 16 * F, hipMemcpyDeviceToHost, c->stream));
   if (pose_status_out) VO_HIP_CHECK(hipMemcpyAsync(pose_status_out, c->out[0].p, sizeof(int32_t) * F, hipMemcpyDeviceToHost, c->stream));
   if (point_status_out && size > 0)

@@ -1,0 +1,707 @@
+// map_bundle.hip -- joint adjustment of a window's poses and the map's points (vox_map_bundle*): Levenberg-Marquardt rounds
+// whose reduced camera system S = U - W V^-1 W^T is never formed; S p is one pass over the landmarks' ordered observation
+// lists (map_refine.hip builds them) and one pass over the frames' rows, and preconditioned conjugate gradients runs on those
+// two passes.  The rules are those of include/vo_map_bundle.h.  Everything is double, every sum has a fixed order, nothing is
+// read back, and no launch waits for another workgroup: a round is a fixed sequence of 3 (n_cg + 2) launches,
+//   bundle_point_kernel<LIN>    16 lanes per landmark: V_j, g_j, the damped V_j^-1
+//   bundle_frame_lin_kernel     one workgroup per frame: U_f, g_f, then D_f and r_f (which need V^-1)
+//   bundle_cg_init_kernel       one workgroup: x = 0, z = D^-1 r, p = z, r.z, |r_0|^2
+//   n_cg times  bundle_point_kernel<PASS_A>  t_j = V_j^-1 sum W^T p_f
+//               bundle_frame_sp_kernel       (S p)_f = U_f p_f - sum W t_j and p_f . (S p)_f
+//               bundle_cg_update_kernel      one workgroup: alpha, x, r, z, beta, p, the stop flag
+//   bundle_point_kernel<BACK>   the candidate points
+//   bundle_cost_kernel<CAND>    one workgroup per frame: the candidate pose, its cost and z flag
+//   bundle_decide_kernel        one workgroup: the accept rule, lambda, the round's record, the copy
+// A PCG that has stopped leaves `stop` set in the control block; its remaining launches read it and return at once.
+// The frame-side reduction is map_pose_refine.hip's: DPP inside every row of 16 lanes, the 16 row sums through LDS, one thread
+// per term adds them in row order.  A single frame runs on one compute unit.
+#include "vo_internal.h"
+#include "../../include/vo_map_bundle.h"
+
+namespace vo {
+
+constexpr int BB = 256;                   // threads per workgroup
+constexpr int BROWS = BB / 16;            // DPP rows per workgroup
+constexpr int BG = 16;                    // lanes per landmark
+constexpr int BLPB = BB / BG;             // landmarks per workgroup and trip
+constexpr int BDEC = 1024;                // threads of the deciding workgroups (the first 256 take part in the sums)
+constexpr int BTERMS = 27;                // most sums a frame reduces at once
+
+enum { BS_OK = 0, BS_FIXED = 1, BS_UNSEEN = 1, BS_FEW_OBS = 2 };
+enum { B_LIN = 0, B_PASS_A = 1, B_BACK = 2 };
+enum { B_START = 0, B_CAND = 1, B_FINAL = 2 };
+
+static_assert(sizeof(vox_map_bundle_params) == 28 && sizeof(vox_map_bundle_round) == 40 && sizeof(vox_map_bundle_stats) == 48,
+              "the deciding kernels write these records field by field");
+
+__device__ __forceinline__ int bundle_size(const MapBundleArgs& a) {
+  int M = a.hdr[0];
+  M = M < a.cap ? M : a.cap;
+  return M < a.bound ? M : a.bound;
+}
+__device__ __forceinline__ int bundle_offset(const MapBundleArgs& a, int e) { return a.l.cnt[e] + a.l.blk[e / 256]; }
+__device__ __forceinline__ bool bundle_free_point(const MapBundleArgs& a, int e, int M) { return e >= 0 && e < M && a.l.cur[e] >= a.min_obs_point; }
+
+// One observation at the pose T (R column-major, then t) and the point p, all in double, with the operations of map_pose_term
+// and map_refine_term (vo_math.h): the residual e, the weight w and rho, Jc = j [I, -[p_cam]x] (2 x 6), Jp = j R (2 x 3).
+struct BundleObs { double w, e0, e1, rho, C0[6], C1[6], P0[3], P1[3]; bool front; };
+__device__ __forceinline__ void bundle_obs(const double K[9], const double T[12], const double p[3], double mu, double mv, double huber,
+                                           BundleObs& o) {
+  double pc[3], q[3];
+#pragma unroll
+  for (int r = 0; r < 3; ++r) pc[r] = __builtin_fma(T[r + 6], p[2], __builtin_fma(T[r + 3], p[1], __builtin_fma(T[r], p[0], T[9 + r])));
+#pragma unroll
+  for (int r = 0; r < 3; ++r) q[r] = __builtin_fma(K[r + 6], pc[2], __builtin_fma(K[r + 3], pc[1], K[r] * pc[0]));
+  const double iz = 1.0 / q[2];
+  const double u = q[0] * iz, v = q[1] * iz;
+  o.e0 = u - mu; o.e1 = v - mv;
+#pragma unroll
+  for (int c = 0; c < 3; ++c) { o.C0[c] = (K[3 * c] - u * K[2 + 3 * c]) * iz; o.C1[c] = (K[1 + 3 * c] - v * K[2 + 3 * c]) * iz; }
+  o.C0[3] = o.C0[2] * pc[1] - o.C0[1] * pc[2]; o.C0[4] = o.C0[0] * pc[2] - o.C0[2] * pc[0]; o.C0[5] = o.C0[1] * pc[0] - o.C0[0] * pc[1];
+  o.C1[3] = o.C1[2] * pc[1] - o.C1[1] * pc[2]; o.C1[4] = o.C1[0] * pc[2] - o.C1[2] * pc[0]; o.C1[5] = o.C1[1] * pc[0] - o.C1[0] * pc[1];
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    o.P0[c] = __builtin_fma(o.C0[2], T[2 + 3 * c], __builtin_fma(o.C0[1], T[1 + 3 * c], o.C0[0] * T[3 * c]));
+    o.P1[c] = __builtin_fma(o.C1[2], T[2 + 3 * c], __builtin_fma(o.C1[1], T[1 + 3 * c], o.C1[0] * T[3 * c]));
+  }
+  const double r2 = o.e0 * o.e0 + o.e1 * o.e1;
+  o.w = 1.0; o.rho = r2;
+  if (huber > 0.0) {
+    const double r = sqrt(r2);
+    if (r > huber) { o.w = huber / r; o.rho = huber * (2.0 * r - huber); }
+  }
+  o.front = pc[2] > 0.0;
+}
+
+template <int N>
+__device__ __forceinline__ void bundle_load(const double* src, double (&dst)[N]) {
+#pragma unroll
+  for (int k = 0; k < N; ++k) dst[k] = src[k];
+}
+
+// y = A x for the symmetric 3x3 A given by its upper triangle ((0,0),(0,1),(0,2),(1,1),(1,2),(2,2))
+__device__ __forceinline__ void sym3_mul(const double A[6], const double x[3], double y[3]) {
+  y[0] = A[0] * x[0] + A[1] * x[1] + A[2] * x[2];
+  y[1] = A[1] * x[0] + A[3] * x[1] + A[4] * x[2];
+  y[2] = A[2] * x[0] + A[4] * x[1] + A[5] * x[2];
+}
+// index of (r, c), r <= c, in the upper triangle of a 6x6 stored row by row
+__device__ __forceinline__ constexpr int tri6(int r, int c) { return r * 6 - r * (r - 1) / 2 + (c - r); }
+
+// the sum of one value per frame in the order of the header: frame f into partial sum f mod 256 in frame order (thread t < 256
+// brings its partial sum), the 256 partial sums by a binary tree.  Every thread of the workgroup calls it and gets the total.
+__device__ __forceinline__ double bundle_tree_sum(double mine, double* s /* [256] */) {
+  __syncthreads();                                            // (s may still be read from the sum before)
+  if (threadIdx.x < 256) s[threadIdx.x] = mine;
+  __syncthreads();
+  for (int h = 128; h >= 1; h >>= 1) {
+    if ((int)threadIdx.x < h) s[threadIdx.x] += s[threadIdx.x + h];
+    __syncthreads();
+  }
+  return s[0];
+}
+
+// the sums of N terms over a frame's workgroup: DPP inside every row of 16 lanes, the 16 row sums through LDS, thread k < N adds
+// term k in row order; afterwards every thread holds the same bits
+template <int N>
+__device__ __forceinline__ void bundle_frame_reduce(double (&acc)[N], double (*s_row)[BTERMS], double* s_tot) {
+  const int tid = threadIdx.x;
+#pragma unroll
+  for (int k = 0; k < N; ++k) acc[k] = refine_row_sum(acc[k]);
+  __syncthreads();                                            // (s_row and s_tot may still be read from the reduction before)
+  if ((tid & 15) == 0) {
+#pragma unroll
+    for (int k = 0; k < N; ++k) s_row[tid >> 4][k] = acc[k];
+  }
+  __syncthreads();
+  if (tid < N) {
+    double s = s_row[0][tid];
+#pragma unroll
+    for (int w = 1; w < BROWS; ++w) s += s_row[w][tid];
+    s_tot[tid] = s;
+  }
+  __syncthreads();
+#pragma unroll
+  for (int k = 0; k < N; ++k) acc[k] = s_tot[k];
+}
+
+// ---- the start: statuses, the state in double, the census ------------------------------------------------------------
+__global__ __launch_bounds__(BB) void bundle_init_frames_kernel(MapBundleArgs a) {
+  __shared__ int s_n;
+  const int f = blockIdx.x, tid = threadIdx.x;
+  const int M = bundle_size(a);
+  const int32_t* ent = a.l.ent + (size_t)f * a.n_max;
+  if (tid == 0) s_n = 0;
+  __syncthreads();
+  int mine = 0;
+  for (int i = tid; i < a.n_max; i += BB) { const int e = ent[i]; mine += e >= 0 && e < M; }
+  if (mine) atomicAdd(&s_n, mine);                           // (an integer count does not depend on the order)
+  __syncthreads();
+  if (tid < 12) {
+    const double v = (double)a.T16[16 * (size_t)f + (tid % 3) + 4 * (tid / 3)];
+    a.w.T[12 * (size_t)f + tid] = v;
+    a.w.Tc[12 * (size_t)f + tid] = v;
+  }
+  if (tid < 6) a.w.x[6 * (size_t)f + tid] = 0.0;
+  if (tid == 0) {
+    const int n = s_n;
+    a.w.n_obs[f] = n;
+    a.w.pose_status[f] = (a.fixed && a.fixed[f] != 0) ? BS_FIXED : n < a.min_obs_pose ? BS_FEW_OBS : BS_OK;
+  }
+}
+
+__global__ __launch_bounds__(BB) void bundle_init_points_kernel(MapBundleArgs a) {
+  const int M = bundle_size(a);
+  const int e = blockIdx.x * BB + threadIdx.x;
+  if (e >= M) return;
+  const int n = a.l.cur[e];
+  a.w.point_status[e] = n == 0 ? BS_UNSEEN : n < a.min_obs_point ? BS_FEW_OBS : BS_OK;
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    const double v = (double)a.pts[3 * (size_t)e + k];
+    a.w.P[3 * (size_t)e + k] = v;
+    a.w.Pc[3 * (size_t)e + k] = v;
+  }
+}
+
+__global__ __launch_bounds__(BB) void bundle_census_kernel(MapBundleArgs a) {
+  __shared__ int s_n[3];
+  const int M = bundle_size(a);
+  if (threadIdx.x < 3) s_n[threadIdx.x] = 0;
+  __syncthreads();
+  int ff = 0, fp = 0, no = 0;
+  for (int f = threadIdx.x; f < a.n_frames; f += BB) { ff += a.w.pose_status[f] == BS_OK; no += a.w.n_obs[f]; }
+  for (int e = threadIdx.x; e < M; e += BB) fp += a.w.point_status[e] == BS_OK;
+  if (ff) atomicAdd(&s_n[0], ff);
+  if (fp) atomicAdd(&s_n[1], fp);
+  if (no) atomicAdd(&s_n[2], no);
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    MapBundleCtl c{};
+    c.lambda = a.lambda0;
+    c.n_free_frames = s_n[0]; c.n_free_points = s_n[1]; c.n_obs = s_n[2];
+    *a.w.ctl = c;
+  }
+}
+
+// ---- the total cost: one workgroup per frame ---------------------------------------------------------------------------
+// START: at the state.  CAND: the candidate pose v2t(x_f) T_f is formed first (every thread the same bits, thread 0 stores it),
+// the points are the candidate's.  FINAL: at the rounded state, which the rounding launch left in the candidate arrays.
+template <int MODE>
+__global__ __launch_bounds__(BB) void bundle_cost_kernel(MapBundleArgs a) {
+  __shared__ double s_row[BROWS][BTERMS], s_tot[BTERMS];
+  const MapBundleCtl& c = *a.w.ctl;
+  if (MODE != B_START && c.dead) return;
+  if (MODE == B_CAND && (c.bad || c.nostep)) return;
+  const int f = blockIdx.x, tid = threadIdx.x;
+  const int M = bundle_size(a);
+  double T[12], K[9];
+  bundle_load((MODE == B_FINAL ? a.w.Tc : a.w.T) + 12 * (size_t)f, T);
+#pragma unroll
+  for (int k = 0; k < 9; ++k) K[k] = a.K[k];
+  if (MODE == B_CAND) {
+    if (a.w.pose_status[f] == BS_OK) {
+      double x[6];
+      bundle_load(a.w.x + 6 * (size_t)f, x);
+      pose_apply_v2t(x, T);
+    }
+#pragma unroll
+    for (int k = 0; k < 12; ++k) if (tid == k) a.w.Tc[12 * (size_t)f + k] = T[k];
+  }
+  const double* P = MODE == B_START ? a.w.P : a.w.Pc;
+  const int32_t* ent = a.l.ent + (size_t)f * a.n_max;
+  const float2* uv = reinterpret_cast<const float2*>(a.uv) + (size_t)f * a.uv_stride;
+  double acc[2] = {0.0, 0.0};                                // the cost; the count of rows whose camera z is not > 0
+  for (int i = tid; i < a.n_max; i += BB) {
+    const int e = ent[i];
+    if (e < 0 || e >= M) continue;
+    double p[3];
+    bundle_load(P + 3 * (size_t)e, p);
+    const float2 m = uv[i];
+    BundleObs o;
+    bundle_obs(K, T, p, (double)m.x, (double)m.y, a.huber, o);
+    acc[0] += o.rho;
+    acc[1] += o.front ? 0.0 : 1.0;
+  }
+  bundle_frame_reduce<2>(acc, s_row, s_tot);
+  if (tid == 0) { a.w.fcost[f] = acc[0]; a.w.fflag[f] = acc[1] != 0.0; }
+}
+
+// the start's verdict: the total cost of the start in the fixed order, NOT_FINITE / BEHIND / NOTHING_FREE
+__global__ __launch_bounds__(BB) void bundle_start_kernel(MapBundleArgs a) {
+  __shared__ double s_sum[256];
+  __shared__ int s_flag;
+  if (threadIdx.x == 0) s_flag = 0;
+  __syncthreads();
+  double mine = 0.0;
+  int fl = 0;
+  for (int f = threadIdx.x; f < a.n_frames; f += BB) { mine += a.w.fcost[f]; fl |= a.w.fflag[f]; }
+  if (fl) atomicOr(&s_flag, 1);
+  const double total = bundle_tree_sum(mine, s_sum);
+  if (threadIdx.x == 0) {
+    MapBundleCtl& c = *a.w.ctl;
+    c.cost_start = total; c.cost_cur = total;
+    int st = VOX_MAP_BUNDLE_OK;
+    if (!refine_finite(total)) st = VOX_MAP_BUNDLE_NOT_FINITE;
+    else if (s_flag) st = VOX_MAP_BUNDLE_BEHIND;
+    else if (c.n_free_frames == 0 && c.n_free_points == 0) st = VOX_MAP_BUNDLE_NOTHING_FREE;
+    c.status = st; c.dead = st != VOX_MAP_BUNDLE_OK;
+  }
+}
+
+// ---- the landmark side: 16 lanes per landmark over its ordered list ------------------------------------------------
+//   LIN     V_j = sum w Jp^T Jp, g_j = sum w Jp^T e over ALL its observations; V_j += lambda diag V_j; V_j^-1 by three solves
+//   PASS_A  t_j = V_j^-1 sum over the observations in free frames of W^T p_f,  W^T v = w Jp^T (Jc v)
+//   BACK    the candidate point p_j - V_j^-1 (g_j + sum over the observations in free frames of W^T x_f)
+template <int MODE>
+__global__ __launch_bounds__(BB) void bundle_point_kernel(MapBundleArgs a) {
+  const MapBundleCtl& c = *a.w.ctl;
+  if (c.dead) return;
+  if (MODE == B_PASS_A && (c.bad || c.stop)) return;
+  if (MODE == B_BACK && (c.bad || c.nostep)) return;
+  const int M = bundle_size(a);
+  const int lg = threadIdx.x & (BG - 1), grp = threadIdx.x / BG;
+  const double lambda = c.lambda;
+  const double* vec = MODE == B_PASS_A ? a.w.p : a.w.x;
+  double K[9];
+#pragma unroll
+  for (int k = 0; k < 9; ++k) K[k] = a.K[k];
+  const int n_batches = (a.bound + BLPB - 1) / BLPB;
+  for (int batch = blockIdx.x; batch < n_batches; batch += gridDim.x) {      // (uniform in the workgroup: the DPP sums see whole rows)
+    const int e = batch * BLPB + grp;
+    const bool run = bundle_free_point(a, e, M);
+    const int n = run ? a.l.cur[e] : 0;
+    const int off = run ? bundle_offset(a, e) : 0;
+    double p[3] = {0.0, 0.0, 0.0};
+    if (run) bundle_load(a.w.P + 3 * (size_t)e, p);
+    constexpr int NT = MODE == B_LIN ? 9 : 3;
+    double acc[9];                                           // (PASS_A and BACK use the first three)
+#pragma unroll
+    for (int k = 0; k < NT; ++k) acc[k] = 0.0;
+    for (int j = lg; j < n; j += BG) {
+      const int key = a.l.keys[off + j];
+      const int f = key / a.n_max, i = key - f * a.n_max;
+      if (MODE != B_LIN && a.w.pose_status[f] != BS_OK) continue;
+      const float2 m = reinterpret_cast<const float2*>(a.uv)[(size_t)f * a.uv_stride + i];
+      double T[12];
+      bundle_load(a.w.T + 12 * (size_t)f, T);
+      BundleObs o;
+      bundle_obs(K, T, p, (double)m.x, (double)m.y, a.huber, o);
+      if constexpr (MODE == B_LIN) {
+        const double w0[3] = {o.w * o.P0[0], o.w * o.P0[1], o.w * o.P0[2]}, w1[3] = {o.w * o.P1[0], o.w * o.P1[1], o.w * o.P1[2]};
+        acc[0] += __builtin_fma(w1[0], o.P1[0], w0[0] * o.P0[0]);
+        acc[1] += __builtin_fma(w1[0], o.P1[1], w0[0] * o.P0[1]);
+        acc[2] += __builtin_fma(w1[0], o.P1[2], w0[0] * o.P0[2]);
+        acc[3] += __builtin_fma(w1[1], o.P1[1], w0[1] * o.P0[1]);
+        acc[4] += __builtin_fma(w1[1], o.P1[2], w0[1] * o.P0[2]);
+        acc[5] += __builtin_fma(w1[2], o.P1[2], w0[2] * o.P0[2]);
+        acc[6] += __builtin_fma(w1[0], o.e1, w0[0] * o.e0);
+        acc[7] += __builtin_fma(w1[1], o.e1, w0[1] * o.e0);
+        acc[8] += __builtin_fma(w1[2], o.e1, w0[2] * o.e0);
+      } else {
+        double v[6];
+        bundle_load(vec + 6 * (size_t)f, v);
+        double s0 = 0.0, s1 = 0.0;
+#pragma unroll
+      for (int k = 0; k < 6; ++k) { s0 += o.C0[k] * v[k]; s1 += o.C1[k] * v[k]; }
+        s0 *= o.w; s1 *= o.w;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) acc[k] += __builtin_fma(o.P1[k], s1, o.P0[k] * s0);
+      }
+    }
+#pragma unroll
+    for (int k = 0; k < NT; ++k) acc[k] = refine_row_sum(acc[k]);
+    if (!run) {
+      if (MODE == B_BACK && e < M && lg < 3) a.w.Pc[3 * (size_t)e + lg] = a.w.P[3 * (size_t)e + lg];
+      continue;
+    }
+    if constexpr (MODE == B_LIN) {
+      const double H[6] = {acc[0] + lambda * acc[0], acc[1], acc[2], acc[3] + lambda * acc[3], acc[4], acc[5] + lambda * acc[5]};
+      double c0[3], c1[3], c2[3];
+      const double e0[3] = {1.0, 0.0, 0.0}, e1[3] = {0.0, 1.0, 0.0}, e2[3] = {0.0, 0.0, 1.0};
+      const bool ok = ldlt3_solve(H, e0, c0) && ldlt3_solve(H, e1, c1) && ldlt3_solve(H, e2, c2) && refine_finite(acc[6]) &&
+                      refine_finite(acc[7]) && refine_finite(acc[8]);
+      if (lg == 0) {
+        if (!ok) {
+          a.w.ctl->bad = 1;                                   // (whoever meets one stores the same 1)
+        } else {
+          double* V = a.w.Vinv + 6 * (size_t)e;
+          V[0] = c0[0]; V[1] = c1[0]; V[2] = c2[0]; V[3] = c1[1]; V[4] = c2[1]; V[5] = c2[2];
+          double* g = a.w.gj + 3 * (size_t)e;
+          g[0] = acc[6]; g[1] = acc[7]; g[2] = acc[8];
+        }
+      }
+    } else {
+      double Vi[6], y[3];
+      bundle_load(a.w.Vinv + 6 * (size_t)e, Vi);
+      if (MODE == B_PASS_A) {
+        sym3_mul(Vi, acc, y);
+        if (lg < 3) a.w.tj[3 * (size_t)e + lg] = lg == 0 ? y[0] : lg == 1 ? y[1] : y[2];
+      } else {
+        double g[3];
+        bundle_load(a.w.gj + 3 * (size_t)e, g);
+        const double s[3] = {g[0] + acc[0], g[1] + acc[1], g[2] + acc[2]};
+        sym3_mul(Vi, s, y);
+        if (lg < 3) a.w.Pc[3 * (size_t)e + lg] = p[lg == 0 ? 0 : lg == 1 ? 1 : 2] - (lg == 0 ? y[0] : lg == 1 ? y[1] : y[2]);
+      }
+    }
+  }
+}
+
+// ---- the frame side: one workgroup per free frame over its rows ------------------------------------------------------
+// U_f = sum w Jc^T Jc and g_f = sum w Jc^T e over ALL its rows; then, over the rows of free landmarks, sum W V^-1 W^T and
+// sum W V^-1 g_j; stored: the damped U_f, D_f = U_f - the first sum, r_f = -g_f + the second
+__global__ __launch_bounds__(BB) void bundle_frame_lin_kernel(MapBundleArgs a) {
+  __shared__ double s_row[BROWS][BTERMS], s_tot[BTERMS];
+  const MapBundleCtl& c = *a.w.ctl;
+  const int f = blockIdx.x, tid = threadIdx.x;
+  if (c.dead || a.w.pose_status[f] != BS_OK) return;
+  const int M = bundle_size(a);
+  const double lambda = c.lambda;
+  double T[12], K[9];
+  bundle_load(a.w.T + 12 * (size_t)f, T);
+#pragma unroll
+  for (int k = 0; k < 9; ++k) K[k] = a.K[k];
+  const int32_t* ent = a.l.ent + (size_t)f * a.n_max;
+  const float2* uv = reinterpret_cast<const float2*>(a.uv) + (size_t)f * a.uv_stride;
+  double acc[27];
+#pragma unroll
+  for (int k = 0; k < 27; ++k) acc[k] = 0.0;
+  for (int i = tid; i < a.n_max; i += BB) {
+    const int e = ent[i];
+    if (e < 0 || e >= M) continue;
+    double p[3];
+    bundle_load(a.w.P + 3 * (size_t)e, p);
+    const float2 m = uv[i];
+    BundleObs o;
+    bundle_obs(K, T, p, (double)m.x, (double)m.y, a.huber, o);
+    int k = 0;
+#pragma unroll
+    for (int r = 0; r < 6; ++r) {
+      const double w0 = o.w * o.C0[r], w1 = o.w * o.C1[r];
+#pragma unroll
+      for (int b = r; b < 6; ++b) acc[k++] += __builtin_fma(w1, o.C1[b], w0 * o.C0[b]);
+      acc[21 + r] += __builtin_fma(w1, o.e1, w0 * o.e0);
+    }
+  }
+  bundle_frame_reduce<27>(acc, s_row, s_tot);
+  double keep = 0.0;                                          // thread k < 27 keeps term k: the damped U (k < 21) or g (k >= 21)
+  {
+    const int diag[6] = {0, 6, 11, 15, 18, 20};
+#pragma unroll
+    for (int k = 0; k < 6; ++k) acc[diag[k]] += lambda * acc[diag[k]];
+#pragma unroll
+    for (int k = 0; k < 27; ++k) if (tid == k) keep = acc[k];
+  }
+#pragma unroll
+  for (int k = 0; k < 27; ++k) acc[k] = 0.0;
+  for (int i = tid; i < a.n_max; i += BB) {
+    const int e = ent[i];
+    if (!bundle_free_point(a, e, M)) continue;
+    double p[3], Vi[6], g[3];
+    bundle_load(a.w.P + 3 * (size_t)e, p);
+    bundle_load(a.w.Vinv + 6 * (size_t)e, Vi);
+    bundle_load(a.w.gj + 3 * (size_t)e, g);
+    const float2 m = uv[i];
+    BundleObs o;
+    bundle_obs(K, T, p, (double)m.x, (double)m.y, a.huber, o);
+    double W[6][3], Y[6][3];
+#pragma unroll
+    for (int r = 0; r < 6; ++r) {
+      const double w0 = o.w * o.C0[r], w1 = o.w * o.C1[r];
+#pragma unroll
+      for (int k = 0; k < 3; ++k) W[r][k] = __builtin_fma(w1, o.P1[k], w0 * o.P0[k]);
+      sym3_mul(Vi, W[r], Y[r]);
+    }
+    int k = 0;
+#pragma unroll
+    for (int r = 0; r < 6; ++r) {
+#pragma unroll
+      for (int b = r; b < 6; ++b) acc[k++] += Y[r][0] * W[b][0] + Y[r][1] * W[b][1] + Y[r][2] * W[b][2];
+      acc[21 + r] += Y[r][0] * g[0] + Y[r][1] * g[1] + Y[r][2] * g[2];
+    }
+  }
+  bundle_frame_reduce<27>(acc, s_row, s_tot);
+#pragma unroll
+  for (int k = 0; k < 27; ++k) {
+    if (tid == k) {
+      if (k < 21) { a.w.U[21 * (size_t)f + k] = keep; a.w.D[21 * (size_t)f + k] = keep - acc[k]; }
+      else a.w.r[6 * (size_t)f + (k - 21)] = -keep + acc[k];
+    }
+  }
+}
+
+// (S p)_f = U_f p_f - sum over the rows of free landmarks of W t_j,  W v = w Jc^T (Jp v);  and p_f . (S p)_f
+__global__ __launch_bounds__(BB) void bundle_frame_sp_kernel(MapBundleArgs a) {
+  __shared__ double s_row[BROWS][BTERMS], s_tot[BTERMS];
+  const MapBundleCtl& c = *a.w.ctl;
+  const int f = blockIdx.x, tid = threadIdx.x;
+  if (c.dead || c.bad || c.stop || a.w.pose_status[f] != BS_OK) return;
+  const int M = bundle_size(a);
+  double T[12], K[9];
+  bundle_load(a.w.T + 12 * (size_t)f, T);
+#pragma unroll
+  for (int k = 0; k < 9; ++k) K[k] = a.K[k];
+  const int32_t* ent = a.l.ent + (size_t)f * a.n_max;
+  const float2* uv = reinterpret_cast<const float2*>(a.uv) + (size_t)f * a.uv_stride;
+  double acc[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+  for (int i = tid; i < a.n_max; i += BB) {
+    const int e = ent[i];
+    if (!bundle_free_point(a, e, M)) continue;
+    double p[3], t[3];
+    bundle_load(a.w.P + 3 * (size_t)e, p);
+    bundle_load(a.w.tj + 3 * (size_t)e, t);
+    const float2 m = uv[i];
+    BundleObs o;
+    bundle_obs(K, T, p, (double)m.x, (double)m.y, a.huber, o);
+    const double s0 = o.w * (o.P0[0] * t[0] + o.P0[1] * t[1] + o.P0[2] * t[2]);
+    const double s1 = o.w * (o.P1[0] * t[0] + o.P1[1] * t[1] + o.P1[2] * t[2]);
+#pragma unroll
+    for (int k = 0; k < 6; ++k) acc[k] += __builtin_fma(o.C1[k], s1, o.C0[k] * s0);
+  }
+  bundle_frame_reduce<6>(acc, s_row, s_tot);
+  if (tid == 0) {
+    double U[21], pv[6], pq = 0.0;
+    bundle_load(a.w.U + 21 * (size_t)f, U);
+    bundle_load(a.w.p + 6 * (size_t)f, pv);
+#pragma unroll
+    for (int r = 0; r < 6; ++r) {
+      double s = 0.0;
+#pragma unroll
+      for (int b = 0; b < 6; ++b) s += U[r <= b ? tri6(r, b) : tri6(b, r)] * pv[b];
+      const double q = s - acc[r];
+      a.w.q[6 * (size_t)f + r] = q;
+      pq += pv[r] * q;
+    }
+    a.w.pq[f] = pq;
+  }
+}
+
+// ---- the vector side of PCG: one workgroup ------------------------------------------------------------------------------
+__global__ __launch_bounds__(BB) void bundle_cg_init_kernel(MapBundleArgs a) {
+  __shared__ double s_sum[256];
+  __shared__ int s_bad;
+  MapBundleCtl& c = *a.w.ctl;
+  if (c.dead) return;
+  const int bad_before = c.bad, n_free = c.n_free_frames;
+  if (threadIdx.x == 0) s_bad = 0;
+  __syncthreads();
+  double rz = 0.0, rr = 0.0;
+  if (!bad_before) {
+    for (int f = threadIdx.x; f < a.n_frames; f += BB) {
+      double* x = a.w.x + 6 * (size_t)f;
+      for (int k = 0; k < 6; ++k) x[k] = 0.0;
+      if (a.w.pose_status[f] != BS_OK) continue;
+      double D[21], r[6], z[6];
+      bundle_load(a.w.D + 21 * (size_t)f, D);
+      bundle_load(a.w.r + 6 * (size_t)f, r);
+      if (!ldlt6d_solve(D, r, z)) { atomicOr(&s_bad, 1); continue; }
+#pragma unroll
+    for (int k = 0; k < 6; ++k) { a.w.z[6 * (size_t)f + k] = z[k]; a.w.p[6 * (size_t)f + k] = z[k]; rz += r[k] * z[k]; rr += r[k] * r[k]; }
+    }
+  }
+  const double t_rz = bundle_tree_sum(rz, s_sum);
+  const double t_rr = bundle_tree_sum(rr, s_sum);
+  if (threadIdx.x == 0) {
+    const int bad = bad_before | s_bad;
+    c.bad = bad; c.iters = 0; c.nostep = 0;
+    c.stop = bad || n_free == 0;
+    c.rz = t_rz; c.rr0 = t_rr; c.rr = t_rr;
+  }
+}
+
+__global__ __launch_bounds__(BB) void bundle_cg_update_kernel(MapBundleArgs a) {
+  __shared__ double s_sum[256];
+  MapBundleCtl& c = *a.w.ctl;
+  if (c.dead || c.bad || c.stop) return;
+  const double rz_old = c.rz, rr0 = c.rr0;
+  const int iters = c.iters;
+  double mine = 0.0;
+  for (int f = threadIdx.x; f < a.n_frames; f += BB)
+    if (a.w.pose_status[f] == BS_OK) mine += a.w.pq[f];
+  const double pSp = bundle_tree_sum(mine, s_sum);
+  if (!(pSp > 0.0) || !refine_finite(pSp)) {                   // (uniform: every thread holds the same total)
+    if (threadIdx.x == 0) { c.stop = 1; c.nostep = iters == 0; }
+    return;
+  }
+  const double alpha = rz_old / pSp;
+  double rz = 0.0, rr = 0.0;
+  for (int f = threadIdx.x; f < a.n_frames; f += BB) {
+    if (a.w.pose_status[f] != BS_OK) continue;
+    double D[21], r[6], z[6];
+    bundle_load(a.w.D + 21 * (size_t)f, D);
+#pragma unroll
+    for (int k = 0; k < 6; ++k) {
+      a.w.x[6 * (size_t)f + k] += alpha * a.w.p[6 * (size_t)f + k];
+      r[k] = a.w.r[6 * (size_t)f + k] - alpha * a.w.q[6 * (size_t)f + k];
+      a.w.r[6 * (size_t)f + k] = r[k];
+    }
+    if (!ldlt6d_solve(D, r, z))                               // (D factorised at the round's start: only a non-finite r ends here)
+#pragma unroll
+      for (int k = 0; k < 6; ++k) z[k] = 0.0;
+#pragma unroll
+    for (int k = 0; k < 6; ++k) { a.w.z[6 * (size_t)f + k] = z[k]; rz += r[k] * z[k]; rr += r[k] * r[k]; }
+  }
+  const double t_rz = bundle_tree_sum(rz, s_sum);
+  const double t_rr = bundle_tree_sum(rr, s_sum);
+  const double beta = t_rz / rz_old;
+  for (int f = threadIdx.x; f < a.n_frames; f += BB) {
+    if (a.w.pose_status[f] != BS_OK) continue;
+    for (int k = 0; k < 6; ++k) a.w.p[6 * (size_t)f + k] = a.w.z[6 * (size_t)f + k] + beta * a.w.p[6 * (size_t)f + k];
+  }
+  if (threadIdx.x == 0) {
+    c.rz = t_rz; c.rr = t_rr; c.iters = iters + 1;
+    if (!(sqrt(t_rr) > a.cg_tol * sqrt(rr0))) c.stop = 1;      // (a residual that is not finite stops as well)
+  }
+}
+
+// ---- the round's verdict: one workgroup ----------------------------------------------------------------------------------
+__global__ __launch_bounds__(BDEC) void bundle_decide_kernel(MapBundleArgs a, int round) {
+  __shared__ double s_sum[256];
+  __shared__ int s_flag;
+  MapBundleCtl& c = *a.w.ctl;
+  vox_map_bundle_round* rec = a.rounds_out ? static_cast<vox_map_bundle_round*>(a.rounds_out) + round : nullptr;
+  if (c.dead) {
+    if (threadIdx.x == 0 && rec) { rec->cost = 0.0; rec->cost_candidate = 0.0; rec->lambda = 0.0; rec->residual = 0.0; rec->cg_iterations = 0; rec->accepted = 0; }
+    return;
+  }
+  const int M = bundle_size(a);
+  const bool formed = !c.bad && !c.nostep;
+  const double cur = c.cost_cur, lambda = c.lambda, rr0 = c.rr0, rr = c.rr;
+  const int iters = c.iters, n_free = c.n_free_frames;
+  if (threadIdx.x == 0) s_flag = 0;
+  __syncthreads();
+  double mine = 0.0;
+  int fl = 0;
+  if (formed && threadIdx.x < 256)
+    for (int f = threadIdx.x; f < a.n_frames; f += 256) { mine += a.w.fcost[f]; fl |= a.w.fflag[f]; }
+  if (fl) atomicOr(&s_flag, 1);
+  const double cand = bundle_tree_sum(mine, s_sum);            // (its barriers publish s_flag too)
+  const bool accept = formed && refine_finite(cand) && !s_flag && cand <= cur;
+  if (accept) {
+    for (size_t k = threadIdx.x; k < 12 * (size_t)a.n_frames; k += BDEC)
+      if (a.w.pose_status[k / 12] == BS_OK) a.w.T[k] = a.w.Tc[k];
+    for (size_t k = threadIdx.x; k < 3 * (size_t)M; k += BDEC) a.w.P[k] = a.w.Pc[k];
+  }
+  if (threadIdx.x == 0) {
+    if (rec) {
+      rec->cost = cur; rec->cost_candidate = formed ? cand : 0.0; rec->lambda = lambda;
+      rec->residual = (n_free > 0 && !c.bad) ? (rr0 > 0.0 ? sqrt(rr / rr0) : 0.0) : 0.0;
+      rec->cg_iterations = iters; rec->accepted = accept;
+    }
+    if (accept) {
+      c.cost_cur = cand; c.n_accepted += 1;
+      if (lambda > 0.0) { const double l = lambda / 10.0; c.lambda = l > 1e-12 ? l : 1e-12; }
+    } else {
+      const double l = 10.0 * lambda;
+      c.lambda = l > 1e-6 ? l : 1e-6;
+    }
+    c.bad = 0; c.stop = 0; c.nostep = 0; c.iters = 0;
+  }
+}
+
+// ---- the end: the state rounded to float32 into the candidate arrays, its cost (bundle_cost_kernel<FINAL>), the verdict ---------
+__global__ __launch_bounds__(BB) void bundle_round_kernel(MapBundleArgs a) {
+  if (a.w.ctl->dead) return;
+  const int M = bundle_size(a);
+  const size_t k = (size_t)blockIdx.x * BB + threadIdx.x;
+  if (k < 12 * (size_t)a.n_frames) a.w.Tc[k] = (double)(float)a.w.T[k];
+  if (k < 3 * (size_t)M) a.w.Pc[k] = (double)(float)a.w.P[k];
+}
+
+__global__ __launch_bounds__(BDEC) void bundle_finish_kernel(MapBundleArgs a) {
+  __shared__ double s_sum[256];
+  const MapBundleCtl& c = *a.w.ctl;
+  const int M = bundle_size(a);
+  double mine = 0.0;
+  if (!c.dead && threadIdx.x < 256)
+    for (int f = threadIdx.x; f < a.n_frames; f += 256) mine += a.w.fcost[f];
+  const double total = bundle_tree_sum(mine, s_sum);
+  int status = c.status;
+  if (!c.dead) {
+    if (a.n_rounds > 0 && c.n_accepted == 0) status = VOX_MAP_BUNDLE_NO_STEP;
+    else if (!(total <= c.cost_start)) status = VOX_MAP_BUNDLE_COST_ROSE;      // (a cost that is not finite has risen)
+  }
+  const bool write = status == VOX_MAP_BUNDLE_OK && c.n_accepted > 0;
+  for (int f = threadIdx.x; f < a.n_frames; f += BDEC) {
+    const int ps = a.w.pose_status[f];
+    if (a.pose_status_out) a.pose_status_out[f] = ps;
+    if (write && ps == BS_OK) {
+      const double* T = a.w.Tc + 12 * (size_t)f;
+      float* o = a.T16 + 16 * (size_t)f;
+      for (int col = 0; col < 4; ++col) {
+        o[4 * col] = (float)T[3 * col]; o[4 * col + 1] = (float)T[3 * col + 1]; o[4 * col + 2] = (float)T[3 * col + 2];
+        o[4 * col + 3] = col == 3 ? 1.f : 0.f;
+      }
+    }
+  }
+  for (int e = threadIdx.x; e < M; e += BDEC) {
+    const int ps = a.w.point_status[e];
+    if (a.point_status_out) a.point_status_out[e] = ps;
+    if (write && ps == BS_OK)
+      for (int k = 0; k < 3; ++k) a.pts[3 * (size_t)e + k] = (float)a.w.Pc[3 * (size_t)e + k];
+  }
+  if (threadIdx.x == 0) {
+    vox_map_bundle_stats* s = static_cast<vox_map_bundle_stats*>(a.stats);
+    s->status = status; s->n_frames = a.n_frames; s->n_entries = M; s->n_obs = c.n_obs; s->n_free_frames = c.n_free_frames;
+    s->n_free_points = c.n_free_points; s->n_accepted = c.n_accepted; s->reserved = 0;
+    s->cost_before = c.cost_start; s->cost_after = c.dead ? c.cost_start : total;
+  }
+}
+
+MapBundleWs map_bundle_layout(void* base, int n_frames, int bound) {
+  MapBundleWs w{};
+  WsCarver c(base);
+  const size_t F = (size_t)n_frames, B = (size_t)(bound > 0 ? bound : 1), d = sizeof(double);
+  w.T = c.take<double>(12 * d * F); w.Tc = c.take<double>(12 * d * F);
+  w.P = c.take<double>(3 * d * B); w.Pc = c.take<double>(3 * d * B);
+  w.Vinv = c.take<double>(6 * d * B); w.gj = c.take<double>(3 * d * B); w.tj = c.take<double>(3 * d * B);
+  w.U = c.take<double>(21 * d * F); w.D = c.take<double>(21 * d * F);
+  w.r = c.take<double>(6 * d * F); w.x = c.take<double>(6 * d * F); w.z = c.take<double>(6 * d * F);
+  w.p = c.take<double>(6 * d * F); w.q = c.take<double>(6 * d * F);
+  w.pq = c.take<double>(d * F); w.fcost = c.take<double>(d * F);
+  w.fflag = c.take<int>(4 * F); w.n_obs = c.take<int>(4 * F);
+  w.pose_status = c.take<int32_t>(4 * F); w.point_status = c.take<int32_t>(4 * B);
+  w.ctl = c.take<MapBundleCtl>(sizeof(MapBundleCtl));
+  w.bytes = c.bytes;
+  return w;
+}
+
+hipError_t launch_map_bundle(hipStream_t st, const MapBundleArgs& a, int n_cu) {
+  MapRefineArgs la{};
+  la.w = a.l; la.bound = a.bound; la.n_frames = a.n_frames; la.n_max = a.n_max;
+  hipError_t e = launch_map_refine_lists(st, la);
+  if (e != hipSuccess) return e;
+  const dim3 frames(a.n_frames), wg(BB), one(1);
+  const int B = a.bound > 0 ? a.bound : 1;
+  const int n_batches = (B + BLPB - 1) / BLPB;
+  const int cap = 4 * (n_cu > 0 ? n_cu : 256);
+  const dim3 points(n_batches < cap ? n_batches : cap);
+  hipLaunchKernelGGL(bundle_init_frames_kernel, frames, wg, 0, st, a);
+  hipLaunchKernelGGL(bundle_init_points_kernel, dim3((B + BB - 1) / BB), wg, 0, st, a);
+  hipLaunchKernelGGL(bundle_census_kernel, one, wg, 0, st, a);
+  hipLaunchKernelGGL(bundle_cost_kernel<B_START>, frames, wg, 0, st, a);
+  hipLaunchKernelGGL(bundle_start_kernel, one, wg, 0, st, a);
+  for (int r = 0; r < a.n_rounds; ++r) {
+    hipLaunchKernelGGL(bundle_point_kernel<B_LIN>, points, wg, 0, st, a);
+    hipLaunchKernelGGL(bundle_frame_lin_kernel, frames, wg, 0, st, a);
+    hipLaunchKernelGGL(bundle_cg_init_kernel, one, wg, 0, st, a);
+    for (int k = 0; k < a.n_cg; ++k) {
+      hipLaunchKernelGGL(bundle_point_kernel<B_PASS_A>, points, wg, 0, st, a);
+      hipLaunchKernelGGL(bundle_frame_sp_kernel, frames, wg, 0, st, a);
+      hipLaunchKernelGGL(bundle_cg_update_kernel, one, wg, 0, st, a);
+    }
+    hipLaunchKernelGGL(bundle_point_kernel<B_BACK>, points, wg, 0, st, a);
+    hipLaunchKernelGGL(bundle_cost_kernel<B_CAND>, frames, wg, 0, st, a);
+    hipLaunchKernelGGL(bundle_decide_kernel, one, dim3(BDEC), 0, st, a, r);
+    e = hipGetLastError();
+    if (e != hipSuccess) return e;
+  }
+  const size_t most = 12 * (size_t)a.n_frames > 3 * (size_t)B ? 12 * (size_t)a.n_frames : 3 * (size_t)B;
+  hipLaunchKernelGGL(bundle_round_kernel, dim3((unsigned)((most + BB - 1) / BB)), wg, 0, st, a);
+  hipLaunchKernelGGL(bundle_cost_kernel<B_FINAL>, frames, wg, 0, st, a);
+  hipLaunchKernelGGL(bundle_finish_kernel, one, dim3(BDEC), 0, st, a);
+  return hipGetLastError();
+}
+
+}  // namespace vo

@@ -245,7 +245,7 @@ MapRefineWs map_refine_layout(void* base, int n_frames, int n_max, int bound) {
   return w;
 }
 
-hipError_t launch_map_refine(hipStream_t st, const MapRefineArgs& a, int n_cu) {
+hipError_t launch_map_refine_lists(hipStream_t st, const MapRefineArgs& a) {
   const size_t rows = (size_t)a.n_frames * (size_t)a.n_max, B = (size_t)(a.bound > 0 ? a.bound : 1);
   const int nbE = (int)((B + RB - 1) / RB);
   hipError_t e = hipMemsetAsync(a.w.cnt, 0, sizeof(int) * 2 * B, st);
@@ -259,6 +259,12 @@ hipError_t launch_map_refine(hipStream_t st, const MapRefineArgs& a, int n_cu) {
     hipLaunchKernelGGL(map_refine_scatter_kernel, dim3(row_blocks), dim3(RB), 0, st, a);
     hipLaunchKernelGGL(map_refine_order_kernel, dim3(row_blocks), dim3(RB), 0, st, a);
   }
+  return hipGetLastError();
+}
+
+hipError_t launch_map_refine(hipStream_t st, const MapRefineArgs& a, int n_cu) {
+  const hipError_t e = launch_map_refine_lists(st, a);
+  if (e != hipSuccess) return e;
   if (a.bound > 0) {
     const int n_batches = (a.bound + RLPB - 1) / RLPB;
     // 104 VGPRs leave 4 waves per SIMD, i.e. 4 workgroups of 256 threads per CU (4 x 24 KiB of LDS fit as well): that many stay

@@ -500,6 +500,51 @@ struct MapPoseArgs {
 // after the lookup has filled `ent`: one workgroup per frame runs all rounds, then the statistics
 hipError_t launch_map_pose_refine(hipStream_t st, const MapPoseArgs& a);
 
+// ---- joint adjustment of poses and points by matrix-free Schur PCG (map_bundle.hip, vox_map_bundle*) ----------------
+// The observation lists of the point half alone (memset, count, offsets, scan, scatter, order): what launch_map_refine runs
+// before its refinement kernel, for callers that traverse the lists themselves.
+hipError_t launch_map_refine_lists(hipStream_t st, const MapRefineArgs& a);
+// the control block of a call: written by the one-workgroup launches (and `bad` by whoever meets a pivot that is not > 0)
+struct MapBundleCtl {
+  double lambda, cost_cur, cost_start, rz, rr0, rr;
+  int status;                           // the call status decided at the start (VOX_MAP_BUNDLE_*), 0 while alive
+  int dead;                             // NOT_FINITE, BEHIND or NOTHING_FREE: no round runs
+  int bad;                              // this round: a pivot of some V_j or D_f is not > 0
+  int stop;                             // this round: PCG has stopped, its remaining launches return at once
+  int nostep;                           // this round: free frames exist and PCG could not take one iteration
+  int iters;                            // this round: PCG iterations taken
+  int n_accepted, n_free_frames, n_free_points, n_obs;
+};
+struct MapBundleWs {
+  double *T, *Tc;                       // [n_frames][12] state / candidate: R column-major, then t
+  double *P, *Pc;                       // [bound][3] state / candidate
+  double *Vinv, *gj, *tj;               // [bound][6] (damped V_j)^-1, upper triangle; [bound][3] g_j; [bound][3] pass A's t_j
+  double *U, *D;                        // [n_frames][21] damped U_f / D_f, upper triangles row by row
+  double *r, *x, *z, *p, *q;            // [n_frames][6] the PCG vectors; q = S p
+  double *pq, *fcost;                   // [n_frames] p_f . q_f / the frame's cost of the last evaluation
+  int *fflag, *n_obs;                   // [n_frames] 1: some camera z not > 0 in the last evaluation / observations
+  int32_t *pose_status, *point_status;  // [n_frames], [bound]
+  MapBundleCtl* ctl;
+  size_t bytes;
+};
+MapBundleWs map_bundle_layout(void* base, int n_frames, int bound);
+struct MapBundleArgs {
+  MapRefineWs l;                        // the lookup's entries and the ordered lists (map_refine_layout)
+  MapBundleWs w;
+  float* pts; const int* hdr; int cap, bound;         // the map
+  const float* uv; size_t uv_stride;
+  int n_max, n_frames;
+  float* T16; const uint8_t* fixed;
+  double K[9];                          // column-major
+  int n_rounds, n_cg, min_obs_pose, min_obs_point;
+  double cg_tol, lambda0, huber;
+  int32_t *pose_status_out, *point_status_out;        // or null
+  void* rounds_out;                     // [n_rounds] vox_map_bundle_round, or null
+  void* stats;                          // vox_map_bundle_stats
+};
+// after the lookup has filled l.ent: the lists, then the fixed sequence of 3 (n_cg + 2) launches per round
+hipError_t launch_map_bundle(hipStream_t st, const MapBundleArgs& a, int n_cu);
+
 // ---- epipolar initialisation, device half (epi.hip) ------------------------------------------------------
 size_t epi_workspace_bytes();
 // maxima of both point sets + the 45 sums of A^T A + the number of rows / of pairs with a bad index, into ws:
