@@ -82,6 +82,21 @@ struct BundleOptions {
   float huber_px = 0;
 };
 
+//! voe_map_cull: which landmarks leave the map.  A threshold of 0 switches its test off.
+struct CullOptions {
+  int min_obs = 3;
+  int min_frames = 2;
+  float max_rms_px = 2.f;
+  float max_err_px = 0;
+  float min_parallax_deg = 0;
+  bool drop_unseen = false;
+  bool dry_run = false;
+};
+inline const char* cull_verdict_name(int verdict) {
+  static const char* names[] = {"KEPT", "UNSEEN", "FEW_OBS", "FEW_FRAMES", "NOT_FINITE", "BEHIND", "HIGH_ERROR", "LOW_PARALLAX"};
+  return verdict >= 0 && verdict < 8 ? names[verdict] : "?";
+}
+
 class DeviceMap {
  public:
   explicit DeviceMap(int capacity = 0, Context& ctx = default_context()) : ctx_(ctx.handle()) {
@@ -254,6 +269,26 @@ class DeviceMap {
       for (int k = 0; k < 16; ++k) poses[f].data()[k] = w.T[16 * f + k];
     r.resize((size_t)(opt.n_rounds > 0 ? opt.n_rounds : 0));
     if (rounds) *rounds = r;
+    return st;
+  }
+
+  //! landmarks taken out of the map (voe_map_cull): every entry judged from all the rows of the frames that see it, the poses
+  //! (p_cam = T p_map, one per frame) given; the survivors keep their order.  *verdict receives one VOE_MAP_CULL_* per OLD entry,
+  //! *remap its new index or -1, *entries its statistics.  With opt.dry_run the map stays as it is.
+  voe_map_cull_stats cull(const Camera& cam, const std::vector<Vector2fVector>& pixels, const std::vector<Vector10fVector>& appearances,
+                          const IsometryVector& poses, const CullOptions& opt = CullOptions(), std::vector<int32_t>* verdict = nullptr,
+                          std::vector<int32_t>* remap = nullptr, std::vector<voe_map_cull_entry>* entries = nullptr) {
+    const Window w = pack("DeviceMap::cull", pixels, appearances, poses);
+    const size_t M = (size_t)size();
+    if (verdict) verdict->assign(M, -1);
+    if (remap) remap->assign(M, -1);
+    if (entries) entries->assign(M, voe_map_cull_entry{});
+    const voe_map_cull_params prm{opt.min_obs, opt.min_frames, opt.max_rms_px, opt.max_err_px, opt.min_parallax_deg, opt.drop_unseen ? 1 : 0,
+                                  opt.dry_run ? 1 : 0};
+    voe_map_cull_stats st{};
+    check(voe_map_cull(h_, (int)w.F, cam.cameraMatrix().data(), w.uv.data(), w.app.data(), w.n.data(), (int)w.cap, w.T.data(), &prm,
+                       verdict && M ? verdict->data() : nullptr, remap && M ? remap->data() : nullptr,
+                       entries && M ? entries->data() : nullptr, &st), "voe_map_cull");
     return st;
   }
 

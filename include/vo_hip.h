@@ -848,4 +848,5 @@ int vo_map_refine(vo_map *m, int n_frames, const float K[9], const float *uv, co
 /* motion-only refinement of a window's poses on the map's cost and its alternation with vo_map_refine: a header of its own */
 #include "vo_map_adjust.h"
 #include "vo_map_bundle.h"
+#include "vo_map_cull.h"
 #endif /* VO_HIP_H */

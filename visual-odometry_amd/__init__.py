@@ -27,6 +27,12 @@ from .api import (  # noqa: F401
     MapBundleRound,
     MapBundleStats,
     MAP_BUNDLE_STATUS,
+    MapCullParams,
+    MapCullEntry,
+    MapCullStats,
+    MAP_CULL_ENTRY_DTYPE,
+    MAP_CULL_VERDICT,
+    MAP_CULL_STATUS,
     PICPSolver,
     VoError,
     compute_correspondences_images,

@@ -626,6 +626,37 @@ class Map:
                 [rounds[k].as_dict() for k in range(max(int(n_rounds), 0))], st.as_dict())
 
 
+    # ---- culling of landmarks (voe_map_cull*, include/vo_map_cull.h) ----
+    def cull_batch_dev(self, camera: Camera, n_frames, d_uv, uv_stride, d_app, app_stride, n_max, d_n, d_T16, params: "MapCullParams",
+                       d_verdict_out, d_remap_out, d_entry_out, d_stats):
+        """voe_map_cull_batch_dev on device pointers (ints; d_n and the three outputs may be None; strides in pixels / rows):
+        enqueues and returns.  d_entry_out: size x 48 bytes (MapCullEntry); d_stats: 48 bytes (MapCullStats)."""
+        v = lambda d: C.c_void_p(d) if d else None
+        _chk(self.lib.voe_map_cull_batch_dev(self.h, C.c_int(n_frames), _ptr(_colmajor(camera._K, 3)), v(d_uv), C.c_size_t(uv_stride),
+                                             v(d_app), C.c_size_t(app_stride), C.c_int(n_max), v(d_n), v(d_T16), C.byref(params),
+                                             v(d_verdict_out), v(d_remap_out), v(d_entry_out), v(d_stats)))
+
+    def cull(self, camera: Camera, frames, poses, min_obs=3, min_frames=2, max_rms_px=2.0, max_err_px=0.0, min_parallax_deg=0.0,
+             drop_unseen=False, dry_run=False):
+        """voe_map_cull: every entry judged from all the rows of `frames` (as in refine) that see it, the poses (4x4,
+        p_cam = T p_map) given; the entries that fail are taken out of the map, the survivors keep their order.  Returns
+        dict(verdict (old size,) int32: MAP_CULL_VERDICT names the codes, remap (old size,) int32: the new index or -1,
+        entries: a structured array of MapCullEntry records, stats dict: MAP_CULL_STATUS names stats["status"])."""
+        F, cap, uv, app, n, T, _ = self._window(frames, poses, None)
+        size = max(len(self), 1)
+        verdict = np.full(size, -1, np.int32)
+        remap = np.full(size, -2, np.int32)
+        entries = np.zeros(size, MAP_CULL_ENTRY_DTYPE)
+        st = MapCullStats()
+        prm = MapCullParams(int(min_obs), int(min_frames), float(max_rms_px), float(max_err_px), float(min_parallax_deg), int(bool(drop_unseen)),
+                            int(bool(dry_run)))
+        _chk(self.lib.voe_map_cull(self.h, C.c_int(F), _ptr(_colmajor(camera._K, 3)), _ptr(uv[:, :cap]) if cap else None,
+                                   _ptr(app[:, :cap]) if cap else None, _ptr(n), C.c_int(cap), _ptr(T), C.byref(prm), _ptr(verdict),
+                                   _ptr(remap), C.c_void_p(entries.ctypes.data), C.byref(st)))
+        k = st.n_before
+        return dict(verdict=verdict[:k].copy(), remap=remap[:k].copy(), entries=entries[:k].copy(), stats=st.as_dict())
+
+
 class MapLocaliseStats(C.Structure):
     """vo_map_localise_stats (include/vo_hip.h)"""
     _fields_ = [("status", C.c_int32), ("n_rows", C.c_int32), ("n_hits", C.c_int32), ("ransac_status", C.c_int32),
@@ -716,6 +747,34 @@ class MapBundleStats(C.Structure):
 
 assert C.sizeof(MapBundleParams) == 28 and C.sizeof(MapBundleRound) == 40 and C.sizeof(MapBundleStats) == 48
 MAP_BUNDLE_STATUS = ("OK", "NOT_FINITE", "BEHIND", "NOTHING_FREE", "NO_STEP", "COST_ROSE")   # VOX_MAP_BUNDLE_*
+
+
+class MapCullParams(C.Structure):
+    """voe_map_cull_params (include/vo_map_cull.h)"""
+    _fields_ = [("min_obs", C.c_int32), ("min_frames", C.c_int32), ("max_rms_px", C.c_float), ("max_err_px", C.c_float),
+                ("min_parallax_deg", C.c_float), ("drop_unseen", C.c_int32), ("dry_run", C.c_int32)]
+
+
+class MapCullEntry(C.Structure):
+    """voe_map_cull_entry (include/vo_map_cull.h): one landmark"""
+    _fields_ = [("verdict", C.c_int32), ("n_obs", C.c_int32), ("n_frames", C.c_int32), ("reserved", C.c_int32), ("mean_sq_px", C.c_double),
+                ("max_sq_px", C.c_double), ("min_z", C.c_double), ("cos_parallax", C.c_double)]
+
+
+class MapCullStats(C.Structure):
+    """voe_map_cull_stats (include/vo_map_cull.h)"""
+    _fields_ = [("status", C.c_int32), ("n_before", C.c_int32), ("n_kept", C.c_int32), ("n_obs", C.c_int32), ("by_verdict", C.c_int32 * 8)]
+
+    def as_dict(self):
+        return dict(status=self.status, n_before=self.n_before, n_kept=self.n_kept, n_obs=self.n_obs, by_verdict=list(self.by_verdict))
+
+
+assert C.sizeof(MapCullParams) == 28 and C.sizeof(MapCullEntry) == 48 and C.sizeof(MapCullStats) == 48
+MAP_CULL_ENTRY_DTYPE = np.dtype([("verdict", "<i4"), ("n_obs", "<i4"), ("n_frames", "<i4"), ("reserved", "<i4"), ("mean_sq_px", "<f8"),
+                                 ("max_sq_px", "<f8"), ("min_z", "<f8"), ("cos_parallax", "<f8")])
+assert MAP_CULL_ENTRY_DTYPE.itemsize == 48
+MAP_CULL_VERDICT = ("KEPT", "UNSEEN", "FEW_OBS", "FEW_FRAMES", "NOT_FINITE", "BEHIND", "HIGH_ERROR", "LOW_PARALLAX")   # VOE_MAP_CULL_*
+MAP_CULL_STATUS = ("OK", "NOTHING_DROPPED")
 
 
 def triangulate_points(k, X, correspondences, p1_img, p2_img, app2=None, want_pairs=True,

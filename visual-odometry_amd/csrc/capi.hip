@@ -2125,6 +2125,7 @@ struct vo_map {
   DevBuf ref_ws;                // vo_map_refine*: the entries seen, the observation lists, status and cost per entry
   DevBuf pose_ws;               // vo_map_refine_poses*: the entries seen, status, observation count and cost per frame
   DevBuf bundle_ws;             // vox_map_bundle*: the state in double, the blocks and the PCG vectors (the lists live in ref_ws)
+  DevBuf cull_ws;               // voe_map_cull*: verdict, remap, ranks, the staging area of the survivors (the lists live in ref_ws)
 };
 
 constexpr int MAP_MAX_ENTRIES = 1 << 29;      // 2.5 x that many table slots still fit 32 bits
@@ -2217,7 +2218,7 @@ int vo_map_destroy(vo_map* m) {
   map_free_arrays(m->d);
   if (m->d.hdr) (void)hipFree(m->d.hdr);
   if (m->hist) (void)hipFree(m->hist);
-  m->scratch.release(); m->up_xyz.release(); m->up_app.release(); m->look_ws.release(); m->loc_ws.release(); m->ref_ws.release(); m->pose_ws.release(); m->bundle_ws.release();
+  m->scratch.release(); m->up_xyz.release(); m->up_app.release(); m->look_ws.release(); m->loc_ws.release(); m->ref_ws.release(); m->pose_ws.release(); m->bundle_ws.release(); m->cull_ws.release();
   if (m->solver) (void)vo_picp_destroy(m->solver);
   delete m;
   return VO_OK;
@@ -2913,6 +2914,97 @@ int vox_map_bundle(vo_map* m, int n_frames, const float K[9], const float* uv, c
   if (point_status_out && size > 0)
     VO_HIP_CHECK(hipMemcpyAsync(point_status_out, c->out[1].p, sizeof(int32_t) * (size_t)size, hipMemcpyDeviceToHost, c->stream));
   VO_HIP_CHECK(hipStreamSynchronize(c->stream));
+  return VO_OK;
+}
+
+// ---- culling of landmarks (map_cull.hip; include/vo_map_cull.h: the voe_ namespace) ---------------------------------------
+static_assert(sizeof(voe_map_cull_params) == 28 && sizeof(voe_map_cull_entry) == 48 && sizeof(voe_map_cull_stats) == 48,
+              "the records of include/vo_map_cull.h as the kernels write them");
+
+static int cull_check_params(const char* fn, const voe_map_cull_params* p) {
+  if (p->min_obs < 1) return fail(VO_ERR_INVALID_ARG, "%s: min_obs must be at least 1", fn);
+  if (p->min_frames < 1) return fail(VO_ERR_INVALID_ARG, "%s: min_frames must be at least 1", fn);
+  if (!(p->max_rms_px >= 0.f && p->max_rms_px <= 3.402823466e38f)) return fail(VO_ERR_INVALID_ARG, "%s: max_rms_px must be finite and not negative", fn);
+  if (!(p->max_err_px >= 0.f && p->max_err_px <= 3.402823466e38f)) return fail(VO_ERR_INVALID_ARG, "%s: max_err_px must be finite and not negative", fn);
+  if (!(p->min_parallax_deg >= 0.f && p->min_parallax_deg < 180.f)) return fail(VO_ERR_INVALID_ARG, "%s: min_parallax_deg must be in [0, 180)", fn);
+  return VO_OK;
+}
+
+int voe_map_cull_batch_dev(vo_map* m, int n_frames, const float K[9], const float* d_uv, size_t uv_stride, const float* d_app,
+                           size_t app_stride, int n_max, const int* d_n, const float* d_T16, const voe_map_cull_params* p,
+                           int32_t* d_verdict_out, int32_t* d_remap_out, voe_map_cull_entry* d_entry_out, voe_map_cull_stats* d_stats) {
+  VO_MAP_LIVE(m);
+  const char* fn = "voe_map_cull_batch_dev";
+  if (!(K && p && d_T16 && d_stats)) return fail(VO_ERR_INVALID_ARG, "%s: null argument", fn);
+  if (!aligned8(d_entry_out)) return fail(VO_ERR_INVALID_ARG, "%s: device arrays must be 8-byte aligned", fn);
+  if (int r = refine_check(fn, n_frames, K, d_uv, uv_stride, d_app, app_stride, n_max, d_stats, 0, INT_MAX, 2, 2, 0.f, 0.f)) return r;
+  if (int r = cull_check_params(fn, p)) return r;
+  vo_ctx* c = m->ctx;
+  const int bound = map_bound(m);
+  MapCullWs cw = map_cull_layout(nullptr, bound);
+  if (c->capturing && m->cull_ws.cap < cw.bytes)              // (before the lookup is enqueued)
+    return fail(VO_ERR_NOT_READY, "%s: the workspace would have to grow inside a graph capture (make one call with %d frames of n_max %d "
+                                  "on this map before capturing)", fn, n_frames, n_max);
+  MapRefineWs rw;
+  if (int r = refine_prepare(fn, m, n_frames, d_app, app_stride, n_max, d_n, &rw)) return r;      // the one lookup of the call
+  VO_HIP_CHECK(m->cull_ws.ensure(cw.bytes, c->stream));
+  MapCullArgs a{};
+  a.l = rw; a.w = map_cull_layout(m->cull_ws.p, bound);
+  a.pts = m->d.pts; a.app = m->d.app; a.hdr = m->d.hdr; a.cap = m->d.cap; a.bound = bound;
+  a.uv = d_uv; a.uv_stride = uv_stride; a.n_max = n_max; a.n_frames = n_frames; a.T16 = d_T16;
+  for (int k = 0; k < 9; ++k) a.K[k] = K[k];
+  a.min_obs = p->min_obs; a.min_frames = p->min_frames; a.drop_unseen = p->drop_unseen != 0; a.dry_run = p->dry_run != 0;
+  a.max_mean_sq = (double)p->max_rms_px * (double)p->max_rms_px;
+  a.max_sq = (double)p->max_err_px * (double)p->max_err_px;
+  a.parallax = p->min_parallax_deg > 0.f;
+  a.cos_thr = a.parallax ? cos((double)p->min_parallax_deg * 3.14159265358979323846 / 180.0) : 1.0;
+  a.verdict = d_verdict_out ? d_verdict_out : a.w.verdict;
+  a.remap = d_remap_out ? d_remap_out : a.w.remap;
+  a.entry_out = d_entry_out; a.stats = d_stats;
+  VO_HIP_CHECK(launch_map_cull(c->stream, a, c->n_cu));
+  VO_HIP_CHECK(launch_map_rehash(c->stream, m->d, bound, a.w.ctl + 2));
+  VO_HIP_CHECK(launch_map_cull_stats(c->stream, a));
+  return VO_OK;
+}
+
+int voe_map_cull(vo_map* m, int n_frames, const float K[9], const float* uv, const float* app, const int* n_rows, int n_max,
+                 const float* T16, const voe_map_cull_params* params, int32_t* verdict_out, int32_t* remap_out,
+                 voe_map_cull_entry* entry_out, voe_map_cull_stats* stats_out) {
+  VO_MAP_LIVE(m);
+  vo_ctx* c = m->ctx;
+  VO_NOT_CAPTURING(c);
+  VO_REQUIRE(K && T16 && params && stats_out, "null argument");
+  VO_REQUIRE(n_frames >= 1 && n_frames <= 65535, "n_frames outside 1 .. 65535");
+  VO_REQUIRE(n_max >= 0 && (n_max == 0 || (uv && app)), "bad frames");
+  VO_REQUIRE((long long)n_max * n_frames <= (1ll << 30), "more than 2^30 rows in one call");
+  if (int r = set_device(c)) return r;
+  const size_t rows = (size_t)n_frames * (size_t)n_max;
+  if (int r = upload(c, c->in[0], uv, sizeof(float) * 2 * rows)) return r;
+  if (int r = upload(c, c->in[1], app, sizeof(float) * 10 * rows)) return r;
+  if (int r = upload(c, c->in[2], T16, sizeof(float) * 16 * (size_t)n_frames)) return r;
+  if (n_rows)
+    if (int r = upload(c, c->in[3], n_rows, sizeof(int) * (size_t)n_frames)) return r;
+  int size = 0;
+  if (int r = vo_map_size(m, &size)) return r;                // (waits: the host arrays may go away after the call)
+  const size_t S = (size_t)(size > 0 ? size : 1);
+  VO_HIP_CHECK(c->out[0].ensure(sizeof(int32_t) * 2 * S, c->stream));
+  VO_HIP_CHECK(c->out[1].ensure(sizeof(voe_map_cull_entry) * S, c->stream));
+  VO_HIP_CHECK(c->out[2].ensure(sizeof(voe_map_cull_stats) + 16, c->stream));
+  int32_t* d_verdict = c->out[0].as<int32_t>();
+  int32_t* d_remap = d_verdict + S;
+  if (int r = voe_map_cull_batch_dev(m, n_frames, K, c->in[0].as<float>(), (size_t)n_max, c->in[1].as<float>(), (size_t)n_max, n_max,
+                                     n_rows ? c->in[3].as<int>() : nullptr, c->in[2].as<float>(), params, verdict_out ? d_verdict : nullptr,
+                                     remap_out ? d_remap : nullptr, entry_out ? c->out[1].as<voe_map_cull_entry>() : nullptr,
+                                     c->out[2].as<voe_map_cull_stats>()))
+    return r;
+  VO_HIP_CHECK(hipMemcpyAsync(stats_out, c->out[2].p, sizeof(voe_map_cull_stats), hipMemcpyDeviceToHost, c->stream));
+  if (size > 0) {
+    if (verdict_out) VO_HIP_CHECK(hipMemcpyAsync(verdict_out, d_verdict, sizeof(int32_t) * (size_t)size, hipMemcpyDeviceToHost, c->stream));
+    if (remap_out) VO_HIP_CHECK(hipMemcpyAsync(remap_out, d_remap, sizeof(int32_t) * (size_t)size, hipMemcpyDeviceToHost, c->stream));
+    if (entry_out) VO_HIP_CHECK(hipMemcpyAsync(entry_out, c->out[1].p, sizeof(voe_map_cull_entry) * (size_t)size, hipMemcpyDeviceToHost, c->stream));
+  }
+  VO_HIP_CHECK(hipStreamSynchronize(c->stream));
+  if (!m->replayable && !params->dry_run) m->size_ub = stats_out->n_kept;
   return VO_OK;
 }
 

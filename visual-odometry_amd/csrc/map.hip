@@ -196,7 +196,9 @@ __global__ __launch_bounds__(MB) void map_commit_kernel(MapArgs a) {
 }
 
 // rebuilds the table from the entries (after the arrays grew): entry j claims or joins its class's slot; the smallest j stays
-__global__ __launch_bounds__(MB) void map_rehash_kernel(MapArgs a) {
+// (guard: launch_map_rehash)
+__global__ __launch_bounds__(MB) void map_rehash_kernel(MapArgs a, const int* guard) {
+  if (guard && *guard == 0) return;
   const int M = a.hdr[0];
   const int j = blockIdx.x * MB + threadIdx.x;
   if (j >= M) return;
@@ -417,13 +419,28 @@ hipError_t launch_map_update(hipStream_t st, const MapDev& m, const float* c_xyz
   return hipGetLastError();
 }
 
-hipError_t launch_map_rehash(hipStream_t st, const MapDev& m, int size_bound) {
-  hipError_t e = hipMemsetAsync(m.table, 0xff, sizeof(unsigned long long) * (size_t)m.tcap, st);
-  if (e != hipSuccess) return e;
-  e = hipMemsetAsync(m.last, 0xff, sizeof(int) * (size_t)m.tcap, st);
-  if (e != hipSuccess || size_bound <= 0) return e;
+// the guarded form's clear of table and last: what the two memsets of the unguarded form write, where the flag is not 0
+__global__ __launch_bounds__(MB) void map_table_clear_kernel(MapArgs a, const int* guard) {
+  if (*guard == 0) return;
+  for (size_t s = (size_t)blockIdx.x * MB + threadIdx.x; s <= (size_t)a.tmask; s += (size_t)gridDim.x * MB) {
+    a.table[s] = MAP_EMPTY;
+    a.last[s] = -1;
+  }
+}
+
+hipError_t launch_map_rehash(hipStream_t st, const MapDev& m, int size_bound, const int* d_guard) {
   const MapArgs a = map_args(m, nullptr, nullptr, 0, nullptr, nullptr, nullptr);
-  hipLaunchKernelGGL(map_rehash_kernel, dim3((size_bound + MB - 1) / MB), dim3(MB), 0, st, a);
+  if (d_guard) {
+    const unsigned want = (m.tcap + MB - 1) / MB;
+    hipLaunchKernelGGL(map_table_clear_kernel, dim3(want < 4096u ? want : 4096u), dim3(MB), 0, st, a, d_guard);
+  } else {
+    hipError_t e = hipMemsetAsync(m.table, 0xff, sizeof(unsigned long long) * (size_t)m.tcap, st);
+    if (e != hipSuccess) return e;
+    e = hipMemsetAsync(m.last, 0xff, sizeof(int) * (size_t)m.tcap, st);
+    if (e != hipSuccess) return e;
+  }
+  if (size_bound <= 0) return hipGetLastError();
+  hipLaunchKernelGGL(map_rehash_kernel, dim3((size_bound + MB - 1) / MB), dim3(MB), 0, st, a, d_guard);
   return hipGetLastError();
 }
 

@@ -380,7 +380,9 @@ size_t map_scratch_ints(int n_max);
 // PointCloudVector<3>::update(T * cloud) (PointCloud.h:52-66,77-82); d_T16 / d_n may be null; d_scratch: map_scratch_ints(n_max) ints
 hipError_t launch_map_update(hipStream_t st, const MapDev& m, const float* d_xyz, const float* d_app, int n_max, const int* d_n,
                              const float* d_T16, int* d_scratch);
-hipError_t launch_map_rehash(hipStream_t st, const MapDev& m, int size_bound);      // empties the table, enters entries 0 .. size-1
+// empties the table, enters entries 0 .. size-1.  d_guard (or null): a device flag read when the launches RUN -- where it is 0
+// the same launches return at once and the table keeps every byte (voe_map_cull: a fixed sequence of launches, whatever the data)
+hipError_t launch_map_rehash(hipStream_t st, const MapDev& m, int size_bound, const int* d_guard = nullptr);
 hipError_t launch_map_history(hipStream_t st, float* d_hist16, const float* d_X16, int reset);
 hipError_t launch_map_transform(hipStream_t st, const MapDev& m, const Pose& T, int size_bound);
 // The read-only lookup (vo_map_lookup*): frame f's rows at q_app + f * q_stride floats, d_n[f] (or n_max) of them live.
@@ -544,6 +546,36 @@ struct MapBundleArgs {
 };
 // after the lookup has filled l.ent: the lists, then the fixed sequence of 3 (n_cg + 2) launches per round
 hipError_t launch_map_bundle(hipStream_t st, const MapBundleArgs& a, int n_cu);
+
+// ---- culling of landmarks (map_cull.hip, voe_map_cull*; include/vo_map_cull.h holds the rules) ----------------------------
+struct MapCullWs {
+  int32_t *verdict, *remap;             // [bound] (the caller's arrays take their places when given)
+  int* rank;                            // [bound] the keep flag, then the survivor's rank inside its block of 256 entries (-1: dropped)
+  int* blk;                             // [ceil(bound / 256)] survivors per block -> block offsets
+  float *stage_pts, *stage_app;         // [bound][3], [bound][10] the survivors, compacted, before they are copied back
+  int* ctl;                             // [0] size before [1] survivors [2] 1: the map changes (something dropped and no dry run)
+  size_t bytes;
+};
+MapCullWs map_cull_layout(void* base, int bound);
+struct MapCullArgs {
+  MapRefineWs l;                        // the lookup's entries and the ordered lists (map_refine_layout)
+  MapCullWs w;
+  float *pts, *app; int* hdr; int cap, bound;         // the map
+  const float* uv; size_t uv_stride;
+  int n_max, n_frames;
+  const float* T16;
+  double K[9];                          // column-major
+  int min_obs, min_frames, drop_unseen, dry_run;
+  double max_mean_sq, max_sq, cos_thr;  // squared thresholds (0: off); cos_thr means something when parallax != 0
+  int parallax;
+  int32_t *verdict, *remap;             // the caller's or the workspace's
+  void* entry_out;                      // [size] voe_map_cull_entry, or null
+  void* stats;                          // voe_map_cull_stats
+};
+// after the lookup has filled l.ent: the lists, score, count, scan, scatter into the staging area, copy back, header; the caller
+// then enqueues launch_map_rehash guarded by w.ctl + 2, and launch_map_cull_stats
+hipError_t launch_map_cull(hipStream_t st, const MapCullArgs& a, int n_cu);
+hipError_t launch_map_cull_stats(hipStream_t st, const MapCullArgs& a);
 
 // ---- epipolar initialisation, device half (epi.hip) ------------------------------------------------------
 size_t epi_workspace_bytes();
