@@ -204,7 +204,11 @@ int vo_picp_get_pose_dev(vo_picp *s, float *d_T16);             /* async copy on
  * the rounds that follow repeat earlier ones and their launches return at once -- the results are the bytes of the full
  * solve.  detected_at: the launch that found the repeat, k + 1 (0: none); period: k - j; skipped: launches that returned
  * at once.  Read them once the stream has drained (vo_memcpy_d2h does).  VO_PICP_CYCLE=0 in the environment (read per
- * call) turns the detection off. */
+ * call) turns the detection off.
+ * Behind the five ints lie the 64 x 12 floats of the pose history, and behind those four ints about the tail launch, the one
+ * launch that may stand for the rounds behind round 16 of such a solve: [0] the last solve used it, [1] the real rounds that
+ * ran inside it (0 where the pose had repeated before), [2] a workgroup of it gave up waiting for the others -- the getters
+ * then fail with VO_ERR_HIP instead of returning numbers --, [3] internal.  VO_PICP_TAIL=0 keeps a launch per round. */
 int vo_picp_pose_dev_ptr(vo_picp *s, const float **d_T16);
 int vo_picp_get_stats(vo_picp *s, float *chi_inliers, float *chi_outliers, int *num_inliers); /* :44-50 */
 /* H (6x6 col-major, damping included, as _H after oneRound) and b of the last round */

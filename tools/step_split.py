@@ -45,6 +45,8 @@ def main():
     # dropped pairs: picp_tally_round_kernel<FINISH, ...>)
     is_finish = lambda n: n.startswith(("picp_round_kernel<true, true", "picp_tally_round_kernel<true"))
     is_round = lambda n: n.startswith(("picp_round_kernel<true, false", "picp_tally_round_kernel<false"))
+    # the one launch that stands for the rounds behind round M (picp_tail_kernel): between the last PRE round and the finish
+    is_tail = lambda n: n.startswith("picp_tail_kernel")
     steps, cur, prev_end = [], [], None
     for s, e, n in rows:
         cur.append((s, e, n))
@@ -77,22 +79,46 @@ def main():
         fixed_total.append(st[first_round][0] - pe)
     rr, rk, rg = [], [], []
     fin_gap, fin_dur, total = [], [], []
+    tail_gap, tail_dur = [], []
+    n_rounds = sum(1 for n in common if is_round(n))
+    per_round = [([], []) for _ in range(n_rounds)]      # per round launch of the step: kernel times, start to next start
     for pe, st in steps:
         rounds = [x for x in st if is_round(x[2])]
+        behind = [x for x in st if is_round(x[2]) or is_tail(x[2]) or x is st[-1]]
+        for k, (a, b) in enumerate(zip(rounds, behind[1:])):
+            per_round[k][0].append(a[1] - a[0])
+            per_round[k][1].append(b[0] - a[0])
         for a, b in zip(rounds, rounds[1:]):
             rr.append(b[0] - a[0])
             rg.append(b[0] - a[1])
         rk += [e - s for s, e, _ in rounds]
+        for k, x in enumerate(st):
+            if is_tail(x[2]):
+                tail_gap.append(x[0] - st[k - 1][1])
+                tail_dur.append(x[1] - x[0])
         fin_gap.append(st[-1][0] - st[-2][1])
         fin_dur.append(st[-1][1] - st[-1][0])
         total.append(st[-1][1] - pe)
-    n_rounds = sum(1 for n in common if is_round(n))
+    # A round launch that finds its pose already seen returns at once: told from a real one by its kernel time (below half of
+    # round 2's, the first plain round).  Their span: the sum of their start-to-next-start times.
+    ktime = [med(k) for k, _ in per_round]
+    span = [med(s) for _, s in per_round]
+    real_time = ktime[1] if len(ktime) > 1 else float("nan")
+    returning = [k for k in range(n_rounds) if ktime[k] < 0.5 * real_time]
+    res.update({"round_launches": [{"round": k + 1, "kernel_time": ktime[k], "start_to_next_start": span[k]} for k in range(n_rounds)],
+                "returning_launches": len(returning), "returning_span": sum(span[k] for k in returning),
+                "real_launches": n_rounds - len(returning), "real_span": sum(span[k] for k in range(n_rounds) if k not in returning),
+                "tail_launches_per_step": sum(1 for n in common if is_tail(n)), "tail_gap": med(tail_gap), "tail_kernel_time": med(tail_dur)})
     res.update({"fixed_total": med(fixed_total), "pre_rounds_per_step": n_rounds, "round_start_to_start": med(rr),
                 "round_kernel_time": med(rk), "round_gap": med(rg), "finish_gap": med(fin_gap), "finish_kernel_time": med(fin_dur),
                 "step_total": med(total)})
     print("  fixed part in all          %7.2f us" % res["fixed_total"])
     print("PRE rounds per step: %d ; start to start %.2f us (kernel %.2f + gap %.2f)"
           % (n_rounds, res["round_start_to_start"], res["round_kernel_time"], res["round_gap"]))
+    print("of them returning at once: %d, span %.2f us; real: %d, span %.2f us"
+          % (res["returning_launches"], res["returning_span"], res["real_launches"], res["real_span"]))
+    if res["tail_launches_per_step"]:
+        print("tail launch: gap %.2f us, kernel %.2f us" % (res["tail_gap"], res["tail_kernel_time"]))
     print("finishing launch: gap %.2f us, kernel %.2f us" % (res["finish_gap"], res["finish_kernel_time"]))
     print("step, finish end to finish end: %.2f us" % res["step_total"])
     if out_json:

@@ -284,6 +284,17 @@ class PICPSolver:
         self.ctx.d2h(blk, p.value + 16 * 4)
         return int(blk[2]), int(blk[3]), int(blk[4])
 
+    def tailInfo(self):
+        """(the last solve ran its rounds behind round M as one tail launch, real rounds that ran inside that launch, a
+        workgroup of it gave up at the grid barrier): three of the four ints behind the 64 x 12 floats of pose history that
+        follow the cycle report (csrc/vo_internal.h, PicpTail); synchronises.  Reads the words in place: an aborted solve
+        makes the getters fail, not this accessor."""
+        p = C.c_void_p()
+        _chk(self.lib.vo_picp_pose_dev_ptr(self.h, C.byref(p)))
+        blk = np.zeros(4, np.int32)
+        self.ctx.d2h(blk, p.value + 16 * 4 + 5 * 4 + 64 * 12 * 4)
+        return bool(blk[0]), int(blk[1]), bool(blk[2])
+
     def setCorrespondences(self, correspondences):
         p = _i32pairs(correspondences)
         _chk(self.lib.vo_picp_set_correspondences(self.h, _ptr(p), C.c_int(len(p))))

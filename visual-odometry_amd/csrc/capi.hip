@@ -164,6 +164,9 @@ struct vo_graph {
   hipGraphExec_t exec = nullptr;
 };
 
+// a handle whose tail launches run real rounds goes back to a launch per round and tries the form again with one solve in
+// PICP_TAIL_PROBE_EVERY, then in twice as many after every probe that ran real rounds again, up to PICP_TAIL_PROBE_MAX
+constexpr int PICP_TAIL_PROBE_EVERY = 1024, PICP_TAIL_PROBE_MAX = 65536;
 struct vo_picp {
   vo_ctx* ctx = nullptr;
   unsigned long long ctx_id = 0;
@@ -218,6 +221,13 @@ struct vo_picp {
   unsigned long long spec_rounds = 0, spec_redone = 0;   // one_round calls enqueued before their comparison / found different
   int use_graph = 1;
   int graph_failures = 0;     // captures that failed (the handle then stays on plain launches): vo_picp_graph_info
+  // Which solves take the tail form (picp_tail_policy).  tail_report: two ints in pinned host memory that the tail launches of
+  // this handle write -- how many of them took the skip path straight, how many ran real rounds inside the launch.
+  int* tail_report = nullptr;
+  int tail_seen[2] = {0, 0};  // the report as last looked at
+  bool tail_on = false;       // eligible solves take the form
+  bool tail_probe = false;    // one solve in the form is in flight to find out; launches per round until it reports
+  int tail_period = PICP_TAIL_PROBE_EVERY, tail_since = PICP_TAIL_PROBE_EVERY - 1;   // off: every tail_period-th eligible solve probes
   std::map<std::tuple<int, int, const void*, size_t, const void*, int>, hipGraphExec_t> graphs;
 };
 
@@ -540,9 +550,17 @@ int vo_picp_create(vo_ctx* c, vo_picp** out) {
   hipError_t e = hipMalloc(reinterpret_cast<void**>(&s->d_params), sizeof(PicpParams));
   if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&s->d_state), sizeof(PicpState));
   if (e == hipSuccess) e = hipMemsetAsync(s->d_state, 0, sizeof(PicpState), c->stream);
+  // (without the report the handle keeps a launch per round: picp_tail_policy)
+  if (e == hipSuccess && hipHostMalloc(reinterpret_cast<void**>(&s->tail_report), 2 * sizeof(int), hipHostMallocDefault) == hipSuccess) {
+    s->tail_report[0] = s->tail_report[1] = 0;
+  } else if (e == hipSuccess) {
+    (void)hipGetLastError();
+    s->tail_report = nullptr;
+  }
   if (e != hipSuccess) {
     if (s->d_params) (void)hipFree(s->d_params);
     if (s->d_state) (void)hipFree(s->d_state);
+    if (s->tail_report) (void)hipHostFree(s->tail_report);
     delete s;
     return fail(VO_ERR_HIP, "vo_picp_create: %s", hipGetErrorString(e));
   }
@@ -568,6 +586,7 @@ int vo_picp_destroy(vo_picp* s) {
   s->packed.release(); s->partials.release();
   if (s->d_params) (void)hipFree(s->d_params);
   if (s->d_state) (void)hipFree(s->d_state);
+  if (s->tail_report) (void)hipHostFree(s->tail_report);
   delete s;
   return VO_OK;
 }
@@ -654,6 +673,47 @@ static bool picp_gather_enabled() { const char* e = getenv("VO_PICP_GATHER"); re
 // VO_PICP_CYCLE=0 in the environment turns the cycle detection of a launch-per-round solve off (read per call, part of the
 // graph's key): no detector workgroup, every round runs.  Diagnostic runs of the round itself (stamps, step splits) set it.
 static bool picp_cycle_enabled() { const char* e = getenv("VO_PICP_CYCLE"); return !(e && e[0] == '0'); }
+
+// Which solves take the tail form (picp.hip, picp_tail_kernel).  The form wins 1.7 us for every launch that would only return
+// -- half of the 50-round headline step -- where the pose repeats within the first PICP_TAIL_FROM rounds, and loses ~10 us for
+// every round that has to run inside the launch where it does not (the sequence leg's frames never repeat in 100 rounds:
+// DESIGN.md section 4.1).  Which of the two a caller's problems are is only known afterwards, and the host must not wait for
+// the device to find out.  So every tail launch reports how it went into two host-visible counters (PicpTailTally), and an
+// enqueue looks at whatever has arrived by then:
+//   * a handle starts with ONE solve in the form, a probe; until it has reported, solves keep a launch per round;
+//   * a probe that took the skip path switches the form on; a tail launch that ran real rounds switches it off;
+//   * while off, one eligible solve in tail_period is a probe; the period doubles with every probe that ran real rounds.
+// A caller that runs far ahead of the device therefore pays for at most one slow solve per probe, never for a queue of them.
+// Results are the same bytes in either form, so the choice is invisible but for the time.  An explicit VO_PICP_TAIL=1 or
+// VO_PICP_TAIL_FROM takes the form for every eligible solve (tests, measurements); solves captured into a caller's graph keep
+// a launch per round (the choice would be frozen into the graph).
+static int picp_tail_policy(vo_picp* s, int n_iters, bool cycle) {
+  bool forced = false;
+  const int m = picp_tail_from(s->grid, n_iters, cycle, s->ctx->n_cu, &forced);
+  if (m == 0 || forced) return m;
+  if (s->ctx->capturing || !s->tail_report) return 0;
+  int now[2];
+  for (int k = 0; k < 2; ++k) now[k] = __atomic_load_n(&s->tail_report[k], __ATOMIC_RELAXED);
+  const bool straight = now[0] != s->tail_seen[0], looped = now[1] != s->tail_seen[1];
+  s->tail_seen[0] = now[0];
+  s->tail_seen[1] = now[1];
+  if (looped) {
+    s->tail_period = s->tail_probe ? (s->tail_period < PICP_TAIL_PROBE_MAX ? 2 * s->tail_period : PICP_TAIL_PROBE_MAX) : PICP_TAIL_PROBE_EVERY;
+    s->tail_on = false;
+    s->tail_probe = false;
+    s->tail_since = 0;
+  } else if (straight && s->tail_probe) {
+    s->tail_on = true;
+    s->tail_probe = false;
+    s->tail_period = PICP_TAIL_PROBE_EVERY;
+  }
+  if (s->tail_on) return m;
+  if (s->tail_probe) return 0;
+  if (++s->tail_since < s->tail_period) return 0;
+  s->tail_since = 0;
+  s->tail_probe = true;
+  return m;
+}
 
 // n_iters / lazy: what the caller hands to picp_enqueue next (0: nothing that could take the gather along)
 static int picp_prepare(vo_picp* s, const int32_t* d_pairs, int n_pairs, const int* d_n, int keep_outliers, int n_iters = 0,
@@ -786,20 +846,22 @@ static int picp_enqueue(vo_picp* s, int n_iters, bool lazy = false) {
     VO_HIP_CHECK(launch_picp_exact(c->stream, s->d_params, s->d_state, pk, n_iters));
     return VO_OK;
   }
+  // rounds behind this index share one launch (0: every round has its own); part of the graph's key
+  const int tail_from = picp_tail_policy(s, n_iters, cycle);
   if (s->use_graph && n_iters >= 2 && !c->capturing) {
     // Where the rounds are launches of their own, round 0 -- whose arguments (what it gathers from, or that it does not) are
     // the caller's and change from call to call -- is a plain launch, and the graph holds what follows it: one graph per
     // solve shape, whatever it is replayed behind.  (Round 0 as the graph's first node measured the same: DESIGN.md section 8.)
     const int part = picp_rounds_chain(s->grid) ? PICP_AFTER_ROUND0 : PICP_WHOLE;
     auto key = std::make_tuple(n_iters, s->grid, (const void*)pk.base, pk.cap, (const void*)partials,
-                               (pinhole ? 1 : 0) | (keep ? 2 : 0) | (cycle ? 4 : 0));
+                               (pinhole ? 1 : 0) | (keep ? 2 : 0) | (cycle ? 4 : 0) | (tail_from << 3));
     auto it = s->graphs.find(key);
     if (it == s->graphs.end()) {
       hipGraph_t graph = nullptr;
       hipGraphExec_t exec = nullptr;
       hipError_t e = hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal);
       if (e == hipSuccess) {
-        hipError_t el = launch_picp_rounds(c->stream, s->d_params, s->d_state, pk, partials, s->grid, n_iters, pinhole, keep, gather, part, cycle);
+        hipError_t el = launch_picp_rounds(c->stream, s->d_params, s->d_state, pk, partials, s->grid, n_iters, pinhole, keep, gather, part, cycle, tail_from, s->tail_report);
         e = hipStreamEndCapture(c->stream, &graph);
         if (e == hipSuccess && el != hipSuccess) e = el;
       }
@@ -827,7 +889,7 @@ static int picp_enqueue(vo_picp* s, int n_iters, bool lazy = false) {
     if (s->use_graph && it != s->graphs.end()) {
       hipError_t e = hipSuccess;
       if (part == PICP_AFTER_ROUND0)
-        e = launch_picp_rounds(c->stream, s->d_params, s->d_state, pk, partials, s->grid, n_iters, pinhole, keep, gather, PICP_ROUND0, cycle);
+        e = launch_picp_rounds(c->stream, s->d_params, s->d_state, pk, partials, s->grid, n_iters, pinhole, keep, gather, PICP_ROUND0, cycle, tail_from, s->tail_report);
       if (e == hipSuccess) e = hipGraphLaunch(it->second, c->stream);
       if (e != hipSuccess && gather.on) s->packed_valid = false;
       VO_HIP_CHECK(e);
@@ -836,7 +898,7 @@ static int picp_enqueue(vo_picp* s, int n_iters, bool lazy = false) {
   }
   {
     const hipError_t e = launch_picp_rounds(c->stream, s->d_params, s->d_state, pk, partials, s->grid, n_iters, pinhole, keep, gather,
-                                            PICP_WHOLE, cycle);
+                                            PICP_WHOLE, cycle, tail_from, s->tail_report);
     if (e != hipSuccess && gather.on) s->packed_valid = false;
     VO_HIP_CHECK(e);
   }
@@ -981,9 +1043,14 @@ int vo_picp_set_exact(vo_picp* s, int on) {
 
 static int picp_read_state(vo_picp* s, PicpState* h) {
   if (int r = picp_flush(s)) return r;
-  // (the pose history of the cycle detection stays on the device: nothing on the host reads it)
-  VO_HIP_CHECK(hipMemcpyAsync(h, s->d_state, offsetof(PicpState, hist), hipMemcpyDeviceToHost, s->ctx->stream));
+  // one copy up to the end of the tail launch's words (nothing on the host reads the 3 KB of pose history in between: they
+  // ride along, cheaper than a second copy)
+  VO_HIP_CHECK(hipMemcpyAsync(h, s->d_state, offsetof(PicpState, tail) + sizeof(PicpTail), hipMemcpyDeviceToHost, s->ctx->stream));
   VO_HIP_CHECK(hipStreamSynchronize(s->ctx->stream));
+  // a workgroup of the tail launch gave up at its grid barrier (picp.hip, picp_tail_kernel): what the state holds is no result
+  if (h->tail.aborted)
+    return fail(VO_ERR_HIP, "vo_picp: the tail launch of the last solve gave up waiting at its grid barrier; the results are void "
+                            "(VO_PICP_TAIL=0 keeps a launch per round)");
   if (h->n_bad > 0)
     return fail(VO_ERR_BAD_INDEX, "vo_picp: %d correspondence(s) index outside the point arrays", h->n_bad);
   return VO_OK;

@@ -429,6 +429,8 @@ __device__ __forceinline__ void picp_round_body(const PicpParams* __restrict__ P
     // a solve starts with every round running and nothing to report (picp_cycle_detect)
     if (blockIdx.x == 0 && tid < (int)(sizeof(PicpCycle) / 4))
       reinterpret_cast<int*>(&S->cyc)[tid] = tid == (int)(offsetof(PicpCycle, skip_from) / 4) ? PICP_CYCLE_RUN : 0;
+    // ... and no tail launch has run, reported, given up or arrived at its barrier (picp_tail_kernel)
+    if (blockIdx.x == 0 && tid >= 64 && tid < 64 + (int)(sizeof(PicpTail) / 4)) reinterpret_cast<int*>(&S->tail)[tid - 64] = 0;
   }
   VO_STAMP(0);
   VO_STAMP_REAL(7);
@@ -737,6 +739,164 @@ __global__ __launch_bounds__(PICP_BLOCK) void picp_tally_round_kernel(const Picp
   picp_round_body<true, FINISH, PINHOLE, KEEP, false, false, true, !FINISH>(P, S, PackedCorr{pk_base, pk_cap}, partials, it, nb, RoundBatch{});
 }
 
+// ---- the rounds behind round M of a solve in ONE launch ---------------------------------------------------------------
+// Once a repeat has been detected the launches that follow compute nothing, and a launch that only returns still costs its
+// boundary (1.7 us of a 3.5 us round).  So only rounds 1 .. M of a solve keep a launch of their own; this kernel, one launch of
+// nb + 1 workgroups (the detector is block nb), stands for rounds first = M + 1 .. last.
+//   SKIP at the start (a repeat was found in launches 1 .. M -- every bench seed's case): what launch `last` does in that
+//     state -- pose from hist[target], workgroup 0 stores it, linearise, reduce, store the row in the slot of round `last` --
+//     and return; the detector workgroup returns at once.  No workgroup waits for another.
+//   RUN: the rounds run here, each as its launch would (rows of round it - 1 from memory, the staged 32-way sum, the tail,
+//     linearisation, reduction, row stored; the detector workgroup runs picp_cycle_detect), with a grid barrier behind each.
+//     The control word is read again behind every barrier: once it says SKIP the workgroups go on to round `last` as above.
+// Same device functions, same operands, same order of every sum as picp_round_body: the same bits.  A thread holds ONE
+// correspondence, loaded once (the host picks the form only where the grid covers the pairs and every workgroup has a CU of
+// its own: picp_tail_from).
+// The barrier: a monotonic counter (zeroed by round 0 with the rest of PicpTail); thread 0 of a workgroup, behind the
+// workgroup's barrier, releases at agent scope -- the rows and the pose are plain stores that workgroups on other XCDs read --,
+// arrives, and polls with relaxed agent-scope loads and s_sleep; behind a second workgroup barrier every thread acquires at
+// agent scope, so that the plain loads of the next round see the other XCDs' stores.  The poll is bounded by the constant
+// clock: a workgroup that has waited PICP_TAIL_WAIT_TICKS sets `aborted` and leaves, and so does every workgroup that finds
+// the word set; the host reports the solve as failed (capi.hip, picp_read_state).
+__device__ __forceinline__ bool picp_tail_barrier(PicpTail* tl, int goal, int* s_go) {
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+    __hip_atomic_fetch_add(&tl->bar, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    const unsigned long long t0 = __builtin_amdgcn_s_memrealtime();
+    int go = 1;
+    for (;;) {
+      const int seen = __hip_atomic_load(&tl->bar, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      const int gone = __hip_atomic_load(&tl->aborted, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      if (gone) { go = 0; break; }
+      if (seen >= goal) break;
+      if (__builtin_amdgcn_s_memrealtime() - t0 > PICP_TAIL_WAIT_TICKS) {
+        __hip_atomic_store(&tl->aborted, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        go = 0;
+        break;
+      }
+      __builtin_amdgcn_s_sleep(2);
+    }
+    *s_go = go;
+  }
+  __syncthreads();
+  const bool go = *s_go != 0;
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+  return go;
+}
+
+template <bool PINHOLE, bool KEEP>
+__global__ __launch_bounds__(PICP_BLOCK) void picp_tail_kernel(const PicpParams* __restrict__ P, PicpState* S, float* pk_base,
+                                                               size_t pk_cap, float* partials, int first, int nb, int last,
+                                                               int* report) {
+  __shared__ __attribute__((aligned(16))) float s_acc[PICP_SACC];
+  __shared__ __attribute__((aligned(16))) float s_stg[PICP_SSTG];
+  __shared__ float s_part[PICP_PARTS * 32];
+  __shared__ int s_go;
+  const PackedCorr pk{pk_base, pk_cap};
+  const int tid = threadIdx.x, lane = tid & 63;
+  const bool detector = (int)blockIdx.x == nb;
+  PicpTail* tl = &S->tail;
+  // the control word, as an earlier launch left it
+  int skip_from = S->cyc.skip_from, target = S->cyc.target;
+  if (detector && first >= skip_from) return;
+  const CamK cam = P->cam;
+  const float thr = P->thr, damping = P->damping;
+  const int n = P->n_corr;
+  const CamBounds cb = cam_bounds(cam);
+  const int i = blockIdx.x * PICP_BLOCK + tid;
+  const bool have = !detector && i < n;
+  float x = 0.f, y = 0.f, z = 0.f, u = 0.f, v = 0.f;
+  if (have) { x = pk.arr(0)[i]; y = pk.arr(1)[i]; z = pk.arr(2)[i]; u = pk.arr(3)[i]; v = pk.arr(4)[i]; }
+  // what the thread index decides (steps (1), (2) of picp_round_body)
+  const int nb_pad = (nb + 255) & ~255;
+  constexpr int NJ = 256 / PICP_GROUPS;
+  const size_t slot_floats = (size_t)nb_pad * PICP_PSTRIDE;
+  const float* rows_mine = partials + (size_t)(blockIdx.x % PICP_REPLICAS) * PICP_SLOTS * slot_floats;
+  const int rr = lane / 6, cc = lane - 6 * rr;
+  const int lo = rr < cc ? rr : cc, hi = rr < cc ? cc : rr;
+  const int sum_slot = lane < 36 ? (13 * lo - lo * lo) / 2 + (hi - lo) : 21 + (lane - 36);
+  const int stg_at = sum_slot * STG_STRIDE, stg_to = (tid & 7) * 4 * STG_STRIDE + (tid >> 3);
+  const bool diag = lane < 36 && rr == cc;
+  const int m3 = lane % 3, c3 = lane < 3 ? 0 : (lane < 6 ? 3 : (lane < 9 ? 6 : 9));
+  int real = 0, goal = 0;
+  for (int it = first;;) {
+    const bool from_hist = it >= skip_from;
+    if (from_hist) it = last;
+    if (detector) {
+      if (from_hist) return;
+      picp_cycle_detect(S, it, last);
+    } else {
+      Pose T;
+      if (from_hist) {
+        // the pose of round `last` has occurred before: hist[target] stands for rows, sums and tail
+        const Pose Th = load_pose12(S->hist[target & (PICP_HIST - 1)]);
+        if (tid == 0 && blockIdx.x == 0) store_pose12(S->pose[it & (PICP_SLOTS - 1)], Th);
+        T = uniform_pose(Th);
+      } else {
+        // the rows of round it - 1: thread (g = tid / 8, q = tid % 8) sums quad q of rows g + 32 j of every pass of 256 rows
+        const char* prev = reinterpret_cast<const char*>(rows_mine + (size_t)((it - 1) & (PICP_SLOTS - 1)) * slot_floats);
+        float4 psum = make_float4(0.f, 0.f, 0.f, 0.f);
+        for (int b0 = 0; b0 < nb; b0 += 256) {
+          float4 r[NJ];
+#pragma unroll
+          for (int j = 0; j < NJ; ++j)
+            r[j] = *reinterpret_cast<const float4*>(prev + (size_t)(b0 + PICP_GROUPS * j) * (PICP_PSTRIDE * 4) + (size_t)tid * 16);
+#pragma unroll
+          for (int j = 0; j < NJ; ++j) { psum.x += r[j].x; psum.y += r[j].y; psum.z += r[j].z; psum.w += r[j].w; }
+        }
+        const float* pp = S->pose[(it - 1) & (PICP_SLOTS - 1)] + c3;
+        const float pb0 = pp[0], pb1 = pp[1], pb2 = pp[2];
+        // the 32 group sums, staged transposed, and this lane's entry of the system (steps (5), (6))
+        s_stg[stg_to + 0 * STG_STRIDE] = psum.x;
+        s_stg[stg_to + 1 * STG_STRIDE] = psum.y;
+        s_stg[stg_to + 2 * STG_STRIDE] = psum.z;
+        s_stg[stg_to + 3 * STG_STRIDE] = psum.w;
+        __syncthreads();
+        float val = 0.f;
+        if (lane < 42) {
+          const float4* row = reinterpret_cast<const float4*>(s_stg + stg_at);
+          float tsum = 0.f;
+#pragma unroll
+          for (int k = 0; k < PICP_GROUPS / 4; ++k) { const float4 t4 = row[k]; tsum += t4.x; tsum += t4.y; tsum += t4.z; tsum += t4.w; }
+          if (lane < 36) val = diag ? tsum + 1.f * damping : tsum;
+          else val = -tsum;
+        }
+        const Pose Tn = picp_tail_direct(val, pb0, pb1, pb2, m3);
+        if (tid == 0 && blockIdx.x == 0) store_pose12(S->pose[it & (PICP_SLOTS - 1)], Tn);
+        T = uniform_pose(Tn);
+        ++real;
+      }
+      float acc[NACC];
+#pragma unroll
+      for (int k = 0; k < NACC; ++k) acc[k] = 0.f;
+      if (have) picp_accumulate_t<PINHOLE, KEEP>(cam, cb, T, thr, x, y, z, u, v, acc);
+      const float tot = block_reduce_quad(acc, s_acc, s_part);
+      if (tid < PICP_PSTRIDE) {
+        const float o = tid < NACC ? tot : 0.f;
+#pragma unroll
+        for (int k = 0; k < PICP_REPLICAS; ++k)
+          partials[(size_t)k * PICP_SLOTS * slot_floats + ((size_t)(it & (PICP_SLOTS - 1)) * nb_pad + blockIdx.x) * PICP_PSTRIDE + tid] = o;
+      }
+    }
+    if (it == last) break;
+    goal += nb + 1;
+    if (!picp_tail_barrier(tl, goal, &s_go)) return;
+    skip_from = __hip_atomic_load(&S->cyc.skip_from, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    target = __hip_atomic_load(&S->cyc.target, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    ++it;
+  }
+  if (blockIdx.x == 0 && tid == 0) {
+    tl->used = 1;
+    tl->rounds = real;
+    // how this launch went, for the host's choice of form for later solves (PicpTailTally; one writer per launch)
+    int* tally = real ? &S->tally.looped : &S->tally.straight;
+    const int c = *tally + 1;
+    *tally = c;
+    if (report) report[real ? 1 : 0] = c;
+  }
+}
+
 // the first round of a solve, with the gather in it when `on` (a launch per solve: its arguments beyond the preloaded ones are
 // loaded)
 template <bool PINHOLE, bool KEEP>
@@ -766,6 +926,21 @@ int picp_grid_for(int n_corr, int n_cu) {
   if (g > cap) g = cap;
   if (g > PICP_MAX_BLOCKS) g = PICP_MAX_BLOCKS;
   return g;
+}
+
+// VO_PICP_TAIL=0 keeps a launch per round; VO_PICP_TAIL_FROM sets the last round with a launch of its own (read per call)
+int picp_tail_from(int grid, int n_iters, bool cycle, int n_cu, bool* forced) {
+  if (forced) *forced = false;
+  if (!cycle) return 0;
+  if (const char* e = getenv("VO_PICP_TAIL")) { if (e[0] == '0') return 0; if (forced && e[0] == '1') *forced = true; }
+  int m = PICP_TAIL_FROM;
+  if (const char* e = getenv("VO_PICP_TAIL_FROM")) { const int v = atoi(e); if (v >= 1) { m = v; if (forced) *forced = true; } }
+  if (!(n_iters - 1 > m + 1)) return 0;
+  // Residency: the loop path's barrier needs every workgroup of the launch on the chip at once.  One workgroup per CU at the
+  // most, where registers and LDS would admit four.  Such a grid lies below both caps of picp_grid_for, i.e. it has a thread
+  // per pair, which the kernel relies on.
+  if (n_cu <= 0 || grid + 1 > n_cu || grid >= PICP_MAX_BLOCKS) return 0;
+  return m;
 }
 
 hipError_t launch_picp_pack(hipStream_t st, const int32_t* d_pairs, const int* d_n, int n_max,
@@ -864,7 +1039,7 @@ static bool picp_small_enabled() {
 
 template <bool PINHOLE, bool KEEP>
 static void launch_rounds_t(hipStream_t st, PicpParams* d_params, PicpState* d_state, PackedCorr pk,
-                            float* d_partials, int grid, int n_iters, const PicpGather& g, int part, bool cycle) {
+                            float* d_partials, int grid, int n_iters, const PicpGather& g, int part, bool cycle, int tail_from, int* tail_report) {
   // With cycle detection every launch behind round 0 carries one more workgroup, the detector (picp_cycle_detect); the rounds
   // are told the last round launch's index.  Round 0 resets the control block whether or not detection is on.
   const int cyc = cycle ? 1 : 0, last = n_iters - 1;
@@ -876,9 +1051,14 @@ static void launch_rounds_t(hipStream_t st, PicpParams* d_params, PicpState* d_s
   if (n_iters > 1)
     hipLaunchKernelGGL((picp_tally_round_kernel<false, PINHOLE, KEEP>), dim3(grid + cyc), dim3(PICP_BLOCK), 0, st,
                        d_params, d_state, pk.base, pk.cap, d_partials, 1, grid);
-  for (int it = 2; it < n_iters; ++it)
+  // the tail form (picp_tail_kernel): rounds 1 .. tail_from as ever, ONE launch for rounds tail_from + 1 .. last
+  const int own = tail_from > 0 ? tail_from + 1 : n_iters;
+  for (int it = 2; it < own; ++it)
     hipLaunchKernelGGL((picp_round_kernel<true, false, PINHOLE, KEEP>), dim3(grid + cyc), dim3(PICP_BLOCK), 0, st,
                        d_params, d_state, pk.base, pk.cap, d_partials, it, grid, last, cyc);
+  if (tail_from > 0)
+    hipLaunchKernelGGL((picp_tail_kernel<PINHOLE, KEEP>), dim3(grid + 1), dim3(PICP_BLOCK), 0, st, d_params, d_state, pk.base,
+                       pk.cap, d_partials, tail_from + 1, grid, last, tail_report);
   if (n_iters == 1)
     hipLaunchKernelGGL((picp_tally_round_kernel<true, false, false>), dim3(1), dim3(PICP_BLOCK), 0, st, d_params,
                        d_state, pk.base, pk.cap, d_partials, n_iters, grid);
@@ -921,8 +1101,9 @@ hipError_t launch_picp_finish(hipStream_t st, const PicpParams* d_params, PicpSt
 
 hipError_t launch_picp_rounds(hipStream_t st, PicpParams* d_params, PicpState* d_state,
                               PackedCorr pk, float* d_partials, int grid, int n_iters, bool pinhole,
-                              bool keep_outliers, const PicpGather& gt, int part, bool cycle) {
+                              bool keep_outliers, const PicpGather& gt, int part, bool cycle, int tail_from, int* tail_report) {
   if (n_iters <= 0) return hipSuccess;
+  if (tail_from < 0 || (tail_from > 0 && (!cycle || n_iters - 1 <= tail_from + 1))) return hipErrorInvalidValue;
   if (grid == 1 && picp_small_enabled()) {      // one workgroup's worth of correspondences (picp_grid_for): all rounds in one launch
     if (part != PICP_WHOLE) return hipErrorInvalidValue;      // (never in parts: picp_rounds_chain(grid) is false)
     const dim3 g(1), b(PICP_BLOCK);
@@ -933,11 +1114,11 @@ hipError_t launch_picp_rounds(hipStream_t st, PicpParams* d_params, PicpState* d
     return hipGetLastError();
   }
   if (pinhole) {
-    if (keep_outliers) launch_rounds_t<true, true>(st, d_params, d_state, pk, d_partials, grid, n_iters, gt, part, cycle);
-    else launch_rounds_t<true, false>(st, d_params, d_state, pk, d_partials, grid, n_iters, gt, part, cycle);
+    if (keep_outliers) launch_rounds_t<true, true>(st, d_params, d_state, pk, d_partials, grid, n_iters, gt, part, cycle, tail_from, tail_report);
+    else launch_rounds_t<true, false>(st, d_params, d_state, pk, d_partials, grid, n_iters, gt, part, cycle, tail_from, tail_report);
   } else {
-    if (keep_outliers) launch_rounds_t<false, true>(st, d_params, d_state, pk, d_partials, grid, n_iters, gt, part, cycle);
-    else launch_rounds_t<false, false>(st, d_params, d_state, pk, d_partials, grid, n_iters, gt, part, cycle);
+    if (keep_outliers) launch_rounds_t<false, true>(st, d_params, d_state, pk, d_partials, grid, n_iters, gt, part, cycle, tail_from, tail_report);
+    else launch_rounds_t<false, false>(st, d_params, d_state, pk, d_partials, grid, n_iters, gt, part, cycle, tail_from, tail_report);
   }
   return hipGetLastError();
 }

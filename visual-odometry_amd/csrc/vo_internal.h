@@ -84,6 +84,31 @@ struct PicpCycle {
   int skipped;
 };
 
+// The tail launch of a launch-per-round solve (picp.hip, picp_tail_kernel): rounds PICP_TAIL_FROM + 1 .. last share ONE launch.
+// After a detected repeat that launch does the last round's work from the history and nothing else; where nothing has repeated
+// yet it runs the rounds in a loop, with a grid barrier over all its workgroups between two rounds.  VO_PICP_TAIL_FROM in the
+// environment overrides the index per call (>= 1), VO_PICP_TAIL=0 switches the form off per call.
+constexpr int PICP_TAIL_FROM = 16;
+// what a workgroup waits at most at the grid barrier before it gives the solve up (a safety net: the host only picks the form
+// where every workgroup of the launch has a CU to itself), in ticks of the constant 100 MHz clock: 100 ms
+constexpr unsigned long long PICP_TAIL_WAIT_TICKS = 10ull * 1000 * 1000;
+// The tail launch's words.  They lie BEHIND the history (the offsets of the control block and of the history are part of the
+// documented layout, include/vo_hip.h) and are zeroed with the control block by round 0 of every solve.
+struct PicpTail {
+  int used;            // reporting: the last solve went through the tail launch
+  int rounds;          // reporting: real rounds (rows summed, system solved) that ran inside it
+  int aborted;         // a workgroup waited PICP_TAIL_WAIT_TICKS at the barrier: the solve's results are void (the getters report it)
+  int bar;             // the barrier's monotonic arrival counter
+};
+// How the tail launches of a handle went, counted over its life (never reset): the launch's workgroup 0 adds one to `straight`
+// (it took the skip path) or to `looped` (real rounds ran inside it, each several times the price of a launched round) and
+// copies the new count into the handle's host-visible report, from which the host decides the form of later solves without
+// ever waiting for the device (capi.hip, picp_tail_policy).
+struct PicpTailTally {
+  int straight;
+  int looped;
+};
+
 // Solver state in device memory.
 struct PicpState {
   float pose[PICP_SLOTS][12];   // ring (slot = round % PICP_SLOTS; slot 0 also holds the finished pose): R (col-major 3x3) then t
@@ -95,6 +120,8 @@ struct PicpState {
   float T16[16];       // pose after the last solve as a column-major 4x4 (written by the finish launch)
   PicpCycle cyc;       // directly behind T16: include/vo_hip.h documents this layout at vo_picp_pose_dev_ptr
   float hist[PICP_HIST][12];    // hist[k % PICP_HIST]: the pose after round k of this solve (pose[k % PICP_SLOTS] when it was written)
+  PicpTail tail;       // directly behind the history
+  PicpTailTally tally;
 #ifdef VO_STAMPS
   // diagnostic build only (make STAMPS=1 -> libvo_hip_stamps.so, tools/stamp_rounds.py):
   // s_memtime at phase boundaries of workgroup 0, per round
@@ -136,10 +163,19 @@ struct PicpGather {
 // are launches of their own (picp_rounds_chain(grid)).
 // cycle: launches behind round 0 carry the detector workgroup and skip rounds whose pose has already occurred in this solve
 // (picp.hip, picp_cycle_detect); results are the same bytes either way.
+// tail_from: 0, or the index M of the last round with a launch of its own -- rounds M + 1 .. n_iters - 1 are then ONE launch of
+// grid + 1 workgroups that must all be resident together (picp_tail_from decides; picp.hip, picp_tail_kernel).
 constexpr int PICP_WHOLE = 0, PICP_ROUND0 = 1, PICP_AFTER_ROUND0 = 2;
 hipError_t launch_picp_rounds(hipStream_t st, PicpParams* d_params, PicpState* d_state,
                               PackedCorr pk, float* d_partials, int grid, int n_iters, bool pinhole,
-                              bool keep_outliers, const PicpGather& g = PicpGather{}, int part = PICP_WHOLE, bool cycle = false);
+                              bool keep_outliers, const PicpGather& g = PicpGather{}, int part = PICP_WHOLE, bool cycle = false,
+                              int tail_from = 0, int* tail_report = nullptr);
+// the tail form's M for a solve of n_iters rounds on `grid` workgroups (picp_grid_for), or 0 where the solve keeps a
+// launch per round: too few rounds, no cycle detection, the form switched off, or a grid that would not leave every workgroup
+// of the tail launch -- the detector included -- a CU of its own.  Reads VO_PICP_TAIL and VO_PICP_TAIL_FROM; *forced (may be
+// null) tells whether either of them asks for the form explicitly (VO_PICP_TAIL=1, or any VO_PICP_TAIL_FROM).
+// tail_report (launch_picp_rounds): two host-visible ints that take the handle's PicpTailTally counts, or null.
+int picp_tail_from(int grid, int n_iters, bool cycle, int n_cu, bool* forced = nullptr);
 
 int picp_grid_for(int n_corr, int n_cu);
 
