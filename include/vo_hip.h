@@ -208,7 +208,12 @@ int vo_picp_get_pose_dev(vo_picp *s, float *d_T16);             /* async copy on
  * Behind the five ints lie the 64 x 12 floats of the pose history, and behind those four ints about the tail launch, the one
  * launch that may stand for the rounds behind round 16 of such a solve: [0] the last solve used it, [1] the real rounds that
  * ran inside it (0 where the pose had repeated before), [2] a workgroup of it gave up waiting for the others -- the getters
- * then fail with VO_ERR_HIP instead of returning numbers --, [3] internal.  VO_PICP_TAIL=0 keeps a launch per round. */
+ * then fail with VO_ERR_HIP instead of returning numbers --, [3] internal.  VO_PICP_TAIL=0 keeps a launch per round.
+ * Behind those four ints lie two counters of the handle's tail launches and then, written by tail launches only (so they
+ * describe the last solve that had one: check [0] above first): how that launch closed the solve -- 1 from partial rows an
+ * earlier launch had left in the ring, 2 after computing the last round's rows again (VO_PICP_TAIL_RING=0 forces this), 3 at
+ * the end of its loop of real rounds -- and the M it ran with (rounds 1 .. M had launches of their own; a handle lowers M to
+ * where its solves repeat, VO_PICP_TAIL_FROM sets it per call).  Such a solve has no finishing launch. */
 int vo_picp_pose_dev_ptr(vo_picp *s, const float **d_T16);
 int vo_picp_get_stats(vo_picp *s, float *chi_inliers, float *chi_outliers, int *num_inliers); /* :44-50 */
 /* H (6x6 col-major, damping included, as _H after oneRound) and b of the last round */

@@ -3,8 +3,9 @@
 
 usage: tools/step_split.py <dir with *kernel_trace.csv> [--json out.json]
 
-A step ends with the finishing launch (picp_round_kernel<true, true, ...>).  Everything between the end of one finishing
-launch and the start of the next step's first PRE round (picp_round_kernel<true, false, ...>, or the tally instantiation
+A step ends with the finishing launch (picp_round_kernel<true, true, ...>) -- or, where the tail launch closes the solve
+(picp_tail_kernel with no finishing launch behind it), with the tail launch; "finish" below is then that launch.  Everything
+between the end of one finishing launch and the start of the next step's first PRE round (picp_round_kernel<true, false, ...>, or the tally instantiation
 of round 1) is the FIXED part of a step:
 it is listed launch by launch (gap in front of the kernel, kernel time).  The rounds are summarised start to start.  All
 figures are medians over the steps of the trace that have the most common launch sequence (the timed region).  The tracer
@@ -47,10 +48,14 @@ def main():
     is_round = lambda n: n.startswith(("picp_round_kernel<true, false", "picp_tally_round_kernel<false"))
     # the one launch that stands for the rounds behind round M (picp_tail_kernel): between the last PRE round and the finish
     is_tail = lambda n: n.startswith("picp_tail_kernel")
+    # the tail launch closes the solve where the launch behind it is not a finishing launch
+    tail_next = [rows[k + 1][2] for k in range(len(rows) - 1) if is_tail(rows[k][2])]
+    tail_closes = bool(tail_next) and sum(1 for n in tail_next if not is_finish(n)) * 2 > len(tail_next)
+    is_end = lambda n: is_tail(n) if tail_closes else is_finish(n)
     steps, cur, prev_end = [], [], None
     for s, e, n in rows:
         cur.append((s, e, n))
-        if is_finish(n):
+        if is_end(n):
             if prev_end is not None:
                 steps.append((prev_end, cur))
             prev_end, cur = e, []
@@ -59,7 +64,8 @@ def main():
     steps = [st for st in steps if sig(st) == common]
     med = lambda xs: statistics.median(xs) / 1e3 if xs else float("nan")
     first_round = next(i for i, n in enumerate(common) if is_round(n))
-    res = {"steps_used": len(steps), "launches_per_step": len(common), "fixed": [], "unit": "us"}
+    res = {"steps_used": len(steps), "launches_per_step": len(common), "tail_launch_closes_the_step": tail_closes,
+           "launch_sequence": list(common), "fixed": [], "unit": "us"}
     print("%d steps of %d launches each" % (len(steps), len(common)))
     print("fixed part (end of the finishing launch -> start of the first PRE round):")
     fixed_total = []

@@ -221,10 +221,13 @@ struct vo_picp {
   unsigned long long spec_rounds = 0, spec_redone = 0;   // one_round calls enqueued before their comparison / found different
   int use_graph = 1;
   int graph_failures = 0;     // captures that failed (the handle then stays on plain launches): vo_picp_graph_info
-  // Which solves take the tail form (picp_tail_policy).  tail_report: two ints in pinned host memory that the tail launches of
-  // this handle write -- how many of them took the skip path straight, how many ran real rounds inside the launch.
+  // Which solves take the tail form (picp_tail_policy).  tail_report: PICP_TAIL_REPORT_WORDS ints in pinned host memory that
+  // the tail launches of this handle write -- how many of them took the skip path straight, how many ran real rounds inside the
+  // launch, the run of skip-path launches with the latest round one of them found its repeat in, the last in-launch round.
   int* tail_report = nullptr;
   int tail_seen[2] = {0, 0};  // the report as last looked at
+  int tail_m = PICP_TAIL_FROM;   // the M of the handle's solves in the form: lowered to where its solves repeat, never for a probe
+  unsigned long long solves = 0; // solves enqueued (VO_PICP_TAIL_LOG's line says at which of them a graph was captured)
   bool tail_on = false;       // eligible solves take the form
   bool tail_probe = false;    // one solve in the form is in flight to find out; launches per round until it reports
   int tail_period = PICP_TAIL_PROBE_EVERY, tail_since = PICP_TAIL_PROBE_EVERY - 1;   // off: every tail_period-th eligible solve probes
@@ -551,8 +554,8 @@ int vo_picp_create(vo_ctx* c, vo_picp** out) {
   if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&s->d_state), sizeof(PicpState));
   if (e == hipSuccess) e = hipMemsetAsync(s->d_state, 0, sizeof(PicpState), c->stream);
   // (without the report the handle keeps a launch per round: picp_tail_policy)
-  if (e == hipSuccess && hipHostMalloc(reinterpret_cast<void**>(&s->tail_report), 2 * sizeof(int), hipHostMallocDefault) == hipSuccess) {
-    s->tail_report[0] = s->tail_report[1] = 0;
+  if (e == hipSuccess && hipHostMalloc(reinterpret_cast<void**>(&s->tail_report), PICP_TAIL_REPORT_WORDS * sizeof(int), hipHostMallocDefault) == hipSuccess) {
+    for (int k = 0; k < PICP_TAIL_REPORT_WORDS; ++k) s->tail_report[k] = 0;
   } else if (e == hipSuccess) {
     (void)hipGetLastError();
     s->tail_report = nullptr;
@@ -687,28 +690,58 @@ static bool picp_cycle_enabled() { const char* e = getenv("VO_PICP_CYCLE"); retu
 // Results are the same bytes in either form, so the choice is invisible but for the time.  An explicit VO_PICP_TAIL=1 or
 // VO_PICP_TAIL_FROM takes the form for every eligible solve (tests, measurements); solves captured into a caller's graph keep
 // a launch per round (the choice would be frozen into the graph).
+//
+// Where the tail launch starts.  Every launch between the one that found the repeat and M is a bare kernel boundary (1.72 us),
+// so a handle whose solves keep repeating early is better off with a lower M.  The tail launches report the run of consecutive
+// skip-path launches and the largest detected_at among them (one word: never a torn pair); once the run is at least
+// PICP_TAIL_LEARN the handle's M is min(PICP_TAIL_FROM, largest detected_at + 1).  The margin of one round: a solve that
+// repeats one round later than any of the last eight still finds its repeat in a launch of its own and takes the skip path.
+// A miss costs ~10 us per round run in the launch, a hit saves 1.72 us per spared launch -- one missed round eats the gain of
+// six spared launches, hence eight witnesses and the margin rather than the latest solve's value.  A launch at a lowered M that
+// ran real rounds puts M back to PICP_TAIL_FROM and the device starts the run again; the form goes off only where the last
+// in-launch round lay beyond PICP_TAIL_FROM, i.e. where a tail at the default M would have looped as well.  M is never
+// lowered for a probe, and eligibility is judged with the M chosen.  Graphs are keyed by M; none of this waits for the device.
 static int picp_tail_policy(vo_picp* s, int n_iters, bool cycle) {
   bool forced = false;
   const int m = picp_tail_from(s->grid, n_iters, cycle, s->ctx->n_cu, &forced);
-  if (m == 0 || forced) return m;
-  if (s->ctx->capturing || !s->tail_report) return 0;
+  if (forced) return m;
+  // (not eligible at the default M and the form not on: no M this handle may choose would make it eligible -- nothing to look at)
+  if (m == 0 && !s->tail_on) return 0;
+  if (!cycle || s->ctx->capturing || !s->tail_report) return 0;
+  if (const char* e = getenv("VO_PICP_TAIL")) if (e[0] == '0') return 0;
+  // ([1] before [3] before [2]: behind a launch that ran real rounds the device stores them the other way round)
   int now[2];
-  for (int k = 0; k < 2; ++k) now[k] = __atomic_load_n(&s->tail_report[k], __ATOMIC_RELAXED);
+  now[1] = __atomic_load_n(&s->tail_report[1], __ATOMIC_ACQUIRE);
+  const int last_round_word = __atomic_load_n(&s->tail_report[3], __ATOMIC_ACQUIRE);
+  const int run_word = __atomic_load_n(&s->tail_report[2], __ATOMIC_ACQUIRE);
+  now[0] = __atomic_load_n(&s->tail_report[0], __ATOMIC_RELAXED);
   const bool straight = now[0] != s->tail_seen[0], looped = now[1] != s->tail_seen[1];
   s->tail_seen[0] = now[0];
   s->tail_seen[1] = now[1];
-  if (looped) {
+  // the last round the latest looping launch ran; unknown (the tag is another launch's) counts as beyond the default M
+  const bool tagged = ((last_round_word >> 16) & 0xffff) == (now[1] & 0xffff);
+  const int last_round = tagged ? (last_round_word & 0xffff) : 0xffff;
+  if (looped && s->tail_on && last_round <= PICP_TAIL_FROM) {
+    s->tail_m = PICP_TAIL_FROM;         // a lowered M missed a repeat the default M would have caught: the form stays on
+  } else if (looped) {
     s->tail_period = s->tail_probe ? (s->tail_period < PICP_TAIL_PROBE_MAX ? 2 * s->tail_period : PICP_TAIL_PROBE_MAX) : PICP_TAIL_PROBE_EVERY;
     s->tail_on = false;
     s->tail_probe = false;
     s->tail_since = 0;
+    s->tail_m = PICP_TAIL_FROM;
   } else if (straight && s->tail_probe) {
     s->tail_on = true;
     s->tail_probe = false;
     s->tail_period = PICP_TAIL_PROBE_EVERY;
   }
-  if (s->tail_on) return m;
-  if (s->tail_probe) return 0;
+  if (s->tail_on) {
+    if (!looped) {
+      const int run = (run_word >> 16) & 0xffff, det = run_word & 0xffff;
+      if (run >= PICP_TAIL_LEARN && det >= 1) s->tail_m = det + 1 < PICP_TAIL_FROM ? det + 1 : PICP_TAIL_FROM;
+    }
+    return picp_tail_from(s->grid, n_iters, cycle, s->ctx->n_cu, nullptr, s->tail_m);
+  }
+  if (s->tail_probe || m == 0) return 0;
   if (++s->tail_since < s->tail_period) return 0;
   s->tail_since = 0;
   s->tail_probe = true;
@@ -848,20 +881,23 @@ static int picp_enqueue(vo_picp* s, int n_iters, bool lazy = false) {
   }
   // rounds behind this index share one launch (0: every round has its own); part of the graph's key
   const int tail_from = picp_tail_policy(s, n_iters, cycle);
+  // (VO_PICP_TAIL_RING=0, read per call: the tail launch recomputes the last round's rows where the ring holds them)
+  const bool tail_ring = tail_from == 0 || picp_tail_ring_enabled();
+  ++s->solves;
   if (s->use_graph && n_iters >= 2 && !c->capturing) {
     // Where the rounds are launches of their own, round 0 -- whose arguments (what it gathers from, or that it does not) are
     // the caller's and change from call to call -- is a plain launch, and the graph holds what follows it: one graph per
     // solve shape, whatever it is replayed behind.  (Round 0 as the graph's first node measured the same: DESIGN.md section 8.)
     const int part = picp_rounds_chain(s->grid) ? PICP_AFTER_ROUND0 : PICP_WHOLE;
     auto key = std::make_tuple(n_iters, s->grid, (const void*)pk.base, pk.cap, (const void*)partials,
-                               (pinhole ? 1 : 0) | (keep ? 2 : 0) | (cycle ? 4 : 0) | (tail_from << 3));
+                               (pinhole ? 1 : 0) | (keep ? 2 : 0) | (cycle ? 4 : 0) | (tail_ring ? 0 : 8) | (tail_from << 4));
     auto it = s->graphs.find(key);
     if (it == s->graphs.end()) {
       hipGraph_t graph = nullptr;
       hipGraphExec_t exec = nullptr;
       hipError_t e = hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal);
       if (e == hipSuccess) {
-        hipError_t el = launch_picp_rounds(c->stream, s->d_params, s->d_state, pk, partials, s->grid, n_iters, pinhole, keep, gather, part, cycle, tail_from, s->tail_report);
+        hipError_t el = launch_picp_rounds(c->stream, s->d_params, s->d_state, pk, partials, s->grid, n_iters, pinhole, keep, gather, part, cycle, tail_from, s->tail_report, tail_ring);
         e = hipStreamEndCapture(c->stream, &graph);
         if (e == hipSuccess && el != hipSuccess) e = el;
       }
@@ -884,12 +920,16 @@ static int picp_enqueue(vo_picp* s, int n_iters, bool lazy = false) {
           s->chain_wanted.clear();
         }
         it = s->graphs.emplace(key, exec).first;
+        // VO_PICP_TAIL_LOG=1: which solve of the handle paid for a capture, and of which form (stderr; a measurement checks
+        // with it that the graph of a learned M is captured inside its warm-up)
+        if (const char* lg = getenv("VO_PICP_TAIL_LOG")) if (lg[0] == '1')
+          fprintf(stderr, "vo_picp: graph of %d rounds, tail_from %d, captured at solve %llu of the handle\n", n_iters, tail_from, s->solves);
       }
     }
     if (s->use_graph && it != s->graphs.end()) {
       hipError_t e = hipSuccess;
       if (part == PICP_AFTER_ROUND0)
-        e = launch_picp_rounds(c->stream, s->d_params, s->d_state, pk, partials, s->grid, n_iters, pinhole, keep, gather, PICP_ROUND0, cycle, tail_from, s->tail_report);
+        e = launch_picp_rounds(c->stream, s->d_params, s->d_state, pk, partials, s->grid, n_iters, pinhole, keep, gather, PICP_ROUND0, cycle, tail_from, s->tail_report, tail_ring);
       if (e == hipSuccess) e = hipGraphLaunch(it->second, c->stream);
       if (e != hipSuccess && gather.on) s->packed_valid = false;
       VO_HIP_CHECK(e);
@@ -898,7 +938,7 @@ static int picp_enqueue(vo_picp* s, int n_iters, bool lazy = false) {
   }
   {
     const hipError_t e = launch_picp_rounds(c->stream, s->d_params, s->d_state, pk, partials, s->grid, n_iters, pinhole, keep, gather,
-                                            PICP_WHOLE, cycle, tail_from, s->tail_report);
+                                            PICP_WHOLE, cycle, tail_from, s->tail_report, tail_ring);
     if (e != hipSuccess && gather.on) s->packed_valid = false;
     VO_HIP_CHECK(e);
   }

@@ -743,9 +743,13 @@ __global__ __launch_bounds__(PICP_BLOCK) void picp_tally_round_kernel(const Picp
 // Once a repeat has been detected the launches that follow compute nothing, and a launch that only returns still costs its
 // boundary (1.7 us of a 3.5 us round).  So only rounds 1 .. M of a solve keep a launch of their own; this kernel, one launch of
 // nb + 1 workgroups (the detector is block nb), stands for rounds first = M + 1 .. last.
-//   SKIP at the start (a repeat was found in launches 1 .. M -- every bench seed's case): what launch `last` does in that
-//     state -- pose from hist[target], workgroup 0 stores it, linearise, reduce, store the row in the slot of round `last` --
-//     and return; the detector workgroup returns at once.  No workgroup waits for another.
+// and then CLOSES the solve in its workgroup 0 (the finishing launch's sums, solve and stores: PicpTailClose, vo_internal.h).
+//   SKIP at the start (a repeat was found in launches 1 .. M -- every bench seed's case): the rows of round `last` are the
+//     rows launch `target` stored (same pose hist[target], same pairs, same code, same order).  Where they still lie in the ring
+//     workgroup 0 stores hist[target] as the pose of round `last` and closes from that slot; every other workgroup returns
+//     behind the control word.  No workgroup waits for another.  Where the slot has been overwritten: what launch `last`
+//     does in that state -- pose from hist[target], linearise, reduce, store the row in the slot of round `last` --, then
+//     every workgroup arrives on the barrier's counter and workgroup 0, having seen them all, closes from that slot.
 //   RUN: the rounds run here, each as its launch would (rows of round it - 1 from memory, the staged 32-way sum, the tail,
 //     linearisation, reduction, row stored; the detector workgroup runs picp_cycle_detect), with a grid barrier behind each.
 //     The control word is read again behind every barrier: once it says SKIP the workgroups go on to round `last` as above.
@@ -785,27 +789,66 @@ __device__ __forceinline__ bool picp_tail_barrier(PicpTail* tl, int goal, int* s
   return go;
 }
 
+// The closing's one-sided wait on the same counter, with the same fences and the same bound.  Every row workgroup -- its row of
+// round `last` stored -- releases and arrives; all but workgroup 0 then leave, workgroup 0 alone waits for the `goal` arrivals
+// and acquires.  (The detector workgroup does not arrive here: it is on nobody's way.)  true in workgroup 0 once all have
+// arrived; false in every other workgroup (it leaves), and in workgroup 0 where it gave up or found `aborted` set.
+__device__ __forceinline__ bool picp_tail_arrive(PicpTail* tl, int goal, int* s_go) {
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+    __hip_atomic_fetch_add(&tl->bar, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+  if (blockIdx.x != 0) return false;
+  if (threadIdx.x == 0) {
+    const unsigned long long t0 = __builtin_amdgcn_s_memrealtime();
+    int go = 1;
+    for (;;) {
+      const int seen = __hip_atomic_load(&tl->bar, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      const int gone = __hip_atomic_load(&tl->aborted, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      if (gone) { go = 0; break; }
+      if (seen >= goal) break;
+      if (__builtin_amdgcn_s_memrealtime() - t0 > PICP_TAIL_WAIT_TICKS) {
+        __hip_atomic_store(&tl->aborted, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        go = 0;
+        break;
+      }
+      __builtin_amdgcn_s_sleep(2);
+    }
+    *s_go = go;
+  }
+  __syncthreads();
+  const bool go = *s_go != 0;
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+  return go;
+}
+
+// `ring`: 0 forces the RECOMPUTED closing where RING would do (VO_PICP_TAIL_RING=0)
 template <bool PINHOLE, bool KEEP>
 __global__ __launch_bounds__(PICP_BLOCK) void picp_tail_kernel(const PicpParams* __restrict__ P, PicpState* S, float* pk_base,
                                                                size_t pk_cap, float* partials, int first, int nb, int last,
-                                                               int* report) {
+                                                               int* report, int ring) {
   __shared__ __attribute__((aligned(16))) float s_acc[PICP_SACC];
   __shared__ __attribute__((aligned(16))) float s_stg[PICP_SSTG];
   __shared__ float s_part[PICP_PARTS * 32];
+  __shared__ float s_stat[4];
   __shared__ int s_go;
   const PackedCorr pk{pk_base, pk_cap};
-  const int tid = threadIdx.x, lane = tid & 63;
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
   const bool detector = (int)blockIdx.x == nb;
   PicpTail* tl = &S->tail;
   // the control word, as an earlier launch left it
   int skip_from = S->cyc.skip_from, target = S->cyc.target;
   if (detector && first >= skip_from) return;
+  // SKIP and the rows of launch `target` still in the ring: workgroup 0 closes the solve from them, nobody else has work
+  const bool ring_at_start = first >= skip_from && ring != 0 && picp_tail_ring_holds(skip_from, target);
+  if (ring_at_start && blockIdx.x != 0) return;
   const CamK cam = P->cam;
   const float thr = P->thr, damping = P->damping;
   const int n = P->n_corr;
   const CamBounds cb = cam_bounds(cam);
   const int i = blockIdx.x * PICP_BLOCK + tid;
-  const bool have = !detector && i < n;
+  const bool have = !detector && !ring_at_start && i < n;
   float x = 0.f, y = 0.f, z = 0.f, u = 0.f, v = 0.f;
   if (have) { x = pk.arr(0)[i]; y = pk.arr(1)[i]; z = pk.arr(2)[i]; u = pk.arr(3)[i]; v = pk.arr(4)[i]; }
   // what the thread index decides (steps (1), (2) of picp_round_body)
@@ -820,6 +863,8 @@ __global__ __launch_bounds__(PICP_BLOCK) void picp_tail_kernel(const PicpParams*
   const bool diag = lane < 36 && rr == cc;
   const int m3 = lane % 3, c3 = lane < 3 ? 0 : (lane < 6 ? 3 : (lane < 9 ? 6 : 9));
   int real = 0, goal = 0;
+  int how = PICP_CLOSE_LOOPED, close_slot = last & (PICP_SLOTS - 1);
+  Pose Tl{};                                                // the pose of round `last`: the closing's old pose
   for (int it = first;;) {
     const bool from_hist = it >= skip_from;
     if (from_hist) it = last;
@@ -833,6 +878,16 @@ __global__ __launch_bounds__(PICP_BLOCK) void picp_tail_kernel(const PicpParams*
         const Pose Th = load_pose12(S->hist[target & (PICP_HIST - 1)]);
         if (tid == 0 && blockIdx.x == 0) store_pose12(S->pose[it & (PICP_SLOTS - 1)], Th);
         T = uniform_pose(Th);
+        Tl = T;
+        // ... and the rows launch `target` stored with that pose stand for the rows of round `last` (picp_tail_ring_holds): the
+        // same in every workgroup, the control word is read behind a kernel boundary or behind the barrier
+        if (ring != 0 && picp_tail_ring_holds(skip_from, target)) {
+          if (blockIdx.x != 0) return;
+          how = PICP_CLOSE_RING;
+          close_slot = target & (PICP_SLOTS - 1);
+          break;
+        }
+        how = PICP_CLOSE_RECOMPUTED;
       } else {
         // the rows of round it - 1: thread (g = tid / 8, q = tid % 8) sums quad q of rows g + 32 j of every pass of 256 rows
         const char* prev = reinterpret_cast<const char*>(rows_mine + (size_t)((it - 1) & (PICP_SLOTS - 1)) * slot_floats);
@@ -865,6 +920,7 @@ __global__ __launch_bounds__(PICP_BLOCK) void picp_tail_kernel(const PicpParams*
         const Pose Tn = picp_tail_direct(val, pb0, pb1, pb2, m3);
         if (tid == 0 && blockIdx.x == 0) store_pose12(S->pose[it & (PICP_SLOTS - 1)], Tn);
         T = uniform_pose(Tn);
+        Tl = T;
         ++real;
       }
       float acc[NACC];
@@ -886,14 +942,104 @@ __global__ __launch_bounds__(PICP_BLOCK) void picp_tail_kernel(const PicpParams*
     target = __hip_atomic_load(&S->cyc.target, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     ++it;
   }
-  if (blockIdx.x == 0 && tid == 0) {
-    tl->used = 1;
-    tl->rounds = real;
-    // how this launch went, for the host's choice of form for later solves (PicpTailTally; one writer per launch)
-    int* tally = real ? &S->tally.looped : &S->tally.straight;
-    const int c = *tally + 1;
-    *tally = c;
-    if (report) report[real ? 1 : 0] = c;
+  if (detector) return;
+  // ---- the closing: what the FINISH instantiation of picp_round_body does, in workgroup 0 -------------------------------
+  // RING: the rows are an earlier launch's (or lie behind a barrier of the loop): nothing to wait for.  Otherwise every row
+  // workgroup has just stored its row of round `last`: all arrive, workgroup 0 waits for the nb of them (`goal` arrivals lie
+  // behind the loop's barriers) and the others leave.  Given up: `aborted` is set and no result field is written.
+  if (how != PICP_CLOSE_RING && !picp_tail_arrive(tl, goal + nb, &s_go)) return;
+  {
+    // The launch's report (below) is one thread's, in the LAST wave: only wave 0 has work behind the staging barrier, so the
+    // report's loads go out here, beside the row loads, and its stores -- two of them cross the host link, and the kernel's
+    // end waits for them -- run beside wave 0's sums and solve instead of behind them.
+    static_assert(PICP_BLOCK >= 128, "the reporting thread is in another wave than the closing one");
+    const bool reporter = tid == PICP_BLOCK - 64;
+    int t_count = 0, t_run = 0, t_det = 0, t_d = 0;
+    if (reporter) {
+      t_count = real ? S->tally.looped : S->tally.straight;
+      t_run = S->close.run;
+      t_det = S->close.max_detected;
+      t_d = S->cyc.detected_at;
+    }
+    // rows of the slot (replica 0, as the one-workgroup finishing launch reads), same loads, same order of every sum
+    const char* prev = reinterpret_cast<const char*>(partials + (size_t)close_slot * slot_floats);
+    float4 psum = make_float4(0.f, 0.f, 0.f, 0.f);
+    for (int b0 = 0; b0 < nb; b0 += 256) {
+      float4 r[NJ];
+#pragma unroll
+      for (int j = 0; j < NJ; ++j)
+        r[j] = *reinterpret_cast<const float4*>(prev + (size_t)(b0 + PICP_GROUPS * j) * (PICP_PSTRIDE * 4) + (size_t)tid * 16);
+#pragma unroll
+      for (int j = 0; j < NJ; ++j) { psum.x += r[j].x; psum.y += r[j].y; psum.z += r[j].z; psum.w += r[j].w; }
+    }
+    // the old pose's column for this lane, from the uniform copy (the bytes pose[last % PICP_SLOTS] holds)
+    float pb0, pb1, pb2;
+    pose_lane_operands(Tl, pb0, pb1, pb2);
+    __syncthreads();                                         // (the staging area may still be read by a slower wave of the last round)
+    s_stg[stg_to + 0 * STG_STRIDE] = psum.x;
+    s_stg[stg_to + 1 * STG_STRIDE] = psum.y;
+    s_stg[stg_to + 2 * STG_STRIDE] = psum.z;
+    s_stg[stg_to + 3 * STG_STRIDE] = psum.w;
+    __syncthreads();
+    if (reporter) {
+      tl->used = 1;
+      tl->rounds = real;
+      S->close.how = how;
+      S->close.m = first - 1;
+      // how this launch went, for the host's choice of form for later solves (PicpTailTally, PicpTailClose; one writer per launch)
+      const int c = t_count + 1;
+      *(real ? &S->tally.looped : &S->tally.straight) = c;
+      // the run of skip-path launches and the latest round in which one of them found its repeat: where the host may start
+      // the tail launch of the next solves (picp_tail_policy)
+      int run = 0, det = 0;
+      if (!real) {
+        run = t_run < 0xffff ? t_run + 1 : 0xffff;
+        det = t_d > t_det ? t_d : t_det;
+        det = det < 0xffff ? det : 0xffff;
+      }
+      S->close.run = run;
+      S->close.max_detected = det;
+      if (report) {
+        report[2] = run << 16 | det;
+        if (real) {
+          // (the host reads [1] first: the word it then finds in [2] must not be the run this launch has just ended)
+          __builtin_amdgcn_fence(__ATOMIC_RELEASE, "");
+          const int lr = first + real - 1;
+          report[3] = (c & 0xffff) << 16 | (lr < 0xffff ? lr : 0xffff);
+          report[1] = c;
+        } else {
+          report[0] = c;
+        }
+      }
+    }
+    if (wave != 0) return;                                   // (every wave would get the same bits; only wave 0's are stored)
+    float val = 0.f;
+    if (lane < 45) {
+      const float4* row = reinterpret_cast<const float4*>(s_stg + stg_at);
+      float tsum = 0.f;
+#pragma unroll
+      for (int k = 0; k < PICP_GROUPS / 4; ++k) { const float4 t4 = row[k]; tsum += t4.x; tsum += t4.y; tsum += t4.z; tsum += t4.w; }
+      if (lane < 36) {
+        val = diag ? tsum + 1.f * damping : tsum;
+        if (wave == 0) S->H[(lane % 6) * 6 + lane / 6] = val;    // col-major
+      } else if (lane < 42) {
+        val = -tsum;
+        if (wave == 0) S->b[lane - 36] = tsum;
+      } else if (wave == 0) {
+        s_stat[lane - 42] = tsum;
+      }
+    }
+    const Pose Tn = picp_tail_direct(val, pb0, pb1, pb2, m3);
+    if (tid == 0) {
+      store_pose12(S->pose[0], Tn);
+      float T16[16];
+      pose_to_T16(Tn, T16);
+#pragma unroll
+      for (int k = 0; k < 16; ++k) S->T16[k] = T16[k];
+      S->chi_in = s_stat[0];
+      S->chi_out = s_stat[1];
+      S->n_in = (int)(s_stat[2] + 0.5f);
+    }
   }
 }
 
@@ -929,11 +1075,13 @@ int picp_grid_for(int n_corr, int n_cu) {
 }
 
 // VO_PICP_TAIL=0 keeps a launch per round; VO_PICP_TAIL_FROM sets the last round with a launch of its own (read per call)
-int picp_tail_from(int grid, int n_iters, bool cycle, int n_cu, bool* forced) {
+bool picp_tail_ring_enabled() { const char* e = getenv("VO_PICP_TAIL_RING"); return !(e && e[0] == '0'); }
+
+int picp_tail_from(int grid, int n_iters, bool cycle, int n_cu, bool* forced, int m_default) {
   if (forced) *forced = false;
   if (!cycle) return 0;
   if (const char* e = getenv("VO_PICP_TAIL")) { if (e[0] == '0') return 0; if (forced && e[0] == '1') *forced = true; }
-  int m = PICP_TAIL_FROM;
+  int m = m_default;
   if (const char* e = getenv("VO_PICP_TAIL_FROM")) { const int v = atoi(e); if (v >= 1) { m = v; if (forced) *forced = true; } }
   if (!(n_iters - 1 > m + 1)) return 0;
   // Residency: the loop path's barrier needs every workgroup of the launch on the chip at once.  One workgroup per CU at the
@@ -1039,7 +1187,8 @@ static bool picp_small_enabled() {
 
 template <bool PINHOLE, bool KEEP>
 static void launch_rounds_t(hipStream_t st, PicpParams* d_params, PicpState* d_state, PackedCorr pk,
-                            float* d_partials, int grid, int n_iters, const PicpGather& g, int part, bool cycle, int tail_from, int* tail_report) {
+                            float* d_partials, int grid, int n_iters, const PicpGather& g, int part, bool cycle, int tail_from, int* tail_report,
+                            bool tail_ring) {
   // With cycle detection every launch behind round 0 carries one more workgroup, the detector (picp_cycle_detect); the rounds
   // are told the last round launch's index.  Round 0 resets the control block whether or not detection is on.
   const int cyc = cycle ? 1 : 0, last = n_iters - 1;
@@ -1051,14 +1200,16 @@ static void launch_rounds_t(hipStream_t st, PicpParams* d_params, PicpState* d_s
   if (n_iters > 1)
     hipLaunchKernelGGL((picp_tally_round_kernel<false, PINHOLE, KEEP>), dim3(grid + cyc), dim3(PICP_BLOCK), 0, st,
                        d_params, d_state, pk.base, pk.cap, d_partials, 1, grid);
-  // the tail form (picp_tail_kernel): rounds 1 .. tail_from as ever, ONE launch for rounds tail_from + 1 .. last
+  // the tail form (picp_tail_kernel): rounds 1 .. tail_from as ever, ONE launch for rounds tail_from + 1 .. last that also
+  // closes the solve -- no finishing launch behind it
   const int own = tail_from > 0 ? tail_from + 1 : n_iters;
   for (int it = 2; it < own; ++it)
     hipLaunchKernelGGL((picp_round_kernel<true, false, PINHOLE, KEEP>), dim3(grid + cyc), dim3(PICP_BLOCK), 0, st,
                        d_params, d_state, pk.base, pk.cap, d_partials, it, grid, last, cyc);
   if (tail_from > 0)
     hipLaunchKernelGGL((picp_tail_kernel<PINHOLE, KEEP>), dim3(grid + 1), dim3(PICP_BLOCK), 0, st, d_params, d_state, pk.base,
-                       pk.cap, d_partials, tail_from + 1, grid, last, tail_report);
+                       pk.cap, d_partials, tail_from + 1, grid, last, tail_report, tail_ring ? 1 : 0);
+  if (tail_from > 0) return;
   if (n_iters == 1)
     hipLaunchKernelGGL((picp_tally_round_kernel<true, false, false>), dim3(1), dim3(PICP_BLOCK), 0, st, d_params,
                        d_state, pk.base, pk.cap, d_partials, n_iters, grid);
@@ -1101,7 +1252,8 @@ hipError_t launch_picp_finish(hipStream_t st, const PicpParams* d_params, PicpSt
 
 hipError_t launch_picp_rounds(hipStream_t st, PicpParams* d_params, PicpState* d_state,
                               PackedCorr pk, float* d_partials, int grid, int n_iters, bool pinhole,
-                              bool keep_outliers, const PicpGather& gt, int part, bool cycle, int tail_from, int* tail_report) {
+                              bool keep_outliers, const PicpGather& gt, int part, bool cycle, int tail_from, int* tail_report,
+                              bool tail_ring) {
   if (n_iters <= 0) return hipSuccess;
   if (tail_from < 0 || (tail_from > 0 && (!cycle || n_iters - 1 <= tail_from + 1))) return hipErrorInvalidValue;
   if (grid == 1 && picp_small_enabled()) {      // one workgroup's worth of correspondences (picp_grid_for): all rounds in one launch
@@ -1114,11 +1266,11 @@ hipError_t launch_picp_rounds(hipStream_t st, PicpParams* d_params, PicpState* d
     return hipGetLastError();
   }
   if (pinhole) {
-    if (keep_outliers) launch_rounds_t<true, true>(st, d_params, d_state, pk, d_partials, grid, n_iters, gt, part, cycle, tail_from, tail_report);
-    else launch_rounds_t<true, false>(st, d_params, d_state, pk, d_partials, grid, n_iters, gt, part, cycle, tail_from, tail_report);
+    if (keep_outliers) launch_rounds_t<true, true>(st, d_params, d_state, pk, d_partials, grid, n_iters, gt, part, cycle, tail_from, tail_report, tail_ring);
+    else launch_rounds_t<true, false>(st, d_params, d_state, pk, d_partials, grid, n_iters, gt, part, cycle, tail_from, tail_report, tail_ring);
   } else {
-    if (keep_outliers) launch_rounds_t<false, true>(st, d_params, d_state, pk, d_partials, grid, n_iters, gt, part, cycle, tail_from, tail_report);
-    else launch_rounds_t<false, false>(st, d_params, d_state, pk, d_partials, grid, n_iters, gt, part, cycle, tail_from, tail_report);
+    if (keep_outliers) launch_rounds_t<false, true>(st, d_params, d_state, pk, d_partials, grid, n_iters, gt, part, cycle, tail_from, tail_report, tail_ring);
+    else launch_rounds_t<false, false>(st, d_params, d_state, pk, d_partials, grid, n_iters, gt, part, cycle, tail_from, tail_report, tail_ring);
   }
   return hipGetLastError();
 }

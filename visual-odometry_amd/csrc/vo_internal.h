@@ -108,6 +108,36 @@ struct PicpTailTally {
   int straight;
   int looped;
 };
+// The tail launch also CLOSES the solve (there is no finishing launch behind it): its workgroup 0 does the finishing launch's
+// work -- the rows of round N - 1 summed, the system solved, pose[0], T16, H, b, statistics -- in one of three ways:
+//   RING       state SKIP and the rows launch `target` stored still lie in the ring (picp_tail_ring_holds): they ARE the rows
+//              launch N - 1 would store, so nothing is linearised; every other workgroup returns behind the control word;
+//   RECOMPUTED state SKIP, slot overwritten (or VO_PICP_TAIL_RING=0): every workgroup linearises with hist[target], stores its
+//              row, arrives on PicpTail::bar and leaves; workgroup 0 waits for all arrivals;
+//   LOOPED     the launch ran round N - 1 as a real round at the end of its loop: closed like RECOMPUTED.
+// The words lie behind the tally so that no earlier offset moves; like the tally they are written by tail launches only and
+// never reset: `how` and `m` describe the last solve THAT HAD a tail launch (PicpTail::used tells whether the last solve did).
+constexpr int PICP_CLOSE_NONE = 0, PICP_CLOSE_RING = 1, PICP_CLOSE_RECOMPUTED = 2, PICP_CLOSE_LOOPED = 3;
+struct PicpTailClose {
+  int how;             // PICP_CLOSE_*
+  int m;               // the M that solve ran with (rounds 1 .. M had launches of their own)
+  int run;             // consecutive tail launches of this handle that took the skip path, since the last one with real rounds
+  int max_detected;    // the largest detected_at among them
+};
+// The rows launch `target` stored in slot target % PICP_SLOTS are intact when launch skip_from - 1, the last one that stored
+// rows, has not come round to that slot: it wrote slot (skip_from - 1) % PICP_SLOTS last, launch target + PICP_SLOTS would
+// have been the first to overwrite.  (target >= j and skip_from = k + 2 for a repeat pose k = pose j: a period of 14 or less
+// always holds.)  target = 0 is included: the gathering round stores the same 30 sums as any round plus the dropped-pair
+// tally in slots 30 and 31, which the closing -- like the FINISH instantiation of a solve of two or more rounds -- never sums.
+__host__ __device__ inline bool picp_tail_ring_holds(int skip_from, int target) {
+  return target >= 0 && skip_from - 1 - target < PICP_SLOTS;
+}
+// the host's report (pinned memory, launch_picp_rounds' tail_report): [0], [1] the tally's two counts; [2] run << 16 |
+// max_detected (each saturating at 0xffff) in ONE word, so that the host never reads a torn pair; [3] behind a launch that ran
+// real rounds: looped << 16 | the last round it ran (first + real - 1, saturating), the count's low half as a consistency tag
+constexpr int PICP_TAIL_REPORT_WORDS = 4;
+// the host lowers M only once this many consecutive tail launches have taken the skip path (capi.hip, picp_tail_policy)
+constexpr int PICP_TAIL_LEARN = 8;
 
 // Solver state in device memory.
 struct PicpState {
@@ -122,6 +152,7 @@ struct PicpState {
   float hist[PICP_HIST][12];    // hist[k % PICP_HIST]: the pose after round k of this solve (pose[k % PICP_SLOTS] when it was written)
   PicpTail tail;       // directly behind the history
   PicpTailTally tally;
+  PicpTailClose close; // behind the tally (the offsets before it are pinned by tests and by include/vo_hip.h)
 #ifdef VO_STAMPS
   // diagnostic build only (make STAMPS=1 -> libvo_hip_stamps.so, tools/stamp_rounds.py):
   // s_memtime at phase boundaries of workgroup 0, per round
@@ -169,13 +200,16 @@ constexpr int PICP_WHOLE = 0, PICP_ROUND0 = 1, PICP_AFTER_ROUND0 = 2;
 hipError_t launch_picp_rounds(hipStream_t st, PicpParams* d_params, PicpState* d_state,
                               PackedCorr pk, float* d_partials, int grid, int n_iters, bool pinhole,
                               bool keep_outliers, const PicpGather& g = PicpGather{}, int part = PICP_WHOLE, bool cycle = false,
-                              int tail_from = 0, int* tail_report = nullptr);
+                              int tail_from = 0, int* tail_report = nullptr, bool tail_ring = true);
 // the tail form's M for a solve of n_iters rounds on `grid` workgroups (picp_grid_for), or 0 where the solve keeps a
 // launch per round: too few rounds, no cycle detection, the form switched off, or a grid that would not leave every workgroup
 // of the tail launch -- the detector included -- a CU of its own.  Reads VO_PICP_TAIL and VO_PICP_TAIL_FROM; *forced (may be
 // null) tells whether either of them asks for the form explicitly (VO_PICP_TAIL=1, or any VO_PICP_TAIL_FROM).
-// tail_report (launch_picp_rounds): two host-visible ints that take the handle's PicpTailTally counts, or null.
-int picp_tail_from(int grid, int n_iters, bool cycle, int n_cu, bool* forced = nullptr);
+// tail_report (launch_picp_rounds): PICP_TAIL_REPORT_WORDS host-visible ints (above), or null.  tail_ring: false forces the
+// RECOMPUTED closing where RING would do (VO_PICP_TAIL_RING=0, read per call by picp_tail_ring_enabled: tests and the A/B).
+// m_default: the M to use where VO_PICP_TAIL_FROM does not set one (the handle's learned M: picp_tail_policy).
+int picp_tail_from(int grid, int n_iters, bool cycle, int n_cu, bool* forced = nullptr, int m_default = PICP_TAIL_FROM);
+bool picp_tail_ring_enabled();
 
 int picp_grid_for(int n_corr, int n_cu);
 
