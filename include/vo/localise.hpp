@@ -7,6 +7,8 @@
 // status in the statistics, not an exception; vo::Error is thrown where the C call refuses.
 #pragma once
 
+#include <cmath>
+
 #include <cstdint>
 #include <limits>
 #include <string>
@@ -95,6 +97,47 @@ struct CullOptions {
 inline const char* cull_verdict_name(int verdict) {
   static const char* names[] = {"KEPT", "UNSEEN", "FEW_OBS", "FEW_FRAMES", "NOT_FINITE", "BEHIND", "HIGH_ERROR", "LOW_PARALLAX"};
   return verdict >= 0 && verdict < 8 ? names[verdict] : "?";
+}
+
+//! voe_map_align: how two maps of one scene relate.  threshold in the units of the map aligned TO.
+struct AlignOptions {
+  float threshold = 0.05f;
+  int n_hypotheses = 64;
+  uint64_t seed = 1;
+  bool with_scale = true;
+  int n_refits = 1;
+  int min_inliers = 3;
+};
+inline const char* align_status_name(int status) {
+  static const char* names[] = {"OK", "FEW_MATCHES", "NO_HYPOTHESIS", "FEW_INLIERS"};
+  return status >= 0 && status < 4 ? names[status] : "?";
+}
+//! a similarity [c R | t] as the library hands it out: column-major 4x4, last row 0 0 0 1
+struct Similarity3f {
+  float m[16];
+  float operator()(int r, int c) const { return m[r + 4 * c]; }
+  const float* data() const { return m; }
+  static Similarity3f Identity() { Similarity3f S{}; S.m[0] = S.m[5] = S.m[10] = S.m[15] = 1.f; return S; }
+};
+//! The pose of a frame of src's in the map moved by S: T (p_cam = T p_src) and S = [c R | t] (p_dst = S p_src) give the rigid
+//! T' = [R_T R^T | c t_T - R_T R^T t], on the host in double.  T' p_dst = c T p_src: camera points only scale by c, so every
+//! projection is unchanged.
+inline Isometry3f similarity_pose(const Isometry3f& T, const Similarity3f& S) {
+  double M[3][3], det;
+  for (int r = 0; r < 3; ++r) for (int c = 0; c < 3; ++c) M[r][c] = S(r, c);
+  det = M[0][0] * (M[1][1] * M[2][2] - M[1][2] * M[2][1]) - M[0][1] * (M[1][0] * M[2][2] - M[1][2] * M[2][0]) +
+        M[0][2] * (M[1][0] * M[2][1] - M[1][1] * M[2][0]);
+  const double c = std::cbrt(det);
+  Isometry3f out = Isometry3f::Identity();
+  double Rn[3][3];
+  for (int r = 0; r < 3; ++r)
+    for (int k = 0; k < 3; ++k) {                              // R_T R^T, R = M / c
+      Rn[r][k] = ((double)T(r, 0) * M[k][0] + (double)T(r, 1) * M[k][1] + (double)T(r, 2) * M[k][2]) / c;
+      out(r, k) = (float)Rn[r][k];
+    }
+  for (int r = 0; r < 3; ++r)
+    out(r, 3) = (float)(c * (double)T(r, 3) - (Rn[r][0] * (double)S(0, 3) + Rn[r][1] * (double)S(1, 3) + Rn[r][2] * (double)S(2, 3)));
+  return out;
 }
 
 class DeviceMap {
@@ -289,6 +332,37 @@ class DeviceMap {
     check(voe_map_cull(h_, (int)w.F, cam.cameraMatrix().data(), w.uv.data(), w.app.data(), w.n.data(), (int)w.cap, w.T.data(), &prm,
                        verdict && M ? verdict->data() : nullptr, remap && M ? remap->data() : nullptr,
                        entries && M ? entries->data() : nullptr, &st), "voe_map_cull");
+    return st;
+  }
+
+  //! the similarity S with p_this ~ S p_src from the landmarks the two maps share (voe_map_align): 3-point RANSAC, then
+  //! opt.n_refits Umeyama refits over the inliers.  S is the identity unless stats->status is VOE_MAP_ALIGN_OK.  *pairs: the
+  //! matches as (src entry, entry of this map); *inliers: one byte per match.
+  Similarity3f align(const DeviceMap& src, const AlignOptions& opt = AlignOptions(), voe_map_align_stats* stats = nullptr,
+                     IntPairVector* pairs = nullptr, std::vector<uint8_t>* inliers = nullptr) const {
+    const size_t n = (size_t)src.size();
+    IntPairVector pr(n ? n : 1);
+    std::vector<uint8_t> mask(n ? n : 1, 0);
+    const voe_map_align_params prm{opt.seed, opt.n_hypotheses, opt.with_scale ? 1 : 0, opt.n_refits, opt.min_inliers, opt.threshold, 0};
+    voe_map_align_stats st{};
+    Similarity3f S = Similarity3f::Identity();
+    int k = 0;
+    check(voe_map_align(h_, src.h_, &prm, S.m, pair_data(pr), &k, mask.data(), nullptr, &st), "voe_map_align");
+    pr.resize((size_t)k); mask.resize((size_t)k);
+    if (stats) *stats = st;
+    if (pairs) *pairs = pr;
+    if (inliers) *inliers = mask;
+    return S;
+  }
+
+  //! src's entries, moved by S (or as they are), into this map (voe_map_merge): VOE_MAP_MERGE_TAKE_SRC as update does, or
+  //! VOE_MAP_MERGE_KEEP_DST appending only what this map does not hold.  *remap: the entry of this map per src entry, or -1.
+  voe_map_merge_stats merge(const DeviceMap& src, const Similarity3f* S = nullptr, int policy = VOE_MAP_MERGE_TAKE_SRC,
+                            std::vector<int32_t>* remap = nullptr) {
+    const size_t n = (size_t)src.size();
+    if (remap) remap->assign(n, -1);
+    voe_map_merge_stats st{};
+    check(voe_map_merge(h_, src.h_, S ? S->m : nullptr, policy, remap && n ? remap->data() : nullptr, &st), "voe_map_merge");
     return st;
   }
 

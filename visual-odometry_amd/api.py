@@ -684,6 +684,59 @@ class Map:
         return dict(verdict=verdict[:k].copy(), remap=remap[:k].copy(), entries=entries[:k].copy(), stats=st.as_dict())
 
 
+    # ---- two maps: alignment by 3-point similarity RANSAC and the merge (voe_map_align*, voe_map_merge*, include/vo_map_align.h) ----
+    def size_bound(self):
+        """voe_map_size_bound: the host's bound of the size (what sizes the arrays of align_dev / merge_dev); no device work"""
+        n = C.c_int()
+        _chk(self.lib.voe_map_size_bound(self.h, C.byref(n)))
+        return n.value
+
+    def align_dev(self, src: "Map", params: "MapAlignParams", d_S16_out, d_pairs_out, d_n_matches, d_inlier_mask, d_hypothesis_counts,
+                  d_stats):
+        """voe_map_align_dev on device pointers (ints; the mask and the counts may be None): this map is dst.  Enqueues and
+        returns.  d_pairs_out: src.size_bound() x 8 bytes; d_stats: 48 bytes (MapAlignStats)."""
+        v = lambda d: C.c_void_p(d) if d else None
+        _chk(self.lib.voe_map_align_dev(self.h, src.h, C.byref(params), v(d_S16_out), v(d_pairs_out), v(d_n_matches), v(d_inlier_mask),
+                                        v(d_hypothesis_counts), v(d_stats)))
+
+    def align(self, src: "Map", threshold, n_hypotheses=64, seed=0, with_scale=True, n_refits=1, min_inliers=3, want_counts=False):
+        """voe_map_align: the similarity S (4x4, p_self ~ S p_src) between `src` and this map from the landmarks they share, by
+        3-point RANSAC and n_refits Umeyama refits over the inliers.  Returns dict(S (4, 4) float32, pairs (k, 2) = (src entry,
+        entry of this map), mask (k,) bool: the inliers, stats dict: MAP_ALIGN_STATUS names stats["status"]) and, with
+        want_counts, counts (n_hypotheses,) int32.  S is the identity unless the status is OK."""
+        n = max(len(src), 1)
+        S = np.zeros(16, np.float32)
+        pairs = np.zeros((n, 2), np.int32)
+        mask = np.zeros(n, np.uint8)
+        counts = np.zeros(int(n_hypotheses), np.int32)
+        k = C.c_int()
+        st = MapAlignStats()
+        prm = MapAlignParams(int(seed) & 0xFFFFFFFFFFFFFFFF, int(n_hypotheses), int(bool(with_scale)), int(n_refits), int(min_inliers),
+                             float(threshold), 0)
+        _chk(self.lib.voe_map_align(self.h, src.h, C.byref(prm), _ptr(S), _ptr(pairs), C.byref(k), _ptr(mask),
+                                    _ptr(counts) if want_counts else None, C.byref(st)))
+        out = dict(S=S.reshape(4, 4).T.copy(), pairs=pairs[: k.value].copy(), mask=mask[: k.value].astype(bool), stats=st.as_dict())
+        if want_counts:
+            out["counts"] = counts
+        return out
+
+    def merge_dev(self, src: "Map", d_S16, policy, d_remap_out, d_stats):
+        """voe_map_merge_dev on device pointers (ints; d_S16 and d_remap_out may be None): this map is dst.  d_stats: 16 bytes"""
+        v = lambda d: C.c_void_p(d) if d else None
+        _chk(self.lib.voe_map_merge_dev(self.h, src.h, v(d_S16), C.c_int(int(policy)), v(d_remap_out), v(d_stats)))
+
+    def merge(self, src: "Map", S=None, policy=0):
+        """voe_map_merge: src's entries, moved by S (4x4 or None), into this map.  policy: MAP_MERGE_TAKE_SRC (a shared landmark
+        takes src's point, as update does) or MAP_MERGE_KEEP_DST (only the entries this map does not hold are appended).
+        Returns (remap (len(src),) int32: the entry of this map that src entry i is found at afterwards, or -1; stats dict)."""
+        n = max(len(src), 1)
+        remap = np.full(n, -2, np.int32)
+        st = MapMergeStats()
+        _chk(self.lib.voe_map_merge(self.h, src.h, _ptr(_colmajor(S, 4)) if S is not None else None, C.c_int(int(policy)), _ptr(remap),
+                                    C.byref(st)))
+        return remap[: st.n_src].copy(), st.as_dict()
+
+
 class MapLocaliseStats(C.Structure):
     """vo_map_localise_stats (include/vo_hip.h)"""
     _fields_ = [("status", C.c_int32), ("n_rows", C.c_int32), ("n_hits", C.c_int32), ("ransac_status", C.c_int32),
@@ -802,6 +855,50 @@ MAP_CULL_ENTRY_DTYPE = np.dtype([("verdict", "<i4"), ("n_obs", "<i4"), ("n_frame
 assert MAP_CULL_ENTRY_DTYPE.itemsize == 48
 MAP_CULL_VERDICT = ("KEPT", "UNSEEN", "FEW_OBS", "FEW_FRAMES", "NOT_FINITE", "BEHIND", "HIGH_ERROR", "LOW_PARALLAX")   # VOE_MAP_CULL_*
 MAP_CULL_STATUS = ("OK", "NOTHING_DROPPED")
+
+
+class MapAlignParams(C.Structure):
+    """voe_map_align_params (include/vo_map_align.h)"""
+    _fields_ = [("seed", C.c_uint64), ("n_hypotheses", C.c_int32), ("with_scale", C.c_int32), ("n_refits", C.c_int32),
+                ("min_inliers", C.c_int32), ("threshold", C.c_float), ("reserved", C.c_int32)]
+
+
+class MapAlignStats(C.Structure):
+    """voe_map_align_stats (include/vo_map_align.h)"""
+    _fields_ = [("status", C.c_int32), ("n_matches", C.c_int32), ("n_inliers", C.c_int32), ("best_hypothesis", C.c_int32),
+                ("best_count", C.c_int32), ("n_valid", C.c_int32), ("refit_kept", C.c_int32), ("reserved", C.c_int32),
+                ("scale", C.c_double), ("rms", C.c_double)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_ if k != "reserved"}
+
+
+class MapMergeStats(C.Structure):
+    """voe_map_merge_stats (include/vo_map_align.h)"""
+    _fields_ = [("n_src", C.c_int32), ("n_shared", C.c_int32), ("n_appended", C.c_int32), ("n_dst_after", C.c_int32)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+assert C.sizeof(MapAlignParams) == 32 and C.sizeof(MapAlignStats) == 48 and C.sizeof(MapMergeStats) == 16
+MAP_ALIGN_STATUS = ("OK", "FEW_MATCHES", "NO_HYPOTHESIS", "FEW_INLIERS")      # VOE_MAP_ALIGN_*
+MAP_ALIGN_MAX_REFITS = 16
+MAP_MERGE_TAKE_SRC, MAP_MERGE_KEEP_DST = 0, 1                                   # VOE_MAP_MERGE_*
+
+
+def similarity_pose(T, S):
+    """The pose of a frame of src's in the map moved by S: T (4x4 rigid, p_cam = T p_src) and S = [c R | t] (4x4, p_dst = S p_src)
+    give the rigid T' = [R_T R^T | c t_T - R_T R^T t], on the host in double.  T' p_dst = c T p_src: camera points only scale by c,
+    so every projection is unchanged."""
+    T, S = np.asarray(T, np.float64).reshape(4, 4), np.asarray(S, np.float64).reshape(4, 4)
+    M = S[:3, :3]
+    c = np.cbrt(np.linalg.det(M))
+    Rn = T[:3, :3] @ (M / c).T
+    out = np.eye(4)
+    out[:3, :3] = Rn
+    out[:3, 3] = c * T[:3, 3] - Rn @ S[:3, 3]
+    return out
 
 
 def triangulate_points(k, X, correspondences, p1_img, p2_img, app2=None, want_pairs=True,

@@ -2233,6 +2233,8 @@ struct vo_map {
   DevBuf pose_ws;               // vo_map_refine_poses*: the entries seen, status, observation count and cost per frame
   DevBuf bundle_ws;             // vox_map_bundle*: the state in double, the blocks and the PCG vectors (the lists live in ref_ws)
   DevBuf cull_ws;               // voe_map_cull*: verdict, remap, ranks, the staging area of the survivors (the lists live in ref_ws)
+  DevBuf align_ws;              // voe_map_align* (on dst): gathered pairs, hypotheses, counts, the blocks' sums
+  DevBuf merge_ws;              // voe_map_merge* (on dst): the lookup's entries, the staging area of the misses
 };
 
 constexpr int MAP_MAX_ENTRIES = 1 << 29;      // 2.5 x that many table slots still fit 32 bits
@@ -2325,7 +2327,7 @@ int vo_map_destroy(vo_map* m) {
   map_free_arrays(m->d);
   if (m->d.hdr) (void)hipFree(m->d.hdr);
   if (m->hist) (void)hipFree(m->hist);
-  m->scratch.release(); m->up_xyz.release(); m->up_app.release(); m->look_ws.release(); m->loc_ws.release(); m->ref_ws.release(); m->pose_ws.release(); m->bundle_ws.release(); m->cull_ws.release();
+  m->scratch.release(); m->up_xyz.release(); m->up_app.release(); m->look_ws.release(); m->loc_ws.release(); m->ref_ws.release(); m->pose_ws.release(); m->bundle_ws.release(); m->cull_ws.release(); m->align_ws.release(); m->merge_ws.release();
   if (m->solver) (void)vo_picp_destroy(m->solver);
   delete m;
   return VO_OK;
@@ -3112,6 +3114,156 @@ int voe_map_cull(vo_map* m, int n_frames, const float K[9], const float* uv, con
   }
   VO_HIP_CHECK(hipStreamSynchronize(c->stream));
   if (!m->replayable && !params->dry_run) m->size_ub = stats_out->n_kept;
+  return VO_OK;
+}
+
+// ---- two maps: alignment by 3-point similarity RANSAC and the merge (map_align.hip; include/vo_map_align.h) ----------------
+static_assert(sizeof(voe_map_align_params) == 32 && sizeof(voe_map_align_stats) == 48 && sizeof(voe_map_merge_stats) == 16,
+              "the records of include/vo_map_align.h as the kernels write them");
+
+int voe_map_size_bound(vo_map* m, int* n_max_out) {
+  VO_MAP_LIVE(m);
+  VO_REQUIRE(n_max_out, "null argument");
+  *n_max_out = map_bound(m);
+  return VO_OK;
+}
+
+static int two_maps_check(const char* fn, const vo_map* dst, const vo_map* src) {
+  if (!dst || !src) return fail(VO_ERR_INVALID_ARG, "%s: null map", fn);
+  if (dst == src) return fail(VO_ERR_INVALID_ARG, "%s: src and dst are one map", fn);
+  if (!ctx_alive(dst->ctx, dst->ctx_id) || !ctx_alive(src->ctx, src->ctx_id))
+    return fail(VO_ERR_INVALID_ARG, "%s: the context a map was made on has been destroyed", fn);
+  if (dst->ctx != src->ctx) return fail(VO_ERR_INVALID_ARG, "%s: the maps live on different contexts", fn);
+  return VO_OK;
+}
+
+static int align_check_params(const char* fn, const voe_map_align_params* p) {
+  if (!p) return fail(VO_ERR_INVALID_ARG, "%s: null argument", fn);
+  if (p->n_hypotheses < 1 || p->n_hypotheses > 65536) return fail(VO_ERR_INVALID_ARG, "%s: n_hypotheses outside 1 .. 65536", fn);
+  if (p->n_refits < 0 || p->n_refits > VOE_MAP_ALIGN_MAX_REFITS)
+    return fail(VO_ERR_INVALID_ARG, "%s: n_refits outside 0 .. %d (the launches of a call are a fixed sequence)", fn, VOE_MAP_ALIGN_MAX_REFITS);
+  if (p->min_inliers < 0) return fail(VO_ERR_INVALID_ARG, "%s: min_inliers must not be negative", fn);
+  if (!(p->threshold > 0.f && p->threshold <= 3.402823466e38f)) return fail(VO_ERR_INVALID_ARG, "%s: threshold must be positive and finite", fn);
+  return VO_OK;
+}
+
+int voe_map_align_dev(vo_map* dst, vo_map* src, const voe_map_align_params* p, float* d_S16_out, int32_t* d_pairs_out, int* d_n_matches,
+                      uint8_t* d_inlier_mask, int32_t* d_hypothesis_counts, voe_map_align_stats* d_stats) {
+  const char* fn = "voe_map_align_dev";
+  if (int r = two_maps_check(fn, dst, src)) return r;
+  if (int r = align_check_params(fn, p)) return r;
+  if (!(d_S16_out && d_pairs_out && d_n_matches && d_stats)) return fail(VO_ERR_INVALID_ARG, "%s: null argument", fn);
+  if (!aligned8(d_pairs_out, d_stats)) return fail(VO_ERR_INVALID_ARG, "%s: d_pairs_out and d_stats must be 8-byte aligned", fn);
+  vo_ctx* c = dst->ctx;
+  const int n_max = map_bound(src);
+  size_t bytes = 0;
+  (void)map_align_layout(nullptr, n_max, p->n_hypotheses, &bytes);
+  if (c->capturing && dst->align_ws.cap < bytes)              // (before the lookup is enqueued)
+    return fail(VO_ERR_NOT_READY, "%s: the workspace would have to grow inside a graph capture (make one call with these maps and %d "
+                                  "hypotheses before capturing)", fn, p->n_hypotheses);
+  if (int r = set_device(c)) return r;
+  VO_HIP_CHECK(dst->align_ws.ensure(bytes, c->stream));
+  MapAlignArgs a = map_align_layout(dst->align_ws.p, n_max, p->n_hypotheses, nullptr);
+  // the matches: the public lookup, on dst, of src's appearances
+  if (int r = vo_map_lookup_dev(dst, src->d.app, n_max, src->d.hdr, d_pairs_out, d_n_matches, a.bxyz, nullptr, nullptr)) return r;
+  a.src_pts = src->d.pts; a.pairs = d_pairs_out; a.d_n = d_n_matches;
+  a.with_scale = p->with_scale != 0; a.n_refits = p->n_refits; a.min_inliers = p->min_inliers; a.seed = p->seed;
+  a.thr2 = p->threshold * p->threshold;
+  if (d_hypothesis_counts) a.counts = d_hypothesis_counts;
+  a.mask_out = d_inlier_mask;
+  a.S16_out = d_S16_out; a.stats = d_stats;
+  VO_HIP_CHECK(launch_map_align(c->stream, a));
+  return VO_OK;
+}
+
+int voe_map_align(vo_map* dst, vo_map* src, const voe_map_align_params* p, float S16_out[16], int32_t* pairs_out, int* n_matches_out,
+                  uint8_t* mask_out, int32_t* counts_out, voe_map_align_stats* stats_out) {
+  const char* fn = "voe_map_align";
+  if (int r = two_maps_check(fn, dst, src)) return r;
+  vo_ctx* c = dst->ctx;
+  VO_NOT_CAPTURING(c);
+  if (int r = align_check_params(fn, p)) return r;
+  VO_REQUIRE(S16_out && stats_out, "null argument");
+  if (int r = set_device(c)) return r;
+  int size = 0;
+  if (int r = vo_map_size(src, &size)) return r;              // (the bound becomes the size, unless an update of src was captured)
+  const size_t n = (size_t)(map_bound(src) > 0 ? map_bound(src) : 1), H = (size_t)p->n_hypotheses;
+  VO_HIP_CHECK(c->out[0].ensure(sizeof(int32_t) * 2 * n, c->stream));
+  VO_HIP_CHECK(c->out[1].ensure(up256(n) + sizeof(int32_t) * H, c->stream));
+  VO_HIP_CHECK(c->out[2].ensure(256, c->stream));
+  uint8_t* d_mask = c->out[1].as<uint8_t>();
+  int32_t* d_counts = reinterpret_cast<int32_t*>(d_mask + up256(n));
+  float* d_S = c->out[2].as<float>();
+  int* d_nm = reinterpret_cast<int*>(d_S + 16);
+  voe_map_align_stats* d_st = reinterpret_cast<voe_map_align_stats*>(d_S + 32);
+  if (int r = voe_map_align_dev(dst, src, p, d_S, c->out[0].as<int32_t>(), d_nm, mask_out ? d_mask : nullptr, counts_out ? d_counts : nullptr, d_st))
+    return r;
+  VO_HIP_CHECK(hipMemcpyAsync(S16_out, d_S, sizeof(float) * 16, hipMemcpyDeviceToHost, c->stream));
+  VO_HIP_CHECK(hipMemcpyAsync(stats_out, d_st, sizeof(voe_map_align_stats), hipMemcpyDeviceToHost, c->stream));
+  if (size > 0) {
+    if (pairs_out) VO_HIP_CHECK(hipMemcpyAsync(pairs_out, c->out[0].p, sizeof(int32_t) * 2 * (size_t)size, hipMemcpyDeviceToHost, c->stream));
+    if (mask_out) VO_HIP_CHECK(hipMemcpyAsync(mask_out, d_mask, (size_t)size, hipMemcpyDeviceToHost, c->stream));
+  }
+  if (counts_out) VO_HIP_CHECK(hipMemcpyAsync(counts_out, d_counts, sizeof(int32_t) * H, hipMemcpyDeviceToHost, c->stream));
+  VO_HIP_CHECK(hipStreamSynchronize(c->stream));
+  if (n_matches_out) *n_matches_out = stats_out->n_matches;
+  return VO_OK;
+}
+
+int voe_map_merge_dev(vo_map* dst, vo_map* src, const float* d_S16, int policy, int32_t* d_remap_out, voe_map_merge_stats* d_stats) {
+  const char* fn = "voe_map_merge_dev";
+  if (int r = two_maps_check(fn, dst, src)) return r;
+  if (policy != VOE_MAP_MERGE_TAKE_SRC && policy != VOE_MAP_MERGE_KEEP_DST) return fail(VO_ERR_INVALID_ARG, "%s: unknown policy %d", fn, policy);
+  if (!d_stats) return fail(VO_ERR_INVALID_ARG, "%s: null argument", fn);
+  vo_ctx* c = dst->ctx;
+  const int n_max = map_bound(src);
+  const MapMergeWs lay = map_merge_layout(nullptr, n_max);
+  const size_t look = sizeof(int) * map_lookup_scratch_ints(n_max, 1, false), upd = sizeof(int) * map_scratch_ints(n_max);
+  if (c->capturing && (dst->merge_ws.cap < lay.bytes || dst->look_ws.cap < look || dst->scratch.cap < upd))      // (before anything is enqueued)
+    return fail(VO_ERR_NOT_READY, "%s: the workspace would have to grow inside a graph capture (make one call with these maps before "
+                                  "capturing)", fn);
+  if (int r = set_device(c)) return r;
+  if (int r = map_reserve(dst, n_max)) return r;              // dst grows here, on the host, or the capture is refused
+  VO_HIP_CHECK(dst->merge_ws.ensure(lay.bytes, c->stream));
+  const MapMergeWs w = map_merge_layout(dst->merge_ws.p, n_max);
+  VO_HIP_CHECK(launch_map_merge_begin(c->stream, w, dst->d.hdr));
+  // the lookup before the merge: which src entries dst holds already
+  if (int r = vo_map_lookup_dev(dst, src->d.app, n_max, src->d.hdr, w.pairs, w.ctl + 1, nullptr, nullptr, w.ent)) return r;
+  if (policy == VOE_MAP_MERGE_TAKE_SRC) {
+    if (int r = vo_map_update_dev(dst, src->d.pts, src->d.app, n_max, src->d.hdr, d_S16)) return r;
+  } else {
+    VO_HIP_CHECK(launch_map_merge_misses(c->stream, w, src->d.pts, src->d.app, src->d.hdr, n_max));
+    if (int r = vo_map_update_dev(dst, w.stage_pts, w.stage_app, n_max, w.ctl + 2, d_S16)) return r;
+  }
+  if (d_remap_out)
+    if (int r = vo_map_lookup_dev(dst, src->d.app, n_max, src->d.hdr, w.pairs, w.ctl + 3, nullptr, nullptr, d_remap_out)) return r;
+  VO_HIP_CHECK(launch_map_merge_stats(c->stream, w, src->d.hdr, dst->d.hdr, n_max, d_stats));
+  return VO_OK;
+}
+
+int voe_map_merge(vo_map* dst, vo_map* src, const float S16[16], int policy, int32_t* remap_out, voe_map_merge_stats* stats_out) {
+  const char* fn = "voe_map_merge";
+  if (int r = two_maps_check(fn, dst, src)) return r;
+  vo_ctx* c = dst->ctx;
+  VO_NOT_CAPTURING(c);
+  VO_REQUIRE(stats_out, "null argument");
+  if (int r = set_device(c)) return r;
+  int size = 0;
+  if (int r = vo_map_size(src, &size)) return r;
+  const size_t n = (size_t)(map_bound(src) > 0 ? map_bound(src) : 1);
+  VO_HIP_CHECK(c->out[0].ensure(sizeof(int32_t) * n, c->stream));
+  VO_HIP_CHECK(c->out[2].ensure(256, c->stream));
+  float* d_S = c->out[2].as<float>();
+  voe_map_merge_stats* d_st = reinterpret_cast<voe_map_merge_stats*>(d_S + 16);
+  if (S16) {
+    VO_HIP_CHECK(hipMemcpyAsync(d_S, S16, sizeof(float) * 16, hipMemcpyHostToDevice, c->stream));
+    VO_HIP_CHECK(hipStreamSynchronize(c->stream));            // the host array may go away after the call
+  }
+  if (int r = voe_map_merge_dev(dst, src, S16 ? d_S : nullptr, policy, remap_out ? c->out[0].as<int32_t>() : nullptr, d_st)) return r;
+  VO_HIP_CHECK(hipMemcpyAsync(stats_out, d_st, sizeof(voe_map_merge_stats), hipMemcpyDeviceToHost, c->stream));
+  if (remap_out && size > 0) VO_HIP_CHECK(hipMemcpyAsync(remap_out, c->out[0].p, sizeof(int32_t) * (size_t)size, hipMemcpyDeviceToHost, c->stream));
+  VO_HIP_CHECK(hipStreamSynchronize(c->stream));
+  if (!dst->replayable) dst->size_ub = stats_out->n_dst_after;
   return VO_OK;
 }
 

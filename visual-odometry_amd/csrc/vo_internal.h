@@ -647,6 +647,57 @@ struct MapCullArgs {
 hipError_t launch_map_cull(hipStream_t st, const MapCullArgs& a, int n_cu);
 hipError_t launch_map_cull_stats(hipStream_t st, const MapCullArgs& a);
 
+// ---- two maps: similarity by 3-point RANSAC and the merge (map_align.hip, voe_map_align* / voe_map_merge*; include/vo_map_align.h
+// holds the rules) ----
+constexpr int ALIGN_FS = 16;            // floats per model: M = c R column-major [0, 9), t [9, 12), [12] = 1 valid / 0 invalid
+constexpr int ALIGN_SUMS = 6;           // doubles per block of the first pass: sum a, sum b
+constexpr int ALIGN_MOMS = 10;          // doubles per block of the second pass: sum db da^T (row-major), sum |da|^2
+struct MapAlignCtl {                    // written by single threads of the one-workgroup kernels
+  float cur[ALIGN_FS];                  // the model whose inliers the next mask pass takes (the winner's, then the refits')
+  float win[ALIGN_FS];                  // the winner's minimal model
+  float ref[ALIGN_FS];                  // the last valid refit
+  float fin[ALIGN_FS];                  // the model handed out
+  double scale_cur, scale_win, scale_ref, scale_fin;
+  int n, win_h, win_cnt, n_valid;       // matches, the winner (-1: none) and its count, valid hypotheses
+  int alive;                            // 1 while the refits go on
+  int have_ref;                         // 1 once a refit was valid
+  int cnt_cur;                          // inliers of the last mask pass
+  int status, kept, n_fin;              // decided: the status, refit_kept, the final count
+};
+struct MapAlignArgs {
+  const float* src_pts;                 // src's points
+  float* bxyz;                          // [n_max][3] dst's point of match k (the lookup's gather)
+  const int32_t* pairs; const int* d_n; int n_max;      // the lookup's pairs and count
+  int n_hyp, with_scale, n_refits, min_inliers; unsigned long long seed; float thr2;
+  float4* pa; float2* pb;               // [n_max] (a0, a1, a2, b0), (b1, b2)
+  float* hyp; double* hyp_scale;        // [n_hyp][ALIGN_FS], [n_hyp]
+  int* counts;                          // [n_hyp] the caller's or the workspace's
+  uint8_t* mask_out;                    // [n_max] the caller's, or null
+  int* blk;                             // [nb] inliers per block of the last mask pass
+  double *sums, *moms, *rms;            // [nb][ALIGN_SUMS], [nb][ALIGN_MOMS], [nb]
+  MapAlignCtl* ctl;
+  float* S16_out; void* stats;
+  int nb;
+};
+MapAlignArgs map_align_layout(void* ws, int n_max, int n_hyp, size_t* bytes);
+// after the lookup has filled pairs, *d_n and bxyz: 2 memsets and 7 + 3 n_refits + 2 (n_refits > 0) launches
+hipError_t launch_map_align(hipStream_t st, const MapAlignArgs& a);
+
+struct MapMergeWs {
+  int32_t* ent;                         // [n_max] the lookup before the merge: dst entry of src entry i, -1
+  int32_t* pairs;                       // [n_max][2] (the lookups' compacted pairs: not handed out)
+  int* blk;                             // [nb] misses per block -> offsets
+  float *stage_pts, *stage_app;         // [n_max][3], [n_max][10] the misses, compacted
+  int* ctl;                             // [0] dst's size before [1] src entries found before [2] misses [3] hits of the remap lookup
+  size_t bytes;
+};
+MapMergeWs map_merge_layout(void* ws, int n_max);
+// ctl[0] <- dst's size (before the lookup and the update are enqueued)
+hipError_t launch_map_merge_begin(hipStream_t st, const MapMergeWs& w, const int* dst_hdr);
+// KEEP_DST, after the lookup has filled w.ent: the misses of src's rows compacted in order into the staging area, their count in ctl[2]
+hipError_t launch_map_merge_misses(hipStream_t st, const MapMergeWs& w, const float* src_pts, const float* src_app, const int* src_hdr, int n_max);
+hipError_t launch_map_merge_stats(hipStream_t st, const MapMergeWs& w, const int* src_hdr, const int* dst_hdr, int n_max, void* stats);
+
 // ---- epipolar initialisation, device half (epi.hip) ------------------------------------------------------
 size_t epi_workspace_bytes();
 // maxima of both point sets + the 45 sums of A^T A + the number of rows / of pairs with a bad index, into ws:
