@@ -99,6 +99,34 @@ inline const char* cull_verdict_name(int verdict) {
   return verdict >= 0 && verdict < 8 ? names[verdict] : "?";
 }
 
+//! voe_map_covis: which entries every frame sees and how many every two frames share
+struct Covisibility {
+  size_t n_frames = 0, n_words = 0;
+  std::vector<uint32_t> bits;        //!< [n_frames][n_words]: bit e & 31 of word e >> 5 of row f is set when frame f sees entry e
+  std::vector<int32_t> counts;       //!< [n_frames][n_frames], or empty when not asked for
+  voe_map_covis_stats stats{};
+  bool sees(size_t f, size_t e) const { return (bits[f * n_words + (e >> 5)] >> (e & 31)) & 1u; }
+  int32_t shared(size_t f, size_t g) const { return counts[f * n_frames + g]; }
+};
+//! voe_map_window: the local window of a frame
+struct WindowOptions {
+  int k_free = 8;                    //!< frames to free, the query among them
+  int k_fixed = 8;                   //!< frames to hold
+  int min_shared = 15;               //!< entries a frame must share to be a candidate
+};
+struct MapWindow {
+  std::vector<int32_t> role;         //!< VOE_MAP_WINDOW_OUTSIDE / _FREE / _FIXED per frame
+  std::vector<int> n_rows;           //!< the frame's live rows inside the window, 0 outside: what bundle / adjust / cull take
+  std::vector<uint8_t> fixed;        //!< 0 for the free frames, 1 otherwise: the mask bundle / adjust take
+  std::vector<int32_t> order;        //!< the free frames in rank order (the query first), the fixed frames in rank order, then -1
+  std::vector<uint32_t> landmarks;   //!< [n_words] the OR of the free frames' rows
+  voe_map_window_stats stats{};
+};
+inline const char* window_status_name(int status) {
+  static const char* names[] = {"OK", "NO_FIXED", "QUERY_UNSEEN"};
+  return status >= 0 && status < 3 ? names[status] : "?";
+}
+
 //! voe_map_align: how two maps of one scene relate.  threshold in the units of the map aligned TO.
 struct AlignOptions {
   float threshold = 0.05f;
@@ -364,6 +392,48 @@ class DeviceMap {
     voe_map_merge_stats st{};
     check(voe_map_merge(h_, src.h_, S ? S->m : nullptr, policy, remap && n ? remap->data() : nullptr, &st), "voe_map_merge");
     return st;
+  }
+
+  //! the covisibility of frames (voe_map_covis): the entries every frame's rows find, as bit rows, and -- with want_counts --
+  //! the number of entries every two frames share.  Two rows of one frame that hit one entry see it once.
+  Covisibility covisibility(const std::vector<Vector10fVector>& appearances, bool want_counts = true) const {
+    Covisibility c;
+    const size_t F = c.n_frames = appearances.size();
+    size_t cap = 0;
+    for (const auto& a : appearances) cap = a.size() > cap ? a.size() : cap;
+    std::vector<float> app(F * cap * 10 + 10, 0.f);
+    std::vector<int> n(F + 1, 0);
+    for (size_t f = 0; f < F; ++f) {
+      n[f] = (int)appearances[f].size();
+      for (size_t i = 0; i < appearances[f].size(); ++i)
+        for (int k = 0; k < 10; ++k) app[(f * cap + i) * 10 + k] = appearances[f][i][k];
+    }
+    int bound = 0;
+    check(voe_map_size_bound(h_, &bound), "voe_map_size_bound");
+    c.n_words = (size_t)(bound > 0 ? (bound + 31) / 32 : 1);
+    c.bits.assign((F ? F : 1) * c.n_words, 0u);
+    if (want_counts) c.counts.assign((F ? F : 1) * (F ? F : 1), 0);
+    check(voe_map_covis(h_, (int)F, app.data(), n.data(), (int)cap, (int)c.n_words, c.bits.data(), want_counts ? c.counts.data() : nullptr,
+                        &c.stats), "voe_map_covis");
+    return c;
+  }
+
+  //! the local window of frame `query` (voe_map_window) from the bit rows of covisibility(): the frames to free, the frames to
+  //! hold, the landmarks between them.  *n_rows: the frames' live rows (what the result's n_rows hands on for the window's
+  //! frames).  The result's n_rows and fixed go to bundle / adjust / cull over the SAME frames.
+  MapWindow window(const Covisibility& cov, int query, const WindowOptions& opt = WindowOptions(), const std::vector<int>* n_rows = nullptr) const {
+    const size_t F = cov.n_frames;
+    if (n_rows && n_rows->size() != F) throw Error(VO_ERR_INVALID_ARG, "DeviceMap::window: one row count per frame");
+    MapWindow w;
+    w.role.assign(F ? F : 1, 0); w.n_rows.assign(F ? F : 1, 0); w.fixed.assign(F ? F : 1, 1); w.order.assign(F ? F : 1, -1);
+    w.landmarks.assign(cov.n_words ? cov.n_words : 1, 0u);
+    int cap = 0;
+    if (n_rows) for (int v : *n_rows) cap = v > cap ? v : cap;
+    const voe_map_window_params prm{query, opt.k_free, opt.k_fixed, opt.min_shared};
+    check(voe_map_window(h_, (int)F, (int)cov.n_words, cov.bits.data(), n_rows ? n_rows->data() : nullptr, cap, &prm, w.role.data(),
+                         w.n_rows.data(), w.fixed.data(), w.order.data(), w.landmarks.data(), &w.stats), "voe_map_window");
+    w.role.resize(F); w.n_rows.resize(F); w.fixed.resize(F); w.order.resize(F);
+    return w;
   }
 
   //! the map's points and appearances in entry order

@@ -736,6 +736,66 @@ class Map:
                                     C.byref(st)))
         return remap[: st.n_src].copy(), st.as_dict()
 
+    # ---- covisibility of frames and the window chosen from it (voe_map_covis*, voe_map_window*, include/vo_map_covis.h) ----
+    def words(self):
+        """the 32-bit words a bit row needs for this map: enough for size_bound() entries, at least one"""
+        return max((self.size_bound() + 31) // 32, 1)
+
+    def covis_batch_dev(self, n_frames, d_app, app_stride, n_max, d_n, n_words, d_bits_out, d_counts_out, d_stats):
+        """voe_map_covis_batch_dev on device pointers (ints; d_n and d_counts_out may be None; the stride in rows): enqueues and
+        returns.  d_bits_out: n_frames x n_words x 4 bytes; d_counts_out: n_frames x n_frames x 4 bytes; d_stats: 32 bytes."""
+        v = lambda d: C.c_void_p(d) if d else None
+        _chk(self.lib.voe_map_covis_batch_dev(self.h, C.c_int(n_frames), v(d_app), C.c_size_t(app_stride), C.c_int(n_max), v(d_n),
+                                              C.c_int(n_words), v(d_bits_out), v(d_counts_out), v(d_stats)))
+
+    def covisibility(self, frames, want_counts=True, n_words=None):
+        """voe_map_covis: which entries every frame sees and how many every two frames share.  frames: [(uv, app)] as in refine,
+        or [app].  Returns dict(bits (F, W) uint32: bit e & 31 of word e >> 5 of row f is set when frame f sees entry e, counts
+        (F, F) int32 or None, stats dict)."""
+        apps = [_f32(f[1] if isinstance(f, (tuple, list)) else f, (-1, 10)) for f in frames]
+        F = len(apps)
+        n = np.array([len(a) for a in apps], np.int32)
+        cap = int(n.max()) if F else 0
+        app = np.zeros((max(F, 1), max(cap, 1), 10), np.float32)
+        for f, a in enumerate(apps):
+            app[f, : n[f]] = a
+        W = self.words() if n_words is None else int(n_words)
+        bits = np.zeros((max(F, 1), max(W, 1)), np.uint32)
+        counts = np.zeros((max(F, 1), max(F, 1)), np.int32) if want_counts else None
+        st = MapCovisStats()
+        _chk(self.lib.voe_map_covis(self.h, C.c_int(F), _ptr(app[:, :cap]) if cap else None, _ptr(n), C.c_int(cap), C.c_int(W), _ptr(bits),
+                                    _ptr(counts) if want_counts else None, C.byref(st)))
+        return dict(bits=bits, counts=counts, stats=st.as_dict())
+
+    def window_dev(self, n_frames, n_words, d_bits, d_n, n_max, params: "MapWindowParams", d_role_out, d_n_rows_out, d_fixed_out,
+                   d_order_out, d_union_out, d_stats):
+        """voe_map_window_dev on device pointers (ints; d_n, d_order_out and d_union_out may be None): enqueues and returns"""
+        v = lambda d: C.c_void_p(d) if d else None
+        _chk(self.lib.voe_map_window_dev(self.h, C.c_int(n_frames), C.c_int(n_words), v(d_bits), v(d_n), C.c_int(n_max), C.byref(params),
+                                         v(d_role_out), v(d_n_rows_out), v(d_fixed_out), v(d_order_out), v(d_union_out), v(d_stats)))
+
+    def window(self, bits, query, k_free=8, k_fixed=8, min_shared=15, n_rows=None, n_max=None):
+        """voe_map_window: the local window of frame `query` from the bit rows of covisibility().  n_rows: the frames' live rows
+        (what n_rows of the result hands on for the window's frames; default: n_max, itself 0 by default, for every frame).
+        Returns dict(role (F,) int32: MAP_WINDOW_ROLE names the codes, n_rows (F,) int32 and fixed (F,) uint8: what bundle /
+        adjust / cull take over the same frames, order (F,) int32, union (W,) uint32, stats dict: MAP_WINDOW_STATUS names
+        stats["status"])."""
+        bits = np.ascontiguousarray(np.asarray(bits, np.uint32))
+        if bits.ndim != 2:
+            raise ValueError("bits: (frames, words)")
+        F, W = bits.shape
+        n = None if n_rows is None else np.ascontiguousarray(np.asarray(n_rows, np.int32))
+        if n is not None and n.shape != (F,):
+            raise ValueError("one row count per frame")
+        cap = int(n_max) if n_max is not None else (int(n.max()) if n is not None and F else 0)
+        role, rows, order = np.full(max(F, 1), -1, np.int32), np.full(max(F, 1), -1, np.int32), np.full(max(F, 1), -2, np.int32)
+        fixed, union = np.full(max(F, 1), 255, np.uint8), np.zeros(max(W, 1), np.uint32)
+        st = MapWindowStats()
+        prm = MapWindowParams(int(query), int(k_free), int(k_fixed), int(min_shared))
+        _chk(self.lib.voe_map_window(self.h, C.c_int(F), C.c_int(W), _ptr(bits), _ptr(n) if n is not None else None, C.c_int(cap), C.byref(prm),
+                                     _ptr(role), _ptr(rows), _ptr(fixed), _ptr(order), _ptr(union), C.byref(st)))
+        return dict(role=role, n_rows=rows, fixed=fixed, order=order, union=union, stats=st.as_dict())
+
 
 class MapLocaliseStats(C.Structure):
     """vo_map_localise_stats (include/vo_hip.h)"""
@@ -885,6 +945,35 @@ assert C.sizeof(MapAlignParams) == 32 and C.sizeof(MapAlignStats) == 48 and C.si
 MAP_ALIGN_STATUS = ("OK", "FEW_MATCHES", "NO_HYPOTHESIS", "FEW_INLIERS")      # VOE_MAP_ALIGN_*
 MAP_ALIGN_MAX_REFITS = 16
 MAP_MERGE_TAKE_SRC, MAP_MERGE_KEEP_DST = 0, 1                                   # VOE_MAP_MERGE_*
+
+
+class MapCovisStats(C.Structure):
+    """voe_map_covis_stats (include/vo_map_covis.h)"""
+    _fields_ = [("n_frames", C.c_int32), ("n_entries", C.c_int32), ("n_hits", C.c_int32), ("n_seen", C.c_int32),
+                ("n_entries_seen", C.c_int32), ("reserved", C.c_int32 * 3)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_ if k != "reserved"}
+
+
+class MapWindowParams(C.Structure):
+    """voe_map_window_params (include/vo_map_covis.h)"""
+    _fields_ = [("query", C.c_int32), ("k_free", C.c_int32), ("k_fixed", C.c_int32), ("min_shared", C.c_int32)]
+
+
+class MapWindowStats(C.Structure):
+    """voe_map_window_stats (include/vo_map_covis.h)"""
+    _fields_ = [("status", C.c_int32), ("n_free", C.c_int32), ("n_fixed", C.c_int32), ("n_candidates", C.c_int32),
+                ("n_fixed_candidates", C.c_int32), ("n_points", C.c_int32), ("query_seen", C.c_int32), ("reserved", C.c_int32)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_ if k != "reserved"}
+
+
+assert C.sizeof(MapCovisStats) == 32 and C.sizeof(MapWindowParams) == 16 and C.sizeof(MapWindowStats) == 32
+MAP_COVIS_MAX_FRAMES = 4096                                                     # VOE_MAP_COVIS_MAX_FRAMES
+MAP_WINDOW_ROLE = ("OUTSIDE", "FREE", "FIXED")                                  # VOE_MAP_WINDOW_*
+MAP_WINDOW_STATUS = ("OK", "NO_FIXED", "QUERY_UNSEEN")
 
 
 def similarity_pose(T, S):

@@ -2235,6 +2235,8 @@ struct vo_map {
   DevBuf cull_ws;               // voe_map_cull*: verdict, remap, ranks, the staging area of the survivors (the lists live in ref_ws)
   DevBuf align_ws;              // voe_map_align* (on dst): gathered pairs, hypotheses, counts, the blocks' sums
   DevBuf merge_ws;              // voe_map_merge* (on dst): the lookup's entries, the staging area of the misses
+  DevBuf covis_ws;              // voe_map_covis*: the lookup's pairs, counts and entries, the population counts per frame and per block of words
+  DevBuf window_ws;             // voe_map_window*: the counts against the query row and against the union, the order, the union
 };
 
 constexpr int MAP_MAX_ENTRIES = 1 << 29;      // 2.5 x that many table slots still fit 32 bits
@@ -2327,7 +2329,7 @@ int vo_map_destroy(vo_map* m) {
   map_free_arrays(m->d);
   if (m->d.hdr) (void)hipFree(m->d.hdr);
   if (m->hist) (void)hipFree(m->hist);
-  m->scratch.release(); m->up_xyz.release(); m->up_app.release(); m->look_ws.release(); m->loc_ws.release(); m->ref_ws.release(); m->pose_ws.release(); m->bundle_ws.release(); m->cull_ws.release(); m->align_ws.release(); m->merge_ws.release();
+  m->scratch.release(); m->up_xyz.release(); m->up_app.release(); m->look_ws.release(); m->loc_ws.release(); m->ref_ws.release(); m->pose_ws.release(); m->bundle_ws.release(); m->cull_ws.release(); m->align_ws.release(); m->merge_ws.release(); m->covis_ws.release(); m->window_ws.release();
   if (m->solver) (void)vo_picp_destroy(m->solver);
   delete m;
   return VO_OK;
@@ -3264,6 +3266,151 @@ int voe_map_merge(vo_map* dst, vo_map* src, const float S16[16], int policy, int
   if (remap_out && size > 0) VO_HIP_CHECK(hipMemcpyAsync(remap_out, c->out[0].p, sizeof(int32_t) * (size_t)size, hipMemcpyDeviceToHost, c->stream));
   VO_HIP_CHECK(hipStreamSynchronize(c->stream));
   if (!dst->replayable) dst->size_ub = stats_out->n_dst_after;
+  return VO_OK;
+}
+
+// ---- covisibility of frames and the window chosen from it (map_covis.hip; include/vo_map_covis.h) --------------------------
+static_assert(sizeof(voe_map_covis_stats) == 32 && sizeof(voe_map_window_params) == 16 && sizeof(voe_map_window_stats) == 32,
+              "the records of include/vo_map_covis.h as the kernels write them");
+
+// the refusals that need no map come first: they are the same on a machine without a device
+// (dev: d_stats is a device pointer, written as 8-byte pieces)
+static int covis_check(const char* fn, int n_frames, int n_words, const void* d_bits, const void* d_stats, bool dev) {
+  if (n_frames < 1 || n_frames > VOE_MAP_COVIS_MAX_FRAMES)
+    return fail(VO_ERR_INVALID_ARG, "%s: n_frames %d outside 1 .. %d", fn, n_frames, VOE_MAP_COVIS_MAX_FRAMES);
+  if (n_words < 1) return fail(VO_ERR_INVALID_ARG, "%s: n_words must be at least 1", fn);
+  if (!d_bits || !d_stats) return fail(VO_ERR_INVALID_ARG, "%s: null argument", fn);
+  if (dev && !aligned8(d_stats)) return fail(VO_ERR_INVALID_ARG, "%s: d_stats must be 8-byte aligned", fn);
+  return VO_OK;
+}
+
+int voe_map_covis_batch_dev(vo_map* m, int n_frames, const float* d_app, size_t app_stride, int n_max, const int* d_n, int n_words,
+                            uint32_t* d_bits_out, int32_t* d_counts_out, voe_map_covis_stats* d_stats) {
+  const char* fn = "voe_map_covis_batch_dev";
+  if (int r = covis_check(fn, n_frames, n_words, d_bits_out, d_stats, true)) return r;
+  VO_MAP_LIVE(m);
+  vo_ctx* c = m->ctx;
+  // the lookup's own refusals, before anything is sized (its pair and count arrays are the workspace's: d_app and d_stats stand
+  // in for them here, null and aligned exactly when those are)
+  if (int r = map_lookup_check(m, n_frames, d_app, app_stride, n_max, reinterpret_cast<const int32_t*>(d_app), reinterpret_cast<const int*>(d_stats), nullptr))
+    return r;
+  if ((long long)32 * n_words < (long long)map_bound(m))
+    return fail(VO_ERR_INVALID_ARG, "%s: %d words hold fewer bits than the map's size bound %d", fn, n_words, map_bound(m));
+  MapCovisWs w = map_covis_layout(nullptr, n_frames, n_max, n_words);
+  const size_t look_need = sizeof(int) * map_lookup_scratch_ints(n_max, n_frames, false);
+  if (c->capturing && (m->covis_ws.cap < w.bytes || (n_max > 0 && m->look_ws.cap < look_need)))      // (before the lookup is enqueued)
+    return fail(VO_ERR_NOT_READY, "%s: the workspace would have to grow inside a graph capture (make one call with %d frames of n_max %d "
+                                  "and %d words on this map before capturing)", fn, n_frames, n_max, n_words);
+  if (int r = set_device(c)) return r;
+  VO_HIP_CHECK(m->covis_ws.ensure(w.bytes, c->stream));
+  w = map_covis_layout(m->covis_ws.p, n_frames, n_max, n_words);
+  if (n_max > 0)                                              // the one lookup of the call, through the public entry point
+    if (int r = vo_map_lookup_batch_dev(m, n_frames, d_app, app_stride, n_max, d_n, w.pairs, w.n_hits, nullptr, nullptr, w.ent)) return r;
+  MapCovisArgs a{};
+  a.w = w; a.hdr = m->d.hdr; a.cap = m->d.cap;
+  a.n_frames = n_frames; a.n_max = n_max; a.n_words = n_words; a.d_n = d_n;
+  a.bits = d_bits_out; a.counts = d_counts_out; a.stats = d_stats;
+  VO_HIP_CHECK(launch_map_covis(c->stream, a));
+  return VO_OK;
+}
+
+int voe_map_covis(vo_map* m, int n_frames, const float* app, const int* n_rows, int n_max, int n_words, uint32_t* bits_out,
+                  int32_t* counts_out, voe_map_covis_stats* stats_out) {
+  const char* fn = "voe_map_covis";
+  if (int r = covis_check(fn, n_frames, n_words, bits_out, stats_out, false)) return r;
+  VO_MAP_LIVE(m);
+  vo_ctx* c = m->ctx;
+  VO_NOT_CAPTURING(c);
+  VO_REQUIRE(n_max >= 0 && (n_max == 0 || app), "bad frames");
+  VO_REQUIRE((long long)n_max * n_frames <= (1ll << 30), "more than 2^30 rows in one call");
+  if (int r = set_device(c)) return r;
+  const size_t F = (size_t)n_frames, W = (size_t)n_words;
+  if (int r = upload(c, c->in[1], app, sizeof(float) * 10 * F * (size_t)n_max)) return r;
+  if (n_rows)
+    if (int r = upload(c, c->in[3], n_rows, sizeof(int) * F)) return r;
+  int size = 0;
+  if (int r = vo_map_size(m, &size)) return r;                // (waits: the host arrays may go away after the call)
+  VO_HIP_CHECK(c->out[0].ensure(sizeof(uint32_t) * F * W, c->stream));
+  if (counts_out) VO_HIP_CHECK(c->out[1].ensure(sizeof(int32_t) * F * F, c->stream));
+  VO_HIP_CHECK(c->out[2].ensure(sizeof(voe_map_covis_stats) + 16, c->stream));
+  if (int r = voe_map_covis_batch_dev(m, n_frames, c->in[1].as<float>(), (size_t)n_max, n_max, n_rows ? c->in[3].as<int>() : nullptr, n_words,
+                                      c->out[0].as<uint32_t>(), counts_out ? c->out[1].as<int32_t>() : nullptr,
+                                      c->out[2].as<voe_map_covis_stats>()))
+    return r;
+  VO_HIP_CHECK(hipMemcpyAsync(bits_out, c->out[0].p, sizeof(uint32_t) * F * W, hipMemcpyDeviceToHost, c->stream));
+  if (counts_out) VO_HIP_CHECK(hipMemcpyAsync(counts_out, c->out[1].p, sizeof(int32_t) * F * F, hipMemcpyDeviceToHost, c->stream));
+  VO_HIP_CHECK(hipMemcpyAsync(stats_out, c->out[2].p, sizeof(voe_map_covis_stats), hipMemcpyDeviceToHost, c->stream));
+  VO_HIP_CHECK(hipStreamSynchronize(c->stream));
+  return VO_OK;
+}
+
+static int window_check(const char* fn, int n_frames, int n_words, const void* d_bits, int n_max, const voe_map_window_params* p,
+                        const void* d_role, const void* d_n_rows_out, const void* d_fixed, const void* d_stats, bool dev) {
+  if (int r = covis_check(fn, n_frames, n_words, d_bits, d_stats, dev)) return r;
+  if (!(p && d_role && d_n_rows_out && d_fixed)) return fail(VO_ERR_INVALID_ARG, "%s: null argument", fn);
+  if (n_max < 0) return fail(VO_ERR_INVALID_ARG, "%s: negative row count", fn);
+  if (p->query < 0 || p->query >= n_frames) return fail(VO_ERR_INVALID_ARG, "%s: query %d outside the %d frames", fn, p->query, n_frames);
+  if (p->k_free < 1 || p->k_free > n_frames) return fail(VO_ERR_INVALID_ARG, "%s: k_free outside 1 .. n_frames", fn);
+  if (p->k_fixed < 0 || p->k_fixed > n_frames) return fail(VO_ERR_INVALID_ARG, "%s: k_fixed outside 0 .. n_frames", fn);
+  if (p->min_shared < 1) return fail(VO_ERR_INVALID_ARG, "%s: min_shared must be at least 1", fn);
+  return VO_OK;
+}
+
+int voe_map_window_dev(vo_map* m, int n_frames, int n_words, const uint32_t* d_bits, const int* d_n, int n_max,
+                       const voe_map_window_params* p, int32_t* d_role_out, int* d_n_rows_out, uint8_t* d_fixed_out, int32_t* d_order_out,
+                       uint32_t* d_union_out, voe_map_window_stats* d_stats) {
+  const char* fn = "voe_map_window_dev";
+  if (int r = window_check(fn, n_frames, n_words, d_bits, n_max, p, d_role_out, d_n_rows_out, d_fixed_out, d_stats, true)) return r;
+  VO_MAP_LIVE(m);
+  vo_ctx* c = m->ctx;
+  MapWindowWs w = map_window_layout(nullptr, n_frames, n_words);
+  if (c->capturing && m->window_ws.cap < w.bytes)
+    return fail(VO_ERR_NOT_READY, "%s: the workspace would have to grow inside a graph capture (make one call with %d frames and %d words "
+                                  "on this map before capturing)", fn, n_frames, n_words);
+  if (int r = set_device(c)) return r;
+  VO_HIP_CHECK(m->window_ws.ensure(w.bytes, c->stream));
+  MapWindowArgs a{};
+  a.w = map_window_layout(m->window_ws.p, n_frames, n_words);
+  a.n_frames = n_frames; a.n_words = n_words; a.n_max = n_max; a.bits = d_bits; a.d_n = d_n;
+  a.query = p->query; a.k_free = p->k_free; a.k_fixed = p->k_fixed; a.min_shared = p->min_shared;
+  a.role = d_role_out; a.n_rows_out = d_n_rows_out; a.fixed_out = d_fixed_out;
+  a.order = d_order_out ? d_order_out : a.w.order;
+  a.uni = d_union_out ? d_union_out : a.w.uni;
+  a.stats = d_stats;
+  VO_HIP_CHECK(launch_map_window(c->stream, a));
+  return VO_OK;
+}
+
+int voe_map_window(vo_map* m, int n_frames, int n_words, const uint32_t* bits, const int* n_rows, int n_max,
+                   const voe_map_window_params* p, int32_t* role_out, int* n_rows_out, uint8_t* fixed_out, int32_t* order_out,
+                   uint32_t* union_out, voe_map_window_stats* stats_out) {
+  const char* fn = "voe_map_window";
+  if (int r = window_check(fn, n_frames, n_words, bits, n_max, p, role_out, n_rows_out, fixed_out, stats_out, false)) return r;
+  VO_MAP_LIVE(m);
+  vo_ctx* c = m->ctx;
+  VO_NOT_CAPTURING(c);
+  if (int r = set_device(c)) return r;
+  const size_t F = (size_t)n_frames, W = (size_t)n_words;
+  if (int r = upload(c, c->in[0], bits, sizeof(uint32_t) * F * W)) return r;
+  if (n_rows)
+    if (int r = upload(c, c->in[3], n_rows, sizeof(int) * F)) return r;
+  // one block of outputs: role, n_rows, order [F] ints each, the union [W], the statistics, the mask [F] bytes
+  const size_t o_role = 0, o_rows = up256(4 * F), o_order = o_rows + up256(4 * F), o_union = o_order + up256(4 * F), o_stats = o_union + up256(4 * W),
+               o_fixed = o_stats + 256, total = o_fixed + up256(F);
+  VO_HIP_CHECK(c->out[0].ensure(total, c->stream));
+  char* d = c->out[0].as<char>();
+  if (int r = voe_map_window_dev(m, n_frames, n_words, c->in[0].as<uint32_t>(), n_rows ? c->in[3].as<int>() : nullptr, n_max, p,
+                                 reinterpret_cast<int32_t*>(d + o_role), reinterpret_cast<int*>(d + o_rows), reinterpret_cast<uint8_t*>(d + o_fixed),
+                                 order_out ? reinterpret_cast<int32_t*>(d + o_order) : nullptr,
+                                 union_out ? reinterpret_cast<uint32_t*>(d + o_union) : nullptr, reinterpret_cast<voe_map_window_stats*>(d + o_stats)))
+    return r;
+  VO_HIP_CHECK(hipMemcpyAsync(role_out, d + o_role, 4 * F, hipMemcpyDeviceToHost, c->stream));
+  VO_HIP_CHECK(hipMemcpyAsync(n_rows_out, d + o_rows, 4 * F, hipMemcpyDeviceToHost, c->stream));
+  VO_HIP_CHECK(hipMemcpyAsync(fixed_out, d + o_fixed, F, hipMemcpyDeviceToHost, c->stream));
+  if (order_out) VO_HIP_CHECK(hipMemcpyAsync(order_out, d + o_order, 4 * F, hipMemcpyDeviceToHost, c->stream));
+  if (union_out) VO_HIP_CHECK(hipMemcpyAsync(union_out, d + o_union, 4 * W, hipMemcpyDeviceToHost, c->stream));
+  VO_HIP_CHECK(hipMemcpyAsync(stats_out, d + o_stats, sizeof(voe_map_window_stats), hipMemcpyDeviceToHost, c->stream));
+  VO_HIP_CHECK(hipStreamSynchronize(c->stream));
   return VO_OK;
 }
 

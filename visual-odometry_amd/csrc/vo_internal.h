@@ -647,6 +647,51 @@ struct MapCullArgs {
 hipError_t launch_map_cull(hipStream_t st, const MapCullArgs& a, int n_cu);
 hipError_t launch_map_cull_stats(hipStream_t st, const MapCullArgs& a);
 
+// ---- covisibility of frames and the window chosen from it (map_covis.hip, voe_map_covis* / voe_map_window*;
+// include/vo_map_covis.h holds the rules).  All integers. ----
+struct MapCovisWs {
+  int32_t* pairs;                       // [n_frames][n_max][2] the lookup's compacted hits (not read afterwards)
+  int32_t* ent;                         // [n_frames][n_max] the lookup's entry per position
+  int* n_hits;                          // [n_frames] the lookup's counts
+  int* row_pop;                         // [n_frames] entries a frame sees
+  int* part;                            // [ceil(n_words / 256)] entries seen by any frame, per block of words
+  size_t bytes;
+};
+MapCovisWs map_covis_layout(void* base, int n_frames, int n_max, int n_words);
+struct MapCovisArgs {
+  MapCovisWs w;
+  const int* hdr; int cap;              // the map's size word and capacity
+  int n_frames, n_max, n_words;
+  const int* d_n;                       // [n_frames] or null
+  uint32_t* bits;                       // [n_frames][n_words]
+  int32_t* counts;                      // [n_frames][n_frames] or null
+  void* stats;                          // voe_map_covis_stats
+};
+// after the lookup has filled w.ent and w.n_hits: memset of the bits, bit pass, count pass (when counts are wanted), the rows'
+// population counts, the union's, the statistics
+hipError_t launch_map_covis(hipStream_t st, const MapCovisArgs& a);
+struct MapWindowWs {
+  int* cnt;                             // [n_frames] c(g), then s(h)
+  int32_t* order;                       // [n_frames] (the caller's array takes its place when given)
+  uint32_t* uni;                        // [n_words] (likewise)
+  int* part;                            // [ceil(n_words / 256)] population count of the union per block of words
+  int* ctl;                             // [0] n_free [1] n_candidates [2] query_seen
+  size_t bytes;
+};
+MapWindowWs map_window_layout(void* base, int n_frames, int n_words);
+struct MapWindowArgs {
+  MapWindowWs w;
+  int n_frames, n_words, n_max;
+  const uint32_t* bits;
+  const int* d_n;                       // [n_frames] or null
+  int query, k_free, k_fixed, min_shared;
+  int32_t* role; int* n_rows_out; uint8_t* fixed_out;
+  int32_t* order;                       // the caller's or the workspace's
+  uint32_t* uni;                        // the caller's or the workspace's
+  void* stats;                          // voe_map_window_stats
+};
+hipError_t launch_map_window(hipStream_t st, const MapWindowArgs& a);
+
 // ---- two maps: similarity by 3-point RANSAC and the merge (map_align.hip, voe_map_align* / voe_map_merge*; include/vo_map_align.h
 // holds the rules) ----
 constexpr int ALIGN_FS = 16;            // floats per model: M = c R column-major [0, 9), t [9, 12), [12] = 1 valid / 0 invalid
