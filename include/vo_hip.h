@@ -212,7 +212,9 @@ int vo_picp_get_pose_dev(vo_picp *s, float *d_T16);             /* async copy on
  * Behind those four ints lie two counters of the handle's tail launches and then, written by tail launches only (so they
  * describe the last solve that had one: check [0] above first): how that launch closed the solve -- 1 from partial rows an
  * earlier launch had left in the ring, 2 after computing the last round's rows again (VO_PICP_TAIL_RING=0 forces this), 3 at
- * the end of its loop of real rounds -- and the M it ran with (rounds 1 .. M had launches of their own; a handle lowers M to
+ * the end of its loop of real rounds, 4 in the round that computed the repeating pose (the early form of the launch, whose
+ * workgroups find the repeat themselves: a handle takes it behind 32 consecutive solves that repeated, VO_PICP_TAIL_EARLY=0 in
+ * the environment keeps it from that, =1 adds the form to a forced VO_PICP_TAIL_FROM; read per call) -- and the M it ran with (rounds 1 .. M had launches of their own; a handle lowers M to
  * where its solves repeat, VO_PICP_TAIL_FROM sets it per call).  Such a solve has no finishing launch. */
 int vo_picp_pose_dev_ptr(vo_picp *s, const float **d_T16);
 int vo_picp_get_stats(vo_picp *s, float *chi_inliers, float *chi_outliers, int *num_inliers); /* :44-50 */

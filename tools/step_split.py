@@ -48,6 +48,9 @@ def main():
     is_round = lambda n: n.startswith(("picp_round_kernel<true, false", "picp_tally_round_kernel<false"))
     # the one launch that stands for the rounds behind round M (picp_tail_kernel): between the last PRE round and the finish
     is_tail = lambda n: n.startswith("picp_tail_kernel")
+    # its early form (picp_tail_kernel<PINHOLE, KEEP, true>) computes the repeating pose, finds the repeat and closes in one
+    # launch: the headline step is then round 0, nine round launches and the tail -- 11 launches against 14
+    is_early_tail = lambda n: is_tail(n) and n.replace(" ", "").endswith(",true>")
     # the tail launch closes the solve where the launch behind it is not a finishing launch
     tail_next = [rows[k + 1][2] for k in range(len(rows) - 1) if is_tail(rows[k][2])]
     tail_closes = bool(tail_next) and sum(1 for n in tail_next if not is_finish(n)) * 2 > len(tail_next)
@@ -65,8 +68,9 @@ def main():
     med = lambda xs: statistics.median(xs) / 1e3 if xs else float("nan")
     first_round = next(i for i, n in enumerate(common) if is_round(n))
     res = {"steps_used": len(steps), "launches_per_step": len(common), "tail_launch_closes_the_step": tail_closes,
+           "tail_form": "early" if any(is_early_tail(n) for n in common) else ("plain" if any(is_tail(n) for n in common) else "none"),
            "launch_sequence": list(common), "fixed": [], "unit": "us"}
-    print("%d steps of %d launches each" % (len(steps), len(common)))
+    print("%d steps of %d launches each (tail launch: %s)" % (len(steps), len(common), res["tail_form"]))
     print("fixed part (end of the finishing launch -> start of the first PRE round):")
     fixed_total = []
     for k in range(first_round + 1):

@@ -295,13 +295,14 @@ class PICPSolver:
         self.ctx.d2h(blk, p.value + 16 * 4 + 5 * 4 + 64 * 12 * 4)
         return bool(blk[0]), int(blk[1]), bool(blk[2])
 
-    TAIL_CLOSE = ("none", "ring", "recomputed", "looped")
+    TAIL_CLOSE = ("none", "ring", "recomputed", "looped", "early")
 
     def tailCloseInfo(self):
         """(how the last solve was closed, the M it ran with): "none" and 0 where the solve had no tail launch and a finishing
         launch closed it; "ring": the tail launch's workgroup 0 closed it from the partial rows an earlier launch had left in
         the ring; "recomputed": all workgroups linearised the last round again first; "looped": the launch ran the last round
-        at the end of its loop.  M: rounds 1 .. M had launches of their own.  The two words lie behind the tail words and the
+        at the end of its loop; "early": the launch, in its early form (VO_PICP_TAIL_EARLY, or the handle's own choice),
+        found the repeat in the round that computed the repeating pose and closed the solve there.  M: rounds 1 .. M had launches of their own.  The two words lie behind the tail words and the
         two tally counts (csrc/vo_internal.h, PicpTailClose); synchronises; reads in place like tailInfo()."""
         p = C.c_void_p()
         _chk(self.lib.vo_picp_pose_dev_ptr(self.h, C.byref(p)))

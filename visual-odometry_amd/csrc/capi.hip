@@ -701,10 +701,20 @@ static bool picp_cycle_enabled() { const char* e = getenv("VO_PICP_CYCLE"); retu
 // ran real rounds puts M back to PICP_TAIL_FROM and the device starts the run again; the form goes off only where the last
 // in-launch round lay beyond PICP_TAIL_FROM, i.e. where a tail at the default M would have looped as well.  M is never
 // lowered for a probe, and eligibility is judged with the M chosen.  Graphs are keyed by M; none of this waits for the device.
-static int picp_tail_policy(vo_picp* s, int n_iters, bool cycle) {
+//
+// The early form (picp.hip, picp_tail_kernel<.., EARLY>) is a further tier on top of the learned M: its tail launch is the one
+// that COMPUTES the repeating pose and closes the solve in the same round, so it starts at M = largest detected_at - 2 -- no
+// margin round, and no launch that only finds out.  A solve that repeats earlier is caught by an ordinary detector and closes
+// from the ring at the start as ever; one that repeats later runs real rounds inside the launch, and the rule above applies: M
+// back to PICP_TAIL_FROM, the run starts again.  Without a margin a miss is likelier, so the tier asks for
+// PICP_TAIL_EARLY_LEARN witnesses.  An early close counts as a skip-path launch in the report.  VO_PICP_TAIL_EARLY=0 keeps the
+// host from choosing the form, VO_PICP_TAIL_EARLY=1 adds it to a forced M (read per call; *early is part of the graph's key).
+static int picp_tail_policy(vo_picp* s, int n_iters, bool cycle, bool* early) {
   bool forced = false;
+  *early = false;
+  const int early_env = picp_tail_early_env();
   const int m = picp_tail_from(s->grid, n_iters, cycle, s->ctx->n_cu, &forced);
-  if (forced) return m;
+  if (forced) { *early = m > 0 && early_env == 1; return m; }
   // (not eligible at the default M and the form not on: no M this handle may choose would make it eligible -- nothing to look at)
   if (m == 0 && !s->tail_on) return 0;
   if (!cycle || s->ctx->capturing || !s->tail_report) return 0;
@@ -738,6 +748,10 @@ static int picp_tail_policy(vo_picp* s, int n_iters, bool cycle) {
     if (!looped) {
       const int run = (run_word >> 16) & 0xffff, det = run_word & 0xffff;
       if (run >= PICP_TAIL_LEARN && det >= 1) s->tail_m = det + 1 < PICP_TAIL_FROM ? det + 1 : PICP_TAIL_FROM;
+      if (early_env != 0 && run >= PICP_TAIL_EARLY_LEARN && det >= 3) {
+        const int me = picp_tail_from(s->grid, n_iters, cycle, s->ctx->n_cu, nullptr, det - 2 < PICP_TAIL_FROM ? det - 2 : PICP_TAIL_FROM);
+        if (me > 0) { *early = true; return me; }
+      }
     }
     return picp_tail_from(s->grid, n_iters, cycle, s->ctx->n_cu, nullptr, s->tail_m);
   }
@@ -880,7 +894,8 @@ static int picp_enqueue(vo_picp* s, int n_iters, bool lazy = false) {
     return VO_OK;
   }
   // rounds behind this index share one launch (0: every round has its own); part of the graph's key
-  const int tail_from = picp_tail_policy(s, n_iters, cycle);
+  bool tail_early = false;
+  const int tail_from = picp_tail_policy(s, n_iters, cycle, &tail_early);
   // (VO_PICP_TAIL_RING=0, read per call: the tail launch recomputes the last round's rows where the ring holds them)
   const bool tail_ring = tail_from == 0 || picp_tail_ring_enabled();
   ++s->solves;
@@ -890,14 +905,14 @@ static int picp_enqueue(vo_picp* s, int n_iters, bool lazy = false) {
     // solve shape, whatever it is replayed behind.  (Round 0 as the graph's first node measured the same: DESIGN.md section 8.)
     const int part = picp_rounds_chain(s->grid) ? PICP_AFTER_ROUND0 : PICP_WHOLE;
     auto key = std::make_tuple(n_iters, s->grid, (const void*)pk.base, pk.cap, (const void*)partials,
-                               (pinhole ? 1 : 0) | (keep ? 2 : 0) | (cycle ? 4 : 0) | (tail_ring ? 0 : 8) | (tail_from << 4));
+                               (pinhole ? 1 : 0) | (keep ? 2 : 0) | (cycle ? 4 : 0) | (tail_ring ? 0 : 8) | (tail_early ? 16 : 0) | (tail_from << 5));
     auto it = s->graphs.find(key);
     if (it == s->graphs.end()) {
       hipGraph_t graph = nullptr;
       hipGraphExec_t exec = nullptr;
       hipError_t e = hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal);
       if (e == hipSuccess) {
-        hipError_t el = launch_picp_rounds(c->stream, s->d_params, s->d_state, pk, partials, s->grid, n_iters, pinhole, keep, gather, part, cycle, tail_from, s->tail_report, tail_ring);
+        hipError_t el = launch_picp_rounds(c->stream, s->d_params, s->d_state, pk, partials, s->grid, n_iters, pinhole, keep, gather, part, cycle, tail_from, s->tail_report, tail_ring, tail_early);
         e = hipStreamEndCapture(c->stream, &graph);
         if (e == hipSuccess && el != hipSuccess) e = el;
       }
@@ -923,13 +938,14 @@ static int picp_enqueue(vo_picp* s, int n_iters, bool lazy = false) {
         // VO_PICP_TAIL_LOG=1: which solve of the handle paid for a capture, and of which form (stderr; a measurement checks
         // with it that the graph of a learned M is captured inside its warm-up)
         if (const char* lg = getenv("VO_PICP_TAIL_LOG")) if (lg[0] == '1')
-          fprintf(stderr, "vo_picp: graph of %d rounds, tail_from %d, captured at solve %llu of the handle\n", n_iters, tail_from, s->solves);
+          fprintf(stderr, "vo_picp: graph of %d rounds, tail_from %d%s, captured at solve %llu of the handle\n", n_iters, tail_from,
+                  tail_early ? " (early form)" : "", s->solves);
       }
     }
     if (s->use_graph && it != s->graphs.end()) {
       hipError_t e = hipSuccess;
       if (part == PICP_AFTER_ROUND0)
-        e = launch_picp_rounds(c->stream, s->d_params, s->d_state, pk, partials, s->grid, n_iters, pinhole, keep, gather, PICP_ROUND0, cycle, tail_from, s->tail_report, tail_ring);
+        e = launch_picp_rounds(c->stream, s->d_params, s->d_state, pk, partials, s->grid, n_iters, pinhole, keep, gather, PICP_ROUND0, cycle, tail_from, s->tail_report, tail_ring, tail_early);
       if (e == hipSuccess) e = hipGraphLaunch(it->second, c->stream);
       if (e != hipSuccess && gather.on) s->packed_valid = false;
       VO_HIP_CHECK(e);
@@ -938,7 +954,7 @@ static int picp_enqueue(vo_picp* s, int n_iters, bool lazy = false) {
   }
   {
     const hipError_t e = launch_picp_rounds(c->stream, s->d_params, s->d_state, pk, partials, s->grid, n_iters, pinhole, keep, gather,
-                                            PICP_WHOLE, cycle, tail_from, s->tail_report, tail_ring);
+                                            PICP_WHOLE, cycle, tail_from, s->tail_report, tail_ring, tail_early);
     if (e != hipSuccess && gather.on) s->packed_valid = false;
     VO_HIP_CHECK(e);
   }

@@ -824,7 +824,24 @@ __device__ __forceinline__ bool picp_tail_arrive(PicpTail* tl, int goal, int* s_
 }
 
 // `ring`: 0 forces the RECOMPUTED closing where RING would do (VO_PICP_TAIL_RING=0)
-template <bool PINHOLE, bool KEEP>
+//
+// EARLY: the form that finds the repeat itself.  The detector of launch `it` compares the pose the launch BEFORE it stored, so
+// a repeat pose k = pose j is known one launch late, and a tail launch that starts at the repeat still runs round k in full,
+// meets at the barrier and runs round k + 1's start before anybody knows.  In this form every workgroup of in-launch round `it`
+// -- the detector's included, which sums the rows and solves like the others and has nothing to linearise -- compares pose `it`,
+// just computed, and pose it - 1 with the history (picp_tail_first_repeat, vo_internal.h): lane l holds the pose of round
+// it - 1 - l, fetched beside the row loads.  hist[it - 1] is in flight from the detector of this very round, so lane 0 takes the
+// old pose instead; hist[<= it - 2] is complete: stored by an earlier launch, or by the detector workgroup of an earlier round of
+// this launch in front of the loop's barrier, on which it arrives like every other workgroup.  The comparison is the same in
+// every workgroup, nobody waits for anybody.  On a repeat with a launch left to skip (picp_cycle_skips: exactly where the
+// launch-per-round solve skips) workgroup 0 stores the control block as the detector of launch k + 1 would have, and the
+// launch goes on as it does from state SKIP, with skip_from = k + 2: closed by workgroup 0 from the ring -- from the sums, old
+// and new pose already in hand where target = it - 1, the rows this round has just summed --, or recomputed by all.
+// What a slower workgroup of the same round may still be reading is left alone: pose it - 1 comes out of registers behind the
+// first in-launch round; in the first one it is read from pose[M % PICP_SLOTS], so the round does not act where that is slot 0
+// (the finished pose's; the loop path takes over) and leaves the copy of hist[target] into the slot of round `last` out where
+// that is the same slot (nothing reads it behind a closed solve); recomputed rows go to slot it % PICP_SLOTS, this round's own.
+template <bool PINHOLE, bool KEEP, bool EARLY = false>
 __global__ __launch_bounds__(PICP_BLOCK) void picp_tail_kernel(const PicpParams* __restrict__ P, PicpState* S, float* pk_base,
                                                                size_t pk_cap, float* partials, int first, int nb, int last,
                                                                int* report, int ring) {
@@ -865,32 +882,57 @@ __global__ __launch_bounds__(PICP_BLOCK) void picp_tail_kernel(const PicpParams*
   int real = 0, goal = 0;
   int how = PICP_CLOSE_LOOPED, close_slot = last & (PICP_SLOTS - 1);
   Pose Tl{};                                                // the pose of round `last`: the closing's old pose
+  // EARLY: the round that found the repeat (early_hit), the launch that would have (early_d); closed without a wait
+  // (early_ring), from what that round left in registers (inhand: its sums, its new pose; Told: the pose it started from)
+  bool early_hit = false, early_ring = false, inhand = false;
+  int early_it = 0, early_d = 0;
+  int det0 = EARLY ? S->cyc.detected_at : 0;                // (the detector workgroup's: a repeat has been reported already)
+  float k_tsum = 0.f;
+  Pose k_Tn{}, Told{};
   for (int it = first;;) {
-    const bool from_hist = it >= skip_from;
+    const bool from_hist = it >= skip_from || (EARLY && early_hit);
     if (from_hist) it = last;
-    if (detector) {
+    if (!EARLY && detector) {
       if (from_hist) return;
       picp_cycle_detect(S, it, last);
     } else {
+      if (EARLY && detector && from_hist) return;
       Pose T;
       if (from_hist) {
         // the pose of round `last` has occurred before: hist[target] stands for rows, sums and tail
-        const Pose Th = load_pose12(S->hist[target & (PICP_HIST - 1)]);
-        if (tid == 0 && blockIdx.x == 0) store_pose12(S->pose[it & (PICP_SLOTS - 1)], Th);
+        // (EARLY, target = the round before the one that found the repeat: that entry is in flight, the old pose is in hand)
+        Pose Th;
+        if (EARLY && early_hit && target == early_it - 1) Th = Told;
+        else Th = load_pose12(S->hist[target & (PICP_HIST - 1)]);
+        const bool slot_in_use = EARLY && early_hit && early_it == first && ((last ^ (early_it - 1)) & (PICP_SLOTS - 1)) == 0;
+        if (tid == 0 && blockIdx.x == 0 && !slot_in_use) store_pose12(S->pose[it & (PICP_SLOTS - 1)], Th);
         T = uniform_pose(Th);
         Tl = T;
         // ... and the rows launch `target` stored with that pose stand for the rows of round `last` (picp_tail_ring_holds): the
         // same in every workgroup, the control word is read behind a kernel boundary or behind the barrier
         if (ring != 0 && picp_tail_ring_holds(skip_from, target)) {
           if (blockIdx.x != 0) return;
-          how = PICP_CLOSE_RING;
+          how = EARLY && early_hit ? PICP_CLOSE_EARLY : PICP_CLOSE_RING;
           close_slot = target & (PICP_SLOTS - 1);
+          if (EARLY && early_hit) { early_ring = true; inhand = target == early_it - 1; }
           break;
         }
-        how = PICP_CLOSE_RECOMPUTED;
+        how = EARLY && early_hit ? PICP_CLOSE_EARLY : PICP_CLOSE_RECOMPUTED;
+        if (EARLY && early_hit) close_slot = early_it & (PICP_SLOTS - 1);
       } else {
         // the rows of round it - 1: thread (g = tid / 8, q = tid % 8) sums quad q of rows g + 32 j of every pass of 256 rows
         const char* prev = reinterpret_cast<const char*>(rows_mine + (size_t)((it - 1) & (PICP_SLOTS - 1)) * slot_floats);
+        // EARLY: this lane's history entry, the pose of round it - 1 - lane, asked for in front of the rows (vector loads: an
+        // opaque zero in the address); lane 0, whose entry is in flight, asks for lane 1's and takes the old pose below
+        int he[12], op[12];
+        int vz = 0;
+        if (EARLY) {
+          asm volatile("" : "+v"(vz));
+          const int r = lane == 0 ? it - 2 : it - 1 - lane;
+          const int* ent = reinterpret_cast<const int*>(S->hist[(r > 0 ? r : 0) & (PICP_HIST - 1)]) + vz;
+#pragma unroll
+          for (int q = 0; q < 12; ++q) he[q] = ent[q];
+        }
         float4 psum = make_float4(0.f, 0.f, 0.f, 0.f);
         for (int b0 = 0; b0 < nb; b0 += 256) {
           float4 r[NJ];
@@ -901,38 +943,117 @@ __global__ __launch_bounds__(PICP_BLOCK) void picp_tail_kernel(const PicpParams*
           for (int j = 0; j < NJ; ++j) { psum.x += r[j].x; psum.y += r[j].y; psum.z += r[j].z; psum.w += r[j].w; }
         }
         const float* pp = S->pose[(it - 1) & (PICP_SLOTS - 1)] + c3;
-        const float pb0 = pp[0], pb1 = pp[1], pb2 = pp[2];
+        float pb0, pb1, pb2;
+        if (EARLY && it > first) {
+          // behind the first in-launch round the old pose is the one this workgroup computed: the same bits, and no read of a
+          // slot that a workgroup which has already found the repeat may be storing the finished pose into
+          pose_lane_operands(Tl, pb0, pb1, pb2);
+#pragma unroll
+          for (int q = 0; q < 12; ++q) op[q] = __float_as_int(q < 9 ? Tl.R[q] : Tl.t[q - 9]);
+        } else {
+          pb0 = pp[0]; pb1 = pp[1]; pb2 = pp[2];
+          if (EARLY) {
+            const int* po = reinterpret_cast<const int*>(S->pose[(it - 1) & (PICP_SLOTS - 1)]) + vz;
+#pragma unroll
+            for (int q = 0; q < 12; ++q) op[q] = po[q];
+          }
+        }
+        // EARLY: the detector workgroup's share of picp_cycle_detect -- the old pose becomes hist[it - 1]; its comparison is the
+        // one every workgroup makes below.  (Not the function itself: it reads pose[(it - 1) % PICP_SLOTS] in every round,
+        // which a workgroup that has found the repeat may be overwriting behind the first one.)
+        if (EARLY && detector && tid < 12) {
+          int mine = op[0];
+#pragma unroll
+          for (int q = 1; q < 12; ++q) mine = tid == q ? op[q] : mine;
+          reinterpret_cast<int*>(S->hist[(it - 1) & (PICP_HIST - 1)])[tid] = mine;
+        }
         // the 32 group sums, staged transposed, and this lane's entry of the system (steps (5), (6))
         s_stg[stg_to + 0 * STG_STRIDE] = psum.x;
         s_stg[stg_to + 1 * STG_STRIDE] = psum.y;
         s_stg[stg_to + 2 * STG_STRIDE] = psum.z;
         s_stg[stg_to + 3 * STG_STRIDE] = psum.w;
         __syncthreads();
-        float val = 0.f;
-        if (lane < 42) {
+        float val = 0.f, tsum = 0.f;
+        if (lane < (EARLY ? 45 : 42)) {                          // (EARLY: the statistics' sums too -- the closing may need them)
           const float4* row = reinterpret_cast<const float4*>(s_stg + stg_at);
-          float tsum = 0.f;
 #pragma unroll
           for (int k = 0; k < PICP_GROUPS / 4; ++k) { const float4 t4 = row[k]; tsum += t4.x; tsum += t4.y; tsum += t4.z; tsum += t4.w; }
           if (lane < 36) val = diag ? tsum + 1.f * damping : tsum;
           else val = -tsum;
         }
         const Pose Tn = picp_tail_direct(val, pb0, pb1, pb2, m3);
+        Pose Tu;
+        if (EARLY) {
+          Tu = uniform_pose(Tn);
+          int d_new = 0, d_old = 0;
+#pragma unroll
+          for (int q = 0; q < 12; ++q) {
+            const int e = lane == 0 ? op[q] : he[q];
+            d_new |= e ^ __float_as_int(q < 9 ? Tu.R[q] : Tu.t[q - 9]);
+            d_old |= e ^ op[q];
+          }
+          const bool live = it - 1 - lane >= 0;
+          const unsigned long long hits_new = __ballot(live && lane < PICP_HIST - 1 && d_new == 0);
+          const unsigned long long hits_old = __ballot(live && lane >= 1 && d_old == 0) >> 1;
+          // (the detector workgroup: what picp_cycle_detect reports for launch `it`, skipping or not)
+          if (detector && hits_old != 0 && det0 == 0) {
+            const int jo = it - 2 - __builtin_ctzll(hits_old);
+            const PicpSkip so = picp_cycle_skip(it - 1, jo, last);
+            const bool skips = picp_cycle_skips(it - 1, last);
+            if (tid == 0) {
+              S->cyc.detected_at = so.detected_at;
+              S->cyc.period = so.period;
+              S->cyc.skipped = skips ? so.skipped : 0;
+              if (skips) {
+                S->cyc.target = so.target;
+                S->cyc.skip_from = so.skip_from;
+              }
+            }
+            det0 = 1;
+          }
+          int kf = 0, jf = 0;
+          const bool may_act = !(it == first && ((it - 1) & (PICP_SLOTS - 1)) == 0);
+          if (may_act && picp_tail_first_repeat(hits_new, hits_old, it, &kf, &jf) && picp_cycle_skips(kf, last)) {
+            const PicpSkip sk = picp_cycle_skip(kf, jf, last);
+            if (tid == 0 && blockIdx.x == 0) {
+              S->cyc.detected_at = sk.detected_at;
+              S->cyc.period = sk.period;
+              S->cyc.skipped = sk.skipped;
+              S->cyc.target = sk.target;
+              S->cyc.skip_from = sk.skip_from;
+            }
+            skip_from = sk.skip_from;
+            target = sk.target;
+            early_hit = true;
+            early_it = it;
+            early_d = sk.detected_at;
+            k_tsum = tsum;
+            k_Tn = Tn;
+#pragma unroll
+            for (int q = 0; q < 9; ++q) Told.R[q] = __int_as_float(__builtin_amdgcn_readfirstlane(op[q]));
+#pragma unroll
+            for (int q = 0; q < 3; ++q) Told.t[q] = __int_as_float(__builtin_amdgcn_readfirstlane(op[9 + q]));
+            continue;
+          }
+        }
         if (tid == 0 && blockIdx.x == 0) store_pose12(S->pose[it & (PICP_SLOTS - 1)], Tn);
-        T = uniform_pose(Tn);
+        T = EARLY ? Tu : uniform_pose(Tn);
         Tl = T;
         ++real;
       }
-      float acc[NACC];
+      if (!(EARLY && detector)) {                                // (EARLY: the detector workgroup has no pair and no row)
+        float acc[NACC];
 #pragma unroll
-      for (int k = 0; k < NACC; ++k) acc[k] = 0.f;
-      if (have) picp_accumulate_t<PINHOLE, KEEP>(cam, cb, T, thr, x, y, z, u, v, acc);
-      const float tot = block_reduce_quad(acc, s_acc, s_part);
-      if (tid < PICP_PSTRIDE) {
-        const float o = tid < NACC ? tot : 0.f;
+        for (int k = 0; k < NACC; ++k) acc[k] = 0.f;
+        if (have) picp_accumulate_t<PINHOLE, KEEP>(cam, cb, T, thr, x, y, z, u, v, acc);
+        const float tot = block_reduce_quad(acc, s_acc, s_part);
+        if (tid < PICP_PSTRIDE) {
+          const float o = tid < NACC ? tot : 0.f;
+          const int row_slot = (EARLY && early_hit ? early_it : it) & (PICP_SLOTS - 1);
 #pragma unroll
-        for (int k = 0; k < PICP_REPLICAS; ++k)
-          partials[(size_t)k * PICP_SLOTS * slot_floats + ((size_t)(it & (PICP_SLOTS - 1)) * nb_pad + blockIdx.x) * PICP_PSTRIDE + tid] = o;
+          for (int k = 0; k < PICP_REPLICAS; ++k)
+            partials[(size_t)k * PICP_SLOTS * slot_floats + ((size_t)row_slot * nb_pad + blockIdx.x) * PICP_PSTRIDE + tid] = o;
+        }
       }
     }
     if (it == last) break;
@@ -947,7 +1068,7 @@ __global__ __launch_bounds__(PICP_BLOCK) void picp_tail_kernel(const PicpParams*
   // RING: the rows are an earlier launch's (or lie behind a barrier of the loop): nothing to wait for.  Otherwise every row
   // workgroup has just stored its row of round `last`: all arrive, workgroup 0 waits for the nb of them (`goal` arrivals lie
   // behind the loop's barriers) and the others leave.  Given up: `aborted` is set and no result field is written.
-  if (how != PICP_CLOSE_RING && !picp_tail_arrive(tl, goal + nb, &s_go)) return;
+  if (how != PICP_CLOSE_RING && !(EARLY && early_ring) && !picp_tail_arrive(tl, goal + nb, &s_go)) return;
   {
     // The launch's report (below) is one thread's, in the LAST wave: only wave 0 has work behind the staging barrier, so the
     // report's loads go out here, beside the row loads, and its stores -- two of them cross the host link, and the kernel's
@@ -960,11 +1081,13 @@ __global__ __launch_bounds__(PICP_BLOCK) void picp_tail_kernel(const PicpParams*
       t_run = S->close.run;
       t_det = S->close.max_detected;
       t_d = S->cyc.detected_at;
+      if (EARLY && early_hit) t_d = early_d;                 // (the word this workgroup stored itself)
     }
     // rows of the slot (replica 0, as the one-workgroup finishing launch reads), same loads, same order of every sum
+    // (EARLY, in hand: the staged sums are this slot's already -- every replica holds the same rows)
     const char* prev = reinterpret_cast<const char*>(partials + (size_t)close_slot * slot_floats);
     float4 psum = make_float4(0.f, 0.f, 0.f, 0.f);
-    for (int b0 = 0; b0 < nb; b0 += 256) {
+    for (int b0 = 0; b0 < (EARLY && inhand ? 0 : nb); b0 += 256) {
       float4 r[NJ];
 #pragma unroll
       for (int j = 0; j < NJ; ++j)
@@ -975,12 +1098,14 @@ __global__ __launch_bounds__(PICP_BLOCK) void picp_tail_kernel(const PicpParams*
     // the old pose's column for this lane, from the uniform copy (the bytes pose[last % PICP_SLOTS] holds)
     float pb0, pb1, pb2;
     pose_lane_operands(Tl, pb0, pb1, pb2);
-    __syncthreads();                                         // (the staging area may still be read by a slower wave of the last round)
-    s_stg[stg_to + 0 * STG_STRIDE] = psum.x;
-    s_stg[stg_to + 1 * STG_STRIDE] = psum.y;
-    s_stg[stg_to + 2 * STG_STRIDE] = psum.z;
-    s_stg[stg_to + 3 * STG_STRIDE] = psum.w;
-    __syncthreads();
+    if (!(EARLY && inhand)) {
+      __syncthreads();                                         // (the staging area may still be read by a slower wave of the last round)
+      s_stg[stg_to + 0 * STG_STRIDE] = psum.x;
+      s_stg[stg_to + 1 * STG_STRIDE] = psum.y;
+      s_stg[stg_to + 2 * STG_STRIDE] = psum.z;
+      s_stg[stg_to + 3 * STG_STRIDE] = psum.w;
+      __syncthreads();
+    }
     if (reporter) {
       tl->used = 1;
       tl->rounds = real;
@@ -1017,8 +1142,11 @@ __global__ __launch_bounds__(PICP_BLOCK) void picp_tail_kernel(const PicpParams*
     if (lane < 45) {
       const float4* row = reinterpret_cast<const float4*>(s_stg + stg_at);
       float tsum = 0.f;
+      if (EARLY && inhand) tsum = k_tsum;
+      else {
 #pragma unroll
-      for (int k = 0; k < PICP_GROUPS / 4; ++k) { const float4 t4 = row[k]; tsum += t4.x; tsum += t4.y; tsum += t4.z; tsum += t4.w; }
+        for (int k = 0; k < PICP_GROUPS / 4; ++k) { const float4 t4 = row[k]; tsum += t4.x; tsum += t4.y; tsum += t4.z; tsum += t4.w; }
+      }
       if (lane < 36) {
         val = diag ? tsum + 1.f * damping : tsum;
         if (wave == 0) S->H[(lane % 6) * 6 + lane / 6] = val;    // col-major
@@ -1029,7 +1157,9 @@ __global__ __launch_bounds__(PICP_BLOCK) void picp_tail_kernel(const PicpParams*
         s_stat[lane - 42] = tsum;
       }
     }
-    const Pose Tn = picp_tail_direct(val, pb0, pb1, pb2, m3);
+    Pose Tn;
+    if (EARLY && inhand) Tn = k_Tn;                          // (the pose the round computed from these very sums and this old pose)
+    else Tn = picp_tail_direct(val, pb0, pb1, pb2, m3);
     if (tid == 0) {
       store_pose12(S->pose[0], Tn);
       float T16[16];
@@ -1076,6 +1206,8 @@ int picp_grid_for(int n_corr, int n_cu) {
 
 // VO_PICP_TAIL=0 keeps a launch per round; VO_PICP_TAIL_FROM sets the last round with a launch of its own (read per call)
 bool picp_tail_ring_enabled() { const char* e = getenv("VO_PICP_TAIL_RING"); return !(e && e[0] == '0'); }
+// VO_PICP_TAIL_EARLY: 1 adds the early form to a forced M, 0 keeps the host from choosing it (read per call); -1: not set
+int picp_tail_early_env() { const char* e = getenv("VO_PICP_TAIL_EARLY"); return !e ? -1 : (e[0] == '1' ? 1 : (e[0] == '0' ? 0 : -1)); }
 
 int picp_tail_from(int grid, int n_iters, bool cycle, int n_cu, bool* forced, int m_default) {
   if (forced) *forced = false;
@@ -1188,7 +1320,7 @@ static bool picp_small_enabled() {
 template <bool PINHOLE, bool KEEP>
 static void launch_rounds_t(hipStream_t st, PicpParams* d_params, PicpState* d_state, PackedCorr pk,
                             float* d_partials, int grid, int n_iters, const PicpGather& g, int part, bool cycle, int tail_from, int* tail_report,
-                            bool tail_ring) {
+                            bool tail_ring, bool tail_early) {
   // With cycle detection every launch behind round 0 carries one more workgroup, the detector (picp_cycle_detect); the rounds
   // are told the last round launch's index.  Round 0 resets the control block whether or not detection is on.
   const int cyc = cycle ? 1 : 0, last = n_iters - 1;
@@ -1206,7 +1338,10 @@ static void launch_rounds_t(hipStream_t st, PicpParams* d_params, PicpState* d_s
   for (int it = 2; it < own; ++it)
     hipLaunchKernelGGL((picp_round_kernel<true, false, PINHOLE, KEEP>), dim3(grid + cyc), dim3(PICP_BLOCK), 0, st,
                        d_params, d_state, pk.base, pk.cap, d_partials, it, grid, last, cyc);
-  if (tail_from > 0)
+  if (tail_from > 0 && tail_early)
+    hipLaunchKernelGGL((picp_tail_kernel<PINHOLE, KEEP, true>), dim3(grid + 1), dim3(PICP_BLOCK), 0, st, d_params, d_state, pk.base,
+                       pk.cap, d_partials, tail_from + 1, grid, last, tail_report, tail_ring ? 1 : 0);
+  else if (tail_from > 0)
     hipLaunchKernelGGL((picp_tail_kernel<PINHOLE, KEEP>), dim3(grid + 1), dim3(PICP_BLOCK), 0, st, d_params, d_state, pk.base,
                        pk.cap, d_partials, tail_from + 1, grid, last, tail_report, tail_ring ? 1 : 0);
   if (tail_from > 0) return;
@@ -1253,7 +1388,7 @@ hipError_t launch_picp_finish(hipStream_t st, const PicpParams* d_params, PicpSt
 hipError_t launch_picp_rounds(hipStream_t st, PicpParams* d_params, PicpState* d_state,
                               PackedCorr pk, float* d_partials, int grid, int n_iters, bool pinhole,
                               bool keep_outliers, const PicpGather& gt, int part, bool cycle, int tail_from, int* tail_report,
-                              bool tail_ring) {
+                              bool tail_ring, bool tail_early) {
   if (n_iters <= 0) return hipSuccess;
   if (tail_from < 0 || (tail_from > 0 && (!cycle || n_iters - 1 <= tail_from + 1))) return hipErrorInvalidValue;
   if (grid == 1 && picp_small_enabled()) {      // one workgroup's worth of correspondences (picp_grid_for): all rounds in one launch
@@ -1266,11 +1401,11 @@ hipError_t launch_picp_rounds(hipStream_t st, PicpParams* d_params, PicpState* d
     return hipGetLastError();
   }
   if (pinhole) {
-    if (keep_outliers) launch_rounds_t<true, true>(st, d_params, d_state, pk, d_partials, grid, n_iters, gt, part, cycle, tail_from, tail_report, tail_ring);
-    else launch_rounds_t<true, false>(st, d_params, d_state, pk, d_partials, grid, n_iters, gt, part, cycle, tail_from, tail_report, tail_ring);
+    if (keep_outliers) launch_rounds_t<true, true>(st, d_params, d_state, pk, d_partials, grid, n_iters, gt, part, cycle, tail_from, tail_report, tail_ring, tail_early);
+    else launch_rounds_t<true, false>(st, d_params, d_state, pk, d_partials, grid, n_iters, gt, part, cycle, tail_from, tail_report, tail_ring, tail_early);
   } else {
-    if (keep_outliers) launch_rounds_t<false, true>(st, d_params, d_state, pk, d_partials, grid, n_iters, gt, part, cycle, tail_from, tail_report, tail_ring);
-    else launch_rounds_t<false, false>(st, d_params, d_state, pk, d_partials, grid, n_iters, gt, part, cycle, tail_from, tail_report, tail_ring);
+    if (keep_outliers) launch_rounds_t<false, true>(st, d_params, d_state, pk, d_partials, grid, n_iters, gt, part, cycle, tail_from, tail_report, tail_ring, tail_early);
+    else launch_rounds_t<false, false>(st, d_params, d_state, pk, d_partials, grid, n_iters, gt, part, cycle, tail_from, tail_report, tail_ring, tail_early);
   }
   return hipGetLastError();
 }

@@ -109,7 +109,7 @@ struct PicpTailTally {
   int looped;
 };
 // The tail launch also CLOSES the solve (there is no finishing launch behind it): its workgroup 0 does the finishing launch's
-// work -- the rows of round N - 1 summed, the system solved, pose[0], T16, H, b, statistics -- in one of three ways:
+// work -- the rows of round N - 1 summed, the system solved, pose[0], T16, H, b, statistics -- in one of four ways:
 //   RING       state SKIP and the rows launch `target` stored still lie in the ring (picp_tail_ring_holds): they ARE the rows
 //              launch N - 1 would store, so nothing is linearised; every other workgroup returns behind the control word;
 //   RECOMPUTED state SKIP, slot overwritten (or VO_PICP_TAIL_RING=0): every workgroup linearises with hist[target], stores its
@@ -117,7 +117,10 @@ struct PicpTailTally {
 //   LOOPED     the launch ran round N - 1 as a real round at the end of its loop: closed like RECOMPUTED.
 // The words lie behind the tally so that no earlier offset moves; like the tally they are written by tail launches only and
 // never reset: `how` and `m` describe the last solve THAT HAD a tail launch (PicpTail::used tells whether the last solve did).
-constexpr int PICP_CLOSE_NONE = 0, PICP_CLOSE_RING = 1, PICP_CLOSE_RECOMPUTED = 2, PICP_CLOSE_LOOPED = 3;
+//   EARLY      (the early form of the launch, below) state RUN, and the workgroups found the repeat themselves in the round that
+//              computed the repeating pose: closed from the sums in hand, from the ring, or recomputed, with nobody waiting for
+//              a detector.
+constexpr int PICP_CLOSE_NONE = 0, PICP_CLOSE_RING = 1, PICP_CLOSE_RECOMPUTED = 2, PICP_CLOSE_LOOPED = 3, PICP_CLOSE_EARLY = 4;
 struct PicpTailClose {
   int how;             // PICP_CLOSE_*
   int m;               // the M that solve ran with (rounds 1 .. M had launches of their own)
@@ -132,12 +135,38 @@ struct PicpTailClose {
 __host__ __device__ inline bool picp_tail_ring_holds(int skip_from, int target) {
   return target >= 0 && skip_from - 1 - target < PICP_SLOTS;
 }
+// The early form of the tail launch (picp.hip, picp_tail_kernel<.., EARLY>): in state RUN every workgroup of in-launch round
+// `it` compares the pose it has just computed, pose `it`, and the pose it started from, pose it - 1, with the history itself.
+//   hits_new  bit l: pose `it` equals the pose of round it - 1 - l      (l = 0 .. PICP_HIST - 2; l = 0 is the old pose)
+//   hits_old  bit l: pose it - 1 equals the pose of round it - 2 - l    (the window the detector of launch `it` looks through)
+// The FIRST repeat is the old pose's where it has one -- the detector workgroup of the same round finds exactly that one and
+// stores the same words --, the new pose's otherwise; the most recent match wins, as in picp_cycle_detect.  Answers whether
+// there is one, and then pose k = pose j.
+__host__ __device__ inline bool picp_tail_first_repeat(unsigned long long hits_new, unsigned long long hits_old, int it, int* k, int* j) {
+  if (hits_old) { *k = it - 1; *j = it - 1 - (__builtin_ctzll(hits_old) + 1); return true; }
+  if (hits_new) { *k = it; *j = it - (__builtin_ctzll(hits_new) + 1); return true; }
+  return false;
+}
+// What the launch-per-round solve makes of the repeat pose k = pose j (picp_cycle_detect in launch k + 1; last = N - 1 is the
+// last round launch): it skips where a launch is left to skip; then launches from k + 2 on skip, and the pose of round `last`
+// is the pose of round `target`.
+struct PicpSkip {
+  int detected_at, period, skipped, target, skip_from;
+};
+__host__ __device__ inline bool picp_cycle_skips(int k, int last) { return k + 2 < last; }
+__host__ __device__ inline PicpSkip picp_cycle_skip(int k, int j, int last) {
+  const int period = k - j;
+  return PicpSkip{k + 1, period, last - 2 - k, j + (last - j) % period, k + 2};
+}
 // the host's report (pinned memory, launch_picp_rounds' tail_report): [0], [1] the tally's two counts; [2] run << 16 |
 // max_detected (each saturating at 0xffff) in ONE word, so that the host never reads a torn pair; [3] behind a launch that ran
 // real rounds: looped << 16 | the last round it ran (first + real - 1, saturating), the count's low half as a consistency tag
 constexpr int PICP_TAIL_REPORT_WORDS = 4;
 // the host lowers M only once this many consecutive tail launches have taken the skip path (capi.hip, picp_tail_policy)
 constexpr int PICP_TAIL_LEARN = 8;
+// ... and takes the early form, at M = largest detected_at - 2, once this many have: that M leaves no margin round, so it asks
+// for four times the witnesses
+constexpr int PICP_TAIL_EARLY_LEARN = 32;
 
 // Solver state in device memory.
 struct PicpState {
@@ -200,7 +229,7 @@ constexpr int PICP_WHOLE = 0, PICP_ROUND0 = 1, PICP_AFTER_ROUND0 = 2;
 hipError_t launch_picp_rounds(hipStream_t st, PicpParams* d_params, PicpState* d_state,
                               PackedCorr pk, float* d_partials, int grid, int n_iters, bool pinhole,
                               bool keep_outliers, const PicpGather& g = PicpGather{}, int part = PICP_WHOLE, bool cycle = false,
-                              int tail_from = 0, int* tail_report = nullptr, bool tail_ring = true);
+                              int tail_from = 0, int* tail_report = nullptr, bool tail_ring = true, bool tail_early = false);
 // the tail form's M for a solve of n_iters rounds on `grid` workgroups (picp_grid_for), or 0 where the solve keeps a
 // launch per round: too few rounds, no cycle detection, the form switched off, or a grid that would not leave every workgroup
 // of the tail launch -- the detector included -- a CU of its own.  Reads VO_PICP_TAIL and VO_PICP_TAIL_FROM; *forced (may be
@@ -208,8 +237,11 @@ hipError_t launch_picp_rounds(hipStream_t st, PicpParams* d_params, PicpState* d
 // tail_report (launch_picp_rounds): PICP_TAIL_REPORT_WORDS host-visible ints (above), or null.  tail_ring: false forces the
 // RECOMPUTED closing where RING would do (VO_PICP_TAIL_RING=0, read per call by picp_tail_ring_enabled: tests and the A/B).
 // m_default: the M to use where VO_PICP_TAIL_FROM does not set one (the handle's learned M: picp_tail_policy).
+// tail_early: the tail launch is the early form (VO_PICP_TAIL_EARLY, read per call by picp_tail_early_env: 1 adds it to a
+// forced M, 0 keeps the host from choosing it, -1: not set).
 int picp_tail_from(int grid, int n_iters, bool cycle, int n_cu, bool* forced = nullptr, int m_default = PICP_TAIL_FROM);
 bool picp_tail_ring_enabled();
+int picp_tail_early_env();
 
 int picp_grid_for(int n_corr, int n_cu);
 
