@@ -270,6 +270,21 @@ def test_multi_gpu_rank_bookkeeping_without_a_gpu(tmp_path):
     assert r.stdout.count("-> ok") >= 40 and "FAILED" not in r.stdout
 
 
+def test_map_window_refusals_under_the_host_sanitizers(tmp_path):
+    """visual-odometry_amd/csrc/map_checks.h -- the refusals every window call of the map shares (frames, round parameters) and
+    the refusal of a workspace that would have to grow inside a graph capture make no HIP call: a stand-alone program runs
+    them under AddressSanitizer and UBSan over the edge values, each row against the code and the whole message the C
+    boundary gave before the checks were shared."""
+    exe = str(tmp_path / "map_checks_check")
+    root = os.path.join(HERE, "..")
+    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-Wall", "-Wextra", "-Werror", "-fsanitize=address,undefined",
+                           "-fno-sanitize-recover=all", "-I" + os.path.join(root, "visual-odometry_amd", "csrc"),
+                           os.path.join(HERE, "hostcheck", "map_checks_check.cpp"), "-o", exe])
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0 and r.stdout.strip().endswith("map_checks_check: all ok"), r.stdout[-3000:] + r.stderr[-3000:]
+    assert r.stdout.count("-> ok") >= 70 and "FAILED" not in r.stdout
+
+
 # ---- host linear algebra of the epipolar initialisation (include/vo/epipolar.hpp, vo/linalg.hpp) ---------------------
 @pytest.fixture(scope="module")
 def epi():

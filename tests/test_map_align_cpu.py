@@ -57,7 +57,7 @@ def test_records_are_pinned(vo):
     assert re.search(r"#define VOE_MAP_MERGE_TAKE_SRC\s+0\b", hdr) and re.search(r"#define VOE_MAP_MERGE_KEEP_DST\s+1\b", hdr)
     assert re.search(r"#define VOE_MAP_ALIGN_MAX_REFITS\s+%d\b" % vo.MAP_ALIGN_MAX_REFITS, hdr) and vo.MAP_ALIGN_MAX_REFITS == A.MAX_REFITS
     assert (vo.MAP_MERGE_TAKE_SRC, vo.MAP_MERGE_KEEP_DST) == (A.TAKE_SRC, A.KEEP_DST)
-    cap = open(os.path.join(ROOT, "visual-odometry_amd", "csrc", "capi.hip")).read()
+    cap = open(os.path.join(ROOT, "visual-odometry_amd", "csrc", "capi_map.hip")).read()
     assert "sizeof(voe_map_align_params) == 32 && sizeof(voe_map_align_stats) == 48 && sizeof(voe_map_merge_stats) == 16" in cap
     for n in ("align", "align_dev", "merge", "merge_dev", "size_bound"):
         assert hasattr(vo.Map, n)

@@ -12,8 +12,7 @@
 #include <tuple>
 #include <vector>
 
-#include "../../include/vo_hip.h"
-#include "vo_internal.h"
+#include "capi_internal.h"
 #include "../../include/vo/epipolar.hpp"   // host linear algebra of vo_estimate_transform
 
 using namespace vo;
@@ -31,54 +30,6 @@ int fail(int code, const char* fmt, ...) {
 }
 void set_error_v(const char* fmt, va_list ap) { vsnprintf(g_err, sizeof(g_err), fmt, ap); }
 
-#define VO_HIP_CHECK(expr)                                                              \
-  do {                                                                                  \
-    hipError_t _e = (expr);                                                             \
-    if (_e != hipSuccess) {                                                             \
-      (void)hipGetLastError(); /* reported here: must not resurface in the next call's launch check */ \
-      return fail(_e == hipErrorOutOfMemory ? VO_ERR_OUT_OF_MEMORY : VO_ERR_HIP,        \
-                  "%s failed: %s (%s:%d)", #expr, hipGetErrorString(_e), __FILE__, __LINE__); \
-    }                                                                                   \
-  } while (0)
-
-#define VO_REQUIRE(cond, msg) \
-  do { if (!(cond)) return fail(VO_ERR_INVALID_ARG, "%s: %s", __func__, msg); } while (0)
-
-// device arrays move as 8-byte pieces (vo_hip.h, Conventions): true when every pointer given is null or on such a boundary
-template <typename... P>
-static bool aligned8(const P*... p) { return ((... | reinterpret_cast<uintptr_t>(p)) & 7u) == 0; }
-
-// entry points that copy host memory or wait for the stream cannot be part of a graph capture (vo_ctx_begin_capture): refused
-// BEFORE any HIP call, because a refused HIP call would invalidate the capture in progress
-#define VO_NOT_CAPTURING(ctx) \
-  do { if ((ctx)->capturing) return fail(VO_ERR_NOT_READY, "%s: not allowed inside a graph capture (only *_dev entry points are)", __func__); } while (0)
-
-struct DevBuf {
-  void* p = nullptr;
-  size_t cap = 0;
-  // grow-only; contents are NOT preserved
-  hipError_t ensure(size_t bytes, hipStream_t st) {
-    if (bytes <= cap) return hipSuccess;
-    {   // growing frees, allocates and synchronises: none of it may happen inside a graph capture
-      hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-      if (hipStreamIsCapturing(st, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone) return hipErrorStreamCaptureUnsupported;
-    }
-    if (p) {
-      hipError_t e = hipStreamSynchronize(st);
-      if (e != hipSuccess) return e;
-      (void)hipFree(p);
-      p = nullptr; cap = 0;
-    }
-    size_t want = bytes + bytes / 4 + 256;
-    hipError_t e = hipMalloc(&p, want);
-    if (e != hipSuccess) { p = nullptr; return e; }
-    cap = want;
-    return hipSuccess;
-  }
-  void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
-  template <class T> T* as() const { return reinterpret_cast<T*>(p); }
-};
-
 }  // namespace
 
 int vo_fail(int code, const char* fmt, ...) {        // for the other translation units (vo_internal.h)
@@ -88,54 +39,6 @@ int vo_fail(int code, const char* fmt, ...) {        // for the other translatio
   va_end(ap);
   return code;
 }
-
-struct vo_ctx {
-  int device = 0;
-  hipStream_t stream = nullptr;
-  bool own_stream = false;
-  int n_cu = 0;
-  char name[128] = "";
-  DevBuf scratch;     // compaction counts
-  DevBuf best;        // matcher keys
-  DevBuf table;       // join table
-  DevBuf in[6];       // staging for host-pointer entry points
-  DevBuf out[3];
-  DevBuf counts;      // small device ints
-  DevBuf batch_pack;  // packed correspondences of the batched solver
-  DevBuf batch_bad;   // its per-problem bad-index counters
-  DevBuf batch_states, batch_partials;   // launch-per-round form of the batched solver: per-problem state + partial rows
-  DevBuf batch_help;  // shared form (fewer problems than CUs): tagged words handed between workgroups
-  PicpParams batch_params_host{};        //   its parameter block as last uploaded, and where
-  const PicpParams* batch_params_dev = nullptr;
-  DevBuf prune_ws;    // sorted copies / tables of the matcher's sorted searches
-  DevBuf epi_ws;      // maxima, A^T A and vote counts of vo_estimate_transform
-  DevBuf ransac_ws;   // points, hypotheses, counts, mask and inlier pairs of vo_estimate_transform_ransac
-  DevBuf pose_ws;     // the same for vo_estimate_pose_ransac
-  DevBuf pose_batch_ws;   // ... and for vo_estimate_pose_ransac_batch_dev (all problems' blocks)
-  DevBuf refine_ws;   // state and workgroup rows of vo_refine_transform_dev
-  DevBuf track_ws;    // vo_frames_batch_track_dev: the moved cloud, the tracked pairs and the winners the caller did not ask for
-  // Steering of the automatic matcher by what the previous batched call found: after a call that ran the
-  // exact-duplicate pass, "did any frame take it?" travels to pinned host memory behind the call (no wait); a later call
-  // that finds the answer "none" there leaves the pass out for the next HINT_SKIP calls, then probes again.  Data whose
-  // descriptors are recomputed per frame (no bitwise copies, ever) then pays the sampling pass once in seventeen calls.
-  // A call that ran WITHOUT the pass asks the same question of the keys the search left (a sample query at distance 0 from
-  // its match): the answer "yes" ends the skipping at once, so data that regains its copies loses one or two calls, not sixteen.
-  // vo_match_set_mode() forgets what was learnt.
-  int* hint_host = nullptr;        // pinned
-  int* hint_dev = nullptr;
-  hipEvent_t hint_ev = nullptr;
-  bool hint_pending = false;
-  int hint_skip_left = 0;
-  bool hint_of_skipped_call = false;   // what the pending answer was asked of
-  int hint_none_streak = 0;            // consecutive answers "no frame took the pass": two in a row start the skipping (a context
-                                       // that alternates between data with and without copies is then never steered wrong)
-  int match_mode = 0; // 0 auto, 1 full scan, 2 bucket-pruned scan, 3 cell-hash search, 4 / 5 exact-duplicate pass first, then 2 / 3
-  int batch_form = 0; // batched solver: 0 auto, 1 one launch per round, 2 one workgroup per problem
-  int batch_last_form = 0, batch_last_wgs = 0;   // what the last batched call ran as (vo_picp_batch_info)
-  int batch_last_help_rows = 0, batch_last_problems = 0, batch_last_help_mode = 0;   // ... and where its helper record lies (vo_picp_batch_help_info)
-  bool capturing = false;
-  unsigned long long id = 0;   // unique per context ever created: an address can be reused, an id cannot
-};
 
 struct vo_event {
   int device = 0;
@@ -148,12 +51,12 @@ struct vo_event {
 static std::mutex g_ctx_mu;
 static std::set<const vo_ctx*> g_ctx_live;
 static unsigned long long g_ctx_next_id = 1;
-static bool ctx_alive(const vo_ctx* c) {
+bool ctx_alive(const vo_ctx* c) {
   std::lock_guard<std::mutex> lk(g_ctx_mu);
   return c && g_ctx_live.count(c) != 0;
 }
 // the context a handle was made on: still there, and still THAT context (not a new one at the recycled address)
-static bool ctx_alive(const vo_ctx* c, unsigned long long id) {
+bool ctx_alive(const vo_ctx* c, unsigned long long id) {
   std::lock_guard<std::mutex> lk(g_ctx_mu);
   return c && g_ctx_live.count(c) != 0 && c->id == id;
 }
@@ -234,7 +137,7 @@ struct vo_picp {
   std::map<std::tuple<int, int, const void*, size_t, const void*, int>, hipGraphExec_t> graphs;
 };
 
-static int set_device(vo_ctx* ctx) {
+int set_device(vo_ctx* ctx) {
   VO_HIP_CHECK(hipSetDevice(ctx->device));
   return VO_OK;
 }
@@ -468,13 +371,13 @@ int vo_memcpy_d2h(vo_ctx* c, void* dst, const void* src, size_t bytes) {
 }  // extern "C"
 
 // ---- helpers for the host-pointer entry points ------------------------------------
-static int upload(vo_ctx* c, DevBuf& b, const void* src, size_t bytes) {
+int upload(vo_ctx* c, DevBuf& b, const void* src, size_t bytes) {
   VO_HIP_CHECK(b.ensure(bytes ? bytes : 16, c->stream));
   if (bytes) VO_HIP_CHECK(hipMemcpyAsync(b.p, src, bytes, hipMemcpyHostToDevice, c->stream));
   return VO_OK;
 }
 
-static int ensure_counts(vo_ctx* c) {
+int ensure_counts(vo_ctx* c) {
   VO_HIP_CHECK(c->counts.ensure(64 * sizeof(int), c->stream));
   return VO_OK;
 }
@@ -627,6 +530,13 @@ int vo_picp_set_kernel_threshold(vo_picp* s, float thr) {
   s->params_dirty = true;
   return VO_OK;
 }
+
+void picp_set_camera_threshold(vo_picp* s, int rows, int cols, int z_near, int z_far, const float K[9], float thr) {
+  const CamK cam = make_cam(rows, cols, z_near, z_far, K);
+  if (memcmp(&cam, &s->hp.cam, sizeof(cam)) != 0) { s->hp.cam = cam; s->params_dirty = true; }
+  if (memcmp(&thr, &s->hp.thr, sizeof(thr)) != 0) { s->hp.thr = thr; s->params_dirty = true; }
+}
+const PicpState* picp_state_dev(const vo_picp* s) { return s->d_state; }
 
 int vo_picp_get_kernel_threshold(vo_picp* s, float* thr) {
   VO_REQUIRE(s && thr, "null argument");
@@ -1856,7 +1766,7 @@ int vo_estimate_transform(vo_ctx* c, const float K[9], const int32_t* pairs, int
 // gather -> hypotheses -> scoring -> selection -> mask and compaction: one read-back (live pairs, bad indices, winner, inliers);
 // then vo_estimate_transform_dev itself on the compacted inlier pairs, which makes the result that of vo_estimate_transform
 // on those pairs bit for bit.
-static int ransac_check_params(const vo_ransac_params* p) {
+int ransac_check_params(const vo_ransac_params* p) {
   if (p->n_hypotheses < 1 || p->n_hypotheses > 65536)
     return fail(VO_ERR_INVALID_ARG, "vo_estimate_transform_ransac: n_hypotheses %d outside 1 .. 65536", p->n_hypotheses);
   if (!(p->threshold_px > 0.f) || !std::isfinite(p->threshold_px))
@@ -1923,29 +1833,6 @@ int vo_estimate_transform_ransac(vo_ctx* c, const float K[9], const int32_t* pai
 // ---- P3P RANSAC in front of the tracking solve (pose_ransac.hip) ---------------------------------------------------------------
 // gather -> hypotheses -> scoring -> selection (status, pose handed on) -> mask and compaction, all on the stream: the device
 // form never reads back, so it falls back to the plain frame (identity pose, every live pair) where the host form refuses.
-// K^-1 in double of the float K (column-major in, column-major out): adjugate / determinant; false when K is singular
-static bool invert_k(const float K[9], double Kinv[9]) {
-  double k[9];
-  for (int i = 0; i < 9; ++i) k[i] = K[i];
-#define VO_K(r, c) k[(r) + 3 * (c)]
-  const double c00 = VO_K(1, 1) * VO_K(2, 2) - VO_K(1, 2) * VO_K(2, 1), c01 = VO_K(1, 2) * VO_K(2, 0) - VO_K(1, 0) * VO_K(2, 2),
-               c02 = VO_K(1, 0) * VO_K(2, 1) - VO_K(1, 1) * VO_K(2, 0);
-  const double det = VO_K(0, 0) * c00 + VO_K(0, 1) * c01 + VO_K(0, 2) * c02;
-  if (!(det != 0.0) || !std::isfinite(det)) return false;
-  // inverse = adjugate / det, column-major: Kinv(r, c) = cofactor(c, r) / det
-  Kinv[0 + 3 * 0] = c00 / det;
-  Kinv[1 + 3 * 0] = c01 / det;
-  Kinv[2 + 3 * 0] = c02 / det;
-  Kinv[0 + 3 * 1] = (VO_K(0, 2) * VO_K(2, 1) - VO_K(0, 1) * VO_K(2, 2)) / det;
-  Kinv[1 + 3 * 1] = (VO_K(0, 0) * VO_K(2, 2) - VO_K(0, 2) * VO_K(2, 0)) / det;
-  Kinv[2 + 3 * 1] = (VO_K(0, 1) * VO_K(2, 0) - VO_K(0, 0) * VO_K(2, 1)) / det;
-  Kinv[0 + 3 * 2] = (VO_K(0, 1) * VO_K(1, 2) - VO_K(0, 2) * VO_K(1, 1)) / det;
-  Kinv[1 + 3 * 2] = (VO_K(0, 2) * VO_K(1, 0) - VO_K(0, 0) * VO_K(1, 2)) / det;
-  Kinv[2 + 3 * 2] = (VO_K(0, 0) * VO_K(1, 1) - VO_K(0, 1) * VO_K(1, 0)) / det;
-#undef VO_K
-  return true;
-}
-
 static int pose_ransac_camera(int rows, int cols, int z_near, int z_far, const float K[9], CamK& cam, double Kinv[9]) {
   for (int i = 0; i < 9; ++i) cam.K[i] = K[i];
   cam.rows = rows; cam.cols = cols; cam.z_near = z_near; cam.z_far = z_far;
@@ -2229,1204 +2116,6 @@ int vo_frames_batch_track_dev(vo_ctx* c, const vo_frame_batch* b, const vo_frame
                                         b->cur_pts, b->n_cur, b->tri_app ? b->cur_app : nullptr, b->tri_xyz, b->tri_pairs,
                                         b->tri_app, n_tri, c->scratch.as<int>(), F, (size_t)q, (size_t)b->n_ref,
                                         (size_t)b->n_cur, (size_t)q));
-  return VO_OK;
-}
-
-// ---- the map (PointCloudVector<3>::update + the history chain of vo_complete.cpp:145-147,175-176,183) ---------------------------
-struct vo_map {
-  vo_ctx* ctx = nullptr;
-  unsigned long long ctx_id = 0;
-  MapDev d;
-  DevBuf scratch;
-  float* hist = nullptr;        // [0,16) the history isometry, [16,32) staging of a host isometry (vo_map_update)
-  long long size_ub = 0;        // upper bound of the size known without asking the device, as long as !replayable
-  bool replayable = false;      // an update of this map has been captured: the graph's replays add entries the host never counts
-  DevBuf up_xyz, up_app;        // staging of vo_map_update
-  DevBuf look_ws;               // vo_map_lookup*: per-workgroup counts, entries per query position
-  DevBuf loc_ws;                // vo_map_localise*: what passes from stage to stage (hits, gathered points, winner, pairs handed on)
-  vo_picp* solver = nullptr;    // vo_map_localise[_dev]: made by the first call
-  DevBuf ref_ws;                // vo_map_refine*: the entries seen, the observation lists, status and cost per entry
-  DevBuf pose_ws;               // vo_map_refine_poses*: the entries seen, status, observation count and cost per frame
-  DevBuf bundle_ws;             // vox_map_bundle*: the state in double, the blocks and the PCG vectors (the lists live in ref_ws)
-  DevBuf cull_ws;               // voe_map_cull*: verdict, remap, ranks, the staging area of the survivors (the lists live in ref_ws)
-  DevBuf align_ws;              // voe_map_align* (on dst): gathered pairs, hypotheses, counts, the blocks' sums
-  DevBuf merge_ws;              // voe_map_merge* (on dst): the lookup's entries, the staging area of the misses
-  DevBuf covis_ws;              // voe_map_covis*: the lookup's pairs, counts and entries, the population counts per frame and per block of words
-  DevBuf window_ws;             // voe_map_window*: the counts against the query row and against the union, the order, the union
-};
-
-constexpr int MAP_MAX_ENTRIES = 1 << 29;      // 2.5 x that many table slots still fit 32 bits
-static unsigned map_tcap_for(int cap) {
-  unsigned t = 1024;
-  while (t < 2u * (unsigned)cap + 2u * ((unsigned)cap >> 2)) t <<= 1;      // at most 40 % full (cap <= MAP_MAX_ENTRIES: t <= 2^31)
-  return t;
-}
-
-static void map_free_arrays(MapDev& d) {
-  if (d.pts) (void)hipFree(d.pts);
-  if (d.app) (void)hipFree(d.app);
-  if (d.table) (void)hipFree(d.table);
-  if (d.last) (void)hipFree(d.last);
-  d.pts = d.app = nullptr; d.table = nullptr; d.last = nullptr;
-}
-
-static int map_alloc_arrays(MapDev& d, int cap) {
-  d.cap = cap; d.tcap = map_tcap_for(cap);
-  VO_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&d.pts), sizeof(float) * 3 * (size_t)cap));
-  VO_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&d.app), sizeof(float) * 10 * (size_t)cap));
-  VO_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&d.table), sizeof(unsigned long long) * (size_t)d.tcap));
-  VO_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&d.last), sizeof(int) * (size_t)d.tcap));
-  return VO_OK;
-}
-
-// what bounds the size where the host must not wait: size_ub, or the capacity once replays may have outrun it
-static int map_bound(const vo_map* m) { return (int)(m->replayable || m->size_ub > m->d.cap ? m->d.cap : m->size_ub); }
-
-// room for n more entries: the bound the host keeps (size_ub grows by a cloud's row count per update) is refreshed from
-// the device only when it would pass the capacity, and the arrays grow only when the true size would.  A map whose update
-// has been captured asks the device every time outside a capture; inside one nobody can ask, and the bound decides as before.
-static int map_reserve(vo_map* m, int n) {
-  vo_ctx* c = m->ctx;
-  if ((c->capturing || !m->replayable) && m->size_ub + n <= m->d.cap) return VO_OK;
-  if (c->capturing) return fail(VO_ERR_NOT_READY, "vo_map: the map would have to grow inside a graph capture (create it with the capacity it will need)");
-  int size = 0;
-  VO_HIP_CHECK(hipMemcpyAsync(&size, m->d.hdr, sizeof(int), hipMemcpyDeviceToHost, c->stream));
-  VO_HIP_CHECK(hipStreamSynchronize(c->stream));
-  m->size_ub = size;
-  if ((long long)size + n <= m->d.cap) return VO_OK;
-  long long want = 2ll * m->d.cap;
-  if (want < (long long)size + n) want = (long long)size + n + ((long long)size + n) / 2;
-  if ((long long)size + n > MAP_MAX_ENTRIES) return fail(VO_ERR_INVALID_ARG, "vo_map: more than 2^29 entries");
-  if (want > MAP_MAX_ENTRIES) want = MAP_MAX_ENTRIES;
-  MapDev old = m->d;
-  MapDev nd = old;
-  nd.pts = nd.app = nullptr; nd.table = nullptr; nd.last = nullptr;
-  if (int r = map_alloc_arrays(nd, (int)want)) { map_free_arrays(nd); return r; }
-  if (size > 0) {
-    VO_HIP_CHECK(hipMemcpyAsync(nd.pts, old.pts, sizeof(float) * 3 * (size_t)size, hipMemcpyDeviceToDevice, c->stream));
-    VO_HIP_CHECK(hipMemcpyAsync(nd.app, old.app, sizeof(float) * 10 * (size_t)size, hipMemcpyDeviceToDevice, c->stream));
-  }
-  VO_HIP_CHECK(launch_map_rehash(c->stream, nd, size));
-  VO_HIP_CHECK(hipStreamSynchronize(c->stream));
-  map_free_arrays(old);
-  m->d = nd;
-  return VO_OK;
-}
-
-#define VO_MAP_LIVE(m) \
-  do { VO_REQUIRE(m, "null map"); VO_REQUIRE(ctx_alive((m)->ctx, (m)->ctx_id), "the context this map was made on has been destroyed"); } while (0)
-
-int vo_map_create(vo_ctx* c, int capacity, vo_map** out) {
-  VO_REQUIRE(c && out, "null argument");
-  VO_NOT_CAPTURING(c);
-  VO_REQUIRE(capacity >= 0 && capacity <= MAP_MAX_ENTRIES, "bad capacity (at most 2^29 entries)");
-  *out = nullptr;
-  if (int r = set_device(c)) return r;
-  vo_map* m = new vo_map();
-  m->ctx = c; m->ctx_id = c->id;
-  const int cap = capacity < 1024 ? 1024 : capacity;
-  int rc = map_alloc_arrays(m->d, cap);
-  if (rc == VO_OK && hipMalloc(reinterpret_cast<void**>(&m->d.hdr), 64) != hipSuccess) rc = fail(VO_ERR_OUT_OF_MEMORY, "vo_map_create: out of device memory");
-  if (rc == VO_OK && hipMalloc(reinterpret_cast<void**>(&m->hist), sizeof(float) * 32) != hipSuccess) rc = fail(VO_ERR_OUT_OF_MEMORY, "vo_map_create: out of device memory");
-  if (rc != VO_OK) { (void)hipGetLastError(); map_free_arrays(m->d); if (m->d.hdr) (void)hipFree(m->d.hdr); if (m->hist) (void)hipFree(m->hist); delete m; return rc; }
-  *out = m;
-  return vo_map_clear(m);
-}
-
-int vo_map_destroy(vo_map* m) {
-  if (!m) return VO_OK;
-  if (ctx_alive(m->ctx, m->ctx_id)) {
-    VO_NOT_CAPTURING(m->ctx);
-    (void)hipSetDevice(m->ctx->device);
-    (void)hipStreamSynchronize(m->ctx->stream);
-  } else {
-    (void)hipDeviceSynchronize();
-  }
-  map_free_arrays(m->d);
-  if (m->d.hdr) (void)hipFree(m->d.hdr);
-  if (m->hist) (void)hipFree(m->hist);
-  m->scratch.release(); m->up_xyz.release(); m->up_app.release(); m->look_ws.release(); m->loc_ws.release(); m->ref_ws.release(); m->pose_ws.release(); m->bundle_ws.release(); m->cull_ws.release(); m->align_ws.release(); m->merge_ws.release(); m->covis_ws.release(); m->window_ws.release();
-  if (m->solver) (void)vo_picp_destroy(m->solver);
-  delete m;
-  return VO_OK;
-}
-
-int vo_map_clear(vo_map* m) {
-  VO_MAP_LIVE(m);
-  vo_ctx* c = m->ctx;
-  VO_NOT_CAPTURING(c);
-  if (int r = set_device(c)) return r;
-  VO_HIP_CHECK(hipMemsetAsync(m->d.hdr, 0, 64, c->stream));
-  VO_HIP_CHECK(launch_map_rehash(c->stream, m->d, 0));
-  const float I[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
-  VO_HIP_CHECK(hipMemcpyAsync(m->hist, I, sizeof(I), hipMemcpyHostToDevice, c->stream));
-  VO_HIP_CHECK(hipStreamSynchronize(c->stream));
-  m->size_ub = 0;
-  return VO_OK;
-}
-
-int vo_map_update_dev(vo_map* m, const float* d_xyz, const float* d_app, int n_max, const int* d_n, const float* d_T16) {
-  VO_MAP_LIVE(m);
-  VO_REQUIRE(n_max >= 0 && n_max <= MAP_MAX_ENTRIES && (n_max == 0 || (d_xyz && d_app)), "bad cloud");
-  VO_REQUIRE(aligned8(d_app), "device appearance rows must be 8-byte aligned");
-  if (n_max == 0) return VO_OK;
-  vo_ctx* c = m->ctx;
-  if (int r = set_device(c)) return r;
-  if (int r = map_reserve(m, n_max)) return r;
-  VO_HIP_CHECK(m->scratch.ensure(sizeof(int) * map_scratch_ints(n_max), c->stream));
-  VO_HIP_CHECK(launch_map_update(c->stream, m->d, d_xyz, d_app, n_max, d_n, d_T16, m->scratch.as<int>()));
-  m->size_ub += n_max;
-  if (c->capturing) m->replayable = true;
-  return VO_OK;
-}
-
-int vo_map_update(vo_map* m, const float* xyz, const float* app, int n, const float T16[16]) {
-  VO_MAP_LIVE(m);
-  VO_NOT_CAPTURING(m->ctx);
-  VO_REQUIRE(n >= 0 && (n == 0 || (xyz && app)), "bad cloud");
-  if (n == 0) return VO_OK;
-  vo_ctx* c = m->ctx;
-  if (int r = set_device(c)) return r;
-  if (int r = upload(c, m->up_xyz, xyz, sizeof(float) * 3 * (size_t)n)) return r;
-  if (int r = upload(c, m->up_app, app, sizeof(float) * 10 * (size_t)n)) return r;
-  if (T16) VO_HIP_CHECK(hipMemcpyAsync(m->hist + 16, T16, sizeof(float) * 16, hipMemcpyHostToDevice, c->stream));
-  VO_HIP_CHECK(hipStreamSynchronize(c->stream));          // the host arrays may go away after the call
-  return vo_map_update_dev(m, m->up_xyz.as<float>(), m->up_app.as<float>(), n, nullptr, T16 ? m->hist + 16 : nullptr);
-}
-
-int vo_map_history_reset_dev(vo_map* m, const float* d_X16) {
-  VO_MAP_LIVE(m);
-  VO_REQUIRE(d_X16, "null pose");
-  if (int r = set_device(m->ctx)) return r;
-  VO_HIP_CHECK(launch_map_history(m->ctx->stream, m->hist, d_X16, 1));
-  return VO_OK;
-}
-
-int vo_map_history_step_dev(vo_map* m, const float* d_X16) {
-  VO_MAP_LIVE(m);
-  VO_REQUIRE(d_X16, "null pose");
-  if (int r = set_device(m->ctx)) return r;
-  VO_HIP_CHECK(launch_map_history(m->ctx->stream, m->hist, d_X16, 0));
-  return VO_OK;
-}
-
-int vo_map_history_dev_ptr(vo_map* m, const float** d_T16) {
-  VO_MAP_LIVE(m);
-  VO_REQUIRE(d_T16, "null argument");
-  *d_T16 = m->hist;
-  return VO_OK;
-}
-
-int vo_map_get_history(vo_map* m, float T16[16]) {
-  VO_MAP_LIVE(m);
-  VO_REQUIRE(T16, "null argument");
-  VO_NOT_CAPTURING(m->ctx);
-  if (int r = set_device(m->ctx)) return r;
-  VO_HIP_CHECK(hipMemcpyAsync(T16, m->hist, sizeof(float) * 16, hipMemcpyDeviceToHost, m->ctx->stream));
-  VO_HIP_CHECK(hipStreamSynchronize(m->ctx->stream));
-  return VO_OK;
-}
-
-int vo_map_size(vo_map* m, int* n) {
-  VO_MAP_LIVE(m);
-  VO_REQUIRE(n, "null argument");
-  VO_NOT_CAPTURING(m->ctx);
-  if (int r = set_device(m->ctx)) return r;
-  int h[4] = {0, 0, 0, 0};
-  VO_HIP_CHECK(hipMemcpyAsync(h, m->d.hdr, sizeof(h), hipMemcpyDeviceToHost, m->ctx->stream));
-  VO_HIP_CHECK(hipStreamSynchronize(m->ctx->stream));
-  m->size_ub = h[0];
-  *n = h[0];
-  if (h[3] > 0) return fail(VO_ERR_BAD_INDEX, "vo_map: %d entries were dropped for lack of room", h[3]);
-  return VO_OK;
-}
-
-int vo_map_read(vo_map* m, float* xyz, float* app, int capacity, int* n_out) {
-  VO_MAP_LIVE(m);
-  VO_REQUIRE(capacity >= 0 && n_out, "bad arguments");
-  int n = 0;
-  if (int r = vo_map_size(m, &n)) return r;
-  *n_out = n;
-  const int k = n < capacity ? n : capacity;
-  if (k > 0 && xyz) VO_HIP_CHECK(hipMemcpyAsync(xyz, m->d.pts, sizeof(float) * 3 * (size_t)k, hipMemcpyDeviceToHost, m->ctx->stream));
-  if (k > 0 && app) VO_HIP_CHECK(hipMemcpyAsync(app, m->d.app, sizeof(float) * 10 * (size_t)k, hipMemcpyDeviceToHost, m->ctx->stream));
-  VO_HIP_CHECK(hipStreamSynchronize(m->ctx->stream));
-  return VO_OK;
-}
-
-int vo_map_transform(vo_map* m, const float T16[16]) {
-  VO_MAP_LIVE(m);
-  VO_REQUIRE(T16, "null argument");
-  if (int r = set_device(m->ctx)) return r;
-  VO_HIP_CHECK(launch_map_transform(m->ctx->stream, m->d, pose_from_T16(T16), map_bound(m)));
-  return VO_OK;
-}
-
-int vo_map_dev_ptrs(vo_map* m, const float** d_xyz, const float** d_app, const int** d_size) {
-  VO_MAP_LIVE(m);
-  if (d_xyz) *d_xyz = m->d.pts;
-  if (d_app) *d_app = m->d.app;
-  if (d_size) *d_size = m->d.hdr;
-  return VO_OK;
-}
-
-// ---- reading the map by appearance: the lookup (map.hip) and the localisation composed of it, the P3P RANSAC and the PICP
-// solvers.  The localisation calls go through the PUBLIC entry points of the stages, in the order the header's contract names.
-static int map_lookup_check(const vo_map* m, int n_frames, const float* d_app, size_t app_stride, int n_max, const int32_t* d_pairs,
-                            const int* d_n_out, const int32_t* d_local) {
-  const char* fn = "vo_map_lookup";
-  if (n_frames < 1 || n_frames > 65535) return fail(VO_ERR_INVALID_ARG, "%s: n_frames %d outside 1 .. 65535 (the frame is a grid dimension)", fn, n_frames);
-  if (n_max < 0) return fail(VO_ERR_INVALID_ARG, "%s: negative row count", fn);
-  if (!d_n_out || (n_max > 0 && !(d_app && d_pairs))) return fail(VO_ERR_INVALID_ARG, "%s: null argument", fn);
-  if (!aligned8(d_app, d_pairs, d_local)) return fail(VO_ERR_INVALID_ARG, "%s: device appearance rows and pair arrays must be 8-byte aligned", fn);
-  if (n_frames > 1 && app_stride < (size_t)n_max) return fail(VO_ERR_INVALID_ARG, "%s: app_stride %zu is smaller than n_max %d", fn, app_stride, n_max);
-  if (app_stride >= 0x7fffffff / 10 || (long long)n_max * n_frames > (1ll << 30))
-    return fail(VO_ERR_INVALID_ARG, "%s: more than 2^30 rows in one call", fn);
-  (void)m;
-  return VO_OK;
-}
-
-static int map_lookup(vo_map* m, int n_frames, const float* d_app, size_t app_stride, int n_max, const int* d_n, int32_t* d_pairs,
-                      int* d_n_out, float* d_xyz, int32_t* d_local, int32_t* d_entries) {
-  VO_MAP_LIVE(m);
-  if (int r = map_lookup_check(m, n_frames, d_app, app_stride, n_max, d_pairs, d_n_out, d_local)) return r;
-  vo_ctx* c = m->ctx;
-  const size_t need = sizeof(int) * map_lookup_scratch_ints(n_max, n_frames, d_entries == nullptr);
-  if (c->capturing && m->look_ws.cap < need)
-    return fail(VO_ERR_NOT_READY, "vo_map_lookup: the scratch would have to grow inside a graph capture (make one call with %d frame(s) "
-                                  "of n_max %d before capturing)", n_frames, n_max);
-  if (int r = set_device(c)) return r;
-  VO_HIP_CHECK(m->look_ws.ensure(need, c->stream));
-  VO_HIP_CHECK(launch_map_lookup(c->stream, m->d, d_app, app_stride, n_max, d_n, n_frames, d_pairs, d_n_out, d_xyz, d_local, d_entries,
-                                 m->look_ws.as<int>()));
-  return VO_OK;
-}
-
-int vo_map_lookup_dev(vo_map* m, const float* d_app, int n_max, const int* d_n, int32_t* d_pairs, int* d_n_out, float* d_xyz,
-                      int32_t* d_local, int32_t* d_entries) {
-  return map_lookup(m, 1, d_app, (size_t)(n_max > 0 ? n_max : 0), n_max, d_n, d_pairs, d_n_out, d_xyz, d_local, d_entries);
-}
-
-int vo_map_lookup_batch_dev(vo_map* m, int n_frames, const float* d_app, size_t app_stride, int n_max, const int* d_n, int32_t* d_pairs,
-                            int* d_n_out, float* d_xyz, int32_t* d_local, int32_t* d_entries) {
-  return map_lookup(m, n_frames, d_app, app_stride, n_max, d_n, d_pairs, d_n_out, d_xyz, d_local, d_entries);
-}
-
-int vo_map_lookup(vo_map* m, const float* app, int n, int32_t* pairs_out, int* n_out, float* xyz_out, int32_t* entry_out) {
-  VO_MAP_LIVE(m);
-  vo_ctx* c = m->ctx;
-  VO_NOT_CAPTURING(c);
-  VO_REQUIRE(n >= 0 && n_out && (n == 0 || (app && pairs_out)), "bad arguments");
-  *n_out = 0;
-  if (n == 0) return VO_OK;
-  if (int r = set_device(c)) return r;
-  if (int r = upload(c, c->in[0], app, sizeof(float) * 10 * (size_t)n)) return r;
-  VO_HIP_CHECK(c->out[0].ensure(sizeof(int32_t) * 2 * (size_t)n, c->stream));
-  VO_HIP_CHECK(c->out[1].ensure(sizeof(float) * 3 * (size_t)n, c->stream));
-  VO_HIP_CHECK(c->out[2].ensure(sizeof(int32_t) * (size_t)n + 128, c->stream));
-  if (int r = ensure_counts(c)) return r;
-  if (int r = vo_map_lookup_dev(m, c->in[0].as<float>(), n, nullptr, c->out[0].as<int32_t>(), c->counts.as<int>(),
-                                xyz_out ? c->out[1].as<float>() : nullptr, nullptr, entry_out ? c->out[2].as<int32_t>() : nullptr))
-    return r;
-  int k = 0;
-  VO_HIP_CHECK(hipMemcpyAsync(&k, c->counts.p, sizeof(int), hipMemcpyDeviceToHost, c->stream));
-  VO_HIP_CHECK(hipStreamSynchronize(c->stream));
-  if (k < 0 || k > n) return fail(VO_ERR_HIP, "vo_map_lookup: unexpected count %d", k);
-  if (k > 0) VO_HIP_CHECK(hipMemcpyAsync(pairs_out, c->out[0].p, sizeof(int32_t) * 2 * (size_t)k, hipMemcpyDeviceToHost, c->stream));
-  if (k > 0 && xyz_out) VO_HIP_CHECK(hipMemcpyAsync(xyz_out, c->out[1].p, sizeof(float) * 3 * (size_t)k, hipMemcpyDeviceToHost, c->stream));
-  if (entry_out) VO_HIP_CHECK(hipMemcpyAsync(entry_out, c->out[2].p, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost, c->stream));
-  VO_HIP_CHECK(hipStreamSynchronize(c->stream));
-  *n_out = k;
-  return VO_OK;
-}
-
-static_assert(sizeof(vo_map_localise_stats) == 32, "the finishing kernel writes eight 4-byte words per frame");
-
-// what passes from stage to stage, per frame, in the map's workspace (256-byte aligned blocks)
-struct LocaliseWs {
-  int32_t *pairs, *local, *handed;   // [F][n_max][2]: (query, entry), (query, k), the pairs handed to the solver
-  float* xyz;                        // [F][n_max][3] gathered points
-  int *n_hits, *n_handed, *rstat;    // [F]
-  float *T_start, *T_solved, *stats4;   // [F][16], [F][16], [F][4]
-  size_t bytes;
-};
-static LocaliseWs localise_layout(void* base, int n_frames, int n_max) {
-  LocaliseWs w{};
-  WsCarver c(base);
-  const size_t F = (size_t)n_frames, N = (size_t)n_max;
-  w.pairs = c.take<int32_t>(8 * F * N);
-  w.local = c.take<int32_t>(8 * F * N);
-  w.handed = c.take<int32_t>(8 * F * N);
-  w.xyz = c.take<float>(12 * F * N);
-  w.n_hits = c.take<int>(4 * F);
-  w.n_handed = c.take<int>(4 * F);
-  w.rstat = c.take<int>(4 * F);
-  w.T_start = c.take<float>(64 * F);
-  w.T_solved = c.take<float>(64 * F);
-  w.stats4 = c.take<float>(16 * F);
-  w.bytes = c.bytes;
-  return w;
-}
-
-static int localise_check(const char* fn, const vo_map* m, const float* K, const float* d_uv, const float* d_app, int n_max,
-                          const vo_ransac_params* params, int n_iters, int min_inliers, const float* d_T0, const float* d_T16,
-                          const vo_map_localise_stats* d_stats) {
-  (void)m;
-  if (!(K && d_uv && d_app && params && d_T16 && d_stats)) return fail(VO_ERR_INVALID_ARG, "%s: null argument", fn);
-  if (n_max < 1) return fail(VO_ERR_INVALID_ARG, "%s: n_max must be positive", fn);
-  if (n_iters < 1) return fail(VO_ERR_INVALID_ARG, "%s: n_iters must be positive", fn);
-  if (min_inliers < 0) return fail(VO_ERR_INVALID_ARG, "%s: negative min_inliers", fn);
-  if (!aligned8(d_uv, d_app, d_stats)) return fail(VO_ERR_INVALID_ARG, "%s: device arrays must be 8-byte aligned", fn);
-  if (params->n_hypotheses == 0) {
-    if (!d_T0) return fail(VO_ERR_INVALID_ARG, "%s: n_hypotheses == 0 (no RANSAC) needs the prior d_T0", fn);
-  } else if (int r = ransac_check_params(params)) {
-    return r;
-  }
-  double Kinv[9];
-  if (!invert_k(K, Kinv)) return fail(VO_ERR_INVALID_ARG, "%s: K is singular", fn);
-  return VO_OK;
-}
-
-int vo_map_localise_dev(vo_map* m, int rows, int cols, int z_near, int z_far, const float K[9], const float* d_uv, const float* d_app,
-                        int n_max, const int* d_n, const vo_ransac_params* params, float thr, int n_iters, int min_inliers,
-                        const float* d_T0, float* d_T16, vo_map_localise_stats* d_stats) {
-  VO_MAP_LIVE(m);
-  if (int r = localise_check("vo_map_localise_dev", m, K, d_uv, d_app, n_max, params, n_iters, min_inliers, d_T0, d_T16, d_stats)) return r;
-  vo_ctx* c = m->ctx;
-  const size_t need = localise_layout(nullptr, 1, n_max).bytes;
-  if (c->capturing && (m->loc_ws.cap < need || !m->solver))
-    return fail(VO_ERR_NOT_READY, "vo_map_localise_dev: the workspace would have to grow inside a graph capture (make one call with n_max "
-                                  "%d before capturing)", n_max);
-  if (int r = set_device(c)) return r;
-  if (!m->solver) { if (int r = vo_picp_create(c, &m->solver)) return r; }
-  VO_HIP_CHECK(m->loc_ws.ensure(need, c->stream));
-  const LocaliseWs w = localise_layout(m->loc_ws.p, 1, n_max);
-  // 1. the lookup, with the hits' points gathered
-  if (int r = vo_map_lookup_dev(m, d_app, n_max, d_n, w.pairs, w.n_hits, w.xyz, w.local, nullptr)) return r;
-  // 2. the start pose and the pairs handed on
-  const bool ransac = params->n_hypotheses > 0;
-  if (ransac) {
-    if (int r = vo_estimate_pose_ransac_dev(c, rows, cols, z_near, z_far, K, w.xyz, n_max, d_uv, n_max, w.local, n_max, w.n_hits, params,
-                                            w.T_start, w.handed, w.n_handed, nullptr, nullptr, w.rstat))
-      return r;
-  }
-  // 3. the rounds (vo_picp_set_camera / _set_kernel_threshold without the pose upload: the pose comes from device memory)
-  vo_picp* s = m->solver;
-  {
-    const CamK cam = make_cam(rows, cols, z_near, z_far, K);
-    if (memcmp(&cam, &s->hp.cam, sizeof(cam)) != 0) { s->hp.cam = cam; s->params_dirty = true; }
-    if (memcmp(&thr, &s->hp.thr, sizeof(thr)) != 0) { s->hp.thr = thr; s->params_dirty = true; }
-  }
-  if (int r = vo_picp_set_points_dev(s, w.xyz, n_max, d_uv, n_max)) return r;
-  if (int r = vo_picp_set_pose_dev(s, ransac ? w.T_start : d_T0)) return r;
-  if (int r = vo_picp_solve_dev(s, ransac ? w.handed : w.local, n_max, ransac ? w.n_handed : w.n_hits, 0, n_iters)) return r;
-  // 4. status, pose, statistics
-  MapLocaliseFinish f{};
-  f.n_frames = 1; f.n_max = n_max; f.d_n = d_n; f.n_hits = w.n_hits; f.ransac_status = ransac ? w.rstat : nullptr;
-  f.n_handed = ransac ? w.n_handed : w.n_hits; f.state = s->d_state; f.T0 = d_T0; f.min_inliers = min_inliers;
-  f.T_out = d_T16; f.stats = reinterpret_cast<int*>(d_stats);
-  VO_HIP_CHECK(launch_map_localise_finish(c->stream, f));
-  return VO_OK;
-}
-
-int vo_map_localise_batch_dev(vo_map* m, int n_frames, int rows, int cols, int z_near, int z_far, const float K[9], const float* d_uv,
-                              size_t uv_stride, const float* d_app, size_t app_stride, int n_max, const int* d_n,
-                              const vo_ransac_params* params, float thr, int n_iters, int min_inliers, const float* d_T0, float* d_T16,
-                              vo_map_localise_stats* d_stats) {
-  VO_MAP_LIVE(m);
-  if (int r = localise_check("vo_map_localise_batch_dev", m, K, d_uv, d_app, n_max, params, n_iters, min_inliers, d_T0, d_T16, d_stats)) return r;
-  VO_REQUIRE(n_frames >= 1 && n_frames <= 65535, "n_frames outside 1 .. 65535 (the frame is a grid dimension)");
-  VO_REQUIRE(uv_stride >= (size_t)n_max && app_stride >= (size_t)n_max, "a stride is smaller than n_max");
-  VO_REQUIRE(uv_stride < 0x7fffffff, "stride too large");
-  vo_ctx* c = m->ctx;
-  const size_t need = localise_layout(nullptr, n_frames, n_max).bytes;
-  if (c->capturing && m->loc_ws.cap < need)
-    return fail(VO_ERR_NOT_READY, "vo_map_localise_batch_dev: the workspace would have to grow inside a graph capture (make one call with "
-                                  "%d frames of n_max %d before capturing)", n_frames, n_max);
-  if (int r = set_device(c)) return r;
-  VO_HIP_CHECK(m->loc_ws.ensure(need, c->stream));
-  const LocaliseWs w = localise_layout(m->loc_ws.p, n_frames, n_max);
-  if (int r = vo_map_lookup_batch_dev(m, n_frames, d_app, app_stride, n_max, d_n, w.pairs, w.n_hits, w.xyz, w.local, nullptr)) return r;
-  const bool ransac = params->n_hypotheses > 0;
-  if (ransac) {
-    if (int r = vo_estimate_pose_ransac_batch_dev(c, n_frames, rows, cols, z_near, z_far, K, w.xyz, (size_t)n_max, n_max, d_uv, uv_stride,
-                                                  n_max, w.local, (size_t)n_max, w.n_hits, params, w.T_start, w.handed, w.n_handed,
-                                                  nullptr, nullptr, w.rstat))
-      return r;
-  }
-  if (int r = vo_picp_solve_batch_dev(c, n_frames, rows, cols, z_near, z_far, K, thr, 0, w.xyz, (size_t)n_max, d_uv, uv_stride,
-                                      ransac ? w.handed : w.local, (size_t)n_max, ransac ? w.n_handed : w.n_hits,
-                                      ransac ? w.T_start : d_T0, n_iters, w.T_solved, w.stats4))
-    return r;
-  MapLocaliseFinish f{};
-  f.n_frames = n_frames; f.n_max = n_max; f.d_n = d_n; f.n_hits = w.n_hits; f.ransac_status = ransac ? w.rstat : nullptr;
-  f.n_handed = ransac ? w.n_handed : w.n_hits; f.state = nullptr; f.T_solved = w.T_solved; f.stats4 = w.stats4; f.T0 = d_T0;
-  f.min_inliers = min_inliers; f.T_out = d_T16; f.stats = reinterpret_cast<int*>(d_stats);
-  VO_HIP_CHECK(launch_map_localise_finish(c->stream, f));
-  return VO_OK;
-}
-
-int vo_map_localise(vo_map* m, int rows, int cols, int z_near, int z_far, const float K[9], const float* uv, const float* app, int n,
-                    const vo_ransac_params* params, float thr, int n_iters, int min_inliers, const float T0[16], float T_out[16],
-                    vo_map_localise_stats* stats_out) {
-  VO_MAP_LIVE(m);
-  vo_ctx* c = m->ctx;
-  VO_NOT_CAPTURING(c);
-  VO_REQUIRE(K && uv && app && params && T_out && stats_out, "null argument");
-  VO_REQUIRE(n >= 1, "n must be positive");
-  if (int r = set_device(c)) return r;
-  if (int r = upload(c, c->in[0], uv, sizeof(float) * 2 * (size_t)n)) return r;
-  if (int r = upload(c, c->in[1], app, sizeof(float) * 10 * (size_t)n)) return r;
-  if (T0)
-    if (int r = upload(c, c->in[2], T0, sizeof(float) * 16)) return r;
-  VO_HIP_CHECK(c->out[2].ensure(128, c->stream));
-  VO_HIP_CHECK(hipStreamSynchronize(c->stream));          // the host arrays may go away after the call
-  struct { float T[16]; vo_map_localise_stats s; } h;
-  static_assert(sizeof(h) == 96, "pose and statistics come back in one copy");
-  char* d_res = c->out[2].as<char>();
-  if (int r = vo_map_localise_dev(m, rows, cols, z_near, z_far, K, c->in[0].as<float>(), c->in[1].as<float>(), n, nullptr, params, thr,
-                                  n_iters, min_inliers, T0 ? c->in[2].as<float>() : nullptr, reinterpret_cast<float*>(d_res),
-                                  reinterpret_cast<vo_map_localise_stats*>(d_res + 64)))
-    return r;
-  VO_HIP_CHECK(hipMemcpyAsync(&h, d_res, sizeof(h), hipMemcpyDeviceToHost, c->stream));
-  VO_HIP_CHECK(hipStreamSynchronize(c->stream));
-  memcpy(T_out, h.T, sizeof(h.T));
-  *stats_out = h.s;
-  return VO_OK;
-}
-
-// ---- structure-only refinement: the lookup of every frame, then the launches of map_refine.hip ----------------------------
-static_assert(sizeof(vo_map_refine_params) == 16 && sizeof(vo_map_refine_stats) == 48, "the statistics kernel writes eight 4-byte words and two doubles");
-
-// the refusals the refinement calls share (both halves of the adjustment take the same frames)
-static int refine_check(const char* fn, int n_frames, const float K[9], const float* d_uv, size_t uv_stride, const float* d_app, size_t app_stride,
-                        int n_max, const void* d_stats, int n_rounds, int most_rounds, int min_obs, int least_obs, float huber_px, float damping) {
-  if (n_frames < 1 || n_frames > 65535) return fail(VO_ERR_INVALID_ARG, "%s: n_frames %d outside 1 .. 65535 (the frame is a grid dimension)", fn, n_frames);
-  if (n_max < 0) return fail(VO_ERR_INVALID_ARG, "%s: negative row count", fn);
-  if (n_max > 0 && !(d_uv && d_app)) return fail(VO_ERR_INVALID_ARG, "%s: null argument", fn);
-  if (!aligned8(d_uv, d_app, d_stats)) return fail(VO_ERR_INVALID_ARG, "%s: device arrays must be 8-byte aligned", fn);
-  if (uv_stride < (size_t)n_max || app_stride < (size_t)n_max) return fail(VO_ERR_INVALID_ARG, "%s: a stride is smaller than n_max", fn);
-  if (uv_stride >= 0x7fffffff) return fail(VO_ERR_INVALID_ARG, "%s: stride too large", fn);
-  if (n_rounds < 0) return fail(VO_ERR_INVALID_ARG, "%s: negative n_rounds", fn);
-  if (n_rounds > most_rounds) return fail(VO_ERR_INVALID_ARG, "%s: more than %d rounds", fn, most_rounds);
-  if (min_obs < least_obs) return fail(VO_ERR_INVALID_ARG, "%s: min_obs must be at least %d", fn, least_obs);
-  if (!(huber_px >= 0.f && huber_px <= 3.402823466e38f)) return fail(VO_ERR_INVALID_ARG, "%s: huber_px must be finite and not negative", fn);
-  if (!(damping >= 0.f && damping <= 3.402823466e38f)) return fail(VO_ERR_INVALID_ARG, "%s: damping must be finite and not negative", fn);
-  double Kinv[9];
-  if (!invert_k(K, Kinv)) return fail(VO_ERR_INVALID_ARG, "%s: K is singular", fn);
-  if (app_stride >= 0x7fffffff / 10 || (long long)n_max * n_frames > (1ll << 30))      // (the lookup's own limit, met before anything is sized)
-    return fail(VO_ERR_INVALID_ARG, "%s: more than 2^30 rows in one call", fn);
-  return VO_OK;
-}
-
-// the point half's workspace, sized and laid out, and the lookup of every frame into it
-static int refine_prepare(const char* fn, vo_map* m, int n_frames, const float* d_app, size_t app_stride, int n_max, const int* d_n, MapRefineWs* out) {
-  vo_ctx* c = m->ctx;
-  const int bound = map_bound(m);
-  MapRefineWs w = map_refine_layout(nullptr, n_frames, n_max, bound);
-  const size_t look_need = sizeof(int) * map_lookup_scratch_ints(n_max, n_frames, false);
-  if (c->capturing && (m->ref_ws.cap < w.bytes || (n_max > 0 && m->look_ws.cap < look_need)))
-    return fail(VO_ERR_NOT_READY, "%s: the workspace would have to grow inside a graph capture (make one call with %d frames of n_max %d "
-                                  "on this map before capturing)", fn, n_frames, n_max);
-  if (int r = set_device(c)) return r;
-  VO_HIP_CHECK(m->ref_ws.ensure(w.bytes, c->stream));
-  w = map_refine_layout(m->ref_ws.p, n_frames, n_max, bound);
-  if (n_max > 0)
-    if (int r = vo_map_lookup_batch_dev(m, n_frames, d_app, app_stride, n_max, d_n, w.pairs, w.n_hits, nullptr, nullptr, w.ent)) return r;
-  *out = w;
-  return VO_OK;
-}
-
-// the point half's launches on a prepared workspace
-static int refine_run(vo_map* m, const MapRefineWs& w, int n_frames, const float K[9], const float* d_uv, size_t uv_stride, int n_max,
-                      const float* d_T16, int n_rounds, int min_obs, float huber_px, float damping, int32_t* d_status_out, float* d_xyz_out,
-                      vo_map_refine_stats* d_stats) {
-  vo_ctx* c = m->ctx;
-  MapRefineArgs a{};
-  a.w = w;
-  a.pts = m->d.pts; a.hdr = m->d.hdr; a.cap = m->d.cap; a.bound = map_bound(m);
-  a.uv = d_uv; a.uv_stride = uv_stride; a.n_max = n_max; a.n_frames = n_frames; a.T16 = d_T16;
-  for (int k = 0; k < 9; ++k) a.K[k] = K[k];
-  a.n_rounds = n_rounds; a.min_obs = min_obs; a.huber = huber_px; a.damping = damping;
-  a.status = d_status_out ? d_status_out : w.status;
-  a.xyz_out = d_xyz_out; a.stats = d_stats;
-  VO_HIP_CHECK(launch_map_refine(c->stream, a, c->n_cu));
-  return VO_OK;
-}
-
-int vo_map_refine_batch_dev(vo_map* m, int n_frames, const float K[9], const float* d_uv, size_t uv_stride, const float* d_app,
-                            size_t app_stride, int n_max, const int* d_n, const float* d_T16, const vo_map_refine_params* params,
-                            int32_t* d_status_out, float* d_xyz_out, vo_map_refine_stats* d_stats) {
-  VO_MAP_LIVE(m);
-  const char* fn = "vo_map_refine_batch_dev";
-  if (!(K && params && d_T16 && d_stats)) return fail(VO_ERR_INVALID_ARG, "%s: null argument", fn);
-  if (int r = refine_check(fn, n_frames, K, d_uv, uv_stride, d_app, app_stride, n_max, d_stats, params->n_rounds, INT_MAX, params->min_obs, 2,
-                           params->huber_px, params->damping))
-    return r;
-  MapRefineWs w;
-  if (int r = refine_prepare(fn, m, n_frames, d_app, app_stride, n_max, d_n, &w)) return r;
-  return refine_run(m, w, n_frames, K, d_uv, uv_stride, n_max, d_T16, params->n_rounds, params->min_obs, params->huber_px, params->damping,
-                    d_status_out, d_xyz_out, d_stats);
-}
-
-int vo_map_refine(vo_map* m, int n_frames, const float K[9], const float* uv, const float* app, const int* n_rows, int n_max,
-                  const float* T16, const vo_map_refine_params* params, int32_t* status_out, vo_map_refine_stats* stats_out) {
-  VO_MAP_LIVE(m);
-  vo_ctx* c = m->ctx;
-  VO_NOT_CAPTURING(c);
-  VO_REQUIRE(K && T16 && params && stats_out, "null argument");
-  VO_REQUIRE(n_frames >= 1 && n_frames <= 65535, "n_frames outside 1 .. 65535");
-  VO_REQUIRE(n_max >= 0 && (n_max == 0 || (uv && app)), "bad frames");
-  VO_REQUIRE((long long)n_max * n_frames <= (1ll << 30), "more than 2^30 rows in one call");
-  if (int r = set_device(c)) return r;
-  const size_t rows = (size_t)n_frames * (size_t)n_max;
-  if (int r = upload(c, c->in[0], uv, sizeof(float) * 2 * rows)) return r;
-  if (int r = upload(c, c->in[1], app, sizeof(float) * 10 * rows)) return r;
-  if (int r = upload(c, c->in[2], T16, sizeof(float) * 16 * (size_t)n_frames)) return r;
-  if (n_rows)
-    if (int r = upload(c, c->in[3], n_rows, sizeof(int) * (size_t)n_frames)) return r;
-  int size = 0;
-  if (int r = vo_map_size(m, &size)) return r;                // (waits: the host arrays may go away after the call)
-  VO_HIP_CHECK(c->out[2].ensure(sizeof(vo_map_refine_stats) + 16, c->stream));
-  if (status_out) VO_HIP_CHECK(c->out[1].ensure(sizeof(int32_t) * (size_t)(size > 0 ? size : 1), c->stream));
-  if (int r = vo_map_refine_batch_dev(m, n_frames, K, c->in[0].as<float>(), (size_t)n_max, c->in[1].as<float>(), (size_t)n_max, n_max,
-                                      n_rows ? c->in[3].as<int>() : nullptr, c->in[2].as<float>(), params,
-                                      status_out ? c->out[1].as<int32_t>() : nullptr, nullptr, c->out[2].as<vo_map_refine_stats>()))
-    return r;
-  VO_HIP_CHECK(hipMemcpyAsync(stats_out, c->out[2].p, sizeof(vo_map_refine_stats), hipMemcpyDeviceToHost, c->stream));
-  if (status_out && size > 0) VO_HIP_CHECK(hipMemcpyAsync(status_out, c->out[1].p, sizeof(int32_t) * (size_t)size, hipMemcpyDeviceToHost, c->stream));
-  VO_HIP_CHECK(hipStreamSynchronize(c->stream));
-  return VO_OK;
-}
-
-// ---- motion-only refinement and the alternation of the two halves (map_pose_refine.hip) ------------------------------------
-static_assert(sizeof(vo_map_pose_refine_params) == 16 && sizeof(vo_map_pose_refine_stats) == 48 && sizeof(vo_map_adjust_params) == 28 &&
-              sizeof(vo_map_adjust_stats) == 96, "the statistics kernels write eight 4-byte words and two doubles each");
-
-// the pose half's workspace; with `ent` (the entries of a lookup already made for these frames) no lookup is enqueued
-static int pose_prepare(const char* fn, vo_map* m, int n_frames, const float* d_app, size_t app_stride, int n_max, const int* d_n,
-                        const int32_t* ent, MapPoseWs* out) {
-  vo_ctx* c = m->ctx;
-  MapPoseWs w = map_pose_layout(nullptr, n_frames, n_max, !ent);
-  const size_t look_need = sizeof(int) * map_lookup_scratch_ints(n_max, n_frames, false);
-  if (c->capturing && (m->pose_ws.cap < w.bytes || (!ent && n_max > 0 && m->look_ws.cap < look_need)))
-    return fail(VO_ERR_NOT_READY, "%s: the workspace would have to grow inside a graph capture (make one call with %d frames of n_max %d "
-                                  "on this map before capturing)", fn, n_frames, n_max);
-  if (int r = set_device(c)) return r;
-  VO_HIP_CHECK(m->pose_ws.ensure(w.bytes, c->stream));
-  w = map_pose_layout(m->pose_ws.p, n_frames, n_max, !ent);
-  if (!ent && n_max > 0)
-    if (int r = vo_map_lookup_batch_dev(m, n_frames, d_app, app_stride, n_max, d_n, w.pairs, w.n_hits, nullptr, nullptr, w.ent)) return r;
-  *out = w;
-  return VO_OK;
-}
-
-static int pose_run(vo_map* m, const MapPoseWs& w, const int32_t* ent, int n_frames, const float K[9], const float* d_uv, size_t uv_stride,
-                    int n_max, const float* d_T_in, const uint8_t* d_fixed, int n_rounds, int min_obs, float huber_px, float damping,
-                    float* d_T_out, int32_t* d_status_out, double* d_H_out, vo_map_pose_refine_stats* d_stats) {
-  vo_ctx* c = m->ctx;
-  MapPoseArgs a{};
-  a.ent = ent ? ent : w.ent; a.n_obs = w.n_obs; a.cost = w.cost;
-  a.pts = m->d.pts; a.hdr = m->d.hdr; a.cap = m->d.cap; a.bound = map_bound(m);
-  a.uv = d_uv; a.uv_stride = uv_stride; a.n_max = n_max; a.n_frames = n_frames;
-  a.T_in = d_T_in; a.T_out = d_T_out; a.fixed = d_fixed;
-  for (int k = 0; k < 9; ++k) a.K[k] = K[k];
-  a.n_rounds = n_rounds; a.min_obs = min_obs; a.huber = huber_px; a.damping = damping;
-  a.status = d_status_out ? d_status_out : w.status;
-  a.H_out = d_H_out; a.stats = d_stats;
-  VO_HIP_CHECK(launch_map_pose_refine(c->stream, a));
-  return VO_OK;
-}
-
-int vo_map_refine_poses_batch_dev(vo_map* m, int n_frames, const float K[9], const float* d_uv, size_t uv_stride, const float* d_app,
-                                  size_t app_stride, int n_max, const int* d_n, const float* d_T16_in, const uint8_t* d_fixed,
-                                  const vo_map_pose_refine_params* params, float* d_T16_out, int32_t* d_status_out, double* d_H_out,
-                                  vo_map_pose_refine_stats* d_stats) {
-  VO_MAP_LIVE(m);
-  const char* fn = "vo_map_refine_poses_batch_dev";
-  if (!(K && params && d_T16_in && d_T16_out && d_stats)) return fail(VO_ERR_INVALID_ARG, "%s: null argument", fn);
-  if (!aligned8(d_H_out)) return fail(VO_ERR_INVALID_ARG, "%s: device arrays must be 8-byte aligned", fn);
-  if (int r = refine_check(fn, n_frames, K, d_uv, uv_stride, d_app, app_stride, n_max, d_stats, params->n_rounds, VO_MAP_ADJUST_MAX_ROUNDS, params->min_obs, 3,
-                           params->huber_px, params->damping))
-    return r;
-  MapPoseWs w;
-  if (int r = pose_prepare(fn, m, n_frames, d_app, app_stride, n_max, d_n, nullptr, &w)) return r;
-  return pose_run(m, w, nullptr, n_frames, K, d_uv, uv_stride, n_max, d_T16_in, d_fixed, params->n_rounds, params->min_obs, params->huber_px,
-                  params->damping, d_T16_out, d_status_out, d_H_out, d_stats);
-}
-
-int vo_map_adjust_batch_dev(vo_map* m, int n_frames, const float K[9], const float* d_uv, size_t uv_stride, const float* d_app,
-                            size_t app_stride, int n_max, const int* d_n, float* d_T16, const uint8_t* d_fixed,
-                            const vo_map_adjust_params* p, int32_t* d_pose_status_out, int32_t* d_point_status_out,
-                            vo_map_adjust_stats* d_stats) {
-  VO_MAP_LIVE(m);
-  const char* fn = "vo_map_adjust_batch_dev";
-  if (!(K && p && d_T16 && d_stats)) return fail(VO_ERR_INVALID_ARG, "%s: null argument", fn);
-  if (p->n_sweeps < 1 || p->n_sweeps > VO_MAP_ADJUST_MAX_ROUNDS) return fail(VO_ERR_INVALID_ARG, "%s: n_sweeps outside 1 .. %d", fn, VO_MAP_ADJUST_MAX_ROUNDS);
-  if (int r = refine_check(fn, n_frames, K, d_uv, uv_stride, d_app, app_stride, n_max, d_stats, p->pose_rounds, VO_MAP_ADJUST_MAX_ROUNDS, p->min_obs_pose, 3, p->huber_px,
-                           p->damping))
-    return r;
-  if (int r = refine_check(fn, n_frames, K, d_uv, uv_stride, d_app, app_stride, n_max, d_stats, p->point_rounds, VO_MAP_ADJUST_MAX_ROUNDS, p->min_obs_point, 2,
-                           p->huber_px, p->damping))
-    return r;
-  vo_ctx* c = m->ctx;
-  if (c->capturing && m->pose_ws.cap < map_pose_layout(nullptr, n_frames, n_max, false).bytes)      // (before the point half enqueues its lookup)
-    return fail(VO_ERR_NOT_READY, "%s: the workspace would have to grow inside a graph capture (make one call with %d frames of n_max %d "
-                                  "on this map before capturing)", fn, n_frames, n_max);
-  MapRefineWs rw;
-  MapPoseWs pw;
-  if (int r = refine_prepare(fn, m, n_frames, d_app, app_stride, n_max, d_n, &rw)) return r;      // the one lookup: both halves read rw.ent
-  if (int r = pose_prepare(fn, m, n_frames, d_app, app_stride, n_max, d_n, rw.ent, &pw)) return r;
-  for (int s = 0; s < p->n_sweeps; ++s) {
-    if (int r = pose_run(m, pw, rw.ent, n_frames, K, d_uv, uv_stride, n_max, d_T16, d_fixed, p->pose_rounds, p->min_obs_pose, p->huber_px,
-                         p->damping, d_T16, d_pose_status_out, nullptr, &d_stats[s].poses))
-      return r;
-    if (int r = refine_run(m, rw, n_frames, K, d_uv, uv_stride, n_max, d_T16, p->point_rounds, p->min_obs_point, p->huber_px, p->damping,
-                           d_point_status_out, nullptr, &d_stats[s].points))
-      return r;
-  }
-  return VO_OK;
-}
-
-// the frames of a host call into the context's staging buffers in[0..4]: pixels, appearances, poses, row counts, the mask
-static int upload_window(vo_ctx* c, int n_frames, const float* uv, const float* app, const int* n_rows, int n_max, const float* T16,
-                         const uint8_t* fixed) {
-  const size_t rows = (size_t)n_frames * (size_t)n_max;
-  if (int r = upload(c, c->in[0], uv, sizeof(float) * 2 * rows)) return r;
-  if (int r = upload(c, c->in[1], app, sizeof(float) * 10 * rows)) return r;
-  if (int r = upload(c, c->in[2], T16, sizeof(float) * 16 * (size_t)n_frames)) return r;
-  if (n_rows)
-    if (int r = upload(c, c->in[3], n_rows, sizeof(int) * (size_t)n_frames)) return r;
-  if (fixed)
-    if (int r = upload(c, c->in[4], fixed, (size_t)n_frames)) return r;
-  return VO_OK;
-}
-
-int vo_map_refine_poses(vo_map* m, int n_frames, const float K[9], const float* uv, const float* app, const int* n_rows, int n_max,
-                        float* T16, const uint8_t* fixed, const vo_map_pose_refine_params* params, int32_t* status_out, double* H_out,
-                        vo_map_pose_refine_stats* stats_out) {
-  VO_MAP_LIVE(m);
-  vo_ctx* c = m->ctx;
-  VO_NOT_CAPTURING(c);
-  VO_REQUIRE(K && T16 && params && stats_out, "null argument");
-  VO_REQUIRE(n_frames >= 1 && n_frames <= 65535, "n_frames outside 1 .. 65535");
-  VO_REQUIRE(n_max >= 0 && (n_max == 0 || (uv && app)), "bad frames");
-  VO_REQUIRE((long long)n_max * n_frames <= (1ll << 30), "more than 2^30 rows in one call");
-  if (int r = set_device(c)) return r;
-  if (int r = upload_window(c, n_frames, uv, app, n_rows, n_max, T16, fixed)) return r;
-  const size_t F = (size_t)n_frames;
-  VO_HIP_CHECK(c->out[0].ensure(sizeof(double) * 36 * F, c->stream));
-  VO_HIP_CHECK(c->out[1].ensure(sizeof(int32_t) * F, c->stream));
-  VO_HIP_CHECK(c->out[2].ensure(sizeof(vo_map_pose_refine_stats) + 16, c->stream));
-  if (H_out) VO_HIP_CHECK(hipMemcpyAsync(c->out[0].p, H_out, sizeof(double) * 36 * F, hipMemcpyHostToDevice, c->stream));
-  if (int r = vo_map_refine_poses_batch_dev(m, n_frames, K, c->in[0].as<float>(), (size_t)n_max, c->in[1].as<float>(), (size_t)n_max, n_max,
-                                            n_rows ? c->in[3].as<int>() : nullptr, c->in[2].as<float>(), fixed ? c->in[4].as<uint8_t>() : nullptr,
-                                            params, c->in[2].as<float>(), status_out ? c->out[1].as<int32_t>() : nullptr,
-                                            H_out ? c->out[0].as<double>() : nullptr, c->out[2].as<vo_map_pose_refine_stats>()))
-    return r;
-  VO_HIP_CHECK(hipMemcpyAsync(stats_out, c->out[2].p, sizeof(vo_map_pose_refine_stats), hipMemcpyDeviceToHost, c->stream));
-  VO_HIP_CHECK(hipMemcpyAsync(T16, c->in[2].p, sizeof(float) * 16 * F, hipMemcpyDeviceToHost, c->stream));
-  if (status_out) VO_HIP_CHECK(hipMemcpyAsync(status_out, c->out[1].p, sizeof(int32_t) * F, hipMemcpyDeviceToHost, c->stream));
-  if (H_out) VO_HIP_CHECK(hipMemcpyAsync(H_out, c->out[0].p, sizeof(double) * 36 * F, hipMemcpyDeviceToHost, c->stream));
-  VO_HIP_CHECK(hipStreamSynchronize(c->stream));
-  return VO_OK;
-}
-
-int vo_map_adjust(vo_map* m, int n_frames, const float K[9], const float* uv, const float* app, const int* n_rows, int n_max, float* T16,
-                  const uint8_t* fixed, const vo_map_adjust_params* params, int32_t* pose_status_out, int32_t* point_status_out,
-                  vo_map_adjust_stats* stats_out) {
-  VO_MAP_LIVE(m);
-  vo_ctx* c = m->ctx;
-  VO_NOT_CAPTURING(c);
-  VO_REQUIRE(K && T16 && params && stats_out, "null argument");
-  VO_REQUIRE(params->n_sweeps >= 1 && params->n_sweeps <= VO_MAP_ADJUST_MAX_ROUNDS, "n_sweeps outside 1 .. 65536");
-  VO_REQUIRE(n_frames >= 1 && n_frames <= 65535, "n_frames outside 1 .. 65535");
-  VO_REQUIRE(n_max >= 0 && (n_max == 0 || (uv && app)), "bad frames");
-  VO_REQUIRE((long long)n_max * n_frames <= (1ll << 30), "more than 2^30 rows in one call");
-  if (int r = set_device(c)) return r;
-  if (int r = upload_window(c, n_frames, uv, app, n_rows, n_max, T16, fixed)) return r;
-  int size = 0;
-  if (int r = vo_map_size(m, &size)) return r;                // (waits: the host arrays may go away after the call)
-  const size_t F = (size_t)n_frames, S = (size_t)params->n_sweeps;
-  VO_HIP_CHECK(c->out[0].ensure(sizeof(int32_t) * F, c->stream));
-  if (point_status_out) VO_HIP_CHECK(c->out[1].ensure(sizeof(int32_t) * (size_t)(size > 0 ? size : 1), c->stream));
-  VO_HIP_CHECK(c->out[2].ensure(sizeof(vo_map_adjust_stats) * S + 16, c->stream));
-  if (int r = vo_map_adjust_batch_dev(m, n_frames, K, c->in[0].as<float>(), (size_t)n_max, c->in[1].as<float>(), (size_t)n_max, n_max,
-                                      n_rows ? c->in[3].as<int>() : nullptr, c->in[2].as<float>(), fixed ? c->in[4].as<uint8_t>() : nullptr,
-                                      params, pose_status_out ? c->out[0].as<int32_t>() : nullptr,
-                                      point_status_out ? c->out[1].as<int32_t>() : nullptr, c->out[2].as<vo_map_adjust_stats>()))
-    return r;
-  VO_HIP_CHECK(hipMemcpyAsync(stats_out, c->out[2].p, sizeof(vo_map_adjust_stats) * S, hipMemcpyDeviceToHost, c->stream));
-  VO_HIP_CHECK(hipMemcpyAsync(T16, c->in[2].p, sizeof(float) * 16 * F, hipMemcpyDeviceToHost, c->stream));
-  if (pose_status_out) VO_HIP_CHECK(hipMemcpyAsync(pose_status_out, c->out[0].p, sizeof(int32_t) * F, hipMemcpyDeviceToHost, c->stream));
-  if (point_status_out && size > 0)
-    VO_HIP_CHECK(hipMemcpyAsync(point_status_out, c->out[1].p, sizeof(int32_t) * (size_t)size, hipMemcpyDeviceToHost, c->stream));
-  VO_HIP_CHECK(hipStreamSynchronize(c->stream));
-  return VO_OK;
-}
-
-// ---- joint adjustment by matrix-free Schur PCG (map_bundle.hip; include/vo_map_bundle.h: the vox_ namespace) ---------------
-static_assert(sizeof(vox_map_bundle_params) == 28 && sizeof(vox_map_bundle_round) == 40 && sizeof(vox_map_bundle_stats) == 48,
-              "the records of include/vo_map_bundle.h as the kernels write them");
-
-int vox_map_bundle_batch_dev(vo_map* m, int n_frames, const float K[9], const float* d_uv, size_t uv_stride, const float* d_app,
-                             size_t app_stride, int n_max, const int* d_n, float* d_T16, const uint8_t* d_fixed,
-                             const vox_map_bundle_params* p, int32_t* d_pose_status_out, int32_t* d_point_status_out,
-                             vox_map_bundle_round* d_rounds_out, vox_map_bundle_stats* d_stats) {
-  VO_MAP_LIVE(m);
-  const char* fn = "vox_map_bundle_batch_dev";
-  if (!(K && p && d_T16 && d_stats)) return fail(VO_ERR_INVALID_ARG, "%s: null argument", fn);
-  if (!aligned8(d_rounds_out)) return fail(VO_ERR_INVALID_ARG, "%s: device arrays must be 8-byte aligned", fn);
-  if (int r = refine_check(fn, n_frames, K, d_uv, uv_stride, d_app, app_stride, n_max, d_stats, p->n_rounds, VOX_MAP_BUNDLE_MAX_STEPS, p->min_obs_pose, 3,
-                           p->huber_px, 0.f))
-    return r;
-  if (p->min_obs_point < 2) return fail(VO_ERR_INVALID_ARG, "%s: min_obs_point must be at least 2", fn);
-  if (p->n_cg < 1) return fail(VO_ERR_INVALID_ARG, "%s: n_cg must be at least 1", fn);
-  if (!(p->cg_tol >= 0.f && p->cg_tol <= 3.402823466e38f)) return fail(VO_ERR_INVALID_ARG, "%s: cg_tol must be finite and not negative", fn);
-  if (!(p->lambda0 >= 0.f && p->lambda0 <= 3.402823466e38f)) return fail(VO_ERR_INVALID_ARG, "%s: lambda0 must be finite and not negative", fn);
-  if ((long long)p->n_rounds * ((long long)p->n_cg + 2) > VOX_MAP_BUNDLE_MAX_STEPS)
-    return fail(VO_ERR_INVALID_ARG, "%s: n_rounds * (n_cg + 2) above %d (the launches of a call are a fixed sequence)", fn, VOX_MAP_BUNDLE_MAX_STEPS);
-  vo_ctx* c = m->ctx;
-  const int bound = map_bound(m);
-  MapBundleWs bw = map_bundle_layout(nullptr, n_frames, bound);
-  if (c->capturing && m->bundle_ws.cap < bw.bytes)            // (before the lookup is enqueued)
-    return fail(VO_ERR_NOT_READY, "%s: the workspace would have to grow inside a graph capture (make one call with %d frames of n_max %d "
-                                  "on this map before capturing)", fn, n_frames, n_max);
-  MapRefineWs rw;
-  if (int r = refine_prepare(fn, m, n_frames, d_app, app_stride, n_max, d_n, &rw)) return r;      // the one lookup of the call
-  VO_HIP_CHECK(m->bundle_ws.ensure(bw.bytes, c->stream));
-  MapBundleArgs a{};
-  a.l = rw; a.w = map_bundle_layout(m->bundle_ws.p, n_frames, bound);
-  a.pts = m->d.pts; a.hdr = m->d.hdr; a.cap = m->d.cap; a.bound = bound;
-  a.uv = d_uv; a.uv_stride = uv_stride; a.n_max = n_max; a.n_frames = n_frames;
-  a.T16 = d_T16; a.fixed = d_fixed;
-  for (int k = 0; k < 9; ++k) a.K[k] = K[k];
-  a.n_rounds = p->n_rounds; a.n_cg = p->n_cg; a.min_obs_pose = p->min_obs_pose; a.min_obs_point = p->min_obs_point;
-  a.cg_tol = p->cg_tol; a.lambda0 = p->lambda0; a.huber = p->huber_px;
-  a.pose_status_out = d_pose_status_out; a.point_status_out = d_point_status_out; a.rounds_out = d_rounds_out; a.stats = d_stats;
-  VO_HIP_CHECK(launch_map_bundle(c->stream, a, c->n_cu));
-  return VO_OK;
-}
-
-int vox_map_bundle(vo_map* m, int n_frames, const float K[9], const float* uv, const float* app, const int* n_rows, int n_max, float* T16,
-                   const uint8_t* fixed, const vox_map_bundle_params* params, int32_t* pose_status_out, int32_t* point_status_out,
-                   vox_map_bundle_round* rounds_out, vox_map_bundle_stats* stats_out) {
-  VO_MAP_LIVE(m);
-  vo_ctx* c = m->ctx;
-  VO_NOT_CAPTURING(c);
-  VO_REQUIRE(K && T16 && params && stats_out, "null argument");
-  VO_REQUIRE(params->n_rounds >= 0 && params->n_rounds <= VOX_MAP_BUNDLE_MAX_STEPS, "n_rounds outside 0 .. 65536");
-  VO_REQUIRE(n_frames >= 1 && n_frames <= 65535, "n_frames outside 1 .. 65535");
-  VO_REQUIRE(n_max >= 0 && (n_max == 0 || (uv && app)), "bad frames");
-  VO_REQUIRE((long long)n_max * n_frames <= (1ll << 30), "more than 2^30 rows in one call");
-  if (int r = set_device(c)) return r;
-  if (int r = upload_window(c, n_frames, uv, app, n_rows, n_max, T16, fixed)) return r;
-  int size = 0;
-  if (int r = vo_map_size(m, &size)) return r;                // (waits: the host arrays may go away after the call)
-  const size_t F = (size_t)n_frames, S = (size_t)params->n_rounds;
-  VO_HIP_CHECK(c->out[0].ensure(sizeof(int32_t) * F, c->stream));
-  if (point_status_out) VO_HIP_CHECK(c->out[1].ensure(sizeof(int32_t) * (size_t)(size > 0 ? size : 1), c->stream));
-  VO_HIP_CHECK(c->out[2].ensure(sizeof(vox_map_bundle_stats) + sizeof(vox_map_bundle_round) * S + 16, c->stream));
-  vox_map_bundle_stats* d_st = c->out[2].as<vox_map_bundle_stats>();
-  vox_map_bundle_round* d_rd = reinterpret_cast<vox_map_bundle_round*>(d_st + 1);
-  if (int r = vox_map_bundle_batch_dev(m, n_frames, K, c->in[0].as<float>(), (size_t)n_max, c->in[1].as<float>(), (size_t)n_max, n_max,
-                                       n_rows ? c->in[3].as<int>() : nullptr, c->in[2].as<float>(), fixed ? c->in[4].as<uint8_t>() : nullptr,
-                                       params, pose_status_out ? c->out[0].as<int32_t>() : nullptr,
-                                       point_status_out ? c->out[1].as<int32_t>() : nullptr, rounds_out && S ? d_rd : nullptr, d_st))
-    return r;
-  VO_HIP_CHECK(hipMemcpyAsync(stats_out, d_st, sizeof(vox_map_bundle_stats), hipMemcpyDeviceToHost, c->stream));
-  if (rounds_out && S) VO_HIP_CHECK(hipMemcpyAsync(rounds_out, d_rd, sizeof(vox_map_bundle_round) * S, hipMemcpyDeviceToHost, c->stream));
-  VO_HIP_CHECK(hipMemcpyAsync(T16, c->in[2].p, sizeof(float) * 16 * F, hipMemcpyDeviceToHost, c->stream));
-  if (pose_status_out) VO_HIP_CHECK(hipMemcpyAsync(pose_status_out, c->out[0].p, sizeof(int32_t) * F, hipMemcpyDeviceToHost, c->stream));
-  if (point_status_out && size > 0)
-    VO_HIP_CHECK(hipMemcpyAsync(point_status_out, c->out[1].p, sizeof(int32_t) * (size_t)size, hipMemcpyDeviceToHost, c->stream));
-  VO_HIP_CHECK(hipStreamSynchronize(c->stream));
-  return VO_OK;
-}
-
-// ---- culling of landmarks (map_cull.hip; include/vo_map_cull.h: the voe_ namespace) ---------------------------------------
-static_assert(sizeof(voe_map_cull_params) == 28 && sizeof(voe_map_cull_entry) == 48 && sizeof(voe_map_cull_stats) == 48,
-              "the records of include/vo_map_cull.h as the kernels write them");
-
-static int cull_check_params(const char* fn, const voe_map_cull_params* p) {
-  if (p->min_obs < 1) return fail(VO_ERR_INVALID_ARG, "%s: min_obs must be at least 1", fn);
-  if (p->min_frames < 1) return fail(VO_ERR_INVALID_ARG, "%s: min_frames must be at least 1", fn);
-  if (!(p->max_rms_px >= 0.f && p->max_rms_px <= 3.402823466e38f)) return fail(VO_ERR_INVALID_ARG, "%s: max_rms_px must be finite and not negative", fn);
-  if (!(p->max_err_px >= 0.f && p->max_err_px <= 3.402823466e38f)) return fail(VO_ERR_INVALID_ARG, "%s: max_err_px must be finite and not negative", fn);
-  if (!(p->min_parallax_deg >= 0.f && p->min_parallax_deg < 180.f)) return fail(VO_ERR_INVALID_ARG, "%s: min_parallax_deg must be in [0, 180)", fn);
-  return VO_OK;
-}
-
-int voe_map_cull_batch_dev(vo_map* m, int n_frames, const float K[9], const float* d_uv, size_t uv_stride, const float* d_app,
-                           size_t app_stride, int n_max, const int* d_n, const float* d_T16, const voe_map_cull_params* p,
-                           int32_t* d_verdict_out, int32_t* d_remap_out, voe_map_cull_entry* d_entry_out, voe_map_cull_stats* d_stats) {
-  VO_MAP_LIVE(m);
-  const char* fn = "voe_map_cull_batch_dev";
-  if (!(K && p && d_T16 && d_stats)) return fail(VO_ERR_INVALID_ARG, "%s: null argument", fn);
-  if (!aligned8(d_entry_out)) return fail(VO_ERR_INVALID_ARG, "%s: device arrays must be 8-byte aligned", fn);
-  if (int r = refine_check(fn, n_frames, K, d_uv, uv_stride, d_app, app_stride, n_max, d_stats, 0, INT_MAX, 2, 2, 0.f, 0.f)) return r;
-  if (int r = cull_check_params(fn, p)) return r;
-  vo_ctx* c = m->ctx;
-  const int bound = map_bound(m);
-  MapCullWs cw = map_cull_layout(nullptr, bound);
-  if (c->capturing && m->cull_ws.cap < cw.bytes)              // (before the lookup is enqueued)
-    return fail(VO_ERR_NOT_READY, "%s: the workspace would have to grow inside a graph capture (make one call with %d frames of n_max %d "
-                                  "on this map before capturing)", fn, n_frames, n_max);
-  MapRefineWs rw;
-  if (int r = refine_prepare(fn, m, n_frames, d_app, app_stride, n_max, d_n, &rw)) return r;      // the one lookup of the call
-  VO_HIP_CHECK(m->cull_ws.ensure(cw.bytes, c->stream));
-  MapCullArgs a{};
-  a.l = rw; a.w = map_cull_layout(m->cull_ws.p, bound);
-  a.pts = m->d.pts; a.app = m->d.app; a.hdr = m->d.hdr; a.cap = m->d.cap; a.bound = bound;
-  a.uv = d_uv; a.uv_stride = uv_stride; a.n_max = n_max; a.n_frames = n_frames; a.T16 = d_T16;
-  for (int k = 0; k < 9; ++k) a.K[k] = K[k];
-  a.min_obs = p->min_obs; a.min_frames = p->min_frames; a.drop_unseen = p->drop_unseen != 0; a.dry_run = p->dry_run != 0;
-  a.max_mean_sq = (double)p->max_rms_px * (double)p->max_rms_px;
-  a.max_sq = (double)p->max_err_px * (double)p->max_err_px;
-  a.parallax = p->min_parallax_deg > 0.f;
-  a.cos_thr = a.parallax ? cos((double)p->min_parallax_deg * 3.14159265358979323846 / 180.0) : 1.0;
-  a.verdict = d_verdict_out ? d_verdict_out : a.w.verdict;
-  a.remap = d_remap_out ? d_remap_out : a.w.remap;
-  a.entry_out = d_entry_out; a.stats = d_stats;
-  VO_HIP_CHECK(launch_map_cull(c->stream, a, c->n_cu));
-  VO_HIP_CHECK(launch_map_rehash(c->stream, m->d, bound, a.w.ctl + 2));
-  VO_HIP_CHECK(launch_map_cull_stats(c->stream, a));
-  return VO_OK;
-}
-
-int voe_map_cull(vo_map* m, int n_frames, const float K[9], const float* uv, const float* app, const int* n_rows, int n_max,
-                 const float* T16, const voe_map_cull_params* params, int32_t* verdict_out, int32_t* remap_out,
-                 voe_map_cull_entry* entry_out, voe_map_cull_stats* stats_out) {
-  VO_MAP_LIVE(m);
-  vo_ctx* c = m->ctx;
-  VO_NOT_CAPTURING(c);
-  VO_REQUIRE(K && T16 && params && stats_out, "null argument");
-  VO_REQUIRE(n_frames >= 1 && n_frames <= 65535, "n_frames outside 1 .. 65535");
-  VO_REQUIRE(n_max >= 0 && (n_max == 0 || (uv && app)), "bad frames");
-  VO_REQUIRE((long long)n_max * n_frames <= (1ll << 30), "more than 2^30 rows in one call");
-  if (int r = set_device(c)) return r;
-  const size_t rows = (size_t)n_frames * (size_t)n_max;
-  if (int r = upload(c, c->in[0], uv, sizeof(float) * 2 * rows)) return r;
-  if (int r = upload(c, c->in[1], app, sizeof(float) * 10 * rows)) return r;
-  if (int r = upload(c, c->in[2], T16, sizeof(float) * 16 * (size_t)n_frames)) return r;
-  if (n_rows)
-    if (int r = upload(c, c->in[3], n_rows, sizeof(int) * (size_t)n_frames)) return r;
-  int size = 0;
-  if (int r = vo_map_size(m, &size)) return r;                // (waits: the host arrays may go away after the call)
-  const size_t S = (size_t)(size > 0 ? size : 1);
-  VO_HIP_CHECK(c->out[0].ensure(sizeof(int32_t) * 2 * S, c->stream));
-  VO_HIP_CHECK(c->out[1].ensure(sizeof(voe_map_cull_entry) * S, c->stream));
-  VO_HIP_CHECK(c->out[2].ensure(sizeof(voe_map_cull_stats) + 16, c->stream));
-  int32_t* d_verdict = c->out[0].as<int32_t>();
-  int32_t* d_remap = d_verdict + S;
-  if (int r = voe_map_cull_batch_dev(m, n_frames, K, c->in[0].as<float>(), (size_t)n_max, c->in[1].as<float>(), (size_t)n_max, n_max,
-                                     n_rows ? c->in[3].as<int>() : nullptr, c->in[2].as<float>(), params, verdict_out ? d_verdict : nullptr,
-                                     remap_out ? d_remap : nullptr, entry_out ? c->out[1].as<voe_map_cull_entry>() : nullptr,
-                                     c->out[2].as<voe_map_cull_stats>()))
-    return r;
-  VO_HIP_CHECK(hipMemcpyAsync(stats_out, c->out[2].p, sizeof(voe_map_cull_stats), hipMemcpyDeviceToHost, c->stream));
-  if (size > 0) {
-    if (verdict_out) VO_HIP_CHECK(hipMemcpyAsync(verdict_out, d_verdict, sizeof(int32_t) * (size_t)size, hipMemcpyDeviceToHost, c->stream));
-    if (remap_out) VO_HIP_CHECK(hipMemcpyAsync(remap_out, d_remap, sizeof(int32_t) * (size_t)size, hipMemcpyDeviceToHost, c->stream));
-    if (entry_out) VO_HIP_CHECK(hipMemcpyAsync(entry_out, c->out[1].p, sizeof(voe_map_cull_entry) * (size_t)size, hipMemcpyDeviceToHost, c->stream));
-  }
-  VO_HIP_CHECK(hipStreamSynchronize(c->stream));
-  if (!m->replayable && !params->dry_run) m->size_ub = stats_out->n_kept;
-  return VO_OK;
-}
-
-// ---- two maps: alignment by 3-point similarity RANSAC and the merge (map_align.hip; include/vo_map_align.h) ----------------
-static_assert(sizeof(voe_map_align_params) == 32 && sizeof(voe_map_align_stats) == 48 && sizeof(voe_map_merge_stats) == 16,
-              "the records of include/vo_map_align.h as the kernels write them");
-
-int voe_map_size_bound(vo_map* m, int* n_max_out) {
-  VO_MAP_LIVE(m);
-  VO_REQUIRE(n_max_out, "null argument");
-  *n_max_out = map_bound(m);
-  return VO_OK;
-}
-
-static int two_maps_check(const char* fn, const vo_map* dst, const vo_map* src) {
-  if (!dst || !src) return fail(VO_ERR_INVALID_ARG, "%s: null map", fn);
-  if (dst == src) return fail(VO_ERR_INVALID_ARG, "%s: src and dst are one map", fn);
-  if (!ctx_alive(dst->ctx, dst->ctx_id) || !ctx_alive(src->ctx, src->ctx_id))
-    return fail(VO_ERR_INVALID_ARG, "%s: the context a map was made on has been destroyed", fn);
-  if (dst->ctx != src->ctx) return fail(VO_ERR_INVALID_ARG, "%s: the maps live on different contexts", fn);
-  return VO_OK;
-}
-
-static int align_check_params(const char* fn, const voe_map_align_params* p) {
-  if (!p) return fail(VO_ERR_INVALID_ARG, "%s: null argument", fn);
-  if (p->n_hypotheses < 1 || p->n_hypotheses > 65536) return fail(VO_ERR_INVALID_ARG, "%s: n_hypotheses outside 1 .. 65536", fn);
-  if (p->n_refits < 0 || p->n_refits > VOE_MAP_ALIGN_MAX_REFITS)
-    return fail(VO_ERR_INVALID_ARG, "%s: n_refits outside 0 .. %d (the launches of a call are a fixed sequence)", fn, VOE_MAP_ALIGN_MAX_REFITS);
-  if (p->min_inliers < 0) return fail(VO_ERR_INVALID_ARG, "%s: min_inliers must not be negative", fn);
-  if (!(p->threshold > 0.f && p->threshold <= 3.402823466e38f)) return fail(VO_ERR_INVALID_ARG, "%s: threshold must be positive and finite", fn);
-  return VO_OK;
-}
-
-int voe_map_align_dev(vo_map* dst, vo_map* src, const voe_map_align_params* p, float* d_S16_out, int32_t* d_pairs_out, int* d_n_matches,
-                      uint8_t* d_inlier_mask, int32_t* d_hypothesis_counts, voe_map_align_stats* d_stats) {
-  const char* fn = "voe_map_align_dev";
-  if (int r = two_maps_check(fn, dst, src)) return r;
-  if (int r = align_check_params(fn, p)) return r;
-  if (!(d_S16_out && d_pairs_out && d_n_matches && d_stats)) return fail(VO_ERR_INVALID_ARG, "%s: null argument", fn);
-  if (!aligned8(d_pairs_out, d_stats)) return fail(VO_ERR_INVALID_ARG, "%s: d_pairs_out and d_stats must be 8-byte aligned", fn);
-  vo_ctx* c = dst->ctx;
-  const int n_max = map_bound(src);
-  size_t bytes = 0;
-  (void)map_align_layout(nullptr, n_max, p->n_hypotheses, &bytes);
-  if (c->capturing && dst->align_ws.cap < bytes)              // (before the lookup is enqueued)
-    return fail(VO_ERR_NOT_READY, "%s: the workspace would have to grow inside a graph capture (make one call with these maps and %d "
-                                  "hypotheses before capturing)", fn, p->n_hypotheses);
-  if (int r = set_device(c)) return r;
-  VO_HIP_CHECK(dst->align_ws.ensure(bytes, c->stream));
-  MapAlignArgs a = map_align_layout(dst->align_ws.p, n_max, p->n_hypotheses, nullptr);
-  // the matches: the public lookup, on dst, of src's appearances
-  if (int r = vo_map_lookup_dev(dst, src->d.app, n_max, src->d.hdr, d_pairs_out, d_n_matches, a.bxyz, nullptr, nullptr)) return r;
-  a.src_pts = src->d.pts; a.pairs = d_pairs_out; a.d_n = d_n_matches;
-  a.with_scale = p->with_scale != 0; a.n_refits = p->n_refits; a.min_inliers = p->min_inliers; a.seed = p->seed;
-  a.thr2 = p->threshold * p->threshold;
-  if (d_hypothesis_counts) a.counts = d_hypothesis_counts;
-  a.mask_out = d_inlier_mask;
-  a.S16_out = d_S16_out; a.stats = d_stats;
-  VO_HIP_CHECK(launch_map_align(c->stream, a));
-  return VO_OK;
-}
-
-int voe_map_align(vo_map* dst, vo_map* src, const voe_map_align_params* p, float S16_out[16], int32_t* pairs_out, int* n_matches_out,
-                  uint8_t* mask_out, int32_t* counts_out, voe_map_align_stats* stats_out) {
-  const char* fn = "voe_map_align";
-  if (int r = two_maps_check(fn, dst, src)) return r;
-  vo_ctx* c = dst->ctx;
-  VO_NOT_CAPTURING(c);
-  if (int r = align_check_params(fn, p)) return r;
-  VO_REQUIRE(S16_out && stats_out, "null argument");
-  if (int r = set_device(c)) return r;
-  int size = 0;
-  if (int r = vo_map_size(src, &size)) return r;              // (the bound becomes the size, unless an update of src was captured)
-  const size_t n = (size_t)(map_bound(src) > 0 ? map_bound(src) : 1), H = (size_t)p->n_hypotheses;
-  VO_HIP_CHECK(c->out[0].ensure(sizeof(int32_t) * 2 * n, c->stream));
-  VO_HIP_CHECK(c->out[1].ensure(up256(n) + sizeof(int32_t) * H, c->stream));
-  VO_HIP_CHECK(c->out[2].ensure(256, c->stream));
-  uint8_t* d_mask = c->out[1].as<uint8_t>();
-  int32_t* d_counts = reinterpret_cast<int32_t*>(d_mask + up256(n));
-  float* d_S = c->out[2].as<float>();
-  int* d_nm = reinterpret_cast<int*>(d_S + 16);
-  voe_map_align_stats* d_st = reinterpret_cast<voe_map_align_stats*>(d_S + 32);
-  if (int r = voe_map_align_dev(dst, src, p, d_S, c->out[0].as<int32_t>(), d_nm, mask_out ? d_mask : nullptr, counts_out ? d_counts : nullptr, d_st))
-    return r;
-  VO_HIP_CHECK(hipMemcpyAsync(S16_out, d_S, sizeof(float) * 16, hipMemcpyDeviceToHost, c->stream));
-  VO_HIP_CHECK(hipMemcpyAsync(stats_out, d_st, sizeof(voe_map_align_stats), hipMemcpyDeviceToHost, c->stream));
-  if (size > 0) {
-    if (pairs_out) VO_HIP_CHECK(hipMemcpyAsync(pairs_out, c->out[0].p, sizeof(int32_t) * 2 * (size_t)size, hipMemcpyDeviceToHost, c->stream));
-    if (mask_out) VO_HIP_CHECK(hipMemcpyAsync(mask_out, d_mask, (size_t)size, hipMemcpyDeviceToHost, c->stream));
-  }
-  if (counts_out) VO_HIP_CHECK(hipMemcpyAsync(counts_out, d_counts, sizeof(int32_t) * H, hipMemcpyDeviceToHost, c->stream));
-  VO_HIP_CHECK(hipStreamSynchronize(c->stream));
-  if (n_matches_out) *n_matches_out = stats_out->n_matches;
-  return VO_OK;
-}
-
-int voe_map_merge_dev(vo_map* dst, vo_map* src, const float* d_S16, int policy, int32_t* d_remap_out, voe_map_merge_stats* d_stats) {
-  const char* fn = "voe_map_merge_dev";
-  if (int r = two_maps_check(fn, dst, src)) return r;
-  if (policy != VOE_MAP_MERGE_TAKE_SRC && policy != VOE_MAP_MERGE_KEEP_DST) return fail(VO_ERR_INVALID_ARG, "%s: unknown policy %d", fn, policy);
-  if (!d_stats) return fail(VO_ERR_INVALID_ARG, "%s: null argument", fn);
-  vo_ctx* c = dst->ctx;
-  const int n_max = map_bound(src);
-  const MapMergeWs lay = map_merge_layout(nullptr, n_max);
-  const size_t look = sizeof(int) * map_lookup_scratch_ints(n_max, 1, false), upd = sizeof(int) * map_scratch_ints(n_max);
-  if (c->capturing && (dst->merge_ws.cap < lay.bytes || dst->look_ws.cap < look || dst->scratch.cap < upd))      // (before anything is enqueued)
-    return fail(VO_ERR_NOT_READY, "%s: the workspace would have to grow inside a graph capture (make one call with these maps before "
-                                  "capturing)", fn);
-  if (int r = set_device(c)) return r;
-  if (int r = map_reserve(dst, n_max)) return r;              // dst grows here, on the host, or the capture is refused
-  VO_HIP_CHECK(dst->merge_ws.ensure(lay.bytes, c->stream));
-  const MapMergeWs w = map_merge_layout(dst->merge_ws.p, n_max);
-  VO_HIP_CHECK(launch_map_merge_begin(c->stream, w, dst->d.hdr));
-  // the lookup before the merge: which src entries dst holds already
-  if (int r = vo_map_lookup_dev(dst, src->d.app, n_max, src->d.hdr, w.pairs, w.ctl + 1, nullptr, nullptr, w.ent)) return r;
-  if (policy == VOE_MAP_MERGE_TAKE_SRC) {
-    if (int r = vo_map_update_dev(dst, src->d.pts, src->d.app, n_max, src->d.hdr, d_S16)) return r;
-  } else {
-    VO_HIP_CHECK(launch_map_merge_misses(c->stream, w, src->d.pts, src->d.app, src->d.hdr, n_max));
-    if (int r = vo_map_update_dev(dst, w.stage_pts, w.stage_app, n_max, w.ctl + 2, d_S16)) return r;
-  }
-  if (d_remap_out)
-    if (int r = vo_map_lookup_dev(dst, src->d.app, n_max, src->d.hdr, w.pairs, w.ctl + 3, nullptr, nullptr, d_remap_out)) return r;
-  VO_HIP_CHECK(launch_map_merge_stats(c->stream, w, src->d.hdr, dst->d.hdr, n_max, d_stats));
-  return VO_OK;
-}
-
-int voe_map_merge(vo_map* dst, vo_map* src, const float S16[16], int policy, int32_t* remap_out, voe_map_merge_stats* stats_out) {
-  const char* fn = "voe_map_merge";
-  if (int r = two_maps_check(fn, dst, src)) return r;
-  vo_ctx* c = dst->ctx;
-  VO_NOT_CAPTURING(c);
-  VO_REQUIRE(stats_out, "null argument");
-  if (int r = set_device(c)) return r;
-  int size = 0;
-  if (int r = vo_map_size(src, &size)) return r;
-  const size_t n = (size_t)(map_bound(src) > 0 ? map_bound(src) : 1);
-  VO_HIP_CHECK(c->out[0].ensure(sizeof(int32_t) * n, c->stream));
-  VO_HIP_CHECK(c->out[2].ensure(256, c->stream));
-  float* d_S = c->out[2].as<float>();
-  voe_map_merge_stats* d_st = reinterpret_cast<voe_map_merge_stats*>(d_S + 16);
-  if (S16) {
-    VO_HIP_CHECK(hipMemcpyAsync(d_S, S16, sizeof(float) * 16, hipMemcpyHostToDevice, c->stream));
-    VO_HIP_CHECK(hipStreamSynchronize(c->stream));            // the host array may go away after the call
-  }
-  if (int r = voe_map_merge_dev(dst, src, S16 ? d_S : nullptr, policy, remap_out ? c->out[0].as<int32_t>() : nullptr, d_st)) return r;
-  VO_HIP_CHECK(hipMemcpyAsync(stats_out, d_st, sizeof(voe_map_merge_stats), hipMemcpyDeviceToHost, c->stream));
-  if (remap_out && size > 0) VO_HIP_CHECK(hipMemcpyAsync(remap_out, c->out[0].p, sizeof(int32_t) * (size_t)size, hipMemcpyDeviceToHost, c->stream));
-  VO_HIP_CHECK(hipStreamSynchronize(c->stream));
-  if (!dst->replayable) dst->size_ub = stats_out->n_dst_after;
-  return VO_OK;
-}
-
-// ---- covisibility of frames and the window chosen from it (map_covis.hip; include/vo_map_covis.h) --------------------------
-static_assert(sizeof(voe_map_covis_stats) == 32 && sizeof(voe_map_window_params) == 16 && sizeof(voe_map_window_stats) == 32,
-              "the records of include/vo_map_covis.h as the kernels write them");
-
-// the refusals that need no map come first: they are the same on a machine without a device
-// (dev: d_stats is a device pointer, written as 8-byte pieces)
-static int covis_check(const char* fn, int n_frames, int n_words, const void* d_bits, const void* d_stats, bool dev) {
-  if (n_frames < 1 || n_frames > VOE_MAP_COVIS_MAX_FRAMES)
-    return fail(VO_ERR_INVALID_ARG, "%s: n_frames %d outside 1 .. %d", fn, n_frames, VOE_MAP_COVIS_MAX_FRAMES);
-  if (n_words < 1) return fail(VO_ERR_INVALID_ARG, "%s: n_words must be at least 1", fn);
-  if (!d_bits || !d_stats) return fail(VO_ERR_INVALID_ARG, "%s: null argument", fn);
-  if (dev && !aligned8(d_stats)) return fail(VO_ERR_INVALID_ARG, "%s: d_stats must be 8-byte aligned", fn);
-  return VO_OK;
-}
-
-int voe_map_covis_batch_dev(vo_map* m, int n_frames, const float* d_app, size_t app_stride, int n_max, const int* d_n, int n_words,
-                            uint32_t* d_bits_out, int32_t* d_counts_out, voe_map_covis_stats* d_stats) {
-  const char* fn = "voe_map_covis_batch_dev";
-  if (int r = covis_check(fn, n_frames, n_words, d_bits_out, d_stats, true)) return r;
-  VO_MAP_LIVE(m);
-  vo_ctx* c = m->ctx;
-  // the lookup's own refusals, before anything is sized (its pair and count arrays are the workspace's: d_app and d_stats stand
-  // in for them here, null and aligned exactly when those are)
-  if (int r = map_lookup_check(m, n_frames, d_app, app_stride, n_max, reinterpret_cast<const int32_t*>(d_app), reinterpret_cast<const int*>(d_stats), nullptr))
-    return r;
-  if ((long long)32 * n_words < (long long)map_bound(m))
-    return fail(VO_ERR_INVALID_ARG, "%s: %d words hold fewer bits than the map's size bound %d", fn, n_words, map_bound(m));
-  MapCovisWs w = map_covis_layout(nullptr, n_frames, n_max, n_words);
-  const size_t look_need = sizeof(int) * map_lookup_scratch_ints(n_max, n_frames, false);
-  if (c->capturing && (m->covis_ws.cap < w.bytes || (n_max > 0 && m->look_ws.cap < look_need)))      // (before the lookup is enqueued)
-    return fail(VO_ERR_NOT_READY, "%s: the workspace would have to grow inside a graph capture (make one call with %d frames of n_max %d "
-                                  "and %d words on this map before capturing)", fn, n_frames, n_max, n_words);
-  if (int r = set_device(c)) return r;
-  VO_HIP_CHECK(m->covis_ws.ensure(w.bytes, c->stream));
-  w = map_covis_layout(m->covis_ws.p, n_frames, n_max, n_words);
-  if (n_max > 0)                                              // the one lookup of the call, through the public entry point
-    if (int r = vo_map_lookup_batch_dev(m, n_frames, d_app, app_stride, n_max, d_n, w.pairs, w.n_hits, nullptr, nullptr, w.ent)) return r;
-  MapCovisArgs a{};
-  a.w = w; a.hdr = m->d.hdr; a.cap = m->d.cap;
-  a.n_frames = n_frames; a.n_max = n_max; a.n_words = n_words; a.d_n = d_n;
-  a.bits = d_bits_out; a.counts = d_counts_out; a.stats = d_stats;
-  VO_HIP_CHECK(launch_map_covis(c->stream, a));
-  return VO_OK;
-}
-
-int voe_map_covis(vo_map* m, int n_frames, const float* app, const int* n_rows, int n_max, int n_words, uint32_t* bits_out,
-                  int32_t* counts_out, voe_map_covis_stats* stats_out) {
-  const char* fn = "voe_map_covis";
-  if (int r = covis_check(fn, n_frames, n_words, bits_out, stats_out, false)) return r;
-  VO_MAP_LIVE(m);
-  vo_ctx* c = m->ctx;
-  VO_NOT_CAPTURING(c);
-  VO_REQUIRE(n_max >= 0 && (n_max == 0 || app), "bad frames");
-  VO_REQUIRE((long long)n_max * n_frames <= (1ll << 30), "more than 2^30 rows in one call");
-  if (int r = set_device(c)) return r;
-  const size_t F = (size_t)n_frames, W = (size_t)n_words;
-  if (int r = upload(c, c->in[1], app, sizeof(float) * 10 * F * (size_t)n_max)) return r;
-  if (n_rows)
-    if (int r = upload(c, c->in[3], n_rows, sizeof(int) * F)) return r;
-  int size = 0;
-  if (int r = vo_map_size(m, &size)) return r;                // (waits: the host arrays may go away after the call)
-  VO_HIP_CHECK(c->out[0].ensure(sizeof(uint32_t) * F * W, c->stream));
-  if (counts_out) VO_HIP_CHECK(c->out[1].ensure(sizeof(int32_t) * F * F, c->stream));
-  VO_HIP_CHECK(c->out[2].ensure(sizeof(voe_map_covis_stats) + 16, c->stream));
-  if (int r = voe_map_covis_batch_dev(m, n_frames, c->in[1].as<float>(), (size_t)n_max, n_max, n_rows ? c->in[3].as<int>() : nullptr, n_words,
-                                      c->out[0].as<uint32_t>(), counts_out ? c->out[1].as<int32_t>() : nullptr,
-                                      c->out[2].as<voe_map_covis_stats>()))
-    return r;
-  VO_HIP_CHECK(hipMemcpyAsync(bits_out, c->out[0].p, sizeof(uint32_t) * F * W, hipMemcpyDeviceToHost, c->stream));
-  if (counts_out) VO_HIP_CHECK(hipMemcpyAsync(counts_out, c->out[1].p, sizeof(int32_t) * F * F, hipMemcpyDeviceToHost, c->stream));
-  VO_HIP_CHECK(hipMemcpyAsync(stats_out, c->out[2].p, sizeof(voe_map_covis_stats), hipMemcpyDeviceToHost, c->stream));
-  VO_HIP_CHECK(hipStreamSynchronize(c->stream));
-  return VO_OK;
-}
-
-static int window_check(const char* fn, int n_frames, int n_words, const void* d_bits, int n_max, const voe_map_window_params* p,
-                        const void* d_role, const void* d_n_rows_out, const void* d_fixed, const void* d_stats, bool dev) {
-  if (int r = covis_check(fn, n_frames, n_words, d_bits, d_stats, dev)) return r;
-  if (!(p && d_role && d_n_rows_out && d_fixed)) return fail(VO_ERR_INVALID_ARG, "%s: null argument", fn);
-  if (n_max < 0) return fail(VO_ERR_INVALID_ARG, "%s: negative row count", fn);
-  if (p->query < 0 || p->query >= n_frames) return fail(VO_ERR_INVALID_ARG, "%s: query %d outside the %d frames", fn, p->query, n_frames);
-  if (p->k_free < 1 || p->k_free > n_frames) return fail(VO_ERR_INVALID_ARG, "%s: k_free outside 1 .. n_frames", fn);
-  if (p->k_fixed < 0 || p->k_fixed > n_frames) return fail(VO_ERR_INVALID_ARG, "%s: k_fixed outside 0 .. n_frames", fn);
-  if (p->min_shared < 1) return fail(VO_ERR_INVALID_ARG, "%s: min_shared must be at least 1", fn);
-  return VO_OK;
-}
-
-int voe_map_window_dev(vo_map* m, int n_frames, int n_words, const uint32_t* d_bits, const int* d_n, int n_max,
-                       const voe_map_window_params* p, int32_t* d_role_out, int* d_n_rows_out, uint8_t* d_fixed_out, int32_t* d_order_out,
-                       uint32_t* d_union_out, voe_map_window_stats* d_stats) {
-  const char* fn = "voe_map_window_dev";
-  if (int r = window_check(fn, n_frames, n_words, d_bits, n_max, p, d_role_out, d_n_rows_out, d_fixed_out, d_stats, true)) return r;
-  VO_MAP_LIVE(m);
-  vo_ctx* c = m->ctx;
-  MapWindowWs w = map_window_layout(nullptr, n_frames, n_words);
-  if (c->capturing && m->window_ws.cap < w.bytes)
-    return fail(VO_ERR_NOT_READY, "%s: the workspace would have to grow inside a graph capture (make one call with %d frames and %d words "
-                                  "on this map before capturing)", fn, n_frames, n_words);
-  if (int r = set_device(c)) return r;
-  VO_HIP_CHECK(m->window_ws.ensure(w.bytes, c->stream));
-  MapWindowArgs a{};
-  a.w = map_window_layout(m->window_ws.p, n_frames, n_words);
-  a.n_frames = n_frames; a.n_words = n_words; a.n_max = n_max; a.bits = d_bits; a.d_n = d_n;
-  a.query = p->query; a.k_free = p->k_free; a.k_fixed = p->k_fixed; a.min_shared = p->min_shared;
-  a.role = d_role_out; a.n_rows_out = d_n_rows_out; a.fixed_out = d_fixed_out;
-  a.order = d_order_out ? d_order_out : a.w.order;
-  a.uni = d_union_out ? d_union_out : a.w.uni;
-  a.stats = d_stats;
-  VO_HIP_CHECK(launch_map_window(c->stream, a));
-  return VO_OK;
-}
-
-int voe_map_window(vo_map* m, int n_frames, int n_words, const uint32_t* bits, const int* n_rows, int n_max,
-                   const voe_map_window_params* p, int32_t* role_out, int* n_rows_out, uint8_t* fixed_out, int32_t* order_out,
-                   uint32_t* union_out, voe_map_window_stats* stats_out) {
-  const char* fn = "voe_map_window";
-  if (int r = window_check(fn, n_frames, n_words, bits, n_max, p, role_out, n_rows_out, fixed_out, stats_out, false)) return r;
-  VO_MAP_LIVE(m);
-  vo_ctx* c = m->ctx;
-  VO_NOT_CAPTURING(c);
-  if (int r = set_device(c)) return r;
-  const size_t F = (size_t)n_frames, W = (size_t)n_words;
-  if (int r = upload(c, c->in[0], bits, sizeof(uint32_t) * F * W)) return r;
-  if (n_rows)
-    if (int r = upload(c, c->in[3], n_rows, sizeof(int) * F)) return r;
-  // one block of outputs: role, n_rows, order [F] ints each, the union [W], the statistics, the mask [F] bytes
-  const size_t o_role = 0, o_rows = up256(4 * F), o_order = o_rows + up256(4 * F), o_union = o_order + up256(4 * F), o_stats = o_union + up256(4 * W),
-               o_fixed = o_stats + 256, total = o_fixed + up256(F);
-  VO_HIP_CHECK(c->out[0].ensure(total, c->stream));
-  char* d = c->out[0].as<char>();
-  if (int r = voe_map_window_dev(m, n_frames, n_words, c->in[0].as<uint32_t>(), n_rows ? c->in[3].as<int>() : nullptr, n_max, p,
-                                 reinterpret_cast<int32_t*>(d + o_role), reinterpret_cast<int*>(d + o_rows), reinterpret_cast<uint8_t*>(d + o_fixed),
-                                 order_out ? reinterpret_cast<int32_t*>(d + o_order) : nullptr,
-                                 union_out ? reinterpret_cast<uint32_t*>(d + o_union) : nullptr, reinterpret_cast<voe_map_window_stats*>(d + o_stats)))
-    return r;
-  VO_HIP_CHECK(hipMemcpyAsync(role_out, d + o_role, 4 * F, hipMemcpyDeviceToHost, c->stream));
-  VO_HIP_CHECK(hipMemcpyAsync(n_rows_out, d + o_rows, 4 * F, hipMemcpyDeviceToHost, c->stream));
-  VO_HIP_CHECK(hipMemcpyAsync(fixed_out, d + o_fixed, F, hipMemcpyDeviceToHost, c->stream));
-  if (order_out) VO_HIP_CHECK(hipMemcpyAsync(order_out, d + o_order, 4 * F, hipMemcpyDeviceToHost, c->stream));
-  if (union_out) VO_HIP_CHECK(hipMemcpyAsync(union_out, d + o_union, 4 * W, hipMemcpyDeviceToHost, c->stream));
-  VO_HIP_CHECK(hipMemcpyAsync(stats_out, d + o_stats, sizeof(voe_map_window_stats), hipMemcpyDeviceToHost, c->stream));
-  VO_HIP_CHECK(hipStreamSynchronize(c->stream));
   return VO_OK;
 }
 

@@ -1,0 +1,1138 @@
+// capi_map.hip -- the map's half of the extern "C" boundary (vo_hip.h: vo_map_*; vo_map_adjust.h, vo_map_bundle.h, vo_map_cull.h,
+// vo_map_align.h, vo_map_covis.h).  Host-side plumbing only, like capi.hip: no kernel lives here.
+#include <limits.h>
+#include <string.h>
+
+#include "capi_internal.h"
+
+using namespace vo;
+
+// ---- the map (PointCloudVector<3>::update + the history chain of vo_complete.cpp:145-147,175-176,183) ---------------------------
+struct vo_map {
+  vo_ctx* ctx = nullptr;
+  unsigned long long ctx_id = 0;
+  MapDev d;
+  DevBuf scratch;
+  float* hist = nullptr;        // [0,16) the history isometry, [16,32) staging of a host isometry (vo_map_update)
+  long long size_ub = 0;        // upper bound of the size known without asking the device, as long as !replayable
+  bool replayable = false;      // an update of this map has been captured: the graph's replays add entries the host never counts
+  DevBuf up_xyz, up_app;        // staging of vo_map_update
+  DevBuf look_ws;               // vo_map_lookup*: per-workgroup counts, entries per query position
+  DevBuf loc_ws;                // vo_map_localise*: what passes from stage to stage (hits, gathered points, winner, pairs handed on)
+  vo_picp* solver = nullptr;    // vo_map_localise[_dev]: made by the first call
+  DevBuf ref_ws;                // vo_map_refine*: the entries seen, the observation lists, status and cost per entry
+  DevBuf pose_ws;               // vo_map_refine_poses*: the entries seen, status, observation count and cost per frame
+  DevBuf bundle_ws;             // vox_map_bundle*: the state in double, the blocks and the PCG vectors (the lists live in ref_ws)
+  DevBuf cull_ws;               // voe_map_cull*: verdict, remap, ranks, the staging area of the survivors (the lists live in ref_ws)
+  DevBuf align_ws;              // voe_map_align* (on dst): gathered pairs, hypotheses, counts, the blocks' sums
+  DevBuf merge_ws;              // voe_map_merge* (on dst): the lookup's entries, the staging area of the misses
+  DevBuf covis_ws;              // voe_map_covis*: the lookup's pairs, counts and entries, the population counts per frame and per block of words
+  DevBuf window_ws;             // voe_map_window*: the counts against the query row and against the union, the order, the union
+};
+
+constexpr int MAP_MAX_ENTRIES = 1 << 29;      // 2.5 x that many table slots still fit 32 bits
+static unsigned map_tcap_for(int cap) {
+  unsigned t = 1024;
+  while (t < 2u * (unsigned)cap + 2u * ((unsigned)cap >> 2)) t <<= 1;      // at most 40 % full (cap <= MAP_MAX_ENTRIES: t <= 2^31)
+  return t;
+}
+
+static void map_free_arrays(MapDev& d) {
+  if (d.pts) (void)hipFree(d.pts);
+  if (d.app) (void)hipFree(d.app);
+  if (d.table) (void)hipFree(d.table);
+  if (d.last) (void)hipFree(d.last);
+  d.pts = d.app = nullptr; d.table = nullptr; d.last = nullptr;
+}
+
+static int map_alloc_arrays(MapDev& d, int cap) {
+  d.cap = cap; d.tcap = map_tcap_for(cap);
+  VO_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&d.pts), sizeof(float) * 3 * (size_t)cap));
+  VO_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&d.app), sizeof(float) * 10 * (size_t)cap));
+  VO_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&d.table), sizeof(unsigned long long) * (size_t)d.tcap));
+  VO_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&d.last), sizeof(int) * (size_t)d.tcap));
+  return VO_OK;
+}
+
+// what bounds the size where the host must not wait: size_ub, or the capacity once replays may have outrun it
+static int map_bound(const vo_map* m) { return (int)(m->replayable || m->size_ub > m->d.cap ? m->d.cap : m->size_ub); }
+
+// room for n more entries: the bound the host keeps (size_ub grows by a cloud's row count per update) is refreshed from
+// the device only when it would pass the capacity, and the arrays grow only when the true size would.  A map whose update
+// has been captured asks the device every time outside a capture; inside one nobody can ask, and the bound decides as before.
+static int map_reserve(vo_map* m, int n) {
+  vo_ctx* c = m->ctx;
+  if ((c->capturing || !m->replayable) && m->size_ub + n <= m->d.cap) return VO_OK;
+  if (c->capturing) return vo_fail(VO_ERR_NOT_READY, "vo_map: the map would have to grow inside a graph capture (create it with the capacity it will need)");
+  int size = 0;
+  VO_HIP_CHECK(hipMemcpyAsync(&size, m->d.hdr, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+  VO_HIP_CHECK(hipStreamSynchronize(c->stream));
+  m->size_ub = size;
+  if ((long long)size + n <= m->d.cap) return VO_OK;
+  long long want = 2ll * m->d.cap;
+  if (want < (long long)size + n) want = (long long)size + n + ((long long)size + n) / 2;
+  if ((long long)size + n > MAP_MAX_ENTRIES) return vo_fail(VO_ERR_INVALID_ARG, "vo_map: more than 2^29 entries");
+  if (want > MAP_MAX_ENTRIES) want = MAP_MAX_ENTRIES;
+  MapDev old = m->d;
+  MapDev nd = old;
+  nd.pts = nd.app = nullptr; nd.table = nullptr; nd.last = nullptr;
+  if (int r = map_alloc_arrays(nd, (int)want)) { map_free_arrays(nd); return r; }
+  if (size > 0) {
+    VO_HIP_CHECK(hipMemcpyAsync(nd.pts, old.pts, sizeof(float) * 3 * (size_t)size, hipMemcpyDeviceToDevice, c->stream));
+    VO_HIP_CHECK(hipMemcpyAsync(nd.app, old.app, sizeof(float) * 10 * (size_t)size, hipMemcpyDeviceToDevice, c->stream));
+  }
+  VO_HIP_CHECK(launch_map_rehash(c->stream, nd, size));
+  VO_HIP_CHECK(hipStreamSynchronize(c->stream));
+  map_free_arrays(old);
+  m->d = nd;
+  return VO_OK;
+}
+
+#define VO_MAP_LIVE(m) \
+  do { VO_REQUIRE(m, "null map"); VO_REQUIRE(ctx_alive((m)->ctx, (m)->ctx_id), "the context this map was made on has been destroyed"); } while (0)
+
+int vo_map_create(vo_ctx* c, int capacity, vo_map** out) {
+  VO_REQUIRE(c && out, "null argument");
+  VO_NOT_CAPTURING(c);
+  VO_REQUIRE(capacity >= 0 && capacity <= MAP_MAX_ENTRIES, "bad capacity (at most 2^29 entries)");
+  *out = nullptr;
+  if (int r = set_device(c)) return r;
+  vo_map* m = new vo_map();
+  m->ctx = c; m->ctx_id = c->id;
+  const int cap = capacity < 1024 ? 1024 : capacity;
+  int rc = map_alloc_arrays(m->d, cap);
+  if (rc == VO_OK && hipMalloc(reinterpret_cast<void**>(&m->d.hdr), 64) != hipSuccess) rc = vo_fail(VO_ERR_OUT_OF_MEMORY, "vo_map_create: out of device memory");
+  if (rc == VO_OK && hipMalloc(reinterpret_cast<void**>(&m->hist), sizeof(float) * 32) != hipSuccess) rc = vo_fail(VO_ERR_OUT_OF_MEMORY, "vo_map_create: out of device memory");
+  if (rc != VO_OK) { (void)hipGetLastError(); map_free_arrays(m->d); if (m->d.hdr) (void)hipFree(m->d.hdr); if (m->hist) (void)hipFree(m->hist); delete m; return rc; }
+  *out = m;
+  return vo_map_clear(m);
+}
+
+int vo_map_destroy(vo_map* m) {
+  if (!m) return VO_OK;
+  if (ctx_alive(m->ctx, m->ctx_id)) {
+    VO_NOT_CAPTURING(m->ctx);
+    (void)hipSetDevice(m->ctx->device);
+    (void)hipStreamSynchronize(m->ctx->stream);
+  } else {
+    (void)hipDeviceSynchronize();
+  }
+  map_free_arrays(m->d);
+  if (m->d.hdr) (void)hipFree(m->d.hdr);
+  if (m->hist) (void)hipFree(m->hist);
+  m->scratch.release(); m->up_xyz.release(); m->up_app.release(); m->look_ws.release(); m->loc_ws.release(); m->ref_ws.release(); m->pose_ws.release(); m->bundle_ws.release(); m->cull_ws.release(); m->align_ws.release(); m->merge_ws.release(); m->covis_ws.release(); m->window_ws.release();
+  if (m->solver) (void)vo_picp_destroy(m->solver);
+  delete m;
+  return VO_OK;
+}
+
+int vo_map_clear(vo_map* m) {
+  VO_MAP_LIVE(m);
+  vo_ctx* c = m->ctx;
+  VO_NOT_CAPTURING(c);
+  if (int r = set_device(c)) return r;
+  VO_HIP_CHECK(hipMemsetAsync(m->d.hdr, 0, 64, c->stream));
+  VO_HIP_CHECK(launch_map_rehash(c->stream, m->d, 0));
+  const float I[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
+  VO_HIP_CHECK(hipMemcpyAsync(m->hist, I, sizeof(I), hipMemcpyHostToDevice, c->stream));
+  VO_HIP_CHECK(hipStreamSynchronize(c->stream));
+  m->size_ub = 0;
+  return VO_OK;
+}
+
+int vo_map_update_dev(vo_map* m, const float* d_xyz, const float* d_app, int n_max, const int* d_n, const float* d_T16) {
+  VO_MAP_LIVE(m);
+  VO_REQUIRE(n_max >= 0 && n_max <= MAP_MAX_ENTRIES && (n_max == 0 || (d_xyz && d_app)), "bad cloud");
+  VO_REQUIRE(aligned8(d_app), "device appearance rows must be 8-byte aligned");
+  if (n_max == 0) return VO_OK;
+  vo_ctx* c = m->ctx;
+  if (int r = set_device(c)) return r;
+  if (int r = map_reserve(m, n_max)) return r;
+  VO_HIP_CHECK(m->scratch.ensure(sizeof(int) * map_scratch_ints(n_max), c->stream));
+  VO_HIP_CHECK(launch_map_update(c->stream, m->d, d_xyz, d_app, n_max, d_n, d_T16, m->scratch.as<int>()));
+  m->size_ub += n_max;
+  if (c->capturing) m->replayable = true;
+  return VO_OK;
+}
+
+int vo_map_update(vo_map* m, const float* xyz, const float* app, int n, const float T16[16]) {
+  VO_MAP_LIVE(m);
+  VO_NOT_CAPTURING(m->ctx);
+  VO_REQUIRE(n >= 0 && (n == 0 || (xyz && app)), "bad cloud");
+  if (n == 0) return VO_OK;
+  vo_ctx* c = m->ctx;
+  if (int r = set_device(c)) return r;
+  if (int r = upload(c, m->up_xyz, xyz, sizeof(float) * 3 * (size_t)n)) return r;
+  if (int r = upload(c, m->up_app, app, sizeof(float) * 10 * (size_t)n)) return r;
+  if (T16) VO_HIP_CHECK(hipMemcpyAsync(m->hist + 16, T16, sizeof(float) * 16, hipMemcpyHostToDevice, c->stream));
+  VO_HIP_CHECK(hipStreamSynchronize(c->stream));          // the host arrays may go away after the call
+  return vo_map_update_dev(m, m->up_xyz.as<float>(), m->up_app.as<float>(), n, nullptr, T16 ? m->hist + 16 : nullptr);
+}
+
+int vo_map_history_reset_dev(vo_map* m, const float* d_X16) {
+  VO_MAP_LIVE(m);
+  VO_REQUIRE(d_X16, "null pose");
+  if (int r = set_device(m->ctx)) return r;
+  VO_HIP_CHECK(launch_map_history(m->ctx->stream, m->hist, d_X16, 1));
+  return VO_OK;
+}
+
+int vo_map_history_step_dev(vo_map* m, const float* d_X16) {
+  VO_MAP_LIVE(m);
+  VO_REQUIRE(d_X16, "null pose");
+  if (int r = set_device(m->ctx)) return r;
+  VO_HIP_CHECK(launch_map_history(m->ctx->stream, m->hist, d_X16, 0));
+  return VO_OK;
+}
+
+int vo_map_history_dev_ptr(vo_map* m, const float** d_T16) {
+  VO_MAP_LIVE(m);
+  VO_REQUIRE(d_T16, "null argument");
+  *d_T16 = m->hist;
+  return VO_OK;
+}
+
+int vo_map_get_history(vo_map* m, float T16[16]) {
+  VO_MAP_LIVE(m);
+  VO_REQUIRE(T16, "null argument");
+  VO_NOT_CAPTURING(m->ctx);
+  if (int r = set_device(m->ctx)) return r;
+  VO_HIP_CHECK(hipMemcpyAsync(T16, m->hist, sizeof(float) * 16, hipMemcpyDeviceToHost, m->ctx->stream));
+  VO_HIP_CHECK(hipStreamSynchronize(m->ctx->stream));
+  return VO_OK;
+}
+
+int vo_map_size(vo_map* m, int* n) {
+  VO_MAP_LIVE(m);
+  VO_REQUIRE(n, "null argument");
+  VO_NOT_CAPTURING(m->ctx);
+  if (int r = set_device(m->ctx)) return r;
+  int h[4] = {0, 0, 0, 0};
+  VO_HIP_CHECK(hipMemcpyAsync(h, m->d.hdr, sizeof(h), hipMemcpyDeviceToHost, m->ctx->stream));
+  VO_HIP_CHECK(hipStreamSynchronize(m->ctx->stream));
+  m->size_ub = h[0];
+  *n = h[0];
+  if (h[3] > 0) return vo_fail(VO_ERR_BAD_INDEX, "vo_map: %d entries were dropped for lack of room", h[3]);
+  return VO_OK;
+}
+
+int vo_map_read(vo_map* m, float* xyz, float* app, int capacity, int* n_out) {
+  VO_MAP_LIVE(m);
+  VO_REQUIRE(capacity >= 0 && n_out, "bad arguments");
+  int n = 0;
+  if (int r = vo_map_size(m, &n)) return r;
+  *n_out = n;
+  const int k = n < capacity ? n : capacity;
+  if (k > 0 && xyz) VO_HIP_CHECK(hipMemcpyAsync(xyz, m->d.pts, sizeof(float) * 3 * (size_t)k, hipMemcpyDeviceToHost, m->ctx->stream));
+  if (k > 0 && app) VO_HIP_CHECK(hipMemcpyAsync(app, m->d.app, sizeof(float) * 10 * (size_t)k, hipMemcpyDeviceToHost, m->ctx->stream));
+  VO_HIP_CHECK(hipStreamSynchronize(m->ctx->stream));
+  return VO_OK;
+}
+
+int vo_map_transform(vo_map* m, const float T16[16]) {
+  VO_MAP_LIVE(m);
+  VO_REQUIRE(T16, "null argument");
+  if (int r = set_device(m->ctx)) return r;
+  VO_HIP_CHECK(launch_map_transform(m->ctx->stream, m->d, pose_from_T16(T16), map_bound(m)));
+  return VO_OK;
+}
+
+int vo_map_dev_ptrs(vo_map* m, const float** d_xyz, const float** d_app, const int** d_size) {
+  VO_MAP_LIVE(m);
+  if (d_xyz) *d_xyz = m->d.pts;
+  if (d_app) *d_app = m->d.app;
+  if (d_size) *d_size = m->d.hdr;
+  return VO_OK;
+}
+
+// ---- reading the map by appearance: the lookup (map.hip) and the localisation composed of it, the P3P RANSAC and the PICP
+// solvers.  The localisation calls go through the PUBLIC entry points of the stages, in the order the header's contract names.
+// the lookup's refusals, of the frames' appearances (no pixels, no camera) and of its pair and count arrays; `own_out`: those
+// arrays are the caller's own workspace's (the covisibility), there and aligned by construction
+static int map_lookup_check(const MapFrames& f, bool own_out, const int32_t* d_pairs = nullptr, const int* d_n_out = nullptr,
+                            const int32_t* d_local = nullptr) {
+  const char* fn = "vo_map_lookup";
+  if (f.n_frames < 1 || f.n_frames > 65535) return vo_fail(VO_ERR_INVALID_ARG, "%s: n_frames %d outside 1 .. 65535 (the frame is a grid dimension)", fn, f.n_frames);
+  if (f.n_max < 0) return vo_fail(VO_ERR_INVALID_ARG, "%s: negative row count", fn);
+  if ((!own_out && (!d_n_out || (f.n_max > 0 && !d_pairs))) || (f.n_max > 0 && !f.d_app)) return vo_fail(VO_ERR_INVALID_ARG, "%s: null argument", fn);
+  if (!aligned8(f.d_app, d_pairs, d_local)) return vo_fail(VO_ERR_INVALID_ARG, "%s: device appearance rows and pair arrays must be 8-byte aligned", fn);
+  if (f.n_frames > 1 && f.app_stride < (size_t)f.n_max) return vo_fail(VO_ERR_INVALID_ARG, "%s: app_stride %zu is smaller than n_max %d", fn, f.app_stride, f.n_max);
+  if (f.app_stride >= 0x7fffffff / 10 || (long long)f.n_max * f.n_frames > (1ll << 30))
+    return vo_fail(VO_ERR_INVALID_ARG, "%s: more than 2^30 rows in one call", fn);
+  return VO_OK;
+}
+
+static size_t lookup_scratch_bytes(const MapFrames& f, bool gather) { return sizeof(int) * map_lookup_scratch_ints(f.n_max, f.n_frames, gather); }
+
+static int map_lookup(vo_map* m, const MapFrames& f, int32_t* d_pairs, int* d_n_out, float* d_xyz, int32_t* d_local, int32_t* d_entries) {
+  VO_MAP_LIVE(m);
+  if (int r = map_lookup_check(f, false, d_pairs, d_n_out, d_local)) return r;
+  vo_ctx* c = m->ctx;
+  const size_t need = lookup_scratch_bytes(f, d_entries == nullptr);
+  if (c->capturing && m->look_ws.cap < need)
+    return vo_fail(VO_ERR_NOT_READY, "vo_map_lookup: the scratch would have to grow inside a graph capture (make one call with %d frame(s) "
+                                  "of n_max %d before capturing)", f.n_frames, f.n_max);
+  if (int r = set_device(c)) return r;
+  VO_HIP_CHECK(m->look_ws.ensure(need, c->stream));
+  VO_HIP_CHECK(launch_map_lookup(c->stream, m->d, f.d_app, f.app_stride, f.n_max, f.d_n, f.n_frames, d_pairs, d_n_out, d_xyz, d_local, d_entries,
+                                 m->look_ws.as<int>()));
+  return VO_OK;
+}
+
+int vo_map_lookup_dev(vo_map* m, const float* d_app, int n_max, const int* d_n, int32_t* d_pairs, int* d_n_out, float* d_xyz,
+                      int32_t* d_local, int32_t* d_entries) {
+  return map_lookup(m, MapFrames{1, nullptr, nullptr, 0, d_app, (size_t)(n_max > 0 ? n_max : 0), n_max, d_n}, d_pairs, d_n_out, d_xyz, d_local, d_entries);
+}
+
+int vo_map_lookup_batch_dev(vo_map* m, int n_frames, const float* d_app, size_t app_stride, int n_max, const int* d_n, int32_t* d_pairs,
+                            int* d_n_out, float* d_xyz, int32_t* d_local, int32_t* d_entries) {
+  return map_lookup(m, MapFrames{n_frames, nullptr, nullptr, 0, d_app, app_stride, n_max, d_n}, d_pairs, d_n_out, d_xyz, d_local, d_entries);
+}
+
+// the lookup of every frame of a window into arrays of the caller's workspace (no points gathered, the entry per row kept)
+static int lookup_window(vo_map* m, const MapFrames& f, int32_t* pairs, int* n_hits, int32_t* ent) {
+  return f.n_max > 0 ? vo_map_lookup_batch_dev(m, f.n_frames, f.d_app, f.app_stride, f.n_max, f.d_n, pairs, n_hits, nullptr, nullptr, ent) : VO_OK;
+}
+
+int vo_map_lookup(vo_map* m, const float* app, int n, int32_t* pairs_out, int* n_out, float* xyz_out, int32_t* entry_out) {
+  VO_MAP_LIVE(m);
+  vo_ctx* c = m->ctx;
+  VO_NOT_CAPTURING(c);
+  VO_REQUIRE(n >= 0 && n_out && (n == 0 || (app && pairs_out)), "bad arguments");
+  *n_out = 0;
+  if (n == 0) return VO_OK;
+  if (int r = set_device(c)) return r;
+  if (int r = upload(c, c->in[0], app, sizeof(float) * 10 * (size_t)n)) return r;
+  VO_HIP_CHECK(c->out[0].ensure(sizeof(int32_t) * 2 * (size_t)n, c->stream));
+  VO_HIP_CHECK(c->out[1].ensure(sizeof(float) * 3 * (size_t)n, c->stream));
+  VO_HIP_CHECK(c->out[2].ensure(sizeof(int32_t) * (size_t)n + 128, c->stream));
+  if (int r = ensure_counts(c)) return r;
+  if (int r = vo_map_lookup_dev(m, c->in[0].as<float>(), n, nullptr, c->out[0].as<int32_t>(), c->counts.as<int>(),
+                                xyz_out ? c->out[1].as<float>() : nullptr, nullptr, entry_out ? c->out[2].as<int32_t>() : nullptr))
+    return r;
+  int k = 0;
+  VO_HIP_CHECK(hipMemcpyAsync(&k, c->counts.p, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+  VO_HIP_CHECK(hipStreamSynchronize(c->stream));
+  if (k < 0 || k > n) return vo_fail(VO_ERR_HIP, "vo_map_lookup: unexpected count %d", k);
+  if (k > 0) VO_HIP_CHECK(hipMemcpyAsync(pairs_out, c->out[0].p, sizeof(int32_t) * 2 * (size_t)k, hipMemcpyDeviceToHost, c->stream));
+  if (k > 0 && xyz_out) VO_HIP_CHECK(hipMemcpyAsync(xyz_out, c->out[1].p, sizeof(float) * 3 * (size_t)k, hipMemcpyDeviceToHost, c->stream));
+  if (entry_out) VO_HIP_CHECK(hipMemcpyAsync(entry_out, c->out[2].p, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost, c->stream));
+  VO_HIP_CHECK(hipStreamSynchronize(c->stream));
+  *n_out = k;
+  return VO_OK;
+}
+
+static_assert(sizeof(vo_map_localise_stats) == 32, "the finishing kernel writes eight 4-byte words per frame");
+
+// what passes from stage to stage, per frame, in the map's workspace (256-byte aligned blocks)
+struct LocaliseWs {
+  int32_t *pairs, *local, *handed;   // [F][n_max][2]: (query, entry), (query, k), the pairs handed to the solver
+  float* xyz;                        // [F][n_max][3] gathered points
+  int *n_hits, *n_handed, *rstat;    // [F]
+  float *T_start, *T_solved, *stats4;   // [F][16], [F][16], [F][4]
+  size_t bytes;
+};
+static LocaliseWs localise_layout(void* base, int n_frames, int n_max) {
+  LocaliseWs w{};
+  WsCarver c(base);
+  const size_t F = (size_t)n_frames, N = (size_t)n_max;
+  w.pairs = c.take<int32_t>(8 * F * N);
+  w.local = c.take<int32_t>(8 * F * N);
+  w.handed = c.take<int32_t>(8 * F * N);
+  w.xyz = c.take<float>(12 * F * N);
+  w.n_hits = c.take<int>(4 * F);
+  w.n_handed = c.take<int>(4 * F);
+  w.rstat = c.take<int>(4 * F);
+  w.T_start = c.take<float>(64 * F);
+  w.T_solved = c.take<float>(64 * F);
+  w.stats4 = c.take<float>(16 * F);
+  w.bytes = c.bytes;
+  return w;
+}
+
+static int localise_check(const char* fn, const MapFrames& f, const vo_ransac_params* params, int n_iters, int min_inliers, const float* d_T0,
+                          const float* d_T16, const vo_map_localise_stats* d_stats) {
+  if (!(f.K && f.d_uv && f.d_app && params && d_T16 && d_stats)) return vo_fail(VO_ERR_INVALID_ARG, "%s: null argument", fn);
+  if (f.n_max < 1) return vo_fail(VO_ERR_INVALID_ARG, "%s: n_max must be positive", fn);
+  if (n_iters < 1) return vo_fail(VO_ERR_INVALID_ARG, "%s: n_iters must be positive", fn);
+  if (min_inliers < 0) return vo_fail(VO_ERR_INVALID_ARG, "%s: negative min_inliers", fn);
+  if (!aligned8(f.d_uv, f.d_app, d_stats)) return vo_fail(VO_ERR_INVALID_ARG, "%s: device arrays must be 8-byte aligned", fn);
+  if (params->n_hypotheses == 0) {
+    if (!d_T0) return vo_fail(VO_ERR_INVALID_ARG, "%s: n_hypotheses == 0 (no RANSAC) needs the prior d_T0", fn);
+  } else if (int r = ransac_check_params(params)) {
+    return r;
+  }
+  double Kinv[9];
+  if (!invert_k(f.K, Kinv)) return vo_fail(VO_ERR_INVALID_ARG, "%s: K is singular", fn);
+  return VO_OK;
+}
+
+int vo_map_localise_dev(vo_map* m, int rows, int cols, int z_near, int z_far, const float K[9], const float* d_uv, const float* d_app,
+                        int n_max, const int* d_n, const vo_ransac_params* params, float thr, int n_iters, int min_inliers,
+                        const float* d_T0, float* d_T16, vo_map_localise_stats* d_stats) {
+  VO_MAP_LIVE(m);
+  const char* fn = "vo_map_localise_dev";
+  if (int r = localise_check(fn, MapFrames{1, K, d_uv, (size_t)n_max, d_app, (size_t)n_max, n_max, d_n}, params, n_iters, min_inliers, d_T0, d_T16, d_stats)) return r;
+  vo_ctx* c = m->ctx;
+  const size_t need = localise_layout(nullptr, 1, n_max).bytes;
+  if (int r = capture_growth_check(c->capturing, fn, {{m->loc_ws.cap, need}, {m->solver ? 1u : 0u, 1}}, "n_max %d", n_max)) return r;      // (the solver is made by the first call)
+  if (int r = set_device(c)) return r;
+  if (!m->solver) { if (int r = vo_picp_create(c, &m->solver)) return r; }
+  VO_HIP_CHECK(m->loc_ws.ensure(need, c->stream));
+  const LocaliseWs w = localise_layout(m->loc_ws.p, 1, n_max);
+  // 1. the lookup, with the hits' points gathered
+  if (int r = vo_map_lookup_dev(m, d_app, n_max, d_n, w.pairs, w.n_hits, w.xyz, w.local, nullptr)) return r;
+  // 2. the start pose and the pairs handed on
+  const bool ransac = params->n_hypotheses > 0;
+  if (ransac) {
+    if (int r = vo_estimate_pose_ransac_dev(c, rows, cols, z_near, z_far, K, w.xyz, n_max, d_uv, n_max, w.local, n_max, w.n_hits, params,
+                                            w.T_start, w.handed, w.n_handed, nullptr, nullptr, w.rstat))
+      return r;
+  }
+  // 3. the rounds (vo_picp_set_camera / _set_kernel_threshold without the pose upload: the pose comes from device memory)
+  vo_picp* s = m->solver;
+  picp_set_camera_threshold(s, rows, cols, z_near, z_far, K, thr);
+  if (int r = vo_picp_set_points_dev(s, w.xyz, n_max, d_uv, n_max)) return r;
+  if (int r = vo_picp_set_pose_dev(s, ransac ? w.T_start : d_T0)) return r;
+  if (int r = vo_picp_solve_dev(s, ransac ? w.handed : w.local, n_max, ransac ? w.n_handed : w.n_hits, 0, n_iters)) return r;
+  // 4. status, pose, statistics
+  MapLocaliseFinish f{};
+  f.n_frames = 1; f.n_max = n_max; f.d_n = d_n; f.n_hits = w.n_hits; f.ransac_status = ransac ? w.rstat : nullptr;
+  f.n_handed = ransac ? w.n_handed : w.n_hits; f.state = picp_state_dev(s); f.T0 = d_T0; f.min_inliers = min_inliers;
+  f.T_out = d_T16; f.stats = reinterpret_cast<int*>(d_stats);
+  VO_HIP_CHECK(launch_map_localise_finish(c->stream, f));
+  return VO_OK;
+}
+
+int vo_map_localise_batch_dev(vo_map* m, int n_frames, int rows, int cols, int z_near, int z_far, const float K[9], const float* d_uv,
+                              size_t uv_stride, const float* d_app, size_t app_stride, int n_max, const int* d_n,
+                              const vo_ransac_params* params, float thr, int n_iters, int min_inliers, const float* d_T0, float* d_T16,
+                              vo_map_localise_stats* d_stats) {
+  VO_MAP_LIVE(m);
+  const char* fn = "vo_map_localise_batch_dev";
+  if (int r = localise_check(fn, MapFrames{n_frames, K, d_uv, uv_stride, d_app, app_stride, n_max, d_n}, params, n_iters, min_inliers, d_T0, d_T16, d_stats)) return r;
+  VO_REQUIRE(n_frames >= 1 && n_frames <= 65535, "n_frames outside 1 .. 65535 (the frame is a grid dimension)");
+  VO_REQUIRE(uv_stride >= (size_t)n_max && app_stride >= (size_t)n_max, "a stride is smaller than n_max");
+  VO_REQUIRE(uv_stride < 0x7fffffff, "stride too large");
+  vo_ctx* c = m->ctx;
+  const size_t need = localise_layout(nullptr, n_frames, n_max).bytes;
+  if (int r = capture_growth_check(c->capturing, fn, {{m->loc_ws.cap, need}}, "%d frames of n_max %d", n_frames, n_max)) return r;
+  if (int r = set_device(c)) return r;
+  VO_HIP_CHECK(m->loc_ws.ensure(need, c->stream));
+  const LocaliseWs w = localise_layout(m->loc_ws.p, n_frames, n_max);
+  if (int r = vo_map_lookup_batch_dev(m, n_frames, d_app, app_stride, n_max, d_n, w.pairs, w.n_hits, w.xyz, w.local, nullptr)) return r;
+  const bool ransac = params->n_hypotheses > 0;
+  if (ransac) {
+    if (int r = vo_estimate_pose_ransac_batch_dev(c, n_frames, rows, cols, z_near, z_far, K, w.xyz, (size_t)n_max, n_max, d_uv, uv_stride,
+                                                  n_max, w.local, (size_t)n_max, w.n_hits, params, w.T_start, w.handed, w.n_handed,
+                                                  nullptr, nullptr, w.rstat))
+      return r;
+  }
+  if (int r = vo_picp_solve_batch_dev(c, n_frames, rows, cols, z_near, z_far, K, thr, 0, w.xyz, (size_t)n_max, d_uv, uv_stride,
+                                      ransac ? w.handed : w.local, (size_t)n_max, ransac ? w.n_handed : w.n_hits,
+                                      ransac ? w.T_start : d_T0, n_iters, w.T_solved, w.stats4))
+    return r;
+  MapLocaliseFinish f{};
+  f.n_frames = n_frames; f.n_max = n_max; f.d_n = d_n; f.n_hits = w.n_hits; f.ransac_status = ransac ? w.rstat : nullptr;
+  f.n_handed = ransac ? w.n_handed : w.n_hits; f.state = nullptr; f.T_solved = w.T_solved; f.stats4 = w.stats4; f.T0 = d_T0;
+  f.min_inliers = min_inliers; f.T_out = d_T16; f.stats = reinterpret_cast<int*>(d_stats);
+  VO_HIP_CHECK(launch_map_localise_finish(c->stream, f));
+  return VO_OK;
+}
+
+int vo_map_localise(vo_map* m, int rows, int cols, int z_near, int z_far, const float K[9], const float* uv, const float* app, int n,
+                    const vo_ransac_params* params, float thr, int n_iters, int min_inliers, const float T0[16], float T_out[16],
+                    vo_map_localise_stats* stats_out) {
+  VO_MAP_LIVE(m);
+  vo_ctx* c = m->ctx;
+  VO_NOT_CAPTURING(c);
+  VO_REQUIRE(K && uv && app && params && T_out && stats_out, "null argument");
+  VO_REQUIRE(n >= 1, "n must be positive");
+  if (int r = set_device(c)) return r;
+  if (int r = upload(c, c->in[0], uv, sizeof(float) * 2 * (size_t)n)) return r;
+  if (int r = upload(c, c->in[1], app, sizeof(float) * 10 * (size_t)n)) return r;
+  if (T0)
+    if (int r = upload(c, c->in[2], T0, sizeof(float) * 16)) return r;
+  VO_HIP_CHECK(c->out[2].ensure(128, c->stream));
+  VO_HIP_CHECK(hipStreamSynchronize(c->stream));          // the host arrays may go away after the call
+  struct { float T[16]; vo_map_localise_stats s; } h;
+  static_assert(sizeof(h) == 96, "pose and statistics come back in one copy");
+  char* d_res = c->out[2].as<char>();
+  if (int r = vo_map_localise_dev(m, rows, cols, z_near, z_far, K, c->in[0].as<float>(), c->in[1].as<float>(), n, nullptr, params, thr,
+                                  n_iters, min_inliers, T0 ? c->in[2].as<float>() : nullptr, reinterpret_cast<float*>(d_res),
+                                  reinterpret_cast<vo_map_localise_stats*>(d_res + 64)))
+    return r;
+  VO_HIP_CHECK(hipMemcpyAsync(&h, d_res, sizeof(h), hipMemcpyDeviceToHost, c->stream));
+  VO_HIP_CHECK(hipStreamSynchronize(c->stream));
+  memcpy(T_out, h.T, sizeof(h.T));
+  *stats_out = h.s;
+  return VO_OK;
+}
+
+// ---- the calls that take a window of frames (MapFrames, map_checks.h): what they share ---------------------------------------
+// the workspaces of a window call inside a capture (capture_growth_check): asked before the call's lookup is enqueued
+static int window_growth_check(const vo_map* m, const char* fn, const MapFrames& f, std::initializer_list<WsNeed> ws) {
+  return capture_growth_check(m->ctx->capturing, fn, ws, "%d frames of n_max %d on this map", f.n_frames, f.n_max);
+}
+
+// the map as a kernel sees it, and the frames, into an argument block that has these members
+template <class A>
+static void fill_map(A& a, const vo_map* m) { a.pts = m->d.pts; a.hdr = m->d.hdr; a.cap = m->d.cap; a.bound = map_bound(m); }
+template <class A>
+static void fill_frames(A& a, const MapFrames& f) {
+  a.uv = f.d_uv; a.uv_stride = f.uv_stride; a.n_max = f.n_max; a.n_frames = f.n_frames;
+  for (int k = 0; k < 9; ++k) a.K[k] = f.K[k];
+}
+
+// The begin step of a host-pointer window call, after the call's own null checks: the refusals of the frames `h` (host arrays,
+// n_max rows per frame; K null: a call without pixels, poses and camera), the uploads into the context's staging buffers in[0..4]
+// -- pixels, appearances, poses, row counts, the mask --, the map's size where the call wants it (asking also waits: the host
+// arrays may go away after the call), and the same frames over the staging buffers in `dev`.
+static int upload_window(const char* fn, vo_map* m, const MapFrames& h, const float* T16, const uint8_t* fixed, int* size, MapFrames* dev) {
+  vo_ctx* c = m->ctx;
+  const bool cam = h.K != nullptr;
+  if (h.n_frames < 1 || h.n_frames > 65535) return vo_fail(VO_ERR_INVALID_ARG, "%s: n_frames outside 1 .. 65535", fn);
+  if (h.n_max < 0 || (h.n_max > 0 && !((h.d_uv || !cam) && h.d_app))) return vo_fail(VO_ERR_INVALID_ARG, "%s: bad frames", fn);
+  if ((long long)h.n_max * h.n_frames > (1ll << 30)) return vo_fail(VO_ERR_INVALID_ARG, "%s: more than 2^30 rows in one call", fn);
+  if (int r = set_device(c)) return r;
+  const size_t F = (size_t)h.n_frames, rows = F * (size_t)h.n_max;
+  const auto up = [c](bool wanted, DevBuf& b, const void* src, size_t bytes) { return wanted ? upload(c, b, src, bytes) : (int)VO_OK; };
+  if (int r = up(cam, c->in[0], h.d_uv, sizeof(float) * 2 * rows)) return r;
+  if (int r = up(true, c->in[1], h.d_app, sizeof(float) * 10 * rows)) return r;
+  if (int r = up(cam, c->in[2], T16, sizeof(float) * 16 * F)) return r;
+  if (int r = up(h.d_n != nullptr, c->in[3], h.d_n, sizeof(int) * F)) return r;
+  if (int r = up(fixed != nullptr, c->in[4], fixed, F)) return r;
+  if (size)
+    if (int r = vo_map_size(m, size)) return r;
+  *dev = MapFrames{h.n_frames, h.K, cam ? c->in[0].as<float>() : nullptr, (size_t)h.n_max, c->in[1].as<float>(), (size_t)h.n_max, h.n_max,
+                   h.d_n ? c->in[3].as<int>() : nullptr};
+  return VO_OK;
+}
+
+// ---- structure-only refinement: the lookup of every frame, then the launches of map_refine.hip ----------------------------
+static_assert(sizeof(vo_map_refine_params) == 16 && sizeof(vo_map_refine_stats) == 48, "the statistics kernel writes eight 4-byte words and two doubles");
+
+// the point half's workspace, sized and laid out, and the lookup of every frame into it
+static int refine_prepare(const char* fn, vo_map* m, const MapFrames& f, MapRefineWs* out) {
+  vo_ctx* c = m->ctx;
+  const int bound = map_bound(m);
+  MapRefineWs w = map_refine_layout(nullptr, f.n_frames, f.n_max, bound);
+  if (int r = window_growth_check(m, fn, f, {{m->ref_ws.cap, w.bytes}, {m->look_ws.cap, f.n_max > 0 ? lookup_scratch_bytes(f, false) : 0}})) return r;
+  if (int r = set_device(c)) return r;
+  VO_HIP_CHECK(m->ref_ws.ensure(w.bytes, c->stream));
+  w = map_refine_layout(m->ref_ws.p, f.n_frames, f.n_max, bound);
+  if (int r = lookup_window(m, f, w.pairs, w.n_hits, w.ent)) return r;
+  *out = w;
+  return VO_OK;
+}
+
+// the point half's launches on a prepared workspace
+static int refine_run(vo_map* m, const MapRefineWs& w, const MapFrames& f, const float* d_T16, const MapRounds& r, int32_t* d_status_out,
+                      float* d_xyz_out, vo_map_refine_stats* d_stats) {
+  vo_ctx* c = m->ctx;
+  MapRefineArgs a{};
+  a.w = w;
+  fill_map(a, m);
+  fill_frames(a, f);
+  a.T16 = d_T16;
+  a.n_rounds = r.n_rounds; a.min_obs = r.min_obs; a.huber = r.huber_px; a.damping = *r.damping;
+  a.status = d_status_out ? d_status_out : w.status;
+  a.xyz_out = d_xyz_out; a.stats = d_stats;
+  VO_HIP_CHECK(launch_map_refine(c->stream, a, c->n_cu));
+  return VO_OK;
+}
+
+int vo_map_refine_batch_dev(vo_map* m, int n_frames, const float K[9], const float* d_uv, size_t uv_stride, const float* d_app,
+                            size_t app_stride, int n_max, const int* d_n, const float* d_T16, const vo_map_refine_params* params,
+                            int32_t* d_status_out, float* d_xyz_out, vo_map_refine_stats* d_stats) {
+  VO_MAP_LIVE(m);
+  const char* fn = "vo_map_refine_batch_dev";
+  if (!(K && params && d_T16 && d_stats)) return vo_fail(VO_ERR_INVALID_ARG, "%s: null argument", fn);
+  const MapFrames f{n_frames, K, d_uv, uv_stride, d_app, app_stride, n_max, d_n};
+  const MapRounds rounds{params->n_rounds, INT_MAX, params->min_obs, 2, params->huber_px, &params->damping};
+  if (int r = map_frames_check(fn, f, d_stats, &rounds)) return r;
+  MapRefineWs w;
+  if (int r = refine_prepare(fn, m, f, &w)) return r;
+  return refine_run(m, w, f, d_T16, rounds, d_status_out, d_xyz_out, d_stats);
+}
+
+int vo_map_refine(vo_map* m, int n_frames, const float K[9], const float* uv, const float* app, const int* n_rows, int n_max,
+                  const float* T16, const vo_map_refine_params* params, int32_t* status_out, vo_map_refine_stats* stats_out) {
+  VO_MAP_LIVE(m);
+  vo_ctx* c = m->ctx;
+  VO_NOT_CAPTURING(c);
+  VO_REQUIRE(K && T16 && params && stats_out, "null argument");
+  MapFrames f;
+  int size = 0;
+  if (int r = upload_window(__func__, m, MapFrames{n_frames, K, uv, 0, app, 0, n_max, n_rows}, T16, nullptr, &size, &f)) return r;
+  VO_HIP_CHECK(c->out[2].ensure(sizeof(vo_map_refine_stats) + 16, c->stream));
+  if (status_out) VO_HIP_CHECK(c->out[1].ensure(sizeof(int32_t) * (size_t)(size > 0 ? size : 1), c->stream));
+  if (int r = vo_map_refine_batch_dev(m, n_frames, K, f.d_uv, f.uv_stride, f.d_app, f.app_stride, n_max, f.d_n, c->in[2].as<float>(), params,
+                                      status_out ? c->out[1].as<int32_t>() : nullptr, nullptr, c->out[2].as<vo_map_refine_stats>()))
+    return r;
+  VO_HIP_CHECK(hipMemcpyAsync(stats_out, c->out[2].p, sizeof(vo_map_refine_stats), hipMemcpyDeviceToHost, c->stream));
+  if (status_out && size > 0) VO_HIP_CHECK(hipMemcpyAsync(status_out, c->out[1].p, sizeof(int32_t) * (size_t)size, hipMemcpyDeviceToHost, c->stream));
+  VO_HIP_CHECK(hipStreamSynchronize(c->stream));
+  return VO_OK;
+}
+
+// ---- motion-only refinement and the alternation of the two halves (map_pose_refine.hip) ------------------------------------
+static_assert(sizeof(vo_map_pose_refine_params) == 16 && sizeof(vo_map_pose_refine_stats) == 48 && sizeof(vo_map_adjust_params) == 28 &&
+              sizeof(vo_map_adjust_stats) == 96, "the statistics kernels write eight 4-byte words and two doubles each");
+
+// the pose half's workspace; with `ent` (the entries of a lookup already made for these frames) no lookup is enqueued
+static int pose_prepare(const char* fn, vo_map* m, const MapFrames& f, int32_t* ent, MapPoseWs* out) {
+  vo_ctx* c = m->ctx;
+  MapPoseWs w = map_pose_layout(nullptr, f.n_frames, f.n_max, !ent);
+  if (int r = window_growth_check(m, fn, f, {{m->pose_ws.cap, w.bytes}, {m->look_ws.cap, !ent && f.n_max > 0 ? lookup_scratch_bytes(f, false) : 0}})) return r;
+  if (int r = set_device(c)) return r;
+  VO_HIP_CHECK(m->pose_ws.ensure(w.bytes, c->stream));
+  w = map_pose_layout(m->pose_ws.p, f.n_frames, f.n_max, !ent);
+  if (ent) w.ent = ent;
+  else if (int r = lookup_window(m, f, w.pairs, w.n_hits, w.ent)) return r;
+  *out = w;
+  return VO_OK;
+}
+
+static int pose_run(vo_map* m, const MapPoseWs& w, const MapFrames& f, const float* d_T_in, const uint8_t* d_fixed, const MapRounds& r,
+                    float* d_T_out, int32_t* d_status_out, double* d_H_out, vo_map_pose_refine_stats* d_stats) {
+  vo_ctx* c = m->ctx;
+  MapPoseArgs a{};
+  a.ent = w.ent; a.n_obs = w.n_obs; a.cost = w.cost;
+  fill_map(a, m);
+  fill_frames(a, f);
+  a.T_in = d_T_in; a.T_out = d_T_out; a.fixed = d_fixed;
+  a.n_rounds = r.n_rounds; a.min_obs = r.min_obs; a.huber = r.huber_px; a.damping = *r.damping;
+  a.status = d_status_out ? d_status_out : w.status;
+  a.H_out = d_H_out; a.stats = d_stats;
+  VO_HIP_CHECK(launch_map_pose_refine(c->stream, a));
+  return VO_OK;
+}
+
+int vo_map_refine_poses_batch_dev(vo_map* m, int n_frames, const float K[9], const float* d_uv, size_t uv_stride, const float* d_app,
+                                  size_t app_stride, int n_max, const int* d_n, const float* d_T16_in, const uint8_t* d_fixed,
+                                  const vo_map_pose_refine_params* params, float* d_T16_out, int32_t* d_status_out, double* d_H_out,
+                                  vo_map_pose_refine_stats* d_stats) {
+  VO_MAP_LIVE(m);
+  const char* fn = "vo_map_refine_poses_batch_dev";
+  if (!(K && params && d_T16_in && d_T16_out && d_stats)) return vo_fail(VO_ERR_INVALID_ARG, "%s: null argument", fn);
+  if (!aligned8(d_H_out)) return vo_fail(VO_ERR_INVALID_ARG, "%s: device arrays must be 8-byte aligned", fn);
+  const MapFrames f{n_frames, K, d_uv, uv_stride, d_app, app_stride, n_max, d_n};
+  const MapRounds rounds{params->n_rounds, VO_MAP_ADJUST_MAX_ROUNDS, params->min_obs, 3, params->huber_px, &params->damping};
+  if (int r = map_frames_check(fn, f, d_stats, &rounds)) return r;
+  MapPoseWs w;
+  if (int r = pose_prepare(fn, m, f, nullptr, &w)) return r;
+  return pose_run(m, w, f, d_T16_in, d_fixed, rounds, d_T16_out, d_status_out, d_H_out, d_stats);
+}
+
+int vo_map_adjust_batch_dev(vo_map* m, int n_frames, const float K[9], const float* d_uv, size_t uv_stride, const float* d_app,
+                            size_t app_stride, int n_max, const int* d_n, float* d_T16, const uint8_t* d_fixed,
+                            const vo_map_adjust_params* p, int32_t* d_pose_status_out, int32_t* d_point_status_out,
+                            vo_map_adjust_stats* d_stats) {
+  VO_MAP_LIVE(m);
+  const char* fn = "vo_map_adjust_batch_dev";
+  if (!(K && p && d_T16 && d_stats)) return vo_fail(VO_ERR_INVALID_ARG, "%s: null argument", fn);
+  if (p->n_sweeps < 1 || p->n_sweeps > VO_MAP_ADJUST_MAX_ROUNDS) return vo_fail(VO_ERR_INVALID_ARG, "%s: n_sweeps outside 1 .. %d", fn, VO_MAP_ADJUST_MAX_ROUNDS);
+  const MapFrames f{n_frames, K, d_uv, uv_stride, d_app, app_stride, n_max, d_n};
+  const MapRounds pose{p->pose_rounds, VO_MAP_ADJUST_MAX_ROUNDS, p->min_obs_pose, 3, p->huber_px, &p->damping},
+                  point{p->point_rounds, VO_MAP_ADJUST_MAX_ROUNDS, p->min_obs_point, 2, p->huber_px, &p->damping};
+  if (int r = map_frames_check(fn, f, d_stats, &pose)) return r;
+  if (int r = map_rounds_check(fn, point)) return r;
+  if (int r = window_growth_check(m, fn, f, {{m->pose_ws.cap, map_pose_layout(nullptr, n_frames, n_max, false).bytes}})) return r;      // (before the point half enqueues its lookup)
+  MapRefineWs rw;
+  MapPoseWs pw;
+  if (int r = refine_prepare(fn, m, f, &rw)) return r;        // the one lookup: both halves read rw.ent
+  if (int r = pose_prepare(fn, m, f, rw.ent, &pw)) return r;
+  for (int s = 0; s < p->n_sweeps; ++s) {
+    if (int r = pose_run(m, pw, f, d_T16, d_fixed, pose, d_T16, d_pose_status_out, nullptr, &d_stats[s].poses)) return r;
+    if (int r = refine_run(m, rw, f, d_T16, point, d_point_status_out, nullptr, &d_stats[s].points)) return r;
+  }
+  return VO_OK;
+}
+
+int vo_map_refine_poses(vo_map* m, int n_frames, const float K[9], const float* uv, const float* app, const int* n_rows, int n_max,
+                        float* T16, const uint8_t* fixed, const vo_map_pose_refine_params* params, int32_t* status_out, double* H_out,
+                        vo_map_pose_refine_stats* stats_out) {
+  VO_MAP_LIVE(m);
+  vo_ctx* c = m->ctx;
+  VO_NOT_CAPTURING(c);
+  VO_REQUIRE(K && T16 && params && stats_out, "null argument");
+  MapFrames f;
+  if (int r = upload_window(__func__, m, MapFrames{n_frames, K, uv, 0, app, 0, n_max, n_rows}, T16, fixed, nullptr, &f)) return r;   // (no size wanted)
+  const size_t F = (size_t)n_frames;
+  VO_HIP_CHECK(c->out[0].ensure(sizeof(double) * 36 * F, c->stream));
+  VO_HIP_CHECK(c->out[1].ensure(sizeof(int32_t) * F, c->stream));
+  VO_HIP_CHECK(c->out[2].ensure(sizeof(vo_map_pose_refine_stats) + 16, c->stream));
+  if (H_out) VO_HIP_CHECK(hipMemcpyAsync(c->out[0].p, H_out, sizeof(double) * 36 * F, hipMemcpyHostToDevice, c->stream));
+  if (int r = vo_map_refine_poses_batch_dev(m, n_frames, K, f.d_uv, f.uv_stride, f.d_app, f.app_stride, n_max, f.d_n, c->in[2].as<float>(),
+                                            fixed ? c->in[4].as<uint8_t>() : nullptr, params, c->in[2].as<float>(),
+                                            status_out ? c->out[1].as<int32_t>() : nullptr, H_out ? c->out[0].as<double>() : nullptr,
+                                            c->out[2].as<vo_map_pose_refine_stats>()))
+    return r;
+  VO_HIP_CHECK(hipMemcpyAsync(stats_out, c->out[2].p, sizeof(vo_map_pose_refine_stats), hipMemcpyDeviceToHost, c->stream));
+  VO_HIP_CHECK(hipMemcpyAsync(T16, c->in[2].p, sizeof(float) * 16 * F, hipMemcpyDeviceToHost, c->stream));
+  if (status_out) VO_HIP_CHECK(hipMemcpyAsync(status_out, c->out[1].p, sizeof(int32_t) * F, hipMemcpyDeviceToHost, c->stream));
+  if (H_out) VO_HIP_CHECK(hipMemcpyAsync(H_out, c->out[0].p, sizeof(double) * 36 * F, hipMemcpyDeviceToHost, c->stream));
+  VO_HIP_CHECK(hipStreamSynchronize(c->stream));
+  return VO_OK;
+}
+
+int vo_map_adjust(vo_map* m, int n_frames, const float K[9], const float* uv, const float* app, const int* n_rows, int n_max, float* T16,
+                  const uint8_t* fixed, const vo_map_adjust_params* params, int32_t* pose_status_out, int32_t* point_status_out,
+                  vo_map_adjust_stats* stats_out) {
+  VO_MAP_LIVE(m);
+  vo_ctx* c = m->ctx;
+  VO_NOT_CAPTURING(c);
+  VO_REQUIRE(K && T16 && params && stats_out, "null argument");
+  VO_REQUIRE(params->n_sweeps >= 1 && params->n_sweeps <= VO_MAP_ADJUST_MAX_ROUNDS, "n_sweeps outside 1 .. 65536");
+  MapFrames f;
+  int size = 0;
+  if (int r = upload_window(__func__, m, MapFrames{n_frames, K, uv, 0, app, 0, n_max, n_rows}, T16, fixed, &size, &f)) return r;
+  const size_t F = (size_t)n_frames, S = (size_t)params->n_sweeps;
+  VO_HIP_CHECK(c->out[0].ensure(sizeof(int32_t) * F, c->stream));
+  if (point_status_out) VO_HIP_CHECK(c->out[1].ensure(sizeof(int32_t) * (size_t)(size > 0 ? size : 1), c->stream));
+  VO_HIP_CHECK(c->out[2].ensure(sizeof(vo_map_adjust_stats) * S + 16, c->stream));
+  if (int r = vo_map_adjust_batch_dev(m, n_frames, K, f.d_uv, f.uv_stride, f.d_app, f.app_stride, n_max, f.d_n, c->in[2].as<float>(),
+                                      fixed ? c->in[4].as<uint8_t>() : nullptr, params, pose_status_out ? c->out[0].as<int32_t>() : nullptr,
+                                      point_status_out ? c->out[1].as<int32_t>() : nullptr, c->out[2].as<vo_map_adjust_stats>()))
+    return r;
+  VO_HIP_CHECK(hipMemcpyAsync(stats_out, c->out[2].p, sizeof(vo_map_adjust_stats) * S, hipMemcpyDeviceToHost, c->stream));
+  VO_HIP_CHECK(hipMemcpyAsync(T16, c->in[2].p, sizeof(float) * 16 * F, hipMemcpyDeviceToHost, c->stream));
+  if (pose_status_out) VO_HIP_CHECK(hipMemcpyAsync(pose_status_out, c->out[0].p, sizeof(int32_t) * F, hipMemcpyDeviceToHost, c->stream));
+  if (point_status_out && size > 0)
+    VO_HIP_CHECK(hipMemcpyAsync(point_status_out, c->out[1].p, sizeof(int32_t) * (size_t)size, hipMemcpyDeviceToHost, c->stream));
+  VO_HIP_CHECK(hipStreamSynchronize(c->stream));
+  return VO_OK;
+}
+
+// ---- joint adjustment by matrix-free Schur PCG (map_bundle.hip; include/vo_map_bundle.h: the vox_ namespace) ---------------
+static_assert(sizeof(vox_map_bundle_params) == 28 && sizeof(vox_map_bundle_round) == 40 && sizeof(vox_map_bundle_stats) == 48,
+              "the records of include/vo_map_bundle.h as the kernels write them");
+
+int vox_map_bundle_batch_dev(vo_map* m, int n_frames, const float K[9], const float* d_uv, size_t uv_stride, const float* d_app,
+                             size_t app_stride, int n_max, const int* d_n, float* d_T16, const uint8_t* d_fixed,
+                             const vox_map_bundle_params* p, int32_t* d_pose_status_out, int32_t* d_point_status_out,
+                             vox_map_bundle_round* d_rounds_out, vox_map_bundle_stats* d_stats) {
+  VO_MAP_LIVE(m);
+  const char* fn = "vox_map_bundle_batch_dev";
+  if (!(K && p && d_T16 && d_stats)) return vo_fail(VO_ERR_INVALID_ARG, "%s: null argument", fn);
+  if (!aligned8(d_rounds_out)) return vo_fail(VO_ERR_INVALID_ARG, "%s: device arrays must be 8-byte aligned", fn);
+  const MapFrames f{n_frames, K, d_uv, uv_stride, d_app, app_stride, n_max, d_n};
+  const MapRounds rounds{p->n_rounds, VOX_MAP_BUNDLE_MAX_STEPS, p->min_obs_pose, 3, p->huber_px, nullptr};
+  if (int r = map_frames_check(fn, f, d_stats, &rounds)) return r;
+  if (p->min_obs_point < 2) return vo_fail(VO_ERR_INVALID_ARG, "%s: min_obs_point must be at least 2", fn);
+  if (p->n_cg < 1) return vo_fail(VO_ERR_INVALID_ARG, "%s: n_cg must be at least 1", fn);
+  if (!(p->cg_tol >= 0.f && p->cg_tol <= 3.402823466e38f)) return vo_fail(VO_ERR_INVALID_ARG, "%s: cg_tol must be finite and not negative", fn);
+  if (!(p->lambda0 >= 0.f && p->lambda0 <= 3.402823466e38f)) return vo_fail(VO_ERR_INVALID_ARG, "%s: lambda0 must be finite and not negative", fn);
+  if ((long long)p->n_rounds * ((long long)p->n_cg + 2) > VOX_MAP_BUNDLE_MAX_STEPS)
+    return vo_fail(VO_ERR_INVALID_ARG, "%s: n_rounds * (n_cg + 2) above %d (the launches of a call are a fixed sequence)", fn, VOX_MAP_BUNDLE_MAX_STEPS);
+  vo_ctx* c = m->ctx;
+  const int bound = map_bound(m);
+  MapBundleWs bw = map_bundle_layout(nullptr, n_frames, bound);
+  if (int r = window_growth_check(m, fn, f, {{m->bundle_ws.cap, bw.bytes}})) return r;      // (before the lookup is enqueued)
+  MapRefineWs rw;
+  if (int r = refine_prepare(fn, m, f, &rw)) return r;        // the one lookup of the call
+  VO_HIP_CHECK(m->bundle_ws.ensure(bw.bytes, c->stream));
+  MapBundleArgs a{};
+  a.l = rw; a.w = map_bundle_layout(m->bundle_ws.p, n_frames, bound);
+  fill_map(a, m);
+  fill_frames(a, f);
+  a.T16 = d_T16; a.fixed = d_fixed;
+  a.n_rounds = p->n_rounds; a.n_cg = p->n_cg; a.min_obs_pose = p->min_obs_pose; a.min_obs_point = p->min_obs_point;
+  a.cg_tol = p->cg_tol; a.lambda0 = p->lambda0; a.huber = p->huber_px;
+  a.pose_status_out = d_pose_status_out; a.point_status_out = d_point_status_out; a.rounds_out = d_rounds_out; a.stats = d_stats;
+  VO_HIP_CHECK(launch_map_bundle(c->stream, a, c->n_cu));
+  return VO_OK;
+}
+
+int vox_map_bundle(vo_map* m, int n_frames, const float K[9], const float* uv, const float* app, const int* n_rows, int n_max, float* T16,
+                   const uint8_t* fixed, const vox_map_bundle_params* params, int32_t* pose_status_out, int32_t* point_status_out,
+                   vox_map_bundle_round* rounds_out, vox_map_bundle_stats* stats_out) {
+  VO_MAP_LIVE(m);
+  vo_ctx* c = m->ctx;
+  VO_NOT_CAPTURING(c);
+  VO_REQUIRE(K && T16 && params && stats_out, "null argument");
+  VO_REQUIRE(params->n_rounds >= 0 && params->n_rounds <= VOX_MAP_BUNDLE_MAX_STEPS, "n_rounds outside 0 .. 65536");
+  MapFrames f;
+  int size = 0;
+  if (int r = upload_window(__func__, m, MapFrames{n_frames, K, uv, 0, app, 0, n_max, n_rows}, T16, fixed, &size, &f)) return r;
+  const size_t F = (size_t)n_frames, S = (size_t)params->n_rounds;
+  VO_HIP_CHECK(c->out[0].ensure(sizeof(int32_t) * F, c->stream));
+  if (point_status_out) VO_HIP_CHECK(c->out[1].ensure(sizeof(int32_t) * (size_t)(size > 0 ? size : 1), c->stream));
+  VO_HIP_CHECK(c->out[2].ensure(sizeof(vox_map_bundle_stats) + sizeof(vox_map_bundle_round) * S + 16, c->stream));
+  vox_map_bundle_stats* d_st = c->out[2].as<vox_map_bundle_stats>();
+  vox_map_bundle_round* d_rd = reinterpret_cast<vox_map_bundle_round*>(d_st + 1);
+  if (int r = vox_map_bundle_batch_dev(m, n_frames, K, f.d_uv, f.uv_stride, f.d_app, f.app_stride, n_max, f.d_n, c->in[2].as<float>(),
+                                       fixed ? c->in[4].as<uint8_t>() : nullptr, params, pose_status_out ? c->out[0].as<int32_t>() : nullptr,
+                                       point_status_out ? c->out[1].as<int32_t>() : nullptr, rounds_out && S ? d_rd : nullptr, d_st))
+    return r;
+  VO_HIP_CHECK(hipMemcpyAsync(stats_out, d_st, sizeof(vox_map_bundle_stats), hipMemcpyDeviceToHost, c->stream));
+  if (rounds_out && S) VO_HIP_CHECK(hipMemcpyAsync(rounds_out, d_rd, sizeof(vox_map_bundle_round) * S, hipMemcpyDeviceToHost, c->stream));
+  VO_HIP_CHECK(hipMemcpyAsync(T16, c->in[2].p, sizeof(float) * 16 * F, hipMemcpyDeviceToHost, c->stream));
+  if (pose_status_out) VO_HIP_CHECK(hipMemcpyAsync(pose_status_out, c->out[0].p, sizeof(int32_t) * F, hipMemcpyDeviceToHost, c->stream));
+  if (point_status_out && size > 0)
+    VO_HIP_CHECK(hipMemcpyAsync(point_status_out, c->out[1].p, sizeof(int32_t) * (size_t)size, hipMemcpyDeviceToHost, c->stream));
+  VO_HIP_CHECK(hipStreamSynchronize(c->stream));
+  return VO_OK;
+}
+
+// ---- culling of landmarks (map_cull.hip; include/vo_map_cull.h: the voe_ namespace) ---------------------------------------
+static_assert(sizeof(voe_map_cull_params) == 28 && sizeof(voe_map_cull_entry) == 48 && sizeof(voe_map_cull_stats) == 48,
+              "the records of include/vo_map_cull.h as the kernels write them");
+
+static int cull_check_params(const char* fn, const voe_map_cull_params* p) {
+  if (p->min_obs < 1) return vo_fail(VO_ERR_INVALID_ARG, "%s: min_obs must be at least 1", fn);
+  if (p->min_frames < 1) return vo_fail(VO_ERR_INVALID_ARG, "%s: min_frames must be at least 1", fn);
+  if (!(p->max_rms_px >= 0.f && p->max_rms_px <= 3.402823466e38f)) return vo_fail(VO_ERR_INVALID_ARG, "%s: max_rms_px must be finite and not negative", fn);
+  if (!(p->max_err_px >= 0.f && p->max_err_px <= 3.402823466e38f)) return vo_fail(VO_ERR_INVALID_ARG, "%s: max_err_px must be finite and not negative", fn);
+  if (!(p->min_parallax_deg >= 0.f && p->min_parallax_deg < 180.f)) return vo_fail(VO_ERR_INVALID_ARG, "%s: min_parallax_deg must be in [0, 180)", fn);
+  return VO_OK;
+}
+
+int voe_map_cull_batch_dev(vo_map* m, int n_frames, const float K[9], const float* d_uv, size_t uv_stride, const float* d_app,
+                           size_t app_stride, int n_max, const int* d_n, const float* d_T16, const voe_map_cull_params* p,
+                           int32_t* d_verdict_out, int32_t* d_remap_out, voe_map_cull_entry* d_entry_out, voe_map_cull_stats* d_stats) {
+  VO_MAP_LIVE(m);
+  const char* fn = "voe_map_cull_batch_dev";
+  if (!(K && p && d_T16 && d_stats)) return vo_fail(VO_ERR_INVALID_ARG, "%s: null argument", fn);
+  if (!aligned8(d_entry_out)) return vo_fail(VO_ERR_INVALID_ARG, "%s: device arrays must be 8-byte aligned", fn);
+  const MapFrames f{n_frames, K, d_uv, uv_stride, d_app, app_stride, n_max, d_n};
+  if (int r = map_frames_check(fn, f, d_stats)) return r;
+  if (int r = cull_check_params(fn, p)) return r;
+  vo_ctx* c = m->ctx;
+  const int bound = map_bound(m);
+  MapCullWs cw = map_cull_layout(nullptr, bound);
+  if (int r = window_growth_check(m, fn, f, {{m->cull_ws.cap, cw.bytes}})) return r;        // (before the lookup is enqueued)
+  MapRefineWs rw;
+  if (int r = refine_prepare(fn, m, f, &rw)) return r;        // the one lookup of the call
+  VO_HIP_CHECK(m->cull_ws.ensure(cw.bytes, c->stream));
+  MapCullArgs a{};
+  a.l = rw; a.w = map_cull_layout(m->cull_ws.p, bound);
+  fill_map(a, m);
+  a.app = m->d.app;
+  fill_frames(a, f);
+  a.T16 = d_T16;
+  a.min_obs = p->min_obs; a.min_frames = p->min_frames; a.drop_unseen = p->drop_unseen != 0; a.dry_run = p->dry_run != 0;
+  a.max_mean_sq = (double)p->max_rms_px * (double)p->max_rms_px;
+  a.max_sq = (double)p->max_err_px * (double)p->max_err_px;
+  a.parallax = p->min_parallax_deg > 0.f;
+  a.cos_thr = a.parallax ? cos((double)p->min_parallax_deg * 3.14159265358979323846 / 180.0) : 1.0;
+  a.verdict = d_verdict_out ? d_verdict_out : a.w.verdict;
+  a.remap = d_remap_out ? d_remap_out : a.w.remap;
+  a.entry_out = d_entry_out; a.stats = d_stats;
+  VO_HIP_CHECK(launch_map_cull(c->stream, a, c->n_cu));
+  VO_HIP_CHECK(launch_map_rehash(c->stream, m->d, bound, a.w.ctl + 2));
+  VO_HIP_CHECK(launch_map_cull_stats(c->stream, a));
+  return VO_OK;
+}
+
+int voe_map_cull(vo_map* m, int n_frames, const float K[9], const float* uv, const float* app, const int* n_rows, int n_max,
+                 const float* T16, const voe_map_cull_params* params, int32_t* verdict_out, int32_t* remap_out,
+                 voe_map_cull_entry* entry_out, voe_map_cull_stats* stats_out) {
+  VO_MAP_LIVE(m);
+  vo_ctx* c = m->ctx;
+  VO_NOT_CAPTURING(c);
+  VO_REQUIRE(K && T16 && params && stats_out, "null argument");
+  MapFrames f;
+  int size = 0;
+  if (int r = upload_window(__func__, m, MapFrames{n_frames, K, uv, 0, app, 0, n_max, n_rows}, T16, nullptr, &size, &f)) return r;
+  const size_t S = (size_t)(size > 0 ? size : 1);
+  VO_HIP_CHECK(c->out[0].ensure(sizeof(int32_t) * 2 * S, c->stream));
+  VO_HIP_CHECK(c->out[1].ensure(sizeof(voe_map_cull_entry) * S, c->stream));
+  VO_HIP_CHECK(c->out[2].ensure(sizeof(voe_map_cull_stats) + 16, c->stream));
+  int32_t* d_verdict = c->out[0].as<int32_t>();
+  int32_t* d_remap = d_verdict + S;
+  if (int r = voe_map_cull_batch_dev(m, n_frames, K, f.d_uv, f.uv_stride, f.d_app, f.app_stride, n_max, f.d_n, c->in[2].as<float>(), params,
+                                     verdict_out ? d_verdict : nullptr, remap_out ? d_remap : nullptr,
+                                     entry_out ? c->out[1].as<voe_map_cull_entry>() : nullptr, c->out[2].as<voe_map_cull_stats>()))
+    return r;
+  VO_HIP_CHECK(hipMemcpyAsync(stats_out, c->out[2].p, sizeof(voe_map_cull_stats), hipMemcpyDeviceToHost, c->stream));
+  if (size > 0) {
+    if (verdict_out) VO_HIP_CHECK(hipMemcpyAsync(verdict_out, d_verdict, sizeof(int32_t) * (size_t)size, hipMemcpyDeviceToHost, c->stream));
+    if (remap_out) VO_HIP_CHECK(hipMemcpyAsync(remap_out, d_remap, sizeof(int32_t) * (size_t)size, hipMemcpyDeviceToHost, c->stream));
+    if (entry_out) VO_HIP_CHECK(hipMemcpyAsync(entry_out, c->out[1].p, sizeof(voe_map_cull_entry) * (size_t)size, hipMemcpyDeviceToHost, c->stream));
+  }
+  VO_HIP_CHECK(hipStreamSynchronize(c->stream));
+  if (!m->replayable && !params->dry_run) m->size_ub = stats_out->n_kept;
+  return VO_OK;
+}
+
+// ---- two maps: alignment by 3-point similarity RANSAC and the merge (map_align.hip; include/vo_map_align.h) ----------------
+static_assert(sizeof(voe_map_align_params) == 32 && sizeof(voe_map_align_stats) == 48 && sizeof(voe_map_merge_stats) == 16,
+              "the records of include/vo_map_align.h as the kernels write them");
+
+int voe_map_size_bound(vo_map* m, int* n_max_out) {
+  VO_MAP_LIVE(m);
+  VO_REQUIRE(n_max_out, "null argument");
+  *n_max_out = map_bound(m);
+  return VO_OK;
+}
+
+static int two_maps_check(const char* fn, const vo_map* dst, const vo_map* src) {
+  if (!dst || !src) return vo_fail(VO_ERR_INVALID_ARG, "%s: null map", fn);
+  if (dst == src) return vo_fail(VO_ERR_INVALID_ARG, "%s: src and dst are one map", fn);
+  if (!ctx_alive(dst->ctx, dst->ctx_id) || !ctx_alive(src->ctx, src->ctx_id))
+    return vo_fail(VO_ERR_INVALID_ARG, "%s: the context a map was made on has been destroyed", fn);
+  if (dst->ctx != src->ctx) return vo_fail(VO_ERR_INVALID_ARG, "%s: the maps live on different contexts", fn);
+  return VO_OK;
+}
+
+static int align_check_params(const char* fn, const voe_map_align_params* p) {
+  if (!p) return vo_fail(VO_ERR_INVALID_ARG, "%s: null argument", fn);
+  if (p->n_hypotheses < 1 || p->n_hypotheses > 65536) return vo_fail(VO_ERR_INVALID_ARG, "%s: n_hypotheses outside 1 .. 65536", fn);
+  if (p->n_refits < 0 || p->n_refits > VOE_MAP_ALIGN_MAX_REFITS)
+    return vo_fail(VO_ERR_INVALID_ARG, "%s: n_refits outside 0 .. %d (the launches of a call are a fixed sequence)", fn, VOE_MAP_ALIGN_MAX_REFITS);
+  if (p->min_inliers < 0) return vo_fail(VO_ERR_INVALID_ARG, "%s: min_inliers must not be negative", fn);
+  if (!(p->threshold > 0.f && p->threshold <= 3.402823466e38f)) return vo_fail(VO_ERR_INVALID_ARG, "%s: threshold must be positive and finite", fn);
+  return VO_OK;
+}
+
+int voe_map_align_dev(vo_map* dst, vo_map* src, const voe_map_align_params* p, float* d_S16_out, int32_t* d_pairs_out, int* d_n_matches,
+                      uint8_t* d_inlier_mask, int32_t* d_hypothesis_counts, voe_map_align_stats* d_stats) {
+  const char* fn = "voe_map_align_dev";
+  if (int r = two_maps_check(fn, dst, src)) return r;
+  if (int r = align_check_params(fn, p)) return r;
+  if (!(d_S16_out && d_pairs_out && d_n_matches && d_stats)) return vo_fail(VO_ERR_INVALID_ARG, "%s: null argument", fn);
+  if (!aligned8(d_pairs_out, d_stats)) return vo_fail(VO_ERR_INVALID_ARG, "%s: d_pairs_out and d_stats must be 8-byte aligned", fn);
+  vo_ctx* c = dst->ctx;
+  const int n_max = map_bound(src);
+  size_t bytes = 0;
+  (void)map_align_layout(nullptr, n_max, p->n_hypotheses, &bytes);
+  if (int r = capture_growth_check(c->capturing, fn, {{dst->align_ws.cap, bytes}}, "these maps and %d hypotheses", p->n_hypotheses)) return r;      // (before the lookup is enqueued)
+  if (int r = set_device(c)) return r;
+  VO_HIP_CHECK(dst->align_ws.ensure(bytes, c->stream));
+  MapAlignArgs a = map_align_layout(dst->align_ws.p, n_max, p->n_hypotheses, nullptr);
+  // the matches: the public lookup, on dst, of src's appearances
+  if (int r = vo_map_lookup_dev(dst, src->d.app, n_max, src->d.hdr, d_pairs_out, d_n_matches, a.bxyz, nullptr, nullptr)) return r;
+  a.src_pts = src->d.pts; a.pairs = d_pairs_out; a.d_n = d_n_matches;
+  a.with_scale = p->with_scale != 0; a.n_refits = p->n_refits; a.min_inliers = p->min_inliers; a.seed = p->seed;
+  a.thr2 = p->threshold * p->threshold;
+  if (d_hypothesis_counts) a.counts = d_hypothesis_counts;
+  a.mask_out = d_inlier_mask;
+  a.S16_out = d_S16_out; a.stats = d_stats;
+  VO_HIP_CHECK(launch_map_align(c->stream, a));
+  return VO_OK;
+}
+
+int voe_map_align(vo_map* dst, vo_map* src, const voe_map_align_params* p, float S16_out[16], int32_t* pairs_out, int* n_matches_out,
+                  uint8_t* mask_out, int32_t* counts_out, voe_map_align_stats* stats_out) {
+  const char* fn = "voe_map_align";
+  if (int r = two_maps_check(fn, dst, src)) return r;
+  vo_ctx* c = dst->ctx;
+  VO_NOT_CAPTURING(c);
+  if (int r = align_check_params(fn, p)) return r;
+  VO_REQUIRE(S16_out && stats_out, "null argument");
+  if (int r = set_device(c)) return r;
+  int size = 0;
+  if (int r = vo_map_size(src, &size)) return r;              // (the bound becomes the size, unless an update of src was captured)
+  const size_t n = (size_t)(map_bound(src) > 0 ? map_bound(src) : 1), H = (size_t)p->n_hypotheses;
+  VO_HIP_CHECK(c->out[0].ensure(sizeof(int32_t) * 2 * n, c->stream));
+  VO_HIP_CHECK(c->out[1].ensure(up256(n) + sizeof(int32_t) * H, c->stream));
+  VO_HIP_CHECK(c->out[2].ensure(256, c->stream));
+  uint8_t* d_mask = c->out[1].as<uint8_t>();
+  int32_t* d_counts = reinterpret_cast<int32_t*>(d_mask + up256(n));
+  float* d_S = c->out[2].as<float>();
+  int* d_nm = reinterpret_cast<int*>(d_S + 16);
+  voe_map_align_stats* d_st = reinterpret_cast<voe_map_align_stats*>(d_S + 32);
+  if (int r = voe_map_align_dev(dst, src, p, d_S, c->out[0].as<int32_t>(), d_nm, mask_out ? d_mask : nullptr, counts_out ? d_counts : nullptr, d_st))
+    return r;
+  VO_HIP_CHECK(hipMemcpyAsync(S16_out, d_S, sizeof(float) * 16, hipMemcpyDeviceToHost, c->stream));
+  VO_HIP_CHECK(hipMemcpyAsync(stats_out, d_st, sizeof(voe_map_align_stats), hipMemcpyDeviceToHost, c->stream));
+  if (size > 0) {
+    if (pairs_out) VO_HIP_CHECK(hipMemcpyAsync(pairs_out, c->out[0].p, sizeof(int32_t) * 2 * (size_t)size, hipMemcpyDeviceToHost, c->stream));
+    if (mask_out) VO_HIP_CHECK(hipMemcpyAsync(mask_out, d_mask, (size_t)size, hipMemcpyDeviceToHost, c->stream));
+  }
+  if (counts_out) VO_HIP_CHECK(hipMemcpyAsync(counts_out, d_counts, sizeof(int32_t) * H, hipMemcpyDeviceToHost, c->stream));
+  VO_HIP_CHECK(hipStreamSynchronize(c->stream));
+  if (n_matches_out) *n_matches_out = stats_out->n_matches;
+  return VO_OK;
+}
+
+int voe_map_merge_dev(vo_map* dst, vo_map* src, const float* d_S16, int policy, int32_t* d_remap_out, voe_map_merge_stats* d_stats) {
+  const char* fn = "voe_map_merge_dev";
+  if (int r = two_maps_check(fn, dst, src)) return r;
+  if (policy != VOE_MAP_MERGE_TAKE_SRC && policy != VOE_MAP_MERGE_KEEP_DST) return vo_fail(VO_ERR_INVALID_ARG, "%s: unknown policy %d", fn, policy);
+  if (!d_stats) return vo_fail(VO_ERR_INVALID_ARG, "%s: null argument", fn);
+  vo_ctx* c = dst->ctx;
+  const int n_max = map_bound(src);
+  const MapMergeWs lay = map_merge_layout(nullptr, n_max);
+  const size_t look = sizeof(int) * map_lookup_scratch_ints(n_max, 1, false), upd = sizeof(int) * map_scratch_ints(n_max);
+  if (int r = capture_growth_check(c->capturing, fn, {{dst->merge_ws.cap, lay.bytes}, {dst->look_ws.cap, look}, {dst->scratch.cap, upd}}, "these maps")) return r;      // (before anything is enqueued)
+  if (int r = set_device(c)) return r;
+  if (int r = map_reserve(dst, n_max)) return r;              // dst grows here, on the host, or the capture is refused
+  VO_HIP_CHECK(dst->merge_ws.ensure(lay.bytes, c->stream));
+  const MapMergeWs w = map_merge_layout(dst->merge_ws.p, n_max);
+  VO_HIP_CHECK(launch_map_merge_begin(c->stream, w, dst->d.hdr));
+  // the lookup before the merge: which src entries dst holds already
+  if (int r = vo_map_lookup_dev(dst, src->d.app, n_max, src->d.hdr, w.pairs, w.ctl + 1, nullptr, nullptr, w.ent)) return r;
+  if (policy == VOE_MAP_MERGE_TAKE_SRC) {
+    if (int r = vo_map_update_dev(dst, src->d.pts, src->d.app, n_max, src->d.hdr, d_S16)) return r;
+  } else {
+    VO_HIP_CHECK(launch_map_merge_misses(c->stream, w, src->d.pts, src->d.app, src->d.hdr, n_max));
+    if (int r = vo_map_update_dev(dst, w.stage_pts, w.stage_app, n_max, w.ctl + 2, d_S16)) return r;
+  }
+  if (d_remap_out)
+    if (int r = vo_map_lookup_dev(dst, src->d.app, n_max, src->d.hdr, w.pairs, w.ctl + 3, nullptr, nullptr, d_remap_out)) return r;
+  VO_HIP_CHECK(launch_map_merge_stats(c->stream, w, src->d.hdr, dst->d.hdr, n_max, d_stats));
+  return VO_OK;
+}
+
+int voe_map_merge(vo_map* dst, vo_map* src, const float S16[16], int policy, int32_t* remap_out, voe_map_merge_stats* stats_out) {
+  const char* fn = "voe_map_merge";
+  if (int r = two_maps_check(fn, dst, src)) return r;
+  vo_ctx* c = dst->ctx;
+  VO_NOT_CAPTURING(c);
+  VO_REQUIRE(stats_out, "null argument");
+  if (int r = set_device(c)) return r;
+  int size = 0;
+  if (int r = vo_map_size(src, &size)) return r;
+  const size_t n = (size_t)(map_bound(src) > 0 ? map_bound(src) : 1);
+  VO_HIP_CHECK(c->out[0].ensure(sizeof(int32_t) * n, c->stream));
+  VO_HIP_CHECK(c->out[2].ensure(256, c->stream));
+  float* d_S = c->out[2].as<float>();
+  voe_map_merge_stats* d_st = reinterpret_cast<voe_map_merge_stats*>(d_S + 16);
+  if (S16) {
+    VO_HIP_CHECK(hipMemcpyAsync(d_S, S16, sizeof(float) * 16, hipMemcpyHostToDevice, c->stream));
+    VO_HIP_CHECK(hipStreamSynchronize(c->stream));            // the host array may go away after the call
+  }
+  if (int r = voe_map_merge_dev(dst, src, S16 ? d_S : nullptr, policy, remap_out ? c->out[0].as<int32_t>() : nullptr, d_st)) return r;
+  VO_HIP_CHECK(hipMemcpyAsync(stats_out, d_st, sizeof(voe_map_merge_stats), hipMemcpyDeviceToHost, c->stream));
+  if (remap_out && size > 0) VO_HIP_CHECK(hipMemcpyAsync(remap_out, c->out[0].p, sizeof(int32_t) * (size_t)size, hipMemcpyDeviceToHost, c->stream));
+  VO_HIP_CHECK(hipStreamSynchronize(c->stream));
+  if (!dst->replayable) dst->size_ub = stats_out->n_dst_after;
+  return VO_OK;
+}
+
+// ---- covisibility of frames and the window chosen from it (map_covis.hip; include/vo_map_covis.h) --------------------------
+static_assert(sizeof(voe_map_covis_stats) == 32 && sizeof(voe_map_window_params) == 16 && sizeof(voe_map_window_stats) == 32,
+              "the records of include/vo_map_covis.h as the kernels write them");
+
+// the refusals that need no map come first: they are the same on a machine without a device
+// (dev: d_stats is a device pointer, written as 8-byte pieces)
+static int covis_check(const char* fn, int n_frames, int n_words, const void* d_bits, const void* d_stats, bool dev) {
+  if (n_frames < 1 || n_frames > VOE_MAP_COVIS_MAX_FRAMES)
+    return vo_fail(VO_ERR_INVALID_ARG, "%s: n_frames %d outside 1 .. %d", fn, n_frames, VOE_MAP_COVIS_MAX_FRAMES);
+  if (n_words < 1) return vo_fail(VO_ERR_INVALID_ARG, "%s: n_words must be at least 1", fn);
+  if (!d_bits || !d_stats) return vo_fail(VO_ERR_INVALID_ARG, "%s: null argument", fn);
+  if (dev && !aligned8(d_stats)) return vo_fail(VO_ERR_INVALID_ARG, "%s: d_stats must be 8-byte aligned", fn);
+  return VO_OK;
+}
+
+int voe_map_covis_batch_dev(vo_map* m, int n_frames, const float* d_app, size_t app_stride, int n_max, const int* d_n, int n_words,
+                            uint32_t* d_bits_out, int32_t* d_counts_out, voe_map_covis_stats* d_stats) {
+  const char* fn = "voe_map_covis_batch_dev";
+  if (int r = covis_check(fn, n_frames, n_words, d_bits_out, d_stats, true)) return r;
+  VO_MAP_LIVE(m);
+  vo_ctx* c = m->ctx;
+  const MapFrames f{n_frames, nullptr, nullptr, 0, d_app, app_stride, n_max, d_n};
+  if (int r = map_lookup_check(f, true)) return r;            // the lookup's own refusals, before anything is sized
+  if ((long long)32 * n_words < (long long)map_bound(m))
+    return vo_fail(VO_ERR_INVALID_ARG, "%s: %d words hold fewer bits than the map's size bound %d", fn, n_words, map_bound(m));
+  MapCovisWs w = map_covis_layout(nullptr, n_frames, n_max, n_words);
+  if (int r = capture_growth_check(c->capturing, fn, {{m->covis_ws.cap, w.bytes}, {m->look_ws.cap, n_max > 0 ? lookup_scratch_bytes(f, false) : 0}},
+                                   "%d frames of n_max %d and %d words on this map", n_frames, n_max, n_words))      // (before the lookup is enqueued)
+    return r;
+  if (int r = set_device(c)) return r;
+  VO_HIP_CHECK(m->covis_ws.ensure(w.bytes, c->stream));
+  w = map_covis_layout(m->covis_ws.p, n_frames, n_max, n_words);
+  if (int r = lookup_window(m, f, w.pairs, w.n_hits, w.ent)) return r;      // the one lookup of the call
+  MapCovisArgs a{};
+  a.w = w; a.hdr = m->d.hdr; a.cap = m->d.cap;
+  a.n_frames = n_frames; a.n_max = n_max; a.n_words = n_words; a.d_n = d_n;
+  a.bits = d_bits_out; a.counts = d_counts_out; a.stats = d_stats;
+  VO_HIP_CHECK(launch_map_covis(c->stream, a));
+  return VO_OK;
+}
+
+int voe_map_covis(vo_map* m, int n_frames, const float* app, const int* n_rows, int n_max, int n_words, uint32_t* bits_out,
+                  int32_t* counts_out, voe_map_covis_stats* stats_out) {
+  const char* fn = "voe_map_covis";
+  if (int r = covis_check(fn, n_frames, n_words, bits_out, stats_out, false)) return r;
+  VO_MAP_LIVE(m);
+  vo_ctx* c = m->ctx;
+  VO_NOT_CAPTURING(c);
+  MapFrames f;
+  int size = 0;
+  if (int r = upload_window(fn, m, MapFrames{n_frames, nullptr, nullptr, 0, app, 0, n_max, n_rows}, nullptr, nullptr, &size, &f)) return r;
+  const size_t F = (size_t)n_frames, W = (size_t)n_words;
+  VO_HIP_CHECK(c->out[0].ensure(sizeof(uint32_t) * F * W, c->stream));
+  if (counts_out) VO_HIP_CHECK(c->out[1].ensure(sizeof(int32_t) * F * F, c->stream));
+  VO_HIP_CHECK(c->out[2].ensure(sizeof(voe_map_covis_stats) + 16, c->stream));
+  if (int r = voe_map_covis_batch_dev(m, n_frames, f.d_app, f.app_stride, n_max, f.d_n, n_words, c->out[0].as<uint32_t>(),
+                                      counts_out ? c->out[1].as<int32_t>() : nullptr, c->out[2].as<voe_map_covis_stats>()))
+    return r;
+  VO_HIP_CHECK(hipMemcpyAsync(bits_out, c->out[0].p, sizeof(uint32_t) * F * W, hipMemcpyDeviceToHost, c->stream));
+  if (counts_out) VO_HIP_CHECK(hipMemcpyAsync(counts_out, c->out[1].p, sizeof(int32_t) * F * F, hipMemcpyDeviceToHost, c->stream));
+  VO_HIP_CHECK(hipMemcpyAsync(stats_out, c->out[2].p, sizeof(voe_map_covis_stats), hipMemcpyDeviceToHost, c->stream));
+  VO_HIP_CHECK(hipStreamSynchronize(c->stream));
+  return VO_OK;
+}
+
+// (have_out: the role, row count and mask arrays are all given)
+static int window_check(const char* fn, int n_frames, int n_words, const void* d_bits, int n_max, const voe_map_window_params* p,
+                        bool have_out, const void* d_stats, bool dev) {
+  if (int r = covis_check(fn, n_frames, n_words, d_bits, d_stats, dev)) return r;
+  if (!(p && have_out)) return vo_fail(VO_ERR_INVALID_ARG, "%s: null argument", fn);
+  if (n_max < 0) return vo_fail(VO_ERR_INVALID_ARG, "%s: negative row count", fn);
+  if (p->query < 0 || p->query >= n_frames) return vo_fail(VO_ERR_INVALID_ARG, "%s: query %d outside the %d frames", fn, p->query, n_frames);
+  if (p->k_free < 1 || p->k_free > n_frames) return vo_fail(VO_ERR_INVALID_ARG, "%s: k_free outside 1 .. n_frames", fn);
+  if (p->k_fixed < 0 || p->k_fixed > n_frames) return vo_fail(VO_ERR_INVALID_ARG, "%s: k_fixed outside 0 .. n_frames", fn);
+  if (p->min_shared < 1) return vo_fail(VO_ERR_INVALID_ARG, "%s: min_shared must be at least 1", fn);
+  return VO_OK;
+}
+
+int voe_map_window_dev(vo_map* m, int n_frames, int n_words, const uint32_t* d_bits, const int* d_n, int n_max,
+                       const voe_map_window_params* p, int32_t* d_role_out, int* d_n_rows_out, uint8_t* d_fixed_out, int32_t* d_order_out,
+                       uint32_t* d_union_out, voe_map_window_stats* d_stats) {
+  const char* fn = "voe_map_window_dev";
+  if (int r = window_check(fn, n_frames, n_words, d_bits, n_max, p, d_role_out && d_n_rows_out && d_fixed_out, d_stats, true)) return r;
+  VO_MAP_LIVE(m);
+  vo_ctx* c = m->ctx;
+  MapWindowWs w = map_window_layout(nullptr, n_frames, n_words);
+  if (int r = capture_growth_check(c->capturing, fn, {{m->window_ws.cap, w.bytes}}, "%d frames and %d words on this map", n_frames, n_words)) return r;
+  if (int r = set_device(c)) return r;
+  VO_HIP_CHECK(m->window_ws.ensure(w.bytes, c->stream));
+  MapWindowArgs a{};
+  a.w = map_window_layout(m->window_ws.p, n_frames, n_words);
+  a.n_frames = n_frames; a.n_words = n_words; a.n_max = n_max; a.bits = d_bits; a.d_n = d_n;
+  a.query = p->query; a.k_free = p->k_free; a.k_fixed = p->k_fixed; a.min_shared = p->min_shared;
+  a.role = d_role_out; a.n_rows_out = d_n_rows_out; a.fixed_out = d_fixed_out;
+  a.order = d_order_out ? d_order_out : a.w.order;
+  a.uni = d_union_out ? d_union_out : a.w.uni;
+  a.stats = d_stats;
+  VO_HIP_CHECK(launch_map_window(c->stream, a));
+  return VO_OK;
+}
+
+int voe_map_window(vo_map* m, int n_frames, int n_words, const uint32_t* bits, const int* n_rows, int n_max,
+                   const voe_map_window_params* p, int32_t* role_out, int* n_rows_out, uint8_t* fixed_out, int32_t* order_out,
+                   uint32_t* union_out, voe_map_window_stats* stats_out) {
+  const char* fn = "voe_map_window";
+  if (int r = window_check(fn, n_frames, n_words, bits, n_max, p, role_out && n_rows_out && fixed_out, stats_out, false)) return r;
+  VO_MAP_LIVE(m);
+  vo_ctx* c = m->ctx;
+  VO_NOT_CAPTURING(c);
+  if (int r = set_device(c)) return r;
+  const size_t F = (size_t)n_frames, W = (size_t)n_words;
+  if (int r = upload(c, c->in[0], bits, sizeof(uint32_t) * F * W)) return r;
+  if (n_rows)
+    if (int r = upload(c, c->in[3], n_rows, sizeof(int) * F)) return r;
+  // one block of outputs: role, n_rows, order [F] ints each, the union [W], the statistics, the mask [F] bytes
+  const size_t o_role = 0, o_rows = up256(4 * F), o_order = o_rows + up256(4 * F), o_union = o_order + up256(4 * F), o_stats = o_union + up256(4 * W),
+               o_fixed = o_stats + 256, total = o_fixed + up256(F);
+  VO_HIP_CHECK(c->out[0].ensure(total, c->stream));
+  char* d = c->out[0].as<char>();
+  if (int r = voe_map_window_dev(m, n_frames, n_words, c->in[0].as<uint32_t>(), n_rows ? c->in[3].as<int>() : nullptr, n_max, p,
+                                 reinterpret_cast<int32_t*>(d + o_role), reinterpret_cast<int*>(d + o_rows), reinterpret_cast<uint8_t*>(d + o_fixed),
+                                 order_out ? reinterpret_cast<int32_t*>(d + o_order) : nullptr,
+                                 union_out ? reinterpret_cast<uint32_t*>(d + o_union) : nullptr, reinterpret_cast<voe_map_window_stats*>(d + o_stats)))
+    return r;
+  VO_HIP_CHECK(hipMemcpyAsync(role_out, d + o_role, 4 * F, hipMemcpyDeviceToHost, c->stream));
+  VO_HIP_CHECK(hipMemcpyAsync(n_rows_out, d + o_rows, 4 * F, hipMemcpyDeviceToHost, c->stream));
+  VO_HIP_CHECK(hipMemcpyAsync(fixed_out, d + o_fixed, F, hipMemcpyDeviceToHost, c->stream));
+  if (order_out) VO_HIP_CHECK(hipMemcpyAsync(order_out, d + o_order, 4 * F, hipMemcpyDeviceToHost, c->stream));
+  if (union_out) VO_HIP_CHECK(hipMemcpyAsync(union_out, d + o_union, 4 * W, hipMemcpyDeviceToHost, c->stream));
+  VO_HIP_CHECK(hipMemcpyAsync(stats_out, d + o_stats, sizeof(voe_map_window_stats), hipMemcpyDeviceToHost, c->stream));
+  VO_HIP_CHECK(hipStreamSynchronize(c->stream));
+  return VO_OK;
+}

@@ -13,7 +13,7 @@
 //   align_finish_kernel   one workgroup: rms, S and the statistics.
 // Every floating-point sum is a tree of fixed shape over LDS (tree_sum below), per block and then over the blocks: no float
 // atomics, the same bytes from every call.  The merge's own kernels (the misses of a lookup compacted in order: count / scan /
-// scatter) are at the end; lookup and update are map.hip's, through their public entry points (capi.hip).
+// scatter) are at the end; lookup and update are map.hip's, through their public entry points (capi_map.hip).
 #include "vo_internal.h"
 #include "ransac_common.h"
 #include "../../include/vo_hip.h"

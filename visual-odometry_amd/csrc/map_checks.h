@@ -1,0 +1,105 @@
+// map_checks.h -- refusals of the host path that make no HIP call and touch neither context nor map: plain C++, so that
+// tests/hostcheck/map_checks_check.cpp compiles them with the host sanitizers and nothing else of the library.
+#pragma once
+
+#include <stdarg.h>
+#include <stddef.h>
+#include <stdint.h>
+#include <stdio.h>
+
+#include <cmath>
+#include <initializer_list>
+
+#include "../../include/vo_hip.h"
+
+int vo_fail(int code, const char* fmt, ...);   // vo_internal.h
+
+// device arrays move as 8-byte pieces (vo_hip.h, Conventions): true when every pointer given is null or on such a boundary
+template <typename... P>
+static bool aligned8(const P*... p) { return ((... | reinterpret_cast<uintptr_t>(p)) & 7u) == 0; }
+
+// K^-1 in double of the float K (column-major in, column-major out): adjugate / determinant; false when K is singular
+static inline bool invert_k(const float K[9], double Kinv[9]) {
+  double k[9];
+  for (int i = 0; i < 9; ++i) k[i] = K[i];
+#define VO_K(r, c) k[(r) + 3 * (c)]
+  const double c00 = VO_K(1, 1) * VO_K(2, 2) - VO_K(1, 2) * VO_K(2, 1), c01 = VO_K(1, 2) * VO_K(2, 0) - VO_K(1, 0) * VO_K(2, 2),
+               c02 = VO_K(1, 0) * VO_K(2, 1) - VO_K(1, 1) * VO_K(2, 0);
+  const double det = VO_K(0, 0) * c00 + VO_K(0, 1) * c01 + VO_K(0, 2) * c02;
+  if (!(det != 0.0) || !std::isfinite(det)) return false;
+  // inverse = adjugate / det, column-major: Kinv(r, c) = cofactor(c, r) / det
+  Kinv[0 + 3 * 0] = c00 / det;
+  Kinv[1 + 3 * 0] = c01 / det;
+  Kinv[2 + 3 * 0] = c02 / det;
+  Kinv[0 + 3 * 1] = (VO_K(0, 2) * VO_K(2, 1) - VO_K(0, 1) * VO_K(2, 2)) / det;
+  Kinv[1 + 3 * 1] = (VO_K(0, 0) * VO_K(2, 2) - VO_K(0, 2) * VO_K(2, 0)) / det;
+  Kinv[2 + 3 * 1] = (VO_K(0, 1) * VO_K(2, 0) - VO_K(0, 0) * VO_K(2, 1)) / det;
+  Kinv[0 + 3 * 2] = (VO_K(0, 1) * VO_K(1, 2) - VO_K(0, 2) * VO_K(1, 1)) / det;
+  Kinv[1 + 3 * 2] = (VO_K(0, 2) * VO_K(1, 0) - VO_K(0, 0) * VO_K(1, 2)) / det;
+  Kinv[2 + 3 * 2] = (VO_K(0, 0) * VO_K(1, 1) - VO_K(0, 1) * VO_K(1, 0)) / det;
+#undef VO_K
+  return true;
+}
+
+// a window of frames as every *_batch_dev call of the map takes it (vo_hip.h, vo_map_refine_batch_dev): frame g's pixels
+// start at d_uv + 2 * g * uv_stride, its appearances at d_app + 10 * g * app_stride; d_n (or null) holds the live rows
+struct MapFrames {
+  int n_frames;
+  const float* K;             // [9] column-major; null where the call has no camera (the covisibility)
+  const float* d_uv; size_t uv_stride; const float* d_app; size_t app_stride;
+  int n_max; const int* d_n;
+};
+
+// what a call that iterates is asked to do, and the limits of that call
+struct MapRounds {
+  int n_rounds, most_rounds, min_obs, least_obs;
+  float huber_px; const float* damping;       // (null: the call has no damping)
+};
+
+static inline int map_rounds_check(const char* fn, const MapRounds& r) {
+  if (r.n_rounds < 0) return vo_fail(VO_ERR_INVALID_ARG, "%s: negative n_rounds", fn);
+  if (r.n_rounds > r.most_rounds) return vo_fail(VO_ERR_INVALID_ARG, "%s: more than %d rounds", fn, r.most_rounds);
+  if (r.min_obs < r.least_obs) return vo_fail(VO_ERR_INVALID_ARG, "%s: min_obs must be at least %d", fn, r.least_obs);
+  if (!(r.huber_px >= 0.f && r.huber_px <= 3.402823466e38f)) return vo_fail(VO_ERR_INVALID_ARG, "%s: huber_px must be finite and not negative", fn);
+  if (r.damping && !(*r.damping >= 0.f && *r.damping <= 3.402823466e38f)) return vo_fail(VO_ERR_INVALID_ARG, "%s: damping must be finite and not negative", fn);
+  return VO_OK;
+}
+
+// The refusals the window calls share (refinement, pose refinement, adjustment, bundle, culling), in the order they fire:
+//   1. n_frames outside 1 .. 65535      2. negative n_max          3. null pixels or appearances with n_max > 0
+//   4. d_uv, d_app or d_stats not on an 8-byte boundary            5. a stride below n_max     6. uv_stride >= 2^31 - 1
+//   7. the round parameters of the call (map_rounds_check), where it has any
+//   8. a singular K                     9. app_stride >= (2^31 - 1) / 10 or more than 2^30 rows (the lookup's own limit, met
+//                                          before anything is sized)
+// Where two would fail, the first is the one reported.
+static inline int map_frames_check(const char* fn, const MapFrames& f, const void* d_stats, const MapRounds* rounds = nullptr) {
+  if (f.n_frames < 1 || f.n_frames > 65535) return vo_fail(VO_ERR_INVALID_ARG, "%s: n_frames %d outside 1 .. 65535 (the frame is a grid dimension)", fn, f.n_frames);
+  if (f.n_max < 0) return vo_fail(VO_ERR_INVALID_ARG, "%s: negative row count", fn);
+  if (f.n_max > 0 && !(f.d_uv && f.d_app)) return vo_fail(VO_ERR_INVALID_ARG, "%s: null argument", fn);
+  if (!aligned8(f.d_uv, f.d_app, d_stats)) return vo_fail(VO_ERR_INVALID_ARG, "%s: device arrays must be 8-byte aligned", fn);
+  if (f.uv_stride < (size_t)f.n_max || f.app_stride < (size_t)f.n_max) return vo_fail(VO_ERR_INVALID_ARG, "%s: a stride is smaller than n_max", fn);
+  if (f.uv_stride >= 0x7fffffff) return vo_fail(VO_ERR_INVALID_ARG, "%s: stride too large", fn);
+  if (rounds)
+    if (int r = map_rounds_check(fn, *rounds)) return r;
+  double Kinv[9];
+  if (!invert_k(f.K, Kinv)) return vo_fail(VO_ERR_INVALID_ARG, "%s: K is singular", fn);
+  if (f.app_stride >= 0x7fffffff / 10 || (long long)f.n_max * f.n_frames > (1ll << 30))
+    return vo_fail(VO_ERR_INVALID_ARG, "%s: more than 2^30 rows in one call", fn);
+  return VO_OK;
+}
+
+// A workspace that would have to grow inside a graph capture: growing frees, allocates and waits.  `ws` lists the buffers the
+// call sizes, each with its capacity and what the call needs; `tail` (printf form) names the call that sizes them outside a
+// capture.  The callers ask BEFORE they enqueue anything: a HIP call refused later would invalidate the capture.
+struct WsNeed { size_t cap, need; };
+static inline int capture_growth_check(bool capturing, const char* fn, std::initializer_list<WsNeed> ws, const char* tail, ...) {
+  bool fits = true;
+  for (const WsNeed& w : ws) fits = fits && w.cap >= w.need;
+  if (!capturing || fits) return VO_OK;
+  char with[160];
+  va_list ap;
+  va_start(ap, tail);
+  vsnprintf(with, sizeof(with), tail, ap);
+  va_end(ap);
+  return vo_fail(VO_ERR_NOT_READY, "%s: the workspace would have to grow inside a graph capture (make one call with %s before capturing)", fn, with);
+}
