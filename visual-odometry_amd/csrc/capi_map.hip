@@ -475,13 +475,11 @@ static int window_growth_check(const vo_map* m, const char* fn, const MapFrames&
   return capture_growth_check(m->ctx->capturing, fn, ws, "%d frames of n_max %d on this map", f.n_frames, f.n_max);
 }
 
-// the map as a kernel sees it, and the frames, into an argument block that has these members
-template <class A>
-static void fill_map(A& a, const vo_map* m) { a.pts = m->d.pts; a.hdr = m->d.hdr; a.cap = m->d.cap; a.bound = map_bound(m); }
-template <class A>
-static void fill_frames(A& a, const MapFrames& f) {
-  a.uv = f.d_uv; a.uv_stride = f.uv_stride; a.n_max = f.n_max; a.n_frames = f.n_frames;
-  for (int k = 0; k < 9; ++k) a.K[k] = f.K[k];
+// the map and the frames as the adjustment kernels see them (MapView, vo_internal.h), with the poses that come in
+static void fill_map(MapView& v, const vo_map* m) { v.pts = m->d.pts; v.hdr = m->d.hdr; v.cap = m->d.cap; v.bound = map_bound(m); }
+static void fill_frames(MapView& v, const MapFrames& f, const float* d_T16) {
+  v.uv = f.d_uv; v.uv_stride = f.uv_stride; v.n_max = f.n_max; v.n_frames = f.n_frames; v.T16 = d_T16;
+  for (int k = 0; k < 9; ++k) v.K[k] = f.K[k];
 }
 
 // The begin step of a host-pointer window call, after the call's own null checks: the refusals of the frames `h` (host arrays,
@@ -532,9 +530,8 @@ static int refine_run(vo_map* m, const MapRefineWs& w, const MapFrames& f, const
   vo_ctx* c = m->ctx;
   MapRefineArgs a{};
   a.w = w;
-  fill_map(a, m);
-  fill_frames(a, f);
-  a.T16 = d_T16;
+  fill_map(a.v, m);
+  fill_frames(a.v, f, d_T16);
   a.n_rounds = r.n_rounds; a.min_obs = r.min_obs; a.huber = r.huber_px; a.damping = *r.damping;
   a.status = d_status_out ? d_status_out : w.status;
   a.xyz_out = d_xyz_out; a.stats = d_stats;
@@ -599,9 +596,9 @@ static int pose_run(vo_map* m, const MapPoseWs& w, const MapFrames& f, const flo
   vo_ctx* c = m->ctx;
   MapPoseArgs a{};
   a.ent = w.ent; a.n_obs = w.n_obs; a.cost = w.cost;
-  fill_map(a, m);
-  fill_frames(a, f);
-  a.T_in = d_T_in; a.T_out = d_T_out; a.fixed = d_fixed;
+  fill_map(a.v, m);
+  fill_frames(a.v, f, d_T_in);
+  a.T_out = d_T_out; a.fixed = d_fixed;
   a.n_rounds = r.n_rounds; a.min_obs = r.min_obs; a.huber = r.huber_px; a.damping = *r.damping;
   a.status = d_status_out ? d_status_out : w.status;
   a.H_out = d_H_out; a.stats = d_stats;
@@ -735,9 +732,9 @@ int vox_map_bundle_batch_dev(vo_map* m, int n_frames, const float K[9], const fl
   VO_HIP_CHECK(m->bundle_ws.ensure(bw.bytes, c->stream));
   MapBundleArgs a{};
   a.l = rw; a.w = map_bundle_layout(m->bundle_ws.p, n_frames, bound);
-  fill_map(a, m);
-  fill_frames(a, f);
-  a.T16 = d_T16; a.fixed = d_fixed;
+  fill_map(a.v, m);
+  fill_frames(a.v, f, d_T16);
+  a.T_out = d_T16; a.fixed = d_fixed;
   a.n_rounds = p->n_rounds; a.n_cg = p->n_cg; a.min_obs_pose = p->min_obs_pose; a.min_obs_point = p->min_obs_point;
   a.cg_tol = p->cg_tol; a.lambda0 = p->lambda0; a.huber = p->huber_px;
   a.pose_status_out = d_pose_status_out; a.point_status_out = d_point_status_out; a.rounds_out = d_rounds_out; a.stats = d_stats;
@@ -808,10 +805,9 @@ int voe_map_cull_batch_dev(vo_map* m, int n_frames, const float K[9], const floa
   VO_HIP_CHECK(m->cull_ws.ensure(cw.bytes, c->stream));
   MapCullArgs a{};
   a.l = rw; a.w = map_cull_layout(m->cull_ws.p, bound);
-  fill_map(a, m);
+  fill_map(a.v, m);
+  fill_frames(a.v, f, d_T16);
   a.app = m->d.app;
-  fill_frames(a, f);
-  a.T16 = d_T16;
   a.min_obs = p->min_obs; a.min_frames = p->min_frames; a.drop_unseen = p->drop_unseen != 0; a.dry_run = p->dry_run != 0;
   a.max_mean_sq = (double)p->max_rms_px * (double)p->max_rms_px;
   a.max_sq = (double)p->max_err_px * (double)p->max_err_px;

@@ -117,29 +117,10 @@ __global__ __launch_bounds__(MB) void map_flag_kernel(MapArgs a) {
 __global__ __launch_bounds__(1024) void map_scan_kernel(MapArgs a) {
   __shared__ int s_w[16];
   __shared__ int s_carry;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  if (tid == 0) s_carry = 0;
-  __syncthreads();
-  for (int base = 0; base < a.nb; base += 1024) {
-    const int j = base + tid;
-    const int v = j < a.nb ? a.counts[j] : 0;
-    int incl = v;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) { const int o = __shfl_up(incl, d); if (lane >= d) incl += o; }
-    if (lane == 63) s_w[wave] = incl;
-    __syncthreads();
-    int woff = 0, tot = 0;
-#pragma unroll
-    for (int w = 0; w < 16; ++w) { const int c = s_w[w]; if (w < wave) woff += c; tot += c; }
-    const int carry = s_carry;
-    if (j < a.nb) a.counts[j] = carry + woff + incl - v;
-    __syncthreads();
-    if (tid == 0) s_carry = carry + tot;
-    __syncthreads();
-  }
-  if (tid == 0) {
+  const int sum = scan_with_carry<1024>(a.counts, a.nb, s_w, &s_carry);
+  if (threadIdx.x == 0) {
     const int M = a.hdr[0];
-    int add = s_carry;
+    int add = sum;
     int dropped = 0;
     if (M + add > a.cap) { dropped = M + add - a.cap; add = a.cap - M; }      // (the host grows the arrays before this can happen)
     a.hdr[1] = M;

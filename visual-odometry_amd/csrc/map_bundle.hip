@@ -13,8 +13,10 @@
 //   bundle_cost_kernel<CAND>    one workgroup per frame: the candidate pose, its cost and z flag
 //   bundle_decide_kernel        one workgroup: the accept rule, lambda, the round's record, the copy
 // A PCG that has stopped leaves `stop` set in the control block; its remaining launches read it and return at once.
-// The frame-side reduction is map_pose_refine.hip's: DPP inside every row of 16 lanes, the 16 row sums through LDS, one thread
-// per term adds them in row order.  A single frame runs on one compute unit.
+// The frame-side reduction is map_pose_refine.hip's (frame_reduce, vo_internal.h): DPP inside every row of 16 lanes, the 16 row
+// sums through LDS, one thread per term adds them in row order.  A single frame runs on one compute unit.  An observation is
+// vo_math.h's map_obs with the Jacobian tail a kernel needs (map_obs_pose_jac: Jc, 2 x 6; map_obs_point_jac: Jp, 2 x 3) and the
+// normal-equation sums of accum_normal<3> / accum_normal<6> -- the one model of the four adjustment files.
 #include "vo_internal.h"
 #include "../../include/vo_map_bundle.h"
 
@@ -23,6 +25,7 @@ namespace vo {
 constexpr int BB = 256;                   // threads per workgroup
 constexpr int BROWS = BB / 16;            // DPP rows per workgroup
 constexpr int BG = 16;                    // lanes per landmark
+static_assert(BB == MAP_WG && BG == MAP_ROW, "the shared helpers of vo_internal.h count on both sizes");
 constexpr int BLPB = BB / BG;             // landmarks per workgroup and trip
 constexpr int BDEC = 1024;                // threads of the deciding workgroups (the first 256 take part in the sums)
 constexpr int BTERMS = 27;                // most sums a frame reduces at once
@@ -34,44 +37,7 @@ enum { B_START = 0, B_CAND = 1, B_FINAL = 2 };
 static_assert(sizeof(vox_map_bundle_params) == 28 && sizeof(vox_map_bundle_round) == 40 && sizeof(vox_map_bundle_stats) == 48,
               "the deciding kernels write these records field by field");
 
-__device__ __forceinline__ int bundle_size(const MapBundleArgs& a) {
-  int M = a.hdr[0];
-  M = M < a.cap ? M : a.cap;
-  return M < a.bound ? M : a.bound;
-}
-__device__ __forceinline__ int bundle_offset(const MapBundleArgs& a, int e) { return a.l.cnt[e] + a.l.blk[e / 256]; }
 __device__ __forceinline__ bool bundle_free_point(const MapBundleArgs& a, int e, int M) { return e >= 0 && e < M && a.l.cur[e] >= a.min_obs_point; }
-
-// One observation at the pose T (R column-major, then t) and the point p, all in double, with the operations of map_pose_term
-// and map_refine_term (vo_math.h): the residual e, the weight w and rho, Jc = j [I, -[p_cam]x] (2 x 6), Jp = j R (2 x 3).
-struct BundleObs { double w, e0, e1, rho, C0[6], C1[6], P0[3], P1[3]; bool front; };
-__device__ __forceinline__ void bundle_obs(const double K[9], const double T[12], const double p[3], double mu, double mv, double huber,
-                                           BundleObs& o) {
-  double pc[3], q[3];
-#pragma unroll
-  for (int r = 0; r < 3; ++r) pc[r] = __builtin_fma(T[r + 6], p[2], __builtin_fma(T[r + 3], p[1], __builtin_fma(T[r], p[0], T[9 + r])));
-#pragma unroll
-  for (int r = 0; r < 3; ++r) q[r] = __builtin_fma(K[r + 6], pc[2], __builtin_fma(K[r + 3], pc[1], K[r] * pc[0]));
-  const double iz = 1.0 / q[2];
-  const double u = q[0] * iz, v = q[1] * iz;
-  o.e0 = u - mu; o.e1 = v - mv;
-#pragma unroll
-  for (int c = 0; c < 3; ++c) { o.C0[c] = (K[3 * c] - u * K[2 + 3 * c]) * iz; o.C1[c] = (K[1 + 3 * c] - v * K[2 + 3 * c]) * iz; }
-  o.C0[3] = o.C0[2] * pc[1] - o.C0[1] * pc[2]; o.C0[4] = o.C0[0] * pc[2] - o.C0[2] * pc[0]; o.C0[5] = o.C0[1] * pc[0] - o.C0[0] * pc[1];
-  o.C1[3] = o.C1[2] * pc[1] - o.C1[1] * pc[2]; o.C1[4] = o.C1[0] * pc[2] - o.C1[2] * pc[0]; o.C1[5] = o.C1[1] * pc[0] - o.C1[0] * pc[1];
-#pragma unroll
-  for (int c = 0; c < 3; ++c) {
-    o.P0[c] = __builtin_fma(o.C0[2], T[2 + 3 * c], __builtin_fma(o.C0[1], T[1 + 3 * c], o.C0[0] * T[3 * c]));
-    o.P1[c] = __builtin_fma(o.C1[2], T[2 + 3 * c], __builtin_fma(o.C1[1], T[1 + 3 * c], o.C1[0] * T[3 * c]));
-  }
-  const double r2 = o.e0 * o.e0 + o.e1 * o.e1;
-  o.w = 1.0; o.rho = r2;
-  if (huber > 0.0) {
-    const double r = sqrt(r2);
-    if (r > huber) { o.w = huber / r; o.rho = huber * (2.0 * r - huber); }
-  }
-  o.front = pc[2] > 0.0;
-}
 
 template <int N>
 __device__ __forceinline__ void bundle_load(const double* src, double (&dst)[N]) {
@@ -101,44 +67,20 @@ __device__ __forceinline__ double bundle_tree_sum(double mine, double* s /* [256
   return s[0];
 }
 
-// the sums of N terms over a frame's workgroup: DPP inside every row of 16 lanes, the 16 row sums through LDS, thread k < N adds
-// term k in row order; afterwards every thread holds the same bits
-template <int N>
-__device__ __forceinline__ void bundle_frame_reduce(double (&acc)[N], double (*s_row)[BTERMS], double* s_tot) {
-  const int tid = threadIdx.x;
-#pragma unroll
-  for (int k = 0; k < N; ++k) acc[k] = refine_row_sum(acc[k]);
-  __syncthreads();                                            // (s_row and s_tot may still be read from the reduction before)
-  if ((tid & 15) == 0) {
-#pragma unroll
-    for (int k = 0; k < N; ++k) s_row[tid >> 4][k] = acc[k];
-  }
-  __syncthreads();
-  if (tid < N) {
-    double s = s_row[0][tid];
-#pragma unroll
-    for (int w = 1; w < BROWS; ++w) s += s_row[w][tid];
-    s_tot[tid] = s;
-  }
-  __syncthreads();
-#pragma unroll
-  for (int k = 0; k < N; ++k) acc[k] = s_tot[k];
-}
-
 // ---- the start: statuses, the state in double, the census ------------------------------------------------------------
 __global__ __launch_bounds__(BB) void bundle_init_frames_kernel(MapBundleArgs a) {
   __shared__ int s_n;
   const int f = blockIdx.x, tid = threadIdx.x;
-  const int M = bundle_size(a);
-  const int32_t* ent = a.l.ent + (size_t)f * a.n_max;
+  const int M = a.v.size();
+  const int32_t* ent = a.l.ent + (size_t)f * a.v.n_max;
   if (tid == 0) s_n = 0;
   __syncthreads();
   int mine = 0;
-  for (int i = tid; i < a.n_max; i += BB) { const int e = ent[i]; mine += e >= 0 && e < M; }
+  for (int i = tid; i < a.v.n_max; i += BB) { const int e = ent[i]; mine += e >= 0 && e < M; }
   if (mine) atomicAdd(&s_n, mine);                           // (an integer count does not depend on the order)
   __syncthreads();
   if (tid < 12) {
-    const double v = (double)a.T16[16 * (size_t)f + (tid % 3) + 4 * (tid / 3)];
+    const double v = (double)a.v.pose_at(f, tid);
     a.w.T[12 * (size_t)f + tid] = v;
     a.w.Tc[12 * (size_t)f + tid] = v;
   }
@@ -151,14 +93,14 @@ __global__ __launch_bounds__(BB) void bundle_init_frames_kernel(MapBundleArgs a)
 }
 
 __global__ __launch_bounds__(BB) void bundle_init_points_kernel(MapBundleArgs a) {
-  const int M = bundle_size(a);
+  const int M = a.v.size();
   const int e = blockIdx.x * BB + threadIdx.x;
   if (e >= M) return;
   const int n = a.l.cur[e];
   a.w.point_status[e] = n == 0 ? BS_UNSEEN : n < a.min_obs_point ? BS_FEW_OBS : BS_OK;
 #pragma unroll
   for (int k = 0; k < 3; ++k) {
-    const double v = (double)a.pts[3 * (size_t)e + k];
+    const double v = (double)a.v.pts[3 * (size_t)e + k];
     a.w.P[3 * (size_t)e + k] = v;
     a.w.Pc[3 * (size_t)e + k] = v;
   }
@@ -166,11 +108,11 @@ __global__ __launch_bounds__(BB) void bundle_init_points_kernel(MapBundleArgs a)
 
 __global__ __launch_bounds__(BB) void bundle_census_kernel(MapBundleArgs a) {
   __shared__ int s_n[3];
-  const int M = bundle_size(a);
+  const int M = a.v.size();
   if (threadIdx.x < 3) s_n[threadIdx.x] = 0;
   __syncthreads();
   int ff = 0, fp = 0, no = 0;
-  for (int f = threadIdx.x; f < a.n_frames; f += BB) { ff += a.w.pose_status[f] == BS_OK; no += a.w.n_obs[f]; }
+  for (int f = threadIdx.x; f < a.v.n_frames; f += BB) { ff += a.w.pose_status[f] == BS_OK; no += a.w.n_obs[f]; }
   for (int e = threadIdx.x; e < M; e += BB) fp += a.w.point_status[e] == BS_OK;
   if (ff) atomicAdd(&s_n[0], ff);
   if (fp) atomicAdd(&s_n[1], fp);
@@ -194,11 +136,11 @@ __global__ __launch_bounds__(BB) void bundle_cost_kernel(MapBundleArgs a) {
   if (MODE != B_START && c.dead) return;
   if (MODE == B_CAND && (c.bad || c.nostep)) return;
   const int f = blockIdx.x, tid = threadIdx.x;
-  const int M = bundle_size(a);
+  const int M = a.v.size();
   double T[12], K[9];
   bundle_load((MODE == B_FINAL ? a.w.Tc : a.w.T) + 12 * (size_t)f, T);
 #pragma unroll
-  for (int k = 0; k < 9; ++k) K[k] = a.K[k];
+  for (int k = 0; k < 9; ++k) K[k] = a.v.K[k];
   if (MODE == B_CAND) {
     if (a.w.pose_status[f] == BS_OK) {
       double x[6];
@@ -209,21 +151,21 @@ __global__ __launch_bounds__(BB) void bundle_cost_kernel(MapBundleArgs a) {
     for (int k = 0; k < 12; ++k) if (tid == k) a.w.Tc[12 * (size_t)f + k] = T[k];
   }
   const double* P = MODE == B_START ? a.w.P : a.w.Pc;
-  const int32_t* ent = a.l.ent + (size_t)f * a.n_max;
-  const float2* uv = reinterpret_cast<const float2*>(a.uv) + (size_t)f * a.uv_stride;
+  const int32_t* ent = a.l.ent + (size_t)f * a.v.n_max;
+  const float2* uv = reinterpret_cast<const float2*>(a.v.uv) + (size_t)f * a.v.uv_stride;
   double acc[2] = {0.0, 0.0};                                // the cost; the count of rows whose camera z is not > 0
-  for (int i = tid; i < a.n_max; i += BB) {
+  for (int i = tid; i < a.v.n_max; i += BB) {
     const int e = ent[i];
     if (e < 0 || e >= M) continue;
     double p[3];
     bundle_load(P + 3 * (size_t)e, p);
     const float2 m = uv[i];
-    BundleObs o;
-    bundle_obs(K, T, p, (double)m.x, (double)m.y, a.huber, o);
+    MapObs o;
+    map_obs(K, T, p, (double)m.x, (double)m.y, a.huber, o);
     acc[0] += o.rho;
-    acc[1] += o.front ? 0.0 : 1.0;
+    acc[1] += o.front() ? 0.0 : 1.0;
   }
-  bundle_frame_reduce<2>(acc, s_row, s_tot);
+  frame_reduce(acc, s_row, s_tot);
   if (tid == 0) { a.w.fcost[f] = acc[0]; a.w.fflag[f] = acc[1] != 0.0; }
 }
 
@@ -235,7 +177,7 @@ __global__ __launch_bounds__(BB) void bundle_start_kernel(MapBundleArgs a) {
   __syncthreads();
   double mine = 0.0;
   int fl = 0;
-  for (int f = threadIdx.x; f < a.n_frames; f += BB) { mine += a.w.fcost[f]; fl |= a.w.fflag[f]; }
+  for (int f = threadIdx.x; f < a.v.n_frames; f += BB) { mine += a.w.fcost[f]; fl |= a.w.fflag[f]; }
   if (fl) atomicOr(&s_flag, 1);
   const double total = bundle_tree_sum(mine, s_sum);
   if (threadIdx.x == 0) {
@@ -259,19 +201,19 @@ __global__ __launch_bounds__(BB) void bundle_point_kernel(MapBundleArgs a) {
   if (c.dead) return;
   if (MODE == B_PASS_A && (c.bad || c.stop)) return;
   if (MODE == B_BACK && (c.bad || c.nostep)) return;
-  const int M = bundle_size(a);
+  const int M = a.v.size();
   const int lg = threadIdx.x & (BG - 1), grp = threadIdx.x / BG;
   const double lambda = c.lambda;
   const double* vec = MODE == B_PASS_A ? a.w.p : a.w.x;
   double K[9];
 #pragma unroll
-  for (int k = 0; k < 9; ++k) K[k] = a.K[k];
-  const int n_batches = (a.bound + BLPB - 1) / BLPB;
+  for (int k = 0; k < 9; ++k) K[k] = a.v.K[k];
+  const int n_batches = (a.v.bound + BLPB - 1) / BLPB;
   for (int batch = blockIdx.x; batch < n_batches; batch += gridDim.x) {      // (uniform in the workgroup: the DPP sums see whole rows)
     const int e = batch * BLPB + grp;
     const bool run = bundle_free_point(a, e, M);
     const int n = run ? a.l.cur[e] : 0;
-    const int off = run ? bundle_offset(a, e) : 0;
+    const int off = run ? a.l.offset(e) : 0;
     double p[3] = {0.0, 0.0, 0.0};
     if (run) bundle_load(a.w.P + 3 * (size_t)e, p);
     constexpr int NT = MODE == B_LIN ? 9 : 3;
@@ -279,34 +221,26 @@ __global__ __launch_bounds__(BB) void bundle_point_kernel(MapBundleArgs a) {
 #pragma unroll
     for (int k = 0; k < NT; ++k) acc[k] = 0.0;
     for (int j = lg; j < n; j += BG) {
-      const int key = a.l.keys[off + j];
-      const int f = key / a.n_max, i = key - f * a.n_max;
+      float2 m;
+      const int f = a.v.decode(a.l.keys[off + j], m);
       if (MODE != B_LIN && a.w.pose_status[f] != BS_OK) continue;
-      const float2 m = reinterpret_cast<const float2*>(a.uv)[(size_t)f * a.uv_stride + i];
-      double T[12];
+      double T[12], P0[3], P1[3];
       bundle_load(a.w.T + 12 * (size_t)f, T);
-      BundleObs o;
-      bundle_obs(K, T, p, (double)m.x, (double)m.y, a.huber, o);
+      MapObs o;
+      map_obs(K, T, p, (double)m.x, (double)m.y, a.huber, o);
+      map_obs_point_jac(o, T, P0, P1);
       if constexpr (MODE == B_LIN) {
-        const double w0[3] = {o.w * o.P0[0], o.w * o.P0[1], o.w * o.P0[2]}, w1[3] = {o.w * o.P1[0], o.w * o.P1[1], o.w * o.P1[2]};
-        acc[0] += __builtin_fma(w1[0], o.P1[0], w0[0] * o.P0[0]);
-        acc[1] += __builtin_fma(w1[0], o.P1[1], w0[0] * o.P0[1]);
-        acc[2] += __builtin_fma(w1[0], o.P1[2], w0[0] * o.P0[2]);
-        acc[3] += __builtin_fma(w1[1], o.P1[1], w0[1] * o.P0[1]);
-        acc[4] += __builtin_fma(w1[1], o.P1[2], w0[1] * o.P0[2]);
-        acc[5] += __builtin_fma(w1[2], o.P1[2], w0[2] * o.P0[2]);
-        acc[6] += __builtin_fma(w1[0], o.e1, w0[0] * o.e0);
-        acc[7] += __builtin_fma(w1[1], o.e1, w0[1] * o.e0);
-        acc[8] += __builtin_fma(w1[2], o.e1, w0[2] * o.e0);
+        accum_normal<3, false>(o, P0, P1, acc);
       } else {
-        double v[6];
+        double v[6], C0[6], C1[6];
         bundle_load(vec + 6 * (size_t)f, v);
+        map_obs_pose_jac(o, C0, C1);
         double s0 = 0.0, s1 = 0.0;
 #pragma unroll
-      for (int k = 0; k < 6; ++k) { s0 += o.C0[k] * v[k]; s1 += o.C1[k] * v[k]; }
+        for (int k = 0; k < 6; ++k) { s0 += C0[k] * v[k]; s1 += C1[k] * v[k]; }
         s0 *= o.w; s1 *= o.w;
 #pragma unroll
-        for (int k = 0; k < 3; ++k) acc[k] += __builtin_fma(o.P1[k], s1, o.P0[k] * s0);
+        for (int k = 0; k < 3; ++k) acc[k] += __builtin_fma(P1[k], s1, P0[k] * s0);
       }
     }
 #pragma unroll
@@ -356,35 +290,30 @@ __global__ __launch_bounds__(BB) void bundle_frame_lin_kernel(MapBundleArgs a) {
   const MapBundleCtl& c = *a.w.ctl;
   const int f = blockIdx.x, tid = threadIdx.x;
   if (c.dead || a.w.pose_status[f] != BS_OK) return;
-  const int M = bundle_size(a);
+  const int M = a.v.size();
   const double lambda = c.lambda;
   double T[12], K[9];
   bundle_load(a.w.T + 12 * (size_t)f, T);
 #pragma unroll
-  for (int k = 0; k < 9; ++k) K[k] = a.K[k];
-  const int32_t* ent = a.l.ent + (size_t)f * a.n_max;
-  const float2* uv = reinterpret_cast<const float2*>(a.uv) + (size_t)f * a.uv_stride;
+  for (int k = 0; k < 9; ++k) K[k] = a.v.K[k];
+  const int32_t* ent = a.l.ent + (size_t)f * a.v.n_max;
+  const float2* uv = reinterpret_cast<const float2*>(a.v.uv) + (size_t)f * a.v.uv_stride;
   double acc[27];
 #pragma unroll
   for (int k = 0; k < 27; ++k) acc[k] = 0.0;
-  for (int i = tid; i < a.n_max; i += BB) {
+  for (int i = tid; i < a.v.n_max; i += BB) {
     const int e = ent[i];
     if (e < 0 || e >= M) continue;
     double p[3];
     bundle_load(a.w.P + 3 * (size_t)e, p);
     const float2 m = uv[i];
-    BundleObs o;
-    bundle_obs(K, T, p, (double)m.x, (double)m.y, a.huber, o);
-    int k = 0;
-#pragma unroll
-    for (int r = 0; r < 6; ++r) {
-      const double w0 = o.w * o.C0[r], w1 = o.w * o.C1[r];
-#pragma unroll
-      for (int b = r; b < 6; ++b) acc[k++] += __builtin_fma(w1, o.C1[b], w0 * o.C0[b]);
-      acc[21 + r] += __builtin_fma(w1, o.e1, w0 * o.e0);
-    }
+    MapObs o;
+    double C0[6], C1[6];
+    map_obs(K, T, p, (double)m.x, (double)m.y, a.huber, o);
+    map_obs_pose_jac(o, C0, C1);
+    accum_normal<6, false>(o, C0, C1, acc);
   }
-  bundle_frame_reduce<27>(acc, s_row, s_tot);
+  frame_reduce(acc, s_row, s_tot);
   double keep = 0.0;                                          // thread k < 27 keeps term k: the damped U (k < 21) or g (k >= 21)
   {
     const int diag[6] = {0, 6, 11, 15, 18, 20};
@@ -395,7 +324,7 @@ __global__ __launch_bounds__(BB) void bundle_frame_lin_kernel(MapBundleArgs a) {
   }
 #pragma unroll
   for (int k = 0; k < 27; ++k) acc[k] = 0.0;
-  for (int i = tid; i < a.n_max; i += BB) {
+  for (int i = tid; i < a.v.n_max; i += BB) {
     const int e = ent[i];
     if (!bundle_free_point(a, e, M)) continue;
     double p[3], Vi[6], g[3];
@@ -403,14 +332,17 @@ __global__ __launch_bounds__(BB) void bundle_frame_lin_kernel(MapBundleArgs a) {
     bundle_load(a.w.Vinv + 6 * (size_t)e, Vi);
     bundle_load(a.w.gj + 3 * (size_t)e, g);
     const float2 m = uv[i];
-    BundleObs o;
-    bundle_obs(K, T, p, (double)m.x, (double)m.y, a.huber, o);
+    MapObs o;
+    double C0[6], C1[6], P0[3], P1[3];
+    map_obs(K, T, p, (double)m.x, (double)m.y, a.huber, o);
+    map_obs_pose_jac(o, C0, C1);
+    map_obs_point_jac(o, T, P0, P1);
     double W[6][3], Y[6][3];
 #pragma unroll
     for (int r = 0; r < 6; ++r) {
-      const double w0 = o.w * o.C0[r], w1 = o.w * o.C1[r];
+      const double w0 = o.w * C0[r], w1 = o.w * C1[r];
 #pragma unroll
-      for (int k = 0; k < 3; ++k) W[r][k] = __builtin_fma(w1, o.P1[k], w0 * o.P0[k]);
+      for (int k = 0; k < 3; ++k) W[r][k] = __builtin_fma(w1, P1[k], w0 * P0[k]);
       sym3_mul(Vi, W[r], Y[r]);
     }
     int k = 0;
@@ -421,7 +353,7 @@ __global__ __launch_bounds__(BB) void bundle_frame_lin_kernel(MapBundleArgs a) {
       acc[21 + r] += Y[r][0] * g[0] + Y[r][1] * g[1] + Y[r][2] * g[2];
     }
   }
-  bundle_frame_reduce<27>(acc, s_row, s_tot);
+  frame_reduce(acc, s_row, s_tot);
 #pragma unroll
   for (int k = 0; k < 27; ++k) {
     if (tid == k) {
@@ -437,29 +369,32 @@ __global__ __launch_bounds__(BB) void bundle_frame_sp_kernel(MapBundleArgs a) {
   const MapBundleCtl& c = *a.w.ctl;
   const int f = blockIdx.x, tid = threadIdx.x;
   if (c.dead || c.bad || c.stop || a.w.pose_status[f] != BS_OK) return;
-  const int M = bundle_size(a);
+  const int M = a.v.size();
   double T[12], K[9];
   bundle_load(a.w.T + 12 * (size_t)f, T);
 #pragma unroll
-  for (int k = 0; k < 9; ++k) K[k] = a.K[k];
-  const int32_t* ent = a.l.ent + (size_t)f * a.n_max;
-  const float2* uv = reinterpret_cast<const float2*>(a.uv) + (size_t)f * a.uv_stride;
+  for (int k = 0; k < 9; ++k) K[k] = a.v.K[k];
+  const int32_t* ent = a.l.ent + (size_t)f * a.v.n_max;
+  const float2* uv = reinterpret_cast<const float2*>(a.v.uv) + (size_t)f * a.v.uv_stride;
   double acc[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-  for (int i = tid; i < a.n_max; i += BB) {
+  for (int i = tid; i < a.v.n_max; i += BB) {
     const int e = ent[i];
     if (!bundle_free_point(a, e, M)) continue;
     double p[3], t[3];
     bundle_load(a.w.P + 3 * (size_t)e, p);
     bundle_load(a.w.tj + 3 * (size_t)e, t);
     const float2 m = uv[i];
-    BundleObs o;
-    bundle_obs(K, T, p, (double)m.x, (double)m.y, a.huber, o);
-    const double s0 = o.w * (o.P0[0] * t[0] + o.P0[1] * t[1] + o.P0[2] * t[2]);
-    const double s1 = o.w * (o.P1[0] * t[0] + o.P1[1] * t[1] + o.P1[2] * t[2]);
+    MapObs o;
+    double C0[6], C1[6], P0[3], P1[3];
+    map_obs(K, T, p, (double)m.x, (double)m.y, a.huber, o);
+    map_obs_pose_jac(o, C0, C1);
+    map_obs_point_jac(o, T, P0, P1);
+    const double s0 = o.w * (P0[0] * t[0] + P0[1] * t[1] + P0[2] * t[2]);
+    const double s1 = o.w * (P1[0] * t[0] + P1[1] * t[1] + P1[2] * t[2]);
 #pragma unroll
-    for (int k = 0; k < 6; ++k) acc[k] += __builtin_fma(o.C1[k], s1, o.C0[k] * s0);
+    for (int k = 0; k < 6; ++k) acc[k] += __builtin_fma(C1[k], s1, C0[k] * s0);
   }
-  bundle_frame_reduce<6>(acc, s_row, s_tot);
+  frame_reduce(acc, s_row, s_tot);
   if (tid == 0) {
     double U[21], pv[6], pq = 0.0;
     bundle_load(a.w.U + 21 * (size_t)f, U);
@@ -488,7 +423,7 @@ __global__ __launch_bounds__(BB) void bundle_cg_init_kernel(MapBundleArgs a) {
   __syncthreads();
   double rz = 0.0, rr = 0.0;
   if (!bad_before) {
-    for (int f = threadIdx.x; f < a.n_frames; f += BB) {
+    for (int f = threadIdx.x; f < a.v.n_frames; f += BB) {
       double* x = a.w.x + 6 * (size_t)f;
       for (int k = 0; k < 6; ++k) x[k] = 0.0;
       if (a.w.pose_status[f] != BS_OK) continue;
@@ -517,7 +452,7 @@ __global__ __launch_bounds__(BB) void bundle_cg_update_kernel(MapBundleArgs a) {
   const double rz_old = c.rz, rr0 = c.rr0;
   const int iters = c.iters;
   double mine = 0.0;
-  for (int f = threadIdx.x; f < a.n_frames; f += BB)
+  for (int f = threadIdx.x; f < a.v.n_frames; f += BB)
     if (a.w.pose_status[f] == BS_OK) mine += a.w.pq[f];
   const double pSp = bundle_tree_sum(mine, s_sum);
   if (!(pSp > 0.0) || !refine_finite(pSp)) {                   // (uniform: every thread holds the same total)
@@ -526,7 +461,7 @@ __global__ __launch_bounds__(BB) void bundle_cg_update_kernel(MapBundleArgs a) {
   }
   const double alpha = rz_old / pSp;
   double rz = 0.0, rr = 0.0;
-  for (int f = threadIdx.x; f < a.n_frames; f += BB) {
+  for (int f = threadIdx.x; f < a.v.n_frames; f += BB) {
     if (a.w.pose_status[f] != BS_OK) continue;
     double D[21], r[6], z[6];
     bundle_load(a.w.D + 21 * (size_t)f, D);
@@ -545,7 +480,7 @@ __global__ __launch_bounds__(BB) void bundle_cg_update_kernel(MapBundleArgs a) {
   const double t_rz = bundle_tree_sum(rz, s_sum);
   const double t_rr = bundle_tree_sum(rr, s_sum);
   const double beta = t_rz / rz_old;
-  for (int f = threadIdx.x; f < a.n_frames; f += BB) {
+  for (int f = threadIdx.x; f < a.v.n_frames; f += BB) {
     if (a.w.pose_status[f] != BS_OK) continue;
     for (int k = 0; k < 6; ++k) a.w.p[6 * (size_t)f + k] = a.w.z[6 * (size_t)f + k] + beta * a.w.p[6 * (size_t)f + k];
   }
@@ -565,7 +500,7 @@ __global__ __launch_bounds__(BDEC) void bundle_decide_kernel(MapBundleArgs a, in
     if (threadIdx.x == 0 && rec) { rec->cost = 0.0; rec->cost_candidate = 0.0; rec->lambda = 0.0; rec->residual = 0.0; rec->cg_iterations = 0; rec->accepted = 0; }
     return;
   }
-  const int M = bundle_size(a);
+  const int M = a.v.size();
   const bool formed = !c.bad && !c.nostep;
   const double cur = c.cost_cur, lambda = c.lambda, rr0 = c.rr0, rr = c.rr;
   const int iters = c.iters, n_free = c.n_free_frames;
@@ -574,12 +509,12 @@ __global__ __launch_bounds__(BDEC) void bundle_decide_kernel(MapBundleArgs a, in
   double mine = 0.0;
   int fl = 0;
   if (formed && threadIdx.x < 256)
-    for (int f = threadIdx.x; f < a.n_frames; f += 256) { mine += a.w.fcost[f]; fl |= a.w.fflag[f]; }
+    for (int f = threadIdx.x; f < a.v.n_frames; f += 256) { mine += a.w.fcost[f]; fl |= a.w.fflag[f]; }
   if (fl) atomicOr(&s_flag, 1);
   const double cand = bundle_tree_sum(mine, s_sum);            // (its barriers publish s_flag too)
   const bool accept = formed && refine_finite(cand) && !s_flag && cand <= cur;
   if (accept) {
-    for (size_t k = threadIdx.x; k < 12 * (size_t)a.n_frames; k += BDEC)
+    for (size_t k = threadIdx.x; k < 12 * (size_t)a.v.n_frames; k += BDEC)
       if (a.w.pose_status[k / 12] == BS_OK) a.w.T[k] = a.w.Tc[k];
     for (size_t k = threadIdx.x; k < 3 * (size_t)M; k += BDEC) a.w.P[k] = a.w.Pc[k];
   }
@@ -603,19 +538,19 @@ __global__ __launch_bounds__(BDEC) void bundle_decide_kernel(MapBundleArgs a, in
 // ---- the end: the state rounded to float32 into the candidate arrays, its cost (bundle_cost_kernel<FINAL>), the verdict ---------
 __global__ __launch_bounds__(BB) void bundle_round_kernel(MapBundleArgs a) {
   if (a.w.ctl->dead) return;
-  const int M = bundle_size(a);
+  const int M = a.v.size();
   const size_t k = (size_t)blockIdx.x * BB + threadIdx.x;
-  if (k < 12 * (size_t)a.n_frames) a.w.Tc[k] = (double)(float)a.w.T[k];
+  if (k < 12 * (size_t)a.v.n_frames) a.w.Tc[k] = (double)(float)a.w.T[k];
   if (k < 3 * (size_t)M) a.w.Pc[k] = (double)(float)a.w.P[k];
 }
 
 __global__ __launch_bounds__(BDEC) void bundle_finish_kernel(MapBundleArgs a) {
   __shared__ double s_sum[256];
   const MapBundleCtl& c = *a.w.ctl;
-  const int M = bundle_size(a);
+  const int M = a.v.size();
   double mine = 0.0;
   if (!c.dead && threadIdx.x < 256)
-    for (int f = threadIdx.x; f < a.n_frames; f += 256) mine += a.w.fcost[f];
+    for (int f = threadIdx.x; f < a.v.n_frames; f += 256) mine += a.w.fcost[f];
   const double total = bundle_tree_sum(mine, s_sum);
   int status = c.status;
   if (!c.dead) {
@@ -623,12 +558,12 @@ __global__ __launch_bounds__(BDEC) void bundle_finish_kernel(MapBundleArgs a) {
     else if (!(total <= c.cost_start)) status = VOX_MAP_BUNDLE_COST_ROSE;      // (a cost that is not finite has risen)
   }
   const bool write = status == VOX_MAP_BUNDLE_OK && c.n_accepted > 0;
-  for (int f = threadIdx.x; f < a.n_frames; f += BDEC) {
+  for (int f = threadIdx.x; f < a.v.n_frames; f += BDEC) {
     const int ps = a.w.pose_status[f];
     if (a.pose_status_out) a.pose_status_out[f] = ps;
     if (write && ps == BS_OK) {
       const double* T = a.w.Tc + 12 * (size_t)f;
-      float* o = a.T16 + 16 * (size_t)f;
+      float* o = a.T_out + 16 * (size_t)f;
       for (int col = 0; col < 4; ++col) {
         o[4 * col] = (float)T[3 * col]; o[4 * col + 1] = (float)T[3 * col + 1]; o[4 * col + 2] = (float)T[3 * col + 2];
         o[4 * col + 3] = col == 3 ? 1.f : 0.f;
@@ -639,11 +574,11 @@ __global__ __launch_bounds__(BDEC) void bundle_finish_kernel(MapBundleArgs a) {
     const int ps = a.w.point_status[e];
     if (a.point_status_out) a.point_status_out[e] = ps;
     if (write && ps == BS_OK)
-      for (int k = 0; k < 3; ++k) a.pts[3 * (size_t)e + k] = (float)a.w.Pc[3 * (size_t)e + k];
+      for (int k = 0; k < 3; ++k) a.v.pts[3 * (size_t)e + k] = (float)a.w.Pc[3 * (size_t)e + k];
   }
   if (threadIdx.x == 0) {
     vox_map_bundle_stats* s = static_cast<vox_map_bundle_stats*>(a.stats);
-    s->status = status; s->n_frames = a.n_frames; s->n_entries = M; s->n_obs = c.n_obs; s->n_free_frames = c.n_free_frames;
+    s->status = status; s->n_frames = a.v.n_frames; s->n_entries = M; s->n_obs = c.n_obs; s->n_free_frames = c.n_free_frames;
     s->n_free_points = c.n_free_points; s->n_accepted = c.n_accepted; s->reserved = 0;
     s->cost_before = c.cost_start; s->cost_after = c.dead ? c.cost_start : total;
   }
@@ -668,15 +603,11 @@ MapBundleWs map_bundle_layout(void* base, int n_frames, int bound) {
 }
 
 hipError_t launch_map_bundle(hipStream_t st, const MapBundleArgs& a, int n_cu) {
-  MapRefineArgs la{};
-  la.w = a.l; la.bound = a.bound; la.n_frames = a.n_frames; la.n_max = a.n_max;
-  hipError_t e = launch_map_refine_lists(st, la);
+  hipError_t e = launch_map_refine_lists(st, a.l, a.v.n_frames, a.v.n_max, a.v.bound);
   if (e != hipSuccess) return e;
-  const dim3 frames(a.n_frames), wg(BB), one(1);
-  const int B = a.bound > 0 ? a.bound : 1;
-  const int n_batches = (B + BLPB - 1) / BLPB;
-  const int cap = 4 * (n_cu > 0 ? n_cu : 256);
-  const dim3 points(n_batches < cap ? n_batches : cap);
+  const dim3 frames(a.v.n_frames), wg(BB), one(1);
+  const int B = a.v.bound > 0 ? a.v.bound : 1;
+  const dim3 points(landmark_grid(a.v.bound, n_cu));
   hipLaunchKernelGGL(bundle_init_frames_kernel, frames, wg, 0, st, a);
   hipLaunchKernelGGL(bundle_init_points_kernel, dim3((B + BB - 1) / BB), wg, 0, st, a);
   hipLaunchKernelGGL(bundle_census_kernel, one, wg, 0, st, a);
@@ -697,7 +628,7 @@ hipError_t launch_map_bundle(hipStream_t st, const MapBundleArgs& a, int n_cu) {
     e = hipGetLastError();
     if (e != hipSuccess) return e;
   }
-  const size_t most = 12 * (size_t)a.n_frames > 3 * (size_t)B ? 12 * (size_t)a.n_frames : 3 * (size_t)B;
+  const size_t most = 12 * (size_t)a.v.n_frames > 3 * (size_t)B ? 12 * (size_t)a.v.n_frames : 3 * (size_t)B;
   hipLaunchKernelGGL(bundle_round_kernel, dim3((unsigned)((most + BB - 1) / BB)), wg, 0, st, a);
   hipLaunchKernelGGL(bundle_cost_kernel<B_FINAL>, frames, wg, 0, st, a);
   hipLaunchKernelGGL(bundle_finish_kernel, one, dim3(BDEC), 0, st, a);

@@ -1,11 +1,13 @@
 // map_cull.hip -- landmarks taken out of the device map (voe_map_cull*): every entry is scored from ALL the rows of n_frames
 // frames that see it, the survivors are compacted in order, the table is rebuilt.  The rules are those of
-// include/vo_map_cull.h.  Launches behind the lookup (which wrote the entry of every query position) and behind the ordered
-// observation lists of map_refine.hip (launch_map_refine_lists, unchanged):
+// include/vo_map_cull.h.  An observation is vo_math.h's map_obs, the one model of the four adjustment files; the view of the map
+// and the frames, the row helpers and the landmark kernels' grid are vo_internal.h's, the scans vo_math.h's.  Launches behind the
+// lookup (which wrote the entry of every query position) and behind the ordered observation lists of map_refine.hip
+// (launch_map_refine_lists, unchanged):
 //   cull_score_kernel      16 lanes per landmark.  Pass 1 strides the ordered list over the lanes (observation k in lane
-//                          k mod 16): the sum of |e|^2 by the fixed DPP tree of refine_row_sum, the extrema and the frame
-//                          changes by the same four row steps.  Pass 2 (only with the parallax test on) visits the pairs in
-//                          tiles of 16 x 16: a lane holds the unit ray of one observation of tile A and one of tile B, tile B's
+//                          k mod 16): the sum of |e|^2 by the fixed DPP tree of refine_row_sum, the extrema (refine_row_max /
+//                          _min) and the frame changes by the same four row steps.  Pass 2 (only with the parallax test on)
+//                          visits the pairs in tiles of 16 x 16: a lane holds the unit ray of one observation of tile A and one of tile B, tile B's
 //                          rays and their list positions go round the DPP row (row_ror:1, 16 steps), every lane keeps the
 //                          minimum of its dot products, the 16 lanes are reduced by a row minimum.  The rays are ALWAYS
 //                          recomputed from the keys -- once per lane and tile pair, 16 pairs of dot products each -- so there
@@ -29,85 +31,66 @@ constexpr int CB = 256;                   // threads per workgroup
 constexpr int CG = 16;                    // lanes per landmark: one DPP row
 constexpr int CLPB = CB / CG;             // landmarks per workgroup and trip
 constexpr int CSTAT = 1024;               // threads of the scan and of the statistics workgroup
-static_assert(CG == 16, "a landmark's lanes are one DPP row (refine_row_sum, vo_internal.h)");
+static_assert(CB == MAP_WG && CG == MAP_ROW, "a landmark's lanes are one DPP row; the shared helpers of vo_internal.h count on both sizes");
 
 enum { CV_KEPT = 0, CV_UNSEEN = 1, CV_FEW_OBS = 2, CV_FEW_FRAMES = 3, CV_NOT_FINITE = 4, CV_BEHIND = 5, CV_HIGH_ERROR = 6, CV_LOW_PARALLAX = 7 };
 
 struct CullEntry { int32_t verdict, n_obs, n_frames, reserved; double mean_sq, max_sq, min_z, cos_parallax; };
 static_assert(sizeof(CullEntry) == 48, "voe_map_cull_entry");
 
-__device__ __forceinline__ int cull_size(const MapCullArgs& a) {
-  int M = a.hdr[0];
-  M = M < a.cap ? M : a.cap;
-  return M < a.bound ? M : a.bound;
-}
-
-// the four steps of refine_row_sum with another exact, commutative operation in place of the sum
-__device__ __forceinline__ double cull_row_max(double x) {
-  x = fmax(x, refine_dpp<0xB1>(x)); x = fmax(x, refine_dpp<0x4E>(x)); x = fmax(x, refine_dpp<0x141>(x)); return fmax(x, refine_dpp<0x140>(x));
-}
-__device__ __forceinline__ double cull_row_min(double x) {
-  x = fmin(x, refine_dpp<0xB1>(x)); x = fmin(x, refine_dpp<0x4E>(x)); x = fmin(x, refine_dpp<0x141>(x)); return fmin(x, refine_dpp<0x140>(x));
-}
 __device__ __forceinline__ int cull_ror1(int x) { return __builtin_amdgcn_update_dpp(x, x, 0x121, 0xf, 0xf, false); }
 
-// One observation of the landmark p: p_cam = R p + t and q = K p_cam as map_refine_term forms them, |e|^2, camera z, and the
-// unit ray u = d / |d|, d = R^T p_cam.
+// One observation of the landmark p by map_obs (no Huber weight: rho is |e|^2): |e|^2, camera z, and the unit ray u = d / |d|,
+// d = R^T p_cam.
 __device__ __forceinline__ void cull_obs(const MapCullArgs& a, const double K[9], const double p[3], int key, double& sq, double& z, double u[3]) {
-  const int f = key / a.n_max, i = key - f * a.n_max;
-  const float2 m = reinterpret_cast<const float2*>(a.uv)[(size_t)f * a.uv_stride + i];
-  const float* T = a.T16 + 16 * (size_t)f;
-  double R[9], pc[3], q[3], d[3];
+  float2 m;
+  const int f = a.v.decode(key, m);
+  float Rt[12];
+  a.v.load_pose(f, Rt);
+  MapObs o;
+  map_obs(K, Rt, p, (double)m.x, (double)m.y, 0.0, o);
+  sq = o.rho;
+  z = o.pc[2];
+  double d[3];
 #pragma unroll
-  for (int k = 0; k < 9; ++k) R[k] = (double)T[(k % 3) + 4 * (k / 3)];      // column-major 3x3
-#pragma unroll
-  for (int r = 0; r < 3; ++r) pc[r] = __builtin_fma(R[r + 6], p[2], __builtin_fma(R[r + 3], p[1], __builtin_fma(R[r], p[0], (double)T[12 + r])));
-#pragma unroll
-  for (int r = 0; r < 3; ++r) q[r] = __builtin_fma(K[r + 6], pc[2], __builtin_fma(K[r + 3], pc[1], K[r] * pc[0]));
-  const double iz = 1.0 / q[2];
-  const double e0 = q[0] * iz - (double)m.x, e1 = q[1] * iz - (double)m.y;
-  sq = e0 * e0 + e1 * e1;
-  z = pc[2];
-#pragma unroll
-  for (int c = 0; c < 3; ++c) d[c] = __builtin_fma(R[2 + 3 * c], pc[2], __builtin_fma(R[1 + 3 * c], pc[1], R[3 * c] * pc[0]));
+  for (int c = 0; c < 3; ++c) d[c] = __builtin_fma((double)Rt[2 + 3 * c], o.pc[2], __builtin_fma((double)Rt[1 + 3 * c], o.pc[1], (double)Rt[3 * c] * o.pc[0]));
   const double nrm = sqrt(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]);
   u[0] = d[0] / nrm; u[1] = d[1] / nrm; u[2] = d[2] / nrm;                 // (|d| == 0: NaN, which pass 1 reports)
 }
 
 __global__ __launch_bounds__(CB) void cull_score_kernel(MapCullArgs a) {
-  const int M = cull_size(a);
+  const int M = a.v.size(), n_max = a.v.n_max;
   const int lg = threadIdx.x & (CG - 1), grp = threadIdx.x / CG;
-  const int shift = (threadIdx.x & 63) & ~(CG - 1);          // this group's bits in a ballot of the wave
   double K[9];
 #pragma unroll
-  for (int k = 0; k < 9; ++k) K[k] = a.K[k];
-  const int n_batches = (a.bound + CLPB - 1) / CLPB;
+  for (int k = 0; k < 9; ++k) K[k] = a.v.K[k];
+  const int n_batches = (a.v.bound + CLPB - 1) / CLPB;
   for (int batch = blockIdx.x; batch < n_batches; batch += gridDim.x) {      // (uniform in the workgroup: the ballot below sees whole waves)
     const int e = batch * CLPB + grp;
     const bool in = e < M;
     const int n = in ? a.l.cur[e] : 0;
-    const int off = in ? a.l.cnt[e] + a.l.blk[e / CB] : 0;
+    const int off = in ? a.l.offset(e) : 0;
     double p[3] = {0.0, 0.0, 0.0};
-    if (in) { p[0] = (double)a.pts[3 * (size_t)e]; p[1] = (double)a.pts[3 * (size_t)e + 1]; p[2] = (double)a.pts[3 * (size_t)e + 2]; }
+    if (in) { p[0] = (double)a.v.pts[3 * (size_t)e]; p[1] = (double)a.v.pts[3 * (size_t)e + 1]; p[2] = (double)a.v.pts[3 * (size_t)e + 2]; }
     // ---- pass 1: the sums, the extrema, the frame changes ----
     double sum = 0.0, mx = 0.0, mz = 1.7976931348623157e308, changes = 0.0;
     bool bad = false;
     for (int j = lg; j < n; j += CG) {
       const int key = a.l.keys[off + j];
-      const int prev = j > 0 ? a.l.keys[off + j - 1] / a.n_max : -1;
+      const int prev = j > 0 ? a.l.keys[off + j - 1] / n_max : -1;
       double sq, z, u[3];
       cull_obs(a, K, p, key, sq, z, u);
       sum += sq;
       mx = fmax(mx, sq);
       mz = fmin(mz, z);
-      changes += (key / a.n_max != prev) ? 1.0 : 0.0;
+      changes += (key / n_max != prev) ? 1.0 : 0.0;
       bad |= !(refine_finite(sq) && refine_finite(z) && refine_finite(u[0]) && refine_finite(u[1]) && refine_finite(u[2]));
     }
     sum = refine_row_sum(sum);
-    mx = cull_row_max(mx);
-    mz = cull_row_min(mz);
+    mx = refine_row_max(mx);
+    mz = refine_row_min(mz);
     const int n_fr = (int)refine_row_sum(changes);           // (whole numbers below 2^31: exact)
-    const bool any_bad = ((__ballot(bad) >> shift) & ((1ull << CG) - 1ull)) != 0ull;
+    const bool any_bad = refine_row_any(bad);
     // ---- pass 2: the smallest u_k . u_l over the pairs ----
     double cmin = 2.0;
     if (a.parallax && n >= 2) {                              // (the same in the 16 lanes of a row: the row's DPP moves see all of them)
@@ -130,7 +113,7 @@ __global__ __launch_bounds__(CB) void cull_score_kernel(MapCullArgs a) {
         }
       }
     }
-    cmin = cull_row_min(cmin);
+    cmin = refine_row_min(cmin);
     if (in && lg == 0) {
       const double cosp = (a.parallax && n >= 2) ? cmin : 1.0;
       const double mean = n > 0 ? sum / (double)n : 0.0;
@@ -157,47 +140,21 @@ __global__ __launch_bounds__(CB) void cull_score_kernel(MapCullArgs a) {
 
 __global__ __launch_bounds__(CB) void cull_count_kernel(MapCullArgs a) {
   __shared__ int s_wave[CB / 64];
-  const int M = cull_size(a);
+  const int M = a.v.size();
   const int e = blockIdx.x * CB + threadIdx.x;
   const int v = e < M ? a.w.rank[e] : 0;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  int incl = v;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) { const int o = __shfl_up(incl, d); if (lane >= d) incl += o; }
-  if (lane == 63) s_wave[wave] = incl;
-  __syncthreads();
-  int woff = 0, tot = 0;
-#pragma unroll
-  for (int w = 0; w < CB / 64; ++w) { const int c = s_wave[w]; if (w < wave) woff += c; tot += c; }
-  if (e < M) a.w.rank[e] = v ? woff + incl - v : -1;
+  int tot;
+  const int x = block_exclusive_scan<CB>(v, s_wave, tot);
+  if (e < M) a.w.rank[e] = v ? x : -1;
   if (threadIdx.x == 0) a.w.blk[blockIdx.x] = tot;
 }
 
 __global__ __launch_bounds__(CSTAT) void cull_scan_kernel(MapCullArgs a, int nb) {
   __shared__ int s_w[CSTAT / 64];
   __shared__ int s_carry;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  if (tid == 0) s_carry = 0;
-  __syncthreads();
-  for (int base = 0; base < nb; base += CSTAT) {
-    const int j = base + tid;
-    const int v = j < nb ? a.w.blk[j] : 0;
-    int incl = v;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) { const int o = __shfl_up(incl, d); if (lane >= d) incl += o; }
-    if (lane == 63) s_w[wave] = incl;
-    __syncthreads();
-    int woff = 0, tot = 0;
-#pragma unroll
-    for (int w = 0; w < CSTAT / 64; ++w) { const int c = s_w[w]; if (w < wave) woff += c; tot += c; }
-    const int carry = s_carry;
-    if (j < nb) a.w.blk[j] = carry + woff + incl - v;
-    __syncthreads();
-    if (tid == 0) s_carry = carry + tot;
-    __syncthreads();
-  }
-  if (tid == 0) {
-    const int M = cull_size(a), kept = s_carry;
+  const int kept = scan_with_carry<CSTAT>(a.w.blk, nb, s_w, &s_carry);
+  if (threadIdx.x == 0) {
+    const int M = a.v.size();
     a.w.ctl[0] = M; a.w.ctl[1] = kept; a.w.ctl[2] = (kept != M && !a.dry_run) ? 1 : 0;
   }
 }
@@ -210,9 +167,9 @@ __global__ __launch_bounds__(CB) void cull_scatter_kernel(MapCullArgs a) {
   const int to = r >= 0 ? a.w.blk[blockIdx.x] + r : -1;
   a.remap[e] = to;
   if (to < 0 || a.w.ctl[2] == 0) return;
-  a.w.stage_pts[3 * (size_t)to] = a.pts[3 * (size_t)e];
-  a.w.stage_pts[3 * (size_t)to + 1] = a.pts[3 * (size_t)e + 1];
-  a.w.stage_pts[3 * (size_t)to + 2] = a.pts[3 * (size_t)e + 2];
+  a.w.stage_pts[3 * (size_t)to] = a.v.pts[3 * (size_t)e];
+  a.w.stage_pts[3 * (size_t)to + 1] = a.v.pts[3 * (size_t)e + 1];
+  a.w.stage_pts[3 * (size_t)to + 2] = a.v.pts[3 * (size_t)e + 2];
   const float2* src = reinterpret_cast<const float2*>(a.app) + 5 * (size_t)e;
   float2* dst = reinterpret_cast<float2*>(a.w.stage_app) + 5 * (size_t)to;
 #pragma unroll
@@ -223,9 +180,9 @@ __global__ __launch_bounds__(CB) void cull_copy_kernel(MapCullArgs a) {
   if (a.w.ctl[2] == 0) return;
   const int j = blockIdx.x * CB + threadIdx.x;
   if (j >= a.w.ctl[1]) return;
-  a.pts[3 * (size_t)j] = a.w.stage_pts[3 * (size_t)j];
-  a.pts[3 * (size_t)j + 1] = a.w.stage_pts[3 * (size_t)j + 1];
-  a.pts[3 * (size_t)j + 2] = a.w.stage_pts[3 * (size_t)j + 2];
+  a.v.pts[3 * (size_t)j] = a.w.stage_pts[3 * (size_t)j];
+  a.v.pts[3 * (size_t)j + 1] = a.w.stage_pts[3 * (size_t)j + 1];
+  a.v.pts[3 * (size_t)j + 2] = a.w.stage_pts[3 * (size_t)j + 2];
   const float2* src = reinterpret_cast<const float2*>(a.w.stage_app) + 5 * (size_t)j;
   float2* dst = reinterpret_cast<float2*>(a.app) + 5 * (size_t)j;
 #pragma unroll
@@ -234,9 +191,9 @@ __global__ __launch_bounds__(CB) void cull_copy_kernel(MapCullArgs a) {
 
 __global__ void cull_header_kernel(MapCullArgs a) {
   if (threadIdx.x != 0 || blockIdx.x != 0 || a.w.ctl[2] == 0) return;
-  a.hdr[0] = a.w.ctl[1];            // the size
-  a.hdr[1] = a.w.ctl[1];            // base of the last update: there is none
-  a.hdr[2] = 0;                     // its rows
+  a.v.hdr[0] = a.w.ctl[1];          // the size
+  a.v.hdr[1] = a.w.ctl[1];          // base of the last update: there is none
+  a.v.hdr[2] = 0;                   // its rows
 }
 
 // voe_map_cull_stats: int32 status, n_before, n_kept, n_obs, by_verdict[8].  Whole numbers: any order gives the same tally.
@@ -278,15 +235,11 @@ MapCullWs map_cull_layout(void* base, int bound) {
 }
 
 hipError_t launch_map_cull(hipStream_t st, const MapCullArgs& a, int n_cu) {
-  MapRefineArgs l{};
-  l.w = a.l; l.bound = a.bound; l.n_frames = a.n_frames; l.n_max = a.n_max;
-  const hipError_t e = launch_map_refine_lists(st, l);
+  const hipError_t e = launch_map_refine_lists(st, a.l, a.v.n_frames, a.v.n_max, a.v.bound);
   if (e != hipSuccess) return e;
-  const int B = a.bound > 0 ? a.bound : 1;
+  const int B = a.v.bound > 0 ? a.v.bound : 1;
   const int nb = (B + CB - 1) / CB;
-  const int n_batches = (B + CLPB - 1) / CLPB;
-  const int cap = 4 * (n_cu > 0 ? n_cu : 256);               // resident workgroups stride over the batches, as in map_refine.hip
-  hipLaunchKernelGGL(cull_score_kernel, dim3(n_batches < cap ? n_batches : cap), dim3(CB), 0, st, a);
+  hipLaunchKernelGGL(cull_score_kernel, dim3(landmark_grid(a.v.bound, n_cu)), dim3(CB), 0, st, a);
   hipLaunchKernelGGL(cull_count_kernel, dim3(nb), dim3(CB), 0, st, a);
   hipLaunchKernelGGL(cull_scan_kernel, dim3(1), dim3(CSTAT), 0, st, a, nb);
   hipLaunchKernelGGL(cull_scatter_kernel, dim3(nb), dim3(CB), 0, st, a);

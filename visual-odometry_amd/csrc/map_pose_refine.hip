@@ -8,11 +8,13 @@
 // Launches behind the lookup (which wrote the entry of every query position):
 //   map_pose_refine_kernel    ONE WORKGROUP PER FRAME, all rounds in this one launch: the pose never leaves the workgroup.  The
 //                             rows are strided over the 256 threads (thread t takes the rows t, t + 256, ... in that order); the
-//                             28 sums are reduced in double by the fixed DPP tree of map_refine.hip inside every row of 16
-//                             lanes, the 16 row sums go through LDS and are added in row order (thread k < 28 adds term k), the
-//                             28 totals go back through LDS, so that all 256 threads hold the same bits and run the 6x6 solve
-//                             and the pose update redundantly.  No scratch; two barriers per round
-//   map_pose_stats_kernel     one workgroup: status census and the two cost sums in a fixed order, no float atomics
+//                             28 sums are reduced in double by frame_reduce (vo_internal.h; map_bundle.hip uses the same):
+//                             the fixed DPP tree inside every row of 16 lanes, the 16 row sums through LDS, added in row order
+//                             (thread k < 28 adds term k), the 28 totals back through LDS, so that all 256 threads hold the
+//                             same bits and run the 6x6 solve and the pose update redundantly.  No scratch; two barriers per
+//                             round, the second of which also gathers the "behind" flags
+//   map_pose_stats_kernel     one workgroup: status census and the two cost sums in a fixed order (status_census)
+// The observation is vo_math.h's map_pose_term on map_obs, the one model of the four adjustment files.
 // A single frame therefore runs on one compute unit; the call fills the device from about 256 frames on.
 #include "vo_internal.h"
 
@@ -20,35 +22,31 @@ namespace vo {
 
 constexpr int PB = 256;                   // threads per workgroup
 constexpr int PROWS = PB / 16;            // DPP rows per workgroup
+static_assert(PB == MAP_WG, "frame_reduce (vo_internal.h) counts on this size");
 constexpr int PSTAT = 1024;               // threads of the statistics workgroup
 
 enum { PS_OK = 0, PS_FIXED = 1, PS_FEW_OBS = 2, PS_BEHIND = 3, PS_NOT_FINITE = 4, PS_COST_ROSE = 5 };
-
-__device__ __forceinline__ int pose_map_size(const MapPoseArgs& a) {
-  int M = a.hdr[0];
-  M = M < a.cap ? M : a.cap;
-  return M < a.bound ? M : a.bound;
-}
 
 __global__ __launch_bounds__(PB) void map_pose_refine_kernel(MapPoseArgs a) {
   __shared__ double s_row[PROWS][NPOSE], s_tot[NPOSE];
   __shared__ int s_n;
   const int f = blockIdx.x, tid = threadIdx.x;
-  const int M = pose_map_size(a);
-  const int32_t* ent = a.ent + (size_t)f * a.n_max;
-  const float2* uv = reinterpret_cast<const float2*>(a.uv) + (size_t)f * a.uv_stride;
+  const int M = a.v.size(), n_max = a.v.n_max;
+  const int32_t* ent = a.ent + (size_t)f * n_max;
+  const float2* uv = reinterpret_cast<const float2*>(a.v.uv) + (size_t)f * a.v.uv_stride;
   if (tid == 0) s_n = 0;
-  const float* T0 = a.T_in + 16 * (size_t)f;                 // the frame's 64 bytes as they came (nobody else writes them)
+  const float* T0 = a.v.T16 + 16 * (size_t)f;                // the frame's 64 bytes as they came (nobody else writes them)
   double T[12];                                              // R column-major, then t
   float Tf[12];
+  a.v.load_pose(f, Tf);
 #pragma unroll
-  for (int k = 0; k < 12; ++k) { Tf[k] = T0[(k % 3) + 4 * (k / 3)]; T[k] = (double)Tf[k]; }
+  for (int k = 0; k < 12; ++k) T[k] = (double)Tf[k];
   double K[9];
 #pragma unroll
-  for (int k = 0; k < 9; ++k) K[k] = a.K[k];
+  for (int k = 0; k < 9; ++k) K[k] = a.v.K[k];
   __syncthreads();
   int mine = 0;
-  for (int i = tid; i < a.n_max; i += PB) { const int e = ent[i]; mine += e >= 0 && e < M; }
+  for (int i = tid; i < n_max; i += PB) { const int e = ent[i]; mine += e >= 0 && e < M; }
   if (mine) atomicAdd(&s_n, mine);                           // (an integer count does not depend on the order)
   __syncthreads();
   const int n = s_n;
@@ -62,30 +60,15 @@ __global__ __launch_bounds__(PB) void map_pose_refine_kernel(MapPoseArgs a) {
     for (int k = 0; k < NPOSE; ++k) acc[k] = 0.0;
     bool bh = false;
     if (run) {
-      for (int i = tid; i < a.n_max; i += PB) {
+      for (int i = tid; i < n_max; i += PB) {
         const int e = ent[i];
         if (e < 0 || e >= M) continue;
-        const float pt[3] = {a.pts[3 * (size_t)e], a.pts[3 * (size_t)e + 1], a.pts[3 * (size_t)e + 2]};
+        const float pt[3] = {a.v.pts[3 * (size_t)e], a.v.pts[3 * (size_t)e + 1], a.v.pts[3 * (size_t)e + 2]};
         const float2 m = uv[i];
         bh |= !map_pose_term(K, T, pt, (double)m.x, (double)m.y, a.huber, acc);
       }
     }
-#pragma unroll
-    for (int k = 0; k < NPOSE; ++k) acc[k] = refine_row_sum(acc[k]);
-    if ((tid & 15) == 0) {
-#pragma unroll
-      for (int k = 0; k < NPOSE; ++k) s_row[tid >> 4][k] = acc[k];
-    }
-    __syncthreads();
-    if (tid < NPOSE) {                                       // the 16 row sums of one term, in row order
-      double s = s_row[0][tid];
-#pragma unroll
-      for (int w = 1; w < PROWS; ++w) s += s_row[w][tid];
-      s_tot[tid] = s;
-    }
-    const bool any_behind = __syncthreads_or(bh) != 0;       // (the barrier that publishes s_tot and frees s_row for the next round)
-#pragma unroll
-    for (int k = 0; k < NPOSE; ++k) acc[k] = s_tot[k];        // every thread holds the same bits from here on
+    const bool any_behind = frame_reduce<NPOSE, NPOSE, true>(acc, s_row, s_tot, bh);      // every thread holds the same bits from here on
     if (run) {
       bool finite = true;
 #pragma unroll
@@ -148,7 +131,7 @@ __global__ __launch_bounds__(PB) void map_pose_refine_kernel(MapPoseArgs a) {
         o[4 * c] = Tf[3 * c]; o[4 * c + 1] = Tf[3 * c + 1]; o[4 * c + 2] = Tf[3 * c + 2];
         o[4 * c + 3] = c == 3 ? 1.f : 0.f;
       }
-    } else if (a.T_out != a.T_in) {                          // as 32-bit words: a NaN keeps its payload
+    } else if (a.T_out != a.v.T16) {                          // as 32-bit words: a NaN keeps its payload
       const unsigned* src = reinterpret_cast<const unsigned*>(T0);
 #pragma unroll
       for (int k = 0; k < 16; ++k) reinterpret_cast<unsigned*>(o)[k] = src[k];
@@ -156,35 +139,9 @@ __global__ __launch_bounds__(PB) void map_pose_refine_kernel(MapPoseArgs a) {
   }
 }
 
-// vo_map_pose_refine_stats: int32 n_frames, n_obs, by_status[6]; double cost_before, cost_after.  Thread t takes the frames t,
-// t + 1024, ... in that order, thread 0 adds the 1024 partial sums in thread order: a fixed order, whatever the scheduling.
+// vo_map_pose_refine_stats: int32 n_frames, n_obs, by_status[6]; double cost_before, cost_after (status_census, vo_internal.h)
 __global__ __launch_bounds__(PSTAT) void map_pose_stats_kernel(MapPoseArgs a) {
-  __shared__ double s_c0[PSTAT], s_c1[PSTAT];
-  __shared__ int s_n[7];
-  if (threadIdx.x < 7) s_n[threadIdx.x] = 0;
-  __syncthreads();
-  int n[7] = {0, 0, 0, 0, 0, 0, 0};
-  double c0 = 0.0, c1 = 0.0;
-  for (int f = threadIdx.x; f < a.n_frames; f += PSTAT) {
-    const int s = a.status[f];
-#pragma unroll
-    for (int k = 0; k < 6; ++k) n[k] += s == k;
-    n[6] += a.n_obs[f];
-    if (s == PS_OK) { c0 += a.cost[2 * (size_t)f]; c1 += a.cost[2 * (size_t)f + 1]; }
-  }
-  s_c0[threadIdx.x] = c0; s_c1[threadIdx.x] = c1;
-#pragma unroll
-  for (int k = 0; k < 7; ++k) if (n[k]) atomicAdd(&s_n[k], n[k]);
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    double t0 = 0.0, t1 = 0.0;
-    for (int t = 0; t < PSTAT; ++t) { t0 += s_c0[t]; t1 += s_c1[t]; }
-    int* si = static_cast<int*>(a.stats);
-    si[0] = a.n_frames; si[1] = s_n[6];
-    for (int k = 0; k < 6; ++k) si[2 + k] = s_n[k];
-    double* sd = reinterpret_cast<double*>(si + 8);
-    sd[0] = t0; sd[1] = t1;
-  }
+  status_census<PSTAT, true>(a.v.n_frames, a.status, a.cost, a.n_obs, nullptr, a.stats);
 }
 
 MapPoseWs map_pose_layout(void* base, int n_frames, int n_max, bool with_lookup) {
@@ -204,7 +161,7 @@ MapPoseWs map_pose_layout(void* base, int n_frames, int n_max, bool with_lookup)
 }
 
 hipError_t launch_map_pose_refine(hipStream_t st, const MapPoseArgs& a) {
-  hipLaunchKernelGGL(map_pose_refine_kernel, dim3(a.n_frames), dim3(PB), 0, st, a);
+  hipLaunchKernelGGL(map_pose_refine_kernel, dim3(a.v.n_frames), dim3(PB), 0, st, a);
   hipLaunchKernelGGL(map_pose_stats_kernel, dim3(1), dim3(PSTAT), 0, st, a);
   return hipGetLastError();
 }

@@ -16,7 +16,10 @@
 //                                   the 10 sums reduced in double by a fixed DPP tree inside the 16 lanes (every lane ends
 //                                   with the same bits), the 3x3 solve done redundantly by the 16
 //   map_refine_stats_kernel         one workgroup: status census and the two cost sums in a fixed order, no float atomics
-// Per-observation terms are evaluated in DOUBLE (vo_math.h: map_refine_term): DESIGN.md section 4.13 says why.
+// Per-observation terms are evaluated in DOUBLE (vo_math.h: map_refine_term on map_obs, the one observation model of the four
+// adjustment files): DESIGN.md section 4.13 says why.  Shared with them (vo_internal.h): the view of the map and the frames
+// (MapView: size, load_pose, decode), the list offset (MapRefineWs::offset), the row helpers (refine_row_sum / _any), the
+// census (status_census), the landmark kernels' grid (landmark_grid); the block scan is vo_math.h's block_exclusive_scan.
 #include "vo_internal.h"
 
 namespace vo {
@@ -29,91 +32,69 @@ constexpr int RSTAT = 1024;               // threads of the statistics workgroup
 
 enum { ST_OK = 0, ST_UNSEEN = 1, ST_FEW_OBS = 2, ST_BEHIND = 3, ST_NOT_FINITE = 4, ST_COST_ROSE = 5 };
 
-__device__ __forceinline__ int refine_size(const MapRefineArgs& a) {
-  int M = a.hdr[0];
-  M = M < a.cap ? M : a.cap;
-  return M < a.bound ? M : a.bound;
-}
-
-__global__ __launch_bounds__(RB) void map_refine_count_kernel(MapRefineArgs a) {
-  const size_t rows = (size_t)a.n_frames * a.n_max;
+// the list kernels read the workspace alone: rows = n_frames * n_max positions, entries below bound
+__global__ __launch_bounds__(RB) void map_refine_count_kernel(MapRefineWs w, size_t rows, int bound) {
   const size_t k = (size_t)blockIdx.x * RB + threadIdx.x;
   if (k >= rows) return;
-  const int e = a.w.ent[k];
-  if (e >= 0 && e < a.bound) atomicAdd(&a.w.cnt[e], 1);
+  const int e = w.ent[k];
+  if (e >= 0 && e < bound) atomicAdd(&w.cnt[e], 1);
 }
 
-__global__ __launch_bounds__(RB) void map_refine_offsets_kernel(MapRefineArgs a) {
+__global__ __launch_bounds__(RB) void map_refine_offsets_kernel(MapRefineWs w, int bound) {
   __shared__ int s_wave[RB / 64];
   const int e = blockIdx.x * RB + threadIdx.x;
-  const int v = e < a.bound ? a.w.cnt[e] : 0;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  int incl = v;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) { const int o = __shfl_up(incl, d); if (lane >= d) incl += o; }
-  if (lane == 63) s_wave[wave] = incl;
-  __syncthreads();
-  int off = 0, tot = 0;
-#pragma unroll
-  for (int w = 0; w < RB / 64; ++w) { const int c = s_wave[w]; if (w < wave) off += c; tot += c; }
-  if (e < a.bound) a.w.cnt[e] = off + incl - v;
-  if (threadIdx.x == 0) a.w.blk[blockIdx.x] = tot;
+  int tot;
+  const int x = block_exclusive_scan<RB>(e < bound ? w.cnt[e] : 0, s_wave, tot);
+  if (e < bound) w.cnt[e] = x;
+  if (threadIdx.x == 0) w.blk[blockIdx.x] = tot;
 }
 
-__device__ __forceinline__ int refine_offset(const MapRefineArgs& a, int e) { return a.w.cnt[e] + a.w.blk[e / RB]; }
-
-__global__ __launch_bounds__(RB) void map_refine_scatter_kernel(MapRefineArgs a) {
-  const size_t rows = (size_t)a.n_frames * a.n_max;
+__global__ __launch_bounds__(RB) void map_refine_scatter_kernel(MapRefineWs w, size_t rows, int bound) {
   const size_t k = (size_t)blockIdx.x * RB + threadIdx.x;
   if (k >= rows) return;
-  const int e = a.w.ent[k];
-  if (e < 0 || e >= a.bound) return;
-  const int at = atomicAdd(&a.w.cur[e], 1);
-  const size_t o = (size_t)refine_offset(a, e) + at;
-  if (o < rows) a.w.tmp[o] = (int)k;                         // (always: the segments partition the observations)
+  const int e = w.ent[k];
+  if (e < 0 || e >= bound) return;
+  const int at = atomicAdd(&w.cur[e], 1);
+  const size_t o = (size_t)w.offset(e) + at;
+  if (o < rows) w.tmp[o] = (int)k;                           // (always: the segments partition the observations)
 }
 
-__global__ __launch_bounds__(RB) void map_refine_order_kernel(MapRefineArgs a) {
-  const size_t rows = (size_t)a.n_frames * a.n_max;
-  const int total = *a.w.total;
+__global__ __launch_bounds__(RB) void map_refine_order_kernel(MapRefineWs w, size_t rows, int bound) {
+  const int total = *w.total;
   const size_t s = (size_t)blockIdx.x * RB + threadIdx.x;
   if (s >= rows || s >= (size_t)total) return;
-  const int key = a.w.tmp[s];
+  const int key = w.tmp[s];
   if (key < 0 || (size_t)key >= rows) return;
-  const int e = a.w.ent[key];
-  if (e < 0 || e >= a.bound) return;
-  const int off = refine_offset(a, e), n = a.w.cur[e];
+  const int e = w.ent[key];
+  if (e < 0 || e >= bound) return;
+  const int off = w.offset(e), n = w.cur[e];
   int rank = 0;
-  for (int j = 0; j < n; ++j) rank += a.w.tmp[off + j] < key;
-  a.w.keys[off + rank] = key;
+  for (int j = 0; j < n; ++j) rank += w.tmp[off + j] < key;
+  w.keys[off + rank] = key;
 }
 
-static_assert(RG == 16, "a landmark's lanes are one DPP row (refine_row_sum, vo_internal.h)");
+static_assert(RB == MAP_WG && RG == MAP_ROW, "a landmark's lanes are one DPP row; the shared helpers of vo_internal.h count on both sizes");
 
 template <bool LDS>
 __global__ __launch_bounds__(RB) void map_refine_kernel(MapRefineArgs a) {
   __shared__ float s_pose[LDS ? REFINE_LDS_FRAMES * 12 : 12];
   if (LDS) {
-    for (int k = threadIdx.x; k < a.n_frames * 12; k += RB) {
-      const int f = k / 12, j = k - 12 * f;
-      s_pose[k] = a.T16[16 * (size_t)f + (j < 9 ? (j % 3) + 4 * (j / 3) : 3 + j)];      // R column-major, then t
-    }
+    for (int k = threadIdx.x; k < a.v.n_frames * 12; k += RB) s_pose[k] = a.v.pose_at(k / 12, k % 12);
     __syncthreads();
   }
-  const int M = refine_size(a);
+  const int M = a.v.size();
   const int lg = threadIdx.x & (RG - 1), grp = threadIdx.x / RG;
-  const int shift = (threadIdx.x & 63) & ~(RG - 1);          // this group's bits in a ballot of the wave
   double K[9];
 #pragma unroll
-  for (int k = 0; k < 9; ++k) K[k] = a.K[k];
-  const int n_batches = (a.bound + RLPB - 1) / RLPB;
+  for (int k = 0; k < 9; ++k) K[k] = a.v.K[k];
+  const int n_batches = (a.v.bound + RLPB - 1) / RLPB;
   for (int batch = blockIdx.x; batch < n_batches; batch += gridDim.x) {      // (uniform in the workgroup: the shuffles below see whole waves)
     const int e = batch * RLPB + grp;
     const bool in = e < M;
     const int n = in ? a.w.cur[e] : 0;
-    const int off = in ? refine_offset(a, e) : 0;
+    const int off = in ? a.w.offset(e) : 0;
     float p0[3] = {0.f, 0.f, 0.f};
-    if (in) { p0[0] = a.pts[3 * (size_t)e]; p0[1] = a.pts[3 * (size_t)e + 1]; p0[2] = a.pts[3 * (size_t)e + 2]; }
+    if (in) { p0[0] = a.v.pts[3 * (size_t)e]; p0[1] = a.v.pts[3 * (size_t)e + 1]; p0[2] = a.v.pts[3 * (size_t)e + 2]; }
     double p[3] = {(double)p0[0], (double)p0[1], (double)p0[2]};
     float pf[3] = {p0[0], p0[1], p0[2]};
     bool run = in && n >= a.min_obs;                         // (min_obs >= 2: an unseen entry does not run either)
@@ -126,25 +107,21 @@ __global__ __launch_bounds__(RB) void map_refine_kernel(MapRefineArgs a) {
       bool bh = false;
       if (run) {
         for (int j = lg; j < n; j += RG) {
-          const int key = a.w.keys[off + j];
-          const int f = key / a.n_max, i = key - f * a.n_max;
-          const float2 m = reinterpret_cast<const float2*>(a.uv)[(size_t)f * a.uv_stride + i];
+          float2 m;
+          const int f = a.v.decode(a.w.keys[off + j], m);
           float Rt[12];
           if (LDS) {
 #pragma unroll
             for (int k = 0; k < 12; ++k) Rt[k] = s_pose[12 * f + k];
           } else {
-            const float* T = a.T16 + 16 * (size_t)f;
-#pragma unroll
-            for (int k = 0; k < 9; ++k) Rt[k] = T[(k % 3) + 4 * (k / 3)];
-            Rt[9] = T[12]; Rt[10] = T[13]; Rt[11] = T[14];
+            a.v.load_pose(f, Rt);
           }
           bh |= !map_refine_term(K, Rt, p, (double)m.x, (double)m.y, a.huber, acc);
         }
       }
 #pragma unroll
       for (int k = 0; k < NREF; ++k) acc[k] = refine_row_sum(acc[k]);
-      const bool any_behind = ((__ballot(bh) >> shift) & ((1ull << RG) - 1ull)) != 0ull;
+      const bool any_behind = refine_row_any(bh);
       if (run) {
         bool finite = true;
 #pragma unroll
@@ -188,42 +165,16 @@ __global__ __launch_bounds__(RB) void map_refine_kernel(MapRefineArgs a) {
         float* o = a.xyz_out + 3 * (size_t)e;
         o[0] = replace ? pf[0] : p0[0]; o[1] = replace ? pf[1] : p0[1]; o[2] = replace ? pf[2] : p0[2];
       } else if (replace) {
-        float* o = a.pts + 3 * (size_t)e;
+        float* o = a.v.pts + 3 * (size_t)e;
         o[0] = pf[0]; o[1] = pf[1]; o[2] = pf[2];
       }
     }
   }
 }
 
-// vo_map_refine_stats: int32 n_entries, n_obs, by_status[6]; double cost_before, cost_after.  Thread t takes the entries t,
-// t + 1024, ... in that order, thread 0 adds the 1024 partial sums in thread order: a fixed order, whatever the scheduling.
+// vo_map_refine_stats: int32 n_entries, n_obs, by_status[6]; double cost_before, cost_after (status_census, vo_internal.h)
 __global__ __launch_bounds__(RSTAT) void map_refine_stats_kernel(MapRefineArgs a) {
-  __shared__ double s_c0[RSTAT], s_c1[RSTAT];
-  __shared__ int s_n[6];
-  const int M = refine_size(a);
-  if (threadIdx.x < 6) s_n[threadIdx.x] = 0;
-  __syncthreads();
-  int n[6] = {0, 0, 0, 0, 0, 0};
-  double c0 = 0.0, c1 = 0.0;
-  for (int e = threadIdx.x; e < M; e += RSTAT) {
-    const int s = a.status[e];
-#pragma unroll
-    for (int k = 0; k < 6; ++k) n[k] += s == k;
-    if (s == ST_OK) { c0 += a.w.cost[2 * (size_t)e]; c1 += a.w.cost[2 * (size_t)e + 1]; }
-  }
-  s_c0[threadIdx.x] = c0; s_c1[threadIdx.x] = c1;
-#pragma unroll
-  for (int k = 0; k < 6; ++k) if (n[k]) atomicAdd(&s_n[k], n[k]);
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    double t0 = 0.0, t1 = 0.0;
-    for (int t = 0; t < RSTAT; ++t) { t0 += s_c0[t]; t1 += s_c1[t]; }
-    int* si = static_cast<int*>(a.stats);
-    si[0] = M; si[1] = *a.w.total;
-    for (int k = 0; k < 6; ++k) si[2 + k] = s_n[k];
-    double* sd = reinterpret_cast<double*>(si + 8);
-    sd[0] = t0; sd[1] = t1;
-  }
+  status_census<RSTAT, false>(a.v.size(), a.status, a.w.cost, nullptr, a.w.total, a.stats);
 }
 
 MapRefineWs map_refine_layout(void* base, int n_frames, int n_max, int bound) {
@@ -245,34 +196,31 @@ MapRefineWs map_refine_layout(void* base, int n_frames, int n_max, int bound) {
   return w;
 }
 
-hipError_t launch_map_refine_lists(hipStream_t st, const MapRefineArgs& a) {
-  const size_t rows = (size_t)a.n_frames * (size_t)a.n_max, B = (size_t)(a.bound > 0 ? a.bound : 1);
+hipError_t launch_map_refine_lists(hipStream_t st, const MapRefineWs& w, int n_frames, int n_max, int bound) {
+  const size_t rows = (size_t)n_frames * (size_t)n_max, B = (size_t)(bound > 0 ? bound : 1);
   const int nbE = (int)((B + RB - 1) / RB);
-  hipError_t e = hipMemsetAsync(a.w.cnt, 0, sizeof(int) * 2 * B, st);
+  hipError_t e = hipMemsetAsync(w.cnt, 0, sizeof(int) * 2 * B, st);
   if (e != hipSuccess) return e;
   const unsigned row_blocks = (unsigned)((rows + RB - 1) / RB);
-  if (rows) hipLaunchKernelGGL(map_refine_count_kernel, dim3(row_blocks), dim3(RB), 0, st, a);
-  hipLaunchKernelGGL(map_refine_offsets_kernel, dim3(nbE), dim3(RB), 0, st, a);
-  e = launch_scan(st, a.w.blk, nbE, a.w.total);
+  if (rows) hipLaunchKernelGGL(map_refine_count_kernel, dim3(row_blocks), dim3(RB), 0, st, w, rows, bound);
+  hipLaunchKernelGGL(map_refine_offsets_kernel, dim3(nbE), dim3(RB), 0, st, w, bound);
+  e = launch_scan(st, w.blk, nbE, w.total);
   if (e != hipSuccess) return e;
   if (rows) {
-    hipLaunchKernelGGL(map_refine_scatter_kernel, dim3(row_blocks), dim3(RB), 0, st, a);
-    hipLaunchKernelGGL(map_refine_order_kernel, dim3(row_blocks), dim3(RB), 0, st, a);
+    hipLaunchKernelGGL(map_refine_scatter_kernel, dim3(row_blocks), dim3(RB), 0, st, w, rows, bound);
+    hipLaunchKernelGGL(map_refine_order_kernel, dim3(row_blocks), dim3(RB), 0, st, w, rows, bound);
   }
   return hipGetLastError();
 }
 
 hipError_t launch_map_refine(hipStream_t st, const MapRefineArgs& a, int n_cu) {
-  const hipError_t e = launch_map_refine_lists(st, a);
+  const hipError_t e = launch_map_refine_lists(st, a.w, a.v.n_frames, a.v.n_max, a.v.bound);
   if (e != hipSuccess) return e;
-  if (a.bound > 0) {
-    const int n_batches = (a.bound + RLPB - 1) / RLPB;
-    // 104 VGPRs leave 4 waves per SIMD, i.e. 4 workgroups of 256 threads per CU (4 x 24 KiB of LDS fit as well): that many stay
-    // resident and stride over the batches, so that the poses are staged once per resident workgroup
-    const int cap = 4 * (n_cu > 0 ? n_cu : 256);
-    const int grid = n_batches < cap ? n_batches : cap;
-    if (a.n_frames <= REFINE_LDS_FRAMES) hipLaunchKernelGGL(map_refine_kernel<true>, dim3(grid), dim3(RB), 0, st, a);
-    else hipLaunchKernelGGL(map_refine_kernel<false>, dim3(grid), dim3(RB), 0, st, a);
+  if (a.v.bound > 0) {
+    // (102 VGPRs leave the 4 waves per SIMD landmark_grid counts on, and 4 x 24 KiB of LDS fit as well)
+    const dim3 grid(landmark_grid(a.v.bound, n_cu));
+    if (a.v.n_frames <= REFINE_LDS_FRAMES) hipLaunchKernelGGL(map_refine_kernel<true>, grid, dim3(RB), 0, st, a);
+    else hipLaunchKernelGGL(map_refine_kernel<false>, grid, dim3(RB), 0, st, a);
   }
   hipLaunchKernelGGL(map_refine_stats_kernel, dim3(1), dim3(RSTAT), 0, st, a);
   return hipGetLastError();

@@ -521,6 +521,42 @@ struct MapLocaliseFinish {
 };
 hipError_t launch_map_localise_finish(hipStream_t st, const MapLocaliseFinish& a);
 
+// ---- a map and a window of frames, as the adjustment kernels see them (map_refine.hip, map_pose_refine.hip, map_bundle.hip,
+// map_cull.hip): embedded in their four argument blocks ----
+constexpr int MAP_WG = 256;             // threads per workgroup of these kernels = entries per block of the list offsets
+constexpr int MAP_ROW = 16;             // lanes per landmark of the landmark kernels: one DPP row
+struct MapView {
+  float* pts; int* hdr; int cap, bound; // the map; bound >= its size (the launches are sized by it, the kernels read the size itself)
+  const float* uv; size_t uv_stride;    // [n_frames] rows of pixels, uv_stride pixels between frames
+  int n_max, n_frames;
+  const float* T16;                     // [n_frames][16] column-major, p_cam = T p_map: the poses as they come in
+  double K[9];                          // column-major
+  __device__ __forceinline__ int size() const {
+    int M = hdr[0];
+    M = M < cap ? M : cap;
+    return M < bound ? M : bound;
+  }
+  // number k of frame f's pose as 12 numbers: R column-major, then t
+  __device__ __forceinline__ float pose_at(int f, int k) const { return T16[16 * (size_t)f + (k % 3) + 4 * (k / 3)]; }
+  template <class S>
+  __device__ __forceinline__ void load_pose(int f, S Rt[12]) const {
+#pragma unroll
+    for (int k = 0; k < 12; ++k) Rt[k] = (S)pose_at(f, k);
+  }
+  // the observation with the key f * n_max + i: its frame, and its pixel into m
+  __device__ __forceinline__ int decode(int key, float2& m) const {
+    const int f = key / n_max, i = key - f * n_max;
+    m = reinterpret_cast<const float2*>(uv)[(size_t)f * uv_stride + i];
+    return f;
+  }
+};
+// workgroups of a 16-lanes-per-landmark kernel: 4 waves per SIMD are resident, i.e. 4 workgroups of 256 threads per CU; that many
+// stride over the batches of 16 landmarks (map_refine.hip stages the poses once per resident workgroup)
+inline unsigned landmark_grid(int bound, int n_cu) {
+  const int n_batches = ((bound > 0 ? bound : 1) + MAP_WG / MAP_ROW - 1) / (MAP_WG / MAP_ROW), cap = 4 * (n_cu > 0 ? n_cu : 256);
+  return (unsigned)(n_batches < cap ? n_batches : cap);
+}
+
 // ---- structure-only refinement of the map's points (map_refine.hip, vo_map_refine*) ---------------------------------
 // The workspace of one call: `bound` >= the map's size (the launches are sized by it, the kernels read the size itself).
 struct MapRefineWs {
@@ -534,16 +570,13 @@ struct MapRefineWs {
   int32_t* status;     // [bound] (the caller's d_status_out takes its place when given)
   double* cost;        // [bound][2] cost before / after
   size_t bytes;
+  // where entry e's segment of the ordered lists begins
+  __device__ __forceinline__ int offset(int e) const { return cnt[e] + blk[e / MAP_WG]; }
 };
 MapRefineWs map_refine_layout(void* base, int n_frames, int n_max, int bound);
 struct MapRefineArgs {
   MapRefineWs w;
-  float* pts; const int* hdr; int cap;  // the map
-  int bound;
-  const float* uv; size_t uv_stride;    // pixels between frames
-  int n_max, n_frames;
-  const float* T16;                     // [n_frames][16] column-major, p_cam = T p_map
-  double K[9];                          // column-major
+  MapView v;
   int n_rounds, min_obs;
   double huber, damping;
   int32_t* status;                      // [size]
@@ -565,14 +598,89 @@ __device__ __forceinline__ double refine_dpp(double x) {
 // the sum over the 16 lanes of a DPP row, the same bits in every lane: the neighbour in the quad (quad_perm [1,0,3,2]), the
 // other pair of the quad (quad_perm [2,3,0,1]), the mirrored half row, the mirrored row.  Every step adds two values that both
 // lanes of a pair hold, and a + b = b + a bit for bit.
-__device__ __forceinline__ double refine_row_sum(double x) {
-  x += refine_dpp<0xB1>(x);
-  x += refine_dpp<0x4E>(x);
-  x += refine_dpp<0x141>(x);
-  x += refine_dpp<0x140>(x);
-  return x;
+template <class Op>
+__device__ __forceinline__ double refine_row_reduce(double x, Op op) {
+  x = op(x, refine_dpp<0xB1>(x));
+  x = op(x, refine_dpp<0x4E>(x));
+  x = op(x, refine_dpp<0x141>(x));
+  return op(x, refine_dpp<0x140>(x));
+}
+__device__ __forceinline__ double refine_row_sum(double x) { return refine_row_reduce(x, [](double a, double b) { return a + b; }); }
+// (fmax and fmin are exact and commutative too)
+__device__ __forceinline__ double refine_row_max(double x) { return refine_row_reduce(x, [](double a, double b) { return fmax(a, b); }); }
+__device__ __forceinline__ double refine_row_min(double x) { return refine_row_reduce(x, [](double a, double b) { return fmin(a, b); }); }
+// whether `flag` is set in any of the 16 lanes of this thread's DPP row (called by whole waves)
+__device__ __forceinline__ bool refine_row_any(bool flag) {
+  const int shift = (threadIdx.x & 63) & ~(MAP_ROW - 1);     // this row's bits in a ballot of the wave
+  return ((__ballot(flag) >> shift) & ((1ull << MAP_ROW) - 1ull)) != 0ull;
 }
 __device__ __forceinline__ bool refine_finite(double x) { return fabs(x) <= 1.7976931348623157e308; }
+
+// The sums of N terms over a frame's workgroup of MAP_WG threads: the DPP tree inside every row of 16 lanes, the 16 row sums
+// through LDS (s_row: 16 rows of LD >= N doubles), thread k < N adds term k in row order into s_tot[k]; afterwards every thread
+// holds the same bits.  Two barriers: the first publishes s_row, the second publishes s_tot -- and frees s_row for the next call,
+// whose own first barrier lies between a thread's reads of s_tot here and anybody's next write to it.  With ANY the second one
+// also tells whether `flag` was set in any thread.
+template <int N, int LD, bool ANY = false>
+__device__ __forceinline__ bool frame_reduce(double (&acc)[N], double (*s_row)[LD], double* s_tot, bool flag = false) {
+  static_assert(N <= LD, "a row of s_row holds the N terms");
+  const int tid = threadIdx.x;
+#pragma unroll
+  for (int k = 0; k < N; ++k) acc[k] = refine_row_sum(acc[k]);
+  if ((tid & (MAP_ROW - 1)) == 0) {
+#pragma unroll
+    for (int k = 0; k < N; ++k) s_row[tid / MAP_ROW][k] = acc[k];
+  }
+  __syncthreads();
+  if (tid < N) {
+    double s = s_row[0][tid];
+#pragma unroll
+    for (int w = 1; w < MAP_WG / MAP_ROW; ++w) s += s_row[w][tid];
+    s_tot[tid] = s;
+  }
+  bool any = false;
+  if (ANY) any = __syncthreads_or(flag) != 0;
+  else __syncthreads();
+#pragma unroll
+  for (int k = 0; k < N; ++k) acc[k] = s_tot[k];
+  return any;
+}
+
+// The census of the two refinements' statistics kernels, by ONE workgroup of NT threads: int32 n_items, n_obs, by_status[6];
+// double cost_before, cost_after over the items of status 0.  Thread t takes the items t, t + NT, ... in that order, thread 0 adds
+// the NT partial sums in thread order: a fixed order, whatever the scheduling, and no float atomics.  n_obs: *obs_total, or with
+// SUM_OBS the sum of obs_each[item].
+template <int NT, bool SUM_OBS>
+__device__ __forceinline__ void status_census(int n_items, const int32_t* status, const double* cost, const int* obs_each,
+                                              const int* obs_total, void* stats) {
+  constexpr int NC = SUM_OBS ? 7 : 6;
+  __shared__ double s_c0[NT], s_c1[NT];
+  __shared__ int s_n[NC];
+  if (threadIdx.x < NC) s_n[threadIdx.x] = 0;
+  __syncthreads();
+  int n[NC] = {};
+  double c0 = 0.0, c1 = 0.0;
+  for (int j = threadIdx.x; j < n_items; j += NT) {
+    const int s = status[j];
+#pragma unroll
+    for (int k = 0; k < 6; ++k) n[k] += s == k;
+    if (SUM_OBS) n[NC - 1] += obs_each[j];
+    if (s == 0) { c0 += cost[2 * (size_t)j]; c1 += cost[2 * (size_t)j + 1]; }
+  }
+  s_c0[threadIdx.x] = c0; s_c1[threadIdx.x] = c1;
+#pragma unroll
+  for (int k = 0; k < NC; ++k) if (n[k]) atomicAdd(&s_n[k], n[k]);
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    double t0 = 0.0, t1 = 0.0;
+    for (int t = 0; t < NT; ++t) { t0 += s_c0[t]; t1 += s_c1[t]; }
+    int* si = static_cast<int*>(stats);
+    si[0] = n_items; si[1] = SUM_OBS ? s_n[NC - 1] : *obs_total;
+    for (int k = 0; k < 6; ++k) si[2 + k] = s_n[k];
+    double* sd = reinterpret_cast<double*>(si + 8);
+    sd[0] = t0; sd[1] = t1;
+  }
+}
 
 // ---- motion-only refinement of the frames' poses on the same cost (map_pose_refine.hip, vo_map_refine_poses*) --------
 struct MapPoseWs {
@@ -589,12 +697,9 @@ MapPoseWs map_pose_layout(void* base, int n_frames, int n_max, bool with_lookup)
 struct MapPoseArgs {
   const int32_t* ent;                   // [n_frames][n_max]: -1 or the entry (also -1 behind the live rows)
   int* n_obs; double* cost;             // of the workspace
-  const float* pts; const int* hdr; int cap, bound;   // the map
-  const float* uv; size_t uv_stride;    // pixels between frames
-  int n_max, n_frames;
-  const float* T_in; float* T_out;      // [n_frames][16] column-major, p_cam = T p_map; may be the same array
+  MapView v;                            // (v.T16: the poses that come in)
+  float* T_out;                         // [n_frames][16] the poses that go out; may be the same array as v.T16
   const uint8_t* fixed;                 // [n_frames] or null
-  double K[9];                          // column-major
   int n_rounds, min_obs;
   double huber, damping;
   int32_t* status;                      // [n_frames]
@@ -607,7 +712,7 @@ hipError_t launch_map_pose_refine(hipStream_t st, const MapPoseArgs& a);
 // ---- joint adjustment of poses and points by matrix-free Schur PCG (map_bundle.hip, vox_map_bundle*) ----------------
 // The observation lists of the point half alone (memset, count, offsets, scan, scatter, order): what launch_map_refine runs
 // before its refinement kernel, for callers that traverse the lists themselves.
-hipError_t launch_map_refine_lists(hipStream_t st, const MapRefineArgs& a);
+hipError_t launch_map_refine_lists(hipStream_t st, const MapRefineWs& w, int n_frames, int n_max, int bound);
 // the control block of a call: written by the one-workgroup launches (and `bad` by whoever meets a pivot that is not > 0)
 struct MapBundleCtl {
   double lambda, cost_cur, cost_start, rz, rr0, rr;
@@ -635,11 +740,9 @@ MapBundleWs map_bundle_layout(void* base, int n_frames, int bound);
 struct MapBundleArgs {
   MapRefineWs l;                        // the lookup's entries and the ordered lists (map_refine_layout)
   MapBundleWs w;
-  float* pts; const int* hdr; int cap, bound;         // the map
-  const float* uv; size_t uv_stride;
-  int n_max, n_frames;
-  float* T16; const uint8_t* fixed;
-  double K[9];                          // column-major
+  MapView v;
+  float* T_out;                         // [n_frames][16] the free frames' poses go back here: the array of v.T16
+  const uint8_t* fixed;
   int n_rounds, n_cg, min_obs_pose, min_obs_point;
   double cg_tol, lambda0, huber;
   int32_t *pose_status_out, *point_status_out;        // or null
@@ -662,11 +765,8 @@ MapCullWs map_cull_layout(void* base, int bound);
 struct MapCullArgs {
   MapRefineWs l;                        // the lookup's entries and the ordered lists (map_refine_layout)
   MapCullWs w;
-  float *pts, *app; int* hdr; int cap, bound;         // the map
-  const float* uv; size_t uv_stride;
-  int n_max, n_frames;
-  const float* T16;
-  double K[9];                          // column-major
+  MapView v;
+  float* app;                           // the map's appearances, compacted with its points
   int min_obs, min_frames, drop_unseen, dry_run;
   double max_mean_sq, max_sq, cos_thr;  // squared thresholds (0: off); cos_thr means something when parallax != 0
   int parallax;

@@ -768,47 +768,77 @@ VO_HD TriConst tri_constants(const float K[9], const Pose& X) {
   return c;
 }
 
+// ---- the map's observation model: ONE copy for map_refine.hip, map_pose_refine.hip, map_bundle.hip and map_cull.hip (and the host) ----
+// One observation of the point p (map frame) at the pose T (R column-major, then t; float32 or double, widened entry by entry), all in
+// double: p_cam = R p + t, q = K p_cam (K column-major, the full matrix), e = (q0 / q2, q1 / q2) - (mu, mv), j = de / dp_cam =
+// (K row 0 - u K row 2, K row 1 - v K row 2) / q2, w = min(1, huber / |e|) (huber == 0: 1) and rho(e).  The four files rely on
+// these operations in this order giving the same bits everywhere: a change here changes refine, pose refine, bundle and cull together.
+struct MapObs {
+  double pc[3], e0, e1, j0[3], j1[3], w, rho;
+  VO_HD bool front() const { return pc[2] > 0.0; }          // the only gate: camera z > 0 (a NaN is not)
+};
+template <class S>
+VO_HD void map_obs(const double K[9], const S T[12], const double p[3], double mu, double mv, double huber, MapObs& o) {
+  double q[3];
+  for (int r = 0; r < 3; ++r)
+    o.pc[r] = __builtin_fma((double)T[r + 6], p[2], __builtin_fma((double)T[r + 3], p[1], __builtin_fma((double)T[r], p[0], (double)T[9 + r])));
+  for (int r = 0; r < 3; ++r) q[r] = __builtin_fma(K[r + 6], o.pc[2], __builtin_fma(K[r + 3], o.pc[1], K[r] * o.pc[0]));
+  const double iz = 1.0 / q[2];
+  const double u = q[0] * iz, v = q[1] * iz;
+  o.e0 = u - mu; o.e1 = v - mv;
+  for (int c = 0; c < 3; ++c) { o.j0[c] = (K[3 * c] - u * K[2 + 3 * c]) * iz; o.j1[c] = (K[1 + 3 * c] - v * K[2 + 3 * c]) * iz; }
+  const double r2 = o.e0 * o.e0 + o.e1 * o.e1;
+  o.w = 1.0; o.rho = r2;
+  if (huber > 0.0) {
+    const double r = sqrt(r2);
+    if (r > huber) { o.w = huber / r; o.rho = huber * (2.0 * r - huber); }
+  }
+}
+// de / dp = j R: the point's Jacobian
+template <class S>
+VO_HD void map_obs_point_jac(const MapObs& o, const S T[12], double J0[3], double J1[3]) {
+  for (int c = 0; c < 3; ++c) {
+    J0[c] = __builtin_fma(o.j0[2], (double)T[2 + 3 * c], __builtin_fma(o.j0[1], (double)T[1 + 3 * c], o.j0[0] * (double)T[3 * c]));
+    J1[c] = __builtin_fma(o.j1[2], (double)T[2 + 3 * c], __builtin_fma(o.j1[1], (double)T[1 + 3 * c], o.j1[0] * (double)T[3 * c]));
+  }
+}
+// de / d(t, alpha) = j [I, -[p_cam]x] = [j, p_cam x j]: the pose's Jacobian for the step of T <- v2t(dx) T
+VO_HD void map_obs_pose_jac(const MapObs& o, double J0[6], double J1[6]) {
+  const double* pc = o.pc;
+  for (int c = 0; c < 3; ++c) { J0[c] = o.j0[c]; J1[c] = o.j1[c]; }
+  J0[3] = J0[2] * pc[1] - J0[1] * pc[2]; J0[4] = J0[0] * pc[2] - J0[2] * pc[0]; J0[5] = J0[1] * pc[0] - J0[0] * pc[1];
+  J1[3] = J1[2] * pc[1] - J1[1] * pc[2]; J1[4] = J1[0] * pc[2] - J1[2] * pc[0]; J1[5] = J1[1] * pc[0] - J1[0] * pc[1];
+}
+// acc += w J^T J (upper triangle row by row, N (N + 1) / 2 sums), then w J^T e (N sums), then, with RHO, rho: N = 3 is the layout of
+// NREF, N = 6 that of NPOSE
+template <int N, bool RHO = true>
+VO_HD void accum_normal(const MapObs& o, const double (&J0)[N], const double (&J1)[N], double* acc) {
+  constexpr int NH = N * (N + 1) / 2;
+  int k = 0;
+#pragma unroll
+  for (int a = 0; a < N; ++a) {
+    const double w0 = o.w * J0[a], w1 = o.w * J1[a];
+#pragma unroll
+    for (int b = a; b < N; ++b) acc[k++] += __builtin_fma(w1, J1[b], w0 * J0[b]);
+    acc[NH + a] += __builtin_fma(w1, o.e1, w0 * o.e0);
+  }
+  if (RHO) acc[NH + N] += o.rho;
+}
+
 // ---- structure-only refinement of a landmark (map_refine.hip; both functions also compile for the host) ----------
 // sums of one evaluation: 0..5 H upper triangle row by row ((0,0),(0,1),(0,2),(1,1),(1,2),(2,2)), 6..8 b, 9 the cost
 constexpr int NREF = 10;
 
-// One observation's terms at the point p (map frame), all in double: p_cam = R p + t (Rt: R column-major, then t, the
-// caller's float32 bits), q = K p_cam (K column-major, the full matrix), e = (q0 / q2, q1 / q2) - (mu, mv); J = de / dp;
-// w = min(1, huber / |e|) (huber == 0: 1); acc += w J^T J, w J^T e, rho(e).  Returns whether camera z is > 0 (a NaN is not).
+// One observation's terms at the point p (Rt: the frame's pose, the caller's float32 bits): J = de / dp; acc += w J^T J, w J^T e,
+// rho(e).  Returns whether camera z is > 0 (a NaN is not).
 VO_HD bool map_refine_term(const double K[9], const float Rt[12], const double p[3], double mu, double mv, double huber,
                            double acc[NREF]) {
-  double pc[3], q[3];
-  for (int r = 0; r < 3; ++r)
-    pc[r] = __builtin_fma((double)Rt[r + 6], p[2], __builtin_fma((double)Rt[r + 3], p[1], __builtin_fma((double)Rt[r], p[0], (double)Rt[9 + r])));
-  for (int r = 0; r < 3; ++r) q[r] = __builtin_fma(K[r + 6], pc[2], __builtin_fma(K[r + 3], pc[1], K[r] * pc[0]));
-  const double iz = 1.0 / q[2];
-  const double u = q[0] * iz, v = q[1] * iz;
-  const double e0 = u - mu, e1 = v - mv;
-  // de / dp_cam = (K row 0 - u K row 2, K row 1 - v K row 2) / q2, then times R
-  double j0[3], j1[3], J0[3], J1[3];
-  for (int c = 0; c < 3; ++c) { j0[c] = (K[3 * c] - u * K[2 + 3 * c]) * iz; j1[c] = (K[1 + 3 * c] - v * K[2 + 3 * c]) * iz; }
-  for (int c = 0; c < 3; ++c) {
-    J0[c] = __builtin_fma(j0[2], (double)Rt[2 + 3 * c], __builtin_fma(j0[1], (double)Rt[1 + 3 * c], j0[0] * (double)Rt[3 * c]));
-    J1[c] = __builtin_fma(j1[2], (double)Rt[2 + 3 * c], __builtin_fma(j1[1], (double)Rt[1 + 3 * c], j1[0] * (double)Rt[3 * c]));
-  }
-  const double r2 = e0 * e0 + e1 * e1;
-  double w = 1.0, rho = r2;
-  if (huber > 0.0) {
-    const double r = sqrt(r2);
-    if (r > huber) { w = huber / r; rho = huber * (2.0 * r - huber); }
-  }
-  const double w0[3] = {w * J0[0], w * J0[1], w * J0[2]}, w1[3] = {w * J1[0], w * J1[1], w * J1[2]};
-  acc[0] += __builtin_fma(w1[0], J1[0], w0[0] * J0[0]);
-  acc[1] += __builtin_fma(w1[0], J1[1], w0[0] * J0[1]);
-  acc[2] += __builtin_fma(w1[0], J1[2], w0[0] * J0[2]);
-  acc[3] += __builtin_fma(w1[1], J1[1], w0[1] * J0[1]);
-  acc[4] += __builtin_fma(w1[1], J1[2], w0[1] * J0[2]);
-  acc[5] += __builtin_fma(w1[2], J1[2], w0[2] * J0[2]);
-  acc[6] += __builtin_fma(w1[0], e1, w0[0] * e0);
-  acc[7] += __builtin_fma(w1[1], e1, w0[1] * e0);
-  acc[8] += __builtin_fma(w1[2], e1, w0[2] * e0);
-  acc[9] += rho;
-  return pc[2] > 0.0;
+  MapObs o;
+  double J0[3], J1[3];
+  map_obs(K, Rt, p, mu, mv, huber, o);
+  map_obs_point_jac(o, Rt, J0, J1);
+  accum_normal(o, J0, J1, acc);
+  return o.front();
 }
 
 // x = H^-1 b for the symmetric 3x3 H (upper triangle as above) by an LDL^T in natural order, in double.  False when a pivot is
@@ -834,39 +864,17 @@ VO_HD bool ldlt3_solve(const double H[6], const double b[3], double x[3]) {
 // sums of one evaluation: 0..20 H upper triangle row by row ((0,0) .. (0,5), (1,1) .. (5,5)), 21..26 b, 27 the cost
 constexpr int NPOSE = 28;
 
-// One observation's terms at the pose T (R column-major, then t, in double): p_cam = R p + t with p the entry's float32 point
-// widened, q = K p_cam, e = (q0 / q2, q1 / q2) - (mu, mv); J = de / dp_cam [I, -[p_cam]x] for the step (t, alpha) of
-// T <- v2t(dx) T; w = min(1, huber / |e|) (huber == 0: 1); acc += w J^T J, w J^T e, rho(e).  Returns whether camera z is > 0.
+// One observation's terms at the pose T (R column-major, then t, in double) with p the entry's float32 point widened: J =
+// de / d(t, alpha); acc += w J^T J, w J^T e, rho(e).  Returns whether camera z is > 0.
 VO_HD bool map_pose_term(const double K[9], const double T[12], const float pt[3], double mu, double mv, double huber,
                          double acc[NPOSE]) {
   const double p[3] = {(double)pt[0], (double)pt[1], (double)pt[2]};
-  double pc[3], q[3];
-  for (int r = 0; r < 3; ++r) pc[r] = __builtin_fma(T[r + 6], p[2], __builtin_fma(T[r + 3], p[1], __builtin_fma(T[r], p[0], T[9 + r])));
-  for (int r = 0; r < 3; ++r) q[r] = __builtin_fma(K[r + 6], pc[2], __builtin_fma(K[r + 3], pc[1], K[r] * pc[0]));
-  const double iz = 1.0 / q[2];
-  const double u = q[0] * iz, v = q[1] * iz;
-  const double e0 = u - mu, e1 = v - mv;
+  MapObs o;
   double J0[6], J1[6];
-  for (int c = 0; c < 3; ++c) { J0[c] = (K[3 * c] - u * K[2 + 3 * c]) * iz; J1[c] = (K[1 + 3 * c] - v * K[2 + 3 * c]) * iz; }
-  // j (-[p_cam]x) = p_cam x j
-  J0[3] = J0[2] * pc[1] - J0[1] * pc[2]; J0[4] = J0[0] * pc[2] - J0[2] * pc[0]; J0[5] = J0[1] * pc[0] - J0[0] * pc[1];
-  J1[3] = J1[2] * pc[1] - J1[1] * pc[2]; J1[4] = J1[0] * pc[2] - J1[2] * pc[0]; J1[5] = J1[1] * pc[0] - J1[0] * pc[1];
-  const double r2 = e0 * e0 + e1 * e1;
-  double w = 1.0, rho = r2;
-  if (huber > 0.0) {
-    const double r = sqrt(r2);
-    if (r > huber) { w = huber / r; rho = huber * (2.0 * r - huber); }
-  }
-  int k = 0;
-#pragma unroll
-  for (int a = 0; a < 6; ++a) {
-    const double w0 = w * J0[a], w1 = w * J1[a];
-#pragma unroll
-    for (int b = a; b < 6; ++b) acc[k++] += __builtin_fma(w1, J1[b], w0 * J0[b]);
-    acc[21 + a] += __builtin_fma(w1, e1, w0 * e0);
-  }
-  acc[27] += rho;
-  return pc[2] > 0.0;
+  map_obs(K, T, p, mu, mv, huber, o);
+  map_obs_pose_jac(o, J0, J1);
+  accum_normal(o, J0, J1, acc);
+  return o.front();
 }
 
 // x = H^-1 b for the symmetric 6x6 H (upper triangle as above) by an LDL^T in natural order, in double.  False when a pivot is
@@ -986,6 +994,47 @@ __device__ __forceinline__ int block_rank(bool flag, int* s_wave, int& total) {
   }
   total = tot;
   return off + before;
+}
+
+// exclusive prefix sum of `v` over a workgroup of NT threads (s_wave: NT / 64 ints of LDS); total = the workgroup's sum
+template <int NT>
+__device__ __forceinline__ int block_exclusive_scan(int v, int* s_wave, int& total) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  int incl = v;                                               // inclusive scan inside the wave
+#pragma unroll
+  for (int d = 1; d < 64; d <<= 1) { const int o = __shfl_up(incl, d); if (lane >= d) incl += o; }
+  if (lane == 63) s_wave[wave] = incl;
+  __syncthreads();
+  int off = 0, tot = 0;
+#pragma unroll
+  for (int w = 0; w < NT / 64; ++w) {
+    const int c = s_wave[w];
+    if (w < wave) off += c;
+    tot += c;
+  }
+  total = tot;
+  return off + incl - v;
+}
+
+// in-place exclusive scan of array[0 .. n) by ONE workgroup of NT threads, NT at a time with a carry (any n); returns the sum
+// (s_w: NT / 64 ints of LDS, s_carry: one).  Ends behind a barrier: every thread may read what it wrote.
+template <int NT>
+__device__ __forceinline__ int scan_with_carry(int* array, int n, int* s_w, int* s_carry) {
+  const int tid = threadIdx.x;
+  if (tid == 0) *s_carry = 0;
+  __syncthreads();
+  for (int base = 0; base < n; base += NT) {
+    const int j = base + tid;
+    const int v = j < n ? array[j] : 0;
+    int tot;
+    const int x = block_exclusive_scan<NT>(v, s_w, tot);
+    const int carry = *s_carry;
+    if (j < n) array[j] = carry + x;
+    __syncthreads();
+    if (tid == 0) *s_carry = carry + tot;
+    __syncthreads();
+  }
+  return *s_carry;
 }
 #endif
 
