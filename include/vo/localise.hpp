@@ -99,6 +99,25 @@ inline const char* cull_verdict_name(int verdict) {
   return verdict >= 0 && verdict < 8 ? names[verdict] : "?";
 }
 
+//! voe_map_grow: which tracks of unmapped rows become landmarks.  A threshold of 0 switches its test off;
+//! max_added 0 means one per row of the window.
+struct GrowOptions {
+  int n_rounds = 5;
+  int min_obs = 3;
+  int min_frames = 3;
+  float huber_px = 0;
+  float damping = 0;
+  float max_rms_px = 2.f;
+  float max_err_px = 0;
+  float min_parallax_deg = 2.f;
+  int max_added = 0;
+  bool dry_run = false;
+};
+inline const char* grow_verdict_name(int verdict) {
+  static const char* names[] = {"ADDED", "FEW_OBS", "FEW_FRAMES", "DEGENERATE", "NOT_FINITE", "BEHIND", "HIGH_ERROR", "LOW_PARALLAX", "NO_ROOM"};
+  return verdict >= 0 && verdict < 9 ? names[verdict] : "?";
+}
+
 //! voe_map_covis: which entries every frame sees and how many every two frames share
 struct Covisibility {
   size_t n_frames = 0, n_words = 0;
@@ -360,6 +379,27 @@ class DeviceMap {
     check(voe_map_cull(h_, (int)w.F, cam.cameraMatrix().data(), w.uv.data(), w.app.data(), w.n.data(), (int)w.cap, w.T.data(), &prm,
                        verdict && M ? verdict->data() : nullptr, remap && M ? remap->data() : nullptr,
                        entries && M ? entries->data() : nullptr, &st), "voe_map_cull");
+    return st;
+  }
+
+  //! landmarks added from the frames (voe_map_grow): the rows that find no entry are grouped into tracks by equal appearance, every
+  //! track is triangulated from all its rows at the poses (p_cam = T p_map, one per frame) given, refined, judged by the cull's
+  //! tests and, when it passes, appended.  *rows receives, frame by frame (the longest frame's length each), the entry every row
+  //! is found at afterwards (-1: no row or a NaN; -2 - t: its track t was not added), *tracks one record per track.  With
+  //! opt.dry_run the map stays as it is.
+  voe_map_grow_stats grow(const Camera& cam, const std::vector<Vector2fVector>& pixels, const std::vector<Vector10fVector>& appearances,
+                          const IsometryVector& poses, const GrowOptions& opt = GrowOptions(), std::vector<int32_t>* rows = nullptr,
+                          std::vector<voe_map_grow_track>* tracks = nullptr) {
+    const Window w = pack("DeviceMap::grow", pixels, appearances, poses);
+    const size_t R = w.F * w.cap;
+    if (rows) rows->assign(R, -1);
+    if (tracks) tracks->assign(R, voe_map_grow_track{});
+    const voe_map_grow_params prm{opt.n_rounds, opt.min_obs, opt.min_frames, opt.huber_px, opt.damping, opt.max_rms_px, opt.max_err_px,
+                                  opt.min_parallax_deg, opt.max_added, opt.dry_run ? 1 : 0};
+    voe_map_grow_stats st{};
+    check(voe_map_grow(h_, (int)w.F, cam.cameraMatrix().data(), w.uv.data(), w.app.data(), w.n.data(), (int)w.cap, w.T.data(), &prm,
+                       rows && R ? rows->data() : nullptr, tracks && R ? tracks->data() : nullptr, tracks && R ? (int)R : 0, &st), "voe_map_grow");
+    if (tracks) tracks->resize((size_t)st.n_tracks < R ? (size_t)st.n_tracks : R);
     return st;
   }
 

@@ -685,6 +685,38 @@ class Map:
         return dict(verdict=verdict[:k].copy(), remap=remap[:k].copy(), entries=entries[:k].copy(), stats=st.as_dict())
 
 
+    # ---- landmarks added from the frames' unmapped tracks (voe_map_grow*, include/vo_map_grow.h) ----
+    def grow_batch_dev(self, camera: Camera, n_frames, d_uv, uv_stride, d_app, app_stride, n_max, d_n, d_T16, params: "MapGrowParams",
+                       d_row_out, d_track_out, track_cap, d_stats):
+        """voe_map_grow_batch_dev on device pointers (ints; d_n and the two outputs may be None; strides in pixels / rows):
+        enqueues and returns.  d_row_out: n_frames x n_max int32; d_track_out: track_cap x 80 bytes (MapGrowTrack); d_stats: 96
+        bytes (MapGrowStats)."""
+        v = lambda d: C.c_void_p(d) if d else None
+        _chk(self.lib.voe_map_grow_batch_dev(self.h, C.c_int(n_frames), _ptr(_colmajor(camera._K, 3)), v(d_uv), C.c_size_t(uv_stride),
+                                             v(d_app), C.c_size_t(app_stride), C.c_int(n_max), v(d_n), v(d_T16), C.byref(params),
+                                             v(d_row_out), v(d_track_out), C.c_int(track_cap), v(d_stats)))
+
+    def grow(self, camera: Camera, frames, poses, n_rounds=5, min_obs=3, min_frames=3, huber_px=0.0, damping=0.0, max_rms_px=2.0,
+             max_err_px=0.0, min_parallax_deg=2.0, max_added=0, dry_run=False, track_cap=None):
+        """voe_map_grow: the rows of `frames` (as in refine) that find no entry are grouped into tracks by equal appearance, every
+        track is triangulated from all its rows at the poses (4x4, p_cam = T p_map) given, refined and judged by the cull's
+        tests; the tracks that pass are appended to the map.  Returns dict(rows (F, n_max) int32: the entry every row is found
+        at afterwards, -1 for a dead or NaN row, -2 - t for an open row whose track t was not added; tracks: a structured array
+        of MapGrowTrack records (MAP_GROW_VERDICT names the codes; track_cap: room for that many, default one per row); stats
+        dict: MAP_GROW_STATUS names stats["status"])."""
+        F, cap, uv, app, n, T, _ = self._window(frames, poses, None)
+        rows = np.full((F, max(cap, 1)), -9, np.int32)
+        track_cap = max(F * cap, 1) if track_cap is None else int(track_cap)
+        tracks = np.zeros(max(track_cap, 1), MAP_GROW_TRACK_DTYPE)
+        st = MapGrowStats()
+        prm = MapGrowParams(int(n_rounds), int(min_obs), int(min_frames), float(huber_px), float(damping), float(max_rms_px), float(max_err_px),
+                            float(min_parallax_deg), int(max_added), int(bool(dry_run)))
+        _chk(self.lib.voe_map_grow(self.h, C.c_int(F), _ptr(_colmajor(camera._K, 3)), _ptr(uv[:, :cap]) if cap else None,
+                                   _ptr(app[:, :cap]) if cap else None, _ptr(n), C.c_int(cap), _ptr(T), C.byref(prm),
+                                   _ptr(rows) if cap else None, C.c_void_p(tracks.ctypes.data) if track_cap else None, C.c_int(track_cap),
+                                   C.byref(st)))
+        return dict(rows=rows[:, :cap].copy(), tracks=tracks[: min(st.n_tracks, track_cap)].copy(), stats=st.as_dict())
+
     # ---- two maps: alignment by 3-point similarity RANSAC and the merge (voe_map_align*, voe_map_merge*, include/vo_map_align.h) ----
     def size_bound(self):
         """voe_map_size_bound: the host's bound of the size (what sizes the arrays of align_dev / merge_dev); no device work"""
@@ -916,6 +948,41 @@ MAP_CULL_ENTRY_DTYPE = np.dtype([("verdict", "<i4"), ("n_obs", "<i4"), ("n_frame
 assert MAP_CULL_ENTRY_DTYPE.itemsize == 48
 MAP_CULL_VERDICT = ("KEPT", "UNSEEN", "FEW_OBS", "FEW_FRAMES", "NOT_FINITE", "BEHIND", "HIGH_ERROR", "LOW_PARALLAX")   # VOE_MAP_CULL_*
 MAP_CULL_STATUS = ("OK", "NOTHING_DROPPED")
+
+
+class MapGrowParams(C.Structure):
+    """voe_map_grow_params (include/vo_map_grow.h)"""
+    _fields_ = [("n_rounds", C.c_int32), ("min_obs", C.c_int32), ("min_frames", C.c_int32), ("huber_px", C.c_float), ("damping", C.c_float),
+                ("max_rms_px", C.c_float), ("max_err_px", C.c_float), ("min_parallax_deg", C.c_float), ("max_added", C.c_int32),
+                ("dry_run", C.c_int32)]
+
+
+class MapGrowTrack(C.Structure):
+    """voe_map_grow_track (include/vo_map_grow.h): one track"""
+    _fields_ = [("verdict", C.c_int32), ("n_obs", C.c_int32), ("n_frames", C.c_int32), ("entry", C.c_int32), ("first_key", C.c_int32),
+                ("refined", C.c_int32), ("reserved", C.c_int32 * 2), ("xyz", C.c_float * 3), ("reserved2", C.c_int32), ("mean_sq_px", C.c_double),
+                ("max_sq_px", C.c_double), ("min_z", C.c_double), ("cos_parallax", C.c_double)]
+
+
+class MapGrowStats(C.Structure):
+    """voe_map_grow_stats (include/vo_map_grow.h)"""
+    _fields_ = [("status", C.c_int32), ("n_live", C.c_int32), ("n_hits", C.c_int32), ("n_nan", C.c_int32), ("n_open", C.c_int32),
+                ("n_tracks", C.c_int32), ("n_added", C.c_int32), ("n_before", C.c_int32), ("n_after", C.c_int32), ("by_verdict", C.c_int32 * 12),
+                ("reserved", C.c_int32 * 3)]
+
+    def as_dict(self):
+        d = {k: getattr(self, k) for k, _ in self._fields_ if k not in ("by_verdict", "reserved")}
+        d["by_verdict"] = list(self.by_verdict)
+        return d
+
+
+assert C.sizeof(MapGrowParams) == 40 and C.sizeof(MapGrowTrack) == 80 and C.sizeof(MapGrowStats) == 96
+MAP_GROW_TRACK_DTYPE = np.dtype([("verdict", "<i4"), ("n_obs", "<i4"), ("n_frames", "<i4"), ("entry", "<i4"), ("first_key", "<i4"), ("refined", "<i4"),
+                                 ("reserved", "<i4", (2,)), ("xyz", "<f4", (3,)), ("reserved2", "<i4"), ("mean_sq_px", "<f8"), ("max_sq_px", "<f8"),
+                                 ("min_z", "<f8"), ("cos_parallax", "<f8")])
+assert MAP_GROW_TRACK_DTYPE.itemsize == 80
+MAP_GROW_VERDICT = ("ADDED", "FEW_OBS", "FEW_FRAMES", "DEGENERATE", "NOT_FINITE", "BEHIND", "HIGH_ERROR", "LOW_PARALLAX", "NO_ROOM")   # VOE_MAP_GROW_*
+MAP_GROW_STATUS = ("OK", "NO_OPEN_ROWS", "NOTHING_ADDED")
 
 
 class MapAlignParams(C.Structure):

@@ -1,5 +1,5 @@
 // capi_map.hip -- the map's half of the extern "C" boundary (vo_hip.h: vo_map_*; vo_map_adjust.h, vo_map_bundle.h, vo_map_cull.h,
-// vo_map_align.h, vo_map_covis.h).  Host-side plumbing only, like capi.hip: no kernel lives here.
+// vo_map_align.h, vo_map_covis.h, vo_map_grow.h).  Host-side plumbing only, like capi.hip: no kernel lives here.
 #include <limits.h>
 #include <string.h>
 
@@ -28,6 +28,7 @@ struct vo_map {
   DevBuf merge_ws;              // voe_map_merge* (on dst): the lookup's entries, the staging area of the misses
   DevBuf covis_ws;              // voe_map_covis*: the lookup's pairs, counts and entries, the population counts per frame and per block of words
   DevBuf window_ws;             // voe_map_window*: the counts against the query row and against the union, the order, the union
+  DevBuf grow_ws;               // voe_map_grow*: the open rows, the tracks' private table, verdicts, the staging area (the lists live in ref_ws)
 };
 
 constexpr int MAP_MAX_ENTRIES = 1 << 29;      // 2.5 x that many table slots still fit 32 bits
@@ -120,7 +121,7 @@ int vo_map_destroy(vo_map* m) {
   map_free_arrays(m->d);
   if (m->d.hdr) (void)hipFree(m->d.hdr);
   if (m->hist) (void)hipFree(m->hist);
-  m->scratch.release(); m->up_xyz.release(); m->up_app.release(); m->look_ws.release(); m->loc_ws.release(); m->ref_ws.release(); m->pose_ws.release(); m->bundle_ws.release(); m->cull_ws.release(); m->align_ws.release(); m->merge_ws.release(); m->covis_ws.release(); m->window_ws.release();
+  m->scratch.release(); m->up_xyz.release(); m->up_app.release(); m->look_ws.release(); m->loc_ws.release(); m->ref_ws.release(); m->pose_ws.release(); m->bundle_ws.release(); m->cull_ws.release(); m->align_ws.release(); m->merge_ws.release(); m->covis_ws.release(); m->window_ws.release(); m->grow_ws.release();
   if (m->solver) (void)vo_picp_destroy(m->solver);
   delete m;
   return VO_OK;
@@ -850,6 +851,92 @@ int voe_map_cull(vo_map* m, int n_frames, const float K[9], const float* uv, con
   }
   VO_HIP_CHECK(hipStreamSynchronize(c->stream));
   if (!m->replayable && !params->dry_run) m->size_ub = stats_out->n_kept;
+  return VO_OK;
+}
+
+// ---- landmarks added from the frames' unmapped tracks (map_grow.hip; include/vo_map_grow.h) ---------------------------------
+static_assert(sizeof(voe_map_grow_params) == 40 && sizeof(voe_map_grow_track) == 80 && sizeof(voe_map_grow_stats) == 96,
+              "the records of include/vo_map_grow.h as the kernels write them");
+
+int voe_map_grow_batch_dev(vo_map* m, int n_frames, const float K[9], const float* d_uv, size_t uv_stride, const float* d_app,
+                           size_t app_stride, int n_max, const int* d_n, const float* d_T16, const voe_map_grow_params* p,
+                           int32_t* d_row_out, voe_map_grow_track* d_track_out, int track_cap, voe_map_grow_stats* d_stats) {
+  VO_MAP_LIVE(m);
+  const char* fn = "voe_map_grow_batch_dev";
+  if (!(K && p && d_T16 && d_stats)) return vo_fail(VO_ERR_INVALID_ARG, "%s: null argument", fn);
+  const MapFrames f{n_frames, K, d_uv, uv_stride, d_app, app_stride, n_max, d_n};
+  const MapRounds rounds{p->n_rounds, INT_MAX, p->min_obs, 2, p->huber_px, &p->damping};
+  if (int r = map_frames_check(fn, f, d_stats, &rounds)) return r;
+  if (int r = map_grow_check(fn, p, d_track_out, track_cap)) return r;
+  vo_ctx* c = m->ctx;
+  const size_t rows = (size_t)n_frames * (size_t)n_max;
+  if (rows > (size_t)MAP_MAX_ENTRIES) return vo_fail(VO_ERR_INVALID_ARG, "%s: more than 2^29 rows in one call (every row may be a track of its own)", fn);
+  const int R = (int)(rows ? rows : 1);
+  const int room = map_grow_room(p, n_frames, n_max), stage = room < R ? room : R;
+  const bool dry = p->dry_run != 0;
+  const unsigned tcap = map_tcap_for(R);
+  // the workspaces: the lists over the TRACKS (bounded by the rows), the call's own, the lookup's and the append's scratch
+  const size_t need_l = map_refine_layout(nullptr, n_frames, n_max, R).bytes, need_g = map_grow_layout(nullptr, rows, stage, tcap).bytes;
+  if (int r = window_growth_check(m, fn, f, {{m->ref_ws.cap, need_l}, {m->grow_ws.cap, need_g}, {m->look_ws.cap, n_max > 0 ? lookup_scratch_bytes(f, false) : 0},
+                                             {m->scratch.cap, sizeof(int) * map_scratch_ints(stage)}})) return r;      // (before anything is enqueued)
+  if (int r = set_device(c)) return r;
+  if (!dry)
+    if (int r = map_reserve(m, room)) return r;               // the map grows here, on the host, or the capture is refused
+  VO_HIP_CHECK(m->ref_ws.ensure(need_l, c->stream));
+  VO_HIP_CHECK(m->grow_ws.ensure(need_g, c->stream));
+  VO_HIP_CHECK(m->scratch.ensure(sizeof(int) * map_scratch_ints(stage), c->stream));
+  MapGrowArgs a{};
+  a.l = map_refine_layout(m->ref_ws.p, n_frames, n_max, R);
+  a.w = map_grow_layout(m->grow_ws.p, rows, stage, tcap);
+  if (int r = lookup_window(m, f, a.l.pairs, a.l.n_hits, a.w.hit)) return r;      // the one lookup of the map
+  a.v.pts = nullptr; a.v.hdr = a.w.priv.hdr; a.v.cap = R; a.v.bound = R;          // (the tracks, not the map: MapGrowArgs)
+  fill_frames(a.v, f, d_T16);
+  a.app = d_app; a.app_stride = 10 * app_stride; a.d_n = d_n;
+  a.map_hdr = m->d.hdr; a.map_cap = m->d.cap;
+  if (!invert_k(K, a.Kinv)) return vo_fail(VO_ERR_INVALID_ARG, "%s: K is singular", fn);      // (never: map_frames_check asked)
+  a.n_rounds = p->n_rounds; a.min_obs = p->min_obs; a.min_frames = p->min_frames; a.huber = p->huber_px; a.damping = p->damping;
+  a.max_mean_sq = (double)p->max_rms_px * (double)p->max_rms_px;
+  a.max_sq = (double)p->max_err_px * (double)p->max_err_px;
+  a.parallax = p->min_parallax_deg > 0.f;
+  a.cos_thr = a.parallax ? cos((double)p->min_parallax_deg * 3.14159265358979323846 / 180.0) : 1.0;
+  a.max_added = room; a.dry_run = dry; a.track_cap = track_cap;
+  a.row_out = d_row_out; a.track_out = d_track_out; a.stats = d_stats;
+  VO_HIP_CHECK(launch_map_grow(c->stream, a, c->n_cu));
+  // the append: vo_map_update_dev's launches on the staging area, returning at once where nothing is added or under dry_run
+  VO_HIP_CHECK(launch_map_update(c->stream, m->d, a.w.stage_pts, a.w.stage_app, stage, a.w.ctl + 3, nullptr, m->scratch.as<int>(), a.w.ctl + 5));
+  VO_HIP_CHECK(launch_map_grow_finish(c->stream, a));
+  if (!dry) {
+    m->size_ub += room;
+    if (c->capturing) m->replayable = true;
+  }
+  return VO_OK;
+}
+
+int voe_map_grow(vo_map* m, int n_frames, const float K[9], const float* uv, const float* app, const int* n_rows, int n_max,
+                 const float* T16, const voe_map_grow_params* params, int32_t* row_out, voe_map_grow_track* track_out, int track_cap,
+                 voe_map_grow_stats* stats_out) {
+  VO_MAP_LIVE(m);
+  vo_ctx* c = m->ctx;
+  VO_NOT_CAPTURING(c);
+  VO_REQUIRE(K && T16 && params && stats_out, "null argument");
+  VO_REQUIRE(track_cap >= 0 && !(track_out && track_cap == 0), "bad track_cap");
+  MapFrames f;
+  if (int r = upload_window(__func__, m, MapFrames{n_frames, K, uv, 0, app, 0, n_max, n_rows}, T16, nullptr, nullptr, &f)) return r;
+  const size_t rows = (size_t)n_frames * (size_t)n_max;
+  VO_HIP_CHECK(c->out[0].ensure(sizeof(int32_t) * (rows ? rows : 1), c->stream));
+  VO_HIP_CHECK(c->out[1].ensure(sizeof(voe_map_grow_track) * (size_t)(track_cap > 0 ? track_cap : 1), c->stream));
+  VO_HIP_CHECK(c->out[2].ensure(sizeof(voe_map_grow_stats) + 16, c->stream));
+  VO_HIP_CHECK(hipStreamSynchronize(c->stream));              // the host arrays may go away after the call
+  if (track_out) VO_HIP_CHECK(hipMemsetAsync(c->out[1].p, 0, sizeof(voe_map_grow_track) * (size_t)track_cap, c->stream));      // (records beyond n_tracks)
+  if (int r = voe_map_grow_batch_dev(m, n_frames, K, f.d_uv, f.uv_stride, f.d_app, f.app_stride, n_max, f.d_n, c->in[2].as<float>(), params,
+                                     row_out ? c->out[0].as<int32_t>() : nullptr, track_out ? c->out[1].as<voe_map_grow_track>() : nullptr, track_cap,
+                                     c->out[2].as<voe_map_grow_stats>()))
+    return r;
+  VO_HIP_CHECK(hipMemcpyAsync(stats_out, c->out[2].p, sizeof(voe_map_grow_stats), hipMemcpyDeviceToHost, c->stream));
+  if (row_out && rows) VO_HIP_CHECK(hipMemcpyAsync(row_out, c->out[0].p, sizeof(int32_t) * rows, hipMemcpyDeviceToHost, c->stream));
+  if (track_out) VO_HIP_CHECK(hipMemcpyAsync(track_out, c->out[1].p, sizeof(voe_map_grow_track) * (size_t)track_cap, hipMemcpyDeviceToHost, c->stream));
+  VO_HIP_CHECK(hipStreamSynchronize(c->stream));
+  if (!m->replayable && !params->dry_run) m->size_ub = stats_out->n_after;
   return VO_OK;
 }
 

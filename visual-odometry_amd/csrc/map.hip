@@ -48,6 +48,9 @@ struct MapArgs {
   int* rank;                   // [n_max] scratch: rank of a first occurrence inside its workgroup
   int* counts;                 // [nb + 1] scratch: per-workgroup counts -> offsets
   int nb;
+  const int* guard;            // or null.  A device flag read when the update's launches RUN: where it is 0 all four return at once
+                               // and the map, its table and its header keep every byte (voe_map_grow: a fixed sequence of launches)
+  __device__ __forceinline__ bool off() const { return guard && *guard == 0; }      // (the same in every thread of a launch)
 };
 
 __device__ __forceinline__ Row map_load_row(const float* app, size_t i) {
@@ -60,6 +63,7 @@ __device__ __forceinline__ Row map_load_row(const float* app, size_t i) {
 // Row, map_row_has_nan, map_rows_equal, map_hash and map_home_slot: vo_math.h (the host build of the tests runs them too)
 
 __global__ __launch_bounds__(MB) void map_probe_kernel(MapArgs a) {
+  if (a.off()) return;
   const int n = live_rows(a.d_n, a.n_max);
   const int M = a.hdr[0];
   const int i = blockIdx.x * MB + threadIdx.x;
@@ -95,6 +99,7 @@ __global__ __launch_bounds__(MB) void map_probe_kernel(MapArgs a) {
 
 __global__ __launch_bounds__(MB) void map_flag_kernel(MapArgs a) {
   __shared__ int s_wave[MB / 64];
+  if (a.off()) return;
   const int n = live_rows(a.d_n, a.n_max);
   const int M = a.hdr[0];
   const int i = blockIdx.x * MB + threadIdx.x;
@@ -117,6 +122,7 @@ __global__ __launch_bounds__(MB) void map_flag_kernel(MapArgs a) {
 __global__ __launch_bounds__(1024) void map_scan_kernel(MapArgs a) {
   __shared__ int s_w[16];
   __shared__ int s_carry;
+  if (a.off()) return;
   const int sum = scan_with_carry<1024>(a.counts, a.nb, s_w, &s_carry);
   if (threadIdx.x == 0) {
     const int M = a.hdr[0];
@@ -131,6 +137,7 @@ __global__ __launch_bounds__(1024) void map_scan_kernel(MapArgs a) {
 }
 
 __global__ __launch_bounds__(MB) void map_commit_kernel(MapArgs a) {
+  if (a.off()) return;
   const int n = a.hdr[2];
   const int M = a.hdr[1];
   const int i = blockIdx.x * MB + threadIdx.x;
@@ -386,13 +393,15 @@ static MapArgs map_args(const MapDev& m, const float* c_xyz, const float* c_app,
   a.c_xyz = c_xyz; a.c_app = c_app; a.n_max = n_max; a.d_n = d_n; a.T16 = T16;
   a.nb = (n_max + MB - 1) / MB;
   a.slot = scratch; a.rank = scratch + n_max; a.counts = scratch + 2 * (size_t)n_max;
+  a.guard = nullptr;
   return a;
 }
 
 hipError_t launch_map_update(hipStream_t st, const MapDev& m, const float* c_xyz, const float* c_app, int n_max, const int* d_n,
-                             const float* d_T16, int* d_scratch) {
+                             const float* d_T16, int* d_scratch, const int* d_guard) {
   if (n_max <= 0) return hipSuccess;
-  const MapArgs a = map_args(m, c_xyz, c_app, n_max, d_n, d_T16, d_scratch);
+  MapArgs a = map_args(m, c_xyz, c_app, n_max, d_n, d_T16, d_scratch);
+  a.guard = d_guard;
   hipLaunchKernelGGL(map_probe_kernel, dim3(a.nb), dim3(MB), 0, st, a);
   hipLaunchKernelGGL(map_flag_kernel, dim3(a.nb), dim3(MB), 0, st, a);
   hipLaunchKernelGGL(map_scan_kernel, dim3(1), dim3(1024), 0, st, a);

@@ -88,6 +88,27 @@ static inline int map_frames_check(const char* fn, const MapFrames& f, const voi
   return VO_OK;
 }
 
+// voe_map_grow*: what the call refuses beyond the frames and the rounds (include/vo_map_grow.h), in the order they fire:
+//   1. min_frames < 2 (min_obs < 2 is the rounds' refusal)          2. a threshold negative or not finite, min_parallax_deg >= 180
+//   3. negative max_added or track_cap        4. a track array with track_cap == 0        5. a track array off an 8-byte boundary
+static inline int map_grow_check(const char* fn, const voe_map_grow_params* p, const void* d_track_out, int track_cap) {
+  if (p->min_frames < 2) return vo_fail(VO_ERR_INVALID_ARG, "%s: min_frames must be at least 2", fn);
+  if (!(p->max_rms_px >= 0.f && p->max_rms_px <= 3.402823466e38f)) return vo_fail(VO_ERR_INVALID_ARG, "%s: max_rms_px must be finite and not negative", fn);
+  if (!(p->max_err_px >= 0.f && p->max_err_px <= 3.402823466e38f)) return vo_fail(VO_ERR_INVALID_ARG, "%s: max_err_px must be finite and not negative", fn);
+  if (!(p->min_parallax_deg >= 0.f && p->min_parallax_deg < 180.f)) return vo_fail(VO_ERR_INVALID_ARG, "%s: min_parallax_deg must be in [0, 180)", fn);
+  if (p->max_added < 0) return vo_fail(VO_ERR_INVALID_ARG, "%s: negative max_added", fn);
+  if (track_cap < 0) return vo_fail(VO_ERR_INVALID_ARG, "%s: negative track_cap", fn);
+  if (d_track_out && track_cap == 0) return vo_fail(VO_ERR_INVALID_ARG, "%s: a track array with track_cap == 0", fn);
+  if (!aligned8(d_track_out)) return vo_fail(VO_ERR_INVALID_ARG, "%s: d_track_out must be 8-byte aligned", fn);
+  return VO_OK;
+}
+// the tracks the call may add: max_added, or with 0 every row of the window (at least 1: it sizes arrays)
+static inline int map_grow_room(const voe_map_grow_params* p, int n_frames, int n_max) {
+  const long long rows = (long long)n_frames * n_max;
+  const long long a = p->max_added > 0 ? p->max_added : rows;
+  return (int)(a > 0 ? a : 1);
+}
+
 // A workspace that would have to grow inside a graph capture: growing frees, allocates and waits.  `ws` lists the buffers the
 // call sizes, each with its capacity and what the call needs; `tail` (printf form) names the call that sizes them outside a
 // capture.  The callers ask BEFORE they enqueue anything: a HIP call refused later would invalidate the capture.

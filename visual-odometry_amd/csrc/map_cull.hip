@@ -4,7 +4,7 @@
 // and the frames, the row helpers and the landmark kernels' grid are vo_internal.h's, the scans vo_math.h's.  Launches behind the
 // lookup (which wrote the entry of every query position) and behind the ordered observation lists of map_refine.hip
 // (launch_map_refine_lists, unchanged):
-//   cull_score_kernel      16 lanes per landmark.  Pass 1 strides the ordered list over the lanes (observation k in lane
+//   cull_score_kernel      16 lanes per landmark, the passes by map_score.h's score_list (shared with map_grow.hip).  Pass 1 strides the ordered list over the lanes (observation k in lane
 //                          k mod 16): the sum of |e|^2 by the fixed DPP tree of refine_row_sum, the extrema (refine_row_max /
 //                          _min) and the frame changes by the same four row steps.  Pass 2 (only with the parallax test on)
 //                          visits the pairs in tiles of 16 x 16: a lane holds the unit ray of one observation of tile A and one of tile B, tile B's
@@ -24,6 +24,7 @@
 //   cull_stats_kernel      one workgroup: an integer tally of the verdicts
 // The count of launches is fixed; where nothing is dropped, or under dry_run, scatter, copy, header and rehash return at once.
 #include "vo_internal.h"
+#include "map_score.h"
 
 namespace vo {
 
@@ -33,37 +34,17 @@ constexpr int CLPB = CB / CG;             // landmarks per workgroup and trip
 constexpr int CSTAT = 1024;               // threads of the scan and of the statistics workgroup
 static_assert(CB == MAP_WG && CG == MAP_ROW, "a landmark's lanes are one DPP row; the shared helpers of vo_internal.h count on both sizes");
 
-enum { CV_KEPT = 0, CV_UNSEEN = 1, CV_FEW_OBS = 2, CV_FEW_FRAMES = 3, CV_NOT_FINITE = 4, CV_BEHIND = 5, CV_HIGH_ERROR = 6, CV_LOW_PARALLAX = 7 };
-
 struct CullEntry { int32_t verdict, n_obs, n_frames, reserved; double mean_sq, max_sq, min_z, cos_parallax; };
 static_assert(sizeof(CullEntry) == 48, "voe_map_cull_entry");
 
-__device__ __forceinline__ int cull_ror1(int x) { return __builtin_amdgcn_update_dpp(x, x, 0x121, 0xf, 0xf, false); }
-
-// One observation of the landmark p by map_obs (no Huber weight: rho is |e|^2): |e|^2, camera z, and the unit ray u = d / |d|,
-// d = R^T p_cam.
-__device__ __forceinline__ void cull_obs(const MapCullArgs& a, const double K[9], const double p[3], int key, double& sq, double& z, double u[3]) {
-  float2 m;
-  const int f = a.v.decode(key, m);
-  float Rt[12];
-  a.v.load_pose(f, Rt);
-  MapObs o;
-  map_obs(K, Rt, p, (double)m.x, (double)m.y, 0.0, o);
-  sq = o.rho;
-  z = o.pc[2];
-  double d[3];
-#pragma unroll
-  for (int c = 0; c < 3; ++c) d[c] = __builtin_fma((double)Rt[2 + 3 * c], o.pc[2], __builtin_fma((double)Rt[1 + 3 * c], o.pc[1], (double)Rt[3 * c] * o.pc[0]));
-  const double nrm = sqrt(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]);
-  u[0] = d[0] / nrm; u[1] = d[1] / nrm; u[2] = d[2] / nrm;                 // (|d| == 0: NaN, which pass 1 reports)
-}
-
 __global__ __launch_bounds__(CB) void cull_score_kernel(MapCullArgs a) {
-  const int M = a.v.size(), n_max = a.v.n_max;
+  const int M = a.v.size();
   const int lg = threadIdx.x & (CG - 1), grp = threadIdx.x / CG;
   double K[9];
 #pragma unroll
   for (int k = 0; k < 9; ++k) K[k] = a.v.K[k];
+  const MapScoreThr thr{a.max_mean_sq, a.max_sq, a.cos_thr, a.parallax};
+  const auto load_pose = [&a](int f, float Rt[12]) { a.v.load_pose(f, Rt); };
   const int n_batches = (a.v.bound + CLPB - 1) / CLPB;
   for (int batch = blockIdx.x; batch < n_batches; batch += gridDim.x) {      // (uniform in the workgroup: the ballot below sees whole waves)
     const int e = batch * CLPB + grp;
@@ -72,60 +53,17 @@ __global__ __launch_bounds__(CB) void cull_score_kernel(MapCullArgs a) {
     const int off = in ? a.l.offset(e) : 0;
     double p[3] = {0.0, 0.0, 0.0};
     if (in) { p[0] = (double)a.v.pts[3 * (size_t)e]; p[1] = (double)a.v.pts[3 * (size_t)e + 1]; p[2] = (double)a.v.pts[3 * (size_t)e + 2]; }
-    // ---- pass 1: the sums, the extrema, the frame changes ----
-    double sum = 0.0, mx = 0.0, mz = 1.7976931348623157e308, changes = 0.0;
-    bool bad = false;
-    for (int j = lg; j < n; j += CG) {
-      const int key = a.l.keys[off + j];
-      const int prev = j > 0 ? a.l.keys[off + j - 1] / n_max : -1;
-      double sq, z, u[3];
-      cull_obs(a, K, p, key, sq, z, u);
-      sum += sq;
-      mx = fmax(mx, sq);
-      mz = fmin(mz, z);
-      changes += (key / n_max != prev) ? 1.0 : 0.0;
-      bad |= !(refine_finite(sq) && refine_finite(z) && refine_finite(u[0]) && refine_finite(u[1]) && refine_finite(u[2]));
-    }
-    sum = refine_row_sum(sum);
-    mx = refine_row_max(mx);
-    mz = refine_row_min(mz);
-    const int n_fr = (int)refine_row_sum(changes);           // (whole numbers below 2^31: exact)
-    const bool any_bad = refine_row_any(bad);
-    // ---- pass 2: the smallest u_k . u_l over the pairs ----
-    double cmin = 2.0;
-    if (a.parallax && n >= 2) {                              // (the same in the 16 lanes of a row: the row's DPP moves see all of them)
-      const int tiles = (n + CG - 1) / CG;
-      for (int ta = 0; ta < tiles; ++ta) {
-        const int ka = ta * CG + lg;
-        double ua[3] = {0.0, 0.0, 0.0}, sq, z;
-        if (ka < n) cull_obs(a, K, p, a.l.keys[off + ka], sq, z, ua);
-        for (int tb = ta; tb < tiles; ++tb) {
-          const int kb = tb * CG + lg;
-          double ub[3] = {ua[0], ua[1], ua[2]};
-          if (tb != ta && kb < n) cull_obs(a, K, p, a.l.keys[off + kb], sq, z, ub);
-          int ib = kb < n ? kb : -1;                         // the list position that travels with the ray
-#pragma unroll
-          for (int s = 0; s < CG; ++s) {
-            if (ka < n && ib >= 0 && ib != ka) cmin = fmin(cmin, ua[0] * ub[0] + ua[1] * ub[1] + ua[2] * ub[2]);
-            ub[0] = refine_dpp<0x121>(ub[0]); ub[1] = refine_dpp<0x121>(ub[1]); ub[2] = refine_dpp<0x121>(ub[2]);
-            ib = cull_ror1(ib);
-          }
-        }
-      }
-    }
-    cmin = refine_row_min(cmin);
+    // the statistics and the four tests: map_score.h, shared with map_grow.hip
+    const MapScore sc = score_list(a.v, load_pose, K, p, a.l.keys + off, n, a.parallax != 0, lg);
     if (in && lg == 0) {
-      const double cosp = (a.parallax && n >= 2) ? cmin : 1.0;
-      const double mean = n > 0 ? sum / (double)n : 0.0;
-      if (n == 0) mz = 0.0;
-      int v = CV_KEPT;
+      double mean, cosp;
+      const int judged = score_judge(sc, n, thr, mean, cosp);
+      const double mx = sc.mx, mz = n == 0 ? 0.0 : sc.mz;
+      const int n_fr = sc.n_fr;
+      int v = judged;
       if (n == 0) v = CV_UNSEEN;
       else if (n < a.min_obs) v = CV_FEW_OBS;
       else if (n_fr < a.min_frames) v = CV_FEW_FRAMES;
-      else if (any_bad) v = CV_NOT_FINITE;
-      else if (!(mz > 0.0)) v = CV_BEHIND;
-      else if ((a.max_mean_sq > 0.0 && mean > a.max_mean_sq) || (a.max_sq > 0.0 && mx > a.max_sq)) v = CV_HIGH_ERROR;
-      else if (a.parallax && cosp > a.cos_thr) v = CV_LOW_PARALLAX;
       a.verdict[e] = v;
       a.w.rank[e] = (v == CV_KEPT || (v == CV_UNSEEN && !a.drop_unseen)) ? 1 : 0;
       if (a.entry_out) {

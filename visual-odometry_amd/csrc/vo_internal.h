@@ -479,9 +479,11 @@ struct MapDev {
   int cap = 0;
 };
 size_t map_scratch_ints(int n_max);
-// PointCloudVector<3>::update(T * cloud) (PointCloud.h:52-66,77-82); d_T16 / d_n may be null; d_scratch: map_scratch_ints(n_max) ints
+// PointCloudVector<3>::update(T * cloud) (PointCloud.h:52-66,77-82); d_T16 / d_n may be null; d_scratch: map_scratch_ints(n_max) ints.
+// d_guard (or null): a device flag read when the launches RUN -- where it is 0 they return at once and the map, its table and
+// its header keep every byte (voe_map_grow)
 hipError_t launch_map_update(hipStream_t st, const MapDev& m, const float* d_xyz, const float* d_app, int n_max, const int* d_n,
-                             const float* d_T16, int* d_scratch);
+                             const float* d_T16, int* d_scratch, const int* d_guard = nullptr);
 // empties the table, enters entries 0 .. size-1.  d_guard (or null): a device flag read when the launches RUN -- where it is 0
 // the same launches return at once and the table keeps every byte (voe_map_cull: a fixed sequence of launches, whatever the data)
 hipError_t launch_map_rehash(hipStream_t st, const MapDev& m, int size_bound, const int* d_guard = nullptr);
@@ -778,6 +780,47 @@ struct MapCullArgs {
 // then enqueues launch_map_rehash guarded by w.ctl + 2, and launch_map_cull_stats
 hipError_t launch_map_cull(hipStream_t st, const MapCullArgs& a, int n_cu);
 hipError_t launch_map_cull_stats(hipStream_t st, const MapCullArgs& a);
+
+// ---- landmarks added from the frames' unmapped tracks (map_grow.hip, voe_map_grow*; include/vo_map_grow.h holds the rules) ----
+// rows = n_frames * n_max query positions (R below: rows, at least 1); a track is numbered below R
+struct MapGrowWs {
+  int32_t* hit;                         // [R] the map's entry per query position (the lookup's own output)
+  int* ocode;                           // [R] an open row's rank inside its block of 256 positions; -1 not live, -2 NaN appearance, -3 a hit
+  int* oblk;                            // [ceil(R / 256)] open rows per block -> block offsets
+  float* oapp;                          // [R][10] the open rows' appearances, compacted in key order: the cloud of the private update
+  int32_t* otrack;                      // [R] the track of compacted open row j (the private lookup's own output)
+  int32_t *verdict, *entry;             // [R] per track: what the track kernel decided, then the final verdict / the entry or -1
+  float* xyz;                           // [R][3] per track: the chosen point (before that: the private update's cloud points, never meant)
+  int *rank, *blk;                      // [R] 1: the track would be added -> its rank inside its block of 256 tracks (-1: not); [ceil(R / 256)]
+  float *stage_pts, *stage_app;         // [A][3], [A][10] the ADDED tracks in track order, A = min(max_added, R): the cloud of the append
+  int *upd, *look;                      // scratch of the private update (map_scratch_ints(R)) and of the private lookup
+  MapDev priv;                          // the tracks' own first-occurrence table: an empty map filled by launch_map_update of oapp
+  int* ctl;                             // [0] open rows [1] (the private lookup's hits) [2] tracks that qualify [3] added [4] size before
+                                        // [5] 1: the map changes (something is added and no dry run)
+  size_t bytes;
+};
+MapGrowWs map_grow_layout(void* base, size_t rows, int stage_rows, unsigned tcap);
+struct MapGrowArgs {
+  MapRefineWs l;                        // the tracks' ordered lists (map_refine_layout with bound R): l.ent holds the TRACK of every position
+  MapGrowWs w;
+  MapView v;                            // the frames; v.hdr is the PRIVATE header, so that v.size() is the number of tracks; v.pts unused
+  const float* app; size_t app_stride;  // the frames' appearances, floats between frames
+  const int* d_n;                       // or null
+  const int* map_hdr; int map_cap;      // the map that grows
+  double Kinv[9];                       // column-major (invert_k)
+  int n_rounds, min_obs, min_frames;
+  double huber, damping;
+  double max_mean_sq, max_sq, cos_thr;  // as in MapCullArgs
+  int parallax;
+  int max_added, dry_run, track_cap;    // max_added: already resolved (never 0)
+  int32_t* row_out;                     // [n_frames][n_max] or null
+  void* track_out;                      // [track_cap] voe_map_grow_track, or null
+  void* stats;                          // voe_map_grow_stats
+};
+// after the lookup has filled w.hit: open rows -> compaction -> private update and lookup -> lists -> tracks -> ranks -> staging.
+// The caller then enqueues launch_map_update of (w.stage_pts, w.stage_app, w.ctl + 3 rows) guarded by w.ctl + 5, and launch_map_grow_finish.
+hipError_t launch_map_grow(hipStream_t st, const MapGrowArgs& a, int n_cu);
+hipError_t launch_map_grow_finish(hipStream_t st, const MapGrowArgs& a);
 
 // ---- covisibility of frames and the window chosen from it (map_covis.hip, voe_map_covis* / voe_map_window*;
 // include/vo_map_covis.h holds the rules).  All integers. ----
