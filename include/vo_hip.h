@@ -669,13 +669,27 @@ int vo_match_appearances_batch_dev(vo_ctx *ctx, int n_frames, const float *d_a1,
  * the map when the rows would not fit, vo_map_transform and vo_map_refine_batch_dev reach every entry (they size their
  * work by the capacity).  The graph names the arrays it was captured on: do not replay it after the map has grown.
  *
+ * A CALL CAPTURED ON A MAP.  The calls that work on the map's own entries -- vo_map_transform, vo_map_refine_batch_dev,
+ * vo_map_refine_poses_batch_dev, vo_map_adjust_batch_dev, vox_map_bundle_batch_dev, voe_map_cull_batch_dev -- size their
+ * launches by the host's bound when they are enqueued outside a capture (they run at once: the bound holds), and BY THE
+ * CAPACITY when they are enqueued inside one, whatever has been captured before: the graph may hold an update BEHIND the
+ * call (the per-frame shape { window call ; vo_map_update_dev }), whose replays add entries before the call's next replay
+ * runs, and every replay must see the map it finds.  Their workspaces that are indexed by entry are ALLOCATED for the
+ * capacity by every call, eager ones too, so that "one eager call of the same shape, then capture" never has to grow
+ * one; an array the caller passes per entry (status, verdict, remap, records) must have room for the size the map can
+ * have when a replay runs.  The rule is MapBound of csrc/map_checks.h (launch_bound, alloc_bound).  voe_map_align_dev and
+ * voe_map_merge_dev take n_max = voe_map_size_bound(src) at the time of the call, as their header says: captured in front
+ * of src's first captured update they see at most that many of its entries (voe_map_covis_batch_dev checks its words
+ * against the bound of that time and reads the size itself).
+ *
  * OVERFLOW.  A replayed update cannot grow the map.  What then does not fit is dropped: the map holds what the
  * reference's map holds cut to `capacity` entries -- the classes with the earliest first occurrence in the cloud stay,
  * entries already there still take their new points -- and a dropped class is forgotten: sent again it is a new class
  * (and dropped again while the map is full).  Every dropped entry is counted; from then on vo_map_size and vo_map_read
  * fail with VO_ERR_BAD_INDEX and name the running count (vo_map_size still sets *n), until vo_map_clear; so does every
- * host form that reads the size first (vo_map_refine).  The entries, vo_map_dev_ptrs, vo_map_lookup and the *_dev forms of
- * lookup, localisation and refinement stay valid on the entries the map kept. */
+ * host form that reads the size first (vo_map_refine).  The entries, vo_map_dev_ptrs, vo_map_lookup and every *_dev form
+ * (lookup, localisation, the refinements, adjustment, bundle, cull, grow, covisibility, alignment and merge) stay valid on
+ * the entries the map kept: a dropped class is a miss (tests/test_gpu_map_states.py). */
 typedef struct vo_map vo_map;
 int vo_map_create(vo_ctx *ctx, int capacity, vo_map **out);
 int vo_map_destroy(vo_map *m);

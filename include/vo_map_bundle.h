@@ -80,7 +80,8 @@ extern "C" {
  * passes through its remaining launches, which return at once.  No launch waits for another workgroup.  A single frame is
  * traversed by ONE workgroup, as in vo_map_refine_poses: the call is meant for windows of many frames.
  * Capturable once a call of the same shape (n_frames, n_max) has sized the workspaces; a capture that would have to grow them
- * is refused (VO_ERR_NOT_READY) before anything is enqueued.
+ * is refused (VO_ERR_NOT_READY) before anything is enqueued.  A captured call is launched for the map's CAPACITY, not for the
+ * host's bound of the moment (vo_hip.h, A CALL CAPTURED ON A MAP), so that it reaches what an update behind it in the graph adds.
  * Refused (VO_ERR_INVALID_ARG): the refusals of vo_map_adjust_batch_dev (n_rounds < 0, min_obs_pose < 3, min_obs_point < 2,
  * huber_px negative or not finite, and those of the frames), n_cg < 1, cg_tol or lambda0 negative or not finite, and
  * n_rounds * (n_cg + 2) > VOX_MAP_BUNDLE_MAX_STEPS. */

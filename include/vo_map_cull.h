@@ -75,7 +75,9 @@ extern "C" {
  * VO_ERR_BAD_INDEX on a map that has dropped rows for lack of room, exactly as vo_map_refine does, while the _dev form works
  * on the entries such a map kept.
  * Capturable once a call of the same shape (n_frames, n_max) has sized the workspaces; a capture that would have to grow them
- * is refused (VO_ERR_NOT_READY) before anything is enqueued.
+ * is refused (VO_ERR_NOT_READY) before anything is enqueued.  A captured cull is launched for the map's CAPACITY, not for the
+ * host's bound of the moment (vo_hip.h, A CALL CAPTURED ON A MAP): in a graph { cull ; vo_map_update_dev } every replay judges
+ * every entry the map holds when it runs, and the per-entry arrays need room for that size.
  * Refused (VO_ERR_INVALID_ARG): the refusals of vo_map_refine_batch_dev for the frames, min_obs < 1, min_frames < 1, a
  * threshold negative or not finite, min_parallax_deg >= 180, a misaligned d_entry_out or d_stats. */
 #define VOE_MAP_CULL_KEPT          0

@@ -69,7 +69,10 @@ extern "C" {
  *                holds: the call is refused with VO_ERR_NOT_READY, before anything is enqueued, if the map or a workspace would
  *                have to grow; otherwise replays add entries the host never counts.  The host's bound of the size rises by
  *                max_added unless dry_run; the host form sets it to the true size after its read-back when no update of the map
- *                has been captured.
+ *                has been captured.  The call itself reads the map through the lookup alone and appends at the size the device
+ *                holds, so no bound of the host clips it; a captured grow that adds makes the capacity the bound of every
+ *                later call outside a capture, and a window call captured in the same graph is launched for the capacity
+ *                wherever it stands (vo_hip.h, A CALL CAPTURED ON A MAP).
  *   determinism  no float atomics: calls from the same start give the same bytes in the map and in every output.
  * OUTPUTS.  d_row_out [n_frames][n_max] (or NULL): the entry the row is found at AFTER the call -- its hit, or its track's new
  * entry; -1 for a row that is not live or has a NaN appearance; -2 - t for an open row whose track t was not added.

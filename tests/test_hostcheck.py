@@ -285,6 +285,22 @@ def test_map_window_refusals_under_the_host_sanitizers(tmp_path):
     assert r.stdout.count("-> ok") >= 70 and "FAILED" not in r.stdout
 
 
+def test_map_size_bound_against_a_model_of_the_true_size(tmp_path):
+    """visual-odometry_amd/csrc/map_checks.h, MapBound -- the number every call that must not wait sizes its launches by, one
+    transition per event.  A stand-alone program drives scripted and seeded random sequences of the events (clear, update, grow,
+    host reads, host cull / grow / merge, growth of the arrays, captures and replays the host never sees) next to a brute-force
+    model of the size the device holds, under AddressSanitizer and UBSan: the bound is never below the size, it IS the size
+    after every event that reads it, and a call captured in front of an update is launched for the capacity."""
+    exe = str(tmp_path / "map_bound_check")
+    root = os.path.join(HERE, "..")
+    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-Wall", "-Wextra", "-Werror", "-fsanitize=address,undefined",
+                           "-fno-sanitize-recover=all", "-I" + os.path.join(root, "visual-odometry_amd", "csrc"),
+                           os.path.join(HERE, "hostcheck", "map_bound_check.cpp"), "-o", exe])
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0 and r.stdout.strip().endswith("map_bound_check: all ok"), r.stdout[-3000:] + r.stderr[-3000:]
+    assert r.stdout.count("-> ok") == 3 and "FAILED" not in r.stdout and "short in 2 of 3 replays" in r.stdout
+
+
 # ---- host linear algebra of the epipolar initialisation (include/vo/epipolar.hpp, vo/linalg.hpp) ---------------------
 @pytest.fixture(scope="module")
 def epi():

@@ -14,8 +14,7 @@ struct vo_map {
   MapDev d;
   DevBuf scratch;
   float* hist = nullptr;        // [0,16) the history isometry, [16,32) staging of a host isometry (vo_map_update)
-  long long size_ub = 0;        // upper bound of the size known without asking the device, as long as !replayable
-  bool replayable = false;      // an update of this map has been captured: the graph's replays add entries the host never counts
+  MapBound bd;                  // the host's bound of the size and its transitions (map_checks.h); bd.cap follows d.cap
   DevBuf up_xyz, up_app;        // staging of vo_map_update
   DevBuf look_ws;               // vo_map_lookup*: per-workgroup counts, entries per query position
   DevBuf loc_ws;                // vo_map_localise*: what passes from stage to stage (hits, gathered points, winner, pairs handed on)
@@ -46,7 +45,7 @@ static void map_free_arrays(MapDev& d) {
   d.pts = d.app = nullptr; d.table = nullptr; d.last = nullptr;
 }
 
-static int map_alloc_arrays(MapDev& d, int cap) {
+static int map_alloc_arrays(MapDev& d, int cap) {      // (the caller tells the map's MapBound: on_arrays)
   d.cap = cap; d.tcap = map_tcap_for(cap);
   VO_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&d.pts), sizeof(float) * 3 * (size_t)cap));
   VO_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&d.app), sizeof(float) * 10 * (size_t)cap));
@@ -55,20 +54,22 @@ static int map_alloc_arrays(MapDev& d, int cap) {
   return VO_OK;
 }
 
-// what bounds the size where the host must not wait: size_ub, or the capacity once replays may have outrun it
-static int map_bound(const vo_map* m) { return (int)(m->replayable || m->size_ub > m->d.cap ? m->d.cap : m->size_ub); }
+// what bounds the size where the host must not wait (MapBound, map_checks.h), and what sizes the launches of a call on the
+// map's own entries enqueued now: inside a capture the capacity, since the graph may append behind the call
+static int map_bound(const vo_map* m) { return m->bd.bound(); }
+static int map_launch_bound(const vo_map* m) { return m->bd.launch_bound(m->ctx->capturing); }
 
 // room for n more entries: the bound the host keeps (size_ub grows by a cloud's row count per update) is refreshed from
 // the device only when it would pass the capacity, and the arrays grow only when the true size would.  A map whose update
 // has been captured asks the device every time outside a capture; inside one nobody can ask, and the bound decides as before.
 static int map_reserve(vo_map* m, int n) {
   vo_ctx* c = m->ctx;
-  if ((c->capturing || !m->replayable) && m->size_ub + n <= m->d.cap) return VO_OK;
+  if (m->bd.room_known(c->capturing, n)) return VO_OK;
   if (c->capturing) return vo_fail(VO_ERR_NOT_READY, "vo_map: the map would have to grow inside a graph capture (create it with the capacity it will need)");
   int size = 0;
   VO_HIP_CHECK(hipMemcpyAsync(&size, m->d.hdr, sizeof(int), hipMemcpyDeviceToHost, c->stream));
   VO_HIP_CHECK(hipStreamSynchronize(c->stream));
-  m->size_ub = size;
+  m->bd.on_size_read(size);
   if ((long long)size + n <= m->d.cap) return VO_OK;
   long long want = 2ll * m->d.cap;
   if (want < (long long)size + n) want = (long long)size + n + ((long long)size + n) / 2;
@@ -86,6 +87,7 @@ static int map_reserve(vo_map* m, int n) {
   VO_HIP_CHECK(hipStreamSynchronize(c->stream));
   map_free_arrays(old);
   m->d = nd;
+  m->bd.on_arrays(nd.cap);
   return VO_OK;
 }
 
@@ -102,6 +104,7 @@ int vo_map_create(vo_ctx* c, int capacity, vo_map** out) {
   m->ctx = c; m->ctx_id = c->id;
   const int cap = capacity < 1024 ? 1024 : capacity;
   int rc = map_alloc_arrays(m->d, cap);
+  m->bd.on_arrays(cap);
   if (rc == VO_OK && hipMalloc(reinterpret_cast<void**>(&m->d.hdr), 64) != hipSuccess) rc = vo_fail(VO_ERR_OUT_OF_MEMORY, "vo_map_create: out of device memory");
   if (rc == VO_OK && hipMalloc(reinterpret_cast<void**>(&m->hist), sizeof(float) * 32) != hipSuccess) rc = vo_fail(VO_ERR_OUT_OF_MEMORY, "vo_map_create: out of device memory");
   if (rc != VO_OK) { (void)hipGetLastError(); map_free_arrays(m->d); if (m->d.hdr) (void)hipFree(m->d.hdr); if (m->hist) (void)hipFree(m->hist); delete m; return rc; }
@@ -137,7 +140,7 @@ int vo_map_clear(vo_map* m) {
   const float I[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
   VO_HIP_CHECK(hipMemcpyAsync(m->hist, I, sizeof(I), hipMemcpyHostToDevice, c->stream));
   VO_HIP_CHECK(hipStreamSynchronize(c->stream));
-  m->size_ub = 0;
+  m->bd.on_clear();
   return VO_OK;
 }
 
@@ -151,8 +154,7 @@ int vo_map_update_dev(vo_map* m, const float* d_xyz, const float* d_app, int n_m
   if (int r = map_reserve(m, n_max)) return r;
   VO_HIP_CHECK(m->scratch.ensure(sizeof(int) * map_scratch_ints(n_max), c->stream));
   VO_HIP_CHECK(launch_map_update(c->stream, m->d, d_xyz, d_app, n_max, d_n, d_T16, m->scratch.as<int>()));
-  m->size_ub += n_max;
-  if (c->capturing) m->replayable = true;
+  m->bd.on_update(n_max, c->capturing);
   return VO_OK;
 }
 
@@ -211,7 +213,7 @@ int vo_map_size(vo_map* m, int* n) {
   int h[4] = {0, 0, 0, 0};
   VO_HIP_CHECK(hipMemcpyAsync(h, m->d.hdr, sizeof(h), hipMemcpyDeviceToHost, m->ctx->stream));
   VO_HIP_CHECK(hipStreamSynchronize(m->ctx->stream));
-  m->size_ub = h[0];
+  m->bd.on_size_read(h[0]);
   *n = h[0];
   if (h[3] > 0) return vo_fail(VO_ERR_BAD_INDEX, "vo_map: %d entries were dropped for lack of room", h[3]);
   return VO_OK;
@@ -234,7 +236,7 @@ int vo_map_transform(vo_map* m, const float T16[16]) {
   VO_MAP_LIVE(m);
   VO_REQUIRE(T16, "null argument");
   if (int r = set_device(m->ctx)) return r;
-  VO_HIP_CHECK(launch_map_transform(m->ctx->stream, m->d, pose_from_T16(T16), map_bound(m)));
+  VO_HIP_CHECK(launch_map_transform(m->ctx->stream, m->d, pose_from_T16(T16), map_launch_bound(m)));
   return VO_OK;
 }
 
@@ -477,7 +479,7 @@ static int window_growth_check(const vo_map* m, const char* fn, const MapFrames&
 }
 
 // the map and the frames as the adjustment kernels see them (MapView, vo_internal.h), with the poses that come in
-static void fill_map(MapView& v, const vo_map* m) { v.pts = m->d.pts; v.hdr = m->d.hdr; v.cap = m->d.cap; v.bound = map_bound(m); }
+static void fill_map(MapView& v, const vo_map* m) { v.pts = m->d.pts; v.hdr = m->d.hdr; v.cap = m->d.cap; v.bound = map_launch_bound(m); }
 static void fill_frames(MapView& v, const MapFrames& f, const float* d_T16) {
   v.uv = f.d_uv; v.uv_stride = f.uv_stride; v.n_max = f.n_max; v.n_frames = f.n_frames; v.T16 = d_T16;
   for (int k = 0; k < 9; ++k) v.K[k] = f.K[k];
@@ -514,12 +516,12 @@ static_assert(sizeof(vo_map_refine_params) == 16 && sizeof(vo_map_refine_stats) 
 // the point half's workspace, sized and laid out, and the lookup of every frame into it
 static int refine_prepare(const char* fn, vo_map* m, const MapFrames& f, MapRefineWs* out) {
   vo_ctx* c = m->ctx;
-  const int bound = map_bound(m);
-  MapRefineWs w = map_refine_layout(nullptr, f.n_frames, f.n_max, bound);
-  if (int r = window_growth_check(m, fn, f, {{m->ref_ws.cap, w.bytes}, {m->look_ws.cap, f.n_max > 0 ? lookup_scratch_bytes(f, false) : 0}})) return r;
+  // (allocated for the capacity, laid out and launched for the bound: MapBound::alloc_bound)
+  const size_t need = map_refine_layout(nullptr, f.n_frames, f.n_max, m->bd.alloc_bound()).bytes;
+  if (int r = window_growth_check(m, fn, f, {{m->ref_ws.cap, need}, {m->look_ws.cap, f.n_max > 0 ? lookup_scratch_bytes(f, false) : 0}})) return r;
   if (int r = set_device(c)) return r;
-  VO_HIP_CHECK(m->ref_ws.ensure(w.bytes, c->stream));
-  w = map_refine_layout(m->ref_ws.p, f.n_frames, f.n_max, bound);
+  VO_HIP_CHECK(m->ref_ws.ensure(need, c->stream));
+  MapRefineWs w = map_refine_layout(m->ref_ws.p, f.n_frames, f.n_max, map_launch_bound(m));
   if (int r = lookup_window(m, f, w.pairs, w.n_hits, w.ent)) return r;
   *out = w;
   return VO_OK;
@@ -725,12 +727,12 @@ int vox_map_bundle_batch_dev(vo_map* m, int n_frames, const float K[9], const fl
   if ((long long)p->n_rounds * ((long long)p->n_cg + 2) > VOX_MAP_BUNDLE_MAX_STEPS)
     return vo_fail(VO_ERR_INVALID_ARG, "%s: n_rounds * (n_cg + 2) above %d (the launches of a call are a fixed sequence)", fn, VOX_MAP_BUNDLE_MAX_STEPS);
   vo_ctx* c = m->ctx;
-  const int bound = map_bound(m);
-  MapBundleWs bw = map_bundle_layout(nullptr, n_frames, bound);
-  if (int r = window_growth_check(m, fn, f, {{m->bundle_ws.cap, bw.bytes}})) return r;      // (before the lookup is enqueued)
+  const int bound = map_launch_bound(m);
+  const size_t need = map_bundle_layout(nullptr, n_frames, m->bd.alloc_bound()).bytes;
+  if (int r = window_growth_check(m, fn, f, {{m->bundle_ws.cap, need}})) return r;      // (before the lookup is enqueued)
   MapRefineWs rw;
   if (int r = refine_prepare(fn, m, f, &rw)) return r;        // the one lookup of the call
-  VO_HIP_CHECK(m->bundle_ws.ensure(bw.bytes, c->stream));
+  VO_HIP_CHECK(m->bundle_ws.ensure(need, c->stream));
   MapBundleArgs a{};
   a.l = rw; a.w = map_bundle_layout(m->bundle_ws.p, n_frames, bound);
   fill_map(a.v, m);
@@ -798,12 +800,12 @@ int voe_map_cull_batch_dev(vo_map* m, int n_frames, const float K[9], const floa
   if (int r = map_frames_check(fn, f, d_stats)) return r;
   if (int r = cull_check_params(fn, p)) return r;
   vo_ctx* c = m->ctx;
-  const int bound = map_bound(m);
-  MapCullWs cw = map_cull_layout(nullptr, bound);
-  if (int r = window_growth_check(m, fn, f, {{m->cull_ws.cap, cw.bytes}})) return r;        // (before the lookup is enqueued)
+  const int bound = map_launch_bound(m);
+  const size_t need = map_cull_layout(nullptr, m->bd.alloc_bound()).bytes;
+  if (int r = window_growth_check(m, fn, f, {{m->cull_ws.cap, need}})) return r;        // (before the lookup is enqueued)
   MapRefineWs rw;
   if (int r = refine_prepare(fn, m, f, &rw)) return r;        // the one lookup of the call
-  VO_HIP_CHECK(m->cull_ws.ensure(cw.bytes, c->stream));
+  VO_HIP_CHECK(m->cull_ws.ensure(need, c->stream));
   MapCullArgs a{};
   a.l = rw; a.w = map_cull_layout(m->cull_ws.p, bound);
   fill_map(a.v, m);
@@ -850,7 +852,7 @@ int voe_map_cull(vo_map* m, int n_frames, const float K[9], const float* uv, con
     if (entry_out) VO_HIP_CHECK(hipMemcpyAsync(entry_out, c->out[1].p, sizeof(voe_map_cull_entry) * (size_t)size, hipMemcpyDeviceToHost, c->stream));
   }
   VO_HIP_CHECK(hipStreamSynchronize(c->stream));
-  if (!m->replayable && !params->dry_run) m->size_ub = stats_out->n_kept;
+  m->bd.on_host_cull(stats_out->n_kept, params->dry_run != 0);
   return VO_OK;
 }
 
@@ -905,10 +907,7 @@ int voe_map_grow_batch_dev(vo_map* m, int n_frames, const float K[9], const floa
   // the append: vo_map_update_dev's launches on the staging area, returning at once where nothing is added or under dry_run
   VO_HIP_CHECK(launch_map_update(c->stream, m->d, a.w.stage_pts, a.w.stage_app, stage, a.w.ctl + 3, nullptr, m->scratch.as<int>(), a.w.ctl + 5));
   VO_HIP_CHECK(launch_map_grow_finish(c->stream, a));
-  if (!dry) {
-    m->size_ub += room;
-    if (c->capturing) m->replayable = true;
-  }
+  m->bd.on_grow(room, c->capturing, dry);
   return VO_OK;
 }
 
@@ -936,7 +935,7 @@ int voe_map_grow(vo_map* m, int n_frames, const float K[9], const float* uv, con
   if (row_out && rows) VO_HIP_CHECK(hipMemcpyAsync(row_out, c->out[0].p, sizeof(int32_t) * rows, hipMemcpyDeviceToHost, c->stream));
   if (track_out) VO_HIP_CHECK(hipMemcpyAsync(track_out, c->out[1].p, sizeof(voe_map_grow_track) * (size_t)track_cap, hipMemcpyDeviceToHost, c->stream));
   VO_HIP_CHECK(hipStreamSynchronize(c->stream));
-  if (!m->replayable && !params->dry_run) m->size_ub = stats_out->n_after;
+  m->bd.on_host_grow(stats_out->n_after, params->dry_run != 0);
   return VO_OK;
 }
 
@@ -1082,7 +1081,7 @@ int voe_map_merge(vo_map* dst, vo_map* src, const float S16[16], int policy, int
   VO_HIP_CHECK(hipMemcpyAsync(stats_out, d_st, sizeof(voe_map_merge_stats), hipMemcpyDeviceToHost, c->stream));
   if (remap_out && size > 0) VO_HIP_CHECK(hipMemcpyAsync(remap_out, c->out[0].p, sizeof(int32_t) * (size_t)size, hipMemcpyDeviceToHost, c->stream));
   VO_HIP_CHECK(hipStreamSynchronize(c->stream));
-  if (!dst->replayable) dst->size_ub = stats_out->n_dst_after;
+  dst->bd.on_host_merge(stats_out->n_dst_after);
   return VO_OK;
 }
 

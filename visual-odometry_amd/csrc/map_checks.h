@@ -124,3 +124,39 @@ static inline int capture_growth_check(bool capturing, const char* fn, std::init
   va_end(ap);
   return vo_fail(VO_ERR_NOT_READY, "%s: the workspace would have to grow inside a graph capture (make one call with %s before capturing)", fn, with);
 }
+
+// ---- the host's bound of a map's size --------------------------------------------------------------------------------------
+// Every call that must not wait for the device sizes its launches and workspaces by a number the host keeps; the kernels read the
+// true size from the map's header and clamp it by that number (MapView::size()), so an entry at or above the number is skipped
+// without a word.  THE RULE: bound() >= the size the device holds whenever a call is enqueued, and launch_bound() >= the size the
+// device holds whenever that call RUNS.  The two differ for a call enqueued inside a graph capture: the graph may hold an update
+// BEHIND the call (the per-frame shape { window call ; update }), whose replays add entries before the call's next replay runs.
+// One transition per event that changes what the host knows; capi_map.hip makes no assignment of its own, and
+// tests/hostcheck/map_bound_check.cpp drives the transitions next to a brute-force model of the true size.
+struct MapBound {
+  long long size_ub = 0;        // upper bound of the size known without asking the device, as long as !replayable
+  bool replayable = false;      // an update (or a grow that adds) of this map has been captured: replays add entries the host never counts
+  int cap = 0;                  // the arrays' capacity: no size passes it (what does not fit is dropped and counted)
+
+  // what bounds the size where the host must not wait: size_ub, or the capacity once replays may have outrun it
+  int bound() const { return (int)(replayable || size_ub > cap ? cap : size_ub); }
+  // what sizes the launches of a call enqueued now on the map's own entries (refinement, pose refinement, adjustment, bundle,
+  // cull, transform): inside a capture the capacity, because the call runs again after whatever the rest of the graph appends
+  int launch_bound(bool capturing) const { return capturing ? cap : bound(); }
+  // what sizes the ALLOCATION of a workspace indexed by entry: always the capacity, so that the call can be captured later
+  // without growing the workspace ("one eager call, then capture") whatever bound the capture then bakes in
+  int alloc_bound() const { return cap; }
+  // room for n more entries without asking the device?  (a map whose update has been captured asks every time outside a capture;
+  // inside one nobody can ask, and the bound decides)
+  bool room_known(bool capturing, int n) const { return (capturing || !replayable) && size_ub + n <= cap; }
+
+  void on_clear() { size_ub = 0; }                                                // (a captured update stays captured)
+  void on_arrays(int new_cap) { cap = new_cap; }                                  // created, or grown on the host
+  void on_size_read(int size) { size_ub = size; }                                 // the host has read the header, the stream idle
+  void on_update(int n, bool capturing) { size_ub += n; if (capturing) replayable = true; }      // n rows enqueued: at most n new entries
+  void on_grow(int room, bool capturing, bool dry) { if (!dry) on_update(room, capturing); }     // at most `room` tracks appended
+  // the host forms that have waited for their statistics: the size they report IS the size, unless replays may run unseen
+  void on_host_cull(int n_kept, bool dry) { if (!replayable && !dry) size_ub = n_kept; }
+  void on_host_grow(int n_after, bool dry) { if (!replayable && !dry) size_ub = n_after; }
+  void on_host_merge(int n_dst_after) { if (!replayable) size_ub = n_dst_after; }
+};
