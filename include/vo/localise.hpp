@@ -187,6 +187,23 @@ inline Isometry3f similarity_pose(const Isometry3f& T, const Similarity3f& S) {
   return out;
 }
 
+//! The rigid pose that goes with a similarity S = [c R | t] of the pose graph (vo/pose_graph.hpp): [R | t / c], on the host in
+//! double.  A map point moved by S_new^-1 S_old of its reference frame (DeviceMap::applyCorrection) projects there, under
+//! rigid_pose(S_new), where it projected before.
+inline Isometry3f rigid_pose(const Similarity3f& S) {
+  double M[3][3];
+  for (int r = 0; r < 3; ++r) for (int c = 0; c < 3; ++c) M[r][c] = S(r, c);
+  const double det = M[0][0] * (M[1][1] * M[2][2] - M[1][2] * M[2][1]) - M[0][1] * (M[1][0] * M[2][2] - M[1][2] * M[2][0]) +
+                     M[0][2] * (M[1][0] * M[2][1] - M[1][1] * M[2][0]);
+  const double c = std::cbrt(det);
+  Isometry3f out = Isometry3f::Identity();
+  for (int r = 0; r < 3; ++r) {
+    for (int k = 0; k < 3; ++k) out(r, k) = (float)(M[r][k] / c);
+    out(r, 3) = (float)((double)S(r, 3) / c);
+  }
+  return out;
+}
+
 class DeviceMap {
  public:
   explicit DeviceMap(int capacity = 0, Context& ctx = default_context()) : ctx_(ctx.handle()) {
@@ -456,6 +473,31 @@ class DeviceMap {
     check(voe_map_covis(h_, (int)F, app.data(), n.data(), (int)cap, (int)c.n_words, c.bits.data(), want_counts ? c.counts.data() : nullptr,
                         &c.stats), "voe_map_covis");
     return c;
+  }
+
+  //! a trajectory's correction carried into the map (voe_map_apply_correction): every entry some row of the frames sees moves by
+  //! S_new[f]^-1 S_old[f] of its reference frame f, the frame of its first observation.  *ref_frame: that frame per entry, -1 for
+  //! an entry no row sees.  With dry_run the map stays as it is.
+  voe_map_apply_stats applyCorrection(const std::vector<Vector10fVector>& appearances, const std::vector<Similarity3f>& S_old,
+                                      const std::vector<Similarity3f>& S_new, bool dry_run = false, std::vector<int32_t>* ref_frame = nullptr) {
+    const size_t F = appearances.size();
+    if (S_old.size() != F || S_new.size() != F) throw Error(VO_ERR_INVALID_ARG, "DeviceMap::applyCorrection: one similarity per frame, before and after");
+    size_t cap = 0;
+    for (const auto& a : appearances) cap = a.size() > cap ? a.size() : cap;
+    std::vector<float> app(F * cap * 10 + 10, 0.f);
+    std::vector<int> n(F + 1, 0);
+    for (size_t f = 0; f < F; ++f) {
+      n[f] = (int)appearances[f].size();
+      for (size_t i = 0; i < appearances[f].size(); ++i)
+        for (int k = 0; k < 10; ++k) app[(f * cap + i) * 10 + k] = appearances[f][i][k];
+    }
+    std::vector<int32_t> ref((size_t)size() + 1, -1);
+    voe_map_apply_stats st{};
+    check(voe_map_apply_correction(h_, (int)F, nullptr, app.data(), n.data(), (int)cap, F ? S_old[0].m : nullptr, F ? S_new[0].m : nullptr,
+                                   dry_run ? 1 : 0, ref.data(), &st), "voe_map_apply_correction");
+    ref.resize((size_t)st.n_entries);
+    if (ref_frame) *ref_frame = ref;
+    return st;
   }
 
   //! the local window of frame `query` (voe_map_window) from the bit rows of covisibility(): the frames to free, the frames to

@@ -877,4 +877,5 @@ int vo_map_refine(vo_map *m, int n_frames, const float K[9], const float *uv, co
 #include "vo_map_align.h"
 #include "vo_map_covis.h"
 #include "vo_map_grow.h"
+#include "vo_pose_graph.h"
 #endif /* VO_HIP_H */

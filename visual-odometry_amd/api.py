@@ -800,6 +800,36 @@ class Map:
                                     _ptr(counts) if want_counts else None, C.byref(st)))
         return dict(bits=bits, counts=counts, stats=st.as_dict())
 
+    # ---- a trajectory's correction carried into the map (voe_map_apply_correction*, include/vo_pose_graph.h) ----
+    def apply_correction_batch_dev(self, n_frames, d_app, app_stride, n_max, d_n, d_S16_old, d_S16_new, dry_run, d_ref_frame_out, d_stats):
+        """voe_map_apply_correction_batch_dev on device pointers (ints; d_n and d_ref_frame_out may be None; the stride in rows):
+        enqueues and returns.  d_ref_frame_out: map size x int32; d_stats: 16 bytes (MapApplyStats)."""
+        v = lambda d: C.c_void_p(d) if d else None
+        _chk(self.lib.voe_map_apply_correction_batch_dev(self.h, C.c_int(n_frames), None, C.c_size_t(n_max), v(d_app), C.c_size_t(app_stride),
+                                                         C.c_int(n_max), v(d_n), v(d_S16_old), v(d_S16_new), C.c_int(int(bool(dry_run))),
+                                                         v(d_ref_frame_out), v(d_stats)))
+
+    def apply_correction(self, frames, S_old, S_new, dry_run=False):
+        """voe_map_apply_correction: every entry some row of `frames` ([(uv, app)] as in refine, or [app]) sees moves by
+        S_new[f]^-1 S_old[f] of its reference frame f -- the frame of its first observation in ascending key -- so that it keeps
+        its place in that frame's camera; S_old, S_new: F x 4 x 4 (p_cam = S p_map).  Returns (ref_frame (size,) int32, -1: unseen;
+        stats dict: n_entries, n_seen, n_moved).  The rigid poses afterwards are rigid_pose(S_new[f])."""
+        apps = [_f32(f[1] if isinstance(f, (tuple, list)) else f, (-1, 10)) for f in frames]
+        F = len(apps)
+        n = np.array([len(a) for a in apps], np.int32)
+        cap = int(n.max()) if F else 0
+        app = np.zeros((max(F, 1), max(cap, 1), 10), np.float32)
+        for f, a in enumerate(apps):
+            app[f, : n[f]] = a
+        So = np.ascontiguousarray(np.asarray(S_old, np.float32).reshape(-1, 4, 4).transpose(0, 2, 1))
+        Sn = np.ascontiguousarray(np.asarray(S_new, np.float32).reshape(-1, 4, 4).transpose(0, 2, 1))
+        assert len(So) == F and len(Sn) == F
+        ref = np.full(max(len(self), 1), -2, np.int32)
+        st = MapApplyStats()
+        _chk(self.lib.voe_map_apply_correction(self.h, C.c_int(F), None, _ptr(app) if cap else None, _ptr(n), C.c_int(cap), _ptr(So), _ptr(Sn),
+                                               C.c_int(int(bool(dry_run))), _ptr(ref), C.byref(st)))
+        return ref[: st.n_entries].copy(), st.as_dict()
+
     def window_dev(self, n_frames, n_words, d_bits, d_n, n_max, params: "MapWindowParams", d_role_out, d_n_rows_out, d_fixed_out,
                    d_order_out, d_union_out, d_stats):
         """voe_map_window_dev on device pointers (ints; d_n, d_order_out and d_union_out may be None): enqueues and returns"""
@@ -1042,6 +1072,96 @@ assert C.sizeof(MapCovisStats) == 32 and C.sizeof(MapWindowParams) == 16 and C.s
 MAP_COVIS_MAX_FRAMES = 4096                                                     # VOE_MAP_COVIS_MAX_FRAMES
 MAP_WINDOW_ROLE = ("OUTSIDE", "FREE", "FIXED")                                  # VOE_MAP_WINDOW_*
 MAP_WINDOW_STATUS = ("OK", "NO_FIXED", "QUERY_UNSEEN")
+
+
+class PoseGraphParams(C.Structure):
+    """voe_pose_graph_params (include/vo_pose_graph.h)"""
+    _fields_ = [("n_rounds", C.c_int32), ("n_cg", C.c_int32), ("cg_tol", C.c_float), ("lambda0", C.c_float), ("huber", C.c_float),
+                ("with_scale", C.c_int32), ("preconditioner", C.c_int32)]
+
+
+class PoseGraphRound(C.Structure):
+    """voe_pose_graph_round (include/vo_pose_graph.h): one round"""
+    _fields_ = [("cost", C.c_double), ("cost_candidate", C.c_double), ("lambda_", C.c_double), ("residual", C.c_double),
+                ("cg_iterations", C.c_int32), ("accepted", C.c_int32)]
+
+
+class PoseGraphStats(C.Structure):
+    """voe_pose_graph_stats (include/vo_pose_graph.h)"""
+    _fields_ = [("status", C.c_int32), ("n_frames", C.c_int32), ("n_edges", C.c_int32), ("n_live_edges", C.c_int32),
+                ("n_free_frames", C.c_int32), ("n_active_frames", C.c_int32), ("n_accepted", C.c_int32), ("reserved", C.c_int32),
+                ("cost_before", C.c_double), ("cost_after", C.c_double)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_ if k != "reserved"}
+
+
+class MapApplyStats(C.Structure):
+    """voe_map_apply_stats (include/vo_pose_graph.h)"""
+    _fields_ = [("n_entries", C.c_int32), ("n_seen", C.c_int32), ("n_moved", C.c_int32), ("reserved", C.c_int32)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_ if k != "reserved"}
+
+
+assert C.sizeof(MapApplyStats) == 16
+assert C.sizeof(PoseGraphParams) == 28 and C.sizeof(PoseGraphRound) == 40 and C.sizeof(PoseGraphStats) == 48
+POSE_GRAPH_ROUND_DTYPE = np.dtype([("cost", "<f8"), ("cost_candidate", "<f8"), ("lambda", "<f8"), ("residual", "<f8"),
+                                   ("cg_iterations", "<i4"), ("accepted", "<i4")])
+assert POSE_GRAPH_ROUND_DTYPE.itemsize == 40
+POSE_GRAPH_STATUS = ("OK", "NOT_FINITE", "NOTHING_FREE", "NO_EDGES", "NO_STEP", "COST_ROSE")      # VOE_POSE_GRAPH_*
+POSE_GRAPH_PRECONDITIONER = ("CHAIN", "JACOBI")
+POSE_GRAPH_EDGE_OK, POSE_GRAPH_EDGE_SKIPPED = 0, 1
+
+
+def pose_graph_dev(ctx: Context, n_frames, d_S16, n_edges, d_edges, d_Z16, d_weights, d_fixed, params: PoseGraphParams,
+                   d_edge_status_out, d_edge_cost_out, d_rounds_out, d_stats):
+    """voe_pose_graph_dev on device pointers (ints; d_weights, d_fixed and the three outputs before d_stats may be None): enqueues
+    and returns.  d_S16: n_frames x 16 float32, column-major 4x4 each, in place; d_edges: n_edges x 2 int32; d_Z16: n_edges x 16;
+    d_edge_cost_out: n_edges doubles; d_rounds_out: n_rounds x 40 bytes (PoseGraphRound); d_stats: 48 bytes (PoseGraphStats)."""
+    v = lambda p: C.c_void_p(p or 0)
+    _chk(ctx.lib.voe_pose_graph_dev(ctx.h, C.c_int(n_frames), v(d_S16), C.c_int(n_edges), v(d_edges), v(d_Z16), v(d_weights), v(d_fixed),
+                                    C.byref(params), v(d_edge_status_out), v(d_edge_cost_out), v(d_rounds_out), v(d_stats)))
+
+
+def pose_graph(S, edges, Z, weights=None, fixed=None, n_rounds=8, n_cg=8, cg_tol=1e-6, lambda0=1e-4, huber=0.0, with_scale=True,
+               preconditioner="CHAIN", ctx: Context | None = None):
+    """voe_pose_graph: the similarities S (F x 4 x 4, p_cam = S_f p_world, S = [c R | t]) optimised under the relative-pose edges
+    (i, j) with measurements Z (E x 4 x 4, Z_ij ~ S_j S_i^-1), weights (E x 3: translation, rotation, log-scale; None: ones) and
+    held frames `fixed` (F booleans or None).  Returns (S_new F x 4 x 4 float32, stats dict, rounds: POSE_GRAPH_ROUND_DTYPE
+    records, edge_status int32, edge_cost float64 -- s^2 of every live edge at S_new).  POSE_GRAPH_STATUS names stats["status"]."""
+    ctx = ctx or default_context()
+    S32 = np.ascontiguousarray(np.asarray(S, np.float32).reshape(-1, 4, 4).transpose(0, 2, 1))      # column-major per frame
+    F = len(S32)
+    e = _i32pairs(edges) if len(edges) else np.zeros((0, 2), np.int32)
+    E = len(e)
+    Z32 = np.ascontiguousarray(np.asarray(Z, np.float32).reshape(-1, 4, 4).transpose(0, 2, 1)) if E else np.zeros((0, 4, 4), np.float32)
+    assert len(Z32) == E
+    w = _f32(weights, (E, 3)) if weights is not None else None
+    fx = np.ascontiguousarray(np.asarray(fixed).astype(np.uint8)) if fixed is not None else None
+    assert fx is None or fx.shape == (F,)
+    prm = PoseGraphParams(int(n_rounds), int(n_cg), float(cg_tol), float(lambda0), float(huber), int(bool(with_scale)),
+                          POSE_GRAPH_PRECONDITIONER.index(preconditioner) if isinstance(preconditioner, str) else int(preconditioner))
+    st = PoseGraphStats()
+    rounds = np.zeros(max(int(n_rounds), 0), POSE_GRAPH_ROUND_DTYPE)
+    es, ec = np.zeros(E, np.int32), np.zeros(E, np.float64)
+    nul = C.c_void_p(0)
+    _chk(ctx.lib.voe_pose_graph(ctx.h, C.c_int(F), _ptr(S32), C.c_int(E), _ptr(e) if E else nul, _ptr(Z32) if E else nul,
+                                _ptr(w) if w is not None and E else nul, _ptr(fx) if fx is not None else nul, C.byref(prm),
+                                _ptr(es) if E else nul, _ptr(ec) if E else nul, _ptr(rounds) if len(rounds) else nul, C.byref(st)))
+    return S32.transpose(0, 2, 1).copy(), st.as_dict(), rounds, es, ec
+
+
+def rigid_pose(S):
+    """The rigid pose that goes with a similarity S = [c R | t] of the pose graph: [R | t / c], on the host in double.  A map point
+    moved by S_new^-1 S_old of its reference frame projects there, under rigid_pose(S_new), where it projected before."""
+    S = np.asarray(S, np.float64).reshape(4, 4)
+    M = S[:3, :3]
+    c = np.cbrt(np.linalg.det(M))
+    out = np.eye(4)
+    out[:3, :3] = M / c
+    out[:3, 3] = S[:3, 3] / c
+    return out
 
 
 def similarity_pose(T, S):

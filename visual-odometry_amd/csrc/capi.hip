@@ -207,7 +207,7 @@ int vo_ctx_destroy(vo_ctx* c) {
   (void)hipStreamSynchronize(c->stream);
   c->scratch.release(); c->best.release(); c->table.release(); c->counts.release();
   c->batch_pack.release(); c->batch_bad.release(); c->prune_ws.release(); c->epi_ws.release(); c->ransac_ws.release(); c->pose_ws.release();
-  c->pose_batch_ws.release(); c->track_ws.release(); c->refine_ws.release();
+  c->pose_batch_ws.release(); c->track_ws.release(); c->refine_ws.release(); c->pose_graph_ws.release();
   if (c->hint_ev) (void)hipEventDestroy(c->hint_ev);
   if (c->hint_host) (void)hipHostFree(c->hint_host);
   if (c->hint_dev) (void)hipFree(c->hint_dev); c->batch_states.release(); c->batch_partials.release(); c->batch_help.release();

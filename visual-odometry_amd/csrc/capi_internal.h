@@ -77,6 +77,7 @@ struct vo_ctx {
   DevBuf pose_batch_ws;   // ... and for vo_estimate_pose_ransac_batch_dev (all problems' blocks)
   DevBuf refine_ws;   // state and workgroup rows of vo_refine_transform_dev
   DevBuf track_ws;    // vo_frames_batch_track_dev: the moved cloud, the tracked pairs and the winners the caller did not ask for
+  DevBuf pose_graph_ws;   // voe_pose_graph*: the state in double, the edges' records, the incidence lists and the PCG vectors
   // Steering of the automatic matcher by what the previous batched call found: after a call that ran the
   // exact-duplicate pass, "did any frame take it?" travels to pinned host memory behind the call (no wait); a later call
   // that finds the answer "none" there leaves the pass out for the next HINT_SKIP calls, then probes again.  Data whose

@@ -1,5 +1,5 @@
 // capi_map.hip -- the map's half of the extern "C" boundary (vo_hip.h: vo_map_*; vo_map_adjust.h, vo_map_bundle.h, vo_map_cull.h,
-// vo_map_align.h, vo_map_covis.h, vo_map_grow.h).  Host-side plumbing only, like capi.hip: no kernel lives here.
+// vo_map_align.h, vo_map_covis.h, vo_map_grow.h) and the pose graph's (vo_pose_graph.h).  Host-side plumbing only, like capi.hip: no kernel lives here.
 #include <limits.h>
 #include <string.h>
 
@@ -1215,6 +1215,123 @@ int voe_map_window(vo_map* m, int n_frames, int n_words, const uint32_t* bits, c
   if (order_out) VO_HIP_CHECK(hipMemcpyAsync(order_out, d + o_order, 4 * F, hipMemcpyDeviceToHost, c->stream));
   if (union_out) VO_HIP_CHECK(hipMemcpyAsync(union_out, d + o_union, 4 * W, hipMemcpyDeviceToHost, c->stream));
   VO_HIP_CHECK(hipMemcpyAsync(stats_out, d + o_stats, sizeof(voe_map_window_stats), hipMemcpyDeviceToHost, c->stream));
+  VO_HIP_CHECK(hipStreamSynchronize(c->stream));
+  return VO_OK;
+}
+
+// ---- the pose graph over similarities (pose_graph.hip; include/vo_pose_graph.h) -- a context and no map ----------------------
+static_assert(sizeof(voe_pose_graph_params) == 28 && sizeof(voe_pose_graph_round) == 40 && sizeof(voe_pose_graph_stats) == 48,
+              "the records of include/vo_pose_graph.h as the kernels write them");
+
+int voe_pose_graph_dev(vo_ctx* c, int n_frames, float* d_S16, int n_edges, const int32_t* d_edges, const float* d_Z16,
+                       const float* d_weights, const uint8_t* d_fixed, const voe_pose_graph_params* p, int32_t* d_edge_status_out,
+                       double* d_edge_cost_out, voe_pose_graph_round* d_rounds_out, voe_pose_graph_stats* d_stats) {
+  const char* fn = "voe_pose_graph_dev";
+  VO_REQUIRE(c, "null context");
+  VO_REQUIRE(ctx_alive(c), "the context has been destroyed");
+  if (int r = pose_graph_check(fn, n_frames, n_edges, PoseGraphPtrs{d_S16, d_edges, d_Z16, d_weights, d_edge_status_out, d_edge_cost_out, d_rounds_out, d_stats}, p))
+    return r;
+  const size_t need = pose_graph_layout(nullptr, n_frames, n_edges).bytes;
+  if (int r = capture_growth_check(c->capturing, fn, {{c->pose_graph_ws.cap, need}}, "at least %d frames and %d edges", n_frames, n_edges)) return r;
+  if (!c->capturing)
+    if (int r = set_device(c)) return r;
+  VO_HIP_CHECK(c->pose_graph_ws.ensure(need, c->stream));
+  PoseGraphArgs a{};
+  a.w = pose_graph_layout(c->pose_graph_ws.p, n_frames, n_edges);
+  a.n_frames = n_frames; a.n_edges = n_edges;
+  a.S16 = d_S16; a.edges = d_edges; a.Z16 = d_Z16; a.weights = d_weights; a.fixed = d_fixed;
+  a.n_rounds = p->n_rounds; a.n_cg = p->n_cg; a.with_scale = p->with_scale != 0; a.precond = p->preconditioner;
+  a.cg_tol = p->cg_tol; a.lambda0 = p->lambda0; a.huber = p->huber;
+  a.edge_status_out = d_edge_status_out; a.edge_cost_out = d_edge_cost_out; a.rounds_out = d_rounds_out; a.stats = d_stats;
+  VO_HIP_CHECK(launch_pose_graph(c->stream, a));
+  return VO_OK;
+}
+
+int voe_pose_graph(vo_ctx* c, int n_frames, float* S16, int n_edges, const int32_t* edges, const float* Z16, const float* weights,
+                   const uint8_t* fixed, const voe_pose_graph_params* params, int32_t* edge_status_out, double* edge_cost_out,
+                   voe_pose_graph_round* rounds_out, voe_pose_graph_stats* stats_out) {
+  const char* fn = "voe_pose_graph";
+  VO_REQUIRE(c, "null context");
+  VO_REQUIRE(ctx_alive(c), "the context has been destroyed");
+  VO_NOT_CAPTURING(c);
+  alignas(8) static const char aligned_stand_in[8] = {};      // the host's own arrays need no device alignment: the staging has it
+  if (int r = pose_graph_check(fn, n_frames, n_edges, PoseGraphPtrs{S16 ? aligned_stand_in : nullptr, edges ? aligned_stand_in : nullptr,
+                                                                    Z16 ? aligned_stand_in : nullptr, nullptr, nullptr, nullptr, nullptr,
+                                                                    stats_out ? aligned_stand_in : nullptr}, params))
+    return r;
+  if (int r = set_device(c)) return r;
+  const size_t F = (size_t)n_frames, E = (size_t)n_edges, R = (size_t)params->n_rounds;
+  if (int r = upload(c, c->in[0], S16, sizeof(float) * 16 * F)) return r;
+  if (int r = upload(c, c->in[1], edges, sizeof(int32_t) * 2 * E)) return r;
+  if (int r = upload(c, c->in[2], Z16, sizeof(float) * 16 * E)) return r;
+  if (weights)
+    if (int r = upload(c, c->in[3], weights, sizeof(float) * 3 * E)) return r;
+  if (fixed)
+    if (int r = upload(c, c->in[4], fixed, F)) return r;
+  VO_HIP_CHECK(c->out[0].ensure(sizeof(int32_t) * (E ? E : 1), c->stream));
+  VO_HIP_CHECK(c->out[1].ensure(sizeof(double) * (E ? E : 1), c->stream));
+  VO_HIP_CHECK(c->out[2].ensure(sizeof(voe_pose_graph_stats) + sizeof(voe_pose_graph_round) * R + 16, c->stream));
+  voe_pose_graph_stats* d_st = c->out[2].as<voe_pose_graph_stats>();
+  voe_pose_graph_round* d_rd = reinterpret_cast<voe_pose_graph_round*>(d_st + 1);
+  if (int r = voe_pose_graph_dev(c, n_frames, c->in[0].as<float>(), n_edges, E ? c->in[1].as<int32_t>() : nullptr, E ? c->in[2].as<float>() : nullptr,
+                                 weights ? c->in[3].as<float>() : nullptr, fixed ? c->in[4].as<uint8_t>() : nullptr, params,
+                                 edge_status_out ? c->out[0].as<int32_t>() : nullptr, edge_cost_out ? c->out[1].as<double>() : nullptr,
+                                 rounds_out && R ? d_rd : nullptr, d_st))
+    return r;
+  VO_HIP_CHECK(hipMemcpyAsync(stats_out, d_st, sizeof(voe_pose_graph_stats), hipMemcpyDeviceToHost, c->stream));
+  if (rounds_out && R) VO_HIP_CHECK(hipMemcpyAsync(rounds_out, d_rd, sizeof(voe_pose_graph_round) * R, hipMemcpyDeviceToHost, c->stream));
+  VO_HIP_CHECK(hipMemcpyAsync(S16, c->in[0].p, sizeof(float) * 16 * F, hipMemcpyDeviceToHost, c->stream));
+  if (edge_status_out && E) VO_HIP_CHECK(hipMemcpyAsync(edge_status_out, c->out[0].p, sizeof(int32_t) * E, hipMemcpyDeviceToHost, c->stream));
+  if (edge_cost_out && E) VO_HIP_CHECK(hipMemcpyAsync(edge_cost_out, c->out[1].p, sizeof(double) * E, hipMemcpyDeviceToHost, c->stream));
+  VO_HIP_CHECK(hipStreamSynchronize(c->stream));
+  return VO_OK;
+}
+
+// ---- the correction carried into the map (pose_graph.hip; include/vo_pose_graph.h): the lookup, the keys, the move -------------
+static_assert(sizeof(voe_map_apply_stats) == 16, "the move kernel writes four 4-byte words");
+
+int voe_map_apply_correction_batch_dev(vo_map* m, int n_frames, const float* d_uv, size_t uv_stride, const float* d_app, size_t app_stride,
+                                       int n_max, const int* d_n, const float* d_S16_old, const float* d_S16_new, int dry_run,
+                                       int32_t* d_ref_frame_out, voe_map_apply_stats* d_stats) {
+  VO_MAP_LIVE(m);
+  const char* fn = "voe_map_apply_correction_batch_dev";
+  (void)d_uv; (void)uv_stride;
+  if (int r = map_apply_check(fn, n_frames, d_app, app_stride, n_max, d_S16_old, d_S16_new, d_ref_frame_out, d_stats)) return r;
+  const MapFrames f{n_frames, nullptr, nullptr, (size_t)n_max, d_app, app_stride, n_max, d_n};
+  MapRefineWs w;
+  if (int r = refine_prepare(fn, m, f, &w)) return r;         // the one lookup of the call (and the capture rule of the workspaces)
+  MapApplyArgs a{};
+  a.ent = w.ent; a.key = w.cnt;
+  a.pts = m->d.pts; a.hdr = m->d.hdr; a.cap = m->d.cap; a.bound = map_launch_bound(m);
+  a.n_frames = n_frames; a.n_max = n_max; a.S_old = d_S16_old; a.S_new = d_S16_new; a.dry_run = dry_run != 0;
+  a.ref_frame_out = d_ref_frame_out; a.stats = reinterpret_cast<int*>(d_stats);
+  VO_HIP_CHECK(launch_map_apply_correction(m->ctx->stream, a));
+  return VO_OK;
+}
+
+int voe_map_apply_correction(vo_map* m, int n_frames, const float* uv, const float* app, const int* n_rows, int n_max, const float* S16_old,
+                             const float* S16_new, int dry_run, int32_t* ref_frame_out, voe_map_apply_stats* stats_out) {
+  VO_MAP_LIVE(m);
+  vo_ctx* c = m->ctx;
+  VO_NOT_CAPTURING(c);
+  (void)uv;
+  VO_REQUIRE(S16_old && S16_new && stats_out, "null argument");
+  MapFrames f;
+  int size = 0;
+  if (int r = upload_window(__func__, m, MapFrames{n_frames, nullptr, nullptr, 0, app, 0, n_max, n_rows}, nullptr, nullptr, &size, &f)) return r;
+  const size_t F = (size_t)n_frames;
+  if (int r = upload(c, c->in[2], S16_old, sizeof(float) * 16 * F)) return r;
+  if (int r = upload(c, c->in[5], S16_new, sizeof(float) * 16 * F)) return r;
+  VO_HIP_CHECK(c->out[0].ensure(sizeof(int32_t) * (size_t)(size > 0 ? size : 1), c->stream));
+  VO_HIP_CHECK(c->out[2].ensure(64, c->stream));
+  VO_HIP_CHECK(hipStreamSynchronize(c->stream));          // the host arrays may go away after the call
+  if (int r = voe_map_apply_correction_batch_dev(m, n_frames, nullptr, f.uv_stride, f.d_app, f.app_stride, n_max, f.d_n, c->in[2].as<float>(),
+                                                 c->in[5].as<float>(), dry_run, ref_frame_out ? c->out[0].as<int32_t>() : nullptr,
+                                                 c->out[2].as<voe_map_apply_stats>()))
+    return r;
+  VO_HIP_CHECK(hipMemcpyAsync(stats_out, c->out[2].p, sizeof(voe_map_apply_stats), hipMemcpyDeviceToHost, c->stream));
+  if (ref_frame_out && size > 0)
+    VO_HIP_CHECK(hipMemcpyAsync(ref_frame_out, c->out[0].p, sizeof(int32_t) * (size_t)size, hipMemcpyDeviceToHost, c->stream));
   VO_HIP_CHECK(hipStreamSynchronize(c->stream));
   return VO_OK;
 }

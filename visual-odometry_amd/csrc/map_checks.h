@@ -109,6 +109,55 @@ static inline int map_grow_room(const voe_map_grow_params* p, int n_frames, int 
   return (int)(a > 0 ? a : 1);
 }
 
+// voe_pose_graph*: what the call refuses (include/vo_pose_graph.h), in the order they fire:
+//   1. a null d_S16, params or d_stats      2. n_frames < 1 or negative n_edges      3. null edges or measurements with n_edges > 0
+//   4. a float32 / int32 array off a 4-byte boundary, the edge costs, the rounds' records or d_stats off an 8-byte one
+//   5. negative n_rounds, n_cg < 1      6. cg_tol, lambda0 or huber negative or not finite      7. too many steps
+//   8. an unknown preconditioner
+struct PoseGraphPtrs {
+  const void *S16, *edges, *Z16, *weights, *edge_status, *edge_cost, *rounds, *stats;
+};
+static inline int pose_graph_check(const char* fn, int n_frames, int n_edges, const PoseGraphPtrs& d, const voe_pose_graph_params* p) {
+  if (!(d.S16 && p && d.stats)) return vo_fail(VO_ERR_INVALID_ARG, "%s: null argument", fn);
+  if (n_frames < 1) return vo_fail(VO_ERR_INVALID_ARG, "%s: n_frames must be at least 1", fn);
+  if (n_edges < 0) return vo_fail(VO_ERR_INVALID_ARG, "%s: negative n_edges", fn);
+  if (n_frames > (1 << 24) || n_edges > (1 << 24)) return vo_fail(VO_ERR_INVALID_ARG, "%s: more than 2^24 frames or edges", fn);
+  if (n_edges > 0 && !(d.edges && d.Z16)) return vo_fail(VO_ERR_INVALID_ARG, "%s: null edges or measurements", fn);
+  const uintptr_t four = reinterpret_cast<uintptr_t>(d.S16) | reinterpret_cast<uintptr_t>(d.edges) | reinterpret_cast<uintptr_t>(d.Z16) |
+                         reinterpret_cast<uintptr_t>(d.weights) | reinterpret_cast<uintptr_t>(d.edge_status);
+  if (four & 3u) return vo_fail(VO_ERR_INVALID_ARG, "%s: float32 and int32 arrays must be 4-byte aligned", fn);
+  if (!aligned8(d.edge_cost, d.rounds, d.stats)) return vo_fail(VO_ERR_INVALID_ARG, "%s: d_edge_cost_out, d_rounds_out and d_stats must be 8-byte aligned", fn);
+  if (p->n_rounds < 0) return vo_fail(VO_ERR_INVALID_ARG, "%s: negative n_rounds", fn);
+  if (p->n_cg < 1) return vo_fail(VO_ERR_INVALID_ARG, "%s: n_cg must be at least 1", fn);
+  if (!(p->cg_tol >= 0.f && p->cg_tol <= 3.402823466e38f)) return vo_fail(VO_ERR_INVALID_ARG, "%s: cg_tol must be finite and not negative", fn);
+  if (!(p->lambda0 >= 0.f && p->lambda0 <= 3.402823466e38f)) return vo_fail(VO_ERR_INVALID_ARG, "%s: lambda0 must be finite and not negative", fn);
+  if (!(p->huber >= 0.f && p->huber <= 3.402823466e38f)) return vo_fail(VO_ERR_INVALID_ARG, "%s: huber must be finite and not negative", fn);
+  if ((long long)p->n_rounds * ((long long)p->n_cg + 2) > VOE_POSE_GRAPH_MAX_STEPS)
+    return vo_fail(VO_ERR_INVALID_ARG, "%s: n_rounds * (n_cg + 2) above %d (the launches of a call are a fixed sequence)", fn, VOE_POSE_GRAPH_MAX_STEPS);
+  if (p->preconditioner != VOE_POSE_GRAPH_CHAIN && p->preconditioner != VOE_POSE_GRAPH_JACOBI)
+    return vo_fail(VO_ERR_INVALID_ARG, "%s: unknown preconditioner %d", fn, p->preconditioner);
+  return VO_OK;
+}
+
+// voe_map_apply_correction*: what the call refuses (include/vo_pose_graph.h), in the order they fire:
+//   1. a null matrix array or d_stats      2. n_frames outside 1 .. 65535, negative n_max      3. null appearances with n_max > 0
+//   4. d_app or d_stats off an 8-byte boundary, a matrix array or d_ref_frame_out off a 4-byte one      5. app_stride < n_max
+//   6. app_stride >= (2^31 - 1) / 10 or more than 2^30 rows
+static inline int map_apply_check(const char* fn, int n_frames, const float* d_app, size_t app_stride, int n_max, const float* d_S16_old,
+                                  const float* d_S16_new, const void* d_ref_frame_out, const void* d_stats) {
+  if (!(d_S16_old && d_S16_new && d_stats)) return vo_fail(VO_ERR_INVALID_ARG, "%s: null argument", fn);
+  if (n_frames < 1 || n_frames > 65535) return vo_fail(VO_ERR_INVALID_ARG, "%s: n_frames %d outside 1 .. 65535 (the frame is a grid dimension)", fn, n_frames);
+  if (n_max < 0) return vo_fail(VO_ERR_INVALID_ARG, "%s: negative row count", fn);
+  if (n_max > 0 && !d_app) return vo_fail(VO_ERR_INVALID_ARG, "%s: null appearances", fn);
+  if (!aligned8(d_app) || (reinterpret_cast<uintptr_t>(d_stats) & 7u)) return vo_fail(VO_ERR_INVALID_ARG, "%s: device arrays must be 8-byte aligned", fn);
+  if ((reinterpret_cast<uintptr_t>(d_S16_old) | reinterpret_cast<uintptr_t>(d_S16_new) | reinterpret_cast<uintptr_t>(d_ref_frame_out)) & 3u)
+    return vo_fail(VO_ERR_INVALID_ARG, "%s: the matrices and d_ref_frame_out must be 4-byte aligned", fn);
+  if (app_stride < (size_t)n_max) return vo_fail(VO_ERR_INVALID_ARG, "%s: a stride is smaller than n_max", fn);
+  if (app_stride >= 0x7fffffff / 10 || (long long)n_max * n_frames > (1ll << 30))
+    return vo_fail(VO_ERR_INVALID_ARG, "%s: more than 2^30 rows in one call", fn);
+  return VO_OK;
+}
+
 // A workspace that would have to grow inside a graph capture: growing frees, allocates and waits.  `ws` lists the buffers the
 // call sizes, each with its capacity and what the call needs; `tail` (printf form) names the call that sizes them outside a
 // capture.  The callers ask BEFORE they enqueue anything: a HIP call refused later would invalidate the capture.

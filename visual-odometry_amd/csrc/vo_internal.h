@@ -1016,4 +1016,66 @@ size_t pose_ransac_batch_workspace_bytes(int n_problems, int n_max, int n_hyp);
 PoseRansacBatchArgs pose_ransac_batch_layout(void* ws, int n_problems, int n_max, int n_hyp, size_t* bytes = nullptr);
 hipError_t launch_pose_ransac_batch(hipStream_t st, const PoseRansacBatchArgs& b);
 
+// ---- the pose graph over similarities (pose_graph.hip, voe_pose_graph*) ------------------------------------------------------
+constexpr int POSE_GRAPH_REC = 30;      // doubles of an edge's record: M_A, t_A, c_A, t_E, the seven weights, the seven residuals
+// the control block of a call: written by the one-workgroup launches alone
+struct PoseGraphCtl {
+  double lambda, cost_cur, cost_start, rz, rr0, rr;
+  int status;                           // the call status decided at the start (VOE_POSE_GRAPH_*), 0 while alive
+  int dead;                             // NOT_FINITE, NOTHING_FREE or NO_EDGES: no round runs
+  int bad;                              // this round: a pivot of JACOBI is not > 0
+  int stop;                             // this round: PCG has stopped, its remaining launches return at once
+  int nostep;                           // this round: PCG could not take one iteration
+  int iters;                            // this round: PCG iterations taken
+  int n_accepted, n_free, n_active, n_live;
+};
+struct PoseGraphWs {
+  int *cnt, *cur;                       // [n_frames] incidences per frame -> offset inside its block of 256 frames; scatter cursors = the counts
+  double *T, *Tc;                       // [n_frames][12] state / candidate: M column-major, then t
+  double* rec;                          // [n_edges][POSE_GRAPH_REC] the edges' records at the state
+  double *ecost, *ecost_c, *es2_start;  // [n_edges][2] (s^2, its cost) at the state / of the last evaluation of Tc; [n_edges] s^2 of the start
+  double* y;                            // [n_edges][7]
+  double *r, *x, *z, *p, *q, *tmp;      // [n_frames][7] the PCG vectors; q = (H + lambda diag H) p; tmp: CHAIN between its two sums
+  double *pq, *H, *W;                   // [n_frames] p_f . q_f; [n_frames][28] H_ff, upper triangle row by row; [n_frames][3] CHAIN's W_f
+  int *blk, *total;                     // [ceil(n_frames / 256)] block totals -> block offsets; [1] incidences in all
+  int *lst_tmp, *keys;                  // [2 n_edges] incidences (2 e + side) as scattered / every frame's segment in ascending order
+  int32_t *estatus, *fstat;             // [n_edges] VOE_POSE_GRAPH_EDGE_*; [n_frames] active / held / isolated
+  PoseGraphCtl* ctl;
+  size_t bytes;
+};
+PoseGraphWs pose_graph_layout(void* base, int n_frames, int n_edges);
+struct PoseGraphArgs {
+  PoseGraphWs w;
+  int n_frames, n_edges;
+  float* S16;                           // [n_frames][16] in and, for the active frames, out
+  const int32_t* edges;                 // [n_edges][2]
+  const float* Z16;                     // [n_edges][16]
+  const float* weights;                 // [n_edges][3] or null
+  const uint8_t* fixed;                 // [n_frames] or null
+  int n_rounds, n_cg, with_scale, precond;
+  double cg_tol, lambda0, huber;
+  int32_t* edge_status_out;             // or null
+  double* edge_cost_out;                // or null
+  void* rounds_out;                     // [n_rounds] voe_pose_graph_round, or null
+  void* stats;                          // voe_pose_graph_stats
+};
+// the lists, the start, then the fixed sequence of 3 (n_cg + 2) launches per round, the rounding and the verdict
+hipError_t launch_pose_graph(hipStream_t st, const PoseGraphArgs& a);
+
+
+// ---- a trajectory's correction carried into the map (pose_graph.hip, voe_map_apply_correction*) ------------------------------
+constexpr int MAP_APPLY_NO_KEY = 0x7f7f7f7f;     // what a memset of 0x7f leaves: above every key f * n_max + i (at most 2^30)
+struct MapApplyArgs {
+  const int32_t* ent;                   // [n_frames][n_max] the lookup's entry per query position, -1: none
+  int* key;                             // [bound] the smallest key that sees the entry (set to MAP_APPLY_NO_KEY before the launches)
+  float* pts; const int* hdr; int cap, bound;
+  int n_frames, n_max;
+  const float *S_old, *S_new;           // [n_frames][16] column-major
+  int dry_run;
+  int32_t* ref_frame_out;               // [size] or null
+  int* stats;                           // voe_map_apply_stats, zeroed before the launches
+};
+// the keys (an integer atomicMin: exact), then the move of every entry and the statistics
+hipError_t launch_map_apply_correction(hipStream_t st, const MapApplyArgs& a);
+
 }  // namespace vo
