@@ -4,7 +4,9 @@
 // frames in the map of world.dat (Z = T_j T_i^-1), ONE voe_pose_graph call distributes them over the chain with frame 0 held,
 // and ONE voe_map_apply_correction call carries the correction into the map that belongs to the drifted chain (every landmark
 // where the drifted pose of the first frame that sees it puts it).
-//   usage: close_loop <data dir> [--seed=1] [--loops=4] [--gap=50] [--jacobi]
+// With --from-map the loop edges come from ONE voe_map_loops call on that drifted map and the drifted chain instead: no
+// localisation in world.dat and no ranking on the host -- what a running system, which has only its own map, can do.
+//   usage: close_loop <data dir> [--seed=1] [--loops=4] [--gap=50] [--jacobi] [--from-map]
 // Printed: the loop edges, the optimiser's rounds, the camera-centre error and the map's distance to world.dat before and after.
 // Exit 0 iff every call's status is OK and the median camera-centre error falls below a fifth of what it was (the float64
 // restatement of the same experiment, tests/test_pose_graph_cpu.py, gives 0.054 of it).
@@ -60,18 +62,20 @@ double median(std::vector<double> v) { std::sort(v.begin(), v.end()); return v.e
 int main(int argc, char* argv[]) {
   unsigned seed = 1;
   int n_loops = 4, gap = 50;
+  bool from_map = false, loops_given = false;
   vo::PoseGraphOptions opt;
   std::vector<std::string> pos;
   for (int i = 1; i < argc; ++i) {
     const std::string s(argv[i]);
     if (s.rfind("--seed=", 0) == 0) seed = (unsigned)std::atoi(s.c_str() + 7);
-    else if (s.rfind("--loops=", 0) == 0) n_loops = std::atoi(s.c_str() + 8);
+    else if (s.rfind("--loops=", 0) == 0) { n_loops = std::atoi(s.c_str() + 8); loops_given = true; }
     else if (s.rfind("--gap=", 0) == 0) gap = std::atoi(s.c_str() + 6);
     else if (s == "--jacobi") opt.preconditioner = VOE_POSE_GRAPH_JACOBI;
+    else if (s == "--from-map") from_map = true;
     else if (s.rfind("--", 0) == 0) { std::printf("unknown option %s\n", s.c_str()); return -1; }
     else pos.push_back(s);
   }
-  if (pos.empty()) { std::printf("usage: close_loop <data dir> [--seed=1] [--loops=4] [--gap=50] [--jacobi]\n"); return -1; }
+  if (pos.empty()) { std::printf("usage: close_loop <data dir> [--seed=1] [--loops=4] [--gap=50] [--jacobi] [--from-map]\n"); return -1; }
   std::string path = pos[0];
   if (path.back() != '/') path.push_back('/');
   try {
@@ -113,11 +117,13 @@ int main(int argc, char* argv[]) {
     // the loop edges: the pairs the covisibility ranks highest beyond the gap, measured by localising both frames in world.dat
     vo::DeviceMap world((int)world_app.size());
     world.update(world_xyz, world_app);
-    const vo::Covisibility cov = world.covisibility(apps);
     std::vector<std::pair<int, std::pair<int, int>>> ranked;
-    for (size_t i = 0; i < F; ++i)
-      for (size_t j = i + (size_t)gap + 1; j < F; ++j) ranked.push_back({-cov.shared(i, j), {(int)i, (int)j}});
-    std::sort(ranked.begin(), ranked.end());
+    if (!from_map) {                                          // (--from-map neither ranks on the host nor localises in world.dat)
+      const vo::Covisibility cov = world.covisibility(apps);
+      for (size_t i = 0; i < F; ++i)
+        for (size_t j = i + (size_t)gap + 1; j < F; ++j) ranked.push_back({-cov.shared(i, j), {(int)i, (int)j}});
+      std::sort(ranked.begin(), ranked.end());
+    }
     const vo::Camera cam = data.camera();
     int taken = 0;
     bool ok = true;
@@ -132,7 +138,7 @@ int main(int argc, char* argv[]) {
       graph.addEdge(i, j, sim(mul(from(Tj), inv(from(Ti)))));
       ++taken;
     }
-    if (taken == 0) { std::printf("no loop edge could be measured\n"); return 1; }
+    if (!from_map && taken == 0) { std::printf("no loop edge could be measured\n"); return 1; }
 
     // the map that belongs to the drifted chain: every landmark where the drifted pose of the first frame that sees it puts it
     std::vector<int32_t> first(world_xyz.size(), -1);
@@ -150,10 +156,27 @@ int main(int argc, char* argv[]) {
     }
     vo::DeviceMap map((int)world_app.size());
     map.update(drifted, world_app);
-
-    // optimise, then carry the correction into the map
     std::vector<vo::Similarity3f> S_old, S_new;
     for (const M4& s : S) S_old.push_back(sim(s));
+
+    // --from-map: the loop edges as the drifted map itself shows them, found and measured by one call
+    if (from_map) {
+      vo::LoopsOptions lo;
+      lo.gap = gap;
+      if (loops_given) lo.max_loops = n_loops;
+      const vo::MapLoops found = map.loops(cam, pixels, apps, S_old, lo);
+      std::printf("voe_map_loops: %d candidates, %d survivors, %d slots, %d measured\n", found.stats.n_candidates, found.stats.n_survivors, found.stats.n_slots,
+                  found.stats.n_ok);
+      for (const voe_map_loop_record& r : found.loops)
+        if (r.status != VOE_MAP_LOOP_EMPTY)
+          std::printf("loop %d - %d: %d landmarks in the band, %d pairs, %d RANSAC inliers, %d solver inliers, %s\n", r.i, r.j, r.c, r.n_pairs, r.ransac_inliers,
+                      r.num_inliers, vo::loop_status_name(r.status));
+      graph.addLoops(found);
+      taken = found.stats.n_ok;
+      if (taken == 0) { std::printf("no loop edge could be measured\n"); return 1; }
+    }
+
+    // optimise, then carry the correction into the map
     S_new = S_old;
     std::vector<uint8_t> fixed(F, 0);
     fixed[0] = 1;

@@ -187,6 +187,30 @@ inline Isometry3f similarity_pose(const Isometry3f& T, const Similarity3f& S) {
   return out;
 }
 
+//! voe_map_loops: the loop edges a drifted map shows (include/vo_map_loops.h)
+struct LoopsOptions {
+  int gap = 50;                      //!< a loop (i, j) has i < j - gap
+  int ref_window = 5;                //!< the band of i: the entries whose reference frame lies in [i - ref_window, i]
+  int min_shared = 12;               //!< entries of the band frame j must see
+  int separation = 3;                //!< candidates this close suppress each other
+  int max_loops = 8;                 //!< slots
+  LocaliseOptions measure;           //!< the P3P RANSAC and the PICP rounds of every slot
+  float w_loop[3] = {1.f, 1.f, 1.f}; //!< (w_t, w_r, w_s) of every OK edge
+};
+struct MapLoops {
+  std::vector<int32_t> edges;        //!< [max_loops][2] (i, j); (-1, -1) for an empty slot
+  std::vector<Similarity3f> Z;       //!< [max_loops] Z_ij ~ S_j S_i^-1; the identity unless the slot is OK
+  std::vector<float> weights;        //!< [max_loops][3]; 0 0 0 unless the slot is OK: voe_pose_graph skips such an edge
+  std::vector<voe_map_loop_record> loops;   //!< [max_loops]
+  std::vector<int32_t> hist;         //!< [n_frames][n_frames], or empty when not asked for
+  std::vector<int32_t> ref_frame;    //!< [map size], or empty when not asked for
+  voe_map_loops_stats stats{};
+};
+inline const char* loop_status_name(int status) {
+  static const char* names[] = {"OK", "FEW_MATCHES", "NO_CONSENSUS", "FEW_INLIERS", "NOT_FINITE", "EMPTY"};
+  return status >= 0 && status < 6 ? names[status] : "?";
+}
+
 //! The rigid pose that goes with a similarity S = [c R | t] of the pose graph (vo/pose_graph.hpp): [R | t / c], on the host in
 //! double.  A map point moved by S_new^-1 S_old of its reference frame (DeviceMap::applyCorrection) projects there, under
 //! rigid_pose(S_new), where it projected before.
@@ -498,6 +522,44 @@ class DeviceMap {
     ref.resize((size_t)st.n_entries);
     if (ref_frame) *ref_frame = ref;
     return st;
+  }
+
+  //! the loop edges this map shows (voe_map_loops): frame j's candidate is the i < j - gap whose band holds the most entries j
+  //! sees; the best max_loops candidates are measured by P3P RANSAC + PICP of frame j against the band of i, and the result goes
+  //! to PoseGraph::addLoops.  S: the drifted similarities, one per frame (p_cam = S p_map).  The map is not written.
+  MapLoops loops(const Camera& cam, const std::vector<Vector2fVector>& pixels, const std::vector<Vector10fVector>& appearances,
+                 const std::vector<Similarity3f>& S, const LoopsOptions& opt = LoopsOptions(), bool want_hist = false, bool want_ref_frame = false) const {
+    const size_t F = pixels.size();
+    if (appearances.size() != F || S.size() != F) throw Error(VO_ERR_INVALID_ARG, "DeviceMap::loops: per-frame arrays differ in size");
+    size_t cap = 1;
+    for (size_t f = 0; f < F; ++f) {
+      if (pixels[f].size() != appearances[f].size()) throw Error(VO_ERR_INVALID_ARG, "DeviceMap::loops: pixels and appearances differ in size");
+      if (pixels[f].size() > cap) cap = pixels[f].size();
+    }
+    std::vector<float> uv(F * cap * 2 + 2, 0.f), app(F * cap * 10 + 10, 0.f);
+    std::vector<int> n(F + 1, 0);
+    for (size_t f = 0; f < F; ++f) {
+      n[f] = (int)pixels[f].size();
+      for (size_t i = 0; i < pixels[f].size(); ++i) {
+        for (int k = 0; k < 2; ++k) uv[(f * cap + i) * 2 + k] = pixels[f][i][k];
+        for (int k = 0; k < 10; ++k) app[(f * cap + i) * 10 + k] = appearances[f][i][k];
+      }
+    }
+    const size_t L = (size_t)(opt.max_loops > 0 ? opt.max_loops : 1);
+    MapLoops out;
+    out.edges.assign(2 * L, -1); out.Z.assign(L, Similarity3f::Identity()); out.weights.assign(3 * L, 0.f); out.loops.assign(L, voe_map_loop_record{});
+    if (want_hist) out.hist.assign((F ? F : 1) * (F ? F : 1), 0);
+    if (want_ref_frame) out.ref_frame.assign((size_t)size() + 1, -1);
+    voe_map_loops_params prm{};
+    prm.gap = opt.gap; prm.ref_window = opt.ref_window; prm.min_shared = opt.min_shared; prm.separation = opt.separation; prm.max_loops = opt.max_loops;
+    prm.ransac = opt.measure.ransac; prm.kernel_threshold = opt.measure.kernel_threshold; prm.n_iters = opt.measure.n_iters;
+    prm.min_inliers = opt.measure.min_inliers;
+    for (int k = 0; k < 3; ++k) prm.w_loop[k] = opt.w_loop[k];
+    check(voe_map_loops(h_, (int)F, cam.rows(), cam.cols(), cam.zNear(), cam.zFar(), cam.cameraMatrix().data(), uv.data(), app.data(), n.data(), (int)cap,
+                        F ? S[0].m : nullptr, &prm, out.edges.data(), out.Z[0].m, out.weights.data(), out.loops.data(),
+                        want_hist ? out.hist.data() : nullptr, want_ref_frame ? out.ref_frame.data() : nullptr, &out.stats), "voe_map_loops");
+    if (want_ref_frame) out.ref_frame.resize((size_t)out.stats.n_entries);
+    return out;
   }
 
   //! the local window of frame `query` (voe_map_window) from the bit rows of covisibility(): the frames to free, the frames to

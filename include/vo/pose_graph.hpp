@@ -36,6 +36,11 @@ class PoseGraph {
     Z_.push_back(Z);
     weights_.push_back(w_t); weights_.push_back(w_r); weights_.push_back(w_s);
   }
+  //! every slot of DeviceMap::loops, in order: a slot that is not OK carries the weights 0 0 0 and is skipped by the optimiser
+  void addLoops(const MapLoops& r) {
+    for (size_t l = 0; l < r.Z.size(); ++l)
+      addEdge(r.edges[2 * l], r.edges[2 * l + 1], r.Z[l], r.weights[3 * l], r.weights[3 * l + 1], r.weights[3 * l + 2]);
+  }
   size_t edges() const { return Z_.size(); }
   void clear() { edges_.clear(); Z_.clear(); weights_.clear(); }
 

@@ -878,4 +878,5 @@ int vo_map_refine(vo_map *m, int n_frames, const float K[9], const float *uv, co
 #include "vo_map_covis.h"
 #include "vo_map_grow.h"
 #include "vo_pose_graph.h"
+#include "vo_map_loops.h"
 #endif /* VO_HIP_H */

@@ -830,6 +830,65 @@ class Map:
                                                C.c_int(int(bool(dry_run))), _ptr(ref), C.byref(st)))
         return ref[: st.n_entries].copy(), st.as_dict()
 
+    # ---- loop edges found and measured in the map (voe_map_loops*, include/vo_map_loops.h) ----
+    def loops_batch_dev(self, camera: Camera, n_frames, d_uv, uv_stride, d_app, app_stride, n_max, d_n, d_S16, params: "MapLoopsParams",
+                        d_edges_out, d_Z16_out, d_weights_out, d_loops_out, d_hist_out, d_ref_frame_out, d_stats):
+        """voe_map_loops_batch_dev on device pointers (ints; d_n, d_hist_out and d_ref_frame_out may be None; strides in pixels /
+        rows): enqueues and returns.  With L = params.max_loops: d_edges_out L x 2 int32, d_Z16_out L x 16 float32, d_weights_out
+        L x 3 float32 -- the three arrays voe_pose_graph_dev takes --, d_loops_out L x 40 bytes (MAP_LOOP_RECORD_DTYPE), d_hist_out
+        n_frames x n_frames int32, d_ref_frame_out map size x int32, d_stats 32 bytes (MapLoopsStats)."""
+        v = lambda d: C.c_void_p(d) if d else None
+        _chk(self.lib.voe_map_loops_batch_dev(self.h, C.c_int(n_frames), C.c_int(camera._rows), C.c_int(camera._cols), C.c_int(camera._z_near),
+                                              C.c_int(camera._z_far), _ptr(_colmajor(camera._K, 3)), v(d_uv), C.c_size_t(uv_stride), v(d_app),
+                                              C.c_size_t(app_stride), C.c_int(n_max), v(d_n), v(d_S16), C.byref(params), v(d_edges_out),
+                                              v(d_Z16_out), v(d_weights_out), v(d_loops_out), v(d_hist_out), v(d_ref_frame_out), v(d_stats)))
+
+    def loops_problems_dev(self):
+        """voe_map_loops_problems_dev: the device pointers (ints) of what the last loops call on this map left in its workspace:
+        dict(world [L][n_max][3] float32, uv [L][n_max][2] float32, pairs [L][n_max][2] int32, n_pairs [L] int32, candidates
+        [F][2] int32, inlier_pairs [L][n_max][2] int32, n_inliers [L] int32, T16 [L][16] float32, solver_stats [L][4] float32)"""
+        out = (C.c_void_p * 9)()
+        _chk(self.lib.voe_map_loops_problems_dev(self.h, C.byref(out)))
+        return dict(zip(("world", "uv", "pairs", "n_pairs", "candidates", "inlier_pairs", "n_inliers", "T16", "solver_stats"), (int(o or 0) for o in out)))
+
+    def loops(self, camera: Camera, frames, S, gap=50, ref_window=5, min_shared=12, separation=3, max_loops=8, threshold_px=2.0,
+              n_hypotheses=64, seed=0, kernel_threshold=10000.0, n_iters=50, min_inliers=6, w_loop=(1.0, 1.0, 1.0), want_hist=True,
+              want_ref_frame=True, n_max=None):
+        """voe_map_loops: the loop edges this map shows for `frames` ([(uv, app)] as in refine) with the drifted similarities S
+        (F x 4 x 4, p_cam = S p_map).  Frame j's candidate is the i < j - gap whose band -- the entries with a reference frame in
+        [i - ref_window, i] -- holds the most entries j sees (at least min_shared); candidates within `separation` frames suppress
+        each other; the best max_loops are measured by P3P RANSAC + PICP of frame j against the band of i.  Returns dict(edges
+        (L, 2) int32, Z (L, 4, 4) float32, weights (L, 3) float32 -- append them to the odometry edges of pose_graph(): every slot that
+        is not OK has weights 0 0 0 and is skipped there --, loops: MAP_LOOP_RECORD_DTYPE records (MAP_LOOP_STATUS names
+        "status"), hist (F, F) int32 or None, ref_frame (size,) int32 or None, stats dict).  n_max: the row capacity the frames are
+        padded to (default: the longest frame)."""
+        F = len(frames)
+        n = np.array([len(_f32(a, (-1, 10))) for _, a in frames], np.int32)
+        cap = max(int(n.max()) if F else 0, 1) if n_max is None else int(n_max)
+        assert F == 0 or int(n.max()) <= cap
+        uv = np.zeros((max(F, 1), cap, 2), np.float32)
+        app = np.zeros((max(F, 1), cap, 10), np.float32)
+        for f, (p, a) in enumerate(frames):
+            uv[f, : n[f]] = _f32(p, (-1, 2))
+            app[f, : n[f]] = _f32(a, (-1, 10))
+        S32 = np.ascontiguousarray(np.asarray(S, np.float32).reshape(-1, 4, 4).transpose(0, 2, 1))
+        assert len(S32) == F
+        prm = MapLoopsParams(int(gap), int(ref_window), int(min_shared), int(separation), int(max_loops), 0,
+                             self._ransac(threshold_px, n_hypotheses, seed), float(kernel_threshold), int(n_iters), int(min_inliers),
+                             (C.c_float * 3)(*[float(x) for x in w_loop]), 0)
+        L = max(int(max_loops), 1)
+        edges, Z, w = np.full((L, 2), -2, np.int32), np.zeros((L, 16), np.float32), np.zeros((L, 3), np.float32)
+        rec = np.zeros(L, MAP_LOOP_RECORD_DTYPE)
+        hist = np.zeros((max(F, 1), max(F, 1)), np.int32) if want_hist else None
+        ref = np.full(max(len(self), 1), -2, np.int32) if want_ref_frame else None
+        st = MapLoopsStats()
+        _chk(self.lib.voe_map_loops(self.h, C.c_int(F), C.c_int(camera._rows), C.c_int(camera._cols), C.c_int(camera._z_near), C.c_int(camera._z_far),
+                                    _ptr(_colmajor(camera._K, 3)), _ptr(uv), _ptr(app), _ptr(n), C.c_int(cap), _ptr(S32), C.byref(prm), _ptr(edges),
+                                    _ptr(Z), _ptr(w), _ptr(rec), _ptr(hist) if want_hist else None, _ptr(ref) if want_ref_frame else None,
+                                    C.byref(st)))
+        return dict(edges=edges, Z=Z.reshape(L, 4, 4).transpose(0, 2, 1).copy(), weights=w, loops=rec, hist=hist,
+                    ref_frame=ref[: st.n_entries].copy() if want_ref_frame else None, stats=st.as_dict())
+
     def window_dev(self, n_frames, n_words, d_bits, d_n, n_max, params: "MapWindowParams", d_role_out, d_n_rows_out, d_fixed_out,
                    d_order_out, d_union_out, d_stats):
         """voe_map_window_dev on device pointers (ints; d_n, d_order_out and d_union_out may be None): enqueues and returns"""
@@ -1250,6 +1309,36 @@ def estimate_transform(k, correspondences, p1_img, p2_img, ctx: Context | None =
 class RansacParams(C.Structure):
     """vo_ransac_params (include/vo_hip.h)"""
     _fields_ = [("n_hypotheses", C.c_int), ("threshold_px", C.c_float), ("seed", C.c_uint64)]
+
+
+class MapLoopsParams(C.Structure):
+    """voe_map_loops_params (include/vo_map_loops.h)"""
+    _fields_ = [("gap", C.c_int32), ("ref_window", C.c_int32), ("min_shared", C.c_int32), ("separation", C.c_int32), ("max_loops", C.c_int32),
+                ("reserved0", C.c_int32), ("ransac", RansacParams), ("kernel_threshold", C.c_float), ("n_iters", C.c_int32),
+                ("min_inliers", C.c_int32), ("w_loop", C.c_float * 3), ("reserved1", C.c_int32)]
+
+
+class MapLoopRecord(C.Structure):
+    """voe_map_loop_record (include/vo_map_loops.h): one slot"""
+    _fields_ = [("i", C.c_int32), ("j", C.c_int32), ("c", C.c_int32), ("n_pairs", C.c_int32), ("ransac_status", C.c_int32),
+                ("ransac_inliers", C.c_int32), ("num_inliers", C.c_int32), ("status", C.c_int32), ("chi_inliers", C.c_float),
+                ("chi_outliers", C.c_float)]
+
+
+class MapLoopsStats(C.Structure):
+    """voe_map_loops_stats (include/vo_map_loops.h)"""
+    _fields_ = [("n_frames", C.c_int32), ("n_entries", C.c_int32), ("n_candidates", C.c_int32), ("n_survivors", C.c_int32),
+                ("n_slots", C.c_int32), ("n_ok", C.c_int32), ("reserved", C.c_int32 * 2)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_ if k != "reserved"}
+
+
+assert C.sizeof(MapLoopsParams) == 72 and C.sizeof(MapLoopRecord) == 40 and C.sizeof(MapLoopsStats) == 32
+MAP_LOOP_RECORD_DTYPE = np.dtype([("i", "<i4"), ("j", "<i4"), ("c", "<i4"), ("n_pairs", "<i4"), ("ransac_status", "<i4"), ("ransac_inliers", "<i4"),
+                                  ("num_inliers", "<i4"), ("status", "<i4"), ("chi_inliers", "<f4"), ("chi_outliers", "<f4")])
+assert MAP_LOOP_RECORD_DTYPE.itemsize == 40
+MAP_LOOP_STATUS = ("OK", "FEW_MATCHES", "NO_CONSENSUS", "FEW_INLIERS", "NOT_FINITE", "EMPTY")      # VOE_MAP_LOOP_*
 
 
 def estimate_transform_ransac(k, correspondences, p1_img, p2_img, threshold_px=1.0, n_hypotheses=2048, seed=0,

@@ -1,5 +1,5 @@
 // capi_map.hip -- the map's half of the extern "C" boundary (vo_hip.h: vo_map_*; vo_map_adjust.h, vo_map_bundle.h, vo_map_cull.h,
-// vo_map_align.h, vo_map_covis.h, vo_map_grow.h) and the pose graph's (vo_pose_graph.h).  Host-side plumbing only, like capi.hip: no kernel lives here.
+// vo_map_align.h, vo_map_covis.h, vo_map_grow.h, vo_map_loops.h) and the pose graph's (vo_pose_graph.h).  Host-side plumbing only, like capi.hip: no kernel lives here.
 #include <limits.h>
 #include <string.h>
 
@@ -28,6 +28,8 @@ struct vo_map {
   DevBuf covis_ws;              // voe_map_covis*: the lookup's pairs, counts and entries, the population counts per frame and per block of words
   DevBuf window_ws;             // voe_map_window*: the counts against the query row and against the union, the order, the union
   DevBuf grow_ws;               // voe_map_grow*: the open rows, the tracks' private table, verdicts, the staging area (the lists live in ref_ws)
+  DevBuf loops_ws;              // voe_map_loops*: the lookup's arrays, keys, reference frames, bit rows, candidates, slots, the gathered problems
+  MapLoopsWs loops_last{};      // ... as the last call laid it out (voe_map_loops_problems_dev); bytes == 0: no call yet
 };
 
 constexpr int MAP_MAX_ENTRIES = 1 << 29;      // 2.5 x that many table slots still fit 32 bits
@@ -124,7 +126,7 @@ int vo_map_destroy(vo_map* m) {
   map_free_arrays(m->d);
   if (m->d.hdr) (void)hipFree(m->d.hdr);
   if (m->hist) (void)hipFree(m->hist);
-  m->scratch.release(); m->up_xyz.release(); m->up_app.release(); m->look_ws.release(); m->loc_ws.release(); m->ref_ws.release(); m->pose_ws.release(); m->bundle_ws.release(); m->cull_ws.release(); m->align_ws.release(); m->merge_ws.release(); m->covis_ws.release(); m->window_ws.release(); m->grow_ws.release();
+  m->scratch.release(); m->up_xyz.release(); m->up_app.release(); m->look_ws.release(); m->loc_ws.release(); m->ref_ws.release(); m->pose_ws.release(); m->bundle_ws.release(); m->cull_ws.release(); m->align_ws.release(); m->merge_ws.release(); m->covis_ws.release(); m->window_ws.release(); m->grow_ws.release(); m->loops_ws.release();
   if (m->solver) (void)vo_picp_destroy(m->solver);
   delete m;
   return VO_OK;
@@ -1332,6 +1334,123 @@ int voe_map_apply_correction(vo_map* m, int n_frames, const float* uv, const flo
   VO_HIP_CHECK(hipMemcpyAsync(stats_out, c->out[2].p, sizeof(voe_map_apply_stats), hipMemcpyDeviceToHost, c->stream));
   if (ref_frame_out && size > 0)
     VO_HIP_CHECK(hipMemcpyAsync(ref_frame_out, c->out[0].p, sizeof(int32_t) * (size_t)size, hipMemcpyDeviceToHost, c->stream));
+  VO_HIP_CHECK(hipStreamSynchronize(c->stream));
+  return VO_OK;
+}
+
+// ---- loop edges found and measured in the map (map_loops.hip; include/vo_map_loops.h) ------------------------------------------
+static_assert(sizeof(voe_map_loops_params) == 72 && sizeof(voe_map_loop_record) == 40 && sizeof(voe_map_loops_stats) == 32,
+              "the records of include/vo_map_loops.h as the kernels write them");
+
+int voe_map_loops_batch_dev(vo_map* m, int n_frames, int rows, int cols, int z_near, int z_far, const float K[9], const float* d_uv,
+                            size_t uv_stride, const float* d_app, size_t app_stride, int n_max, const int* d_n, const float* d_S16,
+                            const voe_map_loops_params* p, int32_t* d_edges_out, float* d_Z16_out, float* d_weights_out,
+                            voe_map_loop_record* d_loops_out, int32_t* d_hist_out, int32_t* d_ref_frame_out, voe_map_loops_stats* d_stats) {
+  const char* fn = "voe_map_loops_batch_dev";
+  // the refusals that need no map come first: they are the same on a machine without a device
+  if (int r = map_loops_check(fn, n_frames, MapLoopsPtrs{d_S16, d_edges_out, d_Z16_out, d_weights_out, d_loops_out, d_hist_out, d_ref_frame_out, d_stats}, p))
+    return r;
+  VO_MAP_LIVE(m);
+  const MapFrames f{n_frames, K, d_uv, uv_stride, d_app, app_stride, n_max, d_n};
+  if (p->ransac.n_hypotheses == 0) return vo_fail(VO_ERR_INVALID_ARG, "%s: n_hypotheses == 0 (a loop has no prior pose to start from)", fn);
+  if (int r = localise_check(fn, f, &p->ransac, p->n_iters, p->min_inliers, nullptr, d_Z16_out, reinterpret_cast<const vo_map_localise_stats*>(d_stats)))
+    return r;
+  VO_REQUIRE(uv_stride >= (size_t)n_max && app_stride >= (size_t)n_max, "a stride is smaller than n_max");
+  VO_REQUIRE(uv_stride < 0x7fffffff, "stride too large");
+  if (int r = map_lookup_check(f, true)) return r;            // the lookup's own refusals, before anything is sized
+  vo_ctx* c = m->ctx;
+  const int L = p->max_loops;
+  const size_t need = map_loops_layout(nullptr, n_frames, n_max, m->bd.alloc_bound(), L).bytes;      // (for the capacity: MapBound::alloc_bound)
+  if (int r = window_growth_check(m, fn, f, {{m->loops_ws.cap, need}, {m->look_ws.cap, lookup_scratch_bytes(f, false)}})) return r;
+  if (int r = set_device(c)) return r;
+  VO_HIP_CHECK(m->loops_ws.ensure(need, c->stream));
+  const int bound = map_launch_bound(m);
+  const MapLoopsWs w = map_loops_layout(m->loops_ws.p, n_frames, n_max, bound, L);
+  m->loops_last = w;
+  // 1. the one lookup of the call
+  if (int r = lookup_window(m, f, w.pairs, w.n_hits, w.ent)) return r;
+  // 2. the reference frames: the launches of voe_map_apply_correction as a dry run with new == old -- nothing can move
+  int32_t* ref = d_ref_frame_out ? d_ref_frame_out : w.ref;
+  MapApplyArgs ap{};
+  ap.ent = w.ent; ap.key = w.key;
+  ap.pts = m->d.pts; ap.hdr = m->d.hdr; ap.cap = m->d.cap; ap.bound = bound;
+  ap.n_frames = n_frames; ap.n_max = n_max; ap.S_old = d_S16; ap.S_new = d_S16; ap.dry_run = 1;
+  ap.ref_frame_out = ref; ap.stats = w.apply_stats;
+  VO_HIP_CHECK(launch_map_apply_correction(c->stream, ap));
+  // 3. the covisibility's bit rows
+  const int n_words = bound > 32 ? (int)(((long long)bound + 31) / 32) : 1;
+  MapCovisArgs cv{};
+  cv.w.ent = w.ent; cv.hdr = m->d.hdr; cv.cap = m->d.cap;
+  cv.n_frames = n_frames; cv.n_max = n_max; cv.n_words = n_words; cv.d_n = d_n; cv.bits = w.bits;
+  VO_HIP_CHECK(launch_map_covis_bits(c->stream, cv));
+  // 4. histogram, candidates, choice, the slots' problems
+  MapLoopsArgs a{};
+  a.w = w;
+  a.pts = m->d.pts; a.hdr = m->d.hdr; a.cap = m->d.cap; a.bound = bound;
+  a.n_frames = n_frames; a.n_max = n_max; a.n_words = n_words;
+  a.uv = d_uv; a.uv_stride = uv_stride; a.d_n = d_n; a.S16 = d_S16;
+  a.gap = p->gap; a.ref_window = p->ref_window; a.min_shared = p->min_shared; a.separation = p->separation; a.max_loops = L;
+  a.min_inliers = p->min_inliers;
+  for (int k = 0; k < 3; ++k) a.w_loop[k] = p->w_loop[k];
+  a.ref = ref; a.hist = d_hist_out;
+  a.edges = d_edges_out; a.Z16 = d_Z16_out; a.weights = d_weights_out; a.loops = d_loops_out; a.stats = d_stats;
+  VO_HIP_CHECK(launch_map_loops_find(c->stream, a));
+  // 5. the measurement: the two public batched calls over the slots, at constant strides of n_max
+  const size_t N = (size_t)n_max;
+  if (int r = vo_estimate_pose_ransac_batch_dev(c, L, rows, cols, z_near, z_far, K, w.world, N, n_max, w.uv, N, n_max, w.lpairs, N, w.n_pairs, &p->ransac,
+                                                w.T_start, w.handed, w.n_handed, nullptr, nullptr, w.rstat))
+    return r;
+  if (int r = vo_picp_solve_batch_dev(c, L, rows, cols, z_near, z_far, K, p->kernel_threshold, 0, w.world, N, w.uv, N, w.handed, N, w.n_handed, w.T_start,
+                                      p->n_iters, w.T_solved, w.stats4))
+    return r;
+  // 6. status, edge, record, statistics
+  VO_HIP_CHECK(launch_map_loops_finish(c->stream, a));
+  return VO_OK;
+}
+
+int voe_map_loops_problems_dev(vo_map* m, voe_map_loops_problems* out) {
+  VO_MAP_LIVE(m);
+  VO_REQUIRE(out, "null argument");
+  const MapLoopsWs& w = m->loops_last;
+  if (w.bytes == 0) return vo_fail(VO_ERR_NOT_READY, "%s: no voe_map_loops call has been made on this map", __func__);
+  *out = voe_map_loops_problems{w.world, w.uv, w.lpairs, w.n_pairs, w.cand, w.handed, w.n_handed, w.T_solved, w.stats4};
+  return VO_OK;
+}
+
+int voe_map_loops(vo_map* m, int n_frames, int rows, int cols, int z_near, int z_far, const float K[9], const float* uv, const float* app,
+                  const int* n_rows, int n_max, const float* S16, const voe_map_loops_params* p, int32_t* edges_out, float* Z16_out,
+                  float* weights_out, voe_map_loop_record* loops_out, int32_t* hist_out, int32_t* ref_frame_out, voe_map_loops_stats* stats_out) {
+  const char* fn = "voe_map_loops";
+  alignas(8) static const char stand_in[8] = {};      // the host's own arrays need no device alignment: the staging has it
+  const auto si = [](const void* q) { return q ? (const void*)stand_in : nullptr; };
+  if (int r = map_loops_check(fn, n_frames, MapLoopsPtrs{si(S16), si(edges_out), si(Z16_out), si(weights_out), si(loops_out), nullptr, nullptr, si(stats_out)}, p))
+    return r;
+  VO_MAP_LIVE(m);
+  vo_ctx* c = m->ctx;
+  VO_NOT_CAPTURING(c);
+  VO_REQUIRE(K && uv && app, "null argument");
+  MapFrames f;
+  int size = 0;
+  if (int r = upload_window(fn, m, MapFrames{n_frames, K, uv, 0, app, 0, n_max, n_rows}, S16, nullptr, &size, &f)) return r;
+  const size_t F = (size_t)n_frames, L = (size_t)p->max_loops, M = (size_t)(size > 0 ? size : 1);
+  // one block of outputs: edges, Z, weights, records, statistics, then the histogram and the reference frames
+  const size_t o_edges = 0, o_Z = o_edges + up256(8 * L), o_w = o_Z + up256(64 * L), o_rec = o_w + up256(12 * L), o_stats = o_rec + up256(40 * L),
+               o_hist = o_stats + 256, o_ref = o_hist + up256(hist_out ? 4 * F * F : 0), total = o_ref + up256(ref_frame_out ? 4 * M : 0);
+  VO_HIP_CHECK(c->out[0].ensure(total, c->stream));
+  char* d = c->out[0].as<char>();
+  if (int r = voe_map_loops_batch_dev(m, n_frames, rows, cols, z_near, z_far, K, f.d_uv, f.uv_stride, f.d_app, f.app_stride, n_max, f.d_n,
+                                      c->in[2].as<float>(), p, reinterpret_cast<int32_t*>(d + o_edges), reinterpret_cast<float*>(d + o_Z),
+                                      reinterpret_cast<float*>(d + o_w), reinterpret_cast<voe_map_loop_record*>(d + o_rec),
+                                      hist_out ? reinterpret_cast<int32_t*>(d + o_hist) : nullptr,
+                                      ref_frame_out ? reinterpret_cast<int32_t*>(d + o_ref) : nullptr, reinterpret_cast<voe_map_loops_stats*>(d + o_stats)))
+    return r;
+  VO_HIP_CHECK(hipMemcpyAsync(edges_out, d + o_edges, 8 * L, hipMemcpyDeviceToHost, c->stream));
+  VO_HIP_CHECK(hipMemcpyAsync(Z16_out, d + o_Z, 64 * L, hipMemcpyDeviceToHost, c->stream));
+  VO_HIP_CHECK(hipMemcpyAsync(weights_out, d + o_w, 12 * L, hipMemcpyDeviceToHost, c->stream));
+  VO_HIP_CHECK(hipMemcpyAsync(loops_out, d + o_rec, 40 * L, hipMemcpyDeviceToHost, c->stream));
+  VO_HIP_CHECK(hipMemcpyAsync(stats_out, d + o_stats, sizeof(voe_map_loops_stats), hipMemcpyDeviceToHost, c->stream));
+  if (hist_out) VO_HIP_CHECK(hipMemcpyAsync(hist_out, d + o_hist, 4 * F * F, hipMemcpyDeviceToHost, c->stream));
+  if (ref_frame_out && size > 0) VO_HIP_CHECK(hipMemcpyAsync(ref_frame_out, d + o_ref, 4 * (size_t)size, hipMemcpyDeviceToHost, c->stream));
   VO_HIP_CHECK(hipStreamSynchronize(c->stream));
   return VO_OK;
 }

@@ -158,6 +158,37 @@ static inline int map_apply_check(const char* fn, int n_frames, const float* d_a
   return VO_OK;
 }
 
+// voe_map_loops*: what the call refuses beyond the lookup's, the localisation's and the covisibility's own refusals
+// (include/vo_map_loops.h), in the order they fire:
+//   1. a null d_S16, params or output      2. n_frames outside 1 .. VOE_MAP_COVIS_MAX_FRAMES
+//   3. d_loops_out or d_stats off an 8-byte boundary, any other array off a 4-byte one
+//   4. gap < 0      5. ref_window < 0      6. min_shared < 1      7. separation < 0      8. max_loops outside 1 .. n_frames
+//   9. a w_loop that is negative or not finite      10. w_loop all zero
+struct MapLoopsPtrs {
+  const void *S16, *edges, *Z16, *weights, *loops, *hist, *ref_frame, *stats;
+};
+static inline int map_loops_check(const char* fn, int n_frames, const MapLoopsPtrs& d, const voe_map_loops_params* p) {
+  if (!(d.S16 && p && d.edges && d.Z16 && d.weights && d.loops && d.stats)) return vo_fail(VO_ERR_INVALID_ARG, "%s: null argument", fn);
+  if (n_frames < 1 || n_frames > VOE_MAP_COVIS_MAX_FRAMES)
+    return vo_fail(VO_ERR_INVALID_ARG, "%s: n_frames %d outside 1 .. %d", fn, n_frames, VOE_MAP_COVIS_MAX_FRAMES);
+  if (!aligned8(d.loops, d.stats)) return vo_fail(VO_ERR_INVALID_ARG, "%s: d_loops_out and d_stats must be 8-byte aligned", fn);
+  const uintptr_t four = reinterpret_cast<uintptr_t>(d.S16) | reinterpret_cast<uintptr_t>(d.edges) | reinterpret_cast<uintptr_t>(d.Z16) |
+                         reinterpret_cast<uintptr_t>(d.weights) | reinterpret_cast<uintptr_t>(d.hist) | reinterpret_cast<uintptr_t>(d.ref_frame);
+  if (four & 3u) return vo_fail(VO_ERR_INVALID_ARG, "%s: float32 and int32 arrays must be 4-byte aligned", fn);
+  if (p->gap < 0) return vo_fail(VO_ERR_INVALID_ARG, "%s: negative gap", fn);
+  if (p->ref_window < 0) return vo_fail(VO_ERR_INVALID_ARG, "%s: negative ref_window", fn);
+  if (p->min_shared < 1) return vo_fail(VO_ERR_INVALID_ARG, "%s: min_shared must be at least 1", fn);
+  if (p->separation < 0) return vo_fail(VO_ERR_INVALID_ARG, "%s: negative separation", fn);
+  if (p->max_loops < 1 || p->max_loops > n_frames) return vo_fail(VO_ERR_INVALID_ARG, "%s: max_loops %d outside 1 .. n_frames", fn, p->max_loops);
+  bool any = false;
+  for (int k = 0; k < 3; ++k) {
+    if (!(p->w_loop[k] >= 0.f && p->w_loop[k] <= 3.402823466e38f)) return vo_fail(VO_ERR_INVALID_ARG, "%s: w_loop must be finite and not negative", fn);
+    any = any || p->w_loop[k] > 0.f;
+  }
+  if (!any) return vo_fail(VO_ERR_INVALID_ARG, "%s: w_loop is all zero", fn);
+  return VO_OK;
+}
+
 // A workspace that would have to grow inside a graph capture: growing frees, allocates and waits.  `ws` lists the buffers the
 // call sizes, each with its capacity and what the call needs; `tail` (printf form) names the call that sizes them outside a
 // capture.  The callers ask BEFORE they enqueue anything: a HIP call refused later would invalidate the capture.

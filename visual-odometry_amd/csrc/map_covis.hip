@@ -290,10 +290,16 @@ MapCovisWs map_covis_layout(void* base, int n_frames, int n_max, int n_words) {
   return w;
 }
 
-hipError_t launch_map_covis(hipStream_t st, const MapCovisArgs& a) {
+hipError_t launch_map_covis_bits(hipStream_t st, const MapCovisArgs& a) {
   const hipError_t e = hipMemsetAsync(a.bits, 0, sizeof(uint32_t) * (size_t)a.n_frames * (size_t)a.n_words, st);
   if (e != hipSuccess) return e;
   if (a.n_max > 0) hipLaunchKernelGGL(covis_bits_kernel, dim3((a.n_max + VB - 1) / VB, a.n_frames), dim3(VB), 0, st, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_map_covis(hipStream_t st, const MapCovisArgs& a) {
+  const hipError_t e = launch_map_covis_bits(st, a);
+  if (e != hipSuccess) return e;
   if (a.counts) hipLaunchKernelGGL(covis_count_kernel, dim3(covis_tiles(a.n_frames)), dim3(VB), 0, st, a, covis_tiles_edge(a.n_frames));
   hipLaunchKernelGGL(covis_rowpop_kernel, dim3(a.n_frames), dim3(VB), 0, st, a);
   hipLaunchKernelGGL(covis_union_kernel, dim3(covis_parts(a.n_words)), dim3(VB), 0, st, a);

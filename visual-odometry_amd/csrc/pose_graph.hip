@@ -16,6 +16,7 @@
 // stopped leaves `stop` set in the control block; its remaining launches read it and return at once.  The incidence lists
 // are built like map_refine.hip's observation lists: count, block offsets, scan, scatter, order by rank.
 #include "vo_internal.h"
+#include "sim3.h"
 #include "../../include/vo_pose_graph.h"
 
 namespace vo {
@@ -36,19 +37,7 @@ static_assert(sizeof(voe_pose_graph_params) == 28 && sizeof(voe_pose_graph_round
               "the deciding kernels write these records field by field");
 
 // ---- 3x3 and similarity algebra, column-major, in the order the header's restatement uses ------------------------------------
-__device__ __forceinline__ double pg_det3(const double* M) {
-  return M[0] * (M[4] * M[8] - M[7] * M[5]) - M[3] * (M[1] * M[8] - M[7] * M[2]) + M[6] * (M[1] * M[5] - M[4] * M[2]);
-}
-__device__ __forceinline__ void pg_inv3(const double* M, double* I) {
-  const double d = pg_det3(M);
-  I[0] = (M[4] * M[8] - M[7] * M[5]) / d; I[3] = (M[6] * M[5] - M[3] * M[8]) / d; I[6] = (M[3] * M[7] - M[6] * M[4]) / d;
-  I[1] = (M[7] * M[2] - M[1] * M[8]) / d; I[4] = (M[0] * M[8] - M[6] * M[2]) / d; I[7] = (M[6] * M[1] - M[0] * M[7]) / d;
-  I[2] = (M[1] * M[5] - M[4] * M[2]) / d; I[5] = (M[3] * M[2] - M[0] * M[5]) / d; I[8] = (M[0] * M[4] - M[3] * M[1]) / d;
-}
-__device__ __forceinline__ void pg_mv(const double* M, const double* x, double* y) {
-#pragma unroll
-  for (int r = 0; r < 3; ++r) y[r] = M[r] * x[0] + M[r + 3] * x[1] + M[r + 6] * x[2];
-}
+// (pg_det3, pg_inv3, pg_mv: sim3.h)
 __device__ __forceinline__ void pg_mtv(const double* M, const double* x, double* y) {
 #pragma unroll
   for (int c = 0; c < 3; ++c) y[c] = M[3 * c] * x[0] + M[3 * c + 1] * x[1] + M[3 * c + 2] * x[2];

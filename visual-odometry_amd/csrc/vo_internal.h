@@ -845,6 +845,8 @@ struct MapCovisArgs {
 // after the lookup has filled w.ent and w.n_hits: memset of the bits, bit pass, count pass (when counts are wanted), the rows'
 // population counts, the union's, the statistics
 hipError_t launch_map_covis(hipStream_t st, const MapCovisArgs& a);
+// its first two steps alone, for a caller that wants the bit rows and nothing else (voe_map_loops*): reads w.ent only
+hipError_t launch_map_covis_bits(hipStream_t st, const MapCovisArgs& a);
 struct MapWindowWs {
   int* cnt;                             // [n_frames] c(g), then s(h)
   int32_t* order;                       // [n_frames] (the caller's array takes its place when given)
@@ -1077,5 +1079,46 @@ struct MapApplyArgs {
 };
 // the keys (an integer atomicMin: exact), then the move of every entry and the statistics
 hipError_t launch_map_apply_correction(hipStream_t st, const MapApplyArgs& a);
+
+// ---- loop edges found and measured in the map (map_loops.hip, voe_map_loops*; include/vo_map_loops.h holds the rules) --------
+constexpr int MAP_LOOPS_MAX_FRAMES = 4096;      // VOE_MAP_COVIS_MAX_FRAMES: a histogram row fits a workgroup's LDS
+// the workspace of one call: `bound` >= the map's size, L = max_loops
+struct MapLoopsWs {
+  int32_t* pairs;                       // [n_frames][n_max][2] the lookup's compacted hits (not read afterwards)
+  int32_t* ent;                         // [n_frames][n_max] the lookup's entry per position
+  int* n_hits;                          // [n_frames] the lookup's counts
+  int* key;                             // [bound] the smallest key per entry (MapApplyArgs::key)
+  int32_t* ref;                         // [32 * words(bound)] the reference frame per entry (the caller's array takes its place when given)
+  int* apply_stats;                     // [4] what the shared move kernel reports (not handed out)
+  uint32_t* bits;                       // [n_frames][words(bound)] sees(f, e)
+  int32_t* cand;                        // [n_frames][2] (i, c) of every frame's candidate; i == -1: none
+  int32_t* slots;                       // [L][4] (i, j, c, 0); i == -1: EMPTY
+  int* ctl;                             // [0] n_candidates [1] n_survivors [2] n_slots
+  float* world;                         // [L][n_max][3] the gathered points
+  float* uv;                            // [L][n_max][2] frame j's pixels
+  int32_t* lpairs;                      // [L][n_max][2] (row, k)
+  int* n_pairs;                         // [L]
+  int32_t* handed;                      // [L][n_max][2] the RANSAC's inlier pairs
+  int *n_handed, *rstat;                // [L]
+  float *T_start, *T_solved, *stats4;   // [L][16], [L][16], [L][4]
+  size_t bytes;
+};
+MapLoopsWs map_loops_layout(void* base, int n_frames, int n_max, int bound, int max_loops);
+struct MapLoopsArgs {
+  MapLoopsWs w;
+  const float* pts; const int* hdr; int cap, bound;      // the map: read only
+  int n_frames, n_max, n_words;
+  const float* uv; size_t uv_stride; const int* d_n;
+  const float* S16;                     // [n_frames][16]
+  int gap, ref_window, min_shared, separation, max_loops, min_inliers;
+  float w_loop[3];
+  const int32_t* ref;                   // w.ref or the caller's
+  int32_t* hist;                        // [n_frames][n_frames] the caller's, or null: a row lives in its workgroup's LDS
+  int32_t* edges; float* Z16; float* weights; void* loops; void* stats;      // the outputs
+};
+// behind the lookup, the reference frames and the bit rows: histogram + candidate per frame, the choice, the slots' pairs
+hipError_t launch_map_loops_find(hipStream_t st, const MapLoopsArgs& a);
+// behind the two public calls: status, edge, record and statistics
+hipError_t launch_map_loops_finish(hipStream_t st, const MapLoopsArgs& a);
 
 }  // namespace vo
