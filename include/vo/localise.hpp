@@ -10,6 +10,7 @@
 #include <cmath>
 
 #include <cstdint>
+#include <cstring>
 #include <limits>
 #include <string>
 #include <vector>
@@ -208,6 +209,25 @@ struct MapLoops {
 };
 inline const char* loop_status_name(int status) {
   static const char* names[] = {"OK", "FEW_MATCHES", "NO_CONSENSUS", "FEW_INLIERS", "NOT_FINITE", "EMPTY"};
+  return status >= 0 && status < 6 ? names[status] : "?";
+}
+
+//! voe_map_nearest: frames associated with the map by the nearest appearance within a radius (include/vo_hip.h, NEAREST; DESIGN.md
+//! section 4.23)
+struct NearestOptions {
+  float radius = 0.1f;               //!< an entry matches when its squared distance is below radius^2
+  float ratio = 0.f;                 //!< 0: off; otherwise a row whose best is not below ratio^2 times its second best is AMBIGUOUS
+  bool unique = false;               //!< an entry keeps its closest row of a frame, the others are DISPLACED
+};
+struct MapNearest {
+  std::vector<std::vector<int32_t>> entry;     //!< per frame, per row: the entry, -1 unless MATCHED
+  std::vector<std::vector<int32_t>> status;    //!< VOE_MAP_NEAREST_*
+  std::vector<std::vector<float>> dist2;       //!< the best squared distance, +inf where there is none
+  std::vector<Vector10fVector> canonical;      //!< the rows as every map call is to see them: matched rows carry their entry's bytes
+  voe_map_nearest_stats stats{};
+};
+inline const char* nearest_status_name(int status) {
+  static const char* names[] = {"MATCHED", "NO_ENTRY", "AMBIGUOUS", "DISPLACED", "NAN_ROW", "NOT_LIVE"};
   return status >= 0 && status < 6 ? names[status] : "?";
 }
 
@@ -497,6 +517,35 @@ class DeviceMap {
     check(voe_map_covis(h_, (int)F, app.data(), n.data(), (int)cap, (int)c.n_words, c.bits.data(), want_counts ? c.counts.data() : nullptr,
                         &c.stats), "voe_map_covis");
     return c;
+  }
+
+  //! the nearest entry within a radius for every row of every frame, and the rows canonicalised (voe_map_nearest): hand
+  //! `canonical` to any other call of this class in place of the appearances and it sees the association decided here
+  MapNearest nearest(const std::vector<Vector10fVector>& appearances, const NearestOptions& o = NearestOptions()) const {
+    MapNearest r;
+    const size_t F = appearances.size();
+    size_t cap = 0;
+    for (const auto& a : appearances) cap = a.size() > cap ? a.size() : cap;
+    std::vector<float> app(F * cap * 10 + 10, 0.f), d2(F * cap + 1, 0.f);
+    std::vector<int> n(F + 1, 0);
+    std::vector<int32_t> ent(F * cap + 1, -1), st(F * cap + 1, VOE_MAP_NEAREST_NOT_LIVE);
+    for (size_t f = 0; f < F; ++f) {
+      n[f] = (int)appearances[f].size();
+      for (size_t i = 0; i < appearances[f].size(); ++i)
+        for (int k = 0; k < 10; ++k) app[(f * cap + i) * 10 + k] = appearances[f][i][k];
+    }
+    const voe_map_nearest_params p{o.radius, o.ratio, o.unique ? 1 : 0, 0};
+    check(voe_map_nearest(h_, (int)F, app.data(), n.data(), (int)cap, &p, ent.data(), st.data(), d2.data(), app.data(), &r.stats), "voe_map_nearest");
+    r.entry.resize(F); r.status.resize(F); r.dist2.resize(F); r.canonical.resize(F);
+    for (size_t f = 0; f < F; ++f) {
+      const size_t m = appearances[f].size();
+      r.entry[f].assign(ent.begin() + f * cap, ent.begin() + f * cap + m);
+      r.status[f].assign(st.begin() + f * cap, st.begin() + f * cap + m);
+      r.dist2[f].assign(d2.begin() + f * cap, d2.begin() + f * cap + m);
+      r.canonical[f].resize(m);
+      for (size_t i = 0; i < m; ++i) std::memcpy(r.canonical[f][i].data(), &app[(f * cap + i) * 10], sizeof(float) * 10);
+    }
+    return r;
   }
 
   //! a trajectory's correction carried into the map (voe_map_apply_correction): every entry some row of the frames sees moves by

@@ -746,6 +746,63 @@ int vo_map_lookup_batch_dev(vo_map *m, int n_frames, const float *d_app, size_t 
 int vo_map_lookup(vo_map *m, const float *app, int n, int32_t *pairs_out, int *n_out, float *xyz_out /* or NULL */,
                   int32_t *entry_out /* or NULL */);
 
+/* NEAREST.  The lookup's sibling for appearances that were computed, not copied: for every live row the NEAREST entry
+ * within a radius, and the frames' rows CANONICALISED -- every matched row gets the 40 bytes of its entry -- so that the
+ * exact lookup above, and with it every map call built on it, finds exactly the association the nearest search decided.
+ * (The voe_ names are declared here and not in a ninth extension header: vo_hip.h is a declaring header of the voe_
+ * namespace like the eight it includes, and these calls belong next to vo_map_lookup*.  DESIGN.md section 4.23.)
+ * Rules; every output is a function of the data alone:
+ *   1. d2(q, e) is the matcher's decision: in float32 the unfused left-to-right sum over components 0..9 of (e_k - q_k)^2;
+ *      r2 = radius * radius in float32.
+ *   2. The best entry of a row has the smallest d2 among the entries with d2 < r2 (strict, and taken only where it evaluates
+ *      true: a NaN or an infinity in the row or in the entry never matches).  Exact ties go to the lowest entry index.
+ *   3. ratio != 0: with d2_2 the smallest d2 over the OTHER entries with d2 < r2, the row is AMBIGUOUS iff such an entry exists
+ *      and d2_best < (ratio * ratio) * d2_2 is false (both products float32).  A second candidate beyond the radius does not count.
+ *   4. unique != 0, per frame: among the rows that passed rule 3 an entry keeps the row with the smallest d2, ties to the lowest
+ *      row; the others are DISPLACED.  With unique == 0 two rows on one entry are two matches.
+ *   5. d_status_out per row POSITION, in this precedence: NOT_LIVE (behind the live count), NAN_ROW (a live row with a NaN),
+ *      NO_ENTRY (nothing within the radius), AMBIGUOUS, DISPLACED, MATCHED.  d_entry_out is the entry where MATCHED and -1
+ *      otherwise (also behind the live rows, as the lookup writes it); d_dist2_out holds d2_best where MATCHED / AMBIGUOUS /
+ *      DISPLACED and +inf otherwise.
+ *   6. d_app_out, live rows only (rows behind the count are left as they were): MATCHED the entry's 40 bytes; NO_ENTRY and
+ *      NAN_ROW the row's own 40 bytes (they stay the open rows voe_map_grow works on); AMBIGUOUS and DISPLACED the row's own
+ *      bytes with component 0 replaced by the quiet NaN 0x7FC00000 (no map call associates such a row, grow opens no track on
+ *      it).  d_app_out == d_app is allowed.  CONTRACT: vo_map_lookup_batch_dev on d_app_out returns, at every position of
+ *      every frame, the bytes of d_entry_out.  (Two corners where rule 2 and operator== part: a row holding an infinity that
+ *      compares equal to an entry, and a radius whose float32 square is 0, are NO_ENTRY here and hits of the lookup.)
+ *   7. *d_stats: the counts of rule 5 over all frames, and n_entries, the size the device holds.
+ * Frames, app_stride (in rows, >= n_max), d_n_rows and the 8-byte alignment of the rows are the lookup's.  The map is never
+ * written and nothing is read back; the launches are a fixed sequence that depends on (n_frames, n_max, the capacity, unique)
+ * alone, no launch waits for another workgroup.  The index of the map is built by every call and kept by none.  Capturable
+ * once a call of the same shape (n_frames, n_max, unique) has sized the map's workspace; a capture that would have to grow
+ * it is refused (VO_ERR_NOT_READY) before anything is enqueued.  Frame f of the batched call is bit for bit the single call.
+ * Refused (VO_ERR_INVALID_ARG): the lookup's refusals for the frames; a null params or d_entry_out; a radius that is not
+ * finite or <= 0; a ratio that is not finite or outside {0} u (0, 1]; unique outside 0 / 1; reserved != 0; an int32 / float32
+ * output off a 4-byte boundary, d_app_out or d_stats off an 8-byte one; d_app_out overlapping d_app without being d_app. */
+#define VOE_MAP_NEAREST_MATCHED   0
+#define VOE_MAP_NEAREST_NO_ENTRY  1
+#define VOE_MAP_NEAREST_AMBIGUOUS 2
+#define VOE_MAP_NEAREST_DISPLACED 3
+#define VOE_MAP_NEAREST_NAN_ROW   4
+#define VOE_MAP_NEAREST_NOT_LIVE  5
+typedef struct voe_map_nearest_params { float radius; float ratio; int unique; int reserved; } voe_map_nearest_params;   /* 16 bytes */
+typedef struct voe_map_nearest_stats  { int n_frames, n_entries, n_live, n_matched, n_no_entry, n_ambiguous, n_displaced, n_nan; } voe_map_nearest_stats; /* 32 bytes */
+int voe_map_nearest_batch_dev(vo_map *m, int n_frames, const float *d_app, size_t app_stride, int n_max,
+                              const int *d_n_rows /* [n_frames] or NULL */, const voe_map_nearest_params *p,
+                              int32_t *d_entry_out   /* [n_frames][n_max] */,
+                              int32_t *d_status_out  /* [n_frames][n_max] or NULL */,
+                              float   *d_dist2_out   /* [n_frames][n_max] or NULL */,
+                              float   *d_app_out     /* frames laid out as d_app (same stride), or NULL; may be d_app itself */,
+                              voe_map_nearest_stats *d_stats /* or NULL */);
+int voe_map_nearest_dev(vo_map *m, const float *d_app, int n_max, const int *d_n_rows /* or NULL */, const voe_map_nearest_params *p,
+                        int32_t *d_entry_out, int32_t *d_status_out /* or NULL */, float *d_dist2_out /* or NULL */,
+                        float *d_app_out /* or NULL */, voe_map_nearest_stats *d_stats /* or NULL */);
+/* host arrays in ([n_frames][n_max][10], n_rows [n_frames] or NULL), host arrays out (any but entry_out may be NULL;
+ * app_out may be app itself); waits */
+int voe_map_nearest(vo_map *m, int n_frames, const float *app, const int *n_rows /* or NULL */, int n_max,
+                    const voe_map_nearest_params *p, int32_t *entry_out, int32_t *status_out, float *dist2_out, float *app_out,
+                    voe_map_nearest_stats *stats_out);
+
 /* LOCALISATION.  The pose of a camera in the map from one frame alone: T (column-major 4x4, p_cam = T * p_map, the
  * convention of vo_picp_set_pose).  d_uv [n_max][2] pixels and d_app [n_max][10] appearances of the frame, *d_n_rows (or
  * NULL) <= n_max of them live.  Steps, all enqueued on the context's stream, no host round trip:

@@ -769,6 +769,38 @@ class Map:
                                     C.byref(st)))
         return remap[: st.n_src].copy(), st.as_dict()
 
+    # ---- the nearest entry within a radius and the canonical rows (voe_map_nearest*, include/vo_hip.h: NEAREST) ----
+    def nearest_batch_dev(self, n_frames, d_app, app_stride, n_max, d_n, params: "MapNearestParams", d_entry_out, d_status_out=None,
+                          d_dist2_out=None, d_app_out=None, d_stats=None):
+        """voe_map_nearest_batch_dev on device pointers (ints; d_n and every output but d_entry_out may be None; the stride in rows;
+        d_app_out may be d_app): enqueues and returns.  d_stats: 32 bytes (MapNearestStats)."""
+        v = lambda d: C.c_void_p(d) if d else None
+        _chk(self.lib.voe_map_nearest_batch_dev(self.h, C.c_int(n_frames), v(d_app), C.c_size_t(app_stride), C.c_int(n_max), v(d_n),
+                                                C.byref(params), v(d_entry_out), v(d_status_out), v(d_dist2_out), v(d_app_out), v(d_stats)))
+
+    def nearest(self, frames, radius, ratio=0.0, unique=False):
+        """voe_map_nearest: for every row of every frame ([app] or [(uv, app)]) the nearest entry within `radius` (ratio: the
+        second-best test, 0 = off; unique: an entry keeps its closest row per frame), and the rows canonicalised so that the exact
+        lookup -- and every map call built on it -- finds that association.  Returns dict(entry, status, dist2: lists of per-frame
+        arrays; app: the canonical rows per frame; stats dict).  Status names: MAP_NEAREST_STATUS."""
+        apps = [_f32(f[1] if isinstance(f, (tuple, list)) else f, (-1, 10)) for f in frames]
+        F = len(apps)
+        n = np.array([len(a) for a in apps], np.int32)
+        cap = int(n.max()) if F else 0
+        app = np.zeros((max(F, 1), max(cap, 1), 10), np.float32)
+        for f, a in enumerate(apps):
+            app[f, : n[f]] = a
+        ent = np.full((max(F, 1), max(cap, 1)), -1, np.int32)
+        sta = np.full((max(F, 1), max(cap, 1)), 5, np.int32)
+        d2 = np.full((max(F, 1), max(cap, 1)), np.inf, np.float32)
+        out = app.copy()
+        st = MapNearestStats()
+        pr = MapNearestParams(float(radius), float(ratio), int(bool(unique)), 0)
+        _chk(self.lib.voe_map_nearest(self.h, C.c_int(F), _ptr(app) if cap else None, _ptr(n), C.c_int(cap), C.byref(pr), _ptr(ent), _ptr(sta),
+                                      _ptr(d2), _ptr(out), C.byref(st)))
+        cut = lambda a: [a[f, : n[f]].copy() for f in range(F)]
+        return dict(entry=cut(ent), status=cut(sta), dist2=cut(d2), app=cut(out), stats=st.as_dict())
+
     # ---- covisibility of frames and the window chosen from it (voe_map_covis*, voe_map_window*, include/vo_map_covis.h) ----
     def words(self):
         """the 32-bit words a bit row needs for this map: enough for size_bound() entries, at least one"""
@@ -1102,6 +1134,24 @@ assert C.sizeof(MapAlignParams) == 32 and C.sizeof(MapAlignStats) == 48 and C.si
 MAP_ALIGN_STATUS = ("OK", "FEW_MATCHES", "NO_HYPOTHESIS", "FEW_INLIERS")      # VOE_MAP_ALIGN_*
 MAP_ALIGN_MAX_REFITS = 16
 MAP_MERGE_TAKE_SRC, MAP_MERGE_KEEP_DST = 0, 1                                   # VOE_MAP_MERGE_*
+
+
+class MapNearestParams(C.Structure):
+    """voe_map_nearest_params (include/vo_hip.h)"""
+    _fields_ = [("radius", C.c_float), ("ratio", C.c_float), ("unique", C.c_int32), ("reserved", C.c_int32)]
+
+
+class MapNearestStats(C.Structure):
+    """voe_map_nearest_stats (include/vo_hip.h)"""
+    _fields_ = [("n_frames", C.c_int32), ("n_entries", C.c_int32), ("n_live", C.c_int32), ("n_matched", C.c_int32),
+                ("n_no_entry", C.c_int32), ("n_ambiguous", C.c_int32), ("n_displaced", C.c_int32), ("n_nan", C.c_int32)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+assert C.sizeof(MapNearestParams) == 16 and C.sizeof(MapNearestStats) == 32
+MAP_NEAREST_STATUS = ("MATCHED", "NO_ENTRY", "AMBIGUOUS", "DISPLACED", "NAN_ROW", "NOT_LIVE")      # VOE_MAP_NEAREST_*
 
 
 class MapCovisStats(C.Structure):

@@ -1,5 +1,5 @@
 // capi_map.hip -- the map's half of the extern "C" boundary (vo_hip.h: vo_map_*; vo_map_adjust.h, vo_map_bundle.h, vo_map_cull.h,
-// vo_map_align.h, vo_map_covis.h, vo_map_grow.h, vo_map_loops.h) and the pose graph's (vo_pose_graph.h).  Host-side plumbing only, like capi.hip: no kernel lives here.
+// vo_map_align.h, vo_map_covis.h, vo_map_grow.h, vo_map_loops.h; voe_map_nearest* of vo_hip.h itself) and the pose graph's (vo_pose_graph.h).  Host-side plumbing only, like capi.hip: no kernel lives here.
 #include <limits.h>
 #include <string.h>
 
@@ -29,6 +29,7 @@ struct vo_map {
   DevBuf window_ws;             // voe_map_window*: the counts against the query row and against the union, the order, the union
   DevBuf grow_ws;               // voe_map_grow*: the open rows, the tracks' private table, verdicts, the staging area (the lists live in ref_ws)
   DevBuf loops_ws;              // voe_map_loops*: the lookup's arrays, keys, reference frames, bit rows, candidates, slots, the gathered problems
+  DevBuf nearest_ws;            // voe_map_nearest*: the call's index of the map (grid, start table, records), best / distance / status per row, the claim words
   MapLoopsWs loops_last{};      // ... as the last call laid it out (voe_map_loops_problems_dev); bytes == 0: no call yet
 };
 
@@ -126,7 +127,7 @@ int vo_map_destroy(vo_map* m) {
   map_free_arrays(m->d);
   if (m->d.hdr) (void)hipFree(m->d.hdr);
   if (m->hist) (void)hipFree(m->hist);
-  m->scratch.release(); m->up_xyz.release(); m->up_app.release(); m->look_ws.release(); m->loc_ws.release(); m->ref_ws.release(); m->pose_ws.release(); m->bundle_ws.release(); m->cull_ws.release(); m->align_ws.release(); m->merge_ws.release(); m->covis_ws.release(); m->window_ws.release(); m->grow_ws.release(); m->loops_ws.release();
+  m->scratch.release(); m->up_xyz.release(); m->up_app.release(); m->look_ws.release(); m->loc_ws.release(); m->ref_ws.release(); m->pose_ws.release(); m->bundle_ws.release(); m->cull_ws.release(); m->align_ws.release(); m->merge_ws.release(); m->covis_ws.release(); m->window_ws.release(); m->grow_ws.release(); m->loops_ws.release(); m->nearest_ws.release();
   if (m->solver) (void)vo_picp_destroy(m->solver);
   delete m;
   return VO_OK;
@@ -509,6 +510,69 @@ static int upload_window(const char* fn, vo_map* m, const MapFrames& h, const fl
     if (int r = vo_map_size(m, size)) return r;
   *dev = MapFrames{h.n_frames, h.K, cam ? c->in[0].as<float>() : nullptr, (size_t)h.n_max, c->in[1].as<float>(), (size_t)h.n_max, h.n_max,
                    h.d_n ? c->in[3].as<int>() : nullptr};
+  return VO_OK;
+}
+
+// ---- the nearest entry within a radius and the canonical rows (map_nearest.hip; include/vo_hip.h, NEAREST) ---------------------
+static_assert(sizeof(voe_map_nearest_params) == 16 && sizeof(voe_map_nearest_stats) == 32, "the finishing kernel writes eight 4-byte words");
+
+int voe_map_nearest_batch_dev(vo_map* m, int n_frames, const float* d_app, size_t app_stride, int n_max, const int* d_n,
+                              const voe_map_nearest_params* p, int32_t* d_entry_out, int32_t* d_status_out, float* d_dist2_out,
+                              float* d_app_out, voe_map_nearest_stats* d_stats) {
+  const char* fn = "voe_map_nearest_batch_dev";
+  const MapFrames f{n_frames, nullptr, nullptr, 0, d_app, app_stride, n_max, d_n};
+  if (int r = map_nearest_check(fn, f, p, MapNearestPtrs{d_entry_out, d_status_out, d_dist2_out, d_app_out, d_stats})) return r;
+  VO_MAP_LIVE(m);
+  vo_ctx* c = m->ctx;
+  // the index is allocated for the capacity (MapBound::alloc_bound) and the launches are sized by the launch bound: inside a
+  // capture the capacity, because the graph may append behind the call; the kernels read the size from the device
+  MapNearestWs w = map_nearest_layout(nullptr, n_frames, n_max, m->bd.alloc_bound(), p->unique != 0);
+  if (int r = capture_growth_check(c->capturing, fn, {{m->nearest_ws.cap, w.bytes}}, "%d frames of n_max %d and unique %d on this map", n_frames, n_max, p->unique))
+    return r;
+  if (int r = set_device(c)) return r;
+  VO_HIP_CHECK(m->nearest_ws.ensure(w.bytes, c->stream));
+  MapNearestArgs a{};
+  a.w = map_nearest_layout(m->nearest_ws.p, n_frames, n_max, m->bd.alloc_bound(), p->unique != 0);
+  a.app = m->d.app; a.hdr = m->d.hdr; a.cap = m->d.cap; a.bound = map_launch_bound(m);
+  a.q_app = d_app; a.q_stride = 10 * app_stride; a.n_frames = n_frames; a.n_max = n_max; a.d_n = d_n;
+  a.radius = p->radius; a.ratio = p->ratio; a.unique = p->unique;
+  a.entry = d_entry_out; a.status = d_status_out; a.dist2 = d_dist2_out; a.app_out = d_app_out; a.stats = reinterpret_cast<int*>(d_stats);
+  VO_HIP_CHECK(launch_map_nearest(c->stream, a));
+  return VO_OK;
+}
+
+int voe_map_nearest_dev(vo_map* m, const float* d_app, int n_max, const int* d_n, const voe_map_nearest_params* p, int32_t* d_entry_out,
+                        int32_t* d_status_out, float* d_dist2_out, float* d_app_out, voe_map_nearest_stats* d_stats) {
+  return voe_map_nearest_batch_dev(m, 1, d_app, (size_t)(n_max > 0 ? n_max : 0), n_max, d_n, p, d_entry_out, d_status_out, d_dist2_out, d_app_out, d_stats);
+}
+
+int voe_map_nearest(vo_map* m, int n_frames, const float* app, const int* n_rows, int n_max, const voe_map_nearest_params* p,
+                    int32_t* entry_out, int32_t* status_out, float* dist2_out, float* app_out, voe_map_nearest_stats* stats_out) {
+  const char* fn = "voe_map_nearest";
+  if (!p || !entry_out) return vo_fail(VO_ERR_INVALID_ARG, "%s: null params or d_entry_out", fn);
+  VO_MAP_LIVE(m);
+  vo_ctx* c = m->ctx;
+  VO_NOT_CAPTURING(c);
+  MapFrames f;
+  if (int r = upload_window(fn, m, MapFrames{n_frames, nullptr, nullptr, 0, app, 0, n_max, n_rows}, nullptr, nullptr, nullptr, &f)) return r;
+  VO_HIP_CHECK(hipStreamSynchronize(c->stream));            // the host arrays may go away after the call
+  const size_t rows = (size_t)n_frames * (size_t)n_max, d2_bytes = (sizeof(float) * rows + 7) & ~(size_t)7;
+  VO_HIP_CHECK(c->out[0].ensure(sizeof(int32_t) * rows + 8, c->stream));
+  VO_HIP_CHECK(c->out[1].ensure(sizeof(int32_t) * rows + 8, c->stream));
+  VO_HIP_CHECK(c->out[2].ensure(d2_bytes + sizeof(voe_map_nearest_stats), c->stream));
+  voe_map_nearest_stats* d_stats = reinterpret_cast<voe_map_nearest_stats*>(static_cast<char*>(c->out[2].p) + d2_bytes);
+  // the canonical rows are written in place over the staged rows (d_app_out == d_app)
+  if (int r = voe_map_nearest_batch_dev(m, n_frames, f.d_app, f.app_stride, n_max, f.d_n, p, c->out[0].as<int32_t>(), c->out[1].as<int32_t>(),
+                                        c->out[2].as<float>(), app_out && rows > 0 ? c->in[1].as<float>() : nullptr, d_stats))
+    return r;
+  if (rows > 0) {
+    VO_HIP_CHECK(hipMemcpyAsync(entry_out, c->out[0].p, sizeof(int32_t) * rows, hipMemcpyDeviceToHost, c->stream));
+    if (status_out) VO_HIP_CHECK(hipMemcpyAsync(status_out, c->out[1].p, sizeof(int32_t) * rows, hipMemcpyDeviceToHost, c->stream));
+    if (dist2_out) VO_HIP_CHECK(hipMemcpyAsync(dist2_out, c->out[2].p, sizeof(float) * rows, hipMemcpyDeviceToHost, c->stream));
+    if (app_out) VO_HIP_CHECK(hipMemcpyAsync(app_out, c->in[1].p, sizeof(float) * 10 * rows, hipMemcpyDeviceToHost, c->stream));
+  }
+  if (stats_out) VO_HIP_CHECK(hipMemcpyAsync(stats_out, d_stats, sizeof(voe_map_nearest_stats), hipMemcpyDeviceToHost, c->stream));
+  VO_HIP_CHECK(hipStreamSynchronize(c->stream));
   return VO_OK;
 }
 

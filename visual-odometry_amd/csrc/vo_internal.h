@@ -1121,4 +1121,36 @@ hipError_t launch_map_loops_find(hipStream_t st, const MapLoopsArgs& a);
 // behind the two public calls: status, edge, record and statistics
 hipError_t launch_map_loops_finish(hipStream_t st, const MapLoopsArgs& a);
 
+// ---- the nearest entry within a radius and the canonical rows (map_nearest.hip, voe_map_nearest*; vo_hip.h holds the rules) ---
+constexpr int NEAREST_NC = 32;                                          // cells per grid component, at most
+constexpr int NEAREST_CELLS = NEAREST_NC * NEAREST_NC * NEAREST_NC * NEAREST_NC;
+constexpr size_t NEAREST_CLAIM_BYTES = (size_t)256 << 20;               // the claim words of one group of frames (unique)
+// the workspace of one call: `cap` the map's capacity (the index is allocated for it: "one eager call, then capture")
+struct MapNearestWs {
+  void* grid;                           // the grid of this call (NearestGrid, map_nearest.hip): 256 bytes
+  int* counts;                          // [NEAREST_CELLS + 1] entries per cell, then the cells' cursors
+  int* starts;                          // [NEAREST_CELLS + 1] first record of every cell; [n_cells] = records in all
+  int* bsum;                            // [1024] the counts' sums per block of 2048 cells
+  uint2* rec;                           // [cap] (filter word, entry), ordered by cell
+  int32_t* best;                        // [n_frames][n_max] the best entry, -1: none
+  uint32_t* d2;                         // [n_frames][n_max] the bits of its distance
+  int32_t* st;                          // [n_frames][n_max] the status so far
+  unsigned long long* claim;            // [group][cap] the smallest (distance bits, row) per entry, or null (unique == 0)
+  int group;                            // frames per group of claim words
+  size_t bytes;
+};
+__attribute__((visibility("hidden"))) MapNearestWs map_nearest_layout(void* base, int n_frames, int n_max, int cap, bool unique);
+struct MapNearestArgs {
+  MapNearestWs w;
+  const float* app; const int* hdr; int cap, bound;      // the map: read only
+  const float* q_app; size_t q_stride;  // floats between frames
+  int n_frames, n_max; const int* d_n;
+  float radius, ratio; int unique;
+  int32_t* entry; int32_t* status; float* dist2; float* app_out; int* stats;      // the outputs (all but entry may be null)
+};
+// (the two helpers the host path shares with map_nearest.hip stay out of the dynamic symbol table)
+// memset of the counts (and of *stats) -> grid -> count -> two scan launches -> place -> search -> per group of frames
+// { memset of the claim words, claim, resolve } when unique -> finish
+__attribute__((visibility("hidden"))) hipError_t launch_map_nearest(hipStream_t st, const MapNearestArgs& a);
+
 }  // namespace vo
