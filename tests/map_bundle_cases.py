@@ -119,6 +119,11 @@ CASES = {
     "nan_point": lambda: failures("nan_point"),
     "camera_turned_away": lambda: failures("behind"),
     "rejected_then_accepted": rejected_then_accepted,
+    # the first round of rejected_then_accepted alone: 1 PCG iteration, the candidate at 1.43e6 against 5.59e4, status NO_STEP.
+    # The driver's other branches stay without a case: `nostep` (p.q not > 0 at the first iteration), `bad` (a pivot of D_f not > 0)
+    # and status COST_ROSE are reached only by inputs on which the restatement's own decision is marginal (a rank-deficient D_f has
+    # a pivot that is zero only up to rounding).
+    "no_step": lambda: _case(Cs.cost_rose(), dict(n_rounds=1, n_cg=12, lambda0=0.1, min_obs_point=1000)),
     "one_cg_iteration": lambda: _case(Cs.hand_adjust(), dict(n_rounds=3, n_cg=1)),
     "zero_rounds": lambda: _case(Cs.hand_adjust(), dict(n_rounds=0)),
     "huber_noisy": lambda: _case(Cs.hand([65, 65, 65, 65], 63, map_size=65, noise_px=0.5, fixed=[1, 0, 0, 0], misses=1, t_amount=0.01, a_amount=0.005),

@@ -149,6 +149,21 @@ def _far_start():
     return _case(g, n_rounds=10, lambda0=0.0)
 
 
+def _bad_pivot():
+    """only the scale is weighted: the translation and rotation diagonals of every H_ff are exactly 0, so JACOBI's first pivot is
+    exactly 0 -- no round is formed, lambda goes up by 10 each time, status NO_STEP, S16 is not written"""
+    g, _ = graph(8, [(0, 7)], seed=15)
+    g["weights"] = np.tile(np.array([0, 0, 1], np.float32), (len(g["edges"]), 1))
+    return _case(g, n_rounds=2, preconditioner="JACOBI")
+
+
+def _first_round_rejected():
+    """one undamped round from a start twice as far as far_start's: 4 PCG iterations, the candidate at 1181.12 against 586.09,
+    rejected, status NO_STEP"""
+    g, _ = graph(20, [(0, 19), (2, 17)], seed=18, rot_noise=0.5, t_noise=0.8, noise=0.4)
+    return _case(g, n_rounds=1, lambda0=0.0)
+
+
 SKIPPED, N_GOOD_BEFORE_SKIPPED = _skipped()
 FALSE_LOOP, FALSE_LOOP_EDGE = _false_loop()
 
@@ -184,6 +199,11 @@ CASES = {
     "cg1": _case(graph(20, [(0, 19)], seed=14)[0], n_rounds=4, n_cg=1),
     "zero_scale_weight_jacobi": _zero_scale_weight(),
     "far_start": _far_start(),
+    # the driver's branches that no other case runs: a pivot that is not > 0, and a call whose only round is rejected.  Its `nostep`
+    # branch (p.q not > 0 at the first iteration) and status COST_ROSE stay without a case: no input is known that reaches them
+    # without the restatement's own decision being marginal.
+    "bad_pivot_jacobi": _bad_pivot(),
+    "first_round_rejected": _first_round_rejected(),
     "jacobi_small": _case(graph(20, [(0, 19)], seed=14)[0], n_rounds=3, preconditioner="JACOBI"),
     "weighted": _case(dict(graph(25, [(0, 24), (1, 23)], seed=16)[0]), n_rounds=3),
 }

@@ -11,7 +11,7 @@
 //   align_decide_kernel   one workgroup: refit or winner, the status;
 //   align_out_kernel      the mask and the squared residuals of the final inliers per block, in double;
 //   align_finish_kernel   one workgroup: rms, S and the statistics.
-// Every floating-point sum is a tree of fixed shape over LDS (tree_sum below), per block and then over the blocks: no float
+// Every floating-point sum is a tree of fixed shape over LDS (block_tree_sum, lm_pcg.h), per block and then over the blocks: no float
 // atomics, the same bytes from every call.  The merge's own kernels (the misses of a lookup compacted in order: count / scan /
 // scatter) are at the end; lookup and update are map.hip's, through their public entry points (capi_map.hip).
 #include "vo_internal.h"
@@ -26,26 +26,6 @@ namespace {
 constexpr int AB = 256;            // threads per workgroup = pairs per block of every sum
 constexpr int ALIGN_PTS = 4;       // pairs per thread of the scoring pass
 
-// v[k] <- the sum of v[k] over the workgroup's AB threads, by a binary tree over the thread index (t with t + 128, + 64, ...
-// + 1), in every thread; s: K * AB doubles of LDS
-template <int K>
-__device__ __forceinline__ void tree_sum(double (&v)[K], double* s) {
-  const int t = threadIdx.x;
-#pragma unroll
-  for (int k = 0; k < K; ++k) s[k * AB + t] = v[k];
-  __syncthreads();
-  for (int d = AB / 2; d >= 1; d >>= 1) {
-    if (t < d) {
-#pragma unroll
-      for (int k = 0; k < K; ++k) s[k * AB + t] += s[k * AB + t + d];
-    }
-    __syncthreads();
-  }
-#pragma unroll
-  for (int k = 0; k < K; ++k) v[k] = s[k * AB];
-  __syncthreads();
-}
-
 // the blocks' rows summed: thread t adds rows t, t + AB, ... in ascending order, then the tree
 template <int K>
 __device__ __forceinline__ void rows_sum(const double* rows, int nb, double (&v)[K], double* s) {
@@ -55,7 +35,7 @@ __device__ __forceinline__ void rows_sum(const double* rows, int nb, double (&v)
 #pragma unroll
     for (int k = 0; k < K; ++k) v[k] += rows[(size_t)j * K + k];
   }
-  tree_sum<K>(v, s);
+  block_tree_sum<K>(v, s);
 }
 
 // the sum of the blocks' inlier counts (integers: any order), in every thread
@@ -267,7 +247,7 @@ __global__ __launch_bounds__(AB) void align_sums_kernel(MapAlignArgs a) {
   }
   int total;
   block_rank<AB>(in, s_wave, total);
-  tree_sum<ALIGN_SUMS>(v, s);
+  block_tree_sum<ALIGN_SUMS>(v, s);
   if (threadIdx.x == 0) {
     a.blk[blockIdx.x] = total;
 #pragma unroll
@@ -299,7 +279,7 @@ __global__ __launch_bounds__(AB) void align_moments_kernel(MapAlignArgs a) {
       v[9] = da[0] * da[0] + da[1] * da[1] + da[2] * da[2];
     }
   }
-  tree_sum<ALIGN_MOMS>(v, s);
+  block_tree_sum<ALIGN_MOMS>(v, s);
   if (threadIdx.x == 0) {
 #pragma unroll
     for (int k = 0; k < ALIGN_MOMS; ++k) a.moms[(size_t)blockIdx.x * ALIGN_MOMS + k] = v[k];
@@ -369,7 +349,7 @@ __global__ __launch_bounds__(AB) void align_out_kernel(MapAlignArgs a) {
     if (in) v[0] = align_d2(m, x);
   }
   if (a.mask_out && i < a.n_max) a.mask_out[i] = in ? 1 : 0;
-  tree_sum<1>(v, s);
+  block_tree_sum<1>(v, s);
   if (threadIdx.x == 0) a.rms[blockIdx.x] = v[0];
 }
 

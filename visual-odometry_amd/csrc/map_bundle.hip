@@ -12,7 +12,9 @@
 //   bundle_point_kernel<BACK>   the candidate points
 //   bundle_cost_kernel<CAND>    one workgroup per frame: the candidate pose, its cost and z flag
 //   bundle_decide_kernel        one workgroup: the accept rule, lambda, the round's record, the copy
-// A PCG that has stopped leaves `stop` set in the control block; its remaining launches read it and return at once.
+// The three one-workgroup launches and the end's verdict run lm_pcg.h's driver, which pose_graph.hip shares: the control block,
+// the ordered sums over the frames, PCG's vector side, the accept rule and lambda.  A PCG that has stopped leaves `stop` set in
+// the control block; its remaining launches read it and return at once.
 // The frame-side reduction is map_pose_refine.hip's (frame_reduce, vo_internal.h): DPP inside every row of 16 lanes, the 16 row
 // sums through LDS, one thread per term adds them in row order.  A single frame runs on one compute unit.  An observation is
 // vo_math.h's map_obs with the Jacobian tail a kernel needs (map_obs_pose_jac: Jc, 2 x 6; map_obs_point_jac: Jp, 2 x 3) and the
@@ -53,19 +55,6 @@ __device__ __forceinline__ void sym3_mul(const double A[6], const double x[3], d
 }
 // index of (r, c), r <= c, in the upper triangle of a 6x6 stored row by row
 __device__ __forceinline__ constexpr int tri6(int r, int c) { return r * 6 - r * (r - 1) / 2 + (c - r); }
-
-// the sum of one value per frame in the order of the header: frame f into partial sum f mod 256 in frame order (thread t < 256
-// brings its partial sum), the 256 partial sums by a binary tree.  Every thread of the workgroup calls it and gets the total.
-__device__ __forceinline__ double bundle_tree_sum(double mine, double* s /* [256] */) {
-  __syncthreads();                                            // (s may still be read from the sum before)
-  if (threadIdx.x < 256) s[threadIdx.x] = mine;
-  __syncthreads();
-  for (int h = 128; h >= 1; h >>= 1) {
-    if ((int)threadIdx.x < h) s[threadIdx.x] += s[threadIdx.x + h];
-    __syncthreads();
-  }
-  return s[0];
-}
 
 // ---- the start: statuses, the state in double, the census ------------------------------------------------------------
 __global__ __launch_bounds__(BB) void bundle_init_frames_kernel(MapBundleArgs a) {
@@ -179,7 +168,7 @@ __global__ __launch_bounds__(BB) void bundle_start_kernel(MapBundleArgs a) {
   int fl = 0;
   for (int f = threadIdx.x; f < a.v.n_frames; f += BB) { mine += a.w.fcost[f]; fl |= a.w.fflag[f]; }
   if (fl) atomicOr(&s_flag, 1);
-  const double total = bundle_tree_sum(mine, s_sum);
+  const double total = block_tree_sum(mine, s_sum);
   if (threadIdx.x == 0) {
     MapBundleCtl& c = *a.w.ctl;
     c.cost_start = total; c.cost_cur = total;
@@ -412,55 +401,29 @@ __global__ __launch_bounds__(BB) void bundle_frame_sp_kernel(MapBundleArgs a) {
   }
 }
 
-// ---- the vector side of PCG: one workgroup ------------------------------------------------------------------------------
-__global__ __launch_bounds__(BB) void bundle_cg_init_kernel(MapBundleArgs a) {
-  __shared__ double s_sum[256];
-  __shared__ int s_bad;
-  MapBundleCtl& c = *a.w.ctl;
-  if (c.dead) return;
-  const int bad_before = c.bad, n_free = c.n_free_frames;
-  if (threadIdx.x == 0) s_bad = 0;
+// ---- the vector side of PCG: one workgroup running lm_pcg.h's driver on the frames of status OK ------------------------------
+// z_f = D_f^-1 r_f at the round's start: a frame whose D_f has a pivot that is not > 0 keeps its z and makes the round bad, as a
+// landmark's V_j has before
+__device__ __forceinline__ bool bundle_precondition(const MapBundleArgs& a, int* s_bad) {
+  if (a.w.ctl->bad) return true;                              // (uniform; thread 0 writes it behind the sums' barriers)
+  if (threadIdx.x == 0) *s_bad = 0;
   __syncthreads();
-  double rz = 0.0, rr = 0.0;
-  if (!bad_before) {
-    for (int f = threadIdx.x; f < a.v.n_frames; f += BB) {
-      double* x = a.w.x + 6 * (size_t)f;
-      for (int k = 0; k < 6; ++k) x[k] = 0.0;
-      if (a.w.pose_status[f] != BS_OK) continue;
-      double D[21], r[6], z[6];
-      bundle_load(a.w.D + 21 * (size_t)f, D);
-      bundle_load(a.w.r + 6 * (size_t)f, r);
-      if (!ldlt6d_solve(D, r, z)) { atomicOr(&s_bad, 1); continue; }
+  for (int f = threadIdx.x; f < a.v.n_frames; f += BB) {
+    if (a.w.pose_status[f] != BS_OK) continue;
+    double D[21], r[6], z[6];
+    bundle_load(a.w.D + 21 * (size_t)f, D);
+    bundle_load(a.w.r + 6 * (size_t)f, r);
+    if (!ldlt6d_solve(D, r, z)) { atomicOr(s_bad, 1); continue; }
 #pragma unroll
-    for (int k = 0; k < 6; ++k) { a.w.z[6 * (size_t)f + k] = z[k]; a.w.p[6 * (size_t)f + k] = z[k]; rz += r[k] * z[k]; rr += r[k] * r[k]; }
-    }
+    for (int k = 0; k < 6; ++k) a.w.z[6 * (size_t)f + k] = z[k];
   }
-  const double t_rz = bundle_tree_sum(rz, s_sum);
-  const double t_rr = bundle_tree_sum(rr, s_sum);
-  if (threadIdx.x == 0) {
-    const int bad = bad_before | s_bad;
-    c.bad = bad; c.iters = 0; c.nostep = 0;
-    c.stop = bad || n_free == 0;
-    c.rz = t_rz; c.rr0 = t_rr; c.rr = t_rr;
-  }
+  __syncthreads();
+  return *s_bad != 0;
 }
 
-__global__ __launch_bounds__(BB) void bundle_cg_update_kernel(MapBundleArgs a) {
-  __shared__ double s_sum[256];
-  MapBundleCtl& c = *a.w.ctl;
-  if (c.dead || c.bad || c.stop) return;
-  const double rz_old = c.rz, rr0 = c.rr0;
-  const int iters = c.iters;
-  double mine = 0.0;
-  for (int f = threadIdx.x; f < a.v.n_frames; f += BB)
-    if (a.w.pose_status[f] == BS_OK) mine += a.w.pq[f];
-  const double pSp = bundle_tree_sum(mine, s_sum);
-  if (!(pSp > 0.0) || !refine_finite(pSp)) {                   // (uniform: every thread holds the same total)
-    if (threadIdx.x == 0) { c.stop = 1; c.nostep = iters == 0; }
-    return;
-  }
-  const double alpha = rz_old / pSp;
-  double rz = 0.0, rr = 0.0;
+// lm_cg_sweep fused in one loop -- D_f solves frame by frame, so nothing waits for another thread: x, r, z_f = D_f^-1 r_f and
+// the thread's share of r.z and |r|^2 (with the two barriers and the trip through memory an iteration measured 5 % slower)
+__device__ __forceinline__ void bundle_cg_sweep(const MapBundleArgs& a, double alpha, double& rz, double& rr) {
   for (int f = threadIdx.x; f < a.v.n_frames; f += BB) {
     if (a.w.pose_status[f] != BS_OK) continue;
     double D[21], r[6], z[6];
@@ -477,17 +440,21 @@ __global__ __launch_bounds__(BB) void bundle_cg_update_kernel(MapBundleArgs a) {
 #pragma unroll
     for (int k = 0; k < 6; ++k) { a.w.z[6 * (size_t)f + k] = z[k]; rz += r[k] * z[k]; rr += r[k] * r[k]; }
   }
-  const double t_rz = bundle_tree_sum(rz, s_sum);
-  const double t_rr = bundle_tree_sum(rr, s_sum);
-  const double beta = t_rz / rz_old;
-  for (int f = threadIdx.x; f < a.v.n_frames; f += BB) {
-    if (a.w.pose_status[f] != BS_OK) continue;
-    for (int k = 0; k < 6; ++k) a.w.p[6 * (size_t)f + k] = a.w.z[6 * (size_t)f + k] + beta * a.w.p[6 * (size_t)f + k];
-  }
-  if (threadIdx.x == 0) {
-    c.rz = t_rz; c.rr = t_rr; c.iters = iters + 1;
-    if (!(sqrt(t_rr) > a.cg_tol * sqrt(rr0))) c.stop = 1;      // (a residual that is not finite stops as well)
-  }
+}
+
+__global__ __launch_bounds__(BB) void bundle_cg_init_kernel(MapBundleArgs a) {
+  __shared__ double s_sum[256];
+  __shared__ int s_bad;
+  MapBundleCtl& c = *a.w.ctl;
+  if (c.dead) return;
+  lm_cg_begin<6, false>(c, a.v.n_frames, c.n_free_frames == 0, a.w.r, a.w.z, a.w.x, a.w.p, [&](int f) { return a.w.pose_status[f] == BS_OK; },
+                        [&] { return bundle_precondition(a, &s_bad); }, s_sum);
+}
+
+__global__ __launch_bounds__(BB) void bundle_cg_update_kernel(MapBundleArgs a) {
+  __shared__ double s_sum[256];
+  lm_cg_step<6, false>(*a.w.ctl, a.v.n_frames, a.cg_tol, a.w.pq, a.w.z, a.w.p, [&](int f) { return a.w.pose_status[f] == BS_OK; },
+                       [&](double alpha, double& rz, double& rr) { bundle_cg_sweep(a, alpha, rz, rr); }, s_sum);
 }
 
 // ---- the round's verdict: one workgroup ----------------------------------------------------------------------------------
@@ -496,14 +463,9 @@ __global__ __launch_bounds__(BDEC) void bundle_decide_kernel(MapBundleArgs a, in
   __shared__ int s_flag;
   MapBundleCtl& c = *a.w.ctl;
   vox_map_bundle_round* rec = a.rounds_out ? static_cast<vox_map_bundle_round*>(a.rounds_out) + round : nullptr;
-  if (c.dead) {
-    if (threadIdx.x == 0 && rec) { rec->cost = 0.0; rec->cost_candidate = 0.0; rec->lambda = 0.0; rec->residual = 0.0; rec->cg_iterations = 0; rec->accepted = 0; }
-    return;
-  }
+  if (c.dead) { lm_round_skipped(rec); return; }
   const int M = a.v.size();
-  const bool formed = !c.bad && !c.nostep;
-  const double cur = c.cost_cur, lambda = c.lambda, rr0 = c.rr0, rr = c.rr;
-  const int iters = c.iters, n_free = c.n_free_frames;
+  const bool formed = lm_formed(c);
   if (threadIdx.x == 0) s_flag = 0;
   __syncthreads();
   double mine = 0.0;
@@ -511,27 +473,11 @@ __global__ __launch_bounds__(BDEC) void bundle_decide_kernel(MapBundleArgs a, in
   if (formed && threadIdx.x < 256)
     for (int f = threadIdx.x; f < a.v.n_frames; f += 256) { mine += a.w.fcost[f]; fl |= a.w.fflag[f]; }
   if (fl) atomicOr(&s_flag, 1);
-  const double cand = bundle_tree_sum(mine, s_sum);            // (its barriers publish s_flag too)
-  const bool accept = formed && refine_finite(cand) && !s_flag && cand <= cur;
-  if (accept) {
+  const double cand = block_tree_sum(mine, s_sum);             // (its barriers publish s_flag too)
+  if (lm_decide(c, rec, cand, s_flag != 0, c.n_free_frames > 0)) {
     for (size_t k = threadIdx.x; k < 12 * (size_t)a.v.n_frames; k += BDEC)
       if (a.w.pose_status[k / 12] == BS_OK) a.w.T[k] = a.w.Tc[k];
     for (size_t k = threadIdx.x; k < 3 * (size_t)M; k += BDEC) a.w.P[k] = a.w.Pc[k];
-  }
-  if (threadIdx.x == 0) {
-    if (rec) {
-      rec->cost = cur; rec->cost_candidate = formed ? cand : 0.0; rec->lambda = lambda;
-      rec->residual = (n_free > 0 && !c.bad) ? (rr0 > 0.0 ? sqrt(rr / rr0) : 0.0) : 0.0;
-      rec->cg_iterations = iters; rec->accepted = accept;
-    }
-    if (accept) {
-      c.cost_cur = cand; c.n_accepted += 1;
-      if (lambda > 0.0) { const double l = lambda / 10.0; c.lambda = l > 1e-12 ? l : 1e-12; }
-    } else {
-      const double l = 10.0 * lambda;
-      c.lambda = l > 1e-6 ? l : 1e-6;
-    }
-    c.bad = 0; c.stop = 0; c.nostep = 0; c.iters = 0;
   }
 }
 
@@ -551,24 +497,13 @@ __global__ __launch_bounds__(BDEC) void bundle_finish_kernel(MapBundleArgs a) {
   double mine = 0.0;
   if (!c.dead && threadIdx.x < 256)
     for (int f = threadIdx.x; f < a.v.n_frames; f += 256) mine += a.w.fcost[f];
-  const double total = bundle_tree_sum(mine, s_sum);
-  int status = c.status;
-  if (!c.dead) {
-    if (a.n_rounds > 0 && c.n_accepted == 0) status = VOX_MAP_BUNDLE_NO_STEP;
-    else if (!(total <= c.cost_start)) status = VOX_MAP_BUNDLE_COST_ROSE;      // (a cost that is not finite has risen)
-  }
+  const double total = block_tree_sum(mine, s_sum);
+  const int status = lm_final_status(c, a.n_rounds, total, VOX_MAP_BUNDLE_NO_STEP, VOX_MAP_BUNDLE_COST_ROSE);
   const bool write = status == VOX_MAP_BUNDLE_OK && c.n_accepted > 0;
   for (int f = threadIdx.x; f < a.v.n_frames; f += BDEC) {
     const int ps = a.w.pose_status[f];
     if (a.pose_status_out) a.pose_status_out[f] = ps;
-    if (write && ps == BS_OK) {
-      const double* T = a.w.Tc + 12 * (size_t)f;
-      float* o = a.T_out + 16 * (size_t)f;
-      for (int col = 0; col < 4; ++col) {
-        o[4 * col] = (float)T[3 * col]; o[4 * col + 1] = (float)T[3 * col + 1]; o[4 * col + 2] = (float)T[3 * col + 2];
-        o[4 * col + 3] = col == 3 ? 1.f : 0.f;
-      }
-    }
+    if (write && ps == BS_OK) store_pose12(a.w.Tc + 12 * (size_t)f, a.T_out + 16 * (size_t)f);
   }
   for (int e = threadIdx.x; e < M; e += BDEC) {
     const int ps = a.w.point_status[e];

@@ -43,27 +43,9 @@ static_assert((VK - 1) * VA * VA * 64 <= 2 * VT * VS, "the waves' sums fit the s
 enum { WR_OUTSIDE = 0, WR_FREE = 1, WR_FIXED = 2 };
 enum { WS_OK = 0, WS_NO_FIXED = 1, WS_QUERY_UNSEEN = 2 };
 
-// the sum of v over the workgroup (any multiple of 64 threads up to 1024), in every thread; s_w: 16 ints of LDS
-__device__ __forceinline__ int covis_block_sum(int v, int* s_w) {
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d);
-  __syncthreads();                                          // (s_w may still be read from a sum before)
-  if ((threadIdx.x & 63) == 0) s_w[threadIdx.x >> 6] = v;
-  __syncthreads();
-  int tot = 0;
-  for (int w = 0; w < (int)(blockDim.x >> 6); ++w) tot += s_w[w];
-  return tot;
-}
-
-__device__ __forceinline__ int covis_live(const int* d_n, int f, int n_max) {
-  int n = d_n ? d_n[f] : n_max;
-  n = n < n_max ? n : n_max;
-  return n > 0 ? n : 0;
-}
-
 __global__ __launch_bounds__(VB) void covis_bits_kernel(MapCovisArgs a) {
   const int f = blockIdx.y, i = blockIdx.x * VB + threadIdx.x;
-  if (i >= covis_live(a.d_n, f, a.n_max)) return;
+  if (i >= live_rows(a.d_n ? a.d_n + f : nullptr, a.n_max)) return;
   int M = a.hdr[0];
   M = M < a.cap ? M : a.cap;
   const int e = a.w.ent[(size_t)f * a.n_max + i];
@@ -148,7 +130,7 @@ __global__ __launch_bounds__(VB) void covis_rowpop_kernel(MapCovisArgs a) {
   const uint32_t* row = a.bits + covis_row(blockIdx.x, a.n_words);
   int n = 0;
   for (int w = threadIdx.x; w < a.n_words; w += VB) n += __popc(row[w]);
-  n = covis_block_sum(n, s_w);
+  n = block_sum(n, s_w);
   if (threadIdx.x == 0) a.w.row_pop[blockIdx.x] = n;
 }
 
@@ -158,7 +140,7 @@ __global__ __launch_bounds__(VB) void covis_union_kernel(MapCovisArgs a) {
   uint32_t u = 0u;
   if (w < a.n_words)
     for (int f = 0; f < a.n_frames; ++f) u |= a.bits[covis_row(f, a.n_words) + w];
-  const int n = covis_block_sum(__popc(u), s_w);
+  const int n = block_sum(__popc(u), s_w);
   if (threadIdx.x == 0) a.w.part[blockIdx.x] = n;
 }
 
@@ -168,9 +150,9 @@ __global__ __launch_bounds__(VB) void covis_stats_kernel(MapCovisArgs a, int n_p
   int hits = 0, seen = 0, any = 0;
   for (int f = threadIdx.x; f < a.n_frames; f += VB) { hits += a.n_max > 0 ? a.w.n_hits[f] : 0; seen += a.w.row_pop[f]; }
   for (int b = threadIdx.x; b < n_parts; b += VB) any += a.w.part[b];
-  hits = covis_block_sum(hits, s_w);
-  seen = covis_block_sum(seen, s_w);
-  any = covis_block_sum(any, s_w);
+  hits = block_sum(hits, s_w);
+  seen = block_sum(seen, s_w);
+  any = block_sum(any, s_w);
   if (threadIdx.x == 0) {
     int M = a.hdr[0];
     M = M < a.cap ? M : a.cap;
@@ -187,7 +169,7 @@ __global__ __launch_bounds__(VB) void window_count_kernel(MapWindowArgs a, int a
   const uint32_t* other = against_union ? a.uni : a.bits + covis_row(a.query, a.n_words);
   int n = 0;
   for (int w = threadIdx.x; w < a.n_words; w += VB) n += __popc(row[w] & other[w]);
-  n = covis_block_sum(n, s_w);
+  n = block_sum(n, s_w);
   if (threadIdx.x == 0) a.w.cnt[blockIdx.x] = n;
 }
 
@@ -209,7 +191,7 @@ __global__ __launch_bounds__(VR) void window_free_kernel(MapWindowArgs a) {
     s_key[g] = cand ? covis_rank_key(c, g) : ~0ull;         // (no candidate's key reaches it)
     n_cand += cand;
   }
-  n_cand = covis_block_sum(n_cand, s_w);                      // (its barriers also publish the keys)
+  n_cand = block_sum(n_cand, s_w);                      // (its barriers also publish the keys)
   for (int g = threadIdx.x; g < a.n_frames; g += VR) {
     int role = WR_OUTSIDE;
     if (g == a.query) {
@@ -237,7 +219,7 @@ __global__ __launch_bounds__(VB) void window_union_kernel(MapWindowArgs a) {
     for (int j = 0; j < n_free; ++j) u |= a.bits[covis_row(a.order[j], a.n_words) + w];
     a.uni[w] = u;
   }
-  const int n = covis_block_sum(__popc(u), s_w);
+  const int n = block_sum(__popc(u), s_w);
   if (threadIdx.x == 0) a.w.part[blockIdx.x] = n;
 }
 
@@ -254,8 +236,8 @@ __global__ __launch_bounds__(VR) void window_fixed_kernel(MapWindowArgs a, int n
     n_cand += cand;
   }
   for (int b = threadIdx.x; b < n_parts; b += VR) points += a.w.part[b];
-  n_cand = covis_block_sum(n_cand, s_w);
-  points = covis_block_sum(points, s_w);
+  n_cand = block_sum(n_cand, s_w);
+  points = block_sum(points, s_w);
   const int n_fixed = n_cand < a.k_fixed ? n_cand : a.k_fixed;
   for (int h = threadIdx.x; h < a.n_frames; h += VR) {
     int role = a.role[h];

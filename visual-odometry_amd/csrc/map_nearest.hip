@@ -182,19 +182,6 @@ __global__ __launch_bounds__(NB) void nearest_count_kernel(MapNearestArgs a) {
   atomicAdd(&a.w.counts[cell_of(a.app + 10 * (size_t)e, g)], 1);
 }
 
-// the sum of v over the workgroup of NB threads, in every thread
-__device__ __forceinline__ int nearest_block_sum(int v, int* s_w) {
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) s_w[threadIdx.x >> 6] = v;
-  __syncthreads();
-  int tot = 0;
-#pragma unroll
-  for (int w = 0; w < NB / 64; ++w) tot += s_w[w];
-  return tot;
-}
-
 __global__ __launch_bounds__(NB) void nearest_sums_kernel(MapNearestArgs a) {
   __shared__ int s_w[NB / 64];
   const int n_cells = reinterpret_cast<const NearestGrid*>(a.w.grid)->n_cells;
@@ -202,7 +189,7 @@ __global__ __launch_bounds__(NB) void nearest_sums_kernel(MapNearestArgs a) {
   int v = 0;
 #pragma unroll
   for (int k = 0; k < NSCAN / NB; ++k) v += i0 + k < n_cells ? a.w.counts[i0 + k] : 0;
-  const int tot = nearest_block_sum(v, s_w);
+  const int tot = block_sum(v, s_w);
   if (threadIdx.x == 0) a.w.bsum[blockIdx.x] = tot;
 }
 
@@ -212,7 +199,7 @@ __global__ __launch_bounds__(NB) void nearest_starts_kernel(MapNearestArgs a) {
   if ((int)blockIdx.x * NSCAN > n_cells) return;            // (the whole workgroup)
   int pre = 0;
   for (int j = threadIdx.x; j < (int)blockIdx.x; j += NB) pre += a.w.bsum[j];
-  pre = nearest_block_sum(pre, s_w);
+  pre = block_sum(pre, s_w);
   const int i0 = blockIdx.x * NSCAN + threadIdx.x * (NSCAN / NB);
   int c[NSCAN / NB], mine = 0;
 #pragma unroll

@@ -12,8 +12,9 @@
 //   pg_edge_kernel<CAND>      the candidate's cost per edge
 //   pg_decide_kernel          one workgroup: the accept rule, lambda, the round's record, the copy
 // M^-1 is the frames' diagonal blocks (JACOBI) or the exact inverse of the odometry chain's matrix (CHAIN): two segmented
-// sums over the frames, run by the one workgroup of the PCG launches block after block with a running total.  A PCG that has
-// stopped leaves `stop` set in the control block; its remaining launches read it and return at once.  The incidence lists
+// sums over the frames, run by the one workgroup of the PCG launches block after block with a running total.  Those launches,
+// the verdict and the end run lm_pcg.h's driver, which map_bundle.hip shares.  A PCG that has stopped leaves `stop` set in the
+// control block; its remaining launches read it and return at once.  The incidence lists
 // are built like map_refine.hip's observation lists: count, block offsets, scan, scatter, order by rank.
 #include "vo_internal.h"
 #include "sim3.h"
@@ -155,63 +156,6 @@ __device__ __forceinline__ void pg_j_t(const double* rec, const PgAd& A, int sid
   for (int k = 0; k < 7; ++k) o[k] = -o[k];
 }
 __device__ __forceinline__ constexpr int tri7(int r, int c) { return r * 7 - r * (r - 1) / 2 + (c - r); }
-
-// x = H^-1 b for the symmetric N x N H (upper triangle of a 7x7 row by row; N = 6 takes its leading block) by an LDL^T in
-// natural order.  False when a pivot is not > 0 (a NaN is not) or the step is not finite.
-template <int N>
-__device__ __forceinline__ bool pg_ldlt_solve(const double* Hu, const double* b, double* x) {
-  double L[N][N], D[N];
-#pragma unroll
-  for (int r = 0; r < N; ++r)
-#pragma unroll
-    for (int c = r; c < N; ++c) L[c][r] = Hu[tri7(r, c)];
-#pragma unroll
-  for (int j = 0; j < N; ++j) {
-    double d = L[j][j];
-#pragma unroll
-    for (int m = 0; m < j; ++m) d -= L[j][m] * L[j][m] * D[m];
-    if (!(d > 0.0)) return false;
-    D[j] = d;
-#pragma unroll
-    for (int i = j + 1; i < N; ++i) {
-      double s = L[i][j];
-#pragma unroll
-      for (int m = 0; m < j; ++m) s -= L[i][m] * L[j][m] * D[m];
-      L[i][j] = s / d;
-    }
-  }
-  double y[N];
-#pragma unroll
-  for (int i = 0; i < N; ++i) {
-    double s = b[i];
-#pragma unroll
-    for (int m = 0; m < i; ++m) s -= L[i][m] * y[m];
-    y[i] = s;
-  }
-  bool finite = true;
-#pragma unroll
-  for (int i = N - 1; i >= 0; --i) {
-    double s = y[i] / D[i];
-#pragma unroll
-    for (int m = i + 1; m < N; ++m) s -= L[m][i] * x[m];
-    x[i] = s;
-    finite = finite && refine_finite(s);
-  }
-  return finite;
-}
-
-// the sum of one value per item in the order of the header: item k into partial sum k mod 256 in item order (thread t < 256
-// brings its partial sum), the 256 partial sums by a binary tree.  Every thread of the workgroup calls it and gets the total.
-__device__ __forceinline__ double pg_tree_sum(double mine, double* s /* [256] */) {
-  __syncthreads();
-  if (threadIdx.x < 256) s[threadIdx.x] = mine;
-  __syncthreads();
-  for (int h = 128; h >= 1; h >>= 1) {
-    if ((int)threadIdx.x < h) s[threadIdx.x] += s[threadIdx.x + h];
-    __syncthreads();
-  }
-  return s[0];
-}
 
 __device__ __forceinline__ int pg_offset(const PoseGraphWs& w, int f) { return w.cnt[f] + w.blk[f / PB]; }
 
@@ -357,7 +301,7 @@ __global__ __launch_bounds__(PB) void pg_start_kernel(PoseGraphArgs a) {
   if (n_free) atomicAdd(&s_n[0], n_free);
   if (n_active) atomicAdd(&s_n[1], n_active);
   if (n_live) atomicAdd(&s_n[2], n_live);
-  const double total = pg_tree_sum(mine, s_sum);              // (its barriers publish s_n too)
+  const double total = block_tree_sum(mine, s_sum);              // (its barriers publish s_n too)
   if (threadIdx.x == 0) {
     PoseGraphCtl c{};
     c.lambda = a.lambda0; c.cost_cur = total; c.cost_start = total;
@@ -530,7 +474,7 @@ __device__ __forceinline__ bool pg_precondition(const PoseGraphArgs& a, double l
         for (int k = 0; k < 28; ++k) D[k] = a.w.H[28 * (size_t)f + k];
 #pragma unroll
         for (int k = 0; k < 7; ++k) { D[tri7(k, k)] += lambda * D[tri7(k, k)]; r[k] = a.w.r[7 * (size_t)f + k]; }
-        const bool ok = a.with_scale ? pg_ldlt_solve<7>(D, r, z) : pg_ldlt_solve<6>(D, r, z);
+        const bool ok = a.with_scale ? ldlt_solve<7, 7>(D, r, z) : ldlt_solve<6, 7>(D, r, z);     // (6: the leading block)
         if (!ok) {
           atomicOr(s_bad, 1);
 #pragma unroll
@@ -598,6 +542,7 @@ __device__ __forceinline__ bool pg_precondition(const PoseGraphArgs& a, double l
   return false;
 }
 
+// the two PCG launches: lm_pcg.h's driver on the ACTIVE frames (DENSE: the others keep r = z = p = 0)
 __global__ __launch_bounds__(PB) void pg_cg_init_kernel(PoseGraphArgs a) {
   __shared__ PgScanLds s_scan;
   __shared__ double s_sum[256];
@@ -605,23 +550,8 @@ __global__ __launch_bounds__(PB) void pg_cg_init_kernel(PoseGraphArgs a) {
   PoseGraphCtl& c = *a.w.ctl;
   if (c.dead) return;
   const double lambda = c.lambda;
-  const bool bad = pg_precondition(a, lambda, s_scan, &s_bad);
-  double rz = 0.0, rr = 0.0;
-  for (int f = threadIdx.x; f < a.n_frames; f += PB) {
-#pragma unroll
-    for (int k = 0; k < 7; ++k) {
-      const double r = a.w.r[7 * (size_t)f + k], z = bad ? 0.0 : a.w.z[7 * (size_t)f + k];
-      a.w.x[7 * (size_t)f + k] = 0.0;
-      a.w.p[7 * (size_t)f + k] = z;
-      rz += r * z; rr += r * r;
-    }
-  }
-  const double t_rz = pg_tree_sum(rz, s_sum);
-  const double t_rr = pg_tree_sum(rr, s_sum);
-  if (threadIdx.x == 0) {
-    c.bad = bad; c.iters = 0; c.nostep = 0; c.stop = bad;
-    c.rz = t_rz; c.rr0 = t_rr; c.rr = t_rr;
-  }
+  lm_cg_begin<7, true>(c, a.n_frames, false, a.w.r, a.w.z, a.w.x, a.w.p, [&](int f) { return a.w.fstat[f] == PF_ACTIVE; },
+                       [&] { return pg_precondition(a, lambda, s_scan, &s_bad); }, s_sum);
 }
 
 __global__ __launch_bounds__(PB) void pg_cg_update_kernel(PoseGraphArgs a) {
@@ -629,50 +559,18 @@ __global__ __launch_bounds__(PB) void pg_cg_update_kernel(PoseGraphArgs a) {
   __shared__ double s_sum[256];
   __shared__ int s_bad;
   PoseGraphCtl& c = *a.w.ctl;
-  if (c.dead || c.bad || c.stop) return;
-  const double rz_old = c.rz, rr0 = c.rr0, lambda = c.lambda;
-  const int iters = c.iters;
-  double mine = 0.0;
-  for (int f = threadIdx.x; f < a.n_frames; f += PB)
-    if (a.w.fstat[f] == PF_ACTIVE) mine += a.w.pq[f];
-  const double pHp = pg_tree_sum(mine, s_sum);
-  if (!(pHp > 0.0) || !refine_finite(pHp)) {                  // (uniform: every thread holds the same total)
-    if (threadIdx.x == 0) { c.stop = 1; c.nostep = iters == 0; }
-    return;
-  }
-  const double alpha = rz_old / pHp;
-  for (int f = threadIdx.x; f < a.n_frames; f += PB) {
-    if (a.w.fstat[f] != PF_ACTIVE) continue;
-#pragma unroll
-    for (int k = 0; k < 7; ++k) {
-      a.w.x[7 * (size_t)f + k] += alpha * a.w.p[7 * (size_t)f + k];
-      a.w.r[7 * (size_t)f + k] -= alpha * a.w.q[7 * (size_t)f + k];
-    }
-  }
-  __syncthreads();
+  const double lambda = c.lambda;
+  const auto active = [&](int f) { return a.w.fstat[f] == PF_ACTIVE; };
   // (the blocks were factorised at the round's start: only a residual that is not finite fails here, and then z = 0 for every frame)
-  if (pg_precondition(a, lambda, s_scan, &s_bad))
-    for (size_t k = threadIdx.x; k < 7 * (size_t)a.n_frames; k += PB) a.w.z[k] = 0.0;
-  __syncthreads();
-  double rz = 0.0, rr = 0.0;
-  for (int f = threadIdx.x; f < a.n_frames; f += PB) {
-#pragma unroll
-    for (int k = 0; k < 7; ++k) {
-      const double r = a.w.r[7 * (size_t)f + k];
-      rz += r * a.w.z[7 * (size_t)f + k]; rr += r * r;
-    }
-  }
-  const double t_rz = pg_tree_sum(rz, s_sum);
-  const double t_rr = pg_tree_sum(rr, s_sum);
-  const double beta = t_rz / rz_old;
-  for (int f = threadIdx.x; f < a.n_frames; f += PB) {
-#pragma unroll
-    for (int k = 0; k < 7; ++k) a.w.p[7 * (size_t)f + k] = a.w.z[7 * (size_t)f + k] + beta * a.w.p[7 * (size_t)f + k];
-  }
-  if (threadIdx.x == 0) {
-    c.rz = t_rz; c.rr = t_rr; c.iters = iters + 1;
-    if (!(sqrt(t_rr) > a.cg_tol * sqrt(rr0))) c.stop = 1;      // (a residual that is not finite stops as well)
-  }
+  const auto precond = [&] {
+    const bool bad = pg_precondition(a, lambda, s_scan, &s_bad);
+    if (bad)
+      for (size_t k = threadIdx.x; k < 7 * (size_t)a.n_frames; k += PB) a.w.z[k] = 0.0;
+    return bad;
+  };
+  lm_cg_step<7, true>(c, a.n_frames, a.cg_tol, a.w.pq, a.w.z, a.w.p, active, [&](double alpha, double& rz, double& rr) {
+    lm_cg_sweep<7, true>(a.n_frames, alpha, a.w.q, a.w.r, a.w.z, a.w.x, a.w.p, active, precond, rz, rr);
+  }, s_sum);
 }
 
 // ---- the candidate and the round's verdict --------------------------------------------------------------------------------------------
@@ -710,35 +608,13 @@ __global__ __launch_bounds__(PDEC) void pg_decide_kernel(PoseGraphArgs a, int ro
   __shared__ double s_sum[256];
   PoseGraphCtl& c = *a.w.ctl;
   voe_pose_graph_round* rec = a.rounds_out ? static_cast<voe_pose_graph_round*>(a.rounds_out) + round : nullptr;
-  if (c.dead) {
-    if (threadIdx.x == 0 && rec) { rec->cost = 0.0; rec->cost_candidate = 0.0; rec->lambda = 0.0; rec->residual = 0.0; rec->cg_iterations = 0; rec->accepted = 0; }
-    return;
-  }
-  const bool formed = !c.bad && !c.nostep;
-  const double cur = c.cost_cur, lambda = c.lambda, rr0 = c.rr0, rr = c.rr;
-  const int iters = c.iters, bad = c.bad;
+  if (c.dead) { lm_round_skipped(rec); return; }
   double mine = 0.0;
-  if (formed && threadIdx.x < 256)
+  if (lm_formed(c) && threadIdx.x < 256)
     for (int e = threadIdx.x; e < a.n_edges; e += 256) mine += a.w.ecost_c[2 * (size_t)e + 1];
-  const double cand = pg_tree_sum(mine, s_sum);
-  const bool accept = formed && refine_finite(cand) && cand <= cur;
-  if (accept)
+  const double cand = block_tree_sum(mine, s_sum);
+  if (lm_decide(c, rec, cand, false, true))
     for (size_t k = threadIdx.x; k < 12 * (size_t)a.n_frames; k += PDEC) a.w.T[k] = a.w.Tc[k];
-  if (threadIdx.x == 0) {
-    if (rec) {
-      rec->cost = cur; rec->cost_candidate = formed ? cand : 0.0; rec->lambda = lambda;
-      rec->residual = !bad ? (rr0 > 0.0 ? sqrt(rr / rr0) : 0.0) : 0.0;
-      rec->cg_iterations = iters; rec->accepted = accept;
-    }
-    if (accept) {
-      c.cost_cur = cand; c.n_accepted += 1;
-      if (lambda > 0.0) { const double l = lambda / 10.0; c.lambda = l > 1e-12 ? l : 1e-12; }
-    } else {
-      const double l = 10.0 * lambda;
-      c.lambda = l > 1e-6 ? l : 1e-6;
-    }
-    c.bad = 0; c.stop = 0; c.nostep = 0; c.iters = 0;
-  }
 }
 
 // ---- the end: the state rounded to float32 into the candidate arrays, its cost (pg_edge_kernel<CAND>), the verdict -------------
@@ -754,23 +630,12 @@ __global__ __launch_bounds__(PDEC) void pg_finish_kernel(PoseGraphArgs a) {
   double mine = 0.0;
   if (!c.dead && threadIdx.x < 256)
     for (int e = threadIdx.x; e < a.n_edges; e += 256) mine += a.w.ecost_c[2 * (size_t)e + 1];
-  const double total = pg_tree_sum(mine, s_sum);
-  int status = c.status;
-  if (!c.dead) {
-    if (a.n_rounds > 0 && c.n_accepted == 0) status = VOE_POSE_GRAPH_NO_STEP;
-    else if (!(total <= c.cost_start)) status = VOE_POSE_GRAPH_COST_ROSE;      // (a cost that is not finite has risen)
-  }
+  const double total = block_tree_sum(mine, s_sum);
+  const int status = lm_final_status(c, a.n_rounds, total, VOE_POSE_GRAPH_NO_STEP, VOE_POSE_GRAPH_COST_ROSE);
   const bool write = status == VOE_POSE_GRAPH_OK && c.n_accepted > 0;
   if (write)
-    for (int f = threadIdx.x; f < a.n_frames; f += PDEC) {
-      if (a.w.fstat[f] != PF_ACTIVE) continue;
-      const double* T = a.w.Tc + 12 * (size_t)f;
-      float* o = a.S16 + 16 * (size_t)f;
-      for (int col = 0; col < 4; ++col) {
-        o[4 * col] = (float)T[3 * col]; o[4 * col + 1] = (float)T[3 * col + 1]; o[4 * col + 2] = (float)T[3 * col + 2];
-        o[4 * col + 3] = col == 3 ? 1.f : 0.f;
-      }
-    }
+    for (int f = threadIdx.x; f < a.n_frames; f += PDEC)
+      if (a.w.fstat[f] == PF_ACTIVE) store_pose12(a.w.Tc + 12 * (size_t)f, a.S16 + 16 * (size_t)f);
   for (int e = threadIdx.x; e < a.n_edges; e += PDEC) {
     if (a.edge_status_out) a.edge_status_out[e] = a.w.estatus[e];
     if (a.edge_cost_out) a.edge_cost_out[e] = write ? a.w.ecost_c[2 * (size_t)e] : a.w.es2_start[e];

@@ -6,6 +6,7 @@
 #include <stdint.h>
 
 #include "vo_math.h"
+#include "lm_pcg.h"
 
 // records the message vo_last_error() returns on this thread and hands `code` back (capi.hip)
 int vo_fail(int code, const char* fmt, ...);
@@ -616,7 +617,6 @@ __device__ __forceinline__ bool refine_row_any(bool flag) {
   const int shift = (threadIdx.x & 63) & ~(MAP_ROW - 1);     // this row's bits in a ballot of the wave
   return ((__ballot(flag) >> shift) & ((1ull << MAP_ROW) - 1ull)) != 0ull;
 }
-__device__ __forceinline__ bool refine_finite(double x) { return fabs(x) <= 1.7976931348623157e308; }
 
 // The sums of N terms over a frame's workgroup of MAP_WG threads: the DPP tree inside every row of 16 lanes, the 16 row sums
 // through LDS (s_row: 16 rows of LD >= N doubles), thread k < N adds term k in row order into s_tot[k]; afterwards every thread
@@ -715,17 +715,10 @@ hipError_t launch_map_pose_refine(hipStream_t st, const MapPoseArgs& a);
 // The observation lists of the point half alone (memset, count, offsets, scan, scatter, order): what launch_map_refine runs
 // before its refinement kernel, for callers that traverse the lists themselves.
 hipError_t launch_map_refine_lists(hipStream_t st, const MapRefineWs& w, int n_frames, int n_max, int bound);
-// the control block of a call: written by the one-workgroup launches (and `bad` by whoever meets a pivot that is not > 0)
-struct MapBundleCtl {
-  double lambda, cost_cur, cost_start, rz, rr0, rr;
-  int status;                           // the call status decided at the start (VOX_MAP_BUNDLE_*), 0 while alive
-  int dead;                             // NOT_FINITE, BEHIND or NOTHING_FREE: no round runs
-  int bad;                              // this round: a pivot of some V_j or D_f is not > 0
-  int stop;                             // this round: PCG has stopped, its remaining launches return at once
-  int nostep;                           // this round: free frames exist and PCG could not take one iteration
-  int iters;                            // this round: PCG iterations taken
-  int n_accepted, n_free_frames, n_free_points, n_obs;
-};
+// the control block of a call: the driver's (lm_pcg.h; `bad`: a pivot of some V_j or D_f is not > 0; `dead`: NOT_FINITE, BEHIND
+// or NOTHING_FREE) and the census
+struct alignas(8) MapBundleCtl : LmCtl { int n_free_frames, n_free_points, n_obs; };
+static_assert(sizeof(MapBundleCtl) == 88, "the size the workspace has always given it");
 struct MapBundleWs {
   double *T, *Tc;                       // [n_frames][12] state / candidate: R column-major, then t
   double *P, *Pc;                       // [bound][3] state / candidate
@@ -1020,17 +1013,10 @@ hipError_t launch_pose_ransac_batch(hipStream_t st, const PoseRansacBatchArgs& b
 
 // ---- the pose graph over similarities (pose_graph.hip, voe_pose_graph*) ------------------------------------------------------
 constexpr int POSE_GRAPH_REC = 30;      // doubles of an edge's record: M_A, t_A, c_A, t_E, the seven weights, the seven residuals
-// the control block of a call: written by the one-workgroup launches alone
-struct PoseGraphCtl {
-  double lambda, cost_cur, cost_start, rz, rr0, rr;
-  int status;                           // the call status decided at the start (VOE_POSE_GRAPH_*), 0 while alive
-  int dead;                             // NOT_FINITE, NOTHING_FREE or NO_EDGES: no round runs
-  int bad;                              // this round: a pivot of JACOBI is not > 0
-  int stop;                             // this round: PCG has stopped, its remaining launches return at once
-  int nostep;                           // this round: PCG could not take one iteration
-  int iters;                            // this round: PCG iterations taken
-  int n_accepted, n_free, n_active, n_live;
-};
+// the control block of a call: the driver's (lm_pcg.h; `bad`: a pivot of JACOBI is not > 0; `dead`: NOT_FINITE, NOTHING_FREE or
+// NO_EDGES) and the census
+struct alignas(8) PoseGraphCtl : LmCtl { int n_free, n_active, n_live; };
+static_assert(sizeof(PoseGraphCtl) == 88, "the size the workspace has always given it");
 struct PoseGraphWs {
   int *cnt, *cur;                       // [n_frames] incidences per frame -> offset inside its block of 256 frames; scatter cursors = the counts
   double *T, *Tc;                       // [n_frames][12] state / candidate: M column-major, then t

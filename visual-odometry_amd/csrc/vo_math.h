@@ -841,6 +841,8 @@ VO_HD bool map_refine_term(const double K[9], const float Rt[12], const double p
   return o.front();
 }
 
+VO_HD bool refine_finite(double x) { return fabs(x) <= 1.7976931348623157e308; }
+
 // x = H^-1 b for the symmetric 3x3 H (upper triangle as above) by an LDL^T in natural order, in double.  False when a pivot is
 // not > 0 (a NaN is not) or the step is not finite.
 VO_HD bool ldlt3_solve(const double H[6], const double b[3], double x[3]) {
@@ -856,8 +858,7 @@ VO_HD bool ldlt3_solve(const double H[6], const double b[3], double x[3]) {
   x[2] = y2 / d2;
   x[1] = y1 / d1 - l21 * x[2];
   x[0] = y0 / d0 - l10 * x[1] - l20 * x[2];
-  const double big = 1.7976931348623157e308;
-  return fabs(x[0]) <= big && fabs(x[1]) <= big && fabs(x[2]) <= big;
+  return refine_finite(x[0]) && refine_finite(x[1]) && refine_finite(x[2]);
 }
 
 // ---- motion-only refinement of a frame's pose on the same cost (map_pose_refine.hip; these also compile for the host) ----
@@ -877,33 +878,34 @@ VO_HD bool map_pose_term(const double K[9], const double T[12], const float pt[3
   return o.front();
 }
 
-// x = H^-1 b for the symmetric 6x6 H (upper triangle as above) by an LDL^T in natural order, in double.  False when a pivot is
-// not > 0 (a NaN is not) or the step is not finite.
-VO_HD bool ldlt6d_solve(const double Hu[21], const double b[6], double x[6]) {
-  double L[6][6], D[6];
-  int k = 0;
+// x = H^-1 b for the symmetric N x N H by an LDL^T in natural order, in double: H is the leading block of an upper triangle packed
+// row by row with rows of length LD, LD - 1, ... (LD = N: the whole triangle).  False when a pivot is not > 0 (a NaN is not) or
+// the step is not finite.
+template <int N, int LD = N>
+VO_HD bool ldlt_solve(const double* Hu, const double* b, double* x) {
+  double L[N][N], D[N];
 #pragma unroll
-  for (int r = 0; r < 6; ++r)
+  for (int r = 0; r < N; ++r)
 #pragma unroll
-    for (int c = r; c < 6; ++c) L[c][r] = Hu[k++];            // the lower triangle holds H, overwritten by L column by column
+    for (int c = r; c < N; ++c) L[c][r] = Hu[r * LD - r * (r - 1) / 2 + (c - r)];      // the lower triangle holds H, overwritten by L column by column
 #pragma unroll
-  for (int j = 0; j < 6; ++j) {
+  for (int j = 0; j < N; ++j) {
     double d = L[j][j];
 #pragma unroll
     for (int m = 0; m < j; ++m) d -= L[j][m] * L[j][m] * D[m];
     if (!(d > 0.0)) return false;
     D[j] = d;
 #pragma unroll
-    for (int i = j + 1; i < 6; ++i) {
+    for (int i = j + 1; i < N; ++i) {
       double s = L[i][j];
 #pragma unroll
       for (int m = 0; m < j; ++m) s -= L[i][m] * L[j][m] * D[m];
       L[i][j] = s / d;
     }
   }
-  double y[6];
+  double y[N];
 #pragma unroll
-  for (int i = 0; i < 6; ++i) {
+  for (int i = 0; i < N; ++i) {
     double s = b[i];
 #pragma unroll
     for (int m = 0; m < i; ++m) s -= L[i][m] * y[m];
@@ -911,15 +913,16 @@ VO_HD bool ldlt6d_solve(const double Hu[21], const double b[6], double x[6]) {
   }
   bool finite = true;
 #pragma unroll
-  for (int i = 5; i >= 0; --i) {
+  for (int i = N - 1; i >= 0; --i) {
     double s = y[i] / D[i];
 #pragma unroll
-    for (int m = i + 1; m < 6; ++m) s -= L[m][i] * x[m];
+    for (int m = i + 1; m < N; ++m) s -= L[m][i] * x[m];
     x[i] = s;
-    finite = finite && fabs(s) <= 1.7976931348623157e308;
+    finite = finite && refine_finite(s);
   }
   return finite;
 }
+VO_HD bool ldlt6d_solve(const double Hu[21], const double b[6], double x[6]) { return ldlt_solve<6>(Hu, b, x); }
 
 // T <- v2t(dx) T in double: v2t is the solver's (translation dx[0:3], R = Rx(dx3) Ry(dx4) Rz(dx5), v2t_from_sincos above)
 VO_HD void pose_apply_v2t(const double dx[6], double T[12]) {
@@ -994,6 +997,18 @@ __device__ __forceinline__ int block_rank(bool flag, int* s_wave, int& total) {
   }
   total = tot;
   return off + before;
+}
+
+// the sum of v over the workgroup (any multiple of 64 threads up to 1024), in every thread; s_w: one int of LDS per wave
+__device__ __forceinline__ int block_sum(int v, int* s_w) {
+#pragma unroll
+  for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d);
+  __syncthreads();                                          // (s_w may still be read from a sum before)
+  if ((threadIdx.x & 63) == 0) s_w[threadIdx.x >> 6] = v;
+  __syncthreads();
+  int tot = 0;
+  for (int w = 0; w < (int)(blockDim.x >> 6); ++w) tot += s_w[w];
+  return tot;
 }
 
 // exclusive prefix sum of `v` over a workgroup of NT threads (s_wave: NT / 64 ints of LDS); total = the workgroup's sum
