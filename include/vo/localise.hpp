@@ -231,6 +231,27 @@ inline const char* nearest_status_name(int status) {
   return status >= 0 && status < 6 ? names[status] : "?";
 }
 
+//! voe_map_guided: frames associated with the map by the nearest appearance among the entries that project, under a pose prior,
+//! within a pixel window of the row (include/vo_hip.h, GUIDED)
+struct GuidedOptions {
+  float radius_px = 8.f;             //!< an entry is a candidate when it projects within radius_px of the row's pixel
+  float radius = 0.1f;               //!< ... and its squared appearance distance is below radius^2
+  float ratio = 0.f;                 //!< 0: off; otherwise a row whose best is not below ratio^2 times its second-best candidate is AMBIGUOUS
+  bool unique = false;               //!< an entry keeps its closest row of a frame, the others are DISPLACED
+};
+struct MapGuided {
+  std::vector<std::vector<int32_t>> entry;     //!< per frame, per row: the entry, -1 unless MATCHED
+  std::vector<std::vector<int32_t>> status;    //!< VOE_MAP_GUIDED_*
+  std::vector<std::vector<float>> dist2;       //!< the best squared appearance distance, +inf where there is none
+  std::vector<std::vector<float>> pix2;        //!< the squared pixel distance of that candidate, +inf where there is none
+  std::vector<Vector10fVector> canonical;      //!< the rows as every map call is to see them: matched rows carry their entry's bytes
+  voe_map_guided_stats stats{};
+};
+inline const char* guided_status_name(int status) {
+  static const char* names[] = {"MATCHED", "NO_ENTRY", "AMBIGUOUS", "DISPLACED", "NAN_ROW", "NOT_LIVE"};
+  return status >= 0 && status < 6 ? names[status] : "?";
+}
+
 //! The rigid pose that goes with a similarity S = [c R | t] of the pose graph (vo/pose_graph.hpp): [R | t / c], on the host in
 //! double.  A map point moved by S_new^-1 S_old of its reference frame (DeviceMap::applyCorrection) projects there, under
 //! rigid_pose(S_new), where it projected before.
@@ -542,6 +563,46 @@ class DeviceMap {
       r.entry[f].assign(ent.begin() + f * cap, ent.begin() + f * cap + m);
       r.status[f].assign(st.begin() + f * cap, st.begin() + f * cap + m);
       r.dist2[f].assign(d2.begin() + f * cap, d2.begin() + f * cap + m);
+      r.canonical[f].resize(m);
+      for (size_t i = 0; i < m; ++i) std::memcpy(r.canonical[f][i].data(), &app[(f * cap + i) * 10], sizeof(float) * 10);
+    }
+    return r;
+  }
+
+  //! the same for a tracker that has a pose prior per frame (p_cam = T p_map): only the entries that project within
+  //! o.radius_px of a row's pixel are its candidates (voe_map_guided; the camera gives K and the depth gate).  `canonical`
+  //! then feeds localise(..., T0 = the prior) with n_hypotheses == 0: tracking against the map.
+  MapGuided guided(const Camera& camera, const std::vector<Vector2fVector>& pixels, const std::vector<Vector10fVector>& appearances,
+                   const IsometryVector& poses, const GuidedOptions& o = GuidedOptions()) const {
+    MapGuided r;
+    const size_t F = appearances.size();
+    if (pixels.size() != F || poses.size() != F) throw Error(VO_ERR_INVALID_ARG, "DeviceMap::guided: per-frame arrays differ in size");
+    size_t cap = 0;
+    for (size_t f = 0; f < F; ++f) {
+      if (pixels[f].size() != appearances[f].size()) throw Error(VO_ERR_INVALID_ARG, "DeviceMap::guided: pixels and appearances differ in size");
+      cap = appearances[f].size() > cap ? appearances[f].size() : cap;
+    }
+    std::vector<float> uv(F * cap * 2 + 2, 0.f), app(F * cap * 10 + 10, 0.f), d2(F * cap + 1, 0.f), g2(F * cap + 1, 0.f), T(F * 16 + 16, 0.f);
+    std::vector<int> n(F + 1, 0);
+    std::vector<int32_t> ent(F * cap + 1, -1), st(F * cap + 1, VOE_MAP_GUIDED_NOT_LIVE);
+    for (size_t f = 0; f < F; ++f) {
+      n[f] = (int)appearances[f].size();
+      std::memcpy(&T[16 * f], poses[f].data(), sizeof(float) * 16);
+      for (size_t i = 0; i < appearances[f].size(); ++i) {
+        for (int k = 0; k < 2; ++k) uv[(f * cap + i) * 2 + k] = pixels[f][i][k];
+        for (int k = 0; k < 10; ++k) app[(f * cap + i) * 10 + k] = appearances[f][i][k];
+      }
+    }
+    const voe_map_guided_params p{o.radius_px, o.radius, o.ratio, o.unique ? 1 : 0, camera.zNear(), camera.zFar(), {0, 0}};
+    check(voe_map_guided(h_, (int)F, camera.cameraMatrix().data(), uv.data(), app.data(), n.data(), (int)cap, T.data(), &p, ent.data(), st.data(),
+                         d2.data(), g2.data(), app.data(), &r.stats), "voe_map_guided");
+    r.entry.resize(F); r.status.resize(F); r.dist2.resize(F); r.pix2.resize(F); r.canonical.resize(F);
+    for (size_t f = 0; f < F; ++f) {
+      const size_t m = appearances[f].size();
+      r.entry[f].assign(ent.begin() + f * cap, ent.begin() + f * cap + m);
+      r.status[f].assign(st.begin() + f * cap, st.begin() + f * cap + m);
+      r.dist2[f].assign(d2.begin() + f * cap, d2.begin() + f * cap + m);
+      r.pix2[f].assign(g2.begin() + f * cap, g2.begin() + f * cap + m);
       r.canonical[f].resize(m);
       for (size_t i = 0; i < m; ++i) std::memcpy(r.canonical[f][i].data(), &app[(f * cap + i) * 10], sizeof(float) * 10);
     }

@@ -803,6 +803,82 @@ int voe_map_nearest(vo_map *m, int n_frames, const float *app, const int *n_rows
                     const voe_map_nearest_params *p, int32_t *entry_out, int32_t *status_out, float *dist2_out, float *app_out,
                     voe_map_nearest_stats *stats_out);
 
+/* GUIDED.  NEAREST's sibling for a tracker that has a pose prior (the last pose, a motion model, the bundle's result): the
+ * candidates of a row are restricted to the entries whose projection under the frame's prior falls within radius_px of the
+ * row's pixel -- "projective" association: it tells landmarks that look alike apart by where they must appear.  What it
+ * costs follows the density of the projections: every entry in a row's window is tested -- about one where the window is
+ * selective (a tracker's local map), hundreds where a dense map projects into the image, and then NEAREST is the faster
+ * call (DESIGN.md section 4.24 has the measurements).  The outputs follow NEAREST's convention, so the exact lookup and
+ * every call built on it consume the association unchanged (vo_map_localise* with n_hypotheses == 0 and d_T0 = the prior is
+ * the consumer this call exists for).  DESIGN.md section 4.24.
+ * d_T16 [n_frames][16]: the priors, column-major, p_cam = T p_map, in DEVICE memory (a pose produced on the device feeds
+ * the call without a read-back); K [9] column-major on the host; d_uv / uv_stride (pixels) and d_app / app_stride (rows) as
+ * in vo_map_localise_batch_dev, both strides >= n_max.  Rules; every output is a function of the data alone:
+ *   1. PIXEL.  The pixel of entry e in frame f is Camera::projectPoint in the reference's float32 order (project_point of
+ *      vo_math.h; the library is built with contraction off): pc = R p + t, ph = K pc, inv = 1 / ph.z, u = ph.x * inv,
+ *      v = ph.y * inv, every three-term sum as x0 + (x1 + x2).  The entry is IN VIEW iff pc.z > 0 and not
+ *      (pc.z > z_far || pc.z < z_near).  The image gate of projectPoint is deliberately NOT applied: under a prior that is
+ *      off by a few pixels an entry just outside the image may be the row's landmark, and rule 2 already bounds where a
+ *      candidate can lie.
+ *   2. PIXEL GATE.  g2 = (u_e - u_row)^2 + (v_e - v_row)^2 in float32, unfused, left to right.  e is GATED for the row iff it
+ *      is in view and g2 < radius_px * radius_px (the product float32; strict, and taken only where it evaluates true: a NaN
+ *      or an infinity in the pose, the entry's point, the projection or the row's pixel never gates).
+ *   3. CANDIDATES.  d2 is NEAREST's rule 1, r2 = radius * radius; the candidates of a row are the gated entries with d2 < r2.
+ *   4. DECISION.  NEAREST's rules 2 to 4 word for word over the candidates: best is the smallest d2, exact ties to the lowest
+ *      entry; ratio is taken against the second-best CANDIDATE (an entry outside the pixel gate or the radius does not count);
+ *      unique is per frame, ties to the lowest row.
+ *   5. STATUSES.  VOE_MAP_GUIDED_* = VOE_MAP_NEAREST_*, the same precedence (NO_ENTRY: no candidate).  d_entry_out and
+ *      d_dist2_out as in NEAREST; d_pix2_out holds g2 of the best candidate where MATCHED / AMBIGUOUS / DISPLACED and +inf
+ *      otherwise.
+ *   6. CANONICAL ROWS.  d_app_out is NEAREST's rule 6 exactly, the quiet NaN 0x7FC00000 in component 0 of AMBIGUOUS and
+ *      DISPLACED rows included; d_app_out == d_app is allowed.  CONTRACT: vo_map_lookup_batch_dev on d_app_out returns, at
+ *      every position of every frame, the bytes of d_entry_out.  (The same two corners: a row holding an infinity that compares
+ *      equal to an entry, and a radius whose float32 square is 0, are NO_ENTRY here and hits of the lookup.  The window adds
+ *      a third of the same kind: a row that compares EQUAL to an entry which is not gated for it -- a copied appearance
+ *      whose landmark the prior puts elsewhere -- is NO_ENTRY here, keeps its bytes by NEAREST's rule 6, and is a hit of the
+ *      lookup.  A measured appearance never is such a copy; a caller that feeds copies and wants the window to hold
+ *      replaces component 0 of its NO_ENTRY rows as rule 6 does for AMBIGUOUS ones.)
+ *   7. STATISTICS.  The counts of rule 5 over all frames, n_entries (the size the device holds), n_in_view (the sum over the
+ *      frames of the entries in view) and n_gated (the (live row, entry) pairs that pass rule 2): integer sums, exact in any
+ *      order.
+ *   8. The map is never written and nothing is read back; no float atomics; no launch waits for another workgroup; the
+ *      launches are a fixed sequence that depends on (n_frames, n_max, the capacity, unique) alone.  The index (per frame: the
+ *      entries in view, sorted into a pixel grid) is built by every call and kept by none.  The host's bound of the size is
+ *      not the size (MapBound, map_checks.h): the kernels read the size from the device; captured, the call is sized by the
+ *      capacity.  Capturable once a call of the same shape (n_frames, n_max, unique) has sized the map's workspace; a capture
+ *      that would have to grow it is refused (VO_ERR_NOT_READY) before anything is enqueued.  Frame f of the batched call is
+ *      bit for bit the single call.
+ *   9. Refused (VO_ERR_INVALID_ARG): the lookup's refusals for the frames; a null params, d_entry_out, d_uv, d_T16 or K;
+ *      radius_px or radius not finite or <= 0; a ratio outside {0} u (0, 1]; unique outside 0 / 1; z_far < z_near; reserved
+ *      != 0; uv_stride or app_stride below n_max; d_uv, d_app_out or d_stats off an 8-byte boundary, a 4-byte output or the
+ *      poses off a 4-byte one; d_app_out overlapping d_app without being d_app. */
+#define VOE_MAP_GUIDED_MATCHED   0
+#define VOE_MAP_GUIDED_NO_ENTRY  1
+#define VOE_MAP_GUIDED_AMBIGUOUS 2
+#define VOE_MAP_GUIDED_DISPLACED 3
+#define VOE_MAP_GUIDED_NAN_ROW   4
+#define VOE_MAP_GUIDED_NOT_LIVE  5
+typedef struct voe_map_guided_params { float radius_px; float radius; float ratio; int32_t unique; int32_t z_near; int32_t z_far; int32_t reserved[2]; } voe_map_guided_params;   /* 32 bytes */
+typedef struct voe_map_guided_stats  { int32_t n_frames, n_entries, n_live, n_matched, n_no_entry, n_ambiguous, n_displaced, n_nan; int64_t n_in_view, n_gated; } voe_map_guided_stats; /* 48 bytes */
+int voe_map_guided_batch_dev(vo_map *m, int n_frames, const float K[9], const float *d_uv, size_t uv_stride, const float *d_app,
+                             size_t app_stride, int n_max, const int *d_n_rows /* [n_frames] or NULL */,
+                             const float *d_T16 /* [n_frames][16] */, const voe_map_guided_params *p,
+                             int32_t *d_entry_out   /* [n_frames][n_max] */,
+                             int32_t *d_status_out  /* [n_frames][n_max] or NULL */,
+                             float   *d_dist2_out   /* [n_frames][n_max] or NULL */,
+                             float   *d_pix2_out    /* [n_frames][n_max] or NULL */,
+                             float   *d_app_out     /* frames laid out as d_app (same stride), or NULL; may be d_app itself */,
+                             voe_map_guided_stats *d_stats /* or NULL */);
+int voe_map_guided_dev(vo_map *m, const float K[9], const float *d_uv, const float *d_app, int n_max, const int *d_n_rows /* or NULL */,
+                       const float *d_T16 /* [16] */, const voe_map_guided_params *p, int32_t *d_entry_out,
+                       int32_t *d_status_out /* or NULL */, float *d_dist2_out /* or NULL */, float *d_pix2_out /* or NULL */,
+                       float *d_app_out /* or NULL */, voe_map_guided_stats *d_stats /* or NULL */);
+/* host arrays in (uv [n_frames][n_max][2], app [n_frames][n_max][10], n_rows [n_frames] or NULL, T16 [n_frames][16]), host
+ * arrays out (any but entry_out may be NULL; app_out may be app itself); waits */
+int voe_map_guided(vo_map *m, int n_frames, const float K[9], const float *uv, const float *app, const int *n_rows /* or NULL */,
+                   int n_max, const float *T16, const voe_map_guided_params *p, int32_t *entry_out, int32_t *status_out,
+                   float *dist2_out, float *pix2_out, float *app_out, voe_map_guided_stats *stats_out);
+
 /* LOCALISATION.  The pose of a camera in the map from one frame alone: T (column-major 4x4, p_cam = T * p_map, the
  * convention of vo_picp_set_pose).  d_uv [n_max][2] pixels and d_app [n_max][10] appearances of the frame, *d_n_rows (or
  * NULL) <= n_max of them live.  Steps, all enqueued on the context's stream, no host round trip:

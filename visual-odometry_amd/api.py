@@ -801,6 +801,42 @@ class Map:
         cut = lambda a: [a[f, : n[f]].copy() for f in range(F)]
         return dict(entry=cut(ent), status=cut(sta), dist2=cut(d2), app=cut(out), stats=st.as_dict())
 
+    # ---- the nearest entry among those that project near the row's pixel under a pose prior (voe_map_guided*, vo_hip.h: GUIDED) ----
+    def guided_batch_dev(self, camera: Camera, n_frames, d_uv, uv_stride, d_app, app_stride, n_max, d_n, d_T16, params: "MapGuidedParams",
+                         d_entry_out, d_status_out=None, d_dist2_out=None, d_pix2_out=None, d_app_out=None, d_stats=None):
+        """voe_map_guided_batch_dev on device pointers (ints; d_n and every output but d_entry_out may be None; strides in pixels /
+        rows; d_T16: n_frames priors of 16 floats, column-major; d_app_out may be d_app): enqueues and returns.  K is the camera's;
+        the depth gate is params.z_near / z_far.  d_stats: 48 bytes (MapGuidedStats)."""
+        v = lambda d: C.c_void_p(d) if d else None
+        _chk(self.lib.voe_map_guided_batch_dev(self.h, C.c_int(n_frames), _ptr(_colmajor(camera._K, 3)), v(d_uv), C.c_size_t(uv_stride),
+                                               v(d_app), C.c_size_t(app_stride), C.c_int(n_max), v(d_n), v(d_T16), C.byref(params),
+                                               v(d_entry_out), v(d_status_out), v(d_dist2_out), v(d_pix2_out), v(d_app_out), v(d_stats)))
+
+    def guided(self, camera: Camera, frames, poses, radius_px, radius, ratio=0.0, unique=False):
+        """voe_map_guided: for every row of every frame [(uv, app)] the nearest entry within `radius` among the entries that
+        project, under the frame's prior `poses[f]` (4x4, p_cam = T p_map), within `radius_px` of the row's pixel; the camera gives
+        K and the depth gate.  Returns dict(entry, status, dist2, pix2: lists of per-frame arrays; app: the canonical rows per
+        frame; stats dict).  Status names: MAP_GUIDED_STATUS."""
+        F = len(frames)
+        assert len(poses) == F
+        n = np.array([len(_f32(a, (-1, 10))) for _, a in frames], np.int32)
+        cap = int(n.max()) if F else 0
+        shape = (max(F, 1), max(cap, 1))
+        uv, app = np.zeros(shape + (2,), np.float32), np.zeros(shape + (10,), np.float32)
+        for f, (p, a) in enumerate(frames):
+            uv[f, : n[f]] = _f32(p, (-1, 2))
+            app[f, : n[f]] = _f32(a, (-1, 10))
+        T = np.stack([_colmajor(X, 4) for X in poses]).astype(np.float32) if F else np.zeros((1, 16), np.float32)
+        ent, sta = np.full(shape, -1, np.int32), np.full(shape, 5, np.int32)
+        d2, g2 = np.full(shape, np.inf, np.float32), np.full(shape, np.inf, np.float32)
+        out = app.copy()
+        st = MapGuidedStats()
+        pr = MapGuidedParams(float(radius_px), float(radius), float(ratio), int(bool(unique)), int(camera._z_near), int(camera._z_far))
+        _chk(self.lib.voe_map_guided(self.h, C.c_int(F), _ptr(_colmajor(camera._K, 3)), _ptr(uv) if cap else None, _ptr(app) if cap else None,
+                                     _ptr(n), C.c_int(cap), _ptr(T), C.byref(pr), _ptr(ent), _ptr(sta), _ptr(d2), _ptr(g2), _ptr(out), C.byref(st)))
+        cut = lambda a: [a[f, : n[f]].copy() for f in range(F)]
+        return dict(entry=cut(ent), status=cut(sta), dist2=cut(d2), pix2=cut(g2), app=cut(out), stats=st.as_dict())
+
     # ---- covisibility of frames and the window chosen from it (voe_map_covis*, voe_map_window*, include/vo_map_covis.h) ----
     def words(self):
         """the 32-bit words a bit row needs for this map: enough for size_bound() entries, at least one"""
@@ -1152,6 +1188,26 @@ class MapNearestStats(C.Structure):
 
 assert C.sizeof(MapNearestParams) == 16 and C.sizeof(MapNearestStats) == 32
 MAP_NEAREST_STATUS = ("MATCHED", "NO_ENTRY", "AMBIGUOUS", "DISPLACED", "NAN_ROW", "NOT_LIVE")      # VOE_MAP_NEAREST_*
+
+
+class MapGuidedParams(C.Structure):
+    """voe_map_guided_params (include/vo_hip.h)"""
+    _fields_ = [("radius_px", C.c_float), ("radius", C.c_float), ("ratio", C.c_float), ("unique", C.c_int32), ("z_near", C.c_int32),
+                ("z_far", C.c_int32), ("reserved", C.c_int32 * 2)]
+
+
+class MapGuidedStats(C.Structure):
+    """voe_map_guided_stats (include/vo_hip.h)"""
+    _fields_ = [("n_frames", C.c_int32), ("n_entries", C.c_int32), ("n_live", C.c_int32), ("n_matched", C.c_int32),
+                ("n_no_entry", C.c_int32), ("n_ambiguous", C.c_int32), ("n_displaced", C.c_int32), ("n_nan", C.c_int32),
+                ("n_in_view", C.c_int64), ("n_gated", C.c_int64)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+assert C.sizeof(MapGuidedParams) == 32 and C.sizeof(MapGuidedStats) == 48
+MAP_GUIDED_STATUS = MAP_NEAREST_STATUS                                          # VOE_MAP_GUIDED_* = VOE_MAP_NEAREST_*
 
 
 class MapCovisStats(C.Structure):

@@ -1,5 +1,5 @@
 // capi_map.hip -- the map's half of the extern "C" boundary (vo_hip.h: vo_map_*; vo_map_adjust.h, vo_map_bundle.h, vo_map_cull.h,
-// vo_map_align.h, vo_map_covis.h, vo_map_grow.h, vo_map_loops.h; voe_map_nearest* of vo_hip.h itself) and the pose graph's (vo_pose_graph.h).  Host-side plumbing only, like capi.hip: no kernel lives here.
+// vo_map_align.h, vo_map_covis.h, vo_map_grow.h, vo_map_loops.h; voe_map_nearest* and voe_map_guided* of vo_hip.h itself) and the pose graph's (vo_pose_graph.h).  Host-side plumbing only, like capi.hip: no kernel lives here.
 #include <limits.h>
 #include <string.h>
 
@@ -30,6 +30,7 @@ struct vo_map {
   DevBuf grow_ws;               // voe_map_grow*: the open rows, the tracks' private table, verdicts, the staging area (the lists live in ref_ws)
   DevBuf loops_ws;              // voe_map_loops*: the lookup's arrays, keys, reference frames, bit rows, candidates, slots, the gathered problems
   DevBuf nearest_ws;            // voe_map_nearest*: the call's index of the map (grid, start table, records), best / distance / status per row, the claim words
+  DevBuf guided_ws;             // voe_map_guided*: per frame of a group the grid, the cell tables and the records; best / distance / status per row, the claim words
   MapLoopsWs loops_last{};      // ... as the last call laid it out (voe_map_loops_problems_dev); bytes == 0: no call yet
 };
 
@@ -127,7 +128,7 @@ int vo_map_destroy(vo_map* m) {
   map_free_arrays(m->d);
   if (m->d.hdr) (void)hipFree(m->d.hdr);
   if (m->hist) (void)hipFree(m->hist);
-  m->scratch.release(); m->up_xyz.release(); m->up_app.release(); m->look_ws.release(); m->loc_ws.release(); m->ref_ws.release(); m->pose_ws.release(); m->bundle_ws.release(); m->cull_ws.release(); m->align_ws.release(); m->merge_ws.release(); m->covis_ws.release(); m->window_ws.release(); m->grow_ws.release(); m->loops_ws.release(); m->nearest_ws.release();
+  m->scratch.release(); m->up_xyz.release(); m->up_app.release(); m->look_ws.release(); m->loc_ws.release(); m->ref_ws.release(); m->pose_ws.release(); m->bundle_ws.release(); m->cull_ws.release(); m->align_ws.release(); m->merge_ws.release(); m->covis_ws.release(); m->window_ws.release(); m->grow_ws.release(); m->loops_ws.release(); m->nearest_ws.release(); m->guided_ws.release();
   if (m->solver) (void)vo_picp_destroy(m->solver);
   delete m;
   return VO_OK;
@@ -572,6 +573,80 @@ int voe_map_nearest(vo_map* m, int n_frames, const float* app, const int* n_rows
     if (app_out) VO_HIP_CHECK(hipMemcpyAsync(app_out, c->in[1].p, sizeof(float) * 10 * rows, hipMemcpyDeviceToHost, c->stream));
   }
   if (stats_out) VO_HIP_CHECK(hipMemcpyAsync(stats_out, d_stats, sizeof(voe_map_nearest_stats), hipMemcpyDeviceToHost, c->stream));
+  VO_HIP_CHECK(hipStreamSynchronize(c->stream));
+  return VO_OK;
+}
+
+// ---- the nearest entry among those that project near the row's pixel under a prior (map_guided.hip; include/vo_hip.h, GUIDED) ----
+static_assert(sizeof(voe_map_guided_params) == 32 && sizeof(voe_map_guided_stats) == 48, "the kernels write eight 4-byte words and two 8-byte ones");
+
+int voe_map_guided_batch_dev(vo_map* m, int n_frames, const float K[9], const float* d_uv, size_t uv_stride, const float* d_app,
+                             size_t app_stride, int n_max, const int* d_n, const float* d_T16, const voe_map_guided_params* p,
+                             int32_t* d_entry_out, int32_t* d_status_out, float* d_dist2_out, float* d_pix2_out, float* d_app_out,
+                             voe_map_guided_stats* d_stats) {
+  const char* fn = "voe_map_guided_batch_dev";
+  const MapFrames f{n_frames, K, d_uv, uv_stride, d_app, app_stride, n_max, d_n};
+  if (int r = map_guided_check(fn, f, p, MapGuidedPtrs{d_T16, d_entry_out, d_status_out, d_dist2_out, d_pix2_out, d_app_out, d_stats})) return r;
+  VO_MAP_LIVE(m);
+  vo_ctx* c = m->ctx;
+  // allocated for the capacity, launched for the launch bound, the size read on the device: as voe_map_nearest_batch_dev
+  const MapGuidedWs need = map_guided_layout(nullptr, n_frames, n_max, m->bd.alloc_bound(), p->unique != 0);
+  if (int r = capture_growth_check(c->capturing, fn, {{m->guided_ws.cap, need.bytes}}, "%d frames of n_max %d and unique %d on this map", n_frames, n_max, p->unique))
+    return r;
+  if (int r = set_device(c)) return r;
+  VO_HIP_CHECK(m->guided_ws.ensure(need.bytes, c->stream));
+  MapGuidedArgs a{};
+  a.w = map_guided_layout(m->guided_ws.p, n_frames, n_max, m->bd.alloc_bound(), p->unique != 0);
+  a.n.w = a.w.n;
+  a.n.app = m->d.app; a.n.hdr = m->d.hdr; a.n.cap = m->d.cap; a.n.bound = map_launch_bound(m);
+  a.n.q_app = d_app; a.n.q_stride = 10 * app_stride; a.n.n_frames = n_frames; a.n.n_max = n_max; a.n.d_n = d_n;
+  a.n.radius = p->radius; a.n.ratio = p->ratio; a.n.unique = p->unique;
+  a.n.entry = d_entry_out; a.n.status = d_status_out; a.n.dist2 = d_dist2_out; a.n.app_out = d_app_out; a.n.stats = reinterpret_cast<int*>(d_stats);
+  a.pts = m->d.pts; a.uv = d_uv; a.uv_stride = 2 * uv_stride; a.T16 = d_T16;
+  for (int k = 0; k < 9; ++k) a.K[k] = K[k];
+  a.radius_px = p->radius_px; a.z_near = p->z_near; a.z_far = p->z_far;
+  a.pix2 = d_pix2_out; a.stats64 = d_stats ? reinterpret_cast<unsigned long long*>(d_stats) + 4 : nullptr;
+  VO_HIP_CHECK(launch_map_guided(c->stream, a));
+  return VO_OK;
+}
+
+int voe_map_guided_dev(vo_map* m, const float K[9], const float* d_uv, const float* d_app, int n_max, const int* d_n, const float* d_T16,
+                       const voe_map_guided_params* p, int32_t* d_entry_out, int32_t* d_status_out, float* d_dist2_out, float* d_pix2_out,
+                       float* d_app_out, voe_map_guided_stats* d_stats) {
+  const size_t stride = (size_t)(n_max > 0 ? n_max : 0);
+  return voe_map_guided_batch_dev(m, 1, K, d_uv, stride, d_app, stride, n_max, d_n, d_T16, p, d_entry_out, d_status_out, d_dist2_out, d_pix2_out, d_app_out, d_stats);
+}
+
+int voe_map_guided(vo_map* m, int n_frames, const float K[9], const float* uv, const float* app, const int* n_rows, int n_max,
+                   const float* T16, const voe_map_guided_params* p, int32_t* entry_out, int32_t* status_out, float* dist2_out,
+                   float* pix2_out, float* app_out, voe_map_guided_stats* stats_out) {
+  const char* fn = "voe_map_guided";
+  if (!p || !entry_out || !T16 || !K) return vo_fail(VO_ERR_INVALID_ARG, "%s: null params, entry_out, T16 or K", fn);
+  VO_MAP_LIVE(m);
+  vo_ctx* c = m->ctx;
+  VO_NOT_CAPTURING(c);
+  MapFrames f;
+  if (int r = upload_window(fn, m, MapFrames{n_frames, K, uv, 0, app, 0, n_max, n_rows}, T16, nullptr, nullptr, &f)) return r;
+  VO_HIP_CHECK(hipStreamSynchronize(c->stream));            // the host arrays may go away after the call
+  const size_t rows = (size_t)n_frames * (size_t)n_max, w_bytes = (sizeof(float) * rows + 7) & ~(size_t)7;
+  VO_HIP_CHECK(c->out[0].ensure(sizeof(int32_t) * rows + 8, c->stream));
+  VO_HIP_CHECK(c->out[1].ensure(sizeof(int32_t) * rows + 8, c->stream));
+  VO_HIP_CHECK(c->out[2].ensure(2 * w_bytes + sizeof(voe_map_guided_stats), c->stream));
+  float* d_pix2 = reinterpret_cast<float*>(static_cast<char*>(c->out[2].p) + w_bytes);
+  voe_map_guided_stats* d_stats = reinterpret_cast<voe_map_guided_stats*>(static_cast<char*>(c->out[2].p) + 2 * w_bytes);
+  // the canonical rows are written in place over the staged rows (d_app_out == d_app)
+  if (int r = voe_map_guided_batch_dev(m, n_frames, K, f.d_uv, f.uv_stride, f.d_app, f.app_stride, n_max, f.d_n, c->in[2].as<float>(), p,
+                                       c->out[0].as<int32_t>(), c->out[1].as<int32_t>(), c->out[2].as<float>(), d_pix2,
+                                       app_out && rows > 0 ? c->in[1].as<float>() : nullptr, d_stats))
+    return r;
+  if (rows > 0) {
+    VO_HIP_CHECK(hipMemcpyAsync(entry_out, c->out[0].p, sizeof(int32_t) * rows, hipMemcpyDeviceToHost, c->stream));
+    if (status_out) VO_HIP_CHECK(hipMemcpyAsync(status_out, c->out[1].p, sizeof(int32_t) * rows, hipMemcpyDeviceToHost, c->stream));
+    if (dist2_out) VO_HIP_CHECK(hipMemcpyAsync(dist2_out, c->out[2].p, sizeof(float) * rows, hipMemcpyDeviceToHost, c->stream));
+    if (pix2_out) VO_HIP_CHECK(hipMemcpyAsync(pix2_out, d_pix2, sizeof(float) * rows, hipMemcpyDeviceToHost, c->stream));
+    if (app_out) VO_HIP_CHECK(hipMemcpyAsync(app_out, c->in[1].p, sizeof(float) * 10 * rows, hipMemcpyDeviceToHost, c->stream));
+  }
+  if (stats_out) VO_HIP_CHECK(hipMemcpyAsync(stats_out, d_stats, sizeof(voe_map_guided_stats), hipMemcpyDeviceToHost, c->stream));
   VO_HIP_CHECK(hipStreamSynchronize(c->stream));
   return VO_OK;
 }

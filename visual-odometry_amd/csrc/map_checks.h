@@ -225,6 +225,45 @@ static inline int map_nearest_check(const char* fn, const MapFrames& f, const vo
   return VO_OK;
 }
 
+// voe_map_guided*: what the call refuses (include/vo_hip.h, GUIDED), in the order they fire.  1 - 6 are the lookup's refusals for
+// the frames as map_nearest_check states them (3 and 4 now also for the pixels); `f` carries K, d_uv and both strides:
+//   1. n_frames outside 1 .. 65535      2. negative n_max      3. null appearances or pixels with n_max > 0
+//   4. appearance rows or pixels off an 8-byte boundary      5. app_stride or uv_stride < n_max
+//   6. app_stride >= (2^31 - 1) / 10, uv_stride >= 2^31 - 1 or more than 2^30 rows
+//   7. a null params, d_entry_out, d_T16 or K      8. radius_px, then radius, not finite or <= 0
+//   9. a ratio that is not finite or outside {0} u (0, 1]      10. unique outside 0 / 1      11. z_far < z_near
+//   12. reserved != 0      13. an int32 / float32 array (the poses among them) off a 4-byte boundary, d_app_out or d_stats off an
+//   8-byte one      14. d_app_out overlapping d_app without being d_app
+struct MapGuidedPtrs {
+  const void *T16, *entry, *status, *dist2, *pix2, *app_out, *stats;
+};
+static inline int map_guided_check(const char* fn, const MapFrames& f, const voe_map_guided_params* p, const MapGuidedPtrs& d) {
+  if (f.n_frames < 1 || f.n_frames > 65535) return vo_fail(VO_ERR_INVALID_ARG, "%s: n_frames %d outside 1 .. 65535 (the frame is a grid dimension)", fn, f.n_frames);
+  if (f.n_max < 0) return vo_fail(VO_ERR_INVALID_ARG, "%s: negative row count", fn);
+  if (f.n_max > 0 && !(f.d_app && f.d_uv)) return vo_fail(VO_ERR_INVALID_ARG, "%s: null argument", fn);
+  if (!aligned8(f.d_app, f.d_uv)) return vo_fail(VO_ERR_INVALID_ARG, "%s: device appearance rows and pixels must be 8-byte aligned", fn);
+  if (f.app_stride < (size_t)f.n_max || f.uv_stride < (size_t)f.n_max) return vo_fail(VO_ERR_INVALID_ARG, "%s: a stride is smaller than n_max %d", fn, f.n_max);
+  if (f.app_stride >= 0x7fffffff / 10 || f.uv_stride >= 0x7fffffff || (long long)f.n_max * f.n_frames > (1ll << 30))
+    return vo_fail(VO_ERR_INVALID_ARG, "%s: more than 2^30 rows in one call", fn);
+  if (!p || !d.entry || !d.T16 || !f.K) return vo_fail(VO_ERR_INVALID_ARG, "%s: null params, d_entry_out, d_T16 or K", fn);
+  if (!(p->radius_px > 0.f && p->radius_px <= 3.402823466e38f)) return vo_fail(VO_ERR_INVALID_ARG, "%s: radius_px must be finite and positive", fn);
+  if (!(p->radius > 0.f && p->radius <= 3.402823466e38f)) return vo_fail(VO_ERR_INVALID_ARG, "%s: radius must be finite and positive", fn);
+  if (!(p->ratio >= 0.f && p->ratio <= 1.f)) return vo_fail(VO_ERR_INVALID_ARG, "%s: ratio must be 0 (off) or in (0, 1]", fn);
+  if (p->unique != 0 && p->unique != 1) return vo_fail(VO_ERR_INVALID_ARG, "%s: unique must be 0 or 1", fn);
+  if (p->z_far < p->z_near) return vo_fail(VO_ERR_INVALID_ARG, "%s: z_far is below z_near", fn);
+  if (p->reserved[0] != 0 || p->reserved[1] != 0) return vo_fail(VO_ERR_INVALID_ARG, "%s: reserved must be 0", fn);
+  if ((reinterpret_cast<uintptr_t>(d.T16) | reinterpret_cast<uintptr_t>(d.entry) | reinterpret_cast<uintptr_t>(d.status) |
+       reinterpret_cast<uintptr_t>(d.dist2) | reinterpret_cast<uintptr_t>(d.pix2)) & 3u)
+    return vo_fail(VO_ERR_INVALID_ARG, "%s: int32 and float32 arrays must be 4-byte aligned", fn);
+  if (!aligned8(d.app_out, d.stats)) return vo_fail(VO_ERR_INVALID_ARG, "%s: d_app_out and d_stats must be 8-byte aligned", fn);
+  if (d.app_out && d.app_out != (const void*)f.d_app && f.n_max > 0) {
+    const uintptr_t span = sizeof(float) * 10 * ((uintptr_t)(f.n_frames - 1) * f.app_stride + (uintptr_t)f.n_max);
+    const uintptr_t a = reinterpret_cast<uintptr_t>(f.d_app), b = reinterpret_cast<uintptr_t>(d.app_out);
+    if (a < b + span && b < a + span) return vo_fail(VO_ERR_INVALID_ARG, "%s: d_app_out overlaps d_app without being d_app", fn);
+  }
+  return VO_OK;
+}
+
 // A workspace that would have to grow inside a graph capture: growing frees, allocates and waits.  `ws` lists the buffers the
 // call sizes, each with its capacity and what the call needs; `tail` (printf form) names the call that sizes them outside a
 // capture.  The callers ask BEFORE they enqueue anything: a HIP call refused later would invalidate the capture.

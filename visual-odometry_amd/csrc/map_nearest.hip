@@ -361,6 +361,22 @@ MapNearestWs map_nearest_layout(void* base, int n_frames, int n_max, int cap, bo
   return w;
 }
 
+// what voe_map_guided* (map_guided.hip) shares with this call, kernel for kernel: uniqueness over the frames [f0, f0 + gf) of a.w
+// (a memset of the claim words, claim, resolve), and the finish over all frames
+hipError_t launch_nearest_unique(hipStream_t st, const MapNearestArgs& a, int f0, int gf) {
+  const unsigned nb = (unsigned)((a.n_max + NB - 1) / NB);
+  hipError_t e = hipMemsetAsync(a.w.claim, 0xFF, sizeof(unsigned long long) * (size_t)gf * (size_t)a.cap, st);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(nearest_claim_kernel, dim3(nb, (unsigned)gf), dim3(NB), 0, st, a, f0);
+  hipLaunchKernelGGL(nearest_resolve_kernel, dim3(nb, (unsigned)gf), dim3(NB), 0, st, a, f0);
+  return hipSuccess;
+}
+hipError_t launch_nearest_finish(hipStream_t st, const MapNearestArgs& a) {
+  const unsigned nb = (unsigned)((a.n_max + NB - 1) / NB);
+  hipLaunchKernelGGL(nearest_finish_kernel, dim3(nb > 0 ? nb : 1, (unsigned)a.n_frames), dim3(NB), 0, st, a);
+  return hipGetLastError();
+}
+
 hipError_t launch_map_nearest(hipStream_t st, const MapNearestArgs& a) {
   hipError_t e = hipMemsetAsync(a.w.counts, 0, sizeof(int) * (NEAREST_CELLS + 1), st);
   if (e != hipSuccess) return e;
@@ -376,13 +392,10 @@ hipError_t launch_map_nearest(hipStream_t st, const MapNearestArgs& a) {
     if (a.unique && a.w.claim)
       for (int f0 = 0; f0 < a.n_frames; f0 += a.w.group) {
         const int gf = a.n_frames - f0 < a.w.group ? a.n_frames - f0 : a.w.group;
-        if ((e = hipMemsetAsync(a.w.claim, 0xFF, sizeof(unsigned long long) * (size_t)gf * (size_t)a.cap, st)) != hipSuccess) return e;
-        hipLaunchKernelGGL(nearest_claim_kernel, dim3(nb, (unsigned)gf), dim3(NB), 0, st, a, f0);
-        hipLaunchKernelGGL(nearest_resolve_kernel, dim3(nb, (unsigned)gf), dim3(NB), 0, st, a, f0);
+        if ((e = launch_nearest_unique(st, a, f0, gf)) != hipSuccess) return e;
       }
   }
-  hipLaunchKernelGGL(nearest_finish_kernel, dim3(nb > 0 ? nb : 1, (unsigned)a.n_frames), dim3(NB), 0, st, a);
-  return hipGetLastError();
+  return launch_nearest_finish(st, a);
 }
 
 }  // namespace vo

@@ -1138,5 +1138,42 @@ struct MapNearestArgs {
 // memset of the counts (and of *stats) -> grid -> count -> two scan launches -> place -> search -> per group of frames
 // { memset of the claim words, claim, resolve } when unique -> finish
 __attribute__((visibility("hidden"))) hipError_t launch_map_nearest(hipStream_t st, const MapNearestArgs& a);
+// the pieces voe_map_guided* takes from it unchanged: { memset of the claim words, claim, resolve } for the frames [f0, f0 + gf)
+// (a.w.claim holds at least gf * cap words), and the finish (entry, status, distance, canonical rows, the eight counts)
+__attribute__((visibility("hidden"))) hipError_t launch_nearest_unique(hipStream_t st, const MapNearestArgs& a, int f0, int gf);
+__attribute__((visibility("hidden"))) hipError_t launch_nearest_finish(hipStream_t st, const MapNearestArgs& a);
+
+// ---- the nearest entry among those that project near the row's pixel under a pose prior (map_guided.hip, voe_map_guided*) ------
+constexpr int GUIDED_NC = 64;                                           // cells per side of a frame's pixel grid, at most
+constexpr int GUIDED_CELLS = GUIDED_NC * GUIDED_NC;
+// What one group of frames may occupy: per frame a 12-byte record and an 8-byte claim word per entry of the capacity, and the
+// two cell tables.  128 MiB is half the 256 MiB Infinity Cache: the records a group's place kernel writes are what its search
+// reads next, and the other half is left to what the search streams beside them (the appearance rows of the survivors, the
+// frames' rows and pixels), so that a group's index is read from the cache and not from HBM.
+constexpr size_t GUIDED_GROUP_BYTES = (size_t)128 << 20;
+struct GuidedRec { float u, v; int32_t e; };                            // an entry in view of one frame: its pixel and its index
+struct MapGuidedWs {
+  MapNearestWs n;                       // best / d2 / st per row, the claim words and the group (the index fields stay null)
+  void* grids;                          // [group] the frames' grids (GuidedGrid, map_guided.hip): 32 bytes each
+  int* counts;                          // [group][GUIDED_CELLS + 1] records per cell, then the cells' cursors
+  int* starts;                          // [group][GUIDED_CELLS + 1] first record of every cell (relative to the frame's records)
+  GuidedRec* rec;                       // [group][cap] ordered by cell
+  size_t bytes;
+};
+__attribute__((visibility("hidden"))) MapGuidedWs map_guided_layout(void* base, int n_frames, int n_max, int cap, bool unique);
+struct MapGuidedArgs {
+  MapGuidedWs w;
+  MapNearestArgs n;                     // the map's appearances, the frames' rows, radius / ratio / unique, the outputs nearest has
+  const float* pts;                     // the map's points: read only
+  const float* uv; size_t uv_stride;    // floats between frames
+  const float* T16;                     // [n_frames][16] the priors
+  float K[9];
+  float radius_px; int z_near, z_far;
+  float* pix2;                          // or null
+  unsigned long long* stats64;          // n_in_view, n_gated behind the eight counts, or null
+};
+// memset of the statistics -> per group of frames { memset of the counts, box, count, starts, place, search, and when unique
+// { memset of the claim words, claim, resolve } } -> finish
+__attribute__((visibility("hidden"))) hipError_t launch_map_guided(hipStream_t st, const MapGuidedArgs& a);
 
 }  // namespace vo
