@@ -252,6 +252,28 @@ inline const char* guided_status_name(int status) {
   return status >= 0 && status < 6 ? names[status] : "?";
 }
 
+//! voe_map_fuse: duplicate landmarks of the map -- mutual nearest in appearance within a radius in space -- fused (include/vo_hip.h,
+//! FUSE)
+struct FuseOptions {
+  float radius_xyz = 0.04f;          //!< two entries can be one landmark when their points lie within radius_xyz
+  float radius = 0.1f;               //!< ... and their squared appearance distance is below radius^2
+  bool midpoint = true;              //!< the survivor's point becomes the midpoint of the two (false: it keeps its own)
+  bool veto_shared_frame = false;    //!< with frames: a pair that some frame sees together is two landmarks and stays
+  bool dry_run = false;              //!< everything is reported, the map and the rows stay as they are
+};
+struct MapFuse {
+  std::vector<int32_t> partner;      //!< per old entry: its partner, -1 for none
+  std::vector<float> dist2, gap2;    //!< the partner's squared appearance distance and squared distance in space, +inf for none
+  std::vector<int32_t> verdict;      //!< VOE_MAP_FUSE_*
+  std::vector<int32_t> remap;        //!< the new index of the entry, for an ABSORBED entry that of its survivor
+  std::vector<Vector10fVector> rows; //!< with frames: the rows as the fused map finds them (rows on an absorbed entry carry the survivor's bytes)
+  voe_map_fuse_stats stats{};
+};
+inline const char* fuse_verdict_name(int verdict) {
+  static const char* names[] = {"NOT_FINITE", "ALONE", "NOT_MUTUAL", "CONFLICT", "SURVIVOR", "ABSORBED"};
+  return verdict >= 0 && verdict < 6 ? names[verdict] : "?";
+}
+
 //! The rigid pose that goes with a similarity S = [c R | t] of the pose graph (vo/pose_graph.hpp): [R | t / c], on the host in
 //! double.  A map point moved by S_new^-1 S_old of its reference frame (DeviceMap::applyCorrection) projects there, under
 //! rigid_pose(S_new), where it projected before.
@@ -605,6 +627,35 @@ class DeviceMap {
       r.pix2[f].assign(g2.begin() + f * cap, g2.begin() + f * cap + m);
       r.canonical[f].resize(m);
       for (size_t i = 0; i < m; ++i) std::memcpy(r.canonical[f][i].data(), &app[(f * cap + i) * 10], sizeof(float) * 10);
+    }
+    return r;
+  }
+
+  //! duplicate landmarks fused (voe_map_fuse): two entries that are each other's nearest in appearance within o.radius among the
+  //! entries within o.radius_xyz in space are one landmark; the higher index is absorbed, the survivors keep their order.  With
+  //! frames (may be empty: none) the veto can be asked for, and `rows` comes back for the other calls of this class.
+  MapFuse fuse(const FuseOptions& o = FuseOptions(), const std::vector<Vector10fVector>& appearances = std::vector<Vector10fVector>()) {
+    MapFuse r;
+    const size_t F = appearances.size(), S = (size_t)size();
+    size_t cap = 0;
+    for (const auto& a : appearances) cap = a.size() > cap ? a.size() : cap;
+    std::vector<float> app(F * cap * 10 + 10, 0.f);
+    std::vector<int> n(F + 1, 0);
+    for (size_t f = 0; f < F; ++f) {
+      n[f] = (int)appearances[f].size();
+      for (size_t i = 0; i < appearances[f].size(); ++i)
+        for (int k = 0; k < 10; ++k) app[(f * cap + i) * 10 + k] = appearances[f][i][k];
+    }
+    r.partner.assign(S + 1, -1); r.verdict.assign(S + 1, -1); r.remap.assign(S + 1, -1);
+    r.dist2.assign(S + 1, 0.f); r.gap2.assign(S + 1, 0.f);
+    const voe_map_fuse_params p{o.radius_xyz, o.radius, o.midpoint ? 1 : 0, o.veto_shared_frame ? 1 : 0, o.dry_run ? 1 : 0, {0, 0, 0}};
+    check(voe_map_fuse(h_, (int)F, F ? app.data() : nullptr, F ? n.data() : nullptr, (int)cap, &p, r.partner.data(), r.dist2.data(), r.gap2.data(),
+                       r.verdict.data(), r.remap.data(), F && cap ? app.data() : nullptr, &r.stats), "voe_map_fuse");
+    r.partner.resize(S); r.verdict.resize(S); r.remap.resize(S); r.dist2.resize(S); r.gap2.resize(S);
+    r.rows.resize(F);
+    for (size_t f = 0; f < F; ++f) {
+      r.rows[f].resize(appearances[f].size());
+      for (size_t i = 0; i < appearances[f].size(); ++i) std::memcpy(r.rows[f][i].data(), &app[(f * cap + i) * 10], sizeof(float) * 10);
     }
     return r;
   }

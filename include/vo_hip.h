@@ -999,6 +999,82 @@ int vo_map_refine(vo_map *m, int n_frames, const float K[9], const float *uv, co
                   int n_max, const float *T16, const vo_map_refine_params *params, int32_t *status_out,
                   vo_map_refine_stats *stats_out);
 
+/* FUSE.  Duplicate landmarks of the map found and taken out: two entries that are each other's nearest in appearance AND
+ * lie within a radius in space are one landmark entered twice (a revisit under GUIDED whose pixel gate failed and that
+ * voe_map_grow appended; a voe_map_merge(KEEP_DST) of two maps with independently measured descriptors).  The step behind
+ * the loop chain: voe_map_loops -> voe_pose_graph -> voe_map_apply_correction -> FUSE -> vox_map_bundle.  Appearance alone
+ * cannot decide the pairs where appearances repeat; DESIGN.md section 4.25 has the experiment.  (Declared here by the rule
+ * NEAREST states.)  Rules; every output is a function of the data alone:
+ *   1. GATES.  d2(a, b) is NEAREST's rule 1 between two entries: the float32, unfused, left-to-right sum over components
+ *      0..9 of (b_k - a_k)^2; it is bit-symmetric.  g2(a, b) = ((dx * dx + dy * dy) + dz * dz) of the two points in float32,
+ *      unfused.  b != a is a CANDIDATE of a iff d2 < radius * radius and g2 < radius_xyz * radius_xyz (both products
+ *      float32, both tests strict and taken only where they evaluate true).  An entry with a NaN or an infinity in its
+ *      point or in its appearance is NOT_FINITE: it is nobody's candidate and has none.
+ *   2. PARTNER.  The candidate with the smallest d2, exact ties to the lowest entry index (NEAREST's rule 2).
+ *      d_partner_out[a] is it, or -1; d_dist2_out[a] and d_gap2_out[a] hold its d2 and g2, or +inf.
+ *   3. MUTUAL PAIR.  a < b form a PAIR iff partner[a] == b and partner[b] == a.  An entry is in at most one pair.  Chains
+ *      are not followed: a caller that wants them fuses again.
+ *   4. VETO.  With veto_shared_frame != 0 (frames given), a pair is a CONFLICT iff some frame has a live row whose exact
+ *      lookup hits a and one whose exact lookup hits b: a landmark is seen once per frame, two entries seen together are
+ *      two landmarks.  Decided on the ordered observation lists of REFINEMENT (key f * n_max + i, ascending) by a merge
+ *      walk of the two lists.
+ *   5. VERDICT per old entry (d_verdict_out), in this precedence: NOT_FINITE, ALONE (no candidate), NOT_MUTUAL, CONFLICT
+ *      (both ends), SURVIVOR (the lower index of a pair), ABSORBED (the higher).
+ *   6. EFFECT.  The survivor keeps its 40 appearance bytes and its place in the order.  Its point keeps its 12 bytes
+ *      (position == 0) or becomes, per component, float32((double(p_a) + double(p_b)) * 0.5) (position == 1).  ABSORBED
+ *      entries are dropped exactly as voe_map_cull drops: stable compaction through a staging area, header and table
+ *      rebuilt.  d_remap_out[old] is the new index of the entry, for an ABSORBED entry the new index of its survivor; it is
+ *      never -1.  The map afterwards is the map vo_map_update of the survivors, in order, into a cleared map would have built.
+ *   7. ROWS.  With frames and d_app_out given, every live row whose exact lookup BEFORE the fuse hits an ABSORBED entry gets
+ *      the survivor's 40 bytes; every other live row gets its own bytes from d_app; rows behind the live count are left as
+ *      they were.  d_app_out == d_app is allowed.  CONTRACT: vo_map_lookup_batch_dev on d_app_out after the call returns,
+ *      position for position, remap[the lookup of d_app before the call] (-1 stays -1).  Two rows of one frame may then hit
+ *      one entry; every window call counts that as two observations.
+ *   8. dry_run != 0: every per-entry output and *d_stats are written as they would be; the map, its table, its header,
+ *      d_app and d_app_out keep every byte.
+ *   9. CALL STATUS (stats.status).  OK: something was absorbed (or would be under dry_run).  NOTHING_FUSED: every byte of
+ *      the map, its table and its header is left (the compaction and the rebuild still run and return at once behind a
+ *      device flag), and the live rows of d_app_out are those of d_app.
+ *  10. n_frames == 0 with NULL d_app and d_n_rows means "no frames": there is no veto and no row is rewritten.
+ *  11. *d_stats: n_before / n_after the sizes, n_pairs the pairs fused, n_conflicts the pairs vetoed, n_rows_rewritten the
+ *      rows of rule 7 that hit an ABSORBED entry (counted with or without d_app_out), by_verdict the census of rule 5,
+ *      n_gated the ordered pairs (a, b), a != b, neither NOT_FINITE, with g2 < radius_xyz * radius_xyz: an integer, exact
+ *      in any order.
+ * The index -- a uniform 3-D grid over the bounding box of the finite points, cells at least 1.001 radius_xyz wide -- is
+ * built by every call and kept by none, and no result depends on it.  Everything runs on the context's stream, nothing is
+ * read back, the launches are a fixed sequence that depends on (n_frames, n_max, the capacity) alone, no launch waits for
+ * another workgroup, every atomic is an integer one.  The size is read on the device.  Capturable once a call of the same
+ * shape has sized the workspaces; a capture that would have to grow one is refused (VO_ERR_NOT_READY) before anything is
+ * enqueued; a captured call is launched for the capacity (A CALL CAPTURED ON A MAP).  The per-entry outputs have room for
+ * the size the map has when the call runs (voe_map_size_bound bounds it).
+ * Refused (VO_ERR_INVALID_ARG): the lookup's refusals for the frames, when frames are given; a null params or d_stats; a
+ * radius_xyz, then a radius, that is not finite or <= 0; position, veto_shared_frame or dry_run outside 0 / 1; reserved
+ * != 0; veto_shared_frame or d_app_out without frames; an int32 / float32 output off a 4-byte boundary, d_app_out or
+ * d_stats off an 8-byte one; d_app_out overlapping d_app without being d_app. */
+#define VOE_MAP_FUSE_NOT_FINITE 0
+#define VOE_MAP_FUSE_ALONE      1
+#define VOE_MAP_FUSE_NOT_MUTUAL 2
+#define VOE_MAP_FUSE_CONFLICT   3
+#define VOE_MAP_FUSE_SURVIVOR   4
+#define VOE_MAP_FUSE_ABSORBED   5
+#define VOE_MAP_FUSE_OK            0
+#define VOE_MAP_FUSE_NOTHING_FUSED 1
+typedef struct voe_map_fuse_params { float radius_xyz; float radius; int32_t position; int32_t veto_shared_frame; int32_t dry_run; int32_t reserved[3]; } voe_map_fuse_params;   /* 32 bytes */
+typedef struct voe_map_fuse_stats  { int32_t status, n_before, n_after, n_pairs, n_conflicts, n_rows_rewritten; int32_t by_verdict[6]; int64_t n_gated; } voe_map_fuse_stats; /* 56 bytes */
+int voe_map_fuse_batch_dev(vo_map *m, int n_frames, const float *d_app /* or NULL: no frames */, size_t app_stride, int n_max,
+                           const int *d_n_rows /* [n_frames] or NULL */, const voe_map_fuse_params *p,
+                           int32_t *d_partner_out /* [map size] or NULL */, float *d_dist2_out /* [map size] or NULL */,
+                           float *d_gap2_out /* [map size] or NULL */, int32_t *d_verdict_out /* [map size] or NULL */,
+                           int32_t *d_remap_out /* [map size] or NULL */,
+                           float *d_app_out /* frames laid out as d_app (same stride), or NULL; may be d_app itself */,
+                           voe_map_fuse_stats *d_stats);
+/* host arrays in ([n_frames][n_max][10], n_rows [n_frames] or NULL; n_frames == 0 and app NULL: no frames), host arrays out
+ * (per-entry arrays [vo_map_size], any may be NULL; app_out may be app itself; stats_out required); uploads, the device
+ * call, one read-back, the same bytes; waits */
+int voe_map_fuse(vo_map *m, int n_frames, const float *app, const int *n_rows /* or NULL */, int n_max,
+                 const voe_map_fuse_params *p, int32_t *partner_out, float *dist2_out, float *gap2_out, int32_t *verdict_out,
+                 int32_t *remap_out, float *app_out, voe_map_fuse_stats *stats_out);
+
 #ifdef __cplusplus
 }
 #endif

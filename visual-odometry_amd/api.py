@@ -837,6 +837,49 @@ class Map:
         cut = lambda a: [a[f, : n[f]].copy() for f in range(F)]
         return dict(entry=cut(ent), status=cut(sta), dist2=cut(d2), pix2=cut(g2), app=cut(out), stats=st.as_dict())
 
+    # ---- duplicate landmarks fused: mutual nearest in space and appearance (voe_map_fuse*, vo_hip.h: FUSE) ----
+    def fuse_batch_dev(self, n_frames, d_app, app_stride, n_max, d_n, params: "MapFuseParams", d_stats, d_partner_out=None, d_dist2_out=None,
+                       d_gap2_out=None, d_verdict_out=None, d_remap_out=None, d_app_out=None):
+        """voe_map_fuse_batch_dev on device pointers (ints; n_frames == 0 with d_app and d_n None: no frames; every output but
+        d_stats may be None; the stride in rows; d_app_out may be d_app): enqueues and returns.  The per-entry outputs hold
+        size_bound() words; d_stats: 56 bytes (MapFuseStats)."""
+        v = lambda d: C.c_void_p(d) if d else None
+        _chk(self.lib.voe_map_fuse_batch_dev(self.h, C.c_int(n_frames), v(d_app), C.c_size_t(app_stride), C.c_int(n_max), v(d_n), C.byref(params),
+                                             v(d_partner_out), v(d_dist2_out), v(d_gap2_out), v(d_verdict_out), v(d_remap_out), v(d_app_out),
+                                             v(d_stats)))
+
+    def fuse(self, radius_xyz, radius, frames=None, position=1, veto_shared_frame=False, dry_run=False):
+        """voe_map_fuse: two entries that are each other's nearest in appearance within `radius` among the entries within
+        `radius_xyz` in space are one landmark; the higher index is absorbed (position: 0 the survivor keeps its point, 1 the
+        midpoint).  frames ([app] or [(uv, app)], or None): with veto_shared_frame a pair seen together in one frame is left
+        alone, and the rows that hit an absorbed entry come back with the survivor's bytes.  Returns dict(partner, dist2, gap2,
+        verdict, remap: (old size,) arrays; app: the rows per frame, or None; stats dict).  MAP_FUSE_VERDICT names the verdicts,
+        MAP_FUSE_STATUS stats["status"]."""
+        size = max(len(self), 1)
+        partner, verdict, remap = np.full(size, -2, np.int32), np.full(size, -1, np.int32), np.full(size, -2, np.int32)
+        d2, g2 = np.full(size, np.nan, np.float32), np.full(size, np.nan, np.float32)
+        st = MapFuseStats()
+        pr = MapFuseParams(float(radius_xyz), float(radius), int(position), int(bool(veto_shared_frame)), int(bool(dry_run)))
+        if frames is None:
+            _chk(self.lib.voe_map_fuse(self.h, C.c_int(0), None, None, C.c_int(0), C.byref(pr), _ptr(partner), _ptr(d2), _ptr(g2), _ptr(verdict),
+                                       _ptr(remap), None, C.byref(st)))
+            out = None
+        else:
+            apps = [_f32(f[1] if isinstance(f, (tuple, list)) else f, (-1, 10)) for f in frames]
+            F = len(apps)
+            n = np.array([len(a) for a in apps], np.int32)
+            cap = int(n.max()) if F else 0
+            app = np.zeros((max(F, 1), max(cap, 1), 10), np.float32)
+            for f, a in enumerate(apps):
+                app[f, : n[f]] = a
+            rows = app.copy()
+            _chk(self.lib.voe_map_fuse(self.h, C.c_int(F), _ptr(app) if cap else None, _ptr(n), C.c_int(cap), C.byref(pr), _ptr(partner), _ptr(d2),
+                                       _ptr(g2), _ptr(verdict), _ptr(remap), _ptr(rows) if cap else None, C.byref(st)))
+            out = [rows[f, : n[f]].copy() for f in range(F)]
+        k = st.n_before
+        return dict(partner=partner[:k].copy(), dist2=d2[:k].copy(), gap2=g2[:k].copy(), verdict=verdict[:k].copy(), remap=remap[:k].copy(),
+                    app=out, stats=st.as_dict())
+
     # ---- covisibility of frames and the window chosen from it (voe_map_covis*, voe_map_window*, include/vo_map_covis.h) ----
     def words(self):
         """the 32-bit words a bit row needs for this map: enough for size_bound() entries, at least one"""
@@ -1208,6 +1251,26 @@ class MapGuidedStats(C.Structure):
 
 assert C.sizeof(MapGuidedParams) == 32 and C.sizeof(MapGuidedStats) == 48
 MAP_GUIDED_STATUS = MAP_NEAREST_STATUS                                          # VOE_MAP_GUIDED_* = VOE_MAP_NEAREST_*
+
+
+class MapFuseParams(C.Structure):
+    """voe_map_fuse_params (include/vo_hip.h)"""
+    _fields_ = [("radius_xyz", C.c_float), ("radius", C.c_float), ("position", C.c_int32), ("veto_shared_frame", C.c_int32),
+                ("dry_run", C.c_int32), ("reserved", C.c_int32 * 3)]
+
+
+class MapFuseStats(C.Structure):
+    """voe_map_fuse_stats (include/vo_hip.h)"""
+    _fields_ = [("status", C.c_int32), ("n_before", C.c_int32), ("n_after", C.c_int32), ("n_pairs", C.c_int32), ("n_conflicts", C.c_int32),
+                ("n_rows_rewritten", C.c_int32), ("by_verdict", C.c_int32 * 6), ("n_gated", C.c_int64)]
+
+    def as_dict(self):
+        return {k: (list(getattr(self, k)) if k == "by_verdict" else getattr(self, k)) for k, _ in self._fields_}
+
+
+assert C.sizeof(MapFuseParams) == 32 and C.sizeof(MapFuseStats) == 56
+MAP_FUSE_VERDICT = ("NOT_FINITE", "ALONE", "NOT_MUTUAL", "CONFLICT", "SURVIVOR", "ABSORBED")      # VOE_MAP_FUSE_* (the verdicts)
+MAP_FUSE_STATUS = ("OK", "NOTHING_FUSED")                                                        # VOE_MAP_FUSE_* (the call)
 
 
 class MapCovisStats(C.Structure):

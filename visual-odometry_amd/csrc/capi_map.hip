@@ -1,5 +1,5 @@
 // capi_map.hip -- the map's half of the extern "C" boundary (vo_hip.h: vo_map_*; vo_map_adjust.h, vo_map_bundle.h, vo_map_cull.h,
-// vo_map_align.h, vo_map_covis.h, vo_map_grow.h, vo_map_loops.h; voe_map_nearest* and voe_map_guided* of vo_hip.h itself) and the pose graph's (vo_pose_graph.h).  Host-side plumbing only, like capi.hip: no kernel lives here.
+// vo_map_align.h, vo_map_covis.h, vo_map_grow.h, vo_map_loops.h; voe_map_nearest*, voe_map_guided* and voe_map_fuse* of vo_hip.h itself) and the pose graph's (vo_pose_graph.h).  Host-side plumbing only, like capi.hip: no kernel lives here.
 #include <limits.h>
 #include <string.h>
 
@@ -30,6 +30,7 @@ struct vo_map {
   DevBuf grow_ws;               // voe_map_grow*: the open rows, the tracks' private table, verdicts, the staging area (the lists live in ref_ws)
   DevBuf loops_ws;              // voe_map_loops*: the lookup's arrays, keys, reference frames, bit rows, candidates, slots, the gathered problems
   DevBuf nearest_ws;            // voe_map_nearest*: the call's index of the map (grid, start table, records), best / distance / status per row, the claim words
+  DevBuf fuse_ws;               // voe_map_fuse*: the call's 3-D grid of the map (cell tables, records), finite flags, partner / verdict / remap (compaction: cull_ws; lists: ref_ws)
   DevBuf guided_ws;             // voe_map_guided*: per frame of a group the grid, the cell tables and the records; best / distance / status per row, the claim words
   MapLoopsWs loops_last{};      // ... as the last call laid it out (voe_map_loops_problems_dev); bytes == 0: no call yet
 };
@@ -128,7 +129,7 @@ int vo_map_destroy(vo_map* m) {
   map_free_arrays(m->d);
   if (m->d.hdr) (void)hipFree(m->d.hdr);
   if (m->hist) (void)hipFree(m->hist);
-  m->scratch.release(); m->up_xyz.release(); m->up_app.release(); m->look_ws.release(); m->loc_ws.release(); m->ref_ws.release(); m->pose_ws.release(); m->bundle_ws.release(); m->cull_ws.release(); m->align_ws.release(); m->merge_ws.release(); m->covis_ws.release(); m->window_ws.release(); m->grow_ws.release(); m->loops_ws.release(); m->nearest_ws.release(); m->guided_ws.release();
+  m->scratch.release(); m->up_xyz.release(); m->up_app.release(); m->look_ws.release(); m->loc_ws.release(); m->ref_ws.release(); m->pose_ws.release(); m->bundle_ws.release(); m->cull_ws.release(); m->align_ws.release(); m->merge_ws.release(); m->covis_ws.release(); m->window_ws.release(); m->grow_ws.release(); m->loops_ws.release(); m->nearest_ws.release(); m->guided_ws.release(); m->fuse_ws.release();
   if (m->solver) (void)vo_picp_destroy(m->solver);
   delete m;
   return VO_OK;
@@ -994,6 +995,97 @@ int voe_map_cull(vo_map* m, int n_frames, const float K[9], const float* uv, con
   }
   VO_HIP_CHECK(hipStreamSynchronize(c->stream));
   m->bd.on_host_cull(stats_out->n_kept, params->dry_run != 0);
+  return VO_OK;
+}
+
+// ---- duplicate landmarks fused: mutual nearest in space and appearance (map_fuse.hip; include/vo_hip.h, FUSE) ----------------
+static_assert(sizeof(voe_map_fuse_params) == 32 && sizeof(voe_map_fuse_stats) == 56, "the finishing kernel writes twelve 4-byte words and one 8-byte one");
+
+int voe_map_fuse_batch_dev(vo_map* m, int n_frames, const float* d_app, size_t app_stride, int n_max, const int* d_n,
+                           const voe_map_fuse_params* p, int32_t* d_partner_out, float* d_dist2_out, float* d_gap2_out,
+                           int32_t* d_verdict_out, int32_t* d_remap_out, float* d_app_out, voe_map_fuse_stats* d_stats) {
+  const char* fn = "voe_map_fuse_batch_dev";
+  const MapFrames f{n_frames, nullptr, nullptr, 0, d_app, app_stride, n_max, d_n};
+  if (int r = map_fuse_check(fn, f, p, MapFusePtrs{d_partner_out, d_dist2_out, d_gap2_out, d_verdict_out, d_remap_out, d_app_out, d_stats})) return r;
+  VO_MAP_LIVE(m);
+  vo_ctx* c = m->ctx;
+  const bool frames = map_fuse_has_frames(f);
+  // allocated for the capacity, launched for the launch bound, the size read on the device: as voe_map_nearest_batch_dev
+  const int bound = map_launch_bound(m);
+  const size_t need = map_fuse_layout(nullptr, m->bd.alloc_bound()).bytes, need_cull = map_cull_layout(nullptr, m->bd.alloc_bound()).bytes;
+  if (int r = capture_growth_check(c->capturing, fn, {{m->fuse_ws.cap, need}, {m->cull_ws.cap, need_cull}}, "%d frames of n_max %d on this map", n_frames, n_max))
+    return r;                                               // (before the lookup is enqueued)
+  MapRefineWs rw{};
+  if (frames) {
+    if (int r = refine_prepare(fn, m, f, &rw)) return r;    // the one lookup of the call: the entry of every row BEFORE the fuse
+  } else if (int r = set_device(c)) return r;
+  VO_HIP_CHECK(m->fuse_ws.ensure(need, c->stream));
+  VO_HIP_CHECK(m->cull_ws.ensure(need_cull, c->stream));
+  // the compaction is the cull's (launch_map_cull_compact): its workspace, its view of the map, the keep flags in its `rank`
+  MapCullArgs k{};
+  k.w = map_cull_layout(m->cull_ws.p, bound);
+  fill_map(k.v, m);
+  k.app = m->d.app; k.dry_run = p->dry_run != 0;
+  MapFuseArgs a{};
+  a.w = map_fuse_layout(m->fuse_ws.p, m->bd.alloc_bound());
+  a.l = rw;
+  a.pts = m->d.pts; a.app = m->d.app; a.hdr = m->d.hdr; a.cap = m->d.cap; a.bound = bound;
+  a.frames = frames; a.q_app = d_app; a.q_stride = 10 * app_stride; a.n_frames = n_frames; a.n_max = n_max; a.d_n = d_n;
+  a.radius_xyz = p->radius_xyz; a.radius = p->radius; a.position = p->position; a.veto = p->veto_shared_frame; a.dry_run = p->dry_run;
+  a.partner = d_partner_out ? d_partner_out : a.w.partner;
+  a.verdict = d_verdict_out ? d_verdict_out : a.w.verdict;
+  a.remap = d_remap_out ? d_remap_out : a.w.remap;
+  a.dist2 = d_dist2_out; a.gap2 = d_gap2_out; a.app_out = d_app_out; a.cull_ctl = k.w.ctl; a.stats = d_stats;
+  k.verdict = a.verdict; k.remap = a.remap;
+  VO_HIP_CHECK(launch_map_fuse(c->stream, a, k.w.rank));
+  VO_HIP_CHECK(launch_map_cull_compact(c->stream, k));
+  VO_HIP_CHECK(launch_map_rehash(c->stream, m->d, bound, k.w.ctl + 2));
+  VO_HIP_CHECK(launch_map_fuse_finish(c->stream, a));
+  return VO_OK;
+}
+
+int voe_map_fuse(vo_map* m, int n_frames, const float* app, const int* n_rows, int n_max, const voe_map_fuse_params* p, int32_t* partner_out,
+                 float* dist2_out, float* gap2_out, int32_t* verdict_out, int32_t* remap_out, float* app_out, voe_map_fuse_stats* stats_out) {
+  const char* fn = "voe_map_fuse";
+  if (!p || !stats_out) return vo_fail(VO_ERR_INVALID_ARG, "%s: null params or stats_out", fn);
+  VO_MAP_LIVE(m);
+  vo_ctx* c = m->ctx;
+  VO_NOT_CAPTURING(c);
+  const bool frames = n_frames != 0 || app || n_rows;
+  MapFrames f{0, nullptr, nullptr, 0, nullptr, 0, n_max, nullptr};
+  int size = 0;
+  if (frames) {
+    if (int r = upload_window(fn, m, MapFrames{n_frames, nullptr, nullptr, 0, app, 0, n_max, n_rows}, nullptr, nullptr, &size, &f)) return r;
+  } else {
+    if (app_out) return vo_fail(VO_ERR_INVALID_ARG, "%s: app_out without frames", fn);
+    if (int r = vo_map_size(m, &size)) return r;
+  }
+  const size_t S = (size_t)(size > 0 ? size : 1), rows = frames ? (size_t)n_frames * (size_t)n_max : 0;
+  VO_HIP_CHECK(c->out[0].ensure(sizeof(int32_t) * 5 * S, c->stream));
+  VO_HIP_CHECK(c->out[2].ensure(sizeof(voe_map_fuse_stats) + 8, c->stream));
+  int32_t* d_partner = c->out[0].as<int32_t>();
+  float* d_dist2 = reinterpret_cast<float*>(d_partner + S);
+  float* d_gap2 = d_dist2 + S;
+  int32_t* d_verdict = d_partner + 3 * S;
+  int32_t* d_remap = d_partner + 4 * S;
+  // the rows are rewritten in place over the staged rows (d_app_out == d_app)
+  if (int r = voe_map_fuse_batch_dev(m, n_frames, f.d_app, f.app_stride, n_max, f.d_n, p, partner_out ? d_partner : nullptr,
+                                     dist2_out ? d_dist2 : nullptr, gap2_out ? d_gap2 : nullptr, verdict_out ? d_verdict : nullptr,
+                                     remap_out ? d_remap : nullptr, app_out && rows > 0 ? c->in[1].as<float>() : nullptr,
+                                     c->out[2].as<voe_map_fuse_stats>()))
+    return r;
+  VO_HIP_CHECK(hipMemcpyAsync(stats_out, c->out[2].p, sizeof(voe_map_fuse_stats), hipMemcpyDeviceToHost, c->stream));
+  if (size > 0) {
+    const size_t b = sizeof(int32_t) * (size_t)size;
+    if (partner_out) VO_HIP_CHECK(hipMemcpyAsync(partner_out, d_partner, b, hipMemcpyDeviceToHost, c->stream));
+    if (dist2_out) VO_HIP_CHECK(hipMemcpyAsync(dist2_out, d_dist2, b, hipMemcpyDeviceToHost, c->stream));
+    if (gap2_out) VO_HIP_CHECK(hipMemcpyAsync(gap2_out, d_gap2, b, hipMemcpyDeviceToHost, c->stream));
+    if (verdict_out) VO_HIP_CHECK(hipMemcpyAsync(verdict_out, d_verdict, b, hipMemcpyDeviceToHost, c->stream));
+    if (remap_out) VO_HIP_CHECK(hipMemcpyAsync(remap_out, d_remap, b, hipMemcpyDeviceToHost, c->stream));
+  }
+  if (app_out && rows > 0) VO_HIP_CHECK(hipMemcpyAsync(app_out, c->in[1].p, sizeof(float) * 10 * rows, hipMemcpyDeviceToHost, c->stream));
+  VO_HIP_CHECK(hipStreamSynchronize(c->stream));
+  m->bd.on_host_cull(stats_out->n_after, p->dry_run != 0);
   return VO_OK;
 }
 

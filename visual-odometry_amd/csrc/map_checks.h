@@ -264,6 +264,52 @@ static inline int map_guided_check(const char* fn, const MapFrames& f, const voe
   return VO_OK;
 }
 
+// voe_map_fuse*: what the call refuses (include/vo_hip.h, FUSE), in the order they fire.  Frames are GIVEN when n_frames != 0 or
+// d_app or d_n is not null; 1 - 6 are then the lookup's refusals for them as map_nearest_check states them:
+//   1. n_frames outside 1 .. 65535      2. negative n_max      3. null appearances with n_max > 0
+//   4. appearance rows off an 8-byte boundary      5. app_stride < n_max (more than one frame)
+//   6. app_stride >= (2^31 - 1) / 10 or more than 2^30 rows
+//   7. a null params or d_stats      8. radius_xyz, then radius, not finite or <= 0
+//   9. position, then veto_shared_frame, then dry_run outside 0 / 1      10. reserved != 0
+//   11. veto_shared_frame, then d_app_out, without frames
+//   12. an int32 / float32 output off a 4-byte boundary, d_app_out or d_stats off an 8-byte one
+//   13. d_app_out overlapping d_app without being d_app
+struct MapFusePtrs {
+  const void *partner, *dist2, *gap2, *verdict, *remap, *app_out, *stats;
+};
+static inline bool map_fuse_has_frames(const MapFrames& f) { return f.n_frames != 0 || f.d_app || f.d_n; }
+static inline int map_fuse_check(const char* fn, const MapFrames& f, const voe_map_fuse_params* p, const MapFusePtrs& d) {
+  const bool frames = map_fuse_has_frames(f);
+  if (frames) {
+    if (f.n_frames < 1 || f.n_frames > 65535) return vo_fail(VO_ERR_INVALID_ARG, "%s: n_frames %d outside 1 .. 65535 (the frame is a grid dimension)", fn, f.n_frames);
+    if (f.n_max < 0) return vo_fail(VO_ERR_INVALID_ARG, "%s: negative row count", fn);
+    if (f.n_max > 0 && !f.d_app) return vo_fail(VO_ERR_INVALID_ARG, "%s: null argument", fn);
+    if (!aligned8(f.d_app)) return vo_fail(VO_ERR_INVALID_ARG, "%s: device appearance rows must be 8-byte aligned", fn);
+    if (f.n_frames > 1 && f.app_stride < (size_t)f.n_max) return vo_fail(VO_ERR_INVALID_ARG, "%s: app_stride %zu is smaller than n_max %d", fn, f.app_stride, f.n_max);
+    if (f.app_stride >= 0x7fffffff / 10 || (long long)f.n_max * f.n_frames > (1ll << 30))
+      return vo_fail(VO_ERR_INVALID_ARG, "%s: more than 2^30 rows in one call", fn);
+  }
+  if (!p || !d.stats) return vo_fail(VO_ERR_INVALID_ARG, "%s: null params or d_stats", fn);
+  if (!(p->radius_xyz > 0.f && p->radius_xyz <= 3.402823466e38f)) return vo_fail(VO_ERR_INVALID_ARG, "%s: radius_xyz must be finite and positive", fn);
+  if (!(p->radius > 0.f && p->radius <= 3.402823466e38f)) return vo_fail(VO_ERR_INVALID_ARG, "%s: radius must be finite and positive", fn);
+  if (p->position != 0 && p->position != 1) return vo_fail(VO_ERR_INVALID_ARG, "%s: position must be 0 or 1", fn);
+  if (p->veto_shared_frame != 0 && p->veto_shared_frame != 1) return vo_fail(VO_ERR_INVALID_ARG, "%s: veto_shared_frame must be 0 or 1", fn);
+  if (p->dry_run != 0 && p->dry_run != 1) return vo_fail(VO_ERR_INVALID_ARG, "%s: dry_run must be 0 or 1", fn);
+  if (p->reserved[0] != 0 || p->reserved[1] != 0 || p->reserved[2] != 0) return vo_fail(VO_ERR_INVALID_ARG, "%s: reserved must be 0", fn);
+  if (!frames && p->veto_shared_frame != 0) return vo_fail(VO_ERR_INVALID_ARG, "%s: veto_shared_frame without frames", fn);
+  if (!frames && d.app_out) return vo_fail(VO_ERR_INVALID_ARG, "%s: d_app_out without frames", fn);
+  if ((reinterpret_cast<uintptr_t>(d.partner) | reinterpret_cast<uintptr_t>(d.dist2) | reinterpret_cast<uintptr_t>(d.gap2) |
+       reinterpret_cast<uintptr_t>(d.verdict) | reinterpret_cast<uintptr_t>(d.remap)) & 3u)
+    return vo_fail(VO_ERR_INVALID_ARG, "%s: int32 and float32 arrays must be 4-byte aligned", fn);
+  if (!aligned8(d.app_out, d.stats)) return vo_fail(VO_ERR_INVALID_ARG, "%s: d_app_out and d_stats must be 8-byte aligned", fn);
+  if (d.app_out && d.app_out != (const void*)f.d_app && f.n_max > 0) {
+    const uintptr_t span = sizeof(float) * 10 * ((uintptr_t)(f.n_frames - 1) * f.app_stride + (uintptr_t)f.n_max);
+    const uintptr_t a = reinterpret_cast<uintptr_t>(f.d_app), b = reinterpret_cast<uintptr_t>(d.app_out);
+    if (a < b + span && b < a + span) return vo_fail(VO_ERR_INVALID_ARG, "%s: d_app_out overlaps d_app without being d_app", fn);
+  }
+  return VO_OK;
+}
+
 // A workspace that would have to grow inside a graph capture: growing frees, allocates and waits.  `ws` lists the buffers the
 // call sizes, each with its capacity and what the call needs; `tail` (printf form) names the call that sizes them outside a
 // capture.  The callers ask BEFORE they enqueue anything: a HIP call refused later would invalidate the capture.

@@ -21,6 +21,7 @@
 //                          place in one launch would let one workgroup write r(j') = j while another still reads j
 //   cull_header_kernel     one thread: size, base and rows of the last update
 //   (launch_map_rehash, guarded by the control word, enqueued by the caller)
+// count .. header are also launch_map_cull_compact, which voe_map_fuse* enqueues behind keep flags of its own (map_fuse.hip)
 //   cull_stats_kernel      one workgroup: an integer tally of the verdicts
 // The count of launches is fixed; where nothing is dropped, or under dry_run, scatter, copy, header and rehash return at once.
 #include "vo_internal.h"
@@ -175,9 +176,14 @@ MapCullWs map_cull_layout(void* base, int bound) {
 hipError_t launch_map_cull(hipStream_t st, const MapCullArgs& a, int n_cu) {
   const hipError_t e = launch_map_refine_lists(st, a.l, a.v.n_frames, a.v.n_max, a.v.bound);
   if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(cull_score_kernel, dim3(landmark_grid(a.v.bound, n_cu)), dim3(CB), 0, st, a);
+  return launch_map_cull_compact(st, a);
+}
+
+// the compaction behind the keep flags in w.rank: what voe_map_fuse* shares with the cull, kernel for kernel
+hipError_t launch_map_cull_compact(hipStream_t st, const MapCullArgs& a) {
   const int B = a.v.bound > 0 ? a.v.bound : 1;
   const int nb = (B + CB - 1) / CB;
-  hipLaunchKernelGGL(cull_score_kernel, dim3(landmark_grid(a.v.bound, n_cu)), dim3(CB), 0, st, a);
   hipLaunchKernelGGL(cull_count_kernel, dim3(nb), dim3(CB), 0, st, a);
   hipLaunchKernelGGL(cull_scan_kernel, dim3(1), dim3(CSTAT), 0, st, a, nb);
   hipLaunchKernelGGL(cull_scatter_kernel, dim3(nb), dim3(CB), 0, st, a);

@@ -773,6 +773,9 @@ struct MapCullArgs {
 // then enqueues launch_map_rehash guarded by w.ctl + 2, and launch_map_cull_stats
 hipError_t launch_map_cull(hipStream_t st, const MapCullArgs& a, int n_cu);
 hipError_t launch_map_cull_stats(hipStream_t st, const MapCullArgs& a);
+// the compaction alone, for a caller that has written the keep flags into w.rank itself (voe_map_fuse*): count, scan, scatter into
+// the staging area, copy back, header.  Reads a.v (pts, hdr, cap, bound), a.w, a.app, a.dry_run; writes a.remap and w.ctl.
+__attribute__((visibility("hidden"))) hipError_t launch_map_cull_compact(hipStream_t st, const MapCullArgs& a);
 
 // ---- landmarks added from the frames' unmapped tracks (map_grow.hip, voe_map_grow*; include/vo_map_grow.h holds the rules) ----
 // rows = n_frames * n_max query positions (R below: rows, at least 1); a track is numbered below R
@@ -1175,5 +1178,47 @@ struct MapGuidedArgs {
 // memset of the statistics -> per group of frames { memset of the counts, box, count, starts, place, search, and when unique
 // { memset of the claim words, claim, resolve } } -> finish
 __attribute__((visibility("hidden"))) hipError_t launch_map_guided(hipStream_t st, const MapGuidedArgs& a);
+
+// ---- duplicate landmarks fused: mutual nearest in space and appearance (map_fuse.hip, voe_map_fuse*; vo_hip.h holds the rules) ----
+constexpr int FUSE_NC = 128;                                            // cells per axis of the call's 3-D grid, at most
+constexpr int FUSE_CELLS = FUSE_NC * FUSE_NC * FUSE_NC;
+constexpr int FUSE_SCAN = 2048;                                         // cells per block of the scan
+constexpr int FUSE_SCAN_BLOCKS = (FUSE_CELLS + 1 + FUSE_SCAN - 1) / FUSE_SCAN;
+// the words the kernels add into, zeroed with the cell counts: [0..5] by_verdict [6] pairs [7] conflicts [8] rows rewritten
+// [10..11] n_gated (64 bits) [12..14] the box's upper corner as order-preserving keys
+constexpr int FUSE_ACC = 16;
+// the workspace of one call: `cap` the map's capacity (allocated for it: "one eager call, then capture")
+struct MapFuseWs {
+  void* grid;                           // the grid of this call (FuseGrid, map_fuse.hip): 64 bytes
+  unsigned* box_lo;                     // [4] the box's lower corner as order-preserving keys (memset to 0xFF)
+  int* acc;                             // [FUSE_ACC], directly in front of counts: one memset clears both
+  int* counts;                          // [FUSE_CELLS + 1] records per cell, then the cells' cursors
+  int* starts;                          // [FUSE_CELLS + 1] first record of every cell; [n_cells] = records in all
+  int* bsum;                            // [FUSE_SCAN_BLOCKS] the counts' sums per block of cells
+  float4* rec;                          // [cap] {x, y, z, entry}, ordered by cell: the finite entries
+  int32_t* fin;                         // [cap] 1: the entry is finite
+  int32_t *partner, *verdict, *remap;   // [cap] (the caller's arrays take their places when given)
+  size_t bytes;
+};
+__attribute__((visibility("hidden"))) MapFuseWs map_fuse_layout(void* base, int cap);
+struct MapFuseArgs {
+  MapFuseWs w;
+  MapRefineWs l;                        // with frames: the lookup's entries and the ordered lists (map_refine_layout)
+  float* pts; const float* app; const int* hdr; int cap, bound;      // the map (a survivor's point is written with position == 1)
+  int frames;                           // 1: frames are given
+  const float* q_app; size_t q_stride;  // floats between frames
+  int n_frames, n_max; const int* d_n;
+  float radius_xyz, radius; int position, veto, dry_run;
+  int32_t *partner, *verdict, *remap;   // the caller's or the workspace's
+  float *dist2, *gap2;                  // or null
+  float* app_out;                       // or null
+  const int* cull_ctl;                  // MapCullWs::ctl of the compaction: [0] size before [1] survivors
+  void* stats;                          // voe_map_fuse_stats
+};
+// memsets -> box -> grid -> count -> two scan launches -> place -> search -> (with frames: the observation lists) -> verdict ->
+// rows.  The caller then enqueues launch_map_cull_compact on w.rank = the keep flags the verdict kernel wrote into `rank`,
+// launch_map_rehash behind the compaction's flag, and launch_map_fuse_finish (the absorbed entries' remap, the statistics).
+__attribute__((visibility("hidden"))) hipError_t launch_map_fuse(hipStream_t st, const MapFuseArgs& a, int* rank);
+__attribute__((visibility("hidden"))) hipError_t launch_map_fuse_finish(hipStream_t st, const MapFuseArgs& a);
 
 }  // namespace vo
