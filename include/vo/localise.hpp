@@ -274,6 +274,29 @@ inline const char* fuse_verdict_name(int verdict) {
   return verdict >= 0 && verdict < 6 ? names[verdict] : "?";
 }
 
+//! voe_map_keyframes: which frames to keep at all -- redundant frames dropped one at a time, the most redundant first
+//! (include/vo_hip.h, KEYFRAMES)
+struct KeyframesOptions {
+  int min_observers = 3;             //!< other kept frames that must see an entry for it to count as redundant in a frame
+  int share_permille = 900;          //!< a frame is a candidate when that many of 1000 of its entries are redundant
+  int min_seen = 1;                  //!< a frame that sees fewer entries is EMPTY and stays
+  int max_gap = 0;                   //!< > 0: no run of more than max_gap missing frames in the chain
+  int max_dropped = VOE_MAP_KEYFRAMES_MAX_STEPS;      //!< 0: the analysis alone
+};
+struct MapKeyframes {
+  std::vector<int32_t> verdict;      //!< VOE_MAP_KEYFRAMES_* per frame
+  std::vector<int> n_rows;           //!< the frame's live rows, 0 for DROPPED and GONE: what refine / bundle / adjust / cull / grow / loops take
+  std::vector<uint8_t> keep;         //!< 0 for DROPPED and GONE, 1 otherwise: the flags of the next call are keep ? flag : GONE
+  std::vector<int32_t> step;         //!< the step at which the frame was dropped, or -1
+  std::vector<int32_t> order;        //!< the dropped frames in drop order, then -1
+  std::vector<int32_t> seen, red;    //!< entries seen / of them redundant: at its own step for a dropped frame, at the end otherwise
+  voe_map_keyframes_stats stats{};
+};
+inline const char* keyframes_verdict_name(int verdict) {
+  static const char* names[] = {"LEFT", "PROTECTED", "GONE", "DROPPED", "EMPTY", "NEEDED", "GAP"};
+  return verdict >= 0 && verdict < 7 ? names[verdict] : "?";
+}
+
 //! The rigid pose that goes with a similarity S = [c R | t] of the pose graph (vo/pose_graph.hpp): [R | t / c], on the host in
 //! double.  A map point moved by S_new^-1 S_old of its reference frame (DeviceMap::applyCorrection) projects there, under
 //! rigid_pose(S_new), where it projected before.
@@ -739,6 +762,27 @@ class DeviceMap {
                          w.n_rows.data(), w.fixed.data(), w.order.data(), w.landmarks.data(), &w.stats), "voe_map_window");
     w.role.resize(F); w.n_rows.resize(F); w.fixed.resize(F); w.order.resize(F);
     return w;
+  }
+
+  //! the frames to keep (voe_map_keyframes) from the bit rows of covisibility().  *flags: VOE_MAP_KEYFRAMES_FREE / _PROTECTED /
+  //! _GONE per frame (default: all free); *n_rows: the frames' live rows.  The result's n_rows goes to refine / bundle / adjust /
+  //! cull / grow / loops over the SAME frames: a dropped frame has no observation there.
+  MapKeyframes keyframes(const Covisibility& cov, const KeyframesOptions& opt = KeyframesOptions(), const std::vector<uint8_t>* flags = nullptr,
+                         const std::vector<int>* n_rows = nullptr) const {
+    const size_t F = cov.n_frames;
+    if (n_rows && n_rows->size() != F) throw Error(VO_ERR_INVALID_ARG, "DeviceMap::keyframes: one row count per frame");
+    if (flags && flags->size() != F) throw Error(VO_ERR_INVALID_ARG, "DeviceMap::keyframes: one flag per frame");
+    MapKeyframes k;
+    const size_t n = F ? F : 1;
+    k.verdict.assign(n, 0); k.n_rows.assign(n, 0); k.keep.assign(n, 1); k.step.assign(n, -1); k.order.assign(n, -1); k.seen.assign(n, 0); k.red.assign(n, 0);
+    int cap = 0;
+    if (n_rows) for (int v : *n_rows) cap = v > cap ? v : cap;
+    const voe_map_keyframes_params prm{opt.min_observers, opt.share_permille, opt.min_seen, opt.max_gap, opt.max_dropped, {0, 0, 0}};
+    check(voe_map_keyframes(h_, (int)F, (int)cov.n_words, cov.bits.data(), n_rows ? n_rows->data() : nullptr, cap, flags ? flags->data() : nullptr,
+                            &prm, k.verdict.data(), k.n_rows.data(), k.keep.data(), k.step.data(), k.order.data(), k.seen.data(), k.red.data(),
+                            &k.stats), "voe_map_keyframes");
+    k.verdict.resize(F); k.n_rows.resize(F); k.keep.resize(F); k.step.resize(F); k.order.resize(F); k.seen.resize(F); k.red.resize(F);
+    return k;
   }
 
   //! the map's points and appearances in entry order

@@ -1075,6 +1075,71 @@ int voe_map_fuse(vo_map *m, int n_frames, const float *app, const int *n_rows /*
                  const voe_map_fuse_params *p, int32_t *partner_out, float *dist2_out, float *gap2_out, int32_t *verdict_out,
                  int32_t *remap_out, float *app_out, voe_map_fuse_stats *stats_out);
 
+/* KEYFRAMES.  Which frames to keep at all: a frame is redundant when enough of the landmarks it sees are also seen by enough
+ * other kept frames (ORB-SLAM's keyframe culling), and redundant frames are dropped one at a time, the most redundant first,
+ * because each drop changes the counts of the others.  Like voe_map_window_dev (vo_map_covis.h) the call reads the bit rows
+ * ALONE -- d_bits [n_frames][n_words] as voe_map_covis_batch_dev writes them; n_frames, n_words, d_n_rows and n_max mean
+ * what they mean there -- and the map is there for the stream and the workspaces: it is neither read nor written.  Every
+ * output is an integer and EXACT; no floating point number is formed.  RULES:
+ *   1. FLAGS.  d_flags [n_frames] bytes (or NULL: all FREE): VOE_MAP_KEYFRAMES_FREE, _PROTECTED (never dropped) or _GONE --
+ *      dropped by an earlier call: its row is ignored, it observes nothing, and it counts as dropped in rule 4.  So a caller
+ *      can run the call again on old bit rows.  The host form refuses a byte above 2; the device form, which cannot, treats
+ *      such a frame as PROTECTED.
+ *   2. QUANTITIES.  seen[f]: the population count of row f; it never changes.  cnt[e]: the frames that are neither GONE nor
+ *      dropped so far and whose row has bit e.  red[f]: the bits e of row f with cnt[e] - 1 >= min_observers.
+ *   3. CANDIDATE.  f is a candidate iff it is FREE and not dropped, seen[f] >= min_seen,
+ *      1000 red[f] >= share_permille seen[f] (int64), and rule 4 holds.
+ *   4. GAP (max_gap > 0 only).  With a the nearest frame below f that is neither GONE nor dropped (-1 if none) and b the
+ *      nearest above (n_frames if none): b - a - 1 <= max_gap.  The frames are in time order: this bounds the run of missing
+ *      frames in the odometry chain.
+ *   5. LOOP.  While fewer than max_dropped frames are dropped and a candidate exists, the BEST candidate is dropped: the
+ *      highest share red / seen, compared by cross-multiplication in int64; ties go to the lowest frame.  Then cnt follows.
+ *      max_dropped == 0 is the analysis alone: nothing is dropped and every verdict is reported.
+ *   6. MONOTONE.  red[f] only falls and runs of missing frames only grow: a frame that has once failed the share test or
+ *      the gap test is never a candidate again.  The kernels stop reading the rows of such frames during the loop.
+ *   7. VERDICT, d_verdict_out [n_frames], the first that holds at the final state: GONE; DROPPED; PROTECTED; EMPTY --
+ *      seen < min_seen; NEEDED -- the share test fails; GAP -- the share test passes and rule 4 blocks; LEFT -- still a
+ *      candidate, because max_dropped was reached.  The verdict of a PROTECTED or GONE frame is the number of its flag.
+ *   8. OUTPUTS.  d_n_rows_out [n_frames]: the frame's live rows (d_n_rows[f], or n_max), 0 for DROPPED and GONE frames --
+ *      what vox_map_bundle_batch_dev, vo_map_adjust_batch_dev, vo_map_refine_batch_dev, voe_map_cull_batch_dev,
+ *      voe_map_grow_batch_dev and voe_map_loops_batch_dev take over the SAME frame arrays with no gather: a frame with 0 live
+ *      rows has no observation.  d_keep_out [n_frames] bytes: 0 for DROPPED and GONE, 1 otherwise.  d_step_out: the step at
+ *      which the frame was dropped, or -1.  d_order_out (or NULL): the dropped frames in drop order, then -1.  d_seen_out,
+ *      d_red_out: for a dropped frame seen and red at its own step, for every other frame at the final state, for a GONE
+ *      frame 0.
+ *   9. *d_stats: n_frames; n_kept: neither DROPPED nor GONE; n_dropped; n_gone; n_protected; n_needed; n_blocked: GAP and
+ *      LEFT; n_empty.
+ * Everything is enqueued on the context's stream and nothing is read back.  The launches are a fixed sequence that depends
+ * on (n_frames, n_words, max_dropped) alone -- two per step; the steps behind the last drop return at once on a device flag --,
+ * no launch waits for another workgroup, the only atomic is an integer atomicAdd.  Capturable once a call of the same shape
+ * (n_frames, n_words) on this map has sized the workspace; a capture that would have to grow it is refused
+ * (VO_ERR_NOT_READY) before anything is enqueued.  params is a host value, read when the call is made.
+ * Refused (VO_ERR_INVALID_ARG): n_frames outside 1 .. VOE_MAP_COVIS_MAX_FRAMES; n_words < 1 or above 2^26 (a row's count
+ * fits an int32); n_max < 0; a null d_bits, params, d_stats or output other than d_order_out; a d_stats that is not 8-byte
+ * aligned; min_observers < 1; share_permille outside 0 .. 1000; min_seen < 1; max_gap < 0; max_dropped outside
+ * 0 .. VOE_MAP_KEYFRAMES_MAX_STEPS; reserved != 0; in the host form a flag byte above 2. */
+#define VOE_MAP_KEYFRAMES_FREE      0     /* flags */
+#define VOE_MAP_KEYFRAMES_PROTECTED 1     /* flag and verdict */
+#define VOE_MAP_KEYFRAMES_GONE      2     /* flag and verdict */
+#define VOE_MAP_KEYFRAMES_LEFT      0     /* verdicts */
+#define VOE_MAP_KEYFRAMES_DROPPED   3
+#define VOE_MAP_KEYFRAMES_EMPTY     4
+#define VOE_MAP_KEYFRAMES_NEEDED    5
+#define VOE_MAP_KEYFRAMES_GAP       6
+#define VOE_MAP_KEYFRAMES_MAX_STEPS 1024  /* two launches per step: a choice, not a measured limit */
+typedef struct voe_map_keyframes_params { int32_t min_observers, share_permille, min_seen, max_gap, max_dropped; int32_t reserved[3]; } voe_map_keyframes_params;   /* 32 bytes */
+typedef struct voe_map_keyframes_stats  { int32_t n_frames, n_kept, n_dropped, n_gone, n_protected, n_needed, n_blocked, n_empty; } voe_map_keyframes_stats;   /* 32 bytes */
+int voe_map_keyframes_dev(vo_map *m, int n_frames, int n_words, const uint32_t *d_bits, const int *d_n_rows /* [n_frames] or NULL */,
+                          int n_max, const uint8_t *d_flags /* [n_frames] or NULL */, const voe_map_keyframes_params *params,
+                          int32_t *d_verdict_out /* [n_frames] */, int *d_n_rows_out /* [n_frames] */, uint8_t *d_keep_out /* [n_frames] */,
+                          int32_t *d_step_out /* [n_frames] */, int32_t *d_order_out /* [n_frames] or NULL */,
+                          int32_t *d_seen_out /* [n_frames] */, int32_t *d_red_out /* [n_frames] */,
+                          voe_map_keyframes_stats *d_stats /* 8-byte aligned */);
+/* host arrays (n_rows, flags and order_out may be NULL).  Uploads, the device call, one read-back; the same bytes. */
+int voe_map_keyframes(vo_map *m, int n_frames, int n_words, const uint32_t *bits, const int *n_rows, int n_max, const uint8_t *flags,
+                      const voe_map_keyframes_params *params, int32_t *verdict_out, int *n_rows_out, uint8_t *keep_out,
+                      int32_t *step_out, int32_t *order_out, int32_t *seen_out, int32_t *red_out, voe_map_keyframes_stats *stats_out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1029,6 +1029,47 @@ class Map:
                                      _ptr(role), _ptr(rows), _ptr(fixed), _ptr(order), _ptr(union), C.byref(st)))
         return dict(role=role, n_rows=rows, fixed=fixed, order=order, union=union, stats=st.as_dict())
 
+    # ---- keyframes chosen from the bit rows (voe_map_keyframes*, vo_hip.h: KEYFRAMES) ----
+    def keyframes_dev(self, n_frames, n_words, d_bits, d_n, n_max, d_flags, params: "MapKeyframesParams", d_verdict_out, d_n_rows_out,
+                      d_keep_out, d_step_out, d_order_out, d_seen_out, d_red_out, d_stats):
+        """voe_map_keyframes_dev on device pointers (ints; d_n, d_flags and d_order_out may be None): enqueues and returns.  The
+        per-frame outputs hold n_frames words (d_keep_out: bytes); d_stats: 32 bytes (MapKeyframesStats)."""
+        v = lambda d: C.c_void_p(d) if d else None
+        _chk(self.lib.voe_map_keyframes_dev(self.h, C.c_int(n_frames), C.c_int(n_words), v(d_bits), v(d_n), C.c_int(n_max), v(d_flags),
+                                            C.byref(params), v(d_verdict_out), v(d_n_rows_out), v(d_keep_out), v(d_step_out), v(d_order_out),
+                                            v(d_seen_out), v(d_red_out), v(d_stats)))
+
+    def keyframes(self, bits, flags=None, min_observers=3, share_permille=900, min_seen=1, max_gap=0, max_dropped=None, n_rows=None,
+                  n_max=None):
+        """voe_map_keyframes: which frames to keep, from the bit rows of covisibility().  A frame is a candidate when at least
+        share_permille / 1000 of the entries it sees are seen by min_observers other kept frames (and it sees min_seen, and with
+        max_gap > 0 dropping it leaves no run of more than max_gap missing frames); the best candidate is dropped, the counts
+        follow, at most max_dropped times (default: MAP_KEYFRAMES_MAX_STEPS; 0: the analysis alone).  flags (F,) uint8: 0 free,
+        1 protected, 2 gone (dropped by an earlier call).  n_rows: the frames' live rows, as in window().  Returns dict(verdict
+        (F,) int32: MAP_KEYFRAMES_VERDICT names the codes, n_rows (F,) int32: what refine / bundle / adjust / cull / grow / loops
+        take over the same frames, keep (F,) uint8, step (F,) int32, order (F,) int32, seen, red (F,) int32, stats dict)."""
+        bits = np.ascontiguousarray(np.asarray(bits, np.uint32))
+        if bits.ndim != 2:
+            raise ValueError("bits: (frames, words)")
+        F, W = bits.shape
+        n = None if n_rows is None else np.ascontiguousarray(np.asarray(n_rows, np.int32))
+        if n is not None and n.shape != (F,):
+            raise ValueError("one row count per frame")
+        fl = None if flags is None else np.ascontiguousarray(np.asarray(flags, np.uint8))
+        if fl is not None and fl.shape != (F,):
+            raise ValueError("one flag per frame")
+        cap = int(n_max) if n_max is not None else (int(n.max()) if n is not None and F else 0)
+        ints = [np.full(max(F, 1), -7, np.int32) for _ in range(6)]
+        keep = np.full(max(F, 1), 255, np.uint8)
+        st = MapKeyframesStats()
+        prm = MapKeyframesParams(int(min_observers), int(share_permille), int(min_seen), int(max_gap),
+                                 MAP_KEYFRAMES_MAX_STEPS if max_dropped is None else int(max_dropped))
+        verdict, rows, step, order, seen, red = ints
+        _chk(self.lib.voe_map_keyframes(self.h, C.c_int(F), C.c_int(W), _ptr(bits), _ptr(n) if n is not None else None, C.c_int(cap),
+                                        _ptr(fl) if fl is not None else None, C.byref(prm), _ptr(verdict), _ptr(rows), _ptr(keep), _ptr(step),
+                                        _ptr(order), _ptr(seen), _ptr(red), C.byref(st)))
+        return dict(verdict=verdict, n_rows=rows, keep=keep, step=step, order=order, seen=seen, red=red, stats=st.as_dict())
+
 
 class MapLocaliseStats(C.Structure):
     """vo_map_localise_stats (include/vo_hip.h)"""
@@ -1271,6 +1312,27 @@ class MapFuseStats(C.Structure):
 assert C.sizeof(MapFuseParams) == 32 and C.sizeof(MapFuseStats) == 56
 MAP_FUSE_VERDICT = ("NOT_FINITE", "ALONE", "NOT_MUTUAL", "CONFLICT", "SURVIVOR", "ABSORBED")      # VOE_MAP_FUSE_* (the verdicts)
 MAP_FUSE_STATUS = ("OK", "NOTHING_FUSED")                                                        # VOE_MAP_FUSE_* (the call)
+
+
+class MapKeyframesParams(C.Structure):
+    """voe_map_keyframes_params (include/vo_hip.h)"""
+    _fields_ = [("min_observers", C.c_int32), ("share_permille", C.c_int32), ("min_seen", C.c_int32), ("max_gap", C.c_int32),
+                ("max_dropped", C.c_int32), ("reserved", C.c_int32 * 3)]
+
+
+class MapKeyframesStats(C.Structure):
+    """voe_map_keyframes_stats (include/vo_hip.h)"""
+    _fields_ = [("n_frames", C.c_int32), ("n_kept", C.c_int32), ("n_dropped", C.c_int32), ("n_gone", C.c_int32), ("n_protected", C.c_int32),
+                ("n_needed", C.c_int32), ("n_blocked", C.c_int32), ("n_empty", C.c_int32)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+assert C.sizeof(MapKeyframesParams) == 32 and C.sizeof(MapKeyframesStats) == 32
+MAP_KEYFRAMES_VERDICT = ("LEFT", "PROTECTED", "GONE", "DROPPED", "EMPTY", "NEEDED", "GAP")      # VOE_MAP_KEYFRAMES_* (the verdicts)
+MAP_KEYFRAMES_FLAG = ("FREE", "PROTECTED", "GONE")                                              # VOE_MAP_KEYFRAMES_* (the flags)
+MAP_KEYFRAMES_MAX_STEPS = 1024                                                                  # VOE_MAP_KEYFRAMES_MAX_STEPS
 
 
 class MapCovisStats(C.Structure):

@@ -1,9 +1,10 @@
 // capi_map.hip -- the map's half of the extern "C" boundary (vo_hip.h: vo_map_*; vo_map_adjust.h, vo_map_bundle.h, vo_map_cull.h,
-// vo_map_align.h, vo_map_covis.h, vo_map_grow.h, vo_map_loops.h; voe_map_nearest*, voe_map_guided* and voe_map_fuse* of vo_hip.h itself) and the pose graph's (vo_pose_graph.h).  Host-side plumbing only, like capi.hip: no kernel lives here.
+// vo_map_align.h, vo_map_covis.h, vo_map_grow.h, vo_map_loops.h; voe_map_nearest*, voe_map_guided*, voe_map_fuse* and voe_map_keyframes* of vo_hip.h itself) and the pose graph's (vo_pose_graph.h).  Host-side plumbing only, like capi.hip: no kernel lives here.
 #include <limits.h>
 #include <string.h>
 
 #include "capi_internal.h"
+#include "keyframes_rules.h"
 
 using namespace vo;
 
@@ -32,6 +33,7 @@ struct vo_map {
   DevBuf nearest_ws;            // voe_map_nearest*: the call's index of the map (grid, start table, records), best / distance / status per row, the claim words
   DevBuf fuse_ws;               // voe_map_fuse*: the call's 3-D grid of the map (cell tables, records), finite flags, partner / verdict / remap (compaction: cull_ws; lists: ref_ws)
   DevBuf guided_ws;             // voe_map_guided*: per frame of a group the grid, the cell tables and the records; best / distance / status per row, the claim words
+  DevBuf keyframes_ws;          // voe_map_keyframes*: the bit planes of the counts, seen / red / live / possible per frame, the order, the control words
   MapLoopsWs loops_last{};      // ... as the last call laid it out (voe_map_loops_problems_dev); bytes == 0: no call yet
 };
 
@@ -129,7 +131,7 @@ int vo_map_destroy(vo_map* m) {
   map_free_arrays(m->d);
   if (m->d.hdr) (void)hipFree(m->d.hdr);
   if (m->hist) (void)hipFree(m->hist);
-  m->scratch.release(); m->up_xyz.release(); m->up_app.release(); m->look_ws.release(); m->loc_ws.release(); m->ref_ws.release(); m->pose_ws.release(); m->bundle_ws.release(); m->cull_ws.release(); m->align_ws.release(); m->merge_ws.release(); m->covis_ws.release(); m->window_ws.release(); m->grow_ws.release(); m->loops_ws.release(); m->nearest_ws.release(); m->guided_ws.release(); m->fuse_ws.release();
+  m->scratch.release(); m->up_xyz.release(); m->up_app.release(); m->look_ws.release(); m->loc_ws.release(); m->ref_ws.release(); m->pose_ws.release(); m->bundle_ws.release(); m->cull_ws.release(); m->align_ws.release(); m->merge_ws.release(); m->covis_ws.release(); m->window_ws.release(); m->grow_ws.release(); m->loops_ws.release(); m->nearest_ws.release(); m->guided_ws.release(); m->fuse_ws.release(); m->keyframes_ws.release();
   if (m->solver) (void)vo_picp_destroy(m->solver);
   delete m;
   return VO_OK;
@@ -1448,6 +1450,74 @@ int voe_map_window(vo_map* m, int n_frames, int n_words, const uint32_t* bits, c
   if (order_out) VO_HIP_CHECK(hipMemcpyAsync(order_out, d + o_order, 4 * F, hipMemcpyDeviceToHost, c->stream));
   if (union_out) VO_HIP_CHECK(hipMemcpyAsync(union_out, d + o_union, 4 * W, hipMemcpyDeviceToHost, c->stream));
   VO_HIP_CHECK(hipMemcpyAsync(stats_out, d + o_stats, sizeof(voe_map_window_stats), hipMemcpyDeviceToHost, c->stream));
+  VO_HIP_CHECK(hipStreamSynchronize(c->stream));
+  return VO_OK;
+}
+
+// ---- keyframes chosen from the bit rows (map_keyframes.hip; include/vo_hip.h: KEYFRAMES) --------------------------------------
+static_assert(sizeof(voe_map_keyframes_params) == 32 && sizeof(voe_map_keyframes_stats) == 32,
+              "the records of include/vo_hip.h (KEYFRAMES) as the kernels write them");
+
+int voe_map_keyframes_dev(vo_map* m, int n_frames, int n_words, const uint32_t* d_bits, const int* d_n, int n_max, const uint8_t* d_flags,
+                          const voe_map_keyframes_params* p, int32_t* d_verdict_out, int* d_n_rows_out, uint8_t* d_keep_out, int32_t* d_step_out,
+                          int32_t* d_order_out, int32_t* d_seen_out, int32_t* d_red_out, voe_map_keyframes_stats* d_stats) {
+  const char* fn = "voe_map_keyframes_dev";
+  if (int r = map_keyframes_check(fn, n_frames, n_words, n_max, nullptr, p,
+                                  MapKeyframesPtrs{d_bits, d_verdict_out, d_n_rows_out, d_keep_out, d_step_out, d_order_out, d_seen_out, d_red_out, d_stats}, true))
+    return r;
+  VO_MAP_LIVE(m);
+  vo_ctx* c = m->ctx;
+  MapKeyframesWs w = map_keyframes_layout(nullptr, n_frames, n_words);
+  if (int r = capture_growth_check(c->capturing, fn, {{m->keyframes_ws.cap, w.bytes}}, "%d frames and %d words on this map", n_frames, n_words)) return r;
+  if (int r = set_device(c)) return r;
+  VO_HIP_CHECK(m->keyframes_ws.ensure(w.bytes, c->stream));
+  MapKeyframesArgs a{};
+  a.w = map_keyframes_layout(m->keyframes_ws.p, n_frames, n_words);
+  a.n_frames = n_frames; a.n_words = n_words; a.n_max = n_max; a.n_planes = keyframes_planes(n_frames);
+  a.bits = d_bits; a.d_n = d_n; a.flags = d_flags;
+  a.min_observers = p->min_observers; a.share_permille = p->share_permille; a.min_seen = p->min_seen; a.max_gap = p->max_gap; a.max_dropped = p->max_dropped;
+  a.verdict = d_verdict_out; a.n_rows_out = d_n_rows_out; a.keep = d_keep_out; a.step = d_step_out;
+  a.order = d_order_out ? d_order_out : a.w.order;
+  a.seen_out = d_seen_out; a.red_out = d_red_out; a.stats = d_stats;
+  VO_HIP_CHECK(launch_map_keyframes(c->stream, a));
+  return VO_OK;
+}
+
+int voe_map_keyframes(vo_map* m, int n_frames, int n_words, const uint32_t* bits, const int* n_rows, int n_max, const uint8_t* flags,
+                      const voe_map_keyframes_params* p, int32_t* verdict_out, int* n_rows_out, uint8_t* keep_out, int32_t* step_out,
+                      int32_t* order_out, int32_t* seen_out, int32_t* red_out, voe_map_keyframes_stats* stats_out) {
+  const char* fn = "voe_map_keyframes";
+  if (int r = map_keyframes_check(fn, n_frames, n_words, n_max, flags, p,
+                                  MapKeyframesPtrs{bits, verdict_out, n_rows_out, keep_out, step_out, order_out, seen_out, red_out, stats_out}, false))
+    return r;
+  VO_MAP_LIVE(m);
+  vo_ctx* c = m->ctx;
+  VO_NOT_CAPTURING(c);
+  if (int r = set_device(c)) return r;
+  const size_t F = (size_t)n_frames, W = (size_t)n_words;
+  if (int r = upload(c, c->in[0], bits, sizeof(uint32_t) * F * W)) return r;
+  if (n_rows)
+    if (int r = upload(c, c->in[3], n_rows, sizeof(int) * F)) return r;
+  if (flags)
+    if (int r = upload(c, c->in[4], flags, F)) return r;
+  // one block of outputs: verdict, n_rows, step, order, seen, red [F] ints each, the statistics, the keep bytes [F]
+  const size_t col = up256(4 * F), o_stats = 6 * col, o_keep = o_stats + 256, total = o_keep + up256(F);
+  VO_HIP_CHECK(c->out[0].ensure(total, c->stream));
+  char* d = c->out[0].as<char>();
+  auto ints = [&](int k) { return reinterpret_cast<int32_t*>(d + k * col); };
+  if (int r = voe_map_keyframes_dev(m, n_frames, n_words, c->in[0].as<uint32_t>(), n_rows ? c->in[3].as<int>() : nullptr, n_max,
+                                    flags ? c->in[4].as<uint8_t>() : nullptr, p, ints(0), reinterpret_cast<int*>(ints(1)),
+                                    reinterpret_cast<uint8_t*>(d + o_keep), ints(2), order_out ? ints(3) : nullptr, ints(4), ints(5),
+                                    reinterpret_cast<voe_map_keyframes_stats*>(d + o_stats)))
+    return r;
+  VO_HIP_CHECK(hipMemcpyAsync(verdict_out, ints(0), 4 * F, hipMemcpyDeviceToHost, c->stream));
+  VO_HIP_CHECK(hipMemcpyAsync(n_rows_out, ints(1), 4 * F, hipMemcpyDeviceToHost, c->stream));
+  VO_HIP_CHECK(hipMemcpyAsync(step_out, ints(2), 4 * F, hipMemcpyDeviceToHost, c->stream));
+  if (order_out) VO_HIP_CHECK(hipMemcpyAsync(order_out, ints(3), 4 * F, hipMemcpyDeviceToHost, c->stream));
+  VO_HIP_CHECK(hipMemcpyAsync(seen_out, ints(4), 4 * F, hipMemcpyDeviceToHost, c->stream));
+  VO_HIP_CHECK(hipMemcpyAsync(red_out, ints(5), 4 * F, hipMemcpyDeviceToHost, c->stream));
+  VO_HIP_CHECK(hipMemcpyAsync(keep_out, d + o_keep, F, hipMemcpyDeviceToHost, c->stream));
+  VO_HIP_CHECK(hipMemcpyAsync(stats_out, d + o_stats, sizeof(voe_map_keyframes_stats), hipMemcpyDeviceToHost, c->stream));
   VO_HIP_CHECK(hipStreamSynchronize(c->stream));
   return VO_OK;
 }

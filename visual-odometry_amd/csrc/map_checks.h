@@ -310,6 +310,43 @@ static inline int map_fuse_check(const char* fn, const MapFrames& f, const voe_m
   return VO_OK;
 }
 
+// voe_map_keyframes*: what the call refuses (include/vo_hip.h, KEYFRAMES), in the order they fire.  1 - 5 are the window's
+// refusals for the shape and the pointers, word for word:
+//   1. n_frames outside 1 .. VOE_MAP_COVIS_MAX_FRAMES      2. n_words < 1      3. a null d_bits or d_stats
+//   4. (device pointers) d_stats off an 8-byte boundary      5. a null params or required output, negative n_max
+//   6. n_words above 2^26      7. min_observers < 1      8. share_permille outside 0 .. 1000      9. min_seen < 1
+//   10. max_gap < 0      11. max_dropped outside 0 .. VOE_MAP_KEYFRAMES_MAX_STEPS      12. reserved != 0
+//   13. (device pointers) an int32 array off a 4-byte boundary      14. (host arrays) a flag byte above 2
+struct MapKeyframesPtrs {
+  const void *bits, *verdict, *n_rows, *keep, *step, *order, *seen, *red, *stats;
+};
+static inline int map_keyframes_check(const char* fn, int n_frames, int n_words, int n_max, const uint8_t* host_flags,
+                                      const voe_map_keyframes_params* p, const MapKeyframesPtrs& d, bool dev) {
+  if (n_frames < 1 || n_frames > VOE_MAP_COVIS_MAX_FRAMES)
+    return vo_fail(VO_ERR_INVALID_ARG, "%s: n_frames %d outside 1 .. %d", fn, n_frames, VOE_MAP_COVIS_MAX_FRAMES);
+  if (n_words < 1) return vo_fail(VO_ERR_INVALID_ARG, "%s: n_words must be at least 1", fn);
+  if (!d.bits || !d.stats) return vo_fail(VO_ERR_INVALID_ARG, "%s: null argument", fn);
+  if (dev && !aligned8(d.stats)) return vo_fail(VO_ERR_INVALID_ARG, "%s: d_stats must be 8-byte aligned", fn);
+  if (!(p && d.verdict && d.n_rows && d.keep && d.step && d.seen && d.red)) return vo_fail(VO_ERR_INVALID_ARG, "%s: null argument", fn);
+  if (n_max < 0) return vo_fail(VO_ERR_INVALID_ARG, "%s: negative row count", fn);
+  if (n_words > (1 << 26)) return vo_fail(VO_ERR_INVALID_ARG, "%s: n_words %d above 2^26", fn, n_words);
+  if (p->min_observers < 1) return vo_fail(VO_ERR_INVALID_ARG, "%s: min_observers must be at least 1", fn);
+  if (p->share_permille < 0 || p->share_permille > 1000) return vo_fail(VO_ERR_INVALID_ARG, "%s: share_permille %d outside 0 .. 1000", fn, p->share_permille);
+  if (p->min_seen < 1) return vo_fail(VO_ERR_INVALID_ARG, "%s: min_seen must be at least 1", fn);
+  if (p->max_gap < 0) return vo_fail(VO_ERR_INVALID_ARG, "%s: negative max_gap", fn);
+  if (p->max_dropped < 0 || p->max_dropped > VOE_MAP_KEYFRAMES_MAX_STEPS)
+    return vo_fail(VO_ERR_INVALID_ARG, "%s: max_dropped %d outside 0 .. %d", fn, p->max_dropped, VOE_MAP_KEYFRAMES_MAX_STEPS);
+  if (p->reserved[0] != 0 || p->reserved[1] != 0 || p->reserved[2] != 0) return vo_fail(VO_ERR_INVALID_ARG, "%s: reserved must be 0", fn);
+  if (dev && ((reinterpret_cast<uintptr_t>(d.bits) | reinterpret_cast<uintptr_t>(d.verdict) | reinterpret_cast<uintptr_t>(d.n_rows) |
+               reinterpret_cast<uintptr_t>(d.step) | reinterpret_cast<uintptr_t>(d.order) | reinterpret_cast<uintptr_t>(d.seen) |
+               reinterpret_cast<uintptr_t>(d.red)) & 3u))
+    return vo_fail(VO_ERR_INVALID_ARG, "%s: int32 arrays must be 4-byte aligned", fn);
+  if (host_flags)
+    for (int f = 0; f < n_frames; ++f)
+      if (host_flags[f] > VOE_MAP_KEYFRAMES_GONE) return vo_fail(VO_ERR_INVALID_ARG, "%s: flag %d of frame %d is none of FREE, PROTECTED, GONE", fn, host_flags[f], f);
+  return VO_OK;
+}
+
 // A workspace that would have to grow inside a graph capture: growing frees, allocates and waits.  `ws` lists the buffers the
 // call sizes, each with its capacity and what the call needs; `tail` (printf form) names the call that sizes them outside a
 // capture.  The callers ask BEFORE they enqueue anything: a HIP call refused later would invalidate the capture.

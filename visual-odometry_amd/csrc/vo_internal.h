@@ -1221,4 +1221,33 @@ struct MapFuseArgs {
 __attribute__((visibility("hidden"))) hipError_t launch_map_fuse(hipStream_t st, const MapFuseArgs& a, int* rank);
 __attribute__((visibility("hidden"))) hipError_t launch_map_fuse_finish(hipStream_t st, const MapFuseArgs& a);
 
+// ---- keyframes chosen: redundant frames dropped one at a time (map_keyframes.hip, voe_map_keyframes*; vo_hip.h holds the rules;
+// the bit-sliced counters and the candidate tests are keyframes_rules.h).  All integers. ----
+struct MapKeyframesWs {
+  uint32_t* planes;                     // [P][n_words] bit p of the count of live frames that see the 32 entries of a word
+  int* seen;                            // [n_frames] population count of the row, 0 for a GONE frame
+  int* red;                             // [n_frames] the accumulator of a step: zero between steps
+  uint8_t* live;                        // [n_frames] 1: neither GONE nor dropped
+  uint8_t* poss;                        // [n_frames] 1: FREE, live, seen >= min_seen, and no share or gap test failed so far
+  int32_t* order;                       // [n_frames] (the caller's array takes its place when given)
+  int* ctl;                             // [0] done [1] frames dropped [2] the frame the last step dropped, or -1
+  size_t bytes;
+};
+__attribute__((visibility("hidden"))) MapKeyframesWs map_keyframes_layout(void* base, int n_frames, int n_words);
+struct MapKeyframesArgs {
+  MapKeyframesWs w;
+  int n_frames, n_words, n_max, n_planes;
+  const uint32_t* bits;
+  const int* d_n;                       // [n_frames] or null
+  const uint8_t* flags;                 // [n_frames] or null
+  int min_observers, share_permille, min_seen, max_gap, max_dropped;
+  int32_t* verdict; int* n_rows_out; uint8_t* keep; int32_t* step;
+  int32_t* order;                       // the caller's or the workspace's
+  int32_t *seen_out, *red_out;
+  void* stats;                          // voe_map_keyframes_stats
+};
+// frames -> planes -> max_dropped x { count over the possible candidates, select } -> count over every live frame -> finish.
+// The steps behind the device's done flag return at once.
+__attribute__((visibility("hidden"))) hipError_t launch_map_keyframes(hipStream_t st, const MapKeyframesArgs& a);
+
 }  // namespace vo
