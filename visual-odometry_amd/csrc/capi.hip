@@ -77,7 +77,9 @@ struct vo_picp {
   PicpParams* d_params = nullptr;
   PicpState* d_state = nullptr;
   bool params_dirty = true;
-  DevBuf world_own, meas_own, pairs_own, packed, partials;
+  DevBuf world_own{true}, meas_own{true}, pairs_own{true};   // keeps_state: the host forms' points and pairs, from the call that set them to the solves that read them
+  DevBuf packed;               // (re-packed whenever it is ensured: packed_valid)
+  DevBuf partials{true};       // keeps_state: rows >= grid are never written and must read as zero (zeroed_for_grid)
   const float* d_world = nullptr;
   const float* d_meas = nullptr;
   int n_world = 0, n_meas = 0;

@@ -5,6 +5,7 @@
 #include "../../include/vo_hip.h"
 #include "vo_internal.h"
 #include "map_checks.h"      // aligned8, invert_k
+#include "ws_poison.h"       // the test hook of DevBuf::ensure
 
 #define VO_HIDDEN __attribute__((visibility("hidden")))
 
@@ -29,13 +30,24 @@
 struct VO_HIDDEN DevBuf {
   void* p = nullptr;
   size_t cap = 0;
-  // grow-only; contents are NOT preserved
+  bool keeps_state = false;   // the buffer carries data from one ensure() to a later one on purpose ("The workspace contract")
+  DevBuf() = default;
+  explicit DevBuf(bool state) : keeps_state(state) {}
+  static bool capturing(hipStream_t st) {
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    return hipStreamIsCapturing(st, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone;
+  }
+  // grow-only; contents are NOT preserved.  A call reads nothing from a workspace that the same call has not written first:
+  // under the test hook VO_WS_POISON=<byte> (ws_poison.h) every ensure() outside a graph capture fills all `cap` bytes with the
+  // byte, on the call's stream -- a buffer that keeps state only when it grows.  Unset: the HIP calls below and no other.
   hipError_t ensure(size_t bytes, hipStream_t st) {
-    if (bytes <= cap) return hipSuccess;
-    {   // growing frees, allocates and synchronises: none of it may happen inside a graph capture
-      hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-      if (hipStreamIsCapturing(st, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone) return hipErrorStreamCaptureUnsupported;
+    const int poison = ws_poison_byte();
+    if (bytes <= cap) {
+      if (poison < 0 || keeps_state || !p || capturing(st)) return hipSuccess;
+      return hipMemsetAsync(p, poison, cap, st);
     }
+    // growing frees, allocates and synchronises: none of it may happen inside a graph capture
+    if (capturing(st)) return hipErrorStreamCaptureUnsupported;
     if (p) {
       hipError_t e = hipStreamSynchronize(st);
       if (e != hipSuccess) return e;
@@ -46,7 +58,7 @@ struct VO_HIDDEN DevBuf {
     hipError_t e = hipMalloc(&p, want);
     if (e != hipSuccess) { p = nullptr; return e; }
     cap = want;
-    return hipSuccess;
+    return poison < 0 ? hipSuccess : hipMemsetAsync(p, poison, cap, st);
   }
   void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
   template <class T> T* as() const { return reinterpret_cast<T*>(p); }
@@ -61,12 +73,14 @@ struct vo_ctx {
   DevBuf scratch;     // compaction counts
   DevBuf best;        // matcher keys
   DevBuf table;       // join table
-  DevBuf in[6];       // staging for host-pointer entry points
-  DevBuf out[3];
+  // staging for host-pointer entry points
+  DevBuf in[6] = {DevBuf(true), DevBuf(true), DevBuf(true), DevBuf(true), DevBuf(true), DevBuf(true)};   // keeps_state: a host form's uploads, from the copy in to the launches that read them
+  DevBuf out[3] = {DevBuf(true), DevBuf(true), DevBuf(true)};   // keeps_state: a host form's results, from the launches that write them to the copy back
   DevBuf counts;      // small device ints
   DevBuf batch_pack;  // packed correspondences of the batched solver
   DevBuf batch_bad;   // its per-problem bad-index counters
-  DevBuf batch_states, batch_partials;   // launch-per-round form of the batched solver: per-problem state + partial rows
+  DevBuf batch_states{true};   // launch-per-round form of the batched solver: per-problem state.  keeps_state: the parameter block behind the states, as last uploaded (batch_params_dev)
+  DevBuf batch_partials;       //   ... and its partial rows
   DevBuf batch_help;  // shared form (fewer problems than CUs): tagged words handed between workgroups
   vo::PicpParams batch_params_host{};    //   its parameter block as last uploaded, and where
   const vo::PicpParams* batch_params_dev = nullptr;

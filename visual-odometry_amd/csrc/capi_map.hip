@@ -16,7 +16,7 @@ struct vo_map {
   DevBuf scratch;
   float* hist = nullptr;        // [0,16) the history isometry, [16,32) staging of a host isometry (vo_map_update)
   MapBound bd;                  // the host's bound of the size and its transitions (map_checks.h); bd.cap follows d.cap
-  DevBuf up_xyz, up_app;        // staging of vo_map_update
+  DevBuf up_xyz{true}, up_app{true};   // staging of vo_map_update.  keeps_state: the host's rows, between their upload and the update's launches
   DevBuf look_ws;               // vo_map_lookup*: per-workgroup counts, entries per query position
   DevBuf loc_ws;                // vo_map_localise*: what passes from stage to stage (hits, gathered points, winner, pairs handed on)
   vo_picp* solver = nullptr;    // vo_map_localise[_dev]: made by the first call
@@ -29,7 +29,7 @@ struct vo_map {
   DevBuf covis_ws;              // voe_map_covis*: the lookup's pairs, counts and entries, the population counts per frame and per block of words
   DevBuf window_ws;             // voe_map_window*: the counts against the query row and against the union, the order, the union
   DevBuf grow_ws;               // voe_map_grow*: the open rows, the tracks' private table, verdicts, the staging area (the lists live in ref_ws)
-  DevBuf loops_ws;              // voe_map_loops*: the lookup's arrays, keys, reference frames, bit rows, candidates, slots, the gathered problems
+  DevBuf loops_ws{true};        // keeps_state: the gathered problems of the last call, handed out by voe_map_loops_problems_dev (loops_last).  voe_map_loops*: the lookup's arrays, keys, reference frames, bit rows, candidates, slots, the gathered problems
   DevBuf nearest_ws;            // voe_map_nearest*: the call's index of the map (grid, start table, records), best / distance / status per row, the claim words
   DevBuf fuse_ws;               // voe_map_fuse*: the call's 3-D grid of the map (cell tables, records), finite flags, partner / verdict / remap (compaction: cull_ws; lists: ref_ws)
   DevBuf guided_ws;             // voe_map_guided*: per frame of a group the grid, the cell tables and the records; best / distance / status per row, the claim words

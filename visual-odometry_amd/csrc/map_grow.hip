@@ -405,7 +405,9 @@ hipError_t launch_map_grow(hipStream_t st, const MapGrowArgs& a, int n_cu) {
   if (e != hipSuccess) return e;
   e = launch_map_rehash(st, a.w.priv, 0);
   if (e != hipSuccess) return e;
-  e = launch_map_update(st, a.w.priv, a.w.xyz, a.w.oapp, (int)R, a.w.ctl + GC_OPEN, nullptr, a.w.upd);
+  // (the private map's points are read by nobody; the commit still copies three floats per open row, so the cloud's points are
+  // the compacted rows -- written above, 10 floats a row -- not w.xyz, which this call writes only in grow_track_kernel)
+  e = launch_map_update(st, a.w.priv, a.w.oapp, a.w.oapp, (int)R, a.w.ctl + GC_OPEN, nullptr, a.w.upd);
   if (e != hipSuccess) return e;
   e = launch_map_lookup(st, a.w.priv, a.w.oapp, R, (int)R, a.w.ctl + GC_OPEN, 1, nullptr, a.w.ctl + GC_PRIV_HITS, nullptr, nullptr, a.w.otrack, a.w.look);
   if (e != hipSuccess) return e;
