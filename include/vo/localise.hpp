@@ -297,6 +297,32 @@ inline const char* keyframes_verdict_name(int verdict) {
   return verdict >= 0 && verdict < 7 ? names[verdict] : "?";
 }
 
+//! voe_map_prune: single observations taken out of their frames, with a guard per landmark and per frame (include/vo_hip.h,
+//! PRUNE)
+struct PruneOptions {
+  float max_err_px = 0.f;            //!< > 0: an eligible observation with |e| above it is HIGH_ERROR
+  float rel_factor = 0.f;            //!< > 0: ... with |e| above rel_factor times its landmark's (lower) median is RELATIVE
+  float rel_floor_px = 0.f;          //!< RELATIVE only above this
+  int rel_min_obs = 3;               //!< RELATIVE only on landmarks with that many eligible observations (at least 3)
+  bool unique = true;                //!< of the rows of one frame on one entry only the best stays
+  int max_share_landmark = 1000;     //!< more soft observations than that many of 1000: the landmark is at fault, its rows stay
+  int max_share_frame = 1000;        //!< the same for a frame, after the landmarks
+};
+struct MapPrune {
+  std::vector<int32_t> entry;        //!< per frame and row (the longest frame's length each): the entry of a row that stays, or -1
+  std::vector<int32_t> status;       //!< VOE_MAP_PRUNE_* per frame and row
+  std::vector<double> sq;            //!< |e|^2 of an observation, +inf elsewhere
+  std::vector<Vector10fVector> appearances;      //!< the frames' rows, a pruned row's first component a NaN: what the other map calls take
+  std::vector<voe_map_prune_landmark> landmarks; //!< one record per entry of the map
+  std::vector<voe_map_prune_frame> frames;       //!< one record per frame
+  size_t n_max = 0;                  //!< the row length of entry, status and sq
+  voe_map_prune_stats stats{};
+};
+inline const char* prune_status_name(int status) {
+  static const char* names[] = {"KEPT", "NOT_LIVE", "MISS", "NOT_FINITE", "BEHIND", "DUPLICATE", "HIGH_ERROR", "RELATIVE", "LANDMARK_AT_FAULT", "FRAME_AT_FAULT"};
+  return status >= 0 && status < 10 ? names[status] : "?";
+}
+
 //! The rigid pose that goes with a similarity S = [c R | t] of the pose graph (vo/pose_graph.hpp): [R | t / c], on the host in
 //! double.  A map point moved by S_new^-1 S_old of its reference frame (DeviceMap::applyCorrection) projects there, under
 //! rigid_pose(S_new), where it projected before.
@@ -783,6 +809,30 @@ class DeviceMap {
                             &k.stats), "voe_map_keyframes");
     k.verdict.resize(F); k.n_rows.resize(F); k.keep.resize(F); k.step.resize(F); k.order.resize(F); k.seen.resize(F); k.red.resize(F);
     return k;
+  }
+
+  //! single observations pruned (voe_map_prune): every observation of the frames judged on its own at the poses (p_cam = T p_map,
+  //! one per frame) given; the map is not written.  The result's appearances go to refine / bundle / cull / grow in place of the
+  //! frames' own: a pruned row finds nothing there.  Named landmarks want DeviceMap::refine, named frames refinePoses.
+  MapPrune prune(const Camera& cam, const std::vector<Vector2fVector>& pixels, const std::vector<Vector10fVector>& appearances,
+                 const IsometryVector& poses, const PruneOptions& opt = PruneOptions()) const {
+    const Window w = pack("DeviceMap::prune", pixels, appearances, poses);
+    const size_t M = (size_t)size(), R = w.F * w.cap;
+    MapPrune r;
+    r.n_max = w.cap;
+    r.entry.assign(R + 1, -1); r.status.assign(R + 1, VOE_MAP_PRUNE_NOT_LIVE); r.sq.assign(R + 1, 0.0);
+    r.landmarks.assign(M + 1, voe_map_prune_landmark{}); r.frames.assign(w.F + 1, voe_map_prune_frame{});
+    std::vector<float> out(w.app.size(), 0.f);
+    const voe_map_prune_params prm{opt.max_err_px, opt.rel_factor, opt.rel_floor_px, opt.rel_min_obs, opt.unique ? 1 : 0, opt.max_share_landmark,
+                                   opt.max_share_frame, 0};
+    check(voe_map_prune(h_, (int)w.F, cam.cameraMatrix().data(), w.uv.data(), w.app.data(), w.n.data(), (int)w.cap, w.T.data(), &prm, r.entry.data(),
+                        r.status.data(), r.sq.data(), out.data(), r.landmarks.data(), r.frames.data(), &r.stats), "voe_map_prune");
+    r.entry.resize(R); r.status.resize(R); r.sq.resize(R); r.landmarks.resize(M); r.frames.resize(w.F);
+    r.appearances = appearances;
+    for (size_t f = 0; f < w.F; ++f)
+      for (size_t i = 0; i < appearances[f].size(); ++i)
+        for (int k = 0; k < 10; ++k) r.appearances[f][i][k] = out[(f * w.cap + i) * 10 + k];
+    return r;
   }
 
   //! the map's points and appearances in entry order

@@ -1140,6 +1140,90 @@ int voe_map_keyframes(vo_map *m, int n_frames, int n_words, const uint32_t *bits
                       const voe_map_keyframes_params *params, int32_t *verdict_out, int *n_rows_out, uint8_t *keep_out,
                       int32_t *step_out, int32_t *order_out, int32_t *seen_out, int32_t *red_out, voe_map_keyframes_stats *stats_out);
 
+/* PRUNE.  One wrong observation taken back.  An association is the 40 appearance bytes of a frame's row; voe_map_nearest,
+ * voe_map_guided and voe_map_fuse write them, a Huber weight only makes a wrong one count less, and voe_map_cull can only drop
+ * the whole landmark.  This call judges every observation of the window on its own (ORB-SLAM erases observations over chi^2 or
+ * with non-positive depth after every local bundle) and hands back rows from which the bad ones are gone -- with two guards,
+ * because a row that disagrees with the map may be right: the landmark may be wrong (vo_map_refine's job) or the frame's pose
+ * (vo_map_refine_poses').  The chain: nearest / guided -> localise -> bundle -> PRUNE -> bundle -> cull.  Frames, pixels,
+ * appearances, d_n_rows, strides, K and d_T16 mean what they mean in voe_map_cull_batch_dev (vo_map_cull.h).  THE MAP, ITS TABLE
+ * AND ITS HEADER ARE NEVER WRITTEN.  Every output is a function of the data alone.  RULES:
+ *   1. OBSERVATION.  Exactly vo_map_refine's: a live row whose exact lookup returns an entry, with key f * n_max + i.  A
+ *      landmark's list is in ascending key.
+ *   2. TERMS.  Per observation, in double: sq = |e|^2 and the camera z, by the device function of voe_map_cull (score_obs) and
+ *      therefore with its bits.  No Huber weight and no gate apply.
+ *   3. HARD TESTS, which need no context.  NOT_FINITE: sq or z is not finite.  BEHIND: z > 0 is false.
+ *   4. DUPLICATE, only with unique != 0.  Among the observations of one (entry, frame) that passed rule 3 the one with the
+ *      smallest (sq, key) stays; the others are DUPLICATE.
+ *   5. ELIGIBLE: the observation passed rules 3 and 4.  n_el: the eligible observations of a landmark.
+ *   6. SOFT TESTS, on eligible observations only; HIGH_ERROR goes before RELATIVE.
+ *      HIGH_ERROR: max_err_px > 0 and sq > max_err_px^2 (the threshold widened to double, then squared; no square root).
+ *      RELATIVE: rel_factor > 0, n_el >= rel_min_obs, sq > rel_factor^2 * med and sq > rel_floor_px^2 (both widened, then
+ *      squared; one double product with med).  med is the LOWER MEDIAN: the element of rank (n_el - 1) / 2 (integer division)
+ *      of the eligible sq in ascending order -- an exact selection, so no order of evaluation can show.
+ *   7. LANDMARK GUARD.  n_soft: the landmark's HIGH_ERROR plus RELATIVE.  If n_soft * 1000 > max_share_landmark * n_el (int64)
+ *      the landmark is at fault: every soft observation of it becomes LANDMARK_AT_FAULT and is KEPT.  1000 switches the guard
+ *      off; 0 names every landmark with a soft observation.
+ *   8. FRAME GUARD, after rule 7.  n_el_f: the frame's eligible observations; n_soft_f: those still HIGH_ERROR or RELATIVE.  If
+ *      n_soft_f * 1000 > max_share_frame * n_el_f the frame is at fault: its soft observations become FRAME_AT_FAULT and are
+ *      KEPT.  1000 switches it off.
+ *   9. STATUS per row POSITION: the VOE_MAP_PRUNE_* below.  NOT_LIVE: the row lies behind the live count.  MISS: live, no entry.
+ *      A row is PRUNED when its status is 3 .. 7.
+ *  10. OUTPUTS.  d_entry_out [n_frames][n_max]: the entry where the status is 0, 8 or 9; -1 elsewhere, also behind the live
+ *      rows.  d_status_out (or NULL): rule 9.  d_sq_out (double, or NULL): sq where the row is an observation, +inf elsewhere.
+ *      d_app_out (or NULL; laid out like d_app, and it may BE d_app): live rows only; a pruned row gets its own bytes with
+ *      component 0 replaced by the quiet NaN 0x7FC00000 -- NEAREST's rule 6: no map call associates such a row and
+ *      voe_map_grow opens no track on it --, every other row its own bytes.  d_landmark_out [size] (or NULL): n_obs, n_el,
+ *      n_soft (rule 7's), n_pruned (the landmark's rows with a final status 3 .. 7), at_fault, and med_sq -- 0 where RELATIVE
+ *      was not evaluated.  d_frame_out [n_frames] (or NULL): n_obs, n_el, n_soft (rule 8's), at_fault.  *d_stats: n_frames,
+ *      n_entries (the map's size), the ten status counts over all positions, n_landmarks_at_fault, n_frames_at_fault, n_obs
+ *      (the statuses other than 1 and 2) and n_pruned: integer sums.
+ *  11. CONTRACT.  vo_map_lookup_batch_dev on d_app_out returns the bytes of d_entry_out at every position of every frame.  With
+ *      rel_factor == 0 and both guards at 1000 a second call on d_app_out prunes nothing, and -- every remaining test being a
+ *      matter of the row, or of the rows of one frame on one entry -- frame f of the batched call is bit for bit the single
+ *      call on frame f (the landmark records excepted: they count the window).  With a guard or RELATIVE on, neither is
+ *      claimed: a pruned row leaves its landmark and its frame, so shares and medians move.
+ * Everything is enqueued on the context's stream and nothing is read back.  The launches are a fixed sequence that depends on
+ * the shape (n_frames, n_max and the map's bound) alone, no launch waits for another workgroup, and the only atomics are
+ * integer ones.  Capturable under the rules of the other map calls: a first call of the shape sizes the workspaces; a capture
+ * that would have to grow one is refused (VO_ERR_NOT_READY) before anything is enqueued.  params is a host value, read when the
+ * call is made.
+ * Refused (VO_ERR_INVALID_ARG): the cull's refusals for the frames (n_frames outside 1 .. 65535, n_max < 0, null pixels or
+ * appearances with n_max > 0, d_uv, d_app or d_stats off an 8-byte boundary, a stride below n_max or too large, a singular K,
+ * more than 2^30 rows, a null K, d_T16 or d_stats); null params or d_entry_out; max_err_px, rel_factor or rel_floor_px negative
+ * or not finite; rel_min_obs < 3; a share outside 0 .. 1000; unique outside 0 / 1; reserved != 0; an int32 output off a 4-byte
+ * boundary; d_sq_out, d_app_out, d_landmark_out or d_frame_out off an 8-byte one; d_app_out overlapping d_app without being
+ * d_app.  NOT refused: all tests off -- max_err_px == 0, rel_factor == 0 and unique == 0 still runs rule 3. */
+#define VOE_MAP_PRUNE_KEPT              0
+#define VOE_MAP_PRUNE_NOT_LIVE          1
+#define VOE_MAP_PRUNE_MISS              2
+#define VOE_MAP_PRUNE_NOT_FINITE        3
+#define VOE_MAP_PRUNE_BEHIND            4
+#define VOE_MAP_PRUNE_DUPLICATE         5
+#define VOE_MAP_PRUNE_HIGH_ERROR        6
+#define VOE_MAP_PRUNE_RELATIVE          7
+#define VOE_MAP_PRUNE_LANDMARK_AT_FAULT 8
+#define VOE_MAP_PRUNE_FRAME_AT_FAULT    9
+typedef struct voe_map_prune_params { float max_err_px, rel_factor, rel_floor_px; int32_t rel_min_obs, unique, max_share_landmark, max_share_frame, reserved; } voe_map_prune_params;   /* 32 bytes */
+typedef struct voe_map_prune_landmark { int32_t n_obs, n_el, n_soft, n_pruned, at_fault, reserved; double med_sq; } voe_map_prune_landmark;   /* 32 bytes */
+typedef struct voe_map_prune_frame { int32_t n_obs, n_el, n_soft, at_fault; } voe_map_prune_frame;   /* 16 bytes */
+typedef struct voe_map_prune_stats { int32_t n_frames, n_entries, by_status[10], n_landmarks_at_fault, n_frames_at_fault, n_obs, n_pruned; } voe_map_prune_stats;   /* 64 bytes */
+int voe_map_prune_batch_dev(vo_map *m, int n_frames, const float K[9], const float *d_uv, size_t uv_stride, const float *d_app,
+                            size_t app_stride, int n_max, const int *d_n_rows /* [n_frames] or NULL */, const float *d_T16,
+                            const voe_map_prune_params *params, int32_t *d_entry_out /* [n_frames][n_max] */,
+                            int32_t *d_status_out /* [n_frames][n_max] or NULL */, double *d_sq_out /* [n_frames][n_max] or NULL */,
+                            float *d_app_out /* like d_app, d_app itself, or NULL */, voe_map_prune_landmark *d_landmark_out /* [size] or NULL */,
+                            voe_map_prune_frame *d_frame_out /* [n_frames] or NULL */, voe_map_prune_stats *d_stats /* 8-byte aligned */);
+/* one frame: n_frames 1, both strides n_max */
+int voe_map_prune_dev(vo_map *m, const float K[9], const float *d_uv, const float *d_app, int n_max, const int *d_n_rows, const float *d_T16,
+                      const voe_map_prune_params *params, int32_t *d_entry_out, int32_t *d_status_out, double *d_sq_out, float *d_app_out,
+                      voe_map_prune_landmark *d_landmark_out, voe_map_prune_frame *d_frame_out, voe_map_prune_stats *d_stats);
+/* host arrays, n_max rows per frame (every output but entry_out may be NULL; landmark_out holds the map's size of records).
+ * Uploads, the device call, one read-back; the same bytes. */
+int voe_map_prune(vo_map *m, int n_frames, const float K[9], const float *uv, const float *app, const int *n_rows /* or NULL */, int n_max,
+                  const float *T16, const voe_map_prune_params *params, int32_t *entry_out, int32_t *status_out, double *sq_out, float *app_out,
+                  voe_map_prune_landmark *landmark_out, voe_map_prune_frame *frame_out, voe_map_prune_stats *stats_out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1070,6 +1070,58 @@ class Map:
                                         _ptr(order), _ptr(seen), _ptr(red), C.byref(st)))
         return dict(verdict=verdict, n_rows=rows, keep=keep, step=step, order=order, seen=seen, red=red, stats=st.as_dict())
 
+    # ---- single observations pruned (voe_map_prune*, vo_hip.h: PRUNE) ----
+    def prune_batch_dev(self, camera: Camera, n_frames, d_uv, uv_stride, d_app, app_stride, n_max, d_n, d_T16, params: "MapPruneParams",
+                        d_entry_out, d_status_out, d_sq_out, d_app_out, d_landmark_out, d_frame_out, d_stats):
+        """voe_map_prune_batch_dev on device pointers (ints; d_n and every output but d_entry_out and d_stats may be None;
+        d_app_out may be d_app; strides in pixels / rows): enqueues and returns.  d_entry_out, d_status_out: n_frames x n_max
+        int32; d_sq_out: the same of float64; d_landmark_out: size x 32 bytes (MAP_PRUNE_LANDMARK_DTYPE); d_frame_out: n_frames x
+        16 bytes (MAP_PRUNE_FRAME_DTYPE); d_stats: 64 bytes (MapPruneStats)."""
+        v = lambda d: C.c_void_p(d) if d else None
+        _chk(self.lib.voe_map_prune_batch_dev(self.h, C.c_int(n_frames), _ptr(_colmajor(camera._K, 3)), v(d_uv), C.c_size_t(uv_stride),
+                                              v(d_app), C.c_size_t(app_stride), C.c_int(n_max), v(d_n), v(d_T16), C.byref(params),
+                                              v(d_entry_out), v(d_status_out), v(d_sq_out), v(d_app_out), v(d_landmark_out), v(d_frame_out),
+                                              v(d_stats)))
+
+    def prune_dev(self, camera: Camera, d_uv, d_app, n_max, d_n, d_T16, params: "MapPruneParams", d_entry_out, d_status_out, d_sq_out,
+                  d_app_out, d_landmark_out, d_frame_out, d_stats):
+        """voe_map_prune_dev: prune_batch_dev on one frame"""
+        v = lambda d: C.c_void_p(d) if d else None
+        _chk(self.lib.voe_map_prune_dev(self.h, _ptr(_colmajor(camera._K, 3)), v(d_uv), v(d_app), C.c_int(n_max), v(d_n), v(d_T16),
+                                        C.byref(params), v(d_entry_out), v(d_status_out), v(d_sq_out), v(d_app_out), v(d_landmark_out),
+                                        v(d_frame_out), v(d_stats)))
+
+    def prune(self, camera: Camera, frames, poses, max_err_px=0.0, rel_factor=0.0, rel_floor_px=0.0, rel_min_obs=3, unique=True,
+              max_share_landmark=1000, max_share_frame=1000):
+        """voe_map_prune: every observation of `frames` (as in refine; poses 4x4, p_cam = T p_map) judged on its own: not finite,
+        behind the camera, a second row of its frame on one entry (unique), |e| above max_err_px, or |e| above rel_factor times
+        its landmark's median (and above rel_floor_px; landmarks with rel_min_obs eligible observations).  A landmark with more
+        than max_share_landmark per mille of soft observations, then a frame with more than max_share_frame, is named instead
+        and keeps its rows (1000: guard off).  The map is not written.  Returns dict(entry (F, n_max) int32: the entry of a row
+        that stays or -1, status (F, n_max) int32: MAP_PRUNE_STATUS names the codes, sq (F, n_max) float64, frames: the list of
+        (uv, app) with the pruned rows' first appearance component made NaN -- what the other map calls take --, landmarks and
+        frame_records: structured arrays, stats dict)."""
+        F, cap, uv, app, n, T, _ = self._window(frames, poses, None)
+        rows = max(cap, 1)
+        entry = np.full((F, rows), -1, np.int32)
+        status = np.full((F, rows), 1, np.int32)
+        sq = np.full((F, rows), np.inf, np.float64)
+        app_in = np.ascontiguousarray(app[:, :cap]) if cap else None
+        app_out = np.zeros((F, rows, 10), np.float32)
+        lm = np.zeros(max(len(self), 1), MAP_PRUNE_LANDMARK_DTYPE)
+        fr = np.zeros(F, MAP_PRUNE_FRAME_DTYPE)
+        st = MapPruneStats()
+        prm = MapPruneParams(float(max_err_px), float(rel_factor), float(rel_floor_px), int(rel_min_obs), int(bool(unique)),
+                             int(max_share_landmark), int(max_share_frame), 0)
+        uv_in = np.ascontiguousarray(uv[:, :cap]) if cap else None
+        e2, s2, q2, a2 = (np.ascontiguousarray(x[:, :cap]) for x in (entry, status, sq, app_out))
+        _chk(self.lib.voe_map_prune(self.h, C.c_int(F), _ptr(_colmajor(camera._K, 3)), _ptr(uv_in) if cap else None,
+                                    _ptr(app_in) if cap else None, _ptr(n), C.c_int(cap), _ptr(T), C.byref(prm), _ptr(e2), _ptr(s2),
+                                    _ptr(q2), _ptr(a2), C.c_void_p(lm.ctypes.data), C.c_void_p(fr.ctypes.data), C.byref(st)))
+        out_frames = [(np.asarray(frames[f][0], np.float32).reshape(-1, 2).copy(), a2[f, : n[f]].copy()) for f in range(F)]
+        return dict(entry=e2, status=s2, sq=q2, frames=out_frames, landmarks=lm[: st.n_entries].copy(), frame_records=fr, stats=st.as_dict())
+
+
 
 class MapLocaliseStats(C.Structure):
     """vo_map_localise_stats (include/vo_hip.h)"""
@@ -1333,6 +1385,32 @@ assert C.sizeof(MapKeyframesParams) == 32 and C.sizeof(MapKeyframesStats) == 32
 MAP_KEYFRAMES_VERDICT = ("LEFT", "PROTECTED", "GONE", "DROPPED", "EMPTY", "NEEDED", "GAP")      # VOE_MAP_KEYFRAMES_* (the verdicts)
 MAP_KEYFRAMES_FLAG = ("FREE", "PROTECTED", "GONE")                                              # VOE_MAP_KEYFRAMES_* (the flags)
 MAP_KEYFRAMES_MAX_STEPS = 1024                                                                  # VOE_MAP_KEYFRAMES_MAX_STEPS
+
+
+class MapPruneParams(C.Structure):
+    """voe_map_prune_params (include/vo_hip.h)"""
+    _fields_ = [("max_err_px", C.c_float), ("rel_factor", C.c_float), ("rel_floor_px", C.c_float), ("rel_min_obs", C.c_int32),
+                ("unique", C.c_int32), ("max_share_landmark", C.c_int32), ("max_share_frame", C.c_int32), ("reserved", C.c_int32)]
+
+
+class MapPruneStats(C.Structure):
+    """voe_map_prune_stats (include/vo_hip.h)"""
+    _fields_ = [("n_frames", C.c_int32), ("n_entries", C.c_int32), ("by_status", C.c_int32 * 10), ("n_landmarks_at_fault", C.c_int32),
+                ("n_frames_at_fault", C.c_int32), ("n_obs", C.c_int32), ("n_pruned", C.c_int32)]
+
+    def as_dict(self):
+        return dict(n_frames=self.n_frames, n_entries=self.n_entries, by_status=list(self.by_status),
+                    n_landmarks_at_fault=self.n_landmarks_at_fault, n_frames_at_fault=self.n_frames_at_fault, n_obs=self.n_obs,
+                    n_pruned=self.n_pruned)
+
+
+assert C.sizeof(MapPruneParams) == 32 and C.sizeof(MapPruneStats) == 64
+MAP_PRUNE_LANDMARK_DTYPE = np.dtype([("n_obs", "<i4"), ("n_el", "<i4"), ("n_soft", "<i4"), ("n_pruned", "<i4"), ("at_fault", "<i4"),
+                                     ("reserved", "<i4"), ("med_sq", "<f8")])      # voe_map_prune_landmark
+MAP_PRUNE_FRAME_DTYPE = np.dtype([("n_obs", "<i4"), ("n_el", "<i4"), ("n_soft", "<i4"), ("at_fault", "<i4")])      # voe_map_prune_frame
+assert MAP_PRUNE_LANDMARK_DTYPE.itemsize == 32 and MAP_PRUNE_FRAME_DTYPE.itemsize == 16
+MAP_PRUNE_STATUS = ("KEPT", "NOT_LIVE", "MISS", "NOT_FINITE", "BEHIND", "DUPLICATE", "HIGH_ERROR", "RELATIVE", "LANDMARK_AT_FAULT",
+                    "FRAME_AT_FAULT")                                                           # VOE_MAP_PRUNE_*
 
 
 class MapCovisStats(C.Structure):

@@ -1,5 +1,5 @@
 // capi_map.hip -- the map's half of the extern "C" boundary (vo_hip.h: vo_map_*; vo_map_adjust.h, vo_map_bundle.h, vo_map_cull.h,
-// vo_map_align.h, vo_map_covis.h, vo_map_grow.h, vo_map_loops.h; voe_map_nearest*, voe_map_guided*, voe_map_fuse* and voe_map_keyframes* of vo_hip.h itself) and the pose graph's (vo_pose_graph.h).  Host-side plumbing only, like capi.hip: no kernel lives here.
+// vo_map_align.h, vo_map_covis.h, vo_map_grow.h, vo_map_loops.h; voe_map_nearest*, voe_map_guided*, voe_map_fuse*, voe_map_keyframes* and voe_map_prune* of vo_hip.h itself) and the pose graph's (vo_pose_graph.h).  Host-side plumbing only, like capi.hip: no kernel lives here.
 #include <limits.h>
 #include <string.h>
 
@@ -34,6 +34,7 @@ struct vo_map {
   DevBuf fuse_ws;               // voe_map_fuse*: the call's 3-D grid of the map (cell tables, records), finite flags, partner / verdict / remap (compaction: cull_ws; lists: ref_ws)
   DevBuf guided_ws;             // voe_map_guided*: per frame of a group the grid, the cell tables and the records; best / distance / status per row, the claim words
   DevBuf keyframes_ws;          // voe_map_keyframes*: the bit planes of the counts, seen / red / live / possible per frame, the order, the control words
+  DevBuf prune_ws;              // voe_map_prune*: |e|^2 and status in list order, the status per row position, the frames' partial counts and census words (the lists live in ref_ws)
   MapLoopsWs loops_last{};      // ... as the last call laid it out (voe_map_loops_problems_dev); bytes == 0: no call yet
 };
 
@@ -131,7 +132,7 @@ int vo_map_destroy(vo_map* m) {
   map_free_arrays(m->d);
   if (m->d.hdr) (void)hipFree(m->d.hdr);
   if (m->hist) (void)hipFree(m->hist);
-  m->scratch.release(); m->up_xyz.release(); m->up_app.release(); m->look_ws.release(); m->loc_ws.release(); m->ref_ws.release(); m->pose_ws.release(); m->bundle_ws.release(); m->cull_ws.release(); m->align_ws.release(); m->merge_ws.release(); m->covis_ws.release(); m->window_ws.release(); m->grow_ws.release(); m->loops_ws.release(); m->nearest_ws.release(); m->guided_ws.release(); m->fuse_ws.release(); m->keyframes_ws.release();
+  m->scratch.release(); m->up_xyz.release(); m->up_app.release(); m->look_ws.release(); m->loc_ws.release(); m->ref_ws.release(); m->pose_ws.release(); m->bundle_ws.release(); m->cull_ws.release(); m->align_ws.release(); m->merge_ws.release(); m->covis_ws.release(); m->window_ws.release(); m->grow_ws.release(); m->loops_ws.release(); m->nearest_ws.release(); m->guided_ws.release(); m->fuse_ws.release(); m->keyframes_ws.release(); m->prune_ws.release();
   if (m->solver) (void)vo_picp_destroy(m->solver);
   delete m;
   return VO_OK;
@@ -1518,6 +1519,92 @@ int voe_map_keyframes(vo_map* m, int n_frames, int n_words, const uint32_t* bits
   VO_HIP_CHECK(hipMemcpyAsync(red_out, ints(5), 4 * F, hipMemcpyDeviceToHost, c->stream));
   VO_HIP_CHECK(hipMemcpyAsync(keep_out, d + o_keep, F, hipMemcpyDeviceToHost, c->stream));
   VO_HIP_CHECK(hipMemcpyAsync(stats_out, d + o_stats, sizeof(voe_map_keyframes_stats), hipMemcpyDeviceToHost, c->stream));
+  VO_HIP_CHECK(hipStreamSynchronize(c->stream));
+  return VO_OK;
+}
+
+// ---- single observations pruned (map_prune.hip; include/vo_hip.h: PRUNE) -------------------------------------------------------
+static_assert(sizeof(voe_map_prune_params) == 32 && sizeof(voe_map_prune_landmark) == 32 && sizeof(voe_map_prune_frame) == 16 &&
+                  sizeof(voe_map_prune_stats) == 64,
+              "the records of include/vo_hip.h (PRUNE) as the kernels write them");
+
+int voe_map_prune_batch_dev(vo_map* m, int n_frames, const float K[9], const float* d_uv, size_t uv_stride, const float* d_app,
+                            size_t app_stride, int n_max, const int* d_n, const float* d_T16, const voe_map_prune_params* p,
+                            int32_t* d_entry_out, int32_t* d_status_out, double* d_sq_out, float* d_app_out,
+                            voe_map_prune_landmark* d_landmark_out, voe_map_prune_frame* d_frame_out, voe_map_prune_stats* d_stats) {
+  const char* fn = "voe_map_prune_batch_dev";
+  const MapFrames f{n_frames, K, d_uv, uv_stride, d_app, app_stride, n_max, d_n};
+  if (int r = map_prune_check(fn, f, p, MapPrunePtrs{d_T16, d_entry_out, d_status_out, d_sq_out, d_app_out, d_landmark_out, d_frame_out, d_stats}))
+    return r;
+  VO_MAP_LIVE(m);
+  vo_ctx* c = m->ctx;
+  // the call's own workspace is indexed by row alone; the lists (ref_ws) are allocated for the capacity and laid out for the
+  // launch bound by refine_prepare, as for the cull
+  const size_t need = map_prune_layout(nullptr, n_frames, n_max).bytes;
+  if (int r = window_growth_check(m, fn, f, {{m->prune_ws.cap, need}})) return r;       // (before the lookup is enqueued)
+  MapRefineWs rw;
+  if (int r = refine_prepare(fn, m, f, &rw)) return r;        // the one lookup of the call
+  VO_HIP_CHECK(m->prune_ws.ensure(need, c->stream));
+  MapPruneArgs a{};
+  a.l = rw; a.w = map_prune_layout(m->prune_ws.p, n_frames, n_max);
+  fill_map(a.v, m);
+  fill_frames(a.v, f, d_T16);
+  a.app = d_app; a.app_stride = app_stride; a.d_n = d_n; a.nb = map_prune_blocks(n_max);
+  a.max_sq = (double)p->max_err_px * (double)p->max_err_px;
+  a.rf2 = (double)p->rel_factor * (double)p->rel_factor;
+  a.floor2 = (double)p->rel_floor_px * (double)p->rel_floor_px;
+  a.rel_on = p->rel_factor > 0.f; a.rel_min_obs = p->rel_min_obs; a.unique = p->unique;
+  a.share_landmark = p->max_share_landmark; a.share_frame = p->max_share_frame;
+  a.entry_out = d_entry_out; a.status_out = d_status_out; a.sq_out = d_sq_out; a.app_out = d_app_out;
+  a.landmark_out = d_landmark_out; a.frame_out = d_frame_out; a.stats = reinterpret_cast<int*>(d_stats);
+  VO_HIP_CHECK(launch_map_prune(c->stream, a, c->n_cu));
+  return VO_OK;
+}
+
+int voe_map_prune_dev(vo_map* m, const float K[9], const float* d_uv, const float* d_app, int n_max, const int* d_n, const float* d_T16,
+                      const voe_map_prune_params* p, int32_t* d_entry_out, int32_t* d_status_out, double* d_sq_out, float* d_app_out,
+                      voe_map_prune_landmark* d_landmark_out, voe_map_prune_frame* d_frame_out, voe_map_prune_stats* d_stats) {
+  const size_t stride = (size_t)(n_max > 0 ? n_max : 0);
+  return voe_map_prune_batch_dev(m, 1, K, d_uv, stride, d_app, stride, n_max, d_n, d_T16, p, d_entry_out, d_status_out, d_sq_out, d_app_out,
+                                 d_landmark_out, d_frame_out, d_stats);
+}
+
+int voe_map_prune(vo_map* m, int n_frames, const float K[9], const float* uv, const float* app, const int* n_rows, int n_max, const float* T16,
+                  const voe_map_prune_params* p, int32_t* entry_out, int32_t* status_out, double* sq_out, float* app_out,
+                  voe_map_prune_landmark* landmark_out, voe_map_prune_frame* frame_out, voe_map_prune_stats* stats_out) {
+  const char* fn = "voe_map_prune";
+  if (!(K && T16)) return vo_fail(VO_ERR_INVALID_ARG, "%s: null argument", fn);
+  if (!p || !entry_out) return vo_fail(VO_ERR_INVALID_ARG, "%s: null params or entry_out", fn);
+  VO_MAP_LIVE(m);
+  vo_ctx* c = m->ctx;
+  VO_NOT_CAPTURING(c);
+  MapFrames f;
+  int size = 0;
+  if (int r = upload_window(fn, m, MapFrames{n_frames, K, uv, 0, app, 0, n_max, n_rows}, T16, nullptr, &size, &f)) return r;
+  // one block of outputs: entries and statuses [rows] ints each, |e|^2 [rows] doubles, the landmarks' and the frames' records,
+  // the statistics.  The rows that go out are written in place over the staged rows (d_app_out == d_app).
+  const size_t F = (size_t)n_frames, rows = F * (size_t)n_max, S = (size_t)(size > 0 ? size : 1);
+  const size_t col = up256(4 * rows), o_sq = 2 * col, o_lm = o_sq + up256(8 * rows), o_fr = o_lm + up256(sizeof(voe_map_prune_landmark) * S),
+               o_stats = o_fr + up256(sizeof(voe_map_prune_frame) * F), total = o_stats + 256;
+  VO_HIP_CHECK(c->out[0].ensure(total, c->stream));
+  char* d = c->out[0].as<char>();
+  if (int r = voe_map_prune_batch_dev(m, n_frames, K, f.d_uv, f.uv_stride, f.d_app, f.app_stride, n_max, f.d_n, c->in[2].as<float>(), p,
+                                      reinterpret_cast<int32_t*>(d), status_out ? reinterpret_cast<int32_t*>(d + col) : nullptr,
+                                      sq_out ? reinterpret_cast<double*>(d + o_sq) : nullptr, app_out && rows > 0 ? c->in[1].as<float>() : nullptr,
+                                      landmark_out ? reinterpret_cast<voe_map_prune_landmark*>(d + o_lm) : nullptr,
+                                      frame_out ? reinterpret_cast<voe_map_prune_frame*>(d + o_fr) : nullptr,
+                                      reinterpret_cast<voe_map_prune_stats*>(d + o_stats)))
+    return r;
+  if (rows > 0) {
+    VO_HIP_CHECK(hipMemcpyAsync(entry_out, d, 4 * rows, hipMemcpyDeviceToHost, c->stream));
+    if (status_out) VO_HIP_CHECK(hipMemcpyAsync(status_out, d + col, 4 * rows, hipMemcpyDeviceToHost, c->stream));
+    if (sq_out) VO_HIP_CHECK(hipMemcpyAsync(sq_out, d + o_sq, 8 * rows, hipMemcpyDeviceToHost, c->stream));
+    if (app_out) VO_HIP_CHECK(hipMemcpyAsync(app_out, c->in[1].p, sizeof(float) * 10 * rows, hipMemcpyDeviceToHost, c->stream));
+  }
+  if (landmark_out && size > 0)
+    VO_HIP_CHECK(hipMemcpyAsync(landmark_out, d + o_lm, sizeof(voe_map_prune_landmark) * (size_t)size, hipMemcpyDeviceToHost, c->stream));
+  if (frame_out) VO_HIP_CHECK(hipMemcpyAsync(frame_out, d + o_fr, sizeof(voe_map_prune_frame) * F, hipMemcpyDeviceToHost, c->stream));
+  if (stats_out) VO_HIP_CHECK(hipMemcpyAsync(stats_out, d + o_stats, sizeof(voe_map_prune_stats), hipMemcpyDeviceToHost, c->stream));
   VO_HIP_CHECK(hipStreamSynchronize(c->stream));
   return VO_OK;
 }

@@ -347,6 +347,39 @@ static inline int map_keyframes_check(const char* fn, int n_frames, int n_words,
   return VO_OK;
 }
 
+// voe_map_prune*: what the call refuses (include/vo_hip.h, PRUNE), in the order they fire.  1 and 2 are the cull's refusals:
+//   1. a null K, d_T16 or d_stats      2. the frames' (map_frames_check)      3. a null params or d_entry_out
+//   4. max_err_px, then rel_factor, then rel_floor_px negative or not finite      5. rel_min_obs < 3
+//   6. max_share_landmark, then max_share_frame, outside 0 .. 1000      7. unique outside 0 / 1      8. reserved != 0
+//   9. an int32 output off a 4-byte boundary; d_sq_out, d_app_out, d_landmark_out or d_frame_out off an 8-byte one
+//   10. d_app_out overlapping d_app without being d_app
+// All tests off (max_err_px == 0, rel_factor == 0, unique == 0) is NOT refused: rule 3 still runs.
+struct MapPrunePtrs {
+  const void *T16, *entry, *status, *sq, *app_out, *landmark, *frame, *stats;
+};
+static inline int map_prune_check(const char* fn, const MapFrames& f, const voe_map_prune_params* p, const MapPrunePtrs& d) {
+  if (!(f.K && d.T16 && d.stats)) return vo_fail(VO_ERR_INVALID_ARG, "%s: null argument", fn);
+  if (int r = map_frames_check(fn, f, d.stats)) return r;
+  if (!p || !d.entry) return vo_fail(VO_ERR_INVALID_ARG, "%s: null params or d_entry_out", fn);
+  if (!(p->max_err_px >= 0.f && p->max_err_px <= 3.402823466e38f)) return vo_fail(VO_ERR_INVALID_ARG, "%s: max_err_px must be finite and not negative", fn);
+  if (!(p->rel_factor >= 0.f && p->rel_factor <= 3.402823466e38f)) return vo_fail(VO_ERR_INVALID_ARG, "%s: rel_factor must be finite and not negative", fn);
+  if (!(p->rel_floor_px >= 0.f && p->rel_floor_px <= 3.402823466e38f)) return vo_fail(VO_ERR_INVALID_ARG, "%s: rel_floor_px must be finite and not negative", fn);
+  if (p->rel_min_obs < 3) return vo_fail(VO_ERR_INVALID_ARG, "%s: rel_min_obs must be at least 3", fn);
+  if (p->max_share_landmark < 0 || p->max_share_landmark > 1000) return vo_fail(VO_ERR_INVALID_ARG, "%s: max_share_landmark %d outside 0 .. 1000", fn, p->max_share_landmark);
+  if (p->max_share_frame < 0 || p->max_share_frame > 1000) return vo_fail(VO_ERR_INVALID_ARG, "%s: max_share_frame %d outside 0 .. 1000", fn, p->max_share_frame);
+  if (p->unique != 0 && p->unique != 1) return vo_fail(VO_ERR_INVALID_ARG, "%s: unique must be 0 or 1", fn);
+  if (p->reserved != 0) return vo_fail(VO_ERR_INVALID_ARG, "%s: reserved must be 0", fn);
+  if ((reinterpret_cast<uintptr_t>(d.entry) | reinterpret_cast<uintptr_t>(d.status)) & 3u)
+    return vo_fail(VO_ERR_INVALID_ARG, "%s: int32 arrays must be 4-byte aligned", fn);
+  if (!aligned8(d.sq, d.app_out, d.landmark, d.frame)) return vo_fail(VO_ERR_INVALID_ARG, "%s: d_sq_out, d_app_out, d_landmark_out and d_frame_out must be 8-byte aligned", fn);
+  if (d.app_out && d.app_out != (const void*)f.d_app && f.n_max > 0) {
+    const uintptr_t span = sizeof(float) * 10 * ((uintptr_t)(f.n_frames - 1) * f.app_stride + (uintptr_t)f.n_max);
+    const uintptr_t a = reinterpret_cast<uintptr_t>(f.d_app), b = reinterpret_cast<uintptr_t>(d.app_out);
+    if (a < b + span && b < a + span) return vo_fail(VO_ERR_INVALID_ARG, "%s: d_app_out overlaps d_app without being d_app", fn);
+  }
+  return VO_OK;
+}
+
 // A workspace that would have to grow inside a graph capture: growing frees, allocates and waits.  `ws` lists the buffers the
 // call sizes, each with its capacity and what the call needs; `tail` (printf form) names the call that sizes them outside a
 // capture.  The callers ask BEFORE they enqueue anything: a HIP call refused later would invalidate the capture.

@@ -1250,4 +1250,34 @@ struct MapKeyframesArgs {
 // The steps behind the device's done flag return at once.
 __attribute__((visibility("hidden"))) hipError_t launch_map_keyframes(hipStream_t st, const MapKeyframesArgs& a);
 
+// ---- single observations pruned, with a guard per landmark and per frame (map_prune.hip, voe_map_prune*; vo_hip.h holds the
+// rules, prune_rules.h the integer decisions).  The lookup's entries and the ordered lists live in the refinement's workspace. ----
+struct MapPruneWs {
+  double* sq_list;                      // [n_frames * n_max] |e|^2 in LIST order, for the lists of more than 16 observations
+  int* st_list;                         // [n_frames * n_max] the status so far, in list order, for the same lists
+  int* row_st;                          // [n_frames][n_max] the status before rule 8 at every position that is an observation
+  int* fpart;                           // [n_frames][nb][4] observations, eligible and soft ones of a workgroup's 256 rows
+  int* cpart;                           // [n_frames][nb][16] the census of a finishing workgroup: ten status counts, observations, pruned, frame named
+  size_t bytes;
+};
+__attribute__((visibility("hidden"))) int map_prune_blocks(int n_max);      // nb: workgroups per frame of the two frame kernels
+__attribute__((visibility("hidden"))) MapPruneWs map_prune_layout(void* base, int n_frames, int n_max);
+struct MapPruneArgs {
+  MapRefineWs l;                        // the lookup's entries and the ordered lists (map_refine_layout)
+  MapPruneWs w;
+  MapView v;
+  const float* app; size_t app_stride;  // the frames' appearance rows, app_stride rows between frames
+  const int* d_n;                       // [n_frames] or null
+  int nb;
+  double max_sq, rf2, floor2;           // max_err_px^2 (0: off), rel_factor^2, rel_floor_px^2, each widened before it is squared
+  int rel_on, rel_min_obs, unique, share_landmark, share_frame;
+  int32_t *entry_out, *status_out;      // [n_frames][n_max]; status_out or null
+  double* sq_out;                       // [n_frames][n_max] or null
+  float* app_out;                       // laid out like app, or null; may be app itself
+  void *landmark_out, *frame_out;       // [size] voe_map_prune_landmark, [n_frames] voe_map_prune_frame, or null
+  int* stats;                           // voe_map_prune_stats: sixteen 4-byte words
+};
+// after the lookup has filled l.ent: a memset of the statistics, the lists, the landmark kernel, the frame counts, the finish, the statistics
+__attribute__((visibility("hidden"))) hipError_t launch_map_prune(hipStream_t st, const MapPruneArgs& a, int n_cu);
+
 }  // namespace vo
