@@ -76,6 +76,10 @@ class PICPSolver {
   //! reference-order arithmetic: bit-identical to the reference's float32 loop (extension, off by default)
   void setExact(bool on) { check(vo_picp_set_exact(h_, on ? 1 : 0), "PICPSolver::setExact"); exact_ = on; }
   bool exact() const { return exact_; }
+  //! multi-round solves of this handle replayed from a captured graph / submitted as plain launches (voe_picp_submit_info)
+  void submitInfo(unsigned long long& graph_solves, unsigned long long& plain_solves) const {
+    check(voe_picp_submit_info(h_, &graph_solves, &plain_solves), "PICPSolver::submitInfo");
+  }
   vo_picp* handle() const { return h_; }
 
  protected:

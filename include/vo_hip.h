@@ -175,6 +175,14 @@ int vo_picp_rounds(vo_picp *s, int keep_outliers, int n_iters);
  * many captures failed.  A failed capture does not fail the solve -- the same kernels run as plain launches -- but it is
  * reported once through vo_last_error() and counted here instead of passing unnoticed. */
 int vo_picp_graph_info(vo_picp *s, int *use_graph, int *n_graphs, int *n_failures);
+/* How the multi-round solves of a handle were submitted since it was made (either pointer may be NULL): replayed from a
+ * captured hipGraph behind a plain launch of round 0, or as plain launches throughout.  A handle submits plainly the solves
+ * that take a tail form at an M it has learned (every launch of such a solve is a real round, and plain launches leave no
+ * gap between two solves that a replayed graph leaves), under VO_PICP_TAIL_SUBMIT=plain, and wherever it has no graph
+ * (VO_PICP_GRAPH=0, a failed capture).  Solves of fewer than two rounds, solves in reference-order arithmetic and solves
+ * captured into a caller's graph are counted in neither.  Results are the same bytes in both forms.  (voe_: like every
+ * entry point added since the set of vo_* names was closed.) */
+int voe_picp_submit_info(vo_picp *s, unsigned long long *graph_solves, unsigned long long *plain_solves);
 /* Reference-order arithmetic (off by default).  on != 0: every later round of this handle is computed
  * with the reference's own rounding -- per-correspondence terms unfused, (J0r*J0c + J1r*J1c)*lambda,
  * H / b / chi summed sequentially in correspondence order (picp_solver.cpp:62-95), Eigen's pivoted

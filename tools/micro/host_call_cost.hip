@@ -58,6 +58,16 @@ int main(int argc, char** argv) {
     auto t2 = clk::now();
     if (w) std::printf("{\"pairs\": %zu, \"memcmp_us\": %.3f, \"bytes_equal_us\": %.3f, ", pairs, us(t0, t1) / reps, us(t1, t2) / reps);
   }
+  {
+    // the switches an enqueue of a tail-form solve reads per call (capi.hip: picp_enqueue, picp_tail_policy), all unset
+    const char* names[] = {"VO_PICP_CYCLE", "VO_PICP_TAIL", "VO_PICP_TAIL_FROM", "VO_PICP_TAIL_EARLY", "VO_PICP_TAIL_SUBMIT", "VO_PICP_TAIL_RING", "VO_PICP_TAIL_LOG"};
+    const int n = 100000;
+    auto t0 = clk::now();
+    for (int r = 0; r < n; ++r)
+      for (const char* nm : names) { sink = sink + (getenv(nm) != nullptr); asm volatile("" ::: "memory"); }
+    auto t1 = clk::now();
+    std::printf("\"seven_getenv_us\": %.3f, ", us(t0, t1) / n);
+  }
   hipStream_t st;
   if (hipStreamCreateWithFlags(&st, hipStreamNonBlocking) != hipSuccess) { std::printf("\"launch_us\": null}\n"); return 1; }
   float* d = nullptr;

@@ -268,6 +268,13 @@ class PICPSolver:
         _chk(self.lib.vo_picp_graph_info(self.h, C.byref(u), C.byref(n), C.byref(f)))
         return u.value, n.value, f.value
 
+    def submitInfo(self):
+        """(multi-round solves of this handle replayed from a captured graph, ... submitted as plain launches):
+        voe_picp_submit_info"""
+        g, p = C.c_ulonglong(), C.c_ulonglong()
+        _chk(self.lib.voe_picp_submit_info(self.h, C.byref(g), C.byref(p)))
+        return g.value, p.value
+
     def chainInfo(self):
         """(rounds whose finishing launch is still to come, oneRound calls enqueued ahead of their comparison, how many
         of those were repeated): vo_picp_chain_info"""

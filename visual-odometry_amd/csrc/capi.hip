@@ -133,6 +133,8 @@ struct vo_picp {
   int tail_seen[2] = {0, 0};  // the report as last looked at
   int tail_m = PICP_TAIL_FROM;   // the M of the handle's solves in the form: lowered to where its solves repeat, never for a probe
   unsigned long long solves = 0; // solves enqueued (VO_PICP_TAIL_LOG's line says at which of them a graph was captured)
+  unsigned long long graph_solves = 0, plain_solves = 0;   // multi-round solves replayed from a graph / submitted plainly: voe_picp_submit_info
+  bool plain_logged = false;  // VO_PICP_TAIL_LOG's line for the handle's first tail-form solve submitted plainly has been printed
   bool tail_on = false;       // eligible solves take the form
   bool tail_probe = false;    // one solve in the form is in flight to find out; launches per round until it reports
   int tail_period = PICP_TAIL_PROBE_EVERY, tail_since = PICP_TAIL_PROBE_EVERY - 1;   // off: every tail_period-th eligible solve probes
@@ -621,12 +623,30 @@ static bool picp_cycle_enabled() { const char* e = getenv("VO_PICP_CYCLE"); retu
 // back to PICP_TAIL_FROM, the run starts again.  Without a margin a miss is likelier, so the tier asks for
 // PICP_TAIL_EARLY_LEARN witnesses.  An early close counts as a skip-path launch in the report.  VO_PICP_TAIL_EARLY=0 keeps the
 // host from choosing the form, VO_PICP_TAIL_EARLY=1 adds it to a forced M (read per call; *early is part of the graph's key).
-static int picp_tail_policy(vo_picp* s, int n_iters, bool cycle, bool* early) {
+//
+// How the solve is submitted (*plain: plain launches throughout, no graph).  A replayed graph costs the device time around
+// it that plain launches of the same kernels do not: at 50 000 pairs the headline step is 47.6 us behind round 0 + graph and
+// 41.7 us as eleven plain launches (medians of five, alternating; ranges 47.5-48.2 against 40.6-42.3), the learned ring form
+// at M = 12 55.4 against 52.5 (55.0-55.9 against 49.1-52.7); eleven do-nothing kernels of a round's length take 53.7 us per
+// step behind a graph and 50.3 us plainly (tools/micro/step_gap): profiles/step_gap.json, DESIGN.md section 8 "Between two
+// steps".  The price is host time: eleven plain launches take the host 31 us where round 0 and a graph launch of ten kernels
+// take 9, so a plain solve stays ahead of the device only while its launches are real rounds (3.45 us each; an empty kernel
+// takes the device 2.2 us, less than the 2.8 us the host needs to launch it).  That is what a learned M
+// says of a handle -- its witnesses found every launch up to M at work --, so the early tier and the learned ring tier
+// (tail_m < PICP_TAIL_FROM) go plain; probes, skip-path solves at the default M (whose launches 12 .. 16 return in 1.72 us,
+// faster than the host issues them) and every solve without a tail form keep the graph, and so does a forced M, so that a
+// test of the forms runs the path it ran.  VO_PICP_TAIL_SUBMIT=graph|plain (read per call) forces the form for every
+// tail-form solve, a forced M included.  Same kernels, same arguments, same bytes either way.
+static int picp_tail_submit_env() { const char* e = getenv("VO_PICP_TAIL_SUBMIT"); return !e ? -1 : (e[0] == 'p' ? 1 : (e[0] == 'g' ? 0 : -1)); }
+
+static int picp_tail_policy(vo_picp* s, int n_iters, bool cycle, bool* early, bool* plain) {
   bool forced = false;
   *early = false;
+  *plain = false;
   const int early_env = picp_tail_early_env();
+  const int submit_env = picp_tail_submit_env();
   const int m = picp_tail_from(s->grid, n_iters, cycle, s->ctx->n_cu, &forced);
-  if (forced) { *early = m > 0 && early_env == 1; return m; }
+  if (forced) { *early = m > 0 && early_env == 1; *plain = m > 0 && submit_env == 1; return m; }
   // (not eligible at the default M and the form not on: no M this handle may choose would make it eligible -- nothing to look at)
   if (m == 0 && !s->tail_on) return 0;
   if (!cycle || s->ctx->capturing || !s->tail_report) return 0;
@@ -662,15 +682,18 @@ static int picp_tail_policy(vo_picp* s, int n_iters, bool cycle, bool* early) {
       if (run >= PICP_TAIL_LEARN && det >= 1) s->tail_m = det + 1 < PICP_TAIL_FROM ? det + 1 : PICP_TAIL_FROM;
       if (early_env != 0 && run >= PICP_TAIL_EARLY_LEARN && det >= 3) {
         const int me = picp_tail_from(s->grid, n_iters, cycle, s->ctx->n_cu, nullptr, det - 2 < PICP_TAIL_FROM ? det - 2 : PICP_TAIL_FROM);
-        if (me > 0) { *early = true; return me; }
+        if (me > 0) { *early = true; *plain = submit_env != 0; return me; }
       }
     }
-    return picp_tail_from(s->grid, n_iters, cycle, s->ctx->n_cu, nullptr, s->tail_m);
+    const int ml = picp_tail_from(s->grid, n_iters, cycle, s->ctx->n_cu, nullptr, s->tail_m);
+    *plain = ml > 0 && (s->tail_m < PICP_TAIL_FROM ? submit_env != 0 : submit_env == 1);
+    return ml;
   }
   if (s->tail_probe || m == 0) return 0;
   if (++s->tail_since < s->tail_period) return 0;
   s->tail_since = 0;
   s->tail_probe = true;
+  *plain = submit_env == 1;
   return m;
 }
 
@@ -806,12 +829,12 @@ static int picp_enqueue(vo_picp* s, int n_iters, bool lazy = false) {
     return VO_OK;
   }
   // rounds behind this index share one launch (0: every round has its own); part of the graph's key
-  bool tail_early = false;
-  const int tail_from = picp_tail_policy(s, n_iters, cycle, &tail_early);
+  bool tail_early = false, tail_plain = false;
+  const int tail_from = picp_tail_policy(s, n_iters, cycle, &tail_early, &tail_plain);
   // (VO_PICP_TAIL_RING=0, read per call: the tail launch recomputes the last round's rows where the ring holds them)
   const bool tail_ring = tail_from == 0 || picp_tail_ring_enabled();
   ++s->solves;
-  if (s->use_graph && n_iters >= 2 && !c->capturing) {
+  if (s->use_graph && n_iters >= 2 && !c->capturing && !tail_plain) {
     // Where the rounds are launches of their own, round 0 -- whose arguments (what it gathers from, or that it does not) are
     // the caller's and change from call to call -- is a plain launch, and the graph holds what follows it: one graph per
     // solve shape, whatever it is replayed behind.  (Round 0 as the graph's first node measured the same: DESIGN.md section 8.)
@@ -861,14 +884,24 @@ static int picp_enqueue(vo_picp* s, int n_iters, bool lazy = false) {
       if (e == hipSuccess) e = hipGraphLaunch(it->second, c->stream);
       if (e != hipSuccess && gather.on) s->packed_valid = false;
       VO_HIP_CHECK(e);
+      ++s->graph_solves;
       return VO_OK;
     }
   }
   {
+    // plain launches throughout: a tail-form solve the policy submits so (no graph is captured or looked up for it), a handle
+    // without the graph, a single round, a caller's capture
+    if (tail_plain && !s->plain_logged) {
+      s->plain_logged = true;
+      if (const char* lg = getenv("VO_PICP_TAIL_LOG")) if (lg[0] == '1')
+        fprintf(stderr, "vo_picp: solve %llu of the handle is its first submitted as plain launches: %d rounds, tail_from %d%s\n", s->solves,
+                n_iters, tail_from, tail_early ? " (early form)" : "");
+    }
     const hipError_t e = launch_picp_rounds(c->stream, s->d_params, s->d_state, pk, partials, s->grid, n_iters, pinhole, keep, gather,
                                             PICP_WHOLE, cycle, tail_from, s->tail_report, tail_ring, tail_early);
     if (e != hipSuccess && gather.on) s->packed_valid = false;
     VO_HIP_CHECK(e);
+    if (n_iters >= 2 && !c->capturing) ++s->plain_solves;
   }
   return VO_OK;
 }
@@ -987,6 +1020,13 @@ int vo_picp_graph_info(vo_picp* s, int* use_graph, int* n_graphs, int* n_failure
   if (use_graph) *use_graph = s->use_graph;
   if (n_graphs) *n_graphs = (int)s->graphs.size();
   if (n_failures) *n_failures = s->graph_failures;
+  return VO_OK;
+}
+
+int voe_picp_submit_info(vo_picp* s, unsigned long long* graph_solves, unsigned long long* plain_solves) {
+  VO_REQUIRE(s, "null argument");
+  if (graph_solves) *graph_solves = s->graph_solves;
+  if (plain_solves) *plain_solves = s->plain_solves;
   return VO_OK;
 }
 
